@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """bench.py — the headline measurement of the hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2|C3|C4|C4tile|C5] [--mesh file.ply|.obj]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2|C3|C4|C4tile|C5] [--mesh file.ply|.obj] [--full]
+                    [--dump-outputs DIR]
 
 Metric (BASELINE.json): Mrays/s (primary + 1-bounce) at 1920x1080 on the 1M-triangle mesh; BVH build ms.
 Default workload = config C3 of SURVEY.md §8(d): Plane(1000,500) (exactly 1 000 000 triangles), fp32, objrender camera.
@@ -17,9 +18,12 @@ under a launcher already, and fails loudly when the box has fewer than N GPUs.  
 are gathered to rank 0 (RCCL gather = grouped send/recv over xGMI), asynchronously and double-buffered.  C2/C3/C5 scale weakly
 (the image grows to W x (H*N)); `--config C4` is BASELINE.json's strong-scaling case.
 
-Output: ONE JSON line on stdout, kept small (benchlib/line.py: the contract's keys + `roofline` + `cpu_baseline` + a few figures of
-merit, a few KB) — and everything else the run measured (other configs, SURVEY 8(f) rows, per-wave parity blocks, counter
-detail) in the side file the line names (`extras_file`, default gpurun_out/bench_extras.json).  Progress notes go to stderr.
+Output: ONE JSON line on stdout, kept small (benchlib/line.py).  A plain run measures the headline figure only: set-up, warm-up,
+the K timed steps, the line (the contract's keys, `config`, `build_ms`, `bvh`).  `--full` adds everything else, as one run:
+`roofline` (counter sub-runs), `cpu_baseline`, the other configs, the strong-scaling C4 case (N > 1), the untimed extras and
+the SURVEY 8(f) rows, with a few figures of merit in the line and the whole result object in the side file the line names
+(`extras_file`); the --no-* options drop parts of a --full run.  `--dump-outputs DIR` writes the hit records and flags of the
+last timed step as float .npy files (benchlib/outputs.py).  Progress notes go to stderr.
 
   roofline      the dominant kernel (named by the library: nrtLastKernelName).  `bound` = the unit this run's counters show
                 closest to its peak (hbm / l1 / valu), with achieved / peak / frac of THAT unit; `hbm` = the contract's HBM figure
@@ -83,6 +87,11 @@ def main():
     ap.add_argument("--config", default=None, choices=sorted(CONFIGS),
                     help="default: C3 (the config BASELINE.json's metric is quoted on; with --gpus N > 1 also its strong-scaling case C4 as `strong_c4`)")
     ap.add_argument("--mesh", default=None, help="C2: a .ply / .obj triangle mesh (e.g. Stanford bun_zipper.ply) instead of the procedural stand-in")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure: roofline (rocprofv3 counter sub-runs), CPU baseline, the other "
+                         "configs, the strong-scaling C4 case (N > 1), the untimed extras and the SURVEY 8(f) rows (the --no-* options drop parts)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the hit records and hit flags of the last step as float .npy files into DIR")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--builds", type=int, default=5)
     ap.add_argument("--no-extras", action="store_true",
@@ -113,6 +122,10 @@ def main():
         args.config = "C3"
     if args.mesh and args.config != "C2":
         raise SystemExit("--mesh applies to --config C2")
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
+    if args.dump_outputs and args.gather == "cabi":
+        raise SystemExit("--dump-outputs: not with --gather cabi (its records land in the group's own buffers)")
 
     if args.pmc_child:
         return pmc_child(args)
@@ -169,9 +182,11 @@ def main():
     accel, n1, n2 = wl.accel, wl.n1, wl.n2
     HIT = wl.HIT
 
-    # ---- work counters -> algorithmic bytes per launch ---------------------------
-    c1, c2 = wl.counters()
-    bytes1, bytes2 = algorithmic_bytes(c1, wl.rb), algorithmic_bytes(c2, wl.rb)
+    full = args.full
+    if full:
+        # ---- work counters -> algorithmic bytes per launch ---------------------------
+        c1, c2 = wl.counters()
+        bytes1, bytes2 = algorithmic_bytes(c1, wl.rb), algorithmic_bytes(c2, wl.rb)
 
     if args.gather == "cabi" and dist is not None and not shared:
         from benchlib.timed import TimedCAbi
@@ -183,13 +198,18 @@ def main():
     launch_ms = region_ms / (2 * args.steps)
     if rank == 0:
         note("%s: %.1f Mrays/s, %.4f ms per step (%d steps), launch %.4f ms" % (args.config, T.value, T.ms_per_step, args.steps, launch_ms))
-    if world > 1:
+        if args.dump_outputs:
+            from benchlib.outputs import dump_outputs
+
+            written = dump_outputs(args.dump_outputs, wl, T.last_outputs)
+            note("outputs of the last timed step: %d arrays in %s" % (len(written), args.dump_outputs))
+    if full and world > 1:
         t = torch.tensor([float(bytes1 + bytes2)], dtype=torch.float64, device=comm_dev)
         allt = [torch.empty_like(t) for _ in range(world)]
         dist.all_gather(allt, t)
         agg_bytes = float(torch.stack(allt).sum())
         agg_ms = T.per_rank["kernel_ms_max"]
-    else:
+    elif full:
         agg_bytes = float(bytes1 + bytes2)
         agg_ms = k_ms1 + k_ms2
 
@@ -197,7 +217,7 @@ def main():
     # the same number of interleaved rows); all ranks wait at the barrier below meanwhile ------------------------------------
     pmc_all, pmc_err = None, None
     counts, counts_err = None, None
-    other_configs = ["C2", "C4tile", "C5"] if (world == 1 and not args.no_configs and default_config) else []
+    other_configs = ["C2", "C4tile", "C5"] if (full and world == 1 and not args.no_configs and default_config) else []
     configs_out = {}
     if rank == 0 and other_configs:
         for name in other_configs:  # (before the counter passes: their own kernel times go into the fractions)
@@ -206,16 +226,14 @@ def main():
                 note("%s: %s Mrays/s, build %s ms" % (name, configs_out[name].get("value"), configs_out[name].get("build_ms")))
             except Exception as e:  # pragma: no cover
                 configs_out[name] = {"error": repr(e)}
-    if rank == 0 and not args.no_pmc:
+    if full and rank == 0 and not args.no_pmc:
         keep = args.pmc_dir and os.path.abspath(args.pmc_dir)
         pmc_all, pmc_err = pmc_collect([args.config] + [c for c in other_configs if "error" not in configs_out.get(c, {})],
                                        args.mesh, rank=0, world=world, keep_dir=keep)
         counts, counts_err = walk_counts(args.config, args.mesh, rank=0, world=world)
         note("counter passes done%s%s" % ("; " + pmc_err if pmc_err else "", "; walk counts: " + counts_err if counts_err else ""))
-    n_cus = torch.cuda.get_device_properties(local_rank).multi_processor_count
-
     strong = None
-    if world > 1 and default_config and not args.no_strong:
+    if full and world > 1 and default_config and not args.no_strong:
         # BASELINE.json's strong-scaling case beside the weak-scaled headline: every rank builds the 10M-triangle plane and
         # traces its 4096/N interleaved rows of the fixed 4096x4096 frame
         del wl.d_rays1, wl.d_rays2
@@ -229,27 +247,7 @@ def main():
         del wl4
 
     if rank == 0:
-        k_ms = {"primary": k_ms1, "bounce": k_ms2}
-        alg_gbs = agg_bytes / (agg_ms * 1e-3) / 1e9  # all ranks' algorithmic bytes over the slowest rank's two launches
         build_ms = float(np.median(wl.build_ms))
-        bbytes = build_bytes(wl.faces.shape[0], wl.num_nodes, wl.rb)
-        build_roof = {"bytes": int(bbytes), "ms": round(build_ms, 4), "GBs": round(bbytes / (build_ms * 1e-3) / 1e9, 1),
-                      "frac": round(bbytes / (build_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)}
-        counters = None
-        if pmc_all is not None and pmc_all.get(args.config, {}).get("primary"):
-            counters = roofline_from_counters(pmc_all[args.config], k_ms, n_cus, launch_ms=launch_ms)
-        comp, _tree_once = br.compulsory_bytes(wl, bytes1, bytes2)
-        roof = br.headline(kernel_name, launch_ms, k_ms, (bytes1 + bytes2) // 2, alg_gbs, comp, counters, br.requested_bytes(wl, counts), build_roof)
-        roof["detail"] = {"per_wave": per_wave_counts(wl, c1, c2, k_ms1, k_ms2), "counters": counters, "walk_counts": counts,
-                          "launch_ms_definition": "HIP events on the launch stream around the whole timed region / (2 x steps)"}
-        if pmc_err or counts_err:
-            roof["detail"]["errors"] = [e for e in (pmc_err, counts_err) if e]
-        hb = counters.get("hbm") if counters else None
-        if hb and world > 1:
-            # per-rank fractions: this rank's measured bytes per launch (the ranks' shares are equally many interleaved rows of the
-            # same frame) over every rank's own average launch of the timed region
-            fr = [hb["bytes_per_launch"] / (x * 1e-3) / 1e9 / HBM_PEAK_GBS for x in T.per_rank["launch_ms"]]
-            roof["per_rank_hbm_frac"] = {"max": round(max(fr), 4), "min": round(min(fr), 4)}
         cfg = wl.cfg
         par = "replicated BVH, interleaved image rows per GPU"
         if world > 1:
@@ -273,8 +271,30 @@ def main():
                        "untimed_clock_ramp_steps": int(T.prewarm_steps)},
             "build_ms": round(build_ms, 4),
             "bvh": {"nodes": wl.num_nodes, "max_depth": int(wl.stats["max_tree_depth"])},
-            "roofline": roof,
         }
+        if full:
+            n_cus = torch.cuda.get_device_properties(local_rank).multi_processor_count
+            k_ms = {"primary": k_ms1, "bounce": k_ms2}
+            alg_gbs = agg_bytes / (agg_ms * 1e-3) / 1e9  # all ranks' algorithmic bytes over the slowest rank's two launches
+            bbytes = build_bytes(wl.faces.shape[0], wl.num_nodes, wl.rb)
+            build_roof = {"bytes": int(bbytes), "ms": round(build_ms, 4), "GBs": round(bbytes / (build_ms * 1e-3) / 1e9, 1),
+                          "frac": round(bbytes / (build_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)}
+            counters = None
+            if pmc_all is not None and pmc_all.get(args.config, {}).get("primary"):
+                counters = roofline_from_counters(pmc_all[args.config], k_ms, n_cus, launch_ms=launch_ms)
+            comp, _tree_once = br.compulsory_bytes(wl, bytes1, bytes2)
+            roof = br.headline(kernel_name, launch_ms, k_ms, (bytes1 + bytes2) // 2, alg_gbs, comp, counters, br.requested_bytes(wl, counts), build_roof)
+            roof["detail"] = {"per_wave": per_wave_counts(wl, c1, c2, k_ms1, k_ms2), "counters": counters, "walk_counts": counts,
+                              "launch_ms_definition": "HIP events on the launch stream around the whole timed region / (2 x steps)"}
+            if pmc_err or counts_err:
+                roof["detail"]["errors"] = [e for e in (pmc_err, counts_err) if e]
+            hb = counters.get("hbm") if counters else None
+            if hb and world > 1:
+                # per-rank fractions: this rank's measured bytes per launch (the ranks' shares are equally many interleaved rows of the
+                # same frame) over every rank's own average launch of the timed region
+                fr = [hb["bytes_per_launch"] / (x * 1e-3) / 1e9 / HBM_PEAK_GBS for x in T.per_rank["launch_ms"]]
+                roof["per_rank_hbm_frac"] = {"max": round(max(fr), 4), "min": round(min(fr), 4)}
+            out["roofline"] = roof
         if dist is not None:
             out["multi_gpu"] = dict(T.per_rank, rccl_ranks=world, backend="gloo (test hook)" if shared else ("RCCL through the C ABI (nrtGroup*)" if args.gather == "cabi" else "nccl (RCCL)"),
                                     gathered_bytes_per_step=T.gathered_bytes_per_step)
@@ -282,7 +302,7 @@ def main():
                 out["multi_gpu"]["gather_check"] = T.gather_check
             if strong is not None:
                 out["strong_c4"] = strong
-        if world == 1 and not args.no_extras:
+        if full and world == 1 and not args.no_extras:
             # extras, outside the timed region: (a) the same K steps with two frames in flight (steps alternate
             # between two streams; a launch's drain tail is filled by the next frame's rays), (b) SURVEY 8(d)'s
             # primary + shadow pair, (c) the host entry point end to end, (d) the application-visible Build()
@@ -304,7 +324,7 @@ def main():
             if bh:
                 out["build_host_ms"] = bh
             note("extras done")
-        if world == 1 and not args.no_cpu_baseline:
+        if full and world == 1 and not args.no_cpu_baseline:
             from benchlib.baseline import cpu_baseline, reference_order_results
 
             nodes, indices = accel.GetTree()
@@ -326,7 +346,7 @@ def main():
                 elif cnts:
                     e["roofline"] = {"waves": cnts, "note": "UNMEASURED (no counter pass in this run)"}
                 out["configs"][name] = e
-        if world == 1 and default_config and not args.no_next_rows and not args.no_extras:
+        if full and world == 1 and default_config and not args.no_next_rows and not args.no_extras:
             del wl
             torch.cuda.empty_cache()
             try:
@@ -335,7 +355,7 @@ def main():
                 out["next_rows"] = bench_rows.next_rows(counters=not args.no_pmc, pmc_dir=args.pmc_dir and os.path.abspath(args.pmc_dir))
             except Exception as e:  # pragma: no cover
                 out["next_rows"] = {"error": repr(e)}
-        extras_file = bl.write_extras(out, args.extras_file)
+        extras_file = bl.write_extras(out, args.extras_file) if (full or args.extras_file) else None
         sys.stderr.flush()
         print(json.dumps(bl.compact_line(out, extras_file)), flush=True)
     if dist is not None:

@@ -100,6 +100,8 @@ class Timed:
         if use_dist:
             dist.barrier()
         self.dt = time.perf_counter() - t0
+        last = (step_no[0] - 1) % nbuf
+        self.last_outputs = (hit_bufs1[last], wl.d_mask1, hit_bufs2[last], wl.d_mask2)  # what the last timed step wrote
         self.kernel_name = accel.LastKernelName()
         self.region_ms = float(region[0].elapsed_time(region[1]))  # HIP events on the launch stream over the timed region
         self.steps = steps
@@ -205,6 +207,7 @@ class TimedCAbi(Timed):
         if dist is not None:
             dist.barrier()
         self.dt = time.perf_counter() - t0
+        self.last_outputs = None  # (the records went to the group's frame / tile buffers: bench.py refuses --dump-outputs here)
         self.region_ms = self.dt * 1e3  # (the group launches on its own stream: the wall clock of the region stands in for the event pair)
         self.steps = steps
         self.rays_per_step = n1 + n2

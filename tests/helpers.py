@@ -1,7 +1,49 @@
-"""Shared test helpers (CPU side): tie-aware hit comparison, option builders."""
+"""Shared test helpers (CPU side): tie-aware hit comparison, option builders, recorded answers of the reference."""
+import hashlib
+import os
+
 import numpy as np
 
 from nanort_amd.wire import default_trace_options
+
+LIVE_REF_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "live_ref")
+
+
+def outputs_digest(*arrays, canonical_nan=False):
+    """sha256 over the arrays, field by field (the padding of fp64 records left out); equal digests = equal bits.  With
+    canonical_nan every NaN counts as the same NaN (np.array_equal(..., equal_nan=True) field by field)."""
+    d = hashlib.sha256()
+    for a in arrays:
+        for k in a.dtype.names or (None,):
+            x = np.ascontiguousarray(a if k is None else a[k])
+            if canonical_nan and x.dtype.kind == "f":
+                x = np.where(np.isnan(x), np.nan, x).astype(x.dtype)
+            d.update(x.tobytes())
+    return d.hexdigest()
+
+
+def reference_answers(case, live=None):
+    """The unmodified reference's answers for one case of a test against it: (nodes, indices, digest of its outputs).
+    Where the reference libraries are built (oracle/_ref), `live()` computes them and they must equal the record under
+    tests/golden/live_ref/ (RECORD_REFERENCE_ANSWERS=1 writes the record instead); elsewhere the record stands in for them."""
+    path = os.path.join(LIVE_REF_DIR, case + ".npz")
+    if live is None:
+        rec = np.load(path)
+        return (rec["nodes"] if rec["nodes"].size else None), (rec["indices"] if rec["indices"].size else None), str(rec["digest"])
+    nodes, indices, digest = live()
+    tree = None
+    if nodes is not None:
+        tree = nodes.copy()
+        tree["axis"][tree["flag"] == 1] = 0  # (the reference never writes a leaf's axis)
+    if os.environ.get("RECORD_REFERENCE_ANSWERS") == "1":
+        os.makedirs(LIVE_REF_DIR, exist_ok=True)
+        np.savez_compressed(path, nodes=tree if tree is not None else np.zeros(0), indices=indices if indices is not None else np.zeros(0),
+                            digest=np.array(digest))
+    rec = np.load(path)
+    assert str(rec["digest"]) == digest, "%s: the reference's outputs differ from the record" % case
+    if tree is not None:
+        assert rec["nodes"].tobytes() == tree.tobytes() and np.array_equal(rec["indices"], indices), "%s: tree differs from the record" % case
+    return nodes, indices, digest
 
 
 def trace_options(range_=None, skip=None, cull=None):

@@ -32,7 +32,7 @@ def _line_and_extras(r, extras_path):
 def test_two_ranks_share_one_gpu_through_the_self_spawn_path(tmp_path):
     # `python bench.py --gpus 2` with no launcher around it: bench.py starts the two ranks itself
     xp = str(tmp_path / "extras.json")
-    r = _run(["--gpus", "2", "--steps", "4", "--warmup", "1", "--builds", "1", "--no-cpu-baseline", "--extras-file", xp], {"NRT_BENCH_TEST_SHARED_GPU": "1"})
+    r = _run(["--gpus", "2", "--full", "--steps", "4", "--warmup", "1", "--builds", "1", "--no-cpu-baseline", "--extras-file", xp], {"NRT_BENCH_TEST_SHARED_GPU": "1"})
     assert r.returncode == 0, r.stdout[-4000:]
     out, full = _line_and_extras(r, xp)
     assert out["n_gpus"] == 2 and out["steps"] == 4 and out["scaling"] == "weak"
@@ -61,7 +61,7 @@ def test_two_ranks_share_one_gpu_through_the_self_spawn_path(tmp_path):
 @pytest.mark.gpu
 def test_strong_scaling_config_splits_a_fixed_frame(tmp_path):
     xp = str(tmp_path / "extras.json")
-    r = _run(["--gpus", "2", "--config", "C4", "--steps", "2", "--warmup", "1", "--builds", "1", "--no-cpu-baseline", "--extras-file", xp],
+    r = _run(["--gpus", "2", "--full", "--config", "C4", "--steps", "2", "--warmup", "1", "--builds", "1", "--no-cpu-baseline", "--extras-file", xp],
              {"NRT_BENCH_TEST_SHARED_GPU": "1"}, timeout=1500)
     assert r.returncode == 0, r.stdout[-4000:]
     out, full = _line_and_extras(r, xp)

@@ -1,11 +1,12 @@
 """SURVEY §8f row 4 (cylinders), CPU side: the C restatement of the cylinder primitive traced through Traverse
 (oracle/cylinder_oracle.c) against the golden fixture made from the unmodified reference example, and against the
-live reference where it was built (oracle/_ref/libcylinder_ref.so)."""
+live reference where it was built (oracle/_ref/libcylinder_ref.so; its recorded answers elsewhere)."""
 import os
 
 import numpy as np
 import pytest
 
+from helpers import outputs_digest, reference_answers
 from nanort_amd import scenes
 from oracle import bindings as ob
 import sphere_fixture
@@ -26,30 +27,35 @@ def test_restatement_matches_golden_fixture(golden_dir):
     assert np.allclose(np.linalg.norm(h["normal"][hit], axis=1), 1.0, atol=1e-5)
 
 
-@pytest.mark.skipif(not ob.have_cylinder_reference(), reason="oracle/_ref/libcylinder_ref.so not built")
+# Against the live reference where oracle/_ref is built, against its recorded answers (tests/golden/live_ref/) elsewhere.
 @pytest.mark.parametrize("n", [1, 2, 5, 64, 3000])
 def test_restatement_matches_live_reference(n):
-    R = ob.CylinderReference()
-    v, r = R.generate(n)
     mv, mr = scenes.random_cylinders(n)
-    assert v.tobytes() == mv.tobytes() and r.tobytes() == mr.tobytes()  # the harness's generator == the example's
-    nodes, idx, st = R.build(v, r)
     rays = sphere_fixture.rays()
-    for cap in (True, False):
-        h, m = R.traverse(rays, test_cap=cap)
-        oh, om = ob.CylinderOracle().traverse(nodes, idx, v, r, rays, test_cap=cap)
-        assert np.array_equal(m, om) and h.tobytes() == oh.tobytes()
+
+    def live():
+        R = ob.CylinderReference()
+        v, r = R.generate(n)
+        assert v.tobytes() == mv.tobytes() and r.tobytes() == mr.tobytes()  # the harness's generator == the example's
+        nodes, idx, st = R.build(v, r)
+        outs = [a for cap in (True, False) for a in R.traverse(rays, test_cap=cap)]
+        return nodes, idx, outputs_digest(*outs)
+
+    nodes, idx, digest = reference_answers("cylinders_%d" % n, live if ob.have_cylinder_reference() else None)
+    outs = [a for cap in (True, False) for a in ob.CylinderOracle().traverse(nodes, idx, mv, mr, rays, test_cap=cap)]
+    assert outputs_digest(*outs) == digest
 
 
-@pytest.mark.skipif(not ob.have_cylinder_reference(), reason="oracle/_ref/libcylinder_ref.so not built")
 def test_degenerate_cylinders_and_hostile_rays_match_live_reference():
     v, r = sphere_fixture.degenerate_cylinders()
     rays = sphere_fixture.hostile_rays()
-    R = ob.CylinderReference()
-    nodes, idx, _ = R.build(v, r)
-    for cap in (True, False):
-        h, m = R.traverse(rays, test_cap=cap)
-        oh, om = ob.CylinderOracle().traverse(nodes, idx, v, r, rays, test_cap=cap)
-        assert np.array_equal(m, om)
-        for f in ("t", "u", "v", "prim_id", "normal"):
-            assert np.array_equal(h[f], oh[f], equal_nan=True), f
+
+    def live():
+        R = ob.CylinderReference()
+        nodes, idx, _ = R.build(v, r)
+        outs = [a for cap in (True, False) for a in R.traverse(rays, test_cap=cap)]
+        return nodes, idx, outputs_digest(*outs, canonical_nan=True)
+
+    nodes, idx, digest = reference_answers("cylinders_degenerate", live if ob.have_cylinder_reference() else None)
+    outs = [a for cap in (True, False) for a in ob.CylinderOracle().traverse(nodes, idx, v, r, rays, test_cap=cap)]
+    assert outputs_digest(*outs, canonical_nan=True) == digest

@@ -2,7 +2,7 @@
 
 Against (a) the golden fixtures produced by running the UNMODIFIED reference
 (oracle/gen_golden.py -> tests/golden/), (b) the known answers of SURVEY.md §8c,
-and (c) the reference itself (oracle/_ref) when that prebuilt library is here.
+and (c) the reference itself (oracle/_ref) when that prebuilt library is here, its recorded answers elsewhere.
 """
 import hashlib
 import json
@@ -11,7 +11,7 @@ import os
 import numpy as np
 import pytest
 
-from helpers import assert_hits_identical, trace_options
+from helpers import assert_hits_identical, outputs_digest, reference_answers, trace_options
 from nanort_amd import scenes
 from nanort_amd.wire import RAY_F64, widen_rays
 from oracle import bindings as ob
@@ -176,7 +176,7 @@ def test_sphere_sample(oracle, golden_dir, ka):
     assert_hits_identical(s["hits"], s["mask"], h, m)
 
 
-@pytest.mark.skipif(not ob.reference_available(), reason="oracle/_ref not built (needs /root/reference)")
+# Against the live reference where oracle/_ref is built, against its recorded answers (tests/golden/live_ref/) elsewhere.
 @pytest.mark.parametrize("real", [np.float32, np.float64])
 def test_oracle_equals_live_reference_on_random_soup(oracle, real):
     """Random triangle soup + random rays (incl. axis-aligned, zero components, strided vertices)."""
@@ -186,11 +186,6 @@ def test_oracle_equals_live_reference_on_random_soup(oracle, real):
     vbuf = rng.uniform(-1, 1, size=(nv, stride_elems)).astype(real)
     faces = rng.integers(0, nv, size=(nf, 3), dtype=np.uint32)
     stride = stride_elems * vbuf.dtype.itemsize
-    R = ob.Reference(vbuf, faces, stride=stride)
-    ok, st = R.build(parallel=False)
-    rn, ri = R.tree()
-    nodes, idx, ost = oracle.build(vbuf, faces, stride=stride)
-    assert masked(nodes).tobytes() == masked(rn).tobytes() and np.array_equal(idx, ri)
     from nanort_amd.wire import ray_dtype
     n = 4000
     rays = np.zeros((n,), dtype=ray_dtype(real))
@@ -203,7 +198,23 @@ def test_oracle_equals_live_reference_on_random_soup(oracle, real):
     rays["dir"] = d
     rays["min_t"] = 0.0
     rays["max_t"] = rng.choice([1e30, 0.7, 2.0], size=n)
-    for opts in (None, trace_options(cull=True), trace_options(skip=17, range_=(5, 2000))):
-        rh, rm, _ = R.traverse(rays, opts)
+    all_opts = (None, trace_options(cull=True), trace_options(skip=17, range_=(5, 2000)))
+
+    def live():
+        R = ob.Reference(vbuf, faces, stride=stride)
+        ok, st = R.build(parallel=False)
+        rn, ri = R.tree()
+        outs = []
+        for opts in all_opts:
+            rh, rm, _ = R.traverse(rays, opts)
+            outs += [rh, rm]
+        return rn, ri, outputs_digest(*outs)
+
+    rn, ri, digest = reference_answers("soup_%s" % np.dtype(real).name, live if ob.reference_available() else None)
+    nodes, idx, ost = oracle.build(vbuf, faces, stride=stride)
+    assert masked(nodes).tobytes() == masked(rn).tobytes() and np.array_equal(idx, ri)
+    outs = []
+    for opts in all_opts:
         h, m = oracle.traverse(nodes, idx, vbuf, faces, rays, opts, stride=stride)
-        assert_hits_identical(rh, rm, h, m)
+        outs += [h, m]
+    assert outputs_digest(*outs) == digest
