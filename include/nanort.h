@@ -987,6 +987,12 @@ struct HipApi<float> {
   static nrt_status OccludedDevice(nrt_ctx *c, const RayPod *r, uint64_t n, const nrt_trace_options *o, uint8_t *m, void *s) {
     return nrtOccludedBatchDevice_f32(c, r, n, o, m, s);
   }
+  static nrt_status MultiHit(nrt_ctx *c, const RayPod *r, uint64_t n, uint32_t k, const nrt_trace_options *o, HitPod *h, uint32_t *cnt) {
+    return nrtMultiHitTraverseBatch_f32(c, r, n, k, o, h, cnt);
+  }
+  static nrt_status MultiHitDevice(nrt_ctx *c, const RayPod *r, uint64_t n, uint32_t k, const nrt_trace_options *o, HitPod *h, uint32_t *cnt, void *s) {
+    return nrtMultiHitTraverseBatchDevice_f32(c, r, n, k, o, h, cnt, s);
+  }
 };
 template <>
 struct HipApi<double> {
@@ -1019,6 +1025,12 @@ struct HipApi<double> {
   static nrt_status Occluded(nrt_ctx *c, const RayPod *r, uint64_t n, const nrt_trace_options *o, uint8_t *m) { return nrtOccludedBatch_f64(c, r, n, o, m); }
   static nrt_status OccludedDevice(nrt_ctx *c, const RayPod *r, uint64_t n, const nrt_trace_options *o, uint8_t *m, void *s) {
     return nrtOccludedBatchDevice_f64(c, r, n, o, m, s);
+  }
+  static nrt_status MultiHit(nrt_ctx *c, const RayPod *r, uint64_t n, uint32_t k, const nrt_trace_options *o, HitPod *h, uint32_t *cnt) {
+    return nrtMultiHitTraverseBatch_f64(c, r, n, k, o, h, cnt);
+  }
+  static nrt_status MultiHitDevice(nrt_ctx *c, const RayPod *r, uint64_t n, uint32_t k, const nrt_trace_options *o, HitPod *h, uint32_t *cnt, void *s) {
+    return nrtMultiHitTraverseBatchDevice_f64(c, r, n, k, o, h, cnt, s);
   }
 };
 struct CtxDeleter {
@@ -1159,6 +1171,76 @@ class BVHAccel {
     const bool hit = intersector.GetT() < ray.max_t;  // strict
     intersector.PostTraversal(ray, hit, isect);
     return hit;
+  }
+
+  // The K = max_intersections frontmost hits along one ray, ascending by (t, prim_id) (the reference's declared
+  // MultiHitTraverse, nanort.h:761-770 — kept there inside `#if 0` — without its non-deducible comparator).  The contract of
+  // include/nanort_hip.h nrtMultiHitTraverseBatch: the binary loop over nodes_ / indices_, slab test on [ray.min_t, B] with
+  // B = ray.max_t while fewer than K hits are held, else the t of the worst held hit; a primitive the intersector accepts
+  // against B with t < ray.max_t enters when fewer than K are held or when its key is below the worst, which is evicted.
+  // Any intersector (Intersect / Update / PostTraversal, as for Traverse); isects receives the held hits only.
+  template <class I, class H>
+  bool MultiHitTraverse(const Ray<T> &ray, int max_intersections, const I &intersector, StackVector<H, 128> *isects,
+                        const BVHTraceOptions &options = BVHTraceOptions()) const {
+    EnsureHostTree();
+    (*isects)->clear();
+    if (max_intersections <= 0) return false;
+    const size_t K = static_cast<size_t>(max_intersections);
+    struct Held {
+      T t;
+      unsigned int prim;
+      H isect;
+    };
+    std::vector<Held> held;  // sorted by (t, prim)
+    held.reserve(K + 1);
+    unsigned int todo[kNANORT_MAX_STACK_DEPTH];
+    int top = 0;
+    todo[0] = 0;
+
+    T bound = ray.max_t;
+    intersector.Update(bound, static_cast<unsigned int>(-1));
+    intersector.PrepareTraversal(ray, options);
+
+    int dir_sign[3];
+    real3<T> dir;
+    for (int k = 0; k < 3; k++) {
+      dir_sign[k] = ray.dir[k] < static_cast<T>(0.0) ? 1 : 0;
+      dir[k] = ray.dir[k];
+    }
+    const real3<T> inv_dir = vsafe_inverse(dir);
+    const real3<T> org(ray.org[0], ray.org[1], ray.org[2]);
+
+    T box_t0, box_t1;
+    while (top >= 0) {
+      const BVHNode<T> &node = nodes_[todo[top--]];
+      if (!IntersectRayAABB(&box_t0, &box_t1, ray.min_t, bound, node.bmin, node.bmax, org, inv_dir, dir_sign)) continue;
+      if (node.flag == 0) {
+        const int near_side = dir_sign[node.axis];
+        todo[++top] = node.data[1 - near_side];
+        todo[++top] = node.data[near_side];
+        assert(top < kNANORT_MAX_STACK_DEPTH);
+        continue;
+      }
+      for (unsigned int i = 0; i < node.data[0]; i++) {
+        const unsigned int prim = indices_[node.data[1] + i];
+        T cand = bound;
+        if (!intersector.Intersect(&cand, prim)) continue;
+        if (!(cand < ray.max_t)) continue;  // (a NaN t too)
+        if (held.size() == K && !(cand < bound || prim < held.back().prim)) continue;  // accepted: cand <= bound
+        Held h;
+        h.t = cand;
+        h.prim = prim;
+        intersector.Update(cand, prim);
+        intersector.PostTraversal(ray, true, &h.isect);
+        size_t j = held.size();
+        while (j > 0 && (held[j - 1].t > cand || (held[j - 1].t == cand && held[j - 1].prim > prim))) j--;
+        held.insert(held.begin() + static_cast<std::ptrdiff_t>(j), h);
+        if (held.size() > K) held.pop_back();
+        if (held.size() == K) bound = held.back().t;
+      }
+    }
+    for (size_t j = 0; j < held.size(); j++) (*isects)->push_back(held[j].isect);
+    return !held.empty();
   }
 
   // The K nearest leaf primitives' [t_min, t_max] intervals along the ray, front to back, for
@@ -1356,6 +1438,43 @@ class BVHAccel {
     nrt_trace_options o;
     std::memcpy(&o, &options, sizeof(o));
     if (Api::OccludedDevice(ctx_.get(), reinterpret_cast<const typename Api::RayPod *>(d_rays), num_rays, &o, d_occluded, hip_stream) != NRT_OK) {
+      backend_error_ = nrtLastError(ctx_.get());
+      return false;
+    }
+    return true;
+  }
+  // The max_hits frontmost hits of each of `num_rays` rays in one GPU launch (nrtMultiHitTraverseBatch: the contract of
+  // MultiHitTraverse above, on a GPU-built or adopted triangle tree).  isects[i * max_hits + j] holds ray i's hits in ascending
+  // (t, prim_id) order, then miss records {0, 0, ray.max_t, 0xFFFFFFFF}; counts_out[i] (may be NULL) how many it holds.
+  bool MultiHitTraverseBatch(const Ray<T> *rays, size_t num_rays, unsigned int max_hits, TriangleIntersection<T> *isects,
+                             unsigned int *counts_out = NULL, const BVHTraceOptions &options = BVHTraceOptions()) const {
+    typedef detail::HipApi<T> Api;
+    if (!TraverseBatchImpl(static_cast<const Ray<T> *>(NULL), 0, static_cast<TriangleIntersection<T> *>(NULL), NULL, options)) return false;  // (context, primitive kind, a tree adopted by Load())
+    if (device_prim_kind_ != 0) {
+      backend_error_ = "MultiHitTraverseBatch: triangle trees only";
+      return false;
+    }
+    nrt_trace_options o;
+    std::memcpy(&o, &options, sizeof(o));
+    if (Api::MultiHit(ctx_.get(), reinterpret_cast<const typename Api::RayPod *>(rays), num_rays, max_hits, &o,
+                      reinterpret_cast<typename Api::HitPod *>(isects), counts_out) != NRT_OK) {
+      backend_error_ = nrtLastError(ctx_.get());
+      return false;
+    }
+    return true;
+  }
+  // ... and with device pointers, asynchronous on `hip_stream` (see TraverseBatchDevice).
+  bool MultiHitTraverseBatchDevice(const Ray<T> *d_rays, size_t num_rays, unsigned int max_hits, TriangleIntersection<T> *d_isects,
+                                   unsigned int *d_counts, void *hip_stream, const BVHTraceOptions &options = BVHTraceOptions()) const {
+    typedef detail::HipApi<T> Api;
+    if (!ctx_ || device_tree_stale_ || device_prim_kind_ != 0) {
+      backend_error_ = "MultiHitTraverseBatchDevice: no triangle tree on the GPU (Build() with the built-in triangle types, or TraverseBatch() once after Load())";
+      return false;
+    }
+    nrt_trace_options o;
+    std::memcpy(&o, &options, sizeof(o));
+    if (Api::MultiHitDevice(ctx_.get(), reinterpret_cast<const typename Api::RayPod *>(d_rays), num_rays, max_hits, &o,
+                            reinterpret_cast<typename Api::HitPod *>(d_isects), d_counts, hip_stream) != NRT_OK) {
       backend_error_ = nrtLastError(ctx_.get());
       return false;
     }

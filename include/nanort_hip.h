@@ -210,6 +210,40 @@ NRT_API nrt_status nrtOccludedBatchDevice_f32(nrt_ctx *ctx, const nrt_ray_f32 *d
 NRT_API nrt_status nrtOccludedBatchDevice_f64(nrt_ctx *ctx, const nrt_ray_f64 *d_rays, uint64_t num_rays,
                                               const nrt_trace_options *options, uint8_t *d_mask_out, void *hip_stream);
 
+/* ---- multi-hit traversal: the K frontmost triangles of every ray ------------------------------------------
+ * The reference declares BVHAccel::MultiHitTraverse (nanort.h:761-770, 2694-2797) but never compiles it (`#if 0`).  Contract,
+ * per ray, with K = max_hits, 1 <= K <= NRT_MAX_MULTIHIT, on a triangle context of the call's precision:
+ *   1. Candidate: a primitive that TriangleIntersector::Intersect accepts against the current bound B (trace options, the
+ *      watertight test with its fp64 edge fallback, `tt > B` rejected, `tt < min_t` rejected — exactly the closest-hit test)
+ *      and whose t is < ray.max_t.  min_t is INCLUSIVE, as in the closest-hit walk (the reference's dead code tests
+ *      `local_t > ray.min_t`).  A NaN t is never reported.
+ *   2. Order: hits are ranked by the key (t, prim_id), ascending; t compares numerically (-0 == +0) and prim_id breaks every
+ *      tie, so which candidates are held never depends on the order in which they were tested.
+ *   3. Walk: the reference's binary loop over the context's node array (nanort.h:2487-2556): pop, slab test on [ray.min_t, B],
+ *      near child first by dir_sign[axis].  B = ray.max_t while fewer than K hits are held, else the t of the worst held hit.
+ *      A candidate enters when fewer than K are held or when its key is smaller than the worst held key, which is evicted.
+ *      The bound only prunes: the result is the K smallest keys among the candidates of the leaves the walk reaches.
+ *   4. Output: hits_out[ray * K + j], j < count, holds the held hits in ascending key order; slots j >= count hold the miss
+ *      record {0, 0, ray.max_t, 0xFFFFFFFF} (every byte is written).  counts_out[ray] (may be NULL) receives count, 0..K.
+ *   5. K = 1: t and the hit flag (count) equal nrtTraverseBatch*'s on every ray; prim_id / u / v differ only where another
+ *      candidate has exactly the same t (multi-hit names the smaller prim_id, closest hit the last one accepted).
+ * options == NULL means the BVHTraceOptions() defaults.  NRT_ERR_INVALID: K == 0 or K > NRT_MAX_MULTIHIT, no tree, NULL rays or
+ * hits (num_rays > 0), a sphere or cylinder context, more than 2^31-1 rays; NRT_ERR_PRECISION: the context's precision is the
+ * other one.  num_rays == 0 returns NRT_OK.  Launches share the context's launch slots: nrtBuild / nrtSetTree / nrtSetMesh /
+ * nrtDestroy wait for them as for closest-hit launches. */
+#define NRT_MAX_MULTIHIT 64u
+NRT_API nrt_status nrtMultiHitTraverseBatch_f32(nrt_ctx *ctx, const nrt_ray_f32 *rays, uint64_t num_rays, uint32_t max_hits,
+                                                const nrt_trace_options *options, nrt_hit_f32 *hits_out, uint32_t *counts_out);
+NRT_API nrt_status nrtMultiHitTraverseBatch_f64(nrt_ctx *ctx, const nrt_ray_f64 *rays, uint64_t num_rays, uint32_t max_hits,
+                                                const nrt_trace_options *options, nrt_hit_f64 *hits_out, uint32_t *counts_out);
+/* Same, on HBM-resident buffers, asynchronously on `hip_stream` (a hipStream_t; NULL = the default stream). */
+NRT_API nrt_status nrtMultiHitTraverseBatchDevice_f32(nrt_ctx *ctx, const nrt_ray_f32 *d_rays, uint64_t num_rays, uint32_t max_hits,
+                                                      const nrt_trace_options *options, nrt_hit_f32 *d_hits_out, uint32_t *d_counts_out,
+                                                      void *hip_stream);
+NRT_API nrt_status nrtMultiHitTraverseBatchDevice_f64(nrt_ctx *ctx, const nrt_ray_f64 *d_rays, uint64_t num_rays, uint32_t max_hits,
+                                                      const nrt_trace_options *options, nrt_hit_f64 *d_hits_out, uint32_t *d_counts_out,
+                                                      void *hip_stream);
+
 /* ---- sphere primitives: replaces the SpherePred / SphereGeometry / SphereIntersector constructors of the
  * reference's custom-primitive example (examples/particle_primitive/main.cc:82-147, 161-166) -------------
  * `centers` holds xyz per sphere (tight), `radii` one radius per sphere.  After this call nrtBuild_f32 builds

@@ -347,6 +347,36 @@ class BVHAccel:
         self._check(getattr(self._L, "nrtOccludedBatchDevice_" + self._s)(self._h, d_rays.data_ptr(), n, _p(options), d_mask.data_ptr(), stream))
         return n
 
+    def MultiHitTraverseBatch(self, rays, max_hits, options=None):
+        """The K = max_hits frontmost hits of every ray (include/nanort_hip.h, nrtMultiHitTraverseBatch): returns (hits[n, K],
+        counts[n]); row i holds ray i's hits by ascending (t, prim_id), then miss records {0, 0, max_t, 0xFFFFFFFF}."""
+        rays = np.ascontiguousarray(rays, dtype=ray_dtype(self.real))
+        n = rays.shape[0]
+        hits = np.zeros((n, max(int(max_hits), 1)), dtype=hit_dtype(self.real))
+        counts = np.zeros((n,), dtype=np.uint32)
+        if options is not None:
+            options = np.asarray(options, dtype=TRACE_OPTIONS).reshape(1)
+        self._check(getattr(self._L, "nrtMultiHitTraverseBatch_" + self._s)(self._h, _p(rays), n, int(max_hits), _p(options), _p(hits), _p(counts)))
+        return hits, counts
+
+    def MultiHitTraverseBatchDevice(self, d_rays, max_hits, d_hits, d_counts=None, options=None, stream=None):
+        """Same on HBM-resident torch tensors (raw PODs: d_hits holds n * max_hits records, d_counts n uint32), asynchronous on
+        `stream` (default: torch's current stream).  Returns n."""
+        import torch
+
+        rsz, hsz = ray_dtype(self.real).itemsize, hit_dtype(self.real).itemsize
+        n = d_rays.numel() * d_rays.element_size() // rsz
+        assert d_hits.numel() * d_hits.element_size() >= n * int(max_hits) * hsz
+        assert d_counts is None or d_counts.numel() * d_counts.element_size() >= n * 4
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+        if options is not None:
+            options = np.asarray(options, dtype=TRACE_OPTIONS).reshape(1)
+        self._check(getattr(self._L, "nrtMultiHitTraverseBatchDevice_" + self._s)(
+            self._h, d_rays.data_ptr(), n, int(max_hits), _p(options), d_hits.data_ptr(),
+            None if d_counts is None else d_counts.data_ptr(), stream))
+        return n
+
     def TraverseCountDevice(self, d_rays, options=None):
         """Work counters (nodes visited, leaves, triangle tests, max stack) of one batch."""
         rsz = ray_dtype(self.real).itemsize

@@ -36,6 +36,10 @@ hipError_t launch_traverse_wide(const TraverseArgs<T> &, unsigned grid, int lds_
 template <typename T>
 int traverse_wide_blocks_per_cu(int lds_stack, int prim_kind, bool wide4);
 template <typename T>
+hipError_t launch_traverse_multihit(const TraverseArgs<T> &, uint32_t max_hits, uint32_t *counts, unsigned grid, hipStream_t); // (multihit.hip)
+template <typename T>
+int traverse_multihit_blocks_per_cu();
+template <typename T>
 hipError_t launch_gather_leaf_spheres(const uint32_t *, const T *, const T *, LeafSphere<T> *, uint32_t, hipStream_t);
 template <typename T>
 hipError_t launch_gather_leaf_cylinders(const uint32_t *, const T *, const T *, LeafCylinder<T> *, uint32_t, hipStream_t);
@@ -171,6 +175,7 @@ struct nrt_ctx {
   int wide_scramble = 0; // probe (tunable wide_scramble): the private node records in a pseudo-random order instead of pre-order
   unsigned wide4_blocks_per_cu = 0;
   unsigned wide_blocks_per_cu = 0, sphere_blocks_per_cu = 0;
+  unsigned multihit_blocks_per_cu = 0; // k_traverse_multihit (multihit.hip)
 
   hipEvent_t ev_b0 = nullptr, ev_b1 = nullptr;
   hipEvent_t ev_build_state = nullptr; // the builder's state block has reached build_state
@@ -865,6 +870,13 @@ int nrt_internal_device(const nrt_ctx *c) { return c ? c->device : 0; } // group
 // ---------------------------------------------------------------------------
 static const nrt_trace_options kDefaultTrace = {{0u, 0x7FFFFFFFu}, 0xFFFFFFFFu, 0, {0, 0, 0}}; // nanort.h:617-623
 
+// A multi-hit launch (nrtMultiHitTraverseBatch*): the binary loop of k_traverse_multihit over the same launch slots; the hit
+// pointer of traverse_device then holds `max_hits` records per ray.
+struct MultiHitLaunch {
+  uint32_t max_hits;
+  uint32_t *counts; // may be null
+};
+
 // Several batches for one launch (nrtTraverseBatchesDevice): fp32 triangle contexts on the WideNode kernels.
 template <typename T>
 struct TraverseBatches {
@@ -880,7 +892,7 @@ template <typename T>
 static nrt_status traverse_device(nrt_ctx *c, const typename Wire<T>::Ray *d_rays, uint64_t n,
                                   const nrt_trace_options *opt, typename Wire<T>::Hit *d_hits, uint8_t *d_mask,
                                   hipStream_t s, bool count, bool timed, void *d_cyl_hits = nullptr, bool any_hit = false,
-                                  const TraverseBatches<T> *mb = nullptr) {
+                                  const TraverseBatches<T> *mb = nullptr, const MultiHitLaunch *mh = nullptr) {
   if (c->prec != (int)sizeof(T)) return fail(c, NRT_ERR_PRECISION, "nrtTraverseBatch: precision mismatch");
   if (mb) { // (the caller checked that this context walks batches in one launch; n = all rays)
     d_rays = mb->rays[0];
@@ -932,8 +944,9 @@ static nrt_status traverse_device(nrt_ctx *c, const typename Wire<T>::Ray *d_ray
     return fail(c, NRT_ERR_INVALID, "nrtTraverse: custom primitives run on the WideNode kernel only (no counting pass)");
   if (any_hit && (spheres || count || !c->d_wide))
     return fail(c, NRT_ERR_INVALID, "nrtOccludedBatch: occlusion queries run on the triangle WideNode kernel only");
-  const bool use_wide = (c->wide || spheres || any_hit) && !count && c->d_wide;
+  const bool use_wide = (c->wide || spheres || any_hit) && !count && c->d_wide && !mh;
   if (c->blocks_per_cu == 0) c->blocks_per_cu = (unsigned)traverse_blocks_per_cu<T>(c->lds_stack);
+  if (mh && c->multihit_blocks_per_cu == 0) c->multihit_blocks_per_cu = (unsigned)traverse_multihit_blocks_per_cu<T>();
   // two levels per step: closest-hit walks of nested fp32 triangle trees, outside the profiling / splitting variants
   // prim ids are < num_faces: nothing can be rejected by these options -> the kernel variant without the id tests
   const bool plain_options = opt->prim_ids_range[0] == 0u && opt->prim_ids_range[1] >= c->num_faces && opt->skip_prim_id >= c->num_faces &&
@@ -950,8 +963,9 @@ static nrt_status traverse_device(nrt_ctx *c, const typename Wire<T>::Ray *d_ray
   if (use_wide4 && !spheres && c->wide4_blocks_per_cu == 0) c->wide4_blocks_per_cu = (unsigned)traverse_wide_blocks_per_cu<T>(kWide4LdsStack, kPrimTriangles, true);
   if (spheres && c->sphere_blocks_per_cu == 0) c->sphere_blocks_per_cu = (unsigned)traverse_wide_blocks_per_cu<T>(10, c->prim_kind, use_wide4); // (one kind and one walk per context)
   unsigned blocks_per_cu = spheres ? c->sphere_blocks_per_cu : (use_wide4 ? c->wide4_blocks_per_cu : (use_wide ? c->wide_blocks_per_cu : c->blocks_per_cu));
+  if (mh) blocks_per_cu = c->multihit_blocks_per_cu;
   if (c->max_blocks_per_cu && blocks_per_cu > c->max_blocks_per_cu) blocks_per_cu = c->max_blocks_per_cu;
-  const int stack_entries = use_wide4 ? kWide4LdsStack : (spheres ? 10 : (use_wide ? c->wide_stack : c->lds_stack));
+  const int stack_entries = mh ? kLdsStackDefault : (use_wide4 ? kWide4LdsStack : (spheres ? 10 : (use_wide ? c->wide_stack : c->lds_stack)));
   uint64_t need_blocks = (n + kTraverseBlock - 1) / kTraverseBlock;
   unsigned grid = (unsigned)std::min<uint64_t>(need_blocks, (uint64_t)c->num_cus * blocks_per_cu);
   const unsigned parts = std::max(1u, std::min(c->num_parts, grid));
@@ -1083,7 +1097,10 @@ static nrt_status traverse_device(nrt_ctx *c, const typename Wire<T>::Ray *d_ray
   a.done_publish = post_pass ? 0u : 1u;
   timed = timed && !use_rec;
   if (timed) HIPCHK(c, hipEventRecord(slot->t0, s));
-  if (use_wide) {
+  if (mh) {
+    HIPCHK(c, launch_traverse_multihit<T>(a, mh->max_hits, mh->counts, grid, s));
+    c->last_kernel = sizeof(T) == 4 ? "nrt::k_traverse_multihit<float>" : "nrt::k_traverse_multihit<double>";
+  } else if (use_wide) {
     HIPCHK(c, launch_traverse_wide<T>(a, grid, c->wide_stack, c->prim_kind, s, &c->last_kernel));
   } else {
     HIPCHK(c, launch_traverse<T>(a, grid, count, c->lds_stack, s));
@@ -1438,7 +1455,79 @@ static nrt_status occluded_host(nrt_ctx *c, const typename Wire<T>::Ray *rays, u
   return NRT_OK;
 }
 
+// ---------------------------------------------------------------------------
+// multi-hit (include/nanort_hip.h, nrtMultiHitTraverseBatch*)
+// ---------------------------------------------------------------------------
+template <typename T>
+static nrt_status multihit_check(nrt_ctx *c, const void *rays, uint64_t n, uint32_t max_hits, const void *hits) {
+  if (!c->d_nodes) return fail(c, NRT_ERR_INVALID, "nrtMultiHitTraverseBatch: no tree (call nrtBuild or nrtSetTree)");
+  if (c->prec != (int)sizeof(T)) return fail(c, NRT_ERR_PRECISION, "nrtMultiHitTraverseBatch: precision mismatch");
+  if (max_hits == 0u || max_hits > NRT_MAX_MULTIHIT)
+    return fail(c, NRT_ERR_INVALID, "nrtMultiHitTraverseBatch: max_hits %u outside 1..%u", max_hits, NRT_MAX_MULTIHIT);
+  if (c->prim_kind != kPrimTriangles) return fail(c, NRT_ERR_INVALID, "nrtMultiHitTraverseBatch: triangle contexts only");
+  if (n == 0) return NRT_OK;
+  if (!rays || !hits) return fail(c, NRT_ERR_INVALID, "nrtMultiHitTraverseBatch: NULL rays/hits");
+  if (n > 0x7FFFFFFFull) return fail(c, NRT_ERR_INVALID, "nrtMultiHitTraverseBatch: more than 2^31-1 rays in one call");
+  return NRT_OK;
+}
+
+template <typename T>
+static nrt_status multihit_device(nrt_ctx *c, const typename Wire<T>::Ray *d_rays, uint64_t n, uint32_t max_hits, const nrt_trace_options *opt,
+                                  typename Wire<T>::Hit *d_hits, uint32_t *d_counts, hipStream_t s) {
+  if (!c) return NRT_ERR_INVALID;
+  nrt_status st = multihit_check<T>(c, d_rays, n, max_hits, d_hits);
+  if (st || n == 0) return st;
+  const MultiHitLaunch mh = {max_hits, d_counts};
+  return traverse_device<T>(c, d_rays, n, opt, d_hits, nullptr, s, false, true, nullptr, false, nullptr, &mh);
+}
+
+template <typename T>
+static nrt_status multihit_host(nrt_ctx *c, const typename Wire<T>::Ray *rays, uint64_t n, uint32_t max_hits, const nrt_trace_options *opt,
+                                typename Wire<T>::Hit *hits, uint32_t *counts) {
+  if (!c) return NRT_ERR_INVALID;
+  nrt_status st = multihit_check<T>(c, rays, n, max_hits, hits);
+  if (st || n == 0) return st;
+  typedef typename Wire<T>::Ray Ray;
+  typedef typename Wire<T>::Hit Hit;
+  std::lock_guard<std::mutex> host_lock(c->host_mutex);
+  HIPCHK(c, hipSetDevice(c->device));
+  // rays per launch: the staged records stay within 256 MiB whatever K is
+  const uint64_t chunk = std::max<uint64_t>(1u, std::min<uint64_t>(1ull << 26, (256ull << 20) / ((uint64_t)max_hits * sizeof(Hit))));
+  for (uint64_t off = 0; off < n; off += chunk) {
+    const uint64_t m = std::min(chunk, n - off);
+    if ((st = ensure(c, c->st_rays, m * sizeof(Ray)))) return st;
+    if ((st = ensure(c, c->st_hits, m * max_hits * sizeof(Hit)))) return st;
+    if ((st = ensure(c, c->st_mask, m * sizeof(uint32_t)))) return st;
+    HIPCHK(c, hipMemcpyAsync(c->st_rays.p, rays + off, m * sizeof(Ray), hipMemcpyHostToDevice, c->stream));
+    const MultiHitLaunch mh = {max_hits, counts ? (uint32_t *)c->st_mask.p : nullptr};
+    st = traverse_device<T>(c, (const Ray *)c->st_rays.p, m, opt, (Hit *)c->st_hits.p, nullptr, c->stream, false, true, nullptr, false,
+                            nullptr, &mh);
+    if (st) return st;
+    HIPCHK(c, hipMemcpyAsync(hits + off * max_hits, c->st_hits.p, m * max_hits * sizeof(Hit), hipMemcpyDeviceToHost, c->stream));
+    if (counts) HIPCHK(c, hipMemcpyAsync(counts + off, c->st_mask.p, m * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  return NRT_OK;
+}
+
 extern "C" {
+
+nrt_status nrtMultiHitTraverseBatch_f32(nrt_ctx *c, const nrt_ray_f32 *r, uint64_t n, uint32_t k, const nrt_trace_options *o, nrt_hit_f32 *h,
+                                        uint32_t *cnt) {
+  return multihit_host<float>(c, r, n, k, o, h, cnt);
+}
+nrt_status nrtMultiHitTraverseBatch_f64(nrt_ctx *c, const nrt_ray_f64 *r, uint64_t n, uint32_t k, const nrt_trace_options *o, nrt_hit_f64 *h,
+                                        uint32_t *cnt) {
+  return multihit_host<double>(c, r, n, k, o, h, cnt);
+}
+nrt_status nrtMultiHitTraverseBatchDevice_f32(nrt_ctx *c, const nrt_ray_f32 *r, uint64_t n, uint32_t k, const nrt_trace_options *o,
+                                              nrt_hit_f32 *h, uint32_t *cnt, void *s) {
+  return multihit_device<float>(c, r, n, k, o, h, cnt, (hipStream_t)s);
+}
+nrt_status nrtMultiHitTraverseBatchDevice_f64(nrt_ctx *c, const nrt_ray_f64 *r, uint64_t n, uint32_t k, const nrt_trace_options *o,
+                                              nrt_hit_f64 *h, uint32_t *cnt, void *s) {
+  return multihit_device<double>(c, r, n, k, o, h, cnt, (hipStream_t)s);
+}
 
 nrt_status nrtSetMesh_f32(nrt_ctx *c, const float *v, size_t stride, const uint32_t *f, uint32_t nf) {
   return set_mesh<float>(c, v, stride, f, nf);
