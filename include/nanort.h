@@ -55,6 +55,9 @@
 #ifdef _OPENMP
 #include <omp.h>
 #endif
+#ifdef __linux__
+#include <sched.h>  // sched_getaffinity: the CPUs this process may run on (detail::HostThreads)
+#endif
 
 #define kNANORT_MAX_STACK_DEPTH (512)
 #define kNANORT_MIN_PRIMITIVES_FOR_PARALLEL_BUILD (1024 * 8)
@@ -77,7 +80,8 @@ namespace detail {
 // Worker threads for the host-side loops of this header (the parallel host build, the hit scatter of TraverseBatch):
 // what the process may actually use — the cgroup CPU quota when there is one (an OpenMP default of "every hardware
 // thread" inside a quota'd container collapses, and starves the HIP runtime's own threads), else the OpenMP / hardware
-// thread count — clamped to [1, 64].
+// thread count, and never more than the CPUs of the process's affinity mask (taskset, cpusets: hardware_concurrency()
+// counts every online CPU of the machine) — clamped to [1, 64].
 inline unsigned int HostThreadsUncached() {
   unsigned int n = 1;
 #if defined(_OPENMP)
@@ -100,6 +104,12 @@ inline unsigned int HostThreadsUncached() {
   }
   if (quota > 0 && period > 0 && static_cast<unsigned long>(quota / period) >= 1 && static_cast<unsigned long>(quota / period) < n)
     n = static_cast<unsigned int>(quota / period);
+#if defined(__linux__) && defined(CPU_COUNT)
+  cpu_set_t allowed;
+  CPU_ZERO(&allowed);
+  if (sched_getaffinity(0, sizeof(allowed), &allowed) == 0 && CPU_COUNT(&allowed) >= 1 && static_cast<unsigned int>(CPU_COUNT(&allowed)) < n)
+    n = static_cast<unsigned int>(CPU_COUNT(&allowed));
+#endif
   return std::min(64u, std::max(1u, n));
 }
 inline unsigned int HostThreads() {
@@ -1051,12 +1061,21 @@ class BVHAccel {
   ~BVHAccel() {}
 #ifdef NANORT_USE_HIP_BACKEND
   // A GPU Build() leaves the tree on the device: nodes_ / indices_ are fetched by the first host access (GetNodes(),
-  // GetIndices(), Traverse(), ListNodeIntersections(), Dump(), Debug()).  A copy shares the device context (shared_ptr), so
-  // it takes the host arrays with it: copying materialises them first — the copy then never depends on what the original's
-  // context holds later.
+  // GetIndices(), Traverse(), MultiHitTraverse(), ListNodeIntersections(), Dump(), Debug(), copying).  A copy takes the host
+  // arrays with it (copying materialises them first) and shares the device contexts (shared_ptr) until either side changes
+  // what a context holds: Build(), the upload of a Load()ed tree and the cylinder cap re-send first move the object that
+  // makes the change to contexts of its own (copy-on-write: the primitive arrays Build() was given are sent again, so they
+  // must outlive the accel, as the reference's Traverse() already requires).  Neither side ever traces the other's tree.
+  // A move transfers the contexts, a pending read-back and the staging buffers as they are (no read-back); the source is
+  // left empty (IsValid() false), ready to be rebuilt or destroyed.
   BVHAccel(const BVHAccel &o) : pad0_(0) { CopyFrom(o); }
   BVHAccel &operator=(const BVHAccel &o) {
     if (this != &o) CopyFrom(o);
+    return *this;
+  }
+  BVHAccel(BVHAccel &&o) noexcept : pad0_(0) { MoveFrom(&o); }  // (noexcept: std::vector moves rather than copies)
+  BVHAccel &operator=(BVHAccel &&o) noexcept {
+    if (this != &o) MoveFrom(&o);
     return *this;
   }
 #endif
@@ -1303,6 +1322,11 @@ class BVHAccel {
   // Requires a tree built by Build() with the built-in triangle types (or Load() after such a
   // Build set the mesh).  Returns false and leaves the outputs untouched on a backend error
   // (LastBackendError() tells why).
+  // Threads: the batch methods below (const, like Traverse()) may be called on one object from many threads at once.  A
+  // per-object mutex (batch_mutex_, a fresh one for every copy) guards the shared staging buffers from the launch to the
+  // scatter into the caller's arrays, and the lazy device-side updates (the upload of a Load()ed tree, the cylinder cap
+  // re-send, a copy-on-write detach); calls on one object are thereby serialised, calls on different objects (copies
+  // included) are not.
   bool TraverseBatch(const Ray<T> *rays, size_t num_rays, TriangleIntersection<T> *isects, unsigned char *hit_out = NULL,
                      const BVHTraceOptions &options = BVHTraceOptions()) const {
     return TraverseBatchImpl(rays, num_rays, isects, hit_out, options);
@@ -1313,6 +1337,7 @@ class BVHAccel {
   // Launches on different streams may overlap on the GPU.
   bool TraverseBatchDevice(const Ray<T> *d_rays, size_t num_rays, TriangleIntersection<T> *d_isects, unsigned char *d_hit,
                            void *hip_stream, const BVHTraceOptions &options = BVHTraceOptions()) const {
+    std::lock_guard<std::mutex> lock(batch_mutex_);
     if (!ctx_ || device_tree_stale_ || device_prim_kind_ != 0) {
       backend_error_ = "TraverseBatchDevice: no triangle tree on the GPU (Build() with the built-in triangle types, or TraverseBatch() once after Load())";
       return false;
@@ -1332,6 +1357,7 @@ class BVHAccel {
                              unsigned char *const *d_hit, const unsigned char *occlusion, void *hip_stream,
                              const BVHTraceOptions &options = BVHTraceOptions()) const {
     typedef detail::HipApi<T> Api;
+    std::lock_guard<std::mutex> lock(batch_mutex_);
     if (!ctx_ || device_tree_stale_ || device_prim_kind_ != 0) {
       backend_error_ = "TraverseBatchesDevice: no triangle tree on the GPU";
       return false;
@@ -1366,7 +1392,8 @@ class BVHAccel {
                        unsigned char *const *hit_out, const unsigned char *occlusion, const BVHTraceOptions &options = BVHTraceOptions()) const {
     typedef detail::HipApi<T> Api;
     typedef typename Api::HitPod HitPod;
-    if (!TraverseBatchImpl(static_cast<const Ray<T> *>(NULL), 0, static_cast<TriangleIntersection<T> *>(NULL), NULL, options)) return false;  // (context, primitive kind, a tree adopted by Load())
+    std::lock_guard<std::mutex> lock(batch_mutex_);
+    if (!DeviceTreeReady(0)) return false;  // (context, primitive kind, a tree adopted by Load())
     size_t total = 0;
     for (size_t k = 0; k < num_waves; k++) total += num_rays[k];
     if (total == 0) return true;
@@ -1415,6 +1442,7 @@ class BVHAccel {
   // TraverseBatch() would report in hit_out[i], but a ray stops at the first primitive it accepts (shadow rays).
   bool OccludedBatch(const Ray<T> *rays, size_t num_rays, unsigned char *occluded_out, const BVHTraceOptions &options = BVHTraceOptions()) const {
     typedef detail::HipApi<T> Api;
+    std::lock_guard<std::mutex> lock(batch_mutex_);
     if (!ctx_ || device_tree_stale_ || device_prim_kind_ != 0) {
       backend_error_ = "OccludedBatch: no triangle tree on the GPU (Build() with the built-in triangle types, or TraverseBatch() once after Load())";
       return false;
@@ -1431,6 +1459,7 @@ class BVHAccel {
   bool OccludedBatchDevice(const Ray<T> *d_rays, size_t num_rays, unsigned char *d_occluded, void *hip_stream,
                            const BVHTraceOptions &options = BVHTraceOptions()) const {
     typedef detail::HipApi<T> Api;
+    std::lock_guard<std::mutex> lock(batch_mutex_);
     if (!ctx_ || device_tree_stale_ || device_prim_kind_ != 0) {
       backend_error_ = "OccludedBatchDevice: no triangle tree on the GPU";
       return false;
@@ -1449,11 +1478,8 @@ class BVHAccel {
   bool MultiHitTraverseBatch(const Ray<T> *rays, size_t num_rays, unsigned int max_hits, TriangleIntersection<T> *isects,
                              unsigned int *counts_out = NULL, const BVHTraceOptions &options = BVHTraceOptions()) const {
     typedef detail::HipApi<T> Api;
-    if (!TraverseBatchImpl(static_cast<const Ray<T> *>(NULL), 0, static_cast<TriangleIntersection<T> *>(NULL), NULL, options)) return false;  // (context, primitive kind, a tree adopted by Load())
-    if (device_prim_kind_ != 0) {
-      backend_error_ = "MultiHitTraverseBatch: triangle trees only";
-      return false;
-    }
+    std::lock_guard<std::mutex> lock(batch_mutex_);
+    if (!DeviceTreeReady(0)) return false;  // (context, primitive kind, a tree adopted by Load())
     nrt_trace_options o;
     std::memcpy(&o, &options, sizeof(o));
     if (Api::MultiHit(ctx_.get(), reinterpret_cast<const typename Api::RayPod *>(rays), num_rays, max_hits, &o,
@@ -1467,6 +1493,7 @@ class BVHAccel {
   bool MultiHitTraverseBatchDevice(const Ray<T> *d_rays, size_t num_rays, unsigned int max_hits, TriangleIntersection<T> *d_isects,
                                    unsigned int *d_counts, void *hip_stream, const BVHTraceOptions &options = BVHTraceOptions()) const {
     typedef detail::HipApi<T> Api;
+    std::lock_guard<std::mutex> lock(batch_mutex_);
     if (!ctx_ || device_tree_stale_ || device_prim_kind_ != 0) {
       backend_error_ = "MultiHitTraverseBatchDevice: no triangle tree on the GPU (Build() with the built-in triangle types, or TraverseBatch() once after Load())";
       return false;
@@ -1492,14 +1519,26 @@ class BVHAccel {
                      const BVHTraceOptions &options = BVHTraceOptions(), bool test_cap = true) const {
     static_assert(detail::same_type<T, float>::value, "the cylinder primitive is fp32");
     static_assert(sizeof(CylinderIntersection) == sizeof(nrt_cyl_hit_f32), "CylinderIntersection layout");
+    std::lock_guard<std::mutex> lock(batch_mutex_);
     if (!ctx_ || !cyl_endpoints_ || device_prim_kind_ != 2) {
       backend_error_ = "TraverseBatch(CylinderIntersection*): Build() with CylinderGeometry/CylinderPred first";
       return false;
     }
     if (test_cap != cyl_test_cap_ || device_tree_stale_) {  // the flag lives with the primitives on the device
-      if (nodes_.empty() || nrtSetCylinders_f32(ctx_.get(), cyl_endpoints_, cyl_radii_, cyl_count_, test_cap ? 1 : 0) != NRT_OK ||
-          nrtSetTree_f32(ctx_.get(), reinterpret_cast<const nrt_node_f32 *>(&nodes_[0]), nodes_.size(), &indices_[0], indices_.size()) != NRT_OK) {
-        backend_error_ = nodes_.empty() ? "TraverseBatch: empty tree" : nrtLastError(ctx_.get());
+      // (the host tree first: it may still be pending after Build(), and nrtSetCylinders_f32 frees the device tree)
+      EnsureHostTree();
+      if (nodes_.empty()) {
+        backend_error_ = "TraverseBatch: empty tree";
+        return false;
+      }
+      if (SharesDeviceContext()) {  // copy-on-write: the shared context stays with the copies
+        if (!DetachDeviceContext(test_cap)) return false;  // (sends the cylinders with the new flag)
+      } else if (nrtSetCylinders_f32(ctx_.get(), cyl_endpoints_, cyl_radii_, cyl_count_, test_cap ? 1 : 0) != NRT_OK) {
+        backend_error_ = nrtLastError(ctx_.get());
+        return false;
+      }
+      if (nrtSetTree_f32(ctx_.get(), reinterpret_cast<const nrt_node_f32 *>(&nodes_[0]), nodes_.size(), &indices_[0], indices_.size()) != NRT_OK) {
+        backend_error_ = nrtLastError(ctx_.get());
         return false;
       }
       cyl_test_cap_ = test_cap;
@@ -1537,36 +1576,48 @@ class BVHAccel {
     typedef detail::HipApi<T> Api;
     return Api::TraverseDevice(c, reinterpret_cast<const typename Api::RayPod *>(r), n, o, reinterpret_cast<typename Api::HitPod *>(h), m, stream);
   }
-  template <class Hit>
-  bool TraverseBatchImpl(const Ray<T> *rays, size_t num_rays, Hit *isects, unsigned char *hit_out, const BVHTraceOptions &options) const {
+  // The checks every host batch call makes (caller holds batch_mutex_): a context, the primitive kind the call's records are
+  // for (0 triangles, 1 spheres), and a tree adopted by Load() uploaded — after a copy-on-write detach when the contexts are
+  // shared with copies.
+  bool DeviceTreeReady(int want_kind) const {
     typedef detail::HipApi<T> Api;
-    static_assert(sizeof(Ray<T>) == sizeof(typename Api::RayPod), "Ray layout");
-    static_assert(sizeof(Hit) == sizeof(typename Api::HitPod), "intersection record layout");
-    static_assert(sizeof(BVHTraceOptions) == sizeof(nrt_trace_options), "BVHTraceOptions layout");
     if (!ctx_) {
       backend_error_ = "TraverseBatch: no GPU context (Build() with TriangleMesh/TriangleSAHPred first)";
       return false;
     }
-    const int want_kind = detail::same_type<Hit, TriangleIntersection<T> >::value ? 0 : 1;
     if (device_prim_kind_ != want_kind) {  // records of one primitive kind must not be read as another's
       backend_error_ = want_kind == 0 ? "TraverseBatch(TriangleIntersection*): this accel was not built over a TriangleMesh"
                                       : "TraverseBatch(SphereIntersection*): this accel was not built over a SphereGeometry";
       return false;
     }
     if (device_tree_stale_) {
-      if (nodes_.empty() || Api::SetTree(ctx_.get(), reinterpret_cast<const typename Api::NodePod *>(&nodes_[0]), nodes_.size(),
-                                         indices_.empty() ? NULL : &indices_[0], indices_.size()) != NRT_OK) {
-        backend_error_ = nodes_.empty() ? "TraverseBatch: empty tree" : nrtLastError(ctx_.get());
+      EnsureHostTree();  // (Load() already dropped any pending read-back: a no-op, kept so the upload never sees a half state)
+      if (nodes_.empty()) {
+        backend_error_ = "TraverseBatch: empty tree";
         return false;
       }
-      for (size_t k = 0; k < peers_.size(); k++) // (the replicas on the other devices adopt the same arrays)
-        if (Api::SetTree(peers_[k].get(), reinterpret_cast<const typename Api::NodePod *>(&nodes_[0]), nodes_.size(),
-                         indices_.empty() ? NULL : &indices_[0], indices_.size()) != NRT_OK) {
-          backend_error_ = nrtLastError(peers_[k].get());
+      if (SharesDeviceContext() && !DetachDeviceContext(cyl_test_cap_)) return false;  // copy-on-write
+      for (size_t k = 0; k <= peers_.size(); k++) {  // (the replicas on the other devices adopt the same arrays)
+        nrt_ctx *c = k == 0 ? ctx_.get() : peers_[k - 1].get();
+        if (Api::SetTree(c, reinterpret_cast<const typename Api::NodePod *>(&nodes_[0]), nodes_.size(), indices_.empty() ? NULL : &indices_[0],
+                         indices_.size()) != NRT_OK) {
+          backend_error_ = nrtLastError(c);
           return false;
         }
+      }
       device_tree_stale_ = false;
     }
+    return true;
+  }
+  template <class Hit>
+  bool TraverseBatchImpl(const Ray<T> *rays, size_t num_rays, Hit *isects, unsigned char *hit_out, const BVHTraceOptions &options) const {
+    typedef detail::HipApi<T> Api;
+    static_assert(sizeof(Ray<T>) == sizeof(typename Api::RayPod), "Ray layout");
+    static_assert(sizeof(Hit) == sizeof(typename Api::HitPod), "intersection record layout");
+    static_assert(sizeof(BVHTraceOptions) == sizeof(nrt_trace_options), "BVHTraceOptions layout");
+    const int want_kind = detail::same_type<Hit, TriangleIntersection<T> >::value ? 0 : 1;
+    std::lock_guard<std::mutex> lock(batch_mutex_);  // (staging, launch and scatter: see the comment above TraverseBatch)
+    if (!DeviceTreeReady(want_kind)) return false;
     if (num_rays == 0) return true;
     // Grow-only byte staging owned by the accel, page-locked when the backend can provide it (the device-to-host copy
     // then runs at PCIe speed; PODs: no per-element construction, no fresh pages to fault in on every wave); the caller's
@@ -1965,6 +2016,7 @@ class BVHAccel {
     // primitives and must not be traced against this tree
     ctx_.reset();
     peers_.clear();
+    devices_.clear();
     device_tree_stale_ = false;
     device_prim_kind_ = -1;
 #endif
@@ -1977,12 +2029,19 @@ class BVHAccel {
                  detail::triangle_tag) {
     (void)pred;
     typedef detail::HipApi<T> Api;
-    return HipBuild(n, options, 0, [&](nrt_ctx *c) { return Api::SetMesh(c, mesh.GetVertices(), mesh.GetVertexStrideBytes(), mesh.GetFaces(), n); });
+    tri_vertices_ = mesh.GetVertices();  // (kept: a copy-on-write detach sends them to the new context)
+    tri_stride_ = mesh.GetVertexStrideBytes();
+    tri_faces_ = mesh.GetFaces();
+    prim_count_ = n;
+    return HipBuild(n, options, 0, [&](nrt_ctx *c) { return Api::SetMesh(c, tri_vertices_, tri_stride_, tri_faces_, n); });
   }
   bool BuildImpl(unsigned int n, const SphereGeometry &geom, const SpherePred &pred, const BVHBuildOptions<T> &options,
                  detail::sphere_tag) {
     (void)pred;
-    return HipBuild(n, options, 1, [&](nrt_ctx *c) { return nrtSetSpheres_f32(c, geom.GetCenters(), geom.GetRadii(), n); });
+    sph_centers_ = geom.GetCenters();
+    sph_radii_ = geom.GetRadii();
+    prim_count_ = n;
+    return HipBuild(n, options, 1, [&](nrt_ctx *c) { return nrtSetSpheres_f32(c, sph_centers_, sph_radii_, n); });
   }
 
   // (the intersector's test_cap flag is a traversal-time property: TraverseBatch() re-sends the primitives if it differs)
@@ -2010,42 +2069,11 @@ class BVHAccel {
     indices_.clear();
     assert(options_.bin_size > 1);
     if (n == 0) return false;
-    if (!ctx_) {
-      // devices: NANORT_HIP_DEVICES ("all" or a comma-separated list; the first is the primary) or the one of NANORT_HIP_DEVICE
-      std::vector<int> devices;
-      if (const char *list = std::getenv("NANORT_HIP_DEVICES")) {
-        if (std::strcmp(list, "all") == 0) {
-          for (int d = 0; d < nrtDeviceCount(); d++) devices.push_back(d);
-        } else {
-          for (const char *p = list; *p;) {
-            devices.push_back(std::atoi(p));
-            while (*p && *p != ',') p++;
-            if (*p == ',') p++;
-          }
-        }
-      }
-      if (devices.empty()) {
-        int device = 0;
-        if (const char *env = std::getenv("NANORT_HIP_DEVICE")) device = std::atoi(env);
-        devices.push_back(device);
-      }
-      for (size_t k = 0; k < devices.size(); k++) {
-        nrt_ctx *raw = NULL;
-        if (nrtCreate(devices[k], &raw) != NRT_OK) {
-          backend_error_ = nrtLastError(NULL);
-          if (k == 0) {
-            fprintf(stderr, "[nanort] HIP backend unavailable: %s\n", backend_error_.c_str());
-            return false;
-          }
-          fprintf(stderr, "[nanort] HIP device %d unavailable (%s): continuing with %zu device(s)\n", devices[k], backend_error_.c_str(), k);
-          break;
-        }
-        if (k == 0)
-          ctx_ = std::shared_ptr<nrt_ctx>(raw, detail::CtxDeleter());
-        else
-          peers_.push_back(std::shared_ptr<nrt_ctx>(raw, detail::CtxDeleter()));
-      }
+    if (SharesDeviceContext()) {  // copy-on-write: the copies keep the contexts they share with this object
+      ctx_.reset();
+      peers_.clear();
     }
+    if (!ctx_ && !CreateContexts(DeviceList())) return false;
     nrt_ctx *c = ctx_.get();
     typename Api::BuildPod o;
     std::memcpy(&o, &options, sizeof(o));
@@ -2086,11 +2114,90 @@ class BVHAccel {
         backend_error_ = nrtLastError(peers_[k].get());
         fprintf(stderr, "[nanort] HIP build of replica %zu failed (%s): tracing on one device\n", k + 1, backend_error_.c_str());
         peers_.clear();
+        devices_.resize(1);
         break;
       }
     }
     device_tree_stale_ = false;
     device_prim_kind_ = prim_kind;
+    return true;
+  }
+
+  // The devices a Build() uses: NANORT_HIP_DEVICES ("all" or a comma-separated list; the first is the primary) or the one of
+  // NANORT_HIP_DEVICE (default 0).
+  static std::vector<int> DeviceList() {
+    std::vector<int> devices;
+    if (const char *list = std::getenv("NANORT_HIP_DEVICES")) {
+      if (std::strcmp(list, "all") == 0) {
+        for (int d = 0; d < nrtDeviceCount(); d++) devices.push_back(d);
+      } else {
+        for (const char *p = list; *p;) {
+          devices.push_back(std::atoi(p));
+          while (*p && *p != ',') p++;
+          if (*p == ',') p++;
+        }
+      }
+    }
+    if (devices.empty()) {
+      int device = 0;
+      if (const char *env = std::getenv("NANORT_HIP_DEVICE")) device = std::atoi(env);
+      devices.push_back(device);
+    }
+    return devices;
+  }
+  // Fresh contexts on `devices` (ctx_ on the first, a replica in peers_ on each other one that opens), replacing the current ones.
+  bool CreateContexts(const std::vector<int> &devices) const {
+    ctx_.reset();
+    peers_.clear();
+    devices_.clear();
+    for (size_t k = 0; k < devices.size(); k++) {
+      nrt_ctx *raw = NULL;
+      if (nrtCreate(devices[k], &raw) != NRT_OK) {
+        backend_error_ = nrtLastError(NULL);
+        if (k == 0) {
+          fprintf(stderr, "[nanort] HIP backend unavailable: %s\n", backend_error_.c_str());
+          return false;
+        }
+        fprintf(stderr, "[nanort] HIP device %d unavailable (%s): continuing with %zu device(s)\n", devices[k], backend_error_.c_str(), k);
+        break;
+      }
+      if (k == 0)
+        ctx_ = std::shared_ptr<nrt_ctx>(raw, detail::CtxDeleter());
+      else
+        peers_.push_back(std::shared_ptr<nrt_ctx>(raw, detail::CtxDeleter()));
+      devices_.push_back(devices[k]);
+    }
+    return true;
+  }
+  // Copies share ctx_ / peers_ until one side changes what they hold (O(1): no device call, no read-back).
+  bool SharesDeviceContext() const {
+    if (ctx_.use_count() > 1) return true;
+    for (size_t k = 0; k < peers_.size(); k++)
+      if (peers_[k].use_count() > 1) return true;
+    return false;
+  }
+  // The primitives of the last built-in Build(), from the arrays it was given (`cylinder_cap`: the cylinder intersector's flag).
+  nrt_status SendPrimitives(nrt_ctx *c, bool cylinder_cap) const {
+    switch (device_prim_kind_) {
+      case 0: return detail::HipApi<T>::SetMesh(c, tri_vertices_, tri_stride_, tri_faces_, prim_count_);
+      case 1: return nrtSetSpheres_f32(c, sph_centers_, sph_radii_, prim_count_);
+      case 2: return nrtSetCylinders_f32(c, cyl_endpoints_, cyl_radii_, cyl_count_, cylinder_cap ? 1 : 0);
+      default: return NRT_ERR_INVALID;
+    }
+  }
+  // Copy-on-write (caller holds batch_mutex_): leave the contexts shared with copies to them and move to fresh ones on the
+  // same devices, holding this object's primitives; the caller then sends the tree (from the host arrays).
+  bool DetachDeviceContext(bool cylinder_cap) const {
+    const std::vector<int> devices = devices_.empty() ? DeviceList() : devices_;
+    device_tree_stale_ = true;  // (until the caller has sent the tree: a failure below leaves a state the next call retries)
+    if (!CreateContexts(devices)) return false;
+    for (size_t k = 0; k <= peers_.size(); k++) {
+      nrt_ctx *c = k == 0 ? ctx_.get() : peers_[k - 1].get();
+      if (SendPrimitives(c, cylinder_cap) != NRT_OK) {
+        backend_error_ = nrtLastError(c);
+        return false;
+      }
+    }
     return true;
   }
 #endif
@@ -2109,12 +2216,14 @@ class BVHAccel {
   void DropPendingHostTree() { __atomic_store_n(&host_tree_pending_, false, __ATOMIC_RELEASE); }
   void CopyFrom(const BVHAccel &o) {
     o.EnsureHostTree();
+    std::lock_guard<std::mutex> lock(o.batch_mutex_);  // (o's contexts may be replaced by a batch call of another thread)
     nodes_ = o.nodes_;
     indices_ = o.indices_;
     options_ = o.options_;
     stats_ = o.stats_;
     ctx_ = o.ctx_;
     peers_ = o.peers_;
+    devices_ = o.devices_;
     batch_row_len_ = o.batch_row_len_;
     device_tree_stale_ = o.device_tree_stale_;
     device_prim_kind_ = o.device_prim_kind_;
@@ -2122,6 +2231,12 @@ class BVHAccel {
     cyl_radii_ = o.cyl_radii_;
     cyl_count_ = o.cyl_count_;
     cyl_test_cap_ = o.cyl_test_cap_;
+    tri_vertices_ = o.tri_vertices_;
+    tri_stride_ = o.tri_stride_;
+    tri_faces_ = o.tri_faces_;
+    sph_centers_ = o.sph_centers_;
+    sph_radii_ = o.sph_radii_;
+    prim_count_ = o.prim_count_;
     host_tree_pending_ = false;
     pending_nodes_ = pending_indices_ = 0;
     for (int k = 0; k < 3; k++) {
@@ -2131,11 +2246,63 @@ class BVHAccel {
     backend_error_ = o.backend_error_;
     // (the staging buffers stay with their owner: they are scratch, grown on the first TraverseBatch())
   }
+  // Everything as it is, the pending read-back and the staging included; `o` is left empty (IsValid() false).
+  void MoveFrom(BVHAccel *o) noexcept {
+    nodes_ = std::move(o->nodes_);
+    indices_ = std::move(o->indices_);
+    o->nodes_.clear();
+    o->indices_.clear();
+    options_ = o->options_;
+    stats_ = o->stats_;
+    host_tree_pending_ = o->HostTreePending();
+    o->DropPendingHostTree();
+    pending_nodes_ = o->pending_nodes_;
+    pending_indices_ = o->pending_indices_;
+    for (int k = 0; k < 3; k++) {
+      root_bmin_[k] = o->root_bmin_[k];
+      root_bmax_[k] = o->root_bmax_[k];
+    }
+    ctx_ = std::move(o->ctx_);
+    peers_ = std::move(o->peers_);
+    devices_ = std::move(o->devices_);
+    o->ctx_.reset();
+    o->peers_.clear();
+    o->devices_.clear();
+    batch_row_len_ = o->batch_row_len_;
+    device_tree_stale_ = o->device_tree_stale_;
+    device_prim_kind_ = o->device_prim_kind_;
+    o->device_tree_stale_ = false;
+    o->device_prim_kind_ = -1;
+    cyl_endpoints_ = o->cyl_endpoints_;
+    cyl_radii_ = o->cyl_radii_;
+    cyl_count_ = o->cyl_count_;
+    cyl_test_cap_ = o->cyl_test_cap_;
+    tri_vertices_ = o->tri_vertices_;
+    tri_stride_ = o->tri_stride_;
+    tri_faces_ = o->tri_faces_;
+    sph_centers_ = o->sph_centers_;
+    sph_radii_ = o->sph_radii_;
+    prim_count_ = o->prim_count_;
+    o->cyl_endpoints_ = o->cyl_radii_ = NULL;
+    o->tri_vertices_ = NULL;
+    o->tri_faces_ = NULL;
+    o->sph_centers_ = o->sph_radii_ = NULL;
+    o->cyl_count_ = o->prim_count_ = 0;
+    stage_hits_ = std::move(o->stage_hits_);
+    stage_mask_ = std::move(o->stage_mask_);
+    stage_hits_cap_ = o->stage_hits_cap_;
+    stage_mask_cap_ = o->stage_mask_cap_;
+    o->stage_hits_cap_ = o->stage_mask_cap_ = 0;
+    backend_error_ = std::move(o->backend_error_);
+    o->backend_error_.clear();
+  }
   mutable bool host_tree_pending_ = false;  // the tree of the last GPU Build() has not been copied to nodes_ / indices_ yet
   uint64_t pending_nodes_ = 0, pending_indices_ = 0;
   T root_bmin_[3] = {T(0), T(0), T(0)}, root_bmax_[3] = {T(0), T(0), T(0)};
-  std::shared_ptr<nrt_ctx> ctx_;
-  std::vector<std::shared_ptr<nrt_ctx> > peers_;  // replicas on the other devices of NANORT_HIP_DEVICES
+  // (mutable: a batch call may move the object to contexts of its own, copy-on-write — DetachDeviceContext)
+  mutable std::shared_ptr<nrt_ctx> ctx_;
+  mutable std::vector<std::shared_ptr<nrt_ctx> > peers_;  // replicas on the other devices of NANORT_HIP_DEVICES
+  mutable std::vector<int> devices_;                      // the devices of ctx_, then of peers_
   size_t batch_row_len_ = 0;                      // rays per interleaved row of a multi-device TraverseBatch (0: 4096)
   mutable bool device_tree_stale_ = false;
   int device_prim_kind_ = -1;  // what the device context was built over: 0 triangles, 1 spheres, 2 cylinders, -1 nothing usable
@@ -2143,6 +2310,13 @@ class BVHAccel {
   const float *cyl_radii_ = NULL;
   unsigned int cyl_count_ = 0;
   mutable bool cyl_test_cap_ = true;
+  const T *tri_vertices_ = NULL;  // triangle / sphere primitives: what Build() was given (a detach sends them again)
+  size_t tri_stride_ = 0;
+  const unsigned int *tri_faces_ = NULL;
+  const float *sph_centers_ = NULL;
+  const float *sph_radii_ = NULL;
+  unsigned int prim_count_ = 0;
+  mutable std::mutex batch_mutex_;  // one per object, never copied: see the comment above TraverseBatch
   // TraverseBatch staging (grow-only): pinned through nrtHostAlloc, plain malloc if that fails
   mutable std::shared_ptr<void> stage_hits_, stage_mask_;
   mutable size_t stage_hits_cap_ = 0, stage_mask_cap_ = 0;

@@ -722,3 +722,19 @@ def test_parallel_host_build_gives_the_serial_tree(tmp_path):
     threads = int(out[("threads", 300000)][6])
     if threads >= 4:  # (lenient: a busy CI box)
         assert float(out[("threads", 300000)][5]) < float(out[("serial", 300000)][5]) / 1.5, out
+
+
+@pytest.mark.skipif(not hasattr(os, "sched_setaffinity"), reason="needs sched_setaffinity")
+@pytest.mark.parametrize("flags", [["-DNANORT_USE_CPP11_FEATURE", "-pthread"], ["-fopenmp", "-DNANORT_ENABLE_PARALLEL_BUILD"]])
+def test_host_threads_follow_the_cpu_affinity(tmp_path, flags):
+    """detail::HostThreads() — the worker count of the parallel host build — never exceeds the CPUs the process may run on:
+    a process pinned to one CPU (taskset, a cpuset) builds with one worker, and still gets the serial tree."""
+    src = os.path.join(ROOT, "tests", "cpp", "par_build_check.cc")
+    exe = tmp_path / "pb"
+    cxx(["-std=c++11", "-O2", "-Wall", "-Wextra"] + flags + ["-I", INC, src, "-o", str(exe)])
+    cpu = min(os.sched_getaffinity(0))
+    r = subprocess.run([str(exe), "5000"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=120,
+                       preexec_fn=lambda: os.sched_setaffinity(0, {cpu}))
+    assert r.returncode == 0 and r.stdout.startswith("ok 1"), r.stdout
+    assert r.stdout.rstrip().endswith("threads 1"), r.stdout
+    assert "hash af04bf7b70b5e7ac" in r.stdout, r.stdout  # (the serial tree of tests/test_host_header.py's 5000 spheres)
