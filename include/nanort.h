@@ -976,6 +976,7 @@ struct HipApi<float> {
   static nrt_status GetTree(nrt_ctx *c, NodePod *n, uint32_t *i) { return nrtGetTree_f32(c, n, i); }
   static nrt_status TreeBounds(nrt_ctx *c, float *lo, float *hi) { return nrtGetTreeBounds_f32(c, lo, hi); }
   static nrt_status SetTree(nrt_ctx *c, const NodePod *n, uint64_t nn, const uint32_t *i, uint64_t ni) { return nrtSetTree_f32(c, n, nn, i, ni); }
+  static nrt_status Refit(nrt_ctx *c, const float *v, size_t s) { return nrtRefit_f32(c, v, s); }
   static nrt_status Traverse(nrt_ctx *c, const RayPod *r, uint64_t n, const nrt_trace_options *o, HitPod *h, uint8_t *m) {
     return nrtTraverseBatch_f32(c, r, n, o, h, m);
   }
@@ -1015,6 +1016,7 @@ struct HipApi<double> {
   static nrt_status GetTree(nrt_ctx *c, NodePod *n, uint32_t *i) { return nrtGetTree_f64(c, n, i); }
   static nrt_status TreeBounds(nrt_ctx *c, double *lo, double *hi) { return nrtGetTreeBounds_f64(c, lo, hi); }
   static nrt_status SetTree(nrt_ctx *c, const NodePod *n, uint64_t nn, const uint32_t *i, uint64_t ni) { return nrtSetTree_f64(c, n, nn, i, ni); }
+  static nrt_status Refit(nrt_ctx *c, const double *v, size_t s) { return nrtRefit_f64(c, v, s); }
   static nrt_status Traverse(nrt_ctx *c, const RayPod *r, uint64_t n, const nrt_trace_options *o, HitPod *h, uint8_t *m) {
     return nrtTraverseBatch_f64(c, r, n, o, h, m);
   }
@@ -1088,6 +1090,92 @@ class BVHAccel {
   }
 
   BVHBuildStatistics GetStatistics() const { return stats_; }
+
+  // Refit: the tree's boxes recomputed bottom-up for primitives that moved, its topology and index array kept (no rebuild).
+  // Each reachable leaf's box becomes the union of its primitives' BoundingBox(&bmin, &bmax, prim_index), each reachable
+  // branch's the union of its two children's (an empty leaf: {+max, -max}); records the walk from the root never reaches keep
+  // theirs.  A refit tree may trace slower than a fresh Build() over the same primitives: rebuild when they moved far.
+  // Returns false (nothing changed) when there is no tree or the tree is malformed (a child or leaf slot out of range, a
+  // record reached twice).
+  template <class Prim>
+  bool Refit(const Prim &p) {
+#ifdef NANORT_USE_HIP_BACKEND
+    if (ctx_ && !device_tree_stale_) {  // (the GPU holds this tree: refit it there — Refit(TriangleMesh) — or rebuild)
+      backend_error_ = "Refit: this tree was built on the GPU over built-in primitives; refit a triangle mesh with Refit(TriangleMesh)";
+      return false;
+    }
+#endif
+    return RefitHost(p);
+  }
+#ifdef NANORT_USE_HIP_BACKEND
+  // The GPU refit (nrtRefit, include/nanort_hip.h) of every context this object holds, the NANORT_HIP_DEVICES replicas
+  // included, from the mesh's vertices and stride; its faces must equal the built ones.  An object that shares its contexts
+  // with a copy first moves to contexts of its own (copy-on-write: the copy keeps its tree and positions) and keeps the new
+  // vertex array, as Build() does: it must outlive the accel.  The host copy of the tree is read back on the next host access.
+  bool Refit(const TriangleMesh<T> &mesh) {
+    typedef detail::HipApi<T> Api;
+    if (!ctx_) return RefitHost(mesh);  // (a tree built on the host or Load()ed before any GPU Build())
+    std::lock_guard<std::mutex> lock(batch_mutex_);
+    if (device_prim_kind_ == 1 || device_prim_kind_ == 2) {
+      backend_error_ = device_prim_kind_ == 1 ? "Refit: sphere trees do not refit on the GPU (Build() again)"
+                                              : "Refit: cylinder trees do not refit on the GPU (Build() again)";
+      return false;
+    }
+    if (device_prim_kind_ != 0) {
+      backend_error_ = "Refit: no triangle tree (Build() with TriangleMesh/TriangleSAHPred first)";
+      return false;
+    }
+    if (mesh.GetFaces() != tri_faces_ &&
+        (!mesh.GetFaces() || !tri_faces_ || std::memcmp(mesh.GetFaces(), tri_faces_, 3 * sizeof(unsigned int) * prim_count_) != 0)) {
+      backend_error_ = "Refit: the mesh's faces differ from the ones the tree was built over";
+      return false;
+    }
+    if (SharesDeviceContext()) {  // copy-on-write: the copies keep the shared contexts, their tree and their positions
+      EnsureHostTree();
+      if (nodes_.empty()) {
+        backend_error_ = "Refit: empty tree";
+        return false;
+      }
+      if (!DetachDeviceContext(cyl_test_cap_)) return false;
+    }
+    if (!DeviceTreeReady(0)) return false;  // (a Load()ed tree is uploaded first)
+    // The primary first: its refusal leaves everything as it was (a device error drops its tree: Build() again).  The
+    // replicas pass the same checks, so only a device error can stop one: the object then traces on the primary alone, as
+    // after a replica's failed build, and never on a replica that still holds the old boxes.
+    if (Api::Refit(ctx_.get(), mesh.GetVertices(), mesh.GetVertexStrideBytes()) != NRT_OK) {
+      backend_error_ = nrtLastError(ctx_.get());
+      return false;
+    }
+    for (size_t k = 0; k < peers_.size(); k++) {
+      if (Api::Refit(peers_[k].get(), mesh.GetVertices(), mesh.GetVertexStrideBytes()) != NRT_OK) {
+        backend_error_ = nrtLastError(peers_[k].get());
+        fprintf(stderr, "[nanort] HIP refit of replica %zu failed (%s): tracing on one device\n", k + 1, backend_error_.c_str());
+        peers_.clear();
+        devices_.resize(1);
+        break;
+      }
+    }
+    tri_vertices_ = mesh.GetVertices();  // (a later detach sends these)
+    tri_stride_ = mesh.GetVertexStrideBytes();
+    uint64_t nn = 0, ni = 0;
+    if (nrtTreeSize(ctx_.get(), &nn, &ni) != NRT_OK || Api::TreeBounds(ctx_.get(), root_bmin_, root_bmax_) != NRT_OK) {
+      backend_error_ = nrtLastError(ctx_.get());
+      return false;
+    }
+    pending_nodes_ = nn;
+    pending_indices_ = ni;
+    __atomic_store_n(&host_tree_pending_, true, __ATOMIC_RELEASE);  // GetNodes(), Traverse(), Dump() and copies read the refit boxes
+    return true;
+  }
+  bool Refit(const SphereGeometry &) {
+    backend_error_ = "Refit: sphere trees do not refit on the GPU (Build() again)";
+    return false;
+  }
+  bool Refit(const CylinderGeometry &) {
+    backend_error_ = "Refit: cylinder trees do not refit on the GPU (Build() again)";
+    return false;
+  }
+#endif
 
 #if defined(NANORT_ENABLE_SERIALIZATION)
   // Raw host-endian dump: size_t count, nodes, size_t count, indices (ref nanort.h:2164-2276).
@@ -1711,6 +1799,64 @@ class BVHAccel {
 #endif
 
  private:
+  // Host refit over nodes_ / indices_.  The walk from the root is validated first (children and leaf slots in range, no record
+  // reached twice) and yields the reachable records in post-order; only then are boxes written, so a malformed Load()ed tree
+  // is refused with nodes_ unchanged.
+  template <class Prim>
+  bool RefitHost(const Prim &prim) {
+    EnsureHostTree();
+    const size_t nn = nodes_.size();
+    if (nn == 0) return false;
+    std::vector<unsigned int> order;  // reachable records, children before their parent
+    std::vector<unsigned char> seen(nn, 0);
+    std::vector<std::pair<unsigned int, bool> > st(1, std::make_pair(0u, false));
+    while (!st.empty()) {
+      const std::pair<unsigned int, bool> e = st.back();
+      st.pop_back();
+      const BVHNode<T> &n = nodes_[e.first];
+      if (e.second) {
+        order.push_back(e.first);
+        continue;
+      }
+      if (seen[e.first]) return false;
+      seen[e.first] = 1;
+      if (n.flag == 0) {
+        if (n.data[0] >= nn || n.data[1] >= nn) return false;
+        st.push_back(std::make_pair(e.first, true));
+        st.push_back(std::make_pair(n.data[1], false));
+        st.push_back(std::make_pair(n.data[0], false));
+      } else {
+        if (static_cast<size_t>(n.data[1]) + n.data[0] > indices_.size()) return false;
+        order.push_back(e.first);
+      }
+    }
+    for (size_t i = 0; i < order.size(); i++) {
+      BVHNode<T> &n = nodes_[order[i]];
+      if (n.flag == 0) {
+        const BVHNode<T> &a = nodes_[n.data[0]], &b = nodes_[n.data[1]];
+        for (int k = 0; k < 3; k++) {
+          n.bmin[k] = std::min(a.bmin[k], b.bmin[k]);
+          n.bmax[k] = std::max(a.bmax[k], b.bmax[k]);
+        }
+      } else {
+        BBox<T> acc;
+        for (unsigned int j = 0; j < n.data[0]; j++) {
+          real3<T> lo, hi;
+          prim.BoundingBox(&lo, &hi, indices_[n.data[1] + j]);
+          for (int k = 0; k < 3; k++) {
+            acc.bmin[k] = std::min(acc.bmin[k], lo[k]);
+            acc.bmax[k] = std::max(acc.bmax[k], hi[k]);
+          }
+        }
+        for (int k = 0; k < 3; k++) {
+          n.bmin[k] = acc.bmin[k];
+          n.bmax[k] = acc.bmax[k];
+        }
+      }
+    }
+    return true;
+  }
+
   // ---- generic host builder: binned SAH over all three axes, iterative, pre-order ----
   struct Pending {
     unsigned int lo, hi, depth, parent;

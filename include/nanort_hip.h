@@ -326,6 +326,37 @@ NRT_API nrt_status nrtSetTree_f32(nrt_ctx *ctx, const nrt_node_f32 *nodes, uint6
 NRT_API nrt_status nrtSetTree_f64(nrt_ctx *ctx, const nrt_node_f64 *nodes, uint64_t num_nodes,
                                   const uint32_t *indices, uint64_t num_indices);
 
+/* ---- refit: the tree's boxes recomputed from moved vertices, its topology kept ------------------------------
+ * For a mesh whose vertices move while its faces stay fixed: instead of nrtSetMesh + nrtBuild every frame.  Contract, on a
+ * triangle context of the call's precision that holds a tree (from nrtBuild_* or nrtSetTree_*):
+ *   1. Input: the context's num_verts vertices (max(faces) + 1, fixed at nrtSetMesh), vertex i at byte offset
+ *      i * vertex_stride_bytes, xyz first (get_vertex_addr, nanort.h:467-472).  Faces are not passed: the context keeps its own.
+ *   2. Result: the context's vertex positions become the new ones (a later nrtBuild builds over them).  Every node record's
+ *      flag, axis and data[] and the index array stay byte-identical.  Each reachable leaf's box is the min / max over every
+ *      coordinate of its triangles; each reachable branch's box is the min / max of its two children's boxes; an empty leaf
+ *      (adopted trees only) gets {+max, -max} and adds nothing to its parent.  Records the walk from the root never reaches
+ *      are left untouched.  The boxes never depend on scheduling; refit with the vertices of the build reproduces its boxes.
+ *      nrtGetTree_* / nrtGetTreeBounds_* return the refit tree.  Build statistics and nrtLastBuildMs do not change.
+ *   3. A committed nrt_scene that instances this context refuses to trace until it is committed again (its top-level boxes
+ *      are stale), as after nrtBuild.
+ *   4. Ordering: the call-order rules of nrtBuild (not re-entrant with the primitive, build or tree calls on one context).
+ *      Both forms first wait on the host for the context's traversal launches in flight.  nrtRefit_* returns when the refit
+ *      is complete.  nrtRefitDevice_* reads `d_vertices` (device memory; never staged through the host) and enqueues
+ *      everything on `hip_stream` (a hipStream_t; NULL = the default stream) and returns without synchronising: the caller
+ *      keeps d_vertices unchanged until the stream reaches the refit.  Every traversal call issued after a refit, on any
+ *      stream and through any entry point, is ordered after it.
+ *   5. Cost: the first refit after a tree changes builds the tree's level plan on the device; in the steady state (same tree,
+ *      repeated frames) a refit allocates nothing.
+ * Refusals write nothing (nrtLastError gives the reason): NRT_ERR_INVALID for a NULL context or vertices, no tree (a fresh
+ * context included), a sphere or cylinder context, a stride below 3 * sizeof(T), and (Device form) a stride or pointer not
+ * aligned to sizeof(T); NRT_ERR_PRECISION when the context holds primitives of the other precision.  The caller's block must
+ * hold all num_verts rows: (num_verts - 1) * stride + 3 * sizeof(T) bytes are read.  NRT_ERR_DEVICE (a HIP error once the
+ * rewrite has started): the context drops its tree and its primitives rather than keep a half-refit tree; set the mesh again. */
+NRT_API nrt_status nrtRefit_f32(nrt_ctx *ctx, const float *vertices, size_t vertex_stride_bytes);
+NRT_API nrt_status nrtRefit_f64(nrt_ctx *ctx, const double *vertices, size_t vertex_stride_bytes);
+NRT_API nrt_status nrtRefitDevice_f32(nrt_ctx *ctx, const float *d_vertices, size_t vertex_stride_bytes, void *hip_stream);
+NRT_API nrt_status nrtRefitDevice_f64(nrt_ctx *ctx, const double *d_vertices, size_t vertex_stride_bytes, void *hip_stream);
+
 /* ---- traverse: replaces N calls of BVHAccel<T>::Traverse with a
  * TriangleIntersector (nanort.h:757-759, 2487-2556, 1014-1229) -------------
  * Closest hit per ray, same arithmetic as the reference (no contraction,

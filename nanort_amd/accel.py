@@ -226,6 +226,61 @@ class BVHAccel:
             getattr(self._L, "nrtSetTree_" + self._s)(self._h, _p(nodes), nodes.shape[0], _p(indices), indices.shape[0])
         )
 
+    def _refit_rows(self):
+        """The context's vertex count (max(faces) + 1 of the mesh last set), or None when no triangle mesh is set (the library
+        then refuses the refit before it reads any vertex)."""
+        m = self._mesh
+        if not isinstance(m, TriangleMesh):
+            return None
+        return int(m.faces.max()) + 1 if m.num_faces else 0
+
+    def Refit(self, vertices, vertex_stride_bytes=None):
+        """New positions for the mesh's vertices, same faces and topology (include/nanort_hip.h, nrtRefit): the tree's boxes are
+        recomputed bottom-up.  `vertices`: a numpy array of the accel's precision holding at least the context's vertex count of
+        rows (max(faces) + 1), xyz first in each row; the row stride defaults to the array's own.  With an explicit
+        `vertex_stride_bytes` the array is a C-contiguous block of at least (nv - 1) * stride + 3 * itemsize bytes."""
+        v = np.asarray(vertices)
+        if v.dtype != self.real:
+            raise TypeError("vertex precision %s != accel precision %s" % (v.dtype, self.real))
+        nv = self._refit_rows()
+        if vertex_stride_bytes is None:
+            v = np.ascontiguousarray(v.reshape(v.shape[0], -1) if v.ndim > 1 else v.reshape(-1, 3))
+            if v.shape[1] < 3:
+                raise ValueError("vertices must be [nv, k >= 3]")
+            if nv is not None and v.shape[0] < nv:
+                raise ValueError("vertices hold %d rows; the mesh has %d vertices" % (v.shape[0], nv))
+            vertex_stride_bytes = v.strides[0]
+        else:
+            if not v.flags["C_CONTIGUOUS"]:
+                raise ValueError("an explicit vertex_stride_bytes needs a C-contiguous array")
+            need = (nv - 1) * int(vertex_stride_bytes) + 3 * v.itemsize if nv else 0
+            if nv is not None and v.nbytes < need:
+                raise ValueError("vertices hold %d bytes; %d vertices at stride %d need %d" % (v.nbytes, nv, int(vertex_stride_bytes), need))
+        self._check(getattr(self._L, "nrtRefit_" + self._s)(self._h, _p(v), int(vertex_stride_bytes)))
+
+    def RefitDevice(self, d_vertices, stream=None):
+        """Refit from a torch tensor on the accel's device (nrtRefitDevice): shape [nv', k >= 3] with nv' at least the mesh's
+        vertex count and stride(1) == 1 (the row stride is stride(0)), dtype of the accel's precision.  Asynchronous on `stream`
+        (default: torch's current stream); keep the tensor unchanged until the stream reaches the refit."""
+        import torch
+
+        want = torch.float32 if self.real == np.float32 else torch.float64
+        if d_vertices.dtype != want:
+            raise TypeError("vertex dtype %s != accel precision %s" % (d_vertices.dtype, self.real))
+        if d_vertices.dim() != 2 or d_vertices.shape[1] < 3 or d_vertices.stride(1) != 1:
+            raise ValueError("vertices must be [nv, k >= 3] with stride(1) == 1")
+        nv = self._refit_rows()
+        if nv is not None and d_vertices.shape[0] < nv:
+            raise ValueError("vertices hold %d rows; the mesh has %d vertices" % (d_vertices.shape[0], nv))
+        if d_vertices.device.type != "cuda" or d_vertices.device.index != self.device:
+            raise ValueError("vertices must live on cuda:%d" % self.device)
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+        elif hasattr(stream, "cuda_stream"):
+            stream = stream.cuda_stream
+        stride = d_vertices.stride(0) * d_vertices.element_size()
+        self._check(getattr(self._L, "nrtRefitDevice_" + self._s)(self._h, d_vertices.data_ptr(), stride, stream))
+
     # -- traverse -----------------------------------------------------------
     def TraverseBatch(self, rays, options=None):
         """N x BVHAccel::Traverse (reference nanort.h:2487-2556). Returns (hits, mask)."""

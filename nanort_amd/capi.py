@@ -28,6 +28,7 @@ SYMBOLS = [
     "nrtTraverseCountDevice_f32", "nrtTraverseCountDevice_f64",
     "nrtOccludedBatch_f32", "nrtOccludedBatch_f64", "nrtOccludedBatchDevice_f32", "nrtOccludedBatchDevice_f64",
     "nrtMultiHitTraverseBatch_f32", "nrtMultiHitTraverseBatch_f64", "nrtMultiHitTraverseBatchDevice_f32", "nrtMultiHitTraverseBatchDevice_f64",
+    "nrtRefit_f32", "nrtRefit_f64", "nrtRefitDevice_f32", "nrtRefitDevice_f64",
     "nrtLastTraverseMs", "nrtSetLaunchTiming", "nrtSetTunable", "nrtGetTunable", "nrtLastBuildMs", "nrtLastKernelName", "nrtHostAlloc", "nrtHostFree",
     "nrtGroupUniqueId", "nrtGroupCreate", "nrtGroupCreateRanked", "nrtGroupDestroy", "nrtGroupLastError", "nrtGroupSetTunable", "nrtGroupInfo",
     "nrtGroupTileRays", "nrtGroupTraverseGather_f32", "nrtGroupTraverseGather_f64", "nrtGroupTraverseGatherTiles_f32", "nrtGroupTraverseGatherTiles_f64", "nrtGroupSynchronize", "nrtGroupLastTraffic",
@@ -126,6 +127,12 @@ def lib():
         f.restype = i32
         f = getattr(L, "nrtMultiHitTraverseBatchDevice_" + sfx)
         f.argtypes = [vp, vp, u64, u32, vp, vp, vp, vp]
+        f.restype = i32
+        f = getattr(L, "nrtRefit_" + sfx)
+        f.argtypes = [vp, vp, sz]
+        f.restype = i32
+        f = getattr(L, "nrtRefitDevice_" + sfx)
+        f.argtypes = [vp, vp, sz, vp]
         f.restype = i32
     L.nrtSetSpheres_f32.argtypes = [vp, vp, vp, u32]
     L.nrtSetSpheres_f32.restype = i32

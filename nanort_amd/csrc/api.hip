@@ -61,6 +61,15 @@ hipError_t gpu_build(hipStream_t s, const T *d_verts, const uint32_t *d_faces, c
                      uint32_t min_leaf, uint32_t max_depth, uint32_t bin_size, unsigned build_flags, // (bit 0: Morton pre-pass, bit 1: one-node-per-step subtree kernel)
                      DevBuf *workspace, DevBuf *nodes_buf, DevBuf *indices_buf, void *pinned, hipEvent_t ev, std::string *err);
 hipError_t gpu_build_result(const void *pinned, hipEvent_t ev, BuildResult *res);
+// (refit.hip) the per-tree level plan of a refit, and one refit over it
+size_t refit_plan_bytes(uint32_t tree_depth, uint64_t num_nodes);
+template <typename T>
+hipError_t launch_refit_plan(const typename Wire<T>::Node *nodes, uint64_t num_nodes, uint32_t num_branch_records, uint32_t tree_depth,
+                             uint32_t root_is_branch, uint32_t *plan, hipStream_t s);
+template <typename T>
+hipError_t launch_refit(const void *src, size_t stride, bool aligned, uint32_t nv, T *verts, const uint32_t *faces, const uint32_t *indices,
+                        typename Wire<T>::Node *nodes, uint64_t num_nodes, uint32_t num_branch_records, uint32_t tree_depth,
+                        const uint32_t *plan, hipStream_t s);
 hipError_t launch_cylinder_segments(const float *verts, const float *radii, const uint32_t *seg_off, uint32_t n, float *seg_verts,
                                     float *seg_radii, uint32_t *seg_prim, hipStream_t s);
 } // namespace nrt
@@ -105,7 +114,14 @@ struct nrt_ctx {
   uint32_t root_is_branch = 0; // node 0 has flag == 0
   uint32_t tree_nested = 1;    // every child box lies inside its parent's (always true of trees built here; checked for adopted ones)
   nrt_build_stats stats = {0, 0, 0, 0.f};
-  uint64_t generation = 0; // bumped whenever the tree or the primitives are replaced (free_tree)
+  uint64_t generation = 0; // bumped whenever the tree or the primitives are replaced (free_tree) or refit
+  // refit (refit.hip): the level plan of the current tree, built on the device by the first refit after the tree changed
+  DevBuf b_refit_plan, b_refit_stage; // (stage: the host form's upload of the caller's vertex block)
+  bool refit_planned = false;
+  // a Device refit enqueued on a caller's stream: every later traversal launch waits for ev_refit on the device until the
+  // host sees it complete, every host-side reader of the tree (nrtGetTree, a rebuild, a scene commit) waits for it on the host
+  hipEvent_t ev_refit = nullptr;
+  bool refit_pending = false;
 
   // traversal scratch.  Every launch owns one LaunchSlot (work cursors + overflow stacks) until it
   // completes, so launches issued on different streams may overlap on the GPU: the drain tail of one
@@ -250,8 +266,37 @@ static hipError_t slot_done(nrt_ctx *c, nrt_ctx::LaunchSlot &sl) {
   return sl.done ? hipEventSynchronize(sl.done) : hipSuccess;
 }
 
+// The host waits for a Device refit still in flight (before anything reads or rewrites the tree on the host's behalf).
+static hipError_t refit_host_wait_locked(nrt_ctx *c) { // (caller holds launch_mutex)
+  if (!c->refit_pending) return hipSuccess;
+  hipError_t e = hipEventSynchronize(c->ev_refit);
+  if (e != hipSuccess) return e;
+  c->refit_pending = false;
+  return hipSuccess;
+}
+static hipError_t refit_host_wait(nrt_ctx *c) {
+  std::lock_guard<std::mutex> lock(c->launch_mutex);
+  return refit_host_wait_locked(c);
+}
+
+// A traversal launch on stream `s` is ordered after a Device refit in flight (under launch_mutex).  Every launch waits on the
+// event until the host sees it complete — not once per stream handle: a destroyed stream's handle may come back as a new
+// stream that has never waited.  (A wait on the same stream again costs one barrier packet.)
+static hipError_t refit_stream_wait(nrt_ctx *c, hipStream_t s) {
+  if (!c->refit_pending) return hipSuccess;
+  const hipError_t q = hipEventQuery(c->ev_refit);
+  if (q == hipSuccess) { // (complete: nobody has to wait any more)
+    c->refit_pending = false;
+    return hipSuccess;
+  }
+  if (q != hipErrorNotReady) return q;
+  return hipStreamWaitEvent(s, c->ev_refit, 0);
+}
+
 static hipError_t wait_for_launches(nrt_ctx *c) {
   std::lock_guard<std::mutex> lock(c->launch_mutex);
+  hipError_t re = refit_host_wait_locked(c);
+  if (re != hipSuccess) return re;
   for (nrt_ctx::LaunchSlot &sl : c->slots) {
     hipError_t e = slot_done(c, sl);
     if (e != hipSuccess) return e;
@@ -269,6 +314,7 @@ static void free_tree(nrt_ctx *c) {
   c->d_tris = nullptr;
   c->num_nodes = c->num_indices = 0;
   c->tree_depth = 0;
+  c->refit_planned = false;
 }
 
 static void free_mesh(nrt_ctx *c) {
@@ -380,6 +426,7 @@ nrt_status nrtCreate(int device, nrt_ctx **out) {
       (e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)) != hipSuccess ||
       (e = hipEventCreate(&c->ev_b0)) != hipSuccess || (e = hipEventCreate(&c->ev_b1)) != hipSuccess ||
       (e = hipEventCreateWithFlags(&c->ev_build_state, hipEventDisableTiming)) != hipSuccess ||
+      (e = hipEventCreateWithFlags(&c->ev_refit, hipEventDisableTiming)) != hipSuccess ||
       (e = hipHostMalloc(&c->build_state, kBuildPinnedBytes, hipHostMallocDefault)) != hipSuccess ||
       (e = hipMalloc((void **)&c->d_counters, 16 * sizeof(unsigned long long))) != hipSuccess) {
     fail(nullptr, NRT_ERR_DEVICE, "nrtCreate: %s", hipGetErrorString(e));
@@ -425,6 +472,7 @@ void nrtDestroy(nrt_ctx *c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
+  if (c->ev_refit) (void)refit_host_wait_locked(c);
   for (nrt_ctx::LaunchSlot &sl : c->slots) { // launches still in flight on the caller's streams
     if (sl.h_done || sl.done) (void)slot_done(c, sl);
     if (sl.d_cursor) (void)hipFree(sl.d_cursor);
@@ -440,12 +488,12 @@ void nrtDestroy(nrt_ctx *c) {
   }
   free_tree(c);
   free_mesh(c);
-  DevBuf *bufs[] = {&c->b_verts, &c->b_radii, &c->b_faces, &c->st_rays, &c->st_hits, &c->st_mask, &c->b_nodes, &c->b_indices, &c->b_tris, &c->b_wide, &c->b_wide4, &c->b_wide_scratch, &c->b_build_ws, &c->b_wave_clock, &c->b_seg_verts, &c->b_seg_radii, &c->b_seg_prim, &c->b_seg_off};
+  DevBuf *bufs[] = {&c->b_verts, &c->b_radii, &c->b_faces, &c->st_rays, &c->st_hits, &c->st_mask, &c->b_nodes, &c->b_indices, &c->b_tris, &c->b_wide, &c->b_wide4, &c->b_wide_scratch, &c->b_build_ws, &c->b_wave_clock, &c->b_seg_verts, &c->b_seg_radii, &c->b_seg_prim, &c->b_seg_off, &c->b_refit_plan, &c->b_refit_stage};
   for (DevBuf *b : bufs)
     if (b->p) (void)hipFree(b->p);
   if (c->d_counters) (void)hipFree(c->d_counters);
   if (c->build_state) (void)hipHostFree(c->build_state);
-  hipEvent_t evs[] = {c->ev_b0, c->ev_b1, c->ev_build_state};
+  hipEvent_t evs[] = {c->ev_b0, c->ev_b1, c->ev_build_state, c->ev_refit};
   for (hipEvent_t ev : evs)
     if (ev) (void)hipEventDestroy(ev);
   for (int k = 0; k < 2; k++)
@@ -614,30 +662,30 @@ static nrt_status set_cylinders(nrt_ctx *c, const float *endpoints, const float 
 // Private traversal layout of a tree, in two steps so that a build can enqueue the first while the tree's size is still
 // on its way to the host: (1) leaf-ordered primitive records (needs the index array only), (2) WideNode / Wide4Node arrays.
 template <typename T>
-static nrt_status finish_leaf_records(nrt_ctx *c) {
+static nrt_status finish_leaf_records(nrt_ctx *c, hipStream_t s) {
   nrt_status st;
   // leaf-ordered primitive records for the traversal kernel
   if (c->prim_kind == kPrimSpheres) {
     if ((st = ensure(c, c->b_tris, std::max<size_t>(1, c->num_indices) * sizeof(LeafSphere<T>)))) return st;
     c->d_tris = c->b_tris.p;
     HIPCHK(c, launch_gather_leaf_spheres<T>(c->d_indices, (const T *)c->d_verts, (const T *)c->d_radii,
-                                            (LeafSphere<T> *)c->d_tris, (uint32_t)c->num_indices, c->stream));
+                                            (LeafSphere<T> *)c->d_tris, (uint32_t)c->num_indices, s));
   } else if (c->prim_kind == kPrimCylinders) {
     if ((st = ensure(c, c->b_tris, std::max<size_t>(1, c->num_indices) * sizeof(LeafCylinder<T>)))) return st;
     c->d_tris = c->b_tris.p;
     HIPCHK(c, launch_gather_leaf_cylinders<T>(c->d_indices, (const T *)c->d_verts, (const T *)c->d_radii,
-                                              (LeafCylinder<T> *)c->d_tris, (uint32_t)c->num_indices, c->stream));
+                                              (LeafCylinder<T> *)c->d_tris, (uint32_t)c->num_indices, s));
   } else {
     if ((st = ensure(c, c->b_tris, std::max<size_t>(1, c->num_indices) * sizeof(LeafTri<T>)))) return st;
     c->d_tris = c->b_tris.p;
     HIPCHK(c, launch_gather_leaf_tris<T>(c->d_indices, c->d_faces, (const T *)c->d_verts,
-                                         (LeafTri<T> *)c->d_tris, (uint32_t)c->num_indices, c->stream));
+                                         (LeafTri<T> *)c->d_tris, (uint32_t)c->num_indices, s));
   }
   return NRT_OK;
 }
 
 template <typename T>
-static nrt_status finish_wide(nrt_ctx *c) {
+static nrt_status finish_wide(nrt_ctx *c, hipStream_t s) {
   nrt_status st;
   // one WideNode per record with flag == 0 (a loaded tree may carry unreachable ones)
   if ((st = ensure(c, c->b_wide, std::max<size_t>(1, c->num_branch_records) * sizeof(WideNode<T>)))) return st;
@@ -655,14 +703,14 @@ static nrt_status finish_wide(nrt_ctx *c) {
   }
   HIPCHK(c, launch_make_wide<T>((const typename Wire<T>::Node *)c->d_nodes, (uint32_t)c->num_nodes, c->packed_leaves,
                                 (uint32_t *)c->b_wide_scratch.p, (WideNode<T> *)c->d_wide, (Wide4Node<T> *)c->d_wide4,
-                                c->wide_scramble ? c->num_branch_records : 0u, c->stream));
+                                c->wide_scramble ? c->num_branch_records : 0u, s));
   return NRT_OK;
 }
 
 template <typename T>
-static nrt_status finish_tree(nrt_ctx *c) {
-  nrt_status st = finish_leaf_records<T>(c);
-  return st ? st : finish_wide<T>(c);
+static nrt_status finish_tree(nrt_ctx *c, hipStream_t s) {
+  nrt_status st = finish_leaf_records<T>(c, s);
+  return st ? st : finish_wide<T>(c, s);
 }
 
 template <typename T>
@@ -729,7 +777,7 @@ static nrt_status set_tree(nrt_ctx *c, const typename Wire<T>::Node *nodes, uint
   c->d_indices = (uint32_t *)c->b_indices.p;
   HIPCHK(c, hipMemcpy(c->d_nodes, nodes, num_nodes * sizeof(typename Wire<T>::Node), hipMemcpyHostToDevice));
   HIPCHK(c, hipMemcpy(c->d_indices, indices, num_indices * sizeof(uint32_t), hipMemcpyHostToDevice));
-  if ((st = finish_tree<T>(c))) return st;
+  if ((st = finish_tree<T>(c, c->stream))) return st;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return NRT_OK;
 }
@@ -741,6 +789,7 @@ static nrt_status get_tree(nrt_ctx *c, typename Wire<T>::Node *nodes_out, uint32
   if (!c->d_nodes) return fail(c, NRT_ERR_INVALID, "nrtGetTree: no tree");
   NRT_RANGE("nrtGetTree (read-back)");
   HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, refit_host_wait(c));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (nodes_out)
     HIPCHK(c, hipMemcpy(nodes_out, c->d_nodes, c->num_nodes * sizeof(typename Wire<T>::Node), hipMemcpyDeviceToHost));
@@ -755,6 +804,7 @@ static nrt_status get_tree_bounds(nrt_ctx *c, T *bmin, T *bmax) {
   if (c->prec != (int)sizeof(T)) return fail(c, NRT_ERR_PRECISION, "nrtGetTreeBounds: precision mismatch");
   if (!c->d_nodes) return fail(c, NRT_ERR_INVALID, "nrtGetTreeBounds: no tree");
   HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, refit_host_wait(c));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   T box[6]; // BVHNode<T> starts with bmin[3], bmax[3] (nanort.h:498-550)
   HIPCHK(c, hipMemcpy(box, c->d_nodes, sizeof(box), hipMemcpyDeviceToHost));
@@ -801,7 +851,7 @@ static nrt_status build(nrt_ctx *c, const typename Wire<T>::BuildOptions *opt, n
   c->d_indices = (uint32_t *)c->b_indices.p;
   c->num_indices = build_n;
   NRT_RANGE_PUSH("build: leaf-ordered primitive records");
-  nrt_status fst = finish_leaf_records<T>(c);
+  nrt_status fst = finish_leaf_records<T>(c, c->stream);
   NRT_RANGE_POP();
   if (fst) {
     free_tree(c); // (no half-built tree is left behind: a later traversal call then reports "no tree")
@@ -819,7 +869,7 @@ static nrt_status build(nrt_ctx *c, const typename Wire<T>::BuildOptions *opt, n
   c->min_leaf_count = 1; // the GPU builder never emits an empty leaf
   c->tree_nested = 1;    // a branch's box is the exact union of its children's
   NRT_RANGE_PUSH("build: WideNode / Wide4Node records");
-  fst = finish_wide<T>(c); // WideNode arrays: part of the build
+  fst = finish_wide<T>(c, c->stream); // WideNode arrays: part of the build
   NRT_RANGE_POP();
   if (fst) {
     free_tree(c);
@@ -839,12 +889,74 @@ static nrt_status build(nrt_ctx *c, const typename Wire<T>::BuildOptions *opt, n
   return NRT_OK;
 }
 
+// ---------------------------------------------------------------------------
+// refit (refit.hip): new vertex positions, the same topology
+// ---------------------------------------------------------------------------
+// `device`: `vertices` is device memory read by the gather kernel, and the call returns once everything is enqueued on `s`;
+// else the caller's vertex block is uploaded into b_refit_stage first and the call returns when the refit is complete.
+template <typename T>
+static nrt_status refit(nrt_ctx *c, const T *vertices, size_t stride, bool device, hipStream_t s) {
+  const char *fn = device ? "nrtRefitDevice" : "nrtRefit";
+  if (!c) return NRT_ERR_INVALID;
+  if (!vertices) return fail(c, NRT_ERR_INVALID, "%s: NULL vertices", fn);
+  if (c->prec != 0 && c->prec != (int)sizeof(T))
+    return fail(c, NRT_ERR_PRECISION, "%s: the context holds %s primitives", fn, c->prec == 8 ? "f64" : "f32");
+  if (c->prim_kind != kPrimTriangles) return fail(c, NRT_ERR_INVALID, "%s: only triangle meshes refit (this context holds %s)", fn,
+                                                  c->prim_kind == kPrimSpheres ? "spheres" : "cylinders");
+  if (!c->d_nodes) return fail(c, NRT_ERR_INVALID, "%s: no tree (call nrtBuild or nrtSetTree)", fn);
+  if (stride < 3 * sizeof(T)) return fail(c, NRT_ERR_INVALID, "%s: vertex stride %zu < %zu", fn, stride, 3 * sizeof(T));
+  if (device && (stride % sizeof(T) != 0 || (uintptr_t)vertices % sizeof(T) != 0))
+    return fail(c, NRT_ERR_INVALID, "%s: vertex stride %zu or pointer not aligned to %zu bytes", fn, stride, sizeof(T));
+  NRT_RANGE("nrtRefit");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, wait_for_launches(c)); // (launches in flight read the arrays the refit rewrites; also a previous Device refit)
+  if (!device) s = c->stream;
+  nrt_status st = NRT_OK;
+  const uint32_t nv = c->num_verts;
+  const size_t block = nv ? (size_t)(nv - 1) * stride + 3 * sizeof(T) : 0;
+  const void *src = vertices;
+  if (!device && nv) {
+    if ((st = ensure(c, c->b_refit_stage, block))) return st;
+    HIPCHK(c, hipMemcpyAsync(c->b_refit_stage.p, vertices, block, hipMemcpyHostToDevice, s));
+    src = c->b_refit_stage.p;
+  }
+  if (!c->refit_planned) { // (first refit of this tree: its level plan, on the device; the tree is only read)
+    if ((st = ensure(c, c->b_refit_plan, refit_plan_bytes(c->tree_depth, c->num_nodes)))) return st;
+    HIPCHK(c, launch_refit_plan<T>((const typename Wire<T>::Node *)c->d_nodes, c->num_nodes, c->num_branch_records, c->tree_depth,
+                                   c->root_is_branch, (uint32_t *)c->b_refit_plan.p, s));
+    c->refit_planned = true;
+  }
+  // From here on the vertices, the boxes and the leaf / wide records are being rewritten: a device error leaves no half-refit
+  // tree behind — the context drops its tree and its primitives (free_tree bumps generation), as a failed build drops its tree.
+  hipError_t e = launch_refit<T>(src, stride, stride % sizeof(T) == 0, nv, (T *)c->d_verts, c->d_faces, c->d_indices,
+                                 (typename Wire<T>::Node *)c->d_nodes, c->num_nodes, c->num_branch_records, c->tree_depth,
+                                 (const uint32_t *)c->b_refit_plan.p, s);
+  // LeafTri / WideNode / Wide4Node from the new boxes and positions, as a build derives them; every box now lies inside its parent's
+  c->tree_nested = 1;
+  if (e == hipSuccess && (st = finish_tree<T>(c, s))) e = hipErrorUnknown;
+  if (e == hipSuccess && !device) e = hipStreamSynchronize(s);
+  if (e == hipSuccess && device) {
+    std::lock_guard<std::mutex> lock(c->launch_mutex);
+    if ((e = hipEventRecord(c->ev_refit, s)) == hipSuccess) c->refit_pending = true;
+  }
+  if (e != hipSuccess) {
+    const std::string why = st ? c->err : std::string(hipGetErrorString(e));
+    (void)hipStreamSynchronize(s);
+    free_tree(c);
+    free_mesh(c);
+    return fail(c, NRT_ERR_DEVICE, "%s: %s (the context's tree and primitives were dropped: set the mesh again)", fn, why.c_str());
+  }
+  c->generation++; // a committed nrt_scene over this context holds stale top-level boxes: it refuses until committed again
+  return NRT_OK;
+}
+
 // Library-internal (scene.hip): where a built fp32 context keeps its tree on the device.  Waits for the context's own
 // stream, so the arrays are complete; they stay valid until the context is rebuilt or destroyed.
 nrt_status nrt_internal_tree_view(nrt_ctx *c, nrt::TreeViewF32 *out) {
   if (!c || !out) return NRT_ERR_INVALID;
   if (c->prec != 4 || !c->d_nodes || !c->d_wide) return fail(c, NRT_ERR_INVALID, "no fp32 tree on the device");
   HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, refit_host_wait(c));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   out->nodes = (const nrt_node_f32 *)c->d_nodes;
   out->indices = c->d_indices;
@@ -914,6 +1026,7 @@ static nrt_status traverse_device(nrt_ctx *c, const typename Wire<T>::Ray *d_ray
 #endif
   std::lock_guard<std::mutex> lock(c->launch_mutex);
   HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, refit_stream_wait(c, s)); // (a Device refit in flight on another stream)
 
   // launch slot: the one this stream used last (stream order already serialises the two launches), else
   // a fresh one, else the oldest — whose previous launch this stream then waits for on the device
@@ -1528,6 +1641,11 @@ nrt_status nrtMultiHitTraverseBatchDevice_f64(nrt_ctx *c, const nrt_ray_f64 *r, 
                                               nrt_hit_f64 *h, uint32_t *cnt, void *s) {
   return multihit_device<double>(c, r, n, k, o, h, cnt, (hipStream_t)s);
 }
+
+nrt_status nrtRefit_f32(nrt_ctx *c, const float *v, size_t stride) { return refit<float>(c, v, stride, false, nullptr); }
+nrt_status nrtRefit_f64(nrt_ctx *c, const double *v, size_t stride) { return refit<double>(c, v, stride, false, nullptr); }
+nrt_status nrtRefitDevice_f32(nrt_ctx *c, const float *v, size_t stride, void *s) { return refit<float>(c, v, stride, true, (hipStream_t)s); }
+nrt_status nrtRefitDevice_f64(nrt_ctx *c, const double *v, size_t stride, void *s) { return refit<double>(c, v, stride, true, (hipStream_t)s); }
 
 nrt_status nrtSetMesh_f32(nrt_ctx *c, const float *v, size_t stride, const uint32_t *f, uint32_t nf) {
   return set_mesh<float>(c, v, stride, f, nf);

@@ -44,6 +44,7 @@
 #include <vector>
 
 #include "common.h"
+#include "minmax_dev.h"
 
 namespace nrt {
 
@@ -122,28 +123,6 @@ struct Ord<double> {
   static __host__ __device__ __forceinline__ U lowest() { return 0ull; }
   static __host__ __device__ __forceinline__ U highest() { return 0xFFFFFFFFFFFFFFFFull; }
 };
-
-template <typename T>
-struct Lim;
-template <>
-struct Lim<float> {
-  static __device__ __forceinline__ float max() { return 3.402823466e+38f; }
-  static __device__ __forceinline__ float inf() { return __builtin_huge_valf(); }
-};
-template <>
-struct Lim<double> {
-  static __device__ __forceinline__ double max() { return 1.7976931348623157e+308; }
-  static __device__ __forceinline__ double inf() { return __builtin_huge_val(); }
-};
-
-template <typename T>
-__device__ __forceinline__ T tmin(T a, T b) {
-  return (b < a) ? b : a;
-}
-template <typename T>
-__device__ __forceinline__ T tmax(T a, T b) {
-  return (a < b) ? b : a;
-}
 
 // Primitive record carried (and physically partitioned) through the build.
 template <typename T>

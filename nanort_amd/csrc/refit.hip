@@ -1,0 +1,210 @@
+// nanort_amd/csrc/refit.hip — BVH refit on gfx950: the boxes of a resident tree recomputed bottom-up from moved vertices
+// (nrtRefit* / nrtRefitDevice*, include/nanort_hip.h).  Topology, leaf slots and the index array stay as they are.
+//
+//   PLAN (first refit after the tree changes; cached in the context, dropped by free_tree)
+//     k_plan_root      level 0: the root in the branch or the leaf list
+//     k_plan_expand    one launch per level d <= tree_depth: the level's branches append their branch children to level
+//                      d + 1 and their leaf children to the leaf list (slots by atomic counters: the lists' order varies
+//                      from plan to plan, no box depends on it)
+//   REFIT (every call)
+//     k_refit_verts    the caller's strided vertices -> the context's tight xyz
+//     k_refit_leaves   every reachable leaf: min / max over each coordinate of its triangles, in slot order
+//     k_refit_branches one launch per level, deepest first: union of the two children's boxes, low child first
+//   then the existing launch_gather_leaf_tris / launch_make_wide (api.hip) re-derive LeafTri and WideNode / Wide4Node.
+//
+// Every level's boxes reach the next level through a launch boundary: no workgroup hands data to another inside a launch.
+// Records the walk from the root never reaches (adopted trees) are in neither list and are left untouched.
+#include <algorithm>
+
+#include "common.h"
+#include "minmax_dev.h"
+
+namespace nrt {
+
+constexpr unsigned kRefitBlock = 256;
+constexpr unsigned kRefitMaxGrid = 1024; // grid-stride kernels: the list lengths live on the device
+
+// Plan header, in uint32 words: cnt[levels], off[levels], leaf count; then the branch list (level-major), then the leaf list.
+static inline size_t plan_header_words(uint32_t levels) { return 2 * (size_t)levels + 2; }
+
+__global__ void __launch_bounds__(1) k_plan_root(uint32_t *plan, uint32_t levels, uint32_t root_is_branch, uint32_t *branch_list,
+                                                 uint32_t *leaf_list) {
+  uint32_t *cnt = plan, *leaf_cnt = plan + 2 * (size_t)levels;
+  if (root_is_branch) {
+    branch_list[0] = 0u;
+    cnt[0] = 1u;
+  } else {
+    leaf_list[0] = 0u;
+    *leaf_cnt = 1u;
+  }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(kRefitBlock) k_plan_expand(const typename Wire<T>::Node *__restrict__ nodes, uint32_t *plan, uint32_t levels,
+                                                             uint32_t d, uint32_t *branch_list, uint32_t branch_cap, uint32_t *leaf_list,
+                                                             uint32_t leaf_cap) {
+  uint32_t *cnt = plan, *off = plan + levels, *leaf_cnt = plan + 2 * (size_t)levels;
+  const uint32_t begin = off[d], n = cnt[d], next = begin + n; // (level d is complete: the previous launch filled it)
+  if (blockIdx.x == 0 && threadIdx.x == 0) off[d + 1] = next;
+  for (uint32_t i = blockIdx.x * kRefitBlock + threadIdx.x; i < n; i += gridDim.x * kRefitBlock) {
+    const uint32_t b = branch_list[begin + i];
+    for (int ch = 0; ch < 2; ch++) {
+      const uint32_t k = nodes[b].data[ch];
+      if (nodes[k].flag == 0) {
+        const uint32_t pos = next + atomicAdd(&cnt[d + 1], 1u);
+        if (pos < branch_cap) branch_list[pos] = k;
+      } else {
+        const uint32_t pos = atomicAdd(leaf_cnt, 1u);
+        if (pos < leaf_cap) leaf_list[pos] = k;
+      }
+    }
+  }
+}
+
+// Aligned: the row stride and the base are multiples of sizeof(T) (typed loads); else byte loads.
+template <typename T, bool Aligned>
+__global__ void __launch_bounds__(kRefitBlock) k_refit_verts(const unsigned char *__restrict__ src, size_t stride, uint32_t nv,
+                                                             T *__restrict__ dst) {
+  const uint32_t i = blockIdx.x * kRefitBlock + threadIdx.x;
+  if (i >= nv) return;
+  const unsigned char *row = src + (size_t)i * stride;
+  T p[3];
+  if (Aligned) {
+    const T *r = reinterpret_cast<const T *>(row);
+    p[0] = r[0];
+    p[1] = r[1];
+    p[2] = r[2];
+  } else {
+    __builtin_memcpy(p, row, sizeof(p));
+  }
+  dst[3 * (size_t)i + 0] = p[0];
+  dst[3 * (size_t)i + 1] = p[1];
+  dst[3 * (size_t)i + 2] = p[2];
+}
+
+template <typename T>
+__device__ __forceinline__ void store_box(typename Wire<T>::Node *n, const T lo[3], const T hi[3]) {
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    n->bmin[k] = lo[k];
+    n->bmax[k] = hi[k];
+  }
+}
+
+// A leaf's box: per triangle tmin(p0, tmin(p1, p2)) as the builder's primitive records (build.hip k_prim_records), folded
+// over the leaf's slots in order.  An empty leaf keeps {+max, -max}, which a parent's union ignores.
+template <typename T>
+__global__ void __launch_bounds__(kRefitBlock) k_refit_leaves(typename Wire<T>::Node *__restrict__ nodes, const uint32_t *__restrict__ indices,
+                                                              const uint32_t *__restrict__ faces, const T *__restrict__ verts,
+                                                              const uint32_t *__restrict__ plan, uint32_t levels, const uint32_t *__restrict__ leaf_list,
+                                                              uint32_t leaf_cap) {
+  const uint32_t n = min(plan[2 * (size_t)levels], leaf_cap);
+  for (uint32_t i = blockIdx.x * kRefitBlock + threadIdx.x; i < n; i += gridDim.x * kRefitBlock) {
+    typename Wire<T>::Node *node = nodes + leaf_list[i];
+    const uint32_t count = node->data[0], first = node->data[1];
+    T lo[3], hi[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+      lo[k] = Lim<T>::max();
+      hi[k] = -Lim<T>::max();
+    }
+    for (uint32_t j = 0; j < count; j++) {
+      const uint32_t *f = faces + 3 * (size_t)indices[first + j];
+      const T *v0 = verts + 3 * (size_t)f[0], *v1 = verts + 3 * (size_t)f[1], *v2 = verts + 3 * (size_t)f[2];
+#pragma unroll
+      for (int k = 0; k < 3; k++) {
+        lo[k] = tmin(lo[k], tmin(v0[k], tmin(v1[k], v2[k])));
+        hi[k] = tmax(hi[k], tmax(v0[k], tmax(v1[k], v2[k])));
+      }
+    }
+    store_box<T>(node, lo, hi);
+  }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(kRefitBlock) k_refit_branches(typename Wire<T>::Node *__restrict__ nodes, const uint32_t *__restrict__ plan,
+                                                                uint32_t levels, uint32_t d, const uint32_t *__restrict__ branch_list,
+                                                                uint32_t branch_cap) {
+  const uint32_t begin = plan[levels + d];
+  const uint32_t n = begin < branch_cap ? min(plan[d], branch_cap - begin) : 0u;
+  for (uint32_t i = blockIdx.x * kRefitBlock + threadIdx.x; i < n; i += gridDim.x * kRefitBlock) {
+    typename Wire<T>::Node *node = nodes + branch_list[begin + i];
+    const typename Wire<T>::Node *a = nodes + node->data[0], *b = nodes + node->data[1];
+    T lo[3], hi[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+      lo[k] = tmin(a->bmin[k], b->bmin[k]);
+      hi[k] = tmax(a->bmax[k], b->bmax[k]);
+    }
+    store_box<T>(node, lo, hi);
+  }
+}
+
+static unsigned refit_grid(uint64_t most) {
+  const uint64_t g = (most + kRefitBlock - 1) / kRefitBlock;
+  return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(g, kRefitMaxGrid));
+}
+
+// header + one word per node record (the branch and the leaf list hold the reachable records, each once)
+size_t refit_plan_bytes(uint32_t tree_depth, uint64_t num_nodes) { return (plan_header_words(tree_depth + 2u) + (size_t)num_nodes) * sizeof(uint32_t); }
+
+// The plan of the current tree into `plan` (refit_plan_bytes): levels 0 .. tree_depth of the walk from the root.
+template <typename T>
+hipError_t launch_refit_plan(const typename Wire<T>::Node *nodes, uint64_t num_nodes, uint32_t num_branch_records, uint32_t tree_depth,
+                             uint32_t root_is_branch, uint32_t *plan, hipStream_t s) {
+  const uint32_t levels = tree_depth + 2u;
+  const size_t hdr = plan_header_words(levels);
+  uint32_t *branch_list = plan + hdr, *leaf_list = branch_list + num_branch_records;
+  const uint32_t leaf_cap = (uint32_t)(num_nodes - num_branch_records);
+  hipError_t e = hipMemsetAsync(plan, 0, hdr * sizeof(uint32_t), s);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_plan_root, dim3(1), dim3(1), 0, s, plan, levels, root_is_branch, branch_list, leaf_list);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  for (uint32_t d = 0; d + 1 < levels; d++) { // (level d holds at most 2^d branches)
+    const uint64_t most = std::min<uint64_t>(d < 32 ? (1ull << d) : ~0ull, num_branch_records);
+    hipLaunchKernelGGL((k_plan_expand<T>), dim3(refit_grid(most)), dim3(kRefitBlock), 0, s, nodes, plan, levels, d, branch_list,
+                       num_branch_records, leaf_list, leaf_cap);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+// One refit over a planned tree: vertices in, boxes of every reachable node out.
+template <typename T>
+hipError_t launch_refit(const void *src, size_t stride, bool aligned, uint32_t nv, T *verts, const uint32_t *faces, const uint32_t *indices,
+                        typename Wire<T>::Node *nodes, uint64_t num_nodes, uint32_t num_branch_records, uint32_t tree_depth,
+                        const uint32_t *plan, hipStream_t s) {
+  const uint32_t levels = tree_depth + 2u;
+  const size_t hdr = plan_header_words(levels);
+  const uint32_t *branch_list = plan + hdr, *leaf_list = branch_list + num_branch_records;
+  const uint32_t leaf_cap = (uint32_t)(num_nodes - num_branch_records);
+  hipError_t e;
+  if (nv) {
+    const dim3 grid((nv + kRefitBlock - 1) / kRefitBlock);
+    if (aligned)
+      hipLaunchKernelGGL((k_refit_verts<T, true>), grid, dim3(kRefitBlock), 0, s, (const unsigned char *)src, stride, nv, verts);
+    else
+      hipLaunchKernelGGL((k_refit_verts<T, false>), grid, dim3(kRefitBlock), 0, s, (const unsigned char *)src, stride, nv, verts);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL((k_refit_leaves<T>), dim3(refit_grid(leaf_cap)), dim3(kRefitBlock), 0, s, nodes, indices, faces, (const T *)verts, plan,
+                     levels, leaf_list, leaf_cap);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  for (uint32_t d = levels - 1u; d-- > 0;) { // deepest level first (level tree_depth + 1 is empty: the walk's last level has leaves only)
+    const uint64_t most = std::min<uint64_t>(d < 32 ? (1ull << d) : ~0ull, num_branch_records);
+    if (most == 0) continue;
+    hipLaunchKernelGGL((k_refit_branches<T>), dim3(refit_grid(most)), dim3(kRefitBlock), 0, s, nodes, plan, levels, d, branch_list,
+                       num_branch_records);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+template hipError_t launch_refit_plan<float>(const Wire<float>::Node *, uint64_t, uint32_t, uint32_t, uint32_t, uint32_t *, hipStream_t);
+template hipError_t launch_refit_plan<double>(const Wire<double>::Node *, uint64_t, uint32_t, uint32_t, uint32_t, uint32_t *, hipStream_t);
+template hipError_t launch_refit<float>(const void *, size_t, bool, uint32_t, float *, const uint32_t *, const uint32_t *, Wire<float>::Node *,
+                                        uint64_t, uint32_t, uint32_t, const uint32_t *, hipStream_t);
+template hipError_t launch_refit<double>(const void *, size_t, bool, uint32_t, double *, const uint32_t *, const uint32_t *, Wire<double>::Node *,
+                                         uint64_t, uint32_t, uint32_t, const uint32_t *, hipStream_t);
+
+} // namespace nrt
