@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "common.h"
+#include "launch_plan.h"
 #ifdef NRT_PROF
 #include "../../include/nanort_hip_prof.h"
 #endif
@@ -159,7 +160,7 @@ struct nrt_ctx {
 
   // traversal tuning (env NRT_LDS_STACK / NRT_REFILL_MIN / NRT_TRAV_MIN / NRT_CHUNK override)
   int lds_stack = kLdsStackDefault;
-  unsigned blocks_per_cu = 0, chunk = 128, chunk_tail_pct = 0, refill_min = 44, trav_min = 16, leaf_min = 32; // (trav_min: 8 until round 3; 12-14 was the optimum of the two-level walk before its inner loop ran two rounds per trip, profiles/r03t_trav_min.txt; 16 with two rounds per trip in the fp64 walk, profiles/r03ZA)
+  unsigned chunk = 128, chunk_tail_pct = 0, refill_min = 44, trav_min = 16, leaf_min = 32; // (trav_min: 8 until round 3; 12-14 was the optimum of the two-level walk before its inner loop ran two rounds per trip, profiles/r03t_trav_min.txt; 16 with two rounds per trip in the fp64 walk, profiles/r03ZA)
   int f64_row_fetch = 1; // fp64 walk: fetch the plane rows of a WideNode<double> by the ray's signs (0: fetch the record and select; the path arrays of 4 GiB and more take)
   unsigned trav_min4 = 24; // the same threshold for the fp32 two-level walk, whose inner loop runs two pop + step rounds per trip (profiles/r03Z_threshold_resweep*.txt)
   unsigned num_parts = 8; // ray partitions == XCDs (env NRT_PARTS)
@@ -189,9 +190,8 @@ struct nrt_ctx {
   int leaf_compact = 1; // traverse.hip "leaf items" (round 6): when the records of all the lanes waiting at a leaf fit one trip of the wave, they are tested one per lane with the owner's ray constants and accepted by the owner in record order — records bit-identical, C3 +2 %, C4 tile +2.8 %; 0: every owner tests its own records
   int dyn_head = 1; // batches too small for a static group per wave: every wave's first chunk is its own (traverse.hip claim_init; tunable dyn_head)
   int wide_scramble = 0; // probe (tunable wide_scramble): the private node records in a pseudo-random order instead of pre-order
-  unsigned wide4_blocks_per_cu = 0;
-  unsigned wide_blocks_per_cu = 0, sphere_blocks_per_cu = 0;
-  unsigned multihit_blocks_per_cu = 0; // k_traverse_multihit (multihit.hip)
+  // resident blocks per CU of the variants launched so far, by what selects the kernel: [walk][primitive kind] at `lds_entries` (a context keeps one precision; size_grid)
+  struct { int lds_entries; unsigned blocks_per_cu; } occupancy[4][3] = {};
 
   hipEvent_t ev_b0 = nullptr, ev_b1 = nullptr;
   hipEvent_t ev_build_state = nullptr; // the builder's state block has reached build_state
@@ -384,8 +384,7 @@ static bool tunable_set(nrt_ctx *c, const char *name, long long v) {
   const TunableDesc *d = tunable_find(name);
   if (!d) return false;
   d->set(c, std::min(d->hi, std::max(d->lo, v)));
-  // the occupancy figures depend on the variant the tunables select: recompute on the next launch
-  c->blocks_per_cu = c->wide_blocks_per_cu = c->wide4_blocks_per_cu = c->sphere_blocks_per_cu = 0;
+  memset(c->occupancy, 0, sizeof(c->occupancy)); // the figures depend on the variant the tunables select: ask again on the next launch
   return true;
 }
 
@@ -982,13 +981,6 @@ int nrt_internal_device(const nrt_ctx *c) { return c ? c->device : 0; } // group
 // ---------------------------------------------------------------------------
 static const nrt_trace_options kDefaultTrace = {{0u, 0x7FFFFFFFu}, 0xFFFFFFFFu, 0, {0, 0, 0}}; // nanort.h:617-623
 
-// A multi-hit launch (nrtMultiHitTraverseBatch*): the binary loop of k_traverse_multihit over the same launch slots; the hit
-// pointer of traverse_device then holds `max_hits` records per ray.
-struct MultiHitLaunch {
-  uint32_t max_hits;
-  uint32_t *counts; // may be null
-};
-
 // Several batches for one launch (nrtTraverseBatchesDevice): fp32 triangle contexts on the WideNode kernels.
 template <typename T>
 struct TraverseBatches {
@@ -1000,118 +992,118 @@ struct TraverseBatches {
   uint32_t anyhit; // bit k: batch k is an occlusion query
 };
 
+// What one traversal launch is asked for: the query kind says which of the outputs it reads.  (Occlusion: every ray stops at the
+// first primitive it accepts; Count: the literal kernel's counting pass into d_counters, no output of its own.)
+enum class Query { Closest, Occlusion, Count, MultiHit, Cylinders, MultiBatch };
 template <typename T>
-static nrt_status traverse_device(nrt_ctx *c, const typename Wire<T>::Ray *d_rays, uint64_t n,
-                                  const nrt_trace_options *opt, typename Wire<T>::Hit *d_hits, uint8_t *d_mask,
-                                  hipStream_t s, bool count, bool timed, void *d_cyl_hits = nullptr, bool any_hit = false,
-                                  const TraverseBatches<T> *mb = nullptr, const MultiHitLaunch *mh = nullptr) {
+struct TraverseLaunch {
+  Query kind;
+  const typename Wire<T>::Ray *rays;
+  uint64_t n;
+  const nrt_trace_options *opt; // null: the reference's defaults
+  hipStream_t stream;
+  bool timed = false; // bracket the launch with the slot's timing events (when it publishes no completion record)
+  typename Wire<T>::Hit *hits = nullptr; // Closest (null: flags only); MultiHit: max_hits records per ray
+  uint8_t *mask = nullptr;               // Closest (may be null), Occlusion, Cylinders
+  void *cyl_hits = nullptr;              // Cylinders: 28-byte records, written by the post pass
+  uint32_t max_hits = 0;
+  uint32_t *hit_counts = nullptr;        // MultiHit (may be null): one word per ray
+  const TraverseBatches<T> *batches = nullptr; // MultiBatch: rays and outputs per batch, n = all their rays (the context takes one launch: the caller checked)
+};
+
+// Every combination a launch cannot be is refused here (under launch_mutex: the tunables hold still).
+template <typename T>
+static nrt_status validate_launch(nrt_ctx *c, const TraverseLaunch<T> &l) {
+  const bool custom = c->prim_kind != kPrimTriangles; // spheres / cylinders
   if (c->prec != (int)sizeof(T)) return fail(c, NRT_ERR_PRECISION, "nrtTraverseBatch: precision mismatch");
-  if (mb) { // (the caller checked that this context walks batches in one launch; n = all rays)
-    d_rays = mb->rays[0];
-    d_hits = mb->hits[0];
-    d_mask = mb->mask[0];
-  }
-  if ((c->prim_kind == kPrimCylinders) != (d_cyl_hits != nullptr))
+  if ((c->prim_kind == kPrimCylinders) != (l.kind == Query::Cylinders))
     return fail(c, NRT_ERR_INVALID, "cylinder primitives are traced with nrtTraverseBatchCylinders*_f32 (28-byte records), "
                                     "every other primitive kind with nrtTraverseBatch*");
   if (!c->d_nodes) return fail(c, NRT_ERR_INVALID, "nrtTraverseBatch: no tree (call nrtBuild or nrtSetTree)");
-  if (n == 0) return NRT_OK;
-  if (!d_rays) return fail(c, NRT_ERR_INVALID, "nrtTraverseBatch: NULL rays");
-  if (n > 0x7FFFFFFFull) return fail(c, NRT_ERR_INVALID, "nrtTraverseBatch: more than 2^31-1 rays in one call");
-  if (!opt) opt = &kDefaultTrace;
-#ifdef NRT_PROF
-  const unsigned dbg = c->debug_flags;
-#else
-  const unsigned dbg = c->debug_flags & ~(32u | 64u | 8192u); // (the counting / clocked instantiations live in libnanort_hip_prof.so)
-#endif
-  std::lock_guard<std::mutex> lock(c->launch_mutex);
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, refit_stream_wait(c, s)); // (a Device refit in flight on another stream)
-
-  // launch slot: the one this stream used last (stream order already serialises the two launches), else
-  // a fresh one, else the oldest — whose previous launch this stream then waits for on the device
-  nrt_ctx::LaunchSlot *slot = nullptr;
-  for (nrt_ctx::LaunchSlot &sl : c->slots)
-    if (sl.used && sl.stream == s) {
-      slot = &sl;
-      break;
-    }
-  if (!slot)
-    for (nrt_ctx::LaunchSlot &sl : c->slots)
-      if (!sl.used) {
-        slot = &sl;
-        break;
-      }
-  if (!slot) {
-    slot = &c->slots[c->next_victim];
-    c->next_victim = (c->next_victim + 1) % nrt_ctx::kSlots;
-    if (slot->last_has_rec)
-      HIPCHK(c, wait_record(*slot)); // (the host waits: a fifth concurrent stream is the rare case)
-    else
-      HIPCHK(c, hipStreamWaitEvent(s, slot->done, 0));
-  }
-
-  // persistent grid: every block resident (occupancy of the chosen variant)
-  const bool spheres = c->prim_kind != kPrimTriangles; // the custom primitives share one launch geometry
-  if (spheres && (count || !c->d_wide))
+  if (l.n == 0) return NRT_OK;
+  if (!l.rays) return fail(c, NRT_ERR_INVALID, "nrtTraverseBatch: NULL rays");
+  if (l.n > 0x7FFFFFFFull) return fail(c, NRT_ERR_INVALID, "nrtTraverseBatch: more than 2^31-1 rays in one call");
+  if (custom && (l.kind == Query::Count || !c->d_wide))
     return fail(c, NRT_ERR_INVALID, "nrtTraverse: custom primitives run on the WideNode kernel only (no counting pass)");
-  if (any_hit && (spheres || count || !c->d_wide))
+  if (l.kind == Query::Occlusion && (custom || !c->d_wide))
     return fail(c, NRT_ERR_INVALID, "nrtOccludedBatch: occlusion queries run on the triangle WideNode kernel only");
-  const bool use_wide = (c->wide || spheres || any_hit) && !count && c->d_wide && !mh;
-  if (c->blocks_per_cu == 0) c->blocks_per_cu = (unsigned)traverse_blocks_per_cu<T>(c->lds_stack);
-  if (mh && c->multihit_blocks_per_cu == 0) c->multihit_blocks_per_cu = (unsigned)traverse_multihit_blocks_per_cu<T>();
+  if (l.kind == Query::MultiBatch && (sizeof(T) != 4 || custom || !c->wide || !c->d_wide))
+    return fail(c, NRT_ERR_INVALID, "internal: multi-batch launch on a context that cannot take it");
+  return NRT_OK;
+}
+
+// Launch slot: the one this stream used last (stream order already serialises the two launches), else
+// a fresh one, else the oldest — whose previous launch this stream then waits for on the device
+static nrt_status take_slot(nrt_ctx *c, hipStream_t s, nrt_ctx::LaunchSlot **out) {
+  for (int pass = 0; pass < 2; pass++) // (0: this stream's own slot, 1: a fresh one)
+    for (nrt_ctx::LaunchSlot &sl : c->slots)
+      if (pass == 0 ? (sl.used && sl.stream == s) : !sl.used) {
+        *out = &sl;
+        return NRT_OK;
+      }
+  nrt_ctx::LaunchSlot *slot = *out = &c->slots[c->next_victim];
+  c->next_victim = (c->next_victim + 1) % nrt_ctx::kSlots;
+  if (slot->last_has_rec)
+    HIPCHK(c, wait_record(*slot)); // (the host waits: a fifth concurrent stream is the rare case)
+  else
+    HIPCHK(c, hipStreamWaitEvent(s, slot->done, 0));
+  return NRT_OK;
+}
+
+// The kernel a launch runs, from the context's tree and tunables and the launch's kind and options.
+enum class Walk { Literal, OneLevel, TwoLevel, MultiHit }; // k_traverse, k_traverse_wide of WIDTH 2 / 4, k_traverse_multihit
+struct WalkChoice {
+  Walk walk;
+  bool plain_options; // prim ids are < num_faces: nothing can be rejected by the trace options -> the kernel variant without the id tests
+  bool wide4_big;     // the two-level records are addressed with 64-bit offsets
+  int lds_entries;    // per-lane stack entries the variant keeps in LDS
+  unsigned dbg;
+  bool wide() const { return walk == Walk::OneLevel || walk == Walk::TwoLevel; }
+  bool wide4() const { return walk == Walk::TwoLevel; }
+};
+template <typename T>
+static WalkChoice choose_walk(const nrt_ctx *c, const TraverseLaunch<T> &l) {
+  WalkChoice w;
+#ifdef NRT_PROF
+  w.dbg = c->debug_flags;
+#else
+  w.dbg = c->debug_flags & ~(32u | 64u | 8192u); // (the counting / clocked instantiations live in libnanort_hip_prof.so)
+#endif
+  const bool custom = c->prim_kind != kPrimTriangles; // the custom primitives share one launch geometry
+  const bool multihit = l.kind == Query::MultiHit;
+  const bool use_wide = (c->wide || custom || l.kind == Query::Occlusion) && l.kind != Query::Count && c->d_wide && !multihit;
   // two levels per step: closest-hit walks of nested fp32 triangle trees, outside the profiling / splitting variants
-  // prim ids are < num_faces: nothing can be rejected by these options -> the kernel variant without the id tests
-  const bool plain_options = opt->prim_ids_range[0] == 0u && opt->prim_ids_range[1] >= c->num_faces && opt->skip_prim_id >= c->num_faces &&
-                             !opt->cull_back_face;
+  w.plain_options = l.opt->prim_ids_range[0] == 0u && l.opt->prim_ids_range[1] >= c->num_faces && l.opt->skip_prim_id >= c->num_faces &&
+                    !l.opt->cull_back_face;
   // (the profiling instantiations of the two-level walk are built for the default trace options only: with options that can
   // reject a primitive a profiled launch walks one level per step, whose profiling variant honours them)
-  const bool prof_needs_w2 = (dbg & (32u | 8192u)) && !plain_options && !spheres;
+  const bool prof_needs_w2 = (w.dbg & (32u | 8192u)) && !w.plain_options && !custom;
   // (a record array of 4 GiB or more is walked two levels per step by the default walk of triangle trees only: closest hits in the
   // reference's order, outside the profiling instantiations)
-  const bool wide4_big = c->num_branch_records >= (1ull << 25) || (c->wide4_big_ok == 2 && c->prim_kind == kPrimTriangles); // (2: forced, for the tests)
+  w.wide4_big = c->num_branch_records >= (1ull << 25) || (c->wide4_big_ok == 2 && c->prim_kind == kPrimTriangles); // (2: forced, for the tests)
   const bool use_wide4 = use_wide && c->d_wide4 && c->wide_stack == 10 && c->tree_nested && c->root_is_branch && !prof_needs_w2 &&
-                         (!wide4_big || (!spheres && !c->order4 && !(dbg & (32u | 8192u))));
-  if (c->wide_blocks_per_cu == 0) c->wide_blocks_per_cu = (unsigned)traverse_wide_blocks_per_cu<T>(c->wide_stack, kPrimTriangles, false);
-  if (use_wide4 && !spheres && c->wide4_blocks_per_cu == 0) c->wide4_blocks_per_cu = (unsigned)traverse_wide_blocks_per_cu<T>(kWide4LdsStack, kPrimTriangles, true);
-  if (spheres && c->sphere_blocks_per_cu == 0) c->sphere_blocks_per_cu = (unsigned)traverse_wide_blocks_per_cu<T>(10, c->prim_kind, use_wide4); // (one kind and one walk per context)
-  unsigned blocks_per_cu = spheres ? c->sphere_blocks_per_cu : (use_wide4 ? c->wide4_blocks_per_cu : (use_wide ? c->wide_blocks_per_cu : c->blocks_per_cu));
-  if (mh) blocks_per_cu = c->multihit_blocks_per_cu;
-  if (c->max_blocks_per_cu && blocks_per_cu > c->max_blocks_per_cu) blocks_per_cu = c->max_blocks_per_cu;
-  const int stack_entries = mh ? kLdsStackDefault : (use_wide4 ? kWide4LdsStack : (spheres ? 10 : (use_wide ? c->wide_stack : c->lds_stack)));
-  uint64_t need_blocks = (n + kTraverseBlock - 1) / kTraverseBlock;
-  unsigned grid = (unsigned)std::min<uint64_t>(need_blocks, (uint64_t)c->num_cus * blocks_per_cu);
-  const unsigned parts = std::max(1u, std::min(c->num_parts, grid));
-  grid = ((grid + parts - 1) / parts) * parts; // whole blocks per partition (ranks are partition-major)
-  const uint32_t total_threads = grid * kTraverseBlock;
-  const uint32_t total_waves = grid * (kTraverseBlock / kWave);
-  // Work distribution (traverse.hip, Claim).  Static share: c->static_pct percent of the batch, in whole 64-ray groups per
-  // wave, cut into up to `static_bands` slices — one at the head of each of as many equal bands of the batch; the rest of
-  // each band (a whole number of chunks) and the tail behind the last band are claimed dynamically.
-  // (less than one group per wave: none — a batch of fewer than ~400 rays per wave is claimed in chunks from its first ray; a forced
-  // group per wave measured -2.7 % on a 1600x960 wave, profiles/r06y_distribution10.txt)
-  const uint32_t static_share = (uint32_t)(((uint64_t)n * c->static_pct / 100) / total_waves / 64); // 64-ray groups per wave
-  // (a slice shorter than two 64-ray groups makes the waves of an XCD drift apart over the bands within one refill, and its
-  // L2 then holds several strips of the scene at once: measured on C3, 64-ray slices in 4 bands cost 3 %; two bands of 128
-  // cost nothing and still take 8 % off C2, whose sky rows otherwise leave one XCD with the whole sphere: profiles/r03d_*)
-  const uint32_t bands = std::max<uint32_t>(1u, std::min<uint32_t>(c->static_bands, static_share / c->static_slice_groups));
-  const uint32_t static_per_wave = (static_share / bands) * 64u;
-  const uint32_t band_static = static_per_wave * total_waves;
-  const uint32_t dyn_per_band = static_per_wave ? (uint32_t)(((uint64_t)n / bands - band_static) / c->chunk) * c->chunk : 0u;
-  const uint32_t band_len = band_static + dyn_per_band;
-  // deepest possible stack: one pending sibling per level of the path — three per TWO levels when a step covers two
-  const uint32_t max_entries = use_wide4 ? 3u * (c->tree_depth / 2u + 1u) + 2u : c->tree_depth + 2u;
-  const uint32_t levels = max_entries > (uint32_t)stack_entries ? max_entries - stack_entries : 0;
-  if (levels) { // (growing a buffer frees the old one, which waits for every launch in flight)
-    nrt_status st = ensure(c, slot->spill, (size_t)levels * total_threads * sizeof(uint32_t));
-    if (st) return st;
-    if (use_wide) {
-      st = ensure(c, slot->spill_tmin, (size_t)levels * total_threads * sizeof(T));
-      if (st) return st;
-    }
-  }
+                         (!w.wide4_big || (!custom && !c->order4 && !(w.dbg & (32u | 8192u))));
+  w.walk = multihit ? Walk::MultiHit : (use_wide4 ? Walk::TwoLevel : (use_wide ? Walk::OneLevel : Walk::Literal));
+  w.lds_entries = multihit ? kLdsStackDefault : (use_wide4 ? kWide4LdsStack : (custom ? 10 : (use_wide ? c->wide_stack : c->lds_stack)));
+  return w;
+}
 
-  TraverseArgs<T> a;
+// Persistent grid: every block resident.  A variant's occupancy is asked for once per context and key (what selects the kernel).
+template <typename T>
+static GridPlan size_grid(nrt_ctx *c, const WalkChoice &w, uint64_t n) {
+  auto &e = c->occupancy[(int)w.walk][c->prim_kind];
+  if (e.blocks_per_cu == 0 || e.lds_entries != w.lds_entries)
+    e = {w.lds_entries, (unsigned)(w.walk == Walk::MultiHit  ? traverse_multihit_blocks_per_cu<T>()
+                        : w.walk == Walk::Literal ? traverse_blocks_per_cu<T>(w.lds_entries)
+                                                  : traverse_wide_blocks_per_cu<T>(w.lds_entries, c->prim_kind, w.wide4()))};
+  const unsigned per_cu = c->max_blocks_per_cu && e.blocks_per_cu > c->max_blocks_per_cu ? c->max_blocks_per_cu : e.blocks_per_cu;
+  return plan_grid(n, kTraverseBlock, (uint32_t)c->num_cus, per_cu, c->num_parts);
+}
+
+// TraverseArgs, part 1: the tree, the trace options and the tunables of the walk.
+template <typename T>
+static void fill_walk_args(const nrt_ctx *c, const TraverseLaunch<T> &l, const WalkChoice &w, TraverseArgs<T> &a) {
+  const bool profiled = (w.dbg & (32u | 8192u)) != 0u;
   a.nodes = (const typename Wire<T>::Node *)c->d_nodes;
   a.tris = (const LeafTri<T> *)c->d_tris;
   a.spheres = (const LeafSphere<T> *)c->d_tris;
@@ -1119,101 +1111,102 @@ static nrt_status traverse_device(nrt_ctx *c, const typename Wire<T>::Ray *d_ray
   a.cylinders = (const LeafCylinder<T> *)c->d_tris;
   a.cyl_test_cap = c->cyl_test_cap;
   a.wide = (const WideNode<T> *)c->d_wide;
-  a.wide4 = use_wide4 ? (const Wide4Node<T> *)c->d_wide4 : nullptr;
+  a.wide4 = w.wide4() ? (const Wide4Node<T> *)c->d_wide4 : nullptr;
   a.packed_leaves = c->packed_leaves;
-  a.wide4_big = (use_wide4 && wide4_big) ? 1u : 0u;
+  a.wide4_big = (w.wide4() && w.wide4_big) ? 1u : 0u;
   a.wide_below_4g = (c->f64_row_fetch && (uint64_t)c->num_branch_records * sizeof(WideNode<T>) < (1ull << 32)) ? 1u : 0u;
   a.root_is_branch = c->root_is_branch;
-  a.debug_flags = dbg;
-  a.spill_tmin = (T *)slot->spill_tmin.p;
-  a.rays = d_rays;
-  a.hits = d_hits;
-  a.mask = d_mask;
-  if (d_cyl_hits) { // compact records + {hit, cap} bits, expanded by the post pass below
-    nrt_status st = ensure(c, slot->cyl_hits, (size_t)n * sizeof(typename Wire<T>::Hit));
-    if (st) return st;
-    if ((st = ensure(c, slot->cyl_bits, (size_t)n))) return st;
-    a.hits = (typename Wire<T>::Hit *)slot->cyl_hits.p;
-    a.mask = (uint8_t *)slot->cyl_bits.p;
-  }
-  a.num_rays = (uint32_t)n;
-  a.num_batches = 1u;
-  a.batch_anyhit = 0u;
-  for (int k = 0; k < kMaxBatches; k++) {
-    a.batch_end[k] = (uint32_t)n;
-    a.batches[k] = BatchPtrs{nullptr, nullptr, nullptr, 0};
-  }
-  if (mb) {
-    if (!use_wide || sizeof(T) != 4 || spheres || count) return fail(c, NRT_ERR_INVALID, "internal: multi-batch launch on a context that cannot take it");
-    a.num_batches = mb->nb;
-    a.batch_anyhit = mb->anyhit;
-    uint64_t start = 0;
-    for (uint32_t k = 0; k < mb->nb; k++) { // pointers addressed by the virtual index: base - start
-      a.batches[k].rays_v = mb->rays[k] - start;
-      a.batches[k].hits_v = mb->hits[k] ? mb->hits[k] - start : nullptr;
-      a.batches[k].mask_v = mb->mask[k] ? mb->mask[k] - start : nullptr;
-      start += mb->count[k];
-      a.batch_end[k] = (uint32_t)start;
-    }
-    for (uint32_t k = mb->nb; k < (uint32_t)kMaxBatches; k++) a.batch_end[k] = (uint32_t)start;
-  }
-  a.range0 = opt->prim_ids_range[0];
-  a.range1 = opt->prim_ids_range[1];
-  a.skip_prim = opt->skip_prim_id;
-  a.cull_back_face = opt->cull_back_face ? 1u : 0u;
-  a.any_hit = any_hit ? 1u : 0u;
-  a.plain_options = plain_options ? 1u : 0u;
+  a.debug_flags = w.dbg;
+  a.range0 = l.opt->prim_ids_range[0];
+  a.range1 = l.opt->prim_ids_range[1];
+  a.skip_prim = l.opt->skip_prim_id;
+  a.cull_back_face = l.opt->cull_back_face ? 1u : 0u;
+  a.any_hit = l.kind == Query::Occlusion ? 1u : 0u;
+  a.plain_options = w.plain_options ? 1u : 0u;
   a.root_test = c->tree_nested ? 0u : 1u;
-  a.order4 = (c->order4 && use_wide4 && !spheres && !any_hit && !(dbg & (32u | 8192u))) ? 1u : 0u;
-  a.leaf_items = (c->leaf_compact && use_wide4 && c->prim_kind == kPrimTriangles && c->max_leaf_count <= 4u && !(dbg & (32u | 8192u))) ? 1u : 0u;
-  a.spill = (uint32_t *)slot->spill.p;
-  a.spill_stride = total_threads;
-  a.spill_levels = levels;
-  a.ray_cursor = slot->d_cursor + (size_t)slot->parity * kCursorStrideWords * kMaxParts;
-  a.next_cursor = slot->d_cursor + (size_t)(slot->parity ^ 1u) * kCursorStrideWords * kMaxParts;
-  a.num_parts = parts;
-  a.static_per_wave = static_per_wave;
-  a.static_bands = static_per_wave ? bands : 0u;
-  a.band_len = band_len;
-  a.band_static = band_static;
-  a.dyn_per_band = dyn_per_band;
-  a.dyn_banded = a.static_bands * dyn_per_band;
-  a.tail_begin = a.static_bands * band_len;
-  a.dyn_total = a.dyn_banded + ((uint32_t)n - a.tail_begin);
-  a.dyn_per_part = (a.dyn_total / parts / c->chunk) * c->chunk;
-  a.blocks_per_part = grid / parts;
+  a.order4 = (c->order4 && w.wide4() && c->prim_kind == kPrimTriangles && l.kind != Query::Occlusion && !profiled) ? 1u : 0u;
+  a.leaf_items = (c->leaf_compact && w.wide4() && c->prim_kind == kPrimTriangles && c->max_leaf_count <= 4u && !profiled) ? 1u : 0u;
   a.dyn_head = c->dyn_head ? 1u : 0u;
   a.counters = c->d_counters;
-  a.wave_clock = nullptr;
-#ifdef NRT_PROF
-  if (dbg & 8192u) { // profiling: per-wave time stamps of this launch (nrtDebugWaveClocks)
-    nrt_status st = ensure(c, c->b_wave_clock, (size_t)total_waves * 3 * sizeof(unsigned long long));
-    if (st) return st;
-    a.wave_clock = (unsigned long long *)c->b_wave_clock.p;
-    c->wave_clock_waves = total_waves;
-  }
-#endif
+  a.wave_clock = (w.dbg & 8192u) ? (unsigned long long *)c->b_wave_clock.p : nullptr; // (sized by traverse_device; the bit is the profiling library's)
   a.chunk = c->chunk;
   a.chunk_tail_pct = c->chunk_tail_pct;
   a.refill_min = c->refill_min;
-  a.trav_min = use_wide4 ? c->trav_min4 : c->trav_min;
+  a.trav_min = w.wide4() ? c->trav_min4 : c->trav_min;
   a.leaf_min = c->leaf_min;
+}
 
-  if (count || (dbg & 32u)) HIPCHK(c, hipMemsetAsync(c->d_counters, 0, 16 * sizeof(unsigned long long), s));
+// ... part 2: the slot's scratch, the grid and the work distribution (launch_plan.h), the rays and where their records go.
+template <typename T>
+static void fill_launch_args(const TraverseLaunch<T> &l, const nrt_ctx::LaunchSlot *slot, const GridPlan &g, const DistributionPlan &d,
+                             uint32_t levels, TraverseArgs<T> &a) {
+  a.spill = (uint32_t *)slot->spill.p;
+  a.spill_tmin = (T *)slot->spill_tmin.p;
+  a.spill_stride = g.grid * kTraverseBlock;
+  a.spill_levels = levels;
+  a.ray_cursor = slot->d_cursor + (size_t)slot->parity * kCursorStrideWords * kMaxParts;
+  a.next_cursor = slot->d_cursor + (size_t)(slot->parity ^ 1u) * kCursorStrideWords * kMaxParts;
+  a.num_parts = g.parts;
+  a.blocks_per_part = g.blocks_per_part;
+  a.static_per_wave = d.static_per_wave;
+  a.static_bands = d.static_bands;
+  a.band_len = d.band_len;
+  a.band_static = d.band_static;
+  a.dyn_per_band = d.dyn_per_band;
+  a.dyn_banded = d.dyn_banded;
+  a.tail_begin = d.tail_begin;
+  a.dyn_total = d.dyn_total;
+  a.dyn_per_part = d.dyn_per_part;
+  a.rays = l.rays;
+  a.hits = l.hits;
+  a.mask = l.mask;
+  if (l.kind == Query::Cylinders) {
+    a.hits = (typename Wire<T>::Hit *)slot->cyl_hits.p;
+    a.mask = (uint8_t *)slot->cyl_bits.p;
+  }
+  a.num_rays = (uint32_t)l.n;
+  a.num_batches = 1u;
+  a.batch_anyhit = 0u;
+  for (int k = 0; k < kMaxBatches; k++) {
+    a.batch_end[k] = (uint32_t)l.n;
+    a.batches[k] = BatchPtrs{nullptr, nullptr, nullptr, 0};
+  }
+  if (l.kind != Query::MultiBatch) return;
+  const TraverseBatches<T> *mb = l.batches;
+  a.num_batches = mb->nb;
+  a.batch_anyhit = mb->anyhit;
+  uint64_t start = 0;
+  for (uint32_t k = 0; k < mb->nb; k++) { // pointers addressed by the virtual index: base - start
+    a.batches[k].rays_v = mb->rays[k] - start;
+    a.batches[k].hits_v = mb->hits[k] ? mb->hits[k] - start : nullptr;
+    a.batches[k].mask_v = mb->mask[k] ? mb->mask[k] - start : nullptr;
+    start += mb->count[k];
+    a.batch_end[k] = (uint32_t)start;
+  }
+  for (uint32_t k = mb->nb; k < (uint32_t)kMaxBatches; k++) a.batch_end[k] = (uint32_t)start;
+}
+
+// The kernel, the slot's bookkeeping, what runs behind the kernel.
+template <typename T>
+static nrt_status enqueue_launch(nrt_ctx *c, const TraverseLaunch<T> &l, const WalkChoice &w, nrt_ctx::LaunchSlot *slot, TraverseArgs<T> &a,
+                                 unsigned grid) {
+  const hipStream_t s = l.stream;
+  const bool count = l.kind == Query::Count;
+  if (count || (w.dbg & 32u)) HIPCHK(c, hipMemsetAsync(c->d_counters, 0, 16 * sizeof(unsigned long long), s));
   // completion record instead of events: the traversal kernel is the launch's last kernel and events were not asked for
-  const bool use_rec = use_wide && !count && !c->launch_timing;
+  const bool use_rec = w.wide() && !count && !c->launch_timing;
   // (the sphere kind's u/v pass and the cylinder kind's normal pass run behind the traversal kernel and close the record in its place)
-  const bool post_pass = (c->prim_kind == kPrimSpheres && d_hits != nullptr) || d_cyl_hits != nullptr;
+  const bool post_pass = (c->prim_kind == kPrimSpheres && l.hits != nullptr) || l.kind == Query::Cylinders;
   a.done_rec = use_rec ? slot->d_done : nullptr;
   a.done_count = slot->d_count;
   a.done_seq = use_rec ? slot->seq + 1u : 0u;
   a.done_publish = post_pass ? 0u : 1u;
-  timed = timed && !use_rec;
+  const bool timed = l.timed && !use_rec;
   if (timed) HIPCHK(c, hipEventRecord(slot->t0, s));
-  if (mh) {
-    HIPCHK(c, launch_traverse_multihit<T>(a, mh->max_hits, mh->counts, grid, s));
+  if (w.walk == Walk::MultiHit) {
+    HIPCHK(c, launch_traverse_multihit<T>(a, l.max_hits, l.hit_counts, grid, s));
     c->last_kernel = sizeof(T) == 4 ? "nrt::k_traverse_multihit<float>" : "nrt::k_traverse_multihit<double>";
-  } else if (use_wide) {
+  } else if (w.wide()) {
     HIPCHK(c, launch_traverse_wide<T>(a, grid, c->wide_stack, c->prim_kind, s, &c->last_kernel));
   } else {
     HIPCHK(c, launch_traverse<T>(a, grid, count, c->lds_stack, s));
@@ -1231,9 +1224,9 @@ static nrt_status traverse_device(nrt_ctx *c, const typename Wire<T>::Ray *d_ray
   slot->stream = s;
   slot->used = true;
   if (use_rec) c->last_timed_slot = (int)(slot - c->slots);
-  if (d_cyl_hits)
-    HIPCHK(c, launch_cylinder_post((const nrt_ray_f32 *)d_rays, (const nrt_hit_f32 *)slot->cyl_hits.p, (const uint8_t *)slot->cyl_bits.p,
-                                   (const float *)c->d_verts, (uint32_t)n, d_cyl_hits, d_mask, a.done_rec, a.done_count, a.done_seq, s));
+  if (l.kind == Query::Cylinders)
+    HIPCHK(c, launch_cylinder_post((const nrt_ray_f32 *)l.rays, (const nrt_hit_f32 *)slot->cyl_hits.p, (const uint8_t *)slot->cyl_bits.p,
+                                   (const float *)c->d_verts, (uint32_t)l.n, l.cyl_hits, l.mask, a.done_rec, a.done_count, a.done_seq, s));
   if (timed) {
     HIPCHK(c, hipEventRecord(slot->t1, s));
     slot->last_timed = true;
@@ -1243,6 +1236,61 @@ static nrt_status traverse_device(nrt_ctx *c, const typename Wire<T>::Ray *d_ray
   return NRT_OK;
 }
 
+// Every ray query of the C ABI ends here.  launch_mutex is held from the checks to the last event record.
+template <typename T>
+static nrt_status traverse_device(nrt_ctx *c, TraverseLaunch<T> l) {
+  if (!l.opt) l.opt = &kDefaultTrace;
+  std::lock_guard<std::mutex> lock(c->launch_mutex);
+  nrt_status st = validate_launch(c, l);
+  if (st || l.n == 0) return st;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, refit_stream_wait(c, l.stream)); // (a Device refit in flight on another stream)
+  nrt_ctx::LaunchSlot *slot = nullptr;
+  if ((st = take_slot(c, l.stream, &slot))) return st;
+  const WalkChoice w = choose_walk(c, l);
+  const GridPlan g = size_grid<T>(c, w, l.n);
+  const uint32_t total_threads = g.grid * kTraverseBlock, total_waves = g.grid * (kTraverseBlock / kWave);
+  const DistributionPlan d = plan_distribution((uint32_t)l.n, total_waves, g.parts, c->static_pct, c->static_bands, c->static_slice_groups, c->chunk);
+  const uint32_t levels = plan_spill_levels(c->tree_depth, w.wide4(), (uint32_t)w.lds_entries);
+  if (levels) { // (growing a buffer frees the old one, which waits for every launch in flight)
+    if ((st = ensure(c, slot->spill, (size_t)levels * total_threads * sizeof(uint32_t)))) return st;
+    if (w.wide() && (st = ensure(c, slot->spill_tmin, (size_t)levels * total_threads * sizeof(T)))) return st;
+  }
+  if (l.kind == Query::Cylinders) { // compact records + {hit, cap} bits, expanded by the post pass
+    if ((st = ensure(c, slot->cyl_hits, (size_t)l.n * sizeof(typename Wire<T>::Hit)))) return st;
+    if ((st = ensure(c, slot->cyl_bits, (size_t)l.n))) return st;
+  }
+  if (w.dbg & 8192u) { // profiling library only: per-wave time stamps of this launch (nrtDebugWaveClocks)
+    if ((st = ensure(c, c->b_wave_clock, (size_t)total_waves * 3 * sizeof(unsigned long long)))) return st;
+    c->wave_clock_waves = total_waves;
+  }
+  TraverseArgs<T> a;
+  fill_walk_args(c, l, w, a);
+  fill_launch_args(l, slot, g, d, levels, a);
+  return enqueue_launch(c, l, w, slot, a, g.grid);
+}
+
+const uint64_t kStagedRays = 1ull << 26; // rays per launch of the staged host paths (keeps staging bounded)
+
+// The staged host path of every ray query (the caller holds host_mutex), in pieces of `chunk` rays: upload into st_rays, the launch
+// `make(rays in the piece)` asks for, rec_bytes / flag_bytes per ray of st_hits / st_mask back into recs / flags (null: not copied).
+template <typename T, typename MakeLaunch>
+static nrt_status staged_host_loop(nrt_ctx *c, const typename Wire<T>::Ray *rays, uint64_t n, uint64_t chunk, size_t rec_bytes, size_t flag_bytes,
+                                   void *recs, void *flags, MakeLaunch make) {
+  const size_t ray_bytes = sizeof(typename Wire<T>::Ray);
+  for (uint64_t off = 0; off < n; off += chunk) {
+    const uint64_t m = std::min(chunk, n - off);
+    nrt_status st;
+    if ((st = ensure(c, c->st_rays, m * ray_bytes)) || (rec_bytes && (st = ensure(c, c->st_hits, m * rec_bytes))) || (st = ensure(c, c->st_mask, m * flag_bytes)))
+      return st;
+    HIPCHK(c, hipMemcpyAsync(c->st_rays.p, rays + off, m * ray_bytes, hipMemcpyHostToDevice, c->stream));
+    if ((st = traverse_device<T>(c, make(m)))) return st;
+    if (recs) HIPCHK(c, hipMemcpyAsync((char *)recs + off * rec_bytes, c->st_hits.p, m * rec_bytes, hipMemcpyDeviceToHost, c->stream));
+    if (flags) HIPCHK(c, hipMemcpyAsync((char *)flags + off * flag_bytes, c->st_mask.p, m * flag_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  return NRT_OK;
+}
 // Is `p` page-locked host memory the device can copy from / to asynchronously (hipHostMalloc / nrtHostAlloc / registered)?
 static bool is_pinned_host(const void *p) {
   hipPointerAttribute_t at;
@@ -1291,7 +1339,7 @@ static nrt_status traverse_host(nrt_ctx *c, const typename Wire<T>::Ray *rays, u
       HIPCHK(c, hipEventRecord(c->ev_in[b], c->copy_in));
       HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_in[b], 0));
       if (piece >= 2) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_out[b], 0));
-      st = traverse_device<T>(c, d_r, m, opt, d_h, d_m, c->stream, false, true);
+      st = traverse_device<T>(c, {.kind = Query::Closest, .rays = d_r, .n = m, .opt = opt, .stream = c->stream, .timed = true, .hits = d_h, .mask = d_m});
       if (st) { // (copies into the caller's buffers may still be in flight: let them land before the call returns)
         (void)hipStreamSynchronize(c->copy_in);
         (void)hipStreamSynchronize(c->stream);
@@ -1308,22 +1356,10 @@ static nrt_status traverse_host(nrt_ctx *c, const typename Wire<T>::Ray *rays, u
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return NRT_OK;
   }
-  const uint64_t kMaxChunk = 1ull << 26; // rays per launch (keeps staging bounded)
-  for (uint64_t off = 0; off < n; off += kMaxChunk) {
-    const uint64_t m = std::min(kMaxChunk, n - off);
-    nrt_status st;
-    if ((st = ensure(c, c->st_rays, m * sizeof(Ray)))) return st;
-    if ((st = ensure(c, c->st_hits, m * sizeof(Hit)))) return st;
-    if ((st = ensure(c, c->st_mask, m))) return st;
-    HIPCHK(c, hipMemcpyAsync(c->st_rays.p, rays + off, m * sizeof(Ray), hipMemcpyHostToDevice, c->stream));
-    st = traverse_device<T>(c, (const Ray *)c->st_rays.p, m, opt, (Hit *)c->st_hits.p, (uint8_t *)c->st_mask.p,
-                            c->stream, false, true);
-    if (st) return st;
-    HIPCHK(c, hipMemcpyAsync(hits + off, c->st_hits.p, m * sizeof(Hit), hipMemcpyDeviceToHost, c->stream));
-    if (mask) HIPCHK(c, hipMemcpyAsync(mask + off, c->st_mask.p, m, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-  }
-  return NRT_OK;
+  return staged_host_loop<T>(c, rays, n, kStagedRays, sizeof(Hit), 1, hits, mask, [&](uint64_t m) -> TraverseLaunch<T> {
+    return {.kind = Query::Closest, .rays = (const Ray *)c->st_rays.p, .n = m, .opt = opt, .stream = c->stream, .timed = true,
+            .hits = (Hit *)c->st_hits.p, .mask = (uint8_t *)c->st_mask.p};
+  });
 }
 
 // One host batch spread over several contexts — one per GPU of the node, each holding the same tree (the build is
@@ -1355,7 +1391,7 @@ static nrt_status traverse_share(nrt_ctx *c, uint32_t k, uint32_t num_ctx, const
   if (full_rows) HIPCHK(c, hipMemcpy2DAsync(d_r, rb, rays + k * row_len, rb * num_ctx, rb, full_rows, hipMemcpyHostToDevice, c->stream));
   if (full_rows < my_rows)
     HIPCHK(c, hipMemcpyAsync(d_r + full_rows * row_len, rays + last_row * row_len, last_len * sizeof(Ray), hipMemcpyHostToDevice, c->stream));
-  if ((st = traverse_device<T>(c, d_r, m, opt, d_h, d_m, c->stream, false, false))) return st;
+  if ((st = traverse_device<T>(c, {.kind = Query::Closest, .rays = d_r, .n = m, .opt = opt, .stream = c->stream, .hits = d_h, .mask = d_m}))) return st;
   if (full_rows) {
     HIPCHK(c, hipMemcpy2DAsync(hits + k * row_len, hb * num_ctx, d_h, hb, hb, full_rows, hipMemcpyDeviceToHost, c->stream));
     if (mask) HIPCHK(c, hipMemcpy2DAsync(mask + k * row_len, mbytes * num_ctx, d_m, mbytes, mbytes, full_rows, hipMemcpyDeviceToHost, c->stream));
@@ -1406,7 +1442,7 @@ static nrt_status traverse_count(nrt_ctx *c, const typename Wire<T>::Ray *d_rays
                                  const nrt_trace_options *opt, nrt_trace_counters *out) {
   if (!c || !out) return NRT_ERR_INVALID;
   memset(out, 0, sizeof(*out));
-  nrt_status st = traverse_device<T>(c, d_rays, n, opt, nullptr, nullptr, c->stream, true, false);
+  nrt_status st = traverse_device<T>(c, {.kind = Query::Count, .rays = d_rays, .n = n, .opt = opt, .stream = c->stream});
   if (st) return st;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   unsigned long long h[4];
@@ -1415,6 +1451,26 @@ static nrt_status traverse_count(nrt_ctx *c, const typename Wire<T>::Ray *d_rays
   out->leaves_tested = h[1];
   out->tris_tested = h[2];
   out->max_stack = h[3];
+  return NRT_OK;
+}
+
+// The batch tables of nrtTraverseBatches* (`fn`: the entry point the messages name): a non-empty batch has rays, an occlusion batch
+// its flag array, a closest-hit batch its record array (a call of occlusion batches only may pass no record table).  Counts the rays.
+template <typename T>
+static nrt_status check_batches(nrt_ctx *c, const char *fn, uint32_t nb, const typename Wire<T>::Ray *const *rays, const uint64_t *counts,
+                                typename Wire<T>::Hit *const *hits, uint8_t *const *masks, const uint32_t *flags, uint64_t *total,
+                                uint64_t *total_closest) {
+  *total = *total_closest = 0;
+  if (!rays || !counts) return fail(c, NRT_ERR_INVALID, "%s: NULL argument", fn);
+  for (uint32_t k = 0; k < nb; k++) {
+    if (!counts[k]) continue;
+    const bool occ = flags && (flags[k] & NRT_BATCH_OCCLUSION);
+    if (!rays[k]) return fail(c, NRT_ERR_INVALID, "%s: batch %u has no rays", fn, k);
+    if (occ && !(masks && masks[k])) return fail(c, NRT_ERR_INVALID, "%s: occlusion batch %u has no flag array", fn, k);
+    if (!occ && !(hits && hits[k])) return fail(c, NRT_ERR_INVALID, "%s: batch %u has no hit array", fn, k);
+    *total += counts[k];
+    if (!occ) *total_closest += counts[k];
+  }
   return NRT_OK;
 }
 
@@ -1428,29 +1484,10 @@ static nrt_status traverse_batches_device(nrt_ctx *c, uint32_t nb, const typenam
                                           uint8_t *const *d_masks, const uint32_t *flags, hipStream_t s) {
   if (!c) return NRT_ERR_INVALID;
   if (nb == 0) return NRT_OK;
-  if (!d_rays || !counts) return fail(c, NRT_ERR_INVALID, "nrtTraverseBatchesDevice: NULL argument");
-  for (uint32_t k = 0; k < nb; k++)
-    if (flags && (flags[k] & NRT_BATCH_OCCLUSION) && counts[k] && !(d_masks && d_masks[k]))
-      return fail(c, NRT_ERR_INVALID, "nrtTraverseBatchesDevice: occlusion batch %u has no flag array", k);
-  // as nrtTraverseBatchDevice: a closest-hit batch needs its record array — an occlusion batch does not, and a call made of
-  // occlusion batches only may pass no record table at all
-  std::vector<typename Wire<T>::Hit *> no_hits;
-  if (!d_hits) {
-    no_hits.assign(nb, nullptr);
-    d_hits = no_hits.data();
-  }
-  for (uint32_t k = 0; k < nb; k++)
-    if (counts[k] && !(flags && (flags[k] & NRT_BATCH_OCCLUSION)) && !d_hits[k])
-      return fail(c, NRT_ERR_INVALID, "nrtTraverseBatchesDevice: batch %u has no hit array", k);
+  uint64_t total, total_closest;
+  const nrt_status bad = check_batches<T>(c, "nrtTraverseBatchesDevice", nb, d_rays, counts, d_hits, d_masks, flags, &total, &total_closest);
+  if (bad || total == 0) return bad;
   TraverseBatches<T> mb;
-  mb.nb = 0;
-  uint64_t total = 0;
-  for (uint32_t k = 0; k < nb; k++) {
-    if (counts[k] == 0) continue;
-    if (!d_rays[k]) return fail(c, NRT_ERR_INVALID, "nrtTraverseBatchesDevice: batch %u has no rays", k);
-    total += counts[k];
-  }
-  if (total == 0) return NRT_OK;
   const bool one_launch = sizeof(T) == 4 && c->prec == 4 && c->prim_kind == kPrimTriangles && c->wide && c->d_wide && total <= 0x7FFFFFFFull;
   uint32_t k = 0;
   while (k < nb) { // groups of up to kMaxBatches non-empty batches per launch
@@ -1461,7 +1498,7 @@ static nrt_status traverse_batches_device(nrt_ctx *c, uint32_t nb, const typenam
       if (counts[k]) {
         const bool occ = flags && (flags[k] & NRT_BATCH_OCCLUSION);
         mb.rays[mb.nb] = d_rays[k];
-        mb.hits[mb.nb] = occ ? nullptr : d_hits[k]; // (an occlusion query writes the flags only)
+        mb.hits[mb.nb] = occ ? nullptr : d_hits[k]; // (an occlusion query writes the flags only: its call may have no record table)
         mb.mask[mb.nb] = d_masks ? d_masks[k] : nullptr;
         mb.count[mb.nb] = counts[k];
         if (occ) mb.anyhit |= 1u << mb.nb;
@@ -1473,12 +1510,15 @@ static nrt_status traverse_batches_device(nrt_ctx *c, uint32_t nb, const typenam
     if (mb.nb == 0) break;
     nrt_status st;
     if (one_launch && mb.nb > 1) {
-      st = traverse_device<T>(c, nullptr, n, opt, nullptr, nullptr, s, false, false, nullptr, false, &mb);
+      st = traverse_device<T>(c, {.kind = Query::MultiBatch, .rays = mb.rays[0], .n = n, .opt = opt, .stream = s, .hits = mb.hits[0],
+                                  .mask = mb.mask[0], .batches = &mb}); // (rays / hits / mask: the first batch's — the kernel reads the table)
       if (st) return st;
     } else {
-      for (uint32_t j = 0; j < mb.nb; j++)
-        if ((st = traverse_device<T>(c, mb.rays[j], mb.count[j], opt, mb.hits[j], mb.mask[j], s, false, false, nullptr, ((mb.anyhit >> j) & 1u) != 0u)))
-          return st;
+      for (uint32_t j = 0; j < mb.nb; j++) {
+        const Query kind = ((mb.anyhit >> j) & 1u) ? Query::Occlusion : Query::Closest;
+        st = traverse_device<T>(c, {.kind = kind, .rays = mb.rays[j], .n = mb.count[j], .opt = opt, .stream = s, .hits = mb.hits[j], .mask = mb.mask[j]});
+        if (st) return st;
+      }
     }
   }
   return NRT_OK;
@@ -1495,22 +1535,12 @@ static nrt_status traverse_batches_host(nrt_ctx *c, uint32_t nb, const typename 
   typedef typename Wire<T>::Hit Hit;
   if (!c) return NRT_ERR_INVALID;
   if (nb == 0) return NRT_OK;
-  if (!rays || !counts) return fail(c, NRT_ERR_INVALID, "nrtTraverseBatches: NULL argument");
-  uint64_t total = 0, total_closest = 0; // (record staging is sized over the closest-hit batches only)
-  for (uint32_t k = 0; k < nb; k++) {
-    if (!counts[k]) continue;
-    const bool occ = flags && (flags[k] & NRT_BATCH_OCCLUSION);
-    if (!rays[k]) return fail(c, NRT_ERR_INVALID, "nrtTraverseBatches: batch %u has no rays", k);
-    if (occ && !(masks && masks[k])) return fail(c, NRT_ERR_INVALID, "nrtTraverseBatches: occlusion batch %u has no flag array", k);
-    if (!occ && !(hits && hits[k])) return fail(c, NRT_ERR_INVALID, "nrtTraverseBatches: batch %u has no hit array", k);
-    total += counts[k];
-    if (!occ) total_closest += counts[k];
-  }
-  if (total == 0) return NRT_OK;
-  if (total > (1ull << 26)) return fail(c, NRT_ERR_INVALID, "nrtTraverseBatches: more than 2^26 rays in one call");
+  uint64_t total, total_closest; // (record staging is sized over the closest-hit batches only)
+  nrt_status st = check_batches<T>(c, "nrtTraverseBatches", nb, rays, counts, hits, masks, flags, &total, &total_closest);
+  if (st || total == 0) return st;
+  if (total > kStagedRays) return fail(c, NRT_ERR_INVALID, "nrtTraverseBatches: more than 2^26 rays in one call");
   std::lock_guard<std::mutex> host_lock(c->host_mutex);
   HIPCHK(c, hipSetDevice(c->device));
-  nrt_status st;
   if ((st = ensure(c, c->st_rays, total * sizeof(Ray))) || (st = ensure(c, c->st_hits, std::max<uint64_t>(1, total_closest) * sizeof(Hit))) ||
       (st = ensure(c, c->st_mask, total)))
     return st;
@@ -1550,22 +1580,12 @@ static nrt_status occluded_host(nrt_ctx *c, const typename Wire<T>::Ray *rays, u
   if (!c) return NRT_ERR_INVALID;
   if (n == 0) return NRT_OK;
   if (!rays || !mask) return fail(c, NRT_ERR_INVALID, "nrtOccludedBatch: NULL rays/mask");
-  typedef typename Wire<T>::Ray Ray;
   std::lock_guard<std::mutex> host_lock(c->host_mutex);
   HIPCHK(c, hipSetDevice(c->device));
-  const uint64_t kMaxChunk = 1ull << 26;
-  for (uint64_t off = 0; off < n; off += kMaxChunk) {
-    const uint64_t m = std::min(kMaxChunk, n - off);
-    nrt_status st;
-    if ((st = ensure(c, c->st_rays, m * sizeof(Ray)))) return st;
-    if ((st = ensure(c, c->st_mask, m))) return st;
-    HIPCHK(c, hipMemcpyAsync(c->st_rays.p, rays + off, m * sizeof(Ray), hipMemcpyHostToDevice, c->stream));
-    st = traverse_device<T>(c, (const Ray *)c->st_rays.p, m, opt, nullptr, (uint8_t *)c->st_mask.p, c->stream, false, true, nullptr, true);
-    if (st) return st;
-    HIPCHK(c, hipMemcpyAsync(mask + off, c->st_mask.p, m, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-  }
-  return NRT_OK;
+  return staged_host_loop<T>(c, rays, n, kStagedRays, 0, 1, nullptr, mask, [&](uint64_t m) -> TraverseLaunch<T> {
+    return {.kind = Query::Occlusion, .rays = (const typename Wire<T>::Ray *)c->st_rays.p, .n = m, .opt = opt, .stream = c->stream, .timed = true,
+            .mask = (uint8_t *)c->st_mask.p};
+  });
 }
 
 // ---------------------------------------------------------------------------
@@ -1590,8 +1610,8 @@ static nrt_status multihit_device(nrt_ctx *c, const typename Wire<T>::Ray *d_ray
   if (!c) return NRT_ERR_INVALID;
   nrt_status st = multihit_check<T>(c, d_rays, n, max_hits, d_hits);
   if (st || n == 0) return st;
-  const MultiHitLaunch mh = {max_hits, d_counts};
-  return traverse_device<T>(c, d_rays, n, opt, d_hits, nullptr, s, false, true, nullptr, false, nullptr, &mh);
+  return traverse_device<T>(c, {.kind = Query::MultiHit, .rays = d_rays, .n = n, .opt = opt, .stream = s, .timed = true, .hits = d_hits,
+                                .max_hits = max_hits, .hit_counts = d_counts});
 }
 
 template <typename T>
@@ -1606,21 +1626,10 @@ static nrt_status multihit_host(nrt_ctx *c, const typename Wire<T>::Ray *rays, u
   HIPCHK(c, hipSetDevice(c->device));
   // rays per launch: the staged records stay within 256 MiB whatever K is
   const uint64_t chunk = std::max<uint64_t>(1u, std::min<uint64_t>(1ull << 26, (256ull << 20) / ((uint64_t)max_hits * sizeof(Hit))));
-  for (uint64_t off = 0; off < n; off += chunk) {
-    const uint64_t m = std::min(chunk, n - off);
-    if ((st = ensure(c, c->st_rays, m * sizeof(Ray)))) return st;
-    if ((st = ensure(c, c->st_hits, m * max_hits * sizeof(Hit)))) return st;
-    if ((st = ensure(c, c->st_mask, m * sizeof(uint32_t)))) return st;
-    HIPCHK(c, hipMemcpyAsync(c->st_rays.p, rays + off, m * sizeof(Ray), hipMemcpyHostToDevice, c->stream));
-    const MultiHitLaunch mh = {max_hits, counts ? (uint32_t *)c->st_mask.p : nullptr};
-    st = traverse_device<T>(c, (const Ray *)c->st_rays.p, m, opt, (Hit *)c->st_hits.p, nullptr, c->stream, false, true, nullptr, false,
-                            nullptr, &mh);
-    if (st) return st;
-    HIPCHK(c, hipMemcpyAsync(hits + off * max_hits, c->st_hits.p, m * max_hits * sizeof(Hit), hipMemcpyDeviceToHost, c->stream));
-    if (counts) HIPCHK(c, hipMemcpyAsync(counts + off, c->st_mask.p, m * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-  }
-  return NRT_OK;
+  return staged_host_loop<T>(c, rays, n, chunk, max_hits * sizeof(Hit), sizeof(uint32_t), hits, counts, [&](uint64_t m) -> TraverseLaunch<T> {
+    return {.kind = Query::MultiHit, .rays = (const Ray *)c->st_rays.p, .n = m, .opt = opt, .stream = c->stream, .timed = true,
+            .hits = (Hit *)c->st_hits.p, .max_hits = max_hits, .hit_counts = counts ? (uint32_t *)c->st_mask.p : nullptr};
+  });
 }
 
 extern "C" {
@@ -1662,7 +1671,8 @@ nrt_status nrtTraverseBatchCylindersDevice_f32(nrt_ctx *c, const nrt_ray_f32 *r,
                                                nrt_cyl_hit_f32 *h, uint8_t *m, void *s) {
   if (!c) return NRT_ERR_INVALID;
   if (n && !h) return fail(c, NRT_ERR_INVALID, "nrtTraverseBatchCylindersDevice: NULL hits");
-  return traverse_device<float>(c, r, n, o, nullptr, m, (hipStream_t)s, false, true, h);
+  return traverse_device<float>(c, {.kind = Query::Cylinders, .rays = r, .n = n, .opt = o, .stream = (hipStream_t)s, .timed = true, .mask = m,
+                                    .cyl_hits = h});
 }
 
 nrt_status nrtTraverseBatchCylinders_f32(nrt_ctx *c, const nrt_ray_f32 *rays, uint64_t n, const nrt_trace_options *opt,
@@ -1672,22 +1682,10 @@ nrt_status nrtTraverseBatchCylinders_f32(nrt_ctx *c, const nrt_ray_f32 *rays, ui
   if (!rays || !hits) return fail(c, NRT_ERR_INVALID, "nrtTraverseBatchCylinders: NULL rays/hits");
   std::lock_guard<std::mutex> host_lock(c->host_mutex);
   HIPCHK(c, hipSetDevice(c->device));
-  const uint64_t kMaxChunk = 1ull << 26;
-  for (uint64_t off = 0; off < n; off += kMaxChunk) {
-    const uint64_t m = std::min(kMaxChunk, n - off);
-    nrt_status st;
-    if ((st = ensure(c, c->st_rays, m * sizeof(nrt_ray_f32)))) return st;
-    if ((st = ensure(c, c->st_hits, m * sizeof(nrt_cyl_hit_f32)))) return st;
-    if ((st = ensure(c, c->st_mask, m))) return st;
-    HIPCHK(c, hipMemcpyAsync(c->st_rays.p, rays + off, m * sizeof(nrt_ray_f32), hipMemcpyHostToDevice, c->stream));
-    st = traverse_device<float>(c, (const nrt_ray_f32 *)c->st_rays.p, m, opt, nullptr, (uint8_t *)c->st_mask.p, c->stream, false,
-                                true, c->st_hits.p);
-    if (st) return st;
-    HIPCHK(c, hipMemcpyAsync(hits + off, c->st_hits.p, m * sizeof(nrt_cyl_hit_f32), hipMemcpyDeviceToHost, c->stream));
-    if (mask) HIPCHK(c, hipMemcpyAsync(mask + off, c->st_mask.p, m, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-  }
-  return NRT_OK;
+  return staged_host_loop<float>(c, rays, n, kStagedRays, sizeof(nrt_cyl_hit_f32), 1, hits, mask, [&](uint64_t m) -> TraverseLaunch<float> {
+    return {.kind = Query::Cylinders, .rays = (const nrt_ray_f32 *)c->st_rays.p, .n = m, .opt = opt, .stream = c->stream, .timed = true,
+            .mask = (uint8_t *)c->st_mask.p, .cyl_hits = c->st_hits.p};
+  });
 }
 
 nrt_status nrtOccludedBatch_f32(nrt_ctx *c, const nrt_ray_f32 *r, uint64_t n, const nrt_trace_options *o, uint8_t *m) {
@@ -1699,12 +1697,12 @@ nrt_status nrtOccludedBatch_f64(nrt_ctx *c, const nrt_ray_f64 *r, uint64_t n, co
 nrt_status nrtOccludedBatchDevice_f32(nrt_ctx *c, const nrt_ray_f32 *r, uint64_t n, const nrt_trace_options *o, uint8_t *m, void *s) {
   if (!c) return NRT_ERR_INVALID;
   if (n && !m) return fail(c, NRT_ERR_INVALID, "nrtOccludedBatchDevice: NULL mask");
-  return traverse_device<float>(c, r, n, o, nullptr, m, (hipStream_t)s, false, true, nullptr, true);
+  return traverse_device<float>(c, {.kind = Query::Occlusion, .rays = r, .n = n, .opt = o, .stream = (hipStream_t)s, .timed = true, .mask = m});
 }
 nrt_status nrtOccludedBatchDevice_f64(nrt_ctx *c, const nrt_ray_f64 *r, uint64_t n, const nrt_trace_options *o, uint8_t *m, void *s) {
   if (!c) return NRT_ERR_INVALID;
   if (n && !m) return fail(c, NRT_ERR_INVALID, "nrtOccludedBatchDevice: NULL mask");
-  return traverse_device<double>(c, r, n, o, nullptr, m, (hipStream_t)s, false, true, nullptr, true);
+  return traverse_device<double>(c, {.kind = Query::Occlusion, .rays = r, .n = n, .opt = o, .stream = (hipStream_t)s, .timed = true, .mask = m});
 }
 
 nrt_status nrtSetSpheres_f32(nrt_ctx *c, const float *centers, const float *radii, uint32_t n) {
@@ -1751,13 +1749,13 @@ nrt_status nrtTraverseBatchDevice_f32(nrt_ctx *c, const nrt_ray_f32 *r, uint64_t
                                       nrt_hit_f32 *h, uint8_t *m, void *s) {
   if (!c) return NRT_ERR_INVALID;
   if (n && !h) return fail(c, NRT_ERR_INVALID, "nrtTraverseBatchDevice: NULL hits");
-  return traverse_device<float>(c, r, n, o, h, m, (hipStream_t)s, false, true);
+  return traverse_device<float>(c, {.kind = Query::Closest, .rays = r, .n = n, .opt = o, .stream = (hipStream_t)s, .timed = true, .hits = h, .mask = m});
 }
 nrt_status nrtTraverseBatchDevice_f64(nrt_ctx *c, const nrt_ray_f64 *r, uint64_t n, const nrt_trace_options *o,
                                       nrt_hit_f64 *h, uint8_t *m, void *s) {
   if (!c) return NRT_ERR_INVALID;
   if (n && !h) return fail(c, NRT_ERR_INVALID, "nrtTraverseBatchDevice: NULL hits");
-  return traverse_device<double>(c, r, n, o, h, m, (hipStream_t)s, false, true);
+  return traverse_device<double>(c, {.kind = Query::Closest, .rays = r, .n = n, .opt = o, .stream = (hipStream_t)s, .timed = true, .hits = h, .mask = m});
 }
 
 nrt_status nrtTraverseBatchMulti_f32(nrt_ctx *const *ctxs, uint32_t num_ctx, const nrt_ray_f32 *r, uint64_t n, uint64_t row_len,
