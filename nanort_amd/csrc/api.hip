@@ -21,59 +21,11 @@
 #include <string>
 #include <vector>
 
-#include "common.h"
+#include "kernels.h"
 #include "launch_plan.h"
 #ifdef NRT_PROF
 #include "../../include/nanort_hip_prof.h"
 #endif
-
-namespace nrt {
-template <typename T>
-hipError_t launch_traverse(const TraverseArgs<T> &, unsigned grid, bool count, int lds_stack, hipStream_t);
-template <typename T>
-int traverse_blocks_per_cu(int lds_stack);
-template <typename T>
-hipError_t launch_traverse_wide(const TraverseArgs<T> &, unsigned grid, int lds_stack, int prim_kind, hipStream_t, const char **name_out);
-template <typename T>
-int traverse_wide_blocks_per_cu(int lds_stack, int prim_kind, bool wide4);
-template <typename T>
-hipError_t launch_traverse_multihit(const TraverseArgs<T> &, uint32_t max_hits, uint32_t *counts, unsigned grid, hipStream_t); // (multihit.hip)
-template <typename T>
-int traverse_multihit_blocks_per_cu();
-template <typename T>
-hipError_t launch_gather_leaf_spheres(const uint32_t *, const T *, const T *, LeafSphere<T> *, uint32_t, hipStream_t);
-template <typename T>
-hipError_t launch_gather_leaf_cylinders(const uint32_t *, const T *, const T *, LeafCylinder<T> *, uint32_t, hipStream_t);
-hipError_t launch_cylinder_post(const nrt_ray_f32 *, const nrt_hit_f32 *, const uint8_t *, const float *, uint32_t, void *,
-                                uint8_t *, DoneRec *, DoneCount *, uint32_t, hipStream_t);
-template <typename T>
-hipError_t launch_make_wide(const typename Wire<T>::Node *, uint32_t, uint32_t packed, uint32_t *scratch, WideNode<T> *, Wide4Node<T> *,
-                            uint32_t scramble_mod, hipStream_t);
-template <typename T>
-hipError_t launch_gather_leaf_tris(const uint32_t *, const uint32_t *, const T *, LeafTri<T> *,
-                                   uint32_t, hipStream_t);
-struct BuildResult {
-  uint64_t num_nodes;
-  uint32_t max_depth, num_leaves, num_branches, max_leaf_count;
-};
-// (build.hip) enqueues a whole build; its size and statistics arrive in `pinned` behind `ev`: gpu_build_result waits for them
-template <typename T>
-hipError_t gpu_build(hipStream_t s, const T *d_verts, const uint32_t *d_faces, const T *d_radii, bool cylinders, const uint32_t *d_prim_map, uint32_t num_faces,
-                     uint32_t min_leaf, uint32_t max_depth, uint32_t bin_size, unsigned build_flags, // (bit 0: Morton pre-pass, bit 1: one-node-per-step subtree kernel)
-                     DevBuf *workspace, DevBuf *nodes_buf, DevBuf *indices_buf, void *pinned, hipEvent_t ev, std::string *err);
-hipError_t gpu_build_result(const void *pinned, hipEvent_t ev, BuildResult *res);
-// (refit.hip) the per-tree level plan of a refit, and one refit over it
-size_t refit_plan_bytes(uint32_t tree_depth, uint64_t num_nodes);
-template <typename T>
-hipError_t launch_refit_plan(const typename Wire<T>::Node *nodes, uint64_t num_nodes, uint32_t num_branch_records, uint32_t tree_depth,
-                             uint32_t root_is_branch, uint32_t *plan, hipStream_t s);
-template <typename T>
-hipError_t launch_refit(const void *src, size_t stride, bool aligned, uint32_t nv, T *verts, const uint32_t *faces, const uint32_t *indices,
-                        typename Wire<T>::Node *nodes, uint64_t num_nodes, uint32_t num_branch_records, uint32_t tree_depth,
-                        const uint32_t *plan, hipStream_t s);
-hipError_t launch_cylinder_segments(const float *verts, const float *radii, const uint32_t *seg_off, uint32_t n, float *seg_verts,
-                                    float *seg_radii, uint32_t *seg_prim, hipStream_t s);
-} // namespace nrt
 
 using namespace nrt;
 
@@ -842,7 +794,7 @@ static nrt_status build(nrt_ctx *c, const typename Wire<T>::BuildOptions *opt, n
   const uint32_t build_n = segs ? c->num_segs : c->num_faces;
   hipError_t e = gpu_build<T>(c->stream, segs ? (const T *)c->b_seg_verts.p : (const T *)c->d_verts, c->d_faces, segs ? (const T *)c->b_seg_radii.p : (const T *)c->d_radii,
                               c->prim_kind == kPrimCylinders, segs ? (const uint32_t *)c->b_seg_prim.p : nullptr, build_n, min_leaf, max_depth,
-                              bin_size, (c->morton ? 1u : 0u) | (c->subtree_rows ? 0u : 2u), &c->b_build_ws, &c->b_nodes, &c->b_indices, c->build_state, c->ev_build_state, &err);
+                              bin_size, (c->morton ? kBuildMorton : 0u) | (c->subtree_rows ? 0u : kBuildSubtreeDfs), &c->b_build_ws, &c->b_nodes, &c->b_indices, c->build_state, c->ev_build_state, &err);
   if (e != hipSuccess) return fail(c, NRT_ERR_DEVICE, "nrtBuild: %s (%s)", err.c_str(), hipGetErrorString(e));
   // everything is enqueued; the leaf-ordered primitive records need the index array only, so they are enqueued too before
   // the host waits for the tree's size (the GPU stays busy meanwhile)
@@ -1207,7 +1159,7 @@ static nrt_status enqueue_launch(nrt_ctx *c, const TraverseLaunch<T> &l, const W
     HIPCHK(c, launch_traverse_multihit<T>(a, l.max_hits, l.hit_counts, grid, s));
     c->last_kernel = sizeof(T) == 4 ? "nrt::k_traverse_multihit<float>" : "nrt::k_traverse_multihit<double>";
   } else if (w.wide()) {
-    HIPCHK(c, launch_traverse_wide<T>(a, grid, c->wide_stack, c->prim_kind, s, &c->last_kernel));
+    HIPCHK(c, launch_traverse_wide<T>(a, grid, w.lds_entries, c->prim_kind, s, &c->last_kernel));
   } else {
     HIPCHK(c, launch_traverse<T>(a, grid, count, c->lds_stack, s));
     c->last_kernel = sizeof(T) == 4 ? "nrt::k_traverse<float>" : "nrt::k_traverse<double>";

@@ -43,17 +43,10 @@
 #include <string>
 #include <vector>
 
-#include "common.h"
+#include "kernels.h"
 #include "minmax_dev.h"
 
 namespace nrt {
-
-enum : unsigned { kBuildMorton = 1u, kBuildSubtreeDfs = 2u }; // gpu_build's build_flags
-
-struct BuildResult {
-  uint64_t num_nodes;
-  uint32_t max_depth, num_leaves, num_branches, max_leaf_count;
-};
 
 constexpr int kSmall = 256;     // nodes at or below this many primitives are binned with kSmallBins bins (part of the tree's definition)
 #ifndef NRT_BUILD_HANDOFF
@@ -201,10 +194,6 @@ __device__ __forceinline__ T half_area(const T mn[3], const T mx[3]) {
   return a * b + b * c + c * a; // CalculateSurfaceArea / 2 (nanort.h:1278-1283)
 }
 
-__device__ __forceinline__ unsigned lane_id_b() {
-  return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-}
-
 // ---- DPP (data-parallel primitive) moves inside 16-lane rows: VALU operand modifiers, no LDS
 // crossbar (ds_bpermute) round trip.  row_shr:n = 0x110+n, row_shl:n = 0x100+n; a lane without a
 // source keeps `old`, so `old` = the identity of the operation gives a clean scan step.
@@ -225,54 +214,6 @@ __device__ __forceinline__ double dpp_mov(double old, double src) {
 template <int CTRL>
 __device__ __forceinline__ uint32_t dpp_mov(uint32_t old, uint32_t src) {
   return dpp_u32<CTRL>(old, src);
-}
-
-// One scan step over a {count, AABB} record inside each 16-lane row.
-template <typename T, int CTRL>
-__device__ __forceinline__ void row_scan_step(uint32_t &cnt, T mn[3], T mx[3]) {
-  cnt += dpp_mov<CTRL>(0u, cnt);
-#pragma unroll
-  for (int d = 0; d < 3; d++) {
-    mn[d] = tmin(mn[d], dpp_mov<CTRL>(Lim<T>::max(), mn[d]));
-    mx[d] = tmax(mx[d], dpp_mov<CTRL>(-Lim<T>::max(), mx[d]));
-  }
-}
-// inclusive prefix (lanes 0..i of the row) / suffix (lanes i..15 of the row)
-template <typename T>
-__device__ __forceinline__ void row_prefix(uint32_t &cnt, T mn[3], T mx[3]) {
-  row_scan_step<T, 0x111>(cnt, mn, mx);
-  row_scan_step<T, 0x112>(cnt, mn, mx);
-  row_scan_step<T, 0x114>(cnt, mn, mx);
-  row_scan_step<T, 0x118>(cnt, mn, mx);
-}
-template <typename T>
-__device__ __forceinline__ void row_suffix(uint32_t &cnt, T mn[3], T mx[3]) {
-  row_scan_step<T, 0x101>(cnt, mn, mx);
-  row_scan_step<T, 0x102>(cnt, mn, mx);
-  row_scan_step<T, 0x104>(cnt, mn, mx);
-  row_scan_step<T, 0x108>(cnt, mn, mx);
-}
-// all-reduce min / max over the 64 lanes: 4 DPP steps inside rows (quad_perm [1,0,3,2], [2,3,0,1],
-// row_half_mirror, row_mirror), then two cross-row exchanges.
-template <typename T>
-__device__ __forceinline__ T wave_min(T x) {
-  x = tmin(x, dpp_mov<0xB1>(x, x));
-  x = tmin(x, dpp_mov<0x4E>(x, x));
-  x = tmin(x, dpp_mov<0x141>(x, x));
-  x = tmin(x, dpp_mov<0x140>(x, x));
-  x = tmin(x, __shfl_xor(x, 16));
-  x = tmin(x, __shfl_xor(x, 32));
-  return x;
-}
-template <typename T>
-__device__ __forceinline__ T wave_max(T x) {
-  x = tmax(x, dpp_mov<0xB1>(x, x));
-  x = tmax(x, dpp_mov<0x4E>(x, x));
-  x = tmax(x, dpp_mov<0x141>(x, x));
-  x = tmax(x, dpp_mov<0x140>(x, x));
-  x = tmax(x, __shfl_xor(x, 16));
-  x = tmax(x, __shfl_xor(x, 32));
-  return x;
 }
 
 // ---------------------------------------------------------------------------
@@ -944,21 +885,9 @@ __global__ __launch_bounds__(1024) void k_level_setup(TopNode<T> *top, uint32_t 
   }
 }
 
-__device__ __forceinline__ uint32_t find_task(const uint32_t *chunk_base, uint32_t num_active, uint32_t chunk) {
-  // last a with chunk_base[a] <= chunk
-  uint32_t lo = 0, hi = num_active;
-  while (hi - lo > 1) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if (chunk_base[mid] <= chunk)
-      lo = mid;
-    else
-      hi = mid;
-  }
-  return lo;
-}
-
-// The same search by one full wave, 64 probes per round (two rounds up to 4096 active nodes, where the binary search is a
-// chain of twelve dependent loads at the head of every k_bin / k_partition block).
+// The active node a chunk belongs to — the last a with chunk_base[a] <= chunk — searched by one full wave, 64 probes per round
+// (two rounds up to 4096 active nodes, where a binary search is a chain of twelve dependent loads at the head of every k_bin /
+// k_partition block).
 __device__ __forceinline__ uint32_t find_task_wave(const uint32_t *chunk_base, uint32_t num_active, uint32_t chunk, unsigned lane) {
   uint32_t lo = 0, hi = num_active; // chunk_base[lo] <= chunk, and (hi == num_active or chunk_base[hi] > chunk)
   while (hi - lo > 1) {
@@ -2471,8 +2400,6 @@ __global__ __launch_bounds__(64) void k_subtree_rows(TopNode<T> *top, const uint
 #endif
 constexpr uint32_t kLayoutLds = NRT_LAYOUT_LDS; // top arrays up to this many nodes are laid out from LDS (2 x 4 bytes per node, dynamic)
 constexpr uint32_t kLayoutOwn = kLayoutLds / 1024;
-template <typename T>
-__device__ __forceinline__ uint32_t layout_contribution(const TopNode<T> &t) { return t.kind == KIND_SMALL ? t.size : 1u; }
 
 // (the walk-up stops below depth kLayoutCut: the few nodes above it — on which every node's additions would pile up —
 // get their sizes level by level from their children afterwards)
@@ -2990,9 +2917,6 @@ hipError_t gpu_build_result(const void *pinned, hipEvent_t ev, BuildResult *res)
   return hipSuccess;
 }
 
-template hipError_t gpu_build<float>(hipStream_t, const float *, const uint32_t *, const float *, bool, const uint32_t *, uint32_t, uint32_t,
-                                     uint32_t, uint32_t, unsigned, DevBuf *, DevBuf *, DevBuf *, void *, hipEvent_t, std::string *);
-template hipError_t gpu_build<double>(hipStream_t, const double *, const uint32_t *, const double *, bool, const uint32_t *, uint32_t, uint32_t,
-                                      uint32_t, uint32_t, unsigned, DevBuf *, DevBuf *, DevBuf *, void *, hipEvent_t, std::string *);
+NRT_INSTANTIATE_F32_F64(gpu_build)
 
 } // namespace nrt

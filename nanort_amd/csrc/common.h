@@ -12,6 +12,7 @@
 #include <stdlib.h>
 
 #include "../../include/nanort_hip.h"
+#include "walk_variant.h" // the primitive kinds, kWide4LdsStack
 
 // roctx ranges: compiled into the PROFILING library only (-DNRT_PROF -DNRT_ROCTX, nanort_amd/csrc/Makefile), so that a
 // `rocprofv3 --marker-trace --kernel-trace` run of tools/ names the build phases and every traversal launch; the product
@@ -129,7 +130,6 @@ struct LeafCylinder {
   uint32_t prim_id;
 };
 static_assert(sizeof(LeafCylinder<float>) == 36, "LeafCylinder<float>");
-enum : int { kPrimTriangles = 0, kPrimSpheres = 1, kPrimCylinders = 2 };
 static_assert(sizeof(LeafTri<double>) == 80, "LeafTri<double>");
 
 // Private traversal layout: one record per BRANCH node holding BOTH children's boxes, so a
@@ -180,10 +180,6 @@ struct alignas(16) Wide4Node {
 static_assert(sizeof(Wide4Node<float>) == 128, "Wide4Node<float>");
 static_assert(sizeof(Wide4Node<double>) == 224, "Wide4Node<double>");
 constexpr uint32_t kWide4Empty = 0xFFFFFFFFu;
-#ifndef NRT_W4_LDS_STACK
-#define NRT_W4_LDS_STACK 12
-#endif
-constexpr int kWide4LdsStack = NRT_W4_LDS_STACK; // per-lane LDS stack entries of the WIDTH = 4 variants (24 KiB per block: six blocks per CU)
 constexpr uint32_t kLeafBit = 0x80000000u;
 constexpr uint32_t kPackedFirstBits = 27;
 constexpr uint32_t kPackedFirstMask = (1u << kPackedFirstBits) - 1u;

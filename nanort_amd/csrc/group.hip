@@ -27,9 +27,8 @@
 #include <string>
 #include <vector>
 
-#include "common.h"
+#include "kernels.h"
 
-int nrt_internal_device(const nrt_ctx *c); // api.hip
 using namespace nrt;
 
 namespace {

@@ -1,0 +1,81 @@
+// nanort_amd/csrc/kernels.h — the interface between the .hip files of this directory: every function one of them defines and
+// another calls is declared here, once, and every one of them that defines or calls such a function includes this header.
+// Not part of the C ABI (include/nanort_hip.h).
+#pragma once
+#include <string>
+
+#include "common.h"
+
+// ---- api.hip: what the scene and group code may ask of a context ----------------------------------------------------------
+nrt_status nrt_internal_tree_view(nrt_ctx *c, nrt::TreeViewF32 *out);
+uint64_t nrt_internal_generation(const nrt_ctx *c); // counts the context's rebuilds
+int nrt_internal_device(const nrt_ctx *c);
+
+namespace nrt {
+
+// The templates below are defined in one .hip file and used from another: their definitions' file instantiates them for both precisions.
+#define NRT_INSTANTIATE_F32_F64(fn)       \
+  template decltype(fn<float>) fn<float>; \
+  template decltype(fn<double>) fn<double>;
+
+// ---- traverse.hip -----------------------------------------------------------------------------------------------------
+// (the *_blocks_per_cu functions: resident blocks per CU of the kernel such a launch runs, what the persistent grid is sized by)
+template <typename T>
+hipError_t launch_traverse(const TraverseArgs<T> &, unsigned grid, bool count, int lds_entries, hipStream_t);
+template <typename T>
+int traverse_blocks_per_cu(int lds_entries);
+// (walk_variant.h: the instantiation follows from `args`, the context's primitive kind and the LDS depth of its one-level walk;
+// `name_out`, optional, receives the kernel's name as rocprofv3 prints it without the argument list)
+template <typename T>
+hipError_t launch_traverse_wide(const TraverseArgs<T> &args, unsigned grid, int lds_entries, int prim_kind, hipStream_t, const char **name_out);
+template <typename T>
+int traverse_wide_blocks_per_cu(int lds_entries, int prim_kind, bool wide4);
+hipError_t launch_scene_trace(const SceneTraceArgs &args, unsigned grid, hipStream_t s);
+int scene_trace_blocks_per_cu();
+hipError_t launch_scene_walk(const SceneWalkArgs &args, unsigned grid, hipStream_t s);
+int scene_walk_blocks_per_cu();
+// scratch: tile counts (ceil(n/1024) u32) followed by dense_of (n u32)
+template <typename T>
+hipError_t launch_make_wide(const typename Wire<T>::Node *nodes, uint32_t n, uint32_t packed, uint32_t *scratch, WideNode<T> *wide,
+                            Wide4Node<T> *wide4, uint32_t scramble_mod, hipStream_t s);
+template <typename T>
+hipError_t launch_gather_leaf_tris(const uint32_t *indices, const uint32_t *faces, const T *verts, LeafTri<T> *out, uint32_t n, hipStream_t s);
+template <typename T>
+hipError_t launch_gather_leaf_spheres(const uint32_t *indices, const T *centers, const T *radii, LeafSphere<T> *out, uint32_t n, hipStream_t s);
+template <typename T>
+hipError_t launch_gather_leaf_cylinders(const uint32_t *indices, const T *verts, const T *radii, LeafCylinder<T> *out, uint32_t n, hipStream_t s);
+hipError_t launch_cylinder_post(const nrt_ray_f32 *rays, const nrt_hit_f32 *compact, const uint8_t *bits, const float *verts, uint32_t n,
+                                void *out, uint8_t *mask, DoneRec *done_rec, DoneCount *done_count, uint32_t done_seq, hipStream_t s);
+
+// ---- multihit.hip -----------------------------------------------------------------------------------------------------
+template <typename T>
+hipError_t launch_traverse_multihit(const TraverseArgs<T> &args, uint32_t max_hits, uint32_t *counts, unsigned grid, hipStream_t s);
+template <typename T>
+int traverse_multihit_blocks_per_cu();
+
+// ---- build.hip --------------------------------------------------------------------------------------------------------
+enum : unsigned { kBuildMorton = 1u, kBuildSubtreeDfs = 2u }; // gpu_build's build_flags: Morton pre-pass, one-node-per-step subtree kernel
+struct BuildResult {
+  uint64_t num_nodes;
+  uint32_t max_depth, num_leaves, num_branches, max_leaf_count;
+};
+// enqueues a whole build; its size and statistics arrive in `pinned` behind `ev`: gpu_build_result waits for them
+template <typename T>
+hipError_t gpu_build(hipStream_t s, const T *d_verts, const uint32_t *d_faces, const T *d_radii, bool cylinders, const uint32_t *d_prim_map,
+                     uint32_t num_faces, uint32_t min_leaf, uint32_t max_depth, uint32_t bin_size, unsigned build_flags, DevBuf *workspace,
+                     DevBuf *nodes_buf, DevBuf *indices_buf, void *pinned, hipEvent_t ev, std::string *err);
+hipError_t gpu_build_result(const void *pinned, hipEvent_t ev, BuildResult *res);
+hipError_t launch_cylinder_segments(const float *verts, const float *radii, const uint32_t *seg_off, uint32_t n, float *seg_verts,
+                                    float *seg_radii, uint32_t *seg_prim, hipStream_t s);
+
+// ---- refit.hip: the per-tree level plan of a refit, and one refit over it ------------------------------------------------
+size_t refit_plan_bytes(uint32_t tree_depth, uint64_t num_nodes);
+template <typename T>
+hipError_t launch_refit_plan(const typename Wire<T>::Node *nodes, uint64_t num_nodes, uint32_t num_branch_records, uint32_t tree_depth,
+                             uint32_t root_is_branch, uint32_t *plan, hipStream_t s);
+template <typename T>
+hipError_t launch_refit(const void *src, size_t stride, bool aligned, uint32_t nv, T *verts, const uint32_t *faces, const uint32_t *indices,
+                        typename Wire<T>::Node *nodes, uint64_t num_nodes, uint32_t num_branch_records, uint32_t tree_depth,
+                        const uint32_t *plan, hipStream_t s);
+
+} // namespace nrt

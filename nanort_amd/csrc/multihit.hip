@@ -16,6 +16,7 @@
 // the worst held prim_id (the worst t is B itself, kept in Lane::hit_t where the slab test reads it).  Insertions are rare
 // next to node visits, so the row costs no LDS and no VGPRs for any K up to NRT_MAX_MULTIHIT, and the kernel keeps
 // k_traverse's register budget.
+#include "kernels.h"
 #include "traverse_dev.h"
 
 namespace nrt {
@@ -212,9 +213,7 @@ int traverse_multihit_blocks_per_cu() {
   return n;
 }
 
-template hipError_t launch_traverse_multihit<float>(const TraverseArgs<float> &, uint32_t, uint32_t *, unsigned, hipStream_t);
-template hipError_t launch_traverse_multihit<double>(const TraverseArgs<double> &, uint32_t, uint32_t *, unsigned, hipStream_t);
-template int traverse_multihit_blocks_per_cu<float>();
-template int traverse_multihit_blocks_per_cu<double>();
+NRT_INSTANTIATE_F32_F64(launch_traverse_multihit)
+NRT_INSTANTIATE_F32_F64(traverse_multihit_blocks_per_cu)
 
 } // namespace nrt

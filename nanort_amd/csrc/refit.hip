@@ -16,7 +16,7 @@
 // Records the walk from the root never reaches (adopted trees) are in neither list and are left untouched.
 #include <algorithm>
 
-#include "common.h"
+#include "kernels.h"
 #include "minmax_dev.h"
 
 namespace nrt {
@@ -200,11 +200,7 @@ hipError_t launch_refit(const void *src, size_t stride, bool aligned, uint32_t n
   return hipSuccess;
 }
 
-template hipError_t launch_refit_plan<float>(const Wire<float>::Node *, uint64_t, uint32_t, uint32_t, uint32_t, uint32_t *, hipStream_t);
-template hipError_t launch_refit_plan<double>(const Wire<double>::Node *, uint64_t, uint32_t, uint32_t, uint32_t, uint32_t *, hipStream_t);
-template hipError_t launch_refit<float>(const void *, size_t, bool, uint32_t, float *, const uint32_t *, const uint32_t *, Wire<float>::Node *,
-                                        uint64_t, uint32_t, uint32_t, const uint32_t *, hipStream_t);
-template hipError_t launch_refit<double>(const void *, size_t, bool, uint32_t, double *, const uint32_t *, const uint32_t *, Wire<double>::Node *,
-                                         uint64_t, uint32_t, uint32_t, const uint32_t *, hipStream_t);
+NRT_INSTANTIATE_F32_F64(launch_refit_plan)
+NRT_INSTANTIATE_F32_F64(launch_refit)
 
 } // namespace nrt

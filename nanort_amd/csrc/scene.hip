@@ -31,20 +31,10 @@
 #include <unordered_map>
 #include <vector>
 
-#include "common.h"
+#include "kernels.h"
 #ifdef NRT_PROF
 #include "../../include/nanort_hip_prof.h"
 #endif
-
-struct nrt_ctx;
-nrt_status nrt_internal_tree_view(nrt_ctx *c, nrt::TreeViewF32 *out); // api.hip
-uint64_t nrt_internal_generation(const nrt_ctx *c);                      // api.hip: counts the context's rebuilds
-namespace nrt {
-hipError_t launch_scene_trace(const SceneTraceArgs &args, unsigned grid, hipStream_t s); // traverse.hip
-int scene_trace_blocks_per_cu();
-hipError_t launch_scene_walk(const SceneWalkArgs &args, unsigned grid, hipStream_t s); // traverse.hip
-int scene_walk_blocks_per_cu();
-}
 
 namespace {
 

@@ -14,15 +14,26 @@
 //   Intersect (watertight)   nanort.h:1054-1150 (fp64 edge fallback, tie rules)
 //   Traverse / TestLeafNode  nanort.h:2526-2556, 2374-2407 (near child first,
 //                            hit iff t_best < ray.max_t)
+#include "kernels.h"
 #include "traverse_dev.h"
 
 #include <algorithm>
-#include <cstdio>
-#include <map>
-#include <mutex>
-#include <string>
 
 namespace nrt {
+
+// The host side of every persistent launch of this file: the kernel is picked once, as a pointer, and the launch and the
+// occupancy query that sizes its grid go through that pointer.
+template <typename A>
+static void launch_persistent(const void *kernel, unsigned grid, const A &args, hipStream_t s) {
+  void *params[] = {(void *)&args};
+  (void)hipLaunchKernel(kernel, dim3(grid), dim3(kTraverseBlock), params, 0, s); // (the callers return hipGetLastError())
+}
+// Resident blocks per CU of `kernel`, 8 at the most; `fallback` where the runtime cannot say.
+static int resident_blocks(const void *kernel, int fallback) {
+  int n = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, kTraverseBlock, 0) != hipSuccess || n < 1) n = fallback;
+  return n > 8 ? 8 : n;
+}
 
 template <typename T, bool COUNT, int STACK>
 __global__ __launch_bounds__(kTraverseBlock) void k_traverse(const TraverseArgs<T> a) {
@@ -1491,20 +1502,16 @@ __global__ __launch_bounds__(kTraverseBlock) void k_scene_trace(const SceneTrace
   }
 }
 
+static const void *scene_trace_kernel(bool scan) {
+  return scan ? (const void *)k_scene_trace<kSceneLdsStack, true> : (const void *)k_scene_trace<kSceneLdsStack, false>;
+}
 hipError_t launch_scene_trace(const SceneTraceArgs &args, unsigned grid, hipStream_t s) {
   if (args.n == 0) return hipSuccess;
-  if (args.scan_nodes)
-    hipLaunchKernelGGL((k_scene_trace<kSceneLdsStack, true>), dim3(grid), dim3(kTraverseBlock), 0, s, args);
-  else
-    hipLaunchKernelGGL((k_scene_trace<kSceneLdsStack, false>), dim3(grid), dim3(kTraverseBlock), 0, s, args);
+  launch_persistent(scene_trace_kernel(args.scan_nodes != 0), grid, args, s);
   return hipGetLastError();
 }
-int scene_trace_blocks_per_cu() {
-  int n = 0;
-  int n1 = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_scene_trace<kSceneLdsStack, false>, kTraverseBlock, 0) != hipSuccess || n < 1) n = 4;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n1, k_scene_trace<kSceneLdsStack, true>, kTraverseBlock, 0) == hipSuccess && n1 >= 1 && n1 < n) n = n1;
-  return n > 8 ? 8 : n;
+int scene_trace_blocks_per_cu() { // (one grid size for both: the fewer)
+  return std::min(resident_blocks(scene_trace_kernel(false), 4), resident_blocks(scene_trace_kernel(true), 8));
 }
 
 // ---------------------------------------------------------------------------
@@ -1886,11 +1893,7 @@ hipError_t launch_scene_walk(const SceneWalkArgs &args, unsigned grid, hipStream
   hipLaunchKernelGGL((k_scene_walk<kSceneWalkLdsStack, false>), dim3(grid), dim3(kTraverseBlock), 0, s, args);
   return hipGetLastError();
 }
-int scene_walk_blocks_per_cu() {
-  int n = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_scene_walk<kSceneWalkLdsStack, false>, kTraverseBlock, 0) != hipSuccess || n < 1) n = 3;
-  return n > 8 ? 8 : n;
-}
+int scene_walk_blocks_per_cu() { return resident_blocks((const void *)k_scene_walk<kSceneWalkLdsStack, false>, 3); }
 
 // BVHNode[] -> dense WideNode[]: (1) branches per 1024-node tile, (2) exclusive scan of the
 // tile counts, (3) dense index of every branch node, (4) the records.
@@ -2092,183 +2095,80 @@ __global__ __launch_bounds__(256) void k_gather_leaf_cylinders(const uint32_t *_
   out[s] = r;
 }
 
-// ---- host-side launchers (called from api.hip) ------------------------------
+// ---- host-side launchers (kernels.h) ----------------------------------------
 
-template <typename T, int STACK>
-static hipError_t launch_traverse_s(const TraverseArgs<T> &args, unsigned grid, bool count, hipStream_t s) {
-  if (count) {
-    hipLaunchKernelGGL((k_traverse<T, true, STACK>), dim3(grid), dim3(kTraverseBlock), 0, s, args);
-  } else {
-    hipLaunchKernelGGL((k_traverse<T, false, STACK>), dim3(grid), dim3(kTraverseBlock), 0, s, args);
+template <typename T>
+static const void *traverse_kernel(bool count, int lds_entries) { // 16, 24, anything else -> 32
+  switch (lds_entries) {
+    case 16: return count ? (const void *)k_traverse<T, true, 16> : (const void *)k_traverse<T, false, 16>;
+    case 24: return count ? (const void *)k_traverse<T, true, 24> : (const void *)k_traverse<T, false, 24>;
+    default: return count ? (const void *)k_traverse<T, true, 32> : (const void *)k_traverse<T, false, 32>;
   }
+}
+template <typename T>
+hipError_t launch_traverse(const TraverseArgs<T> &args, unsigned grid, bool count, int lds_entries, hipStream_t s) {
+  launch_persistent(traverse_kernel<T>(count, lds_entries), grid, args, s);
   return hipGetLastError();
 }
-
 template <typename T>
-hipError_t launch_traverse(const TraverseArgs<T> &args, unsigned grid, bool count, int lds_stack, hipStream_t s) {
-  switch (lds_stack) {
-    case 16: return launch_traverse_s<T, 16>(args, grid, count, s);
-    case 24: return launch_traverse_s<T, 24>(args, grid, count, s);
-    default: return launch_traverse_s<T, 32>(args, grid, count, s);
-  }
+int traverse_blocks_per_cu(int lds_entries) { // (of the non-counting kernel)
+  return resident_blocks(traverse_kernel<T>(false, lds_entries), 4);
 }
 
-// Resident blocks per CU of the (non-counting) traversal kernel for a given LDS stack depth.
-template <typename T>
-int traverse_blocks_per_cu(int lds_stack) {
-  int n = 0;
-  hipError_t e;
-  switch (lds_stack) {
-    case 16: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_traverse<T, false, 16>, kTraverseBlock, 0); break;
-    case 24: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_traverse<T, false, 24>, kTraverseBlock, 0); break;
-    default: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_traverse<T, false, 32>, kTraverseBlock, 0); break;
-  }
-  if (e != hipSuccess || n < 1) n = 4;
-  return n > 8 ? 8 : n;
-}
-
-// `name_out` (optional) receives the name of the variant launched, as rocprofv3 prints it without the argument list.
-static const char *variant_name(bool f32, int stack, bool stats, int kind, bool plain, bool clock, int width, int order) {
-  static std::mutex m;
-  static std::map<std::string, std::string> *names = new std::map<std::string, std::string>(); // (never destroyed: the pointers are handed out)
-  char buf[160];
-  snprintf(buf, sizeof(buf), "nrt::k_traverse_wide<%s, %d, %s, %d, %s, %s, %d, %d>", f32 ? "float" : "double", stack,
-           stats ? "true" : "false", kind, plain ? "true" : "false", clock ? "true" : "false", width, order);
-  std::lock_guard<std::mutex> lock(m);
-  return names->emplace(buf, buf).first->second.c_str();
-}
-#define NRT_LAUNCH_WIDE_O(STACK_, STATS_, KIND_, PLAIN_, CLOCK_, WIDTH_, ORDER_)                                          \
-  do {                                                                                                                  \
-    const char *vn_ = variant_name(sizeof(T) == 4, STACK_, STATS_, KIND_, PLAIN_, CLOCK_, WIDTH_, ORDER_);              \
-    NRT_RANGE_PUSH(vn_); /* (profiling library: a marker range per traversal launch, named like the kernel) */          \
-    hipLaunchKernelGGL((k_traverse_wide<T, STACK_, STATS_, KIND_, PLAIN_, CLOCK_, WIDTH_, ORDER_>), dim3(grid),         \
-                       dim3(kTraverseBlock), 0, s, args);                                                               \
-    NRT_RANGE_POP();                                                                                                    \
-    if (name_out) *name_out = vn_;                                                                                      \
-  } while (0)
-#define NRT_LAUNCH_WIDE(STACK_, STATS_, KIND_, PLAIN_, CLOCK_, WIDTH_) NRT_LAUNCH_WIDE_O(STACK_, STATS_, KIND_, PLAIN_, CLOCK_, WIDTH_, 0)
-
-template <typename T>
-hipError_t launch_traverse_wide(const TraverseArgs<T> &args, unsigned grid, int lds_stack, int prim_kind, hipStream_t s,
-                                const char **name_out) {
-  if (prim_kind == kPrimSpheres) { // 10 LDS entries walking one level per step, kWide4LdsStack walking two (the caller sizes the overflow stack)
-    if constexpr (sizeof(T) == 4) {
-      if (args.wide4)
-        NRT_LAUNCH_WIDE(kWide4LdsStack, false, kPrimSpheres, false, false, 4);
-      else
-        NRT_LAUNCH_WIDE(10, false, kPrimSpheres, false, false, 2);
-    } else {
-      NRT_LAUNCH_WIDE(10, false, kPrimSpheres, false, false, 2);
-    }
-    if (args.hits) // (args.done_publish == 0: this pass closes the launch's completion record)
-      hipLaunchKernelGGL((k_sphere_uv<T>), dim3(std::min((args.num_rays + 255u) / 256u, 2048u)), dim3(256), 0, s, args.rays, args.hits,
-                         args.centers, args.num_rays, args.done_publish ? nullptr : args.done_rec, args.done_count, args.done_seq);
-    return hipGetLastError();
-  }
-  if (prim_kind == kPrimCylinders) {
-    if constexpr (sizeof(T) == 4) {
-      if (args.wide4)
-        NRT_LAUNCH_WIDE(kWide4LdsStack, false, kPrimCylinders, false, false, 4);
-      else
-        NRT_LAUNCH_WIDE(10, false, kPrimCylinders, false, false, 2);
-    } else {
-      NRT_LAUNCH_WIDE(10, false, kPrimCylinders, false, false, 2);
-    }
-    return hipGetLastError();
-  }
-  if (args.wide4) { // two tree levels per step (the caller checked what that needs)
-    if constexpr (sizeof(T) == 4) {
-#ifdef NRT_PROF // (the profiling instantiations exist in libnanort_hip_prof.so only: nanort_hip_prof.h)
-      if (args.debug_flags & 32u)
-        NRT_LAUNCH_WIDE(kWide4LdsStack, true, kPrimTriangles, true, false, 4); // profiling instantiation (default trace options only)
-      else if (args.wave_clock)
-        NRT_LAUNCH_WIDE(kWide4LdsStack, false, kPrimTriangles, true, true, 4); // per-wave time stamps (default trace options only)
-      else
-#endif
-      if (args.wide4_big) { // a record array of 4 GiB or more: the default walk with 64-bit record offsets (api.hip sends nothing else here)
-        if (args.leaf_items && args.plain_options)
-          NRT_LAUNCH_WIDE_O(kWide4LdsStack, false, kPrimTriangles, true, false, 4, 6);
-        else if (args.leaf_items)
-          NRT_LAUNCH_WIDE_O(kWide4LdsStack, false, kPrimTriangles, false, false, 4, 6);
-        else if (args.plain_options)
-          NRT_LAUNCH_WIDE_O(kWide4LdsStack, false, kPrimTriangles, true, false, 4, 4);
-        else
-          NRT_LAUNCH_WIDE_O(kWide4LdsStack, false, kPrimTriangles, false, false, 4, 4);
-      } else if (args.leaf_items && !args.order4 && args.plain_options) // leaf phase over items (tunable leaf_compact): the reference's walk, records bit-identical
-        NRT_LAUNCH_WIDE_O(kWide4LdsStack, false, kPrimTriangles, true, false, 4, 2);
-      else if (args.leaf_items && !args.order4)
-        NRT_LAUNCH_WIDE_O(kWide4LdsStack, false, kPrimTriangles, false, false, 4, 2);
-      else if (args.leaf_items && args.plain_options)
-        NRT_LAUNCH_WIDE_O(kWide4LdsStack, false, kPrimTriangles, true, false, 4, 3);
-      else if (args.leaf_items)
-        NRT_LAUNCH_WIDE_O(kWide4LdsStack, false, kPrimTriangles, false, false, 4, 3);
-      else if (args.order4 && args.plain_options) // slots entered by entry distance (tunable order4; contract-level parity: see NRT_STEP_NODE4_DIST)
-        NRT_LAUNCH_WIDE_O(kWide4LdsStack, false, kPrimTriangles, true, false, 4, 1);
-      else if (args.order4)
-        NRT_LAUNCH_WIDE_O(kWide4LdsStack, false, kPrimTriangles, false, false, 4, 1);
-      else if (args.plain_options)
-        NRT_LAUNCH_WIDE(kWide4LdsStack, false, kPrimTriangles, true, false, 4);
-      else
-        NRT_LAUNCH_WIDE(kWide4LdsStack, false, kPrimTriangles, false, false, 4);
-      return hipGetLastError();
-    } else {
-      return hipErrorInvalidValue;
-    }
-  }
-  switch (lds_stack) {
-    case 8: NRT_LAUNCH_WIDE(8, false, kPrimTriangles, false, false, 2); break;
-    case 10:
+// Every instantiation of k_traverse_wide in this library, by its template arguments (walk_variant.h), with its name as
+// rocprofv3 prints it without the argument list.  The profiling instantiations exist in libnanort_hip_prof.so only (nanort_hip_prof.h).
 #ifdef NRT_PROF
-      if (args.debug_flags & 32u) {
-        NRT_LAUNCH_WIDE(10, true, kPrimTriangles, false, false, 2);
-      } else if (args.wave_clock) { // profiling: per-wave time stamps (default trace options only)
-        NRT_LAUNCH_WIDE(10, false, kPrimTriangles, true, true, 2);
-      } else
+constexpr bool kProfBuild = true;
+#else
+constexpr bool kProfBuild = false;
 #endif
-      if (args.plain_options) {
-        NRT_LAUNCH_WIDE(10, false, kPrimTriangles, true, false, 2);
-      } else {
-        NRT_LAUNCH_WIDE(10, false, kPrimTriangles, false, false, 2);
-      }
-      break;
-    case 12: NRT_LAUNCH_WIDE(12, false, kPrimTriangles, false, false, 2); break;
-    default: NRT_LAUNCH_WIDE(16, false, kPrimTriangles, false, false, 2); break;
-  }
-  return hipGetLastError();
+struct WideKernel {
+  WalkVariant v;
+  const void *kernel;
+  const char *name;
+};
+#define NRT_STR2(x) #x
+#define NRT_STR(x) NRT_STR2(x)
+#define NRT_WIDE_KERNEL(T_, STACK_, STATS_, KIND_, PLAIN_, CLOCK_, WIDTH_, ORDER_)                          \
+  {{sizeof(T_) == 4, STACK_, STATS_, KIND_, PLAIN_, CLOCK_, WIDTH_, ORDER_},                                \
+   (const void *)k_traverse_wide<T_, STACK_, STATS_, KIND_, PLAIN_, CLOCK_, WIDTH_, ORDER_>,                \
+   "nrt::k_traverse_wide<" #T_ ", " NRT_STR(STACK_) ", " #STATS_ ", " #KIND_ ", " #PLAIN_ ", " #CLOCK_ ", " #WIDTH_ ", " #ORDER_ ">"},
+static const WideKernel kWideKernels[] = {
+    NRT_WALK_VARIANTS(NRT_WIDE_KERNEL)
+#ifdef NRT_PROF
+    NRT_WALK_VARIANTS_PROF(NRT_WIDE_KERNEL)
+#endif
+};
+#undef NRT_WIDE_KERNEL
+static const WideKernel *find_wide_kernel(const WalkVariant &v) {
+  for (const WideKernel &k : kWideKernels)
+    if (k.v == v) return &k;
+  return nullptr; // (tests/test_walk_variant.py: no request picks a variant that is not listed)
 }
-#undef NRT_LAUNCH_WIDE
-#undef NRT_LAUNCH_WIDE_O
 
 template <typename T>
-int traverse_wide_blocks_per_cu(int lds_stack, int prim_kind, bool wide4) {
-  int n = 0;
-  hipError_t e = hipErrorInvalidValue;
-  if (prim_kind == kPrimSpheres) {
-    if constexpr (sizeof(T) == 4) {
-      if (wide4) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_traverse_wide<T, kWide4LdsStack, false, kPrimSpheres, false, false, 4>, kTraverseBlock, 0);
-    }
-    if (!wide4 || sizeof(T) != 4) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_traverse_wide<T, 10, false, kPrimSpheres>, kTraverseBlock, 0);
-  } else if (prim_kind == kPrimCylinders) {
-    if constexpr (sizeof(T) == 4) {
-      if (wide4) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_traverse_wide<T, kWide4LdsStack, false, kPrimCylinders, false, false, 4>, kTraverseBlock, 0);
-    }
-    if (!wide4 || sizeof(T) != 4) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_traverse_wide<T, 10, false, kPrimCylinders>, kTraverseBlock, 0);
-  } else if (wide4) {
-    if constexpr (sizeof(T) == 4)
-      e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_traverse_wide<T, kWide4LdsStack, false, kPrimTriangles, true, false, 4>, kTraverseBlock, 0);
-  } else {
-    switch (lds_stack) {
-      case 8: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_traverse_wide<T, 8, false, kPrimTriangles>, kTraverseBlock, 0); break;
-      case 10: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_traverse_wide<T, 10, false, kPrimTriangles, true>, kTraverseBlock, 0); break;
-      case 12: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_traverse_wide<T, 12, false, kPrimTriangles>, kTraverseBlock, 0); break;
-      default: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_traverse_wide<T, 16, false, kPrimTriangles>, kTraverseBlock, 0); break;
-    }
-  }
-  if (e != hipSuccess || n < 1) n = 4;
-  return n > 8 ? 8 : n;
+hipError_t launch_traverse_wide(const TraverseArgs<T> &args, unsigned grid, int lds_entries, int prim_kind, hipStream_t s,
+                                const char **name_out) {
+  const WalkRequest r = {sizeof(T) == 4, prim_kind, lds_entries, args.wide4 != nullptr, args.wide4_big != 0, args.leaf_items != 0, args.order4 != 0,
+                         args.plain_options != 0, (args.debug_flags & 32u) != 0, args.wave_clock != nullptr};
+  const WideKernel *k = find_wide_kernel(pick_wide_variant(r, kProfBuild));
+  if (!k) return hipErrorInvalidValue;
+  NRT_RANGE_PUSH(k->name); // (profiling library: a marker range per traversal launch, named like the kernel)
+  launch_persistent(k->kernel, grid, args, s);
+  NRT_RANGE_POP();
+  if (name_out) *name_out = k->name;
+  if (prim_kind == kPrimSpheres && args.hits) // (args.done_publish == 0: this pass closes the launch's completion record)
+    hipLaunchKernelGGL((k_sphere_uv<T>), dim3(std::min((args.num_rays + 255u) / 256u, 2048u)), dim3(256), 0, s, args.rays, args.hits,
+                       args.centers, args.num_rays, args.done_publish ? nullptr : args.done_rec, args.done_count, args.done_seq);
+  return hipGetLastError();
 }
 
-// scratch: tile counts (ceil(n/1024) u32) followed by dense_of (n u32)
+template <typename T>
+int traverse_wide_blocks_per_cu(int lds_entries, int prim_kind, bool wide4) {
+  const WideKernel *k = find_wide_kernel(occupancy_variant(sizeof(T) == 4, prim_kind, lds_entries, wide4));
+  return k ? resident_blocks(k->kernel, 4) : 4;
+}
+
 template <typename T>
 hipError_t launch_make_wide(const typename Wire<T>::Node *nodes, uint32_t n, uint32_t packed, uint32_t *scratch,
                             WideNode<T> *wide, Wide4Node<T> *wide4, uint32_t scramble_mod, hipStream_t s) {
@@ -2306,10 +2206,7 @@ hipError_t launch_gather_leaf_cylinders(const uint32_t *indices, const T *verts,
   hipLaunchKernelGGL((k_gather_leaf_cylinders<T>), dim3((n + 255u) / 256u), dim3(256), 0, s, indices, verts, radii, out, n);
   return hipGetLastError();
 }
-template hipError_t launch_gather_leaf_cylinders<float>(const uint32_t *, const float *, const float *, LeafCylinder<float> *,
-                                                        uint32_t, hipStream_t);
-template hipError_t launch_gather_leaf_cylinders<double>(const uint32_t *, const double *, const double *,
-                                                         LeafCylinder<double> *, uint32_t, hipStream_t);
+NRT_INSTANTIATE_F32_F64(launch_gather_leaf_cylinders)
 
 hipError_t launch_cylinder_post(const nrt_ray_f32 *rays, const nrt_hit_f32 *compact, const uint8_t *bits, const float *verts,
                                 uint32_t n, void *out, uint8_t *mask, DoneRec *done_rec, DoneCount *done_count, uint32_t done_seq,
@@ -2320,26 +2217,12 @@ hipError_t launch_cylinder_post(const nrt_ray_f32 *rays, const nrt_hit_f32 *comp
   return hipGetLastError();
 }
 
-template hipError_t launch_traverse<float>(const TraverseArgs<float> &, unsigned, bool, int, hipStream_t);
-template hipError_t launch_traverse<double>(const TraverseArgs<double> &, unsigned, bool, int, hipStream_t);
-template hipError_t launch_traverse_wide<float>(const TraverseArgs<float> &, unsigned, int, int, hipStream_t, const char **);
-template hipError_t launch_traverse_wide<double>(const TraverseArgs<double> &, unsigned, int, int, hipStream_t, const char **);
-template int traverse_wide_blocks_per_cu<float>(int, int, bool);
-template int traverse_wide_blocks_per_cu<double>(int, int, bool);
-template hipError_t launch_gather_leaf_spheres<float>(const uint32_t *, const float *, const float *, LeafSphere<float> *,
-                                                      uint32_t, hipStream_t);
-template hipError_t launch_gather_leaf_spheres<double>(const uint32_t *, const double *, const double *,
-                                                       LeafSphere<double> *, uint32_t, hipStream_t);
-template hipError_t launch_make_wide<float>(const nrt_node_f32 *, uint32_t, uint32_t, uint32_t *, WideNode<float> *,
-                                            Wide4Node<float> *, uint32_t, hipStream_t);
-template hipError_t launch_make_wide<double>(const nrt_node_f64 *, uint32_t, uint32_t, uint32_t *, WideNode<double> *,
-                                             Wide4Node<double> *, uint32_t, hipStream_t);
-template int traverse_blocks_per_cu<float>(int);
-template int traverse_blocks_per_cu<double>(int);
-template hipError_t launch_gather_leaf_tris<float>(const uint32_t *, const uint32_t *, const float *,
-                                                   LeafTri<float> *, uint32_t, hipStream_t);
-template hipError_t launch_gather_leaf_tris<double>(const uint32_t *, const uint32_t *,
-                                                    const double *, LeafTri<double> *, uint32_t,
-                                                    hipStream_t);
+NRT_INSTANTIATE_F32_F64(launch_traverse)
+NRT_INSTANTIATE_F32_F64(launch_traverse_wide)
+NRT_INSTANTIATE_F32_F64(traverse_wide_blocks_per_cu)
+NRT_INSTANTIATE_F32_F64(launch_gather_leaf_spheres)
+NRT_INSTANTIATE_F32_F64(launch_make_wide)
+NRT_INSTANTIATE_F32_F64(traverse_blocks_per_cu)
+NRT_INSTANTIATE_F32_F64(launch_gather_leaf_tris)
 
 } // namespace nrt

@@ -33,7 +33,15 @@ CONFIGS = [
     ("f64_default", np.float64, {}, False, WIDE % "double, 10, false, 0, true, false, 2, 0"),
     ("f64_cull", np.float64, {}, True, WIDE % "double, 10, false, 0, false, false, 2, 0"),
     ("no_wide", np.float32, {"wide": 0}, False, "nrt::k_traverse<float>"),
+    # (the rows below: what the library printed at the commit before the kernels were put into one table)
+    ("wide4_big_forced_cull", np.float32, {"wide4_big": 2}, True, WIDE % "float, 12, false, 0, false, false, 4, 6"),
+    ("wide4_big_forced_no_leaf_compact", np.float32, {"wide4_big": 2, "leaf_compact": 0}, False, WIDE % "float, 12, false, 0, true, false, 4, 4"),
+    ("wide_stack_8", np.float32, {"wide_stack": 8}, False, WIDE % "float, 8, false, 0, false, false, 2, 0"),
+    ("wide_stack_12", np.float32, {"wide_stack": 12}, False, WIDE % "float, 12, false, 0, false, false, 2, 0"),
+    ("wide_stack_16", np.float32, {"wide_stack": 16}, False, WIDE % "float, 16, false, 0, false, false, 2, 0"),
 ]
+# custom primitives built with wide4 = 0 walk one level per step on ten LDS entries
+ONE_LEVEL_CUSTOM = {"spheres": WIDE % "float, 10, false, 1, false, false, 2, 0", "cylinders": WIDE % "float, 10, false, 2, false, false, 2, 0"}
 
 
 @pytest.fixture(scope="module")
@@ -113,6 +121,17 @@ def assert_same_records(got, want):
     assert_hits_identical(got[0], got[1], want[0], want[1])
     if "normal" in (got[0].dtype.names or ()):  # the cylinder record's fifth field
         assert got[0]["normal"].tobytes() == want[0]["normal"].tobytes()
+
+
+@pytest.mark.parametrize("kind", sorted(ONE_LEVEL_CUSTOM))
+def test_custom_primitives_without_wide4(c1_mesh, rays, kind):
+    g, r, _ = stage_geometry(c1_mesh, rays)[kind]
+    a = built(np.float32, g, {"wide4": 0})
+    got = a.TraverseBatch(r)
+    print(a.LastKernelName())
+    assert a.LastKernelName() == ONE_LEVEL_CUSTOM[kind]
+    assert got[1].any()
+    assert_same_records(got, built(np.float32, g).TraverseBatch(r))
 
 
 def test_one_context_through_every_kind_equals_fresh_contexts(c1_mesh, rays):
