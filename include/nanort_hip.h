@@ -357,6 +357,41 @@ NRT_API nrt_status nrtRefit_f64(nrt_ctx *ctx, const double *vertices, size_t ver
 NRT_API nrt_status nrtRefitDevice_f32(nrt_ctx *ctx, const float *d_vertices, size_t vertex_stride_bytes, void *hip_stream);
 NRT_API nrt_status nrtRefitDevice_f64(nrt_ctx *ctx, const double *d_vertices, size_t vertex_stride_bytes, void *hip_stream);
 
+/* ---- device-resident geometry: nrtSetMesh_* / nrtSetSpheres_f32 for arrays that are already in HBM ------------------
+ * For a mesh or a particle set produced on the GPU (a tensor, a simulation, a remesher): no copy to the host and back.
+ * Contract:
+ *   1. Input: every pointer is device memory on the context's GPU.  `d_vertices` holds `num_vertices` rows, row i at byte
+ *      offset i * vertex_stride_bytes, xyz first; `d_faces` is tight 3 x u32 per face; `d_centers` is tight xyz per sphere and
+ *      `d_radii` one radius per sphere.  `hip_stream` is a hipStream_t; NULL = the default stream.
+ *   2. Result: exactly the state the matching host call (nrtSetMesh_f32 / _f64, nrtSetSpheres_f32) leaves, given the same array
+ *      contents: the same precision, primitive kind and num_faces, positions stored as tight xyz, the tree dropped (a committed
+ *      nrt_scene over the context refuses until it is committed again).  A following nrtBuild_* produces a node array and an
+ *      index array byte-identical to the host path's.  The context's num_verts is max(faces) + 1 — NOT num_vertices —, so
+ *      the refit contract above is unchanged.
+ *   3. num_vertices, the guard the host form has no need of: the number of rows the caller's vertex block really holds (a
+ *      tensor's shape[0]).  The library computes the largest face index on the device; when it is >= num_vertices the call
+ *      returns NRT_ERR_INVALID before it reads a single vertex and before it drops anything: the context keeps its primitives
+ *      and its tree and still traces.  A bad index buffer becomes an error string, never an out-of-bounds read.  Rows
+ *      0 .. max(faces) are read: at most (num_vertices - 1) * stride + 3 * sizeof(T) bytes.
+ *   4. Ordering: the call-order rules of nrtBuild.  The call first waits on the host for the context's launches in flight,
+ *      as nrtSetMesh does.  The work is enqueued on `hip_stream`, behind whatever the caller queued there to produce the
+ *      buffers, and the call returns when the context owns its copy: the caller may reuse or free the buffers at once, and
+ *      a later nrtBuild (on the context's own stream) needs no extra ordering.  The cost of this simplicity is two host
+ *      waits per mesh call — a 4-byte read-back of the largest index, and the final wait — and one for spheres.
+ * Refusals leave the context untouched (nrtLastError gives the reason): NRT_ERR_INVALID for a NULL context and, with
+ * num_faces (num_spheres) > 0, for a NULL pointer, num_vertices == 0, a stride below 3 * sizeof(T), a stride or vertex
+ * pointer not aligned to sizeof(T) (the rule of nrtRefitDevice), d_faces not 4-byte aligned (centres or radii not
+ * 4-byte aligned), and a face index out of range; NRT_ERR_PRECISION when the context holds primitives of the other precision.
+ * num_faces == 0 behaves as in nrtSetMesh: NRT_OK, an empty triangle context, nrtBuild then returns NRT_ERR_EMPTY.
+ * NRT_ERR_DEVICE: a HIP error; once the old primitives have been dropped it leaves an empty context.
+ * Cylinders have no device form: nrtSetCylinders_f32 plans their segments on the host. */
+NRT_API nrt_status nrtSetMeshDevice_f32(nrt_ctx *ctx, const float *d_vertices, uint32_t num_vertices, size_t vertex_stride_bytes,
+                                        const uint32_t *d_faces, uint32_t num_faces, void *hip_stream);
+NRT_API nrt_status nrtSetMeshDevice_f64(nrt_ctx *ctx, const double *d_vertices, uint32_t num_vertices, size_t vertex_stride_bytes,
+                                        const uint32_t *d_faces, uint32_t num_faces, void *hip_stream);
+NRT_API nrt_status nrtSetSpheresDevice_f32(nrt_ctx *ctx, const float *d_centers, const float *d_radii, uint32_t num_spheres,
+                                           void *hip_stream);
+
 /* ---- traverse: replaces N calls of BVHAccel<T>::Traverse with a
  * TriangleIntersector (nanort.h:757-759, 2487-2556, 1014-1229) -------------
  * Closest hit per ray, same arithmetic as the reference (no contraction,

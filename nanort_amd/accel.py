@@ -85,6 +85,17 @@ class CylinderGeometry:
         self.num_faces = int(self.radii.shape[0])
 
 
+class DeviceGeometry:
+    """What the accel remembers of primitives set from device tensors (SetMeshDevice / SetSpheresDevice): nothing of the
+    tensors themselves — the context owns its copy.  `kind` is "triangles" or "spheres"; `num_verts` is the context's vertex
+    count (max(faces) + 1 for triangles), what Refit / RefitDevice check their rows against."""
+
+    def __init__(self, kind, num_faces, num_verts):
+        self.kind = kind
+        self.num_faces = int(num_faces)
+        self.num_verts = int(num_verts)
+
+
 class BVHAccel:
     """nanort::BVHAccel<T> on one MI355X (built-in triangle geometry, or the sphere / cylinder primitives in fp32)."""
 
@@ -151,6 +162,75 @@ class BVHAccel:
             else:
                 mesh = TriangleMesh(mesh.vertices, mesh.faces[:num_primitives], mesh.vertex_stride_bytes)
         self.SetMesh(mesh)
+        return self.BuildCurrent(options)
+
+    def _stream_handle(self, stream):
+        import torch
+
+        if stream is None:
+            return torch.cuda.current_stream(self.device).cuda_stream
+        return stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+
+    def _on_device(self, t, what):
+        if t.device.type != "cuda" or t.device.index != self.device:
+            raise ValueError("%s must live on cuda:%d" % (what, self.device))
+
+    def SetMeshDevice(self, d_vertices, d_faces, stream=None):
+        """SetMesh from torch tensors on the accel's device (nrtSetMeshDevice): nothing goes through the host.  `d_vertices`:
+        [nv, k >= 3] of the accel's precision with stride(1) == 1 (the row stride is stride(0)); `d_faces`: [nf, 3], contiguous,
+        torch.int32 or torch.uint32 (read as u32).  The library refuses a face index >= nv before it reads a vertex.  Enqueued on
+        `stream` (default: torch's current stream), behind whatever produced the tensors there; returns when the accel owns
+        its copy."""
+        import torch
+
+        want = torch.float32 if self.real == np.float32 else torch.float64
+        if d_vertices.dtype != want:
+            raise TypeError("vertex dtype %s != accel precision %s" % (d_vertices.dtype, self.real))
+        index_types = [torch.int32] + ([torch.uint32] if hasattr(torch, "uint32") else [])
+        if d_faces.dtype not in index_types:
+            raise TypeError("faces must be torch.int32 or torch.uint32 (got %s): convert explicitly, 64-bit indices are not read" % d_faces.dtype)
+        if d_vertices.dim() != 2 or d_vertices.shape[1] < 3 or d_vertices.stride(1) != 1:
+            raise ValueError("vertices must be [nv, k >= 3] with stride(1) == 1")
+        if d_faces.dim() != 2 or d_faces.shape[1] != 3 or not d_faces.is_contiguous():
+            raise ValueError("faces must be [nf, 3], contiguous")
+        self._on_device(d_vertices, "vertices")
+        self._on_device(d_faces, "faces")
+        nv, nf = int(d_vertices.shape[0]), int(d_faces.shape[0])
+        stride = d_vertices.stride(0) * d_vertices.element_size()
+        self._check(getattr(self._L, "nrtSetMeshDevice_" + self._s)(
+            self._h, d_vertices.data_ptr() if nv else None, nv, stride, d_faces.data_ptr() if nf else None, nf, self._stream_handle(stream)))
+        # The library accepted the indices: all are < nv.  Below 2^31 the int32 view orders them as u32 does; a larger block
+        # (never seen) is remembered by its row count, which is at least the context's vertex count.
+        if nf == 0:
+            rows = 0
+        elif nv > 2 ** 31:
+            rows = nv
+        else:
+            rows = int(d_faces.view(torch.int32).max().item()) + 1
+        self._mesh = DeviceGeometry("triangles", nf, rows)
+
+    def SetSpheresDevice(self, d_centers, d_radii, stream=None):
+        """SetMesh(SphereGeometry) from torch float32 tensors on the accel's device (nrtSetSpheresDevice): `d_centers` [n, 3] and
+        `d_radii` [n], both contiguous.  Ordering as SetMeshDevice."""
+        import torch
+
+        if self.real != np.float32:
+            raise TypeError("sphere primitives are fp32 (as the reference example)")
+        if d_centers.dtype != torch.float32 or d_radii.dtype != torch.float32:
+            raise TypeError("centers and radii must be torch.float32")
+        if d_centers.dim() != 2 or d_centers.shape[1] != 3 or not d_centers.is_contiguous():
+            raise ValueError("centers must be [n, 3], contiguous")
+        if d_radii.dim() != 1 or d_radii.shape[0] != d_centers.shape[0] or not d_radii.is_contiguous():
+            raise ValueError("one radius per centre, contiguous")
+        self._on_device(d_centers, "centers")
+        self._on_device(d_radii, "radii")
+        n = int(d_radii.shape[0])
+        self._check(self._L.nrtSetSpheresDevice_f32(
+            self._h, d_centers.data_ptr() if n else None, d_radii.data_ptr() if n else None, n, self._stream_handle(stream)))
+        self._mesh = DeviceGeometry("spheres", n, n)
+
+    def BuildCurrent(self, options=None):
+        """nrtBuild over the primitives last set (SetMesh, SetMeshDevice or SetSpheresDevice).  Returns False iff there are none."""
         if options is not None:
             want = BUILD_OPTIONS_F32 if self.real == np.float32 else BUILD_OPTIONS_F64
             options = np.asarray(options, dtype=want).reshape(1)
@@ -160,6 +240,11 @@ class BVHAccel:
             return False
         self._check(st)
         return True
+
+    def BuildDevice(self, d_vertices, d_faces, options=None, stream=None):
+        """SetMeshDevice + nrtBuild: Build() for a mesh that lives on the device.  Returns False iff the mesh is empty."""
+        self.SetMeshDevice(d_vertices, d_faces, stream)
+        return self.BuildCurrent(options)
 
     def GetStatistics(self):
         return self._stats.copy()
@@ -230,6 +315,8 @@ class BVHAccel:
         """The context's vertex count (max(faces) + 1 of the mesh last set), or None when no triangle mesh is set (the library
         then refuses the refit before it reads any vertex)."""
         m = self._mesh
+        if isinstance(m, DeviceGeometry) and m.kind == "triangles":
+            return m.num_verts
         if not isinstance(m, TriangleMesh):
             return None
         return int(m.faces.max()) + 1 if m.num_faces else 0

@@ -29,6 +29,7 @@ SYMBOLS = [
     "nrtOccludedBatch_f32", "nrtOccludedBatch_f64", "nrtOccludedBatchDevice_f32", "nrtOccludedBatchDevice_f64",
     "nrtMultiHitTraverseBatch_f32", "nrtMultiHitTraverseBatch_f64", "nrtMultiHitTraverseBatchDevice_f32", "nrtMultiHitTraverseBatchDevice_f64",
     "nrtRefit_f32", "nrtRefit_f64", "nrtRefitDevice_f32", "nrtRefitDevice_f64",
+    "nrtSetMeshDevice_f32", "nrtSetMeshDevice_f64", "nrtSetSpheresDevice_f32",
     "nrtLastTraverseMs", "nrtSetLaunchTiming", "nrtSetTunable", "nrtGetTunable", "nrtLastBuildMs", "nrtLastKernelName", "nrtHostAlloc", "nrtHostFree",
     "nrtGroupUniqueId", "nrtGroupCreate", "nrtGroupCreateRanked", "nrtGroupDestroy", "nrtGroupLastError", "nrtGroupSetTunable", "nrtGroupInfo",
     "nrtGroupTileRays", "nrtGroupTraverseGather_f32", "nrtGroupTraverseGather_f64", "nrtGroupTraverseGatherTiles_f32", "nrtGroupTraverseGatherTiles_f64", "nrtGroupSynchronize", "nrtGroupLastTraffic",
@@ -134,8 +135,13 @@ def lib():
         f = getattr(L, "nrtRefitDevice_" + sfx)
         f.argtypes = [vp, vp, sz, vp]
         f.restype = i32
+        f = getattr(L, "nrtSetMeshDevice_" + sfx)
+        f.argtypes = [vp, vp, u32, sz, vp, u32, vp]
+        f.restype = i32
     L.nrtSetSpheres_f32.argtypes = [vp, vp, vp, u32]
     L.nrtSetSpheres_f32.restype = i32
+    L.nrtSetSpheresDevice_f32.argtypes = [vp, vp, vp, u32, vp]
+    L.nrtSetSpheresDevice_f32.restype = i32
     L.nrtSetCylinders_f32.argtypes = [vp, vp, vp, u32, i32]
     L.nrtSetCylinders_f32.restype = i32
     L.nrtTraverseBatchCylinders_f32.argtypes = [vp, vp, u64, vp, vp, vp]

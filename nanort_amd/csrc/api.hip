@@ -51,6 +51,9 @@ struct nrt_ctx {
   void *d_radii = nullptr;
   uint32_t *d_faces = nullptr;
   uint32_t num_faces = 0, num_verts = 0;
+  // nrtSetMeshDevice (mesh.hip): the largest face index, reduced on the device and read back through a page-locked word
+  DevBuf b_max_index;
+  uint32_t *h_max_index = nullptr;
 
   // tree (grow-only buffers: a per-frame rebuild allocates nothing in the steady state)
   DevBuf b_nodes, b_indices, b_tris, b_wide, b_wide4, b_wide_scratch, b_build_ws;
@@ -439,11 +442,12 @@ void nrtDestroy(nrt_ctx *c) {
   }
   free_tree(c);
   free_mesh(c);
-  DevBuf *bufs[] = {&c->b_verts, &c->b_radii, &c->b_faces, &c->st_rays, &c->st_hits, &c->st_mask, &c->b_nodes, &c->b_indices, &c->b_tris, &c->b_wide, &c->b_wide4, &c->b_wide_scratch, &c->b_build_ws, &c->b_wave_clock, &c->b_seg_verts, &c->b_seg_radii, &c->b_seg_prim, &c->b_seg_off, &c->b_refit_plan, &c->b_refit_stage};
+  DevBuf *bufs[] = {&c->b_verts, &c->b_radii, &c->b_faces, &c->st_rays, &c->st_hits, &c->st_mask, &c->b_nodes, &c->b_indices, &c->b_tris, &c->b_wide, &c->b_wide4, &c->b_wide_scratch, &c->b_build_ws, &c->b_wave_clock, &c->b_seg_verts, &c->b_seg_radii, &c->b_seg_prim, &c->b_seg_off, &c->b_refit_plan, &c->b_refit_stage, &c->b_max_index};
   for (DevBuf *b : bufs)
     if (b->p) (void)hipFree(b->p);
   if (c->d_counters) (void)hipFree(c->d_counters);
   if (c->build_state) (void)hipHostFree(c->build_state);
+  if (c->h_max_index) (void)hipHostFree(c->h_max_index);
   hipEvent_t evs[] = {c->ev_b0, c->ev_b1, c->ev_build_state, c->ev_refit};
   for (hipEvent_t ev : evs)
     if (ev) (void)hipEventDestroy(ev);
@@ -533,6 +537,98 @@ static nrt_status set_spheres(nrt_ctx *c, const T *centers, const T *radii, uint
   c->d_radii = c->b_radii.p;
   HIPCHK(c, hipMemcpy(c->d_verts, centers, 3 * (size_t)n * sizeof(T), hipMemcpyHostToDevice));
   HIPCHK(c, hipMemcpy(c->d_radii, radii, (size_t)n * sizeof(T), hipMemcpyHostToDevice));
+  return NRT_OK;
+}
+
+// ---------------------------------------------------------------------------
+// primitives that are already in device memory (mesh.hip)
+// ---------------------------------------------------------------------------
+// What remains of a Device set call once the old primitives are gone and a HIP call fails: an empty context and the reason.
+static nrt_status set_device_failed(nrt_ctx *c, const char *fn, hipStream_t s, hipError_t e) {
+  (void)hipStreamSynchronize(s);
+  free_mesh(c);
+  return fail(c, NRT_ERR_DEVICE, "%s: %s (the context's primitives were dropped: set them again)", fn, hipGetErrorString(e));
+}
+
+// nrtSetMesh for arrays in HBM: the same state as set_mesh leaves, the vertex count derived and the caller's `num_vertices`
+// checked on the device before any vertex is read and before anything of the context is dropped.
+template <typename T>
+static nrt_status set_mesh_device(nrt_ctx *c, const T *vertices, uint32_t num_vertices, size_t stride, const uint32_t *faces,
+                                  uint32_t num_faces, hipStream_t s) {
+  const char *fn = "nrtSetMeshDevice";
+  if (!c) return NRT_ERR_INVALID;
+  if (c->prec != 0 && c->prec != (int)sizeof(T))
+    return fail(c, NRT_ERR_PRECISION, "%s: context already holds a %s mesh", fn, c->prec == 4 ? "f32" : "f64");
+  if (num_faces) {
+    if (!vertices || !faces) return fail(c, NRT_ERR_INVALID, "%s: NULL mesh pointer", fn);
+    if (num_vertices == 0) return fail(c, NRT_ERR_INVALID, "%s: num_vertices == 0 with %u faces", fn, num_faces);
+    if (stride < 3 * sizeof(T)) return fail(c, NRT_ERR_INVALID, "%s: vertex stride %zu < %zu", fn, stride, 3 * sizeof(T));
+    if (stride % sizeof(T) != 0 || (uintptr_t)vertices % sizeof(T) != 0)
+      return fail(c, NRT_ERR_INVALID, "%s: vertex stride %zu or pointer not aligned to %zu bytes", fn, stride, sizeof(T));
+    if ((uintptr_t)faces % sizeof(uint32_t) != 0) return fail(c, NRT_ERR_INVALID, "%s: face pointer not aligned to 4 bytes", fn);
+  }
+  NRT_RANGE("nrtSetMeshDevice");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, wait_for_launches(c));
+  uint32_t nv = 0;
+  const size_t ni = 3 * (size_t)num_faces;
+  if (num_faces) { // the guard: nothing of the context has changed yet
+    if (!c->h_max_index) HIPCHK(c, hipHostMalloc((void **)&c->h_max_index, sizeof(uint32_t), hipHostMallocDefault));
+    nrt_status st;
+    if ((st = ensure(c, c->b_max_index, sizeof(uint32_t)))) return st;
+    HIPCHK(c, launch_max_index(faces, ni, (uint32_t *)c->b_max_index.p, s));
+    HIPCHK(c, hipMemcpyAsync(c->h_max_index, c->b_max_index.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    const uint32_t maxv = *c->h_max_index;
+    if (maxv >= num_vertices)
+      return fail(c, NRT_ERR_INVALID, "%s: face index %u is out of range: the vertex block holds %u rows", fn, maxv, num_vertices);
+    nv = maxv + 1;
+  }
+  free_tree(c);
+  free_mesh(c);
+  c->prec = (int)sizeof(T);
+  c->prim_kind = kPrimTriangles;
+  if (num_faces == 0) return NRT_OK;
+  hipError_t e;
+  if ((e = devbuf_ensure(&c->b_verts, 3 * (size_t)nv * sizeof(T))) != hipSuccess || (e = devbuf_ensure(&c->b_faces, ni * sizeof(uint32_t))) != hipSuccess ||
+      (e = stride == 3 * sizeof(T) ? hipMemcpyAsync(c->b_verts.p, vertices, 3 * (size_t)nv * sizeof(T), hipMemcpyDeviceToDevice, s) // (tight already)
+                                   : launch_gather_vertices<T>(vertices, stride, nv, (T *)c->b_verts.p, s)) != hipSuccess ||
+      (e = hipMemcpyAsync(c->b_faces.p, faces, ni * sizeof(uint32_t), hipMemcpyDeviceToDevice, s)) != hipSuccess ||
+      (e = hipStreamSynchronize(s)) != hipSuccess) // (the context owns its copy: the caller's buffers are free again)
+    return set_device_failed(c, fn, s, e);
+  c->d_verts = c->b_verts.p;
+  c->d_faces = (uint32_t *)c->b_faces.p;
+  c->num_faces = num_faces;
+  c->num_verts = nv;
+  return NRT_OK;
+}
+
+template <typename T>
+static nrt_status set_spheres_device(nrt_ctx *c, const T *centers, const T *radii, uint32_t n, hipStream_t s) {
+  const char *fn = "nrtSetSpheresDevice";
+  if (!c) return NRT_ERR_INVALID;
+  if (c->prec != 0 && c->prec != (int)sizeof(T))
+    return fail(c, NRT_ERR_PRECISION, "%s: context already holds %s primitives", fn, c->prec == 4 ? "f32" : "f64");
+  if (n && (!centers || !radii)) return fail(c, NRT_ERR_INVALID, "%s: NULL pointer", fn);
+  if (n && ((uintptr_t)centers % sizeof(T) != 0 || (uintptr_t)radii % sizeof(T) != 0))
+    return fail(c, NRT_ERR_INVALID, "%s: pointer not aligned to %zu bytes", fn, sizeof(T));
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, wait_for_launches(c));
+  free_tree(c);
+  free_mesh(c);
+  c->prec = (int)sizeof(T);
+  c->prim_kind = kPrimSpheres;
+  if (n == 0) return NRT_OK;
+  hipError_t e;
+  if ((e = devbuf_ensure(&c->b_verts, 3 * (size_t)n * sizeof(T))) != hipSuccess || (e = devbuf_ensure(&c->b_radii, (size_t)n * sizeof(T))) != hipSuccess ||
+      (e = hipMemcpyAsync(c->b_verts.p, centers, 3 * (size_t)n * sizeof(T), hipMemcpyDeviceToDevice, s)) != hipSuccess ||
+      (e = hipMemcpyAsync(c->b_radii.p, radii, (size_t)n * sizeof(T), hipMemcpyDeviceToDevice, s)) != hipSuccess ||
+      (e = hipStreamSynchronize(s)) != hipSuccess)
+    return set_device_failed(c, fn, s, e);
+  c->d_verts = c->b_verts.p;
+  c->d_radii = c->b_radii.p;
+  c->num_faces = n;
+  c->num_verts = n;
   return NRT_OK;
 }
 
@@ -879,7 +975,7 @@ static nrt_status refit(nrt_ctx *c, const T *vertices, size_t stride, bool devic
   }
   // From here on the vertices, the boxes and the leaf / wide records are being rewritten: a device error leaves no half-refit
   // tree behind — the context drops its tree and its primitives (free_tree bumps generation), as a failed build drops its tree.
-  hipError_t e = launch_refit<T>(src, stride, stride % sizeof(T) == 0, nv, (T *)c->d_verts, c->d_faces, c->d_indices,
+  hipError_t e = launch_refit<T>(src, stride, nv, (T *)c->d_verts, c->d_faces, c->d_indices,
                                  (typename Wire<T>::Node *)c->d_nodes, c->num_nodes, c->num_branch_records, c->tree_depth,
                                  (const uint32_t *)c->b_refit_plan.p, s);
   // LeafTri / WideNode / Wide4Node from the new boxes and positions, as a build derives them; every box now lies inside its parent's
@@ -1657,6 +1753,15 @@ nrt_status nrtOccludedBatchDevice_f64(nrt_ctx *c, const nrt_ray_f64 *r, uint64_t
   return traverse_device<double>(c, {.kind = Query::Occlusion, .rays = r, .n = n, .opt = o, .stream = (hipStream_t)s, .timed = true, .mask = m});
 }
 
+nrt_status nrtSetMeshDevice_f32(nrt_ctx *c, const float *v, uint32_t nv, size_t stride, const uint32_t *f, uint32_t nf, void *s) {
+  return set_mesh_device<float>(c, v, nv, stride, f, nf, (hipStream_t)s);
+}
+nrt_status nrtSetMeshDevice_f64(nrt_ctx *c, const double *v, uint32_t nv, size_t stride, const uint32_t *f, uint32_t nf, void *s) {
+  return set_mesh_device<double>(c, v, nv, stride, f, nf, (hipStream_t)s);
+}
+nrt_status nrtSetSpheresDevice_f32(nrt_ctx *c, const float *centers, const float *radii, uint32_t n, void *s) {
+  return set_spheres_device<float>(c, centers, radii, n, (hipStream_t)s);
+}
 nrt_status nrtSetSpheres_f32(nrt_ctx *c, const float *centers, const float *radii, uint32_t n) {
   return set_spheres<float>(c, centers, radii, n);
 }

@@ -74,8 +74,16 @@ template <typename T>
 hipError_t launch_refit_plan(const typename Wire<T>::Node *nodes, uint64_t num_nodes, uint32_t num_branch_records, uint32_t tree_depth,
                              uint32_t root_is_branch, uint32_t *plan, hipStream_t s);
 template <typename T>
-hipError_t launch_refit(const void *src, size_t stride, bool aligned, uint32_t nv, T *verts, const uint32_t *faces, const uint32_t *indices,
+hipError_t launch_refit(const void *src, size_t stride, uint32_t nv, T *verts, const uint32_t *faces, const uint32_t *indices,
                         typename Wire<T>::Node *nodes, uint64_t num_nodes, uint32_t num_branch_records, uint32_t tree_depth,
                         const uint32_t *plan, hipStream_t s);
+
+// ---- mesh.hip: geometry taken from device memory ------------------------------------------------------------------------
+// the largest of `n_indices` u32 (4-byte aligned, any length) into *out (device), 0 for none
+hipError_t launch_max_index(const uint32_t *faces, uint64_t n_indices, uint32_t *out, hipStream_t s);
+// `nv` rows of device memory, row i at byte offset i * stride with xyz first, to tight xyz (typed loads when `src` and `stride`
+// are multiples of sizeof(T), byte loads otherwise)
+template <typename T>
+hipError_t launch_gather_vertices(const void *src, size_t stride, uint32_t nv, T *tight, hipStream_t s);
 
 } // namespace nrt

@@ -7,7 +7,7 @@
 //                      d + 1 and their leaf children to the leaf list (slots by atomic counters: the lists' order varies
 //                      from plan to plan, no box depends on it)
 //   REFIT (every call)
-//     k_refit_verts    the caller's strided vertices -> the context's tight xyz
+//     (mesh.hip)       launch_gather_vertices: the caller's strided vertices -> the context's tight xyz
 //     k_refit_leaves   every reachable leaf: min / max over each coordinate of its triangles, in slot order
 //     k_refit_branches one launch per level, deepest first: union of the two children's boxes, low child first
 //   then the existing launch_gather_leaf_tris / launch_make_wide (api.hip) re-derive LeafTri and WideNode / Wide4Node.
@@ -59,27 +59,6 @@ __global__ void __launch_bounds__(kRefitBlock) k_plan_expand(const typename Wire
       }
     }
   }
-}
-
-// Aligned: the row stride and the base are multiples of sizeof(T) (typed loads); else byte loads.
-template <typename T, bool Aligned>
-__global__ void __launch_bounds__(kRefitBlock) k_refit_verts(const unsigned char *__restrict__ src, size_t stride, uint32_t nv,
-                                                             T *__restrict__ dst) {
-  const uint32_t i = blockIdx.x * kRefitBlock + threadIdx.x;
-  if (i >= nv) return;
-  const unsigned char *row = src + (size_t)i * stride;
-  T p[3];
-  if (Aligned) {
-    const T *r = reinterpret_cast<const T *>(row);
-    p[0] = r[0];
-    p[1] = r[1];
-    p[2] = r[2];
-  } else {
-    __builtin_memcpy(p, row, sizeof(p));
-  }
-  dst[3 * (size_t)i + 0] = p[0];
-  dst[3 * (size_t)i + 1] = p[1];
-  dst[3 * (size_t)i + 2] = p[2];
 }
 
 template <typename T>
@@ -171,22 +150,15 @@ hipError_t launch_refit_plan(const typename Wire<T>::Node *nodes, uint64_t num_n
 
 // One refit over a planned tree: vertices in, boxes of every reachable node out.
 template <typename T>
-hipError_t launch_refit(const void *src, size_t stride, bool aligned, uint32_t nv, T *verts, const uint32_t *faces, const uint32_t *indices,
+hipError_t launch_refit(const void *src, size_t stride, uint32_t nv, T *verts, const uint32_t *faces, const uint32_t *indices,
                         typename Wire<T>::Node *nodes, uint64_t num_nodes, uint32_t num_branch_records, uint32_t tree_depth,
                         const uint32_t *plan, hipStream_t s) {
   const uint32_t levels = tree_depth + 2u;
   const size_t hdr = plan_header_words(levels);
   const uint32_t *branch_list = plan + hdr, *leaf_list = branch_list + num_branch_records;
   const uint32_t leaf_cap = (uint32_t)(num_nodes - num_branch_records);
-  hipError_t e;
-  if (nv) {
-    const dim3 grid((nv + kRefitBlock - 1) / kRefitBlock);
-    if (aligned)
-      hipLaunchKernelGGL((k_refit_verts<T, true>), grid, dim3(kRefitBlock), 0, s, (const unsigned char *)src, stride, nv, verts);
-    else
-      hipLaunchKernelGGL((k_refit_verts<T, false>), grid, dim3(kRefitBlock), 0, s, (const unsigned char *)src, stride, nv, verts);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-  }
+  hipError_t e = launch_gather_vertices<T>(src, stride, nv, verts, s);
+  if (e != hipSuccess) return e;
   hipLaunchKernelGGL((k_refit_leaves<T>), dim3(refit_grid(leaf_cap)), dim3(kRefitBlock), 0, s, nodes, indices, faces, (const T *)verts, plan,
                      levels, leaf_list, leaf_cap);
   if ((e = hipGetLastError()) != hipSuccess) return e;
