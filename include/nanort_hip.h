@@ -630,6 +630,35 @@ NRT_API uint64_t nrtSceneLastRedone(const nrt_scene *scene);
  * over), 0 = the listing path alone (small scenes, single_pass = 0, a mesh whose tree the walk cannot step through, back-off). */
 NRT_API int nrtSceneLastPath(const nrt_scene *scene);
 
+/* ---- occlusion queries on a scene: is the ray blocked at all? (shadow rays, rtcOccluded) --------------------------
+ * The any-hit form of nrtSceneTraverseBatch*: a ray stops at the first instance in which it finds a hit instead of looking for
+ * the nearest one, and one byte per ray is the whole result.  Contract, on a committed scene:
+ *   1. Result: mask_out[i] is exactly what nrtSceneTraverseBatch_f32 / nrtSceneTraverseBatchDevice_f32 would put in
+ *      hit_mask_out[i] for the same committed scene and ray: 1 = blocked, 0 = not.  The query changes how much work is done,
+ *      never the answer — the reference's quirks included: only the 64 nearest entered node boxes by (entry distance, node id)
+ *      count (kMaxIntersections, nanosg.h:786), so a blocker that ranks 65th or later does not occlude; the local ray carries the
+ *      default [0, FLT_MAX] interval and default trace options; a local hit counts only when its world distance is < FLT_MAX
+ *      (nanosg.h:848 with t_nearest initialised to max); the world ray's min_t / max_t act on the box listing only.
+ *   2. Limit of exactness: 1. holds for rays on which the world distance of every local hit is finite.  Where a world distance
+ *      overflows or is NaN, the first accepted primitive of an instance and its nearest one may disagree on
+ *      `t_world < FLT_MAX`; such rays are outside the contract.
+ *   3. Output: no hit records are produced, staged or copied; one byte per ray leaves the GPU (host form) or is written to
+ *      d_mask_out (Device form), nothing else.
+ *   4. Ordering: as the closest-hit scene calls — synchronous, on the scene's stream, `d_rays` complete before the call; the
+ *      scene owns its scratch (not re-entrant with any other call on the same scene).
+ *   5. Errors, as nrtSceneTraverseBatch*: NRT_ERR_INVALID for a NULL scene, for NULL rays or a NULL mask with num_rays > 0, for
+ *      an uncommitted scene, for a scene made stale by nrtBuild / nrtSetMesh / nrtSetTree / nrtRefit* on one of its meshes (until
+ *      it is committed again), and for more rays than the closest-hit call accepts (2^31 - 1); num_rays == 0 returns NRT_OK.
+ *   6. Path reporting: nrtSceneLastRedone / nrtSceneLastPath describe an occlusion call as they describe a closest-hit call;
+ *      "single_pass", "walk_min", "scan_max", "fuse_scan" and the phase thresholds select paths for it the same way and never
+ *      change a flag.  The single-pass walk certifies a flag by a rule of its own (traverse.hip, above k_scene_walk): no
+ *      traced hit at all is 0; a hit in an instance with provably fewer than 64 entered boxes ranking before it is 1; any other
+ *      ray is re-done by the listing path, which applies the reference's loop literally.
+ *   7. Back-off: the closest-hit back-off ("walk_backoff_pct") is neither consulted nor updated by occlusion calls — its cause,
+ *      the reference's cull comparing a distance with a parameter, cannot hand an occlusion ray over. */
+NRT_API nrt_status nrtSceneOccludedBatch_f32(nrt_scene *scene, const nrt_ray_f32 *rays, uint64_t num_rays, uint8_t *mask_out);
+NRT_API nrt_status nrtSceneOccludedBatchDevice_f32(nrt_scene *scene, const nrt_ray_f32 *d_rays, uint64_t num_rays, uint8_t *d_mask_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -628,3 +628,25 @@ class Scene:
         torch.cuda.current_stream().synchronize()
         self._check(self._L.nrtSceneTraverseBatchDevice_f32(self._h, d_rays.data_ptr(), n, d_hits.data_ptr(),
                                                             d_mask.data_ptr() if d_mask is not None else None))
+
+    def OccludedBatch(self, rays):
+        """Occlusion query (nrtSceneOccludedBatch_f32): the hit flags `TraverseBatch` would return, and nothing else — a ray
+        stops at its first hit, no hit record is produced or copied."""
+        from .wire import RAY_F32
+
+        rays = np.ascontiguousarray(rays, dtype=RAY_F32)
+        mask = np.zeros((rays.shape[0],), dtype=np.uint8)
+        self._check(self._L.nrtSceneOccludedBatch_f32(self._h, _p(rays), rays.shape[0], _p(mask)))
+        return mask
+
+    def OccludedBatchDevice(self, d_rays, d_mask):
+        """Rays and flags in HBM: torch uint8 tensors holding RAY_F32 records in, one flag byte per ray out.  Synchronous (see
+        nrtSceneOccludedBatchDevice_f32); waits for torch's current stream first."""
+        import torch
+
+        from .wire import RAY_F32
+
+        n = d_rays.numel() // RAY_F32.itemsize
+        assert d_rays.is_cuda and d_mask.is_cuda and d_mask.numel() >= n
+        torch.cuda.current_stream().synchronize()
+        self._check(self._L.nrtSceneOccludedBatchDevice_f32(self._h, d_rays.data_ptr(), n, d_mask.data_ptr()))

@@ -34,7 +34,7 @@ SYMBOLS = [
     "nrtGroupUniqueId", "nrtGroupCreate", "nrtGroupCreateRanked", "nrtGroupDestroy", "nrtGroupLastError", "nrtGroupSetTunable", "nrtGroupInfo",
     "nrtGroupTileRays", "nrtGroupTraverseGather_f32", "nrtGroupTraverseGather_f64", "nrtGroupTraverseGatherTiles_f32", "nrtGroupTraverseGatherTiles_f64", "nrtGroupSynchronize", "nrtGroupLastTraffic",
     "nrtSceneCreate", "nrtSceneDestroy", "nrtSceneLastError", "nrtSceneAddNode_f32", "nrtSceneCommit", "nrtSceneNodeState_f32",
-    "nrtSceneBounds_f32", "nrtSceneTraverseBatch_f32", "nrtSceneTraverseBatchDevice_f32", "nrtSceneSetTunable", "nrtSceneLastRedone", "nrtSceneLastPath",
+    "nrtSceneBounds_f32", "nrtSceneTraverseBatch_f32", "nrtSceneTraverseBatchDevice_f32", "nrtSceneOccludedBatch_f32", "nrtSceneOccludedBatchDevice_f32", "nrtSceneSetTunable", "nrtSceneLastRedone", "nrtSceneLastPath",
 ]
 
 
@@ -166,6 +166,10 @@ def lib():
     L.nrtSceneTraverseBatch_f32.restype = i32
     L.nrtSceneTraverseBatchDevice_f32.argtypes = [vp, vp, u64, vp, vp]
     L.nrtSceneTraverseBatchDevice_f32.restype = i32
+    L.nrtSceneOccludedBatch_f32.argtypes = [vp, vp, u64, vp]
+    L.nrtSceneOccludedBatch_f32.restype = i32
+    L.nrtSceneOccludedBatchDevice_f32.argtypes = [vp, vp, u64, vp]
+    L.nrtSceneOccludedBatchDevice_f32.restype = i32
     L.nrtSceneSetTunable.argtypes = [vp, ctypes.c_char_p, i32]
     L.nrtSceneSetTunable.restype = i32
     L.nrtSceneLastRedone.argtypes = [vp]

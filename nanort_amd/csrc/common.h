@@ -270,6 +270,7 @@ struct SceneTraceArgs {
                               // that — expensive, divergent — step for them; fewer wait while `cand_busy_max` or more lanes still walk
   uint32_t cand_busy_max;
   const uint32_t *subset;     // non-null: the launch traces rays[subset[s]] for s < n (lists and counts are indexed by s, results by the ray)
+  uint32_t any_hit;           // launcher only: the occlusion instantiation (k_scene_trace<.., ANY = true>): flags only, `hits` is never touched
 };
 
 // The single-pass scene walk (traverse.hip k_scene_walk): the top-level tree and the instances' trees walked by the same lane on
@@ -315,6 +316,8 @@ struct SceneWalkArgs {
   uint32_t *redo;       // [n]: rays left to the listing path
   uint32_t *redo_count; // zero at launch
   unsigned long long *counters; // profiling build only (libnanort_hip_prof.so): 13 loop counters of the launch, or null
+  uint32_t any_hit;     // launcher only: the occlusion instantiation (k_scene_walk<.., ANY = true>): flags only, `hits` is never touched, `mask` non-null
+  uint32_t num_insts;   // ... which ends a ray at its first hit when the scene has at most 64 instances (every entered box is listed)
 };
 
 // Completion record of a launch slot, in page-locked host memory the device writes to: the last wave of a traversal

@@ -223,6 +223,8 @@ inline RTCRay *ray_at(RTCRay *base, size_t i, size_t stride) {
 // which the traversal needs 32 and returns 20: the records are converted on the host into the (page-locked) staging the
 // scene call copies from.  Long streams go piece by piece with the three stages overlapped — while the GPU traces piece k
 // (a helper thread sits in nrtSceneTraverseBatch_f32) this thread's team converts piece k+1 and writes piece k-1 back.
+// An occlusion query (rtcOccluded*) goes through nrtSceneOccludedBatch_f32: one flag byte per ray comes back, no record
+// staging is allocated and no record crosses PCIe.
 template <class Get>
 void trace(Scene *s, size_t n, bool occluded, Get get) {
   if (!s || n == 0) return;
@@ -234,9 +236,9 @@ void trace(Scene *s, size_t n, bool occluded, Get get) {
   uint8_t *mask = nullptr;
   if (ok) {
     rays = static_cast<nrt_ray_f32 *>(s->rays.ensure(n * sizeof(nrt_ray_f32)));
-    hits = static_cast<nrt_scene_hit_f32 *>(s->hits.ensure(n * sizeof(nrt_scene_hit_f32)));
+    if (!occluded) hits = static_cast<nrt_scene_hit_f32 *>(s->hits.ensure(n * sizeof(nrt_scene_hit_f32)));
     mask = static_cast<uint8_t *>(s->mask.ensure(n));
-    if (!rays || !hits || !mask) {
+    if (!rays || (!occluded && !hits) || !mask) {
       report(s->device, RTC_OUT_OF_MEMORY, "rtcIntersect/rtcOccluded: no host memory for %zu rays", n);
       ok = false;
     }
@@ -282,6 +284,7 @@ void trace(Scene *s, size_t n, bool occluded, Get get) {
     }
   };
   auto gpu = [&](size_t lo, size_t hi) {
+    if (occluded) return nrtSceneOccludedBatch_f32(s->scene, rays + lo, hi - lo, mask + lo) == NRT_OK;
     return nrtSceneTraverseBatch_f32(s->scene, rays + lo, hi - lo, hits + lo, mask + lo) == NRT_OK;
   };
   if (!ok) {

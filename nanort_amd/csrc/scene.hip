@@ -683,9 +683,10 @@ nrt_status nrtSceneNodeState_f32(nrt_scene *s, uint32_t node_id, float out[64]) 
 } // extern "C"
 
 // The listing path: one of the listing kernels + k_scene_trace, enqueued on the scene's stream, over the whole batch
-// (`subset` == nullptr) or over the rays named by `subset` (the ones the single-pass walk left over).
+// (`subset` == nullptr) or over the rays named by `subset` (the ones the single-pass walk left over).  `any_hit`: the occlusion
+// instantiation of k_scene_trace — the same lists, flags only, d_hits unused.
 static nrt_status scene_list_and_trace(nrt_scene *s, const nrt_ray_f32 *d_rays, uint32_t n, const uint32_t *subset,
-                                       nrt_scene_hit_f32 *d_hits, uint8_t *d_mask) {
+                                       nrt_scene_hit_f32 *d_hits, uint8_t *d_mask, bool any_hit) {
   const uint32_t num_nodes = (uint32_t)s->insts.size();
   const uint32_t cap = std::min<uint32_t>(kMaxList, num_nodes);
   SCHK(s, nrt::devbuf_ensure(&s->d_list_t, (size_t)cap * n * sizeof(float)));
@@ -741,6 +742,7 @@ static nrt_status scene_list_and_trace(nrt_scene *s, const nrt_ray_f32 *d_rays, 
   a.cand_min = s->cand_min;
   a.cand_busy_max = s->cand_busy_max;
   a.subset = subset;
+  a.any_hit = any_hit ? 1u : 0u;
   SCHK(s, nrt::launch_scene_trace(a, trace_grid, s->stream));
   return NRT_OK;
 }
@@ -748,23 +750,26 @@ static nrt_status scene_list_and_trace(nrt_scene *s, const nrt_ray_f32 *d_rays, 
 // `device` = rays / hits_out / mask_out are device pointers (no PCIe traffic).  Scenes with a top-level tree: ONE launch of the
 // single-pass walk (k_scene_walk), then — only if it left rays over — the listing path on those; other scenes (a handful of
 // nodes) and single_pass = 0: the listing path on the whole batch.  The call returns with everything finished (the scene owns
-// the per-ray scratch).
+// the per-ray scratch).  `occluded`: the occlusion query (scene_occluded below) — the same path selection and ray staging with
+// the any-hit kernel instantiations; no record buffer is allocated, written or copied (hits_out is NULL), mask_out is required,
+// and the closest-hit back-off is neither consulted nor updated.
 static nrt_status scene_traverse(nrt_scene *s, const nrt_ray_f32 *rays, uint64_t n64, nrt_scene_hit_f32 *hits_out,
-                                 uint8_t *mask_out, bool device) {
+                                 uint8_t *mask_out, bool device, bool occluded = false) {
   if (!s) return NRT_ERR_INVALID;
-  if (!s->committed) return sfail(s, NRT_ERR_INVALID, "nrtSceneTraverseBatch: commit the scene first");
+  const char *what = occluded ? "nrtSceneOccludedBatch" : "nrtSceneTraverseBatch";
+  if (!s->committed) return sfail(s, NRT_ERR_INVALID, "%s: commit the scene first", what);
   if (n64 == 0) return NRT_OK;
-  if (!rays || !hits_out) return sfail(s, NRT_ERR_INVALID, "nrtSceneTraverseBatch: NULL rays/hits");
-  if (n64 > 0x7FFFFFFFull) return sfail(s, NRT_ERR_INVALID, "nrtSceneTraverseBatch: too many rays in one call");
+  if (!rays || (occluded ? !mask_out : !hits_out)) return sfail(s, NRT_ERR_INVALID, "%s: NULL rays/%s", what, occluded ? "mask" : "hits");
+  if (n64 > 0x7FFFFFFFull) return sfail(s, NRT_ERR_INVALID, "%s: too many rays in one call", what);
   // the instance table holds device addresses, layout flags and stack depths of the mesh contexts' trees as they were at
   // Commit: a context rebuilt or re-set since then may have moved or re-shaped them — refuse instead of walking stale memory
   for (size_t m = 0; m < s->mesh_gens.size(); m++)
     if (nrt_internal_generation(s->mesh_gens[m].first) != s->mesh_gens[m].second)
-      return sfail(s, NRT_ERR_INVALID, "nrtSceneTraverseBatch: a mesh context was rebuilt or re-set since nrtSceneCommit (commit the scene again)");
+      return sfail(s, NRT_ERR_INVALID, "%s: a mesh context was rebuilt or re-set since nrtSceneCommit (commit the scene again)", what);
   const uint32_t n = (uint32_t)n64;
   SCHK(s, hipSetDevice(s->device));
   if (!device) SCHK(s, nrt::devbuf_ensure(&s->d_rays, (size_t)n * sizeof(nrt_ray_f32)));
-  if (!device) SCHK(s, nrt::devbuf_ensure(&s->d_best, (size_t)n * sizeof(nrt_scene_hit_f32)));
+  if (!device && !occluded) SCHK(s, nrt::devbuf_ensure(&s->d_best, (size_t)n * sizeof(nrt_scene_hit_f32)));
   if (!device && mask_out) SCHK(s, nrt::devbuf_ensure(&s->d_mask, (size_t)n));
   if (s->trace_blocks_per_cu == 0) {
     s->trace_blocks_per_cu = (unsigned)nrt::scene_trace_blocks_per_cu();
@@ -791,7 +796,7 @@ static nrt_status scene_traverse(nrt_scene *s, const nrt_ray_f32 *rays, uint64_t
   }
   SCHK(s, nrt::devbuf_ensure(&s->d_cursor, (size_t)nrt::kMaxParts * nrt::kCursorStrideWords * sizeof(uint32_t)));
   const nrt_ray_f32 *d_rays = device ? rays : (const nrt_ray_f32 *)s->d_rays.p;
-  nrt_scene_hit_f32 *d_hits = device ? hits_out : (nrt_scene_hit_f32 *)s->d_best.p;
+  nrt_scene_hit_f32 *d_hits = occluded ? nullptr : (device ? hits_out : (nrt_scene_hit_f32 *)s->d_best.p);
   uint8_t *d_mask = device ? mask_out : (mask_out ? (uint8_t *)s->d_mask.p : nullptr);
   if (!device) SCHK(s, hipMemcpyAsync(s->d_rays.p, rays, (size_t)n * sizeof(nrt_ray_f32), hipMemcpyHostToDevice, s->stream));
 
@@ -802,7 +807,9 @@ static nrt_status scene_traverse(nrt_scene *s, const nrt_ray_f32 *rays, uint64_t
   // a batch the walk could not certify for the most part (direction vectors far shorter than 1: the reference's cull then compares
   // a distance with a parameter and fires early, nanosg.h:795) costs more than the listing path alone: after one, the next
   // kWalkBackoff calls go straight to the listing path, then the walk is tried again
-  const bool walk = eligible && (s->single_pass > 1 || s->walk_backoff == 0);
+  // (an occlusion ray cannot be handed over by that cull — it acts only once there is a hit, and the first hit ends the ray — so
+  // occlusion calls always take the walk when it is eligible and leave the back-off counter alone)
+  const bool walk = eligible && (occluded || s->single_pass > 1 || s->walk_backoff == 0);
   if (eligible && !walk) s->walk_backoff--;
   if (walk) {
     s->last_path = 1;
@@ -841,8 +848,10 @@ static nrt_status scene_traverse(nrt_scene *s, const nrt_ray_f32 *rays, uint64_t
     w.redo = (uint32_t *)s->d_redo.p;
     w.redo_count = (uint32_t *)s->d_redo_count.p;
     w.counters = nullptr;
+    w.any_hit = occluded ? 1u : 0u;
+    w.num_insts = (uint32_t)s->insts.size();
 #ifdef NRT_PROF
-    if (s->count_loops) {
+    if (s->count_loops && !occluded) {
       SCHK(s, nrt::devbuf_ensure(&s->d_counters, 16 * sizeof(unsigned long long)));
       SCHK(s, hipMemsetAsync(s->d_counters.p, 0, 16 * sizeof(unsigned long long), s->stream));
       w.counters = (unsigned long long *)s->d_counters.p;
@@ -852,24 +861,38 @@ static nrt_status scene_traverse(nrt_scene *s, const nrt_ray_f32 *rays, uint64_t
     SCHK(s, hipMemcpyAsync(s->h_redo_count, s->d_redo_count.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
     SCHK(s, hipStreamSynchronize(s->stream));
     s->last_redone = *s->h_redo_count;
-    if ((uint64_t)*s->h_redo_count * 100u > (uint64_t)n * s->walk_backoff_pct) s->walk_backoff = kWalkBackoff;
+    if (!occluded && (uint64_t)*s->h_redo_count * 100u > (uint64_t)n * s->walk_backoff_pct) s->walk_backoff = kWalkBackoff;
     if (*s->h_redo_count) {
-      const nrt_status st = scene_list_and_trace(s, d_rays, *s->h_redo_count, (const uint32_t *)s->d_redo.p, d_hits, d_mask);
+      const nrt_status st = scene_list_and_trace(s, d_rays, *s->h_redo_count, (const uint32_t *)s->d_redo.p, d_hits, d_mask, occluded);
       if (st != NRT_OK) return st;
     }
   } else {
-    const nrt_status st = scene_list_and_trace(s, d_rays, n, nullptr, d_hits, d_mask);
+    const nrt_status st = scene_list_and_trace(s, d_rays, n, nullptr, d_hits, d_mask, occluded);
     if (st != NRT_OK) return st;
   }
   if (!device) {
-    SCHK(s, hipMemcpyAsync(hits_out, s->d_best.p, (size_t)n * sizeof(nrt_scene_hit_f32), hipMemcpyDeviceToHost, s->stream));
+    if (!occluded) SCHK(s, hipMemcpyAsync(hits_out, s->d_best.p, (size_t)n * sizeof(nrt_scene_hit_f32), hipMemcpyDeviceToHost, s->stream));
     if (mask_out) SCHK(s, hipMemcpyAsync(mask_out, s->d_mask.p, (size_t)n, hipMemcpyDeviceToHost, s->stream));
   }
   SCHK(s, hipStreamSynchronize(s->stream));
   return NRT_OK;
 }
 
+// The occlusion query: scene_traverse's path selection and ray staging with the any-hit kernels; one byte per ray is all that is
+// produced, staged or copied (include/nanort_hip.h: the nrtSceneOccludedBatch contract).
+static nrt_status scene_occluded(nrt_scene *s, const nrt_ray_f32 *rays, uint64_t n64, uint8_t *mask_out, bool device) {
+  return scene_traverse(s, rays, n64, nullptr, mask_out, device, true);
+}
+
 extern "C" {
+
+nrt_status nrtSceneOccludedBatch_f32(nrt_scene *s, const nrt_ray_f32 *rays, uint64_t n, uint8_t *mask_out) {
+  return scene_occluded(s, rays, n, mask_out, false);
+}
+
+nrt_status nrtSceneOccludedBatchDevice_f32(nrt_scene *s, const nrt_ray_f32 *d_rays, uint64_t n, uint8_t *d_mask_out) {
+  return scene_occluded(s, d_rays, n, d_mask_out, true);
+}
 
 nrt_status nrtSceneTraverseBatch_f32(nrt_scene *s, const nrt_ray_f32 *rays, uint64_t n, nrt_scene_hit_f32 *hits_out,
                                      uint8_t *mask_out) {

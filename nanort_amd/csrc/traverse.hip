@@ -1262,7 +1262,15 @@ __device__ __forceinline__ void scene_mult_v(float dst[3], const float m[4][4], 
 // the ray — every world box tested in id order, exactly what the listing kernel of such scenes did in a launch of its own
 // (scene.hip k_scene_list) — into its own slots of the list arrays, which it alone reads back: one launch per batch, no second
 // pass over the rays.
-template <int STACK, bool SCAN>
+// ANY: the occlusion query (nrtSceneOccludedBatch*): only the flag is wanted.  The flag of the closest-hit form is "some candidate
+// the loop opens has a local hit whose world distance is < FLT_MAX" — the first such hit sets it and nothing clears it, and until
+// that hit the nearest distance is still FLT_MAX, so the cull (nanosg.h:795) opens the same candidates in both forms.  So the ANY
+// form walks the same candidates in the same order, lets a local walk drop its stack at the first leaf that accepts a primitive
+// (the single-level any-hit rule of k_traverse_wide), and finishes the ray with flag 1 at the first local hit with
+// t_world < FLT_MAX.  It writes no record (a.hits is not read).  The one place the forms can differ: the dropped walk's hit is the
+// first accepted, not the nearest, and where world distances overflow or are NaN the two may disagree on t_world < FLT_MAX
+// (include/nanort_hip.h states that limit).
+template <int STACK, bool SCAN, bool ANY = false>
 __global__ __launch_bounds__(kTraverseBlock) void k_scene_trace(const SceneTraceArgs a) {
   typedef float T;
   typedef StackEntry<float> SE;
@@ -1343,6 +1351,7 @@ __global__ __launch_bounds__(kTraverseBlock) void k_scene_trace(const SceneTrace
           last_id = 0u;
           best_t = 3.402823466e+38f;
           has_hit = false;
+          if constexpr (!ANY) {
           nrt_scene_hit_f32 h; // the miss record; overwritten by every strictly nearer hit
           h.t = r.max_t;
           h.u = 0.0f;
@@ -1350,6 +1359,7 @@ __global__ __launch_bounds__(kTraverseBlock) void k_scene_trace(const SceneTrace
           h.prim_id = 0xFFFFFFFFu;
           h.node_id = 0xFFFFFFFFu;
           a.hits[ri] = h;
+          }
           state = S_NEXT;
         }
       }
@@ -1373,6 +1383,12 @@ __global__ __launch_bounds__(kTraverseBlock) void k_scene_trace(const SceneTrace
         scene_mult_v(wp, nd.xform, lp);
         const float px = wp[0] - worg[0], py = wp[1] - worg[1], pz = wp[2] - worg[2];
         const float t_world = __builtin_sqrtf(px * px + py * py + pz * pz); // vlength, nanort.h:383-385
+        if constexpr (ANY) {
+          if (t_world < best_t) { // (best_t is still FLT_MAX) occluded: no further candidate is opened, S_NEXT below writes the flag
+            has_hit = true;
+            j = cnt;
+          }
+        } else
         if (t_world < best_t) {                                             // strict, nanosg.h:838
           best_t = t_world;
           has_hit = true;
@@ -1497,6 +1513,8 @@ __global__ __launch_bounds__(kTraverseBlock) void k_scene_trace(const SceneTrace
           tri_test<float, true>(L, t1, two, 0u, 0u, 0u, false);
         }
       }
+      // occlusion query: any accepted primitive settles this instance — drop what is left of its stack (as k_traverse_wide does)
+      if constexpr (ANY) sp = (state == W_LEAF && L.hit_t < L.max_t) ? 0 : sp;
       state = (state == W_LEAF) ? W_POP : state;
     }
   }
@@ -1505,9 +1523,12 @@ __global__ __launch_bounds__(kTraverseBlock) void k_scene_trace(const SceneTrace
 static const void *scene_trace_kernel(bool scan) {
   return scan ? (const void *)k_scene_trace<kSceneLdsStack, true> : (const void *)k_scene_trace<kSceneLdsStack, false>;
 }
+static const void *scene_trace_any_kernel(bool scan) {
+  return scan ? (const void *)k_scene_trace<kSceneLdsStack, true, true> : (const void *)k_scene_trace<kSceneLdsStack, false, true>;
+}
 hipError_t launch_scene_trace(const SceneTraceArgs &args, unsigned grid, hipStream_t s) {
   if (args.n == 0) return hipSuccess;
-  launch_persistent(scene_trace_kernel(args.scan_nodes != 0), grid, args, s);
+  launch_persistent(args.any_hit ? scene_trace_any_kernel(args.scan_nodes != 0) : scene_trace_kernel(args.scan_nodes != 0), grid, args, s);
   return hipGetLastError();
 }
 int scene_trace_blocks_per_cu() { // (one grid size for both: the fewer)
@@ -1537,6 +1558,29 @@ int scene_trace_blocks_per_cu() { // (one grid size for both: the fewer)
 // The argument is spelled out and tested on the CPU, with random visiting orders and random skipping, by the model
 // sgo_traverse_unordered_model (tests/test_scene_walk_model.py); tests/test_gpu_scene.py compares this kernel with the listing
 // path and the restatement record by record.
+//
+// ANY = true: THE OCCLUSION FORM (nrtSceneOccludedBatch*).  Only the flag is wanted, and the reference's flag is
+//     F = "one of the 64 entered instances of smallest rank (entry distance, id) has a local hit with t_world < FLT_MAX"
+// (before the first such hit the nearest distance is still FLT_MAX, so the cull at nanosg.h:795 cannot skip a listed instance
+// whose entry distance is <= FLT_MAX; the first such hit sets the flag and nothing clears it).  The closest-hit certificate above
+// does not carry over — there is no winner to compare with.  The walk instead runs in two modes:
+//   * searching  (no qualifying hit yet): nothing is skipped — skipping needs a winner, cull_t stays +inf — so every entered
+//                instance the top-level walk reaches is opened (`traced` counts them), and its local walk drops its stack at the
+//                first leaf that accepts a primitive.  If the top-level walk ends in this mode, EVERY entered instance was traced
+//                and none has a qualifying hit; the reference's 64 are a subset of them: F = 0, however many boxes were entered.
+//   * counting   after the first qualifying hit, in instance h entered at e_h: F = 1 if h is one of the 64 of smallest rank, i.e.
+//                if fewer than 64 entered instances rank before (e_h, id_h).  (If h is NOT among them, F depends on instances this
+//                lane has not traced: nothing is claimed, the ray goes to `redo`.)  The lane does not keep the ranks of the
+//                instances it opened before h, so it bounds: B = (instances opened before h, all of them taken to rank before h)
+//                + (entered instances met later in the top-level walk with (e, id) < (e_h, id_h)).  B >= the true number in front
+//                of h, so B < 64 proves F = 1.  In this mode no instance is opened; top-level subtrees entered beyond
+//                max(e_h, ray.min_t) are skipped for tame rays (everything inside is entered no earlier than the subtree's box,
+//                hence ranks behind h and does not count — the closest-hit skip rule with the hit distance left out); other rays
+//                walk every top-level box they enter.  B reaching 64 sends the ray to `redo` at once; so does a hit in an instance
+//                entered beyond FLT_MAX (the one entry distance the reference's cull does fire on before a hit).
+//   * shortcut   a scene of at most 64 instances: every entered instance is listed, the first qualifying hit ends the ray with 1.
+// `redo` rays go through the listing path in its ANY form, which is exact.  No record is written (a.hits is not read).  The rule
+// is modelled and tested on the CPU with random visiting orders and random legal skipping (tests/test_scene_occlusion_model.py).
 // ---------------------------------------------------------------------------
 enum : int { T_ENTER = 7, S_END = 8 }; // a top-level leaf was reached: open its instance / the top-level stack ran empty: the ray is finished
 
@@ -1565,7 +1609,7 @@ do {                                                                            
   state = fin_ ? (in_top ? S_END : S_FIN) : (enter_ ? ((ref_ & kLeafBit) ? W_LEAF : W_TRAV) : W_POP); \
 } while (0)
 
-template <int STACK, bool STATS>
+template <int STACK, bool STATS, bool ANY = false>
 __global__ __launch_bounds__(kTraverseBlock, STATS ? 1 : NRT_SCENE_WALK_WAVES) void k_scene_walk(const SceneWalkArgs a) {
   typedef float T;
   typedef StackEntry<float> SE;
@@ -1663,6 +1707,7 @@ __global__ __launch_bounds__(kTraverseBlock, STATS ? 1 : NRT_SCENE_WALK_WAVES) v
             cull_t = __builtin_huge_valf();
             has_hit = false;
             traced = 0u;
+            if constexpr (!ANY) {
             nrt_scene_hit_f32 h; // the miss record; overwritten by every better hit
             h.t = r.max_t;
             h.u = 0.0f;
@@ -1670,6 +1715,7 @@ __global__ __launch_bounds__(kTraverseBlock, STATS ? 1 : NRT_SCENE_WALK_WAVES) v
             h.prim_id = 0xFFFFFFFFu;
             h.node_id = 0xFFFFFFFFu;
             a.hits[i] = h;
+            }
             sp = 0;
             world_ray();
             cur = 0u; // record 0 == the root branch (its own box test is implied by its children's)
@@ -1699,6 +1745,24 @@ __global__ __launch_bounds__(kTraverseBlock, STATS ? 1 : NRT_SCENE_WALK_WAVES) v
             scene_mult_v(wp, nd.xform, lp);
             const float px = wp[0] - worg[0], py = wp[1] - worg[1], pz = wp[2] - worg[2];
             const float t_world = __builtin_sqrtf(px * px + py * py + pz * pz); // vlength, nanort.h:383-385
+            if constexpr (ANY) {
+              if (t_world < 3.402823466e+38f) { // the first qualifying hit (searching mode ends; see the comment above the kernel)
+                const uint32_t before = traced - 1u; // instances opened before this one: all taken to rank before it
+                if (3.402823466e+38f < cur_tmin || before >= 64u) {
+                  a.redo[atomicAdd(a.redo_count, 1u)] = i;
+                  state = S_DONE;
+                } else if (a.num_insts <= 64u) {
+                  a.mask[i] = 1;
+                  state = S_DONE;
+                } else { // counting mode: (best_tmin, best_id) = h's rank, traced = the bound B
+                  has_hit = true;
+                  best_tmin = cur_tmin;
+                  best_id = inst;
+                  traced = before;
+                  cull_t = tame ? (cur_tmin > wmin_t ? cur_tmin : wmin_t) : __builtin_huge_valf();
+                }
+              }
+            } else {
             // strict '<' in rank order (nanosg.h:838) == smallest (t_world, rank) in any order
             const bool wins = t_world < best_t ||
                               (has_hit && t_world == best_t && (cur_tmin < best_tmin || (cur_tmin == best_tmin && inst < best_id)));
@@ -1720,9 +1784,12 @@ __global__ __launch_bounds__(kTraverseBlock, STATS ? 1 : NRT_SCENE_WALK_WAVES) v
             } else if (t_world < t2) {
               t2 = t_world;
             }
+            }
           }
-          world_ray();
-          state = W_POP;
+          if (!ANY || state != S_DONE) {
+            world_ray();
+            state = W_POP;
+          }
         } else if (state == T_ENTER) {
           // cur: a leaf reference of the top-level tree, (count - 1, first) into its index array.  One instance is opened now;
           // the others of a leaf of several (boxes the builder could not separate) wait on the stack as a leaf of one fewer.
@@ -1762,9 +1829,19 @@ __global__ __launch_bounds__(kTraverseBlock, STATS ? 1 : NRT_SCENE_WALK_WAVES) v
           float f = (b1 < b0) ? b1 : b0;
           f = (b2 < f) ? b2 : f;
           const bool entered = tmn <= tmx && e <= f;
-          const bool behind = has_hit && best_t < e && (best_tmin < e || (best_tmin == e && best_id < k)); // ranks behind a nearer hit
+          bool behind = has_hit && best_t < e && (best_tmin < e || (best_tmin == e && best_id < k)); // ranks behind a nearer hit
+          if constexpr (ANY) { // counting mode: nothing is opened any more; an entered box that ranks before the hit instance's counts
+            behind = has_hit;
+            if (has_hit && entered && (e < best_tmin || (e == best_tmin && k < best_id))) traced++;
+          }
           if (!entered || behind) {
             state = W_POP; // (still in the top-level tree)
+            if constexpr (ANY) {
+              if (has_hit && traced >= 64u) { // B reached 64: the hit instance may lie outside the reference's list
+                a.redo[atomicAdd(a.redo_count, 1u)] = i;
+                state = S_DONE;
+              }
+            }
           } else {
             inst = k;
             cur_tmin = e;
@@ -1794,7 +1871,7 @@ __global__ __launch_bounds__(kTraverseBlock, STATS ? 1 : NRT_SCENE_WALK_WAVES) v
             }
           }
         } else if (state == S_END) {
-          const bool certified = traced <= 64u && (!has_hit || t2 >= best_tmin);
+          const bool certified = ANY || (traced <= 64u && (!has_hit || t2 >= best_tmin)); // (ANY: no hit: 0; a hit with B < 64: 1 — B >= 64 left above)
           if (certified) {
             if (a.mask) a.mask[i] = has_hit ? 1 : 0;
           } else {
@@ -1871,6 +1948,8 @@ __global__ __launch_bounds__(kTraverseBlock, STATS ? 1 : NRT_SCENE_WALK_WAVES) v
           tri_test<float, true>(L, t1, two, 0u, 0u, 0u, false);
         }
       }
+      // occlusion query: any accepted primitive settles this instance — drop what is left of ITS part of the stack
+      if constexpr (ANY) sp = (state == W_LEAF && L.hit_t < L.max_t) ? base : sp;
       state = (state == W_LEAF) ? W_POP : state;
       if (STATS) st[12] += clock64() - c2_;
     }
@@ -1890,7 +1969,10 @@ hipError_t launch_scene_walk(const SceneWalkArgs &args, unsigned grid, hipStream
   }
 #endif
   NRT_RANGE("scene walk launch (k_scene_walk)");
-  hipLaunchKernelGGL((k_scene_walk<kSceneWalkLdsStack, false>), dim3(grid), dim3(kTraverseBlock), 0, s, args);
+  if (args.any_hit)
+    hipLaunchKernelGGL((k_scene_walk<kSceneWalkLdsStack, false, true>), dim3(grid), dim3(kTraverseBlock), 0, s, args);
+  else
+    hipLaunchKernelGGL((k_scene_walk<kSceneWalkLdsStack, false>), dim3(grid), dim3(kTraverseBlock), 0, s, args);
   return hipGetLastError();
 }
 int scene_walk_blocks_per_cu() { return resident_blocks((const void *)k_scene_walk<kSceneWalkLdsStack, false>, 3); }
