@@ -932,6 +932,194 @@ class CylinderIntersector {
 };
 
 // ---------------------------------------------------------------------------
+// Built-in curve primitive: hair and fur as cubic Bezier curves, the reference's third custom-primitive example,
+// examples/curves_primitive/main.cc (GetZAlign :382-417, Xform :419-430, EvaluateBezier :432-454, EvaluateBezierTangent
+// :456-462, CurvePred :481-509, CurveGeometry :513-604, CurveIntersection :606-619, CurveIntersector :621-840) — same concepts,
+// same arithmetic.  Named BezierCurve* so that a program which still carries the example's own Curve* classes compiles
+// against this header unchanged.  Four control points (12 floats) and four radii per curve; the intersector walks the curve
+// as `num_subdivisions` line segments in a frame whose z axis is the ray and reads the first and the last radius.  With
+// NANORT_USE_HIP_BACKEND, Build() over (BezierCurveGeometry, BezierCurvePred) and TraverseBatch() with
+// BezierCurveIntersection run on the GPU (nrtSetCurves_f32).  fp32, like the example.
+// ---------------------------------------------------------------------------
+class BezierCurvePred {
+ public:
+  explicit BezierCurvePred(const float *control_points) : axis_(0), pos_(0.0f), cps_(control_points) {}
+  void Set(int axis, float pos) const {
+    axis_ = axis;
+    pos_ = pos;
+  }
+  bool operator()(unsigned int i) const {
+    const float *p = cps_ + 12 * static_cast<size_t>(i) + axis_;
+    return (p[0] + p[3] + p[6] + p[9]) / 4.0f < pos_;
+  }
+
+ private:
+  mutable int axis_;
+  mutable float pos_;
+  const float *cps_;
+};
+
+class BezierCurveGeometry {
+ public:
+  BezierCurveGeometry(const float *control_points, const float *radii) : cps_(control_points), radii_(radii) {}
+  // (a Bezier curve lies inside the hull of its control points: the box of the four points, each grown by its radius)
+  void BoundingBox(real3<float> *bmin, real3<float> *bmax, unsigned int i) const {
+    const float *p = cps_ + 12 * static_cast<size_t>(i), *r = radii_ + 4 * static_cast<size_t>(i);
+    for (int k = 0; k < 3; k++) {
+      (*bmin)[k] = p[k] - r[0];
+      (*bmax)[k] = p[k] + r[0];
+      for (int j = 1; j < 4; j++) {
+        (*bmin)[k] = std::min(p[3 * j + k] - r[j], (*bmin)[k]);
+        (*bmax)[k] = std::max(p[3 * j + k] + r[j], (*bmax)[k]);
+      }
+    }
+  }
+  void BoundingBoxAndCenter(real3<float> *bmin, real3<float> *bmax, real3<float> *center, unsigned int i) const {
+    BoundingBox(bmin, bmax, i);
+    const float *p = cps_ + 12 * static_cast<size_t>(i);
+    for (int k = 0; k < 3; k++) (*center)[k] = (p[k] + p[3 + k] + p[6 + k] + p[9 + k]) / 4.0f;
+  }
+  const float *GetControlPoints() const { return cps_; }
+  const float *GetRadii() const { return radii_; }
+
+ private:
+  const float *cps_;
+  const float *radii_;
+};
+
+class BezierCurveIntersection {
+ public:
+  BezierCurveIntersection() : t(std::numeric_limits<float>::max()), prim_id(static_cast<unsigned int>(-1)), u(0.0f), v(0.0f), tangent(0.0f), normal(0.0f) {}
+  float t;
+  unsigned int prim_id;
+  float u;                // curve parameter of the hit, over the whole curve
+  float v;                // distance of the ray from the curve's axis there
+  real3<float> tangent;   // curve direction
+  real3<float> normal;    // perpendicular to the curve, in the plane of the ray and the tangent
+};
+
+template <class H = BezierCurveIntersection>
+class BezierCurveIntersector {
+ public:
+  BezierCurveIntersector(const float *control_points, const float *radii, int num_subdivisions = 4)
+      : cps_(control_points), radii_(radii), num_subdivisions_(num_subdivisions), t_(0.0f), u_(0.0f), v_(0.0f), prim_id_(0), u_param_(0.0f),
+        v_param_(0.0f) {}
+
+  bool Intersect(float *t_inout, unsigned int i) const {
+    if (i < opts_.prim_ids_range[0] || i >= opts_.prim_ids_range[1]) return false;
+    float m[3][3], tr[3];
+    ZAlign(m, tr);
+    const float *p = cps_ + 12 * static_cast<size_t>(i);
+    const float r0 = radii_[4 * static_cast<size_t>(i)], r3 = radii_[4 * static_cast<size_t>(i) + 3];
+    float c[4][3];
+    float t_z = 0.0f;
+    for (int j = 0; j < 4; j++) {
+      for (int k = 0; k < 3; k++) c[j][k] = p[3 * j] * m[0][k] + p[3 * j + 1] * m[1][k] + p[3 * j + 2] * m[2][k] + tr[k];
+      if (t_z < c[j][2]) t_z = c[j][2];
+    }
+    const float uw = std::max(r0, r3) / 2.0f;
+    if (t_z < 4.0f * uw) return false;
+    bool has_hit = false;
+    const int n = num_subdivisions_;
+    const float inv_n = 1.0f / static_cast<float>(n);
+    const float w0 = 0.5f * r0, w1 = 0.5f * r3;
+    for (int s = 0; s < n; s++) {
+      float p0[3], p1[3];
+      Bezier(c, s / static_cast<float>(n), p0);
+      Bezier(c, (s + 1) / static_cast<float>(n), p1);
+      const float ax = 0.0f - p0[0], ay = 0.0f - p0[1];  // the origin, projected onto the segment in the frame's xy plane
+      const float bx = p1[0] - p0[0], by = p1[1] - p0[1], bz = p1[2] - p0[2], bw = w1 - w0;
+      const float d0 = (ax * bx) + (ay * by), d1 = (bx * bx) + (by * by);
+      float u = d0 / d1;
+      u = std::max(0.0f, std::min(1.0f, u));  // (a NaN u, from a zero-length segment, becomes 1)
+      const float px = p0[0] + (u * bx), py = p0[1] + (u * by), t = p0[2] + (u * bz), r = w0 + (u * bw);
+      const float r2 = r * r, d2 = (px * px) + (py * py);
+      if ((d2 <= r2) && (t < (*t_inout))) {
+        u_param_ = (u + static_cast<float>(s)) * inv_n;
+        v_param_ = std::sqrt(d2);
+        (*t_inout) = t;
+        has_hit = true;
+      }
+    }
+    return has_hit;
+  }
+  float GetT() const { return t_; }
+  void Update(float t, unsigned int i) const {
+    t_ = t;
+    prim_id_ = i;
+    u_ = u_param_;
+    v_ = v_param_;
+  }
+  void PrepareTraversal(const Ray<float> &ray, const BVHTraceOptions &options) const {
+    org_ = real3<float>(ray.org);
+    dir_ = real3<float>(ray.dir);
+    opts_ = options;
+  }
+  void PostTraversal(const Ray<float> &, bool hit, H *isect) const {
+    if (!hit || !isect) return;
+    const float *p = cps_ + 12 * static_cast<size_t>(prim_id_);
+    const real3<float> v0(p), v1(p + 3), v2(p + 6), v3(p + 9);
+    const real3<float> C1 = v3 - (3.0f * v2) + (3.0f * v1) - v0;
+    const real3<float> C2 = (3.0f * v2) - (6.0f * v1) + (3.0f * v0);
+    const real3<float> C3 = (3.0f * v1) - (3.0f * v0);
+    isect->tangent = vnormalize((3.0f * C1 * u_ * u_) + (2.0f * C2 * u_) + C3);
+    isect->normal = vnormalize(vcross(vcross(dir_, isect->tangent), isect->tangent));
+    isect->t = t_;
+    isect->u = u_;
+    isect->v = v_;
+    isect->prim_id = prim_id_;
+  }
+  int NumSubdivisions() const { return num_subdivisions_; }
+
+ private:
+  // The rotation that puts the ray's direction on the z axis, and the translation that puts its origin at 0.
+  void ZAlign(float m[3][3], float tr[3]) const {
+    const float lx = dir_[0], ly = dir_[1], lz = dir_[2];
+    const float dxz = std::sqrt(lx * lx + lz * lz);
+    if (dxz > 0) {
+      const float lxdxz = lx / dxz, lydxz = ly / dxz, lzdxz = lz / dxz;
+      m[0][0] = lzdxz;
+      m[0][1] = -lxdxz * ly;
+      m[0][2] = lx;
+      m[1][0] = 0;
+      m[1][1] = dxz;
+      m[1][2] = ly;
+      m[2][0] = -lxdxz;
+      m[2][1] = -lydxz * lz;
+      m[2][2] = lz;
+    } else {
+      m[0][0] = 1;
+      m[0][1] = 0;
+      m[0][2] = 0;
+      m[1][0] = 0;
+      m[1][1] = 0;
+      m[1][2] = (ly > 0) ? -1.0f : 1.0f;
+      m[2][0] = 0;
+      m[2][1] = (ly > 0) ? 1.0f : -1.0f;
+      m[2][2] = 0;
+    }
+    for (int k = 0; k < 3; k++) tr[k] = -(org_[0] * m[0][k] + org_[1] * m[1][k] + org_[2] * m[2][k]);
+  }
+  static void Bezier(const float c[4][3], float t, float out[3]) {  // de Casteljau
+    const float u = 1 - t;
+    for (int k = 0; k < 3; k++) {
+      const float a0 = c[0][k] * u + c[1][k] * t, a1 = c[1][k] * u + c[2][k] * t, a2 = c[2][k] * u + c[3][k] * t;
+      const float b0 = a0 * u + a1 * t, b1 = a1 * u + a2 * t;
+      out[k] = b0 * u + b1 * t;
+    }
+  }
+
+  const float *cps_;
+  const float *radii_;
+  const int num_subdivisions_;
+  mutable real3<float> org_, dir_;
+  mutable BVHTraceOptions opts_;
+  mutable float t_, u_, v_;
+  mutable unsigned int prim_id_;
+  mutable float u_param_, v_param_;
+};
+
+// ---------------------------------------------------------------------------
 // BVHAccel
 // ---------------------------------------------------------------------------
 namespace detail {
@@ -947,6 +1135,7 @@ struct generic_tag {};
 struct triangle_tag {};
 struct sphere_tag {};
 struct cylinder_tag {};
+struct curve_tag {};
 template <typename T, class Prim, class Pred>
 struct build_tag {
 #ifdef NANORT_USE_HIP_BACKEND
@@ -954,8 +1143,10 @@ struct build_tag {
       same_type<Prim, TriangleMesh<T> >::value && same_type<Pred, TriangleSAHPred<T> >::value, triangle_tag,
       typename std::conditional<
           same_type<T, float>::value && same_type<Prim, SphereGeometry>::value && same_type<Pred, SpherePred>::value, sphere_tag,
-          typename std::conditional<same_type<T, float>::value && same_type<Prim, CylinderGeometry>::value && same_type<Pred, CylinderPred>::value,
-                                    cylinder_tag, generic_tag>::type>::type>::type type;
+          typename std::conditional<
+              same_type<T, float>::value && same_type<Prim, CylinderGeometry>::value && same_type<Pred, CylinderPred>::value, cylinder_tag,
+              typename std::conditional<same_type<T, float>::value && same_type<Prim, BezierCurveGeometry>::value && same_type<Pred, BezierCurvePred>::value,
+                                        curve_tag, generic_tag>::type>::type>::type>::type type;
 #else
   typedef generic_tag type;
 #endif
@@ -1116,9 +1307,10 @@ class BVHAccel {
     typedef detail::HipApi<T> Api;
     if (!ctx_) return RefitHost(mesh);  // (a tree built on the host or Load()ed before any GPU Build())
     std::lock_guard<std::mutex> lock(batch_mutex_);
-    if (device_prim_kind_ == 1 || device_prim_kind_ == 2) {
+    if (device_prim_kind_ == 1 || device_prim_kind_ == 2 || device_prim_kind_ == 3) {
       backend_error_ = device_prim_kind_ == 1 ? "Refit: sphere trees do not refit on the GPU (Build() again)"
-                                              : "Refit: cylinder trees do not refit on the GPU (Build() again)";
+                                              : (device_prim_kind_ == 2 ? "Refit: cylinder trees do not refit on the GPU (Build() again)"
+                                                                        : "Refit: curve trees do not refit on the GPU (Build() again)");
       return false;
     }
     if (device_prim_kind_ != 0) {
@@ -1173,6 +1365,10 @@ class BVHAccel {
   }
   bool Refit(const CylinderGeometry &) {
     backend_error_ = "Refit: cylinder trees do not refit on the GPU (Build() again)";
+    return false;
+  }
+  bool Refit(const BezierCurveGeometry &) {
+    backend_error_ = "Refit: curve trees do not refit on the GPU (Build() again)";
     return false;
   }
 #endif
@@ -1639,6 +1835,57 @@ class BVHAccel {
     std::memcpy(&o, &options, sizeof(o));
     if (nrtTraverseBatchCylinders_f32(ctx_.get(), reinterpret_cast<const nrt_ray_f32 *>(rays), num_rays, &o,
                                       reinterpret_cast<nrt_cyl_hit_f32 *>(&tmp[0]), &mask[0]) != NRT_OK) {
+      backend_error_ = nrtLastError(ctx_.get());
+      return false;
+    }
+    for (size_t i = 0; i < num_rays; i++) {
+      if (mask[i]) isects[i] = tmp[i];
+      if (hit_out) hit_out[i] = mask[i];
+    }
+    return true;
+  }
+  // Same for a tree built over the built-in curve primitive (BezierCurveGeometry + BezierCurvePred); `num_subdivisions` is the
+  // BezierCurveIntersector constructor argument (1..64).
+  bool TraverseBatch(const Ray<T> *rays, size_t num_rays, BezierCurveIntersection *isects, unsigned char *hit_out = NULL,
+                     const BVHTraceOptions &options = BVHTraceOptions(), int num_subdivisions = 4) const {
+    static_assert(detail::same_type<T, float>::value, "the curve primitive is fp32");
+    static_assert(sizeof(BezierCurveIntersection) == sizeof(nrt_curve_hit_f32), "BezierCurveIntersection layout");
+    std::lock_guard<std::mutex> lock(batch_mutex_);
+    if (!ctx_ || !crv_cps_ || device_prim_kind_ != 3) {
+      backend_error_ = "TraverseBatch(BezierCurveIntersection*): Build() with BezierCurveGeometry/BezierCurvePred first";
+      return false;
+    }
+    if (num_subdivisions < 1 || num_subdivisions > 64) {
+      backend_error_ = "TraverseBatch(BezierCurveIntersection*): num_subdivisions outside 1..64";
+      return false;
+    }
+    if (num_subdivisions != crv_subdiv_ || device_tree_stale_) {  // the count lives with the primitives on the device
+      // (the host tree first: it may still be pending after Build(), and nrtSetCurves_f32 frees the device tree)
+      EnsureHostTree();
+      if (nodes_.empty()) {
+        backend_error_ = "TraverseBatch: empty tree";
+        return false;
+      }
+      crv_subdiv_ = num_subdivisions;
+      if (SharesDeviceContext()) {  // copy-on-write: the shared context stays with the copies
+        if (!DetachDeviceContext(cyl_test_cap_)) return false;  // (sends the curves with the new count)
+      } else if (nrtSetCurves_f32(ctx_.get(), crv_cps_, crv_radii_, prim_count_, static_cast<uint32_t>(num_subdivisions)) != NRT_OK) {
+        backend_error_ = nrtLastError(ctx_.get());
+        return false;
+      }
+      if (nrtSetTree_f32(ctx_.get(), reinterpret_cast<const nrt_node_f32 *>(&nodes_[0]), nodes_.size(), &indices_[0], indices_.size()) != NRT_OK) {
+        backend_error_ = nrtLastError(ctx_.get());
+        return false;
+      }
+      device_tree_stale_ = false;
+    }
+    if (num_rays == 0) return true;
+    std::vector<BezierCurveIntersection> tmp(num_rays);
+    std::vector<unsigned char> mask(num_rays);
+    nrt_trace_options o;
+    std::memcpy(&o, &options, sizeof(o));
+    if (nrtTraverseBatchCurves_f32(ctx_.get(), reinterpret_cast<const nrt_ray_f32 *>(rays), num_rays, &o,
+                                   reinterpret_cast<nrt_curve_hit_f32 *>(&tmp[0]), &mask[0]) != NRT_OK) {
       backend_error_ = nrtLastError(ctx_.get());
       return false;
     }
@@ -2201,6 +2448,17 @@ class BVHAccel {
     return HipBuild(n, options, 2, [&](nrt_ctx *c) { return nrtSetCylinders_f32(c, geom.GetEndpoints(), geom.GetRadii(), n, 1); });
   }
 
+  // (the intersector's num_subdivisions is a traversal-time property: TraverseBatch() re-sends the primitives if it differs)
+  bool BuildImpl(unsigned int n, const BezierCurveGeometry &geom, const BezierCurvePred &pred, const BVHBuildOptions<T> &options,
+                 detail::curve_tag) {
+    (void)pred;
+    crv_cps_ = geom.GetControlPoints();
+    crv_radii_ = geom.GetRadii();
+    crv_subdiv_ = 4;
+    prim_count_ = n;
+    return HipBuild(n, options, 3, [&](nrt_ctx *c) { return nrtSetCurves_f32(c, crv_cps_, crv_radii_, n, 4); });
+  }
+
   template <class SetPrims>
   bool HipBuild(unsigned int n, const BVHBuildOptions<T> &options, int prim_kind, SetPrims set_prims) {
     device_prim_kind_ = -1;
@@ -2328,6 +2586,7 @@ class BVHAccel {
       case 0: return detail::HipApi<T>::SetMesh(c, tri_vertices_, tri_stride_, tri_faces_, prim_count_);
       case 1: return nrtSetSpheres_f32(c, sph_centers_, sph_radii_, prim_count_);
       case 2: return nrtSetCylinders_f32(c, cyl_endpoints_, cyl_radii_, cyl_count_, cylinder_cap ? 1 : 0);
+      case 3: return nrtSetCurves_f32(c, crv_cps_, crv_radii_, prim_count_, static_cast<uint32_t>(crv_subdiv_));
       default: return NRT_ERR_INVALID;
     }
   }
@@ -2382,6 +2641,9 @@ class BVHAccel {
     tri_faces_ = o.tri_faces_;
     sph_centers_ = o.sph_centers_;
     sph_radii_ = o.sph_radii_;
+    crv_cps_ = o.crv_cps_;
+    crv_radii_ = o.crv_radii_;
+    crv_subdiv_ = o.crv_subdiv_;
     prim_count_ = o.prim_count_;
     host_tree_pending_ = false;
     pending_nodes_ = pending_indices_ = 0;
@@ -2428,7 +2690,11 @@ class BVHAccel {
     tri_faces_ = o->tri_faces_;
     sph_centers_ = o->sph_centers_;
     sph_radii_ = o->sph_radii_;
+    crv_cps_ = o->crv_cps_;
+    crv_radii_ = o->crv_radii_;
+    crv_subdiv_ = o->crv_subdiv_;
     prim_count_ = o->prim_count_;
+    o->crv_cps_ = o->crv_radii_ = NULL;
     o->cyl_endpoints_ = o->cyl_radii_ = NULL;
     o->tri_vertices_ = NULL;
     o->tri_faces_ = NULL;
@@ -2451,7 +2717,7 @@ class BVHAccel {
   mutable std::vector<int> devices_;                      // the devices of ctx_, then of peers_
   size_t batch_row_len_ = 0;                      // rays per interleaved row of a multi-device TraverseBatch (0: 4096)
   mutable bool device_tree_stale_ = false;
-  int device_prim_kind_ = -1;  // what the device context was built over: 0 triangles, 1 spheres, 2 cylinders, -1 nothing usable
+  int device_prim_kind_ = -1;  // what the device context was built over: 0 triangles, 1 spheres, 2 cylinders, 3 curves, -1 nothing usable
   const float *cyl_endpoints_ = NULL;  // cylinder primitive: what Build() was given
   const float *cyl_radii_ = NULL;
   unsigned int cyl_count_ = 0;
@@ -2461,6 +2727,9 @@ class BVHAccel {
   const unsigned int *tri_faces_ = NULL;
   const float *sph_centers_ = NULL;
   const float *sph_radii_ = NULL;
+  const float *crv_cps_ = NULL;  // curve primitive: what Build() was given, and the subdivision count the device context holds
+  const float *crv_radii_ = NULL;
+  mutable int crv_subdiv_ = 4;
   unsigned int prim_count_ = 0;
   mutable std::mutex batch_mutex_;  // one per object, never copied: see the comment above TraverseBatch
   // TraverseBatch staging (grow-only): pinned through nrtHostAlloc, plain malloc if that fails

@@ -287,6 +287,52 @@ NRT_API nrt_status nrtTraverseBatchCylindersDevice_f32(nrt_ctx *ctx, const nrt_r
                                                        const nrt_trace_options *options, nrt_cyl_hit_f32 *d_hits_out,
                                                        uint8_t *d_hit_mask_out, void *hip_stream);
 
+/* ---- curve primitives: replaces the CurvePred / CurveGeometry / CurveIntersector constructors of the reference's
+ * third custom-primitive example, hair and fur as cubic Bezier curves (examples/curves_primitive/main.cc:481-840) ----
+ * `control_points` holds four xyz points per curve (tight, 12 floats), `radii` four radii per curve, `num_subdivisions`
+ * (1..64; the example's default is 4) is the intersector's constructor argument.  fp32 only, as the example.  Contract:
+ *   1. Box (CurveGeometry::BoundingBoxAndCenter, :557-597): min / max over the four `point -/+ its radius`; SAH position
+ *      ((p0 + p1) + p2 + p3) / 4.  nrtBuild_f32 builds over these; nrtGetTree_f32 / nrtSetTree_f32 / nrtTreeSize /
+ *      nrtGetTreeBounds_f32 work as for every kind.
+ *   2. Intersect (:637-759), per (ray, curve, current t): prim_ids_range; the frame that puts the ray on the z axis
+ *      (GetZAlign :382-417, both branches); the four points in that frame; reject when the largest z (from 0) is below
+ *      4 * (max(r[0], r[3]) / 2); then for s < n the segment from the curve at s / n to the curve at (s + 1) / n (de
+ *      Casteljau, :432-454): u = the origin's foot on the 2-D segment clamped as max(0, min(1, u)) in std::min / std::max
+ *      operand order (a NaN u becomes 1), radius interpolated from 0.5 r[0] to 0.5 r[3], accepted when d2 <= r2 and
+ *      t < current; later segments see the lowered t.  No min_t test, no t >= 0 test.  Only radii 0 and 3 are read.
+ *      skip_prim_id and cull_back_face do not exist in that intersector and are ignored.
+ *   3. The current distance starts at ray.max_t (BVHAccel::Traverse, nanort.h:2494-2501), as for every kind.
+ *   4. Hit record: the example's CurveIntersection (:606-619), 40 bytes — {t, prim_id, u, v, tangent[3], normal[3]} with
+ *      u = (u_segment + s) / n, v = sqrt(d2), tangent = vnormalize(EvaluateBezierTangent(points, u)) and normal =
+ *      vnormalize(cross(cross(dir, tangent), tangent)) (PostTraversal :789-823; vnormalize, nanort.h:388-398, leaves a
+ *      vector no longer than epsilon as it is).  A miss leaves {ray.max_t, 0xFFFFFFFF, 0, 0, (0,0,0), (0,0,0)}: every
+ *      byte of every record is written.
+ *   5. Parity: the reference's Traverse with that intersector over the same node and index arrays gives the same bits.
+ * nrtSetCurvesDevice_f32 takes the two arrays from HBM under the contract of nrtSetSpheresDevice_f32 below (4-byte
+ * alignment, copied on `hip_stream`, the caller may free them on return, a following build is byte-identical to the host
+ * form's).  Refusals leave the context untouched: NRT_ERR_INVALID for a NULL context, num_subdivisions outside 1..64, a
+ * NULL or (Device) misaligned pointer with num_curves > 0; NRT_ERR_PRECISION on a context that holds fp64 primitives.
+ * A curve context is traced by nrtTraverseBatchCurves*_f32 only: every other traversal, occlusion, multi-hit, counting,
+ * refit, scene and multi-context entry point refuses it with an error string (and these two refuse every other kind). */
+typedef struct nrt_curve_hit_f32 {
+  float t;
+  uint32_t prim_id;
+  float u, v;
+  float tangent[3];
+  float normal[3];
+} nrt_curve_hit_f32;
+NRT_API nrt_status nrtSetCurves_f32(nrt_ctx *ctx, const float *control_points, const float *radii, uint32_t num_curves,
+                                    uint32_t num_subdivisions);
+NRT_API nrt_status nrtSetCurvesDevice_f32(nrt_ctx *ctx, const float *d_control_points, const float *d_radii, uint32_t num_curves,
+                                          uint32_t num_subdivisions, void *hip_stream);
+NRT_API nrt_status nrtTraverseBatchCurves_f32(nrt_ctx *ctx, const nrt_ray_f32 *rays, uint64_t num_rays,
+                                              const nrt_trace_options *options, nrt_curve_hit_f32 *hits_out,
+                                              uint8_t *hit_mask_out);
+/* Same with HBM-resident buffers, asynchronous on `hip_stream` (a hipStream_t). */
+NRT_API nrt_status nrtTraverseBatchCurvesDevice_f32(nrt_ctx *ctx, const nrt_ray_f32 *d_rays, uint64_t num_rays,
+                                                    const nrt_trace_options *options, nrt_curve_hit_f32 *d_hits_out,
+                                                    uint8_t *d_hit_mask_out, void *hip_stream);
+
 /* ---- build: replaces BVHAccel<T>::Build (nanort.h:716-718, 1892-2149) ----
  * Binned-SAH construction on the GPU over the mesh set above.  Honours
  * min_leaf_primitives and max_tree_depth (the reference's leaf rule,

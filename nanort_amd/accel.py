@@ -85,9 +85,22 @@ class CylinderGeometry:
         self.num_faces = int(self.radii.shape[0])
 
 
+class CurveGeometry:
+    """The cubic Bezier curve primitive of the reference (examples/curves_primitive/main.cc:481-840: CurvePred + CurveGeometry +
+    CurveIntersector): four control points (n, 4, 3) and four radii (n, 4) per curve, and the intersector's num_subdivisions."""
+
+    def __init__(self, control_points, radii, num_subdivisions=4):
+        self.control_points = np.ascontiguousarray(control_points, dtype=np.float32).reshape(-1, 4, 3)
+        self.radii = np.ascontiguousarray(radii, dtype=np.float32).reshape(-1, 4)
+        if self.control_points.shape[0] != self.radii.shape[0]:
+            raise ValueError("four radii per curve")
+        self.num_subdivisions = int(num_subdivisions)
+        self.num_faces = int(self.radii.shape[0])
+
+
 class DeviceGeometry:
-    """What the accel remembers of primitives set from device tensors (SetMeshDevice / SetSpheresDevice): nothing of the
-    tensors themselves — the context owns its copy.  `kind` is "triangles" or "spheres"; `num_verts` is the context's vertex
+    """What the accel remembers of primitives set from device tensors (SetMeshDevice / SetSpheresDevice / SetCurvesDevice): nothing
+    of the tensors themselves — the context owns its copy.  `kind` is "triangles", "spheres" or "curves"; `num_verts` is the context's vertex
     count (max(faces) + 1 for triangles), what Refit / RefitDevice check their rows against."""
 
     def __init__(self, kind, num_faces, num_verts):
@@ -97,7 +110,7 @@ class DeviceGeometry:
 
 
 class BVHAccel:
-    """nanort::BVHAccel<T> on one MI355X (built-in triangle geometry, or the sphere / cylinder primitives in fp32)."""
+    """nanort::BVHAccel<T> on one MI355X (built-in triangle geometry, or the sphere / cylinder / curve primitives in fp32)."""
 
     def __init__(self, real=np.float32, device=0):
         self.real = np.dtype(real)
@@ -131,6 +144,12 @@ class BVHAccel:
 
     # -- mesh / build -------------------------------------------------------
     def SetMesh(self, mesh):
+        if isinstance(mesh, CurveGeometry):
+            if self.real != np.float32:
+                raise TypeError("curve primitives are fp32 (as the reference example)")
+            self._check(self._L.nrtSetCurves_f32(self._h, _p(mesh.control_points), _p(mesh.radii), mesh.num_faces, mesh.num_subdivisions))
+            self._mesh = mesh
+            return
         if isinstance(mesh, CylinderGeometry):
             if self.real != np.float32:
                 raise TypeError("cylinder primitives are fp32 (as the reference example)")
@@ -155,7 +174,9 @@ class BVHAccel:
     def Build(self, num_primitives, mesh, options=None):
         """BVHAccel::Build (reference nanort.h:1892-2149). Returns False iff n == 0."""
         if num_primitives != mesh.num_faces:
-            if isinstance(mesh, CylinderGeometry):
+            if isinstance(mesh, CurveGeometry):
+                mesh = CurveGeometry(mesh.control_points[:num_primitives], mesh.radii[:num_primitives], mesh.num_subdivisions)
+            elif isinstance(mesh, CylinderGeometry):
                 mesh = CylinderGeometry(mesh.endpoints[:num_primitives], mesh.radii[:num_primitives], mesh.test_cap)
             elif isinstance(mesh, SphereGeometry):
                 mesh = SphereGeometry(mesh.centers[:num_primitives], mesh.radii[:num_primitives])
@@ -229,8 +250,33 @@ class BVHAccel:
             self._h, d_centers.data_ptr() if n else None, d_radii.data_ptr() if n else None, n, self._stream_handle(stream)))
         self._mesh = DeviceGeometry("spheres", n, n)
 
+    def SetCurvesDevice(self, d_control_points, d_radii, num_subdivisions=4, stream=None):
+        """SetMesh(CurveGeometry) from torch float32 tensors on the accel's device (nrtSetCurvesDevice): `d_control_points`
+        [n, 4, 3] and `d_radii` [n, 4], both contiguous.  Ordering as SetMeshDevice."""
+        import torch
+
+        if self.real != np.float32:
+            raise TypeError("curve primitives are fp32 (as the reference example)")
+        if d_control_points.dtype != torch.float32 or d_radii.dtype != torch.float32:
+            raise TypeError("control points and radii must be torch.float32")
+        if d_control_points.dim() != 3 or tuple(d_control_points.shape[1:]) != (4, 3) or not d_control_points.is_contiguous():
+            raise ValueError("control points must be [n, 4, 3], contiguous")
+        if d_radii.dim() != 2 or d_radii.shape[1] != 4 or d_radii.shape[0] != d_control_points.shape[0] or not d_radii.is_contiguous():
+            raise ValueError("four radii per curve, contiguous")
+        self._on_device(d_control_points, "control points")
+        self._on_device(d_radii, "radii")
+        n = int(d_radii.shape[0])
+        self._check(self._L.nrtSetCurvesDevice_f32(
+            self._h, d_control_points.data_ptr() if n else None, d_radii.data_ptr() if n else None, n, int(num_subdivisions),
+            self._stream_handle(stream)))
+        self._mesh = DeviceGeometry("curves", n, 4 * n)
+
+    def _is_curves(self):
+        m = self._mesh
+        return isinstance(m, CurveGeometry) or (isinstance(m, DeviceGeometry) and m.kind == "curves")
+
     def BuildCurrent(self, options=None):
-        """nrtBuild over the primitives last set (SetMesh, SetMeshDevice or SetSpheresDevice).  Returns False iff there are none."""
+        """nrtBuild over the primitives last set (SetMesh, SetMeshDevice, SetSpheresDevice or SetCurvesDevice).  Returns False iff there are none."""
         if options is not None:
             want = BUILD_OPTIONS_F32 if self.real == np.float32 else BUILD_OPTIONS_F64
             options = np.asarray(options, dtype=want).reshape(1)
@@ -376,6 +422,12 @@ class BVHAccel:
         mask = np.zeros((n,), dtype=np.uint8)
         if options is not None:
             options = np.asarray(options, dtype=TRACE_OPTIONS).reshape(1)
+        if self._is_curves():  # the example's 40-byte CurveIntersection records
+            from .wire import CURVE_HIT_F32
+
+            hits = np.zeros((n,), dtype=CURVE_HIT_F32)
+            self._check(self._L.nrtTraverseBatchCurves_f32(self._h, _p(rays), n, _p(options), _p(hits), _p(mask)))
+            return hits, mask
         if isinstance(self._mesh, CylinderGeometry):  # the example's 28-byte CylinderIntersection records
             from .wire import CYL_HIT_F32
 
@@ -393,14 +445,18 @@ class BVHAccel:
         (default: torch's current stream)."""
         import torch
 
-        cyl = isinstance(self._mesh, CylinderGeometry)
-        rsz, hsz = ray_dtype(self.real).itemsize, (28 if cyl else hit_dtype(self.real).itemsize)
+        cyl, curves = isinstance(self._mesh, CylinderGeometry), self._is_curves()
+        rsz, hsz = ray_dtype(self.real).itemsize, (28 if cyl else (40 if curves else hit_dtype(self.real).itemsize))
         n = d_rays.numel() * d_rays.element_size() // rsz
         assert d_hits.numel() * d_hits.element_size() >= n * hsz
         if stream is None:
             stream = torch.cuda.current_stream(self.device).cuda_stream
         if options is not None:
             options = np.asarray(options, dtype=TRACE_OPTIONS).reshape(1)
+        if curves:
+            self._check(self._L.nrtTraverseBatchCurvesDevice_f32(
+                self._h, d_rays.data_ptr(), n, _p(options), d_hits.data_ptr(), None if d_mask is None else d_mask.data_ptr(), stream))
+            return n
         if cyl:
             self._check(self._L.nrtTraverseBatchCylindersDevice_f32(
                 self._h, d_rays.data_ptr(), n, _p(options), d_hits.data_ptr(), None if d_mask is None else d_mask.data_ptr(), stream))

@@ -19,6 +19,7 @@ SYMBOLS = [
     "nrtCreate", "nrtDestroy", "nrtLastError", "nrtVersion",
     "nrtSetMesh_f32", "nrtSetMesh_f64", "nrtSetSpheres_f32",
     "nrtSetCylinders_f32", "nrtTraverseBatchCylinders_f32", "nrtTraverseBatchCylindersDevice_f32",
+    "nrtSetCurves_f32", "nrtSetCurvesDevice_f32", "nrtTraverseBatchCurves_f32", "nrtTraverseBatchCurvesDevice_f32",
     "nrtBuild_f32", "nrtBuild_f64",
     "nrtGetTree_f32", "nrtGetTree_f64", "nrtTreeSize", "nrtGetTreeBounds_f32", "nrtGetTreeBounds_f64",
     "nrtSetTree_f32", "nrtSetTree_f64",
@@ -148,6 +149,14 @@ def lib():
     L.nrtTraverseBatchCylinders_f32.restype = i32
     L.nrtTraverseBatchCylindersDevice_f32.argtypes = [vp, vp, u64, vp, vp, vp, vp]
     L.nrtTraverseBatchCylindersDevice_f32.restype = i32
+    L.nrtSetCurves_f32.argtypes = [vp, vp, vp, u32, u32]
+    L.nrtSetCurves_f32.restype = i32
+    L.nrtSetCurvesDevice_f32.argtypes = [vp, vp, vp, u32, u32, vp]
+    L.nrtSetCurvesDevice_f32.restype = i32
+    L.nrtTraverseBatchCurves_f32.argtypes = [vp, vp, u64, vp, vp, vp]
+    L.nrtTraverseBatchCurves_f32.restype = i32
+    L.nrtTraverseBatchCurvesDevice_f32.argtypes = [vp, vp, u64, vp, vp, vp, vp]
+    L.nrtTraverseBatchCurvesDevice_f32.restype = i32
     L.nrtSceneCreate.argtypes = [i32, ctypes.POINTER(vp)]
     L.nrtSceneCreate.restype = i32
     L.nrtSceneDestroy.argtypes = [vp]

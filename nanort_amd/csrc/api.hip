@@ -39,8 +39,9 @@ struct nrt_ctx {
   int num_cus = 256;
 
   // mesh (tight xyz in HBM)
-  int prim_kind = kPrimTriangles; // kPrimSpheres: d_verts = centres, d_radii = radii, no faces; kPrimCylinders: d_verts = 2 end points, d_radii = 2 radii per primitive
+  int prim_kind = kPrimTriangles; // kPrimSpheres: d_verts = centres, d_radii = radii, no faces; kPrimCylinders: d_verts = 2 end points, d_radii = 2 radii per primitive; kPrimCurves: d_verts = 4 control points, d_radii = 4 radii per primitive
   uint32_t cyl_test_cap = 1;
+  uint32_t curve_subdiv = 4; // curves: line segments per curve (the intersector's num_subdivisions; nrtSetCurves)
   // cylinders cut into segments for the builder (build.hip k_cylinder_segments): what the tree is built over when num_segs != 0
   DevBuf b_seg_verts, b_seg_radii, b_seg_prim, b_seg_off;
   uint32_t num_segs = 0;
@@ -86,7 +87,7 @@ struct nrt_ctx {
     uint32_t *d_cursor = nullptr; // two sets of ray cursors (one per partition, 4 KiB apart): a launch uses one and zeroes the other
     unsigned parity = 0;
     DevBuf spill, spill_tmin;
-    DevBuf cyl_hits, cyl_bits;    // cylinder kind: compact records + {hit, cap} bits between the traversal and its post pass
+    DevBuf cyl_hits, cyl_bits;    // cylinder / curve kinds: compact records + {hit, cap} bits between the traversal and its post pass
     hipEvent_t done = nullptr;    // recorded after the slot's last launch (launches that do not publish a completion record)
     hipEvent_t t0 = nullptr, t1 = nullptr; // event timing of the slot's last launch (per slot: launches on different streams overlap)
     hipStream_t stream = nullptr; // stream of that launch
@@ -146,7 +147,7 @@ struct nrt_ctx {
   int dyn_head = 1; // batches too small for a static group per wave: every wave's first chunk is its own (traverse.hip claim_init; tunable dyn_head)
   int wide_scramble = 0; // probe (tunable wide_scramble): the private node records in a pseudo-random order instead of pre-order
   // resident blocks per CU of the variants launched so far, by what selects the kernel: [walk][primitive kind] at `lds_entries` (a context keeps one precision; size_grid)
-  struct { int lds_entries; unsigned blocks_per_cu; } occupancy[4][3] = {};
+  struct { int lds_entries; unsigned blocks_per_cu; } occupancy[4][kNumPrimKinds] = {};
 
   hipEvent_t ev_b0 = nullptr, ev_b1 = nullptr;
   hipEvent_t ev_build_state = nullptr; // the builder's state block has reached build_state
@@ -703,6 +704,46 @@ static nrt_status set_cylinders(nrt_ctx *c, const float *endpoints, const float 
   return NRT_OK;
 }
 
+// Curve primitives (CurveGeometry of examples/curves_primitive/main.cc:513-604): four control points and four radii each, in
+// host memory or (`device`: copied on `s`, the rules of set_spheres_device) in HBM.  Every refusal comes before anything changes.
+static nrt_status set_curves(nrt_ctx *c, const float *cps, const float *radii, uint32_t n, uint32_t subdiv, bool device, hipStream_t s) {
+  const char *fn = device ? "nrtSetCurvesDevice" : "nrtSetCurves";
+  if (!c) return NRT_ERR_INVALID;
+  if (c->prec != 0 && c->prec != 4) return fail(c, NRT_ERR_PRECISION, "%s: context already holds f64 primitives", fn);
+  if (subdiv < 1u || subdiv > 64u) return fail(c, NRT_ERR_INVALID, "%s: num_subdivisions %u outside 1..64", fn, subdiv);
+  if (n && (!cps || !radii)) return fail(c, NRT_ERR_INVALID, "%s: NULL pointer", fn);
+  if (n >= (1u << 28)) return fail(c, NRT_ERR_INVALID, "%s: too many curves", fn);
+  if (device && n && ((uintptr_t)cps % sizeof(float) != 0 || (uintptr_t)radii % sizeof(float) != 0))
+    return fail(c, NRT_ERR_INVALID, "%s: pointer not aligned to 4 bytes", fn);
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, wait_for_launches(c));
+  free_tree(c);
+  free_mesh(c);
+  c->prec = 4;
+  c->prim_kind = kPrimCurves;
+  c->curve_subdiv = subdiv;
+  if (n == 0) return NRT_OK;
+  const size_t cp_bytes = 12 * (size_t)n * sizeof(float), rad_bytes = 4 * (size_t)n * sizeof(float);
+  if (device) {
+    hipError_t e;
+    if ((e = devbuf_ensure(&c->b_verts, cp_bytes)) != hipSuccess || (e = devbuf_ensure(&c->b_radii, rad_bytes)) != hipSuccess ||
+        (e = hipMemcpyAsync(c->b_verts.p, cps, cp_bytes, hipMemcpyDeviceToDevice, s)) != hipSuccess ||
+        (e = hipMemcpyAsync(c->b_radii.p, radii, rad_bytes, hipMemcpyDeviceToDevice, s)) != hipSuccess ||
+        (e = hipStreamSynchronize(s)) != hipSuccess) // (the context owns its copy: the caller's buffers are free again)
+      return set_device_failed(c, fn, s, e);
+  } else {
+    nrt_status st;
+    if ((st = ensure(c, c->b_verts, cp_bytes)) || (st = ensure(c, c->b_radii, rad_bytes))) return st;
+    HIPCHK(c, hipMemcpy(c->b_verts.p, cps, cp_bytes, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->b_radii.p, radii, rad_bytes, hipMemcpyHostToDevice));
+  }
+  c->d_verts = c->b_verts.p;
+  c->d_radii = c->b_radii.p;
+  c->num_faces = n;
+  c->num_verts = 4 * n;
+  return NRT_OK;
+}
+
 // ---------------------------------------------------------------------------
 // tree adoption / retrieval
 // ---------------------------------------------------------------------------
@@ -722,6 +763,11 @@ static nrt_status finish_leaf_records(nrt_ctx *c, hipStream_t s) {
     c->d_tris = c->b_tris.p;
     HIPCHK(c, launch_gather_leaf_cylinders<T>(c->d_indices, (const T *)c->d_verts, (const T *)c->d_radii,
                                               (LeafCylinder<T> *)c->d_tris, (uint32_t)c->num_indices, s));
+  } else if (c->prim_kind == kPrimCurves) { // (fp32 contexts only: nrtSetCurves)
+    if ((st = ensure(c, c->b_tris, std::max<size_t>(1, c->num_indices) * sizeof(LeafCurve)))) return st;
+    c->d_tris = c->b_tris.p;
+    HIPCHK(c, launch_gather_leaf_curves(c->d_indices, (const float *)c->d_verts, (const float *)c->d_radii, (LeafCurve *)c->d_tris,
+                                        (uint32_t)c->num_indices, s));
   } else {
     if ((st = ensure(c, c->b_tris, std::max<size_t>(1, c->num_indices) * sizeof(LeafTri<T>)))) return st;
     c->d_tris = c->b_tris.p;
@@ -889,7 +935,7 @@ static nrt_status build(nrt_ctx *c, const typename Wire<T>::BuildOptions *opt, n
   const bool segs = c->prim_kind == kPrimCylinders && c->num_segs != 0 && sizeof(T) == 4;
   const uint32_t build_n = segs ? c->num_segs : c->num_faces;
   hipError_t e = gpu_build<T>(c->stream, segs ? (const T *)c->b_seg_verts.p : (const T *)c->d_verts, c->d_faces, segs ? (const T *)c->b_seg_radii.p : (const T *)c->d_radii,
-                              c->prim_kind == kPrimCylinders, segs ? (const uint32_t *)c->b_seg_prim.p : nullptr, build_n, min_leaf, max_depth,
+                              c->prim_kind, segs ? (const uint32_t *)c->b_seg_prim.p : nullptr, build_n, min_leaf, max_depth,
                               bin_size, (c->morton ? kBuildMorton : 0u) | (c->subtree_rows ? 0u : kBuildSubtreeDfs), &c->b_build_ws, &c->b_nodes, &c->b_indices, c->build_state, c->ev_build_state, &err);
   if (e != hipSuccess) return fail(c, NRT_ERR_DEVICE, "nrtBuild: %s (%s)", err.c_str(), hipGetErrorString(e));
   // everything is enqueued; the leaf-ordered primitive records need the index array only, so they are enqueued too before
@@ -949,7 +995,7 @@ static nrt_status refit(nrt_ctx *c, const T *vertices, size_t stride, bool devic
   if (c->prec != 0 && c->prec != (int)sizeof(T))
     return fail(c, NRT_ERR_PRECISION, "%s: the context holds %s primitives", fn, c->prec == 8 ? "f64" : "f32");
   if (c->prim_kind != kPrimTriangles) return fail(c, NRT_ERR_INVALID, "%s: only triangle meshes refit (this context holds %s)", fn,
-                                                  c->prim_kind == kPrimSpheres ? "spheres" : "cylinders");
+                                                  c->prim_kind == kPrimSpheres ? "spheres" : (c->prim_kind == kPrimCylinders ? "cylinders" : "curves"));
   if (!c->d_nodes) return fail(c, NRT_ERR_INVALID, "%s: no tree (call nrtBuild or nrtSetTree)", fn);
   if (stride < 3 * sizeof(T)) return fail(c, NRT_ERR_INVALID, "%s: vertex stride %zu < %zu", fn, stride, 3 * sizeof(T));
   if (device && (stride % sizeof(T) != 0 || (uintptr_t)vertices % sizeof(T) != 0))
@@ -1023,6 +1069,7 @@ nrt_status nrt_internal_tree_view(nrt_ctx *c, nrt::TreeViewF32 *out) {
 }
 uint64_t nrt_internal_generation(const nrt_ctx *c) { return c ? c->generation : 0; }
 int nrt_internal_device(const nrt_ctx *c) { return c ? c->device : 0; } // group.hip
+int nrt_internal_prim_kind(const nrt_ctx *c) { return c ? c->prim_kind : (int)kPrimTriangles; } // scene.hip
 
 // ---------------------------------------------------------------------------
 // traverse
@@ -1042,7 +1089,7 @@ struct TraverseBatches {
 
 // What one traversal launch is asked for: the query kind says which of the outputs it reads.  (Occlusion: every ray stops at the
 // first primitive it accepts; Count: the literal kernel's counting pass into d_counters, no output of its own.)
-enum class Query { Closest, Occlusion, Count, MultiHit, Cylinders, MultiBatch };
+enum class Query { Closest, Occlusion, Count, MultiHit, Cylinders, MultiBatch, Curves };
 template <typename T>
 struct TraverseLaunch {
   Query kind;
@@ -1052,8 +1099,8 @@ struct TraverseLaunch {
   hipStream_t stream;
   bool timed = false; // bracket the launch with the slot's timing events (when it publishes no completion record)
   typename Wire<T>::Hit *hits = nullptr; // Closest (null: flags only); MultiHit: max_hits records per ray
-  uint8_t *mask = nullptr;               // Closest (may be null), Occlusion, Cylinders
-  void *cyl_hits = nullptr;              // Cylinders: 28-byte records, written by the post pass
+  uint8_t *mask = nullptr;               // Closest (may be null), Occlusion, Cylinders, Curves
+  void *cyl_hits = nullptr;              // Cylinders: 28-byte records, Curves: 40-byte records, written by the post pass
   uint32_t max_hits = 0;
   uint32_t *hit_counts = nullptr;        // MultiHit (may be null): one word per ray
   const TraverseBatches<T> *batches = nullptr; // MultiBatch: rays and outputs per batch, n = all their rays (the context takes one launch: the caller checked)
@@ -1067,6 +1114,9 @@ static nrt_status validate_launch(nrt_ctx *c, const TraverseLaunch<T> &l) {
   if ((c->prim_kind == kPrimCylinders) != (l.kind == Query::Cylinders))
     return fail(c, NRT_ERR_INVALID, "cylinder primitives are traced with nrtTraverseBatchCylinders*_f32 (28-byte records), "
                                     "every other primitive kind with nrtTraverseBatch*");
+  if ((c->prim_kind == kPrimCurves) != (l.kind == Query::Curves))
+    return fail(c, NRT_ERR_INVALID, "curve primitives are traced with nrtTraverseBatchCurves*_f32 (40-byte records) and by nothing else, "
+                                    "every other primitive kind by its own entry points");
   if (!c->d_nodes) return fail(c, NRT_ERR_INVALID, "nrtTraverseBatch: no tree (call nrtBuild or nrtSetTree)");
   if (l.n == 0) return NRT_OK;
   if (!l.rays) return fail(c, NRT_ERR_INVALID, "nrtTraverseBatch: NULL rays");
@@ -1158,6 +1208,8 @@ static void fill_walk_args(const nrt_ctx *c, const TraverseLaunch<T> &l, const W
   a.centers = (const T *)c->d_verts;
   a.cylinders = (const LeafCylinder<T> *)c->d_tris;
   a.cyl_test_cap = c->cyl_test_cap;
+  a.curves = (const LeafCurve *)c->d_tris;
+  a.curve_subdiv = c->curve_subdiv;
   a.wide = (const WideNode<T> *)c->d_wide;
   a.wide4 = w.wide4() ? (const Wide4Node<T> *)c->d_wide4 : nullptr;
   a.packed_leaves = c->packed_leaves;
@@ -1208,7 +1260,7 @@ static void fill_launch_args(const TraverseLaunch<T> &l, const nrt_ctx::LaunchSl
   a.rays = l.rays;
   a.hits = l.hits;
   a.mask = l.mask;
-  if (l.kind == Query::Cylinders) {
+  if (l.kind == Query::Cylinders || l.kind == Query::Curves) {
     a.hits = (typename Wire<T>::Hit *)slot->cyl_hits.p;
     a.mask = (uint8_t *)slot->cyl_bits.p;
   }
@@ -1244,7 +1296,7 @@ static nrt_status enqueue_launch(nrt_ctx *c, const TraverseLaunch<T> &l, const W
   // completion record instead of events: the traversal kernel is the launch's last kernel and events were not asked for
   const bool use_rec = w.wide() && !count && !c->launch_timing;
   // (the sphere kind's u/v pass and the cylinder kind's normal pass run behind the traversal kernel and close the record in its place)
-  const bool post_pass = (c->prim_kind == kPrimSpheres && l.hits != nullptr) || l.kind == Query::Cylinders;
+  const bool post_pass = (c->prim_kind == kPrimSpheres && l.hits != nullptr) || l.kind == Query::Cylinders || l.kind == Query::Curves;
   a.done_rec = use_rec ? slot->d_done : nullptr;
   a.done_count = slot->d_count;
   a.done_seq = use_rec ? slot->seq + 1u : 0u;
@@ -1275,6 +1327,9 @@ static nrt_status enqueue_launch(nrt_ctx *c, const TraverseLaunch<T> &l, const W
   if (l.kind == Query::Cylinders)
     HIPCHK(c, launch_cylinder_post((const nrt_ray_f32 *)l.rays, (const nrt_hit_f32 *)slot->cyl_hits.p, (const uint8_t *)slot->cyl_bits.p,
                                    (const float *)c->d_verts, (uint32_t)l.n, l.cyl_hits, l.mask, a.done_rec, a.done_count, a.done_seq, s));
+  if (l.kind == Query::Curves)
+    HIPCHK(c, launch_curve_post((const nrt_ray_f32 *)l.rays, (const nrt_hit_f32 *)slot->cyl_hits.p, (const uint8_t *)slot->cyl_bits.p,
+                                (const float *)c->d_verts, (uint32_t)l.n, l.cyl_hits, l.mask, a.done_rec, a.done_count, a.done_seq, s));
   if (timed) {
     HIPCHK(c, hipEventRecord(slot->t1, s));
     slot->last_timed = true;
@@ -1304,7 +1359,7 @@ static nrt_status traverse_device(nrt_ctx *c, TraverseLaunch<T> l) {
     if ((st = ensure(c, slot->spill, (size_t)levels * total_threads * sizeof(uint32_t)))) return st;
     if (w.wide() && (st = ensure(c, slot->spill_tmin, (size_t)levels * total_threads * sizeof(T)))) return st;
   }
-  if (l.kind == Query::Cylinders) { // compact records + {hit, cap} bits, expanded by the post pass
+  if (l.kind == Query::Cylinders || l.kind == Query::Curves) { // compact records + {hit, cap} bits, expanded by the post pass
     if ((st = ensure(c, slot->cyl_hits, (size_t)l.n * sizeof(typename Wire<T>::Hit)))) return st;
     if ((st = ensure(c, slot->cyl_bits, (size_t)l.n))) return st;
   }
@@ -1732,6 +1787,34 @@ nrt_status nrtTraverseBatchCylinders_f32(nrt_ctx *c, const nrt_ray_f32 *rays, ui
   HIPCHK(c, hipSetDevice(c->device));
   return staged_host_loop<float>(c, rays, n, kStagedRays, sizeof(nrt_cyl_hit_f32), 1, hits, mask, [&](uint64_t m) -> TraverseLaunch<float> {
     return {.kind = Query::Cylinders, .rays = (const nrt_ray_f32 *)c->st_rays.p, .n = m, .opt = opt, .stream = c->stream, .timed = true,
+            .mask = (uint8_t *)c->st_mask.p, .cyl_hits = c->st_hits.p};
+  });
+}
+
+nrt_status nrtSetCurves_f32(nrt_ctx *c, const float *cps, const float *radii, uint32_t n, uint32_t subdiv) {
+  return set_curves(c, cps, radii, n, subdiv, false, nullptr);
+}
+nrt_status nrtSetCurvesDevice_f32(nrt_ctx *c, const float *cps, const float *radii, uint32_t n, uint32_t subdiv, void *s) {
+  return set_curves(c, cps, radii, n, subdiv, true, (hipStream_t)s);
+}
+
+nrt_status nrtTraverseBatchCurvesDevice_f32(nrt_ctx *c, const nrt_ray_f32 *r, uint64_t n, const nrt_trace_options *o, nrt_curve_hit_f32 *h,
+                                            uint8_t *m, void *s) {
+  if (!c) return NRT_ERR_INVALID;
+  if (n && !h) return fail(c, NRT_ERR_INVALID, "nrtTraverseBatchCurvesDevice: NULL hits");
+  return traverse_device<float>(c, {.kind = Query::Curves, .rays = r, .n = n, .opt = o, .stream = (hipStream_t)s, .timed = true, .mask = m,
+                                    .cyl_hits = h});
+}
+
+nrt_status nrtTraverseBatchCurves_f32(nrt_ctx *c, const nrt_ray_f32 *rays, uint64_t n, const nrt_trace_options *opt, nrt_curve_hit_f32 *hits,
+                                      uint8_t *mask) {
+  if (!c) return NRT_ERR_INVALID;
+  if (n == 0) return NRT_OK;
+  if (!rays || !hits) return fail(c, NRT_ERR_INVALID, "nrtTraverseBatchCurves: NULL rays/hits");
+  std::lock_guard<std::mutex> host_lock(c->host_mutex);
+  HIPCHK(c, hipSetDevice(c->device));
+  return staged_host_loop<float>(c, rays, n, kStagedRays, sizeof(nrt_curve_hit_f32), 1, hits, mask, [&](uint64_t m) -> TraverseLaunch<float> {
+    return {.kind = Query::Curves, .rays = (const nrt_ray_f32 *)c->st_rays.p, .n = m, .opt = opt, .stream = c->stream, .timed = true,
             .mask = (uint8_t *)c->st_mask.p, .cyl_hits = c->st_hits.p};
   });
 }

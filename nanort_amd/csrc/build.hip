@@ -355,7 +355,7 @@ struct __attribute__((packed, aligned(4))) Vec3Of { // three consecutive element
 template <typename T>
 __global__ __launch_bounds__(256) void k_prim_records(const T *__restrict__ verts,
                                                       const uint32_t *__restrict__ faces,
-                                                      const T *__restrict__ radii, bool cylinders, uint32_t n,
+                                                      const T *__restrict__ radii, int kind, uint32_t n,
                                                       const uint32_t *__restrict__ prim_map,
                                                       PrimRec<T> *__restrict__ recs,
                                                       BoundsAcc<T> *__restrict__ scene) {
@@ -389,17 +389,28 @@ __global__ __launch_bounds__(256) void k_prim_records(const T *__restrict__ vert
         r.bmin[k] = tmin(p0, tmin(p1, p2)); // nanort.h:967-968
         r.bmax[k] = tmax(p0, tmax(p1, p2));
         r.c[k] = ((p0 + p1) + p2) * third; // nanort.h:970
-      } else if (!cylinders) { // spheres: SphereGeometry::BoundingBoxAndCenter (examples/particle_primitive/main.cc:124-136)
+      } else if (kind == kPrimSpheres) { // spheres: SphereGeometry::BoundingBoxAndCenter (examples/particle_primitive/main.cc:124-136)
         const T c = verts[3 * (size_t)i + k], rad = radii[i];
         r.bmin[k] = c - rad;
         r.bmax[k] = c + rad;
         r.c[k] = c;
-      } else { // cylinders: CylinderGeometry::BoundingBoxAndCenter (examples/cylinder_primitive/main.cc:166-205)
+      } else if (kind == kPrimCylinders) { // cylinders: CylinderGeometry::BoundingBoxAndCenter (examples/cylinder_primitive/main.cc:166-205)
         const T a0 = verts[3 * (size_t)(2 * i) + k], a1 = verts[3 * (size_t)(2 * i + 1) + k];
         const T r0 = radii[2 * (size_t)i], r1 = radii[2 * (size_t)i + 1];
         r.bmin[k] = tmin(a1 - r1, a0 - r0); // std::min(second, first): identical unless NaN
         r.bmax[k] = tmax(a1 + r1, a0 + r0);
         r.c[k] = (a0 + a1) / T(2.0);
+      } else { // curves: CurveGeometry::BoundingBoxAndCenter (examples/curves_primitive/main.cc:557-597): control point -+ its radius
+        const T *cp = verts + 12 * (size_t)i + k, *rad = radii + 4 * (size_t)i;
+        T lo_ = cp[0] - rad[0], hi_ = cp[0] + rad[0];
+#pragma unroll
+        for (int j = 1; j < 4; j++) {
+          lo_ = tmin(cp[3 * j] - rad[j], lo_); // std::min(new, running) / std::max(new, running), operands in the example's order
+          hi_ = tmax(cp[3 * j] + rad[j], hi_);
+        }
+        r.bmin[k] = lo_;
+        r.bmax[k] = hi_;
+        r.c[k] = (((cp[0] + cp[3]) + cp[6]) + cp[9]) / T(4.0);
       }
       lo[k] = tmin(lo[k], r.bmin[k]);
       hi[k] = tmax(hi[k], r.bmax[k]);
@@ -2746,7 +2757,7 @@ hipError_t launch_cylinder_segments(const float *verts, const float *radii, cons
 // (their grids are upper bounds; the node array is sized for the 2n - 1 nodes a tree over n primitives can have).
 // gpu_build returns once everything is enqueued; gpu_build_result() waits for the final state block.
 template <typename T>
-hipError_t gpu_build(hipStream_t s, const T *d_verts, const uint32_t *d_faces, const T *d_radii, bool cylinders, const uint32_t *d_prim_map, uint32_t n,
+hipError_t gpu_build(hipStream_t s, const T *d_verts, const uint32_t *d_faces, const T *d_radii, int prim_kind, const uint32_t *d_prim_map, uint32_t n,
                      uint32_t min_leaf, uint32_t max_depth, uint32_t bin_size, unsigned build_flags, DevBuf *workspace, DevBuf *nodes_buf,
                      DevBuf *indices_buf, void *pinned, hipEvent_t ev, std::string *err) {
   typedef typename Wire<T>::Node Node;
@@ -2792,7 +2803,7 @@ hipError_t gpu_build(hipStream_t s, const T *d_verts, const uint32_t *d_faces, c
                        (uint32_t)plan.max_active);
     {
       unsigned grid = (unsigned)std::min<size_t>(((size_t)n + 255) / 256, 2048);
-      hipLaunchKernelGGL((k_prim_records<T>), dim3(grid), dim3(256), 0, s, d_verts, d_faces, d_radii, cylinders, n, d_prim_map, recs[0], scene);
+      hipLaunchKernelGGL((k_prim_records<T>), dim3(grid), dim3(256), 0, s, d_verts, d_faces, d_radii, prim_kind, n, d_prim_map, recs[0], scene);
     }
     NRT_RANGE_POP();
     int cur = 0; // buffer holding the ranges of the nodes being split

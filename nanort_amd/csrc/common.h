@@ -132,6 +132,17 @@ struct LeafCylinder {
 static_assert(sizeof(LeafCylinder<float>) == 36, "LeafCylinder<float>");
 static_assert(sizeof(LeafTri<double>) == 80, "LeafTri<double>");
 
+// Leaf-ordered curve record (primitive kind 3: the cubic Bezier curves of examples/curves_primitive/main.cc:513-840; fp32 only, as
+// the example): the four control points and the two radii its intersector reads (those of the first and the last point), padded
+// to one 64-byte line so that a lane fetches it in four 16-byte loads.
+struct alignas(16) LeafCurve {
+  float cp[12];
+  float r0, r3;
+  uint32_t prim_id;
+  uint32_t pad;
+};
+static_assert(sizeof(LeafCurve) == 64, "LeafCurve");
+
 // Private traversal layout: one record per BRANCH node holding BOTH children's boxes, so a
 // step fetches one record and tests two boxes.  Records are dense, in the pre-order of the
 // branch nodes (record j <-> the j-th branch of the BVHNode array); the child boxes are copied
@@ -407,7 +418,10 @@ struct TraverseArgs {
   DoneRec *done_rec;                 // completion record of this launch's slot (device-visible host memory), or null: none
   DoneCount *done_count;             // its device-side words
   uint32_t done_seq;                 // sequence number of this launch within its slot
-  uint32_t done_publish;             // 1: the traversal kernel's last wave closes the record; 0: a post pass behind it does (sphere / cylinder kinds)
+  uint32_t done_publish;             // 1: the traversal kernel's last wave closes the record; 0: a post pass behind it does (sphere / cylinder / curve kinds)
+  // (the curve kind's fields come last: the offsets of everything the other kinds' instantiations read stay where they were)
+  const LeafCurve *curves;           // primitive kind 3 (leaf order)
+  uint32_t curve_subdiv;             // primitive kind 3: line segments per curve (the intersector's num_subdivisions, 1..64)
 };
 
 } // namespace nrt

@@ -10,6 +10,7 @@
 nrt_status nrt_internal_tree_view(nrt_ctx *c, nrt::TreeViewF32 *out);
 uint64_t nrt_internal_generation(const nrt_ctx *c); // counts the context's rebuilds
 int nrt_internal_device(const nrt_ctx *c);
+int nrt_internal_prim_kind(const nrt_ctx *c); // nrt::kPrim*
 
 namespace nrt {
 
@@ -46,6 +47,9 @@ template <typename T>
 hipError_t launch_gather_leaf_cylinders(const uint32_t *indices, const T *verts, const T *radii, LeafCylinder<T> *out, uint32_t n, hipStream_t s);
 hipError_t launch_cylinder_post(const nrt_ray_f32 *rays, const nrt_hit_f32 *compact, const uint8_t *bits, const float *verts, uint32_t n,
                                 void *out, uint8_t *mask, DoneRec *done_rec, DoneCount *done_count, uint32_t done_seq, hipStream_t s);
+hipError_t launch_gather_leaf_curves(const uint32_t *indices, const float *cps, const float *radii, LeafCurve *out, uint32_t n, hipStream_t s);
+hipError_t launch_curve_post(const nrt_ray_f32 *rays, const nrt_hit_f32 *compact, const uint8_t *bits, const float *cps, uint32_t n,
+                             void *out, uint8_t *mask, DoneRec *done_rec, DoneCount *done_count, uint32_t done_seq, hipStream_t s);
 
 // ---- multihit.hip -----------------------------------------------------------------------------------------------------
 template <typename T>
@@ -61,7 +65,7 @@ struct BuildResult {
 };
 // enqueues a whole build; its size and statistics arrive in `pinned` behind `ev`: gpu_build_result waits for them
 template <typename T>
-hipError_t gpu_build(hipStream_t s, const T *d_verts, const uint32_t *d_faces, const T *d_radii, bool cylinders, const uint32_t *d_prim_map,
+hipError_t gpu_build(hipStream_t s, const T *d_verts, const uint32_t *d_faces, const T *d_radii, int prim_kind, const uint32_t *d_prim_map,
                      uint32_t num_faces, uint32_t min_leaf, uint32_t max_depth, uint32_t bin_size, unsigned build_flags, DevBuf *workspace,
                      DevBuf *nodes_buf, DevBuf *indices_buf, void *pinned, hipEvent_t ev, std::string *err);
 hipError_t gpu_build_result(const void *pinned, hipEvent_t ev, BuildResult *res);

@@ -496,6 +496,8 @@ nrt_status nrtSceneAddNode_f32(nrt_scene *s, nrt_ctx *mesh, const float local_xf
   uint64_t nn = 0, ni = 0;
   if (nrtTreeSize(mesh, &nn, &ni) != NRT_OK || nn == 0)
     return sfail(s, NRT_ERR_INVALID, "nrtSceneAddNode: the mesh context has no tree (call nrtBuild first)");
+  if (nrt_internal_prim_kind(mesh) == (int)nrt::kPrimCurves)
+    return sfail(s, NRT_ERR_INVALID, "nrtSceneAddNode: scenes instance triangle meshes (this context holds curves)");
   nrt_scene::Inst in;
   in.mesh = mesh;
   memcpy(in.local, local_xform, sizeof(in.local));

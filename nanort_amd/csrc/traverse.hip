@@ -318,6 +318,68 @@ __global__ __launch_bounds__(256) void k_cylinder_post(const Wire<float>::Ray *_
   done_end_blocks(done_rec, done_count, done_seq);
 }
 
+// CurveIntersector::PostTraversal (examples/curves_primitive/main.cc:789-823) as a pass over the finished compact records
+// {u_param, v_param, t, prim} + 0/1 mask: the curve's tangent at u (EvaluateBezierTangent :456-462, the power-basis
+// coefficients in the example's association) and the normal vnormalize(cross(cross(dir, tangent), tangent)), into the caller's
+// 40-byte records {t, prim_id, u, v, tangent[3], normal[3]}.  `cps` holds the four control points of every curve (4 x xyz).
+// vnormalize (nanort.h:388-398) leaves a vector shorter than epsilon as it is.  A miss writes {max_t, ~0, 0, 0, 0, 0}.
+struct CurveHit32 {
+  float t;
+  uint32_t prim_id;
+  float u, v, tangent[3], normal[3];
+};
+static_assert(sizeof(CurveHit32) == 40, "nrt_curve_hit_f32");
+
+__global__ __launch_bounds__(256) void k_curve_post(const Wire<float>::Ray *__restrict__ rays,
+                                                    const Wire<float>::Hit *__restrict__ compact,
+                                                    const uint8_t *__restrict__ bits, const float *__restrict__ cps, uint32_t n,
+                                                    CurveHit32 *__restrict__ out, uint8_t *__restrict__ mask, DoneRec *done_rec,
+                                                    DoneCount *done_count, uint32_t done_seq) {
+  for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) { // (grid-stride: see k_sphere_uv)
+  const Wire<float>::Hit h = compact[i];
+  const uint8_t b = bits[i];
+  CurveHit32 o;
+  if (b & 1u) {
+    const Wire<float>::Ray r = rays[i];
+    const float *v = cps + 12 * (size_t)h.prim_id;
+    float dv[3], tan[3], c1[3], c2[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+      const float v0 = v[k], v1 = v[3 + k], v2 = v[6 + k], v3 = v[9 + k];
+      const float C1 = ((v3 - v2 * 3.0f) + v1 * 3.0f) - v0;
+      const float C2 = (v2 * 3.0f - v1 * 6.0f) + v0 * 3.0f;
+      const float C3 = v1 * 3.0f - v0 * 3.0f;
+      dv[k] = (((C1 * 3.0f) * h.u) * h.u + (C2 * 2.0f) * h.u) + C3;
+    }
+    cyl_normalize<float>(dv, tan);
+    const float dir[3] = {r.dir[0], r.dir[1], r.dir[2]};
+    c1[0] = dir[1] * tan[2] - dir[2] * tan[1]; // vcross (nanort.h:400-407)
+    c1[1] = dir[2] * tan[0] - dir[0] * tan[2];
+    c1[2] = dir[0] * tan[1] - dir[1] * tan[0];
+    c2[0] = c1[1] * tan[2] - c1[2] * tan[1];
+    c2[1] = c1[2] * tan[0] - c1[0] * tan[2];
+    c2[2] = c1[0] * tan[1] - c1[1] * tan[0];
+    cyl_normalize<float>(c2, o.normal);
+    o.tangent[0] = tan[0];
+    o.tangent[1] = tan[1];
+    o.tangent[2] = tan[2];
+    o.t = h.t;
+    o.prim_id = h.prim_id;
+    o.u = h.u;
+    o.v = h.v;
+  } else {
+    o.t = h.t; // the kernel's miss record carries max_t
+    o.prim_id = kInvalid;
+    o.u = o.v = 0.0f;
+    o.tangent[0] = o.tangent[1] = o.tangent[2] = 0.0f;
+    o.normal[0] = o.normal[1] = o.normal[2] = 0.0f;
+  }
+  out[i] = o;
+  if (mask) mask[i] = b & 1u;
+  }
+  done_end_blocks(done_rec, done_count, done_seq);
+}
+
 // Both child boxes of one WideNode at once.  For fp32 the two boxes ride in the two halves of
 // 64-bit register pairs, so the subtract / multiply chain issues as v_pk_add_f32 / v_pk_mul_f32
 // (one VALU slot for two IEEE operations: same operations, same rounding, half the issue slots).
@@ -844,6 +906,7 @@ __device__ __forceinline__ bool leaf_items_one_trip(Lane<float> &L, uint32_t cnt
 template <typename T, int STACK, bool STATS, int KIND, bool PLAIN = false, bool CLOCK = false, int WIDTH = 2, int ORDER = 0>
 __global__ __launch_bounds__(kTraverseBlock, (WIDTH == 4 && sizeof(T) == 4) ? NRT_W4_WAVES : 1) void k_traverse_wide(const TraverseArgs<T> a) {
   static_assert(WIDTH == 2 || WIDTH == 4, "one or two tree levels per step");
+  static_assert(KIND != kPrimCurves || sizeof(T) == 4, "curves are fp32 only, as their example");
   static_assert(ORDER == 0 || (WIDTH == 4 && sizeof(T) == 4), "distance order / leaf items are variants of the fp32 two-level step");
   static_assert((ORDER & 2) == 0 || (KIND == kPrimTriangles && !STATS), "leaf items: triangle records, production instantiations");
   static_assert((ORDER & 4) == 0 || ((ORDER & 1) == 0 && KIND == kPrimTriangles && !STATS && !CLOCK), "records addressed by 64-bit offsets: the default walk of triangle trees");
@@ -925,6 +988,9 @@ __global__ __launch_bounds__(kTraverseBlock, (WIDTH == 4 && sizeof(T) == 4) ? NR
     } else if (KIND == kPrimCylinders) {                                                               \
       const LeafCylinder<T> cy_ = a.cylinders[(slot_)];                                                \
       cylinder_test<T>(L, cy_, (act_), a.range0, a.range1, a.cyl_test_cap != 0u);                      \
+    } else if constexpr (KIND == kPrimCurves) { /* (compile-time: no other instantiation sees it) */   \
+      const LeafCurve cv_ = a.curves[(slot_)];                                                         \
+      curve_test<T>(L, cv_, (act_), a.range0, a.range1, a.curve_subdiv);                               \
     } else {                                                                                           \
       const LeafTri<T> tri_ = a.tris[(slot_)];                                                         \
       if (PLAIN)                                                                                       \
@@ -2177,6 +2243,23 @@ __global__ __launch_bounds__(256) void k_gather_leaf_cylinders(const uint32_t *_
   out[s] = r;
 }
 
+// Leaf-ordered curve records from (indices, control points, radii): of a curve's four radii the intersector reads the first
+// and the last.  Every byte of the 64-byte record is written.
+__global__ __launch_bounds__(256) void k_gather_leaf_curves(const uint32_t *__restrict__ indices, const float *__restrict__ cps,
+                                                            const float *__restrict__ radii, LeafCurve *__restrict__ out, uint32_t n) {
+  const uint32_t s = blockIdx.x * 256u + threadIdx.x;
+  if (s >= n) return;
+  const uint32_t prim = indices[s];
+  LeafCurve r;
+#pragma unroll
+  for (int k = 0; k < 12; k++) r.cp[k] = cps[12 * (size_t)prim + k];
+  r.r0 = radii[4 * (size_t)prim];
+  r.r3 = radii[4 * (size_t)prim + 3];
+  r.prim_id = prim;
+  r.pad = 0u;
+  out[s] = r;
+}
+
 // ---- host-side launchers (kernels.h) ----------------------------------------
 
 template <typename T>
@@ -2296,6 +2379,21 @@ hipError_t launch_cylinder_post(const nrt_ray_f32 *rays, const nrt_hit_f32 *comp
   if (n == 0) return hipSuccess;
   hipLaunchKernelGGL(k_cylinder_post, dim3(std::min((n + 255u) / 256u, 2048u)), dim3(256), 0, s, rays, compact, bits, verts, n,
                      (CylHit32 *)out, mask, done_rec, done_count, done_seq);
+  return hipGetLastError();
+}
+
+hipError_t launch_gather_leaf_curves(const uint32_t *indices, const float *cps, const float *radii, LeafCurve *out, uint32_t n,
+                                     hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_gather_leaf_curves, dim3((n + 255u) / 256u), dim3(256), 0, s, indices, cps, radii, out, n);
+  return hipGetLastError();
+}
+
+hipError_t launch_curve_post(const nrt_ray_f32 *rays, const nrt_hit_f32 *compact, const uint8_t *bits, const float *cps, uint32_t n,
+                             void *out, uint8_t *mask, DoneRec *done_rec, DoneCount *done_count, uint32_t done_seq, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_curve_post, dim3(std::min((n + 255u) / 256u, 2048u)), dim3(256), 0, s, rays, compact, bits, cps, n,
+                     (CurveHit32 *)out, mask, done_rec, done_count, done_seq);
   return hipGetLastError();
 }
 

@@ -363,6 +363,112 @@ __device__ __forceinline__ void cylinder_test(Lane<T> &L, const LeafCylinder<T> 
   L.prim = accept ? prim : L.prim;
 }
 
+// CurveIntersector::Intersect (examples/curves_primitive/main.cc:637-759) against one leaf record: the curve as `n` line
+// segments in a frame whose z axis is the ray (GetZAlign :382-417, Xform :419-430), de Casteljau (:432-454) at s / n, every
+// sum in the reference's association and every comparison in its own form so that NaNs take the same side.  There is no min_t
+// test, no t >= 0 test and no skip_prim_id in that intersector; `t < current` is strict.  u_param / v_param of the accepted
+// segment are the lane's u, v: as there, they change exactly when a segment is accepted, and later segments see the lowered t.
+//
+// The frame (9 + 3 floats) depends on the ray alone.  It is RECOMPUTED here, at each leaf record, not carried in the lane across
+// the walk.  By register count: with the frame recomputed the two instantiations of this kind hold 111 (two levels per step) and
+// 107 (one level) VGPRs, no scratch, four waves per SIMD; twelve more registers live through the inner-node loop would put them at
+// 119 - 123 of the 128 that four waves allow, with nothing left before scratch or three waves.  The recomputation is one sqrt,
+// three divisions and a dozen multiplies in front of a test of 9 * (n + 1) interpolations, and the compiler is free to hoist it
+// out of a leaf's record loop.  It is a pure function of the ray and contraction is off: the values are those a stored frame holds.
+struct CurveFrame {
+  float m00, m01, m02, m10, m11, m12, m20, m21, m22, t0, t1, t2;
+};
+__device__ __forceinline__ CurveFrame curve_frame(float ox, float oy, float oz, float lx, float ly, float lz) {
+  CurveFrame f;
+  const float dxz = __builtin_sqrtf(lx * lx + lz * lz);
+  if (dxz > 0.0f) {
+    const float lxdxz = lx / dxz, lydxz = ly / dxz, lzdxz = lz / dxz;
+    f.m00 = lzdxz;
+    f.m01 = -lxdxz * ly;
+    f.m02 = lx;
+    f.m10 = 0.0f;
+    f.m11 = dxz;
+    f.m12 = ly;
+    f.m20 = -lxdxz;
+    f.m21 = -lydxz * lz;
+    f.m22 = lz;
+  } else { // the ray runs along y (or its direction is zero / NaN)
+    f.m00 = 1.0f;
+    f.m01 = 0.0f;
+    f.m02 = 0.0f;
+    f.m10 = 0.0f;
+    f.m11 = 0.0f;
+    f.m12 = (ly > 0.0f) ? -1.0f : 1.0f;
+    f.m20 = 0.0f;
+    f.m21 = (ly > 0.0f) ? 1.0f : -1.0f;
+    f.m22 = 0.0f;
+  }
+  f.t0 = -((ox * f.m00 + oy * f.m10) + oz * f.m20);
+  f.t1 = -((ox * f.m01 + oy * f.m11) + oz * f.m21);
+  f.t2 = -((ox * f.m02 + oy * f.m12) + oz * f.m22);
+  return f;
+}
+// EvaluateBezier on one component: three, two, one linear interpolations
+__device__ __forceinline__ float curve_bezier1(float v0, float v1, float v2, float v3, float t) {
+  const float u = 1.0f - t;
+  const float a0 = v0 * u + v1 * t, a1 = v1 * u + v2 * t, a2 = v2 * u + v3 * t;
+  const float b0 = a0 * u + a1 * t, b1 = a1 * u + a2 * t;
+  return b0 * u + b1 * t;
+}
+
+template <typename T>
+__device__ __forceinline__ void curve_test(Lane<T> &L, const LeafCurve &cv, bool active, uint32_t range0, uint32_t range1,
+                                           uint32_t subdiv) {
+  const uint32_t prim = cv.prim_id;
+  bool ok = active & (prim >= range0) & (prim < range1);
+  const CurveFrame f = curve_frame(L.org0, L.org1, L.org2, L.d0, L.d1, L.d2);
+  float x[4], y[4], z[4];
+  float t_z = 0.0f;
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    const float px = cv.cp[3 * i + 0], py = cv.cp[3 * i + 1], pz = cv.cp[3 * i + 2];
+    x[i] = ((px * f.m00 + py * f.m10) + pz * f.m20) + f.t0;
+    y[i] = ((px * f.m01 + py * f.m11) + pz * f.m21) + f.t1;
+    z[i] = ((px * f.m02 + py * f.m12) + pz * f.m22) + f.t2;
+    t_z = (t_z < z[i]) ? z[i] : t_z;
+  }
+  const float uw = ((cv.r0 < cv.r3) ? cv.r3 : cv.r0) / 2.0f; // std::max(r0, r3) / 2
+  ok = ok & !(t_z < 4.0f * uw);
+  if (ok) { // (skipped by the whole wave when no lane got this far)
+    const float fn = (float)(int)subdiv, inv_n = 1.0f / fn;
+    const float w0 = 0.5f * cv.r0, w1 = 0.5f * cv.r3, bw = w1 - w0;
+    float cur = L.hit_t, up = L.u, vp = L.v;
+    bool hit = false;
+    // (segment s ends where segment s + 1 begins: (s + 1) / n is evaluated once)
+    float p1x = curve_bezier1(x[0], x[1], x[2], x[3], 0.0f / fn), p1y = curve_bezier1(y[0], y[1], y[2], y[3], 0.0f / fn),
+          p1z = curve_bezier1(z[0], z[1], z[2], z[3], 0.0f / fn);
+    for (uint32_t s = 0; s < subdiv; s++) {
+      const float p0x = p1x, p0y = p1y, p0z = p1z;
+      const float t1 = (float)(int)(s + 1u) / fn;
+      p1x = curve_bezier1(x[0], x[1], x[2], x[3], t1);
+      p1y = curve_bezier1(y[0], y[1], y[2], y[3], t1);
+      p1z = curve_bezier1(z[0], z[1], z[2], z[3], t1);
+      const float ax = 0.0f - p0x, ay = 0.0f - p0y; // the origin projected onto the segment, in the frame's xy plane
+      const float bx = p1x - p0x, by = p1y - p0y, bz = p1z - p0z;
+      const float d0 = (ax * bx) + (ay * by), d1 = (bx * bx) + (by * by);
+      float u = d0 / d1;
+      u = (u < 1.0f) ? u : 1.0f; // std::min(1.0f, u): NaN -> 1
+      u = (0.0f < u) ? u : 0.0f; // std::max(0.0f, .)
+      const float qx = p0x + (u * bx), qy = p0y + (u * by), t = p0z + (u * bz), r = w0 + (u * bw);
+      const float r2 = r * r, d2 = (qx * qx) + (qy * qy);
+      const bool acc = (d2 <= r2) & (t < cur);
+      up = acc ? (u + (float)(int)s) * inv_n : up;
+      vp = acc ? __builtin_sqrtf(d2) : vp;
+      cur = acc ? t : cur;
+      hit = hit | acc;
+    }
+    L.hit_t = cur; // (unchanged unless a segment was accepted)
+    L.u = up;
+    L.v = vp;
+    L.prim = hit ? prim : L.prim;
+  }
+}
+
 __device__ __forceinline__ unsigned lane_id() {
   return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
 }

@@ -6,7 +6,8 @@
 
 namespace nrt {
 
-enum : int { kPrimTriangles = 0, kPrimSpheres = 1, kPrimCylinders = 2 };
+enum : int { kPrimTriangles = 0, kPrimSpheres = 1, kPrimCylinders = 2, kPrimCurves = 3 };
+constexpr int kNumPrimKinds = 4;
 #ifndef NRT_W4_LDS_STACK
 #define NRT_W4_LDS_STACK 12
 #endif
@@ -28,15 +29,17 @@ inline bool operator==(const WalkVariant &a, const WalkVariant &b) {
          a.width == b.width && a.order == b.order;
 }
 
-static_assert(kPrimTriangles == 0 && kPrimSpheres == 1 && kPrimCylinders == 2, "the rows below spell KIND as its number");
+static_assert(kPrimTriangles == 0 && kPrimSpheres == 1 && kPrimCylinders == 2 && kPrimCurves == 3, "the rows below spell KIND as its number");
 // Every instantiation there is: X(T, STACK, STATS, KIND, PLAIN, CLOCK, WIDTH, ORDER), KIND spelled as its number (the row is also
 // the kernel's printed name).  traverse.hip builds its kernel table from these rows and walk_variant_exists() its membership
 // test, so a variant that is picked but not listed fails tests/test_walk_variant.py, not a launch.
 #define NRT_WALK_VARIANTS(X)                                                                                        \
-  X(float, NRT_W4_LDS_STACK, false, 1, false, false, 4, 0) /* spheres, cylinders: the id tests stay */             \
+  X(float, NRT_W4_LDS_STACK, false, 1, false, false, 4, 0) /* spheres, cylinders, curves: the id tests stay */     \
   X(float, 10, false, 1, false, false, 2, 0)                                                                        \
   X(float, NRT_W4_LDS_STACK, false, 2, false, false, 4, 0)                                                          \
   X(float, 10, false, 2, false, false, 2, 0)                                                                        \
+  X(float, NRT_W4_LDS_STACK, false, 3, false, false, 4, 0) /* (curves are fp32 only, as their example) */           \
+  X(float, 10, false, 3, false, false, 2, 0)                                                                        \
   X(float, NRT_W4_LDS_STACK, false, 0, true, false, 4, 6) /* triangles, two levels per step: PLAIN x ORDER */      \
   X(float, NRT_W4_LDS_STACK, false, 0, false, false, 4, 6)                                                          \
   X(float, NRT_W4_LDS_STACK, false, 0, true, false, 4, 4)                                                           \

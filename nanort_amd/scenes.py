@@ -85,6 +85,41 @@ def random_cylinders(n, bmin=(-1.0, -1.0, -1.0), bmax=(1.0, 1.0, 1.0)):
     return verts, radii
 
 
+def synthetic_hair(n, seed=0, ball_radius=4.0, length=1.5, thickness=0.02):
+    """Hair for the curve primitive: `n` cubic Bezier strands rooted at random points of a sphere of `ball_radius`, each growing
+    outwards by about `length` through jittered control points, root radius `thickness` tapering to a fifth of it at the tip.
+    Seeded numpy, no noise tables.  Returns control points (n, 4, 3) and radii (n, 4), float32."""
+    rng = np.random.default_rng(seed)
+    d = rng.normal(size=(n, 3))
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    root = d * ball_radius
+    step = length / 3.0
+    cps = np.empty((n, 4, 3), dtype=np.float64)
+    cps[:, 0] = root
+    for k in range(1, 4):  # every further control point: one step outwards plus a jitter that grows towards the tip
+        cps[:, k] = cps[:, k - 1] + d * step * rng.uniform(0.7, 1.3, size=(n, 1)) + rng.normal(size=(n, 3)) * (0.15 * k * step)
+    radii = thickness * np.linspace(1.0, 0.2, 4)[None, :] * rng.uniform(0.8, 1.2, size=(n, 1))
+    return cps.astype(np.float32), radii.astype(np.float32)
+
+
+def curves_camera_rays(width, height):
+    """The curve example's camera (reference examples/curves_primitive/main.cc:893-913), row-major: the eye at (0, 0, 20), pixel
+    (x, y) looking along normalize(x / width - 0.5, y / height - 0.5, -1), every step in float32 as there."""
+    f = np.float32
+    x = (np.arange(width, dtype=np.int64).astype(f) / f(width)) - f(0.5)
+    y = (np.arange(height, dtype=np.int64).astype(f) / f(height)) - f(0.5)
+    dx = np.broadcast_to(x[None, :], (height, width)).reshape(-1).astype(f)
+    dy = np.broadcast_to(y[:, None], (height, width)).reshape(-1).astype(f)
+    dz = np.full(dx.shape, -1.0, dtype=f)
+    ln = np.sqrt((dx * dx + dy * dy) + dz * dz).astype(f)  # vnormalize (nanort.h:383-398): * (1 / len)
+    inv = (f(1.0) / ln).astype(f)
+    rays = np.zeros((width * height,), dtype=RAY_F32)
+    rays["org"] = (0.0, 0.0, 20.0)
+    rays["dir"][:, 0], rays["dir"][:, 1], rays["dir"][:, 2] = dx * inv, dy * inv, dz * inv
+    rays["min_t"], rays["max_t"] = 0.0, 1.0e30
+    return rays
+
+
 def particle_camera_rays(width, height):
     """That example's camera (main.cc:367-389), row-major."""
     rays = np.empty((width * height,), dtype=RAY_F32)

@@ -86,6 +86,10 @@ assert SCENE_HIT_F32.itemsize == 20
 CYL_HIT_F32 = np.dtype([("u", "<f4"), ("v", "<f4"), ("normal", "<f4", 3), ("t", "<f4"), ("prim_id", "<u4")])
 assert CYL_HIT_F32.itemsize == 28
 
+# CurveIntersection of the reference's curve example (examples/curves_primitive/main.cc:606-619)
+CURVE_HIT_F32 = np.dtype([("t", "<f4"), ("prim_id", "<u4"), ("u", "<f4"), ("v", "<f4"), ("tangent", "<f4", 3), ("normal", "<f4", 3)])
+assert CURVE_HIT_F32.itemsize == 40
+
 MISS_PRIM_ID = 0xFFFFFFFF
 
 
