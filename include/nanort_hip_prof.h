@@ -22,8 +22,9 @@ extern "C" {
  * while rays were still being handed out (the steady part of a launch: the rest is its drain).  Returns 0 on success. */
 NRT_API int nrtDebugCounters(nrt_ctx *ctx, unsigned long long *out, int capacity /* >= 16 */);
 /* Profiling aid: with NRT_DEBUG bit 8192 every wave of a traversal launch records when it started, ran out of rays and
- * finished (100 MHz realtime ticks, 3 x u64 per wave).  Copies up to `cap` records of the most recent launch; returns
- * the number of waves of that launch, or -1 (tools/drain_probe.py). */
+ * finished, and when — out of rays — its live lanes first numbered at most 16, 8 and 4 (100 MHz realtime ticks, 6 x u64 per
+ * wave: start, dry, done, <= 16, <= 8, <= 4; a mark never reached equals `done`).  Copies up to `cap` records of the most
+ * recent launch; returns the number of waves of that launch, or -1 (tools/drain_probe.py). */
 NRT_API long nrtDebugWaveClocks(nrt_ctx *ctx, unsigned long long *out, long cap);
 /* Profiling aid: loop counters of the last scene query made after nrtSceneSetTunable(scene, "count_loops", 1) (a separately
  * instantiated, slower k_scene_walk).  out16[0] = outer trips of all waves, [1..2] level-change blocks run / lanes served,

@@ -118,6 +118,7 @@ struct nrt_ctx {
   int lds_stack = kLdsStackDefault;
   unsigned chunk = 128, chunk_tail_pct = 0, refill_min = 44, trav_min = 16, leaf_min = 32; // (trav_min: 8 until round 3; 12-14 was the optimum of the two-level walk before its inner loop ran two rounds per trip, profiles/r03t_trav_min.txt; 16 with two rounds per trip in the fp64 walk, profiles/r03ZA)
   int f64_row_fetch = 1; // fp64 walk: fetch the plane rows of a WideNode<double> by the ray's signs (0: fetch the record and select; the path arrays of 4 GiB and more take)
+  unsigned tail_quad = 4; // traverse.hip "four lanes to a ray": live lanes of a wave that is out of rays at or below which it finishes them a quad per ray (0: never; records bit-identical at every value).  4 is the smallest threshold whose slowest bench run beat the parent library's fastest (C3 +2.5 %; 8: +3.5 %, 16: +5 %; at 0 the branch's registers cost 2.3 %): profiles/r07a_tail_quad.txt
   unsigned trav_min4 = 24; // the same threshold for the fp32 two-level walk, whose inner loop runs two pop + step rounds per trip (profiles/r03Z_threshold_resweep*.txt)
   unsigned num_parts = 8; // ray partitions == XCDs (env NRT_PARTS)
   unsigned debug_flags = 0;
@@ -316,6 +317,7 @@ static const TunableDesc kTunables[] = {
     NRT_TUNABLE("wide4_big", 0, 2, wide4_big_ok, int),            // ... also for record arrays of 4 GiB and more (64-bit offsets; next build / set_tree); 2: 64-bit offsets whatever the size (tests)
     NRT_TUNABLE("wide4", 0, 1, wide4, int),                       // two tree levels per step (next build / set_tree)
     NRT_TUNABLE("leaf_compact", 0, 1, leaf_compact, int),         // two-level walk, triangle trees with leaves of <= 4 records: leaf phase over items (records bit-identical)
+    NRT_TUNABLE("tail_quad", 0, 16, tail_quad, unsigned),         // two-level triangle walk: a wave out of rays with at most this many live lanes finishes them four lanes to a ray (0: never; records bit-identical)
     NRT_TUNABLE("dyn_head", 0, 1, dyn_head, int),                 // a batch without a static share: a wave's first chunk without an atomic
     NRT_TUNABLE("order4", 0, 1, order4, int),                     // two-level walk: 0 (default) = the reference's order, every field bit-identical; 1 = slots by entry distance (faster; contract-level parity at ties)
     NRT_TUNABLE("launch_timing", 0, 1, launch_timing, int),       // == nrtSetLaunchTiming
@@ -1234,6 +1236,7 @@ static void fill_walk_args(const nrt_ctx *c, const TraverseLaunch<T> &l, const W
   a.refill_min = c->refill_min;
   a.trav_min = w.wide4() ? c->trav_min4 : c->trav_min;
   a.leaf_min = c->leaf_min;
+  a.tail_lanes = c->tail_quad;
 }
 
 // ... part 2: the slot's scratch, the grid and the work distribution (launch_plan.h), the rays and where their records go.
@@ -1364,7 +1367,7 @@ static nrt_status traverse_device(nrt_ctx *c, TraverseLaunch<T> l) {
     if ((st = ensure(c, slot->cyl_bits, (size_t)l.n))) return st;
   }
   if (w.dbg & 8192u) { // profiling library only: per-wave time stamps of this launch (nrtDebugWaveClocks)
-    if ((st = ensure(c, c->b_wave_clock, (size_t)total_waves * 3 * sizeof(unsigned long long)))) return st;
+    if ((st = ensure(c, c->b_wave_clock, (size_t)total_waves * kWaveClockWords * sizeof(unsigned long long)))) return st;
     c->wave_clock_waves = total_waves;
   }
   TraverseArgs<T> a;
@@ -2015,7 +2018,7 @@ long nrtDebugWaveClocks(nrt_ctx *c, unsigned long long *out, long cap) {
   if (!c || !out || !c->b_wave_clock.p) return -1;
   if (hipDeviceSynchronize() != hipSuccess) return -1;
   const long n = std::min<long>(cap, (long)c->wave_clock_waves);
-  if (hipMemcpy(out, c->b_wave_clock.p, (size_t)n * 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+  if (hipMemcpy(out, c->b_wave_clock.p, (size_t)n * kWaveClockWords * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess) return -1;
   return (long)c->wave_clock_waves;
 }
 

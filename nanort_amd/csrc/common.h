@@ -192,6 +192,7 @@ static_assert(sizeof(Wide4Node<float>) == 128, "Wide4Node<float>");
 static_assert(sizeof(Wide4Node<double>) == 224, "Wide4Node<double>");
 constexpr uint32_t kWide4Empty = 0xFFFFFFFFu;
 constexpr uint32_t kLeafBit = 0x80000000u;
+constexpr int kWaveClockWords = 6; // u64 stamps per wave of a clocked launch (TraverseArgs::wave_clock, nrtDebugWaveClocks)
 constexpr uint32_t kPackedFirstBits = 27;
 constexpr uint32_t kPackedFirstMask = (1u << kPackedFirstBits) - 1u;
 constexpr uint32_t kPackedMaxCount = 16;
@@ -409,12 +410,13 @@ struct TraverseArgs {
   uint32_t blocks_per_part;          // gridDim.x / num_parts
   uint32_t dyn_head;                 // a batch without a static share: the first chunk of a wave is chunk `wave index` of its home range, without an atomic (tunable dyn_head)
   unsigned long long *counters;      // 4 x u64 when counting
-  unsigned long long *wave_clock;    // profiling (NRT_DEBUG bit 8192): 3 x u64 per wave {start, out of rays, done}, 100 MHz ticks; else null
+  unsigned long long *wave_clock;    // profiling (NRT_DEBUG bit 8192): kWaveClockWords x u64 per wave {start, out of rays, done, live lanes first <= 16, <= 8, <= 4}, 100 MHz ticks; else null
   uint32_t chunk;                    // rays claimed per atomic (a multiple of 32)
   uint32_t chunk_tail_pct;           // the last this-many percent of every partition's dynamic range go out in half chunks
   uint32_t refill_min;               // refill idle lanes once this many are idle (1..64)
   uint32_t trav_min;                 // leave the inner-node loop when fewer lanes than this are walking
   uint32_t leaf_min;                 // with fewer lanes than this waiting at a leaf, refill first (if a refill is due) and test triangles later
+  uint32_t tail_lanes;               // out of rays and at most this many lanes of a wave still hold one (0..16, 0 = never): the wave finishes them four lanes to a ray (tunable tail_quad; the fp32 two-level triangle walk in the reference's order)
   DoneRec *done_rec;                 // completion record of this launch's slot (device-visible host memory), or null: none
   DoneCount *done_count;             // its device-side words
   uint32_t done_seq;                 // sequence number of this launch within its slot
