@@ -1029,6 +1029,9 @@ __global__ __launch_bounds__(kTraverseBlock, (WIDTH == 4 && sizeof(T) == 4) ? NR
     }                                                                                                  \
   } while (0)
 
+  // (QUAD: the wave leaves the loop for the tail below; which of its lanes were idle then)
+  bool to_tail = false;
+  unsigned long long tail_idle = 0ull;
   for (;;) {
     // ---- refill idle lanes ---------------------------------------------------------
     if (STATS) st_stamp = __builtin_amdgcn_s_memtime();
@@ -1087,226 +1090,14 @@ __global__ __launch_bounds__(kTraverseBlock, (WIDTH == 4 && sizeof(T) == 4) ? NR
     if (clocked && ck.exhausted && clk_dry == 0ull) clk_dry = __builtin_amdgcn_s_memrealtime();
     NRT_CLOCK_LIVE(64u - (unsigned)__builtin_popcountll(idle));
     if constexpr (QUAD) {
-      // ---- the tail of a launch: FOUR LANES TO A RAY ------------------------------------------------------------------------
-      // No rays are left to hand out and at most a.tail_lanes lanes of this wave still hold one (tunable tail_quad): what the launch
-      // waits for from here on is the dependent chain of those rays, ~200 wave instructions a step of which a handful of lanes use
-      // anything.  The wave's own idle lanes shorten the step instead.  Live ray number q (ballot rank) moves to quad q — its
-      // constants and state by ds_bpermute, its stack stays where it is: the quad addresses its owner's column of s_stack and of
-      // the spill arrays — and the quads finish the rays: lane j tests box j of a record (slab4_presel's arithmetic, operation for
-      // operation) and ranks its slot in the binary loop's order (NRT_STEP_NODE4_SL), two DPP quad permutes combine the four hit
-      // bits, the first hit in rank order is entered and the others are pushed in reverse rank order with their t_min; at a leaf
-      // lane j tests record i + j (tri_test's operations on the same operands) and the four results are accepted IN RECORD ORDER
-      // through the reference's rule (nanort.h:1133-1139), every lane following the sequence on its copy of the hit distance; u, v
-      // and the primitive stay with the lane that tested the accepted record (`owner_`), which writes the result.  Every ray sees
-      // the pops, steps and leaf tests its lane would have continued with, in the same order: records bit-identical
-      // (tests/test_gpu_tail_quad.py).  Nothing leaves the wave.
+      // The tail of a launch, four lanes to a ray (behind this loop): no rays are left to hand out and at most a.tail_lanes lanes of
+      // this wave still hold one (tunable tail_quad).  The tail finishes every ray the wave holds and nothing returns from it, so
+      // only the switch stands here: the tail's twenty moved registers and its temporaries stay out of the allocation and the
+      // scheduling of the loop that every launch runs (profiles/r07b_tail_behind_loop.txt).
       const unsigned live_n_ = 64u - (unsigned)__builtin_popcountll(idle);
       if (ck.exhausted && live_n_ != 0u && live_n_ <= NRT_TAIL_N) { // (wave-uniform)
-        if (state == W_IDLE && rid != kInvalid) NRT_WRITE_RESULT(); // finished results leave before their lanes are reused
-        const unsigned q_ = lane >> 2, j_ = lane & 3u;
-        uint32_t src_ = 0u; // the lane whose ray this quad takes: the q-th live one
-        {
-          unsigned k_ = 0u;
-          for (unsigned long long m_ = ~idle; m_ != 0ull; m_ &= m_ - 1ull, k_++) src_ = (q_ == k_) ? (uint32_t)__builtin_ctzll(m_) : src_;
-        }
-        const bool has_ = q_ < live_n_;
-        const int sa_ = (int)(src_ << 2);
-#define NRT_QMOVE_F(x_) x_ = __int_as_float(__builtin_amdgcn_ds_bpermute(sa_, __float_as_int(x_)))
-#define NRT_QMOVE_U(x_) x_ = (uint32_t)__builtin_amdgcn_ds_bpermute(sa_, (int)(x_))
-        NRT_QMOVE_F(L.org0);
-        NRT_QMOVE_F(L.org1);
-        NRT_QMOVE_F(L.org2);
-        NRT_QMOVE_F(L.inv0);
-        NRT_QMOVE_F(L.inv1);
-        NRT_QMOVE_F(L.inv2);
-        NRT_QMOVE_F(L.min_t);
-        NRT_QMOVE_F(L.max_t);
-        NRT_QMOVE_F(L.hit_t);
-        NRT_QMOVE_F(L.Sx);
-        NRT_QMOVE_F(L.Sy);
-        NRT_QMOVE_F(L.Sz);
-        NRT_QMOVE_F(L.u);
-        NRT_QMOVE_F(L.v);
-        NRT_QMOVE_U(L.pk); // (with the any-hit bit of the ray's batch)
-        NRT_QMOVE_U(L.prim);
-        NRT_QMOVE_U(rid);
-        NRT_QMOVE_U(cur);
-        state = __builtin_amdgcn_ds_bpermute(sa_, state);
-        sp = __builtin_amdgcn_ds_bpermute(sa_, sp);
-#undef NRT_QMOVE_F
-#undef NRT_QMOVE_U
-        L.so0 = (L.pk & 1u) ? 48u : 0u; // (lane_init: 48 where the direction is negative — the sign bits of pk)
-        L.so1 = (L.pk & 2u) ? 48u : 0u;
-        L.so2 = (L.pk & 4u) ? 48u : 0u;
-        state = has_ ? state : W_IDLE; // (a lane waiting at a leaf stays waiting at that leaf)
-        rid = has_ ? rid : kInvalid;
-        sp = has_ ? sp : 0;
-        const unsigned otid_ = (tid & ~63u) | src_;                   // the owner's column of s_stack
-        const unsigned ogslot_ = blockIdx.x * kTraverseBlock + otid_; // ... and of the spill arrays
-        bool owner_ = j_ == 0u; // this lane holds u, v, prim of the ray's best hit (exactly one lane of a quad)
-        const char *wb_ = reinterpret_cast<const char *>(a.wide4);
-        for (;;) {
-          const unsigned long long liveq_ = __ballot(state != W_IDLE);
-          NRT_CLOCK_LIVE((unsigned)__builtin_popcountll(liveq_) >> 2);
-          if (liveq_ == 0ull) break;
-          if (state == W_POP) { // NRT_POP_ENTRY, every lane of the quad alike
-            int s1_ = sp - 1;
-            s1_ = s1_ < 0 ? 0 : s1_;
-            const int sl_ = s1_ > STACK - 1 ? STACK - 1 : s1_;
-            typename SE::type e_ = s_stack[sl_][otid_];
-            if (s1_ >= STACK) {
-              const size_t o_ = (size_t)(s1_ - STACK) * a.spill_stride + ogslot_;
-              e_ = SE::make(a.spill[o_], a.spill_tmin[o_]);
-            }
-            const bool fin_ = (sp == 0);
-            const bool enter_ = !fin_ & (SE::tmin(e_) <= L.hit_t);
-            const uint32_t ref_ = SE::ref(e_);
-            sp = s1_;
-            cur = enter_ ? (ref_ & ~kLeafBit) : cur;
-            state = fin_ ? W_IDLE : (enter_ ? ((ref_ & kLeafBit) ? W_LEAF : W_TRAV) : W_POP);
-          }
-          if (state == W_TRAV) { // NRT_STEP_NODE4_SL over slab4_presel's arithmetic, slot j in lane j
-            const uint32_t rec0_ = cur << 7, rec_ = rec0_ + 4u * j_, rec48_ = rec_ + 48u;
-            const float lo0 = *reinterpret_cast<const float *>(wb_ + (size_t)(rec_ + L.so0));
-            const float hi0 = *reinterpret_cast<const float *>(wb_ + (size_t)(rec48_ - L.so0));
-            const float lo1 = *reinterpret_cast<const float *>(wb_ + (size_t)(rec_ + L.so1) + 16);
-            const float hi1 = *reinterpret_cast<const float *>(wb_ + (size_t)(rec48_ - L.so1) + 16);
-            const float lo2 = *reinterpret_cast<const float *>(wb_ + (size_t)(rec_ + L.so2) + 32);
-            const float hi2 = *reinterpret_cast<const float *>(wb_ + (size_t)(rec48_ - L.so2) + 32);
-            const uint32_t c_ = *reinterpret_cast<const uint32_t *>(wb_ + (size_t)rec_ + 96);
-            const int ax0_ = *reinterpret_cast<const int32_t *>(wb_ + (size_t)rec0_ + 112);
-            const int axh_ = *reinterpret_cast<const int32_t *>(wb_ + (size_t)(rec0_ + 4u * (j_ >> 1)) + 116); // axis1 for slots 0, 1; axis2 for slots 2, 3
-            const float mm = Const<float>::maxmult();
-            float tmin = L.min_t, tmax = L.hit_t;
-            {
-              const float t0 = (lo0 - L.org0) * L.inv0;
-              const float t1 = ((hi0 - L.org0) * L.inv0) * mm;
-              tmin = Const<float>::fmax(t0, tmin); // see slab_test
-              tmax = Const<float>::fmin(t1, tmax);
-            }
-            {
-              const float t0 = (lo1 - L.org1) * L.inv1;
-              const float t1 = ((hi1 - L.org1) * L.inv1) * mm;
-              tmin = Const<float>::fmax(t0, tmin);
-              tmax = Const<float>::fmin(t1, tmax);
-            }
-            {
-              const float t0 = (lo2 - L.org2) * L.inv2;
-              const float t1 = ((hi2 - L.org2) * L.inv2) * mm;
-              tmin = Const<float>::fmax(t0, tmin);
-              tmax = Const<float>::fmin(t1, tmax);
-            }
-            const bool h_ = (tmin <= tmax) & (((j_ & 1u) == 0u) | (c_ != kWide4Empty)); // (slots 1 and 3 can be empty)
-            // rank of slot j in the binary loop's order: the near half (by the node's axis) first, inside a half its near slot first
-            const uint32_t s0_ = (uint32_t)L.sign(ax0_), sh_ = (uint32_t)L.sign(axh_);
-            const uint32_t rank_ = ((((j_ >> 1) ^ s0_) & 1u) << 1) | ((j_ ^ sh_) & 1u);
-            const uint32_t m_ = quad_or(h_ ? (1u << rank_) : 0u); // the quad's hits by rank
-            const uint32_t n_ = (uint32_t)__builtin_popcount(m_);
-            const uint32_t pos_ = (uint32_t)__builtin_popcount(m_ & ((1u << rank_) - 1u)); // hits before mine
-            // the first hit in rank order is entered; the others are pushed in reverse rank order (they pop in rank order)
-            if (h_ && pos_ != 0u) {
-              const int at_ = sp + (int)(n_ - 1u - pos_);
-              if (at_ < STACK) {
-                s_stack[at_][otid_] = SE::make(c_, tmin);
-              } else {
-                const size_t o_ = (size_t)(at_ - STACK) * a.spill_stride + ogslot_;
-                a.spill[o_] = c_;
-                a.spill_tmin[o_] = tmin;
-              }
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); // (what one lane of the quad pushed, the four pop: program order holds across lanes)
-            sp += n_ != 0u ? (int)(n_ - 1u) : 0;
-            const uint32_t next_ = quad_or((h_ && pos_ == 0u) ? c_ : 0u); // (a reference is never 0: record 0 is the root)
-            cur = n_ != 0u ? (next_ & ~kLeafBit) : cur;
-            state = n_ != 0u ? ((next_ & kLeafBit) ? W_LEAF : W_TRAV) : W_POP;
-          }
-          if (__ballot(state == W_LEAF) != 0ull) { // records i .. i + 3 per trip, any count
-            uint32_t cnt = 0, first = 0;
-            if (state == W_LEAF) {
-              if (a.packed_leaves) {
-                cnt = (cur >> kPackedFirstBits) + 1u;
-                first = cur & kPackedFirstMask;
-              } else {
-                const Node *nd = a.nodes + cur;
-                cnt = nd->data[0];
-                first = nd->data[1];
-              }
-            }
-            if (a.debug_flags & 1u) cnt = 0;
-            for (uint32_t i = 0; __ballot(i < cnt) != 0ull; i += 4u) {
-              const bool act_ = i + j_ < cnt;
-              const LeafTri<T> tri = a.tris[first + (act_ ? i + j_ : 0u)];
-              // TriangleIntersector::Intersect (nanort.h:1054-1150) up to the hit distance: tri_test's own operations
-              const uint32_t prim_i = tri.prim_id;
-              bool ok = PLAIN ? act_ : (act_ & (prim_i >= a.range0) & (prim_i < a.range1) & (prim_i != a.skip_prim));
-              const bool cull_i = PLAIN ? false : cull;
-              const T A0 = tri.p0[0] - L.org0, A1 = tri.p0[1] - L.org1, A2 = tri.p0[2] - L.org2;
-              const T B0 = tri.p1[0] - L.org0, B1 = tri.p1[1] - L.org1, B2 = tri.p1[2] - L.org2;
-              const T C0 = tri.p2[0] - L.org0, C1 = tri.p2[1] - L.org1, C2 = tri.p2[2] - L.org2;
-              const T Akz = sel3(A0, A1, A2, L.kz()), Bkz = sel3(B0, B1, B2, L.kz()), Ckz = sel3(C0, C1, C2, L.kz());
-              const T Ax = sel3(A0, A1, A2, L.kx()) - L.Sx * Akz;
-              const T Ay = sel3(A0, A1, A2, L.ky()) - L.Sy * Akz;
-              const T Bx = sel3(B0, B1, B2, L.kx()) - L.Sx * Bkz;
-              const T By = sel3(B0, B1, B2, L.ky()) - L.Sy * Bkz;
-              const T Cx = sel3(C0, C1, C2, L.kx()) - L.Sx * Ckz;
-              const T Cy = sel3(C0, C1, C2, L.ky()) - L.Sy * Ckz;
-              T U = Cx * By - Cy * Bx;
-              T V = Ax * Cy - Ay * Cx;
-              T W = Bx * Ay - By * Ax;
-              if (ok && (U == T(0) || V == T(0) || W == T(0))) { // nanort.h:1094-1107
-                const double CxBy = double(Cx) * double(By), CyBx = double(Cy) * double(Bx);
-                const double AxCy = double(Ax) * double(Cy), AyCx = double(Ay) * double(Cx);
-                const double BxAy = double(Bx) * double(Ay), ByAx = double(By) * double(Ax);
-                U = T(CxBy - CyBx);
-                V = T(AxCy - AyCx);
-                W = T(BxAy - ByAx);
-              }
-              const bool neg = (U < T(0)) | (V < T(0)) | (W < T(0));
-              const bool pos = (U > T(0)) | (V > T(0)) | (W > T(0));
-              ok = ok & !(neg & (cull_i | pos));
-              const T det = U + V + W;
-              ok = ok & !(det == T(0));
-              T tt_i = T(0), uu_i = T(0), vv_i = T(0);
-              if (ok) {
-                const T Az = L.Sz * Akz, Bz = L.Sz * Bkz, Cz = L.Sz * Ckz;
-                const T D = U * Az + V * Bz + W * Cz;
-                const T rcp = T(1.0) / det;
-                tt_i = D * rcp;
-                uu_i = V * rcp;
-                vv_i = W * rcp;
-              }
-              // ... accepted in record order, the same sequence in every lane of the quad
-              const uint32_t okm_ = quad_or(ok ? (1u << j_) : 0u);
-              if (__ballot(okm_ != 0u) != 0ull) {
-                bool got_ = false;
-                uint32_t win_ = 0u;
-#define NRT_QUAD_ACCEPT(K_)                                                                                                    \
-                do {                                                                                                           \
-                  const T ttk_ = quad_bcast<K_>(tt_i);                                                                         \
-                  const bool acc_ = ((okm_ >> K_) & 1u) != 0u && !(ttk_ > L.hit_t) && !(ttk_ < L.min_t); /* nanort.h:1133-1139 */ \
-                  L.hit_t = acc_ ? ttk_ : L.hit_t;                                                                             \
-                  win_ = acc_ ? (uint32_t)K_ : win_;                                                                           \
-                  got_ = got_ | acc_;                                                                                          \
-                } while (0)
-                NRT_QUAD_ACCEPT(0);
-                NRT_QUAD_ACCEPT(1);
-                NRT_QUAD_ACCEPT(2);
-                NRT_QUAD_ACCEPT(3);
-#undef NRT_QUAD_ACCEPT
-                const bool me_ = got_ & (win_ == j_);
-                owner_ = got_ ? me_ : owner_;
-                L.u = me_ ? uu_i : L.u;
-                L.v = me_ ? vv_i : L.v;
-                L.prim = me_ ? prim_i : L.prim;
-              }
-            }
-            // occlusion query: any accepted primitive settles the ray — drop what is left of its stack
-            if (a.any_hit | a.batch_anyhit) sp = (state == W_LEAF && L.hit_t < L.max_t && (a.any_hit != 0u || (L.pk & 512u) != 0u)) ? 0 : sp;
-            state = (state == W_LEAF) ? W_POP : state;
-          }
-        }
-        if (owner_ && rid != kInvalid) NRT_WRITE_RESULT();
-        rid = kInvalid;
+        tail_idle = idle;
+        to_tail = true;
         break;
       }
     }
@@ -1504,6 +1295,230 @@ __global__ __launch_bounds__(kTraverseBlock, (WIDTH == 4 && sizeof(T) == 4) ? NR
       state = (state == W_LEAF) ? W_POP : state;
     }
     if (STATS) st_t_p2 += __builtin_amdgcn_s_memtime() - st_stamp;
+  }
+  if constexpr (QUAD) {
+    // ---- the tail of a launch: FOUR LANES TO A RAY ------------------------------------------------------------------------
+    // No rays are left to hand out and at most a.tail_lanes lanes of this wave still hold one (tunable tail_quad): what the launch
+    // waits for from here on is the dependent chain of those rays, ~200 wave instructions a step of which a handful of lanes use
+    // anything.  The wave's own idle lanes shorten the step instead.  Live ray number q (ballot rank) moves to quad q — its
+    // constants and state by ds_bpermute, its stack stays where it is: the quad addresses its owner's column of s_stack and of
+    // the spill arrays — and the quads finish the rays: lane j tests box j of a record (slab4_presel's arithmetic, operation for
+    // operation) and ranks its slot in the binary loop's order (NRT_STEP_NODE4_SL), two DPP quad permutes combine the four hit
+    // bits, the first hit in rank order is entered and the others are pushed in reverse rank order with their t_min; at a leaf
+    // lane j tests record i + j (tri_test's operations on the same operands) and the four results are accepted IN RECORD ORDER
+    // through the reference's rule (nanort.h:1133-1139), every lane following the sequence on its copy of the hit distance; u, v
+    // and the primitive stay with the lane that tested the accepted record (`owner_`), which writes the result.  Every ray sees
+    // the pops, steps and leaf tests its lane would have continued with, in the same order: records bit-identical
+    // (tests/test_gpu_tail_quad.py).  Nothing leaves the wave.
+    if (to_tail) { // (wave-uniform; the only way here with a live lane)
+      const unsigned long long idle = tail_idle;
+      const unsigned live_n_ = 64u - (unsigned)__builtin_popcountll(idle);
+      if (state == W_IDLE && rid != kInvalid) NRT_WRITE_RESULT(); // finished results leave before their lanes are reused
+      const unsigned q_ = lane >> 2, j_ = lane & 3u;
+      uint32_t src_ = 0u; // the lane whose ray this quad takes: the q-th live one
+      {
+        unsigned k_ = 0u;
+        for (unsigned long long m_ = ~idle; m_ != 0ull; m_ &= m_ - 1ull, k_++) src_ = (q_ == k_) ? (uint32_t)__builtin_ctzll(m_) : src_;
+      }
+      const bool has_ = q_ < live_n_;
+      const int sa_ = (int)(src_ << 2);
+#define NRT_QMOVE_F(x_) x_ = __int_as_float(__builtin_amdgcn_ds_bpermute(sa_, __float_as_int(x_)))
+#define NRT_QMOVE_U(x_) x_ = (uint32_t)__builtin_amdgcn_ds_bpermute(sa_, (int)(x_))
+      NRT_QMOVE_F(L.org0);
+      NRT_QMOVE_F(L.org1);
+      NRT_QMOVE_F(L.org2);
+      NRT_QMOVE_F(L.inv0);
+      NRT_QMOVE_F(L.inv1);
+      NRT_QMOVE_F(L.inv2);
+      NRT_QMOVE_F(L.min_t);
+      NRT_QMOVE_F(L.max_t);
+      NRT_QMOVE_F(L.hit_t);
+      NRT_QMOVE_F(L.Sx);
+      NRT_QMOVE_F(L.Sy);
+      NRT_QMOVE_F(L.Sz);
+      NRT_QMOVE_F(L.u);
+      NRT_QMOVE_F(L.v);
+      NRT_QMOVE_U(L.pk); // (with the any-hit bit of the ray's batch)
+      NRT_QMOVE_U(L.prim);
+      NRT_QMOVE_U(rid);
+      NRT_QMOVE_U(cur);
+      state = __builtin_amdgcn_ds_bpermute(sa_, state);
+      sp = __builtin_amdgcn_ds_bpermute(sa_, sp);
+#undef NRT_QMOVE_F
+#undef NRT_QMOVE_U
+      L.so0 = (L.pk & 1u) ? 48u : 0u; // (lane_init: 48 where the direction is negative — the sign bits of pk)
+      L.so1 = (L.pk & 2u) ? 48u : 0u;
+      L.so2 = (L.pk & 4u) ? 48u : 0u;
+      state = has_ ? state : W_IDLE; // (a lane waiting at a leaf stays waiting at that leaf)
+      rid = has_ ? rid : kInvalid;
+      sp = has_ ? sp : 0;
+      const unsigned otid_ = (tid & ~63u) | src_;                   // the owner's column of s_stack
+      const unsigned ogslot_ = blockIdx.x * kTraverseBlock + otid_; // ... and of the spill arrays
+      bool owner_ = j_ == 0u; // this lane holds u, v, prim of the ray's best hit (exactly one lane of a quad)
+      const char *wb_ = reinterpret_cast<const char *>(a.wide4);
+      for (;;) {
+        const unsigned long long liveq_ = __ballot(state != W_IDLE);
+        NRT_CLOCK_LIVE((unsigned)__builtin_popcountll(liveq_) >> 2);
+        if (liveq_ == 0ull) break;
+        if (state == W_POP) { // NRT_POP_ENTRY, every lane of the quad alike
+          int s1_ = sp - 1;
+          s1_ = s1_ < 0 ? 0 : s1_;
+          const int sl_ = s1_ > STACK - 1 ? STACK - 1 : s1_;
+          typename SE::type e_ = s_stack[sl_][otid_];
+          if (s1_ >= STACK) {
+            const size_t o_ = (size_t)(s1_ - STACK) * a.spill_stride + ogslot_;
+            e_ = SE::make(a.spill[o_], a.spill_tmin[o_]);
+          }
+          const bool fin_ = (sp == 0);
+          const bool enter_ = !fin_ & (SE::tmin(e_) <= L.hit_t);
+          const uint32_t ref_ = SE::ref(e_);
+          sp = s1_;
+          cur = enter_ ? (ref_ & ~kLeafBit) : cur;
+          state = fin_ ? W_IDLE : (enter_ ? ((ref_ & kLeafBit) ? W_LEAF : W_TRAV) : W_POP);
+        }
+        if (state == W_TRAV) { // NRT_STEP_NODE4_SL over slab4_presel's arithmetic, slot j in lane j
+          const uint32_t rec0_ = cur << 7, rec_ = rec0_ + 4u * j_, rec48_ = rec_ + 48u;
+          const float lo0 = *reinterpret_cast<const float *>(wb_ + (size_t)(rec_ + L.so0));
+          const float hi0 = *reinterpret_cast<const float *>(wb_ + (size_t)(rec48_ - L.so0));
+          const float lo1 = *reinterpret_cast<const float *>(wb_ + (size_t)(rec_ + L.so1) + 16);
+          const float hi1 = *reinterpret_cast<const float *>(wb_ + (size_t)(rec48_ - L.so1) + 16);
+          const float lo2 = *reinterpret_cast<const float *>(wb_ + (size_t)(rec_ + L.so2) + 32);
+          const float hi2 = *reinterpret_cast<const float *>(wb_ + (size_t)(rec48_ - L.so2) + 32);
+          const uint32_t c_ = *reinterpret_cast<const uint32_t *>(wb_ + (size_t)rec_ + 96);
+          const int ax0_ = *reinterpret_cast<const int32_t *>(wb_ + (size_t)rec0_ + 112);
+          const int axh_ = *reinterpret_cast<const int32_t *>(wb_ + (size_t)(rec0_ + 4u * (j_ >> 1)) + 116); // axis1 for slots 0, 1; axis2 for slots 2, 3
+          const float mm = Const<float>::maxmult();
+          float tmin = L.min_t, tmax = L.hit_t;
+          {
+            const float t0 = (lo0 - L.org0) * L.inv0;
+            const float t1 = ((hi0 - L.org0) * L.inv0) * mm;
+            tmin = Const<float>::fmax(t0, tmin); // see slab_test
+            tmax = Const<float>::fmin(t1, tmax);
+          }
+          {
+            const float t0 = (lo1 - L.org1) * L.inv1;
+            const float t1 = ((hi1 - L.org1) * L.inv1) * mm;
+            tmin = Const<float>::fmax(t0, tmin);
+            tmax = Const<float>::fmin(t1, tmax);
+          }
+          {
+            const float t0 = (lo2 - L.org2) * L.inv2;
+            const float t1 = ((hi2 - L.org2) * L.inv2) * mm;
+            tmin = Const<float>::fmax(t0, tmin);
+            tmax = Const<float>::fmin(t1, tmax);
+          }
+          const bool h_ = (tmin <= tmax) & (((j_ & 1u) == 0u) | (c_ != kWide4Empty)); // (slots 1 and 3 can be empty)
+          // rank of slot j in the binary loop's order: the near half (by the node's axis) first, inside a half its near slot first
+          const uint32_t s0_ = (uint32_t)L.sign(ax0_), sh_ = (uint32_t)L.sign(axh_);
+          const uint32_t rank_ = ((((j_ >> 1) ^ s0_) & 1u) << 1) | ((j_ ^ sh_) & 1u);
+          const uint32_t m_ = quad_or(h_ ? (1u << rank_) : 0u); // the quad's hits by rank
+          const uint32_t n_ = (uint32_t)__builtin_popcount(m_);
+          const uint32_t pos_ = (uint32_t)__builtin_popcount(m_ & ((1u << rank_) - 1u)); // hits before mine
+          // the first hit in rank order is entered; the others are pushed in reverse rank order (they pop in rank order)
+          if (h_ && pos_ != 0u) {
+            const int at_ = sp + (int)(n_ - 1u - pos_);
+            if (at_ < STACK) {
+              s_stack[at_][otid_] = SE::make(c_, tmin);
+            } else {
+              const size_t o_ = (size_t)(at_ - STACK) * a.spill_stride + ogslot_;
+              a.spill[o_] = c_;
+              a.spill_tmin[o_] = tmin;
+            }
+          }
+          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); // (what one lane of the quad pushed, the four pop: program order holds across lanes)
+          sp += n_ != 0u ? (int)(n_ - 1u) : 0;
+          const uint32_t next_ = quad_or((h_ && pos_ == 0u) ? c_ : 0u); // (a reference is never 0: record 0 is the root)
+          cur = n_ != 0u ? (next_ & ~kLeafBit) : cur;
+          state = n_ != 0u ? ((next_ & kLeafBit) ? W_LEAF : W_TRAV) : W_POP;
+        }
+        if (__ballot(state == W_LEAF) != 0ull) { // records i .. i + 3 per trip, any count
+          uint32_t cnt = 0, first = 0;
+          if (state == W_LEAF) {
+            if (a.packed_leaves) {
+              cnt = (cur >> kPackedFirstBits) + 1u;
+              first = cur & kPackedFirstMask;
+            } else {
+              const Node *nd = a.nodes + cur;
+              cnt = nd->data[0];
+              first = nd->data[1];
+            }
+          }
+          if (a.debug_flags & 1u) cnt = 0;
+          for (uint32_t i = 0; __ballot(i < cnt) != 0ull; i += 4u) {
+            const bool act_ = i + j_ < cnt;
+            const LeafTri<T> tri = a.tris[first + (act_ ? i + j_ : 0u)];
+            // TriangleIntersector::Intersect (nanort.h:1054-1150) up to the hit distance: tri_test's own operations
+            const uint32_t prim_i = tri.prim_id;
+            bool ok = PLAIN ? act_ : (act_ & (prim_i >= a.range0) & (prim_i < a.range1) & (prim_i != a.skip_prim));
+            const bool cull_i = PLAIN ? false : cull;
+            const T A0 = tri.p0[0] - L.org0, A1 = tri.p0[1] - L.org1, A2 = tri.p0[2] - L.org2;
+            const T B0 = tri.p1[0] - L.org0, B1 = tri.p1[1] - L.org1, B2 = tri.p1[2] - L.org2;
+            const T C0 = tri.p2[0] - L.org0, C1 = tri.p2[1] - L.org1, C2 = tri.p2[2] - L.org2;
+            const T Akz = sel3(A0, A1, A2, L.kz()), Bkz = sel3(B0, B1, B2, L.kz()), Ckz = sel3(C0, C1, C2, L.kz());
+            const T Ax = sel3(A0, A1, A2, L.kx()) - L.Sx * Akz;
+            const T Ay = sel3(A0, A1, A2, L.ky()) - L.Sy * Akz;
+            const T Bx = sel3(B0, B1, B2, L.kx()) - L.Sx * Bkz;
+            const T By = sel3(B0, B1, B2, L.ky()) - L.Sy * Bkz;
+            const T Cx = sel3(C0, C1, C2, L.kx()) - L.Sx * Ckz;
+            const T Cy = sel3(C0, C1, C2, L.ky()) - L.Sy * Ckz;
+            T U = Cx * By - Cy * Bx;
+            T V = Ax * Cy - Ay * Cx;
+            T W = Bx * Ay - By * Ax;
+            if (ok && (U == T(0) || V == T(0) || W == T(0))) { // nanort.h:1094-1107
+              const double CxBy = double(Cx) * double(By), CyBx = double(Cy) * double(Bx);
+              const double AxCy = double(Ax) * double(Cy), AyCx = double(Ay) * double(Cx);
+              const double BxAy = double(Bx) * double(Ay), ByAx = double(By) * double(Ax);
+              U = T(CxBy - CyBx);
+              V = T(AxCy - AyCx);
+              W = T(BxAy - ByAx);
+            }
+            const bool neg = (U < T(0)) | (V < T(0)) | (W < T(0));
+            const bool pos = (U > T(0)) | (V > T(0)) | (W > T(0));
+            ok = ok & !(neg & (cull_i | pos));
+            const T det = U + V + W;
+            ok = ok & !(det == T(0));
+            T tt_i = T(0), uu_i = T(0), vv_i = T(0);
+            if (ok) {
+              const T Az = L.Sz * Akz, Bz = L.Sz * Bkz, Cz = L.Sz * Ckz;
+              const T D = U * Az + V * Bz + W * Cz;
+              const T rcp = T(1.0) / det;
+              tt_i = D * rcp;
+              uu_i = V * rcp;
+              vv_i = W * rcp;
+            }
+            // ... accepted in record order, the same sequence in every lane of the quad
+            const uint32_t okm_ = quad_or(ok ? (1u << j_) : 0u);
+            if (__ballot(okm_ != 0u) != 0ull) {
+              bool got_ = false;
+              uint32_t win_ = 0u;
+#define NRT_QUAD_ACCEPT(K_)                                                                                                    \
+              do {                                                                                                           \
+                const T ttk_ = quad_bcast<K_>(tt_i);                                                                         \
+                const bool acc_ = ((okm_ >> K_) & 1u) != 0u && !(ttk_ > L.hit_t) && !(ttk_ < L.min_t); /* nanort.h:1133-1139 */ \
+                L.hit_t = acc_ ? ttk_ : L.hit_t;                                                                             \
+                win_ = acc_ ? (uint32_t)K_ : win_;                                                                           \
+                got_ = got_ | acc_;                                                                                          \
+              } while (0)
+              NRT_QUAD_ACCEPT(0);
+              NRT_QUAD_ACCEPT(1);
+              NRT_QUAD_ACCEPT(2);
+              NRT_QUAD_ACCEPT(3);
+#undef NRT_QUAD_ACCEPT
+              const bool me_ = got_ & (win_ == j_);
+              owner_ = got_ ? me_ : owner_;
+              L.u = me_ ? uu_i : L.u;
+              L.v = me_ ? vv_i : L.v;
+              L.prim = me_ ? prim_i : L.prim;
+            }
+          }
+          // occlusion query: any accepted primitive settles the ray — drop what is left of its stack
+          if (a.any_hit | a.batch_anyhit) sp = (state == W_LEAF && L.hit_t < L.max_t && (a.any_hit != 0u || (L.pk & 512u) != 0u)) ? 0 : sp;
+          state = (state == W_LEAF) ? W_POP : state;
+        }
+      }
+      if (owner_ && rid != kInvalid) NRT_WRITE_RESULT();
+      rid = kInvalid;
+    }
   }
   if (rid != kInvalid) NRT_WRITE_RESULT(); // results still held in registers
 #undef NRT_WRITE_RESULT
