@@ -196,6 +196,22 @@ constexpr int kWaveClockWords = 6; // u64 stamps per wave of a clocked launch (T
 constexpr uint32_t kPackedFirstBits = 27;
 constexpr uint32_t kPackedFirstMask = (1u << kPackedFirstBits) - 1u;
 constexpr uint32_t kPackedMaxCount = 16;
+// A PACKED leaf reference without its leaf bit (see "Child reference" above): THE one statement of the format.
+__host__ __device__ constexpr uint32_t packed_leaf_ref(uint32_t count, uint32_t first) { return ((count - 1u) << kPackedFirstBits) | first; }
+__host__ __device__ constexpr uint32_t packed_leaf_count(uint32_t ref) { return (ref >> kPackedFirstBits) + 1u; }
+__host__ __device__ constexpr uint32_t packed_leaf_first(uint32_t ref) { return ref & kPackedFirstMask; }
+// The records of the leaf a walk has reached, `cur` = its reference without the leaf bit: packed, or the index of the leaf's
+// BVHNode, which holds {count, first}.
+template <typename NODE>
+__host__ __device__ inline void leaf_span(uint32_t packed, const NODE *nodes, uint32_t cur, uint32_t &cnt, uint32_t &first) {
+  if (packed) {
+    cnt = packed_leaf_count(cur);
+    first = packed_leaf_first(cur);
+  } else {
+    cnt = nodes[cur].data[0];
+    first = nodes[cur].data[1];
+  }
+}
 
 // Device-side view of a context's fp32 tree for the code inside this library that walks it in its own kernels (the
 // two-level scene kernel, scene.hip).  Not part of the C ABI.

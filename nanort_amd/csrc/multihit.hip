@@ -48,6 +48,7 @@ __global__ __launch_bounds__(kTraverseBlock) void k_traverse_multihit(const Mult
   const unsigned lane = lane_id();
   const unsigned gslot = blockIdx.x * kTraverseBlock + tid;
   const bool cull = a.cull_back_face != 0;
+  const LaneStack<StackRef, STACK, TraverseArgs<T>> stk = {a, tid, gslot};
 
   Lane<T> L; // L.hit_t == B outside the triangle test
   uint32_t rid = kInvalid;
@@ -77,16 +78,7 @@ __global__ __launch_bounds__(kTraverseBlock) void k_traverse_multihit(const Mult
       for (uint32_t j_ = held; j_ < K; j_++) row_[j_] = miss_;                                    \
       if (m.counts) m.counts[rid] = held;                                                         \
     }                                                                                             \
-    uint32_t popped_ = cur;                                                                       \
-    if (!fin_) {                                                                                  \
-      const int sp1_ = sp - 1;                                                                    \
-      if (sp1_ < STACK) {                                                                         \
-        popped_ = s_stack[sp1_][tid];                                                             \
-      } else {                                                                                    \
-        popped_ = a.spill[(size_t)(sp1_ - STACK) * a.spill_stride + gslot];                       \
-      }                                                                                           \
-    }                                                                                             \
-    cur = popped_;                                                                                \
+    if (!fin_) stk.load(s_stack, sp - 1, cur);                                                    \
     sp = fin_ ? sp : sp - 1;                                                                      \
     rid = fin_ ? kInvalid : rid;                                                                  \
     state = fin_ ? LANE_IDLE : LANE_TRAV;                                                         \
@@ -129,11 +121,7 @@ __global__ __launch_bounds__(kTraverseBlock) void k_traverse_multihit(const Mult
           const int near = L.sign(nd.axis);
           const uint32_t far_child = near ? nd.data[0] : nd.data[1];
           cur = near ? nd.data[1] : nd.data[0];
-          if (sp < STACK) {
-            s_stack[sp][tid] = far_child;
-          } else {
-            a.spill[(size_t)(sp - STACK) * a.spill_stride + gslot] = far_child;
-          }
+          stk.store(s_stack, sp, far_child);
           sp++;
         } else {
           leaf_cnt = nd.data[0];

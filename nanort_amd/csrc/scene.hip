@@ -266,14 +266,7 @@ __global__ __launch_bounds__(256) void k_scene_list_w4(const nrt_ray_f32 *__rest
         continue;
       }
       uint32_t lcount, lfirst;
-      if (packed_leaves) {
-        lcount = ((cj & ~nrt::kLeafBit) >> nrt::kPackedFirstBits) + 1u;
-        lfirst = cj & nrt::kPackedFirstMask;
-      } else {
-        const nrt_node_f32 &leaf = top_nodes[cj & ~nrt::kLeafBit];
-        lcount = leaf.data[0];
-        lfirst = leaf.data[1];
-      }
+      nrt::leaf_span(packed_leaves, top_nodes, cj & ~nrt::kLeafBit, lcount, lfirst);
       for (uint32_t q = 0; q < lcount; q++) {
         const uint32_t k = top_indices[lfirst + q];
         float t;
@@ -631,7 +624,7 @@ nrt_status nrtSceneCommit(nrt_scene *s) {
                               root.data[1] <= nrt::kPackedFirstMask;
         if (one_leaf) {
           mt[m].root_leaf = 1;
-          mt[m].leaf_ref = ((root.data[0] - 1u) << nrt::kPackedFirstBits) | root.data[1];
+          mt[m].leaf_ref = nrt::packed_leaf_ref(root.data[0], root.data[1]);
           memcpy(mt[m].bmin, root.bmin, sizeof(mt[m].bmin));
           memcpy(mt[m].bmax, root.bmax, sizeof(mt[m].bmax));
         }

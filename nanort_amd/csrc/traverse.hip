@@ -48,6 +48,7 @@ __global__ __launch_bounds__(kTraverseBlock) void k_traverse(const TraverseArgs<
   const unsigned lane = lane_id();
   const unsigned gslot = blockIdx.x * kTraverseBlock + tid;
   const bool cull = a.cull_back_face != 0;
+  const LaneStack<StackRef, STACK, TraverseArgs<T>> stk = {a, tid, gslot};
 
   Lane<T> L;
   uint32_t rid = kInvalid; // ray this lane is working on
@@ -81,16 +82,7 @@ __global__ __launch_bounds__(kTraverseBlock) void k_traverse(const TraverseArgs<
       }                                                                                  \
       if (a.mask) a.mask[rid] = hit_ ? 1 : 0;                                            \
     }                                                                                    \
-    uint32_t popped_ = cur;                                                              \
-    if (!fin_) {                                                                         \
-      const int sp1_ = sp - 1;                                                           \
-      if (sp1_ < STACK) {                                                                \
-        popped_ = s_stack[sp1_][tid];                                                    \
-      } else {                                                                           \
-        popped_ = a.spill[(size_t)(sp1_ - STACK) * a.spill_stride + gslot];              \
-      }                                                                                  \
-    }                                                                                    \
-    cur = popped_;                                                                       \
+    if (!fin_) stk.load(s_stack, sp - 1, cur);                                           \
     sp = fin_ ? sp : sp - 1;                                                             \
     rid = fin_ ? kInvalid : rid;                                                         \
     state = fin_ ? LANE_IDLE : LANE_TRAV;                                                \
@@ -134,11 +126,7 @@ __global__ __launch_bounds__(kTraverseBlock) void k_traverse(const TraverseArgs<
           const uint32_t far_child = near ? nd.data[0] : nd.data[1];
           cur = near ? nd.data[1] : nd.data[0];
           // push far; near stays in `cur` (it would be popped next anyway: nanort.h:2542-2543)
-          if (sp < STACK) {
-            s_stack[sp][tid] = far_child;
-          } else {
-            a.spill[(size_t)(sp - STACK) * a.spill_stride + gslot] = far_child;
-          }
+          stk.store(s_stack, sp, far_child);
           sp++;
           if (COUNT) {
             // the reference holds near+far on its stack at this point
@@ -202,24 +190,6 @@ __global__ __launch_bounds__(kTraverseBlock) void k_traverse(const TraverseArgs<
 // (t_min <= hit_t) (nanort.h:2315-2318: hit_t is the innermost operand of the
 // safemin chain).
 // ---------------------------------------------------------------------------
-template <typename T>
-__device__ __forceinline__ bool slab_test_tmin(const Lane<T> &L, const T box[6], T &tmin_out) {
-  const T mm = Const<T>::maxmult();
-  T tmin = L.min_t, tmax = L.hit_t;
-#pragma unroll
-  for (int k = 0; k < 3; k++) {
-    const int sg = L.sign(k);
-    const T lo = sg ? box[3 + k] : box[k];
-    const T hi = sg ? box[k] : box[3 + k];
-    const T t0 = (lo - L.org(k)) * L.inv(k);
-    const T t1 = (hi - L.org(k)) * L.inv(k) * mm;
-    tmin = Const<T>::fmax(t0, tmin); // see slab_test
-    tmax = Const<T>::fmin(t1, tmax);
-  }
-  tmin_out = tmin;
-  return tmin <= tmax;
-}
-
 enum : int { W_IDLE = 0, W_TRAV = 1, W_LEAF = 2, W_POP = 3 };
 
 // SphereIntersector::PostTraversal (examples/particle_primitive/main.cc:262-277) as a pass over the finished
@@ -402,7 +372,7 @@ __device__ __forceinline__ SlabPair<float> slab_pair(const Lane<float> &L, const
     const f2 iv = {L.inv(k), L.inv(k)};
     const f2 t0 = (lo - o) * iv;
     const f2 t1 = ((hi - o) * iv) * mm;
-    tmin0 = Const<float>::fmax(t0.x, tmin0); // see slab_test
+    tmin0 = Const<float>::fmax(t0.x, tmin0); // see slab_axis
     tmin1 = Const<float>::fmax(t0.y, tmin1);
     tmax0 = Const<float>::fmin(t1.x, tmax0);
     tmax1 = Const<float>::fmin(t1.y, tmax1);
@@ -419,12 +389,12 @@ __device__ __forceinline__ SlabPair<double> slab_pair(const Lane<double> &L, con
   SlabPair<double> r;
   const double b0[6] = {w.mn[0][0], w.mn[1][0], w.mn[2][0], w.mx[0][0], w.mx[1][0], w.mx[2][0]};
   const double b1[6] = {w.mn[0][1], w.mn[1][1], w.mn[2][1], w.mx[0][1], w.mx[1][1], w.mx[2][1]};
-  r.h0 = slab_test_tmin<double>(L, b0, r.tm0);
-  r.h1 = slab_test_tmin<double>(L, b1, r.tm1);
+  r.h0 = slab_test_tmin<double>(L, b0, b0 + 3, r.tm0);
+  r.h1 = slab_test_tmin<double>(L, b1, b1 + 3, r.tm1);
   return r;
 }
 // The same two tests with the near / far rows of each axis fetched by the ray's direction signs (Lane::so0..2: 0 or 48,
-// the distance between the mn and mx rows of a WideNode<double>): the same values into slab_test_tmin's arithmetic,
+// the distance between the mn and mx rows of a WideNode<double>): the same values into slab_axis's arithmetic,
 // twelve 64-bit selects per step fewer.  `rec` = byte offset of the record (32 bits: arrays below 4 GiB).
 struct WideTail { // bytes 96..111 of a WideNode<double>
   uint32_t c0, c1;
@@ -443,7 +413,7 @@ __device__ __forceinline__ SlabPair<double> slab_pair_presel(const Lane<double> 
     const d2 hi = *reinterpret_cast<const d2 *>(base + (size_t)(rec48 - so) + 16 * k);
     const double t00 = (lo.x - L.org(k)) * L.inv(k), t01 = (lo.y - L.org(k)) * L.inv(k);
     const double t10 = (hi.x - L.org(k)) * L.inv(k) * mm, t11 = (hi.y - L.org(k)) * L.inv(k) * mm;
-    tmin0 = Const<double>::fmax(t00, tmin0); // see slab_test
+    tmin0 = Const<double>::fmax(t00, tmin0); // see slab_axis
     tmin1 = Const<double>::fmax(t01, tmin1);
     tmax0 = Const<double>::fmin(t10, tmax0);
     tmax1 = Const<double>::fmin(t11, tmax1);
@@ -478,7 +448,7 @@ __device__ __forceinline__ Slab4<float> slab4(const Lane<float> &L, const Wide4N
       const f2 hi = {sg ? w.bmin[k][2 * p] : w.bmax[k][2 * p], sg ? w.bmin[k][2 * p + 1] : w.bmax[k][2 * p + 1]};
       const f2 t0 = (lo - o) * iv;
       const f2 t1 = ((hi - o) * iv) * mm;
-      tmin[2 * p] = Const<float>::fmax(t0.x, tmin[2 * p]); // see slab_test
+      tmin[2 * p] = Const<float>::fmax(t0.x, tmin[2 * p]); // see slab_axis
       tmin[2 * p + 1] = Const<float>::fmax(t0.y, tmin[2 * p + 1]);
       tmax[2 * p] = Const<float>::fmin(t1.x, tmax[2 * p]);
       tmax[2 * p + 1] = Const<float>::fmin(t1.y, tmax[2 * p + 1]);
@@ -523,7 +493,7 @@ __device__ __forceinline__ Slab4<float> slab4_presel(const Lane<float> &L, const
       const f2 hi = {p ? hi4.z : hi4.x, p ? hi4.w : hi4.y};
       const f2 t0 = (lo - o) * iv;
       const f2 t1 = ((hi - o) * iv) * mm;
-      tmin[2 * p] = Const<float>::fmax(t0.x, tmin[2 * p]); // see slab_test
+      tmin[2 * p] = Const<float>::fmax(t0.x, tmin[2 * p]); // see slab_axis
       tmin[2 * p + 1] = Const<float>::fmax(t0.y, tmin[2 * p + 1]);
       tmax[2 * p] = Const<float>::fmin(t1.x, tmax[2 * p]);
       tmax[2 * p + 1] = Const<float>::fmin(t1.y, tmax[2 * p + 1]);
@@ -543,7 +513,7 @@ __device__ __forceinline__ Slab4<double> slab4(const Lane<double> &L, const Wide
 #pragma unroll
   for (int j = 0; j < 4; j++) {
     const double box[6] = {w.bmin[0][j], w.bmin[1][j], w.bmin[2][j], w.bmax[0][j], w.bmax[1][j], w.bmax[2][j]};
-    r.h[j] = slab_test_tmin<double>(L, box, r.tm[j]);
+    r.h[j] = slab_test_tmin<double>(L, box, box + 3, r.tm[j]);
   }
   return r;
 }
@@ -555,6 +525,7 @@ struct StackEntry;
 template <>
 struct StackEntry<float> {
   typedef uint2 type;
+  static constexpr bool kHasTmin = true; // (LaneStack: the t_min half lies in spill_tmin)
   static __device__ __forceinline__ type make(uint32_t ref, float tm) { return make_uint2(ref, __float_as_uint(tm)); }
   static __device__ __forceinline__ uint32_t ref(const type &e) { return e.x; }
   static __device__ __forceinline__ float tmin(const type &e) { return __uint_as_float(e.y); }
@@ -562,6 +533,7 @@ struct StackEntry<float> {
 template <>
 struct StackEntry<double> {
   typedef uint4 type; // {ref, pad, t_min lo, t_min hi}
+  static constexpr bool kHasTmin = true;
   static __device__ __forceinline__ type make(uint32_t ref, double tm) {
     const unsigned long long b = (unsigned long long)__double_as_longlong(tm);
     return make_uint4(ref, 0u, (uint32_t)b, (uint32_t)(b >> 32));
@@ -572,28 +544,57 @@ struct StackEntry<double> {
   }
 };
 
-// The two per-lane moves of the WideNode walk, shared by k_traverse_wide and the two-level kernel k_scene_trace.  They
-// expand inside a kernel that has these names in scope: L (Lane<T>), cur, state, sp, tid, gslot, s_stack[STACK][block],
-// SE = StackEntry<T>, `a` with .spill / .spill_tmin / .spill_stride.
+// The per-lane moves of the wide walks, shared by k_traverse_wide, the tail of its launches and the scene kernels
+// (k_scene_trace, k_scene_walk).  What a macro may assume in the scope it expands in, and nothing else:
+//   L (Lane<T>), cur, state, sp   the lane's ray and where its walk stands — read and written;
+//   T, STACK, SE = StackEntry<T>  the kernel's types;
+//   s_stack[STACK][block]         the block's LDS stacks;
+//   stk                           the lane's OWN stack in them and in the launch's overflow arrays (LaneStack<SE, STACK, ...>,
+//                                 traverse_dev.h: its two columns): the step macros push there;
+//   a                             the launch's argument block: NRT_STACK_STORE writes its .spill / .spill_tmin;
+//   tid                           NRT_STEP_NODE4_SL / _DIST only: the lane's column of s_stack, for the three unguarded stores they
+//                                 make when every lane of the wave has room in LDS.
+// A pop names the stack it pops from as its argument: a lane's own (`stk`) or, in the tail of a launch, its owner's column.
+// Where entry i lies is said twice, once per direction: LaneStack::load reads it, NRT_STACK_STORE writes it, both over the
+// view's columns and its spill_at(); no other macro and no kernel computes a stack address.
 
-// One stack pop (a lane in W_POP): the entry is entered iff its t_min still beats the hit distance — the reference's
-// slab test at pop time (see the comment above the kernel); an empty stack finishes the ray.
-#define NRT_POP_ENTRY()                                                                                \
+// One stack pop (a lane in W_POP) from the stack `stk_`: the entry is entered iff its t_min still beats the hit distance — the
+// reference's slab test at pop time (see the comment above the kernel); an empty stack finishes the ray.
+#define NRT_POP_ENTRY(stk_)                                                                            \
 do {                                                                                                 \
   int s1_ = sp - 1;                                                                                  \
-  s1_ = s1_ < 0 ? 0 : s1_;                                                                           \
-  const int sl_ = s1_ > STACK - 1 ? STACK - 1 : s1_; /* (max then min: one v_med3_i32) */            \
-  typename SE::type e_ = s_stack[sl_][tid];                                                          \
-  if (s1_ >= STACK) { /* rare: the entry lives in the global overflow stack */                       \
-    const size_t o_ = (size_t)(s1_ - STACK) * a.spill_stride + gslot;                                \
-    e_ = SE::make(a.spill[o_], a.spill_tmin[o_]);                                                    \
-  }                                                                                                  \
+  s1_ = s1_ < 0 ? 0 : s1_; /* (with the accessor's own clamp at STACK - 1: one v_med3_i32) */        \
+  typename SE::type e_;                                                                              \
+  (stk_).load(s_stack, s1_, e_);                                                                     \
   const bool fin_ = (sp == 0);                        /* empty stack: the ray is done */             \
   const bool enter_ = !fin_ & (SE::tmin(e_) <= L.hit_t);                                             \
   const uint32_t ref_ = SE::ref(e_);                                                                 \
   sp = s1_;                                                                                          \
   cur = enter_ ? (ref_ & ~kLeafBit) : cur;                                                           \
   state = fin_ ? W_IDLE : (enter_ ? ((ref_ & kLeafBit) ? W_LEAF : W_TRAV) : W_POP);                  \
+} while (0)
+
+// Entry `i_` of the stack `stk_` := {ref_, tm_}: LaneStack::load's counterpart for StackEntry.  A macro, its columns taken from the
+// view: as a function (member or free, whatever it is handed) the fp64 one-level walk's step loads its record's 12-byte tail
+// in two pieces and C5 runs 9 % slower (profiles/r08a_one_statement.txt).
+#define NRT_STACK_STORE(stk_, i_, ref_, tm_)                                                           \
+do {                                                                                                 \
+  if ((i_) < STACK) {                                                                                \
+    s_stack[(i_)][(stk_).col] = SE::make((ref_), (tm_));                                             \
+  } else {                                                                                           \
+    const size_t o_ = (stk_).spill_at((i_));                                                         \
+    a.spill[o_] = (ref_);                                                                            \
+    a.spill_tmin[o_] = (tm_);                                                                        \
+  }                                                                                                  \
+} while (0)
+
+// One push onto the lane's own stack.
+#define NRT_PUSH_IF(cond_, ref_, tm_)                                                                  \
+do {                                                                                                 \
+  if (cond_) {                                                                                       \
+    NRT_STACK_STORE(stk, sp, (ref_), (tm_));                                                         \
+    sp++;                                                                                            \
+  }                                                                                                  \
 } while (0)
 
 // One step of a lane in W_TRAV over the WideNode record `w_`: both child boxes tested, the far child of two hits
@@ -608,18 +609,8 @@ do {                                                                            
 do {                                                                                                 \
   const bool near1_ = L.sign((w_).axis) != 0; /* near child = data[dir_sign[axis]] (nanort.h:2538) */ \
   const bool both_ = sl_.h0 & sl_.h1, any_ = sl_.h0 | sl_.h1;                                        \
-  if (both_) { /* the far child waits with its t_min */                                              \
-    const uint32_t rf_ = near1_ ? (w_).c0 : (w_).c1;                                                 \
-    const T tf_ = near1_ ? sl_.tm0 : sl_.tm1;                                                        \
-    if (sp < STACK) {                                                                                \
-      s_stack[sp][tid] = SE::make(rf_, tf_);                                                         \
-    } else {                                                                                         \
-      const size_t o_ = (size_t)(sp - STACK) * a.spill_stride + gslot;                               \
-      a.spill[o_] = rf_;                                                                             \
-      a.spill_tmin[o_] = tf_;                                                                        \
-    }                                                                                                \
-    sp++;                                                                                            \
-  }                                                                                                  \
+  /* the far child of two hits waits with its t_min */                                               \
+  NRT_PUSH_IF(both_, near1_ ? (w_).c0 : (w_).c1, near1_ ? sl_.tm0 : sl_.tm1);                        \
   /* both hit: the near one; one hit: that one */                                                    \
   const bool go1_ = both_ ? near1_ : sl_.h1;                                                         \
   const uint32_t next_ = go1_ ? (w_).c1 : (w_).c0;                                                   \
@@ -681,20 +672,6 @@ do {                                                                            
   const uint32_t next_ = q0_ ? r0_ : (q1_ ? r1_ : (q2_ ? r2_ : r3_));                                \
   cur = any_ ? (next_ & ~kLeafBit) : cur;                                                            \
   state = any_ ? ((next_ & kLeafBit) ? W_LEAF : W_TRAV) : W_POP;                                     \
-} while (0)
-
-#define NRT_PUSH_IF(cond_, ref_, tm_)                                                                  \
-do {                                                                                                 \
-  if (cond_) {                                                                                       \
-    if (sp < STACK) {                                                                                \
-      s_stack[sp][tid] = SE::make((ref_), (tm_));                                                    \
-    } else {                                                                                         \
-      const size_t o_ = (size_t)(sp - STACK) * a.spill_stride + gslot;                               \
-      a.spill[o_] = (ref_);                                                                          \
-      a.spill_tmin[o_] = (tm_);                                                                      \
-    }                                                                                                \
-    sp++;                                                                                            \
-  }                                                                                                  \
 } while (0)
 
 // The Wide4Node step with the four slots entered in order of their ENTRY DISTANCE (template parameter ORDER = 1; tunable
@@ -797,7 +774,7 @@ do {                                                                            
 // ballots), item j is tested by lane j with its OWNER's ray constants (org, Sx Sy Sz and the packed axes, fetched by ds_bpermute;
 // the record's address and the owner's lane through two small LDS arrays), and every owner then takes its items' results IN RECORD
 // ORDER through the reference's own accept rule (`tt > t` / `tt < min_t` reject, equality and NaN accepted, nanort.h:1133-1139).
-// The same tests on the same operands (tri_test's operations, one for one), accepted in the same sequence: the lane state after
+// The same tests on the same operands (tri_solve, as tri_test), accepted in the same sequence: the lane state after
 // the leaf is bit for bit what the owner's own loop leaves (tests/test_gpu_leaf_items.py, tests/test_gpu_scene.py).  Returns false
 // — nothing done — when the records do not fit one trip: the caller's owner loop then runs.  Wave-uniform control flow only.
 // (SLOT: how an item names its record in LDS — a 32-bit index into `base` (k_traverse_wide: one array per launch; 4 bytes per item
@@ -836,45 +813,10 @@ __device__ __forceinline__ bool leaf_items_one_trip(Lane<float> &L, uint32_t cnt
               sz = __int_as_float(__builtin_amdgcn_ds_bpermute(oa_, __float_as_int(L.Sz)));
   const uint32_t pk = (uint32_t)__builtin_amdgcn_ds_bpermute(oa_, (int)L.pk);
   const int ikx = (int)((pk >> 3) & 3u), iky = (int)((pk >> 5) & 3u), ikz = (int)((pk >> 7) & 3u);
-  // TriangleIntersector::Intersect (nanort.h:1054-1150) up to the hit distance: tri_test's own operations on the owner's constants
   const uint32_t prim_i = tri.prim_id;
-  bool ok = PLAIN ? item_ : (item_ & (prim_i >= range0) & (prim_i < range1) & (prim_i != skip_prim));
-  const bool cull_i = PLAIN ? false : cull;
-  const T A0 = tri.p0[0] - o0, A1 = tri.p0[1] - o1, A2 = tri.p0[2] - o2;
-  const T B0 = tri.p1[0] - o0, B1 = tri.p1[1] - o1, B2 = tri.p1[2] - o2;
-  const T C0 = tri.p2[0] - o0, C1 = tri.p2[1] - o1, C2 = tri.p2[2] - o2;
-  const T Akz = sel3(A0, A1, A2, ikz), Bkz = sel3(B0, B1, B2, ikz), Ckz = sel3(C0, C1, C2, ikz);
-  const T Ax = sel3(A0, A1, A2, ikx) - sx * Akz;
-  const T Ay = sel3(A0, A1, A2, iky) - sy * Akz;
-  const T Bx = sel3(B0, B1, B2, ikx) - sx * Bkz;
-  const T By = sel3(B0, B1, B2, iky) - sy * Bkz;
-  const T Cx = sel3(C0, C1, C2, ikx) - sx * Ckz;
-  const T Cy = sel3(C0, C1, C2, iky) - sy * Ckz;
-  T U = Cx * By - Cy * Bx;
-  T V = Ax * Cy - Ay * Cx;
-  T W = Bx * Ay - By * Ax;
-  if (ok && (U == T(0) || V == T(0) || W == T(0))) { // nanort.h:1094-1107
-    const double CxBy = double(Cx) * double(By), CyBx = double(Cy) * double(Bx);
-    const double AxCy = double(Ax) * double(Cy), AyCx = double(Ay) * double(Cx);
-    const double BxAy = double(Bx) * double(Ay), ByAx = double(By) * double(Ax);
-    U = T(CxBy - CyBx);
-    V = T(AxCy - AyCx);
-    W = T(BxAy - ByAx);
-  }
-  const bool neg = (U < T(0)) | (V < T(0)) | (W < T(0));
-  const bool pos = (U > T(0)) | (V > T(0)) | (W > T(0));
-  ok = ok & !(neg & (cull_i | pos));
-  const T det = U + V + W;
-  ok = ok & !(det == T(0));
-  T tt_i = T(0), uu_i = T(0), vv_i = T(0);
-  if (ok) {
-    const T Az = sz * Akz, Bz = sz * Bkz, Cz = sz * Ckz;
-    const T D = U * Az + V * Bz + W * Cz;
-    const T rcp = T(1.0) / det;
-    tt_i = D * rcp;
-    uu_i = V * rcp;
-    vv_i = W * rcp;
-  }
+  const TriSolve<T> ts_ = tri_solve<T, PLAIN>(tri, item_, o0, o1, o2, sx, sy, sz, ikx, iky, ikz, range0, range1, skip_prim, cull); // (on the owner's constants)
+  const bool ok = ts_.ok;
+  const T tt_i = ts_.tt, uu_i = ts_.uu, vv_i = ts_.vv;
   // ... and back to the owners, record by record
   const unsigned long long okm_ = __ballot(ok);
   bool got_ = false;
@@ -941,6 +883,7 @@ __global__ __launch_bounds__(kTraverseBlock, (WIDTH == 4 && sizeof(T) == 4) ? NR
   const unsigned lane = lane_id();
   const unsigned gslot = blockIdx.x * kTraverseBlock + tid;
   const bool cull = a.cull_back_face != 0;
+  const LaneStack<SE, STACK, TraverseArgs<T>> stk = {a, tid, gslot};
 
   NRT_BATCH_TABLE_SETUP();
   Lane<T> L;
@@ -1073,7 +1016,7 @@ __global__ __launch_bounds__(kTraverseBlock, (WIDTH == 4 && sizeof(T) == 4) ? NR
           } else { // single-leaf tree: test the root box, then its primitives
             const Node root = a.nodes[0];
             const bool root_hit = slab_test<T>(L, root.bmin, root.bmax);
-            cur = a.packed_leaves ? (((root.data[0] - 1u) << kPackedFirstBits) | root.data[1]) : 0u;
+            cur = a.packed_leaves ? packed_leaf_ref(root.data[0], root.data[1]) : 0u;
             state = root_hit ? W_LEAF : W_POP; // W_POP with sp == 0 finishes the ray
           }
           if (a.debug_flags & 2u) state = W_POP;
@@ -1126,7 +1069,7 @@ __global__ __launch_bounds__(kTraverseBlock, (WIDTH == 4 && sizeof(T) == 4) ? NR
       // a lane that must pop does so first and, if the popped entry survives, steps into it in the same iteration
 #pragma unroll
       for (int u_ = 0; u_ < ((WIDTH == 4 && sizeof(T) == 4 && !STATS) ? NRT_W4_P1_UNROLL : ((WIDTH == 2 && sizeof(T) == 8 && !STATS) ? NRT_W2_F64_P1_UNROLL : 1)); u_++) { // (several pop + step rounds per trip: the loop's own bookkeeping — two ballots, the exit test — runs once per trip)
-      if (state == W_POP) NRT_POP_ENTRY();
+      if (state == W_POP) NRT_POP_ENTRY(stk);
       if (state == W_TRAV) {
         if (STATS) st_steps++;
         if constexpr (WIDTH == 4) {
@@ -1214,16 +1157,7 @@ __global__ __launch_bounds__(kTraverseBlock, (WIDTH == 4 && sizeof(T) == 4) ? NR
     const bool refill_due = !ck.exhausted && (unsigned)__builtin_popcountll(__ballot(state == W_IDLE)) >= a.refill_min;
     if (n_leaf != 0u && !(n_leaf < a.leaf_min && refill_due)) {
       uint32_t cnt = 0, first = 0;
-      if (state == W_LEAF) {
-        if (a.packed_leaves) {
-          cnt = (cur >> kPackedFirstBits) + 1u;
-          first = cur & kPackedFirstMask;
-        } else {
-          const Node *nd = a.nodes + cur;
-          cnt = nd->data[0];
-          first = nd->data[1];
-        }
-      }
+      if (state == W_LEAF) leaf_span(a.packed_leaves, a.nodes, cur, cnt, first);
       if (a.debug_flags & 1u) cnt = 0;
       if (STATS) {
         st_entries2++;
@@ -1301,11 +1235,11 @@ __global__ __launch_bounds__(kTraverseBlock, (WIDTH == 4 && sizeof(T) == 4) ? NR
     // No rays are left to hand out and at most a.tail_lanes lanes of this wave still hold one (tunable tail_quad): what the launch
     // waits for from here on is the dependent chain of those rays, ~200 wave instructions a step of which a handful of lanes use
     // anything.  The wave's own idle lanes shorten the step instead.  Live ray number q (ballot rank) moves to quad q — its
-    // constants and state by ds_bpermute, its stack stays where it is: the quad addresses its owner's column of s_stack and of
-    // the spill arrays — and the quads finish the rays: lane j tests box j of a record (slab4_presel's arithmetic, operation for
-    // operation) and ranks its slot in the binary loop's order (NRT_STEP_NODE4_SL), two DPP quad permutes combine the four hit
-    // bits, the first hit in rank order is entered and the others are pushed in reverse rank order with their t_min; at a leaf
-    // lane j tests record i + j (tri_test's operations on the same operands) and the four results are accepted IN RECORD ORDER
+    // constants and state by ds_bpermute, its stack stays where it is: the quad pops and pushes through a LaneStack over its
+    // owner's column (`ostk_`; the pop is NRT_POP_ENTRY itself) — and the quads finish the rays: lane j tests box j of a record
+    // (slab_axis on the rows slab4_presel fetches) and ranks its slot in the binary loop's order (NRT_STEP_NODE4_SL), two DPP quad
+    // permutes combine the four hit bits, the first hit in rank order is entered and the others are pushed in reverse rank order
+    // with their t_min; at a leaf lane j tests record i + j (tri_solve, as tri_test) and the four results are accepted IN RECORD ORDER
     // through the reference's rule (nanort.h:1133-1139), every lane following the sequence on its copy of the hit distance; u, v
     // and the primitive stay with the lane that tested the accepted record (`owner_`), which writes the result.  Every ray sees
     // the pops, steps and leaf tests its lane would have continued with, in the same order: records bit-identical
@@ -1352,31 +1286,16 @@ __global__ __launch_bounds__(kTraverseBlock, (WIDTH == 4 && sizeof(T) == 4) ? NR
       state = has_ ? state : W_IDLE; // (a lane waiting at a leaf stays waiting at that leaf)
       rid = has_ ? rid : kInvalid;
       sp = has_ ? sp : 0;
-      const unsigned otid_ = (tid & ~63u) | src_;                   // the owner's column of s_stack
-      const unsigned ogslot_ = blockIdx.x * kTraverseBlock + otid_; // ... and of the spill arrays
+      const unsigned otid_ = (tid & ~63u) | src_; // the owner's column of s_stack, and of the spill arrays: the stack of the ray this quad took
+      const LaneStack<SE, STACK, TraverseArgs<T>> ostk_ = {a, otid_, blockIdx.x * kTraverseBlock + otid_};
       bool owner_ = j_ == 0u; // this lane holds u, v, prim of the ray's best hit (exactly one lane of a quad)
       const char *wb_ = reinterpret_cast<const char *>(a.wide4);
       for (;;) {
         const unsigned long long liveq_ = __ballot(state != W_IDLE);
         NRT_CLOCK_LIVE((unsigned)__builtin_popcountll(liveq_) >> 2);
         if (liveq_ == 0ull) break;
-        if (state == W_POP) { // NRT_POP_ENTRY, every lane of the quad alike
-          int s1_ = sp - 1;
-          s1_ = s1_ < 0 ? 0 : s1_;
-          const int sl_ = s1_ > STACK - 1 ? STACK - 1 : s1_;
-          typename SE::type e_ = s_stack[sl_][otid_];
-          if (s1_ >= STACK) {
-            const size_t o_ = (size_t)(s1_ - STACK) * a.spill_stride + ogslot_;
-            e_ = SE::make(a.spill[o_], a.spill_tmin[o_]);
-          }
-          const bool fin_ = (sp == 0);
-          const bool enter_ = !fin_ & (SE::tmin(e_) <= L.hit_t);
-          const uint32_t ref_ = SE::ref(e_);
-          sp = s1_;
-          cur = enter_ ? (ref_ & ~kLeafBit) : cur;
-          state = fin_ ? W_IDLE : (enter_ ? ((ref_ & kLeafBit) ? W_LEAF : W_TRAV) : W_POP);
-        }
-        if (state == W_TRAV) { // NRT_STEP_NODE4_SL over slab4_presel's arithmetic, slot j in lane j
+        if (state == W_POP) NRT_POP_ENTRY(ostk_); // (every lane of the quad alike)
+        if (state == W_TRAV) { // NRT_STEP_NODE4_SL's order over the rows slab4_presel fetches, slot j in lane j
           const uint32_t rec0_ = cur << 7, rec_ = rec0_ + 4u * j_, rec48_ = rec_ + 48u;
           const float lo0 = *reinterpret_cast<const float *>(wb_ + (size_t)(rec_ + L.so0));
           const float hi0 = *reinterpret_cast<const float *>(wb_ + (size_t)(rec48_ - L.so0));
@@ -1387,26 +1306,10 @@ __global__ __launch_bounds__(kTraverseBlock, (WIDTH == 4 && sizeof(T) == 4) ? NR
           const uint32_t c_ = *reinterpret_cast<const uint32_t *>(wb_ + (size_t)rec_ + 96);
           const int ax0_ = *reinterpret_cast<const int32_t *>(wb_ + (size_t)rec0_ + 112);
           const int axh_ = *reinterpret_cast<const int32_t *>(wb_ + (size_t)(rec0_ + 4u * (j_ >> 1)) + 116); // axis1 for slots 0, 1; axis2 for slots 2, 3
-          const float mm = Const<float>::maxmult();
           float tmin = L.min_t, tmax = L.hit_t;
-          {
-            const float t0 = (lo0 - L.org0) * L.inv0;
-            const float t1 = ((hi0 - L.org0) * L.inv0) * mm;
-            tmin = Const<float>::fmax(t0, tmin); // see slab_test
-            tmax = Const<float>::fmin(t1, tmax);
-          }
-          {
-            const float t0 = (lo1 - L.org1) * L.inv1;
-            const float t1 = ((hi1 - L.org1) * L.inv1) * mm;
-            tmin = Const<float>::fmax(t0, tmin);
-            tmax = Const<float>::fmin(t1, tmax);
-          }
-          {
-            const float t0 = (lo2 - L.org2) * L.inv2;
-            const float t1 = ((hi2 - L.org2) * L.inv2) * mm;
-            tmin = Const<float>::fmax(t0, tmin);
-            tmax = Const<float>::fmin(t1, tmax);
-          }
+          slab_axis<float>(lo0, hi0, L.org0, L.inv0, tmin, tmax);
+          slab_axis<float>(lo1, hi1, L.org1, L.inv1, tmin, tmax);
+          slab_axis<float>(lo2, hi2, L.org2, L.inv2, tmin, tmax);
           const bool h_ = (tmin <= tmax) & (((j_ & 1u) == 0u) | (c_ != kWide4Empty)); // (slots 1 and 3 can be empty)
           // rank of slot j in the binary loop's order: the near half (by the node's axis) first, inside a half its near slot first
           const uint32_t s0_ = (uint32_t)L.sign(ax0_), sh_ = (uint32_t)L.sign(axh_);
@@ -1415,16 +1318,7 @@ __global__ __launch_bounds__(kTraverseBlock, (WIDTH == 4 && sizeof(T) == 4) ? NR
           const uint32_t n_ = (uint32_t)__builtin_popcount(m_);
           const uint32_t pos_ = (uint32_t)__builtin_popcount(m_ & ((1u << rank_) - 1u)); // hits before mine
           // the first hit in rank order is entered; the others are pushed in reverse rank order (they pop in rank order)
-          if (h_ && pos_ != 0u) {
-            const int at_ = sp + (int)(n_ - 1u - pos_);
-            if (at_ < STACK) {
-              s_stack[at_][otid_] = SE::make(c_, tmin);
-            } else {
-              const size_t o_ = (size_t)(at_ - STACK) * a.spill_stride + ogslot_;
-              a.spill[o_] = c_;
-              a.spill_tmin[o_] = tmin;
-            }
-          }
+          if (h_ && pos_ != 0u) NRT_STACK_STORE(ostk_, sp + (int)(n_ - 1u - pos_), c_, tmin);
           __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); // (what one lane of the quad pushed, the four pop: program order holds across lanes)
           sp += n_ != 0u ? (int)(n_ - 1u) : 0;
           const uint32_t next_ = quad_or((h_ && pos_ == 0u) ? c_ : 0u); // (a reference is never 0: record 0 is the root)
@@ -1433,59 +1327,15 @@ __global__ __launch_bounds__(kTraverseBlock, (WIDTH == 4 && sizeof(T) == 4) ? NR
         }
         if (__ballot(state == W_LEAF) != 0ull) { // records i .. i + 3 per trip, any count
           uint32_t cnt = 0, first = 0;
-          if (state == W_LEAF) {
-            if (a.packed_leaves) {
-              cnt = (cur >> kPackedFirstBits) + 1u;
-              first = cur & kPackedFirstMask;
-            } else {
-              const Node *nd = a.nodes + cur;
-              cnt = nd->data[0];
-              first = nd->data[1];
-            }
-          }
+          if (state == W_LEAF) leaf_span(a.packed_leaves, a.nodes, cur, cnt, first);
           if (a.debug_flags & 1u) cnt = 0;
           for (uint32_t i = 0; __ballot(i < cnt) != 0ull; i += 4u) {
             const bool act_ = i + j_ < cnt;
             const LeafTri<T> tri = a.tris[first + (act_ ? i + j_ : 0u)];
-            // TriangleIntersector::Intersect (nanort.h:1054-1150) up to the hit distance: tri_test's own operations
             const uint32_t prim_i = tri.prim_id;
-            bool ok = PLAIN ? act_ : (act_ & (prim_i >= a.range0) & (prim_i < a.range1) & (prim_i != a.skip_prim));
-            const bool cull_i = PLAIN ? false : cull;
-            const T A0 = tri.p0[0] - L.org0, A1 = tri.p0[1] - L.org1, A2 = tri.p0[2] - L.org2;
-            const T B0 = tri.p1[0] - L.org0, B1 = tri.p1[1] - L.org1, B2 = tri.p1[2] - L.org2;
-            const T C0 = tri.p2[0] - L.org0, C1 = tri.p2[1] - L.org1, C2 = tri.p2[2] - L.org2;
-            const T Akz = sel3(A0, A1, A2, L.kz()), Bkz = sel3(B0, B1, B2, L.kz()), Ckz = sel3(C0, C1, C2, L.kz());
-            const T Ax = sel3(A0, A1, A2, L.kx()) - L.Sx * Akz;
-            const T Ay = sel3(A0, A1, A2, L.ky()) - L.Sy * Akz;
-            const T Bx = sel3(B0, B1, B2, L.kx()) - L.Sx * Bkz;
-            const T By = sel3(B0, B1, B2, L.ky()) - L.Sy * Bkz;
-            const T Cx = sel3(C0, C1, C2, L.kx()) - L.Sx * Ckz;
-            const T Cy = sel3(C0, C1, C2, L.ky()) - L.Sy * Ckz;
-            T U = Cx * By - Cy * Bx;
-            T V = Ax * Cy - Ay * Cx;
-            T W = Bx * Ay - By * Ax;
-            if (ok && (U == T(0) || V == T(0) || W == T(0))) { // nanort.h:1094-1107
-              const double CxBy = double(Cx) * double(By), CyBx = double(Cy) * double(Bx);
-              const double AxCy = double(Ax) * double(Cy), AyCx = double(Ay) * double(Cx);
-              const double BxAy = double(Bx) * double(Ay), ByAx = double(By) * double(Ax);
-              U = T(CxBy - CyBx);
-              V = T(AxCy - AyCx);
-              W = T(BxAy - ByAx);
-            }
-            const bool neg = (U < T(0)) | (V < T(0)) | (W < T(0));
-            const bool pos = (U > T(0)) | (V > T(0)) | (W > T(0));
-            ok = ok & !(neg & (cull_i | pos));
-            const T det = U + V + W;
-            ok = ok & !(det == T(0));
-            T tt_i = T(0), uu_i = T(0), vv_i = T(0);
-            if (ok) {
-              const T Az = L.Sz * Akz, Bz = L.Sz * Bkz, Cz = L.Sz * Ckz;
-              const T D = U * Az + V * Bz + W * Cz;
-              const T rcp = T(1.0) / det;
-              tt_i = D * rcp;
-              uu_i = V * rcp;
-              vv_i = W * rcp;
-            }
+            const TriSolve<T> ts_ = tri_solve<T, PLAIN>(tri, act_, L.org0, L.org1, L.org2, L.Sx, L.Sy, L.Sz, L.kx(), L.ky(), L.kz(), a.range0, a.range1, a.skip_prim, cull);
+            const bool ok = ts_.ok;
+            const T tt_i = ts_.tt, uu_i = ts_.uu, vv_i = ts_.vv;
             // ... accepted in record order, the same sequence in every lane of the quad
             const uint32_t okm_ = quad_or(ok ? (1u << j_) : 0u);
             if (__ballot(okm_ != 0u) != 0ull) {
@@ -1625,6 +1475,7 @@ __global__ __launch_bounds__(kTraverseBlock) void k_scene_trace(const SceneTrace
   const unsigned tid = threadIdx.x;
   const unsigned lane = lane_id();
   const unsigned gslot = blockIdx.x * kTraverseBlock + tid;
+  const LaneStack<SE, STACK, SceneTraceArgs> stk = {a, tid, gslot};
 
   // Persistent threads: a lane whose ray is finished takes the next one from a work cursor (claimed for the whole wave by
   // one atomic once `refill_min` lanes are free), so a wave keeps its lanes busy to the end of the batch instead of
@@ -1801,7 +1652,7 @@ __global__ __launch_bounds__(kTraverseBlock) void k_scene_trace(const SceneTrace
             if (nd.root_is_branch) {
               state = root_hit ? W_TRAV : W_POP;
             } else { // single-leaf tree
-              cur = packed ? (((root.data[0] - 1u) << kPackedFirstBits) | root.data[1]) : 0u;
+              cur = packed ? packed_leaf_ref(root.data[0], root.data[1]) : 0u;
               state = root_hit ? W_LEAF : W_POP;
             }
           }
@@ -1821,7 +1672,7 @@ __global__ __launch_bounds__(kTraverseBlock) void k_scene_trace(const SceneTrace
 #pragma unroll
       for (int u_ = 0; u_ < NRT_SCENE_P1_UNROLL; u_++) { // (pop + step rounds per trip, as in k_traverse_wide)
       if (state == W_POP) {
-        NRT_POP_ENTRY();
+        NRT_POP_ENTRY(stk);
         state = (state == W_IDLE) ? S_FIN : state; // an empty stack ends this instance's walk
       }
       if (state == W_TRAV) {
@@ -1841,15 +1692,7 @@ __global__ __launch_bounds__(kTraverseBlock) void k_scene_trace(const SceneTrace
     // ---- phase 2: leaves -----------------------------------------------------------------------------------------
     if (__ballot(state == W_LEAF) != 0ull) {
       uint32_t lcnt = 0, first = 0;
-      if (state == W_LEAF) {
-        if (packed) {
-          lcnt = (cur >> kPackedFirstBits) + 1u;
-          first = cur & kPackedFirstMask;
-        } else {
-          lcnt = nodes[cur].data[0];
-          first = nodes[cur].data[1];
-        }
-      }
+      if (state == W_LEAF) leaf_span(packed, nodes, cur, lcnt, first);
       for (uint32_t k = 0; __ballot(k < lcnt) != 0ull; k += 2u) { // two records per trip, as in k_traverse_wide
         if (k < lcnt) { // (divergent on purpose: the lanes' record arrays differ)
           const bool two = k + 1u < lcnt;
@@ -1942,12 +1785,8 @@ enum : int { T_ENTER = 7, S_END = 8 }; // a top-level leaf was reached: open its
 do {                                                                                                 \
   const bool fin_ = (sp <= base);                     /* this level's part of the stack is empty */  \
   const int s1_ = fin_ ? sp : sp - 1;                                                                \
-  const int sr_ = s1_ > 0 ? s1_ : 0;                                                                 \
-  typename SE::type e_ = s_stack[sr_ < STACK ? sr_ : STACK - 1][tid];                                \
-  if (!fin_ && s1_ >= STACK) {                                                                       \
-    const size_t o_ = (size_t)(s1_ - STACK) * a.spill_stride + gslot;                                \
-    e_ = SE::make(a.spill[o_], a.spill_tmin[o_]);                                                    \
-  }                                                                                                  \
+  typename SE::type e_;                                                                              \
+  stk.load(s_stack, s1_ > 0 ? s1_ : 0, e_, !fin_); /* (fin_: entry sp is nobody's) */                 \
   const bool enter_ = !fin_ & (SE::tmin(e_) <= (in_top ? cull_t : L.hit_t));                         \
   const uint32_t ref_ = SE::ref(e_);                                                                 \
   sp = s1_;                                                                                          \
@@ -1970,6 +1809,7 @@ __global__ __launch_bounds__(kTraverseBlock, STATS ? 1 : NRT_SCENE_WALK_WAVES) v
   const unsigned tid = threadIdx.x;
   const unsigned lane = lane_id();
   const unsigned gslot = blockIdx.x * kTraverseBlock + tid;
+  const LaneStack<SE, STACK, SceneWalkArgs> stk = {a, tid, gslot};
 
   Lane<float> L;
   uint32_t i = 0;   // this lane's ray
@@ -2139,8 +1979,8 @@ __global__ __launch_bounds__(kTraverseBlock, STATS ? 1 : NRT_SCENE_WALK_WAVES) v
         } else if (state == T_ENTER) {
           // cur: a leaf reference of the top-level tree, (count - 1, first) into its index array.  One instance is opened now;
           // the others of a leaf of several (boxes the builder could not separate) wait on the stack as a leaf of one fewer.
-          const uint32_t lcount = (cur >> kPackedFirstBits) + 1u, lfirst = cur & kPackedFirstMask;
-          if (lcount > 1u) NRT_PUSH_IF(true, kLeafBit | ((lcount - 2u) << kPackedFirstBits) | (lfirst + 1u), -__builtin_huge_valf());
+          const uint32_t lcount = packed_leaf_count(cur), lfirst = packed_leaf_first(cur);
+          NRT_PUSH_IF(lcount > 1u, kLeafBit | packed_leaf_ref(lcount - 1u, lfirst + 1u), -__builtin_huge_valf());
           const SceneOpen &nd = a.open_top[lfirst]; // (everything the opening needs in one 128-byte line: id, world box, matrices, mesh)
           const uint32_t k = nd.id;
           const float bx[6] = {nd.xbmin[0], nd.xbmin[1], nd.xbmin[2], nd.xbmax[0], nd.xbmax[1], nd.xbmax[2]};
@@ -2274,8 +2114,8 @@ __global__ __launch_bounds__(kTraverseBlock, STATS ? 1 : NRT_SCENE_WALK_WAVES) v
     if (__ballot(state == W_LEAF) != 0ull) {
       uint32_t lcnt = 0, first = 0;
       if (state == W_LEAF) { // (packed leaf references: scene.hip checks)
-        lcnt = (cur >> kPackedFirstBits) + 1u;
-        first = cur & kPackedFirstMask;
+        lcnt = packed_leaf_count(cur);
+        first = packed_leaf_first(cur);
       }
       // (few lanes wait at a leaf in this kernel — 10 of 64 on the instanced scenes: their records nearly always fit one trip)
       const bool items_done_ = !STATS && a.leaf_items != 0u &&
@@ -2417,8 +2257,8 @@ __global__ __launch_bounds__(256) void k_make_wide(const typename Wire<T>::Node 
       w.box1[3 + k] = b.bmax[k];
     }
   }
-  const uint32_t la = packed ? (((a.data[0] - 1u) << kPackedFirstBits) | a.data[1]) : nd.data[0];
-  const uint32_t lb = packed ? (((b.data[0] - 1u) << kPackedFirstBits) | b.data[1]) : nd.data[1];
+  const uint32_t la = packed ? packed_leaf_ref(a.data[0], a.data[1]) : nd.data[0];
+  const uint32_t lb = packed ? packed_leaf_ref(b.data[0], b.data[1]) : nd.data[1];
   w.c0 = a.flag != 0 ? (kLeafBit | la) : dense_of[nd.data[0]];
   w.c1 = b.flag != 0 ? (kLeafBit | lb) : dense_of[nd.data[1]];
   w.axis = nd.axis;
@@ -2446,7 +2286,7 @@ __global__ __launch_bounds__(256) void k_make_wide(const typename Wire<T>::Node 
           q.bmin[k][2 * h + j] = g.bmin[k];
           q.bmax[k][2 * h + j] = g.bmax[k];
         }
-        const uint32_t lg = packed ? (((g.data[0] - 1u) << kPackedFirstBits) | g.data[1]) : gi;
+        const uint32_t lg = packed ? packed_leaf_ref(g.data[0], g.data[1]) : gi;
         q.c[2 * h + j] = g.flag != 0 ? (kLeafBit | lg) : dense_of[gi];
       }
     } else { // a leaf child (or a branch whose children cannot be read: then it is entered through its own record)

@@ -131,47 +131,62 @@ __device__ __forceinline__ void lane_init(Lane<T> &L, const typename Wire<T>::Ra
   L.inv2 = safe_inverse<T>(d2);
 }
 
-// IntersectRayAABB (nanort.h:2285-2370); safemin/safemax (nanort.h:1236-1243).
+// One axis of IntersectRayAABB (nanort.h:2285-2370): the near plane `lo` and the far plane `hi` (chosen by the ray's direction
+// sign) narrow the interval.  safemax(t0, tmin) / safemin(t1, tmax) (nanort.h:1236-1243): a NaN first operand is dropped and the
+// running value is never NaN, which is exactly maxNum/minNum (v_max_f32 / v_min_f32); the only difference, the sign of a zero
+// result, cannot change `tmin <= tmax`.  (The packed two-box forms of traverse.hip write the same operations over register pairs.)
 template <typename T>
-__device__ __forceinline__ bool slab_test(const Lane<T> &L, const T bmin[3], const T bmax[3]) {
-  const T mm = Const<T>::maxmult();
+__device__ __forceinline__ void slab_axis(T lo, T hi, T org, T inv, T &tmin, T &tmax) {
+  const T t0 = (lo - org) * inv;
+  const T t1 = ((hi - org) * inv) * Const<T>::maxmult();
+  tmin = Const<T>::fmax(t0, tmin);
+  tmax = Const<T>::fmin(t1, tmax);
+}
+
+// IntersectRayAABB (nanort.h:2285-2370) over a box given as {bmin[3], bmax[3]}; `tmin_out`: where the ray enters it.
+template <typename T>
+__device__ __forceinline__ bool slab_test_tmin(const Lane<T> &L, const T bmin[3], const T bmax[3], T &tmin_out) {
   T tmin = L.min_t, tmax = L.hit_t;
 #pragma unroll
   for (int k = 0; k < 3; k++) {
     const int sg = L.sign(k);
-    const T lo = sg ? bmax[k] : bmin[k];
-    const T hi = sg ? bmin[k] : bmax[k];
-    const T t0 = (lo - L.org(k)) * L.inv(k);
-    const T t1 = (hi - L.org(k)) * L.inv(k) * mm;
-    // safemax(t0, tmin) / safemin(t1, tmax) (nanort.h:1236-1243): a NaN first operand is dropped and the
-    // running value is never NaN, which is exactly maxNum/minNum (v_max_f32 / v_min_f32); the only
-    // difference, the sign of a zero result, cannot change `tmin <= tmax`.
-    tmin = Const<T>::fmax(t0, tmin);
-    tmax = Const<T>::fmin(t1, tmax);
+    slab_axis<T>(sg ? bmax[k] : bmin[k], sg ? bmin[k] : bmax[k], L.org(k), L.inv(k), tmin, tmax);
   }
+  tmin_out = tmin;
   return tmin <= tmax;
 }
+template <typename T>
+__device__ __forceinline__ bool slab_test(const Lane<T> &L, const T bmin[3], const T bmax[3]) {
+  T tmin;
+  return slab_test_tmin<T>(L, bmin, bmax, tmin);
+}
 
-// TriangleIntersector::Intersect (nanort.h:1054-1150) against one leaf record.
-// Written as one running predicate with select-style updates (the reference's early returns
-// in the same order): all loads of the record are issued together, and the lane state stays
-// in the same registers on every path.
+// TriangleIntersector::Intersect (nanort.h:1054-1150) against one leaf record, up to the hit distance and the barycentrics: every
+// reject of the reference in its own order, the accept rule (nanort.h:1133-1139) left to the caller.  The ray constants come as
+// VALUES — a lane's own (tri_test) or another lane's, fetched across the wave (leaf items, the tail of a launch): THE one
+// statement of this arithmetic.  Written as one running predicate with select-style updates: all loads of the record are issued
+// together, and the lane state stays in the same registers on every path.  PLAIN: trace options that cannot reject a primitive.
+template <typename T>
+struct TriSolve {
+  bool ok;      // the record passed every reject; tt, uu, vv are 0 otherwise
+  T tt, uu, vv; // hit distance, barycentrics
+};
 template <typename T, bool PLAIN = false>
-__device__ __forceinline__ void tri_test(Lane<T> &L, const LeafTri<T> &tri, bool active, uint32_t range0,
-                                         uint32_t range1, uint32_t skip, bool cull) {
+__device__ __forceinline__ TriSolve<T> tri_solve(const LeafTri<T> &tri, bool active, T org0, T org1, T org2, T Sx, T Sy, T Sz, int kx, int ky,
+                                                 int kz, uint32_t range0, uint32_t range1, uint32_t skip, bool cull) {
   const uint32_t prim = tri.prim_id;
   bool ok = PLAIN ? active : (active & (prim >= range0) & (prim < range1) & (prim != skip)); // nanort.h:2387-2395
   if (PLAIN) cull = false;
-  const T A0 = tri.p0[0] - L.org0, A1 = tri.p0[1] - L.org1, A2 = tri.p0[2] - L.org2;
-  const T B0 = tri.p1[0] - L.org0, B1 = tri.p1[1] - L.org1, B2 = tri.p1[2] - L.org2;
-  const T C0 = tri.p2[0] - L.org0, C1 = tri.p2[1] - L.org1, C2 = tri.p2[2] - L.org2;
-  const T Akz = sel3(A0, A1, A2, L.kz()), Bkz = sel3(B0, B1, B2, L.kz()), Ckz = sel3(C0, C1, C2, L.kz());
-  const T Ax = sel3(A0, A1, A2, L.kx()) - L.Sx * Akz;
-  const T Ay = sel3(A0, A1, A2, L.ky()) - L.Sy * Akz;
-  const T Bx = sel3(B0, B1, B2, L.kx()) - L.Sx * Bkz;
-  const T By = sel3(B0, B1, B2, L.ky()) - L.Sy * Bkz;
-  const T Cx = sel3(C0, C1, C2, L.kx()) - L.Sx * Ckz;
-  const T Cy = sel3(C0, C1, C2, L.ky()) - L.Sy * Ckz;
+  const T A0 = tri.p0[0] - org0, A1 = tri.p0[1] - org1, A2 = tri.p0[2] - org2;
+  const T B0 = tri.p1[0] - org0, B1 = tri.p1[1] - org1, B2 = tri.p1[2] - org2;
+  const T C0 = tri.p2[0] - org0, C1 = tri.p2[1] - org1, C2 = tri.p2[2] - org2;
+  const T Akz = sel3(A0, A1, A2, kz), Bkz = sel3(B0, B1, B2, kz), Ckz = sel3(C0, C1, C2, kz);
+  const T Ax = sel3(A0, A1, A2, kx) - Sx * Akz;
+  const T Ay = sel3(A0, A1, A2, ky) - Sy * Akz;
+  const T Bx = sel3(B0, B1, B2, kx) - Sx * Bkz;
+  const T By = sel3(B0, B1, B2, ky) - Sy * Bkz;
+  const T Cx = sel3(C0, C1, C2, kx) - Sx * Ckz;
+  const T Cy = sel3(C0, C1, C2, ky) - Sy * Ckz;
   T U = Cx * By - Cy * Bx;
   T V = Ax * Cy - Ay * Cx;
   T W = Bx * Ay - By * Ax;
@@ -188,18 +203,30 @@ __device__ __forceinline__ void tri_test(Lane<T> &L, const LeafTri<T> &tri, bool
   ok = ok & !(neg & (cull | pos));
   const T det = U + V + W;
   ok = ok & !(det == T(0));
+  TriSolve<T> r = {ok, T(0), T(0), T(0)};
   if (ok) { // skipped by the whole wave when no lane got this far
-    const T Az = L.Sz * Akz, Bz = L.Sz * Bkz, Cz = L.Sz * Ckz;
+    const T Az = Sz * Akz, Bz = Sz * Bkz, Cz = Sz * Ckz;
     const T D = U * Az + V * Bz + W * Cz;
     const T rcp = T(1.0) / det;
-    const T tt = D * rcp;
+    r.tt = D * rcp;
+    r.uu = V * rcp;
+    r.vv = W * rcp;
+  }
+  return r;
+}
+
+// ... against a lane's own ray, with the reference's accept rule.
+template <typename T, bool PLAIN = false>
+__device__ __forceinline__ void tri_test(Lane<T> &L, const LeafTri<T> &tri, bool active, uint32_t range0,
+                                         uint32_t range1, uint32_t skip, bool cull) {
+  const TriSolve<T> s = tri_solve<T, PLAIN>(tri, active, L.org0, L.org1, L.org2, L.Sx, L.Sy, L.Sz, L.kx(), L.ky(), L.kz(), range0, range1, skip, cull);
+  if (s.ok) {
     // `if (tt > t) return; if (tt < min_t) return;` — equality (and NaN) accepted (nanort.h:1133-1139)
-    const bool acc = !(tt > L.hit_t) & !(tt < L.min_t);
-    const T uu = V * rcp, vv = W * rcp;
-    L.hit_t = acc ? tt : L.hit_t;
-    L.u = acc ? uu : L.u;
-    L.v = acc ? vv : L.v;
-    L.prim = acc ? prim : L.prim;
+    const bool acc = !(s.tt > L.hit_t) & !(s.tt < L.min_t);
+    L.hit_t = acc ? s.tt : L.hit_t;
+    L.u = acc ? s.uu : L.u;
+    L.v = acc ? s.vv : L.v;
+    L.prim = acc ? tri.prim_id : L.prim;
   }
 }
 
@@ -669,6 +696,47 @@ __device__ __forceinline__ void done_end(const TraverseArgs<T> &a, unsigned lane
   __hip_atomic_store(&r->t_end, (unsigned long long)__builtin_amdgcn_s_memrealtime(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   __hip_atomic_store(&r->seq, a.done_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
+
+// A lane's traversal stack.  Entry i lies in the block's LDS array, lds[i][col], below STACK, and from there on in the launch's
+// global overflow arrays at (i - STACK) * spill_stride + gcol.  `col` / `gcol` name the column on both sides: a lane's own
+// (threadIdx.x, its global thread index) or, in the tail of a launch, the column of the lane whose ray a quad has taken over.
+// SE says what an entry is: StackRef here, StackEntry<T> (reference + t_min; the t_min half lies in spill_tmin) in traverse.hip;
+// A is the launch's argument block (spill, spill_stride and, for StackEntry, spill_tmin).  THE one statement of "entry i": every
+// guarded push and every pop of every walk goes through load / store.
+// (The block's LDS array is an argument of load / store, not a member: a pointer to LDS held in a struct reaches the code
+// generator as a generic pointer, and the pop becomes a flat load whose address is selected between LDS and global memory.)
+struct StackRef { // a bare node reference (the binary loops: k_traverse, k_traverse_multihit)
+  typedef uint32_t type;
+  static constexpr bool kHasTmin = false;
+};
+template <typename SE, int STACK, typename A>
+struct LaneStack {
+  typedef typename SE::type Entry;
+  const A &a;
+  unsigned col, gcol;
+  // where entry i >= STACK lies in the overflow arrays
+  __device__ __forceinline__ size_t spill_at(int i) const { return (size_t)(i - STACK) * a.spill_stride + gcol; }
+  // Entry i >= 0.  The LDS read is unconditional (of the last LDS entry when i lies beyond); the rare entry in the overflow arrays
+  // replaces it.  `live` false: the caller will not use the value (its stack is empty) and nothing beyond LDS is read.
+  __device__ __forceinline__ void load(const Entry (&lds)[STACK][kTraverseBlock], int i, Entry &e, bool live = true) const {
+    e = lds[i > STACK - 1 ? STACK - 1 : i][col];
+    if (live && i >= STACK) {
+      const size_t o = spill_at(i);
+      if constexpr (SE::kHasTmin)
+        e = SE::make(a.spill[o], a.spill_tmin[o]);
+      else
+        e = a.spill[o];
+    }
+  }
+  // (StackRef entries; a StackEntry is stored by traverse.hip's NRT_STACK_STORE, which says why it is a macro)
+  __device__ __forceinline__ void store(Entry (&lds)[STACK][kTraverseBlock], int i, uint32_t ref) const {
+    if (i < STACK) {
+      lds[i][col] = ref;
+    } else {
+      a.spill[spill_at(i)] = ref;
+    }
+  }
+};
 
 // Lane states of the while-while loop.
 enum : int { LANE_IDLE = 0, LANE_TRAV = 1, LANE_LEAF = 2 };

@@ -126,3 +126,51 @@ def is_reference_order_two_level_walk(kernel_name):
 def is_distance_order_two_level_walk(kernel_name):
     w, o = walk_order_bits(kernel_name)
     return w == 4 and (o & 1) == 1
+
+
+def first_leaf_stack_bound(nodes):
+    """Entries the two-level walk holds, at the least, when a ray that hits EVERY box reaches its first leaf: a step over a record
+    with k occupied slots pushes k - 1 and enters one; whichever slot the ray's signs rank first, the minimum over the slots bounds
+    it from below (nothing is culled before the first leaf: there is no hit yet)."""
+    leaf = nodes["flag"] != 0
+    kids = nodes["data"]
+    g = {}
+    todo = [0]
+    while todo:  # post-order without recursion
+        i = todo[-1]
+        slots = []
+        for c in kids[i]:
+            slots += [int(c)] if leaf[c] else [int(x) for x in kids[c]]
+        missing = [s for s in slots if not leaf[s] and s not in g]
+        if missing:
+            todo += missing
+            continue
+        g[i] = len(slots) - 1 + min(0 if leaf[s] else g[s] for s in slots)
+        todo.pop()
+    return g[0]
+
+
+def deep_stack_case(n_rays=1500, nt=6144, ndup=2048, seed=11):
+    """A pile of nt large triangles that all straddle the z axis plus `ndup` exact duplicates (of the two that the rays hit first
+    and of random others), and n_rays rays along that axis, alternately from z = -5 and z = +5, through |x|, |y| < 0.3.  Built with
+    min_leaf_primitives = 1, every box of the pile's tree is hit by every ray: every two-level step pushes three entries and the
+    walk's stack passes its LDS entries into the spill arrays (the tests establish both from the built tree: the boxes, and
+    first_leaf_stack_bound).  Returns (verts, faces, dup, nt, rays): faces nt.. are the duplicates of faces dup."""
+    from nanort_amd import scenes
+
+    rng = np.random.default_rng(seed)
+    z = rng.uniform(-0.5, 0.5, nt).astype(np.float32)
+    base = np.array([[-1.0, -1.0], [1.0, -1.0], [0.0, 1.5]], dtype=np.float32)
+    v = np.zeros((nt, 3, 3), dtype=np.float32)
+    v[:, :, :2] = base[None] + rng.uniform(-0.1, 0.1, (nt, 3, 2)).astype(np.float32)
+    v[:, :, 2] = z[:, None]
+    v = v.reshape(-1, 3)
+    f = np.arange(3 * nt, dtype=np.uint32).reshape(nt, 3)
+    dup = np.concatenate([[int(np.argmin(z)), int(np.argmax(z))], rng.integers(0, nt, ndup - 2)])  # (the two triangles the rays hit first among them)
+    f = np.concatenate([f, f[dup]]).astype(np.uint32)  # exact duplicates
+    rays = np.zeros(n_rays, dtype=scenes.camera_rays(2, 2).dtype)
+    rays["org"][:, :2] = rng.uniform(-0.3, 0.3, (n_rays, 2))
+    rays["org"][:, 2] = np.where(np.arange(n_rays) % 2 == 0, -5.0, 5.0)
+    rays["dir"][:, 2] = -np.sign(rays["org"][:, 2])
+    rays["max_t"] = np.finfo(np.float32).max
+    return v, f, dup, nt, rays

@@ -452,3 +452,53 @@ def test_walk_opens_one_leaf_meshes_too(oracle):
     h0, m0 = sc.TraverseBatch(rays)
     assert sc.LastPath() == 0
     assert np.array_equal(m0, om) and fields_equal(h0, oh, ("t", "u", "v", "prim_id", "node_id"))
+
+
+def test_local_walk_spills_past_the_lds_stack(oracle):
+    """A local walk deeper than the single-pass walk's LDS stack: two instances (identity, a translation) of the pile of
+    test_gpu_tail_quad.test_deep_stack_spills_and_ties, rays along the z axis through both.  Every box of the pile's tree is hit by
+    every ray in either instance's space, so the walk to the first leaf holds at least first_leaf_stack_bound entries above the
+    top-level ones: more than the 16 the walk keeps in LDS — its pushes and pops beyond go through the spill arrays.  Every field
+    equals the listing path's and the restatement's; the walk (not the listing path) did the work."""
+    from helpers import deep_stack_case, first_leaf_stack_bound
+    from nanort_amd.wire import default_build_options
+
+    shifts = ((0.0, 0.0, 0.0), (0.25, -0.2, 2.0))
+    bo = default_build_options()
+    bo["min_leaf_primitives"] = 1
+    # That test's pile of 8192 triangles passes ITS 12 entries (bound 14); this walk keeps 16: the same pile, doubled until its
+    # tree says so.  (Bounds of the trees built here: 14 at 8192 triangles, 15 at 16384 and 32768, 16 at 65536.)
+    for nt in (6144 << k for k in range(9)):
+        v, f, _, _, rays = deep_stack_case(nt=nt, ndup=nt // 3)
+        a = BVHAccel(np.float32)
+        assert a.Build(f.shape[0], TriangleMesh(v, f), bo)
+        nodes, idx = a.GetTree()
+        bound = first_leaf_stack_bound(nodes)
+        print("pile of %d triangles: first-leaf stack bound %d" % (f.shape[0], bound))
+        if bound > 16:
+            break
+    assert bound > 16
+    for dx, dy, dz in shifts:  # the rays in this instance's space: inside every box in x, y; spanning all of them in z
+        x, y = rays["org"][:, 0] - dx, rays["org"][:, 1] - dy
+        assert nodes["bmin"][:, 0].max() < x.min() and nodes["bmax"][:, 0].min() > x.max()
+        assert nodes["bmin"][:, 1].max() < y.min() and nodes["bmax"][:, 1].min() > y.max()
+        assert nodes["bmin"][:, 2].min() + dz > -5.0 and nodes["bmax"][:, 2].max() + dz < 5.0
+    sc = Scene()
+    O = ob.SceneOracle(oracle)
+    for t in shifts:
+        x = xform(trans=t)
+        sc.AddNode(a, x)
+        O.add_node(v, f, x, tree=(nodes, idx))
+    assert sc.Commit() and O.commit()
+    oh, om = O.traverse(rays)
+    assert om.all()
+    keys = ("t", "u", "v", "prim_id", "node_id")
+    sc.SetTunable("single_pass", 2)
+    h, m = sc.TraverseBatch(rays)
+    assert sc.LastPath() == 1 and sc.LastRedone() < len(rays)
+    sc.SetTunable("single_pass", 0)
+    h0, m0 = sc.TraverseBatch(rays)
+    assert sc.LastPath() == 0
+    assert np.array_equal(m, m0) and fields_equal(h, h0, keys)
+    assert np.array_equal(m, om) and fields_equal(h, oh, keys)
+    assert set(int(k) for k in h["node_id"]) == {0, 1}  # rays from either side: each instance is the near one for half of them

@@ -6,7 +6,7 @@ where the oracle covers the case, to the restated reference's on the same node a
 import numpy as np
 import pytest
 
-from helpers import assert_hits_identical
+from helpers import assert_hits_identical, deep_stack_case, first_leaf_stack_bound
 from nanort_amd import BVHAccel, TriangleMesh, scenes
 from nanort_amd.wire import default_build_options, default_trace_options
 
@@ -61,55 +61,17 @@ def test_batch_sizes(oracle, c1_mesh):
     assert_hits_identical(oh, om, h, m)
 
 
-def first_leaf_stack_bound(nodes):
-    """Entries the two-level walk holds, at the least, when a ray that hits EVERY box reaches its first leaf: a step over a record
-    with k occupied slots pushes k - 1 and enters one; whichever slot the ray's signs rank first, the minimum over the slots bounds
-    it from below (nothing is culled before the first leaf: there is no hit yet)."""
-    leaf = nodes["flag"] != 0
-    kids = nodes["data"]
-    g = {}
-    todo = [0]
-    while todo:  # post-order without recursion
-        i = todo[-1]
-        slots = []
-        for c in kids[i]:
-            slots += [int(c)] if leaf[c] else [int(x) for x in kids[c]]
-        missing = [s for s in slots if not leaf[s] and s not in g]
-        if missing:
-            todo += missing
-            continue
-        g[i] = len(slots) - 1 + min(0 if leaf[s] else g[s] for s in slots)
-        todo.pop()
-    return g[0]
-
-
 def test_deep_stack_spills_and_ties(oracle):
     """A pile of 8192 large triangles that all straddle the z axis (a quarter of them exact duplicates of others), rays along that
     axis: every box of the tree is hit, so every step pushes three entries and the stack passes its 12 LDS entries into the spill
     arrays — established from the built tree itself: every box is hit by the rays (slab test below) and first_leaf_stack_bound
     exceeds 12.  Exact-t ties (the duplicates) are decided by record order."""
-    rng = np.random.default_rng(11)
-    nt = 6144
-    z = rng.uniform(-0.5, 0.5, nt).astype(np.float32)
-    base = np.array([[-1.0, -1.0], [1.0, -1.0], [0.0, 1.5]], dtype=np.float32)
-    v = np.zeros((nt, 3, 3), dtype=np.float32)
-    v[:, :, :2] = base[None] + rng.uniform(-0.1, 0.1, (nt, 3, 2)).astype(np.float32)
-    v[:, :, 2] = z[:, None]
-    v = v.reshape(-1, 3)
-    f = np.arange(3 * nt, dtype=np.uint32).reshape(nt, 3)
-    dup = np.concatenate([[int(np.argmin(z)), int(np.argmax(z))], rng.integers(0, nt, 2046)])  # (the two triangles the rays hit first among them)
-    f = np.concatenate([f, f[dup]]).astype(np.uint32)  # exact duplicates
+    v, f, dup, nt, rays = deep_stack_case()
     a = BVHAccel(np.float32)
     bo = default_build_options()
     bo["min_leaf_primitives"] = 1
     assert a.Build(f.shape[0], TriangleMesh(v, f), bo)
     nodes, idx = a.GetTree()
-    n = 1500
-    rays = np.zeros(n, dtype=scenes.camera_rays(2, 2).dtype)
-    rays["org"][:, :2] = rng.uniform(-0.3, 0.3, (n, 2))
-    rays["org"][:, 2] = np.where(np.arange(n) % 2 == 0, -5.0, 5.0)
-    rays["dir"][:, 2] = -np.sign(rays["org"][:, 2])
-    rays["max_t"] = np.finfo(np.float32).max
     # every ray passes through every node's box (x, y inside, the ray spans all of z) ...
     assert (nodes["bmin"][:, :2].max(axis=0) < -0.3).all() and (nodes["bmax"][:, :2].min(axis=0) > 0.3).all()
     assert nodes["bmin"][:, 2].min() > -5.0 and nodes["bmax"][:, 2].max() < 5.0
