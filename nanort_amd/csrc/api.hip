@@ -42,7 +42,7 @@ struct nrt_ctx {
   int prim_kind = kPrimTriangles; // kPrimSpheres: d_verts = centres, d_radii = radii, no faces; kPrimCylinders: d_verts = 2 end points, d_radii = 2 radii per primitive; kPrimCurves: d_verts = 4 control points, d_radii = 4 radii per primitive
   uint32_t cyl_test_cap = 1;
   uint32_t curve_subdiv = 4; // curves: line segments per curve (the intersector's num_subdivisions; nrtSetCurves)
-  // cylinders cut into segments for the builder (build.hip k_cylinder_segments): what the tree is built over when num_segs != 0
+  // cylinders cut into segments for the builder (prims.hip k_cylinder_segments): what the tree is built over when num_segs != 0
   DevBuf b_seg_verts, b_seg_radii, b_seg_prim, b_seg_off;
   uint32_t num_segs = 0;
   int cyl_split = 32;     // most segments a cylinder is cut into (tunable "cyl_split"; 1: never; read by nrtSetCylinders)
@@ -52,7 +52,7 @@ struct nrt_ctx {
   void *d_radii = nullptr;
   uint32_t *d_faces = nullptr;
   uint32_t num_faces = 0, num_verts = 0;
-  // nrtSetMeshDevice (mesh.hip): the largest face index, reduced on the device and read back through a page-locked word
+  // nrtSetMeshDevice (prims.hip): the largest face index, reduced on the device and read back through a page-locked word
   DevBuf b_max_index;
   uint32_t *h_max_index = nullptr;
 
@@ -468,33 +468,81 @@ const char *nrtLastError(const nrt_ctx *c) { return c ? c->err.c_str() : g_creat
 } // extern "C"
 
 // ---------------------------------------------------------------------------
-// mesh
+// primitives: one path for the setters of every kind (prim_kinds.h), from host memory or (the *Device forms: copied on the
+// caller's stream) from HBM.  Every refusal comes before anything changes; the counts are set once the primitives are in place,
+// so a failed upload leaves an empty context.
 // ---------------------------------------------------------------------------
+// The first refusal of every setter.
+static nrt_status refuse_precision(nrt_ctx *c, const char *fn, int kind, int prec) {
+  if (!c) return NRT_ERR_INVALID;
+  if (c->prec == 0 || c->prec == prec) return NRT_OK;
+  return fail(c, NRT_ERR_PRECISION, kind == kPrimTriangles ? "%s: context already holds a %s mesh" : "%s: context already holds %s primitives", fn,
+              c->prec == 4 ? "f32" : "f64");
+}
+
+// Nothing is refused any more: the old tree and primitives go, the context is of this kind and precision.
+static void drop_primitives(nrt_ctx *c, int kind, int prec) {
+  free_tree(c);
+  free_mesh(c);
+  c->prec = prec;
+  c->prim_kind = kind;
+}
+static nrt_status begin_set(nrt_ctx *c, int kind, int prec) {
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, wait_for_launches(c));
+  drop_primitives(c, kind, prec);
+  return NRT_OK;
+}
+
+// What remains of a Device set call once the old primitives are gone and a HIP call fails: an empty context and the reason.
+static nrt_status set_device_failed(nrt_ctx *c, const char *fn, hipStream_t s, hipError_t e) {
+  (void)hipStreamSynchronize(s);
+  free_mesh(c);
+  return fail(c, NRT_ERR_DEVICE, "%s: %s (the context's primitives were dropped: set them again)", fn, hipGetErrorString(e));
+}
+
+// `src` (null: nothing to copy yet) into the grow-only buffer `b`: from the host, or (`device`) from HBM on `s`.
+static nrt_status upload(nrt_ctx *c, const char *fn, DevBuf &b, const void *src, size_t bytes, bool device, hipStream_t s) {
+  if (!device) {
+    if (nrt_status st = ensure(c, b, bytes)) return st;
+    if (src) HIPCHK(c, hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice));
+    return NRT_OK;
+  }
+  hipError_t e = devbuf_ensure(&b, bytes);
+  if (e == hipSuccess && src) e = hipMemcpyAsync(b.p, src, bytes, hipMemcpyDeviceToDevice, s);
+  return e == hipSuccess ? NRT_OK : set_device_failed(c, fn, s, e);
+}
+// The tail of every setter: a Device form waits for its copies (the context owns its copy: the caller's buffers are free again),
+// and the primitives are in place.
+static nrt_status adopt_primitives(nrt_ctx *c, const char *fn, bool device, hipStream_t s, bool faces, bool radii, uint32_t n, uint32_t num_verts) {
+  if (device) {
+    const hipError_t e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return set_device_failed(c, fn, s, e);
+  }
+  c->d_verts = c->b_verts.p;
+  c->d_faces = faces ? (uint32_t *)c->b_faces.p : nullptr;
+  c->d_radii = radii ? c->b_radii.p : nullptr;
+  c->num_faces = n;
+  c->num_verts = num_verts;
+  return NRT_OK;
+}
+
 template <typename T>
 static nrt_status set_mesh(nrt_ctx *c, const T *vertices, size_t stride, const uint32_t *faces,
                            uint32_t num_faces) {
-  if (!c) return NRT_ERR_INVALID;
-  if (c->prec != 0 && c->prec != (int)sizeof(T))
-    return fail(c, NRT_ERR_PRECISION, "nrtSetMesh: context already holds a %s mesh",
-                c->prec == 4 ? "f32" : "f64");
+  const char *fn = "nrtSetMesh";
+  if (nrt_status st = refuse_precision(c, fn, kPrimTriangles, (int)sizeof(T))) return st;
   if (num_faces && (!vertices || !faces)) return fail(c, NRT_ERR_INVALID, "nrtSetMesh: NULL mesh pointer");
   if (stride < 3 * sizeof(T) && num_faces)
     return fail(c, NRT_ERR_INVALID, "nrtSetMesh: vertex stride %zu < %zu", stride, 3 * sizeof(T));
   NRT_RANGE("nrtSetMesh (compaction + upload)");
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, wait_for_launches(c));
-  free_tree(c);
-  free_mesh(c);
-  c->prec = (int)sizeof(T);
-  c->prim_kind = kPrimTriangles;
-  c->num_faces = num_faces;
+  if (nrt_status st = begin_set(c, kPrimTriangles, (int)sizeof(T))) return st;
   if (num_faces == 0) return NRT_OK;
   // The reference's mesh carries no vertex count (nanort.h:925-930): derive it.
   uint32_t maxv = 0;
   const size_t ni = 3 * (size_t)num_faces;
   for (size_t i = 0; i < ni; i++) maxv = faces[i] > maxv ? faces[i] : maxv;
   const uint32_t nv = maxv + 1;
-  c->num_verts = nv;
   // Compact the strided vertex array (get_vertex_addr, nanort.h:467-472) to tight xyz.
   const T *src = vertices;
   std::vector<T> tight;
@@ -510,47 +558,9 @@ static nrt_status set_mesh(nrt_ctx *c, const T *vertices, size_t stride, const u
     src = tight.data();
   }
   nrt_status st;
-  if ((st = ensure(c, c->b_verts, 3 * (size_t)nv * sizeof(T))) || (st = ensure(c, c->b_faces, ni * sizeof(uint32_t)))) return st;
-  c->d_verts = c->b_verts.p;
-  c->d_faces = (uint32_t *)c->b_faces.p;
-  HIPCHK(c, hipMemcpy(c->d_verts, src, 3 * (size_t)nv * sizeof(T), hipMemcpyHostToDevice));
-  HIPCHK(c, hipMemcpy(c->d_faces, faces, ni * sizeof(uint32_t), hipMemcpyHostToDevice));
-  return NRT_OK;
-}
-
-// Sphere primitives (SphereGeometry of examples/particle_primitive/main.cc:113-147): xyz centres, one radius each.
-template <typename T>
-static nrt_status set_spheres(nrt_ctx *c, const T *centers, const T *radii, uint32_t n) {
-  if (!c) return NRT_ERR_INVALID;
-  if (c->prec != 0 && c->prec != (int)sizeof(T))
-    return fail(c, NRT_ERR_PRECISION, "nrtSetSpheres: context already holds %s primitives", c->prec == 4 ? "f32" : "f64");
-  if (n && (!centers || !radii)) return fail(c, NRT_ERR_INVALID, "nrtSetSpheres: NULL pointer");
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, wait_for_launches(c));
-  free_tree(c);
-  free_mesh(c);
-  c->prec = (int)sizeof(T);
-  c->prim_kind = kPrimSpheres;
-  c->num_faces = n;
-  c->num_verts = n;
-  if (n == 0) return NRT_OK;
-  nrt_status st;
-  if ((st = ensure(c, c->b_verts, 3 * (size_t)n * sizeof(T))) || (st = ensure(c, c->b_radii, (size_t)n * sizeof(T)))) return st;
-  c->d_verts = c->b_verts.p;
-  c->d_radii = c->b_radii.p;
-  HIPCHK(c, hipMemcpy(c->d_verts, centers, 3 * (size_t)n * sizeof(T), hipMemcpyHostToDevice));
-  HIPCHK(c, hipMemcpy(c->d_radii, radii, (size_t)n * sizeof(T), hipMemcpyHostToDevice));
-  return NRT_OK;
-}
-
-// ---------------------------------------------------------------------------
-// primitives that are already in device memory (mesh.hip)
-// ---------------------------------------------------------------------------
-// What remains of a Device set call once the old primitives are gone and a HIP call fails: an empty context and the reason.
-static nrt_status set_device_failed(nrt_ctx *c, const char *fn, hipStream_t s, hipError_t e) {
-  (void)hipStreamSynchronize(s);
-  free_mesh(c);
-  return fail(c, NRT_ERR_DEVICE, "%s: %s (the context's primitives were dropped: set them again)", fn, hipGetErrorString(e));
+  if ((st = upload(c, fn, c->b_verts, src, 3 * (size_t)nv * sizeof(T), false, nullptr)) || (st = upload(c, fn, c->b_faces, faces, ni * sizeof(uint32_t), false, nullptr)))
+    return st;
+  return adopt_primitives(c, fn, false, nullptr, true, false, num_faces, nv);
 }
 
 // nrtSetMesh for arrays in HBM: the same state as set_mesh leaves, the vertex count derived and the caller's `num_vertices`
@@ -559,9 +569,7 @@ template <typename T>
 static nrt_status set_mesh_device(nrt_ctx *c, const T *vertices, uint32_t num_vertices, size_t stride, const uint32_t *faces,
                                   uint32_t num_faces, hipStream_t s) {
   const char *fn = "nrtSetMeshDevice";
-  if (!c) return NRT_ERR_INVALID;
-  if (c->prec != 0 && c->prec != (int)sizeof(T))
-    return fail(c, NRT_ERR_PRECISION, "%s: context already holds a %s mesh", fn, c->prec == 4 ? "f32" : "f64");
+  if (nrt_status st = refuse_precision(c, fn, kPrimTriangles, (int)sizeof(T))) return st;
   if (num_faces) {
     if (!vertices || !faces) return fail(c, NRT_ERR_INVALID, "%s: NULL mesh pointer", fn);
     if (num_vertices == 0) return fail(c, NRT_ERR_INVALID, "%s: num_vertices == 0 with %u faces", fn, num_faces);
@@ -587,162 +595,82 @@ static nrt_status set_mesh_device(nrt_ctx *c, const T *vertices, uint32_t num_ve
       return fail(c, NRT_ERR_INVALID, "%s: face index %u is out of range: the vertex block holds %u rows", fn, maxv, num_vertices);
     nv = maxv + 1;
   }
-  free_tree(c);
-  free_mesh(c);
-  c->prec = (int)sizeof(T);
-  c->prim_kind = kPrimTriangles;
+  drop_primitives(c, kPrimTriangles, (int)sizeof(T));
   if (num_faces == 0) return NRT_OK;
-  hipError_t e;
-  if ((e = devbuf_ensure(&c->b_verts, 3 * (size_t)nv * sizeof(T))) != hipSuccess || (e = devbuf_ensure(&c->b_faces, ni * sizeof(uint32_t))) != hipSuccess ||
-      (e = stride == 3 * sizeof(T) ? hipMemcpyAsync(c->b_verts.p, vertices, 3 * (size_t)nv * sizeof(T), hipMemcpyDeviceToDevice, s) // (tight already)
-                                   : launch_gather_vertices<T>(vertices, stride, nv, (T *)c->b_verts.p, s)) != hipSuccess ||
-      (e = hipMemcpyAsync(c->b_faces.p, faces, ni * sizeof(uint32_t), hipMemcpyDeviceToDevice, s)) != hipSuccess ||
-      (e = hipStreamSynchronize(s)) != hipSuccess) // (the context owns its copy: the caller's buffers are free again)
-    return set_device_failed(c, fn, s, e);
-  c->d_verts = c->b_verts.p;
-  c->d_faces = (uint32_t *)c->b_faces.p;
-  c->num_faces = num_faces;
-  c->num_verts = nv;
-  return NRT_OK;
+  const bool tight = stride == 3 * sizeof(T); // (tight already: a copy; else the gather kernel)
+  nrt_status st;
+  if ((st = upload(c, fn, c->b_verts, tight ? vertices : nullptr, 3 * (size_t)nv * sizeof(T), true, s))) return st;
+  if (!tight) {
+    const hipError_t e = launch_gather_vertices<T>(vertices, stride, nv, (T *)c->b_verts.p, s);
+    if (e != hipSuccess) return set_device_failed(c, fn, s, e);
+  }
+  if ((st = upload(c, fn, c->b_faces, faces, ni * sizeof(uint32_t), true, s))) return st;
+  return adopt_primitives(c, fn, true, s, true, false, num_faces, nv);
 }
 
-template <typename T>
-static nrt_status set_spheres_device(nrt_ctx *c, const T *centers, const T *radii, uint32_t n, hipStream_t s) {
-  const char *fn = "nrtSetSpheresDevice";
-  if (!c) return NRT_ERR_INVALID;
-  if (c->prec != 0 && c->prec != (int)sizeof(T))
-    return fail(c, NRT_ERR_PRECISION, "%s: context already holds %s primitives", fn, c->prec == 4 ? "f32" : "f64");
-  if (n && (!centers || !radii)) return fail(c, NRT_ERR_INVALID, "%s: NULL pointer", fn);
-  if (n && ((uintptr_t)centers % sizeof(T) != 0 || (uintptr_t)radii % sizeof(T) != 0))
-    return fail(c, NRT_ERR_INVALID, "%s: pointer not aligned to %zu bytes", fn, sizeof(T));
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, wait_for_launches(c));
-  free_tree(c);
-  free_mesh(c);
-  c->prec = (int)sizeof(T);
-  c->prim_kind = kPrimSpheres;
-  if (n == 0) return NRT_OK;
-  hipError_t e;
-  if ((e = devbuf_ensure(&c->b_verts, 3 * (size_t)n * sizeof(T))) != hipSuccess || (e = devbuf_ensure(&c->b_radii, (size_t)n * sizeof(T))) != hipSuccess ||
-      (e = hipMemcpyAsync(c->b_verts.p, centers, 3 * (size_t)n * sizeof(T), hipMemcpyDeviceToDevice, s)) != hipSuccess ||
-      (e = hipMemcpyAsync(c->b_radii.p, radii, (size_t)n * sizeof(T), hipMemcpyDeviceToDevice, s)) != hipSuccess ||
-      (e = hipStreamSynchronize(s)) != hipSuccess)
-    return set_device_failed(c, fn, s, e);
-  c->d_verts = c->b_verts.p;
-  c->d_radii = c->b_radii.p;
-  c->num_faces = n;
-  c->num_verts = n;
-  return NRT_OK;
-}
-
-// Cylinder primitives (CylinderGeometry of examples/cylinder_primitive/main.cc:124-210): two end points and two radii each.
-static nrt_status set_cylinders(nrt_ctx *c, const float *endpoints, const float *radii, uint32_t n, int test_cap) {
-  if (!c) return NRT_ERR_INVALID;
-  if (c->prec != 0 && c->prec != 4) return fail(c, NRT_ERR_PRECISION, "nrtSetCylinders: context already holds f64 primitives");
-  if (n && (!endpoints || !radii)) return fail(c, NRT_ERR_INVALID, "nrtSetCylinders: NULL pointer");
-  if (n >= 0x40000000u) return fail(c, NRT_ERR_INVALID, "nrtSetCylinders: too many cylinders");
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, wait_for_launches(c));
-  free_tree(c);
-  free_mesh(c);
-  c->prec = 4;
-  c->prim_kind = kPrimCylinders;
-  c->cyl_test_cap = test_cap ? 1u : 0u;
-  c->num_faces = n;
-  c->num_verts = 2 * n;
+// The kinds with radii — spheres (SphereGeometry of examples/particle_primitive/main.cc:113-147), cylinders (CylinderGeometry of
+// examples/cylinder_primitive/main.cc:124-210), curves (CurveGeometry of examples/curves_primitive/main.cc:513-604) — as their
+// row of kPrimKinds describes them: `n` times pos_floats positions and radius_floats radii of `prec` bytes each.
+// `extra_refusal`: the caller's own refusal (null: none), in its place among the shared ones.
+static nrt_status set_radius_prims(nrt_ctx *c, const char *fn, int kind, int prec, const void *positions, const void *radii, uint32_t n, bool device,
+                                   hipStream_t s, const char *extra_refusal = nullptr) {
+  const PrimKind &k = kPrimKinds[kind];
+  if (nrt_status st = refuse_precision(c, fn, kind, prec)) return st;
+  if (extra_refusal) return fail(c, NRT_ERR_INVALID, "%s: %s", fn, extra_refusal);
+  if (n && (!positions || !radii)) return fail(c, NRT_ERR_INVALID, "%s: NULL pointer", fn);
+  if (k.max_count && n >= k.max_count) return fail(c, NRT_ERR_INVALID, "%s: too many %s", fn, k.name);
+  if (device && n && ((uintptr_t)positions % (size_t)prec != 0 || (uintptr_t)radii % (size_t)prec != 0))
+    return fail(c, NRT_ERR_INVALID, "%s: pointer not aligned to %d bytes", fn, prec);
+  if (nrt_status st = begin_set(c, kind, prec)) return st;
   if (n == 0) return NRT_OK;
   nrt_status st;
-  if ((st = ensure(c, c->b_verts, 6 * (size_t)n * sizeof(float))) || (st = ensure(c, c->b_radii, 2 * (size_t)n * sizeof(float)))) return st;
-  c->d_verts = c->b_verts.p;
-  c->d_radii = c->b_radii.p;
-  HIPCHK(c, hipMemcpy(c->d_verts, endpoints, 6 * (size_t)n * sizeof(float), hipMemcpyHostToDevice));
-  HIPCHK(c, hipMemcpy(c->d_radii, radii, 2 * (size_t)n * sizeof(float), hipMemcpyHostToDevice));
-  // Segments for the builder (build.hip, k_cylinder_segments): a cylinder many radii long is handed over as several pieces
-  // with their own tight boxes and the cylinder's id.  Counts on the host (the arrays are here anyway), pieces on the device.
+  if ((st = upload(c, fn, c->b_verts, positions, (size_t)k.pos_floats * n * (size_t)prec, device, s)) ||
+      (st = upload(c, fn, c->b_radii, radii, (size_t)k.radius_floats * n * (size_t)prec, device, s)))
+    return st;
+  return adopt_primitives(c, fn, device, s, false, true, n, (uint32_t)k.num_verts * n);
+}
+
+// Segments for the builder (prims.hip, k_cylinder_segments): a cylinder many radii long is handed over as several pieces
+// with their own tight boxes and the cylinder's id.  Counts on the host (the arrays are here anyway), pieces on the device.
+static nrt_status segment_cylinders(nrt_ctx *c, const float *endpoints, const float *radii, uint32_t n) {
   c->num_segs = 0;
   c->segment_ms = 0.f;
   // (zero-radius "cylinders" are boxes — the top-level tree of a scene is built over them — and cyl_split = 1 asks for the
   // example's own boxes: neither needs the counting pass or its array)
   bool any_radius = false;
   for (size_t i = 0; i < 2 * (size_t)n && !any_radius; i++) any_radius = radii[i] > 0.0f;
-  if (c->cyl_split > 1 && any_radius) {
-    const auto seg_t0 = std::chrono::steady_clock::now();
-    std::vector<uint32_t> off((size_t)n + 1);
-    uint64_t total = 0;
-    for (int pass = 0; pass < 2 && total == 0; pass++) {
-      // (second pass: the segment array would not fit the packed leaf references — fall back to half as many pieces at most)
-      const uint32_t kmax = (uint32_t)c->cyl_split >> pass;
-      uint64_t t = 0;
-      for (uint32_t i = 0; i < n; i++) {
-        const float *p0 = endpoints + 6 * (size_t)i, *p1 = p0 + 3;
-        const float r0 = radii[2 * (size_t)i], r1 = radii[2 * (size_t)i + 1];
-        const float rr = r0 > r1 ? r0 : r1;
-        const double dx = (double)p1[0] - p0[0], dy = (double)p1[1] - p0[1], dz = (double)p1[2] - p0[2];
-        const double len = sqrt(dx * dx + dy * dy + dz * dz);
-        uint32_t k = 1;
-        if (kmax > 1 && rr > 0.0f && std::isfinite(len) && std::isfinite(rr) && len > 0.0) { // (zero-radius "cylinders" are boxes: the top-level tree of a scene)
-          const double want = ceil(len / ((double)c->cyl_seg_radii * (double)rr));
-          k = want >= (double)kmax ? kmax : (want < 1.0 ? 1u : (uint32_t)want);
-        }
-        off[i] = (uint32_t)t;
-        t += k;
-      }
-      off[n] = (uint32_t)t;
-      if (t < (uint64_t)kPackedFirstMask) total = t;
-    }
-    if (total > (uint64_t)n) {
-      if ((st = ensure(c, c->b_seg_off, ((size_t)n + 1) * sizeof(uint32_t))) || (st = ensure(c, c->b_seg_verts, 6 * (size_t)total * sizeof(float))) ||
-          (st = ensure(c, c->b_seg_radii, 2 * (size_t)total * sizeof(float))) || (st = ensure(c, c->b_seg_prim, (size_t)total * sizeof(uint32_t))))
-        return st;
-      HIPCHK(c, hipMemcpyAsync(c->b_seg_off.p, off.data(), ((size_t)n + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-      HIPCHK(c, launch_cylinder_segments((const float *)c->d_verts, (const float *)c->d_radii, (const uint32_t *)c->b_seg_off.p, n,
-                                         (float *)c->b_seg_verts.p, (float *)c->b_seg_radii.p, (uint32_t *)c->b_seg_prim.p, c->stream));
-      HIPCHK(c, hipStreamSynchronize(c->stream)); // (`off` is pageable host memory)
-      c->num_segs = (uint32_t)total;
-    }
-    // the segmentation is part of building this tree: its wall time is added to the build's (nrtLastBuildMs, build_secs)
-    c->segment_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - seg_t0).count();
+  if (c->cyl_split <= 1 || !any_radius) return NRT_OK;
+  const auto seg_t0 = std::chrono::steady_clock::now();
+  std::vector<uint32_t> off((size_t)n + 1);
+  const uint64_t total = cylinder_segment_offsets(endpoints, radii, n, c->cyl_seg_radii, (uint32_t)c->cyl_split, kPackedFirstMask, off.data());
+  if (total > (uint64_t)n) {
+    nrt_status st;
+    if ((st = ensure(c, c->b_seg_off, ((size_t)n + 1) * sizeof(uint32_t))) || (st = ensure(c, c->b_seg_verts, 6 * (size_t)total * sizeof(float))) ||
+        (st = ensure(c, c->b_seg_radii, 2 * (size_t)total * sizeof(float))) || (st = ensure(c, c->b_seg_prim, (size_t)total * sizeof(uint32_t))))
+      return st;
+    HIPCHK(c, hipMemcpyAsync(c->b_seg_off.p, off.data(), ((size_t)n + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, launch_cylinder_segments((const float *)c->d_verts, (const float *)c->d_radii, (const uint32_t *)c->b_seg_off.p, n,
+                                       (float *)c->b_seg_verts.p, (float *)c->b_seg_radii.p, (uint32_t *)c->b_seg_prim.p, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream)); // (`off` is pageable host memory)
+    c->num_segs = (uint32_t)total;
   }
+  // the segmentation is part of building this tree: its wall time is added to the build's (nrtLastBuildMs, build_secs)
+  c->segment_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - seg_t0).count();
   return NRT_OK;
 }
 
-// Curve primitives (CurveGeometry of examples/curves_primitive/main.cc:513-604): four control points and four radii each, in
-// host memory or (`device`: copied on `s`, the rules of set_spheres_device) in HBM.  Every refusal comes before anything changes.
+static nrt_status set_cylinders(nrt_ctx *c, const float *endpoints, const float *radii, uint32_t n, int test_cap) {
+  if (nrt_status st = set_radius_prims(c, "nrtSetCylinders", kPrimCylinders, 4, endpoints, radii, n, false, nullptr)) return st;
+  c->cyl_test_cap = test_cap ? 1u : 0u;
+  return n ? segment_cylinders(c, endpoints, radii, n) : NRT_OK;
+}
+
 static nrt_status set_curves(nrt_ctx *c, const float *cps, const float *radii, uint32_t n, uint32_t subdiv, bool device, hipStream_t s) {
-  const char *fn = device ? "nrtSetCurvesDevice" : "nrtSetCurves";
-  if (!c) return NRT_ERR_INVALID;
-  if (c->prec != 0 && c->prec != 4) return fail(c, NRT_ERR_PRECISION, "%s: context already holds f64 primitives", fn);
-  if (subdiv < 1u || subdiv > 64u) return fail(c, NRT_ERR_INVALID, "%s: num_subdivisions %u outside 1..64", fn, subdiv);
-  if (n && (!cps || !radii)) return fail(c, NRT_ERR_INVALID, "%s: NULL pointer", fn);
-  if (n >= (1u << 28)) return fail(c, NRT_ERR_INVALID, "%s: too many curves", fn);
-  if (device && n && ((uintptr_t)cps % sizeof(float) != 0 || (uintptr_t)radii % sizeof(float) != 0))
-    return fail(c, NRT_ERR_INVALID, "%s: pointer not aligned to 4 bytes", fn);
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, wait_for_launches(c));
-  free_tree(c);
-  free_mesh(c);
-  c->prec = 4;
-  c->prim_kind = kPrimCurves;
+  char refusal[64] = "";
+  if (subdiv < 1u || subdiv > 64u) snprintf(refusal, sizeof(refusal), "num_subdivisions %u outside 1..64", subdiv);
+  if (nrt_status st = set_radius_prims(c, device ? "nrtSetCurvesDevice" : "nrtSetCurves", kPrimCurves, 4, cps, radii, n, device, s, refusal[0] ? refusal : nullptr))
+    return st;
   c->curve_subdiv = subdiv;
-  if (n == 0) return NRT_OK;
-  const size_t cp_bytes = 12 * (size_t)n * sizeof(float), rad_bytes = 4 * (size_t)n * sizeof(float);
-  if (device) {
-    hipError_t e;
-    if ((e = devbuf_ensure(&c->b_verts, cp_bytes)) != hipSuccess || (e = devbuf_ensure(&c->b_radii, rad_bytes)) != hipSuccess ||
-        (e = hipMemcpyAsync(c->b_verts.p, cps, cp_bytes, hipMemcpyDeviceToDevice, s)) != hipSuccess ||
-        (e = hipMemcpyAsync(c->b_radii.p, radii, rad_bytes, hipMemcpyDeviceToDevice, s)) != hipSuccess ||
-        (e = hipStreamSynchronize(s)) != hipSuccess) // (the context owns its copy: the caller's buffers are free again)
-      return set_device_failed(c, fn, s, e);
-  } else {
-    nrt_status st;
-    if ((st = ensure(c, c->b_verts, cp_bytes)) || (st = ensure(c, c->b_radii, rad_bytes))) return st;
-    HIPCHK(c, hipMemcpy(c->b_verts.p, cps, cp_bytes, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->b_radii.p, radii, rad_bytes, hipMemcpyHostToDevice));
-  }
-  c->d_verts = c->b_verts.p;
-  c->d_radii = c->b_radii.p;
-  c->num_faces = n;
-  c->num_verts = 4 * n;
   return NRT_OK;
 }
 
@@ -753,29 +681,10 @@ static nrt_status set_curves(nrt_ctx *c, const float *cps, const float *radii, u
 // on its way to the host: (1) leaf-ordered primitive records (needs the index array only), (2) WideNode / Wide4Node arrays.
 template <typename T>
 static nrt_status finish_leaf_records(nrt_ctx *c, hipStream_t s) {
-  nrt_status st;
   // leaf-ordered primitive records for the traversal kernel
-  if (c->prim_kind == kPrimSpheres) {
-    if ((st = ensure(c, c->b_tris, std::max<size_t>(1, c->num_indices) * sizeof(LeafSphere<T>)))) return st;
-    c->d_tris = c->b_tris.p;
-    HIPCHK(c, launch_gather_leaf_spheres<T>(c->d_indices, (const T *)c->d_verts, (const T *)c->d_radii,
-                                            (LeafSphere<T> *)c->d_tris, (uint32_t)c->num_indices, s));
-  } else if (c->prim_kind == kPrimCylinders) {
-    if ((st = ensure(c, c->b_tris, std::max<size_t>(1, c->num_indices) * sizeof(LeafCylinder<T>)))) return st;
-    c->d_tris = c->b_tris.p;
-    HIPCHK(c, launch_gather_leaf_cylinders<T>(c->d_indices, (const T *)c->d_verts, (const T *)c->d_radii,
-                                              (LeafCylinder<T> *)c->d_tris, (uint32_t)c->num_indices, s));
-  } else if (c->prim_kind == kPrimCurves) { // (fp32 contexts only: nrtSetCurves)
-    if ((st = ensure(c, c->b_tris, std::max<size_t>(1, c->num_indices) * sizeof(LeafCurve)))) return st;
-    c->d_tris = c->b_tris.p;
-    HIPCHK(c, launch_gather_leaf_curves(c->d_indices, (const float *)c->d_verts, (const float *)c->d_radii, (LeafCurve *)c->d_tris,
-                                        (uint32_t)c->num_indices, s));
-  } else {
-    if ((st = ensure(c, c->b_tris, std::max<size_t>(1, c->num_indices) * sizeof(LeafTri<T>)))) return st;
-    c->d_tris = c->b_tris.p;
-    HIPCHK(c, launch_gather_leaf_tris<T>(c->d_indices, c->d_faces, (const T *)c->d_verts,
-                                         (LeafTri<T> *)c->d_tris, (uint32_t)c->num_indices, s));
-  }
+  if (nrt_status st = ensure(c, c->b_tris, std::max<size_t>(1, c->num_indices) * leaf_record_bytes<T>(c->prim_kind))) return st;
+  c->d_tris = c->b_tris.p;
+  HIPCHK(c, launch_gather_leaf<T>(c->prim_kind, c->d_indices, c->d_faces, (const T *)c->d_verts, (const T *)c->d_radii, c->d_tris, (uint32_t)c->num_indices, s));
   return NRT_OK;
 }
 
@@ -997,7 +906,7 @@ static nrt_status refit(nrt_ctx *c, const T *vertices, size_t stride, bool devic
   if (c->prec != 0 && c->prec != (int)sizeof(T))
     return fail(c, NRT_ERR_PRECISION, "%s: the context holds %s primitives", fn, c->prec == 8 ? "f64" : "f32");
   if (c->prim_kind != kPrimTriangles) return fail(c, NRT_ERR_INVALID, "%s: only triangle meshes refit (this context holds %s)", fn,
-                                                  c->prim_kind == kPrimSpheres ? "spheres" : (c->prim_kind == kPrimCylinders ? "cylinders" : "curves"));
+                                                  kPrimKinds[c->prim_kind].name);
   if (!c->d_nodes) return fail(c, NRT_ERR_INVALID, "%s: no tree (call nrtBuild or nrtSetTree)", fn);
   if (stride < 3 * sizeof(T)) return fail(c, NRT_ERR_INVALID, "%s: vertex stride %zu < %zu", fn, stride, 3 * sizeof(T));
   if (device && (stride % sizeof(T) != 0 || (uintptr_t)vertices % sizeof(T) != 0))
@@ -1299,7 +1208,7 @@ static nrt_status enqueue_launch(nrt_ctx *c, const TraverseLaunch<T> &l, const W
   // completion record instead of events: the traversal kernel is the launch's last kernel and events were not asked for
   const bool use_rec = w.wide() && !count && !c->launch_timing;
   // (the sphere kind's u/v pass and the cylinder kind's normal pass run behind the traversal kernel and close the record in its place)
-  const bool post_pass = (c->prim_kind == kPrimSpheres && l.hits != nullptr) || l.kind == Query::Cylinders || l.kind == Query::Curves;
+  const bool post_pass = kPrimKinds[c->prim_kind].post_pass && (c->prim_kind != kPrimSpheres || l.hits != nullptr); // (validate_launch: such a context takes its kind's own query only)
   a.done_rec = use_rec ? slot->d_done : nullptr;
   a.done_count = slot->d_count;
   a.done_seq = use_rec ? slot->seq + 1u : 0u;
@@ -1327,12 +1236,9 @@ static nrt_status enqueue_launch(nrt_ctx *c, const TraverseLaunch<T> &l, const W
   slot->stream = s;
   slot->used = true;
   if (use_rec) c->last_timed_slot = (int)(slot - c->slots);
-  if (l.kind == Query::Cylinders)
-    HIPCHK(c, launch_cylinder_post((const nrt_ray_f32 *)l.rays, (const nrt_hit_f32 *)slot->cyl_hits.p, (const uint8_t *)slot->cyl_bits.p,
-                                   (const float *)c->d_verts, (uint32_t)l.n, l.cyl_hits, l.mask, a.done_rec, a.done_count, a.done_seq, s));
-  if (l.kind == Query::Curves)
-    HIPCHK(c, launch_curve_post((const nrt_ray_f32 *)l.rays, (const nrt_hit_f32 *)slot->cyl_hits.p, (const uint8_t *)slot->cyl_bits.p,
-                                (const float *)c->d_verts, (uint32_t)l.n, l.cyl_hits, l.mask, a.done_rec, a.done_count, a.done_seq, s));
+  if (post_pass) // (fill_launch_args: a.hits / a.mask are the slot's compact records and bits where the pass writes the caller's records)
+    HIPCHK(c, launch_post_pass<T>(c->prim_kind, l.rays, a.hits, a.mask, (const T *)c->d_verts, (uint32_t)l.n, l.cyl_hits, l.mask, a.done_rec, a.done_count,
+                                  a.done_seq, s));
   if (timed) {
     HIPCHK(c, hipEventRecord(slot->t1, s));
     slot->last_timed = true;
@@ -1846,10 +1752,10 @@ nrt_status nrtSetMeshDevice_f64(nrt_ctx *c, const double *v, uint32_t nv, size_t
   return set_mesh_device<double>(c, v, nv, stride, f, nf, (hipStream_t)s);
 }
 nrt_status nrtSetSpheresDevice_f32(nrt_ctx *c, const float *centers, const float *radii, uint32_t n, void *s) {
-  return set_spheres_device<float>(c, centers, radii, n, (hipStream_t)s);
+  return set_radius_prims(c, "nrtSetSpheresDevice", kPrimSpheres, 4, centers, radii, n, true, (hipStream_t)s);
 }
 nrt_status nrtSetSpheres_f32(nrt_ctx *c, const float *centers, const float *radii, uint32_t n) {
-  return set_spheres<float>(c, centers, radii, n);
+  return set_radius_prims(c, "nrtSetSpheres", kPrimSpheres, 4, centers, radii, n, false, nullptr);
 }
 
 nrt_status nrtBuild_f32(nrt_ctx *c, const nrt_build_options_f32 *o, nrt_build_stats *st, uint64_t *nn) {

@@ -45,6 +45,7 @@
 
 #include "kernels.h"
 #include "minmax_dev.h"
+#include "prims_dev.h"
 
 namespace nrt {
 
@@ -371,7 +372,6 @@ __global__ __launch_bounds__(256) void k_prim_records(const T *__restrict__ vert
   }
   for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) {
     PrimRec<T> r;
-    const T third = T(1) / T(3);
     // three indices, then three vertices, each as ONE 12/24-byte load (dword-aligned vectors) instead of nine scalar gathers
     Vec3Of<uint32_t> f = {0, 0, 0};
     Vec3Of<T> v0 = {T(0), T(0), T(0)}, v1 = v0, v2 = v0;
@@ -383,41 +383,14 @@ __global__ __launch_bounds__(256) void k_prim_records(const T *__restrict__ vert
     }
 #pragma unroll
     for (int k = 0; k < 3; k++) {
-      if (faces) { // triangles
-        const T p0 = k == 0 ? v0.x : (k == 1 ? v0.y : v0.z), p1 = k == 0 ? v1.x : (k == 1 ? v1.y : v1.z),
-                p2 = k == 0 ? v2.x : (k == 1 ? v2.y : v2.z);
-        r.bmin[k] = tmin(p0, tmin(p1, p2)); // nanort.h:967-968
-        r.bmax[k] = tmax(p0, tmax(p1, p2));
-        r.c[k] = ((p0 + p1) + p2) * third; // nanort.h:970
-      } else if (kind == kPrimSpheres) { // spheres: SphereGeometry::BoundingBoxAndCenter (examples/particle_primitive/main.cc:124-136)
-        const T c = verts[3 * (size_t)i + k], rad = radii[i];
-        r.bmin[k] = c - rad;
-        r.bmax[k] = c + rad;
-        r.c[k] = c;
-      } else if (kind == kPrimCylinders) { // cylinders: CylinderGeometry::BoundingBoxAndCenter (examples/cylinder_primitive/main.cc:166-205)
-        const T a0 = verts[3 * (size_t)(2 * i) + k], a1 = verts[3 * (size_t)(2 * i + 1) + k];
-        const T r0 = radii[2 * (size_t)i], r1 = radii[2 * (size_t)i + 1];
-        r.bmin[k] = tmin(a1 - r1, a0 - r0); // std::min(second, first): identical unless NaN
-        r.bmax[k] = tmax(a1 + r1, a0 + r0);
-        r.c[k] = (a0 + a1) / T(2.0);
-      } else { // curves: CurveGeometry::BoundingBoxAndCenter (examples/curves_primitive/main.cc:557-597): control point -+ its radius
-        const T *cp = verts + 12 * (size_t)i + k, *rad = radii + 4 * (size_t)i;
-        T lo_ = cp[0] - rad[0], hi_ = cp[0] + rad[0];
-#pragma unroll
-        for (int j = 1; j < 4; j++) {
-          lo_ = tmin(cp[3 * j] - rad[j], lo_); // std::min(new, running) / std::max(new, running), operands in the example's order
-          hi_ = tmax(cp[3 * j] + rad[j], hi_);
-        }
-        r.bmin[k] = lo_;
-        r.bmax[k] = hi_;
-        r.c[k] = (((cp[0] + cp[3]) + cp[6]) + cp[9]) / T(4.0);
-      }
+      const T p0 = k == 0 ? v0.x : (k == 1 ? v0.y : v0.z), p1 = k == 0 ? v1.x : (k == 1 ? v1.y : v1.z), p2 = k == 0 ? v2.x : (k == 1 ? v2.y : v2.z);
+      prim_box_axis<T>(faces != nullptr, kind, i, k, verts, radii, p0, p1, p2, r.bmin[k], r.bmax[k], r.c[k]);
       lo[k] = tmin(lo[k], r.bmin[k]);
       hi[k] = tmax(hi[k], r.bmax[k]);
       clo[k] = tmin(clo[k], r.c[k]);
       chi[k] = tmax(chi[k], r.c[k]);
     }
-    r.prim = prim_map ? prim_map[i] : i; // (cylinder SEGMENTS carry their cylinder's id: k_cylinder_segments)
+    r.prim = prim_map ? prim_map[i] : i; // (cylinder SEGMENTS carry their cylinder's id: prims.hip, k_cylinder_segments)
     recs[i] = r;
   }
 #pragma unroll
@@ -2678,76 +2651,6 @@ struct BuildPlan { // carve-up of the build workspace for n primitives
       return e_;                                                        \
     }                                                                   \
   } while (0)
-
-// ---------------------------------------------------------------------------
-// Long cylinders, cut into SEGMENTS for the builder (round 5).  The cylinder example's scene is box-spanning needles (random
-// end points in the scene box, examples/cylinder_primitive/main.cc:428-462): a tree over their whole boxes prunes nothing —
-// every box covers a fair part of the scene (4 200 L1 look-ups per ray, 44 Mrays/s in round 4).  So the builder is handed
-// one primitive per SEGMENT of a cylinder's axis, each with the tight box of its piece of the tube — the box of the two
-// end points of the piece, each grown by the radius the intersector uses for the whole tube, max(r0, r1)
-// (main.cc:256), plus a few ulps for the rounding of the interior end points — and the CYLINDER's id: the index array then
-// names a cylinder once per segment, a leaf tests the whole cylinder (CylinderIntersector::Intersect is a pure function of
-// (ray, cylinder, current t): testing a cylinder twice returns the same record or rejects it), and the closest hit of a
-// cylinder lies in the box of the segment it falls on.  The segment count is fixed on the host (nrtSetCylinders: length over
-// `cyl_seg_radii` tube radii, at most `cyl_split`); a cylinder of one segment keeps the reference's own box
-// (CylinderGeometry::BoundingBox, main.cc:132-165: p0 -/+ r0, p1 -/+ r1).
-// ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_cylinder_segments(const float *__restrict__ verts, const float *__restrict__ radii,
-                                                           const uint32_t *__restrict__ seg_off, uint32_t n,
-                                                           float *__restrict__ seg_verts, float *__restrict__ seg_radii,
-                                                           uint32_t *__restrict__ seg_prim) {
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  if (i >= n) return;
-  const uint32_t first = seg_off[i], K = seg_off[i + 1] - first;
-  float p0[3], p1[3];
-#pragma unroll
-  for (int k = 0; k < 3; k++) {
-    p0[k] = verts[6 * (size_t)i + k];
-    p1[k] = verts[6 * (size_t)i + 3 + k];
-  }
-  const float r0 = radii[2 * (size_t)i], r1 = radii[2 * (size_t)i + 1];
-  if (K <= 1u) { // unsplit: the reference's own box
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-      seg_verts[6 * (size_t)first + k] = p0[k];
-      seg_verts[6 * (size_t)first + 3 + k] = p1[k];
-    }
-    seg_radii[2 * (size_t)first] = r0;
-    seg_radii[2 * (size_t)first + 1] = r1;
-    seg_prim[first] = i;
-    return;
-  }
-  const float rr = r0 > r1 ? r0 : r1; // std::max<float>(r0, r1), main.cc:256
-  const float invK = 1.0f / (float)K;
-  float a[3] = {p0[0], p0[1], p0[2]};
-  // The interior end points p0 + (p1 - p0) * s are rounded: p1 - p0 alone carries an error of the order of an ulp of the
-  // CYLINDER's end points, whatever the size of the interior point itself (a long cylinder spanning the origin has interior
-  // points near 0 whose error is that of its far ends).  So the slack the radius carries is sized once, from the end points.
-  const float mag = fmaxf(fmaxf(fabsf(p0[0]), fabsf(p0[1])), fabsf(p0[2])) + fmaxf(fmaxf(fabsf(p1[0]), fabsf(p1[1])), fabsf(p1[2])) + rr;
-  const float rs = rr + 1.0e-6f * mag;
-  for (uint32_t j = 0; j < K; j++) {
-    float b[3];
-#pragma unroll
-    for (int k = 0; k < 3; k++) b[k] = (j + 1u == K) ? p1[k] : p0[k] + (p1[k] - p0[k]) * ((float)(j + 1u) * invK);
-    const size_t o = (size_t)first + j;
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-      seg_verts[6 * o + k] = a[k];
-      seg_verts[6 * o + 3 + k] = b[k];
-      a[k] = b[k];
-    }
-    seg_radii[2 * o] = rs;
-    seg_radii[2 * o + 1] = rs;
-    seg_prim[o] = i;
-  }
-}
-
-hipError_t launch_cylinder_segments(const float *verts, const float *radii, const uint32_t *seg_off, uint32_t n, float *seg_verts,
-                                    float *seg_radii, uint32_t *seg_prim, hipStream_t s) {
-  if (n == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_cylinder_segments, dim3((n + 255u) / 256u), dim3(256), 0, s, verts, radii, seg_off, n, seg_verts, seg_radii, seg_prim);
-  return hipGetLastError();
-}
 
 // Builds into caller-owned grow-only buffers (no allocation in the steady state of a per-frame rebuild).
 // The host has to learn two things from the device: that the top phase has run out of large nodes, and the tree's size

@@ -12,7 +12,7 @@
 #include <stdlib.h>
 
 #include "../../include/nanort_hip.h"
-#include "walk_variant.h" // the primitive kinds, kWide4LdsStack
+#include "walk_variant.h" // kWide4LdsStack, and through it prim_kinds.h: the primitive kinds
 
 // roctx ranges: compiled into the PROFILING library only (-DNRT_PROF -DNRT_ROCTX, nanort_amd/csrc/Makefile), so that a
 // `rocprofv3 --marker-trace --kernel-trace` run of tools/ names the build phases and every traversal launch; the product
@@ -142,6 +142,17 @@ struct alignas(16) LeafCurve {
   uint32_t pad;
 };
 static_assert(sizeof(LeafCurve) == 64, "LeafCurve");
+
+// Each record holds what its kind's row of kPrimKinds (prim_kinds.h) says a primitive consists of, and the primitive's id.
+constexpr size_t leaf_payload_bytes(int kind, int verts, size_t scalar) {
+  return (size_t)(verts * kPrimKinds[kind].pos_floats + kPrimKinds[kind].radius_floats) * scalar + sizeof(uint32_t);
+}
+static_assert(sizeof(LeafTri<float>) == leaf_payload_bytes(kPrimTriangles, 3, 4) && sizeof(LeafTri<double>) == leaf_payload_bytes(kPrimTriangles, 3, 8) + 4,
+              "LeafTri: three vertices (fp64: padded to 8 bytes)");
+static_assert(sizeof(LeafSphere<float>) == leaf_payload_bytes(kPrimSpheres, 1, 4), "LeafSphere: centre and radius");
+static_assert(sizeof(LeafCylinder<float>) == leaf_payload_bytes(kPrimCylinders, 1, 4), "LeafCylinder: two end points, two radii");
+static_assert(sizeof(LeafCurve::cp) == kPrimKinds[kPrimCurves].pos_floats * sizeof(float) && kPrimKinds[kPrimCurves].radius_floats == 4,
+              "LeafCurve: four control points; of the four radii the first and the last");
 
 // Private traversal layout: one record per BRANCH node holding BOTH children's boxes, so a
 // step fetches one record and tests two boxes.  Records are dense, in the pre-order of the

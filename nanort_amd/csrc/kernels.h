@@ -39,17 +39,6 @@ int scene_walk_blocks_per_cu();
 template <typename T>
 hipError_t launch_make_wide(const typename Wire<T>::Node *nodes, uint32_t n, uint32_t packed, uint32_t *scratch, WideNode<T> *wide,
                             Wide4Node<T> *wide4, uint32_t scramble_mod, hipStream_t s);
-template <typename T>
-hipError_t launch_gather_leaf_tris(const uint32_t *indices, const uint32_t *faces, const T *verts, LeafTri<T> *out, uint32_t n, hipStream_t s);
-template <typename T>
-hipError_t launch_gather_leaf_spheres(const uint32_t *indices, const T *centers, const T *radii, LeafSphere<T> *out, uint32_t n, hipStream_t s);
-template <typename T>
-hipError_t launch_gather_leaf_cylinders(const uint32_t *indices, const T *verts, const T *radii, LeafCylinder<T> *out, uint32_t n, hipStream_t s);
-hipError_t launch_cylinder_post(const nrt_ray_f32 *rays, const nrt_hit_f32 *compact, const uint8_t *bits, const float *verts, uint32_t n,
-                                void *out, uint8_t *mask, DoneRec *done_rec, DoneCount *done_count, uint32_t done_seq, hipStream_t s);
-hipError_t launch_gather_leaf_curves(const uint32_t *indices, const float *cps, const float *radii, LeafCurve *out, uint32_t n, hipStream_t s);
-hipError_t launch_curve_post(const nrt_ray_f32 *rays, const nrt_hit_f32 *compact, const uint8_t *bits, const float *cps, uint32_t n,
-                             void *out, uint8_t *mask, DoneRec *done_rec, DoneCount *done_count, uint32_t done_seq, hipStream_t s);
 
 // ---- multihit.hip -----------------------------------------------------------------------------------------------------
 template <typename T>
@@ -69,8 +58,6 @@ hipError_t gpu_build(hipStream_t s, const T *d_verts, const uint32_t *d_faces, c
                      uint32_t num_faces, uint32_t min_leaf, uint32_t max_depth, uint32_t bin_size, unsigned build_flags, DevBuf *workspace,
                      DevBuf *nodes_buf, DevBuf *indices_buf, void *pinned, hipEvent_t ev, std::string *err);
 hipError_t gpu_build_result(const void *pinned, hipEvent_t ev, BuildResult *res);
-hipError_t launch_cylinder_segments(const float *verts, const float *radii, const uint32_t *seg_off, uint32_t n, float *seg_verts,
-                                    float *seg_radii, uint32_t *seg_prim, hipStream_t s);
 
 // ---- refit.hip: the per-tree level plan of a refit, and one refit over it ------------------------------------------------
 size_t refit_plan_bytes(uint32_t tree_depth, uint64_t num_nodes);
@@ -82,12 +69,26 @@ hipError_t launch_refit(const void *src, size_t stride, uint32_t nv, T *verts, c
                         typename Wire<T>::Node *nodes, uint64_t num_nodes, uint32_t num_branch_records, uint32_t tree_depth,
                         const uint32_t *plan, hipStream_t s);
 
-// ---- mesh.hip: geometry taken from device memory ------------------------------------------------------------------------
+// ---- prims.hip: per primitive kind (prim_kinds.h), outside the walk ------------------------------------------------------
 // the largest of `n_indices` u32 (4-byte aligned, any length) into *out (device), 0 for none
 hipError_t launch_max_index(const uint32_t *faces, uint64_t n_indices, uint32_t *out, hipStream_t s);
 // `nv` rows of device memory, row i at byte offset i * stride with xyz first, to tight xyz (typed loads when `src` and `stride`
 // are multiples of sizeof(T), byte loads otherwise)
 template <typename T>
 hipError_t launch_gather_vertices(const void *src, size_t stride, uint32_t nv, T *tight, hipStream_t s);
+hipError_t launch_cylinder_segments(const float *verts, const float *radii, const uint32_t *seg_off, uint32_t n, float *seg_verts,
+                                    float *seg_radii, uint32_t *seg_prim, hipStream_t s);
+// the kind's Leaf* record (common.h) for each of the `n` slots of `indices`, into `out` (`faces`: triangles only, `radii`: the others)
+template <typename T>
+size_t leaf_record_bytes(int kind);
+template <typename T>
+hipError_t launch_gather_leaf(int kind, const uint32_t *indices, const uint32_t *faces, const T *verts, const T *radii, void *out, uint32_t n,
+                              hipStream_t s);
+// the pass behind a walk over a kind whose row says post_pass; it closes the launch's completion record (`done_rec`, which the walk
+// left open: done_publish == 0).  Spheres: u / v into `hits` in place.  Cylinders, curves: `hits` + `bits` are the walk's compact
+// records and {hit, cap} bits, `out` the caller's records of the row's hit_bytes, `mask` (optional) its 0/1 mask.
+template <typename T>
+hipError_t launch_post_pass(int kind, const typename Wire<T>::Ray *rays, typename Wire<T>::Hit *hits, const uint8_t *bits, const T *verts, uint32_t n,
+                            void *out, uint8_t *mask, DoneRec *done_rec, DoneCount *done_count, uint32_t done_seq, hipStream_t s);
 
 } // namespace nrt

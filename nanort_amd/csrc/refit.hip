@@ -7,10 +7,10 @@
 //                      d + 1 and their leaf children to the leaf list (slots by atomic counters: the lists' order varies
 //                      from plan to plan, no box depends on it)
 //   REFIT (every call)
-//     (mesh.hip)       launch_gather_vertices: the caller's strided vertices -> the context's tight xyz
+//     (prims.hip)      launch_gather_vertices: the caller's strided vertices -> the context's tight xyz
 //     k_refit_leaves   every reachable leaf: min / max over each coordinate of its triangles, in slot order
 //     k_refit_branches one launch per level, deepest first: union of the two children's boxes, low child first
-//   then the existing launch_gather_leaf_tris / launch_make_wide (api.hip) re-derive LeafTri and WideNode / Wide4Node.
+//   then the existing launch_gather_leaf / launch_make_wide (api.hip) re-derive LeafTri and WideNode / Wide4Node.
 //
 // Every level's boxes reach the next level through a launch boundary: no workgroup hands data to another inside a launch.
 // Records the walk from the root never reaches (adopted trees) are in neither list and are left untouched.

@@ -192,164 +192,6 @@ __global__ __launch_bounds__(kTraverseBlock) void k_traverse(const TraverseArgs<
 // ---------------------------------------------------------------------------
 enum : int { W_IDLE = 0, W_TRAV = 1, W_LEAF = 2, W_POP = 3 };
 
-// SphereIntersector::PostTraversal (examples/particle_primitive/main.cc:262-277) as a pass over the finished
-// hit records (the double-precision atan2/acos would otherwise cost the traversal kernel half its occupancy):
-// u, v = spherical coordinates of the unit normal at the hit point; atan2/acos in double as there (device
-// libm agrees with glibc to the last place or so of the double, i.e. to ~1 ulp of the float result).
-template <typename T>
-__global__ __launch_bounds__(256) void k_sphere_uv(const typename Wire<T>::Ray *__restrict__ rays,
-                                                   typename Wire<T>::Hit *__restrict__ hits,
-                                                   const T *__restrict__ centers, uint32_t n, DoneRec *done_rec,
-                                                   DoneCount *done_count, uint32_t done_seq) {
-  // (grid-stride: a bounded number of blocks, so that the completion hand-off at the end — one returning atomic per block —
-  // is paid a couple of thousand times, not once per 256 rays)
-  for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) {
-  typename Wire<T>::Hit h = hits[i];
-  if (h.prim_id == kInvalid) continue;
-  const typename Wire<T>::Ray r = rays[i];
-  const double kPi = 3.14159265358979323846;
-  const T h0 = r.org[0] + h.t * r.dir[0], h1 = r.org[1] + h.t * r.dir[1], h2 = r.org[2] + h.t * r.dir[2];
-  T n0 = h0 - centers[3 * (size_t)h.prim_id + 0], n1 = h1 - centers[3 * (size_t)h.prim_id + 1],
-    n2 = h2 - centers[3 * (size_t)h.prim_id + 2];
-  const T len = Const<T>::sqrt((n0 * n0 + n1 * n1) + n2 * n2); // vnormalize (nanort.h:383-398)
-  if (Const<T>::abs(len) > Const<T>::eps()) {
-    const T inv_len = T(1.0) / len;
-    n0 *= inv_len;
-    n1 *= inv_len;
-    n2 *= inv_len;
-  }
-  h.u = T(float(atan2(double(n0), double(n2)) + kPi) * 0.5f * float(1.0 / kPi));
-  h.v = T(float(acos(double(n1)) / kPi));
-  hits[i] = h;
-  }
-  done_end_blocks(done_rec, done_count, done_seq);
-}
-
-// CylinderIntersector::PostTraversal (examples/cylinder_primitive/main.cc:367-418) as a pass over the finished compact
-// records {u_param, v_param, t, prim} + mask {bit 0 hit, bit 1 hit_cap_}: the surface normal, into the caller's
-// 28-byte records {u, v, normal[3], t, prim_id} (t is the intersector's t; the example never writes isect->t) and
-// 0/1 mask.  `verts` holds the two end points of every cylinder (2 x xyz).  A miss writes {0, 0, 0, max_t, ~0}.
-struct CylHit32 {
-  float u, v, normal[3], t;
-  uint32_t prim_id;
-};
-static_assert(sizeof(CylHit32) == 28, "nrt_cyl_hit_f32");
-
-__global__ __launch_bounds__(256) void k_cylinder_post(const Wire<float>::Ray *__restrict__ rays,
-                                                       const Wire<float>::Hit *__restrict__ compact,
-                                                       const uint8_t *__restrict__ bits, const float *__restrict__ verts,
-                                                       uint32_t n, CylHit32 *__restrict__ out, uint8_t *__restrict__ mask,
-                                                       DoneRec *done_rec, DoneCount *done_count, uint32_t done_seq) {
-  for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) { // (grid-stride: see k_sphere_uv)
-  const Wire<float>::Hit h = compact[i];
-  const uint8_t b = bits[i];
-  CylHit32 o;
-  if (b & 1u) {
-    const Wire<float>::Ray r = rays[i];
-    const float *p0 = verts + 3 * (size_t)(2 * h.prim_id), *p1 = p0 + 3;
-    float d01[3], pos[3], nrm[3];
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-      d01[k] = p1[k] - p0[k];
-      pos[k] = r.org[k] + r.dir[k] * h.t;
-    }
-    if (b & 2u) { // a cap: +-axis, whichever faces the hit point from the cylinder's middle
-      float pc[3];
-      cyl_normalize<float>(d01, nrm);
-#pragma unroll
-      for (int k = 0; k < 3; k++) pc[k] = pos[k] - (d01[k] * 0.5f + p0[k]);
-      if (!(cyl_dot<float>(pc, nrm) > 0.0f)) {
-        nrm[0] = -nrm[0];
-        nrm[1] = -nrm[1];
-        nrm[2] = -nrm[2];
-      }
-    } else { // the side: away from the axis point at parameter v
-      float pc[3];
-#pragma unroll
-      for (int k = 0; k < 3; k++) pc[k] = pos[k] - (p0[k] + h.v * d01[k]);
-      cyl_normalize<float>(pc, nrm);
-    }
-    o.u = h.u;
-    o.v = h.v;
-    o.normal[0] = nrm[0];
-    o.normal[1] = nrm[1];
-    o.normal[2] = nrm[2];
-    o.t = h.t;
-    o.prim_id = h.prim_id;
-  } else {
-    o.u = o.v = 0.0f;
-    o.normal[0] = o.normal[1] = o.normal[2] = 0.0f;
-    o.t = h.t; // the kernel's miss record carries max_t
-    o.prim_id = kInvalid;
-  }
-  out[i] = o;
-  if (mask) mask[i] = b & 1u;
-  }
-  done_end_blocks(done_rec, done_count, done_seq);
-}
-
-// CurveIntersector::PostTraversal (examples/curves_primitive/main.cc:789-823) as a pass over the finished compact records
-// {u_param, v_param, t, prim} + 0/1 mask: the curve's tangent at u (EvaluateBezierTangent :456-462, the power-basis
-// coefficients in the example's association) and the normal vnormalize(cross(cross(dir, tangent), tangent)), into the caller's
-// 40-byte records {t, prim_id, u, v, tangent[3], normal[3]}.  `cps` holds the four control points of every curve (4 x xyz).
-// vnormalize (nanort.h:388-398) leaves a vector shorter than epsilon as it is.  A miss writes {max_t, ~0, 0, 0, 0, 0}.
-struct CurveHit32 {
-  float t;
-  uint32_t prim_id;
-  float u, v, tangent[3], normal[3];
-};
-static_assert(sizeof(CurveHit32) == 40, "nrt_curve_hit_f32");
-
-__global__ __launch_bounds__(256) void k_curve_post(const Wire<float>::Ray *__restrict__ rays,
-                                                    const Wire<float>::Hit *__restrict__ compact,
-                                                    const uint8_t *__restrict__ bits, const float *__restrict__ cps, uint32_t n,
-                                                    CurveHit32 *__restrict__ out, uint8_t *__restrict__ mask, DoneRec *done_rec,
-                                                    DoneCount *done_count, uint32_t done_seq) {
-  for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) { // (grid-stride: see k_sphere_uv)
-  const Wire<float>::Hit h = compact[i];
-  const uint8_t b = bits[i];
-  CurveHit32 o;
-  if (b & 1u) {
-    const Wire<float>::Ray r = rays[i];
-    const float *v = cps + 12 * (size_t)h.prim_id;
-    float dv[3], tan[3], c1[3], c2[3];
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-      const float v0 = v[k], v1 = v[3 + k], v2 = v[6 + k], v3 = v[9 + k];
-      const float C1 = ((v3 - v2 * 3.0f) + v1 * 3.0f) - v0;
-      const float C2 = (v2 * 3.0f - v1 * 6.0f) + v0 * 3.0f;
-      const float C3 = v1 * 3.0f - v0 * 3.0f;
-      dv[k] = (((C1 * 3.0f) * h.u) * h.u + (C2 * 2.0f) * h.u) + C3;
-    }
-    cyl_normalize<float>(dv, tan);
-    const float dir[3] = {r.dir[0], r.dir[1], r.dir[2]};
-    c1[0] = dir[1] * tan[2] - dir[2] * tan[1]; // vcross (nanort.h:400-407)
-    c1[1] = dir[2] * tan[0] - dir[0] * tan[2];
-    c1[2] = dir[0] * tan[1] - dir[1] * tan[0];
-    c2[0] = c1[1] * tan[2] - c1[2] * tan[1];
-    c2[1] = c1[2] * tan[0] - c1[0] * tan[2];
-    c2[2] = c1[0] * tan[1] - c1[1] * tan[0];
-    cyl_normalize<float>(c2, o.normal);
-    o.tangent[0] = tan[0];
-    o.tangent[1] = tan[1];
-    o.tangent[2] = tan[2];
-    o.t = h.t;
-    o.prim_id = h.prim_id;
-    o.u = h.u;
-    o.v = h.v;
-  } else {
-    o.t = h.t; // the kernel's miss record carries max_t
-    o.prim_id = kInvalid;
-    o.u = o.v = 0.0f;
-    o.tangent[0] = o.tangent[1] = o.tangent[2] = 0.0f;
-    o.normal[0] = o.normal[1] = o.normal[2] = 0.0f;
-  }
-  out[i] = o;
-  if (mask) mask[i] = b & 1u;
-  }
-  done_end_blocks(done_rec, done_count, done_seq);
-}
-
 // Both child boxes of one WideNode at once.  For fp32 the two boxes ride in the two halves of
 // 64-bit register pairs, so the subtract / multiply chain issues as v_pk_add_f32 / v_pk_mul_f32
 // (one VALU slot for two IEEE operations: same operations, same rounding, half the issue slots).
@@ -2305,81 +2147,6 @@ __global__ __launch_bounds__(256) void k_make_wide(const typename Wire<T>::Node 
   wide4[dense_of[i]] = q;
 }
 
-// Leaf-ordered triangle records from (indices, faces, tight vertices).
-template <typename T>
-__global__ __launch_bounds__(256) void k_gather_leaf_tris(const uint32_t *__restrict__ indices,
-                                                          const uint32_t *__restrict__ faces,
-                                                          const T *__restrict__ verts,
-                                                          LeafTri<T> *__restrict__ out, uint32_t n) {
-  const uint32_t s = blockIdx.x * 256u + threadIdx.x;
-  if (s >= n) return;
-  const uint32_t prim = indices[s];
-  const uint32_t f0 = faces[3 * (size_t)prim + 0], f1 = faces[3 * (size_t)prim + 1],
-                 f2 = faces[3 * (size_t)prim + 2];
-  LeafTri<T> t;
-#pragma unroll
-  for (int k = 0; k < 3; k++) {
-    t.p0[k] = verts[3 * (size_t)f0 + k];
-    t.p1[k] = verts[3 * (size_t)f1 + k];
-    t.p2[k] = verts[3 * (size_t)f2 + k];
-  }
-  t.prim_id = prim;
-  out[s] = t;
-}
-
-// Leaf-ordered sphere records from (indices, centers, radii).
-template <typename T>
-__global__ __launch_bounds__(256) void k_gather_leaf_spheres(const uint32_t *__restrict__ indices,
-                                                             const T *__restrict__ centers, const T *__restrict__ radii,
-                                                             LeafSphere<T> *__restrict__ out, uint32_t n) {
-  const uint32_t s = blockIdx.x * 256u + threadIdx.x;
-  if (s >= n) return;
-  const uint32_t prim = indices[s];
-  LeafSphere<T> r;
-#pragma unroll
-  for (int k = 0; k < 3; k++) r.c[k] = centers[3 * (size_t)prim + k];
-  r.r = radii[prim];
-  r.prim_id = prim;
-  out[s] = r;
-}
-
-// Leaf-ordered cylinder records from (indices, end points, radii).
-template <typename T>
-__global__ __launch_bounds__(256) void k_gather_leaf_cylinders(const uint32_t *__restrict__ indices,
-                                                               const T *__restrict__ verts, const T *__restrict__ radii,
-                                                               LeafCylinder<T> *__restrict__ out, uint32_t n) {
-  const uint32_t s = blockIdx.x * 256u + threadIdx.x;
-  if (s >= n) return;
-  const uint32_t prim = indices[s];
-  LeafCylinder<T> r;
-#pragma unroll
-  for (int k = 0; k < 3; k++) {
-    r.p0[k] = verts[3 * (size_t)(2 * prim) + k];
-    r.p1[k] = verts[3 * (size_t)(2 * prim + 1) + k];
-  }
-  r.r0 = radii[2 * (size_t)prim];
-  r.r1 = radii[2 * (size_t)prim + 1];
-  r.prim_id = prim;
-  out[s] = r;
-}
-
-// Leaf-ordered curve records from (indices, control points, radii): of a curve's four radii the intersector reads the first
-// and the last.  Every byte of the 64-byte record is written.
-__global__ __launch_bounds__(256) void k_gather_leaf_curves(const uint32_t *__restrict__ indices, const float *__restrict__ cps,
-                                                            const float *__restrict__ radii, LeafCurve *__restrict__ out, uint32_t n) {
-  const uint32_t s = blockIdx.x * 256u + threadIdx.x;
-  if (s >= n) return;
-  const uint32_t prim = indices[s];
-  LeafCurve r;
-#pragma unroll
-  for (int k = 0; k < 12; k++) r.cp[k] = cps[12 * (size_t)prim + k];
-  r.r0 = radii[4 * (size_t)prim];
-  r.r3 = radii[4 * (size_t)prim + 3];
-  r.prim_id = prim;
-  r.pad = 0u;
-  out[s] = r;
-}
-
 // ---- host-side launchers (kernels.h) ----------------------------------------
 
 template <typename T>
@@ -2442,9 +2209,6 @@ hipError_t launch_traverse_wide(const TraverseArgs<T> &args, unsigned grid, int 
   launch_persistent(k->kernel, grid, args, s);
   NRT_RANGE_POP();
   if (name_out) *name_out = k->name;
-  if (prim_kind == kPrimSpheres && args.hits) // (args.done_publish == 0: this pass closes the launch's completion record)
-    hipLaunchKernelGGL((k_sphere_uv<T>), dim3(std::min((args.num_rays + 255u) / 256u, 2048u)), dim3(256), 0, s, args.rays, args.hits,
-                       args.centers, args.num_rays, args.done_publish ? nullptr : args.done_rec, args.done_count, args.done_seq);
   return hipGetLastError();
 }
 
@@ -2467,62 +2231,10 @@ hipError_t launch_make_wide(const typename Wire<T>::Node *nodes, uint32_t n, uin
   return hipGetLastError();
 }
 
-template <typename T>
-hipError_t launch_gather_leaf_tris(const uint32_t *indices, const uint32_t *faces, const T *verts,
-                                   LeafTri<T> *out, uint32_t n, hipStream_t s) {
-  if (n == 0) return hipSuccess;
-  hipLaunchKernelGGL((k_gather_leaf_tris<T>), dim3((n + 255u) / 256u), dim3(256), 0, s, indices,
-                     faces, verts, out, n);
-  return hipGetLastError();
-}
-
-template <typename T>
-hipError_t launch_gather_leaf_spheres(const uint32_t *indices, const T *centers, const T *radii, LeafSphere<T> *out,
-                                      uint32_t n, hipStream_t s) {
-  if (n == 0) return hipSuccess;
-  hipLaunchKernelGGL((k_gather_leaf_spheres<T>), dim3((n + 255u) / 256u), dim3(256), 0, s, indices, centers, radii, out, n);
-  return hipGetLastError();
-}
-
-template <typename T>
-hipError_t launch_gather_leaf_cylinders(const uint32_t *indices, const T *verts, const T *radii, LeafCylinder<T> *out,
-                                        uint32_t n, hipStream_t s) {
-  if (n == 0) return hipSuccess;
-  hipLaunchKernelGGL((k_gather_leaf_cylinders<T>), dim3((n + 255u) / 256u), dim3(256), 0, s, indices, verts, radii, out, n);
-  return hipGetLastError();
-}
-NRT_INSTANTIATE_F32_F64(launch_gather_leaf_cylinders)
-
-hipError_t launch_cylinder_post(const nrt_ray_f32 *rays, const nrt_hit_f32 *compact, const uint8_t *bits, const float *verts,
-                                uint32_t n, void *out, uint8_t *mask, DoneRec *done_rec, DoneCount *done_count, uint32_t done_seq,
-                                hipStream_t s) {
-  if (n == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_cylinder_post, dim3(std::min((n + 255u) / 256u, 2048u)), dim3(256), 0, s, rays, compact, bits, verts, n,
-                     (CylHit32 *)out, mask, done_rec, done_count, done_seq);
-  return hipGetLastError();
-}
-
-hipError_t launch_gather_leaf_curves(const uint32_t *indices, const float *cps, const float *radii, LeafCurve *out, uint32_t n,
-                                     hipStream_t s) {
-  if (n == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_gather_leaf_curves, dim3((n + 255u) / 256u), dim3(256), 0, s, indices, cps, radii, out, n);
-  return hipGetLastError();
-}
-
-hipError_t launch_curve_post(const nrt_ray_f32 *rays, const nrt_hit_f32 *compact, const uint8_t *bits, const float *cps, uint32_t n,
-                             void *out, uint8_t *mask, DoneRec *done_rec, DoneCount *done_count, uint32_t done_seq, hipStream_t s) {
-  if (n == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_curve_post, dim3(std::min((n + 255u) / 256u, 2048u)), dim3(256), 0, s, rays, compact, bits, cps, n,
-                     (CurveHit32 *)out, mask, done_rec, done_count, done_seq);
-  return hipGetLastError();
-}
-
 NRT_INSTANTIATE_F32_F64(launch_traverse)
 NRT_INSTANTIATE_F32_F64(launch_traverse_wide)
 NRT_INSTANTIATE_F32_F64(traverse_wide_blocks_per_cu)
-NRT_INSTANTIATE_F32_F64(launch_gather_leaf_spheres)
 NRT_INSTANTIATE_F32_F64(launch_make_wide)
 NRT_INSTANTIATE_F32_F64(traverse_blocks_per_cu)
-NRT_INSTANTIATE_F32_F64(launch_gather_leaf_tris)
 
 } // namespace nrt

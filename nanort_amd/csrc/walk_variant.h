@@ -3,11 +3,10 @@
 // launch_plan.h, so that tests/cpp/walk_variant_check.cc can sweep the whole input space on a machine without a GPU: hit
 // records are identical under every variant, so no parity test notices a wrong pick.
 #pragma once
+#include "prim_kinds.h" // kPrim*
 
 namespace nrt {
 
-enum : int { kPrimTriangles = 0, kPrimSpheres = 1, kPrimCylinders = 2, kPrimCurves = 3 };
-constexpr int kNumPrimKinds = 4;
 #ifndef NRT_W4_LDS_STACK
 #define NRT_W4_LDS_STACK 12
 #endif

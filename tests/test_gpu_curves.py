@@ -241,7 +241,8 @@ def test_every_other_entry_point_refuses_a_curve_context(rays):
 
 def test_one_context_through_triangles_curves_spheres_curves(rays):
     """No state of one kind survives into the next: the same context as a triangle mesh, curves, spheres and other curves with
-    another subdivision count, compared after every switch."""
+    another subdivision count, then as cut cylinders, spheres and curves set from device memory, uncut cylinders and a mesh set from
+    device memory, compared after every switch."""
     from oracle import bindings as ob
 
     v, f = scenes.load_c1_mesh()
@@ -265,6 +266,59 @@ def test_one_context_through_triangles_curves_spheres_curves(rays):
     fc, fr = cf.fur()
     assert a.Build(400, CurveGeometry(fc, fr))
     check_against_model(a, fc, fr, rays)
+    # ... and on through the setters that share one path (api.hip), 64 primitives and 256 rays a stage: what one of them could leave
+    # behind for the next is the segment array, the radii, the faces, test_cap and the subdivision count
+    import torch
+
+    from nanort_amd import CylinderGeometry
+    from test_gpu_cylinders import check as check_cylinders
+    from test_gpu_prim_kinds import aimed, box_mesh
+    from test_gpu_spheres import check as check_spheres
+
+    # 1. cylinders long enough to be cut: needles of 50 radii, so seven segments each at the default cyl_split / cyl_seg_radii
+    cv, _ = scenes.random_cylinders(64)
+    length = np.linalg.norm(cv[:, 1].astype(np.float64) - cv[:, 0], axis=1)
+    cr = np.repeat((length / 50.0).astype(np.float32)[:, None], 2, axis=1)
+    assert float((length / cr[:, 0]).min()) >= 40.0
+    crays = aimed(scenes.particle_camera_rays(16, 16), cv.mean(axis=1))
+    assert a.Build(64, CylinderGeometry(cv, cr))
+    nodes, idx = a.GetTree()
+    assert idx.shape[0] > 64 and sorted(set(idx.tolist())) == list(range(64))  # (num_segs > n)
+    h, m = a.TraverseBatch(crays)
+    check_cylinders(h, m, *ob.CylinderOracle().traverse(nodes, idx, cv, cr, crays))
+    assert int(m.sum()) >= 32
+    # 2. spheres, from device memory
+    sc, sr = scenes.random_spheres(64)
+    srays = aimed(scenes.particle_camera_rays(16, 16), sc)
+    a.SetSpheresDevice(torch.from_numpy(sc).cuda(), torch.from_numpy(sr).cuda())
+    assert a.BuildCurrent()
+    nodes, idx = a.GetTree()
+    assert sorted(idx.tolist()) == list(range(64))
+    h, m = a.TraverseBatch(srays)
+    check_spheres(h, m, *ob.SphereOracle().traverse(nodes, idx, sc, sr, srays))
+    assert int(m.sum()) >= 32
+    # 3. curves, from device memory, three subdivisions
+    hc, hr = cf.hair(64)
+    hrays = aimed(cf.camera(16, 16), (hc[:, 0] + 3 * hc[:, 1] + 3 * hc[:, 2] + hc[:, 3]) / np.float32(8))
+    a.SetCurvesDevice(torch.from_numpy(hc).cuda(), torch.from_numpy(hr).cuda(), 3)
+    assert a.BuildCurrent()
+    check_against_model(a, hc, hr, hrays, 3)
+    # 4. the same cylinders uncut (cyl_split = 1), without their caps: the tree is over the 64 whole boxes
+    a.SetTunable("cyl_split", 1)
+    assert a.Build(64, CylinderGeometry(cv, cr, test_cap=False))
+    nodes, idx = a.GetTree()
+    assert sorted(idx.tolist()) == list(range(64))
+    h, m = a.TraverseBatch(crays)
+    check_cylinders(h, m, *ob.CylinderOracle().traverse(nodes, idx, cv, cr, crays, test_cap=False))
+    assert int(m.sum()) >= 32
+    # 5. triangles, from device memory: the 12-triangle box
+    bv, bf = box_mesh()
+    brays = scenes.camera_rays(16, 16)
+    assert a.BuildDevice(torch.from_numpy(bv).cuda(), torch.from_numpy(bf.view(np.int32).copy()).cuda())
+    nodes, idx = a.GetTree()
+    h, m = a.TraverseBatch(brays)
+    oh, om = ob.Oracle().traverse(nodes, idx, bv, bf, brays)
+    assert h.tobytes() == oh.tobytes() and np.array_equal(m, om) and m.any()
 
 
 def test_header_backend_build_and_batch_equal_the_host_loop(tmp_path):

@@ -1,4 +1,4 @@
-"""Device-resident geometry (nrtSetMeshDevice_* / nrtSetSpheresDevice_f32, nanort_amd/csrc/mesh.hip): a context fed from torch
+"""Device-resident geometry (nrtSetMeshDevice_* / nrtSetSpheresDevice_f32, nanort_amd/csrc/prims.hip): a context fed from torch
 tensors ends in the state the host call leaves, so the tree built over it and every trace of it are byte-identical to the host
 path's — no tolerance anywhere (builder determinism across contexts is the library's contract).  Also: the index reduction at
 wave / block / 128-bit boundaries, strides, views, a side stream, the lifecycle, the num_vertices guard and the refusals."""
