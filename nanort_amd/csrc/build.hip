@@ -18,8 +18,8 @@
 //                    the next level's active list).  Four kernels per level:
 //                    bins and accumulators are handed on clean by their
 //                    consumers (clean_bins) instead of being re-initialised.
-//   SUBTREE PHASE    one wave per node with <= kSmall primitives builds the
-//                    whole subtree out of LDS (lane == split candidate).
+//   SUBTREE PHASE    one wave per node with <= kHandoff primitives builds the
+//                    whole subtree out of LDS (build_subtree.hip, launch_subtree).
 //   RELAYOUT         subtree sizes bottom-up, DFS pre-order indices top-down,
 //                    splice of the per-wave subtrees (the GPU analogue of the
 //                    reference's shallow-tree splice, nanort.h:2040-2059), so
@@ -36,6 +36,11 @@
 //   * the partition is stable and the whole build is deterministic.
 // Hit records do not depend on tree topology, which is what
 // parity is judged on.
+//
+// Where the rules live: build_dev.h states each decision once — bins (node_bins, bin_of, record_bins), cost (sah_cost),
+// leaf rule (LeafRule, is_leaf), partition predicate (goes_left), median fallback, bins handed on clean (take_bin,
+// empty_box_e) — and the kernels of both phases call it.  This file: primitive records, Morton pre-pass, top phase, relayout,
+// emission and the host driver.
 #include <stddef.h>
 #include <stdlib.h>
 
@@ -43,24 +48,14 @@
 #include <string>
 #include <vector>
 
+
+#include "build_dev.h"
 #include "kernels.h"
 #include "minmax_dev.h"
 #include "prims_dev.h"
 
 namespace nrt {
 
-constexpr int kSmall = 256;     // nodes at or below this many primitives are binned with kSmallBins bins (part of the tree's definition)
-#ifndef NRT_BUILD_HANDOFF
-#define NRT_BUILD_HANDOFF 256
-#endif
-// Nodes at or below this many primitives leave the level-synchronous top phase for the one-wave-per-node subtree phase.
-// Both phases take the same decisions for a node (same bins — see node_bins —, same cost, same tie rules, same leaf rule),
-// so this is a scheduling knob: any value <= kSmall gives the same tree (tools/tree_hash.py).
-constexpr int kHandoff = NRT_BUILD_HANDOFF;
-static_assert(kHandoff <= kSmall && kHandoff >= 64, "hand-off size");
-#ifndef NRT_SUBTREE_REC_LDS
-#define NRT_SUBTREE_REC_LDS 0 // 1: k_subtree copies its node's primitive records into LDS (10 KB per wave: 10 waves per CU instead of 22; measured slower, profiles/r02j_build_subtree_ab.txt)
-#endif
 #ifndef NRT_BIN_REPL
 #define NRT_BIN_REPL 4 // copies of k_bin's LDS bins (fp64: at most 2), neighbouring lanes on different copies: 1 M 1.418 -> 1.314 ms, fp64 2.13 -> 2.08 (1 / 2 / 4 / 8 copies: 1.414 / 1.343 / 1.312 / 1.330; profiles/r05l_bin_repl_variants.txt)
 #endif
@@ -71,283 +66,11 @@ static_assert(kHandoff <= kSmall && kHandoff >= 64, "hand-off size");
 #define NRT_BUILD_TILE 2048
 #endif
 constexpr int kTile = NRT_BUILD_TILE; // primitives per top-phase chunk (256 threads x kTile / 256 rounds); any value gives the same tree
-constexpr int kMaxBins = 64;    // top phase: lane == bin
-constexpr int kSmallBins = 16;  // subtree phase: 3 x 15 candidates == 45 lanes
-constexpr uint32_t kMedian = 0xFFFFFFFFu;
 constexpr int kSceneReplicas = 16; // k_prim_records spreads its per-block atomics on the scene bounds over this many copies
-[[maybe_unused]] constexpr int kSubStack = 48; // pending high-side children per subtree wave of k_subtree (LDS; profiling build)
-constexpr int kSubStackSafe = 36; // above this many, splits are forced to the object median (depth <= log2 n more)
-
-enum : uint32_t { KIND_SPLIT = 0, KIND_SMALL = 1, KIND_LEAF = 2 };
-
-// ---- order-preserving integer images of floating-point values ---------------
-template <typename T>
-struct Ord;
-template <>
-struct Ord<float> {
-  typedef uint32_t U;
-  static __host__ __device__ __forceinline__ U enc(float f) {
-    uint32_t u;
-    __builtin_memcpy(&u, &f, 4);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-  }
-  static __host__ __device__ __forceinline__ float dec(U e) {
-    uint32_t u = (e & 0x80000000u) ? (e & 0x7FFFFFFFu) : ~e;
-    float f;
-    __builtin_memcpy(&f, &u, 4);
-    return f;
-  }
-  static __host__ __device__ __forceinline__ U lowest() { return 0u; }
-  static __host__ __device__ __forceinline__ U highest() { return 0xFFFFFFFFu; }
-};
-template <>
-struct Ord<double> {
-  typedef unsigned long long U;
-  static __host__ __device__ __forceinline__ U enc(double f) {
-    unsigned long long u;
-    __builtin_memcpy(&u, &f, 8);
-    return (u & 0x8000000000000000ull) ? ~u : (u | 0x8000000000000000ull);
-  }
-  static __host__ __device__ __forceinline__ double dec(U e) {
-    unsigned long long u = (e & 0x8000000000000000ull) ? (e & 0x7FFFFFFFFFFFFFFFull) : ~e;
-    double f;
-    __builtin_memcpy(&f, &u, 8);
-    return f;
-  }
-  static __host__ __device__ __forceinline__ U lowest() { return 0ull; }
-  static __host__ __device__ __forceinline__ U highest() { return 0xFFFFFFFFFFFFFFFFull; }
-};
-
-// Primitive record carried (and physically partitioned) through the build.
-template <typename T>
-struct alignas(8) PrimRec {
-  T bmin[3];
-  T bmax[3];
-  T c[3];
-  uint32_t prim;
-};
-static_assert(sizeof(PrimRec<float>) == 40, "PrimRec<float>");
-static_assert(sizeof(PrimRec<double>) == 80, "PrimRec<double>");
-
-template <typename T>
-struct TopNode {
-  T bmin[3], bmax[3]; // node AABB
-  T cmin[3], cmax[3]; // centroid bounds
-  uint32_t l, r;      // primitive range
-  uint32_t depth;
-  uint32_t kind;
-  int32_t axis;
-  uint32_t split_bin; // kMedian: object-median fallback (reference nanort.h:1849)
-  uint32_t nleft;
-  uint32_t child0;    // top index of the low-side child; high side is child0 + 1
-  uint32_t size;      // nodes in this subtree
-  uint32_t dfs;       // final node index
-  uint32_t buf;       // record buffer holding [l, r) once the node stops splitting
-  uint32_t chunk_base, nchunks;
-  uint32_t parent;    // top index of the parent | kHighChild when this is its high-side child; kNoParent for node 0
-};
-constexpr uint32_t kHighChild = 0x80000000u, kNoParent = 0x7FFFFFFFu;
-
-template <typename T>
-struct BoundsAcc { // integer-ordered images: bmin[3] bmax[3] cmin[3] cmax[3]
-  typename Ord<T>::U v[12];
-};
-
-constexpr int kMaxTopLevels = 120; // top-phase levels recorded for the relayout
-
-// Device-resident state of the top phase: the host launches level after level with
-// upper-bound grids and reads this back only to decide when to stop.
-struct LevelInfo {
-  uint32_t num_active;  // SPLIT nodes of the level being processed
-  uint32_t num_chunks;
-  uint32_t num_small;   // running count of subtree tasks (all levels)
-  uint32_t max_depth;   // stats
-  uint32_t num_leaves;
-  uint32_t num_branches;
-  uint32_t max_leaf_count;
-  uint32_t error;       // 1: top array capacity exceeded
-  uint32_t cand_begin, cand_end; // top nodes created by the previous level (candidates for this one)
-  uint32_t top_count;   // top nodes allocated so far
-  uint32_t child_base;  // first top index of the children created by the level being processed
-  uint32_t top_cap;
-  uint32_t num_levels;  // levels recorded in level_begin
-  uint32_t num_nodes;   // nodes of the finished tree (k_layout)
-  uint32_t level_begin[kMaxTopLevels + 2];
-};
-
-template <typename T>
-__device__ __forceinline__ T bin_scale(T lo, T hi, int K) {
-  const T ext = hi - lo;
-  return (ext > T(0)) ? T(K) / ext : T(0);
-}
-// Bins of a node of n primitives: `kpack` carries the build's bin count for large nodes (low byte) and the one for nodes
-// of at most kSmall primitives (second byte) — the subtree phase's lane == (axis, bin) layout holds 16.
-__device__ __forceinline__ int node_bins(int kpack, uint32_t n) { return n <= (uint32_t)kSmall ? ((kpack >> 8) & 0xFF) : (kpack & 0xFF); }
-template <typename T>
-__device__ __forceinline__ int bin_of(T c, T lo, T scale, int K) {
-  int i = (int)((c - lo) * scale);
-  i = i < 0 ? 0 : i;
-  return i > K - 1 ? K - 1 : i;
-}
-template <typename T>
-__device__ __forceinline__ T half_area(const T mn[3], const T mx[3]) {
-  const T a = mx[0] - mn[0], b = mx[1] - mn[1], c = mx[2] - mn[2];
-  return a * b + b * c + c * a; // CalculateSurfaceArea / 2 (nanort.h:1278-1283)
-}
-
-// ---- DPP (data-parallel primitive) moves inside 16-lane rows: VALU operand modifiers, no LDS
-// crossbar (ds_bpermute) round trip.  row_shr:n = 0x110+n, row_shl:n = 0x100+n; a lane without a
-// source keeps `old`, so `old` = the identity of the operation gives a clean scan step.
-template <int CTRL>
-__device__ __forceinline__ uint32_t dpp_u32(uint32_t old, uint32_t src) {
-  return (uint32_t)__builtin_amdgcn_update_dpp((int)old, (int)src, CTRL, 0xF, 0xF, false);
-}
-template <int CTRL>
-__device__ __forceinline__ float dpp_mov(float old, float src) {
-  return __builtin_bit_cast(float, dpp_u32<CTRL>(__builtin_bit_cast(uint32_t, old), __builtin_bit_cast(uint32_t, src)));
-}
-template <int CTRL>
-__device__ __forceinline__ double dpp_mov(double old, double src) {
-  const unsigned long long o = __builtin_bit_cast(unsigned long long, old), v = __builtin_bit_cast(unsigned long long, src);
-  const uint32_t lo = dpp_u32<CTRL>((uint32_t)o, (uint32_t)v), hi = dpp_u32<CTRL>((uint32_t)(o >> 32), (uint32_t)(v >> 32));
-  return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
-}
-template <int CTRL>
-__device__ __forceinline__ uint32_t dpp_mov(uint32_t old, uint32_t src) {
-  return dpp_u32<CTRL>(old, src);
-}
 
 // ---------------------------------------------------------------------------
 // primitive records + scene bounds
 // ---------------------------------------------------------------------------
-// Wave-uniform broadcast of lane `src` (an SGPR): v_readlane, no LDS crossbar round trip.
-__device__ __forceinline__ uint32_t lane_bcast(uint32_t x, int src) { return (uint32_t)__builtin_amdgcn_readlane((int)x, src); }
-__device__ __forceinline__ float lane_bcast(float x, int src) {
-  return __builtin_bit_cast(float, lane_bcast(__builtin_bit_cast(uint32_t, x), src));
-}
-__device__ __forceinline__ double lane_bcast(double x, int src) {
-  const unsigned long long v = __builtin_bit_cast(unsigned long long, x);
-  const uint32_t lo = lane_bcast((uint32_t)v, src), hi = lane_bcast((uint32_t)(v >> 32), src);
-  return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
-}
-__device__ __forceinline__ unsigned long long lane_bcast(unsigned long long v, int src) {
-  const uint32_t lo = lane_bcast((uint32_t)v, src), hi = lane_bcast((uint32_t)(v >> 32), src);
-  return ((unsigned long long)hi << 32) | lo;
-}
-template <int CTRL>
-__device__ __forceinline__ unsigned long long dpp_mov(unsigned long long old, unsigned long long src) {
-  const uint32_t lo = dpp_u32<CTRL>((uint32_t)old, (uint32_t)src), hi = dpp_u32<CTRL>((uint32_t)(old >> 32), (uint32_t)(src >> 32));
-  return ((unsigned long long)hi << 32) | lo;
-}
-// The subtree kernel is bound by VALU issue (a wave instruction costs the same for 5 active lanes as for 64), so its
-// scans and reductions run on the ORDER-PRESERVING INTEGER IMAGES of the values (Ord<T>): for fp32 the compiler then
-// folds each DPP move into the v_min_u32 / v_max_u32 that consumes it — one instruction per scan step and value where
-// the float form (compare + select on a separately moved operand) takes three.
-template <typename U>
-__device__ __forceinline__ U umin_(U a, U b) {
-  return a < b ? a : b;
-}
-template <typename U>
-__device__ __forceinline__ U umax_(U a, U b) {
-  return a > b ? a : b;
-}
-template <typename T, int CTRL>
-__device__ __forceinline__ void row_scan_step_e(uint32_t &cnt, typename Ord<T>::U mn[3], typename Ord<T>::U mx[3]) {
-  cnt += dpp_mov<CTRL>(0u, cnt);
-#pragma unroll
-  for (int d = 0; d < 3; d++) {
-    mn[d] = umin_(mn[d], dpp_mov<CTRL>(Ord<T>::highest(), mn[d]));
-    mx[d] = umax_(mx[d], dpp_mov<CTRL>(Ord<T>::lowest(), mx[d]));
-  }
-}
-template <typename T>
-__device__ __forceinline__ void row_prefix_e(uint32_t &cnt, typename Ord<T>::U mn[3], typename Ord<T>::U mx[3]) {
-  row_scan_step_e<T, 0x111>(cnt, mn, mx);
-  row_scan_step_e<T, 0x112>(cnt, mn, mx);
-  row_scan_step_e<T, 0x114>(cnt, mn, mx);
-  row_scan_step_e<T, 0x118>(cnt, mn, mx);
-}
-template <typename T>
-__device__ __forceinline__ void row_suffix_e(uint32_t &cnt, typename Ord<T>::U mn[3], typename Ord<T>::U mx[3]) {
-  row_scan_step_e<T, 0x101>(cnt, mn, mx);
-  row_scan_step_e<T, 0x102>(cnt, mn, mx);
-  row_scan_step_e<T, 0x104>(cnt, mn, mx);
-  row_scan_step_e<T, 0x108>(cnt, mn, mx);
-}
-// All-reduce min / max with a wave-uniform result: 4 DPP steps leave every lane with its row's value (quad_perm
-// [1,0,3,2], [2,3,0,1], row_half_mirror, row_mirror; `old` = the identity so that the move folds into the min / max),
-// the four rows are combined through scalar registers.
-template <typename U>
-__device__ __forceinline__ U wave_umin(U x) {
-  x = umin_(x, dpp_mov<0xB1>((U)~(U)0, x));
-  x = umin_(x, dpp_mov<0x4E>((U)~(U)0, x));
-  x = umin_(x, dpp_mov<0x141>((U)~(U)0, x));
-  x = umin_(x, dpp_mov<0x140>((U)~(U)0, x));
-  return umin_(umin_(lane_bcast(x, 0), lane_bcast(x, 16)), umin_(lane_bcast(x, 32), lane_bcast(x, 48)));
-}
-template <typename U>
-__device__ __forceinline__ U wave_umax(U x) {
-  x = umax_(x, dpp_mov<0xB1>((U)0, x));
-  x = umax_(x, dpp_mov<0x4E>((U)0, x));
-  x = umax_(x, dpp_mov<0x141>((U)0, x));
-  x = umax_(x, dpp_mov<0x140>((U)0, x));
-  return umax_(umax_(lane_bcast(x, 0), lane_bcast(x, 16)), umax_(lane_bcast(x, 32), lane_bcast(x, 48)));
-}
-template <typename T>
-__device__ __forceinline__ T wave_min_u(T x) {
-  return Ord<T>::dec(wave_umin<typename Ord<T>::U>(Ord<T>::enc(x)));
-}
-template <typename T>
-__device__ __forceinline__ T wave_max_u(T x) {
-  return Ord<T>::dec(wave_umax<typename Ord<T>::U>(Ord<T>::enc(x)));
-}
-
-// Inclusive scans over all 64 lanes (k_split: lane == bin, up to 64 bins): the row scans above, then each row takes
-// the totals of the rows before (prefix) / after (suffix) it, which travel through scalar registers.
-template <typename U, bool MIN>
-__device__ __forceinline__ U row_carry(U x, U t_a, U t_b, U t_c, unsigned row, bool prefix) {
-  // prefix: t_a, t_b, t_c = totals of rows 0, 1, 2;  suffix: totals of rows 1, 2, 3
-  const U id = MIN ? (U) ~(U)0 : (U)0;
-  auto op = [](U p, U q) { return MIN ? umin_(p, q) : umax_(p, q); };
-  U c;
-  if (prefix)
-    c = row == 0 ? id : (row == 1 ? t_a : (row == 2 ? op(t_a, t_b) : op(op(t_a, t_b), t_c)));
-  else
-    c = row == 3 ? id : (row == 2 ? t_c : (row == 1 ? op(t_b, t_c) : op(op(t_a, t_b), t_c)));
-  return op(x, c);
-}
-template <typename T>
-__device__ __forceinline__ void wave_prefix_e(uint32_t &cnt, typename Ord<T>::U mn[3], typename Ord<T>::U mx[3], unsigned lane) {
-  typedef typename Ord<T>::U U;
-  row_prefix_e<T>(cnt, mn, mx);
-  const unsigned row = lane >> 4;
-  const uint32_t c0 = lane_bcast(cnt, 15), c1 = lane_bcast(cnt, 31), c2 = lane_bcast(cnt, 47);
-  cnt += row == 0 ? 0u : (row == 1 ? c0 : (row == 2 ? c0 + c1 : c0 + c1 + c2));
-#pragma unroll
-  for (int d = 0; d < 3; d++) {
-    mn[d] = row_carry<U, true>(mn[d], lane_bcast(mn[d], 15), lane_bcast(mn[d], 31), lane_bcast(mn[d], 47), row, true);
-    mx[d] = row_carry<U, false>(mx[d], lane_bcast(mx[d], 15), lane_bcast(mx[d], 31), lane_bcast(mx[d], 47), row, true);
-  }
-}
-template <typename T>
-__device__ __forceinline__ void wave_suffix_e(uint32_t &cnt, typename Ord<T>::U mn[3], typename Ord<T>::U mx[3], unsigned lane) {
-  typedef typename Ord<T>::U U;
-  row_suffix_e<T>(cnt, mn, mx);
-  const unsigned row = lane >> 4;
-  const uint32_t c1 = lane_bcast(cnt, 16), c2 = lane_bcast(cnt, 32), c3 = lane_bcast(cnt, 48);
-  cnt += row == 3 ? 0u : (row == 2 ? c3 : (row == 1 ? c2 + c3 : c1 + c2 + c3));
-#pragma unroll
-  for (int d = 0; d < 3; d++) {
-    mn[d] = row_carry<U, true>(mn[d], lane_bcast(mn[d], 16), lane_bcast(mn[d], 32), lane_bcast(mn[d], 48), row, false);
-    mx[d] = row_carry<U, false>(mx[d], lane_bcast(mx[d], 16), lane_bcast(mx[d], 32), lane_bcast(mx[d], 48), row, false);
-  }
-}
-// value of lane - 1 (lane 0: `first`): DPP wave_shr:1
-template <typename U>
-__device__ __forceinline__ U wave_shr1(U first, U x) {
-  return dpp_mov<0x138>(first, x);
-}
-
 template <typename E>
 struct __attribute__((packed, aligned(4))) Vec3Of { // three consecutive elements of a tight xyz / ijk array (element-aligned only)
   E x, y, z;
@@ -437,11 +160,7 @@ struct GBins { // per active node, integer-ordered, accumulated with global atom
 template <typename T>
 __device__ __forceinline__ void clean_bins(GBins<T> *g, int k, unsigned bin) {
   g->count[k][bin] = 0;
-#pragma unroll
-  for (int d = 0; d < 3; d++) {
-    g->bmin[k][bin][d] = Ord<T>::highest();
-    g->bmax[k][bin][d] = Ord<T>::lowest();
-  }
+  empty_box_e<T>(g->bmin[k][bin], g->bmax[k][bin]);
 }
 template <typename T>
 __device__ __forceinline__ void clean_acc(BoundsAcc<T> *acc) {
@@ -497,14 +216,10 @@ __global__ void k_init_scene(BoundsAcc<T> *scene, LevelInfo *info, uint32_t top_
   }
 }
 
-// The reference's leaf rule (nanort.h:1781-1783): a range of at most min_leaf_primitives, or one at the depth cap, is a leaf.
-struct LeafRule {
-  uint32_t max_depth, leaf_max; // leaf_max = max(min_leaf_primitives, 1)
-};
 template <typename T>
 __device__ __forceinline__ uint32_t classify(uint32_t n, uint32_t depth, LeafRule rule) {
   if (n <= (uint32_t)kHandoff) return KIND_SMALL;
-  if (depth >= rule.max_depth || n <= rule.leaf_max) return KIND_LEAF; // the rule applied to a node too large for one wave
+  if (is_leaf(n, depth, rule)) return KIND_LEAF; // the rule applied to a node too large for one wave
   return KIND_SPLIT;
 }
 
@@ -915,19 +630,13 @@ __device__ __forceinline__ void eval_split(int K, unsigned lane, const uint32_t 
     wave_suffix_e<T>(sc, smn, smx, lane); // inclusive over lanes lane..63
     // candidate s == lane (1..K-1): left = bins [0, s), right = bins [s, K)
     const uint32_t nl = wave_shr1<uint32_t>(0u, pc);
-    T cost = Lim<T>::inf();
-    {
-      T lmn[3], lmx[3], rmn[3], rmx[3];
+    U lmn[3], lmx[3];
 #pragma unroll
-      for (int d = 0; d < 3; d++) {
-        lmn[d] = Ord<T>::dec(wave_shr1<U>(Ord<T>::highest(), pmn[d]));
-        lmx[d] = Ord<T>::dec(wave_shr1<U>(Ord<T>::lowest(), pmx[d]));
-        rmn[d] = Ord<T>::dec(smn[d]);
-        rmx[d] = Ord<T>::dec(smx[d]);
-      }
-      if (lane >= 1 && (int)lane < K && nl > 0 && sc > 0) cost = T(nl) * half_area<T>(lmn, lmx) + T(sc) * half_area<T>(rmn, rmx);
+    for (int d = 0; d < 3; d++) {
+      lmn[d] = wave_shr1<U>(Ord<T>::highest(), pmn[d]);
+      lmx[d] = wave_shr1<U>(Ord<T>::lowest(), pmx[d]);
     }
-    if (!(cost == cost)) cost = Lim<T>::inf(); // a NaN cost never wins
+    const T cost = sah_cost<T>(lane >= 1 && (int)lane < K, nl, sc, lmn, lmx, smn, smx);
     // wave argmin, ties -> lowest lane
     const U ecost = Ord<T>::enc(cost);
     const U ebest = wave_umin<U>(ecost);
@@ -1013,14 +722,12 @@ __global__ __launch_bounds__(256) void k_bin(TopNode<T> *top, const uint32_t *__
     };
     auto bin_rec = [&](const PrimRec<T> &r) {
       U emin[3], emax[3];
-#pragma unroll
-      for (int d = 0; d < 3; d++) {
-        emin[d] = Ord<T>::enc(r.bmin[d]);
-        emax[d] = Ord<T>::enc(r.bmax[d]);
-      }
+      int bk[3];
+      encode_box<T>(r, emin, emax);
+      record_bins<T>(r, lo, sc, K, bk);
 #pragma unroll
       for (int k = 0; k < 3; k++) {
-        const int b = bin_of<T>(r.c[k], lo[k], sc[k], K);
+        const int b = bk[k];
         if (b == pb[k]) {
           pc[k]++;
 #pragma unroll
@@ -1161,15 +868,13 @@ __global__ __launch_bounds__(64) void k_split(TopNode<T> *top, const uint32_t *_
 #pragma unroll
   for (int k = 0; k < 3; k++) {
     if ((int)lane < K) cnt3[k] = g.count[k][lane];
+    empty_box_e<T>(mn3[k], mx3[k]);
 #pragma unroll
-    for (int d = 0; d < 3; d++) {
-      mn3[k][d] = Ord<T>::highest();
-      mx3[k][d] = Ord<T>::lowest();
+    for (int d = 0; d < 3; d++)
       if ((int)lane < K) {
         mn3[k][d] = g.bmin[k][lane][d];
         mx3[k][d] = g.bmax[k][lane][d];
       }
-    }
   }
   if (rep_node(num_active, nch)) { // a top level: the node's chunks added into kRep copies (the regular slot stayed clean)
     // (axis by axis: the kRep copies of an axis are requested together, folded, and cleaned only then — a store would pin the
@@ -1182,11 +887,7 @@ __global__ __launch_bounds__(64) void k_split(TopNode<T> *top, const uint32_t *_
       for (uint32_t r = 0; r < kRep; r++) {
         const GBins<T> &gr = gbins[max_active + a * kRep + r];
         rc[r] = 0;
-#pragma unroll
-        for (int d = 0; d < 3; d++) {
-          rmn[r][d] = Ord<T>::highest();
-          rmx[r][d] = Ord<T>::lowest();
-        }
+        empty_box_e<T>(rmn[r], rmx[r]);
         if ((int)lane < K) {
           rc[r] = gr.count[k][lane];
 #pragma unroll
@@ -1293,8 +994,8 @@ __global__ __launch_bounds__(256) void k_partition(const TopNode<T> *__restrict_
   const uint32_t right_base = off_in_node - left_base;
   const int axis = nd.axis;
   const uint32_t split_bin = nd.split_bin, nleft = nd.nleft;
-  const T lo = axis == 0 ? nd.cmin[0] : (axis == 1 ? nd.cmin[1] : nd.cmin[2]);
-  const T hi = axis == 0 ? nd.cmax[0] : (axis == 1 ? nd.cmax[1] : nd.cmax[2]);
+  const T lo = axis == 0 ? nd.cmin[0] : (axis == 1 ? nd.cmin[1] : nd.cmin[2]); // (nd is in memory: only the split axis is loaded; pick_axis'
+  const T hi = axis == 0 ? nd.cmax[0] : (axis == 1 ? nd.cmax[1] : nd.cmax[2]); //  three loads cost this kernel 2 VGPRs, 65 -> 67)
   const T sc = bin_scale<T>(lo, hi, node_bins(kpack, nd.r - nd.l));
   const int K = node_bins(kpack, nd.r - nd.l);
 
@@ -1316,17 +1017,10 @@ __global__ __launch_bounds__(256) void k_partition(const TopNode<T> *__restrict_
     const uint32_t p = p0 + tid;
     const bool valid = p < end;
     PrimRec<T> r;
-    bool left = false;
     if (valid) r = r_next;
     if (p + 256u < end) r_next = src[p + 256u];
-    if (valid) {
-      if (split_bin == kMedian) {
-        left = (p - nd.l) < nleft;
-      } else {
-        const T c = axis == 0 ? r.c[0] : (axis == 1 ? r.c[1] : r.c[2]);
-        left = (uint32_t)bin_of<T>(c, lo, sc, K) < split_bin;
-      }
-    }
+    bool left = false;
+    if (valid) left = goes_left<T>(split_bin == kMedian, p - nd.l, nleft, pick_axis<T>(r.c, axis), lo, sc, K, split_bin);
     const unsigned long long bl = __ballot(valid && left), br = __ballot(valid && !left);
     if (lane == 0) {
       s_w[0][w] = (uint32_t)__builtin_popcountll(bl);
@@ -1403,968 +1097,6 @@ __global__ __launch_bounds__(256) void k_partition(const TopNode<T> *__restrict_
   }
 }
 
-// A subtree task's statistics (leaves, deepest node, largest leaf) are left in fields of its own top record that only split
-// nodes use, and k_layout — which visits every top record anyway — adds them up: four device-scope atomics per task on four
-// neighbouring words (22 000 per 1 M-triangle build, 220 000 at 10 M, through one L2 channel at ~100 per microsecond) were a
-// queue every finishing wave stood in.
-template <typename T>
-__device__ __forceinline__ void task_stats(TopNode<T> &task, uint32_t leaves, uint32_t deepest, uint32_t biggest_leaf) {
-  task.nleft = leaves;
-  task.split_bin = deepest;
-  task.nchunks = biggest_leaf;
-}
-
-// ---------------------------------------------------------------------------
-// subtree phase: one wave builds everything below a node of <= kSmall prims
-// ---------------------------------------------------------------------------
-#ifdef NRT_PROF // the one-node-per-step form lives in libnanort_hip_prof.so only: the cross-check of the row form (tests/test_gpu_build.py, tunable subtree_rows = 0)
-// Pending high-side child of the per-wave subtree builder.
-template <typename T>
-struct SubPending {
-  T bmin[3], bmax[3]; // its AABB (from the parent's bins, or reduced during the parent's median partition)
-  T cmin[3], cmax[3]; // its centroid bounds (reduced during the parent's partition)
-  uint16_t lo, hi, parent;
-  uint16_t buf;       // which of the two permutation buffers holds [lo, hi)
-  uint32_t depth;
-};
-
-// One wave per node of <= kSmall primitives: records in LDS, a 16-bit permutation ping-ponged between two
-// buffers by the stable partition, LDS bin reduction (3 axes x K <= 16 bins, ds_min/ds_max on integer-ordered
-// keys), lane == (axis, bin) prefix/suffix sweeps inside 16-lane groups.  The low-side child is processed next
-// (so it is numbered parent + 1, pre-order); the high-side child waits on an LDS stack with its AABB and
-// centroid bounds.  A node costs a chain of dependent LDS round trips, not arithmetic, so the chain is kept
-// short: each lane keeps its first element (all of a node of <= 64 primitives) in registers across the binning
-// and partition passes; a child's centroid bounds (and, after a median split, its AABB) are reduced in the
-// parent's partition pass instead of a pass of its own; the bins are reset by the lanes that read them; wave
-// reductions and the winner's broadcast go through DPP and scalar registers.  Two barriers per inner node.
-template <typename T>
-__global__ __launch_bounds__(64) void k_subtree(TopNode<T> *top, const uint32_t *__restrict__ small_list,
-                                                const PrimRec<T> *__restrict__ recs0,
-                                                const PrimRec<T> *__restrict__ recs1, int K, uint32_t min_leaf,
-                                                uint32_t max_depth, typename Wire<T>::Node *scratch_nodes,
-                                                uint32_t *indices, LevelInfo *info) {
-  typedef typename Wire<T>::Node Node;
-  typedef typename Ord<T>::U U;
-#if NRT_SUBTREE_REC_LDS
-  __shared__ PrimRec<T> s_rec[kHandoff];
-#define NRT_SUB_REC(id_) s_rec[(id_)]
-#else // records stay where they are (10 KB per subtree, contiguous: L1 / L2 hits); 10 KB less LDS per wave = more waves per CU
-#define NRT_SUB_REC(id_) src[(id_)]
-#endif
-  __shared__ uint16_t s_perm[2][kHandoff];
-  __shared__ SubPending<T> s_stack[kSubStack];
-  __shared__ uint32_t s_cnt[3][kSmallBins];
-  __shared__ U s_bmin[3][kSmallBins][3];
-  __shared__ U s_bmax[3][kSmallBins][3];
-
-  const unsigned lane = threadIdx.x;
-  if (blockIdx.x >= info->num_small) return; // grid is an upper bound
-  TopNode<T> &task = top[small_list[blockIdx.x]];
-  const uint32_t L = task.l, n_all = task.r - task.l;
-  const PrimRec<T> *src = (task.buf ? recs1 : recs0) + L;
-  for (uint32_t i = lane; i < n_all; i += 64u) {
-#if NRT_SUBTREE_REC_LDS
-    s_rec[i] = src[i];
-#endif
-    s_perm[0][i] = (uint16_t)i;
-  }
-  if (lane < 3 * kSmallBins) { // bins start clean and are handed on clean by their readers
-    const int k = (int)lane / kSmallBins, bq = (int)lane % kSmallBins;
-    s_cnt[k][bq] = 0;
-#pragma unroll
-    for (int d = 0; d < 3; d++) {
-      s_bmin[k][bq][d] = Ord<T>::highest();
-      s_bmax[k][bq][d] = Ord<T>::lowest();
-    }
-  }
-  Node *out = scratch_nodes + 2 * (size_t)L;
-  uint32_t node_count = 0, leaves = 0, deepest = 0, biggest_leaf = 0;
-  int sp = 0;
-  const uint32_t leaf_max = min_leaf > 1u ? min_leaf : 1u;
-
-  // current node (wave-uniform)
-  uint32_t lo = 0, hi = n_all, depth = task.depth, parent = 0xFFFFu, pb = 0;
-  bool is_high = false;
-  T mn[3], mx[3], cmn[3], cmx[3];
-#pragma unroll
-  for (int d = 0; d < 3; d++) {
-    mn[d] = task.bmin[d];
-    mx[d] = task.bmax[d];
-    cmn[d] = task.cmin[d];
-    cmx[d] = task.cmax[d];
-  }
-  __syncthreads();
-
-  for (;;) {
-    const uint32_t n = hi - lo;
-    const uint32_t me = node_count++;
-    deepest = depth > deepest ? depth : deepest;
-    if (is_high && lane == 0) out[parent].data[1] = me;
-
-    const bool leaf = n <= leaf_max || depth >= max_depth; // nanort.h:1781-1783
-    // this lane's first element stays in registers for every pass over the node
-    const uint32_t i_first = lo + lane;
-    const bool have = i_first < hi;
-    uint16_t id0 = 0;
-    PrimRec<T> r0;
-    if (have) {
-      id0 = s_perm[pb][i_first];
-      r0 = NRT_SUB_REC(id0);
-    }
-
-    Node nd;
-#pragma unroll
-    for (int d = 0; d < 3; d++) {
-      nd.bmin[d] = mn[d];
-      nd.bmax[d] = mx[d];
-    }
-
-    bool descend = false;
-    if (leaf) {
-      nd.flag = 1;
-      nd.axis = 0;
-      nd.data[0] = n;
-      nd.data[1] = L + lo;
-      if (lane == 0) out[me] = nd;
-      if (have) indices[L + i_first] = r0.prim;
-      for (uint32_t i = i_first + 64u; i < hi; i += 64u) indices[L + i] = NRT_SUB_REC(s_perm[pb][i]).prim;
-      leaves++;
-      biggest_leaf = n > biggest_leaf ? n : biggest_leaf;
-    } else {
-      // ---- LDS bin reduction ------------------------------------------------------------------
-      T sc[3];
-#pragma unroll
-      for (int k = 0; k < 3; k++) sc[k] = bin_scale<T>(cmn[k], cmx[k], K);
-      auto bin_one = [&](const PrimRec<T> &r) {
-        U emin[3], emax[3];
-#pragma unroll
-        for (int d = 0; d < 3; d++) {
-          emin[d] = Ord<T>::enc(r.bmin[d]);
-          emax[d] = Ord<T>::enc(r.bmax[d]);
-        }
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-          const int b = bin_of<T>(r.c[k], cmn[k], sc[k], K);
-          atomicAdd(&s_cnt[k][b], 1u);
-#pragma unroll
-          for (int d = 0; d < 3; d++) {
-            atomicMin(&s_bmin[k][b][d], emin[d]);
-            atomicMax(&s_bmax[k][b][d], emax[d]);
-          }
-        }
-      };
-      if (have) bin_one(r0);
-      for (uint32_t i = i_first + 64u; i < hi; i += 64u) bin_one(NRT_SUB_REC(s_perm[pb][i]));
-      __syncthreads();
-
-      // ---- lane == (axis, bin): sweeps inside 16-lane groups, on the integer images ----------------------
-      const int ax = (int)lane >> 4, bn = (int)lane & 15;
-      uint32_t cnt = 0;
-      U pmn[3], pmx[3];
-#pragma unroll
-      for (int d = 0; d < 3; d++) {
-        pmn[d] = Ord<T>::highest();
-        pmx[d] = Ord<T>::lowest();
-      }
-      if (ax < 3 && bn < K) {
-        cnt = s_cnt[ax][bn];
-        if (cnt) {
-#pragma unroll
-          for (int d = 0; d < 3; d++) {
-            pmn[d] = s_bmin[ax][bn][d];
-            pmx[d] = s_bmax[ax][bn][d];
-          }
-          s_cnt[ax][bn] = 0; // read: hand the bin on clean (made visible by the barrier after the partition)
-#pragma unroll
-          for (int d = 0; d < 3; d++) {
-            s_bmin[ax][bn][d] = Ord<T>::highest();
-            s_bmax[ax][bn][d] = Ord<T>::lowest();
-          }
-        }
-      }
-      uint32_t pc = cnt, sc_n = cnt; // inclusive prefix / suffix inside the 16-lane row (DPP row shifts)
-      U smn[3] = {pmn[0], pmn[1], pmn[2]}, smx[3] = {pmx[0], pmx[1], pmx[2]};
-      row_prefix_e<T>(pc, pmn, pmx);
-      row_suffix_e<T>(sc_n, smn, smx);
-      // candidate (ax, s = bn), s in 1..K-1: low side = bins [0, s), high side = bins [s, K)
-      const uint32_t nl = dpp_mov<0x111>(0u, pc);
-      U lmn[3], lmx[3];
-#pragma unroll
-      for (int d = 0; d < 3; d++) {
-        lmn[d] = dpp_mov<0x111>(Ord<T>::highest(), pmn[d]);
-        lmx[d] = dpp_mov<0x111>(Ord<T>::lowest(), pmx[d]);
-      }
-      T cost = Lim<T>::inf();
-      if (ax < 3 && bn >= 1 && bn < K && nl > 0 && sc_n > 0) {
-        T a0[3], a1[3], b0[3], b1[3];
-#pragma unroll
-        for (int d = 0; d < 3; d++) {
-          a0[d] = Ord<T>::dec(lmn[d]);
-          a1[d] = Ord<T>::dec(lmx[d]);
-          b0[d] = Ord<T>::dec(smn[d]);
-          b1[d] = Ord<T>::dec(smx[d]);
-        }
-        cost = T(nl) * half_area<T>(a0, a1) + T(sc_n) * half_area<T>(b0, b1);
-      }
-      if (!(cost == cost)) cost = Lim<T>::inf(); // a NaN cost never wins
-      // argmin: the smallest cost, ties -> lowest lane; lane order == (axis, bin): lowest axis, then lowest bin
-      const U ecost = Ord<T>::enc(cost);
-      const U ebest = wave_umin<U>(ecost);
-      const int who = (int)__builtin_ctzll(__ballot(ecost == ebest));
-      const bool found = ebest < Ord<T>::enc(Lim<T>::inf());
-      int axis = 0;
-      uint32_t split_bin = kMedian, nleft = n >> 1;
-      T cl[3], ch[3], rl[3], rh[3]; // children AABBs
-      // a pathological chain of lopsided SAH splits could outgrow the LDS stack: past kSubStackSafe
-      // pending nodes fall back to balanced object-median splits (at most log2(kSmall) more levels)
-      if (found && sp < kSubStackSafe) {
-        axis = who >> 4;
-        split_bin = (uint32_t)who & 15u;
-        nleft = lane_bcast(nl, who);
-#pragma unroll
-        for (int d = 0; d < 3; d++) {
-          cl[d] = Ord<T>::dec(lane_bcast(lmn[d], who));
-          ch[d] = Ord<T>::dec(lane_bcast(lmx[d], who));
-          rl[d] = Ord<T>::dec(lane_bcast(smn[d], who));
-          rh[d] = Ord<T>::dec(lane_bcast(smx[d], who));
-        }
-      } else {
-#pragma unroll
-        for (int d = 0; d < 3; d++) {
-          cl[d] = rl[d] = Lim<T>::max();
-          ch[d] = rh[d] = -Lim<T>::max();
-        }
-      }
-      const bool median = split_bin == kMedian;
-
-      // ---- stable partition of s_perm[pb][lo, hi) into s_perm[1 - pb], reducing the children's centroid bounds
-      //      (and, after a median split, their AABBs) on the way ----------------------------------------------
-      const bool low_leaf = nleft <= leaf_max || depth + 1 >= max_depth, high_leaf = n - nleft <= leaf_max || depth + 1 >= max_depth;
-      const bool both_leaves = low_leaf && high_leaf; // the common case at the bottom: finished here, no trip through the stack
-      T ccl[3], cch[3], crl[3], crh[3];
-#pragma unroll
-      for (int d = 0; d < 3; d++) {
-        ccl[d] = crl[d] = Lim<T>::max();
-        cch[d] = crh[d] = -Lim<T>::max();
-      }
-      {
-        const T clo = axis == 0 ? cmn[0] : (axis == 1 ? cmn[1] : cmn[2]);
-        const T scl = axis == 0 ? sc[0] : (axis == 1 ? sc[1] : sc[2]);
-        uint32_t run_l = 0, run_r = 0;
-        for (uint32_t i0 = lo; i0 < hi; i0 += 64u) {
-          const uint32_t i = i0 + lane;
-          const bool valid = i < hi;
-          uint16_t id = id0;
-          PrimRec<T> r = r0;
-          if (valid && i0 != lo) {
-            id = s_perm[pb][i];
-            r = NRT_SUB_REC(id);
-          }
-          bool left = false;
-          if (valid) {
-            if (median) {
-              left = (i - lo) < nleft;
-            } else {
-              const T c = axis == 0 ? r.c[0] : (axis == 1 ? r.c[1] : r.c[2]);
-              left = (uint32_t)bin_of<T>(c, clo, scl, K) < split_bin;
-            }
-          }
-          const unsigned long long bl = __ballot(valid && left), br = __ballot(valid && !left);
-          const unsigned long long lt = (1ull << lane) - 1ull;
-          if (valid) {
-            const uint32_t d = left ? lo + run_l + (uint32_t)__builtin_popcountll(bl & lt)
-                                    : lo + nleft + run_r + (uint32_t)__builtin_popcountll(br & lt);
-            s_perm[1 - pb][d] = id;
-            if (both_leaves || (low_leaf && left)) indices[L + d] = r.prim; // index slots of the leaves emitted below, in partition order
-#pragma unroll
-            for (int k = 0; k < 3; k++) {
-              if (left) {
-                ccl[k] = tmin(ccl[k], r.c[k]);
-                cch[k] = tmax(cch[k], r.c[k]);
-              } else {
-                crl[k] = tmin(crl[k], r.c[k]);
-                crh[k] = tmax(crh[k], r.c[k]);
-              }
-              if (median) {
-                if (left) {
-                  cl[k] = tmin(cl[k], r.bmin[k]);
-                  ch[k] = tmax(ch[k], r.bmax[k]);
-                } else {
-                  rl[k] = tmin(rl[k], r.bmin[k]);
-                  rh[k] = tmax(rh[k], r.bmax[k]);
-                }
-              }
-            }
-          }
-          run_l += (uint32_t)__builtin_popcountll(bl);
-          run_r += (uint32_t)__builtin_popcountll(br);
-        }
-      }
-      // (a child that becomes a leaf needs no centroid bounds)
-#pragma unroll
-      for (int d = 0; d < 3; d++) {
-        if (!low_leaf) {
-          ccl[d] = wave_min_u<T>(ccl[d]);
-          cch[d] = wave_max_u<T>(cch[d]);
-        }
-        if (!high_leaf) {
-          crl[d] = wave_min_u<T>(crl[d]);
-          crh[d] = wave_max_u<T>(crh[d]);
-        }
-        if (median) {
-          cl[d] = wave_min_u<T>(cl[d]);
-          ch[d] = wave_max_u<T>(ch[d]);
-          rl[d] = wave_min_u<T>(rl[d]);
-          rh[d] = wave_max_u<T>(rh[d]);
-        }
-      }
-
-      nd.flag = 0;
-      nd.axis = axis;
-      nd.data[0] = me + 1; // low-side child follows its parent (pre-order)
-      nd.data[1] = 0;      // patched when the high-side child is emitted
-      if (both_leaves) {
-        // both children are leaves: emit the three nodes now (pre-order: parent, low leaf, high leaf)
-        nd.data[1] = me + 2;
-        if (lane == 0) {
-          out[me] = nd;
-          Node lf;
-          lf.flag = 1;
-          lf.axis = 0;
-#pragma unroll
-          for (int d = 0; d < 3; d++) {
-            lf.bmin[d] = cl[d];
-            lf.bmax[d] = ch[d];
-          }
-          lf.data[0] = nleft;
-          lf.data[1] = L + lo;
-          out[me + 1] = lf;
-#pragma unroll
-          for (int d = 0; d < 3; d++) {
-            lf.bmin[d] = rl[d];
-            lf.bmax[d] = rh[d];
-          }
-          lf.data[0] = n - nleft;
-          lf.data[1] = L + lo + nleft;
-          out[me + 2] = lf;
-        }
-        node_count += 2;
-        leaves += 2;
-        deepest = depth + 1 > deepest ? depth + 1 : deepest;
-        const uint32_t big = nleft > n - nleft ? nleft : n - nleft;
-        biggest_leaf = big > biggest_leaf ? big : biggest_leaf;
-        __syncthreads(); // the reset bins are visible to the next node
-      } else if (low_leaf) {
-        // the low child is a leaf, the high one is not: emit the leaf (node me + 1) and continue with the high child
-        // right away (it is node me + 2; the loop head patches the parent's data[1]) — no stack entry
-        if (lane == 0) {
-          out[me] = nd;
-          Node lf;
-          lf.flag = 1;
-          lf.axis = 0;
-#pragma unroll
-          for (int d = 0; d < 3; d++) {
-            lf.bmin[d] = cl[d];
-            lf.bmax[d] = ch[d];
-          }
-          lf.data[0] = nleft;
-          lf.data[1] = L + lo;
-          out[me + 1] = lf;
-        }
-        node_count += 1;
-        leaves += 1;
-        deepest = depth + 1 > deepest ? depth + 1 : deepest;
-        biggest_leaf = nleft > biggest_leaf ? nleft : biggest_leaf;
-        lo = lo + nleft;
-        depth = depth + 1;
-        parent = me;
-        is_high = true;
-        pb = 1u - pb;
-#pragma unroll
-        for (int d = 0; d < 3; d++) {
-          mn[d] = rl[d];
-          mx[d] = rh[d];
-          cmn[d] = crl[d];
-          cmx[d] = crh[d];
-        }
-        descend = true;
-        __syncthreads(); // the permutation and the reset bins are visible to the next node
-      } else {
-      if (lane == 0) {
-        out[me] = nd;
-        SubPending<T> &e = s_stack[sp];
-#pragma unroll
-        for (int d = 0; d < 3; d++) {
-          e.bmin[d] = rl[d];
-          e.bmax[d] = rh[d];
-          e.cmin[d] = crl[d];
-          e.cmax[d] = crh[d];
-        }
-        e.lo = (uint16_t)(lo + nleft);
-        e.hi = (uint16_t)hi;
-        e.parent = (uint16_t)me;
-        e.buf = (uint16_t)(1u - pb);
-        e.depth = depth + 1;
-      }
-      sp++;
-      // continue with the low side
-      hi = lo + nleft;
-      depth = depth + 1;
-      parent = me;
-      is_high = false;
-      pb = 1u - pb;
-#pragma unroll
-      for (int d = 0; d < 3; d++) {
-        mn[d] = cl[d];
-        mx[d] = ch[d];
-        cmn[d] = ccl[d];
-        cmx[d] = cch[d];
-      }
-      descend = true;
-      __syncthreads(); // the permutation, the reset bins and the stack entry are visible to the next node
-      }
-    }
-    if (!descend) {
-      if (sp == 0) break;
-      sp--;
-      const SubPending<T> &e = s_stack[sp];
-      lo = e.lo;
-      hi = e.hi;
-      depth = e.depth;
-      parent = e.parent;
-      pb = e.buf;
-      is_high = true;
-#pragma unroll
-      for (int d = 0; d < 3; d++) {
-        mn[d] = e.bmin[d];
-        mx[d] = e.bmax[d];
-        cmn[d] = e.cmin[d];
-        cmx[d] = e.cmax[d];
-      }
-    }
-  }
-  if (lane == 0) { // (statistics: left in the task's record, summed by k_layout — see task_stats)
-    task.size = node_count;
-    task_stats<T>(task, leaves, deepest, biggest_leaf);
-  }
-}
-#undef NRT_SUB_REC
-#endif // NRT_PROF
-
-// ---------------------------------------------------------------------------
-// subtree phase, row form: up to four nodes of a subtree per step, one per 16-lane row
-// ---------------------------------------------------------------------------
-// k_subtree above spends about 700 wave instructions on an inner node whatever its size, and three quarters of a
-// subtree's inner nodes hold 16 primitives or fewer (5 to 16 of 64 lanes busy).  This form keeps the nodes that wait to be
-// split on an LDS stack and takes up to FOUR of them per step, one per 16-lane DPP row: lane == primitive for the binning
-// and the partition (16 at a time), lane == bin for the cut search (the three axes one after the other, the 16-lane
-// prefix / suffix scans are the ones k_subtree uses), the winner's data is handed to its row by ds_bpermute.  With one or
-// two nodes on the stack (the first steps of a subtree, where the nodes are large) a node gets 64 or 32 lanes instead.
-// Every decision is the one k_subtree takes — same bins, cost expression, tie rule (lowest axis, then lowest bin), leaf
-// rule and object-median fallback (including k_subtree's stack-depth guard, whose depth every node carries along) — and
-// min / max / counts do not depend on the order they are combined in, so the tree is the same.  Nodes are created in
-// step order, not in pre-order: they are written to the scratch array under their creation index (children c, c + 1
-// with c odd) and the wave finishes by computing each node's pre-order index from the parent links (subtree sizes by
-// walking up, then the index as the sum over the path to the root), which k_emit_small applies when it splices the
-// subtree into the tree (premap).
-struct RowEntry {
-  uint16_t lo, hi; // range in the permutation
-  uint16_t me;     // creation index of the node
-  uint8_t ldepth;  // depth below the subtree's root
-  uint8_t misc;    // bit 7: permutation buffer holding [lo, hi); bits 0..5: k_subtree's stack depth at this node
-};
-static_assert(sizeof(RowEntry) == 8, "RowEntry");
-constexpr int kRowStack = kHandoff / 2; // pending nodes are disjoint ranges of at least 2 primitives
-
-template <typename U>
-__device__ __forceinline__ U row_allmin(U x) { // every lane of a 16-lane row gets the row's minimum
-  x = umin_(x, dpp_mov<0xB1>((U) ~(U)0, x));
-  x = umin_(x, dpp_mov<0x4E>((U) ~(U)0, x));
-  x = umin_(x, dpp_mov<0x141>((U) ~(U)0, x));
-  x = umin_(x, dpp_mov<0x140>((U) ~(U)0, x));
-  return x;
-}
-template <typename U>
-__device__ __forceinline__ U row_allmax(U x) {
-  x = umax_(x, dpp_mov<0xB1>((U)0, x));
-  x = umax_(x, dpp_mov<0x4E>((U)0, x));
-  x = umax_(x, dpp_mov<0x141>((U)0, x));
-  x = umax_(x, dpp_mov<0x140>((U)0, x));
-  return x;
-}
-// (groups of 16, 32 or 64 lanes: shift = 4, 5, 6 — wave-uniform)
-template <typename U>
-__device__ __forceinline__ U group_allmin(U x, uint32_t shift) {
-  x = row_allmin<U>(x);
-  if (shift >= 5u) x = umin_(x, (U)__shfl_xor(x, 16));
-  if (shift >= 6u) x = umin_(x, (U)__shfl_xor(x, 32));
-  return x;
-}
-template <typename U>
-__device__ __forceinline__ U group_allmax(U x, uint32_t shift) {
-  x = row_allmax<U>(x);
-  if (shift >= 5u) x = umax_(x, (U)__shfl_xor(x, 16));
-  if (shift >= 6u) x = umax_(x, (U)__shfl_xor(x, 32));
-  return x;
-}
-
-template <typename T>
-__global__ __launch_bounds__(64) void k_subtree_rows(TopNode<T> *top, const uint32_t *__restrict__ small_list,
-                                                     const PrimRec<T> *__restrict__ recs0,
-                                                     const PrimRec<T> *__restrict__ recs1, int K, uint32_t min_leaf,
-                                                     uint32_t max_depth, typename Wire<T>::Node *scratch_nodes,
-                                                     uint16_t *premap, uint32_t *indices, LevelInfo *info) {
-  typedef typename Wire<T>::Node Node;
-  typedef typename Ord<T>::U U;
-  __shared__ uint16_t s_perm[2][kHandoff];
-  __shared__ RowEntry s_stack[kRowStack];
-  __shared__ uint16_t s_parent[2 * kHandoff];
-  __shared__ uint32_t s_cnt[4][3][kSmallBins];
-  __shared__ U s_bmin[4][3][kSmallBins][3]; // (after the last step: the nodes' subtree sizes, 2 * kHandoff uint32)
-  __shared__ U s_bmax[4][3][kSmallBins][3];
-  static_assert(sizeof(U) * 4 * 3 * kSmallBins * 3 >= sizeof(uint32_t) * 2 * kHandoff, "sizes fit the bins");
-
-  const unsigned lane = threadIdx.x;
-  if (blockIdx.x >= info->num_small) return; // grid is an upper bound
-  TopNode<T> &task = top[small_list[blockIdx.x]];
-  const uint32_t L = task.l, n_all = task.r - task.l;
-  const PrimRec<T> *src = (task.buf ? recs1 : recs0) + L;
-  Node *out = scratch_nodes + 2 * (size_t)L;
-  uint16_t *map = premap + 2 * (size_t)L;
-  const uint32_t leaf_max = min_leaf > 1u ? min_leaf : 1u;
-  const uint32_t depth0 = task.depth;
-
-  if (n_all <= leaf_max || depth0 >= max_depth) { // the task is a leaf (nanort.h:1781-1783)
-    for (uint32_t i = lane; i < n_all; i += 64u) indices[L + i] = src[i].prim;
-    if (lane == 0) {
-      Node nd;
-#pragma unroll
-      for (int d = 0; d < 3; d++) {
-        nd.bmin[d] = task.bmin[d];
-        nd.bmax[d] = task.bmax[d];
-      }
-      nd.flag = 1;
-      nd.axis = 0;
-      nd.data[0] = n_all;
-      nd.data[1] = L;
-      out[0] = nd;
-      map[0] = 0;
-      task.size = 1;
-      task_stats<T>(task, 1u, depth0, n_all);
-    }
-    return;
-  }
-
-  for (uint32_t i = lane; i < n_all; i += 64u) s_perm[0][i] = (uint16_t)i;
-  for (uint32_t q = lane; q < 4u * 3u * kSmallBins; q += 64u) { // bins start clean and are handed on clean by their readers
-    (&s_cnt[0][0][0])[q] = 0;
-#pragma unroll
-    for (int d = 0; d < 3; d++) {
-      (&s_bmin[0][0][0][0])[3 * q + d] = Ord<T>::highest();
-      (&s_bmax[0][0][0][0])[3 * q + d] = Ord<T>::lowest();
-    }
-  }
-  if (lane == 0) {
-#pragma unroll
-    for (int d = 0; d < 3; d++) {
-      out[0].bmin[d] = task.bmin[d];
-      out[0].bmax[d] = task.bmax[d];
-    }
-    RowEntry e;
-    e.lo = 0;
-    e.hi = (uint16_t)n_all;
-    e.me = 0;
-    e.ldepth = 0;
-    e.misc = 0;
-    s_stack[0] = e;
-    s_parent[0] = 0;
-  }
-  uint32_t stack_n = 1, node_count = 1;                // wave-uniform
-  uint32_t leaves = 0, deepest = 0, biggest_leaf = 0;  // kept by the group leaders, combined at the end
-  __syncthreads();
-
-  for (uint32_t step = 0; stack_n > 0; step++) {
-    if (step > 4u * kHandoff) { // cannot happen (every step splits at least one node, a subtree has fewer than kHandoff inner nodes)
-      if (lane == 0) info->error = 1;
-      break;
-    }
-    const uint32_t m = stack_n < 4u ? stack_n : 4u;
-    const uint32_t shift = m == 1u ? 6u : (m == 2u ? 5u : 4u); // lanes per node: 64, 32 or 16
-    const uint32_t G = 1u << shift, g = lane >> shift, lg = lane & (G - 1u), gbase = g << shift;
-    const bool act = g < m;
-    RowEntry e = s_stack[act ? stack_n - 1u - g : 0u];
-    stack_n -= m;
-    const uint32_t lo = act ? e.lo : 0u, hi = act ? e.hi : 0u, n = hi - lo, me = e.me;
-    const uint32_t ldepth = e.ldepth, depth = depth0 + ldepth, pb = e.misc >> 7, vsp = e.misc & 63u;
-    // passes over the node: G primitives at a time; the wave runs the longest group's count
-    const uint32_t my_pass = (n + G - 1u) >> shift;
-    uint32_t npass = (uint32_t)__builtin_amdgcn_readlane((int)my_pass, 0);
-    {
-      const uint32_t p1 = (uint32_t)__builtin_amdgcn_readlane((int)my_pass, 16), p2 = (uint32_t)__builtin_amdgcn_readlane((int)my_pass, 32),
-                     p3 = (uint32_t)__builtin_amdgcn_readlane((int)my_pass, 48);
-      npass = npass > p1 ? npass : p1;
-      npass = npass > p2 ? npass : p2;
-      npass = npass > p3 ? npass : p3;
-      npass = npass < (uint32_t)(kHandoff >> 4) ? npass : (uint32_t)(kHandoff >> 4); // (a range never exceeds the subtree)
-    }
-
-    // ---- this lane's first element stays in registers for every pass; the node's centroid bounds --------------------
-    const uint32_t i0 = lo + lg;
-    const bool have0 = i0 < hi;
-    uint32_t id0 = 0;
-    PrimRec<T> r0;
-    if (have0) {
-      id0 = s_perm[pb][i0];
-      r0 = src[id0];
-    }
-    T cmn[3], cmx[3];
-    if (step == 0) { // the subtree's root: reduced by the top phase
-#pragma unroll
-      for (int k = 0; k < 3; k++) {
-        cmn[k] = task.cmin[k];
-        cmx[k] = task.cmax[k];
-      }
-    } else {
-      U emn[3], emx[3];
-#pragma unroll
-      for (int k = 0; k < 3; k++) {
-        emn[k] = have0 ? Ord<T>::enc(r0.c[k]) : Ord<T>::highest();
-        emx[k] = have0 ? Ord<T>::enc(r0.c[k]) : Ord<T>::lowest();
-      }
-      for (uint32_t pass = 1; pass < npass; pass++) {
-        const uint32_t i = i0 + (pass << shift);
-        if (i < hi) {
-          const PrimRec<T> &r = src[s_perm[pb][i]];
-#pragma unroll
-          for (int k = 0; k < 3; k++) {
-            const U ec = Ord<T>::enc(r.c[k]);
-            emn[k] = umin_(emn[k], ec);
-            emx[k] = umax_(emx[k], ec);
-          }
-        }
-      }
-#pragma unroll
-      for (int k = 0; k < 3; k++) {
-        cmn[k] = Ord<T>::dec(group_allmin<U>(emn[k], shift));
-        cmx[k] = Ord<T>::dec(group_allmax<U>(emx[k], shift));
-      }
-    }
-
-    // ---- LDS bin reduction into the group's bins ---------------------------------------------------------------------
-    T sc[3];
-#pragma unroll
-    for (int k = 0; k < 3; k++) sc[k] = bin_scale<T>(cmn[k], cmx[k], K);
-    for (uint32_t pass = 0; pass < npass; pass++) {
-      const uint32_t i = i0 + (pass << shift);
-      if (i < hi) {
-        PrimRec<T> r = r0;
-        if (pass) r = src[s_perm[pb][i]];
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-          const int b = bin_of<T>(r.c[k], cmn[k], sc[k], K);
-          atomicAdd(&s_cnt[g][k][b], 1u);
-#pragma unroll
-          for (int d = 0; d < 3; d++) {
-            atomicMin(&s_bmin[g][k][b][d], Ord<T>::enc(r.bmin[d]));
-            atomicMax(&s_bmax[g][k][b][d], Ord<T>::enc(r.bmax[d]));
-          }
-        }
-      }
-    }
-    __syncthreads();
-
-    // ---- cut search: the first 16 lanes of the group, lane == bin, one axis after the other ---------------------------
-    T best_cost = Lim<T>::inf();
-    int axis = 0;
-    uint32_t split_bin = kMedian, nleft = n >> 1;
-    T cl[3], ch[3], rl[3], rh[3]; // children AABBs
-    U ecl[3], ech[3], erl[3], erh[3]; // (their integer images while the axes compete)
-#pragma unroll
-    for (int d = 0; d < 3; d++) {
-      ecl[d] = erl[d] = Ord<T>::enc(Lim<T>::max());
-      ech[d] = erh[d] = Ord<T>::enc(-Lim<T>::max());
-    }
-    const bool bin_lane = act && lg < (uint32_t)K && lg < 16u;
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-      uint32_t cnt = 0;
-      U pmn[3], pmx[3];
-#pragma unroll
-      for (int d = 0; d < 3; d++) {
-        pmn[d] = Ord<T>::highest();
-        pmx[d] = Ord<T>::lowest();
-      }
-      if (bin_lane) {
-        cnt = s_cnt[g][k][lg];
-        if (cnt) {
-#pragma unroll
-          for (int d = 0; d < 3; d++) {
-            pmn[d] = s_bmin[g][k][lg][d];
-            pmx[d] = s_bmax[g][k][lg][d];
-          }
-          s_cnt[g][k][lg] = 0; // read: hand the bin on clean (made visible by the barrier that ends the step)
-#pragma unroll
-          for (int d = 0; d < 3; d++) {
-            s_bmin[g][k][lg][d] = Ord<T>::highest();
-            s_bmax[g][k][lg][d] = Ord<T>::lowest();
-          }
-        }
-      }
-      uint32_t pc = cnt, sc_n = cnt; // inclusive prefix / suffix inside the 16-lane row (DPP row shifts)
-      U smn[3] = {pmn[0], pmn[1], pmn[2]}, smx[3] = {pmx[0], pmx[1], pmx[2]};
-      row_prefix_e<T>(pc, pmn, pmx);
-      row_suffix_e<T>(sc_n, smn, smx);
-      // candidate s = bin, s in 1..K-1: low side = bins [0, s), high side = bins [s, K)
-      const uint32_t nl = dpp_mov<0x111>(0u, pc);
-      U lmn[3], lmx[3];
-#pragma unroll
-      for (int d = 0; d < 3; d++) {
-        lmn[d] = dpp_mov<0x111>(Ord<T>::highest(), pmn[d]);
-        lmx[d] = dpp_mov<0x111>(Ord<T>::lowest(), pmx[d]);
-      }
-      T cost = Lim<T>::inf();
-      if (bin_lane && lg >= 1u && nl > 0 && sc_n > 0) {
-        T a0[3], a1[3], b0[3], b1[3];
-#pragma unroll
-        for (int d = 0; d < 3; d++) {
-          a0[d] = Ord<T>::dec(lmn[d]);
-          a1[d] = Ord<T>::dec(lmx[d]);
-          b0[d] = Ord<T>::dec(smn[d]);
-          b1[d] = Ord<T>::dec(smx[d]);
-        }
-        cost = T(nl) * half_area<T>(a0, a1) + T(sc_n) * half_area<T>(b0, b1);
-      }
-      if (!(cost == cost)) cost = Lim<T>::inf(); // a NaN cost never wins
-      const U ecost = Ord<T>::enc(cost);
-      const U rbest = row_allmin<U>(ecost);
-      const unsigned long long hit = __ballot(ecost == rbest);
-      // the group's first row holds its candidates: the row's best, ties -> lowest bin
-      const U gbest = (U)__shfl(rbest, (int)gbase);
-      const T c = Ord<T>::dec(gbest);
-      const bool better = c < best_cost; // ties -> lowest axis
-      if (__ballot(better) != 0ull) {    // (uniform: the winner's data travels only when some group wants it)
-        const uint32_t who = (uint32_t)__builtin_ctz(((uint32_t)(hit >> gbase) & 0xFFFFu) | 0x10000u);
-        const int from = (int)(gbase + (who & 15u));
-        const uint32_t w_nl = (uint32_t)__shfl(nl, from);
-        U w_lmn[3], w_lmx[3], w_smn[3], w_smx[3];
-#pragma unroll
-        for (int d = 0; d < 3; d++) {
-          w_lmn[d] = (U)__shfl(lmn[d], from);
-          w_lmx[d] = (U)__shfl(lmx[d], from);
-          w_smn[d] = (U)__shfl(smn[d], from);
-          w_smx[d] = (U)__shfl(smx[d], from);
-        }
-        if (better) {
-          best_cost = c;
-          axis = k;
-          split_bin = who;
-          nleft = w_nl;
-#pragma unroll
-          for (int d = 0; d < 3; d++) {
-            ecl[d] = w_lmn[d];
-            ech[d] = w_lmx[d];
-            erl[d] = w_smn[d];
-            erh[d] = w_smx[d];
-          }
-        }
-      }
-    }
-#pragma unroll
-    for (int d = 0; d < 3; d++) {
-      cl[d] = Ord<T>::dec(ecl[d]);
-      ch[d] = Ord<T>::dec(ech[d]);
-      rl[d] = Ord<T>::dec(erl[d]);
-      rh[d] = Ord<T>::dec(erh[d]);
-    }
-    // a pathological chain of lopsided SAH splits is cut off as in k_subtree: past kSubStackSafe pending nodes (there),
-    // balanced object-median splits
-    if (!(best_cost < Lim<T>::inf()) || vsp >= (uint32_t)kSubStackSafe) {
-      axis = 0;
-      split_bin = kMedian;
-      nleft = n >> 1;
-#pragma unroll
-      for (int d = 0; d < 3; d++) {
-        cl[d] = rl[d] = Lim<T>::max();
-        ch[d] = rh[d] = -Lim<T>::max();
-      }
-    }
-    const bool median = split_bin == kMedian;
-    const bool low_leaf = nleft <= leaf_max || depth + 1u >= max_depth, high_leaf = n - nleft <= leaf_max || depth + 1u >= max_depth;
-
-    // ---- stable partition of s_perm[pb][lo, hi) into s_perm[1 - pb] ---------------------------------------------------
-    {
-      const T clo = axis == 0 ? cmn[0] : (axis == 1 ? cmn[1] : cmn[2]);
-      const T scl = axis == 0 ? sc[0] : (axis == 1 ? sc[1] : sc[2]);
-      const unsigned long long gmask = (G == 64u ? ~0ull : ((1ull << G) - 1ull)), lt = (1ull << lg) - 1ull;
-      const bool any_median = __ballot(act && median) != 0ull;
-      uint32_t run_l = 0, run_r = 0;
-      for (uint32_t pass = 0; pass < npass; pass++) {
-        const uint32_t i = i0 + (pass << shift);
-        const bool valid = i < hi;
-        uint32_t id = id0;
-        PrimRec<T> r = r0;
-        if (valid && pass) {
-          id = s_perm[pb][i];
-          r = src[id];
-        }
-        bool left = false;
-        if (valid) {
-          if (median) {
-            left = (i - lo) < nleft;
-          } else {
-            const T c = axis == 0 ? r.c[0] : (axis == 1 ? r.c[1] : r.c[2]);
-            left = (uint32_t)bin_of<T>(c, clo, scl, K) < split_bin;
-          }
-        }
-        const unsigned long long bl = (__ballot(valid && left) >> gbase) & gmask, br = (__ballot(valid && !left) >> gbase) & gmask;
-        if (valid) {
-          const uint32_t d = left ? lo + run_l + (uint32_t)__builtin_popcountll(bl & lt)
-                                  : lo + nleft + run_r + (uint32_t)__builtin_popcountll(br & lt);
-          s_perm[1u - pb][d] = (uint16_t)id;
-          if (left ? low_leaf : high_leaf) indices[L + d] = r.prim; // index slots of the leaves emitted below, in partition order
-          if (median) {
-#pragma unroll
-            for (int k = 0; k < 3; k++) {
-              if (left) {
-                cl[k] = tmin(cl[k], r.bmin[k]);
-                ch[k] = tmax(ch[k], r.bmax[k]);
-              } else {
-                rl[k] = tmin(rl[k], r.bmin[k]);
-                rh[k] = tmax(rh[k], r.bmax[k]);
-              }
-            }
-          }
-        }
-        run_l += (uint32_t)__builtin_popcountll(bl);
-        run_r += (uint32_t)__builtin_popcountll(br);
-      }
-      if (any_median) { // (uniform: the reductions run for every group, only the median ones keep the result)
-#pragma unroll
-        for (int d = 0; d < 3; d++) {
-          const T a = Ord<T>::dec(group_allmin<U>(Ord<T>::enc(cl[d]), shift)), b = Ord<T>::dec(group_allmax<U>(Ord<T>::enc(ch[d]), shift));
-          const T c = Ord<T>::dec(group_allmin<U>(Ord<T>::enc(rl[d]), shift)), e2 = Ord<T>::dec(group_allmax<U>(Ord<T>::enc(rh[d]), shift));
-          if (median) {
-            cl[d] = a;
-            ch[d] = b;
-            rl[d] = c;
-            rh[d] = e2;
-          }
-        }
-      }
-    }
-
-    // ---- the group's first lane writes the node and its children -----------------------------------------------------
-    {
-      const bool lead = act && lg == 0u;
-      const unsigned long long push_l = __ballot(lead && !low_leaf), push_h = __ballot(lead && !high_leaf);
-      const unsigned long long below = (1ull << lane) - 1ull;
-      if (lead) {
-        const uint32_t c0 = node_count + 2u * g;
-        out[me].flag = 0;
-        out[me].axis = axis;
-        out[me].data[0] = c0;
-        out[me].data[1] = c0 + 1u;
-        s_parent[c0] = (uint16_t)me;
-        s_parent[c0 + 1u] = (uint16_t)me;
-        uint32_t slot = stack_n + (uint32_t)__builtin_popcountll(push_l & below) + (uint32_t)__builtin_popcountll(push_h & below);
-        Node lf;
-        lf.flag = 1;
-        lf.axis = 0;
-#pragma unroll
-        for (int d = 0; d < 3; d++) {
-          lf.bmin[d] = cl[d];
-          lf.bmax[d] = ch[d];
-        }
-        lf.data[0] = nleft;
-        lf.data[1] = L + lo;
-        if (low_leaf) {
-          out[c0] = lf;
-        } else {
-#pragma unroll
-          for (int d = 0; d < 3; d++) {
-            out[c0].bmin[d] = cl[d];
-            out[c0].bmax[d] = ch[d];
-          }
-          RowEntry ne;
-          ne.lo = (uint16_t)lo;
-          ne.hi = (uint16_t)(lo + nleft);
-          ne.me = (uint16_t)c0;
-          ne.ldepth = (uint8_t)(ldepth + 1u);
-          ne.misc = (uint8_t)(((1u - pb) << 7) | (vsp + 1u)); // k_subtree descends into the low side with the high side pending
-          s_stack[slot++] = ne;
-        }
-#pragma unroll
-        for (int d = 0; d < 3; d++) {
-          lf.bmin[d] = rl[d];
-          lf.bmax[d] = rh[d];
-        }
-        lf.data[0] = n - nleft;
-        lf.data[1] = L + lo + nleft;
-        if (high_leaf) {
-          out[c0 + 1u] = lf;
-        } else {
-#pragma unroll
-          for (int d = 0; d < 3; d++) {
-            out[c0 + 1u].bmin[d] = rl[d];
-            out[c0 + 1u].bmax[d] = rh[d];
-          }
-          RowEntry ne;
-          ne.lo = (uint16_t)(lo + nleft);
-          ne.hi = (uint16_t)hi;
-          ne.me = (uint16_t)(c0 + 1u);
-          ne.ldepth = (uint8_t)(ldepth + 1u);
-          ne.misc = (uint8_t)(((1u - pb) << 7) | vsp);
-          s_stack[slot] = ne;
-        }
-        if (low_leaf || high_leaf) {
-          leaves += (low_leaf ? 1u : 0u) + (high_leaf ? 1u : 0u);
-          deepest = depth + 1u > deepest ? depth + 1u : deepest;
-          const uint32_t big = (low_leaf ? nleft : 0u) > (high_leaf ? n - nleft : 0u) ? (low_leaf ? nleft : 0u) : (high_leaf ? n - nleft : 0u);
-          biggest_leaf = big > biggest_leaf ? big : biggest_leaf;
-        }
-      }
-      stack_n += (uint32_t)__builtin_popcountll(push_l) + (uint32_t)__builtin_popcountll(push_h);
-      node_count += 2u * m;
-    }
-    __syncthreads(); // the permutation, the reset bins, the stack and the parent links are visible to the next step
-  }
-
-  // ---- pre-order index of every node from the parent links ------------------------------------------------------------
-  uint32_t *s_size = reinterpret_cast<uint32_t *>(&s_bmin[0][0][0][0]);
-  const uint32_t N = node_count;
-  for (uint32_t x = lane; x < N; x += 64u) s_size[x] = 1u;
-  __syncthreads();
-  for (uint32_t x = lane; x < N; x += 64u) {
-    if (x == 0u) continue;
-    uint32_t p = s_parent[x];
-    for (uint32_t it = 0; it < 2u * kHandoff; it++) { // every ancestor counts this node
-      atomicAdd(&s_size[p], 1u);
-      if (p == 0u) break;
-      p = s_parent[p];
-    }
-  }
-  __syncthreads();
-  for (uint32_t x = lane; x < N; x += 64u) {
-    // pre-order: a low-side child (odd creation index) follows its parent, a high-side child follows the low side's subtree
-    uint32_t acc = 0, y = x;
-    for (uint32_t it = 0; it < 2u * kHandoff && y != 0u; it++) {
-      acc += 1u + ((y & 1u) ? 0u : s_size[y - 1u]);
-      y = s_parent[y];
-    }
-    map[x] = (uint16_t)acc;
-  }
-  // stats: the leaders' partial values
-  for (int off = 32; off > 0; off >>= 1) {
-    leaves += __shfl_xor(leaves, off);
-    const uint32_t dd = __shfl_xor(deepest, off), bb = __shfl_xor(biggest_leaf, off);
-    deepest = dd > deepest ? dd : deepest;
-    biggest_leaf = bb > biggest_leaf ? bb : biggest_leaf;
-  }
-  if (lane == 0) {
-    task.size = N;
-    task_stats<T>(task, leaves, deepest, biggest_leaf);
-  }
-}
 
 // ---------------------------------------------------------------------------
 // relayout: sizes bottom-up, DFS pre-order top-down (single block over the
@@ -2664,11 +1396,6 @@ hipError_t gpu_build(hipStream_t s, const T *d_verts, const uint32_t *d_faces, c
                      uint32_t min_leaf, uint32_t max_depth, uint32_t bin_size, unsigned build_flags, DevBuf *workspace, DevBuf *nodes_buf,
                      DevBuf *indices_buf, void *pinned, hipEvent_t ev, std::string *err) {
   typedef typename Wire<T>::Node Node;
-#ifdef NRT_PROF
-  const bool subtree_rows = (build_flags & kBuildSubtreeDfs) == 0;
-#else
-  const bool subtree_rows = true; // (k_subtree is not in this library)
-#endif
   const bool morton_order = (build_flags & kBuildMorton) != 0;
   static_assert(offsetof(LevelInfo, level_begin) <= kBuildPinnedBytes, "state block");
   const int K = (int)(bin_size < 2 ? 2 : (bin_size > (uint32_t)kMaxBins ? (uint32_t)kMaxBins : bin_size));
@@ -2729,7 +1456,7 @@ hipError_t gpu_build(hipStream_t s, const T *d_verts, const uint32_t *d_faces, c
       hipLaunchKernelGGL((k_gather_records<T>), dim3((n + 255) / 256), dim3(256), 0, s, recs[0], vals[pp], n, recs[1]);
       cur = 1;
     }
-    const LeafRule rule = {max_depth, min_leaf > 1u ? min_leaf : 1u};
+    const LeafRule rule = make_leaf_rule(min_leaf, max_depth);
     hipLaunchKernelGGL((k_make_root<T>), dim3(1), dim3(64), 0, s, scene, n, rule, (uint32_t)cur, top, small_list,
                        info);
     BCHK(hipGetLastError());
@@ -2785,16 +1512,10 @@ hipError_t gpu_build(hipStream_t s, const T *d_verts, const uint32_t *d_faces, c
     NRT_RANGE("build: subtree phase + layout + emission");
 
     // ---- subtree phase + relayout + emission ---------------------------------------------------------
-    if (num_small) {
-#ifdef NRT_PROF
-      if (!subtree_rows) // (the one-node-per-step form: the cross-check of the row form, tunable subtree_rows = 0 of the profiling build)
-        hipLaunchKernelGGL((k_subtree<T>), dim3(num_small), dim3(64), 0, s, top, small_list, recs[0], recs[1], Ks,
-                           min_leaf, max_depth, scratch, indices, info);
-      else
-#endif
-        hipLaunchKernelGGL((k_subtree_rows<T>), dim3(num_small), dim3(64), 0, s, top, small_list, recs[0], recs[1], Ks,
-                           min_leaf, max_depth, scratch, premap, indices, info);
-    }
+    const uint16_t *emit_map = nullptr; // (build_subtree.hip: how k_emit_small finds a task's nodes)
+    if (num_small)
+      emit_map = launch_subtree<T>(top, small_list, recs[0], recs[1], Ks, rule, scratch, premap, indices, info, num_small,
+                                   (build_flags & kBuildSubtreeDfs) != 0, s);
     BCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_layout<T>), hipFuncAttributeMaxDynamicSharedMemorySize,
                              (int)(2 * kLayoutLds * sizeof(uint32_t)))); // (per device: set on every build, it costs nothing)
     if (plan.max_top > kLayoutLds) { // (a top array that may not fit LDS: the grid-wide form of the same steps; no-ops if it does fit)
@@ -2811,8 +1532,7 @@ hipError_t gpu_build(hipStream_t s, const T *d_verts, const uint32_t *d_faces, c
     hipLaunchKernelGGL((k_emit_top<T>), dim3((unsigned)((plan.max_top + 255) / 256)), dim3(256), 0, s, top, info, recs[0], recs[1],
                        nodes, indices);
     if (num_small)
-      hipLaunchKernelGGL((k_emit_small<T>), dim3(num_small), dim3(64), 0, s, top, small_list, scratch,
-                         subtree_rows ? premap : (uint16_t *)nullptr, nodes, info);
+      hipLaunchKernelGGL((k_emit_small<T>), dim3(num_small), dim3(64), 0, s, top, small_list, scratch, emit_map, nodes, info);
     BCHK(hipGetLastError());
     return hipSuccess;
   }

@@ -59,6 +59,20 @@ hipError_t gpu_build(hipStream_t s, const T *d_verts, const uint32_t *d_faces, c
                      DevBuf *nodes_buf, DevBuf *indices_buf, void *pinned, hipEvent_t ev, std::string *err);
 hipError_t gpu_build_result(const void *pinned, hipEvent_t ev, BuildResult *res);
 
+// ---- build_subtree.hip: the subtree phase of a build (the types are the builder's own: build_dev.h) ------------------------
+template <typename T>
+struct TopNode;
+template <typename T>
+struct PrimRec;
+struct LeafRule;
+struct LevelInfo;
+// one wave per task of small_list; returns the creation-index map k_emit_small has to apply (nullptr: nodes in pre-order).
+// dfs_form: the one-node-per-step kernel, which only the profiling library carries (the product library ignores it)
+template <typename T>
+const uint16_t *launch_subtree(TopNode<T> *top, const uint32_t *small_list, const PrimRec<T> *recs0, const PrimRec<T> *recs1, int Ks,
+                               LeafRule rule, typename Wire<T>::Node *scratch, uint16_t *premap, uint32_t *indices, LevelInfo *info,
+                               uint32_t num_small, bool dfs_form, hipStream_t stream);
+
 // ---- refit.hip: the per-tree level plan of a refit, and one refit over it ------------------------------------------------
 size_t refit_plan_bytes(uint32_t tree_depth, uint64_t num_nodes);
 template <typename T>

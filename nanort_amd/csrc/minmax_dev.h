@@ -1,4 +1,4 @@
-// nanort_amd/csrc/minmax_dev.h — the comparison helpers of the builder (build.hip) and the refit (refit.hip).
+// nanort_amd/csrc/minmax_dev.h — the comparison helpers of the builder (build.hip, build_subtree.hip) and the refit (refit.hip).
 //
 // Both compute node boxes with these exact selects, in a fixed order, so a box never depends on scheduling and a refit of
 // an unchanged mesh reproduces the built boxes.

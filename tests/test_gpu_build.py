@@ -511,3 +511,27 @@ def test_the_two_subtree_kernels_agree_on_random_meshes_and_options(seed):
                max_tree_depth=int(rng.choice([3, 9, 20, 256])))
     nodes, idx, st = _two_subtree_kernels(real, v, f, **opt)
     validate_bvh(nodes, idx, v, f, min_leaf=opt["min_leaf_primitives"], max_depth=opt["max_tree_depth"], stats=st)
+
+
+@pytest.mark.parametrize("real", [np.float32, np.float64])
+def test_rebuilds_of_one_context_hand_their_bins_on_clean(real):
+    """Bins and accumulators are never re-initialised between builds: every reader hands its bin on clean (take_bin /
+    clean_bins).  One context is rebuilt back to back over sizes that take every path to a split — a one-chunk node cut inside
+    k_bin (257), a multi-chunk node through k_split (4097, 2049), subtree tasks on either side of the hand-off (255, 257's
+    children) and a task that is itself a leaf (3 with min_leaf 4) — while the bin count and the leaf size change under it:
+    each tree must be, byte for byte, the one a fresh context builds."""
+    rng = np.random.default_rng(77)
+    reused = BVHAccel(real)
+    for i, n in enumerate([257, 4097, 255, 2049, 3] * 2):
+        tri = rng.uniform(-1, 1, (n, 1, 3)) + rng.normal(0, 0.03, (n, 3, 3))
+        v, f = tri.reshape(-1, 3).astype(real), np.arange(3 * n, dtype=np.uint32).reshape(n, 3)
+        opt = dict(bin_size=(2, 16, 64)[i % 3], min_leaf_primitives=(1, 4)[i % 2])
+        o = default_build_options(real)
+        for k, val in opt.items():
+            o[k] = val
+        assert reused.Build(n, TriangleMesh(v, f), o)
+        nodes, idx = reused.GetTree()
+        fresh, fnodes, fidx = build(real, v, f, **opt)
+        fresh.close()
+        assert nodes.tobytes() == fnodes.tobytes() and idx.tobytes() == fidx.tobytes(), (i, n, opt)
+        validate_bvh(nodes, idx, v, f, min_leaf=opt["min_leaf_primitives"], stats=reused.GetStatistics())

@@ -1,5 +1,5 @@
 #!/bin/bash
-# A/B of compile-time variants of the builder (build.hip): each argument is a string of -D flags ("" = as shipped).
+# A/B of compile-time variants of the builder (build.hip, build_subtree.hip): each argument is a string of -D flags ("" = as shipped).
 # Builds a private copy of the library per variant, prints median build ms (1M-triangle plane fp32 / fp64, 70k sphere, 10M plane)
 # and a fingerprint of the fp32 1M tree (must not change), restores the shipped library.
 #   tools/build_variant_ab.sh out.txt "" "-DNRT_BUILD_TILE=1024"
@@ -12,7 +12,8 @@ cp nanort_amd/lib/libnanort_hip.so /tmp/libnanort_hip.keep
 trap 'cp /tmp/libnanort_hip.keep nanort_amd/lib/libnanort_hip.so' EXIT
 for flags in "$@"; do
   (cd nanort_amd/csrc && /opt/rocm/bin/hipcc $F $flags -c build.hip -o /tmp/build_probe.o &&
-   /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../lib/libnanort_hip.so api.o traverse.o /tmp/build_probe.o scene.o)
+   /opt/rocm/bin/hipcc $F $flags -c build_subtree.hip -o /tmp/build_subtree_probe.o &&
+   /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../lib/libnanort_hip.so api.o traverse.o /tmp/build_probe.o /tmp/build_subtree_probe.o scene.o)
   echo "== ${flags:-as shipped}" >> "$out"
   python - >> "$out" 2>&1 <<'PY'
 import sys, hashlib, numpy as np
