@@ -1189,6 +1189,28 @@ struct HipApi<float> {
   static nrt_status OccludedDevice(nrt_ctx *c, const RayPod *r, uint64_t n, const nrt_trace_options *o, uint8_t *m, void *s) {
     return nrtOccludedBatchDevice_f32(c, r, n, o, m, s);
   }
+  // (per-ray skip ids, include/nanort_hip.h: the calls above with one skip id per ray)
+  static nrt_status TraverseSkip(nrt_ctx *c, const RayPod *r, uint64_t n, const nrt_trace_options *o, const uint32_t *ids, HitPod *h, uint8_t *m) {
+    return nrtTraverseBatchSkip_f32(c, r, n, o, ids, h, m);
+  }
+  static nrt_status TraverseSkipDevice(nrt_ctx *c, const RayPod *r, uint64_t n, const nrt_trace_options *o, const uint32_t *ids, HitPod *h, uint8_t *m,
+                                       void *s) {
+    return nrtTraverseBatchSkipDevice_f32(c, r, n, o, ids, h, m, s);
+  }
+  static nrt_status OccludedSkip(nrt_ctx *c, const RayPod *r, uint64_t n, const nrt_trace_options *o, const uint32_t *ids, uint8_t *m) {
+    return nrtOccludedBatchSkip_f32(c, r, n, o, ids, m);
+  }
+  static nrt_status OccludedSkipDevice(nrt_ctx *c, const RayPod *r, uint64_t n, const nrt_trace_options *o, const uint32_t *ids, uint8_t *m, void *s) {
+    return nrtOccludedBatchSkipDevice_f32(c, r, n, o, ids, m, s);
+  }
+  static nrt_status TraverseBatchesSkip(nrt_ctx *c, uint32_t nb, const RayPod *const *r, const uint64_t *n, const nrt_trace_options *o,
+                                        const uint32_t *const *ids, HitPod *const *h, uint8_t *const *m, const uint32_t *fl, void *s) {
+    return nrtTraverseBatchesSkipDevice_f32(c, nb, r, n, o, ids, h, m, fl, s);
+  }
+  static nrt_status TraverseBatchesSkipHost(nrt_ctx *c, uint32_t nb, const RayPod *const *r, const uint64_t *n, const nrt_trace_options *o,
+                                            const uint32_t *const *ids, HitPod *const *h, uint8_t *const *m, const uint32_t *fl) {
+    return nrtTraverseBatchesSkip_f32(c, nb, r, n, o, ids, h, m, fl);
+  }
   static nrt_status MultiHit(nrt_ctx *c, const RayPod *r, uint64_t n, uint32_t k, const nrt_trace_options *o, HitPod *h, uint32_t *cnt) {
     return nrtMultiHitTraverseBatch_f32(c, r, n, k, o, h, cnt);
   }
@@ -1228,6 +1250,28 @@ struct HipApi<double> {
   static nrt_status Occluded(nrt_ctx *c, const RayPod *r, uint64_t n, const nrt_trace_options *o, uint8_t *m) { return nrtOccludedBatch_f64(c, r, n, o, m); }
   static nrt_status OccludedDevice(nrt_ctx *c, const RayPod *r, uint64_t n, const nrt_trace_options *o, uint8_t *m, void *s) {
     return nrtOccludedBatchDevice_f64(c, r, n, o, m, s);
+  }
+  // (per-ray skip ids, include/nanort_hip.h: the calls above with one skip id per ray)
+  static nrt_status TraverseSkip(nrt_ctx *c, const RayPod *r, uint64_t n, const nrt_trace_options *o, const uint32_t *ids, HitPod *h, uint8_t *m) {
+    return nrtTraverseBatchSkip_f64(c, r, n, o, ids, h, m);
+  }
+  static nrt_status TraverseSkipDevice(nrt_ctx *c, const RayPod *r, uint64_t n, const nrt_trace_options *o, const uint32_t *ids, HitPod *h, uint8_t *m,
+                                       void *s) {
+    return nrtTraverseBatchSkipDevice_f64(c, r, n, o, ids, h, m, s);
+  }
+  static nrt_status OccludedSkip(nrt_ctx *c, const RayPod *r, uint64_t n, const nrt_trace_options *o, const uint32_t *ids, uint8_t *m) {
+    return nrtOccludedBatchSkip_f64(c, r, n, o, ids, m);
+  }
+  static nrt_status OccludedSkipDevice(nrt_ctx *c, const RayPod *r, uint64_t n, const nrt_trace_options *o, const uint32_t *ids, uint8_t *m, void *s) {
+    return nrtOccludedBatchSkipDevice_f64(c, r, n, o, ids, m, s);
+  }
+  static nrt_status TraverseBatchesSkip(nrt_ctx *c, uint32_t nb, const RayPod *const *r, const uint64_t *n, const nrt_trace_options *o,
+                                        const uint32_t *const *ids, HitPod *const *h, uint8_t *const *m, const uint32_t *fl, void *s) {
+    return nrtTraverseBatchesSkipDevice_f64(c, nb, r, n, o, ids, h, m, fl, s);
+  }
+  static nrt_status TraverseBatchesSkipHost(nrt_ctx *c, uint32_t nb, const RayPod *const *r, const uint64_t *n, const nrt_trace_options *o,
+                                            const uint32_t *const *ids, HitPod *const *h, uint8_t *const *m, const uint32_t *fl) {
+    return nrtTraverseBatchesSkip_f64(c, nb, r, n, o, ids, h, m, fl);
   }
   static nrt_status MultiHit(nrt_ctx *c, const RayPod *r, uint64_t n, uint32_t k, const nrt_trace_options *o, HitPod *h, uint32_t *cnt) {
     return nrtMultiHitTraverseBatch_f64(c, r, n, k, o, h, cnt);
@@ -1600,6 +1644,25 @@ class BVHAccel {
     return true;
   }
 
+  // The batch call on the HOST, with or without NANORT_USE_HIP_BACKEND and for any intersector: N calls of Traverse(), ray i
+  // through a copy of `intersector` of its own and with its own options — `options` with skip_prim_id replaced by
+  // skip_prim_ids[i] when the array is given (the contract of include/nanort_hip.h, "per-ray skip ids": 0xFFFFFFFF or an id
+  // that names no primitive skips nothing).  isects[i] is written only when ray i hits; hit_out[i] (optional) receives 1 / 0.
+  template <class I, class H>
+  bool TraverseBatch(const Ray<T> *rays, size_t num_rays, const I &intersector, H *isects, unsigned char *hit_out = NULL,
+                     const BVHTraceOptions &options = BVHTraceOptions(), const unsigned int *skip_prim_ids = NULL) const {
+    for (size_t i = 0; i < num_rays; i++) {
+      const I ray_intersector(intersector);
+      BVHTraceOptions ray_options(options);
+      if (skip_prim_ids) ray_options.skip_prim_id = skip_prim_ids[i];
+      H isect;
+      const bool hit = Traverse(rays[i], ray_intersector, &isect, ray_options);
+      if (hit) isects[i] = isect;
+      if (hit_out) hit_out[i] = hit ? 1 : 0;
+    }
+    return true;
+  }
+
 #ifdef NANORT_USE_HIP_BACKEND
   // Closest hit for each of `num_rays` rays in one GPU launch.  isects[i] is written only when
   // ray i hits (exactly like N calls of Traverse()); hit_out[i] (optional) receives 1 / 0.
@@ -1611,16 +1674,20 @@ class BVHAccel {
   // scatter into the caller's arrays, and the lazy device-side updates (the upload of a Load()ed tree, the cylinder cap
   // re-send, a copy-on-write detach); calls on one object are thereby serialised, calls on different objects (copies
   // included) are not.
+  // `skip_prim_ids` (here and on the Device / Occluded / Batches forms below; triangle accels): one id per ray, traced in the place
+  // of options.skip_prim_id for that ray — a bounce or shadow wave whose rays leave different triangles needs no epsilon
+  // (include/nanort_hip.h, "per-ray skip ids"; NULL: the call as it always was).  On a multi-device accel such a batch is traced
+  // by the first device alone: the records are the same.
   bool TraverseBatch(const Ray<T> *rays, size_t num_rays, TriangleIntersection<T> *isects, unsigned char *hit_out = NULL,
-                     const BVHTraceOptions &options = BVHTraceOptions()) const {
-    return TraverseBatchImpl(rays, num_rays, isects, hit_out, options);
+                     const BVHTraceOptions &options = BVHTraceOptions(), const unsigned int *skip_prim_ids = NULL) const {
+    return TraverseBatchImpl(rays, num_rays, isects, hit_out, options, skip_prim_ids);
   }
   // The same launch for callers that keep their ray waves in HBM (a wavefront renderer whose shading runs on the GPU):
   // `d_rays`, `d_isects`, `d_hit` are device pointers, the call is asynchronous on `hip_stream` (a hipStream_t).
   // Unlike the host variant every record is written: a miss stores {u = 0, v = 0, t = ray.max_t, prim_id = 0xFFFFFFFF}.
   // Launches on different streams may overlap on the GPU.
   bool TraverseBatchDevice(const Ray<T> *d_rays, size_t num_rays, TriangleIntersection<T> *d_isects, unsigned char *d_hit,
-                           void *hip_stream, const BVHTraceOptions &options = BVHTraceOptions()) const {
+                           void *hip_stream, const BVHTraceOptions &options = BVHTraceOptions(), const unsigned int *d_skip_prim_ids = NULL) const {
     std::lock_guard<std::mutex> lock(batch_mutex_);
     if (!ctx_ || device_tree_stale_ || device_prim_kind_ != 0) {
       backend_error_ = "TraverseBatchDevice: no triangle tree on the GPU (Build() with the built-in triangle types, or TraverseBatch() once after Load())";
@@ -1628,7 +1695,7 @@ class BVHAccel {
     }
     nrt_trace_options o;
     std::memcpy(&o, &options, sizeof(o));
-    if (DeviceLaunch(ctx_.get(), d_rays, num_rays, &o, d_isects, d_hit, hip_stream) != NRT_OK) {
+    if (DeviceLaunch(ctx_.get(), d_rays, num_rays, &o, d_isects, d_hit, hip_stream, d_skip_prim_ids) != NRT_OK) {
       backend_error_ = nrtLastError(ctx_.get());
       return false;
     }
@@ -1639,7 +1706,7 @@ class BVHAccel {
   // shadow query and next path wave, without a second stream.  Records equal those of separate calls.  `occlusion` may be NULL.
   bool TraverseBatchesDevice(size_t num_waves, const Ray<T> *const *d_rays, const size_t *num_rays, TriangleIntersection<T> *const *d_isects,
                              unsigned char *const *d_hit, const unsigned char *occlusion, void *hip_stream,
-                             const BVHTraceOptions &options = BVHTraceOptions()) const {
+                             const BVHTraceOptions &options = BVHTraceOptions(), const unsigned int *const *d_skip_prim_ids = NULL) const {
     typedef detail::HipApi<T> Api;
     std::lock_guard<std::mutex> lock(batch_mutex_);
     if (!ctx_ || device_tree_stale_ || device_prim_kind_ != 0) {
@@ -1660,7 +1727,10 @@ class BVHAccel {
       n[k] = num_rays[k];
       fl[k] = (occlusion && occlusion[k]) ? NRT_BATCH_OCCLUSION : 0u;
     }
-    if (Api::TraverseBatches(ctx_.get(), static_cast<uint32_t>(num_waves), r.data(), n.data(), &o, h.data(), m.data(), fl.data(), hip_stream) != NRT_OK) {
+    if ((d_skip_prim_ids ? Api::TraverseBatchesSkip(ctx_.get(), static_cast<uint32_t>(num_waves), r.data(), n.data(), &o, d_skip_prim_ids, h.data(),
+                                                    m.data(), fl.data(), hip_stream)
+                         : Api::TraverseBatches(ctx_.get(), static_cast<uint32_t>(num_waves), r.data(), n.data(), &o, h.data(), m.data(), fl.data(),
+                                                hip_stream)) != NRT_OK) {
       backend_error_ = nrtLastError(ctx_.get());
       return false;
     }
@@ -1673,7 +1743,8 @@ class BVHAccel {
   // TraverseBatch(); hit_out[k] may be NULL.  Records and flags are exactly those of separate TraverseBatch() /
   // OccludedBatch() calls.  `occlusion` may be NULL.
   bool TraverseBatches(size_t num_waves, const Ray<T> *const *rays, const size_t *num_rays, TriangleIntersection<T> *const *isects,
-                       unsigned char *const *hit_out, const unsigned char *occlusion, const BVHTraceOptions &options = BVHTraceOptions()) const {
+                       unsigned char *const *hit_out, const unsigned char *occlusion, const BVHTraceOptions &options = BVHTraceOptions(),
+                       const unsigned int *const *skip_prim_ids = NULL) const {
     typedef detail::HipApi<T> Api;
     typedef typename Api::HitPod HitPod;
     std::lock_guard<std::mutex> lock(batch_mutex_);
@@ -1708,7 +1779,10 @@ class BVHAccel {
     }
     nrt_trace_options o;
     std::memcpy(&o, &options, sizeof(o));
-    if (Api::TraverseBatchesHost(ctx_.get(), static_cast<uint32_t>(num_waves), r.data(), n.data(), &o, h.data(), m.data(), fl.data()) != NRT_OK) {
+    if ((skip_prim_ids ? Api::TraverseBatchesSkipHost(ctx_.get(), static_cast<uint32_t>(num_waves), r.data(), n.data(), &o, skip_prim_ids, h.data(),
+                                                      m.data(), fl.data())
+                       : Api::TraverseBatchesHost(ctx_.get(), static_cast<uint32_t>(num_waves), r.data(), n.data(), &o, h.data(), m.data(), fl.data())) !=
+        NRT_OK) {
       backend_error_ = nrtLastError(ctx_.get());
       return false;
     }
@@ -1724,7 +1798,8 @@ class BVHAccel {
   }
   // Opt-in extension without a reference counterpart: occlusion queries.  occluded_out[i] is exactly what
   // TraverseBatch() would report in hit_out[i], but a ray stops at the first primitive it accepts (shadow rays).
-  bool OccludedBatch(const Ray<T> *rays, size_t num_rays, unsigned char *occluded_out, const BVHTraceOptions &options = BVHTraceOptions()) const {
+  bool OccludedBatch(const Ray<T> *rays, size_t num_rays, unsigned char *occluded_out, const BVHTraceOptions &options = BVHTraceOptions(),
+                     const unsigned int *skip_prim_ids = NULL) const {
     typedef detail::HipApi<T> Api;
     std::lock_guard<std::mutex> lock(batch_mutex_);
     if (!ctx_ || device_tree_stale_ || device_prim_kind_ != 0) {
@@ -1733,7 +1808,9 @@ class BVHAccel {
     }
     nrt_trace_options o;
     std::memcpy(&o, &options, sizeof(o));
-    if (Api::Occluded(ctx_.get(), reinterpret_cast<const typename Api::RayPod *>(rays), num_rays, &o, occluded_out) != NRT_OK) {
+    const typename Api::RayPod *r = reinterpret_cast<const typename Api::RayPod *>(rays);
+    if ((skip_prim_ids ? Api::OccludedSkip(ctx_.get(), r, num_rays, &o, skip_prim_ids, occluded_out) : Api::Occluded(ctx_.get(), r, num_rays, &o, occluded_out)) !=
+        NRT_OK) {
       backend_error_ = nrtLastError(ctx_.get());
       return false;
     }
@@ -1741,7 +1818,7 @@ class BVHAccel {
   }
   // ... and with device pointers, asynchronous on `hip_stream` (see TraverseBatchDevice).
   bool OccludedBatchDevice(const Ray<T> *d_rays, size_t num_rays, unsigned char *d_occluded, void *hip_stream,
-                           const BVHTraceOptions &options = BVHTraceOptions()) const {
+                           const BVHTraceOptions &options = BVHTraceOptions(), const unsigned int *d_skip_prim_ids = NULL) const {
     typedef detail::HipApi<T> Api;
     std::lock_guard<std::mutex> lock(batch_mutex_);
     if (!ctx_ || device_tree_stale_ || device_prim_kind_ != 0) {
@@ -1750,7 +1827,9 @@ class BVHAccel {
     }
     nrt_trace_options o;
     std::memcpy(&o, &options, sizeof(o));
-    if (Api::OccludedDevice(ctx_.get(), reinterpret_cast<const typename Api::RayPod *>(d_rays), num_rays, &o, d_occluded, hip_stream) != NRT_OK) {
+    const typename Api::RayPod *r = reinterpret_cast<const typename Api::RayPod *>(d_rays);
+    if ((d_skip_prim_ids ? Api::OccludedSkipDevice(ctx_.get(), r, num_rays, &o, d_skip_prim_ids, d_occluded, hip_stream)
+                         : Api::OccludedDevice(ctx_.get(), r, num_rays, &o, d_occluded, hip_stream)) != NRT_OK) {
       backend_error_ = nrtLastError(ctx_.get());
       return false;
     }
@@ -1907,8 +1986,9 @@ class BVHAccel {
 
  private:
   static nrt_status DeviceLaunch(nrt_ctx *c, const Ray<T> *r, size_t n, const nrt_trace_options *o, TriangleIntersection<T> *h,
-                                 unsigned char *m, void *stream) {
+                                 unsigned char *m, void *stream, const unsigned int *ids = NULL) {
     typedef detail::HipApi<T> Api;
+    if (ids) return Api::TraverseSkipDevice(c, reinterpret_cast<const typename Api::RayPod *>(r), n, o, ids, reinterpret_cast<typename Api::HitPod *>(h), m, stream);
     return Api::TraverseDevice(c, reinterpret_cast<const typename Api::RayPod *>(r), n, o, reinterpret_cast<typename Api::HitPod *>(h), m, stream);
   }
   // The checks every host batch call makes (caller holds batch_mutex_): a context, the primitive kind the call's records are
@@ -1945,7 +2025,8 @@ class BVHAccel {
     return true;
   }
   template <class Hit>
-  bool TraverseBatchImpl(const Ray<T> *rays, size_t num_rays, Hit *isects, unsigned char *hit_out, const BVHTraceOptions &options) const {
+  bool TraverseBatchImpl(const Ray<T> *rays, size_t num_rays, Hit *isects, unsigned char *hit_out, const BVHTraceOptions &options,
+                         const unsigned int *skip_prim_ids = NULL) const {
     typedef detail::HipApi<T> Api;
     static_assert(sizeof(Ray<T>) == sizeof(typename Api::RayPod), "Ray layout");
     static_assert(sizeof(Hit) == sizeof(typename Api::HitPod), "intersection record layout");
@@ -1966,7 +2047,12 @@ class BVHAccel {
     }
     nrt_trace_options o;
     std::memcpy(&o, &options, sizeof(o));
-    if (!peers_.empty() && want_kind == 0) {
+    if (skip_prim_ids) {  // (one device: nrtTraverseBatchMulti takes no per-ray ids, and the records are the same)
+      if (Api::TraverseSkip(ctx_.get(), reinterpret_cast<const typename Api::RayPod *>(rays), num_rays, &o, skip_prim_ids, tmp, mask) != NRT_OK) {
+        backend_error_ = nrtLastError(ctx_.get());
+        return false;
+      }
+    } else if (!peers_.empty() && want_kind == 0) {
       // NANORT_HIP_DEVICES: the batch is split row-interleaved over the replicas, one per device (nrtTraverseBatchMulti)
       std::vector<nrt_ctx *> cs(1, ctx_.get());
       for (size_t k = 0; k < peers_.size(); k++) cs.push_back(peers_[k].get());

@@ -492,6 +492,57 @@ NRT_API nrt_status nrtTraverseBatches_f64(nrt_ctx *ctx, uint32_t num_batches, co
                                           const nrt_trace_options *options, nrt_hit_f64 *const *hits_out, uint8_t *const *masks_out,
                                           const uint32_t *batch_flags);
 
+/* ---- per-ray skip ids: BVHTraceOptions::skip_prim_id (nanort.h:617-623, 2387-2395) for every ray of a batch -----------------
+ * The reference's answer to self-intersection — a ray that leaves triangle p is traced with skip_prim_id = p and needs no
+ * epsilon — works per ray there, because Traverse() takes one ray and that ray's own options.  The batch calls above take one
+ * nrt_trace_options per launch; these take, besides it, one id per ray (a bounce or shadow wave: the previous wave's prim_id
+ * column; fed back wave after wave: depth peeling).  The contract, for a call that passes `skip_prim_ids`:
+ *  - every output of ray i is exactly what the same entry point without the array returns for that ray traced alone with
+ *    options->skip_prim_id replaced by skip_prim_ids[i] — bit for bit, under every walk and tunable;
+ *  - 0xFFFFFFFF skips nothing, and so does any id at or above the context's number of faces;
+ *  - options->skip_prim_id is not read; prim_ids_range and cull_back_face keep their launch-wide meaning;
+ *  - skip_prim_ids == NULL is the existing call: the same kernel variant, the same bytes out.
+ * Triangle contexts only, both precisions.  Sphere, cylinder and curve contexts refuse with NRT_ERR_INVALID (their intersectors
+ * have no skip id), a context of the other precision with NRT_ERR_PRECISION, a device array that is not 4-byte aligned with
+ * NRT_ERR_INVALID; a refusal sets nrtLastError and writes nothing.  The host forms upload the ids beside the rays (a batch
+ * traced in pieces: each piece with its slice); the Device forms read `d_skip_prim_ids` (num_rays words in HBM) during the
+ * launch, asynchronously on `hip_stream`.  nrtOccludedBatchSkip*: mask[i] is the hit flag of the closest-hit form with the same ids.
+ * nrtTraverseBatchesSkip*: an array of `num_batches` pointers; the array or any entry of it may be NULL, and a batch with a NULL
+ * entry uses options->skip_prim_id; records are exactly those of separate calls (fp32: still one launch, fp64: one after the other).
+ * Not covered: multi-hit, nrtTraverseCountDevice, nrtTraverseBatchMulti, nrtGroup*, scenes and the Embree shim take no per-ray ids. */
+NRT_API nrt_status nrtTraverseBatchSkip_f32(nrt_ctx *ctx, const nrt_ray_f32 *rays, uint64_t num_rays, const nrt_trace_options *options,
+                                            const uint32_t *skip_prim_ids, nrt_hit_f32 *hits_out, uint8_t *hit_mask_out);
+NRT_API nrt_status nrtTraverseBatchSkip_f64(nrt_ctx *ctx, const nrt_ray_f64 *rays, uint64_t num_rays, const nrt_trace_options *options,
+                                            const uint32_t *skip_prim_ids, nrt_hit_f64 *hits_out, uint8_t *hit_mask_out);
+NRT_API nrt_status nrtTraverseBatchSkipDevice_f32(nrt_ctx *ctx, const nrt_ray_f32 *d_rays, uint64_t num_rays, const nrt_trace_options *options,
+                                                  const uint32_t *d_skip_prim_ids, nrt_hit_f32 *d_hits_out, uint8_t *d_hit_mask_out,
+                                                  void *hip_stream);
+NRT_API nrt_status nrtTraverseBatchSkipDevice_f64(nrt_ctx *ctx, const nrt_ray_f64 *d_rays, uint64_t num_rays, const nrt_trace_options *options,
+                                                  const uint32_t *d_skip_prim_ids, nrt_hit_f64 *d_hits_out, uint8_t *d_hit_mask_out,
+                                                  void *hip_stream);
+NRT_API nrt_status nrtOccludedBatchSkip_f32(nrt_ctx *ctx, const nrt_ray_f32 *rays, uint64_t num_rays, const nrt_trace_options *options,
+                                            const uint32_t *skip_prim_ids, uint8_t *mask_out);
+NRT_API nrt_status nrtOccludedBatchSkip_f64(nrt_ctx *ctx, const nrt_ray_f64 *rays, uint64_t num_rays, const nrt_trace_options *options,
+                                            const uint32_t *skip_prim_ids, uint8_t *mask_out);
+NRT_API nrt_status nrtOccludedBatchSkipDevice_f32(nrt_ctx *ctx, const nrt_ray_f32 *d_rays, uint64_t num_rays, const nrt_trace_options *options,
+                                                  const uint32_t *d_skip_prim_ids, uint8_t *d_mask_out, void *hip_stream);
+NRT_API nrt_status nrtOccludedBatchSkipDevice_f64(nrt_ctx *ctx, const nrt_ray_f64 *d_rays, uint64_t num_rays, const nrt_trace_options *options,
+                                                  const uint32_t *d_skip_prim_ids, uint8_t *d_mask_out, void *hip_stream);
+NRT_API nrt_status nrtTraverseBatchesSkipDevice_f32(nrt_ctx *ctx, uint32_t num_batches, const nrt_ray_f32 *const *d_rays,
+                                                    const uint64_t *num_rays, const nrt_trace_options *options,
+                                                    const uint32_t *const *d_skip_prim_ids, nrt_hit_f32 *const *d_hits_out,
+                                                    uint8_t *const *d_masks_out, const uint32_t *batch_flags, void *hip_stream);
+NRT_API nrt_status nrtTraverseBatchesSkipDevice_f64(nrt_ctx *ctx, uint32_t num_batches, const nrt_ray_f64 *const *d_rays,
+                                                    const uint64_t *num_rays, const nrt_trace_options *options,
+                                                    const uint32_t *const *d_skip_prim_ids, nrt_hit_f64 *const *d_hits_out,
+                                                    uint8_t *const *d_masks_out, const uint32_t *batch_flags, void *hip_stream);
+NRT_API nrt_status nrtTraverseBatchesSkip_f32(nrt_ctx *ctx, uint32_t num_batches, const nrt_ray_f32 *const *rays, const uint64_t *num_rays,
+                                              const nrt_trace_options *options, const uint32_t *const *skip_prim_ids,
+                                              nrt_hit_f32 *const *hits_out, uint8_t *const *masks_out, const uint32_t *batch_flags);
+NRT_API nrt_status nrtTraverseBatchesSkip_f64(nrt_ctx *ctx, uint32_t num_batches, const nrt_ray_f64 *const *rays, const uint64_t *num_rays,
+                                              const nrt_trace_options *options, const uint32_t *const *skip_prim_ids,
+                                              nrt_hit_f64 *const *hits_out, uint8_t *const *masks_out, const uint32_t *batch_flags);
+
 /* One HOST batch spread over several contexts — typically one per GPU of the node (nrtDeviceCount), each holding the same
  * tree: nrtBuild is deterministic, so building the same mesh on every context gives bit-identical replicas (or nrtSetTree the
  * same arrays).  The batch is cut into rows of `row_len` rays (an image row; 0 = 4096) and row r is traced by context

@@ -415,13 +415,32 @@ class BVHAccel:
         self._check(getattr(self._L, "nrtRefitDevice_" + self._s)(self._h, d_vertices.data_ptr(), stride, stream))
 
     # -- traverse -----------------------------------------------------------
-    def TraverseBatch(self, rays, options=None):
-        """N x BVHAccel::Traverse (reference nanort.h:2487-2556). Returns (hits, mask)."""
+    @staticmethod
+    def _host_skip_ids(skip_prim_ids, n):
+        """One uint32 skip id per ray (include/nanort_hip.h, "per-ray skip ids"), contiguous."""
+        ids = np.ascontiguousarray(skip_prim_ids, dtype=np.uint32).reshape(-1)
+        if ids.shape[0] != n:
+            raise ValueError("skip_prim_ids: %d ids for %d rays" % (ids.shape[0], n))
+        return ids
+
+    @staticmethod
+    def _device_skip_ids(d_skip_prim_ids, n):
+        assert d_skip_prim_ids.numel() * d_skip_prim_ids.element_size() >= 4 * n, "skip_prim_ids: fewer ids than rays"
+        return d_skip_prim_ids.data_ptr()
+
+    def TraverseBatch(self, rays, options=None, skip_prim_ids=None):
+        """N x BVHAccel::Traverse (reference nanort.h:2487-2556). Returns (hits, mask).  `skip_prim_ids`: one uint32 per ray, traced
+        in the place of options.skip_prim_id for that ray (triangle meshes; nrtTraverseBatchSkip)."""
         rays = np.ascontiguousarray(rays, dtype=ray_dtype(self.real))
         n = rays.shape[0]
         mask = np.zeros((n,), dtype=np.uint8)
         if options is not None:
             options = np.asarray(options, dtype=TRACE_OPTIONS).reshape(1)
+        if skip_prim_ids is not None:  # (the library refuses the primitive kinds that have no skip id)
+            ids = self._host_skip_ids(skip_prim_ids, n)
+            hits = np.zeros((n,), dtype=hit_dtype(self.real))
+            self._check(getattr(self._L, "nrtTraverseBatchSkip_" + self._s)(self._h, _p(rays), n, _p(options), _p(ids), _p(hits), _p(mask)))
+            return hits, mask
         if self._is_curves():  # the example's 40-byte CurveIntersection records
             from .wire import CURVE_HIT_F32
 
@@ -440,9 +459,9 @@ class BVHAccel:
         )
         return hits, mask
 
-    def TraverseBatchDevice(self, d_rays, d_hits, d_mask=None, options=None, stream=None):
+    def TraverseBatchDevice(self, d_rays, d_hits, d_mask=None, options=None, stream=None, skip_prim_ids=None):
         """Same on HBM-resident torch uint8 tensors (raw PODs), async on `stream`
-        (default: torch's current stream)."""
+        (default: torch's current stream).  `skip_prim_ids`: a device tensor of one uint32 per ray (nrtTraverseBatchSkipDevice)."""
         import torch
 
         cyl, curves = isinstance(self._mesh, CylinderGeometry), self._is_curves()
@@ -453,6 +472,11 @@ class BVHAccel:
             stream = torch.cuda.current_stream(self.device).cuda_stream
         if options is not None:
             options = np.asarray(options, dtype=TRACE_OPTIONS).reshape(1)
+        if skip_prim_ids is not None:
+            self._check(getattr(self._L, "nrtTraverseBatchSkipDevice_" + self._s)(
+                self._h, d_rays.data_ptr(), n, _p(options), self._device_skip_ids(skip_prim_ids, n), d_hits.data_ptr(),
+                None if d_mask is None else d_mask.data_ptr(), self._stream_handle(stream)))
+            return n
         if curves:
             self._check(self._L.nrtTraverseBatchCurvesDevice_f32(
                 self._h, d_rays.data_ptr(), n, _p(options), d_hits.data_ptr(), None if d_mask is None else d_mask.data_ptr(), stream))
@@ -469,10 +493,11 @@ class BVHAccel:
         )
         return n
 
-    def TraverseBatchesDevice(self, batches, options=None, stream=None):
+    def TraverseBatchesDevice(self, batches, options=None, stream=None, skip_prim_ids=None):
         """nrtTraverseBatchesDevice: several independent batches — a list of (d_rays, d_hits, d_mask or None, n or None[, "occlusion"])
         torch uint8 tensors — walked by ONE persistent launch (asynchronous on `stream`).  A batch marked "occlusion" is an
-        occlusion query: only its d_mask is written (d_hits may be None).  Returns the ray counts."""
+        occlusion query: only its d_mask is written (d_hits may be None).  Returns the ray counts.  `skip_prim_ids`: a list with
+        one entry per batch, a device tensor of one uint32 per ray or None (that batch uses options.skip_prim_id)."""
         import torch
 
         rsz, hsz = ray_dtype(self.real).itemsize, hit_dtype(self.real).itemsize
@@ -494,13 +519,22 @@ class BVHAccel:
             stream = torch.cuda.current_stream(self.device).cuda_stream
         if options is not None:
             options = np.asarray(options, dtype=TRACE_OPTIONS).reshape(1)
+        if skip_prim_ids is not None:
+            assert len(skip_prim_ids) == nb, "skip_prim_ids: one entry per batch"
+            ids = (ctypes.c_void_p * nb)()
+            for k, t in enumerate(skip_prim_ids):
+                ids[k] = None if t is None else self._device_skip_ids(t, counts[k])
+            self._check(getattr(self._L, "nrtTraverseBatchesSkipDevice_" + self._s)(self._h, nb, rays, counts, _p(options), ids, hits, masks, flags,
+                                                                                  self._stream_handle(stream)))
+            return [int(c) for c in counts]
         self._check(getattr(self._L, "nrtTraverseBatchesDevice_" + self._s)(self._h, nb, rays, counts, _p(options), hits, masks, flags, stream))
         return [int(c) for c in counts]
 
-    def TraverseBatches(self, batches, options=None):
+    def TraverseBatches(self, batches, options=None, skip_prim_ids=None):
         """nrtTraverseBatches: several independent HOST batches — a list of ray arrays or (rays, "occlusion") pairs — uploaded
         together, walked by ONE persistent launch, downloaded together.  Returns a list of (hits, mask) per closest-hit batch
-        and (None, mask) per occlusion batch: exactly what TraverseBatch / OccludedBatch return for each of them."""
+        and (None, mask) per occlusion batch: exactly what TraverseBatch / OccludedBatch return for each of them.
+        `skip_prim_ids`: a list with one entry per batch, an array of one uint32 per ray or None (that batch uses options.skip_prim_id)."""
         RAY, HIT = ray_dtype(self.real), hit_dtype(self.real)
         nb = len(batches)
         rays = (ctypes.c_void_p * nb)()
@@ -521,19 +555,36 @@ class BVHAccel:
             masks[k] = m.ctypes.data if r.shape[0] else None
         if options is not None:
             options = np.asarray(options, dtype=TRACE_OPTIONS).reshape(1)
+        if skip_prim_ids is not None:
+            assert len(skip_prim_ids) == nb, "skip_prim_ids: one entry per batch"
+            ids = (ctypes.c_void_p * nb)()
+            for k, a in enumerate(skip_prim_ids):
+                if a is None or not counts[k]:
+                    ids[k] = None
+                    continue
+                a = self._host_skip_ids(a, counts[k])
+                keep.append(a)
+                ids[k] = a.ctypes.data
+            self._check(getattr(self._L, "nrtTraverseBatchesSkip_" + self._s)(self._h, nb, rays, counts, _p(options), ids, hits, masks, flags))
+            return out
         self._check(getattr(self._L, "nrtTraverseBatches_" + self._s)(self._h, nb, rays, counts, _p(options), hits, masks, flags))
         return out
 
-    def OccludedBatch(self, rays, options=None):
-        """Opt-in extension: only the hit flags of TraverseBatch(), each ray stopping at the first primitive it accepts."""
+    def OccludedBatch(self, rays, options=None, skip_prim_ids=None):
+        """Opt-in extension: only the hit flags of TraverseBatch(), each ray stopping at the first primitive it accepts.
+        `skip_prim_ids`: as for TraverseBatch (nrtOccludedBatchSkip)."""
         rays = np.ascontiguousarray(rays, dtype=ray_dtype(self.real))
         mask = np.zeros((rays.shape[0],), dtype=np.uint8)
         if options is not None:
             options = np.asarray(options, dtype=TRACE_OPTIONS).reshape(1)
+        if skip_prim_ids is not None:
+            ids = self._host_skip_ids(skip_prim_ids, rays.shape[0])
+            self._check(getattr(self._L, "nrtOccludedBatchSkip_" + self._s)(self._h, _p(rays), rays.shape[0], _p(options), _p(ids), _p(mask)))
+            return mask
         self._check(getattr(self._L, "nrtOccludedBatch_" + self._s)(self._h, _p(rays), rays.shape[0], _p(options), _p(mask)))
         return mask
 
-    def OccludedBatchDevice(self, d_rays, d_mask, options=None, stream=None):
+    def OccludedBatchDevice(self, d_rays, d_mask, options=None, stream=None, skip_prim_ids=None):
         import torch
 
         n = d_rays.numel() * d_rays.element_size() // ray_dtype(self.real).itemsize
@@ -542,6 +593,11 @@ class BVHAccel:
             stream = torch.cuda.current_stream(self.device).cuda_stream
         if options is not None:
             options = np.asarray(options, dtype=TRACE_OPTIONS).reshape(1)
+        if skip_prim_ids is not None:
+            self._check(getattr(self._L, "nrtOccludedBatchSkipDevice_" + self._s)(self._h, d_rays.data_ptr(), n, _p(options),
+                                                                                self._device_skip_ids(skip_prim_ids, n), d_mask.data_ptr(),
+                                                                                self._stream_handle(stream)))
+            return n
         self._check(getattr(self._L, "nrtOccludedBatchDevice_" + self._s)(self._h, d_rays.data_ptr(), n, _p(options), d_mask.data_ptr(), stream))
         return n
 

@@ -25,6 +25,9 @@ SYMBOLS = [
     "nrtSetTree_f32", "nrtSetTree_f64",
     "nrtTraverseBatch_f32", "nrtTraverseBatch_f64",
     "nrtTraverseBatchDevice_f32", "nrtTraverseBatchDevice_f64", "nrtTraverseBatchesDevice_f32", "nrtTraverseBatchesDevice_f64", "nrtTraverseBatches_f32", "nrtTraverseBatches_f64",
+    "nrtTraverseBatchSkip_f32", "nrtTraverseBatchSkip_f64", "nrtTraverseBatchSkipDevice_f32", "nrtTraverseBatchSkipDevice_f64",
+    "nrtOccludedBatchSkip_f32", "nrtOccludedBatchSkip_f64", "nrtOccludedBatchSkipDevice_f32", "nrtOccludedBatchSkipDevice_f64",
+    "nrtTraverseBatchesSkipDevice_f32", "nrtTraverseBatchesSkipDevice_f64", "nrtTraverseBatchesSkip_f32", "nrtTraverseBatchesSkip_f64",
     "nrtTraverseBatchMulti_f32", "nrtTraverseBatchMulti_f64", "nrtDeviceCount",
     "nrtTraverseCountDevice_f32", "nrtTraverseCountDevice_f64",
     "nrtOccludedBatch_f32", "nrtOccludedBatch_f64", "nrtOccludedBatchDevice_f32", "nrtOccludedBatchDevice_f64",
@@ -113,6 +116,25 @@ def lib():
         f.restype = i32
         f = getattr(L, "nrtTraverseBatches_" + s)
         f.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp]
+        f.restype = i32
+        # per-ray skip ids: the rows above with the id array behind the options
+        f = getattr(L, "nrtTraverseBatchSkip_" + s)
+        f.argtypes = [vp, vp, u64, vp, vp, vp, vp]
+        f.restype = i32
+        f = getattr(L, "nrtTraverseBatchSkipDevice_" + s)
+        f.argtypes = [vp, vp, u64, vp, vp, vp, vp, vp]
+        f.restype = i32
+        f = getattr(L, "nrtOccludedBatchSkip_" + s)
+        f.argtypes = [vp, vp, u64, vp, vp, vp]
+        f.restype = i32
+        f = getattr(L, "nrtOccludedBatchSkipDevice_" + s)
+        f.argtypes = [vp, vp, u64, vp, vp, vp, vp]
+        f.restype = i32
+        f = getattr(L, "nrtTraverseBatchesSkipDevice_" + s)
+        f.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp]
+        f.restype = i32
+        f = getattr(L, "nrtTraverseBatchesSkip_" + s)
+        f.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, vp]
         f.restype = i32
         f = getattr(L, "nrtTraverseCountDevice_" + s)
         f.argtypes = [vp, vp, u64, vp, ctypes.POINTER(TraceCounters)]

@@ -107,6 +107,7 @@ struct nrt_ctx {
   std::mutex host_mutex;   // the host-buffer traversal calls share one set of staging buffers: one at a time
   unsigned long long *d_counters = nullptr;  // 16 x u64 (counting pass / profiling instantiation only)
   DevBuf st_rays, st_hits, st_mask;
+  DevBuf st_skip; // per-ray skip ids of the staged host forms, beside st_rays
   // host entry point with page-locked caller buffers: upload / trace / download pipelined over three streams
   hipStream_t copy_in = nullptr, copy_out = nullptr;
   hipEvent_t ev_in[2] = {nullptr, nullptr}, ev_tr[2] = {nullptr, nullptr}, ev_out[2] = {nullptr, nullptr};
@@ -445,7 +446,7 @@ void nrtDestroy(nrt_ctx *c) {
   }
   free_tree(c);
   free_mesh(c);
-  DevBuf *bufs[] = {&c->b_verts, &c->b_radii, &c->b_faces, &c->st_rays, &c->st_hits, &c->st_mask, &c->b_nodes, &c->b_indices, &c->b_tris, &c->b_wide, &c->b_wide4, &c->b_wide_scratch, &c->b_build_ws, &c->b_wave_clock, &c->b_seg_verts, &c->b_seg_radii, &c->b_seg_prim, &c->b_seg_off, &c->b_refit_plan, &c->b_refit_stage, &c->b_max_index};
+  DevBuf *bufs[] = {&c->b_verts, &c->b_radii, &c->b_faces, &c->st_rays, &c->st_hits, &c->st_mask, &c->st_skip, &c->b_nodes, &c->b_indices, &c->b_tris, &c->b_wide, &c->b_wide4, &c->b_wide_scratch, &c->b_build_ws, &c->b_wave_clock, &c->b_seg_verts, &c->b_seg_radii, &c->b_seg_prim, &c->b_seg_off, &c->b_refit_plan, &c->b_refit_stage, &c->b_max_index};
   for (DevBuf *b : bufs)
     if (b->p) (void)hipFree(b->p);
   if (c->d_counters) (void)hipFree(c->d_counters);
@@ -995,6 +996,7 @@ struct TraverseBatches {
   typename Wire<T>::Hit *hits[kMaxBatches];
   uint8_t *mask[kMaxBatches];
   uint64_t count[kMaxBatches];
+  const uint32_t *skip[kMaxBatches]; // per-ray skip ids of batch k, or null: the call's skip_prim_id
   uint32_t anyhit; // bit k: batch k is an occlusion query
 };
 
@@ -1015,6 +1017,15 @@ struct TraverseLaunch {
   uint32_t max_hits = 0;
   uint32_t *hit_counts = nullptr;        // MultiHit (may be null): one word per ray
   const TraverseBatches<T> *batches = nullptr; // MultiBatch: rays and outputs per batch, n = all their rays (the context takes one launch: the caller checked)
+  const uint32_t *skip_ids = nullptr;    // Closest, Occlusion (nrt*BatchSkip*): one skip id per ray in the place of opt->skip_prim_id (MultiBatch: batches->skip[])
+  // the launch carries per-ray skip ids
+  bool has_skip_ids() const {
+    if (skip_ids) return true;
+    if (batches)
+      for (uint32_t k = 0; k < batches->nb; k++)
+        if (batches->skip[k]) return true;
+    return false;
+  }
 };
 
 // Every combination a launch cannot be is refused here (under launch_mutex: the tunables hold still).
@@ -1022,6 +1033,16 @@ template <typename T>
 static nrt_status validate_launch(nrt_ctx *c, const TraverseLaunch<T> &l) {
   const bool custom = c->prim_kind != kPrimTriangles; // spheres / cylinders
   if (c->prec != (int)sizeof(T)) return fail(c, NRT_ERR_PRECISION, "nrtTraverseBatch: precision mismatch");
+  if (l.has_skip_ids()) { // (include/nanort_hip.h, "per-ray skip ids")
+    if (custom)
+      return fail(c, NRT_ERR_INVALID, "per-ray skip ids: triangle contexts only (the sphere, cylinder and curve intersectors have no skip id)");
+    if (l.kind != Query::Closest && l.kind != Query::Occlusion && l.kind != Query::MultiBatch)
+      return fail(c, NRT_ERR_INVALID, "per-ray skip ids: closest-hit and occlusion queries only");
+    bool aligned = ((uintptr_t)l.skip_ids & 3u) == 0u;
+    if (l.batches)
+      for (uint32_t k = 0; k < l.batches->nb; k++) aligned = aligned && ((uintptr_t)l.batches->skip[k] & 3u) == 0u;
+    if (!aligned) return fail(c, NRT_ERR_INVALID, "per-ray skip ids: the device array is not 4-byte aligned");
+  }
   if ((c->prim_kind == kPrimCylinders) != (l.kind == Query::Cylinders))
     return fail(c, NRT_ERR_INVALID, "cylinder primitives are traced with nrtTraverseBatchCylinders*_f32 (28-byte records), "
                                     "every other primitive kind with nrtTraverseBatch*");
@@ -1084,6 +1105,7 @@ static WalkChoice choose_walk(const nrt_ctx *c, const TraverseLaunch<T> &l) {
   // two levels per step: closest-hit walks of nested fp32 triangle trees, outside the profiling / splitting variants
   w.plain_options = l.opt->prim_ids_range[0] == 0u && l.opt->prim_ids_range[1] >= c->num_faces && l.opt->skip_prim_id >= c->num_faces &&
                     !l.opt->cull_back_face;
+  if (l.has_skip_ids()) w.plain_options = false; // (any ray may carry an id that rejects a primitive: the id tests stay)
   // (the profiling instantiations of the two-level walk are built for the default trace options only: with options that can
   // reject a primitive a profiled launch walks one level per step, whose profiling variant honours them)
   const bool prof_needs_w2 = (w.dbg & (32u | 8192u)) && !w.plain_options && !custom;
@@ -1131,6 +1153,7 @@ static void fill_walk_args(const nrt_ctx *c, const TraverseLaunch<T> &l, const W
   a.range0 = l.opt->prim_ids_range[0];
   a.range1 = l.opt->prim_ids_range[1];
   a.skip_prim = l.opt->skip_prim_id;
+  a.skip_ids = l.skip_ids; // (MultiBatch: null, the table's skip_v instead)
   a.cull_back_face = l.opt->cull_back_face ? 1u : 0u;
   a.any_hit = l.kind == Query::Occlusion ? 1u : 0u;
   a.plain_options = w.plain_options ? 1u : 0u;
@@ -1181,7 +1204,7 @@ static void fill_launch_args(const TraverseLaunch<T> &l, const nrt_ctx::LaunchSl
   a.batch_anyhit = 0u;
   for (int k = 0; k < kMaxBatches; k++) {
     a.batch_end[k] = (uint32_t)l.n;
-    a.batches[k] = BatchPtrs{nullptr, nullptr, nullptr, 0};
+    a.batches[k] = BatchPtrs{nullptr, nullptr, nullptr, nullptr};
   }
   if (l.kind != Query::MultiBatch) return;
   const TraverseBatches<T> *mb = l.batches;
@@ -1192,6 +1215,7 @@ static void fill_launch_args(const TraverseLaunch<T> &l, const nrt_ctx::LaunchSl
     a.batches[k].rays_v = mb->rays[k] - start;
     a.batches[k].hits_v = mb->hits[k] ? mb->hits[k] - start : nullptr;
     a.batches[k].mask_v = mb->mask[k] ? mb->mask[k] - start : nullptr;
+    a.batches[k].skip_v = mb->skip[k] ? mb->skip[k] - start : nullptr;
     start += mb->count[k];
     a.batch_end[k] = (uint32_t)start;
   }
@@ -1286,9 +1310,10 @@ const uint64_t kStagedRays = 1ull << 26; // rays per launch of the staged host p
 
 // The staged host path of every ray query (the caller holds host_mutex), in pieces of `chunk` rays: upload into st_rays, the launch
 // `make(rays in the piece)` asks for, rec_bytes / flag_bytes per ray of st_hits / st_mask back into recs / flags (null: not copied).
+// `skip_ids` (may be null): one skip id per ray; every piece's slice of it is uploaded into st_skip beside the piece's rays.
 template <typename T, typename MakeLaunch>
 static nrt_status staged_host_loop(nrt_ctx *c, const typename Wire<T>::Ray *rays, uint64_t n, uint64_t chunk, size_t rec_bytes, size_t flag_bytes,
-                                   void *recs, void *flags, MakeLaunch make) {
+                                   void *recs, void *flags, MakeLaunch make, const uint32_t *skip_ids = nullptr) {
   const size_t ray_bytes = sizeof(typename Wire<T>::Ray);
   for (uint64_t off = 0; off < n; off += chunk) {
     const uint64_t m = std::min(chunk, n - off);
@@ -1296,6 +1321,10 @@ static nrt_status staged_host_loop(nrt_ctx *c, const typename Wire<T>::Ray *rays
     if ((st = ensure(c, c->st_rays, m * ray_bytes)) || (rec_bytes && (st = ensure(c, c->st_hits, m * rec_bytes))) || (st = ensure(c, c->st_mask, m * flag_bytes)))
       return st;
     HIPCHK(c, hipMemcpyAsync(c->st_rays.p, rays + off, m * ray_bytes, hipMemcpyHostToDevice, c->stream));
+    if (skip_ids) {
+      if ((st = ensure(c, c->st_skip, m * sizeof(uint32_t)))) return st;
+      HIPCHK(c, hipMemcpyAsync(c->st_skip.p, skip_ids + off, m * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    }
     if ((st = traverse_device<T>(c, make(m)))) return st;
     if (recs) HIPCHK(c, hipMemcpyAsync((char *)recs + off * rec_bytes, c->st_hits.p, m * rec_bytes, hipMemcpyDeviceToHost, c->stream));
     if (flags) HIPCHK(c, hipMemcpyAsync((char *)flags + off * flag_bytes, c->st_mask.p, m * flag_bytes, hipMemcpyDeviceToHost, c->stream));
@@ -1319,7 +1348,7 @@ static bool is_pinned_host(const void *p) {
 // so the call approaches the slower of the two copy directions instead of their sum plus the kernel.
 template <typename T>
 static nrt_status traverse_host(nrt_ctx *c, const typename Wire<T>::Ray *rays, uint64_t n,
-                                const nrt_trace_options *opt, typename Wire<T>::Hit *hits, uint8_t *mask) {
+                                const nrt_trace_options *opt, typename Wire<T>::Hit *hits, uint8_t *mask, const uint32_t *skip_ids = nullptr) {
   if (!c) return NRT_ERR_INVALID;
   if (n == 0) return NRT_OK;
   if (!rays || !hits) return fail(c, NRT_ERR_INVALID, "nrtTraverseBatch: NULL rays/hits");
@@ -1328,7 +1357,8 @@ static nrt_status traverse_host(nrt_ctx *c, const typename Wire<T>::Ray *rays, u
   std::lock_guard<std::mutex> host_lock(c->host_mutex);
   HIPCHK(c, hipSetDevice(c->device));
   const uint64_t kPiece = 1ull << 19; // rays per pipeline stage (19 MB up, 8 MB down in fp32)
-  if (n >= 2 * kPiece && c->host_pipeline && is_pinned_host(rays) && is_pinned_host(hits) && (!mask || is_pinned_host(mask))) {
+  if (n >= 2 * kPiece && c->host_pipeline && is_pinned_host(rays) && is_pinned_host(hits) && (!mask || is_pinned_host(mask)) &&
+      (!skip_ids || is_pinned_host(skip_ids))) {
     if (!c->copy_in) HIPCHK(c, hipStreamCreateWithFlags(&c->copy_in, hipStreamNonBlocking));
     if (!c->copy_out) HIPCHK(c, hipStreamCreateWithFlags(&c->copy_out, hipStreamNonBlocking));
     for (int k = 0; k < 2; k++)
@@ -1336,7 +1366,7 @@ static nrt_status traverse_host(nrt_ctx *c, const typename Wire<T>::Ray *rays, u
         if (!*e) HIPCHK(c, hipEventCreateWithFlags(e, hipEventDisableTiming));
     nrt_status st;
     if ((st = ensure(c, c->st_rays, 2 * kPiece * sizeof(Ray))) || (st = ensure(c, c->st_hits, 2 * kPiece * sizeof(Hit))) ||
-        (st = ensure(c, c->st_mask, 2 * kPiece)))
+        (st = ensure(c, c->st_mask, 2 * kPiece)) || (skip_ids && (st = ensure(c, c->st_skip, 2 * kPiece * sizeof(uint32_t)))))
       return st;
     uint64_t piece = 0;
     for (uint64_t off = 0; off < n; off += kPiece, piece++) {
@@ -1345,13 +1375,16 @@ static nrt_status traverse_host(nrt_ctx *c, const typename Wire<T>::Ray *rays, u
       Ray *d_r = (Ray *)c->st_rays.p + (size_t)b * kPiece;
       Hit *d_h = (Hit *)c->st_hits.p + (size_t)b * kPiece;
       uint8_t *d_m = (uint8_t *)c->st_mask.p + (size_t)b * kPiece;
+      uint32_t *d_s = skip_ids ? (uint32_t *)c->st_skip.p + (size_t)b * kPiece : nullptr; // (the piece's slice of the ids travels with its rays)
       // the ray slot is free once the trace that read it (two pieces ago) is done; the record slot once its download is
       if (piece >= 2) HIPCHK(c, hipStreamWaitEvent(c->copy_in, c->ev_tr[b], 0));
       HIPCHK(c, hipMemcpyAsync(d_r, rays + off, m * sizeof(Ray), hipMemcpyHostToDevice, c->copy_in));
+      if (d_s) HIPCHK(c, hipMemcpyAsync(d_s, skip_ids + off, m * sizeof(uint32_t), hipMemcpyHostToDevice, c->copy_in));
       HIPCHK(c, hipEventRecord(c->ev_in[b], c->copy_in));
       HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_in[b], 0));
       if (piece >= 2) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_out[b], 0));
-      st = traverse_device<T>(c, {.kind = Query::Closest, .rays = d_r, .n = m, .opt = opt, .stream = c->stream, .timed = true, .hits = d_h, .mask = d_m});
+      st = traverse_device<T>(c, {.kind = Query::Closest, .rays = d_r, .n = m, .opt = opt, .stream = c->stream, .timed = true, .hits = d_h, .mask = d_m,
+                                  .skip_ids = d_s});
       if (st) { // (copies into the caller's buffers may still be in flight: let them land before the call returns)
         (void)hipStreamSynchronize(c->copy_in);
         (void)hipStreamSynchronize(c->stream);
@@ -1370,8 +1403,8 @@ static nrt_status traverse_host(nrt_ctx *c, const typename Wire<T>::Ray *rays, u
   }
   return staged_host_loop<T>(c, rays, n, kStagedRays, sizeof(Hit), 1, hits, mask, [&](uint64_t m) -> TraverseLaunch<T> {
     return {.kind = Query::Closest, .rays = (const Ray *)c->st_rays.p, .n = m, .opt = opt, .stream = c->stream, .timed = true,
-            .hits = (Hit *)c->st_hits.p, .mask = (uint8_t *)c->st_mask.p};
-  });
+            .hits = (Hit *)c->st_hits.p, .mask = (uint8_t *)c->st_mask.p, .skip_ids = skip_ids ? (const uint32_t *)c->st_skip.p : nullptr};
+  }, skip_ids);
 }
 
 // One host batch spread over several contexts — one per GPU of the node, each holding the same tree (the build is
@@ -1493,7 +1526,7 @@ static nrt_status check_batches(nrt_ctx *c, const char *fn, uint32_t nb, const t
 template <typename T>
 static nrt_status traverse_batches_device(nrt_ctx *c, uint32_t nb, const typename Wire<T>::Ray *const *d_rays, const uint64_t *counts,
                                           const nrt_trace_options *opt, typename Wire<T>::Hit *const *d_hits,
-                                          uint8_t *const *d_masks, const uint32_t *flags, hipStream_t s) {
+                                          uint8_t *const *d_masks, const uint32_t *flags, hipStream_t s, const uint32_t *const *d_skip = nullptr) {
   if (!c) return NRT_ERR_INVALID;
   if (nb == 0) return NRT_OK;
   uint64_t total, total_closest;
@@ -1513,6 +1546,7 @@ static nrt_status traverse_batches_device(nrt_ctx *c, uint32_t nb, const typenam
         mb.hits[mb.nb] = occ ? nullptr : d_hits[k]; // (an occlusion query writes the flags only: its call may have no record table)
         mb.mask[mb.nb] = d_masks ? d_masks[k] : nullptr;
         mb.count[mb.nb] = counts[k];
+        mb.skip[mb.nb] = d_skip ? d_skip[k] : nullptr;
         if (occ) mb.anyhit |= 1u << mb.nb;
         n += counts[k];
         mb.nb++;
@@ -1528,7 +1562,8 @@ static nrt_status traverse_batches_device(nrt_ctx *c, uint32_t nb, const typenam
     } else {
       for (uint32_t j = 0; j < mb.nb; j++) {
         const Query kind = ((mb.anyhit >> j) & 1u) ? Query::Occlusion : Query::Closest;
-        st = traverse_device<T>(c, {.kind = kind, .rays = mb.rays[j], .n = mb.count[j], .opt = opt, .stream = s, .hits = mb.hits[j], .mask = mb.mask[j]});
+        st = traverse_device<T>(c, {.kind = kind, .rays = mb.rays[j], .n = mb.count[j], .opt = opt, .stream = s, .hits = mb.hits[j], .mask = mb.mask[j],
+                                    .skip_ids = mb.skip[j]});
         if (st) return st;
       }
     }
@@ -1542,7 +1577,7 @@ static nrt_status traverse_batches_device(nrt_ctx *c, uint32_t nb, const typenam
 template <typename T>
 static nrt_status traverse_batches_host(nrt_ctx *c, uint32_t nb, const typename Wire<T>::Ray *const *rays, const uint64_t *counts,
                                         const nrt_trace_options *opt, typename Wire<T>::Hit *const *hits, uint8_t *const *masks,
-                                        const uint32_t *flags) {
+                                        const uint32_t *flags, const uint32_t *const *skip_ids = nullptr) {
   typedef typename Wire<T>::Ray Ray;
   typedef typename Wire<T>::Hit Hit;
   if (!c) return NRT_ERR_INVALID;
@@ -1554,8 +1589,9 @@ static nrt_status traverse_batches_host(nrt_ctx *c, uint32_t nb, const typename 
   std::lock_guard<std::mutex> host_lock(c->host_mutex);
   HIPCHK(c, hipSetDevice(c->device));
   if ((st = ensure(c, c->st_rays, total * sizeof(Ray))) || (st = ensure(c, c->st_hits, std::max<uint64_t>(1, total_closest) * sizeof(Hit))) ||
-      (st = ensure(c, c->st_mask, total)))
+      (st = ensure(c, c->st_mask, total)) || (skip_ids && (st = ensure(c, c->st_skip, total * sizeof(uint32_t)))))
     return st;
+  std::vector<const uint32_t *> d_s(nb, nullptr); // (a batch's ids are staged at its rays' offset)
   std::vector<const Ray *> d_r(nb, nullptr);
   std::vector<Hit *> d_h(nb, nullptr);
   std::vector<uint8_t *> d_m(nb, nullptr);
@@ -1570,9 +1606,13 @@ static nrt_status traverse_batches_host(nrt_ctx *c, uint32_t nb, const typename 
     }
     d_m[k] = (uint8_t *)c->st_mask.p + off;
     HIPCHK(c, hipMemcpyAsync((void *)d_r[k], rays[k], counts[k] * sizeof(Ray), hipMemcpyHostToDevice, c->stream));
+    if (skip_ids && skip_ids[k]) {
+      d_s[k] = (const uint32_t *)c->st_skip.p + off;
+      HIPCHK(c, hipMemcpyAsync((void *)d_s[k], skip_ids[k], counts[k] * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    }
     off += counts[k];
   }
-  st = traverse_batches_device<T>(c, nb, d_r.data(), counts, opt, d_h.data(), d_m.data(), flags, c->stream);
+  st = traverse_batches_device<T>(c, nb, d_r.data(), counts, opt, d_h.data(), d_m.data(), flags, c->stream, skip_ids ? d_s.data() : nullptr);
   if (st) {
     (void)hipStreamSynchronize(c->stream);
     return st;
@@ -1588,7 +1628,8 @@ static nrt_status traverse_batches_host(nrt_ctx *c, uint32_t nb, const typename 
 }
 
 template <typename T>
-static nrt_status occluded_host(nrt_ctx *c, const typename Wire<T>::Ray *rays, uint64_t n, const nrt_trace_options *opt, uint8_t *mask) {
+static nrt_status occluded_host(nrt_ctx *c, const typename Wire<T>::Ray *rays, uint64_t n, const nrt_trace_options *opt, uint8_t *mask,
+                                const uint32_t *skip_ids = nullptr) {
   if (!c) return NRT_ERR_INVALID;
   if (n == 0) return NRT_OK;
   if (!rays || !mask) return fail(c, NRT_ERR_INVALID, "nrtOccludedBatch: NULL rays/mask");
@@ -1596,8 +1637,8 @@ static nrt_status occluded_host(nrt_ctx *c, const typename Wire<T>::Ray *rays, u
   HIPCHK(c, hipSetDevice(c->device));
   return staged_host_loop<T>(c, rays, n, kStagedRays, 0, 1, nullptr, mask, [&](uint64_t m) -> TraverseLaunch<T> {
     return {.kind = Query::Occlusion, .rays = (const typename Wire<T>::Ray *)c->st_rays.p, .n = m, .opt = opt, .stream = c->stream, .timed = true,
-            .mask = (uint8_t *)c->st_mask.p};
-  });
+            .mask = (uint8_t *)c->st_mask.p, .skip_ids = skip_ids ? (const uint32_t *)c->st_skip.p : nullptr};
+  }, skip_ids);
 }
 
 // ---------------------------------------------------------------------------
@@ -1644,6 +1685,22 @@ static nrt_status multihit_host(nrt_ctx *c, const typename Wire<T>::Ray *rays, u
   });
 }
 
+// Per-ray skip ids (include/nanort_hip.h): the entry points above with one skip id per ray; a NULL array is the call above itself.
+template <typename T>
+static nrt_status traverse_skip_device(nrt_ctx *c, const typename Wire<T>::Ray *r, uint64_t n, const nrt_trace_options *o, const uint32_t *ids,
+                                       typename Wire<T>::Hit *h, uint8_t *m, void *s) {
+  if (!c) return NRT_ERR_INVALID;
+  if (n && !h) return fail(c, NRT_ERR_INVALID, "nrtTraverseBatchSkipDevice: NULL hits");
+  return traverse_device<T>(c, {.kind = Query::Closest, .rays = r, .n = n, .opt = o, .stream = (hipStream_t)s, .timed = true, .hits = h, .mask = m,
+                                .skip_ids = ids});
+}
+template <typename T>
+static nrt_status occluded_skip_device(nrt_ctx *c, const typename Wire<T>::Ray *r, uint64_t n, const nrt_trace_options *o, const uint32_t *ids,
+                                       uint8_t *m, void *s) {
+  if (!c) return NRT_ERR_INVALID;
+  if (n && !m) return fail(c, NRT_ERR_INVALID, "nrtOccludedBatchSkipDevice: NULL mask");
+  return traverse_device<T>(c, {.kind = Query::Occlusion, .rays = r, .n = n, .opt = o, .stream = (hipStream_t)s, .timed = true, .mask = m, .skip_ids = ids});
+}
 extern "C" {
 
 nrt_status nrtMultiHitTraverseBatch_f32(nrt_ctx *c, const nrt_ray_f32 *r, uint64_t n, uint32_t k, const nrt_trace_options *o, nrt_hit_f32 *h,
@@ -1805,6 +1862,54 @@ nrt_status nrtTraverseBatchDevice_f64(nrt_ctx *c, const nrt_ray_f64 *r, uint64_t
   if (!c) return NRT_ERR_INVALID;
   if (n && !h) return fail(c, NRT_ERR_INVALID, "nrtTraverseBatchDevice: NULL hits");
   return traverse_device<double>(c, {.kind = Query::Closest, .rays = r, .n = n, .opt = o, .stream = (hipStream_t)s, .timed = true, .hits = h, .mask = m});
+}
+
+// Per-ray skip ids (include/nanort_hip.h): the entry points above with one skip id per ray; a NULL array is the call above itself.
+nrt_status nrtTraverseBatchSkip_f32(nrt_ctx *c, const nrt_ray_f32 *r, uint64_t n, const nrt_trace_options *o, const uint32_t *ids, nrt_hit_f32 *h,
+                                    uint8_t *m) {
+  return traverse_host<float>(c, r, n, o, h, m, ids);
+}
+nrt_status nrtTraverseBatchSkip_f64(nrt_ctx *c, const nrt_ray_f64 *r, uint64_t n, const nrt_trace_options *o, const uint32_t *ids, nrt_hit_f64 *h,
+                                    uint8_t *m) {
+  return traverse_host<double>(c, r, n, o, h, m, ids);
+}
+nrt_status nrtTraverseBatchSkipDevice_f32(nrt_ctx *c, const nrt_ray_f32 *r, uint64_t n, const nrt_trace_options *o, const uint32_t *ids,
+                                          nrt_hit_f32 *h, uint8_t *m, void *s) {
+  return traverse_skip_device<float>(c, r, n, o, ids, h, m, s);
+}
+nrt_status nrtTraverseBatchSkipDevice_f64(nrt_ctx *c, const nrt_ray_f64 *r, uint64_t n, const nrt_trace_options *o, const uint32_t *ids,
+                                          nrt_hit_f64 *h, uint8_t *m, void *s) {
+  return traverse_skip_device<double>(c, r, n, o, ids, h, m, s);
+}
+nrt_status nrtOccludedBatchSkip_f32(nrt_ctx *c, const nrt_ray_f32 *r, uint64_t n, const nrt_trace_options *o, const uint32_t *ids, uint8_t *m) {
+  return occluded_host<float>(c, r, n, o, m, ids);
+}
+nrt_status nrtOccludedBatchSkip_f64(nrt_ctx *c, const nrt_ray_f64 *r, uint64_t n, const nrt_trace_options *o, const uint32_t *ids, uint8_t *m) {
+  return occluded_host<double>(c, r, n, o, m, ids);
+}
+nrt_status nrtOccludedBatchSkipDevice_f32(nrt_ctx *c, const nrt_ray_f32 *r, uint64_t n, const nrt_trace_options *o, const uint32_t *ids, uint8_t *m,
+                                          void *s) {
+  return occluded_skip_device<float>(c, r, n, o, ids, m, s);
+}
+nrt_status nrtOccludedBatchSkipDevice_f64(nrt_ctx *c, const nrt_ray_f64 *r, uint64_t n, const nrt_trace_options *o, const uint32_t *ids, uint8_t *m,
+                                          void *s) {
+  return occluded_skip_device<double>(c, r, n, o, ids, m, s);
+}
+nrt_status nrtTraverseBatchesSkipDevice_f32(nrt_ctx *c, uint32_t nb, const nrt_ray_f32 *const *r, const uint64_t *n, const nrt_trace_options *o,
+                                            const uint32_t *const *ids, nrt_hit_f32 *const *h, uint8_t *const *m, const uint32_t *fl, void *s) {
+  return traverse_batches_device<float>(c, nb, r, n, o, h, m, fl, (hipStream_t)s, ids);
+}
+nrt_status nrtTraverseBatchesSkipDevice_f64(nrt_ctx *c, uint32_t nb, const nrt_ray_f64 *const *r, const uint64_t *n, const nrt_trace_options *o,
+                                            const uint32_t *const *ids, nrt_hit_f64 *const *h, uint8_t *const *m, const uint32_t *fl, void *s) {
+  return traverse_batches_device<double>(c, nb, r, n, o, h, m, fl, (hipStream_t)s, ids);
+}
+nrt_status nrtTraverseBatchesSkip_f32(nrt_ctx *c, uint32_t nb, const nrt_ray_f32 *const *r, const uint64_t *n, const nrt_trace_options *o,
+                                      const uint32_t *const *ids, nrt_hit_f32 *const *h, uint8_t *const *m, const uint32_t *fl) {
+  return traverse_batches_host<float>(c, nb, r, n, o, h, m, fl, ids);
+}
+nrt_status nrtTraverseBatchesSkip_f64(nrt_ctx *c, uint32_t nb, const nrt_ray_f64 *const *r, const uint64_t *n, const nrt_trace_options *o,
+                                      const uint32_t *const *ids, nrt_hit_f64 *const *h, uint8_t *const *m, const uint32_t *fl) {
+  return traverse_batches_host<double>(c, nb, r, n, o, h, m, fl, ids);
 }
 
 nrt_status nrtTraverseBatchMulti_f32(nrt_ctx *const *ctxs, uint32_t num_ctx, const nrt_ray_f32 *r, uint64_t n, uint64_t row_len,

@@ -384,8 +384,9 @@ struct BatchPtrs {
   const void *rays_v;
   void *hits_v;
   uint8_t *mask_v; // may be null
-  uint64_t pad;
+  const uint32_t *skip_v; // the batch's per-ray skip ids (TraverseArgs::skip_ids), or null: the launch's skip_prim
 };
+static_assert(sizeof(BatchPtrs) == 32, "BatchPtrs");
 
 template <typename T>
 struct TraverseArgs {
@@ -451,6 +452,11 @@ struct TraverseArgs {
   // (the curve kind's fields come last: the offsets of everything the other kinds' instantiations read stay where they were)
   const LeafCurve *curves;           // primitive kind 3 (leaf order)
   uint32_t curve_subdiv;             // primitive kind 3: line segments per curve (the intersector's num_subdivisions, 1..64)
+  // Per-ray skip ids (nrt*BatchSkip*; triangle walks, never PLAIN): ray i is traced with skip_ids[i] in the place of skip_prim.  Null
+  // for every other launch.  The walks do not carry the id: a lane re-reads it at every leaf it enters, by the ray index it holds for
+  // its output, so a refilled lane, an item tested on another lane and a quad of the tail all see the id of the ray they work on.
+  // (Multi-batch launches: BatchPtrs::skip_v per batch instead, addressed by the virtual index like its neighbours.)
+  const uint32_t *skip_ids;
 };
 
 } // namespace nrt

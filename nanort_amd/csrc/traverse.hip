@@ -149,11 +149,14 @@ __global__ __launch_bounds__(kTraverseBlock) void k_traverse(const TraverseArgs<
     // ---- phase 2: lanes holding a leaf test its triangles together ------------------
     if (__ballot(state == LANE_LEAF) != 0ull) {
       const uint32_t cnt = state == LANE_LEAF ? leaf_cnt : 0u;
+      uint32_t skip = a.skip_prim;
+      if constexpr (!COUNT) // (the counting pass takes no ids: api.hip)
+        if (a.skip_ids != nullptr && state == LANE_LEAF) skip = a.skip_ids[rid]; // per-ray skip ids (common.h): the id of the ray the lane holds NOW
       for (uint32_t i = 0; __ballot(i < cnt) != 0ull; i++) {
         if (i < cnt) {
           const LeafTri<T> tri = a.tris[leaf_first + i];
           if (COUNT) c_tris++;
-          tri_test<T>(L, tri, true, a.range0, a.range1, a.skip_prim, cull);
+          tri_test<T>(L, tri, true, a.range0, a.range1, skip, cull);
         }
       }
       if (state == LANE_LEAF) NRT_POP_OR_FINISH();
@@ -619,6 +622,8 @@ do {                                                                            
 // The same tests on the same operands (tri_solve, as tri_test), accepted in the same sequence: the lane state after
 // the leaf is bit for bit what the owner's own loop leaves (tests/test_gpu_leaf_items.py, tests/test_gpu_scene.py).  Returns false
 // — nothing done — when the records do not fit one trip: the caller's owner loop then runs.  Wave-uniform control flow only.
+// `skip_prim` is the calling lane's OWN skip id (per-ray skip ids, common.h): an item is tested against its owner's, fetched like the
+// owner's ray constants.
 // (SLOT: how an item names its record in LDS — a 32-bit index into `base` (k_traverse_wide: one array per launch; 4 bytes per item
 // keep the block's LDS below a sixth of the CU's) or the record's address (k_scene_walk: every owner's mesh has its own array))
 template <bool PLAIN, typename SLOT>
@@ -655,8 +660,10 @@ __device__ __forceinline__ bool leaf_items_one_trip(Lane<float> &L, uint32_t cnt
               sz = __int_as_float(__builtin_amdgcn_ds_bpermute(oa_, __float_as_int(L.Sz)));
   const uint32_t pk = (uint32_t)__builtin_amdgcn_ds_bpermute(oa_, (int)L.pk);
   const int ikx = (int)((pk >> 3) & 3u), iky = (int)((pk >> 5) & 3u), ikz = (int)((pk >> 7) & 3u);
+  uint32_t skip_o = 0u;
+  if constexpr (!PLAIN) skip_o = (uint32_t)__builtin_amdgcn_ds_bpermute(oa_, (int)skip_prim);
   const uint32_t prim_i = tri.prim_id;
-  const TriSolve<T> ts_ = tri_solve<T, PLAIN>(tri, item_, o0, o1, o2, sx, sy, sz, ikx, iky, ikz, range0, range1, skip_prim, cull); // (on the owner's constants)
+  const TriSolve<T> ts_ = tri_solve<T, PLAIN>(tri, item_, o0, o1, o2, sx, sy, sz, ikx, iky, ikz, range0, range1, skip_o, cull); // (on the owner's constants)
   const bool ok = ts_.ok;
   const T tt_i = ts_.tt, uu_i = ts_.uu, vv_i = ts_.vv;
   // ... and back to the owners, record by record
@@ -793,7 +800,20 @@ __global__ __launch_bounds__(kTraverseBlock, (WIDTH == 4 && sizeof(T) == 4) ? NR
     if (mp_) mp_[rid] = hit_ ? (KIND == kPrimCylinders ? (uint8_t)(1u | (L.cap << 1)) : (uint8_t)1) : (uint8_t)0; \
   } while (0)
 
+  // The skip id of the ray a lane holds (`live_`: it holds one and waits at a leaf), into skip_: the launch's, or with per-ray skip
+  // ids (common.h TraverseArgs::skip_ids; a multi-batch launch: its batch's array, or none) the ray's own, re-read at every leaf by the
+  // index the lane keeps for its output — so whoever works on a ray (its lane after a refill, a quad of the tail) tests against ITS id.
+#define NRT_RAY_SKIP(skip_, live_)                                                                     \
+  uint32_t skip_ = a.skip_prim;                                                                        \
+  if constexpr (!PLAIN && KIND == kPrimTriangles) {                                                    \
+    const uint32_t *ids_ = a.skip_ids;                                                                 \
+    if (multi) ids_ = s_tbl[batch_of<T>(a, rid)].skip_v;                                               \
+    if ((live_) && ids_ != nullptr) skip_ = ids_[rid];                                                 \
+  }                                                                                                    \
+  (void)skip_
+
   // One primitive record (slot `slot_` of the leaf-ordered arrays) against a lane's ray; `act_` false -> no effect.
+  // (`skip` is the leaf phase's: NRT_RAY_SKIP)
 #define NRT_TEST_PRIM(slot_, act_)                                                                     \
   do {                                                                                                 \
     if (KIND == kPrimSpheres) {                                                                        \
@@ -810,7 +830,7 @@ __global__ __launch_bounds__(kTraverseBlock, (WIDTH == 4 && sizeof(T) == 4) ? NR
       if (PLAIN)                                                                                       \
         tri_test<T, true>(L, tri_, (act_), 0u, 0u, 0u, false);                                         \
       else                                                                                             \
-        tri_test<T>(L, tri_, (act_), a.range0, a.range1, a.skip_prim, cull);                           \
+        tri_test<T>(L, tri_, (act_), a.range0, a.range1, skip, cull);                                  \
     }                                                                                                  \
   } while (0)
 
@@ -1001,6 +1021,7 @@ __global__ __launch_bounds__(kTraverseBlock, (WIDTH == 4 && sizeof(T) == 4) ? NR
       uint32_t cnt = 0, first = 0;
       if (state == W_LEAF) leaf_span(a.packed_leaves, a.nodes, cur, cnt, first);
       if (a.debug_flags & 1u) cnt = 0;
+      NRT_RAY_SKIP(skip, state == W_LEAF);
       if (STATS) {
         st_entries2++;
         st_idle2 += (unsigned)__builtin_popcountll(__ballot(state == W_IDLE));
@@ -1018,7 +1039,7 @@ __global__ __launch_bounds__(kTraverseBlock, (WIDTH == 4 && sizeof(T) == 4) ? NR
         // the owner's own loop leaves (tests/test_gpu_leaf_items.py).  More records than lanes: the owners' loop below.  Trees
         // whose leaves hold more than four records do not take this variant at all (api.hip).
         items_done_ = leaf_items_one_trip<PLAIN, uint32_t>(L, cnt, a.tris, first, lane, s_item_owner[tid / kWave], s_item_rec[tid / kWave], a.range0, a.range1,
-                                                 a.skip_prim, cull);
+                                                 skip, cull);
       }
       if (items_done_) {
         // (the waiting lanes' records were tested as items)
@@ -1045,7 +1066,7 @@ __global__ __launch_bounds__(kTraverseBlock, (WIDTH == 4 && sizeof(T) == 4) ? NR
             if (PLAIN)
               tri_test<T, true>(L, t_[j], i + j < cnt, 0u, 0u, 0u, false);
             else
-              tri_test<T>(L, t_[j], i + j < cnt, a.range0, a.range1, a.skip_prim, cull);
+              tri_test<T>(L, t_[j], i + j < cnt, a.range0, a.range1, skip, cull);
           }
         }
       } else if constexpr (!STATS && KIND == kPrimSpheres && NRT_SPHERE_UNROLL > 1) { // the same for the 20-byte sphere records
@@ -1171,11 +1192,12 @@ __global__ __launch_bounds__(kTraverseBlock, (WIDTH == 4 && sizeof(T) == 4) ? NR
           uint32_t cnt = 0, first = 0;
           if (state == W_LEAF) leaf_span(a.packed_leaves, a.nodes, cur, cnt, first);
           if (a.debug_flags & 1u) cnt = 0;
+          NRT_RAY_SKIP(skip, state == W_LEAF); // (the quad's ray's: rid moved with the ray)
           for (uint32_t i = 0; __ballot(i < cnt) != 0ull; i += 4u) {
             const bool act_ = i + j_ < cnt;
             const LeafTri<T> tri = a.tris[first + (act_ ? i + j_ : 0u)];
             const uint32_t prim_i = tri.prim_id;
-            const TriSolve<T> ts_ = tri_solve<T, PLAIN>(tri, act_, L.org0, L.org1, L.org2, L.Sx, L.Sy, L.Sz, L.kx(), L.ky(), L.kz(), a.range0, a.range1, a.skip_prim, cull);
+            const TriSolve<T> ts_ = tri_solve<T, PLAIN>(tri, act_, L.org0, L.org1, L.org2, L.Sx, L.Sy, L.Sz, L.kx(), L.ky(), L.kz(), a.range0, a.range1, skip, cull);
             const bool ok = ts_.ok;
             const T tt_i = ts_.tt, uu_i = ts_.uu, vv_i = ts_.vv;
             // ... accepted in record order, the same sequence in every lane of the quad
@@ -1215,6 +1237,7 @@ __global__ __launch_bounds__(kTraverseBlock, (WIDTH == 4 && sizeof(T) == 4) ? NR
   if (rid != kInvalid) NRT_WRITE_RESULT(); // results still held in registers
 #undef NRT_WRITE_RESULT
 #undef NRT_TEST_PRIM
+#undef NRT_RAY_SKIP
 #undef NRT_CLOCK_LIVE
 #undef NRT_TAIL_N
   done_end<T>(a, lane);
