@@ -748,7 +748,7 @@ NRT_API int nrtSceneLastPath(const nrt_scene *scene);
  *      it is committed again), and for more rays than the closest-hit call accepts (2^31 - 1); num_rays == 0 returns NRT_OK.
  *   6. Path reporting: nrtSceneLastRedone / nrtSceneLastPath describe an occlusion call as they describe a closest-hit call;
  *      "single_pass", "walk_min", "scan_max", "fuse_scan" and the phase thresholds select paths for it the same way and never
- *      change a flag.  The single-pass walk certifies a flag by a rule of its own (traverse.hip, above k_scene_walk): no
+ *      change a flag.  The single-pass walk certifies a flag by a rule of its own (scene_kernels.hip, above k_scene_walk): no
  *      traced hit at all is 0; a hit in an instance with provably fewer than 64 entered boxes ranking before it is 1; any other
  *      ray is re-done by the listing path, which applies the reference's loop literally.
  *   7. Back-off: the closest-hit back-off ("walk_backoff_pct") is neither consulted nor updated by occlusion calls — its cause,

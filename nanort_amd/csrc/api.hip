@@ -136,7 +136,7 @@ struct nrt_ctx {
   unsigned static_slice_groups = 2; // ... each of at least this many 64-ray groups
   unsigned max_blocks_per_cu = 0; // env NRT_BLOCKS_PER_CU caps the persistent grid
   int wide = 1, wide_stack = 10; // production path: WideNode kernel (env NRT_WIDE=0 selects the binary kernel)
-  // Two tree levels per step (Wide4Node records, traverse.hip NRT_STEP_NODE4): the production walk of fp32 triangle trees
+  // Two tree levels per step (Wide4Node records, walk_dev.h NRT_STEP_NODE4): the production walk of fp32 triangle trees
   // whose child boxes lie inside their parents'.  env NRT_WIDE4=0 goes back to one level per step.
   int wide4 = 1;
   int wide4_big_ok = 1; // ... also when the record array reaches 4 GiB (tunable wide4_big; 0: such trees walk one level per step, as until round 6)
@@ -145,7 +145,7 @@ struct nrt_ctx {
   // 1 (opt-in): by entry distance, +2...5 % — the closest t is the reference's except where a leaf box's entry distance rounds
   // above a hit inside it, and among primitives at exactly the same t another one may be named (contract-level parity)
   int order4 = 0;
-  int leaf_compact = 1; // traverse.hip "leaf items" (round 6): when the records of all the lanes waiting at a leaf fit one trip of the wave, they are tested one per lane with the owner's ray constants and accepted by the owner in record order — records bit-identical, C3 +2 %, C4 tile +2.8 %; 0: every owner tests its own records
+  int leaf_compact = 1; // walk_dev.h "leaf items" (leaf_items_one_trip, round 6): when the records of all the lanes waiting at a leaf fit one trip of the wave, they are tested one per lane with the owner's ray constants and accepted by the owner in record order — records bit-identical, C3 +2 %, C4 tile +2.8 %; 0: every owner tests its own records
   int dyn_head = 1; // batches too small for a static group per wave: every wave's first chunk is its own (traverse.hip claim_init; tunable dyn_head)
   int wide_scramble = 0; // probe (tunable wide_scramble): the private node records in a pseudo-random order instead of pre-order
   // resident blocks per CU of the variants launched so far, by what selects the kernel: [walk][primitive kind] at `lds_entries` (a context keeps one precision; size_grid)

@@ -1,5 +1,5 @@
 // nanort_amd/csrc/common.h — device-side PODs and launch-argument blocks shared
-// by the gfx950 kernels (traverse.hip, build.hip) and the C ABI (api.hip).
+// by the gfx950 kernels (traverse.hip, scene_kernels.hip, build.hip) and the C ABI (api.hip, scene.hip).
 //
 // The node / ray / hit records are the reference's wire formats
 // (include/nanort_hip.h; reference nanort.h:474-550, 996-1005).  Everything
@@ -172,7 +172,7 @@ struct alignas(16) WideNode {
 };
 // fp64: the same record component-major — mn[k][child], mx[k][child]: a 16-byte row per plane pair, so that the walk fetches
 // the near and far rows of each axis by the ray's direction sign (a per-ray byte offset, as for Wide4Node<float>:
-// traverse.hip slab_pair_presel) instead of fetching all twelve doubles and selecting six pairs.
+// walk_dev.h slab_pair_presel) instead of fetching all twelve doubles and selecting six pairs.
 template <>
 struct alignas(16) WideNode<double> {
   double mn[3][2]; // [component][child]
@@ -190,7 +190,7 @@ static_assert(sizeof(WideNode<double>) == 112, "WideNode<double>");
 // node, at the same dense index as its WideNode, so any branch can be entered through either array; a walk that
 // starts at record 0 and follows c[] only ever touches the records of the even-depth branches.
 // axis0 = split axis of the node, axis1 / axis2 = split axes of child data[0] / data[1] (0 when that child is a leaf).
-// Walking this array visits the same leaves in the same order as the binary loop (see NRT_STEP_NODE4, traverse.hip).
+// Walking this array visits the same leaves in the same order as the binary loop (see NRT_STEP_NODE4, walk_dev.h).
 template <typename T>
 struct alignas(16) Wide4Node {
   T bmin[3][4]; // [component][slot]
@@ -238,7 +238,27 @@ struct TreeViewF32 {
   uint64_t generation;           // counts the context's rebuilds: a view is stale once the context's generation has moved on
 };
 
-// ---- two-level (instanced) traversal: one kernel for a whole ray batch (traverse.hip k_scene_trace) -------------
+// ---- two-level (instanced) traversal: one kernel for a whole ray batch (scene_kernels.hip k_scene_trace) --------
+// Matrix::MultV — nanosg.h:232-240, over a matrix kept whole (W = 4) or as the twelve entries this reads (W = 3).  The order of the
+// sum is the reference's: part of the parity contract (no contraction).
+template <int W>
+__host__ __device__ __forceinline__ void mult_v(float dst[3], const float (&m)[4][W], const float v[3]) {
+  const float t0 = m[0][0] * v[0] + m[1][0] * v[1] + m[2][0] * v[2] + m[3][0];
+  const float t1 = m[0][1] * v[0] + m[1][1] * v[1] + m[2][1] * v[2] + m[3][1];
+  const float t2 = m[0][2] * v[0] + m[1][2] * v[1] + m[2][2] * v[2] + m[3][2];
+  dst[0] = t0;
+  dst[1] = t1;
+  dst[2] = t2;
+}
+// What Node::Update derives for an instance (nanosg.h:397-437): Commit's per-instance table, which the listing kernels read.
+struct NodeDev {
+  float xbmin[3], xbmax[3]; // world AABB
+  float inv_xform[4][4];    // world -> local (points)
+  float inv_xform33[4][4];  // world -> local (directions)
+  float xform[4][4];        // local -> world
+};
+constexpr int kMaxList = 64;  // kMaxIntersections, nanosg.h:782
+constexpr int kTopStack = 64; // per-ray stack of the listing kernels' top-level walk (a deeper top-level tree falls back to the scan)
 // Per instance, in HBM: where its tree lives and the three matrices nanosg's Node::Update derives (nanosg.h:397-437).
 struct SceneInst {
   const void *wide;           // WideNode<float>[]
@@ -312,7 +332,7 @@ struct SceneTraceArgs {
   uint32_t any_hit;           // launcher only: the occlusion instantiation (k_scene_trace<.., ANY = true>): flags only, `hits` is never touched
 };
 
-// The single-pass scene walk (traverse.hip k_scene_walk): the top-level tree and the instances' trees walked by the same lane on
+// The single-pass scene walk (scene_kernels.hip k_scene_walk): the top-level tree and the instances' trees walked by the same lane on
 // one stack, no per-ray list.  Rays it cannot certify (see the kernel) are appended to `redo` for the listing path.
 #ifndef NRT_SCENE_WALK_STACK
 #define NRT_SCENE_WALK_STACK 16

@@ -31,14 +31,22 @@ template <typename T>
 hipError_t launch_traverse_wide(const TraverseArgs<T> &args, unsigned grid, int lds_entries, int prim_kind, hipStream_t, const char **name_out);
 template <typename T>
 int traverse_wide_blocks_per_cu(int lds_entries, int prim_kind, bool wide4);
-hipError_t launch_scene_trace(const SceneTraceArgs &args, unsigned grid, hipStream_t s);
-int scene_trace_blocks_per_cu();
-hipError_t launch_scene_walk(const SceneWalkArgs &args, unsigned grid, hipStream_t s);
-int scene_walk_blocks_per_cu();
 // scratch: tile counts (ceil(n/1024) u32) followed by dense_of (n u32)
 template <typename T>
 hipError_t launch_make_wide(const typename Wire<T>::Node *nodes, uint32_t n, uint32_t packed, uint32_t *scratch, WideNode<T> *wide,
                             Wide4Node<T> *wide4, uint32_t scramble_mod, hipStream_t s);
+
+// ---- scene_kernels.hip: the kernels of the two-level path (which of them a call runs: scene.hip) -------------------------------
+hipError_t launch_scene_trace(const SceneTraceArgs &args, unsigned grid, hipStream_t s);
+int scene_trace_blocks_per_cu();
+hipError_t launch_scene_walk(const SceneWalkArgs &args, unsigned grid, hipStream_t s);
+int scene_walk_blocks_per_cu();
+// The listing step in the form the host chose: a scan of every world box (`nodes`, `num_nodes`), or a walk of the top-level tree
+// `top` through its reference-format nodes or its Wide4Node records, the latter with or without pruning beyond a full list.
+// One ray per thread, rays[subset ? subset[i] : i] into slot i of n; at most `cap` entries per ray.
+enum SceneListForm : int { kSceneListScan, kSceneListBvh, kSceneListW4, kSceneListW4Prune };
+hipError_t launch_scene_list(SceneListForm form, const TreeViewF32 &top, const nrt_ray_f32 *rays, uint32_t n, const NodeDev *nodes, uint32_t num_nodes,
+                             uint32_t cap, float *list_t, uint32_t *list_node, uint32_t *count, const uint32_t *subset, hipStream_t s);
 
 // ---- multihit.hip -----------------------------------------------------------------------------------------------------
 template <typename T>

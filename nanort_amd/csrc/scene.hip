@@ -1,23 +1,18 @@
-// nanort_amd/csrc/scene.hip — two-level (instanced) traversal on the GPU: SURVEY.md §8(f) row 3.
+// nanort_amd/csrc/scene.hip — the HOST side of two-level (instanced) traversal: SURVEY.md §8(f) row 3.  Commit, the choice of
+// path per call, the tunables and the C entry points; every kernel it launches is scene_kernels.hip's, behind kernels.h.
 //
 // Replaces nanosg::Scene<float, M>::Commit / Traverse (reference examples/nanosg/nanosg.h:700-870) and the
 // BVHAccel::ListNodeIntersections it rests on (reference nanort.h:2608-2692).  Two paths give the same records:
 //
-//   THE SINGLE-PASS WALK (scenes of kWalkMinNodes nodes or more): k_scene_walk (traverse.hip) walks the top-level tree and, on
+//   THE SINGLE-PASS WALK (scenes of kWalkMinNodes nodes or more): k_scene_walk walks the top-level tree and, on
 //   reaching an instance, the instance's own tree in the same lane on the same stack — no per-ray list; a per-ray certificate
 //   says when the record is provably the reference's, the other rays (few) are appended to a list and go through
 //   THE LISTING PATH (small scenes; the rays handed over; tunable single_pass = 0):
 //
-//   k_scene_list*     per ray: which node boxes does the ray enter, sorted by entry distance, at most 64 — a walk
-//                     over the TOP-LEVEL BVH of the instances' world boxes (built on the GPU by the ordinary builder
-//                     with min_leaf_primitives = 1, as nanosg.h:730-735 does on the host).  The set of listed nodes
-//                     does not depend on the shape of that tree (every ancestor box contains the leaf box and the slab
-//                     arithmetic is monotone); scenes of a handful of nodes skip the tree (k_scene_list: a scan);
-//   k_scene_trace     (traverse.hip) per ray: the reference's loop over that list — early cull, ray into the node's
-//                     space, the node's own tree walked in the same lane, world distance, strict-nearer update —
-//                     for the whole batch (or the subset handed over) in one launch: no per-node launches, no host round trips.
+//   k_scene_list* (per ray: the at most 64 nearest instances whose world boxes it enters, through the top-level BVH or, for a
+//   handful of nodes, a scan) + k_scene_trace (the reference's loop over that list), for the whole batch or the subset handed over.
 //
-// The per-node arithmetic (Matrix::Mult / Inverse / MultV, XformBoundingBox, the two slab tests) follows the
+// The per-node arithmetic of Commit (Matrix::Mult / Inverse / MultV, XformBoundingBox) follows the
 // reference operation for operation; this file is compiled with the same no-contraction / IEEE flags.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -38,265 +33,12 @@
 
 namespace {
 
-struct NodeDev { // per-instance table in HBM
-  float xbmin[3], xbmax[3]; // world AABB
-  float inv_xform[4][4];    // world -> local (points)
-  float inv_xform33[4][4];  // world -> local (directions)
-  float xform[4][4];        // local -> world
-};
+using nrt::kMaxList, nrt::kTopStack, nrt::mult_v, nrt::NodeDev;
 
-constexpr int kMaxList = 64; // kMaxIntersections, nanosg.h:782
-constexpr int kTopStack = 64; // per-ray stack of the top-level walk (a deeper top-level tree falls back to the scan)
 constexpr uint32_t kScanMaxNodes = 8; // scenes of at most this many nodes are listed by the scan
 constexpr unsigned kWalkBackoff = 15;   // listing-path calls after a batch of which the walk handed over more than a quarter
 constexpr uint32_t kWalkMinNodes = 64; // scenes of at least this many nodes are traced by the single-pass walk (100 - 1 000 instances: 5-8 % faster than the
                                       // listing path, 10 000: 1.7x, 100 000: 9x; the 5-node fixture: 6-20 % slower — profiles/r04n_scene_walk.txt, r04t_*)
-
-// Matrix::MultV — nanosg.h:232-240
-__host__ __device__ inline void mult_v(float dst[3], const float m[4][4], const float v[3]) {
-  const float t0 = m[0][0] * v[0] + m[1][0] * v[1] + m[2][0] * v[2] + m[3][0];
-  const float t1 = m[0][1] * v[0] + m[1][1] * v[1] + m[2][1] * v[2] + m[3][1];
-  const float t2 = m[0][2] * v[0] + m[1][2] * v[1] + m[2][2] * v[2] + m[3][2];
-  dst[0] = t0;
-  dst[1] = t1;
-  dst[2] = t2;
-}
-
-// Does the ray enter node box `nd`, and over which interval?  nrt::scene_node_interval (common.h): the BVH leaf's robust test, then
-// NodeBBoxIntersector::Intersect.
-__device__ inline bool node_interval_box(const nrt_ray_f32 &r, const float xbmin[3], const float xbmax[3], float &t_min_out) {
-  return nrt::scene_node_interval(r, xbmin, xbmax, t_min_out);
-}
-__device__ inline bool node_interval(const nrt_ray_f32 &r, const NodeDev &nd, float &t_min_out) {
-  return nrt::scene_node_interval(r, nd.xbmin, nd.xbmax, t_min_out);
-}
-
-// A ray's candidate list while it is being collected: UNSORTED, at most `cap` entries — the cap nearest by (entry distance,
-// node id), which is what BVHAccel::ListNodeIntersections keeps (nanort.h:2608-2692: a priority queue of kMaxIntersections).
-// Adding a candidate is one store; only a ray that enters more than `cap` boxes pays for finding the farthest entry to
-// replace.  k_scene_trace picks the candidates in (distance, id) order as it needs them (round 2 kept the list sorted by
-// insertion in global memory: most of the listing kernel's time).
-struct ListTail {
-  uint32_t cnt = 0;
-  bool far_known = false; // far_* describe the farthest entry of a full list
-  float far_t = 0.0f;
-  uint32_t far_id = 0, far_pos = 0;
-};
-__device__ inline void list_farthest(ListTail &st, uint32_t cap, const float *list_t, const uint32_t *list_node, uint32_t n, uint32_t i) {
-  st.far_t = list_t[i];
-  st.far_id = list_node[i];
-  st.far_pos = 0;
-  for (uint32_t q = 1; q < cap; q++) {
-    const float qt = list_t[(size_t)q * n + i];
-    const uint32_t qk = list_node[(size_t)q * n + i];
-    if (qt > st.far_t || (qt == st.far_t && qk > st.far_id)) {
-      st.far_t = qt;
-      st.far_id = qk;
-      st.far_pos = q;
-    }
-  }
-  st.far_known = true;
-}
-__device__ inline void list_add(ListTail &st, float t, uint32_t k, uint32_t cap, float *__restrict__ list_t,
-                                uint32_t *__restrict__ list_node, uint32_t n, uint32_t i) {
-  if (st.cnt < cap) {
-    list_t[(size_t)st.cnt * n + i] = t;
-    list_node[(size_t)st.cnt * n + i] = k;
-    st.cnt++;
-    return;
-  }
-  if (!st.far_known) list_farthest(st, cap, list_t, list_node, n, i);
-  if (t < st.far_t || (t == st.far_t && k < st.far_id)) { // nearer than the farthest kept: takes its place
-    list_t[(size_t)st.far_pos * n + i] = t;
-    list_node[(size_t)st.far_pos * n + i] = k;
-    st.far_known = false;
-  }
-}
-
-// list_t / list_node: [kMaxList or num_nodes][n] (entry-major, so lane-consecutive accesses coalesce)
-__global__ __launch_bounds__(256) void k_scene_list(const nrt_ray_f32 *__restrict__ rays, uint32_t n,
-                                                    const NodeDev *__restrict__ nodes, uint32_t num_nodes, uint32_t cap,
-                                                    float *__restrict__ list_t, uint32_t *__restrict__ list_node,
-                                                    uint32_t *__restrict__ count, const uint32_t *__restrict__ subset) {
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  if (i >= n) return;
-  const nrt_ray_f32 r = rays[subset ? subset[i] : i]; // (a subset launch lists rays[subset[i]] into slot i of n)
-  ListTail st;
-  for (uint32_t k = 0; k < num_nodes; k++) {
-    float t;
-    if (!node_interval(r, nodes[k], t)) continue;
-    list_add(st, t, k, cap, list_t, list_node, n, i);
-  }
-  count[i] = st.cnt;
-}
-
-// The same listing through the top-level BVH: reference-format nodes over the instances' world boxes, leaves name the
-// instances through `top_indices`.  Inner boxes are tested as ListNodeIntersections tests them (IntersectRayAABB with
-// hit_t == ray.max_t throughout, nanort.h:2651), leaves with node_interval; entries are kept sorted by (entry distance,
-// node id) — the order the scan above produces — whatever order the walk finds them in.
-__device__ inline bool top_box_hit(const nrt_ray_f32 &r, const float inv[3], const int sign[3], const float bmin[3], const float bmax[3]) {
-  float tmin = r.min_t, tmax = r.max_t;
-#pragma unroll
-  for (int k = 0; k < 3; k++) {
-    const float lo = sign[k] ? bmax[k] : bmin[k], hi = sign[k] ? bmin[k] : bmax[k];
-    const float t0 = (lo - r.org[k]) * inv[k];
-    const float t1 = (hi - r.org[k]) * inv[k] * 1.00000024f;
-    tmin = (t0 > tmin) ? t0 : tmin;
-    tmax = (t1 < tmax) ? t1 : tmax;
-  }
-  return tmin <= tmax;
-}
-
-__global__ __launch_bounds__(256) void k_scene_list_bvh(const nrt_ray_f32 *__restrict__ rays, uint32_t n,
-                                                        const nrt_node_f32 *__restrict__ top_nodes,
-                                                        const uint32_t *__restrict__ top_indices,
-                                                        const NodeDev *__restrict__ nodes, uint32_t cap,
-                                                        float *__restrict__ list_t, uint32_t *__restrict__ list_node,
-                                                        uint32_t *__restrict__ count, const uint32_t *__restrict__ subset) {
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  if (i >= n) return;
-  const nrt_ray_f32 r = rays[subset ? subset[i] : i];
-  float inv[3];
-  int sign[3];
-#pragma unroll
-  for (int k = 0; k < 3; k++) {
-    const float d = r.dir[k];
-    sign[k] = d < 0.0f ? 1 : 0;
-    inv[k] = (__builtin_fabsf(d) < 1.1920928955078125e-07f) ? __builtin_huge_valf() * (sign[k] ? -1.0f : 1.0f) : 1.0f / d;
-  }
-  uint32_t stack[kTopStack];
-  int sp = 0;
-  stack[0] = 0u;
-  ListTail st;
-  while (sp >= 0) {
-    const nrt_node_f32 nd = top_nodes[stack[sp]];
-    sp--;
-    if (!top_box_hit(r, inv, sign, nd.bmin, nd.bmax)) continue;
-    if (nd.flag == 0) {
-      const int near = sign[nd.axis];
-      stack[++sp] = nd.data[1 - near];
-      stack[++sp] = nd.data[near];
-      continue;
-    }
-    for (uint32_t q = 0; q < nd.data[0]; q++) {
-      const uint32_t k = top_indices[nd.data[1] + q];
-      float t;
-      if (!node_interval(r, nodes[k], t)) continue;
-      list_add(st, t, k, cap, list_t, list_node, n, i);
-    }
-  }
-  count[i] = st.cnt;
-}
-
-// The same listing through the top-level tree's Wide4Node records (two tree levels per 128-byte fetch: a third of the
-// dependent round trips of the walk above).  Which instances a ray lists does not depend on the walk: an instance is listed iff
-// node_interval passes on its world box, and the tree only prunes — a subtree is skipped when the ray misses its box by the
-// same IntersectRayAABB arithmetic, and a box that contains an entered box is entered (the slab arithmetic is monotone), so
-// testing the four grandchild boxes instead of child-then-grandchild prunes the same subtrees.  A leaf of one instance needs
-// no fetch at all: its slot's box IS the instance's world box (the builder's box of the zero-radius cylinder xbmin -> xbmax).
-// PRUNE: keep entry distances on the stack, walk front to back and skip what lies beyond a full list (scenes of many
-// instances, where rays enter more boxes than the list holds; on smaller scenes the bookkeeping costs 5-10 % and buys nothing).
-template <bool PRUNE>
-__global__ __launch_bounds__(256) void k_scene_list_w4(const nrt_ray_f32 *__restrict__ rays, uint32_t n,
-                                                       const nrt::Wide4Node<float> *__restrict__ wide4,
-                                                       const nrt_node_f32 *__restrict__ top_nodes, uint32_t packed_leaves,
-                                                       const uint32_t *__restrict__ top_indices,
-                                                       const NodeDev *__restrict__ nodes, uint32_t cap,
-                                                       float *__restrict__ list_t, uint32_t *__restrict__ list_node,
-                                                       uint32_t *__restrict__ count, const uint32_t *__restrict__ subset) {
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  if (i >= n) return;
-  const nrt_ray_f32 r = rays[subset ? subset[i] : i];
-  float inv[3], pinv[3];
-  int sign[3];
-  bool tame = PRUNE; // every direction component is an ordinary non-zero number and the origin is finite: entry distances are monotone in the box
-#pragma unroll
-  for (int k = 0; k < 3; k++) {
-    const float d = r.dir[k];
-    sign[k] = d < 0.0f ? 1 : 0;
-    inv[k] = (__builtin_fabsf(d) < 1.1920928955078125e-07f) ? __builtin_huge_valf() * (sign[k] ? -1.0f : 1.0f) : 1.0f / d;
-    pinv[k] = 1.0f / d; // NodeBBoxIntersector's plain reciprocal (nanosg.h:603-639)
-    tame = tame && (__builtin_fabsf(d) >= 1.1920928955078125e-07f) && (__builtin_fabsf(pinv[k]) < __builtin_huge_valf()) &&
-           (__builtin_fabsf(r.org[k]) < __builtin_huge_valf());
-  }
-  // entry distance of a box as node_interval computes it for an instance's box (unclipped, plain reciprocal): for a tame ray
-  // it can only grow from a box to a box inside it, so a subtree whose box is entered beyond the farthest entry of a FULL
-  // list holds nothing that could still make the list — the walk skips it (a ray through 100 000 instances lists its 64
-  // nearest without visiting the rest)
-  auto entry = [&](const float bmin[3], const float bmax[3]) -> float {
-    float a = -__builtin_huge_valf();
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-      const float lo = sign[k] ? bmax[k] : bmin[k];
-      const float t = (lo - r.org[k]) * pinv[k];
-      a = (t > a) ? t : a;
-    }
-    return a;
-  };
-  uint32_t stack[kTopStack];
-  float stack_t[PRUNE ? kTopStack : 1]; // entry distance of the pushed record's box (tame rays; else unused)
-  int sp = 0;
-  stack[0] = 0u; // record 0 == the root branch
-  stack_t[0] = -__builtin_huge_valf();
-  sp = 1;
-  ListTail st;
-  while (sp > 0) {
-    sp--;
-    if constexpr (PRUNE) {
-      if (tame && st.cnt == cap) { // the list is full: anything entered beyond its farthest entry cannot get in
-        if (!st.far_known) list_farthest(st, cap, list_t, list_node, n, i);
-        if (stack_t[sp] > st.far_t) continue;
-      }
-    }
-    const nrt::Wide4Node<float> w = wide4[stack[sp]];
-    uint32_t in_ref[4];
-    float in_t[4];
-    int nin = 0;
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-      const uint32_t cj = w.c[j];
-      if (cj == nrt::kWide4Empty) continue;
-      const float bmin[3] = {w.bmin[0][j], w.bmin[1][j], w.bmin[2][j]}, bmax[3] = {w.bmax[0][j], w.bmax[1][j], w.bmax[2][j]};
-      if (!(cj & nrt::kLeafBit)) {
-        if (top_box_hit(r, inv, sign, bmin, bmax)) {
-          in_ref[nin] = cj;
-          in_t[nin] = PRUNE ? entry(bmin, bmax) : 0.0f;
-          nin++;
-        }
-        continue;
-      }
-      uint32_t lcount, lfirst;
-      nrt::leaf_span(packed_leaves, top_nodes, cj & ~nrt::kLeafBit, lcount, lfirst);
-      for (uint32_t q = 0; q < lcount; q++) {
-        const uint32_t k = top_indices[lfirst + q];
-        float t;
-        if (lcount == 1u) {
-          if (!node_interval_box(r, bmin, bmax, t)) continue;
-        } else if (!node_interval(r, nodes[k], t)) {
-          continue;
-        }
-        list_add(st, t, k, cap, list_t, list_node, n, i);
-      }
-    }
-    // nearest box on top of the stack: the walk runs roughly front to back, the list fills with near entries first and the
-    // far subtrees fall to the test above (insertion sort of at most four entries, farthest first)
-    for (int x = 1; PRUNE && x < nin; x++)
-      for (int y = x; y > 0 && in_t[y] > in_t[y - 1]; y--) {
-        const float tt = in_t[y];
-        in_t[y] = in_t[y - 1];
-        in_t[y - 1] = tt;
-        const uint32_t rr = in_ref[y];
-        in_ref[y] = in_ref[y - 1];
-        in_ref[y - 1] = rr;
-      }
-    for (int x = 0; x < nin; x++) {
-      stack[sp] = in_ref[x];
-      if constexpr (PRUNE) stack_t[sp] = in_t[x];
-      sp++;
-    }
-  }
-  count[i] = st.cnt;
-}
 
 // ---- host-side restatement of the per-node update (nanosg.h:92-241, 246-302, 397-437) ----------------
 void mat_mult(float dst[4][4], const float m0[4][4], const float m1[4][4]) {
@@ -414,7 +156,7 @@ struct nrt_scene {
   unsigned single_pass = 1;   // scenes of kWalkMinNodes nodes or more are traced by k_scene_walk (no per-ray list); 0: always listing +
                               // k_scene_trace; 2: k_scene_walk for every scene of two nodes or more
   unsigned walk_blocks_per_cu = 0;
-  unsigned walk_leaf_items = 1; // the walk's leaf phase over items (traverse.hip leaf_items_one_trip; records bit-identical) when every mesh's leaves hold <= 4 records
+  unsigned walk_leaf_items = 1; // the walk's leaf phase over items (walk_dev.h leaf_items_one_trip; records bit-identical) when every mesh's leaves hold <= 4 records
   unsigned max_mesh_leaf = 0;   // most records a leaf of any instanced mesh holds (set by commit)
   unsigned walk_trav_min = 24, walk_refill_min = 24; // the walk's own phase thresholds (profiles/r04t_scene_walk_thresholds.txt: 8 / 56, the listing path's, cost it 10-13 %)
   unsigned walk_backoff = 0;  // calls left that skip the walk (see scene_traverse)
@@ -539,7 +281,7 @@ nrt_status nrtSceneCommit(nrt_scene *s) {
     const nrt::TreeViewF32 &tv = meshes[mesh_of[i]].second.tv;
     nrt::SceneInst &e = table[i];
     e.wide = tv.wide;
-    e.wide4 = (tv.tree_nested && tv.root_is_branch) ? tv.wide4 : nullptr; // two levels per step need nested boxes (traverse.hip)
+    e.wide4 = (tv.tree_nested && tv.root_is_branch) ? tv.wide4 : nullptr; // two levels per step need nested boxes (walk_dev.h NRT_STEP_NODE4)
     e.tris = tv.prims;
     e.nodes = tv.nodes;
     e.packed_leaves = tv.packed_leaves;
@@ -697,26 +439,14 @@ static nrt_status scene_list_and_trace(nrt_scene *s, const nrt_ray_f32 *d_rays, 
   SCHK(s, hipMemsetAsync(s->d_cursor.p, 0, (size_t)nrt::kMaxParts * nrt::kCursorStrideWords * sizeof(uint32_t), s->stream));
   const NodeDev *d_nodes = (const NodeDev *)s->d_nodes.p;
   const bool fused_scan = !s->use_top && s->fuse_scan && num_nodes <= (uint32_t)kMaxList; // (every entered box fits the list: no replacement logic needed in the trace kernel)
-  if (s->use_top && s->top_view.wide4 && s->top_view.root_is_branch && s->top_view.tree_nested &&
-      3u * (s->top_view.tree_depth / 2u + 1u) + 2u < (uint32_t)kTopStack)
-  {
-    if (num_nodes >= s->prune_min) // (rays can enter more boxes than the list holds: the pruning walk)
-      hipLaunchKernelGGL(k_scene_list_w4<true>, dim3(grid), dim3(256), 0, s->stream, d_rays, n, (const nrt::Wide4Node<float> *)s->top_view.wide4,
-                         s->top_view.nodes, s->top_view.packed_leaves, s->top_view.indices, d_nodes, cap, (float *)s->d_list_t.p,
-                         (uint32_t *)s->d_list_node.p, (uint32_t *)s->d_count.p, subset);
-    else
-      hipLaunchKernelGGL(k_scene_list_w4<false>, dim3(grid), dim3(256), 0, s->stream, d_rays, n, (const nrt::Wide4Node<float> *)s->top_view.wide4,
-                         s->top_view.nodes, s->top_view.packed_leaves, s->top_view.indices, d_nodes, cap, (float *)s->d_list_t.p,
-                         (uint32_t *)s->d_list_node.p, (uint32_t *)s->d_count.p, subset);
-  }
-  else if (s->use_top)
-    hipLaunchKernelGGL(k_scene_list_bvh, dim3(grid), dim3(256), 0, s->stream, d_rays, n, s->top_view.nodes, s->top_view.indices,
-                       d_nodes, cap, (float *)s->d_list_t.p, (uint32_t *)s->d_list_node.p, (uint32_t *)s->d_count.p, subset);
-  else if (!fused_scan)
-    hipLaunchKernelGGL(k_scene_list, dim3(grid), dim3(256), 0, s->stream, d_rays, n, d_nodes, num_nodes, cap,
-                       (float *)s->d_list_t.p, (uint32_t *)s->d_list_node.p, (uint32_t *)s->d_count.p, subset);
-  // (else: a handful of nodes — k_scene_trace tests every world box itself as it fetches a ray: no listing launch)
-  SCHK(s, hipGetLastError());
+  const bool top_w4 = s->use_top && s->top_view.wide4 && s->top_view.root_is_branch && s->top_view.tree_nested &&
+                      3u * (s->top_view.tree_depth / 2u + 1u) + 2u < (uint32_t)kTopStack;
+  const nrt::SceneListForm form = top_w4 ? (num_nodes >= s->prune_min ? nrt::kSceneListW4Prune // (rays can enter more boxes than the list holds: the pruning walk)
+                                                                      : nrt::kSceneListW4)
+                                         : (s->use_top ? nrt::kSceneListBvh : nrt::kSceneListScan);
+  if (s->use_top || !fused_scan) // (else: a handful of nodes — k_scene_trace tests every world box itself as it fetches a ray: no listing launch)
+    SCHK(s, nrt::launch_scene_list(form, s->top_view, d_rays, n, d_nodes, num_nodes, cap, (float *)s->d_list_t.p, (uint32_t *)s->d_list_node.p,
+                                   (uint32_t *)s->d_count.p, subset, s->stream));
   nrt::SceneTraceArgs a;
   a.scan_nodes = fused_scan ? num_nodes : 0u;
   a.rays = d_rays;

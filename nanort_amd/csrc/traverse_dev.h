@@ -1,5 +1,5 @@
 // nanort_amd/csrc/traverse_dev.h — the device pieces of the binary-loop traversal that more than one kernel file uses
-// (traverse.hip, multihit.hip): ray setup, slab and primitive tests, ray claims, streaming loads / stores, completion
+// (traverse.hip and scene_kernels.hip through walk_dev.h, multihit.hip): ray setup, slab and primitive tests, ray claims, streaming loads / stores, completion
 // records.  Everything here is a template or forceinline device code, so each including file compiles its own copy.
 #pragma once
 
@@ -134,7 +134,7 @@ __device__ __forceinline__ void lane_init(Lane<T> &L, const typename Wire<T>::Ra
 // One axis of IntersectRayAABB (nanort.h:2285-2370): the near plane `lo` and the far plane `hi` (chosen by the ray's direction
 // sign) narrow the interval.  safemax(t0, tmin) / safemin(t1, tmax) (nanort.h:1236-1243): a NaN first operand is dropped and the
 // running value is never NaN, which is exactly maxNum/minNum (v_max_f32 / v_min_f32); the only difference, the sign of a zero
-// result, cannot change `tmin <= tmax`.  (The packed two-box forms of traverse.hip write the same operations over register pairs.)
+// result, cannot change `tmin <= tmax`.  (The packed two-box forms of walk_dev.h write the same operations over register pairs.)
 template <typename T>
 __device__ __forceinline__ void slab_axis(T lo, T hi, T org, T inv, T &tmin, T &tmax) {
   const T t0 = (lo - org) * inv;
@@ -700,7 +700,7 @@ __device__ __forceinline__ void done_end(const TraverseArgs<T> &a, unsigned lane
 // A lane's traversal stack.  Entry i lies in the block's LDS array, lds[i][col], below STACK, and from there on in the launch's
 // global overflow arrays at (i - STACK) * spill_stride + gcol.  `col` / `gcol` name the column on both sides: a lane's own
 // (threadIdx.x, its global thread index) or, in the tail of a launch, the column of the lane whose ray a quad has taken over.
-// SE says what an entry is: StackRef here, StackEntry<T> (reference + t_min; the t_min half lies in spill_tmin) in traverse.hip;
+// SE says what an entry is: StackRef here, StackEntry<T> (reference + t_min; the t_min half lies in spill_tmin) in walk_dev.h;
 // A is the launch's argument block (spill, spill_stride and, for StackEntry, spill_tmin).  THE one statement of "entry i": every
 // guarded push and every pop of every walk goes through load / store.
 // (The block's LDS array is an argument of load / store, not a member: a pointer to LDS held in a struct reaches the code
@@ -728,7 +728,7 @@ struct LaneStack {
         e = a.spill[o];
     }
   }
-  // (StackRef entries; a StackEntry is stored by traverse.hip's NRT_STACK_STORE, which says why it is a macro)
+  // (StackRef entries; a StackEntry is stored by walk_dev.h's NRT_STACK_STORE, which says why it is a macro)
   __device__ __forceinline__ void store(Entry (&lds)[STACK][kTraverseBlock], int i, uint32_t ref) const {
     if (i < STACK) {
       lds[i][col] = ref;

@@ -290,7 +290,7 @@ void sgo_traverse(const sg_node *nodes, uint32_t num_nodes, const sg_ray *rays, 
   free(list);
 }
 
-/* MODEL (not a restatement) of the single-pass scene walk of nanort_amd/csrc/traverse.hip (k_scene_walk): the instances whose
+/* MODEL (not a restatement) of the single-pass scene walk of nanort_amd/csrc/scene_kernels.hip (k_scene_walk): the instances whose
  * boxes a ray enters are visited in ANY order — here a seeded shuffle, or the sorted order with local disorder — and no list is
  * kept.  Rules:
  *   rank(i)   = (t_min_i, i), the order Scene::Traverse visits its list in (nanosg.h:793-795 over nanort.h:2676-2687);

@@ -1,6 +1,6 @@
 /* oracle/wide4_model_body.inc — TEST INFRASTRUCTURE, NOT PRODUCT CODE.
  *
- * A sequential MODEL of the traversal kernel's two-levels-per-step walk (nanort_amd/csrc/traverse.hip,
+ * A sequential MODEL of the traversal kernel's two-levels-per-step walk (nanort_amd/csrc/walk_dev.h,
  * NRT_STEP_NODE4 / NRT_POP_ENTRY; DESIGN.md §3.1), used by tests/test_wide4_model.py to check, on the CPU and on
  * hostile inputs, that it visits the same leaves in the same order as the restated reference loop above
  * (nanort.h:2526-2548):

@@ -1,4 +1,4 @@
-"""CPU model of the occlusion form of the single-pass scene walk (nanort_amd/csrc/traverse.hip, k_scene_walk<.., ANY = true>) and
+"""CPU model of the occlusion form of the single-pass scene walk (nanort_amd/csrc/scene_kernels.hip, k_scene_walk<.., ANY = true>) and
 of its certificate, plus the interface checks of nrtSceneOccludedBatch*.
 
 What the reference's flag is: of the instances whose boxes a ray enters, the 64 of smallest (entry distance, id) are listed

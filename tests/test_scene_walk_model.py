@@ -1,4 +1,4 @@
-"""CPU proof-by-test of the single-pass scene walk (nanort_amd/csrc/traverse.hip, k_scene_walk): its model in
+"""CPU proof-by-test of the single-pass scene walk (nanort_amd/csrc/scene_kernels.hip, k_scene_walk): its model in
 oracle/nanosg_oracle.c visits the instances a ray enters in a RANDOM order, skips by coin what the skipping rule allows, keeps no
 list — and every ray that carries the model's certificate must equal the restatement of nanosg::Scene::Traverse
 (reference examples/nanosg/nanosg.h:778-870 over nanort.h:2608-2692) bit for bit.  Hostile material on purpose: flat planes

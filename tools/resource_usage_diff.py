@@ -1,24 +1,31 @@
 #!/usr/bin/env python3
-"""Compare the compiler's kernel resource-usage remarks of two builds of traverse.hip.
+"""Compare the compiler's kernel resource usage of two builds of the kernel files.
 
-Compile the file once per tree with the flags of nanort_amd/csrc/Makefile plus
-`-Rpass-analysis=kernel-resource-usage` (add `-DNRT_PROF=1 -DNRT_ROCTX=1` for the profiling instantiations), one
-compile per log so that the remarks of two compilers do not interleave:
+Compile each file once per tree with the flags of nanort_amd/csrc/Makefile plus `-Rpass-analysis=kernel-resource-usage`
+(add `-DNRT_PROF=1 -DNRT_ROCTX=1` for the profiling instantiations), one compile per log so that the remarks of two
+compilers do not interleave; with `-S --cuda-device-only` the assembly gives the code length as well:
 
-    hipcc $HIPFLAGS -Rpass-analysis=kernel-resource-usage -c traverse.hip -o /dev/null 2> log
+    hipcc $HIPFLAGS -Rpass-analysis=kernel-resource-usage -S --cuda-device-only traverse.hip -o traverse.s 2> traverse.log
 
-    tools/resource_usage_diff.py parent.log branch.log
+    tools/resource_usage_diff.py parent/traverse.log,parent/traverse.s branch/traverse.log,branch/traverse.s
 
-prints one markdown row per k_traverse* kernel: VGPRs, SGPRs, scratch bytes per lane, waves per SIMD and LDS bytes per
-block of both builds, and whether they are the same.  Exit status 1 when a PLAIN instantiation differs in any figure or a
-non-PLAIN one changed its waves per SIMD or gained scratch.
+Each side is a comma-separated list of remark logs and assembly files (any number of source files: a kernel that moved from one
+file to another is found by its mangled name).  `--kernels REGEX` picks the kernels by their demangled names (default
+`k_traverse`).  Prints one markdown row per kernel: VGPRs, SGPRs, scratch bytes per lane, waves per SIMD, LDS bytes per block
+and code bytes (`-` without assembly) of both builds, and whether they are the same.  A kernel whose mangled name exists on
+one side only is paired with one of the same demangled name without its parameter list, and the row says that the name differs.
+
+Exit status 1 when a PLAIN instantiation of k_traverse_wide differs in any figure, or any other kernel changed its waves per SIMD
+or gained scratch, or a kernel has no partner; with `--strict`, when anything differs at all.
 """
+import argparse
 import re
 import subprocess
 import sys
 
 FIELDS = (("VGPRs", "vgpr"), ("TotalSGPRs", "sgpr"), ("ScratchSize [bytes/lane]", "scratch"), ("Occupancy [waves/SIMD]", "waves"),
           ("LDS Size [bytes/block]", "lds"))
+KEYS = [k for _, k in FIELDS] + ["code"]
 
 
 def demangle(names):
@@ -26,19 +33,30 @@ def demangle(names):
     return dict(zip(names, out))
 
 
-def parse(path):
-    kernels, cur = {}, None
-    for line in open(path, errors="replace"):
-        m = re.search(r"remark: Function Name: (\S+)", line)
-        if m:
-            cur = kernels.setdefault(m.group(1), {})
-            continue
-        if cur is None:
-            continue
-        for label, key in FIELDS:
-            m = re.search(r"remark:\s+" + re.escape(label) + r": (\d+)", line)
+def parse(paths):
+    kernels = {}
+    for path in paths.split(","):
+        cur = asm = None
+        for line in open(path, errors="replace"):
+            m = re.search(r"remark: Function Name: (\S+)", line)
             if m:
-                cur[key] = int(m.group(1))
+                cur = kernels.setdefault(m.group(1), {})
+                continue
+            m = re.match(r"\s*\.amdhsa_kernel (\S+)", line)
+            if m:
+                asm = kernels.setdefault(m.group(1), {})
+                continue
+            m = re.match(r"; codeLenInByte = (\d+)", line)
+            if m and asm is not None:
+                asm["code"] = int(m.group(1))
+                asm = None
+                continue
+            if cur is None:
+                continue
+            for label, key in FIELDS:
+                m = re.search(r"remark:\s+" + re.escape(label) + r": (\d+)", line)
+                if m:
+                    cur[key] = int(m.group(1))
     return kernels
 
 
@@ -51,26 +69,50 @@ def is_plain(name):
     return len(args) > 4 and args[4] == "true"
 
 
+def short_name(name):
+    return re.sub(r"\(.*$", "", name.replace("(anonymous namespace)::", "")).replace("void ", "").replace("nrt::", "")
+
+
 def main():
-    a, b = parse(sys.argv[1]), parse(sys.argv[2])
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("first")
+    ap.add_argument("second")
+    ap.add_argument("--kernels", default="k_traverse", help="regular expression over the demangled kernel names")
+    ap.add_argument("--strict", action="store_true", help="any difference fails")
+    o = ap.parse_args()
+    a, b = parse(o.first), parse(o.second)
     names = demangle(sorted(set(a) | set(b)))
-    bad = 0
-    print("| kernel | PLAIN | VGPRs | SGPRs | scratch | waves/SIMD | LDS | same |")
-    print("|---|---|---|---|---|---|---|---|")
-    for mangled, name in sorted(names.items(), key=lambda kv: kv[1]):
-        if "k_traverse" not in name:
+    rows = []  # (short name, plain, first figures, second figures, same mangled name)
+    alone = {}
+    for mangled, name in names.items():
+        if not re.search(o.kernels, name):
             continue
-        short = re.sub(r"\(.*$", "", name).replace("void nrt::", "").replace("(nrt::TraverseArgs", "")
-        x, y = a.get(mangled), b.get(mangled)
+        if mangled in a and mangled in b:
+            rows.append((short_name(name), is_plain(name), a[mangled], b[mangled], True))
+        else:
+            alone.setdefault(short_name(name), {})["a" if mangled in a else "b"] = (a.get(mangled) or b.get(mangled))
+    for short, sides in alone.items():
+        rows.append((short, None, sides.get("a"), sides.get("b"), False))
+    bad = 0
+    print("| kernel | PLAIN | VGPRs | SGPRs | scratch | waves/SIMD | LDS | code bytes | same |")
+    print("|---|---|---|---|---|---|---|---|---|")
+    for short, plain, x, y, same_name in sorted(rows, key=lambda r: r[0]):
         if x is None or y is None:
-            print("| `%s` | | only in %s | | | | | no |" % (short, "the second" if x is None else "the first"))
+            print("| `%s` | | only in %s | | | | | | no |" % (short, "the second" if x is None else "the first"))
             bad = 1
             continue
-        plain = is_plain(name)
-        same = x == y
-        cells = ["%d" % x[k] if x[k] == y[k] else "%d -> %d" % (x[k], y[k]) for _, k in FIELDS]
-        print("| `%s` | %s | %s | %s |" % (short, {None: "-", True: "yes", False: "no"}[plain], " | ".join(cells), "yes" if same else "no"))
-        if plain and not same:
+        same = all(x.get(k) == y.get(k) for k in KEYS)
+        cells = []
+        for k in KEYS:
+            if x.get(k) is None and y.get(k) is None:
+                cells.append("-")
+            elif x.get(k) == y.get(k):
+                cells.append("%d" % x[k])
+            else:
+                cells.append("%s -> %s" % (x.get(k, "-"), y.get(k, "-")))
+        verdict = ("yes" if same else "no") + ("" if same_name else " (mangled name differs)")
+        print("| `%s` | %s | %s | %s |" % (short, {None: "-", True: "yes", False: "no"}[plain], " | ".join(cells), verdict))
+        if (plain or o.strict) and not same:
             bad = 1
         if not plain and (x["waves"] != y["waves"] or y["scratch"] > x["scratch"]):
             bad = 1
