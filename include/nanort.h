@@ -1662,6 +1662,19 @@ class BVHAccel {
     }
     return true;
   }
+  // The occlusion query on the HOST, with or without NANORT_USE_HIP_BACKEND and for any intersector whose intersection record is
+  // H: occluded_out[i] is 1 / 0, the flag of Traverse() for ray i through a copy of `intersector` of its own.  This is the
+  // statement of what OccludedBatchSpheres / OccludedBatchCylinders / OccludedBatchCurves (and nrtOccludedBatchPrims_f32) answer.
+  template <class I, class H>
+  bool OccludedBatch(const Ray<T> *rays, size_t num_rays, const I &intersector, unsigned char *occluded_out,
+                     const BVHTraceOptions &options = BVHTraceOptions()) const {
+    for (size_t i = 0; i < num_rays; i++) {
+      const I ray_intersector(intersector);
+      H isect;
+      occluded_out[i] = Traverse(rays[i], ray_intersector, &isect, options) ? 1 : 0;
+    }
+    return true;
+  }
 
 #ifdef NANORT_USE_HIP_BACKEND
   // Closest hit for each of `num_rays` rays in one GPU launch.  isects[i] is written only when
@@ -1883,30 +1896,7 @@ class BVHAccel {
     static_assert(detail::same_type<T, float>::value, "the cylinder primitive is fp32");
     static_assert(sizeof(CylinderIntersection) == sizeof(nrt_cyl_hit_f32), "CylinderIntersection layout");
     std::lock_guard<std::mutex> lock(batch_mutex_);
-    if (!ctx_ || !cyl_endpoints_ || device_prim_kind_ != 2) {
-      backend_error_ = "TraverseBatch(CylinderIntersection*): Build() with CylinderGeometry/CylinderPred first";
-      return false;
-    }
-    if (test_cap != cyl_test_cap_ || device_tree_stale_) {  // the flag lives with the primitives on the device
-      // (the host tree first: it may still be pending after Build(), and nrtSetCylinders_f32 frees the device tree)
-      EnsureHostTree();
-      if (nodes_.empty()) {
-        backend_error_ = "TraverseBatch: empty tree";
-        return false;
-      }
-      if (SharesDeviceContext()) {  // copy-on-write: the shared context stays with the copies
-        if (!DetachDeviceContext(test_cap)) return false;  // (sends the cylinders with the new flag)
-      } else if (nrtSetCylinders_f32(ctx_.get(), cyl_endpoints_, cyl_radii_, cyl_count_, test_cap ? 1 : 0) != NRT_OK) {
-        backend_error_ = nrtLastError(ctx_.get());
-        return false;
-      }
-      if (nrtSetTree_f32(ctx_.get(), reinterpret_cast<const nrt_node_f32 *>(&nodes_[0]), nodes_.size(), &indices_[0], indices_.size()) != NRT_OK) {
-        backend_error_ = nrtLastError(ctx_.get());
-        return false;
-      }
-      cyl_test_cap_ = test_cap;
-      device_tree_stale_ = false;
-    }
+    if (!CylinderTreeReady("TraverseBatch(CylinderIntersection*)", test_cap)) return false;
     if (num_rays == 0) return true;
     std::vector<CylinderIntersection> tmp(num_rays);
     std::vector<unsigned char> mask(num_rays);
@@ -1930,34 +1920,7 @@ class BVHAccel {
     static_assert(detail::same_type<T, float>::value, "the curve primitive is fp32");
     static_assert(sizeof(BezierCurveIntersection) == sizeof(nrt_curve_hit_f32), "BezierCurveIntersection layout");
     std::lock_guard<std::mutex> lock(batch_mutex_);
-    if (!ctx_ || !crv_cps_ || device_prim_kind_ != 3) {
-      backend_error_ = "TraverseBatch(BezierCurveIntersection*): Build() with BezierCurveGeometry/BezierCurvePred first";
-      return false;
-    }
-    if (num_subdivisions < 1 || num_subdivisions > 64) {
-      backend_error_ = "TraverseBatch(BezierCurveIntersection*): num_subdivisions outside 1..64";
-      return false;
-    }
-    if (num_subdivisions != crv_subdiv_ || device_tree_stale_) {  // the count lives with the primitives on the device
-      // (the host tree first: it may still be pending after Build(), and nrtSetCurves_f32 frees the device tree)
-      EnsureHostTree();
-      if (nodes_.empty()) {
-        backend_error_ = "TraverseBatch: empty tree";
-        return false;
-      }
-      crv_subdiv_ = num_subdivisions;
-      if (SharesDeviceContext()) {  // copy-on-write: the shared context stays with the copies
-        if (!DetachDeviceContext(cyl_test_cap_)) return false;  // (sends the curves with the new count)
-      } else if (nrtSetCurves_f32(ctx_.get(), crv_cps_, crv_radii_, prim_count_, static_cast<uint32_t>(num_subdivisions)) != NRT_OK) {
-        backend_error_ = nrtLastError(ctx_.get());
-        return false;
-      }
-      if (nrtSetTree_f32(ctx_.get(), reinterpret_cast<const nrt_node_f32 *>(&nodes_[0]), nodes_.size(), &indices_[0], indices_.size()) != NRT_OK) {
-        backend_error_ = nrtLastError(ctx_.get());
-        return false;
-      }
-      device_tree_stale_ = false;
-    }
+    if (!CurveTreeReady("TraverseBatch(BezierCurveIntersection*)", num_subdivisions)) return false;
     if (num_rays == 0) return true;
     std::vector<BezierCurveIntersection> tmp(num_rays);
     std::vector<unsigned char> mask(num_rays);
@@ -1973,6 +1936,47 @@ class BVHAccel {
       if (hit_out) hit_out[i] = mask[i];
     }
     return true;
+  }
+  // Opt-in extension without a reference counterpart: occlusion queries of the sphere, cylinder and curve accels
+  // (nrtOccludedBatchPrims_f32).  occluded_out[i] is 1 / 0: exactly the flag of the host OccludedBatch(rays, n, intersector, out)
+  // above with the kind's intersector — of TraverseBatch(<Kind>Intersection*)'s hit_out[i] != 0 — but a ray stops at the first
+  // primitive that settles it and no record is produced, staged or copied.  Refusals are those of the matching TraverseBatch().
+  // (OccludedBatch() / OccludedBatchDevice() above stay the triangle accels' calls and refuse these kinds.)
+  bool OccludedBatchSpheres(const Ray<T> *rays, size_t num_rays, unsigned char *occluded_out, const BVHTraceOptions &options = BVHTraceOptions()) const {
+    static_assert(detail::same_type<T, float>::value, "the sphere primitive is fp32");
+    std::lock_guard<std::mutex> lock(batch_mutex_);
+    return DeviceTreeReady(1) && OccludedPrims(rays, num_rays, occluded_out, options, false, NULL);
+  }
+  bool OccludedBatchCylinders(const Ray<T> *rays, size_t num_rays, unsigned char *occluded_out, const BVHTraceOptions &options = BVHTraceOptions(),
+                              bool test_cap = true) const {
+    static_assert(detail::same_type<T, float>::value, "the cylinder primitive is fp32");
+    std::lock_guard<std::mutex> lock(batch_mutex_);
+    return CylinderTreeReady("OccludedBatchCylinders", test_cap) && OccludedPrims(rays, num_rays, occluded_out, options, false, NULL);
+  }
+  bool OccludedBatchCurves(const Ray<T> *rays, size_t num_rays, unsigned char *occluded_out, const BVHTraceOptions &options = BVHTraceOptions(),
+                           int num_subdivisions = 4) const {
+    static_assert(detail::same_type<T, float>::value, "the curve primitive is fp32");
+    std::lock_guard<std::mutex> lock(batch_mutex_);
+    return CurveTreeReady("OccludedBatchCurves", num_subdivisions) && OccludedPrims(rays, num_rays, occluded_out, options, false, NULL);
+  }
+  // ... and with device pointers, asynchronous on `hip_stream` (see TraverseBatchDevice).
+  bool OccludedBatchSpheresDevice(const Ray<T> *d_rays, size_t num_rays, unsigned char *d_occluded, void *hip_stream,
+                                  const BVHTraceOptions &options = BVHTraceOptions()) const {
+    static_assert(detail::same_type<T, float>::value, "the sphere primitive is fp32");
+    std::lock_guard<std::mutex> lock(batch_mutex_);
+    return DeviceTreeReady(1) && OccludedPrims(d_rays, num_rays, d_occluded, options, true, hip_stream);
+  }
+  bool OccludedBatchCylindersDevice(const Ray<T> *d_rays, size_t num_rays, unsigned char *d_occluded, void *hip_stream,
+                                    const BVHTraceOptions &options = BVHTraceOptions(), bool test_cap = true) const {
+    static_assert(detail::same_type<T, float>::value, "the cylinder primitive is fp32");
+    std::lock_guard<std::mutex> lock(batch_mutex_);
+    return CylinderTreeReady("OccludedBatchCylindersDevice", test_cap) && OccludedPrims(d_rays, num_rays, d_occluded, options, true, hip_stream);
+  }
+  bool OccludedBatchCurvesDevice(const Ray<T> *d_rays, size_t num_rays, unsigned char *d_occluded, void *hip_stream,
+                                 const BVHTraceOptions &options = BVHTraceOptions(), int num_subdivisions = 4) const {
+    static_assert(detail::same_type<T, float>::value, "the curve primitive is fp32");
+    std::lock_guard<std::mutex> lock(batch_mutex_);
+    return CurveTreeReady("OccludedBatchCurvesDevice", num_subdivisions) && OccludedPrims(d_rays, num_rays, d_occluded, options, true, hip_stream);
   }
   const std::string &LastBackendError() const { return backend_error_; }
   // The C-ABI context behind this accel (NULL before a GPU Build()): what nrtSceneAddNode_f32 takes (include/nanosg_hip.h).
@@ -2021,6 +2025,78 @@ class BVHAccel {
         }
       }
       device_tree_stale_ = false;
+    }
+    return true;
+  }
+  // The same for the cylinder and the curve accels (caller holds batch_mutex_; `who` opens the error text).  The intersector's
+  // constructor argument — test_cap, num_subdivisions — lives with the primitives on the device: when it differs from what was
+  // sent last, or the tree was adopted by Load(), the primitives go again with the new value and the tree behind them.
+  bool CylinderTreeReady(const char *who, bool test_cap) const {
+    if (!ctx_ || !cyl_endpoints_ || device_prim_kind_ != 2) {
+      backend_error_ = std::string(who) + ": Build() with CylinderGeometry/CylinderPred first";
+      return false;
+    }
+    if (test_cap == cyl_test_cap_ && !device_tree_stale_) return true;
+    // (the host tree first: it may still be pending after Build(), and nrtSetCylinders_f32 frees the device tree)
+    EnsureHostTree();
+    if (nodes_.empty()) {
+      backend_error_ = std::string(who) + ": empty tree";
+      return false;
+    }
+    if (SharesDeviceContext()) {  // copy-on-write: the shared context stays with the copies
+      if (!DetachDeviceContext(test_cap)) return false;  // (sends the cylinders with the new flag)
+    } else if (nrtSetCylinders_f32(ctx_.get(), cyl_endpoints_, cyl_radii_, cyl_count_, test_cap ? 1 : 0) != NRT_OK) {
+      backend_error_ = nrtLastError(ctx_.get());
+      return false;
+    }
+    if (nrtSetTree_f32(ctx_.get(), reinterpret_cast<const nrt_node_f32 *>(&nodes_[0]), nodes_.size(), &indices_[0], indices_.size()) != NRT_OK) {
+      backend_error_ = nrtLastError(ctx_.get());
+      return false;
+    }
+    cyl_test_cap_ = test_cap;
+    device_tree_stale_ = false;
+    return true;
+  }
+  bool CurveTreeReady(const char *who, int num_subdivisions) const {
+    if (!ctx_ || !crv_cps_ || device_prim_kind_ != 3) {
+      backend_error_ = std::string(who) + ": Build() with BezierCurveGeometry/BezierCurvePred first";
+      return false;
+    }
+    if (num_subdivisions < 1 || num_subdivisions > 64) {
+      backend_error_ = std::string(who) + ": num_subdivisions outside 1..64";
+      return false;
+    }
+    if (num_subdivisions == crv_subdiv_ && !device_tree_stale_) return true;
+    // (the host tree first: it may still be pending after Build(), and nrtSetCurves_f32 frees the device tree)
+    EnsureHostTree();
+    if (nodes_.empty()) {
+      backend_error_ = std::string(who) + ": empty tree";
+      return false;
+    }
+    crv_subdiv_ = num_subdivisions;
+    if (SharesDeviceContext()) {  // copy-on-write: the shared context stays with the copies
+      if (!DetachDeviceContext(cyl_test_cap_)) return false;  // (sends the curves with the new count)
+    } else if (nrtSetCurves_f32(ctx_.get(), crv_cps_, crv_radii_, prim_count_, static_cast<uint32_t>(num_subdivisions)) != NRT_OK) {
+      backend_error_ = nrtLastError(ctx_.get());
+      return false;
+    }
+    if (nrtSetTree_f32(ctx_.get(), reinterpret_cast<const nrt_node_f32 *>(&nodes_[0]), nodes_.size(), &indices_[0], indices_.size()) != NRT_OK) {
+      backend_error_ = nrtLastError(ctx_.get());
+      return false;
+    }
+    device_tree_stale_ = false;
+    return true;
+  }
+  // The launch of OccludedBatch<Kind>[Device] once the kind's tree is ready (caller holds batch_mutex_).
+  bool OccludedPrims(const Ray<T> *rays, size_t num_rays, unsigned char *occluded, const BVHTraceOptions &options, bool device, void *hip_stream) const {
+    static_assert(sizeof(BVHTraceOptions) == sizeof(nrt_trace_options), "BVHTraceOptions layout");
+    nrt_trace_options o;
+    std::memcpy(&o, &options, sizeof(o));
+    const nrt_ray_f32 *r = reinterpret_cast<const nrt_ray_f32 *>(rays);
+    if ((device ? nrtOccludedBatchPrimsDevice_f32(ctx_.get(), r, num_rays, &o, occluded, hip_stream)
+                : nrtOccludedBatchPrims_f32(ctx_.get(), r, num_rays, &o, occluded)) != NRT_OK) {
+      backend_error_ = nrtLastError(ctx_.get());
+      return false;
     }
     return true;
   }

@@ -200,7 +200,8 @@ NRT_API nrt_status nrtSetMesh_f64(nrt_ctx *ctx, const double *vertices, size_t v
  * The reference answers "is anything in the way?" with a closest-hit Traverse (CheckForOccluder,
  * examples/path_tracer/main.cc:675-701).  These entry points return only the hit flag — mask_out[i] is exactly what
  * nrtTraverseBatch* would put in hit_mask_out[i], for every ray and option — but a ray stops at the first primitive it
- * accepts instead of looking for the nearest one.  Triangle contexts only. */
+ * accepts instead of looking for the nearest one.  These four take triangle contexts only and refuse every other kind;
+ * sphere, cylinder and curve contexts are asked through nrtOccludedBatchPrims*_f32 (below, behind the curve primitives). */
 NRT_API nrt_status nrtOccludedBatch_f32(nrt_ctx *ctx, const nrt_ray_f32 *rays, uint64_t num_rays,
                                         const nrt_trace_options *options, uint8_t *mask_out);
 NRT_API nrt_status nrtOccludedBatch_f64(nrt_ctx *ctx, const nrt_ray_f64 *rays, uint64_t num_rays,
@@ -312,8 +313,9 @@ NRT_API nrt_status nrtTraverseBatchCylindersDevice_f32(nrt_ctx *ctx, const nrt_r
  * alignment, copied on `hip_stream`, the caller may free them on return, a following build is byte-identical to the host
  * form's).  Refusals leave the context untouched: NRT_ERR_INVALID for a NULL context, num_subdivisions outside 1..64, a
  * NULL or (Device) misaligned pointer with num_curves > 0; NRT_ERR_PRECISION on a context that holds fp64 primitives.
- * A curve context is traced by nrtTraverseBatchCurves*_f32 only: every other traversal, occlusion, multi-hit, counting,
- * refit, scene and multi-context entry point refuses it with an error string (and these two refuse every other kind). */
+ * A curve context is traced by nrtTraverseBatchCurves*_f32 and nrtOccludedBatchPrims*_f32 (below) only: every other traversal,
+ * occlusion, multi-hit, counting, refit, scene and multi-context entry point refuses it with an error string (and the two
+ * nrtTraverseBatchCurves*_f32 refuse every other kind). */
 typedef struct nrt_curve_hit_f32 {
   float t;
   uint32_t prim_id;
@@ -332,6 +334,38 @@ NRT_API nrt_status nrtTraverseBatchCurves_f32(nrt_ctx *ctx, const nrt_ray_f32 *r
 NRT_API nrt_status nrtTraverseBatchCurvesDevice_f32(nrt_ctx *ctx, const nrt_ray_f32 *d_rays, uint64_t num_rays,
                                                     const nrt_trace_options *options, nrt_curve_hit_f32 *d_hits_out,
                                                     uint8_t *d_hit_mask_out, void *hip_stream);
+
+/* ---- occlusion queries for every primitive kind: an OPT-IN EXTENSION with no reference counterpart ----------------------
+ * "Is anything in the way?" for whatever kind the context holds — spheres, cylinders, curves, triangles.  fp32 only (the setters
+ * of the three custom kinds are).  Contract:
+ *   1. Result: mask_out[i] is exactly 0 or 1, and 1 exactly when the closest-hit call of the context's kind writes a non-zero
+ *      hit_mask_out[i] for the same ray and options: nrtTraverseBatch_f32 (spheres, triangles), nrtTraverseBatchCylinders_f32,
+ *      nrtTraverseBatchCurves_f32.  Under both walks (tunable "wide4" 0 and 1) and every scheduling tunable.  The cylinder
+ *      calls' cap bit (bit 1 of their mask) never appears here.
+ *   2. Options: sphere, cylinder and curve contexts honour prim_ids_range; their intersectors have no skip_prim_id and no
+ *      cull_back_face, which are ignored as in their closest-hit calls.  A triangle context honours all three and goes straight
+ *      to the path of nrtOccludedBatch*_f32: the same bytes.  Cylinders use the context's test_cap, curves its num_subdivisions.
+ *   3. Exactness: the agreement is exact, not approximate.  Until a ray's first acceptance its pops, steps and leaf tests are
+ *      those of the closest-hit walk (the bound is still max_t); the ray stops once `hit_t < max_t` holds, the very predicate
+ *      of the closest-hit flag — a sphere accepted at t == max_t, or an acceptance that leaves a NaN, does not stop it, as it
+ *      leaves the closest-hit flag 0; cylinders and curves only ever lower an accepted distance, so the predicate is final when
+ *      it first holds.  One case is outside this: the SPHERE intersector accepts a NaN distance (`if (t > t_inout) return
+ *      false`), so a sphere with a NaN centre or radius (or an overflow inside the quadratic) met AFTER a finite hit clears the
+ *      closest-hit flag again, where this call has answered 1.  Finite spheres, and rays whose every test yields NaN, agree.
+ *   4. Output: one byte per ray is the whole result; no hit record is produced, staged or copied, no compact record is
+ *      written to scratch and no pass runs behind the walk.  The host form stages rays in and flags out; the Device form is
+ *      asynchronous on `hip_stream`, like nrtOccludedBatchDevice_f32.  nrtLastTraverseMs / nrtLastKernelName describe the
+ *      launch as any other.
+ *   5. Errors: NRT_ERR_INVALID for a NULL context, NULL rays or mask with num_rays > 0, a context without a tree, more than
+ *      2^31-1 rays; NRT_ERR_PRECISION for an fp64 context; num_rays == 0 is NRT_OK.  A refusal writes nothing to the mask and
+ *      sets nrtLastError.
+ * Unchanged, and out of scope here: nrtOccludedBatch* above keep refusing sphere, cylinder and curve contexts, as do
+ * NRT_BATCH_OCCLUSION batches of nrtTraverseBatches*; there is no multi-hit, per-ray skip id, group or scene form for these
+ * kinds. */
+NRT_API nrt_status nrtOccludedBatchPrims_f32(nrt_ctx *ctx, const nrt_ray_f32 *rays, uint64_t num_rays,
+                                             const nrt_trace_options *options, uint8_t *mask_out);
+NRT_API nrt_status nrtOccludedBatchPrimsDevice_f32(nrt_ctx *ctx, const nrt_ray_f32 *d_rays, uint64_t num_rays,
+                                                   const nrt_trace_options *options, uint8_t *d_mask_out, void *hip_stream);
 
 /* ---- build: replaces BVHAccel<T>::Build (nanort.h:716-718, 1892-2149) ----
  * Binned-SAH construction on the GPU over the mesh set above.  Honours

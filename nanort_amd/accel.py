@@ -271,6 +271,11 @@ class BVHAccel:
             self._stream_handle(stream)))
         self._mesh = DeviceGeometry("curves", n, 4 * n)
 
+    def _is_custom_kind(self):
+        """The accel holds spheres, cylinders or curves: its occlusion queries go through nrtOccludedBatchPrims*_f32."""
+        m = self._mesh
+        return isinstance(m, (SphereGeometry, CylinderGeometry, CurveGeometry)) or (isinstance(m, DeviceGeometry) and m.kind in ("spheres", "curves"))
+
     def _is_curves(self):
         m = self._mesh
         return isinstance(m, CurveGeometry) or (isinstance(m, DeviceGeometry) and m.kind == "curves")
@@ -571,12 +576,18 @@ class BVHAccel:
         return out
 
     def OccludedBatch(self, rays, options=None, skip_prim_ids=None):
-        """Opt-in extension: only the hit flags of TraverseBatch(), each ray stopping at the first primitive it accepts.
-        `skip_prim_ids`: as for TraverseBatch (nrtOccludedBatchSkip)."""
+        """Opt-in extension: only the hit flags of TraverseBatch() (0 / 1: `mask != 0` of it), each ray stopping at the first
+        primitive that settles it.  Sphere, cylinder and curve accels go through nrtOccludedBatchPrims_f32.
+        `skip_prim_ids`: as for TraverseBatch (nrtOccludedBatchSkip; triangle meshes only: raises on another kind)."""
         rays = np.ascontiguousarray(rays, dtype=ray_dtype(self.real))
         mask = np.zeros((rays.shape[0],), dtype=np.uint8)
         if options is not None:
             options = np.asarray(options, dtype=TRACE_OPTIONS).reshape(1)
+        if self._is_custom_kind():
+            if skip_prim_ids is not None:
+                raise ValueError("skip_prim_ids: triangle meshes only (the sphere, cylinder and curve intersectors have no skip id)")
+            self._check(self._L.nrtOccludedBatchPrims_f32(self._h, _p(rays), rays.shape[0], _p(options), _p(mask)))
+            return mask
         if skip_prim_ids is not None:
             ids = self._host_skip_ids(skip_prim_ids, rays.shape[0])
             self._check(getattr(self._L, "nrtOccludedBatchSkip_" + self._s)(self._h, _p(rays), rays.shape[0], _p(options), _p(ids), _p(mask)))
@@ -593,6 +604,11 @@ class BVHAccel:
             stream = torch.cuda.current_stream(self.device).cuda_stream
         if options is not None:
             options = np.asarray(options, dtype=TRACE_OPTIONS).reshape(1)
+        if self._is_custom_kind():  # (as OccludedBatch)
+            if skip_prim_ids is not None:
+                raise ValueError("skip_prim_ids: triangle meshes only (the sphere, cylinder and curve intersectors have no skip id)")
+            self._check(self._L.nrtOccludedBatchPrimsDevice_f32(self._h, d_rays.data_ptr(), n, _p(options), d_mask.data_ptr(), self._stream_handle(stream)))
+            return n
         if skip_prim_ids is not None:
             self._check(getattr(self._L, "nrtOccludedBatchSkipDevice_" + self._s)(self._h, d_rays.data_ptr(), n, _p(options),
                                                                                 self._device_skip_ids(skip_prim_ids, n), d_mask.data_ptr(),

@@ -31,6 +31,7 @@ SYMBOLS = [
     "nrtTraverseBatchMulti_f32", "nrtTraverseBatchMulti_f64", "nrtDeviceCount",
     "nrtTraverseCountDevice_f32", "nrtTraverseCountDevice_f64",
     "nrtOccludedBatch_f32", "nrtOccludedBatch_f64", "nrtOccludedBatchDevice_f32", "nrtOccludedBatchDevice_f64",
+    "nrtOccludedBatchPrims_f32", "nrtOccludedBatchPrimsDevice_f32",
     "nrtMultiHitTraverseBatch_f32", "nrtMultiHitTraverseBatch_f64", "nrtMultiHitTraverseBatchDevice_f32", "nrtMultiHitTraverseBatchDevice_f64",
     "nrtRefit_f32", "nrtRefit_f64", "nrtRefitDevice_f32", "nrtRefitDevice_f64",
     "nrtSetMeshDevice_f32", "nrtSetMeshDevice_f64", "nrtSetSpheresDevice_f32",
@@ -139,6 +140,10 @@ def lib():
         f = getattr(L, "nrtTraverseCountDevice_" + s)
         f.argtypes = [vp, vp, u64, vp, ctypes.POINTER(TraceCounters)]
         f.restype = i32
+    L.nrtOccludedBatchPrims_f32.argtypes = [vp, vp, u64, vp, vp]
+    L.nrtOccludedBatchPrims_f32.restype = i32
+    L.nrtOccludedBatchPrimsDevice_f32.argtypes = [vp, vp, u64, vp, vp, vp]
+    L.nrtOccludedBatchPrimsDevice_f32.restype = i32
     for sfx in ("f32", "f64"):
         f = getattr(L, "nrtOccludedBatch_" + sfx)
         f.argtypes = [vp, vp, u64, vp, vp]

@@ -1001,8 +1001,10 @@ struct TraverseBatches {
 };
 
 // What one traversal launch is asked for: the query kind says which of the outputs it reads.  (Occlusion: every ray stops at the
-// first primitive it accepts; Count: the literal kernel's counting pass into d_counters, no output of its own.)
-enum class Query { Closest, Occlusion, Count, MultiHit, Cylinders, MultiBatch, Curves };
+// first primitive it accepts; Count: the literal kernel's counting pass into d_counters, no output of its own; OcclusionPrims: the
+// occlusion query of nrtOccludedBatchPrims*, which every primitive kind takes — flags straight into the caller's mask, no compact
+// records, no post pass; on a triangle context it IS Occlusion: traverse_device says so under the lock.)
+enum class Query { Closest, Occlusion, Count, MultiHit, Cylinders, MultiBatch, Curves, OcclusionPrims };
 template <typename T>
 struct TraverseLaunch {
   Query kind;
@@ -1012,7 +1014,7 @@ struct TraverseLaunch {
   hipStream_t stream;
   bool timed = false; // bracket the launch with the slot's timing events (when it publishes no completion record)
   typename Wire<T>::Hit *hits = nullptr; // Closest (null: flags only); MultiHit: max_hits records per ray
-  uint8_t *mask = nullptr;               // Closest (may be null), Occlusion, Cylinders, Curves
+  uint8_t *mask = nullptr;               // Closest (may be null), Occlusion, OcclusionPrims, Cylinders, Curves
   void *cyl_hits = nullptr;              // Cylinders: 28-byte records, Curves: 40-byte records, written by the post pass
   uint32_t max_hits = 0;
   uint32_t *hit_counts = nullptr;        // MultiHit (may be null): one word per ray
@@ -1043,10 +1045,12 @@ static nrt_status validate_launch(nrt_ctx *c, const TraverseLaunch<T> &l) {
       for (uint32_t k = 0; k < l.batches->nb; k++) aligned = aligned && ((uintptr_t)l.batches->skip[k] & 3u) == 0u;
     if (!aligned) return fail(c, NRT_ERR_INVALID, "per-ray skip ids: the device array is not 4-byte aligned");
   }
-  if ((c->prim_kind == kPrimCylinders) != (l.kind == Query::Cylinders))
+  const bool prims = l.kind == Query::OcclusionPrims; // (a sphere, cylinder or curve context: traverse_device)
+  if (prims && !l.mask && l.n) return fail(c, NRT_ERR_INVALID, "nrtOccludedBatchPrims: NULL mask");
+  if (!prims && (c->prim_kind == kPrimCylinders) != (l.kind == Query::Cylinders))
     return fail(c, NRT_ERR_INVALID, "cylinder primitives are traced with nrtTraverseBatchCylinders*_f32 (28-byte records), "
                                     "every other primitive kind with nrtTraverseBatch*");
-  if ((c->prim_kind == kPrimCurves) != (l.kind == Query::Curves))
+  if (!prims && (c->prim_kind == kPrimCurves) != (l.kind == Query::Curves))
     return fail(c, NRT_ERR_INVALID, "curve primitives are traced with nrtTraverseBatchCurves*_f32 (40-byte records) and by nothing else, "
                                     "every other primitive kind by its own entry points");
   if (!c->d_nodes) return fail(c, NRT_ERR_INVALID, "nrtTraverseBatch: no tree (call nrtBuild or nrtSetTree)");
@@ -1155,7 +1159,7 @@ static void fill_walk_args(const nrt_ctx *c, const TraverseLaunch<T> &l, const W
   a.skip_prim = l.opt->skip_prim_id;
   a.skip_ids = l.skip_ids; // (MultiBatch: null, the table's skip_v instead)
   a.cull_back_face = l.opt->cull_back_face ? 1u : 0u;
-  a.any_hit = l.kind == Query::Occlusion ? 1u : 0u;
+  a.any_hit = (l.kind == Query::Occlusion || l.kind == Query::OcclusionPrims) ? 1u : 0u;
   a.plain_options = w.plain_options ? 1u : 0u;
   a.root_test = c->tree_nested ? 0u : 1u;
   a.order4 = (c->order4 && w.wide4() && c->prim_kind == kPrimTriangles && l.kind != Query::Occlusion && !profiled) ? 1u : 0u;
@@ -1232,7 +1236,10 @@ static nrt_status enqueue_launch(nrt_ctx *c, const TraverseLaunch<T> &l, const W
   // completion record instead of events: the traversal kernel is the launch's last kernel and events were not asked for
   const bool use_rec = w.wide() && !count && !c->launch_timing;
   // (the sphere kind's u/v pass and the cylinder kind's normal pass run behind the traversal kernel and close the record in its place)
-  const bool post_pass = kPrimKinds[c->prim_kind].post_pass && (c->prim_kind != kPrimSpheres || l.hits != nullptr); // (validate_launch: such a context takes its kind's own query only)
+  // (an occlusion query of these kinds has no records to finish: no pass, and the walk's last wave closes the record itself — left
+  // to a pass that never runs, wait_for_launches would poll it for ever)
+  const bool post_pass = kPrimKinds[c->prim_kind].post_pass && (c->prim_kind != kPrimSpheres || l.hits != nullptr) &&
+                         l.kind != Query::OcclusionPrims; // (validate_launch: such a context takes its kind's own query or that one only)
   a.done_rec = use_rec ? slot->d_done : nullptr;
   a.done_count = slot->d_count;
   a.done_seq = use_rec ? slot->seq + 1u : 0u;
@@ -1277,6 +1284,7 @@ template <typename T>
 static nrt_status traverse_device(nrt_ctx *c, TraverseLaunch<T> l) {
   if (!l.opt) l.opt = &kDefaultTrace;
   std::lock_guard<std::mutex> lock(c->launch_mutex);
+  if (l.kind == Query::OcclusionPrims && c->prim_kind == kPrimTriangles) l.kind = Query::Occlusion; // (the same launch, byte for byte)
   nrt_status st = validate_launch(c, l);
   if (st || l.n == 0) return st;
   HIPCHK(c, hipSetDevice(c->device));
@@ -1795,6 +1803,23 @@ nrt_status nrtOccludedBatchDevice_f32(nrt_ctx *c, const nrt_ray_f32 *r, uint64_t
   if (!c) return NRT_ERR_INVALID;
   if (n && !m) return fail(c, NRT_ERR_INVALID, "nrtOccludedBatchDevice: NULL mask");
   return traverse_device<float>(c, {.kind = Query::Occlusion, .rays = r, .n = n, .opt = o, .stream = (hipStream_t)s, .timed = true, .mask = m});
+}
+// Occlusion queries of whatever kind the context holds (include/nanort_hip.h, "occlusion queries for every primitive kind").
+nrt_status nrtOccludedBatchPrims_f32(nrt_ctx *c, const nrt_ray_f32 *rays, uint64_t n, const nrt_trace_options *opt, uint8_t *mask) {
+  if (!c) return NRT_ERR_INVALID;
+  if (n == 0) return NRT_OK;
+  if (!rays || !mask) return fail(c, NRT_ERR_INVALID, "nrtOccludedBatchPrims: NULL rays/mask");
+  std::lock_guard<std::mutex> host_lock(c->host_mutex);
+  HIPCHK(c, hipSetDevice(c->device));
+  return staged_host_loop<float>(c, rays, n, kStagedRays, 0, 1, nullptr, mask, [&](uint64_t m) -> TraverseLaunch<float> {
+    return {.kind = Query::OcclusionPrims, .rays = (const nrt_ray_f32 *)c->st_rays.p, .n = m, .opt = opt, .stream = c->stream, .timed = true,
+            .mask = (uint8_t *)c->st_mask.p};
+  });
+}
+nrt_status nrtOccludedBatchPrimsDevice_f32(nrt_ctx *c, const nrt_ray_f32 *r, uint64_t n, const nrt_trace_options *o, uint8_t *m, void *s) {
+  if (!c) return NRT_ERR_INVALID;
+  if (n && !m) return fail(c, NRT_ERR_INVALID, "nrtOccludedBatchPrimsDevice: NULL mask");
+  return traverse_device<float>(c, {.kind = Query::OcclusionPrims, .rays = r, .n = n, .opt = o, .stream = (hipStream_t)s, .timed = true, .mask = m});
 }
 nrt_status nrtOccludedBatchDevice_f64(nrt_ctx *c, const nrt_ray_f64 *r, uint64_t n, const nrt_trace_options *o, uint8_t *m, void *s) {
   if (!c) return NRT_ERR_INVALID;

@@ -324,7 +324,7 @@ __global__ __launch_bounds__(kTraverseBlock, (WIDTH == 4 && sizeof(T) == 4) ? NR
       mp_ = bp_.mask_v;                                 \
     }                                                   \
     if (hp_) store_hit_nt<T>(hp_ + rid, h_);            \
-    if (mp_) mp_[rid] = hit_ ? (KIND == kPrimCylinders ? (uint8_t)(1u | (L.cap << 1)) : (uint8_t)1) : (uint8_t)0; \
+    if (mp_) mp_[rid] = hit_ ? ((KIND == kPrimCylinders && !a.any_hit) ? (uint8_t)(1u | (L.cap << 1)) : (uint8_t)1) : (uint8_t)0; /* (an occlusion flag is 0 or 1: no cap bit) */ \
   } while (0)
 
   // The skip id of the ray a lane holds (`live_`: it holds one and waits at a leaf), into skip_: the launch's, or with per-ray skip
@@ -339,9 +339,31 @@ __global__ __launch_bounds__(kTraverseBlock, (WIDTH == 4 && sizeof(T) == 4) ? NR
   }                                                                                                    \
   (void)skip_
 
+  // Occlusion queries of the sphere, cylinder and curve kinds (api.hip, Query::OcclusionPrims: a.any_hit on these instantiations,
+  // flags into the caller's mask, no records).  A ray is SETTLED once `L.hit_t < L.max_t` — the very predicate NRT_WRITE_RESULT
+  // writes as the closest-hit flag, and nothing weaker.  A settled lane tests no further record of its leaf (NRT_RAY_OPEN in the
+  // record loops' `act_` and in their ballots: NRT_SPHERE_LOOP, NRT_RECORD_LOOP), a curve stops at its first accepted segment
+  // (curve_test), and the exit behind the leaf phase drops the stack.  Why the flag is the closest-hit call's, exactly:
+  //  * until a ray settles nothing here differs from the closest-hit walk: the bound of its box tests is still hit_t == max_t (or
+  //    the NaN an acceptance left), so its pops, steps and leaf tests are the same, in the same order, on the same operands;
+  //  * an acceptance that does not settle leaves the closest-hit flag 0 as well — a sphere accepted at t == max_t (`!(t > hit_t)`),
+  //    an acceptance that leaves a NaN — and the ray walks on, as there;
+  //  * a settled ray stays settled in the closest-hit walk: cylinders (`t <= tmax`, `pT < tmax`) and curves (`t < current`) accept
+  //    only smaller, ordered distances, so hit_t < max_t is final the moment it holds.  Spheres accept `!(t > hit_t)`: the same,
+  //    unless a LATER test yields a NaN distance (a NaN centre or radius, or an overflow inside the quadratic) — the closest-hit
+  //    call then ends on whatever it accepts last, the occlusion call has answered 1.  Finite spheres under finite rays, and rays
+  //    whose every test is NaN, agree exactly (include/nanort_hip.h says so);
+  //  * a cylinder that its tree names once per segment (tunable cyl_split) is a pure function of (ray, cylinder, current t):
+  //    skipping its repeats after the ray settled, or testing it again before, changes nothing.
+  // Any-hit only REMOVES tests; those that run keep their order.  The record loops of these kinds stand twice in the code, behind
+  // one wave-uniform branch (AH_ is the literal true or false): the closest-hit copy carries no trace of the predicate — measured
+  // with it folded into one loop, the closest-hit calls of the sphere and curve kinds ran 1 - 3 % slower than before.
+  const bool anyhit_ = KIND != kPrimTriangles && a.any_hit != 0u; // (wave-uniform)
+#define NRT_RAY_OPEN(AH_) (!((AH_) && L.hit_t < L.max_t))
+
   // One primitive record (slot `slot_` of the leaf-ordered arrays) against a lane's ray; `act_` false -> no effect.
   // (`skip` is the leaf phase's: NRT_RAY_SKIP)
-#define NRT_TEST_PRIM(slot_, act_)                                                                     \
+#define NRT_TEST_PRIM(slot_, act_, AH_)                                                                \
   do {                                                                                                 \
     if (KIND == kPrimSpheres) {                                                                        \
       const LeafSphere<T> sp_ = a.spheres[(slot_)];                                                    \
@@ -351,7 +373,7 @@ __global__ __launch_bounds__(kTraverseBlock, (WIDTH == 4 && sizeof(T) == 4) ? NR
       cylinder_test<T>(L, cy_, (act_), a.range0, a.range1, a.cyl_test_cap != 0u);                      \
     } else if constexpr (KIND == kPrimCurves) { /* (compile-time: no other instantiation sees it) */   \
       const LeafCurve cv_ = a.curves[(slot_)];                                                         \
-      curve_test<T>(L, cv_, (act_), a.range0, a.range1, a.curve_subdiv);                               \
+      curve_test<T>(L, cv_, (act_), a.range0, a.range1, a.curve_subdiv, (AH_));                        \
     } else {                                                                                           \
       const LeafTri<T> tri_ = a.tris[(slot_)];                                                         \
       if (PLAIN)                                                                                       \
@@ -360,6 +382,26 @@ __global__ __launch_bounds__(kTraverseBlock, (WIDTH == 4 && sizeof(T) == 4) ? NR
         tri_test<T>(L, tri_, (act_), a.range0, a.range1, skip, cull);                                  \
     }                                                                                                  \
   } while (0)
+
+  // The record loops of a leaf for the sphere kind (NRT_SPHERE_UNROLL records fetched per trip, all before any is tested) and for
+  // whatever has no loop of its own; AH_: the occlusion copy, which ends when no waiting lane has an unsettled record left.
+#define NRT_SPHERE_LOOP(AH_)                                                                                              \
+  for (uint32_t i = 0; __ballot(i < cnt && NRT_RAY_OPEN(AH_)) != 0ull; i += NRT_SPHERE_UNROLL) {                          \
+    LeafSphere<T> s_[NRT_SPHERE_UNROLL];                                                                                  \
+    _Pragma("unroll") for (uint32_t j = 0; j < NRT_SPHERE_UNROLL; j++) s_[j] = a.spheres[first + (i + j < cnt ? i + j : 0u)]; \
+    _Pragma("unroll") for (uint32_t j = 0; j < NRT_SPHERE_UNROLL; j++)                                                    \
+      sphere_test<T>(L, s_[j], i + j < cnt && NRT_RAY_OPEN(AH_), a.range0, a.range1);                                     \
+  }
+#define NRT_RECORD_LOOP(AH_)                                                                                              \
+  for (uint32_t i = 0; __ballot(i < cnt && NRT_RAY_OPEN(AH_)) != 0ull; i++) {                                             \
+    if (STATS) {                                                                                                          \
+      st_it2++;                                                                                                           \
+      st_act2 += (unsigned)__builtin_popcountll(__ballot(i < cnt));                                                       \
+      if (i < cnt) st_tris++;                                                                                             \
+    }                                                                                                                     \
+    /* no divergent region here: lanes past their count re-test their first record with ok = false */                    \
+    NRT_TEST_PRIM(first + (i < cnt ? i : 0u), i < cnt && NRT_RAY_OPEN(AH_), AH_);                                         \
+  }
 
   // (QUAD: the wave leaves the loop for the tail below; which of its lanes were idle then)
   bool to_tail = false;
@@ -597,22 +639,19 @@ __global__ __launch_bounds__(kTraverseBlock, (WIDTH == 4 && sizeof(T) == 4) ? NR
           }
         }
       } else if constexpr (!STATS && KIND == kPrimSpheres && NRT_SPHERE_UNROLL > 1) { // the same for the 20-byte sphere records
-        for (uint32_t i = 0; __ballot(i < cnt) != 0ull; i += NRT_SPHERE_UNROLL) {
-          LeafSphere<T> s_[NRT_SPHERE_UNROLL];
-#pragma unroll
-          for (uint32_t j = 0; j < NRT_SPHERE_UNROLL; j++) s_[j] = a.spheres[first + (i + j < cnt ? i + j : 0u)];
-#pragma unroll
-          for (uint32_t j = 0; j < NRT_SPHERE_UNROLL; j++) sphere_test<T>(L, s_[j], i + j < cnt, a.range0, a.range1);
+        if (anyhit_) {
+          NRT_SPHERE_LOOP(true)
+        } else {
+          NRT_SPHERE_LOOP(false)
         }
-      } else
-      for (uint32_t i = 0; __ballot(i < cnt) != 0ull; i++) {
-        if (STATS) {
-          st_it2++;
-          st_act2 += (unsigned)__builtin_popcountll(__ballot(i < cnt));
-          if (i < cnt) st_tris++;
+      } else if constexpr (KIND != kPrimTriangles) {
+        if (anyhit_) {
+          NRT_RECORD_LOOP(true)
+        } else {
+          NRT_RECORD_LOOP(false)
         }
-        // no divergent region here: lanes past their count re-test their first record with ok = false
-        NRT_TEST_PRIM(first + (i < cnt ? i : 0u), i < cnt);
+      } else {
+        NRT_RECORD_LOOP(false)
       }
       // occlusion query: any accepted primitive settles the ray — drop what is left of its stack
       if (a.any_hit | a.batch_anyhit) sp = (state == W_LEAF && L.hit_t < L.max_t && (a.any_hit != 0u || (L.pk & 512u) != 0u)) ? 0 : sp;
@@ -763,7 +802,10 @@ __global__ __launch_bounds__(kTraverseBlock, (WIDTH == 4 && sizeof(T) == 4) ? NR
   }
   if (rid != kInvalid) NRT_WRITE_RESULT(); // results still held in registers
 #undef NRT_WRITE_RESULT
+#undef NRT_RECORD_LOOP
+#undef NRT_SPHERE_LOOP
 #undef NRT_TEST_PRIM
+#undef NRT_RAY_OPEN
 #undef NRT_RAY_SKIP
 #undef NRT_CLOCK_LIVE
 #undef NRT_TAIL_N

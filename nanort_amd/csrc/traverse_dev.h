@@ -397,9 +397,9 @@ __device__ __forceinline__ void cylinder_test(Lane<T> &L, const LeafCylinder<T> 
 // segment are the lane's u, v: as there, they change exactly when a segment is accepted, and later segments see the lowered t.
 //
 // The frame (9 + 3 floats) depends on the ray alone.  It is RECOMPUTED here, at each leaf record, not carried in the lane across
-// the walk.  By register count: with the frame recomputed the two instantiations of this kind hold 111 (two levels per step) and
-// 107 (one level) VGPRs, no scratch, four waves per SIMD; twelve more registers live through the inner-node loop would put them at
-// 119 - 123 of the 128 that four waves allow, with nothing left before scratch or three waves.  The recomputation is one sqrt,
+// the walk.  By register count: with the frame recomputed the two instantiations of this kind hold 121 (two levels per step) and
+// 117 (one level) VGPRs (111 and 107 before the occlusion copy of the record loop, traverse.hip), no scratch, four waves per SIMD;
+// twelve more registers live through the inner-node loop would not fit the 128 that four waves allow, with nothing left before scratch or three waves.  The recomputation is one sqrt,
 // three divisions and a dozen multiplies in front of a test of 9 * (n + 1) interpolations, and the compiler is free to hoist it
 // out of a leaf's record loop.  It is a pure function of the ray and contraction is off: the values are those a stored frame holds.
 struct CurveFrame {
@@ -443,9 +443,12 @@ __device__ __forceinline__ float curve_bezier1(float v0, float v1, float v2, flo
   return b0 * u + b1 * t;
 }
 
+// `anyhit` (wave-uniform; occlusion queries, traverse.hip "SETTLED"): the segment loop of a lane ends at its first accepted segment —
+// later segments could only lower t, and `t < current` with current <= max_t has settled the ray — and neither sqrt(d2) nor the u
+// parameter is computed: u, v and prim of such a launch are never read.  The closest-hit loop is the one it always was.
 template <typename T>
 __device__ __forceinline__ void curve_test(Lane<T> &L, const LeafCurve &cv, bool active, uint32_t range0, uint32_t range1,
-                                           uint32_t subdiv) {
+                                           uint32_t subdiv, bool anyhit = false) {
   const uint32_t prim = cv.prim_id;
   bool ok = active & (prim >= range0) & (prim < range1);
   const CurveFrame f = curve_frame(L.org0, L.org1, L.org2, L.d0, L.d1, L.d2);
@@ -469,6 +472,27 @@ __device__ __forceinline__ void curve_test(Lane<T> &L, const LeafCurve &cv, bool
     // (segment s ends where segment s + 1 begins: (s + 1) / n is evaluated once)
     float p1x = curve_bezier1(x[0], x[1], x[2], x[3], 0.0f / fn), p1y = curve_bezier1(y[0], y[1], y[2], y[3], 0.0f / fn),
           p1z = curve_bezier1(z[0], z[1], z[2], z[3], 0.0f / fn);
+    if (anyhit) {
+      for (uint32_t s = 0; s < subdiv && !hit; s++) { // (the same segments in the same order, up to the first accepted one)
+        const float p0x = p1x, p0y = p1y, p0z = p1z;
+        const float t1 = (float)(int)(s + 1u) / fn;
+        p1x = curve_bezier1(x[0], x[1], x[2], x[3], t1);
+        p1y = curve_bezier1(y[0], y[1], y[2], y[3], t1);
+        p1z = curve_bezier1(z[0], z[1], z[2], z[3], t1);
+        const float ax = 0.0f - p0x, ay = 0.0f - p0y;
+        const float bx = p1x - p0x, by = p1y - p0y, bz = p1z - p0z;
+        const float d0 = (ax * bx) + (ay * by), d1 = (bx * bx) + (by * by);
+        float u = d0 / d1;
+        u = (u < 1.0f) ? u : 1.0f;
+        u = (0.0f < u) ? u : 0.0f;
+        const float qx = p0x + (u * bx), qy = p0y + (u * by), t = p0z + (u * bz), r = w0 + (u * bw);
+        const float r2 = r * r, d2 = (qx * qx) + (qy * qy);
+        hit = (d2 <= r2) & (t < cur);
+        cur = hit ? t : cur;
+      }
+      L.hit_t = cur;
+      return;
+    }
     for (uint32_t s = 0; s < subdiv; s++) {
       const float p0x = p1x, p0y = p1y, p0z = p1z;
       const float t1 = (float)(int)(s + 1u) / fn;
