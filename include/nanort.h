@@ -1366,42 +1366,10 @@ class BVHAccel {
       backend_error_ = "Refit: the mesh's faces differ from the ones the tree was built over";
       return false;
     }
-    if (SharesDeviceContext()) {  // copy-on-write: the copies keep the shared contexts, their tree and their positions
-      EnsureHostTree();
-      if (nodes_.empty()) {
-        backend_error_ = "Refit: empty tree";
-        return false;
-      }
-      if (!DetachDeviceContext(cyl_test_cap_)) return false;
-    }
-    if (!DeviceTreeReady(0)) return false;  // (a Load()ed tree is uploaded first)
-    // The primary first: its refusal leaves everything as it was (a device error drops its tree: Build() again).  The
-    // replicas pass the same checks, so only a device error can stop one: the object then traces on the primary alone, as
-    // after a replica's failed build, and never on a replica that still holds the old boxes.
-    if (Api::Refit(ctx_.get(), mesh.GetVertices(), mesh.GetVertexStrideBytes()) != NRT_OK) {
-      backend_error_ = nrtLastError(ctx_.get());
-      return false;
-    }
-    for (size_t k = 0; k < peers_.size(); k++) {
-      if (Api::Refit(peers_[k].get(), mesh.GetVertices(), mesh.GetVertexStrideBytes()) != NRT_OK) {
-        backend_error_ = nrtLastError(peers_[k].get());
-        fprintf(stderr, "[nanort] HIP refit of replica %zu failed (%s): tracing on one device\n", k + 1, backend_error_.c_str());
-        peers_.clear();
-        devices_.resize(1);
-        break;
-      }
-    }
+    if (!RefitContexts(0, [&](nrt_ctx *c) { return Api::Refit(c, mesh.GetVertices(), mesh.GetVertexStrideBytes()); })) return false;
     tri_vertices_ = mesh.GetVertices();  // (a later detach sends these)
     tri_stride_ = mesh.GetVertexStrideBytes();
-    uint64_t nn = 0, ni = 0;
-    if (nrtTreeSize(ctx_.get(), &nn, &ni) != NRT_OK || Api::TreeBounds(ctx_.get(), root_bmin_, root_bmax_) != NRT_OK) {
-      backend_error_ = nrtLastError(ctx_.get());
-      return false;
-    }
-    pending_nodes_ = nn;
-    pending_indices_ = ni;
-    __atomic_store_n(&host_tree_pending_, true, __ATOMIC_RELEASE);  // GetNodes(), Traverse(), Dump() and copies read the refit boxes
-    return true;
+    return RefitDone();
   }
   bool Refit(const SphereGeometry &) {
     backend_error_ = "Refit: sphere trees do not refit on the GPU (Build() again)";
@@ -1414,6 +1382,30 @@ class BVHAccel {
   bool Refit(const BezierCurveGeometry &) {
     backend_error_ = "Refit: curve trees do not refit on the GPU (Build() again)";
     return false;
+  }
+  // The GPU refit of a sphere or curve accel (nrtRefitPrims, include/nanort_hip.h) from the geometry's arrays, as Refit(TriangleMesh)
+  // for a mesh: every context this object holds, after a copy-on-write detach when they are shared with copies; the new arrays
+  // are kept as Build() keeps its own (they must outlive the accel).  The geometry carries no count: `num_primitives`, when
+  // given, must be the count of the Build().  False with a reason (LastBackendError()) when the object holds another kind or count.
+  bool RefitGeometry(const SphereGeometry &geom, unsigned int num_primitives = ~0u) {
+    std::lock_guard<std::mutex> lock(batch_mutex_);
+    const float *centers = geom.GetCenters(), *radii = geom.GetRadii();
+    if (!HoldsKind("RefitGeometry(SphereGeometry)", 1, num_primitives) ||
+        !RefitContexts(1, [&](nrt_ctx *c) { return nrtRefitPrims_f32(c, centers, radii, prim_count_); }))
+      return false;
+    sph_centers_ = centers;  // (a later detach sends these)
+    sph_radii_ = radii;
+    return RefitDone();
+  }
+  bool RefitGeometry(const BezierCurveGeometry &geom, unsigned int num_primitives = ~0u) {
+    std::lock_guard<std::mutex> lock(batch_mutex_);
+    const float *cps = geom.GetControlPoints(), *radii = geom.GetRadii();
+    if (!HoldsKind("RefitGeometry(BezierCurveGeometry)", 3, num_primitives) ||
+        !RefitContexts(3, [&](nrt_ctx *c) { return nrtRefitPrims_f32(c, cps, radii, prim_count_); }))
+      return false;
+    crv_cps_ = cps;
+    crv_radii_ = radii;
+    return RefitDone();
   }
 #endif
 
@@ -1994,6 +1986,62 @@ class BVHAccel {
     typedef detail::HipApi<T> Api;
     if (ids) return Api::TraverseSkipDevice(c, reinterpret_cast<const typename Api::RayPod *>(r), n, o, ids, reinterpret_cast<typename Api::HitPod *>(h), m, stream);
     return Api::TraverseDevice(c, reinterpret_cast<const typename Api::RayPod *>(r), n, o, reinterpret_cast<typename Api::HitPod *>(h), m, stream);
+  }
+  // What a GPU refit does around the call that is its own (caller holds batch_mutex_; `kind` is the object's device_prim_kind_):
+  // an object that shares its contexts with copies first moves to contexts of its own, a Load()ed tree is uploaded, then
+  // `refit_ctx` runs on the primary and on every replica.
+  template <class RefitCtx>
+  bool RefitContexts(int kind, RefitCtx refit_ctx) {
+    if (SharesDeviceContext()) {  // copy-on-write: the copies keep the shared contexts, their tree and their positions
+      EnsureHostTree();
+      if (nodes_.empty()) {
+        backend_error_ = "Refit: empty tree";
+        return false;
+      }
+      if (!DetachDeviceContext(cyl_test_cap_)) return false;
+    }
+    if (!DeviceTreeReady(kind)) return false;  // (a Load()ed tree is uploaded first)
+    // The primary first: its refusal leaves everything as it was (a device error drops its tree: Build() again).  The
+    // replicas pass the same checks, so only a device error can stop one: the object then traces on the primary alone, as
+    // after a replica's failed build, and never on a replica that still holds the old boxes.
+    if (refit_ctx(ctx_.get()) != NRT_OK) {
+      backend_error_ = nrtLastError(ctx_.get());
+      return false;
+    }
+    for (size_t k = 0; k < peers_.size(); k++) {
+      if (refit_ctx(peers_[k].get()) != NRT_OK) {
+        backend_error_ = nrtLastError(peers_[k].get());
+        fprintf(stderr, "[nanort] HIP refit of replica %zu failed (%s): tracing on one device\n", k + 1, backend_error_.c_str());
+        peers_.clear();
+        devices_.resize(1);
+        break;
+      }
+    }
+    return true;
+  }
+  // ... and behind it: the root's box, and the host copy of the tree is read back on the next host access.
+  bool RefitDone() {
+    uint64_t nn = 0, ni = 0;
+    if (nrtTreeSize(ctx_.get(), &nn, &ni) != NRT_OK || detail::HipApi<T>::TreeBounds(ctx_.get(), root_bmin_, root_bmax_) != NRT_OK) {
+      backend_error_ = nrtLastError(ctx_.get());
+      return false;
+    }
+    pending_nodes_ = nn;
+    pending_indices_ = ni;
+    __atomic_store_n(&host_tree_pending_, true, __ATOMIC_RELEASE);  // GetNodes(), Traverse(), Dump() and copies read the refit boxes
+    return true;
+  }
+  // RefitGeometry: the object was built on the GPU over `kind` (1 spheres, 3 curves) and, when a count is given, over that many.
+  bool HoldsKind(const char *who, int kind, unsigned int num_primitives) {
+    if (!ctx_ || device_prim_kind_ != kind) {
+      backend_error_ = std::string(who) + (kind == 1 ? ": this accel was not built on the GPU over a SphereGeometry" : ": this accel was not built on the GPU over a BezierCurveGeometry");
+      return false;
+    }
+    if (num_primitives != ~0u && num_primitives != prim_count_) {
+      backend_error_ = std::string(who) + ": the tree was built over another number of primitives";
+      return false;
+    }
+    return true;
   }
   // The checks every host batch call makes (caller holds batch_mutex_): a context, the primitive kind the call's records are
   // for (0 triangles, 1 spheres), and a tree adopted by Load() uploaded — after a copy-on-write detach when the contexts are

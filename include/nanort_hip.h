@@ -437,6 +437,37 @@ NRT_API nrt_status nrtRefit_f64(nrt_ctx *ctx, const double *vertices, size_t ver
 NRT_API nrt_status nrtRefitDevice_f32(nrt_ctx *ctx, const float *d_vertices, size_t vertex_stride_bytes, void *hip_stream);
 NRT_API nrt_status nrtRefitDevice_f64(nrt_ctx *ctx, const double *d_vertices, size_t vertex_stride_bytes, void *hip_stream);
 
+/* ---- refit of spheres and curves: the tree's boxes recomputed from moved primitives, its topology kept -------
+ * For particles that move and hair that is combed: instead of nrtSetSpheres[Device] / nrtSetCurves[Device] + nrtBuild every
+ * frame.  Contract, on a sphere or curve context (fp32) that holds a tree (from nrtBuild_f32 or nrtSetTree_f32):
+ *   1. Input: tight arrays in the layout of the kind's setter.  Spheres: `positions` 3 floats and `radii` 1 float per sphere;
+ *      curves: `positions` 12 floats (four control points) and `radii` 4 floats per curve.  radii == NULL keeps the context's
+ *      radii (particles that move at a fixed size).  `num_prims` is a guard: it must equal the count the context was set with.
+ *   2. Result: the context's positions (and radii, if given) become the new ones (a later nrtBuild builds over them).  Every
+ *      node record's flag, axis and data[] and the index array stay byte-identical.  Each reachable leaf's box is the min / max
+ *      over its slots, in slot order, of the primitive's box as the builder computes it — sphere: centre -/+ radius; curve:
+ *      min / max over the four `control point -/+ its radius` — so a refit with the arrays of the build reproduces the build's
+ *      boxes.  Each reachable branch's box is the min / max of its two children's; an empty leaf (adopted trees only) gets
+ *      {+max, -max}; records the walk from the root never reaches are left untouched.  The leaf records and the private node
+ *      arrays of the traversal are derived again as after a build.  num_subdivisions, build statistics and nrtLastBuildMs do
+ *      not change.  Inputs that are not finite are outside the box contract: the boxes of a leaf that holds a NaN or an
+ *      infinity, and of its ancestors, are unspecified (nothing is read or written out of bounds).
+ *   3. A committed nrt_scene that instances this context refuses to trace until it is committed again, as after nrtRefit.
+ *   4. Ordering: exactly that of nrtRefit_* / nrtRefitDevice_*.  Both forms first wait on the host for the context's launches
+ *      in flight.  nrtRefitPrims_f32 returns when the refit is complete.  nrtRefitPrimsDevice_f32 copies the caller's device
+ *      arrays into the context's own buffers and enqueues everything on `hip_stream` (a hipStream_t; NULL = the default stream)
+ *      and returns without synchronising: the caller keeps the arrays unchanged until the stream reaches the refit.  Every
+ *      traversal call issued after a refit, on any stream and through any entry point, is ordered after it.
+ *   5. Cost: as nrtRefit — the first refit of a tree builds its level plan; in the steady state a refit allocates nothing.
+ * Refusals write nothing (nrtLastError gives the reason): NRT_ERR_INVALID for a NULL context or NULL positions, no tree (a
+ * fresh context included), a triangle context (use nrtRefit_*), a cylinder context (its tree is built over segments the
+ * builder cut the cylinders into, and they are not recoverable from the index array), num_prims different from the context's
+ * count, and (Device form) a pointer not aligned to 4 bytes; NRT_ERR_PRECISION for a context that holds fp64 primitives.
+ * NRT_ERR_DEVICE (a HIP error once the rewrite has started): the context drops its tree and its primitives, as nrtRefit does. */
+NRT_API nrt_status nrtRefitPrims_f32(nrt_ctx *ctx, const float *positions, const float *radii, uint32_t num_prims);
+NRT_API nrt_status nrtRefitPrimsDevice_f32(nrt_ctx *ctx, const float *d_positions, const float *d_radii, uint32_t num_prims,
+                                           void *hip_stream);
+
 /* ---- device-resident geometry: nrtSetMesh_* / nrtSetSpheres_f32 for arrays that are already in HBM ------------------
  * For a mesh or a particle set produced on the GPU (a tensor, a simulation, a remesher): no copy to the host and back.
  * Contract:

@@ -419,6 +419,55 @@ class BVHAccel:
         stride = d_vertices.stride(0) * d_vertices.element_size()
         self._check(getattr(self._L, "nrtRefitDevice_" + self._s)(self._h, d_vertices.data_ptr(), stride, stream))
 
+    def _refit_prims_layout(self):
+        """(count, position floats, radius floats per primitive) of the spheres or curves last set, or None when the accel holds
+        another kind (the library then refuses the refit, with the reason)."""
+        m = self._mesh
+        if isinstance(m, SphereGeometry) or (isinstance(m, DeviceGeometry) and m.kind == "spheres"):
+            return m.num_faces, 3, 1
+        if self._is_curves():
+            return m.num_faces, 12, 4
+        return None
+
+    def _refit_prims_checked(self, positions, radii, numel):
+        """The shapes of RefitPrims / RefitPrimsDevice against the kind and count, before the library is called: `numel` gives
+        an array's element count.  Returns the primitive count to pass (0 when the accel holds another kind: the library refuses)."""
+        lay = self._refit_prims_layout()
+        if lay is None:
+            return 0
+        n, pf, rf = lay
+        if numel(positions) != pf * n:
+            raise ValueError("positions hold %d floats; %d primitives need %d" % (numel(positions), n, pf * n))
+        if radii is not None and numel(radii) != rf * n:
+            raise ValueError("radii hold %d floats; %d primitives need %d" % (numel(radii), n, rf * n))
+        return n
+
+    def RefitPrims(self, positions, radii=None):
+        """New positions (and radii) for the spheres or curves last set, same count and topology (include/nanort_hip.h,
+        nrtRefitPrims): the tree's boxes are recomputed bottom-up.  `positions`: float32, [n, 3] centres or [n, 4, 3] control
+        points; `radii`: [n] or [n, 4], or None to keep the accel's radii."""
+        p = np.ascontiguousarray(positions, dtype=np.float32)
+        r = None if radii is None else np.ascontiguousarray(radii, dtype=np.float32)
+        n = self._refit_prims_checked(p, r, lambda a: a.size)
+        self._check(self._L.nrtRefitPrims_f32(self._h, _p(p), _p(r), n))
+
+    def RefitPrimsDevice(self, d_positions, d_radii=None, stream=None):
+        """RefitPrims from torch float32 tensors on the accel's device, contiguous (nrtRefitPrimsDevice).  Asynchronous on `stream`
+        (default: torch's current stream); keep the tensors unchanged until the stream reaches the refit."""
+        import torch
+
+        for t, what in ((d_positions, "positions"), (d_radii, "radii")):
+            if t is None:
+                continue
+            if t.dtype != torch.float32:
+                raise TypeError("%s must be torch.float32" % what)
+            if not t.is_contiguous():
+                raise ValueError("%s must be contiguous" % what)
+            self._on_device(t, what)
+        n = self._refit_prims_checked(d_positions, d_radii, lambda t: t.numel())
+        self._check(self._L.nrtRefitPrimsDevice_f32(self._h, d_positions.data_ptr(), None if d_radii is None else d_radii.data_ptr(), n,
+                                                    self._stream_handle(stream)))
+
     # -- traverse -----------------------------------------------------------
     @staticmethod
     def _host_skip_ids(skip_prim_ids, n):

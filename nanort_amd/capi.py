@@ -33,7 +33,7 @@ SYMBOLS = [
     "nrtOccludedBatch_f32", "nrtOccludedBatch_f64", "nrtOccludedBatchDevice_f32", "nrtOccludedBatchDevice_f64",
     "nrtOccludedBatchPrims_f32", "nrtOccludedBatchPrimsDevice_f32",
     "nrtMultiHitTraverseBatch_f32", "nrtMultiHitTraverseBatch_f64", "nrtMultiHitTraverseBatchDevice_f32", "nrtMultiHitTraverseBatchDevice_f64",
-    "nrtRefit_f32", "nrtRefit_f64", "nrtRefitDevice_f32", "nrtRefitDevice_f64",
+    "nrtRefit_f32", "nrtRefit_f64", "nrtRefitDevice_f32", "nrtRefitDevice_f64", "nrtRefitPrims_f32", "nrtRefitPrimsDevice_f32",
     "nrtSetMeshDevice_f32", "nrtSetMeshDevice_f64", "nrtSetSpheresDevice_f32",
     "nrtLastTraverseMs", "nrtSetLaunchTiming", "nrtSetTunable", "nrtGetTunable", "nrtLastBuildMs", "nrtLastKernelName", "nrtHostAlloc", "nrtHostFree",
     "nrtGroupUniqueId", "nrtGroupCreate", "nrtGroupCreateRanked", "nrtGroupDestroy", "nrtGroupLastError", "nrtGroupSetTunable", "nrtGroupInfo",
@@ -166,6 +166,10 @@ def lib():
         f = getattr(L, "nrtSetMeshDevice_" + sfx)
         f.argtypes = [vp, vp, u32, sz, vp, u32, vp]
         f.restype = i32
+    L.nrtRefitPrims_f32.argtypes = [vp, vp, vp, u32]
+    L.nrtRefitPrims_f32.restype = i32
+    L.nrtRefitPrimsDevice_f32.argtypes = [vp, vp, vp, u32, vp]
+    L.nrtRefitPrimsDevice_f32.restype = i32
     L.nrtSetSpheres_f32.argtypes = [vp, vp, vp, u32]
     L.nrtSetSpheres_f32.restype = i32
     L.nrtSetSpheresDevice_f32.argtypes = [vp, vp, vp, u32, vp]

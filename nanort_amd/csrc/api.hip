@@ -897,6 +897,41 @@ static nrt_status build(nrt_ctx *c, const typename Wire<T>::BuildOptions *opt, n
 // ---------------------------------------------------------------------------
 // refit (refit.hip): new vertex positions, the same topology
 // ---------------------------------------------------------------------------
+// The level plan of the current tree, built on the device by the first refit after the tree changed (the tree is only read).
+template <typename T>
+static nrt_status refit_plan(nrt_ctx *c, hipStream_t s) {
+  if (c->refit_planned) return NRT_OK;
+  if (nrt_status st = ensure(c, c->b_refit_plan, refit_plan_bytes(c->tree_depth, c->num_nodes))) return st;
+  HIPCHK(c, launch_refit_plan<T>((const typename Wire<T>::Node *)c->d_nodes, c->num_nodes, c->num_branch_records, c->tree_depth,
+                                 c->root_is_branch, (uint32_t *)c->b_refit_plan.p, s));
+  c->refit_planned = true;
+  return NRT_OK;
+}
+
+// What follows the new boxes (`e`: how their launches went): the leaf records and WideNode / Wide4Node arrays from the new boxes
+// and positions, as a build derives them; then the host form waits, the Device form records ev_refit.  A device error leaves no
+// half-refit tree behind: the context drops its tree and its primitives, and the message ends in `remedy`.
+template <typename T>
+static nrt_status refit_finish(nrt_ctx *c, const char *fn, hipError_t e, bool device, hipStream_t s, const char *remedy) {
+  nrt_status st = NRT_OK;
+  c->tree_nested = 1; // every box now lies inside its parent's
+  if (e == hipSuccess && (st = finish_tree<T>(c, s))) e = hipErrorUnknown;
+  if (e == hipSuccess && !device) e = hipStreamSynchronize(s);
+  if (e == hipSuccess && device) {
+    std::lock_guard<std::mutex> lock(c->launch_mutex);
+    if ((e = hipEventRecord(c->ev_refit, s)) == hipSuccess) c->refit_pending = true;
+  }
+  if (e != hipSuccess) {
+    const std::string why = st ? c->err : std::string(hipGetErrorString(e));
+    (void)hipStreamSynchronize(s);
+    free_tree(c);
+    free_mesh(c);
+    return fail(c, NRT_ERR_DEVICE, "%s: %s (the context's tree and primitives were dropped: %s)", fn, why.c_str(), remedy);
+  }
+  c->generation++; // a committed nrt_scene over this context holds stale top-level boxes: it refuses until committed again
+  return NRT_OK;
+}
+
 // `device`: `vertices` is device memory read by the gather kernel, and the call returns once everything is enqueued on `s`;
 // else the caller's vertex block is uploaded into b_refit_stage first and the call returns when the refit is complete.
 template <typename T>
@@ -925,34 +960,46 @@ static nrt_status refit(nrt_ctx *c, const T *vertices, size_t stride, bool devic
     HIPCHK(c, hipMemcpyAsync(c->b_refit_stage.p, vertices, block, hipMemcpyHostToDevice, s));
     src = c->b_refit_stage.p;
   }
-  if (!c->refit_planned) { // (first refit of this tree: its level plan, on the device; the tree is only read)
-    if ((st = ensure(c, c->b_refit_plan, refit_plan_bytes(c->tree_depth, c->num_nodes)))) return st;
-    HIPCHK(c, launch_refit_plan<T>((const typename Wire<T>::Node *)c->d_nodes, c->num_nodes, c->num_branch_records, c->tree_depth,
-                                   c->root_is_branch, (uint32_t *)c->b_refit_plan.p, s));
-    c->refit_planned = true;
-  }
+  if ((st = refit_plan<T>(c, s))) return st;
   // From here on the vertices, the boxes and the leaf / wide records are being rewritten: a device error leaves no half-refit
   // tree behind — the context drops its tree and its primitives (free_tree bumps generation), as a failed build drops its tree.
-  hipError_t e = launch_refit<T>(src, stride, nv, (T *)c->d_verts, c->d_faces, c->d_indices,
-                                 (typename Wire<T>::Node *)c->d_nodes, c->num_nodes, c->num_branch_records, c->tree_depth,
-                                 (const uint32_t *)c->b_refit_plan.p, s);
-  // LeafTri / WideNode / Wide4Node from the new boxes and positions, as a build derives them; every box now lies inside its parent's
-  c->tree_nested = 1;
-  if (e == hipSuccess && (st = finish_tree<T>(c, s))) e = hipErrorUnknown;
-  if (e == hipSuccess && !device) e = hipStreamSynchronize(s);
-  if (e == hipSuccess && device) {
-    std::lock_guard<std::mutex> lock(c->launch_mutex);
-    if ((e = hipEventRecord(c->ev_refit, s)) == hipSuccess) c->refit_pending = true;
-  }
-  if (e != hipSuccess) {
-    const std::string why = st ? c->err : std::string(hipGetErrorString(e));
-    (void)hipStreamSynchronize(s);
-    free_tree(c);
-    free_mesh(c);
-    return fail(c, NRT_ERR_DEVICE, "%s: %s (the context's tree and primitives were dropped: set the mesh again)", fn, why.c_str());
-  }
-  c->generation++; // a committed nrt_scene over this context holds stale top-level boxes: it refuses until committed again
-  return NRT_OK;
+  const hipError_t e = launch_refit<T>(src, stride, nv, (T *)c->d_verts, c->d_faces, c->d_indices,
+                                       (typename Wire<T>::Node *)c->d_nodes, c->num_nodes, c->num_branch_records, c->tree_depth,
+                                       (const uint32_t *)c->b_refit_plan.p, s);
+  return refit_finish<T>(c, fn, e, device, s, "set the mesh again");
+}
+
+// nrtRefitPrims* (spheres and curves): the context's positions (and radii, when given) replaced by the caller's tight arrays, then
+// the boxes from them by the kind's builder rule.  `device`: the arrays are device memory copied on `s`, and the call returns once
+// everything is enqueued there; else the call returns when the refit is complete.
+static nrt_status refit_prims(nrt_ctx *c, const float *positions, const float *radii, uint32_t n, bool device, hipStream_t s) {
+  const char *fn = device ? "nrtRefitPrimsDevice" : "nrtRefitPrims";
+  if (!c) return NRT_ERR_INVALID;
+  if (!positions) return fail(c, NRT_ERR_INVALID, "%s: NULL positions", fn);
+  if (c->prec == 8) return fail(c, NRT_ERR_PRECISION, "%s: the context holds f64 primitives", fn);
+  if (c->prec != 0 && c->prim_kind == kPrimTriangles)
+    return fail(c, NRT_ERR_INVALID, "%s: this context holds triangles: refit a mesh with nrtRefit / nrtRefitDevice", fn);
+  if (c->prec != 0 && c->prim_kind == kPrimCylinders)
+    return fail(c, NRT_ERR_INVALID, "%s: cylinders do not refit: the tree is built over segments the builder cut them into, and which "
+                "cylinder end a slot of the index array stands for is not recoverable from it (nrtSetCylinders + nrtBuild again)", fn);
+  if (!c->d_nodes) return fail(c, NRT_ERR_INVALID, "%s: no tree (call nrtBuild or nrtSetTree)", fn);
+  const PrimKind &k = kPrimKinds[c->prim_kind];
+  if (n != c->num_faces) return fail(c, NRT_ERR_INVALID, "%s: num_prims %u differs from the context's %u %s", fn, n, c->num_faces, k.name);
+  if (device && ((uintptr_t)positions % sizeof(float) != 0 || (uintptr_t)radii % sizeof(float) != 0))
+    return fail(c, NRT_ERR_INVALID, "%s: pointer not aligned to 4 bytes", fn);
+  NRT_RANGE("nrtRefitPrims");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, wait_for_launches(c)); // (launches in flight read the arrays the refit rewrites; also a previous Device refit)
+  if (!device) s = c->stream;
+  if (nrt_status st = refit_plan<float>(c, s)) return st;
+  // From here on the context's arrays are being rewritten (refit_finish: a device error drops the tree and the primitives).
+  const hipMemcpyKind dir = device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+  hipError_t e = hipMemcpyAsync(c->d_verts, positions, (size_t)k.pos_floats * n * sizeof(float), dir, s);
+  if (e == hipSuccess && radii) e = hipMemcpyAsync(c->d_radii, radii, (size_t)k.radius_floats * n * sizeof(float), dir, s);
+  if (e == hipSuccess)
+    e = launch_refit_prims(c->prim_kind, (const float *)c->d_verts, (const float *)c->d_radii, c->d_indices, (nrt_node_f32 *)c->d_nodes, c->num_nodes,
+                           c->num_branch_records, c->tree_depth, (const uint32_t *)c->b_refit_plan.p, s);
+  return refit_finish<float>(c, fn, e, device, s, "set the primitives again");
 }
 
 // Library-internal (scene.hip): where a built fp32 context keeps its tree on the device.  Waits for the context's own
@@ -1732,6 +1779,8 @@ nrt_status nrtRefit_f32(nrt_ctx *c, const float *v, size_t stride) { return refi
 nrt_status nrtRefit_f64(nrt_ctx *c, const double *v, size_t stride) { return refit<double>(c, v, stride, false, nullptr); }
 nrt_status nrtRefitDevice_f32(nrt_ctx *c, const float *v, size_t stride, void *s) { return refit<float>(c, v, stride, true, (hipStream_t)s); }
 nrt_status nrtRefitDevice_f64(nrt_ctx *c, const double *v, size_t stride, void *s) { return refit<double>(c, v, stride, true, (hipStream_t)s); }
+nrt_status nrtRefitPrims_f32(nrt_ctx *c, const float *p, const float *r, uint32_t n) { return refit_prims(c, p, r, n, false, nullptr); }
+nrt_status nrtRefitPrimsDevice_f32(nrt_ctx *c, const float *p, const float *r, uint32_t n, void *s) { return refit_prims(c, p, r, n, true, (hipStream_t)s); }
 
 nrt_status nrtSetMesh_f32(nrt_ctx *c, const float *v, size_t stride, const uint32_t *f, uint32_t nf) {
   return set_mesh<float>(c, v, stride, f, nf);

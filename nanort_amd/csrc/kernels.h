@@ -90,6 +90,9 @@ template <typename T>
 hipError_t launch_refit(const void *src, size_t stride, uint32_t nv, T *verts, const uint32_t *faces, const uint32_t *indices,
                         typename Wire<T>::Node *nodes, uint64_t num_nodes, uint32_t num_branch_records, uint32_t tree_depth,
                         const uint32_t *plan, hipStream_t s);
+// the same for spheres and curves (fp32): the boxes from the context's positions and radii, already the new ones
+hipError_t launch_refit_prims(int kind, const float *verts, const float *radii, const uint32_t *indices, nrt_node_f32 *nodes, uint64_t num_nodes,
+                              uint32_t num_branch_records, uint32_t tree_depth, const uint32_t *plan, hipStream_t s);
 
 // ---- prims.hip: per primitive kind (prim_kinds.h), outside the walk ------------------------------------------------------
 // the largest of `n_indices` u32 (4-byte aligned, any length) into *out (device), 0 for none
