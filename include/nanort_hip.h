@@ -715,8 +715,8 @@ NRT_API nrt_status nrtSetLaunchTiming(nrt_ctx *ctx, int on);
  *                     "static_pct", "static_bands", "static_slice_groups", "blocks_per_cu", "lds_stack", "wide_stack"
  *   builder           "morton" (Morton pre-pass); libnanort_hip_prof.so only: "subtree_rows" (0: the one-node-per-step subtree kernel; same tree)
  *   launches / host   "launch_timing" (== nrtSetLaunchTiming), "host_pipeline"
- *   probes            "debug" (bit mask: 1 / 2 skip triangle tests / traversal, 4 plain ray loads; the profiling bits 32 / 64 / 8192
- *                     act in libnanort_hip_prof.so only), "wide_scramble" (layout probe; next build)
+ *   probes            "debug" (bit mask: 1 / 2 skip triangle tests / traversal; the profiling bits 4 — non-temporal ray loads —,
+ *                     32 / 64 / 8192 act in libnanort_hip_prof.so only), "wide_scramble" (layout probe; next build)
  * Values are clamped to the tunable's range; an unknown name is NRT_ERR_INVALID.  Tunables that shape the private tree layout
  * ("wide4", "wide_scramble", "morton") take effect with the next nrtBuild / nrtSetTree.  The environment variable
  * NRT_<NAME> (upper case) overrides a default at nrtCreate ONLY when the process also sets NRT_ALLOW_ENV=1 (libnanort_hip_prof.so:

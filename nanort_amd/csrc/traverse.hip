@@ -88,7 +88,7 @@ __global__ __launch_bounds__(kTraverseBlock) void k_traverse(const TraverseArgs<
         const unsigned rank = (unsigned)__builtin_popcountll(idle & ((1ull << lane) - 1ull));
         if (state == LANE_IDLE && rank < take) {
           rid = ck.next + rank;
-          const Ray r = (a.debug_flags & 4u) ? a.rays[rid] : load_ray_nt<T>(a.rays + rid);
+          const Ray r = load_ray<T>(as_global(a.rays) + rid, a.debug_flags);
           lane_init<T>(L, r);
           cur = 0;
           sp = 0;
@@ -316,12 +316,12 @@ __global__ __launch_bounds__(kTraverseBlock, (WIDTH == 4 && sizeof(T) == 4) ? NR
     }                                                   \
     h_.t = hit_ ? L.hit_t : L.max_t;                    \
     h_.prim_id = hit_ ? L.prim : kInvalid;              \
-    Hit *hp_ = a.hits;                                  \
-    uint8_t *mp_ = a.mask;                              \
+    Hit NRT_GLOBAL *hp_ = as_global(a.hits);            \
+    uint8_t NRT_GLOBAL *mp_ = as_global(a.mask);        \
     if (multi) {                                        \
       const BatchPtrs bp_ = s_tbl[batch_of<T>(a, rid)]; \
-      hp_ = (Hit *)bp_.hits_v;                          \
-      mp_ = bp_.mask_v;                                 \
+      hp_ = as_global((Hit *)bp_.hits_v);               \
+      mp_ = as_global(bp_.mask_v);                      \
     }                                                   \
     if (hp_) store_hit_nt<T>(hp_ + rid, h_);            \
     if (mp_) mp_[rid] = hit_ ? ((KIND == kPrimCylinders && !a.any_hit) ? (uint8_t)(1u | (L.cap << 1)) : (uint8_t)1) : (uint8_t)0; /* (an occlusion flag is 0 or 1: no cap bit) */ \
@@ -333,8 +333,8 @@ __global__ __launch_bounds__(kTraverseBlock, (WIDTH == 4 && sizeof(T) == 4) ? NR
 #define NRT_RAY_SKIP(skip_, live_)                                                                     \
   uint32_t skip_ = a.skip_prim;                                                                        \
   if constexpr (!PLAIN && KIND == kPrimTriangles) {                                                    \
-    const uint32_t *ids_ = a.skip_ids;                                                                 \
-    if (multi) ids_ = s_tbl[batch_of<T>(a, rid)].skip_v;                                               \
+    const uint32_t NRT_GLOBAL *ids_ = as_global(a.skip_ids);                                           \
+    if (multi) ids_ = as_global(s_tbl[batch_of<T>(a, rid)].skip_v);                                    \
     if ((live_) && ids_ != nullptr) skip_ = ids_[rid];                                                 \
   }                                                                                                    \
   (void)skip_
@@ -422,14 +422,14 @@ __global__ __launch_bounds__(kTraverseBlock, (WIDTH == 4 && sizeof(T) == 4) ? NR
         if (state == W_IDLE && rank < take) {
           if (rid != kInvalid) NRT_WRITE_RESULT();
           rid = ck.next + rank;
-          const Ray *rp_ = a.rays;
+          const Ray NRT_GLOBAL *rp_ = as_global(a.rays);
           uint32_t bq_ = 0u; // this ray belongs to an occlusion-query batch
           if (multi) {
             const uint32_t b_ = batch_of<T>(a, rid);
-            rp_ = (const Ray *)s_tbl[b_].rays_v;
+            rp_ = as_global((const Ray *)s_tbl[b_].rays_v);
             bq_ = (a.batch_anyhit >> b_) & 1u;
           }
-          const Ray r = (a.debug_flags & 4u) ? rp_[rid] : load_ray_nt<T>(rp_ + rid);
+          const Ray r = load_ray<T>(rp_ + rid, a.debug_flags);
           lane_init<T>(L, r);
           L.pk |= bq_ << 9;
           sp = 0;

@@ -654,7 +654,8 @@ __device__ __forceinline__ bool claim_chunk(const TraverseArgs<T> &a, Claim &c, 
 }
 
 // Streaming accesses (each ray is read once, each hit written once): keep them out of the
-// way of the tree data in L2 with the non-temporal hint.
+// way of the tree data in L2 with the non-temporal hint.  (The hit stores of every walk; the ray loads of the multi-hit walk only:
+// k_traverse and k_traverse_wide measured slower with it — load_ray below.)
 template <typename T>
 __device__ __forceinline__ typename Wire<T>::Ray load_ray_nt(const typename Wire<T>::Ray *p) {
   typename Wire<T>::Ray r;
@@ -671,6 +672,50 @@ __device__ __forceinline__ void store_hit_nt(typename Wire<T>::Hit *p, const typ
   u32x4 *dst = reinterpret_cast<u32x4 *>(p);
 #pragma unroll
   for (unsigned k = 0; k < sizeof(h) / 16; k++) __builtin_nontemporal_store(src[k], dst + k);
+}
+
+// A launch's own streams — rays in; hit records, flags and per-ray skip ids by the ray's index — lie in device memory, whether their
+// pointer is a kernel argument or comes out of the multi-batch table in LDS (BatchPtrs).  A pointer read from memory is a generic one
+// as far as the compiler can tell, and one selected between the two stays generic: every access through it is a flat_ instruction,
+// which also takes a slot of the LDS queue and is waited for on both counters.  The walks therefore hold these pointers as
+// global-address-space ones (as walk_dev.h's load_global_record does for the scene kernels' records) and the accesses are global_.
+#define NRT_GLOBAL __attribute__((address_space(1)))
+template <typename R>
+__device__ __forceinline__ R NRT_GLOBAL *as_global(R *p) {
+  return (R NRT_GLOBAL *)p;
+}
+template <typename T>
+__device__ __forceinline__ void store_hit_nt(typename Wire<T>::Hit NRT_GLOBAL *p, const typename Wire<T>::Hit &h) {
+  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+  const u32x4 *src = reinterpret_cast<const u32x4 *>(&h);
+  u32x4 NRT_GLOBAL *dst = (u32x4 NRT_GLOBAL *)p;
+#pragma unroll
+  for (unsigned k = 0; k < sizeof(h) / 16; k++) __builtin_nontemporal_store(src[k], dst + k);
+}
+// The ray a lane takes at a refill of the walks (k_traverse, k_traverse_wide): loaded with the DEFAULT cache policy.  The walks used
+// to read `(debug & 4) ? plain load : load_ray_nt` of one address, which the compiler merged into one plain load — so the plain load
+// is what every launch ran for as long as the select stood there.  With the hint really in the binary (nt on every piece, bypassing the vector L1)
+// C3's step is 3.8 % SLOWER (profiles/r11a_ray_streams.txt): the lanes of a wave take neighbouring 36-byte records, so the pieces
+// of a wave's rays share their 128-byte lines, and the L1 is what merges them.  Probe bit 4 of `debug` now selects the non-temporal
+// load, in the profiling library only (the address goes through an empty asm, so that the two loads stay two in the binary).
+template <typename T>
+__device__ __forceinline__ typename Wire<T>::Ray load_ray(const typename Wire<T>::Ray NRT_GLOBAL *p, uint32_t debug_flags) {
+  typename Wire<T>::Ray r;
+  const uint32_t NRT_GLOBAL *src = (const uint32_t NRT_GLOBAL *)p;
+  uint32_t *dst = reinterpret_cast<uint32_t *>(&r);
+#ifdef NRT_PROF
+  if (debug_flags & 4u) { // (wave-uniform)
+    asm volatile("" : "+v"(src));
+#pragma unroll
+    for (unsigned k = 0; k < sizeof(r) / 4; k++) dst[k] = __builtin_nontemporal_load(src + k);
+    asm volatile("" : "+v"(dst[0])); // (... and nothing like it ends the other arm: the loads are not sunk into one behind the branch)
+    return r;
+  }
+#endif
+  (void)debug_flags;
+#pragma unroll
+  for (unsigned k = 0; k < sizeof(r) / 4; k++) dst[k] = src[k]; // (neighbouring words: merged into the widest loads the 4-byte alignment allows)
+  return r;
 }
 
 // Completion record of a launch (common.h, DoneRec): no event is recorded in the stream for it.  Start — one thread of each
