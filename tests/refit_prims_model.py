@@ -32,11 +32,20 @@ def refit_boxes(nodes, indices, lo_p, hi_p):
     idx = np.asarray(indices, dtype=np.int64)
     lv = levels(nodes)
     reach = np.concatenate(lv)
-    for i in reach[nodes["flag"][reach] != 0]:
-        cnt, first = int(nodes["data"][i, 0]), int(nodes["data"][i, 1])
-        p = idx[first:first + cnt]
-        out["bmin"][i] = lo_p[p].min(axis=0) if cnt else np.full(3, big, F32)
-        out["bmax"][i] = hi_p[p].max(axis=0) if cnt else np.full(3, -big, F32)
+    leaves = reach[nodes["flag"][reach] != 0]
+    cnt = nodes["data"][leaves, 0].astype(np.int64)
+    first = nodes["data"][leaves, 1].astype(np.int64)
+    lo = np.full((leaves.size, 3), big, dtype=F32)
+    hi = np.full((leaves.size, 3), -big, dtype=F32)
+    ne = cnt > 0
+    if ne.any():  # per-leaf reduction over its slot range, every range on its own (as refit_model.refit: 300 000 leaves in a second)
+        c = cnt[ne]
+        seg = np.repeat(np.nonzero(ne)[0], c)
+        slot = np.repeat(first[ne], c) + (np.arange(c.sum()) - np.repeat(np.cumsum(c) - c, c))
+        np.minimum.at(lo, seg, lo_p[idx[slot]])
+        np.maximum.at(hi, seg, hi_p[idx[slot]])
+    out["bmin"][leaves] = lo
+    out["bmax"][leaves] = hi
     for lvl in reversed(lv):
         br = lvl[nodes["flag"][lvl] == 0]
         if br.size == 0:
