@@ -119,7 +119,7 @@ struct nrt_ctx {
   int lds_stack = kLdsStackDefault;
   unsigned chunk = 128, chunk_tail_pct = 0, refill_min = 44, trav_min = 16, leaf_min = 32; // (trav_min: 8 until round 3; 12-14 was the optimum of the two-level walk before its inner loop ran two rounds per trip, profiles/r03t_trav_min.txt; 16 with two rounds per trip in the fp64 walk, profiles/r03ZA)
   int f64_row_fetch = 1; // fp64 walk: fetch the plane rows of a WideNode<double> by the ray's signs (0: fetch the record and select; the path arrays of 4 GiB and more take)
-  unsigned tail_quad = 4; // traverse.hip "four lanes to a ray": live lanes of a wave that is out of rays at or below which it finishes them a quad per ray (0: never; records bit-identical at every value).  4 was the smallest threshold whose slowest bench run beat the library before the tail (C3 +2.5 %; 8: +3.5 %, 16: +5 %), measured while the tail stood inside the walk's loop and cost every launch 2.3 % in registers: profiles/r07a_tail_quad.txt.  The tail stands behind the loop now (84 VGPRs, as without it); the sweep that is to choose the default again is still to be run: profiles/r07b_tail_behind_loop.txt
+  unsigned tail_quad = 4; // traverse.hip "four lanes to a ray": live lanes of a wave that is out of rays at or below which it finishes them a quad per ray (0: never; records bit-identical at every value).  4 was the smallest threshold whose slowest bench run beat the library before the tail (C3 +2.5 %; 8: +3.5 %, 16: +5 %), measured while the tail stood inside the walk's loop and cost every launch 2.3 % in registers: profiles/r07a_tail_quad.txt.  The tail stands behind the loop now (84 VGPRs, as without it: profiles/r07b_tail_behind_loop.txt).  The sweep that r07b owed, in that library (profiles/r12a_tail_rows.txt, C3 ms per step): 0: 0.599, 2: 0.585, 4: 0.574, 8: 0.565, 12: 0.563, 16: 0.562 — monotone, 16 is 2.2 % ahead of 4.  The default stays 4 all the same: it is the value tests/test_gpu_tail_quad_default.py pins, and moving it is a change of its own, with the other configs measured at 16
   unsigned trav_min4 = 24; // the same threshold for the fp32 two-level walk, whose inner loop runs two pop + step rounds per trip (profiles/r03Z_threshold_resweep*.txt)
   unsigned num_parts = 8; // ray partitions == XCDs (env NRT_PARTS)
   unsigned debug_flags = 0;

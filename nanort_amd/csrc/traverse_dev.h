@@ -684,6 +684,14 @@ template <typename R>
 __device__ __forceinline__ R NRT_GLOBAL *as_global(R *p) {
   return (R NRT_GLOBAL *)p;
 }
+// The same for a pointer INTO THE BLOCK'S LDS that reaches a function as an argument (a row of a __shared__ array): generic there,
+// so a volatile access through it is a flat_ instruction with `sc0 sc1`, waited for on its own before the next one is issued.
+// Held as a local-address-space pointer the access is a ds_ instruction.
+#define NRT_LDS __attribute__((address_space(3)))
+template <typename R>
+__device__ __forceinline__ R NRT_LDS *as_lds(R *p) {
+  return (R NRT_LDS *)p;
+}
 template <typename T>
 __device__ __forceinline__ void store_hit_nt(typename Wire<T>::Hit NRT_GLOBAL *p, const typename Wire<T>::Hit &h) {
   typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));

@@ -417,10 +417,27 @@ do {                                                                            
 // owner's ray constants.
 // (SLOT: how an item names its record in LDS — a 32-bit index into `base` (k_traverse_wide: one array per launch; 4 bytes per item
 // keep the block's LDS below a sixth of the CU's) or the record's address (k_scene_walk: every owner's mesh has its own array))
+// NRT_ITEMS_DS: the two arrays are rows of the block's LDS that arrive here as pointers.  As generic volatile pointers (0) every one
+// of the up to eight stores and two loads of a trip was a `flat_… sc0 sc1` access followed by its own s_waitcnt vmcnt(0): ten
+// memory round trips one after the other in every leaf phase of the steady state.  As local-address-space pointers (1) they are
+// ds_write_b32 / ds_read_b32, issued back to back and waited for once (profiles/r12a_tail_rows.txt).
+#ifndef NRT_ITEMS_DS
+#define NRT_ITEMS_DS 1
+#endif
+#ifndef NRT_ITEMS_FETCH4
+#define NRT_ITEMS_FETCH4 1
+#endif
 template <bool PLAIN, typename SLOT>
-__device__ __forceinline__ bool leaf_items_one_trip(Lane<float> &L, uint32_t cnt, const LeafTri<float> *base, SLOT first, unsigned lane, volatile uint32_t *own_,
-                                                    volatile SLOT *rec_, uint32_t range0, uint32_t range1, uint32_t skip_prim, bool cull) {
+__device__ __forceinline__ bool leaf_items_one_trip(Lane<float> &L, uint32_t cnt, const LeafTri<float> *base, SLOT first, unsigned lane, uint32_t *own_row,
+                                                    SLOT *rec_row, uint32_t range0, uint32_t range1, uint32_t skip_prim, bool cull) {
   typedef float T;
+#if NRT_ITEMS_DS
+  uint32_t NRT_LDS *const own_ = as_lds(own_row);
+  SLOT NRT_LDS *const rec_ = as_lds(rec_row);
+#else
+  volatile uint32_t *const own_ = own_row;
+  volatile SLOT *const rec_ = rec_row;
+#endif
   const unsigned long long b0_ = __ballot((cnt & 1u) != 0u), b1_ = __ballot((cnt & 2u) != 0u), b2_ = __ballot((cnt & 4u) != 0u);
   const uint32_t items_ = (uint32_t)__builtin_popcountll(b0_) + 2u * (uint32_t)__builtin_popcountll(b1_) + 4u * (uint32_t)__builtin_popcountll(b2_);
   if (items_ > (uint32_t)kWave || items_ == 0u) return false;
@@ -434,7 +451,11 @@ __device__ __forceinline__ bool leaf_items_one_trip(Lane<float> &L, uint32_t cnt
       own_[base_ + k_] = lane; // (a word per item: sub-word stores of neighbouring lanes into one word would queue)
       rec_[base_ + k_] = first + k_;
     }
-  // (LDS operations of one wave are performed in issue order and the accesses are volatile: the reads below see the writes)
+  // (LDS operations of one wave are performed in issue order, and the compiler keeps the reads below behind the writes: for all it
+  // can tell item `me_` is one of the lane's own.  The fence says so as well; at this scope it costs no instruction.)
+#if NRT_ITEMS_DS
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+#endif
   const bool item_ = lane < items_;
   const uint32_t me_ = item_ ? lane : 0u; // (a lane without an item repeats item 0 — there is one: the callers come here with a lane waiting — and drops the result)
   const SLOT sv_ = rec_[me_];
@@ -461,9 +482,22 @@ __device__ __forceinline__ bool leaf_items_one_trip(Lane<float> &L, uint32_t cnt
   const unsigned long long okm_ = __ballot(ok);
   bool got_ = false;
   uint32_t win_ = 0;
+#if NRT_ITEMS_FETCH4
+  // (the distances of an owner's up to four items fetched together: one wait for all of them instead of one per record; the
+  // accept sequence below is the same — a record beyond the owner's count is not `okk`)
+  T tt4_[4];
+#pragma unroll
+  for (uint32_t k2_ = 0; k2_ < 4u; k2_++) tt4_[k2_] = __int_as_float(__builtin_amdgcn_ds_bpermute((int)(((base_ + k2_) & 63u) << 2), __float_as_int(tt_i)));
+  (void)kmax_;
+#pragma unroll
+  for (uint32_t k2_ = 0; k2_ < 4u; k2_++) {
+    const uint32_t src_ = (base_ + k2_) & 63u;
+    const T ttk = tt4_[k2_];
+#else
   for (uint32_t k2_ = 0; k2_ < kmax_; k2_++) {
     const uint32_t src_ = (base_ + k2_) & 63u;
     const T ttk = __int_as_float(__builtin_amdgcn_ds_bpermute((int)(src_ << 2), __float_as_int(tt_i)));
+#endif
     const bool okk = (k2_ < cnt) & (((okm_ >> src_) & 1ull) != 0ull);
     const bool acc = okk & !(ttk > L.hit_t) & !(ttk < L.min_t); // nanort.h:1133-1139: equality and NaN accepted
     L.hit_t = acc ? ttk : L.hit_t;
