@@ -47,6 +47,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "nanort_motion.h"  // the motion-blur vertex rule (MotionTriangleIntersector), shared with the device walk
 #ifdef NANORT_USE_HIP_BACKEND
 #include <mutex>
 
@@ -512,9 +513,17 @@ class TriangleIntersector {
     if (prim_index < trace_options_.prim_ids_range[0] || prim_index >= trace_options_.prim_ids_range[1]) return false;
     if (prim_index == trace_options_.skip_prim_id) return false;
 
-    const real3<T> A = real3<T>(get_vertex_addr<T>(vertices_, faces_[3 * prim_index + 0], vertex_stride_bytes_)) - ray_org_;
-    const real3<T> B = real3<T>(get_vertex_addr<T>(vertices_, faces_[3 * prim_index + 1], vertex_stride_bytes_)) - ray_org_;
-    const real3<T> C = real3<T>(get_vertex_addr<T>(vertices_, faces_[3 * prim_index + 2], vertex_stride_bytes_)) - ray_org_;
+    return IntersectVertices(t_inout, real3<T>(get_vertex_addr<T>(vertices_, faces_[3 * prim_index + 0], vertex_stride_bytes_)),
+                             real3<T>(get_vertex_addr<T>(vertices_, faces_[3 * prim_index + 1], vertex_stride_bytes_)),
+                             real3<T>(get_vertex_addr<T>(vertices_, faces_[3 * prim_index + 2], vertex_stride_bytes_)));
+  }
+
+  // THE arithmetic of the test, over the three corners wherever they come from (the mesh: Intersect above; two keyframes
+  // interpolated to the ray's time: MotionTriangleIntersector).
+  bool IntersectVertices(T *t_inout, const real3<T> &p0, const real3<T> &p1, const real3<T> &p2) const {
+    const real3<T> A = p0 - ray_org_;
+    const real3<T> B = p1 - ray_org_;
+    const real3<T> C = p2 - ray_org_;
     const int kx = ray_coeff_.kx, ky = ray_coeff_.ky, kz = ray_coeff_.kz;
 
     const T Ax = A[kx] - ray_coeff_.Sx * A[kz], Ay = A[ky] - ray_coeff_.Sy * A[kz];
@@ -588,7 +597,7 @@ class TriangleIntersector {
     }
   }
 
- private:
+ protected:
   const T *vertices_;
   const unsigned int *faces_;
   const size_t vertex_stride_bytes_;
@@ -600,6 +609,113 @@ class TriangleIntersector {
   mutable T u_;
   mutable T v_;
   mutable unsigned int prim_id_;
+};
+
+// ---------------------------------------------------------------------------
+// Motion blur: a triangle mesh with a second vertex keyframe (include/nanort_hip.h, "motion blur").  Host classes first: Build()
+// over (MotionTriangleMesh, MotionTriangleSAHPred) and the per-ray Traverse() with a MotionTriangleIntersector whose SetTime()
+// was called for the ray work without the backend.  With NANORT_USE_HIP_BACKEND the same Build() runs on the GPU
+// (nrtSetMesh + nrtSetMeshMotion + nrtBuild) and TraverseBatchMotion() / OccludedBatchMotion() trace a batch with one time per ray.
+// ---------------------------------------------------------------------------
+// Primitive accessor: keyframe 0 and keyframe 1 share the faces and the stride.  A primitive's box is the union of the triangle
+// rule's box on each keyframe, its SAH position the mean of the two keyframes' centres.
+template <typename T = float>
+class MotionTriangleMesh {
+ public:
+  MotionTriangleMesh(const T *vertices0, const T *vertices1, const unsigned int *faces, const size_t vertex_stride_bytes)
+      : k0_(vertices0, faces, vertex_stride_bytes), k1_(vertices1, faces, vertex_stride_bytes) {}
+
+  void BoundingBox(real3<T> *bmin, real3<T> *bmax, unsigned int prim_index) const {
+    real3<T> lo1, hi1;
+    k0_.BoundingBox(bmin, bmax, prim_index);
+    k1_.BoundingBox(&lo1, &hi1, prim_index);
+    for (int k = 0; k < 3; k++) {
+      (*bmin)[k] = std::min((*bmin)[k], lo1[k]);
+      (*bmax)[k] = std::max((*bmax)[k], hi1[k]);
+    }
+  }
+
+  void BoundingBoxAndCenter(real3<T> *bmin, real3<T> *bmax, real3<T> *center, unsigned int prim_index) const {
+    real3<T> lo1, hi1, c1;
+    k0_.BoundingBoxAndCenter(bmin, bmax, center, prim_index);
+    k1_.BoundingBoxAndCenter(&lo1, &hi1, &c1, prim_index);
+    for (int k = 0; k < 3; k++) {
+      (*bmin)[k] = std::min((*bmin)[k], lo1[k]);
+      (*bmax)[k] = std::max((*bmax)[k], hi1[k]);
+    }
+    *center = (*center + c1) * T(0.5);
+  }
+
+  const T *GetVertices() const { return k0_.GetVertices(); }    // keyframe 0
+  const T *GetVertices1() const { return k1_.GetVertices(); }   // keyframe 1
+  const unsigned int *GetFaces() const { return k0_.GetFaces(); }
+  size_t GetVertexStrideBytes() const { return k0_.GetVertexStrideBytes(); }
+
+ private:
+  TriangleMesh<T> k0_, k1_;
+};
+
+// Partition predicate: the primitive's SAH position (MotionTriangleMesh::BoundingBoxAndCenter) on `axis` against pos.
+template <typename T = float>
+class MotionTriangleSAHPred {
+ public:
+  MotionTriangleSAHPred(const T *vertices0, const T *vertices1, const unsigned int *faces, size_t vertex_stride_bytes)
+      : axis_(0), pos_(static_cast<T>(0.0)), vertices0_(vertices0), vertices1_(vertices1), faces_(faces), vertex_stride_bytes_(vertex_stride_bytes) {}
+  void Set(int axis, T pos) const {
+    axis_ = axis;
+    pos_ = pos;
+  }
+  bool operator()(unsigned int i) const {
+    real3<T> lo, hi, c;
+    MotionTriangleMesh<T>(vertices0_, vertices1_, faces_, vertex_stride_bytes_).BoundingBoxAndCenter(&lo, &hi, &c, i);
+    return c[axis_] < pos_;
+  }
+  const T *GetVertices() const { return vertices0_; }
+  const T *GetVertices1() const { return vertices1_; }
+  const unsigned int *GetFaces() const { return faces_; }
+  size_t GetVertexStrideBytes() const { return vertex_stride_bytes_; }
+
+ private:
+  mutable int axis_;
+  mutable T pos_;
+  const T *vertices0_;
+  const T *vertices1_;
+  const unsigned int *faces_;
+  size_t vertex_stride_bytes_;
+};
+
+// TriangleIntersector over the two keyframes: the three corners are interpolated to the time last given to SetTime() by the shared
+// rule (nanort_motion.h), then tested by TriangleIntersector's own arithmetic.  SetTime() before Traverse(), once per ray.
+template <typename T = float, class H = TriangleIntersection<T> >
+class MotionTriangleIntersector : public TriangleIntersector<T, H> {
+  typedef TriangleIntersector<T, H> Base;
+
+ public:
+  template <class M>
+  MotionTriangleIntersector(const M &m) : Base(m), vertices1_(m.GetVertices1()), shutter_(static_cast<T>(0.0)) {}
+  MotionTriangleIntersector(const T *vertices0, const T *vertices1, const unsigned int *faces, const size_t vertex_stride_bytes)
+      : Base(vertices0, faces, vertex_stride_bytes), vertices1_(vertices1), shutter_(static_cast<T>(0.0)) {}
+
+  // The ray's time: clamped to [0, 1], NaN and negatives to 0.
+  void SetTime(T time) const { shutter_ = nanort_motion::ClampTime<T>(time); }
+  T GetShutterTime() const { return shutter_; }
+
+  bool Intersect(T *t_inout, const unsigned int prim_index) const {
+    if (prim_index < this->trace_options_.prim_ids_range[0] || prim_index >= this->trace_options_.prim_ids_range[1]) return false;
+    if (prim_index == this->trace_options_.skip_prim_id) return false;
+    real3<T> p[3];
+    for (int c = 0; c < 3; c++) {
+      const unsigned int vi = this->faces_[3 * prim_index + c];
+      const T *a = get_vertex_addr<T>(this->vertices_, vi, this->vertex_stride_bytes_);
+      const T *b = get_vertex_addr<T>(vertices1_, vi, this->vertex_stride_bytes_);
+      for (int k = 0; k < 3; k++) p[c][k] = nanort_motion::Lerp<T>(a[k], b[k], shutter_);
+    }
+    return this->IntersectVertices(t_inout, p[0], p[1], p[2]);
+  }
+
+ private:
+  const T *vertices1_;
+  mutable T shutter_;
 };
 
 // Robust slab test (Ize 2013), t_max terms widened by MaxMult
@@ -1136,17 +1252,20 @@ struct triangle_tag {};
 struct sphere_tag {};
 struct cylinder_tag {};
 struct curve_tag {};
+struct motion_triangle_tag {};
 template <typename T, class Prim, class Pred>
 struct build_tag {
 #ifdef NANORT_USE_HIP_BACKEND
   typedef typename std::conditional<
       same_type<Prim, TriangleMesh<T> >::value && same_type<Pred, TriangleSAHPred<T> >::value, triangle_tag,
       typename std::conditional<
+          same_type<Prim, MotionTriangleMesh<T> >::value && same_type<Pred, MotionTriangleSAHPred<T> >::value, motion_triangle_tag,
+      typename std::conditional<
           same_type<T, float>::value && same_type<Prim, SphereGeometry>::value && same_type<Pred, SpherePred>::value, sphere_tag,
           typename std::conditional<
               same_type<T, float>::value && same_type<Prim, CylinderGeometry>::value && same_type<Pred, CylinderPred>::value, cylinder_tag,
               typename std::conditional<same_type<T, float>::value && same_type<Prim, BezierCurveGeometry>::value && same_type<Pred, BezierCurvePred>::value,
-                                        curve_tag, generic_tag>::type>::type>::type>::type type;
+                                        curve_tag, generic_tag>::type>::type>::type>::type>::type type;
 #else
   typedef generic_tag type;
 #endif
@@ -1217,6 +1336,14 @@ struct HipApi<float> {
   static nrt_status MultiHitDevice(nrt_ctx *c, const RayPod *r, uint64_t n, uint32_t k, const nrt_trace_options *o, HitPod *h, uint32_t *cnt, void *s) {
     return nrtMultiHitTraverseBatchDevice_f32(c, r, n, k, o, h, cnt, s);
   }
+  // (motion blur, include/nanort_hip.h: the second vertex keyframe and the queries with one time per ray)
+  static nrt_status SetMeshMotion(nrt_ctx *c, const float *v, size_t s) { return nrtSetMeshMotion_f32(c, v, s); }
+  static nrt_status TraverseMotion(nrt_ctx *c, const RayPod *r, const float *t, uint64_t n, const nrt_trace_options *o, HitPod *h, uint8_t *m) {
+    return nrtTraverseBatchMotion_f32(c, r, t, n, o, h, m);
+  }
+  static nrt_status OccludedMotion(nrt_ctx *c, const RayPod *r, const float *t, uint64_t n, const nrt_trace_options *o, uint8_t *m) {
+    return nrtOccludedBatchMotion_f32(c, r, t, n, o, m);
+  }
 };
 template <>
 struct HipApi<double> {
@@ -1278,6 +1405,14 @@ struct HipApi<double> {
   }
   static nrt_status MultiHitDevice(nrt_ctx *c, const RayPod *r, uint64_t n, uint32_t k, const nrt_trace_options *o, HitPod *h, uint32_t *cnt, void *s) {
     return nrtMultiHitTraverseBatchDevice_f64(c, r, n, k, o, h, cnt, s);
+  }
+  // (motion blur, include/nanort_hip.h: the second vertex keyframe and the queries with one time per ray)
+  static nrt_status SetMeshMotion(nrt_ctx *c, const double *v, size_t s) { return nrtSetMeshMotion_f64(c, v, s); }
+  static nrt_status TraverseMotion(nrt_ctx *c, const RayPod *r, const double *t, uint64_t n, const nrt_trace_options *o, HitPod *h, uint8_t *m) {
+    return nrtTraverseBatchMotion_f64(c, r, t, n, o, h, m);
+  }
+  static nrt_status OccludedMotion(nrt_ctx *c, const RayPod *r, const double *t, uint64_t n, const nrt_trace_options *o, uint8_t *m) {
+    return nrtOccludedBatchMotion_f64(c, r, t, n, o, m);
   }
 };
 struct CtxDeleter {
@@ -1359,6 +1494,10 @@ class BVHAccel {
     }
     if (device_prim_kind_ != 0) {
       backend_error_ = "Refit: no triangle tree (Build() with TriangleMesh/TriangleSAHPred first)";
+      return false;
+    }
+    if (tri_vertices1_) {  // (the library refuses too: nrtRefit on a context that holds a motion keyframe)
+      backend_error_ = "Refit: this accel was built over a MotionTriangleMesh: its boxes hold both keyframes (Build() again)";
       return false;
     }
     if (mesh.GetFaces() != tri_faces_ &&
@@ -1857,6 +1996,38 @@ class BVHAccel {
     }
     return true;
   }
+  // Motion blur (include/nanort_hip.h, "motion blur"): the closest hit of each of `num_rays` rays at its own time, over a tree built
+  // by Build() with MotionTriangleMesh / MotionTriangleSAHPred.  times[i] is ray i's time (clamped to [0, 1]; NULL: every ray at
+  // time 0).  EVERY record is written — a miss stores {0, 0, ray.max_t, 0xFFFFFFFF} — and each equals what the per-ray Traverse()
+  // with a MotionTriangleIntersector set to that time gives over the same tree; hit_out[i] (optional) receives 1 / 0.
+  bool TraverseBatchMotion(const Ray<T> *rays, const T *times, size_t num_rays, TriangleIntersection<T> *isects, unsigned char *hit_out = NULL,
+                           const BVHTraceOptions &options = BVHTraceOptions()) const {
+    typedef detail::HipApi<T> Api;
+    std::lock_guard<std::mutex> lock(batch_mutex_);
+    if (!MotionTreeReady("TraverseBatchMotion")) return false;
+    nrt_trace_options o;
+    std::memcpy(&o, &options, sizeof(o));
+    if (Api::TraverseMotion(ctx_.get(), reinterpret_cast<const typename Api::RayPod *>(rays), times, num_rays, &o,
+                            reinterpret_cast<typename Api::HitPod *>(isects), hit_out) != NRT_OK) {
+      backend_error_ = nrtLastError(ctx_.get());
+      return false;
+    }
+    return true;
+  }
+  // ... and its occlusion query: occluded_out[i] is exactly the hit_out[i] of TraverseBatchMotion().
+  bool OccludedBatchMotion(const Ray<T> *rays, const T *times, size_t num_rays, unsigned char *occluded_out,
+                           const BVHTraceOptions &options = BVHTraceOptions()) const {
+    typedef detail::HipApi<T> Api;
+    std::lock_guard<std::mutex> lock(batch_mutex_);
+    if (!MotionTreeReady("OccludedBatchMotion")) return false;
+    nrt_trace_options o;
+    std::memcpy(&o, &options, sizeof(o));
+    if (Api::OccludedMotion(ctx_.get(), reinterpret_cast<const typename Api::RayPod *>(rays), times, num_rays, &o, occluded_out) != NRT_OK) {
+      backend_error_ = nrtLastError(ctx_.get());
+      return false;
+    }
+    return true;
+  }
   // ... and with device pointers, asynchronous on `hip_stream` (see TraverseBatchDevice).
   bool MultiHitTraverseBatchDevice(const Ray<T> *d_rays, size_t num_rays, unsigned int max_hits, TriangleIntersection<T> *d_isects,
                                    unsigned int *d_counts, void *hip_stream, const BVHTraceOptions &options = BVHTraceOptions()) const {
@@ -2042,6 +2213,14 @@ class BVHAccel {
       return false;
     }
     return true;
+  }
+  // The checks of the motion queries (caller holds batch_mutex_): a triangle accel built over a MotionTriangleMesh.
+  bool MotionTreeReady(const char *who) const {
+    if (!ctx_ || device_prim_kind_ != 0 || !tri_vertices1_) {
+      backend_error_ = std::string(who) + ": Build() with MotionTriangleMesh/MotionTriangleSAHPred first";
+      return false;
+    }
+    return DeviceTreeReady(0);
   }
   // The checks every host batch call makes (caller holds batch_mutex_): a context, the primitive kind the call's records are
   // for (0 triangles, 1 spheres), and a tree adopted by Load() uploaded — after a copy-on-write detach when the contexts are
@@ -2635,8 +2814,25 @@ class BVHAccel {
     tri_vertices_ = mesh.GetVertices();  // (kept: a copy-on-write detach sends them to the new context)
     tri_stride_ = mesh.GetVertexStrideBytes();
     tri_faces_ = mesh.GetFaces();
+    tri_vertices1_ = NULL;
     prim_count_ = n;
     return HipBuild(n, options, 0, [&](nrt_ctx *c) { return Api::SetMesh(c, tri_vertices_, tri_stride_, tri_faces_, n); });
+  }
+  // A triangle mesh with a second vertex keyframe: nrtSetMesh + nrtSetMeshMotion + nrtBuild.  The accel stays a triangle accel (the
+  // triangle batch methods answer for keyframe 0); TraverseBatchMotion() / OccludedBatchMotion() trace it with one time per ray.
+  bool BuildImpl(unsigned int n, const MotionTriangleMesh<T> &mesh, const MotionTriangleSAHPred<T> &pred, const BVHBuildOptions<T> &options,
+                 detail::motion_triangle_tag) {
+    (void)pred;
+    typedef detail::HipApi<T> Api;
+    tri_vertices_ = mesh.GetVertices();
+    tri_stride_ = mesh.GetVertexStrideBytes();
+    tri_faces_ = mesh.GetFaces();
+    tri_vertices1_ = mesh.GetVertices1();
+    prim_count_ = n;
+    return HipBuild(n, options, 0, [&](nrt_ctx *c) {
+      const nrt_status st = Api::SetMesh(c, tri_vertices_, tri_stride_, tri_faces_, n);
+      return st != NRT_OK ? st : Api::SetMeshMotion(c, tri_vertices1_, tri_stride_);
+    });
   }
   bool BuildImpl(unsigned int n, const SphereGeometry &geom, const SpherePred &pred, const BVHBuildOptions<T> &options,
                  detail::sphere_tag) {
@@ -2793,7 +2989,10 @@ class BVHAccel {
   // The primitives of the last built-in Build(), from the arrays it was given (`cylinder_cap`: the cylinder intersector's flag).
   nrt_status SendPrimitives(nrt_ctx *c, bool cylinder_cap) const {
     switch (device_prim_kind_) {
-      case 0: return detail::HipApi<T>::SetMesh(c, tri_vertices_, tri_stride_, tri_faces_, prim_count_);
+      case 0: {
+        const nrt_status st = detail::HipApi<T>::SetMesh(c, tri_vertices_, tri_stride_, tri_faces_, prim_count_);
+        return (st != NRT_OK || !tri_vertices1_) ? st : detail::HipApi<T>::SetMeshMotion(c, tri_vertices1_, tri_stride_);
+      }
       case 1: return nrtSetSpheres_f32(c, sph_centers_, sph_radii_, prim_count_);
       case 2: return nrtSetCylinders_f32(c, cyl_endpoints_, cyl_radii_, cyl_count_, cylinder_cap ? 1 : 0);
       case 3: return nrtSetCurves_f32(c, crv_cps_, crv_radii_, prim_count_, static_cast<uint32_t>(crv_subdiv_));
@@ -2847,6 +3046,7 @@ class BVHAccel {
     cyl_count_ = o.cyl_count_;
     cyl_test_cap_ = o.cyl_test_cap_;
     tri_vertices_ = o.tri_vertices_;
+    tri_vertices1_ = o.tri_vertices1_;
     tri_stride_ = o.tri_stride_;
     tri_faces_ = o.tri_faces_;
     sph_centers_ = o.sph_centers_;
@@ -2896,6 +3096,7 @@ class BVHAccel {
     cyl_count_ = o->cyl_count_;
     cyl_test_cap_ = o->cyl_test_cap_;
     tri_vertices_ = o->tri_vertices_;
+    tri_vertices1_ = o->tri_vertices1_;
     tri_stride_ = o->tri_stride_;
     tri_faces_ = o->tri_faces_;
     sph_centers_ = o->sph_centers_;
@@ -2907,6 +3108,7 @@ class BVHAccel {
     o->crv_cps_ = o->crv_radii_ = NULL;
     o->cyl_endpoints_ = o->cyl_radii_ = NULL;
     o->tri_vertices_ = NULL;
+    o->tri_vertices1_ = NULL;
     o->tri_faces_ = NULL;
     o->sph_centers_ = o->sph_radii_ = NULL;
     o->cyl_count_ = o->prim_count_ = 0;
@@ -2934,6 +3136,7 @@ class BVHAccel {
   mutable bool cyl_test_cap_ = true;
   const T *tri_vertices_ = NULL;  // triangle / sphere primitives: what Build() was given (a detach sends them again)
   size_t tri_stride_ = 0;
+  const T *tri_vertices1_ = NULL;  // ... and the second vertex keyframe of a Build() over MotionTriangleMesh (NULL: none)
   const unsigned int *tri_faces_ = NULL;
   const float *sph_centers_ = NULL;
   const float *sph_radii_ = NULL;

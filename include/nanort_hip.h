@@ -608,6 +608,64 @@ NRT_API nrt_status nrtTraverseBatchesSkip_f64(nrt_ctx *ctx, uint32_t num_batches
                                               const nrt_trace_options *options, const uint32_t *const *skip_prim_ids,
                                               nrt_hit_f64 *const *hits_out, uint8_t *const *masks_out, const uint32_t *batch_flags);
 
+/* ---- motion blur: a second vertex keyframe and a time per ray ----------------------------------------------------------------
+ * An OPT-IN EXTENSION (the reference lists motion blur as open in its TODO).  A triangle context may hold a SECOND VERTEX KEYFRAME:
+ * keyframe 0 is what nrtSetMesh* gave, keyframe 1 has the same faces and the same vertex count.  A vertex moves linearly between
+ * the two; its position at a ray's time is defined per component, each operation rounded on its own (include/nanort_motion.h — the
+ * one statement of the rule, which the device walk and nanort.h's MotionTriangleIntersector both include):
+ *
+ *     s = (time > 0) ? (time < 1 ? time : 1) : 0        NaN and negatives -> 0, above 1 -> 1
+ *     x = (T(1) - s) * a + s * b                          a: keyframe 0, b: keyframe 1
+ *     x = x < min(a,b) ? min(a,b) : (x > max(a,b) ? max(a,b) : x)
+ *
+ * so time 0 is keyframe 0, time 1 is keyframe 1, and every interpolated vertex lies inside the box the builder gives the triangle.
+ *
+ * Setters.  nrtSetMeshMotion_* copies `vertices_t1` (rows of vertex_stride_bytes, xyz first, as many rows as the mesh has
+ * vertices) into the context; nrtSetMeshMotionDevice_* reads device memory on `hip_stream` and refuses a `num_vertices` below the
+ * context's vertex count before anything is enqueued.  Both need a triangle context of that precision with a mesh set
+ * (NRT_ERR_INVALID / NRT_ERR_PRECISION otherwise, nothing changed), wait for the launches in flight, DROP THE TREE and return when
+ * the context owns its copy.  vertices_t1 == NULL removes the keyframe (and drops the tree too).  Every nrtSetMesh* /
+ * nrtSetSpheres* / nrtSetCylinders* / nrtSetCurves* removes the keyframe.
+ *
+ * Trees.  nrtBuild_* on such a context gives every triangle the union of its two keyframes' boxes (per axis the triangle rule on
+ * each keyframe, then min / max of the two) and bins it at (c0 + c1) * 0.5; everything else of the build is unchanged, so a
+ * keyframe 1 equal to keyframe 0 builds the bytes of a plain build.  nrtSetTree_* adopts the caller's tree as it does today: its
+ * boxes are the caller's business (they have to hold both keyframes).  nrtRefit* refuses a context that holds a keyframe.
+ *
+ * Queries.  `times`: one value per ray, NULL = every ray at time 0.  Records, miss records ({0, 0, max_t, 0xFFFFFFFF}) and masks
+ * are those of nrtTraverseBatch*, all three trace options apply; nrtOccludedBatchMotion* writes exactly the closest-hit flag (a ray
+ * is settled once its hit distance is < max_t).  The walk is the reference's binary loop over the context's node array with the
+ * leaf records of both keyframes interpolated to the ray's time in front of the triangle test: every field of every record is
+ * bit-identical to the reference's Traverse over vertices interpolated by the rule above.  The *Device forms are asynchronous on
+ * `hip_stream`; nrtBuild / nrtSetTree / nrtSetMesh* / nrtSetMeshMotion* / nrtDestroy wait for them.  A context without a keyframe
+ * and contexts of the other primitive kinds are refused (NRT_ERR_INVALID).
+ *
+ * Every other entry point keeps working on a motion context and answers for keyframe 0 (over the wider boxes). */
+NRT_API nrt_status nrtSetMeshMotion_f32(nrt_ctx *ctx, const float *vertices_t1, size_t vertex_stride_bytes);
+NRT_API nrt_status nrtSetMeshMotion_f64(nrt_ctx *ctx, const double *vertices_t1, size_t vertex_stride_bytes);
+NRT_API nrt_status nrtSetMeshMotionDevice_f32(nrt_ctx *ctx, const float *d_vertices_t1, uint32_t num_vertices, size_t vertex_stride_bytes,
+                                              void *hip_stream);
+NRT_API nrt_status nrtSetMeshMotionDevice_f64(nrt_ctx *ctx, const double *d_vertices_t1, uint32_t num_vertices, size_t vertex_stride_bytes,
+                                              void *hip_stream);
+NRT_API nrt_status nrtTraverseBatchMotion_f32(nrt_ctx *ctx, const nrt_ray_f32 *rays, const float *times, uint64_t num_rays,
+                                              const nrt_trace_options *options, nrt_hit_f32 *hits_out, uint8_t *hit_mask_out);
+NRT_API nrt_status nrtTraverseBatchMotion_f64(nrt_ctx *ctx, const nrt_ray_f64 *rays, const double *times, uint64_t num_rays,
+                                              const nrt_trace_options *options, nrt_hit_f64 *hits_out, uint8_t *hit_mask_out);
+NRT_API nrt_status nrtTraverseBatchMotionDevice_f32(nrt_ctx *ctx, const nrt_ray_f32 *d_rays, const float *d_times, uint64_t num_rays,
+                                                    const nrt_trace_options *options, nrt_hit_f32 *d_hits_out, uint8_t *d_mask_out,
+                                                    void *hip_stream);
+NRT_API nrt_status nrtTraverseBatchMotionDevice_f64(nrt_ctx *ctx, const nrt_ray_f64 *d_rays, const double *d_times, uint64_t num_rays,
+                                                    const nrt_trace_options *options, nrt_hit_f64 *d_hits_out, uint8_t *d_mask_out,
+                                                    void *hip_stream);
+NRT_API nrt_status nrtOccludedBatchMotion_f32(nrt_ctx *ctx, const nrt_ray_f32 *rays, const float *times, uint64_t num_rays,
+                                              const nrt_trace_options *options, uint8_t *mask_out);
+NRT_API nrt_status nrtOccludedBatchMotion_f64(nrt_ctx *ctx, const nrt_ray_f64 *rays, const double *times, uint64_t num_rays,
+                                              const nrt_trace_options *options, uint8_t *mask_out);
+NRT_API nrt_status nrtOccludedBatchMotionDevice_f32(nrt_ctx *ctx, const nrt_ray_f32 *d_rays, const float *d_times, uint64_t num_rays,
+                                                    const nrt_trace_options *options, uint8_t *d_mask_out, void *hip_stream);
+NRT_API nrt_status nrtOccludedBatchMotionDevice_f64(nrt_ctx *ctx, const nrt_ray_f64 *d_rays, const double *d_times, uint64_t num_rays,
+                                                    const nrt_trace_options *options, uint8_t *d_mask_out, void *hip_stream);
+
 /* One HOST batch spread over several contexts — typically one per GPU of the node (nrtDeviceCount), each holding the same
  * tree: nrtBuild is deterministic, so building the same mesh on every context gives bit-identical replicas (or nrtSetTree the
  * same arrays).  The batch is cut into rows of `row_len` rays (an image row; 0 = 4096) and row r is traced by context

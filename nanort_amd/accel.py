@@ -58,6 +58,20 @@ class TriangleMesh:
         return self.vertex_stride_bytes
 
 
+class MotionTriangleMesh(TriangleMesh):
+    """A triangle mesh with a second vertex keyframe (include/nanort_hip.h, "motion blur"): `vertices0` at time 0, `vertices1` at
+    time 1, the same faces and the same row layout for both."""
+
+    def __init__(self, vertices0, vertices1, faces, vertex_stride_bytes=None):
+        TriangleMesh.__init__(self, vertices0, faces, vertex_stride_bytes)
+        self.vertices1 = np.ascontiguousarray(vertices1)
+        if self.vertices1.dtype != self.vertices.dtype or self.vertices1.shape != self.vertices.shape:
+            raise ValueError("the two keyframes must have the same dtype and shape")
+
+    def GetVertices1(self):
+        return self.vertices1
+
+
 class SphereGeometry:
     """The sphere ("particle") custom primitive of the reference (examples/particle_primitive/main.cc:82-291:
     SpherePred + SphereGeometry + SphereIntersector rolled into one description): xyz centres and one radius each."""
@@ -170,6 +184,54 @@ class BVHAccel:
             )
         )
         self._mesh = mesh
+        if isinstance(mesh, MotionTriangleMesh) and mesh.num_faces:
+            self._check(getattr(self._L, "nrtSetMeshMotion_" + self._s)(self._h, _p(mesh.vertices1), mesh.vertex_stride_bytes))
+
+    def SetMeshMotion(self, vertices1, vertex_stride_bytes=None):
+        """nrtSetMeshMotion: the second vertex keyframe of the triangle mesh last set (None removes it); drops the tree.  `vertices1`:
+        a numpy array of the accel's precision with at least the mesh's vertex count of rows, xyz first in each row (the row stride
+        defaults to the array's own)."""
+        if vertices1 is None:
+            self._check(getattr(self._L, "nrtSetMeshMotion_" + self._s)(self._h, None, 0))
+            return
+        v = np.asarray(vertices1)
+        if v.dtype != self.real:
+            raise TypeError("vertex precision %s != accel precision %s" % (v.dtype, self.real))
+        nv = self._refit_rows()
+        if vertex_stride_bytes is None:
+            v = np.ascontiguousarray(v.reshape(v.shape[0], -1) if v.ndim > 1 else v.reshape(-1, 3))
+            if v.shape[1] < 3:
+                raise ValueError("vertices must be [nv, k >= 3]")
+            if nv is not None and v.shape[0] < nv:
+                raise ValueError("vertices hold %d rows; the mesh has %d vertices" % (v.shape[0], nv))
+            vertex_stride_bytes = v.strides[0]
+        else:
+            if not v.flags["C_CONTIGUOUS"]:
+                raise ValueError("an explicit vertex_stride_bytes needs a C-contiguous array")
+            need = (nv - 1) * int(vertex_stride_bytes) + 3 * v.itemsize if nv else 0
+            if nv is not None and v.nbytes < need:
+                raise ValueError("vertices hold %d bytes; %d vertices at stride %d need %d" % (v.nbytes, nv, int(vertex_stride_bytes), need))
+        self._check(getattr(self._L, "nrtSetMeshMotion_" + self._s)(self._h, _p(v), int(vertex_stride_bytes)))
+
+    def SetMeshMotionDevice(self, d_vertices1, stream=None):
+        """nrtSetMeshMotionDevice: the second keyframe from a torch tensor on the accel's device, [nv', k >= 3] of the accel's
+        precision with stride(1) == 1 (the row stride is stride(0)); the library refuses nv' below the mesh's vertex count before it
+        enqueues anything.  Read on `stream` (default: torch's current stream); returns when the accel owns its copy.  None removes
+        the keyframe."""
+        import torch
+
+        if d_vertices1 is None:
+            self._check(getattr(self._L, "nrtSetMeshMotionDevice_" + self._s)(self._h, None, 0, 0, self._stream_handle(stream)))
+            return
+        want = torch.float32 if self.real == np.float32 else torch.float64
+        if d_vertices1.dtype != want:
+            raise TypeError("vertex dtype %s != accel precision %s" % (d_vertices1.dtype, self.real))
+        if d_vertices1.dim() != 2 or d_vertices1.shape[1] < 3 or d_vertices1.stride(1) != 1:
+            raise ValueError("vertices must be [nv, k >= 3] with stride(1) == 1")
+        self._on_device(d_vertices1, "vertices")
+        stride = d_vertices1.stride(0) * d_vertices1.element_size()
+        self._check(getattr(self._L, "nrtSetMeshMotionDevice_" + self._s)(
+            self._h, d_vertices1.data_ptr(), int(d_vertices1.shape[0]), stride, self._stream_handle(stream)))
 
     def Build(self, num_primitives, mesh, options=None):
         """BVHAccel::Build (reference nanort.h:1892-2149). Returns False iff n == 0."""
@@ -180,6 +242,8 @@ class BVHAccel:
                 mesh = CylinderGeometry(mesh.endpoints[:num_primitives], mesh.radii[:num_primitives], mesh.test_cap)
             elif isinstance(mesh, SphereGeometry):
                 mesh = SphereGeometry(mesh.centers[:num_primitives], mesh.radii[:num_primitives])
+            elif isinstance(mesh, MotionTriangleMesh):
+                mesh = MotionTriangleMesh(mesh.vertices, mesh.vertices1, mesh.faces[:num_primitives], mesh.vertex_stride_bytes)
             else:
                 mesh = TriangleMesh(mesh.vertices, mesh.faces[:num_primitives], mesh.vertex_stride_bytes)
         self.SetMesh(mesh)
@@ -664,6 +728,68 @@ class BVHAccel:
                                                                                 self._stream_handle(stream)))
             return n
         self._check(getattr(self._L, "nrtOccludedBatchDevice_" + self._s)(self._h, d_rays.data_ptr(), n, _p(options), d_mask.data_ptr(), stream))
+        return n
+
+    # -- motion blur (include/nanort_hip.h, "motion blur") -------------------
+    def _host_times(self, times, n):
+        """One time per ray in the accel's precision, contiguous (None: every ray at time 0)."""
+        if times is None:
+            return None
+        t = np.ascontiguousarray(times, dtype=self.real).reshape(-1)
+        if t.shape[0] != n:
+            raise ValueError("times: %d values for %d rays" % (t.shape[0], n))
+        return t
+
+    def _device_times(self, d_times, n):
+        if d_times is None:
+            return None
+        assert d_times.numel() * d_times.element_size() >= self.real.itemsize * n, "times: fewer values than rays"
+        return d_times.data_ptr()
+
+    def TraverseBatchMotion(self, rays, times, options=None):
+        """nrtTraverseBatchMotion: TraverseBatch with one shutter time per ray over the mesh's two vertex keyframes.  Returns
+        (hits, mask)."""
+        rays = np.ascontiguousarray(rays, dtype=ray_dtype(self.real))
+        n = rays.shape[0]
+        t = self._host_times(times, n)
+        hits = np.zeros((n,), dtype=hit_dtype(self.real))
+        mask = np.zeros((n,), dtype=np.uint8)
+        if options is not None:
+            options = np.asarray(options, dtype=TRACE_OPTIONS).reshape(1)
+        self._check(getattr(self._L, "nrtTraverseBatchMotion_" + self._s)(self._h, _p(rays), _p(t), n, _p(options), _p(hits), _p(mask)))
+        return hits, mask
+
+    def TraverseBatchMotionDevice(self, d_rays, d_times, d_hits, d_mask=None, options=None, stream=None):
+        """Same on HBM-resident torch tensors (raw PODs; `d_times`: one value of the accel's precision per ray, or None),
+        asynchronous on `stream` (default: torch's current stream).  Returns n."""
+        rsz, hsz = ray_dtype(self.real).itemsize, hit_dtype(self.real).itemsize
+        n = d_rays.numel() * d_rays.element_size() // rsz
+        assert d_hits.numel() * d_hits.element_size() >= n * hsz
+        if options is not None:
+            options = np.asarray(options, dtype=TRACE_OPTIONS).reshape(1)
+        self._check(getattr(self._L, "nrtTraverseBatchMotionDevice_" + self._s)(
+            self._h, d_rays.data_ptr(), self._device_times(d_times, n), n, _p(options), d_hits.data_ptr(),
+            None if d_mask is None else d_mask.data_ptr(), self._stream_handle(stream)))
+        return n
+
+    def OccludedBatchMotion(self, rays, times, options=None):
+        """nrtOccludedBatchMotion: only the hit flags of TraverseBatchMotion, each ray stopping at the first triangle that settles it."""
+        rays = np.ascontiguousarray(rays, dtype=ray_dtype(self.real))
+        n = rays.shape[0]
+        t = self._host_times(times, n)
+        mask = np.zeros((n,), dtype=np.uint8)
+        if options is not None:
+            options = np.asarray(options, dtype=TRACE_OPTIONS).reshape(1)
+        self._check(getattr(self._L, "nrtOccludedBatchMotion_" + self._s)(self._h, _p(rays), _p(t), n, _p(options), _p(mask)))
+        return mask
+
+    def OccludedBatchMotionDevice(self, d_rays, d_times, d_mask, options=None, stream=None):
+        n = d_rays.numel() * d_rays.element_size() // ray_dtype(self.real).itemsize
+        assert d_mask.numel() >= n
+        if options is not None:
+            options = np.asarray(options, dtype=TRACE_OPTIONS).reshape(1)
+        self._check(getattr(self._L, "nrtOccludedBatchMotionDevice_" + self._s)(
+            self._h, d_rays.data_ptr(), self._device_times(d_times, n), n, _p(options), d_mask.data_ptr(), self._stream_handle(stream)))
         return n
 
     def MultiHitTraverseBatch(self, rays, max_hits, options=None):

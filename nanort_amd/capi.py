@@ -35,6 +35,9 @@ SYMBOLS = [
     "nrtMultiHitTraverseBatch_f32", "nrtMultiHitTraverseBatch_f64", "nrtMultiHitTraverseBatchDevice_f32", "nrtMultiHitTraverseBatchDevice_f64",
     "nrtRefit_f32", "nrtRefit_f64", "nrtRefitDevice_f32", "nrtRefitDevice_f64", "nrtRefitPrims_f32", "nrtRefitPrimsDevice_f32",
     "nrtSetMeshDevice_f32", "nrtSetMeshDevice_f64", "nrtSetSpheresDevice_f32",
+    "nrtSetMeshMotion_f32", "nrtSetMeshMotion_f64", "nrtSetMeshMotionDevice_f32", "nrtSetMeshMotionDevice_f64",
+    "nrtTraverseBatchMotion_f32", "nrtTraverseBatchMotion_f64", "nrtTraverseBatchMotionDevice_f32", "nrtTraverseBatchMotionDevice_f64",
+    "nrtOccludedBatchMotion_f32", "nrtOccludedBatchMotion_f64", "nrtOccludedBatchMotionDevice_f32", "nrtOccludedBatchMotionDevice_f64",
     "nrtLastTraverseMs", "nrtSetLaunchTiming", "nrtSetTunable", "nrtGetTunable", "nrtLastBuildMs", "nrtLastKernelName", "nrtHostAlloc", "nrtHostFree",
     "nrtGroupUniqueId", "nrtGroupCreate", "nrtGroupCreateRanked", "nrtGroupDestroy", "nrtGroupLastError", "nrtGroupSetTunable", "nrtGroupInfo",
     "nrtGroupTileRays", "nrtGroupTraverseGather_f32", "nrtGroupTraverseGather_f64", "nrtGroupTraverseGatherTiles_f32", "nrtGroupTraverseGatherTiles_f64", "nrtGroupSynchronize", "nrtGroupLastTraffic",
@@ -156,6 +159,24 @@ def lib():
         f.restype = i32
         f = getattr(L, "nrtMultiHitTraverseBatchDevice_" + sfx)
         f.argtypes = [vp, vp, u64, u32, vp, vp, vp, vp]
+        f.restype = i32
+        f = getattr(L, "nrtSetMeshMotion_" + sfx)
+        f.argtypes = [vp, vp, sz]
+        f.restype = i32
+        f = getattr(L, "nrtSetMeshMotionDevice_" + sfx)
+        f.argtypes = [vp, vp, u32, sz, vp]
+        f.restype = i32
+        f = getattr(L, "nrtTraverseBatchMotion_" + sfx)
+        f.argtypes = [vp, vp, vp, u64, vp, vp, vp]
+        f.restype = i32
+        f = getattr(L, "nrtTraverseBatchMotionDevice_" + sfx)
+        f.argtypes = [vp, vp, vp, u64, vp, vp, vp, vp]
+        f.restype = i32
+        f = getattr(L, "nrtOccludedBatchMotion_" + sfx)
+        f.argtypes = [vp, vp, vp, u64, vp, vp]
+        f.restype = i32
+        f = getattr(L, "nrtOccludedBatchMotionDevice_" + sfx)
+        f.argtypes = [vp, vp, vp, u64, vp, vp, vp]
         f.restype = i32
         f = getattr(L, "nrtRefit_" + sfx)
         f.argtypes = [vp, vp, sz]

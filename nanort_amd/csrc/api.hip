@@ -149,7 +149,7 @@ struct nrt_ctx {
   int dyn_head = 1; // batches too small for a static group per wave: every wave's first chunk is its own (traverse.hip claim_init; tunable dyn_head)
   int wide_scramble = 0; // probe (tunable wide_scramble): the private node records in a pseudo-random order instead of pre-order
   // resident blocks per CU of the variants launched so far, by what selects the kernel: [walk][primitive kind] at `lds_entries` (a context keeps one precision; size_grid)
-  struct { int lds_entries; unsigned blocks_per_cu; } occupancy[4][kNumPrimKinds] = {};
+  struct { int lds_entries; unsigned blocks_per_cu; } occupancy[5][kNumPrimKinds] = {};
 
   hipEvent_t ev_b0 = nullptr, ev_b1 = nullptr;
   hipEvent_t ev_build_state = nullptr; // the builder's state block has reached build_state
@@ -159,6 +159,12 @@ struct nrt_ctx {
   bool have_build_time = false;
   float segment_ms = 0.f; // cylinders: wall time nrtSetCylinders spent cutting them into segments (counted into the next build's time)
   const char *last_kernel = ""; // variant of the most recent traversal launch (nrtLastKernelName)
+
+  // motion blur (nrtSetMeshMotion*): the second vertex keyframe of a triangle mesh (tight xyz, num_verts rows) and,
+  // while a tree is present, its LeafTri<T> records in leaf order beside d_tris
+  DevBuf b_verts1, b_tris1, st_times; // (st_times: per-ray times of the staged host forms, beside st_rays)
+  void *d_verts1 = nullptr; // == b_verts1.p while a keyframe is set
+  void *d_tris1 = nullptr;  // == b_tris1.p while a keyframe and a tree are present
 };
 
 static nrt_status fail(nrt_ctx *c, nrt_status st, const char *fmt, ...) {
@@ -270,6 +276,7 @@ static void free_tree(nrt_ctx *c) {
   c->d_nodes = nullptr;
   c->d_indices = nullptr;
   c->d_tris = nullptr;
+  c->d_tris1 = nullptr;
   c->num_nodes = c->num_indices = 0;
   c->tree_depth = 0;
   c->refit_planned = false;
@@ -279,6 +286,7 @@ static void free_mesh(nrt_ctx *c) {
   c->d_verts = nullptr; // (the buffers stay allocated for the next primitives)
   c->d_faces = nullptr;
   c->d_radii = nullptr;
+  c->d_verts1 = nullptr; // (the motion keyframe goes with the mesh it belongs to)
   c->num_faces = c->num_verts = 0;
   c->num_segs = 0;
 }
@@ -446,7 +454,7 @@ void nrtDestroy(nrt_ctx *c) {
   }
   free_tree(c);
   free_mesh(c);
-  DevBuf *bufs[] = {&c->b_verts, &c->b_radii, &c->b_faces, &c->st_rays, &c->st_hits, &c->st_mask, &c->st_skip, &c->b_nodes, &c->b_indices, &c->b_tris, &c->b_wide, &c->b_wide4, &c->b_wide_scratch, &c->b_build_ws, &c->b_wave_clock, &c->b_seg_verts, &c->b_seg_radii, &c->b_seg_prim, &c->b_seg_off, &c->b_refit_plan, &c->b_refit_stage, &c->b_max_index};
+  DevBuf *bufs[] = {&c->b_verts, &c->b_radii, &c->b_faces, &c->st_rays, &c->st_hits, &c->st_mask, &c->st_skip, &c->b_nodes, &c->b_indices, &c->b_tris, &c->b_wide, &c->b_wide4, &c->b_wide_scratch, &c->b_build_ws, &c->b_wave_clock, &c->b_seg_verts, &c->b_seg_radii, &c->b_seg_prim, &c->b_seg_off, &c->b_refit_plan, &c->b_refit_stage, &c->b_max_index, &c->b_verts1, &c->b_tris1, &c->st_times};
   for (DevBuf *b : bufs)
     if (b->p) (void)hipFree(b->p);
   if (c->d_counters) (void)hipFree(c->d_counters);
@@ -686,6 +694,11 @@ static nrt_status finish_leaf_records(nrt_ctx *c, hipStream_t s) {
   if (nrt_status st = ensure(c, c->b_tris, std::max<size_t>(1, c->num_indices) * leaf_record_bytes<T>(c->prim_kind))) return st;
   c->d_tris = c->b_tris.p;
   HIPCHK(c, launch_gather_leaf<T>(c->prim_kind, c->d_indices, c->d_faces, (const T *)c->d_verts, (const T *)c->d_radii, c->d_tris, (uint32_t)c->num_indices, s));
+  if (c->d_verts1 && c->prim_kind == kPrimTriangles) { // motion keyframe: the same gather over the second vertex array
+    if (nrt_status st = ensure(c, c->b_tris1, std::max<size_t>(1, c->num_indices) * leaf_record_bytes<T>(c->prim_kind))) return st;
+    c->d_tris1 = c->b_tris1.p;
+    HIPCHK(c, launch_gather_leaf<T>(c->prim_kind, c->d_indices, c->d_faces, (const T *)c->d_verts1, (const T *)nullptr, c->d_tris1, (uint32_t)c->num_indices, s));
+  }
   return NRT_OK;
 }
 
@@ -846,7 +859,7 @@ static nrt_status build(nrt_ctx *c, const typename Wire<T>::BuildOptions *opt, n
   // (cylinder contexts whose cylinders were cut into segments: the tree is built over the segments, each carrying its cylinder's id)
   const bool segs = c->prim_kind == kPrimCylinders && c->num_segs != 0 && sizeof(T) == 4;
   const uint32_t build_n = segs ? c->num_segs : c->num_faces;
-  hipError_t e = gpu_build<T>(c->stream, segs ? (const T *)c->b_seg_verts.p : (const T *)c->d_verts, c->d_faces, segs ? (const T *)c->b_seg_radii.p : (const T *)c->d_radii,
+  hipError_t e = gpu_build<T>(c->stream, segs ? (const T *)c->b_seg_verts.p : (const T *)c->d_verts, c->prim_kind == kPrimTriangles ? (const T *)c->d_verts1 : nullptr, c->d_faces, segs ? (const T *)c->b_seg_radii.p : (const T *)c->d_radii,
                               c->prim_kind, segs ? (const uint32_t *)c->b_seg_prim.p : nullptr, build_n, min_leaf, max_depth,
                               bin_size, (c->morton ? kBuildMorton : 0u) | (c->subtree_rows ? 0u : kBuildSubtreeDfs), &c->b_build_ws, &c->b_nodes, &c->b_indices, c->build_state, c->ev_build_state, &err);
   if (e != hipSuccess) return fail(c, NRT_ERR_DEVICE, "nrtBuild: %s (%s)", err.c_str(), hipGetErrorString(e));
@@ -943,6 +956,9 @@ static nrt_status refit(nrt_ctx *c, const T *vertices, size_t stride, bool devic
     return fail(c, NRT_ERR_PRECISION, "%s: the context holds %s primitives", fn, c->prec == 8 ? "f64" : "f32");
   if (c->prim_kind != kPrimTriangles) return fail(c, NRT_ERR_INVALID, "%s: only triangle meshes refit (this context holds %s)", fn,
                                                   kPrimKinds[c->prim_kind].name);
+  if (c->d_verts1)
+    return fail(c, NRT_ERR_INVALID, "%s: the context holds a motion keyframe (nrtSetMeshMotion): its boxes cover both keyframes and a refit of "
+                "one would shrink them; remove the keyframe or set the mesh and build again", fn);
   if (!c->d_nodes) return fail(c, NRT_ERR_INVALID, "%s: no tree (call nrtBuild or nrtSetTree)", fn);
   if (stride < 3 * sizeof(T)) return fail(c, NRT_ERR_INVALID, "%s: vertex stride %zu < %zu", fn, stride, 3 * sizeof(T));
   if (device && (stride % sizeof(T) != 0 || (uintptr_t)vertices % sizeof(T) != 0))
@@ -1051,7 +1067,8 @@ struct TraverseBatches {
 // first primitive it accepts; Count: the literal kernel's counting pass into d_counters, no output of its own; OcclusionPrims: the
 // occlusion query of nrtOccludedBatchPrims*, which every primitive kind takes — flags straight into the caller's mask, no compact
 // records, no post pass; on a triangle context it IS Occlusion: traverse_device says so under the lock.)
-enum class Query { Closest, Occlusion, Count, MultiHit, Cylinders, MultiBatch, Curves, OcclusionPrims };
+// (Motion / MotionOcclusion: the closest-hit and occlusion queries of nrt*BatchMotion*, every ray at its own time: motion.hip)
+enum class Query { Closest, Occlusion, Count, MultiHit, Cylinders, MultiBatch, Curves, OcclusionPrims, Motion, MotionOcclusion };
 template <typename T>
 struct TraverseLaunch {
   Query kind;
@@ -1067,6 +1084,8 @@ struct TraverseLaunch {
   uint32_t *hit_counts = nullptr;        // MultiHit (may be null): one word per ray
   const TraverseBatches<T> *batches = nullptr; // MultiBatch: rays and outputs per batch, n = all their rays (the context takes one launch: the caller checked)
   const uint32_t *skip_ids = nullptr;    // Closest, Occlusion (nrt*BatchSkip*): one skip id per ray in the place of opt->skip_prim_id (MultiBatch: batches->skip[])
+  const T *times = nullptr;              // Motion, MotionOcclusion: one time per ray (null: every ray at time 0)
+  bool motion() const { return kind == Query::Motion || kind == Query::MotionOcclusion; }
   // the launch carries per-ray skip ids
   bool has_skip_ids() const {
     if (skip_ids) return true;
@@ -1082,6 +1101,13 @@ template <typename T>
 static nrt_status validate_launch(nrt_ctx *c, const TraverseLaunch<T> &l) {
   const bool custom = c->prim_kind != kPrimTriangles; // spheres / cylinders
   if (c->prec != (int)sizeof(T)) return fail(c, NRT_ERR_PRECISION, "nrtTraverseBatch: precision mismatch");
+  if (l.motion()) { // (include/nanort_hip.h, "motion blur")
+    if (custom) return fail(c, NRT_ERR_INVALID, "motion queries: triangle contexts only (this context holds %s)", kPrimKinds[c->prim_kind].name);
+    if (!c->d_verts1) return fail(c, NRT_ERR_INVALID, "motion queries: the context holds no motion keyframe (nrtSetMeshMotion)");
+    if (c->d_nodes && !c->d_tris1) return fail(c, NRT_ERR_INVALID, "motion queries: internal: no keyframe-1 leaf records");
+    if (((uintptr_t)l.times % sizeof(T)) != 0u) return fail(c, NRT_ERR_INVALID, "motion queries: the times array is not aligned to %zu bytes", sizeof(T));
+    if (l.kind == Query::MotionOcclusion && !l.mask && l.n) return fail(c, NRT_ERR_INVALID, "nrtOccludedBatchMotion: NULL mask");
+  }
   if (l.has_skip_ids()) { // (include/nanort_hip.h, "per-ray skip ids")
     if (custom)
       return fail(c, NRT_ERR_INVALID, "per-ray skip ids: triangle contexts only (the sphere, cylinder and curve intersectors have no skip id)");
@@ -1132,7 +1158,7 @@ static nrt_status take_slot(nrt_ctx *c, hipStream_t s, nrt_ctx::LaunchSlot **out
 }
 
 // The kernel a launch runs, from the context's tree and tunables and the launch's kind and options.
-enum class Walk { Literal, OneLevel, TwoLevel, MultiHit }; // k_traverse, k_traverse_wide of WIDTH 2 / 4, k_traverse_multihit
+enum class Walk { Literal, OneLevel, TwoLevel, MultiHit, Motion }; // k_traverse, k_traverse_wide of WIDTH 2 / 4, k_traverse_multihit, k_traverse_motion
 struct WalkChoice {
   Walk walk;
   bool plain_options; // prim ids are < num_faces: nothing can be rejected by the trace options -> the kernel variant without the id tests
@@ -1152,7 +1178,7 @@ static WalkChoice choose_walk(const nrt_ctx *c, const TraverseLaunch<T> &l) {
 #endif
   const bool custom = c->prim_kind != kPrimTriangles; // the custom primitives share one launch geometry
   const bool multihit = l.kind == Query::MultiHit;
-  const bool use_wide = (c->wide || custom || l.kind == Query::Occlusion) && l.kind != Query::Count && c->d_wide && !multihit;
+  const bool use_wide = (c->wide || custom || l.kind == Query::Occlusion) && l.kind != Query::Count && c->d_wide && !multihit && !l.motion();
   // two levels per step: closest-hit walks of nested fp32 triangle trees, outside the profiling / splitting variants
   w.plain_options = l.opt->prim_ids_range[0] == 0u && l.opt->prim_ids_range[1] >= c->num_faces && l.opt->skip_prim_id >= c->num_faces &&
                     !l.opt->cull_back_face;
@@ -1165,8 +1191,8 @@ static WalkChoice choose_walk(const nrt_ctx *c, const TraverseLaunch<T> &l) {
   w.wide4_big = c->num_branch_records >= (1ull << 25) || (c->wide4_big_ok == 2 && c->prim_kind == kPrimTriangles); // (2: forced, for the tests)
   const bool use_wide4 = use_wide && c->d_wide4 && c->wide_stack == 10 && c->tree_nested && c->root_is_branch && !prof_needs_w2 &&
                          (!w.wide4_big || (!custom && !c->order4 && !(w.dbg & (32u | 8192u))));
-  w.walk = multihit ? Walk::MultiHit : (use_wide4 ? Walk::TwoLevel : (use_wide ? Walk::OneLevel : Walk::Literal));
-  w.lds_entries = multihit ? kLdsStackDefault : (use_wide4 ? kWide4LdsStack : (custom ? 10 : (use_wide ? c->wide_stack : c->lds_stack)));
+  w.walk = l.motion() ? Walk::Motion : multihit ? Walk::MultiHit : (use_wide4 ? Walk::TwoLevel : (use_wide ? Walk::OneLevel : Walk::Literal));
+  w.lds_entries = (multihit || l.motion()) ? kLdsStackDefault : (use_wide4 ? kWide4LdsStack : (custom ? 10 : (use_wide ? c->wide_stack : c->lds_stack)));
   return w;
 }
 
@@ -1175,7 +1201,8 @@ template <typename T>
 static GridPlan size_grid(nrt_ctx *c, const WalkChoice &w, uint64_t n) {
   auto &e = c->occupancy[(int)w.walk][c->prim_kind];
   if (e.blocks_per_cu == 0 || e.lds_entries != w.lds_entries)
-    e = {w.lds_entries, (unsigned)(w.walk == Walk::MultiHit  ? traverse_multihit_blocks_per_cu<T>()
+    e = {w.lds_entries, (unsigned)(w.walk == Walk::Motion    ? traverse_motion_blocks_per_cu<T>()
+                        : w.walk == Walk::MultiHit  ? traverse_multihit_blocks_per_cu<T>()
                         : w.walk == Walk::Literal ? traverse_blocks_per_cu<T>(w.lds_entries)
                                                   : traverse_wide_blocks_per_cu<T>(w.lds_entries, c->prim_kind, w.wide4()))};
   const unsigned per_cu = c->max_blocks_per_cu && e.blocks_per_cu > c->max_blocks_per_cu ? c->max_blocks_per_cu : e.blocks_per_cu;
@@ -1206,7 +1233,7 @@ static void fill_walk_args(const nrt_ctx *c, const TraverseLaunch<T> &l, const W
   a.skip_prim = l.opt->skip_prim_id;
   a.skip_ids = l.skip_ids; // (MultiBatch: null, the table's skip_v instead)
   a.cull_back_face = l.opt->cull_back_face ? 1u : 0u;
-  a.any_hit = (l.kind == Query::Occlusion || l.kind == Query::OcclusionPrims) ? 1u : 0u;
+  a.any_hit = (l.kind == Query::Occlusion || l.kind == Query::OcclusionPrims || l.kind == Query::MotionOcclusion) ? 1u : 0u;
   a.plain_options = w.plain_options ? 1u : 0u;
   a.root_test = c->tree_nested ? 0u : 1u;
   a.order4 = (c->order4 && w.wide4() && c->prim_kind == kPrimTriangles && l.kind != Query::Occlusion && !profiled) ? 1u : 0u;
@@ -1293,7 +1320,10 @@ static nrt_status enqueue_launch(nrt_ctx *c, const TraverseLaunch<T> &l, const W
   a.done_publish = post_pass ? 0u : 1u;
   const bool timed = l.timed && !use_rec;
   if (timed) HIPCHK(c, hipEventRecord(slot->t0, s));
-  if (w.walk == Walk::MultiHit) {
+  if (w.walk == Walk::Motion) {
+    HIPCHK(c, launch_traverse_motion<T>(a, c->d_tris1, l.times, grid, s));
+    c->last_kernel = sizeof(T) == 4 ? "nrt::k_traverse_motion<float>" : "nrt::k_traverse_motion<double>";
+  } else if (w.walk == Walk::MultiHit) {
     HIPCHK(c, launch_traverse_multihit<T>(a, l.max_hits, l.hit_counts, grid, s));
     c->last_kernel = sizeof(T) == 4 ? "nrt::k_traverse_multihit<float>" : "nrt::k_traverse_multihit<double>";
   } else if (w.wide()) {
@@ -1362,13 +1392,15 @@ static nrt_status traverse_device(nrt_ctx *c, TraverseLaunch<T> l) {
 }
 
 const uint64_t kStagedRays = 1ull << 26; // rays per launch of the staged host paths (keeps staging bounded)
+const uint64_t kPiece = 1ull << 19; // rays per pipeline stage of traverse_host (19 MB up, 8 MB down in fp32), and per launch of the motion queries' staged path
 
 // The staged host path of every ray query (the caller holds host_mutex), in pieces of `chunk` rays: upload into st_rays, the launch
 // `make(rays in the piece)` asks for, rec_bytes / flag_bytes per ray of st_hits / st_mask back into recs / flags (null: not copied).
 // `skip_ids` (may be null): one skip id per ray; every piece's slice of it is uploaded into st_skip beside the piece's rays.
+// `times` (may be null; the motion queries): one time per ray, staged and advanced per piece in the same way, into st_times.
 template <typename T, typename MakeLaunch>
 static nrt_status staged_host_loop(nrt_ctx *c, const typename Wire<T>::Ray *rays, uint64_t n, uint64_t chunk, size_t rec_bytes, size_t flag_bytes,
-                                   void *recs, void *flags, MakeLaunch make, const uint32_t *skip_ids = nullptr) {
+                                   void *recs, void *flags, MakeLaunch make, const uint32_t *skip_ids = nullptr, const T *times = nullptr) {
   const size_t ray_bytes = sizeof(typename Wire<T>::Ray);
   for (uint64_t off = 0; off < n; off += chunk) {
     const uint64_t m = std::min(chunk, n - off);
@@ -1379,6 +1411,10 @@ static nrt_status staged_host_loop(nrt_ctx *c, const typename Wire<T>::Ray *rays
     if (skip_ids) {
       if ((st = ensure(c, c->st_skip, m * sizeof(uint32_t)))) return st;
       HIPCHK(c, hipMemcpyAsync(c->st_skip.p, skip_ids + off, m * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    }
+    if (times) {
+      if ((st = ensure(c, c->st_times, m * sizeof(T)))) return st;
+      HIPCHK(c, hipMemcpyAsync(c->st_times.p, times + off, m * sizeof(T), hipMemcpyHostToDevice, c->stream));
     }
     if ((st = traverse_device<T>(c, make(m)))) return st;
     if (recs) HIPCHK(c, hipMemcpyAsync((char *)recs + off * rec_bytes, c->st_hits.p, m * rec_bytes, hipMemcpyDeviceToHost, c->stream));
@@ -1403,7 +1439,8 @@ static bool is_pinned_host(const void *p) {
 // so the call approaches the slower of the two copy directions instead of their sum plus the kernel.
 template <typename T>
 static nrt_status traverse_host(nrt_ctx *c, const typename Wire<T>::Ray *rays, uint64_t n,
-                                const nrt_trace_options *opt, typename Wire<T>::Hit *hits, uint8_t *mask, const uint32_t *skip_ids = nullptr) {
+                                const nrt_trace_options *opt, typename Wire<T>::Hit *hits, uint8_t *mask, const uint32_t *skip_ids = nullptr,
+                                Query kind = Query::Closest, const T *times = nullptr) { // (kind: Closest, or Motion with its `times`, which may be null)
   if (!c) return NRT_ERR_INVALID;
   if (n == 0) return NRT_OK;
   if (!rays || !hits) return fail(c, NRT_ERR_INVALID, "nrtTraverseBatch: NULL rays/hits");
@@ -1411,9 +1448,8 @@ static nrt_status traverse_host(nrt_ctx *c, const typename Wire<T>::Ray *rays, u
   typedef typename Wire<T>::Hit Hit;
   std::lock_guard<std::mutex> host_lock(c->host_mutex);
   HIPCHK(c, hipSetDevice(c->device));
-  const uint64_t kPiece = 1ull << 19; // rays per pipeline stage (19 MB up, 8 MB down in fp32)
   if (n >= 2 * kPiece && c->host_pipeline && is_pinned_host(rays) && is_pinned_host(hits) && (!mask || is_pinned_host(mask)) &&
-      (!skip_ids || is_pinned_host(skip_ids))) {
+      (!skip_ids || is_pinned_host(skip_ids)) && (!times || is_pinned_host(times))) {
     if (!c->copy_in) HIPCHK(c, hipStreamCreateWithFlags(&c->copy_in, hipStreamNonBlocking));
     if (!c->copy_out) HIPCHK(c, hipStreamCreateWithFlags(&c->copy_out, hipStreamNonBlocking));
     for (int k = 0; k < 2; k++)
@@ -1421,7 +1457,8 @@ static nrt_status traverse_host(nrt_ctx *c, const typename Wire<T>::Ray *rays, u
         if (!*e) HIPCHK(c, hipEventCreateWithFlags(e, hipEventDisableTiming));
     nrt_status st;
     if ((st = ensure(c, c->st_rays, 2 * kPiece * sizeof(Ray))) || (st = ensure(c, c->st_hits, 2 * kPiece * sizeof(Hit))) ||
-        (st = ensure(c, c->st_mask, 2 * kPiece)) || (skip_ids && (st = ensure(c, c->st_skip, 2 * kPiece * sizeof(uint32_t)))))
+        (st = ensure(c, c->st_mask, 2 * kPiece)) || (skip_ids && (st = ensure(c, c->st_skip, 2 * kPiece * sizeof(uint32_t)))) ||
+        (times && (st = ensure(c, c->st_times, 2 * kPiece * sizeof(T)))))
       return st;
     uint64_t piece = 0;
     for (uint64_t off = 0; off < n; off += kPiece, piece++) {
@@ -1431,15 +1468,17 @@ static nrt_status traverse_host(nrt_ctx *c, const typename Wire<T>::Ray *rays, u
       Hit *d_h = (Hit *)c->st_hits.p + (size_t)b * kPiece;
       uint8_t *d_m = (uint8_t *)c->st_mask.p + (size_t)b * kPiece;
       uint32_t *d_s = skip_ids ? (uint32_t *)c->st_skip.p + (size_t)b * kPiece : nullptr; // (the piece's slice of the ids travels with its rays)
+      T *d_t = times ? (T *)c->st_times.p + (size_t)b * kPiece : nullptr;                 // (... and its slice of the times)
       // the ray slot is free once the trace that read it (two pieces ago) is done; the record slot once its download is
       if (piece >= 2) HIPCHK(c, hipStreamWaitEvent(c->copy_in, c->ev_tr[b], 0));
       HIPCHK(c, hipMemcpyAsync(d_r, rays + off, m * sizeof(Ray), hipMemcpyHostToDevice, c->copy_in));
       if (d_s) HIPCHK(c, hipMemcpyAsync(d_s, skip_ids + off, m * sizeof(uint32_t), hipMemcpyHostToDevice, c->copy_in));
+      if (d_t) HIPCHK(c, hipMemcpyAsync(d_t, times + off, m * sizeof(T), hipMemcpyHostToDevice, c->copy_in));
       HIPCHK(c, hipEventRecord(c->ev_in[b], c->copy_in));
       HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_in[b], 0));
       if (piece >= 2) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_out[b], 0));
-      st = traverse_device<T>(c, {.kind = Query::Closest, .rays = d_r, .n = m, .opt = opt, .stream = c->stream, .timed = true, .hits = d_h, .mask = d_m,
-                                  .skip_ids = d_s});
+      st = traverse_device<T>(c, {.kind = kind, .rays = d_r, .n = m, .opt = opt, .stream = c->stream, .timed = true, .hits = d_h, .mask = d_m,
+                                  .skip_ids = d_s, .times = d_t});
       if (st) { // (copies into the caller's buffers may still be in flight: let them land before the call returns)
         (void)hipStreamSynchronize(c->copy_in);
         (void)hipStreamSynchronize(c->stream);
@@ -1456,10 +1495,12 @@ static nrt_status traverse_host(nrt_ctx *c, const typename Wire<T>::Ray *rays, u
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return NRT_OK;
   }
-  return staged_host_loop<T>(c, rays, n, kStagedRays, sizeof(Hit), 1, hits, mask, [&](uint64_t m) -> TraverseLaunch<T> {
-    return {.kind = Query::Closest, .rays = (const Ray *)c->st_rays.p, .n = m, .opt = opt, .stream = c->stream, .timed = true,
-            .hits = (Hit *)c->st_hits.p, .mask = (uint8_t *)c->st_mask.p, .skip_ids = skip_ids ? (const uint32_t *)c->st_skip.p : nullptr};
-  }, skip_ids);
+  // (the motion queries go in pieces of kPiece rays here too: their staging stays as small as the pipeline's)
+  return staged_host_loop<T>(c, rays, n, kind == Query::Motion ? kPiece : kStagedRays, sizeof(Hit), 1, hits, mask, [&](uint64_t m) -> TraverseLaunch<T> {
+    return {.kind = kind, .rays = (const Ray *)c->st_rays.p, .n = m, .opt = opt, .stream = c->stream, .timed = true,
+            .hits = (Hit *)c->st_hits.p, .mask = (uint8_t *)c->st_mask.p, .skip_ids = skip_ids ? (const uint32_t *)c->st_skip.p : nullptr,
+            .times = times ? (const T *)c->st_times.p : nullptr};
+  }, skip_ids, times);
 }
 
 // One host batch spread over several contexts — one per GPU of the node, each holding the same tree (the build is
@@ -1684,16 +1725,18 @@ static nrt_status traverse_batches_host(nrt_ctx *c, uint32_t nb, const typename 
 
 template <typename T>
 static nrt_status occluded_host(nrt_ctx *c, const typename Wire<T>::Ray *rays, uint64_t n, const nrt_trace_options *opt, uint8_t *mask,
-                                const uint32_t *skip_ids = nullptr) {
+                                const uint32_t *skip_ids = nullptr, Query kind = Query::Occlusion, const T *times = nullptr) {
   if (!c) return NRT_ERR_INVALID;
   if (n == 0) return NRT_OK;
   if (!rays || !mask) return fail(c, NRT_ERR_INVALID, "nrtOccludedBatch: NULL rays/mask");
   std::lock_guard<std::mutex> host_lock(c->host_mutex);
   HIPCHK(c, hipSetDevice(c->device));
-  return staged_host_loop<T>(c, rays, n, kStagedRays, 0, 1, nullptr, mask, [&](uint64_t m) -> TraverseLaunch<T> {
-    return {.kind = Query::Occlusion, .rays = (const typename Wire<T>::Ray *)c->st_rays.p, .n = m, .opt = opt, .stream = c->stream, .timed = true,
-            .mask = (uint8_t *)c->st_mask.p, .skip_ids = skip_ids ? (const uint32_t *)c->st_skip.p : nullptr};
-  }, skip_ids);
+  const uint64_t chunk = kind == Query::MotionOcclusion ? kPiece : kStagedRays; // (motion: traverse_host's pieces)
+  return staged_host_loop<T>(c, rays, n, chunk, 0, 1, nullptr, mask, [&](uint64_t m) -> TraverseLaunch<T> {
+    return {.kind = kind, .rays = (const typename Wire<T>::Ray *)c->st_rays.p, .n = m, .opt = opt, .stream = c->stream, .timed = true,
+            .mask = (uint8_t *)c->st_mask.p, .skip_ids = skip_ids ? (const uint32_t *)c->st_skip.p : nullptr,
+            .times = times ? (const T *)c->st_times.p : nullptr};
+  }, skip_ids, times);
 }
 
 // ---------------------------------------------------------------------------
@@ -1740,6 +1783,73 @@ static nrt_status multihit_host(nrt_ctx *c, const typename Wire<T>::Ray *rays, u
   });
 }
 
+// ---------------------------------------------------------------------------
+// motion blur (include/nanort_hip.h, nrtSetMeshMotion* / nrt*BatchMotion*)
+// ---------------------------------------------------------------------------
+// The second vertex keyframe of the context's triangle mesh, from host memory or (`device`: read on `s`) from HBM, into the context's
+// own tight array through launch_gather_vertices.  Every refusal comes before anything changes or is enqueued; then the tree goes
+// (its boxes and leaf records belong to the keyframes it was built over) and the call returns when the context owns its copy.
+// `vertices` == NULL removes the keyframe.
+template <typename T>
+static nrt_status set_mesh_motion(nrt_ctx *c, const T *vertices, uint32_t num_vertices, size_t stride, bool device, hipStream_t s) {
+  const char *fn = device ? "nrtSetMeshMotionDevice" : "nrtSetMeshMotion";
+  if (!c) return NRT_ERR_INVALID;
+  if (c->prec != 0 && c->prec != (int)sizeof(T))
+    return fail(c, NRT_ERR_PRECISION, "%s: the context holds %s primitives", fn, c->prec == 8 ? "f64" : "f32");
+  if (c->prec == 0 || c->prim_kind != kPrimTriangles || !c->d_verts || c->num_faces == 0)
+    return fail(c, NRT_ERR_INVALID, "%s: set a triangle mesh first (nrtSetMesh): the keyframe shares its faces and its vertex count", fn);
+  if (vertices) {
+    if (stride < 3 * sizeof(T)) return fail(c, NRT_ERR_INVALID, "%s: vertex stride %zu < %zu", fn, stride, 3 * sizeof(T));
+    if (device && (stride % sizeof(T) != 0 || (uintptr_t)vertices % sizeof(T) != 0))
+      return fail(c, NRT_ERR_INVALID, "%s: vertex stride %zu or pointer not aligned to %zu bytes", fn, stride, sizeof(T));
+    // (the faces were validated against num_verts when the mesh was set: a block of that many rows is all the gather reads — what
+    // DESIGN 3.7 asks of nrtSetMeshDevice, without an index reduction)
+    if (device && num_vertices < c->num_verts)
+      return fail(c, NRT_ERR_INVALID, "%s: the vertex block holds %u rows, the context's mesh has %u vertices", fn, num_vertices, c->num_verts);
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, wait_for_launches(c));
+  free_tree(c); // (bumps generation)
+  c->d_verts1 = nullptr;
+  if (!vertices) return NRT_OK;
+  const uint32_t nv = c->num_verts;
+  if (nrt_status st = ensure(c, c->b_verts1, 3 * (size_t)nv * sizeof(T))) return st;
+  if (!device) s = c->stream;
+  const void *src = vertices;
+  if (!device) { // the caller's block, as it lies, into the staging buffer the host refit uses
+    const size_t block = (size_t)(nv - 1) * stride + 3 * sizeof(T);
+    if (nrt_status st = ensure(c, c->b_refit_stage, block)) return st;
+    HIPCHK(c, hipMemcpyAsync(c->b_refit_stage.p, vertices, block, hipMemcpyHostToDevice, s));
+    src = c->b_refit_stage.p;
+  }
+  HIPCHK(c, launch_gather_vertices<T>(src, stride, nv, (T *)c->b_verts1.p, s));
+  HIPCHK(c, hipStreamSynchronize(s)); // the context owns its copy: the caller's buffer is free again
+  c->d_verts1 = c->b_verts1.p;
+  return NRT_OK;
+}
+
+template <typename T>
+static nrt_status traverse_motion_host(nrt_ctx *c, const typename Wire<T>::Ray *r, const T *times, uint64_t n, const nrt_trace_options *o,
+                                       typename Wire<T>::Hit *h, uint8_t *m) {
+  return traverse_host<T>(c, r, n, o, h, m, nullptr, Query::Motion, times);
+}
+template <typename T>
+static nrt_status traverse_motion_device(nrt_ctx *c, const typename Wire<T>::Ray *r, const T *times, uint64_t n, const nrt_trace_options *o,
+                                         typename Wire<T>::Hit *h, uint8_t *m, void *s) {
+  if (!c) return NRT_ERR_INVALID;
+  if (n && !h) return fail(c, NRT_ERR_INVALID, "nrtTraverseBatchMotionDevice: NULL hits");
+  return traverse_device<T>(c, {.kind = Query::Motion, .rays = r, .n = n, .opt = o, .stream = (hipStream_t)s, .timed = true, .hits = h, .mask = m,
+                                .times = times});
+}
+template <typename T>
+static nrt_status occluded_motion_device(nrt_ctx *c, const typename Wire<T>::Ray *r, const T *times, uint64_t n, const nrt_trace_options *o,
+                                         uint8_t *m, void *s) {
+  if (!c) return NRT_ERR_INVALID;
+  if (n && !m) return fail(c, NRT_ERR_INVALID, "nrtOccludedBatchMotionDevice: NULL mask");
+  return traverse_device<T>(c, {.kind = Query::MotionOcclusion, .rays = r, .n = n, .opt = o, .stream = (hipStream_t)s, .timed = true, .mask = m,
+                                .times = times});
+}
+
 // Per-ray skip ids (include/nanort_hip.h): the entry points above with one skip id per ray; a NULL array is the call above itself.
 template <typename T>
 static nrt_status traverse_skip_device(nrt_ctx *c, const typename Wire<T>::Ray *r, uint64_t n, const nrt_trace_options *o, const uint32_t *ids,
@@ -1773,6 +1883,45 @@ nrt_status nrtMultiHitTraverseBatchDevice_f32(nrt_ctx *c, const nrt_ray_f32 *r, 
 nrt_status nrtMultiHitTraverseBatchDevice_f64(nrt_ctx *c, const nrt_ray_f64 *r, uint64_t n, uint32_t k, const nrt_trace_options *o,
                                               nrt_hit_f64 *h, uint32_t *cnt, void *s) {
   return multihit_device<double>(c, r, n, k, o, h, cnt, (hipStream_t)s);
+}
+
+nrt_status nrtSetMeshMotion_f32(nrt_ctx *c, const float *v, size_t stride) { return set_mesh_motion<float>(c, v, 0, stride, false, nullptr); }
+nrt_status nrtSetMeshMotion_f64(nrt_ctx *c, const double *v, size_t stride) { return set_mesh_motion<double>(c, v, 0, stride, false, nullptr); }
+nrt_status nrtSetMeshMotionDevice_f32(nrt_ctx *c, const float *v, uint32_t nv, size_t stride, void *s) {
+  return set_mesh_motion<float>(c, v, nv, stride, true, (hipStream_t)s);
+}
+nrt_status nrtSetMeshMotionDevice_f64(nrt_ctx *c, const double *v, uint32_t nv, size_t stride, void *s) {
+  return set_mesh_motion<double>(c, v, nv, stride, true, (hipStream_t)s);
+}
+nrt_status nrtTraverseBatchMotion_f32(nrt_ctx *c, const nrt_ray_f32 *r, const float *t, uint64_t n, const nrt_trace_options *o, nrt_hit_f32 *h,
+                                      uint8_t *m) {
+  return traverse_motion_host<float>(c, r, t, n, o, h, m);
+}
+nrt_status nrtTraverseBatchMotion_f64(nrt_ctx *c, const nrt_ray_f64 *r, const double *t, uint64_t n, const nrt_trace_options *o, nrt_hit_f64 *h,
+                                      uint8_t *m) {
+  return traverse_motion_host<double>(c, r, t, n, o, h, m);
+}
+nrt_status nrtTraverseBatchMotionDevice_f32(nrt_ctx *c, const nrt_ray_f32 *r, const float *t, uint64_t n, const nrt_trace_options *o,
+                                            nrt_hit_f32 *h, uint8_t *m, void *s) {
+  return traverse_motion_device<float>(c, r, t, n, o, h, m, s);
+}
+nrt_status nrtTraverseBatchMotionDevice_f64(nrt_ctx *c, const nrt_ray_f64 *r, const double *t, uint64_t n, const nrt_trace_options *o,
+                                            nrt_hit_f64 *h, uint8_t *m, void *s) {
+  return traverse_motion_device<double>(c, r, t, n, o, h, m, s);
+}
+nrt_status nrtOccludedBatchMotion_f32(nrt_ctx *c, const nrt_ray_f32 *r, const float *t, uint64_t n, const nrt_trace_options *o, uint8_t *m) {
+  return occluded_host<float>(c, r, n, o, m, nullptr, Query::MotionOcclusion, t);
+}
+nrt_status nrtOccludedBatchMotion_f64(nrt_ctx *c, const nrt_ray_f64 *r, const double *t, uint64_t n, const nrt_trace_options *o, uint8_t *m) {
+  return occluded_host<double>(c, r, n, o, m, nullptr, Query::MotionOcclusion, t);
+}
+nrt_status nrtOccludedBatchMotionDevice_f32(nrt_ctx *c, const nrt_ray_f32 *r, const float *t, uint64_t n, const nrt_trace_options *o, uint8_t *m,
+                                            void *s) {
+  return occluded_motion_device<float>(c, r, t, n, o, m, s);
+}
+nrt_status nrtOccludedBatchMotionDevice_f64(nrt_ctx *c, const nrt_ray_f64 *r, const double *t, uint64_t n, const nrt_trace_options *o, uint8_t *m,
+                                            void *s) {
+  return occluded_motion_device<double>(c, r, t, n, o, m, s);
 }
 
 nrt_status nrtRefit_f32(nrt_ctx *c, const float *v, size_t stride) { return refit<float>(c, v, stride, false, nullptr); }

@@ -76,8 +76,10 @@ struct __attribute__((packed, aligned(4))) Vec3Of { // three consecutive element
   E x, y, z;
 };
 
-template <typename T>
-__global__ __launch_bounds__(256) void k_prim_records(const T *__restrict__ verts,
+// MOTION (triangles with a second vertex keyframe `verts1`: DESIGN.md 3.9): the kind's rule applied to keyframe 0 and to keyframe 1;
+// the box is the tmin / tmax of the two, the SAH position (c0 + c1) * T(0.5).  With verts1 == verts these are the plain records.
+template <typename T, bool MOTION>
+__global__ __launch_bounds__(256) void k_prim_records(const T *__restrict__ verts, const T *__restrict__ verts1,
                                                       const uint32_t *__restrict__ faces,
                                                       const T *__restrict__ radii, int kind, uint32_t n,
                                                       const uint32_t *__restrict__ prim_map,
@@ -104,10 +106,24 @@ __global__ __launch_bounds__(256) void k_prim_records(const T *__restrict__ vert
       v1 = *reinterpret_cast<const Vec3Of<T> *>(verts + 3 * (size_t)f.y);
       v2 = *reinterpret_cast<const Vec3Of<T> *>(verts + 3 * (size_t)f.z);
     }
+    Vec3Of<T> w0 = v0, w1 = v0, w2 = v0;
+    if constexpr (MOTION) { // (a motion context is a triangle context: faces != nullptr)
+      w0 = *reinterpret_cast<const Vec3Of<T> *>(verts1 + 3 * (size_t)f.x);
+      w1 = *reinterpret_cast<const Vec3Of<T> *>(verts1 + 3 * (size_t)f.y);
+      w2 = *reinterpret_cast<const Vec3Of<T> *>(verts1 + 3 * (size_t)f.z);
+    }
 #pragma unroll
     for (int k = 0; k < 3; k++) {
       const T p0 = k == 0 ? v0.x : (k == 1 ? v0.y : v0.z), p1 = k == 0 ? v1.x : (k == 1 ? v1.y : v1.z), p2 = k == 0 ? v2.x : (k == 1 ? v2.y : v2.z);
       prim_box_axis<T>(faces != nullptr, kind, i, k, verts, radii, p0, p1, p2, r.bmin[k], r.bmax[k], r.c[k]);
+      if constexpr (MOTION) {
+        const T q0 = k == 0 ? w0.x : (k == 1 ? w0.y : w0.z), q1 = k == 0 ? w1.x : (k == 1 ? w1.y : w1.z), q2 = k == 0 ? w2.x : (k == 1 ? w2.y : w2.z);
+        T bmin1, bmax1, c1;
+        prim_box_axis<T>(true, kind, i, k, verts1, radii, q0, q1, q2, bmin1, bmax1, c1);
+        r.bmin[k] = tmin(r.bmin[k], bmin1);
+        r.bmax[k] = tmax(r.bmax[k], bmax1);
+        r.c[k] = (r.c[k] + c1) * T(0.5);
+      }
       lo[k] = tmin(lo[k], r.bmin[k]);
       hi[k] = tmax(hi[k], r.bmax[k]);
       clo[k] = tmin(clo[k], r.c[k]);
@@ -1392,7 +1408,7 @@ struct BuildPlan { // carve-up of the build workspace for n primitives
 // (their grids are upper bounds; the node array is sized for the 2n - 1 nodes a tree over n primitives can have).
 // gpu_build returns once everything is enqueued; gpu_build_result() waits for the final state block.
 template <typename T>
-hipError_t gpu_build(hipStream_t s, const T *d_verts, const uint32_t *d_faces, const T *d_radii, int prim_kind, const uint32_t *d_prim_map, uint32_t n,
+hipError_t gpu_build(hipStream_t s, const T *d_verts, const T *d_verts1, const uint32_t *d_faces, const T *d_radii, int prim_kind, const uint32_t *d_prim_map, uint32_t n,
                      uint32_t min_leaf, uint32_t max_depth, uint32_t bin_size, unsigned build_flags, DevBuf *workspace, DevBuf *nodes_buf,
                      DevBuf *indices_buf, void *pinned, hipEvent_t ev, std::string *err) {
   typedef typename Wire<T>::Node Node;
@@ -1433,7 +1449,10 @@ hipError_t gpu_build(hipStream_t s, const T *d_verts, const uint32_t *d_faces, c
                        (uint32_t)plan.max_active);
     {
       unsigned grid = (unsigned)std::min<size_t>(((size_t)n + 255) / 256, 2048);
-      hipLaunchKernelGGL((k_prim_records<T>), dim3(grid), dim3(256), 0, s, d_verts, d_faces, d_radii, prim_kind, n, d_prim_map, recs[0], scene);
+      if (d_verts1 != nullptr && d_faces != nullptr)
+        hipLaunchKernelGGL((k_prim_records<T, true>), dim3(grid), dim3(256), 0, s, d_verts, d_verts1, d_faces, d_radii, prim_kind, n, d_prim_map, recs[0], scene);
+      else
+        hipLaunchKernelGGL((k_prim_records<T, false>), dim3(grid), dim3(256), 0, s, d_verts, nullptr, d_faces, d_radii, prim_kind, n, d_prim_map, recs[0], scene);
     }
     NRT_RANGE_POP();
     int cur = 0; // buffer holding the ranges of the nodes being split

@@ -54,6 +54,14 @@ hipError_t launch_traverse_multihit(const TraverseArgs<T> &args, uint32_t max_hi
 template <typename T>
 int traverse_multihit_blocks_per_cu();
 
+// ---- motion.hip: the motion-blur walk (a triangle context with a second vertex keyframe) --------------------------------------
+// `tris1`: the LeafTri<T> records of keyframe 1 in leaf order; `times`: one time per ray, or null (every ray at time 0);
+// args.any_hit: the occlusion query
+template <typename T>
+hipError_t launch_traverse_motion(const TraverseArgs<T> &args, const void *tris1, const T *times, unsigned grid, hipStream_t s);
+template <typename T>
+int traverse_motion_blocks_per_cu();
+
 // ---- build.hip --------------------------------------------------------------------------------------------------------
 enum : unsigned { kBuildMorton = 1u, kBuildSubtreeDfs = 2u }; // gpu_build's build_flags: Morton pre-pass, one-node-per-step subtree kernel
 struct BuildResult {
@@ -61,8 +69,9 @@ struct BuildResult {
   uint32_t max_depth, num_leaves, num_branches, max_leaf_count;
 };
 // enqueues a whole build; its size and statistics arrive in `pinned` behind `ev`: gpu_build_result waits for them
+// (`d_verts1`: the second vertex keyframe of a triangle mesh, or null — a primitive's box then holds both keyframes)
 template <typename T>
-hipError_t gpu_build(hipStream_t s, const T *d_verts, const uint32_t *d_faces, const T *d_radii, int prim_kind, const uint32_t *d_prim_map,
+hipError_t gpu_build(hipStream_t s, const T *d_verts, const T *d_verts1, const uint32_t *d_faces, const T *d_radii, int prim_kind, const uint32_t *d_prim_map,
                      uint32_t num_faces, uint32_t min_leaf, uint32_t max_depth, uint32_t bin_size, unsigned build_flags, DevBuf *workspace,
                      DevBuf *nodes_buf, DevBuf *indices_buf, void *pinned, hipEvent_t ev, std::string *err);
 hipError_t gpu_build_result(const void *pinned, hipEvent_t ev, BuildResult *res);
