@@ -1,6 +1,7 @@
-// nanort_amd/csrc/traverse.hip — batched closest-hit traversal of ONE tree for gfx950: the single-level walks (k_traverse, the binary
-// loop; k_traverse_wide, the production kernel, and its variant table) and, at the end of the file, the conversion of a
-// reference-format tree into the WideNode / Wide4Node records they step through (k_wide_count … k_make_wide).
+// nanort_amd/csrc/traverse.hip — batched closest-hit traversal of ONE tree for gfx950: the single-level walks (k_traverse, the
+// closest-hit query of the binary loop that binary_walk_dev.h states; k_traverse_wide, the production kernel, and its variant
+// table) and, at the end of the file, the conversion of a reference-format tree into the WideNode / Wide4Node records they step
+// through (k_wide_count … k_make_wide).
 //
 // Replaces N calls of the reference's BVHAccel<T>::Traverse (nanort.h:2487-2556)
 // with its TriangleIntersector (nanort.h:1014-1229) by one persistent-threads
@@ -16,6 +17,7 @@
 //   Intersect (watertight)   nanort.h:1054-1150 (fp64 edge fallback, tie rules)
 //   Traverse / TestLeafNode  nanort.h:2526-2556, 2374-2407 (near child first,
 //                            hit iff t_best < ray.max_t)
+#include "binary_walk_dev.h"
 #include "kernels.h"
 #include "walk_dev.h"
 
@@ -23,156 +25,73 @@
 
 namespace nrt {
 
-template <typename T, bool COUNT, int STACK>
-__global__ __launch_bounds__(kTraverseBlock) void k_traverse(const TraverseArgs<T> a) {
-  // [depth][thread]: a wave's 64 lanes hit 64 consecutive dwords -> conflict-free.
-  __shared__ uint32_t s_stack[STACK][kTraverseBlock];
+// The closest-hit query of the binary walk (binary_walk_dev.h).  COUNT: the counting pass — nodes fetched, leaves entered, records
+// tested and the deepest stack the reference would have held, per launch.
+template <typename T, bool COUNT>
+struct ClosestQuery : BinaryQuery {
+  unsigned long long c_nodes = 0, c_leaves = 0, c_tris = 0;
+  unsigned c_stack = 0; // (a depth: 32 bits in the lane, widened for the atomic — the fp64 instantiation sits on the 96-register edge of five waves)
+  uint32_t skip = 0; // the skip id of the leaves the wave is taking
 
-  typedef typename Wire<T>::Node Node;
-  typedef typename Wire<T>::Ray Ray;
-  typedef typename Wire<T>::Hit Hit;
-
-  const unsigned tid = threadIdx.x;
-  const unsigned lane = lane_id();
-  const unsigned gslot = blockIdx.x * kTraverseBlock + tid;
-  const bool cull = a.cull_back_face != 0;
-  const LaneStack<StackRef, STACK, TraverseArgs<T>> stk = {a, tid, gslot};
-
-  Lane<T> L;
-  uint32_t rid = kInvalid; // ray this lane is working on
-  uint32_t cur = 0;        // node to visit next (LANE_TRAV)
-  uint32_t leaf_first = 0, leaf_cnt = 0; // pending leaf (LANE_LEAF)
-  int state = LANE_IDLE;
-  int sp = 0; // entries on this lane's stack
-
-  Claim ck; // wave-uniform claimed range
-  claim_init<T>(a, ck);
-  if (blockIdx.x == 0 && threadIdx.x < kMaxParts) a.next_cursor[kCursorStrideWords * threadIdx.x] = 0u;
-
-  unsigned long long c_nodes = 0, c_leaves = 0, c_tris = 0, c_stack = 0;
-
-  // Pop the next node, or finish the ray when the stack is empty:
-  // PostTraversal (nanort.h:1205-1211) with the strict final predicate (:2552).
-  // (A macro with select-style updates: every state variable is assigned on both
-  // paths, which keeps them all in registers.)
-#define NRT_POP_OR_FINISH()                                                              \
-  do {                                                                                   \
-    const bool fin_ = (sp == 0);                                                         \
-    if (fin_) {                                                                          \
-      const bool hit_ = L.hit_t < L.max_t;                                               \
-      if (a.hits) {                                                                      \
-        Hit h_;                                                                          \
-        h_.u = hit_ ? L.u : T(0);                                                        \
-        h_.v = hit_ ? L.v : T(0);                                                        \
-        h_.t = hit_ ? L.hit_t : L.max_t;                                                 \
-        h_.prim_id = hit_ ? L.prim : kInvalid;                                           \
-        store_hit_nt<T>(a.hits + rid, h_);                                               \
-      }                                                                                  \
-      if (a.mask) a.mask[rid] = hit_ ? 1 : 0;                                            \
-    }                                                                                    \
-    if (!fin_) stk.load(s_stack, sp - 1, cur);                                           \
-    sp = fin_ ? sp : sp - 1;                                                             \
-    rid = fin_ ? kInvalid : rid;                                                         \
-    state = fin_ ? LANE_IDLE : LANE_TRAV;                                                \
-  } while (0)
-
-  for (;;) {
-    // ---- hand new rays to idle lanes (ballot rank inside the wave's chunk) ----
-    unsigned long long idle = __ballot(state == LANE_IDLE);
-    if (!ck.exhausted && (unsigned)__builtin_popcountll(idle) >= a.refill_min) {
-      while (idle != 0ull && !ck.exhausted) {
-        if (ck.next == ck.end && !claim_chunk<T>(a, ck, lane, __builtin_ctzll(idle))) break;
-        const unsigned want = (unsigned)__builtin_popcountll(idle);
-        const unsigned avail = ck.end - ck.next;
-        const unsigned take = want < avail ? want : avail;
-        const unsigned rank = (unsigned)__builtin_popcountll(idle & ((1ull << lane) - 1ull));
-        if (state == LANE_IDLE && rank < take) {
-          rid = ck.next + rank;
-          const Ray r = load_ray<T>(as_global(a.rays) + rid, a.debug_flags);
-          lane_init<T>(L, r);
-          cur = 0;
-          sp = 0;
-          state = LANE_TRAV;
-          if (COUNT) c_stack = c_stack > 1ull ? c_stack : 1ull;
-        }
-        ck.next += take;
-        idle = __ballot(state == LANE_IDLE);
-      }
-    }
-    if (idle == ~0ull) {
-      if (ck.exhausted) break; // nothing left anywhere in this wave
-      continue;             // (cannot happen: refill_min <= 64)
-    }
-
-    // ---- phase 1: inner nodes, until this lane reaches a leaf or finishes -----------
-    while (state == LANE_TRAV) {
-      const Node nd = a.nodes[cur];
-      if (COUNT) c_nodes++;
-      if (slab_test<T>(L, nd.bmin, nd.bmax)) {
-        if (nd.flag == 0) {
-          const int near = L.sign(nd.axis);
-          const uint32_t far_child = near ? nd.data[0] : nd.data[1];
-          cur = near ? nd.data[1] : nd.data[0];
-          // push far; near stays in `cur` (it would be popped next anyway: nanort.h:2542-2543)
-          stk.store(s_stack, sp, far_child);
-          sp++;
-          if (COUNT) {
-            // the reference holds near+far on its stack at this point
-            const unsigned long long need = (unsigned long long)sp + 1ull;
-            c_stack = need > c_stack ? need : c_stack;
-          }
-        } else {
-          leaf_cnt = nd.data[0];
-          leaf_first = nd.data[1];
-          state = LANE_LEAF;
-          if (COUNT) c_leaves++;
-        }
-      } else {
-        NRT_POP_OR_FINISH();
-      }
-      // leave early when too few lanes are still walking inner nodes
-      if ((unsigned)__builtin_popcountll(__ballot(state == LANE_TRAV)) < a.trav_min) break;
-    }
-
-    // ---- phase 2: lanes holding a leaf test its triangles together ------------------
-    if (__ballot(state == LANE_LEAF) != 0ull) {
-      const uint32_t cnt = state == LANE_LEAF ? leaf_cnt : 0u;
-      uint32_t skip = a.skip_prim;
-      if constexpr (!COUNT) // (the counting pass takes no ids: api.hip)
-        if (a.skip_ids != nullptr && state == LANE_LEAF) skip = a.skip_ids[rid]; // per-ray skip ids (common.h): the id of the ray the lane holds NOW
-      for (uint32_t i = 0; __ballot(i < cnt) != 0ull; i++) {
-        if (i < cnt) {
-          const LeafTri<T> tri = a.tris[leaf_first + i];
-          if (COUNT) c_tris++;
-          tri_test<T>(L, tri, true, a.range0, a.range1, skip, cull);
-        }
-      }
-      if (state == LANE_LEAF) NRT_POP_OR_FINISH();
+  __device__ __forceinline__ typename Wire<T>::Ray load(const TraverseArgs<T> &a, uint32_t rid) const {
+    return load_ray<T>(as_global(a.rays) + rid, a.debug_flags);
+  }
+  __device__ __forceinline__ void begin(const TraverseArgs<T> &, uint32_t) {
+    if (COUNT) c_stack = c_stack > 1u ? c_stack : 1u;
+  }
+  __device__ __forceinline__ void node() {
+    if (COUNT) c_nodes++;
+  }
+  __device__ __forceinline__ void pushed(int sp) {
+    if (COUNT) {
+      // the reference holds near+far on its stack at this point
+      const unsigned need = (unsigned)sp + 1u;
+      c_stack = need > c_stack ? need : c_stack;
     }
   }
-
-  if (COUNT) {
-    // wave reduction, then one atomic per wave per counter
+  __device__ __forceinline__ void leaf() {
+    if (COUNT) c_leaves++;
+  }
+  __device__ __forceinline__ void enter_leaves(const TraverseArgs<T> &a, uint32_t rid, bool at_leaf) {
+    skip = a.skip_prim;
+    if constexpr (!COUNT) // (the counting pass takes no ids: api.hip)
+      if (a.skip_ids != nullptr && at_leaf) skip = a.skip_ids[rid]; // per-ray skip ids (common.h): the id of the ray the lane holds NOW
+  }
+  __device__ __forceinline__ void record(const TraverseArgs<T> &a, Lane<T> &L, uint32_t, uint32_t k) {
+    const LeafTri<T> tri = a.tris[k];
+    if (COUNT) c_tris++;
+    tri_test<T>(L, tri, true, a.range0, a.range1, skip, a.cull_back_face != 0);
+  }
+  __device__ __forceinline__ void finish(const TraverseArgs<T> &a, const Lane<T> &L, uint32_t rid) const { store_closest_hit<T>(a, L, rid); }
+  // wave reduction, then one atomic per wave per counter
+  __device__ __forceinline__ void after(const TraverseArgs<T> &a, unsigned lane) {
+    if (!COUNT) return;
     for (int off = 32; off > 0; off >>= 1) {
       c_nodes += __shfl_xor(c_nodes, off);
       c_leaves += __shfl_xor(c_leaves, off);
       c_tris += __shfl_xor(c_tris, off);
-      unsigned long long o = __shfl_xor(c_stack, off);
+      const unsigned o = __shfl_xor(c_stack, off);
       c_stack = o > c_stack ? o : c_stack;
     }
     if (lane == 0) {
       atomicAdd(&a.counters[0], c_nodes);
       atomicAdd(&a.counters[1], c_leaves);
       atomicAdd(&a.counters[2], c_tris);
-      atomicMax(&a.counters[3], c_stack);
+      atomicMax(&a.counters[3], (unsigned long long)c_stack);
     }
   }
-#undef NRT_POP_OR_FINISH
+};
+
+template <typename T, bool COUNT, int STACK>
+__global__ __launch_bounds__(kTraverseBlock) void k_traverse(const TraverseArgs<T> a) {
+  // [depth][thread]: a wave's 64 lanes hit 64 consecutive dwords -> conflict-free.
+  __shared__ uint32_t s_stack[STACK][kTraverseBlock];
+  binary_walk<T, STACK>(a, s_stack, ClosestQuery<T, COUNT>());
 }
 
 // ---------------------------------------------------------------------------
 // Production kernel: same traversal ORDER and same culling decisions as the
-// binary loop above (hence the same hit records, ties included), but each step
+// binary loop of k_traverse (hence the same hit records, ties included), but each step
 // fetches one WideNode and tests both children.  A child that passes its slab
 // test is entered at once (near first) or pushed with its t_min; a popped entry
 // is entered iff t_min <= hit_t, which is exactly the reference's test at pop

@@ -1,6 +1,8 @@
 // nanort_amd/csrc/traverse_dev.h — the device pieces of the binary-loop traversal that more than one kernel file uses
-// (traverse.hip and scene_kernels.hip through walk_dev.h, multihit.hip): ray setup, slab and primitive tests, ray claims, streaming loads / stores, completion
-// records.  Everything here is a template or forceinline device code, so each including file compiles its own copy.
+// (traverse.hip and scene_kernels.hip through walk_dev.h; traverse.hip, multihit.hip and motion.hip through binary_walk_dev.h, which
+// states the loop itself): ray setup, slab and primitive tests, ray claims, streaming loads / stores, completion records, the lane
+// stack and, at the end, the host side of a persistent launch.  Everything here is a template, forceinline device code or a static
+// host function, so each including file compiles its own copy.
 #pragma once
 
 #include "common.h"
@@ -782,7 +784,7 @@ __device__ __forceinline__ void done_end(const TraverseArgs<T> &a, unsigned lane
 // guarded push and every pop of every walk goes through load / store.
 // (The block's LDS array is an argument of load / store, not a member: a pointer to LDS held in a struct reaches the code
 // generator as a generic pointer, and the pop becomes a flat load whose address is selected between LDS and global memory.)
-struct StackRef { // a bare node reference (the binary loops: k_traverse, k_traverse_multihit)
+struct StackRef { // a bare node reference (the binary walk, binary_walk_dev.h: k_traverse, k_traverse_multihit, k_traverse_motion)
   typedef uint32_t type;
   static constexpr bool kHasTmin = false;
 };
@@ -815,7 +817,21 @@ struct LaneStack {
   }
 };
 
-// Lane states of the while-while loop.
+// Lane states of the while-while loop (binary_walk_dev.h).
 enum : int { LANE_IDLE = 0, LANE_TRAV = 1, LANE_LEAF = 2 };
+
+// The host side of every persistent launch of the walks: the kernel is picked once, as a pointer, and the launch and the
+// occupancy query that sizes its grid go through that pointer.
+template <typename A>
+static void launch_persistent(const void *kernel, unsigned grid, const A &args, hipStream_t s) {
+  void *params[] = {(void *)&args};
+  (void)hipLaunchKernel(kernel, dim3(grid), dim3(kTraverseBlock), params, 0, s); // (the callers return hipGetLastError())
+}
+// Resident blocks per CU of `kernel`, 8 at the most; `fallback` where the runtime cannot say.
+static int resident_blocks(const void *kernel, int fallback) {
+  int n = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, kTraverseBlock, 0) != hipSuccess || n < 1) n = fallback;
+  return n > 8 ? 8 : n;
+}
 
 } // namespace nrt

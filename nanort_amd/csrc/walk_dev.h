@@ -1,27 +1,13 @@
 // nanort_amd/csrc/walk_dev.h — the moves every WIDE walk shares (a step tests the two boxes of a WideNode or the four of a
 // Wide4Node; stack entries carry their t_min): the box tests, the stack entry, the pop / push / step macros and their contract, the
-// leaf items, the typed global record load, and the host side of a persistent launch.  Included by the two files that hold wide
-// walks: traverse.hip (k_traverse_wide) and scene_kernels.hip (k_scene_trace, k_scene_walk).  What the binary loops need as well
-// (ray setup, slab and primitive tests, LaneStack) is traverse_dev.h's.
+// leaf items and the typed global record load.  Included by the two files that hold wide walks: traverse.hip (k_traverse_wide) and
+// scene_kernels.hip (k_scene_trace, k_scene_walk).  What the binary walk (binary_walk_dev.h) needs as well — ray setup, slab and
+// primitive tests, LaneStack, the host side of a persistent launch — is traverse_dev.h's.
 #pragma once
 
 #include "traverse_dev.h"
 
 namespace nrt {
-
-// The host side of every persistent launch of the including files: the kernel is picked once, as a pointer, and the launch and the
-// occupancy query that sizes its grid go through that pointer.
-template <typename A>
-static void launch_persistent(const void *kernel, unsigned grid, const A &args, hipStream_t s) {
-  void *params[] = {(void *)&args};
-  (void)hipLaunchKernel(kernel, dim3(grid), dim3(kTraverseBlock), params, 0, s); // (the callers return hipGetLastError())
-}
-// Resident blocks per CU of `kernel`, 8 at the most; `fallback` where the runtime cannot say.
-static int resident_blocks(const void *kernel, int fallback) {
-  int n = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, kTraverseBlock, 0) != hipSuccess || n < 1) n = fallback;
-  return n > 8 ? 8 : n;
-}
 
 // Lane states of the wide walks.
 enum : int { W_IDLE = 0, W_TRAV = 1, W_LEAF = 2, W_POP = 3 };

@@ -1,0 +1,74 @@
+"""The three kernels that run the binary walk (nanort_amd/csrc/binary_walk_dev.h) under odd thresholds and work splits: closest hit
+with the literal walk (tunable wide = 0, k_traverse), multi-hit (k_traverse_multihit) and motion closest hit / occlusion
+(k_traverse_motion).  The walk's refill gate, its early exit from the inner-node loop and the static / dynamic hand-out of rays are
+one piece of code under all three; whatever the setting, every ray is traced exactly once and its walk is its own, so records,
+masks and counts equal the default configuration's byte for byte.  (The defaults themselves are tied to the oracle by
+test_gpu_traverse.py, test_gpu_launch_variants.py, test_gpu_skip_ids.py, test_gpu_multihit.py and test_gpu_motion.py;
+test_work_distribution_tunables_cover_every_ray sweeps the same settings on the default wide walk.)"""
+import numpy as np
+import pytest
+
+import motion_fixture as mf
+from nanort_amd import BVHAccel, MotionTriangleMesh, TriangleMesh, scenes
+
+pytestmark = pytest.mark.gpu
+
+K = 3
+# (97, 13): more than one wave, more than one chunk, a ragged end; (1, 1): one ray, 63 idle lanes, every other wave with nothing to claim
+SIZES = [(97, 13), (1, 1)]
+COMBOS = [dict(refill_min=1, trav_min=1), dict(refill_min=64, trav_min=64), dict(static_pct=0, chunk=16, parts=3), dict(static_pct=100),
+          dict(blocks_per_cu=1, static_bands=3)]
+
+
+def run_walks(plain, moving, rays, times):
+    """name -> bytes of everything the walk's launch wrote."""
+    out = {}
+    h, m = plain.TraverseBatch(rays)
+    assert plain.LastKernelName() == "nrt::k_traverse<float>"
+    out["closest"] = h.tobytes() + m.tobytes()
+    h, c = plain.MultiHitTraverseBatch(rays, K)
+    assert plain.LastKernelName() == "nrt::k_traverse_multihit<float>"
+    out["multihit"] = h.tobytes() + c.tobytes()
+    h, m = moving.TraverseBatchMotion(rays, times)
+    assert moving.LastKernelName() == "nrt::k_traverse_motion<float>"
+    out["motion"] = h.tobytes() + m.tobytes()
+    out["motion occlusion"] = moving.OccludedBatchMotion(rays, times).tobytes()
+    return out
+
+
+@pytest.fixture(scope="module")
+def world():
+    v, f = scenes.plane(120, 60)
+    v = np.ascontiguousarray(v, dtype=np.float32)
+    plain, moving = BVHAccel(np.float32), BVHAccel(np.float32)
+    assert plain.Build(f.shape[0], TriangleMesh(v, f))
+    plain.SetTunable("wide", 0)
+    assert moving.Build(f.shape[0], MotionTriangleMesh(v, mf.deformations(v)["wave"], f))
+    cases = {}
+    for size in SIZES:
+        rays = scenes.camera_rays(*size)
+        times = mf.assign_times(rays.shape[0], np.float32)
+        cases[size] = (rays, times, run_walks(plain, moving, rays, times))  # under the default tunables, computed once
+    h, m = plain.TraverseBatch(cases[SIZES[0]][0])
+    assert 0 < int(m.sum())  # (not vacuous: rays hit the mesh)
+    yield plain, moving, cases
+    plain.close()
+    moving.close()
+
+
+@pytest.mark.parametrize("size", SIZES, ids=lambda s: "%dx%d" % s)
+@pytest.mark.parametrize("combo", COMBOS, ids=lambda c: ",".join("%s=%d" % kv for kv in c.items()))
+def test_thresholds_and_work_split_leave_every_record_as_it_is(world, combo, size):
+    plain, moving, cases = world
+    rays, times, ref = cases[size]
+    saved = [(a, k, a.GetTunable(k)) for a in (plain, moving) for k in combo]
+    try:
+        for a in (plain, moving):
+            for k, val in combo.items():
+                a.SetTunable(k, val)
+        got = run_walks(plain, moving, rays, times)
+    finally:
+        for a, k, val in saved:
+            a.SetTunable(k, val)
+    for name in ref:
+        assert got[name] == ref[name], (name, size, combo)
