@@ -35,6 +35,11 @@ def _p(a):
     return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
 
 
+def _opts(options):
+    """The caller's trace options as one TRACE_OPTIONS record (None: the library's defaults)."""
+    return None if options is None else np.asarray(options, dtype=TRACE_OPTIONS).reshape(1)
+
+
 class TriangleMesh:
     """nanort::TriangleMesh<T> (reference nanort.h:922-991): caller-owned flat arrays."""
 
@@ -256,6 +261,10 @@ class BVHAccel:
             return torch.cuda.current_stream(self.device).cuda_stream
         return stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
 
+    def _n_rays(self, d_rays):
+        """Rays of the accel's precision a device tensor of raw bytes (or of any element size) holds."""
+        return d_rays.numel() * d_rays.element_size() // ray_dtype(self.real).itemsize
+
     def _on_device(self, t, what):
         if t.device.type != "cuda" or t.device.index != self.device:
             raise ValueError("%s must live on cuda:%d" % (what, self.device))
@@ -476,10 +485,7 @@ class BVHAccel:
             raise ValueError("vertices hold %d rows; the mesh has %d vertices" % (d_vertices.shape[0], nv))
         if d_vertices.device.type != "cuda" or d_vertices.device.index != self.device:
             raise ValueError("vertices must live on cuda:%d" % self.device)
-        if stream is None:
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-        elif hasattr(stream, "cuda_stream"):
-            stream = stream.cuda_stream
+        stream = self._stream_handle(stream)
         stride = d_vertices.stride(0) * d_vertices.element_size()
         self._check(getattr(self._L, "nrtRefitDevice_" + self._s)(self._h, d_vertices.data_ptr(), stride, stream))
 
@@ -552,8 +558,7 @@ class BVHAccel:
         rays = np.ascontiguousarray(rays, dtype=ray_dtype(self.real))
         n = rays.shape[0]
         mask = np.zeros((n,), dtype=np.uint8)
-        if options is not None:
-            options = np.asarray(options, dtype=TRACE_OPTIONS).reshape(1)
+        options = _opts(options)
         if skip_prim_ids is not None:  # (the library refuses the primitive kinds that have no skip id)
             ids = self._host_skip_ids(skip_prim_ids, n)
             hits = np.zeros((n,), dtype=hit_dtype(self.real))
@@ -580,20 +585,16 @@ class BVHAccel:
     def TraverseBatchDevice(self, d_rays, d_hits, d_mask=None, options=None, stream=None, skip_prim_ids=None):
         """Same on HBM-resident torch uint8 tensors (raw PODs), async on `stream`
         (default: torch's current stream).  `skip_prim_ids`: a device tensor of one uint32 per ray (nrtTraverseBatchSkipDevice)."""
-        import torch
-
         cyl, curves = isinstance(self._mesh, CylinderGeometry), self._is_curves()
-        rsz, hsz = ray_dtype(self.real).itemsize, (28 if cyl else (40 if curves else hit_dtype(self.real).itemsize))
-        n = d_rays.numel() * d_rays.element_size() // rsz
+        hsz = 28 if cyl else (40 if curves else hit_dtype(self.real).itemsize)
+        n = self._n_rays(d_rays)
         assert d_hits.numel() * d_hits.element_size() >= n * hsz
-        if stream is None:
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-        if options is not None:
-            options = np.asarray(options, dtype=TRACE_OPTIONS).reshape(1)
+        stream = self._stream_handle(stream)
+        options = _opts(options)
         if skip_prim_ids is not None:
             self._check(getattr(self._L, "nrtTraverseBatchSkipDevice_" + self._s)(
                 self._h, d_rays.data_ptr(), n, _p(options), self._device_skip_ids(skip_prim_ids, n), d_hits.data_ptr(),
-                None if d_mask is None else d_mask.data_ptr(), self._stream_handle(stream)))
+                None if d_mask is None else d_mask.data_ptr(), stream))
             return n
         if curves:
             self._check(self._L.nrtTraverseBatchCurvesDevice_f32(
@@ -616,9 +617,7 @@ class BVHAccel:
         torch uint8 tensors — walked by ONE persistent launch (asynchronous on `stream`).  A batch marked "occlusion" is an
         occlusion query: only its d_mask is written (d_hits may be None).  Returns the ray counts.  `skip_prim_ids`: a list with
         one entry per batch, a device tensor of one uint32 per ray or None (that batch uses options.skip_prim_id)."""
-        import torch
-
-        rsz, hsz = ray_dtype(self.real).itemsize, hit_dtype(self.real).itemsize
+        hsz = hit_dtype(self.real).itemsize
         nb = len(batches)
         rays = (ctypes.c_void_p * nb)()
         hits = (ctypes.c_void_p * nb)()
@@ -627,23 +626,21 @@ class BVHAccel:
         flags = (ctypes.c_uint32 * nb)()
         for k, b in enumerate(batches):
             d_rays, d_hits, d_mask = b[0], b[1], b[2]
-            n = b[3] if len(b) > 3 and b[3] is not None else d_rays.numel() * d_rays.element_size() // rsz
+            n = b[3] if len(b) > 3 and b[3] is not None else self._n_rays(d_rays)
             occ = len(b) > 4 and b[4] == "occlusion"
             assert occ or d_hits.numel() * d_hits.element_size() >= n * hsz
             flags[k] = 1 if occ else 0
             rays[k], hits[k], counts[k] = d_rays.data_ptr(), (None if d_hits is None else d_hits.data_ptr()), n
             masks[k] = None if d_mask is None else d_mask.data_ptr()
-        if stream is None:
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-        if options is not None:
-            options = np.asarray(options, dtype=TRACE_OPTIONS).reshape(1)
+        stream = self._stream_handle(stream)
+        options = _opts(options)
         if skip_prim_ids is not None:
             assert len(skip_prim_ids) == nb, "skip_prim_ids: one entry per batch"
             ids = (ctypes.c_void_p * nb)()
             for k, t in enumerate(skip_prim_ids):
                 ids[k] = None if t is None else self._device_skip_ids(t, counts[k])
             self._check(getattr(self._L, "nrtTraverseBatchesSkipDevice_" + self._s)(self._h, nb, rays, counts, _p(options), ids, hits, masks, flags,
-                                                                                  self._stream_handle(stream)))
+                                                                                  stream))
             return [int(c) for c in counts]
         self._check(getattr(self._L, "nrtTraverseBatchesDevice_" + self._s)(self._h, nb, rays, counts, _p(options), hits, masks, flags, stream))
         return [int(c) for c in counts]
@@ -671,8 +668,7 @@ class BVHAccel:
             rays[k], counts[k], flags[k] = (r.ctypes.data if r.shape[0] else None), r.shape[0], (1 if occ else 0)
             hits[k] = None if (occ or not r.shape[0]) else h.ctypes.data
             masks[k] = m.ctypes.data if r.shape[0] else None
-        if options is not None:
-            options = np.asarray(options, dtype=TRACE_OPTIONS).reshape(1)
+        options = _opts(options)
         if skip_prim_ids is not None:
             assert len(skip_prim_ids) == nb, "skip_prim_ids: one entry per batch"
             ids = (ctypes.c_void_p * nb)()
@@ -694,8 +690,7 @@ class BVHAccel:
         `skip_prim_ids`: as for TraverseBatch (nrtOccludedBatchSkip; triangle meshes only: raises on another kind)."""
         rays = np.ascontiguousarray(rays, dtype=ray_dtype(self.real))
         mask = np.zeros((rays.shape[0],), dtype=np.uint8)
-        if options is not None:
-            options = np.asarray(options, dtype=TRACE_OPTIONS).reshape(1)
+        options = _opts(options)
         if self._is_custom_kind():
             if skip_prim_ids is not None:
                 raise ValueError("skip_prim_ids: triangle meshes only (the sphere, cylinder and curve intersectors have no skip id)")
@@ -709,23 +704,19 @@ class BVHAccel:
         return mask
 
     def OccludedBatchDevice(self, d_rays, d_mask, options=None, stream=None, skip_prim_ids=None):
-        import torch
-
-        n = d_rays.numel() * d_rays.element_size() // ray_dtype(self.real).itemsize
+        n = self._n_rays(d_rays)
         assert d_mask.numel() >= n
-        if stream is None:
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-        if options is not None:
-            options = np.asarray(options, dtype=TRACE_OPTIONS).reshape(1)
+        stream = self._stream_handle(stream)
+        options = _opts(options)
         if self._is_custom_kind():  # (as OccludedBatch)
             if skip_prim_ids is not None:
                 raise ValueError("skip_prim_ids: triangle meshes only (the sphere, cylinder and curve intersectors have no skip id)")
-            self._check(self._L.nrtOccludedBatchPrimsDevice_f32(self._h, d_rays.data_ptr(), n, _p(options), d_mask.data_ptr(), self._stream_handle(stream)))
+            self._check(self._L.nrtOccludedBatchPrimsDevice_f32(self._h, d_rays.data_ptr(), n, _p(options), d_mask.data_ptr(), stream))
             return n
         if skip_prim_ids is not None:
             self._check(getattr(self._L, "nrtOccludedBatchSkipDevice_" + self._s)(self._h, d_rays.data_ptr(), n, _p(options),
                                                                                 self._device_skip_ids(skip_prim_ids, n), d_mask.data_ptr(),
-                                                                                self._stream_handle(stream)))
+                                                                                stream))
             return n
         self._check(getattr(self._L, "nrtOccludedBatchDevice_" + self._s)(self._h, d_rays.data_ptr(), n, _p(options), d_mask.data_ptr(), stream))
         return n
@@ -754,19 +745,17 @@ class BVHAccel:
         t = self._host_times(times, n)
         hits = np.zeros((n,), dtype=hit_dtype(self.real))
         mask = np.zeros((n,), dtype=np.uint8)
-        if options is not None:
-            options = np.asarray(options, dtype=TRACE_OPTIONS).reshape(1)
+        options = _opts(options)
         self._check(getattr(self._L, "nrtTraverseBatchMotion_" + self._s)(self._h, _p(rays), _p(t), n, _p(options), _p(hits), _p(mask)))
         return hits, mask
 
     def TraverseBatchMotionDevice(self, d_rays, d_times, d_hits, d_mask=None, options=None, stream=None):
         """Same on HBM-resident torch tensors (raw PODs; `d_times`: one value of the accel's precision per ray, or None),
         asynchronous on `stream` (default: torch's current stream).  Returns n."""
-        rsz, hsz = ray_dtype(self.real).itemsize, hit_dtype(self.real).itemsize
-        n = d_rays.numel() * d_rays.element_size() // rsz
+        hsz = hit_dtype(self.real).itemsize
+        n = self._n_rays(d_rays)
         assert d_hits.numel() * d_hits.element_size() >= n * hsz
-        if options is not None:
-            options = np.asarray(options, dtype=TRACE_OPTIONS).reshape(1)
+        options = _opts(options)
         self._check(getattr(self._L, "nrtTraverseBatchMotionDevice_" + self._s)(
             self._h, d_rays.data_ptr(), self._device_times(d_times, n), n, _p(options), d_hits.data_ptr(),
             None if d_mask is None else d_mask.data_ptr(), self._stream_handle(stream)))
@@ -778,16 +767,14 @@ class BVHAccel:
         n = rays.shape[0]
         t = self._host_times(times, n)
         mask = np.zeros((n,), dtype=np.uint8)
-        if options is not None:
-            options = np.asarray(options, dtype=TRACE_OPTIONS).reshape(1)
+        options = _opts(options)
         self._check(getattr(self._L, "nrtOccludedBatchMotion_" + self._s)(self._h, _p(rays), _p(t), n, _p(options), _p(mask)))
         return mask
 
     def OccludedBatchMotionDevice(self, d_rays, d_times, d_mask, options=None, stream=None):
-        n = d_rays.numel() * d_rays.element_size() // ray_dtype(self.real).itemsize
+        n = self._n_rays(d_rays)
         assert d_mask.numel() >= n
-        if options is not None:
-            options = np.asarray(options, dtype=TRACE_OPTIONS).reshape(1)
+        options = _opts(options)
         self._check(getattr(self._L, "nrtOccludedBatchMotionDevice_" + self._s)(
             self._h, d_rays.data_ptr(), self._device_times(d_times, n), n, _p(options), d_mask.data_ptr(), self._stream_handle(stream)))
         return n
@@ -799,24 +786,19 @@ class BVHAccel:
         n = rays.shape[0]
         hits = np.zeros((n, max(int(max_hits), 1)), dtype=hit_dtype(self.real))
         counts = np.zeros((n,), dtype=np.uint32)
-        if options is not None:
-            options = np.asarray(options, dtype=TRACE_OPTIONS).reshape(1)
+        options = _opts(options)
         self._check(getattr(self._L, "nrtMultiHitTraverseBatch_" + self._s)(self._h, _p(rays), n, int(max_hits), _p(options), _p(hits), _p(counts)))
         return hits, counts
 
     def MultiHitTraverseBatchDevice(self, d_rays, max_hits, d_hits, d_counts=None, options=None, stream=None):
         """Same on HBM-resident torch tensors (raw PODs: d_hits holds n * max_hits records, d_counts n uint32), asynchronous on
         `stream` (default: torch's current stream).  Returns n."""
-        import torch
-
-        rsz, hsz = ray_dtype(self.real).itemsize, hit_dtype(self.real).itemsize
-        n = d_rays.numel() * d_rays.element_size() // rsz
+        hsz = hit_dtype(self.real).itemsize
+        n = self._n_rays(d_rays)
         assert d_hits.numel() * d_hits.element_size() >= n * int(max_hits) * hsz
         assert d_counts is None or d_counts.numel() * d_counts.element_size() >= n * 4
-        if stream is None:
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-        if options is not None:
-            options = np.asarray(options, dtype=TRACE_OPTIONS).reshape(1)
+        stream = self._stream_handle(stream)
+        options = _opts(options)
         self._check(getattr(self._L, "nrtMultiHitTraverseBatchDevice_" + self._s)(
             self._h, d_rays.data_ptr(), n, int(max_hits), _p(options), d_hits.data_ptr(),
             None if d_counts is None else d_counts.data_ptr(), stream))
@@ -824,11 +806,9 @@ class BVHAccel:
 
     def TraverseCountDevice(self, d_rays, options=None):
         """Work counters (nodes visited, leaves, triangle tests, max stack) of one batch."""
-        rsz = ray_dtype(self.real).itemsize
-        n = d_rays.numel() * d_rays.element_size() // rsz
+        n = self._n_rays(d_rays)
         c = capi.TraceCounters()
-        if options is not None:
-            options = np.asarray(options, dtype=TRACE_OPTIONS).reshape(1)
+        options = _opts(options)
         self._check(
             getattr(self._L, "nrtTraverseCountDevice_" + self._s)(self._h, d_rays.data_ptr(), n, _p(options), ctypes.byref(c))
         )

@@ -1,5 +1,5 @@
 // nanort_amd/csrc/common.h — device-side PODs and launch-argument blocks shared
-// by the gfx950 kernels (traverse.hip, scene_kernels.hip, build.hip) and the C ABI (api.hip, scene.hip).
+// by the gfx950 kernels (traverse.hip, scene_kernels.hip, build.hip) and the C ABI (api_*.hip, scene.hip).
 //
 // The node / ray / hit records are the reference's wire formats
 // (include/nanort_hip.h; reference nanort.h:474-550, 996-1005).  Everything

@@ -6,7 +6,7 @@
 
 #include "common.h"
 
-// ---- api.hip: what the scene and group code may ask of a context ----------------------------------------------------------
+// ---- api_ctx.hip: what the scene and group code may ask of a context ----------------------------------------------------------
 nrt_status nrt_internal_tree_view(nrt_ctx *c, nrt::TreeViewF32 *out);
 uint64_t nrt_internal_generation(const nrt_ctx *c); // counts the context's rebuilds
 int nrt_internal_device(const nrt_ctx *c);

@@ -1,4 +1,4 @@
-// nanort_amd/csrc/launch_plan.h — the integer arithmetic of a traversal launch (api.hip, traverse_device): how large the
+// nanort_amd/csrc/launch_plan.h — the integer arithmetic of a traversal launch (api_query.hip, traverse_device): how large the
 // persistent grid is, how a batch is dealt out to its waves, how deep the overflow stack has to be.  Plain C++ without a HIP
 // include, so that tests/cpp/launch_plan_check.cc can check it on a machine without a GPU: hit records are identical under
 // every plan, so no parity test notices a slip here.  (Which kernel the launch runs: walk_variant.h, in the same style.)

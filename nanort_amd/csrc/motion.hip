@@ -12,7 +12,7 @@
 //   * occlusion (a.any_hit): a ray is settled once hit_t < max_t — the predicate the finish writes as the closest-hit flag; a
 //     settled lane tests no further record and finishes its ray;
 //   * finish: the record and mask stores of k_traverse (store_closest_hit).
-// Like the multi-hit walk the launch publishes no completion record: its slot is closed by an event (api.hip, enqueue_launch).
+// Like the multi-hit walk the launch publishes no completion record: its slot is closed by an event (api_query.hip, enqueue_launch).
 #include "binary_walk_dev.h"
 #include "kernels.h"
 #include "../../include/nanort_motion.h"

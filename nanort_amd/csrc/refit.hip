@@ -11,9 +11,9 @@
 //     (prims.hip)      launch_gather_vertices: the caller's strided vertices -> the context's tight xyz
 //     k_refit_leaves   every reachable leaf: min / max over each coordinate of its triangles, in slot order.  Spheres and
 //                      curves (nrtRefitPrims*, launch_refit_prims): the same fold over the builder's box of each primitive
-//                      (prims_dev.h), from the context's positions and radii, which api.hip has already replaced
+//                      (prims_dev.h), from the context's positions and radii, which api_tree.hip has already replaced
 //     k_refit_branches one launch per level, deepest first: union of the two children's boxes, low child first
-//   then the existing launch_gather_leaf / launch_make_wide (api.hip) re-derive LeafTri and WideNode / Wide4Node.
+//   then the existing launch_gather_leaf / launch_make_wide (api_tree.hip) re-derive LeafTri and WideNode / Wide4Node.
 //
 // Every level's boxes reach the next level through a launch boundary: no workgroup hands data to another inside a launch.
 // Records the walk from the root never reaches (adopted trees) are in neither list and are left untouched.

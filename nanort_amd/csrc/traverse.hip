@@ -54,7 +54,7 @@ struct ClosestQuery : BinaryQuery {
   }
   __device__ __forceinline__ void enter_leaves(const TraverseArgs<T> &a, uint32_t rid, bool at_leaf) {
     skip = a.skip_prim;
-    if constexpr (!COUNT) // (the counting pass takes no ids: api.hip)
+    if constexpr (!COUNT) // (the counting pass takes no ids: api_query.hip)
       if (a.skip_ids != nullptr && at_leaf) skip = a.skip_ids[rid]; // per-ray skip ids (common.h): the id of the ray the lane holds NOW
   }
   __device__ __forceinline__ void record(const TraverseArgs<T> &a, Lane<T> &L, uint32_t, uint32_t k) {
@@ -258,7 +258,7 @@ __global__ __launch_bounds__(kTraverseBlock, (WIDTH == 4 && sizeof(T) == 4) ? NR
   }                                                                                                    \
   (void)skip_
 
-  // Occlusion queries of the sphere, cylinder and curve kinds (api.hip, Query::OcclusionPrims: a.any_hit on these instantiations,
+  // Occlusion queries of the sphere, cylinder and curve kinds (api_query.hip, Query::OcclusionPrims: a.any_hit on these instantiations,
   // flags into the caller's mask, no records).  A ray is SETTLED once `L.hit_t < L.max_t` — the very predicate NRT_WRITE_RESULT
   // writes as the closest-hit flag, and nothing weaker.  A settled lane tests no further record of its leaf (NRT_RAY_OPEN in the
   // record loops' `act_` and in their ballots: NRT_SPHERE_LOOP, NRT_RECORD_LOOP), a curve stops at its first accepted segment
@@ -426,7 +426,7 @@ __global__ __launch_bounds__(kTraverseBlock, (WIDTH == 4 && sizeof(T) == 4) ? NR
 #if NRT_W4_PRESEL
           if constexpr (sizeof(T) == 4) {
             const char *wb_ = reinterpret_cast<const char *>(a.wide4);
-            const RecOff rec_ = (RecOff)cur << 7; // (32 bits: api.hip sends arrays of 4 GiB and more to the ORDER & 4 instantiations)
+            const RecOff rec_ = (RecOff)cur << 7; // (32 bits: api_query.hip sends arrays of 4 GiB and more to the ORDER & 4 instantiations)
             const Slab4<float> sl = slab4_presel<RecOff>(L, wb_, rec_);
             const Wide4Tail w = *reinterpret_cast<const Wide4Tail *>(wb_ + (size_t)rec_ + 96);
             if constexpr ((ORDER & 1) == 1)
@@ -525,7 +525,7 @@ __global__ __launch_bounds__(kTraverseBlock, (WIDTH == 4 && sizeof(T) == 4) ? NR
         // the reference's own accept rule (`tt > t` / `tt < min_t` reject, equality and NaN accepted, nanort.h:1133-1139): the
         // same tests on the same operands, accepted in the same sequence, so the lane state after the leaf is bit for bit what
         // the owner's own loop leaves (tests/test_gpu_leaf_items.py).  More records than lanes: the owners' loop below.  Trees
-        // whose leaves hold more than four records do not take this variant at all (api.hip).
+        // whose leaves hold more than four records do not take this variant at all (api_query.hip).
         items_done_ = leaf_items_one_trip<PLAIN, uint32_t>(L, cnt, a.tris, first, lane, s_item_owner[tid / kWave], s_item_rec[tid / kWave], a.range0, a.range1,
                                                  skip, cull);
       }

@@ -100,7 +100,7 @@ inline WalkVariant pick_wide_variant(const WalkRequest &r, bool prof_build) {
   const bool stats = prof_build && r.stats, clock = prof_build && r.clock && !stats;
   if (two) {
     if (stats || clock) return {true, kWide4LdsStack, stats, kPrimTriangles, true, clock, 4, 0}; // (default trace options only)
-    // a record array of 4 GiB or more: the default walk with 64-bit record offsets (api.hip sends nothing else here); else
+    // a record array of 4 GiB or more: the default walk with 64-bit record offsets (api_query.hip sends nothing else here); else
     // bit 1: leaf phase over items (tunable leaf_compact), bit 0: slots entered by entry distance (tunable order4)
     const int order = r.wide4_big ? (r.leaf_items ? 6 : 4) : ((r.leaf_items ? 2 : 0) | (r.order4 ? 1 : 0));
     return {true, kWide4LdsStack, false, kPrimTriangles, r.plain_options, false, 4, order};

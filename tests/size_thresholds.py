@@ -30,7 +30,7 @@ CAPS = {
                    "B5 (k_max_index) of test_gpu_size_thresholds.py: MAX_INDEX_CAP_WORDS"),
     "post pass grid": (2048, "prims.hip", r"const\s+dim3\s+grid\(std::min\(\(n \+ 255u\) / 256u,\s*(\d+)u\)\),\s*block\(256\);",
                        "B4 (post passes) of test_gpu_size_thresholds.py: POST_PASS_CAP"),
-    "kPiece": (1 << 19, "api.hip", r"const\s+uint64_t\s+kPiece\s*=\s*1ull\s*<<\s*(\d+)\s*;",
+    "kPiece": (1 << 19, "api_query.hip", r"const\s+uint64_t\s+kPiece\s*=\s*1ull\s*<<\s*(\d+)\s*;",
                "B6 (pipelined host path) of test_gpu_size_thresholds.py: PIECE"),
 }
 

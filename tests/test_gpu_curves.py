@@ -266,7 +266,7 @@ def test_one_context_through_triangles_curves_spheres_curves(rays):
     fc, fr = cf.fur()
     assert a.Build(400, CurveGeometry(fc, fr))
     check_against_model(a, fc, fr, rays)
-    # ... and on through the setters that share one path (api.hip), 64 primitives and 256 rays a stage: what one of them could leave
+    # ... and on through the setters that share one path (api_geometry.hip), 64 primitives and 256 rays a stage: what one of them could leave
     # behind for the next is the segment array, the radii, the faces, test_cap and the subdivision count
     import torch
 

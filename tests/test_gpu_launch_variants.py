@@ -1,4 +1,4 @@
-"""Which kernel a traversal launch runs (api.hip: the walk chosen from the context's state, its tunables and the trace options).
+"""Which kernel a traversal launch runs (api_query.hip: the walk chosen from the context's state, its tunables and the trace options).
 Hit records are bit-identical under every variant, so the parity tests cannot see a wrong choice: this pins nrtLastKernelName
 per configuration — `nrt::k_traverse_wide<T, STACK, STATS, KIND, PLAIN, CLOCK, WIDTH, ORDER>` — on the C1 mesh with a 96 x 64
 camera wave, and walks one context through every primitive kind: at each stage it launches the kernel and returns the records

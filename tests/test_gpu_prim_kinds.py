@@ -1,4 +1,4 @@
-"""What the setters of the four primitive kinds share (nanort_amd/csrc/api.hip: one path from the refusals to the adopted
+"""What the setters of the four primitive kinds share (nanort_amd/csrc/api_geometry.hip: one path from the refusals to the adopted
 primitives) and the pass behind a walk over spheres, cylinders and curves (prims.hip, launch_post_pass), on small sets:
   * each of the seven set entry points takes n == 0, leaves a context that builds nothing and traces nothing, and takes the same
     primitives again with the same records as before;

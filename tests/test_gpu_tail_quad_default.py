@@ -13,7 +13,7 @@ from nanort_amd import BVHAccel, TriangleMesh, scenes
 
 pytestmark = pytest.mark.gpu
 
-DEFAULT = 4  # api.hip: tail_quad's default (profiles/r07a_tail_quad.txt; the sweep with the tail behind the loop is outstanding: r07b)
+DEFAULT = 4  # ctx.h: tail_quad's default (profiles/r07a_tail_quad.txt; the sweep with the tail behind the loop is outstanding: r07b)
 
 
 @pytest.fixture(scope="module")

@@ -41,7 +41,7 @@ def test_c1_camera_wave_same_trail():
     wh, wm, wc, t_ref, t_w4 = orc.traverse_wide4_model(nodes, idx, v, f, rays, trail_cap=int(oc[1]) + 1)
     assert np.array_equal(om, wm) and oh.tobytes() == wh.tobytes()
     assert np.array_equal(t_ref, t_w4) and int(wc[2]) == int(oc[2])
-    # deepest stack: three pending entries per two levels at most (what api.hip sizes the overflow area for)
+    # deepest stack: three pending entries per two levels at most (what api_query.hip sizes the overflow area for)
     depth = max_depth(nodes)
     assert int(wc[3]) <= 3 * (depth // 2 + 1)
 
