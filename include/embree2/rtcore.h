@@ -15,7 +15,9 @@
  *    order (nanort-embree.cc:545 stores nanosg's node index; the reference demo indexes meshes[ray.geomID]);
  *  - a miss sets geomID = primID = instID = RTC_INVALID_GEOMETRY_ID and leaves tfar alone; Ng is never written;
  *  - no back-face culling, ray masks and time are ignored; the ray's [tnear, tfar] selects candidate meshes by
- *    their boxes, the per-mesh search itself is unbounded (nanosg.h:817, see nanort_hip.h "two-level scenes"). */
+ *    their boxes, the per-mesh search itself is unbounded (nanosg.h:817, see nanort_hip.h "two-level scenes").
+ *    (The library has visibility masks — nanort_hip.h, "visibility masks" — for single triangle contexts only; this shim goes
+ *    through two-level scenes, which take none, so ray.mask and rtcSetMask stay without effect here.) */
 #ifndef NANORT_EMBREE2_RTCORE_H_
 #define NANORT_EMBREE2_RTCORE_H_
 

@@ -718,6 +718,33 @@ class MotionTriangleIntersector : public TriangleIntersector<T, H> {
   mutable T shutter_;
 };
 
+// Visibility masks (include/nanort_hip.h, "visibility masks"): a TriangleIntersector that holds one 32-bit word per primitive and the
+// word of the ray being traced, and returns false from Intersect() for a primitive the ray does not see — (prim_mask & ray_mask)
+// == 0 — before any of its arithmetic: the reference's template-filter mechanism, as data.  Works on the host without the backend;
+// SetRayMask() before Traverse(), once per ray.  prim_masks == NULL: every primitive carries 0xFFFFFFFF.
+template <typename T = float, class H = TriangleIntersection<T> >
+class MaskedTriangleIntersector : public TriangleIntersector<T, H> {
+  typedef TriangleIntersector<T, H> Base;
+
+ public:
+  template <class M>
+  MaskedTriangleIntersector(const M &m, const unsigned int *prim_masks) : Base(m), prim_masks_(prim_masks), ray_mask_(0xFFFFFFFFu) {}
+  MaskedTriangleIntersector(const T *vertices, const unsigned int *faces, const size_t vertex_stride_bytes, const unsigned int *prim_masks)
+      : Base(vertices, faces, vertex_stride_bytes), prim_masks_(prim_masks), ray_mask_(0xFFFFFFFFu) {}
+
+  void SetRayMask(unsigned int ray_mask) const { ray_mask_ = ray_mask; }
+  unsigned int GetRayMask() const { return ray_mask_; }
+
+  bool Intersect(T *t_inout, const unsigned int prim_index) const {
+    if (((prim_masks_ ? prim_masks_[prim_index] : 0xFFFFFFFFu) & ray_mask_) == 0u) return false;
+    return Base::Intersect(t_inout, prim_index);
+  }
+
+ private:
+  const unsigned int *prim_masks_;
+  mutable unsigned int ray_mask_;
+};
+
 // Robust slab test (Ize 2013), t_max terms widened by MaxMult
 // (ref nanort.h:2278-2370).
 namespace detail {
@@ -1344,6 +1371,13 @@ struct HipApi<float> {
   static nrt_status OccludedMotion(nrt_ctx *c, const RayPod *r, const float *t, uint64_t n, const nrt_trace_options *o, uint8_t *m) {
     return nrtOccludedBatchMotion_f32(c, r, t, n, o, m);
   }
+  // (visibility masks, include/nanort_hip.h: the queries with one word per ray; the setter nrtSetPrimMasks has no precision)
+  static nrt_status TraverseMasked(nrt_ctx *c, const RayPod *r, const uint32_t *v, uint64_t n, const nrt_trace_options *o, HitPod *h, uint8_t *m) {
+    return nrtTraverseBatchMasked_f32(c, r, v, n, o, h, m);
+  }
+  static nrt_status OccludedMasked(nrt_ctx *c, const RayPod *r, const uint32_t *v, uint64_t n, const nrt_trace_options *o, uint8_t *m) {
+    return nrtOccludedBatchMasked_f32(c, r, v, n, o, m);
+  }
 };
 template <>
 struct HipApi<double> {
@@ -1413,6 +1447,13 @@ struct HipApi<double> {
   }
   static nrt_status OccludedMotion(nrt_ctx *c, const RayPod *r, const double *t, uint64_t n, const nrt_trace_options *o, uint8_t *m) {
     return nrtOccludedBatchMotion_f64(c, r, t, n, o, m);
+  }
+  // (visibility masks, include/nanort_hip.h: the queries with one word per ray; the setter nrtSetPrimMasks has no precision)
+  static nrt_status TraverseMasked(nrt_ctx *c, const RayPod *r, const uint32_t *v, uint64_t n, const nrt_trace_options *o, HitPod *h, uint8_t *m) {
+    return nrtTraverseBatchMasked_f64(c, r, v, n, o, h, m);
+  }
+  static nrt_status OccludedMasked(nrt_ctx *c, const RayPod *r, const uint32_t *v, uint64_t n, const nrt_trace_options *o, uint8_t *m) {
+    return nrtOccludedBatchMasked_f64(c, r, v, n, o, m);
   }
 };
 struct CtxDeleter {
@@ -2028,6 +2069,57 @@ class BVHAccel {
     }
     return true;
   }
+  // Visibility masks (include/nanort_hip.h, "visibility masks"): one word per primitive of the triangle mesh the accel was built
+  // over (`count` must be its primitive count; NULL removes the masks).  The array is copied to the GPU now and kept by pointer, as
+  // Build() keeps the mesh's arrays (a copy-on-write detach sends it again): it must outlive the accel or the next SetPrimMasks().
+  // The tree is untouched: no Build(), no Refit().  An object that shares its contexts with copies first moves to contexts of its
+  // own, so the copies keep their visibility.  Build() over a new mesh drops the masks.
+  bool SetPrimMasks(const unsigned int *prim_masks, size_t count) {
+    std::lock_guard<std::mutex> lock(batch_mutex_);
+    if (!ctx_ || device_prim_kind_ != 0) {
+      backend_error_ = "SetPrimMasks: no triangle mesh on the GPU (Build() with the built-in triangle types first)";
+      return false;
+    }
+    if (prim_masks && count != prim_count_) {
+      backend_error_ = "SetPrimMasks: count differs from the number of primitives the tree was built over";
+      return false;
+    }
+    if (!RefitContexts(0, [&](nrt_ctx *c) { return nrtSetPrimMasks(c, prim_masks, count); })) return false;
+    tri_masks_ = prim_masks;
+    return true;
+  }
+  // The closest hit of each of `num_rays` rays among the triangles it sees: ray i sees primitive p iff (prim_masks[p] & ray_masks[i])
+  // != 0 (ray_masks == NULL: every ray 0xFFFFFFFF).  EVERY record is written — a miss stores {0, 0, ray.max_t, 0xFFFFFFFF} — and each
+  // equals what the per-ray Traverse() with a MaskedTriangleIntersector set to that ray's mask gives over the same tree; hit_out[i]
+  // (optional) receives 1 / 0.
+  bool TraverseBatchMasked(const Ray<T> *rays, const unsigned int *ray_masks, size_t num_rays, TriangleIntersection<T> *isects,
+                           unsigned char *hit_out = NULL, const BVHTraceOptions &options = BVHTraceOptions()) const {
+    typedef detail::HipApi<T> Api;
+    std::lock_guard<std::mutex> lock(batch_mutex_);
+    if (!MaskedTreeReady("TraverseBatchMasked")) return false;
+    nrt_trace_options o;
+    std::memcpy(&o, &options, sizeof(o));
+    if (Api::TraverseMasked(ctx_.get(), reinterpret_cast<const typename Api::RayPod *>(rays), ray_masks, num_rays, &o,
+                            reinterpret_cast<typename Api::HitPod *>(isects), hit_out) != NRT_OK) {
+      backend_error_ = nrtLastError(ctx_.get());
+      return false;
+    }
+    return true;
+  }
+  // ... and its occlusion query: occluded_out[i] is exactly the hit_out[i] of TraverseBatchMasked().
+  bool OccludedBatchMasked(const Ray<T> *rays, const unsigned int *ray_masks, size_t num_rays, unsigned char *occluded_out,
+                           const BVHTraceOptions &options = BVHTraceOptions()) const {
+    typedef detail::HipApi<T> Api;
+    std::lock_guard<std::mutex> lock(batch_mutex_);
+    if (!MaskedTreeReady("OccludedBatchMasked")) return false;
+    nrt_trace_options o;
+    std::memcpy(&o, &options, sizeof(o));
+    if (Api::OccludedMasked(ctx_.get(), reinterpret_cast<const typename Api::RayPod *>(rays), ray_masks, num_rays, &o, occluded_out) != NRT_OK) {
+      backend_error_ = nrtLastError(ctx_.get());
+      return false;
+    }
+    return true;
+  }
   // ... and with device pointers, asynchronous on `hip_stream` (see TraverseBatchDevice).
   bool MultiHitTraverseBatchDevice(const Ray<T> *d_rays, size_t num_rays, unsigned int max_hits, TriangleIntersection<T> *d_isects,
                                    unsigned int *d_counts, void *hip_stream, const BVHTraceOptions &options = BVHTraceOptions()) const {
@@ -2218,6 +2310,14 @@ class BVHAccel {
   bool MotionTreeReady(const char *who) const {
     if (!ctx_ || device_prim_kind_ != 0 || !tri_vertices1_) {
       backend_error_ = std::string(who) + ": Build() with MotionTriangleMesh/MotionTriangleSAHPred first";
+      return false;
+    }
+    return DeviceTreeReady(0);
+  }
+  // The checks of the masked queries (caller holds batch_mutex_): a triangle accel that holds masks.
+  bool MaskedTreeReady(const char *who) const {
+    if (!ctx_ || device_prim_kind_ != 0 || !tri_masks_) {
+      backend_error_ = std::string(who) + ": SetPrimMasks() on an accel built over a TriangleMesh first";
       return false;
     }
     return DeviceTreeReady(0);
@@ -2815,6 +2915,7 @@ class BVHAccel {
     tri_stride_ = mesh.GetVertexStrideBytes();
     tri_faces_ = mesh.GetFaces();
     tri_vertices1_ = NULL;
+    tri_masks_ = NULL;  // (nrtSetMesh drops the masks: they belong to the mesh)
     prim_count_ = n;
     return HipBuild(n, options, 0, [&](nrt_ctx *c) { return Api::SetMesh(c, tri_vertices_, tri_stride_, tri_faces_, n); });
   }
@@ -2828,6 +2929,7 @@ class BVHAccel {
     tri_stride_ = mesh.GetVertexStrideBytes();
     tri_faces_ = mesh.GetFaces();
     tri_vertices1_ = mesh.GetVertices1();
+    tri_masks_ = NULL;
     prim_count_ = n;
     return HipBuild(n, options, 0, [&](nrt_ctx *c) {
       const nrt_status st = Api::SetMesh(c, tri_vertices_, tri_stride_, tri_faces_, n);
@@ -2990,8 +3092,9 @@ class BVHAccel {
   nrt_status SendPrimitives(nrt_ctx *c, bool cylinder_cap) const {
     switch (device_prim_kind_) {
       case 0: {
-        const nrt_status st = detail::HipApi<T>::SetMesh(c, tri_vertices_, tri_stride_, tri_faces_, prim_count_);
-        return (st != NRT_OK || !tri_vertices1_) ? st : detail::HipApi<T>::SetMeshMotion(c, tri_vertices1_, tri_stride_);
+        nrt_status st = detail::HipApi<T>::SetMesh(c, tri_vertices_, tri_stride_, tri_faces_, prim_count_);
+        if (st == NRT_OK && tri_vertices1_) st = detail::HipApi<T>::SetMeshMotion(c, tri_vertices1_, tri_stride_);
+        return (st != NRT_OK || !tri_masks_) ? st : nrtSetPrimMasks(c, tri_masks_, prim_count_);
       }
       case 1: return nrtSetSpheres_f32(c, sph_centers_, sph_radii_, prim_count_);
       case 2: return nrtSetCylinders_f32(c, cyl_endpoints_, cyl_radii_, cyl_count_, cylinder_cap ? 1 : 0);
@@ -3047,6 +3150,7 @@ class BVHAccel {
     cyl_test_cap_ = o.cyl_test_cap_;
     tri_vertices_ = o.tri_vertices_;
     tri_vertices1_ = o.tri_vertices1_;
+    tri_masks_ = o.tri_masks_;
     tri_stride_ = o.tri_stride_;
     tri_faces_ = o.tri_faces_;
     sph_centers_ = o.sph_centers_;
@@ -3097,6 +3201,7 @@ class BVHAccel {
     cyl_test_cap_ = o->cyl_test_cap_;
     tri_vertices_ = o->tri_vertices_;
     tri_vertices1_ = o->tri_vertices1_;
+    tri_masks_ = o->tri_masks_;
     tri_stride_ = o->tri_stride_;
     tri_faces_ = o->tri_faces_;
     sph_centers_ = o->sph_centers_;
@@ -3109,6 +3214,7 @@ class BVHAccel {
     o->cyl_endpoints_ = o->cyl_radii_ = NULL;
     o->tri_vertices_ = NULL;
     o->tri_vertices1_ = NULL;
+    o->tri_masks_ = NULL;
     o->tri_faces_ = NULL;
     o->sph_centers_ = o->sph_radii_ = NULL;
     o->cyl_count_ = o->prim_count_ = 0;
@@ -3137,6 +3243,7 @@ class BVHAccel {
   const T *tri_vertices_ = NULL;  // triangle / sphere primitives: what Build() was given (a detach sends them again)
   size_t tri_stride_ = 0;
   const T *tri_vertices1_ = NULL;  // ... and the second vertex keyframe of a Build() over MotionTriangleMesh (NULL: none)
+  const unsigned int *tri_masks_ = NULL;  // ... and the visibility masks of the last SetPrimMasks() (NULL: none)
   const unsigned int *tri_faces_ = NULL;
   const float *sph_centers_ = NULL;
   const float *sph_radii_ = NULL;

@@ -666,6 +666,62 @@ NRT_API nrt_status nrtOccludedBatchMotionDevice_f32(nrt_ctx *ctx, const nrt_ray_
 NRT_API nrt_status nrtOccludedBatchMotionDevice_f64(nrt_ctx *ctx, const nrt_ray_f64 *d_rays, const double *d_times, uint64_t num_rays,
                                                     const nrt_trace_options *options, uint8_t *d_mask_out, void *hip_stream);
 
+/* ---- visibility masks: 32 bits per triangle, 32 bits per ray -------------------------------------------------------------------
+ * An OPT-IN EXTENSION: visibility by ray type (Embree's ray.mask / rtcSetMask, the instance masks of DXR and OptiX).  The reference's
+ * answer is a custom intersection filter through its TriangleIntersector template; user code does not run on the GPU, so here the
+ * filter is data: a triangle context may hold ONE 32-BIT WORD PER FACE, a masked query carries one word per ray, and
+ *
+ *     a triangle exists for a ray  iff  (prim_mask & ray_mask) != 0.
+ *
+ * (A camera bit, a shadow bit, a reflection bit: a light's geometry without the camera bit, a shadow catcher without the reflection
+ * bit, a matte object without the shadow bit; INTEGRATION.md.)
+ *
+ * Setters.  nrtSetPrimMasks copies `count` words from host memory, one per face in face (prim id) order; nrtSetPrimMasksDevice
+ * copies them from device memory on `hip_stream` (4-byte aligned) and returns when the context owns its copy.  Masks have no
+ * precision: one pair serves both.  Both need a triangle context with a mesh set and count == its number of faces (NRT_ERR_INVALID
+ * otherwise, naming the kind the context holds; nothing changed).  masks == NULL removes the masks (count is not read).
+ * The masks belong to the mesh: every nrtSetMesh* / nrtSetSpheres* / nrtSetCylinders* / nrtSetCurves* drops them, as it drops the
+ * motion keyframe.  They are NO PART OF THE TREE: setting, changing or removing them keeps the tree, before or after nrtBuild, and
+ * nrtBuild / nrtSetTree / nrtRefit* / nrtSetMeshMotion* keep the masks — visibility changes between two queries with no build and
+ * no refit.  (The setters wait for the launches in flight; the first masked query behind a change of the masks or of the tree
+ * re-derives the words' leaf-order copy on the device and waits for it on the host, some tens of microseconds.)
+ *
+ * Queries.  nrtTraverseBatchMasked* / nrtOccludedBatchMasked* are nrtTraverseBatch* / nrtOccludedBatch* with `ray_masks`: one word
+ * per ray, NULL = every ray carries 0xFFFFFFFF; a ray whose word is 0 sees nothing.  A record is that of the reference's Traverse
+ * (nanort.h:2487-2556) over the context's own node array with an intersector that returns false for every triangle the ray does not
+ * see: every field of every record is bit-identical to that, a miss is the usual miss record ({0, 0, max_t, 0xFFFFFFFF}), and the
+ * occlusion flags are exactly the closest-hit flags.  prim_ids_range, skip_prim_id and cull_back_face keep their launch-wide
+ * meaning, on the triangles the ray sees.  With all-ones words on both sides the records are those of nrtTraverseBatch*.  On a
+ * context with a motion keyframe they answer for keyframe 0, as nrtTraverseBatch* does.  The host forms upload the words beside
+ * the rays (a batch traced in pieces: each piece with its slice); the *Device forms read `d_ray_masks` (num_rays words in HBM,
+ * 4-byte aligned) during the launch, asynchronously on `hip_stream`; nrtBuild / nrtSetTree / nrtSetMesh* / nrtSetPrimMasks* /
+ * nrtDestroy wait for them.  NRT_ERR_INVALID: a context without masks, a context of another primitive kind, a misaligned
+ * `d_ray_masks`; NRT_ERR_PRECISION: a context of the other precision.  A refusal sets nrtLastError and writes nothing.
+ *
+ * Not covered: every other entry point ignores the masks — multi-hit, the motion queries, per-ray skip ids, the batch tables,
+ * nrtTraverseBatchMulti, nrtGroup*, scenes / instances (and with them the Embree shim, whose ray.mask stays ignored); spheres,
+ * cylinders and curves take no masks. */
+NRT_API nrt_status nrtSetPrimMasks(nrt_ctx *ctx, const uint32_t *masks, uint64_t count);
+NRT_API nrt_status nrtSetPrimMasksDevice(nrt_ctx *ctx, const uint32_t *d_masks, uint64_t count, void *hip_stream);
+NRT_API nrt_status nrtTraverseBatchMasked_f32(nrt_ctx *ctx, const nrt_ray_f32 *rays, const uint32_t *ray_masks, uint64_t num_rays,
+                                              const nrt_trace_options *options, nrt_hit_f32 *hits_out, uint8_t *hit_mask_out);
+NRT_API nrt_status nrtTraverseBatchMasked_f64(nrt_ctx *ctx, const nrt_ray_f64 *rays, const uint32_t *ray_masks, uint64_t num_rays,
+                                              const nrt_trace_options *options, nrt_hit_f64 *hits_out, uint8_t *hit_mask_out);
+NRT_API nrt_status nrtTraverseBatchMaskedDevice_f32(nrt_ctx *ctx, const nrt_ray_f32 *d_rays, const uint32_t *d_ray_masks, uint64_t num_rays,
+                                                    const nrt_trace_options *options, nrt_hit_f32 *d_hits_out, uint8_t *d_mask_out,
+                                                    void *hip_stream);
+NRT_API nrt_status nrtTraverseBatchMaskedDevice_f64(nrt_ctx *ctx, const nrt_ray_f64 *d_rays, const uint32_t *d_ray_masks, uint64_t num_rays,
+                                                    const nrt_trace_options *options, nrt_hit_f64 *d_hits_out, uint8_t *d_mask_out,
+                                                    void *hip_stream);
+NRT_API nrt_status nrtOccludedBatchMasked_f32(nrt_ctx *ctx, const nrt_ray_f32 *rays, const uint32_t *ray_masks, uint64_t num_rays,
+                                              const nrt_trace_options *options, uint8_t *mask_out);
+NRT_API nrt_status nrtOccludedBatchMasked_f64(nrt_ctx *ctx, const nrt_ray_f64 *rays, const uint32_t *ray_masks, uint64_t num_rays,
+                                              const nrt_trace_options *options, uint8_t *mask_out);
+NRT_API nrt_status nrtOccludedBatchMaskedDevice_f32(nrt_ctx *ctx, const nrt_ray_f32 *d_rays, const uint32_t *d_ray_masks, uint64_t num_rays,
+                                                    const nrt_trace_options *options, uint8_t *d_mask_out, void *hip_stream);
+NRT_API nrt_status nrtOccludedBatchMaskedDevice_f64(nrt_ctx *ctx, const nrt_ray_f64 *d_rays, const uint32_t *d_ray_masks, uint64_t num_rays,
+                                                    const nrt_trace_options *options, uint8_t *d_mask_out, void *hip_stream);
+
 /* One HOST batch spread over several contexts — typically one per GPU of the node (nrtDeviceCount), each holding the same
  * tree: nrtBuild is deterministic, so building the same mesh on every context gives bit-identical replicas (or nrtSetTree the
  * same arrays).  The batch is cut into rows of `row_len` rays (an image row; 0 = 4096) and row r is traced by context

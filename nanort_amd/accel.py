@@ -779,6 +779,88 @@ class BVHAccel:
             self._h, d_rays.data_ptr(), self._device_times(d_times, n), n, _p(options), d_mask.data_ptr(), self._stream_handle(stream)))
         return n
 
+    # -- visibility masks (include/nanort_hip.h, "visibility masks") ----------
+    def SetPrimMasks(self, masks, stream=None):
+        """nrtSetPrimMasks / nrtSetPrimMasksDevice: one uint32 per face of the triangle mesh last set, in face order; a triangle
+        exists for a ray iff (prim_mask & ray_mask) != 0.  `masks`: a numpy array (or anything numpy converts), or a torch tensor on
+        the accel's device (int32 or uint32, contiguous: read as u32 on `stream`, default torch's current stream); None removes the
+        masks.  The tree stays as it is."""
+        if masks is None:
+            self._check(self._L.nrtSetPrimMasks(self._h, None, 0))
+            return
+        if hasattr(masks, "data_ptr"):  # a torch tensor
+            return self.SetPrimMasksDevice(masks, stream)
+        m = np.ascontiguousarray(masks, dtype=np.uint32).reshape(-1)
+        self._check(self._L.nrtSetPrimMasks(self._h, _p(m), m.shape[0]))
+
+    def SetPrimMasksDevice(self, d_masks, stream=None):
+        """nrtSetPrimMasksDevice: the masks from a contiguous torch tensor of 32-bit integers on the accel's device, copied on
+        `stream` (default: torch's current stream); returns when the accel owns its copy.  None removes the masks."""
+        if d_masks is None:
+            self._check(self._L.nrtSetPrimMasksDevice(self._h, None, 0, self._stream_handle(stream)))
+            return
+        if d_masks.element_size() != 4 or d_masks.is_floating_point() or not d_masks.is_contiguous():
+            raise TypeError("masks: a contiguous tensor of 32-bit integers")
+        self._on_device(d_masks, "masks")
+        self._check(self._L.nrtSetPrimMasksDevice(self._h, d_masks.data_ptr(), int(d_masks.numel()), self._stream_handle(stream)))
+
+    def _host_ray_masks(self, ray_masks, n):
+        """One uint32 per ray, contiguous (None: every ray 0xFFFFFFFF)."""
+        if ray_masks is None:
+            return None
+        v = np.ascontiguousarray(ray_masks, dtype=np.uint32).reshape(-1)
+        if v.shape[0] != n:
+            raise ValueError("ray_masks: %d values for %d rays" % (v.shape[0], n))
+        return v
+
+    def _device_ray_masks(self, d_ray_masks, n):
+        if d_ray_masks is None:
+            return None
+        assert d_ray_masks.numel() * d_ray_masks.element_size() >= 4 * n, "ray_masks: fewer values than rays"
+        return d_ray_masks.data_ptr()
+
+    def TraverseBatchMasked(self, rays, ray_masks, options=None):
+        """nrtTraverseBatchMasked: TraverseBatch in which ray i sees only the triangles whose mask shares a bit with ray_masks[i]
+        (None: every ray 0xFFFFFFFF).  Returns (hits, mask)."""
+        rays = np.ascontiguousarray(rays, dtype=ray_dtype(self.real))
+        n = rays.shape[0]
+        v = self._host_ray_masks(ray_masks, n)
+        hits = np.zeros((n,), dtype=hit_dtype(self.real))
+        mask = np.zeros((n,), dtype=np.uint8)
+        options = _opts(options)
+        self._check(getattr(self._L, "nrtTraverseBatchMasked_" + self._s)(self._h, _p(rays), _p(v), n, _p(options), _p(hits), _p(mask)))
+        return hits, mask
+
+    def TraverseBatchMaskedDevice(self, d_rays, d_ray_masks, d_hits, d_mask=None, options=None, stream=None):
+        """Same on HBM-resident torch tensors (raw PODs; `d_ray_masks`: one 32-bit word per ray, or None), asynchronous on `stream`
+        (default: torch's current stream).  Returns n."""
+        hsz = hit_dtype(self.real).itemsize
+        n = self._n_rays(d_rays)
+        assert d_hits.numel() * d_hits.element_size() >= n * hsz
+        options = _opts(options)
+        self._check(getattr(self._L, "nrtTraverseBatchMaskedDevice_" + self._s)(
+            self._h, d_rays.data_ptr(), self._device_ray_masks(d_ray_masks, n), n, _p(options), d_hits.data_ptr(),
+            None if d_mask is None else d_mask.data_ptr(), self._stream_handle(stream)))
+        return n
+
+    def OccludedBatchMasked(self, rays, ray_masks, options=None):
+        """nrtOccludedBatchMasked: only the hit flags of TraverseBatchMasked, each ray stopping at the first triangle that settles it."""
+        rays = np.ascontiguousarray(rays, dtype=ray_dtype(self.real))
+        n = rays.shape[0]
+        v = self._host_ray_masks(ray_masks, n)
+        mask = np.zeros((n,), dtype=np.uint8)
+        options = _opts(options)
+        self._check(getattr(self._L, "nrtOccludedBatchMasked_" + self._s)(self._h, _p(rays), _p(v), n, _p(options), _p(mask)))
+        return mask
+
+    def OccludedBatchMaskedDevice(self, d_rays, d_ray_masks, d_mask, options=None, stream=None):
+        n = self._n_rays(d_rays)
+        assert d_mask.numel() >= n
+        options = _opts(options)
+        self._check(getattr(self._L, "nrtOccludedBatchMaskedDevice_" + self._s)(
+            self._h, d_rays.data_ptr(), self._device_ray_masks(d_ray_masks, n), n, _p(options), d_mask.data_ptr(), self._stream_handle(stream)))
+        return n
+
     def MultiHitTraverseBatch(self, rays, max_hits, options=None):
         """The K = max_hits frontmost hits of every ray (include/nanort_hip.h, nrtMultiHitTraverseBatch): returns (hits[n, K],
         counts[n]); row i holds ray i's hits by ascending (t, prim_id), then miss records {0, 0, max_t, 0xFFFFFFFF}."""

@@ -33,7 +33,7 @@ _LIB = None
 vp, u32, u64, sz, i32, P = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER
 _BOTH, _F32 = ("f32", "f64"), ("f32",)
 _Q = [vp, vp, u64, vp]       # ctx, rays, num_rays, options: how every ray query starts
-_QT = [vp, vp, vp, u64, vp]  # ... with the per-ray times of the motion queries behind the rays
+_QT = [vp, vp, vp, u64, vp]  # ... with the per-ray times of the motion queries (the per-ray words of the masked ones) behind the rays
 _QB = [vp, u32, vp, vp, vp]  # ctx, num_batches, rays[], num_rays[], options: the multi-batch forms
 
 # The binding of include/nanort_hip.h, one row per declaration in the header's order: (name, precision suffixes or None,
@@ -89,6 +89,13 @@ SIGNATURES = [
     ("nrtTraverseBatchMotionDevice", _BOTH, _QT + [vp, vp, vp], i32),
     ("nrtOccludedBatchMotion", _BOTH, _QT + [vp], i32),
     ("nrtOccludedBatchMotionDevice", _BOTH, _QT + [vp, vp], i32),
+    # visibility masks: one word per face (no precision), and the motion rows' shape with the per-ray words where those have the times
+    ("nrtSetPrimMasks", None, [vp, vp, u64], i32),
+    ("nrtSetPrimMasksDevice", None, [vp, vp, u64, vp], i32),
+    ("nrtTraverseBatchMasked", _BOTH, _QT + [vp, vp], i32),
+    ("nrtTraverseBatchMaskedDevice", _BOTH, _QT + [vp, vp, vp], i32),
+    ("nrtOccludedBatchMasked", _BOTH, _QT + [vp], i32),
+    ("nrtOccludedBatchMaskedDevice", _BOTH, _QT + [vp, vp], i32),
     ("nrtTraverseBatchMulti", _BOTH, [vp, u32, vp, u64, u64, vp, vp, vp], i32),
     ("nrtDeviceCount", None, [], i32),
     ("nrtTraverseCountDevice", _BOTH, _Q + [P(TraceCounters)], i32),

@@ -1,5 +1,5 @@
 // nanort_amd/csrc/api_geometry.hip — the setters behind the C ABI (include/nanort_hip.h): the four primitive kinds from host
-// memory or from HBM, and the motion keyframe of a triangle mesh.
+// memory or from HBM, the motion keyframe of a triangle mesh, and its visibility masks.
 #include "ctx.h"
 
 // ---------------------------------------------------------------------------
@@ -254,6 +254,39 @@ static nrt_status set_mesh_motion(nrt_ctx *c, const T *vertices, uint32_t num_ve
   return NRT_OK;
 }
 
+// ---------------------------------------------------------------------------
+// visibility masks (include/nanort_hip.h, nrtSetPrimMasks*; the queries nrt*BatchMasked*: api_query.hip)
+// ---------------------------------------------------------------------------
+// One 32-bit word per face of the context's triangle mesh, in face order, from host memory or (`device`: copied on `s`) from HBM.
+// Every refusal comes before anything changes; the tree stays as it is — the words are no part of it — and the leaf-order copy the
+// walk reads is derived by the next masked query (leaf_masks_stale).  `masks` == NULL removes the masks.
+static nrt_status set_prim_masks(nrt_ctx *c, const uint32_t *masks, uint64_t count, bool device, hipStream_t s) {
+  const char *fn = device ? "nrtSetPrimMasksDevice" : "nrtSetPrimMasks";
+  if (!c) return NRT_ERR_INVALID;
+  if (c->prec != 0 && c->prim_kind != kPrimTriangles)
+    return fail(c, NRT_ERR_INVALID, "%s: visibility masks: triangle contexts only (this context holds %s)", fn, kPrimKinds[c->prim_kind].name);
+  if (c->prec == 0 || !c->d_verts || c->num_faces == 0)
+    return fail(c, NRT_ERR_INVALID, "%s: set a triangle mesh first (nrtSetMesh): the masks are one word per face of it", fn);
+  if (masks && count != (uint64_t)c->num_faces)
+    return fail(c, NRT_ERR_INVALID, "%s: count %llu differs from the mesh's %u faces", fn, (unsigned long long)count, c->num_faces);
+  if (device && ((uintptr_t)masks & 3u) != 0u) return fail(c, NRT_ERR_INVALID, "%s: the device array is not 4-byte aligned", fn);
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, wait_for_launches(c)); // (masked launches in flight read the leaf-order words the next masked query rewrites)
+  c->d_prim_masks = nullptr;
+  c->leaf_masks_stale = true;
+  if (!masks) return NRT_OK;
+  const size_t bytes = (size_t)count * sizeof(uint32_t);
+  if (nrt_status st = ensure(c, c->b_prim_masks, bytes)) return st;
+  if (device) {
+    HIPCHK(c, hipMemcpyAsync(c->b_prim_masks.p, masks, bytes, hipMemcpyDeviceToDevice, s));
+    HIPCHK(c, hipStreamSynchronize(s)); // the context owns its copy: the caller's buffer is free again
+  } else {
+    HIPCHK(c, hipMemcpy(c->b_prim_masks.p, masks, bytes, hipMemcpyHostToDevice));
+  }
+  c->d_prim_masks = (uint32_t *)c->b_prim_masks.p;
+  return NRT_OK;
+}
+
 extern "C" {
 
 nrt_status nrtSetMesh_f32(nrt_ctx *c, const float *v, size_t stride, const uint32_t *f, uint32_t nf) {
@@ -295,6 +328,11 @@ nrt_status nrtSetMeshMotionDevice_f32(nrt_ctx *c, const float *v, uint32_t nv, s
 }
 nrt_status nrtSetMeshMotionDevice_f64(nrt_ctx *c, const double *v, uint32_t nv, size_t stride, void *s) {
   return set_mesh_motion<double>(c, v, nv, stride, true, (hipStream_t)s);
+}
+
+nrt_status nrtSetPrimMasks(nrt_ctx *c, const uint32_t *masks, uint64_t count) { return set_prim_masks(c, masks, count, false, nullptr); }
+nrt_status nrtSetPrimMasksDevice(nrt_ctx *c, const uint32_t *masks, uint64_t count, void *s) {
+  return set_prim_masks(c, masks, count, true, (hipStream_t)s);
 }
 
 } // extern "C"

@@ -23,7 +23,8 @@ struct TraverseBatches {
 // occlusion query of nrtOccludedBatchPrims*, which every primitive kind takes — flags straight into the caller's mask, no compact
 // records, no post pass; on a triangle context it IS Occlusion: traverse_device says so under the lock.)
 // (Motion / MotionOcclusion: the closest-hit and occlusion queries of nrt*BatchMotion*, every ray at its own time: motion.hip)
-enum class Query { Closest, Occlusion, Count, MultiHit, Cylinders, MultiBatch, Curves, OcclusionPrims, Motion, MotionOcclusion };
+// (Masked / MaskedOcclusion: those of nrt*BatchMasked*, every ray with its own visibility word: masked.hip)
+enum class Query { Closest, Occlusion, Count, MultiHit, Cylinders, MultiBatch, Curves, OcclusionPrims, Motion, MotionOcclusion, Masked, MaskedOcclusion };
 template <typename T>
 struct TraverseLaunch {
   Query kind;
@@ -40,9 +41,12 @@ struct TraverseLaunch {
   const TraverseBatches<T> *batches = nullptr; // MultiBatch: rays and outputs per batch, n = all their rays (the context takes one launch: the caller checked)
   const uint32_t *skip_ids = nullptr;    // Closest, Occlusion (nrt*BatchSkip*): one skip id per ray in the place of opt->skip_prim_id (MultiBatch: batches->skip[])
   const T *times = nullptr;              // Motion, MotionOcclusion: one time per ray (null: every ray at time 0)
+  const uint32_t *ray_masks = nullptr;   // Masked, MaskedOcclusion: one visibility word per ray (null: every ray 0xFFFFFFFF)
   bool motion() const { return kind == Query::Motion || kind == Query::MotionOcclusion; }
+  bool masked() const { return kind == Query::Masked || kind == Query::MaskedOcclusion; }
+  bool own_walk() const { return kind == Query::MultiHit || motion() || masked(); } // a binary walk of its own: no wide records, no completion record
   // the output the kind is for — what a call with rays cannot do without — is its flags; else its records: hits, or (Cylinders, Curves) cyl_hits
-  bool flags_only() const { return kind == Query::Occlusion || kind == Query::OcclusionPrims || kind == Query::MotionOcclusion; }
+  bool flags_only() const { return kind == Query::Occlusion || kind == Query::OcclusionPrims || kind == Query::MotionOcclusion || kind == Query::MaskedOcclusion; }
   void *records() const { return (kind == Query::Cylinders || kind == Query::Curves) ? cyl_hits : (void *)hits; }
   // the launch carries per-ray skip ids
   bool has_skip_ids() const {
@@ -65,6 +69,12 @@ static nrt_status validate_launch(nrt_ctx *c, const TraverseLaunch<T> &l) {
     if (!c->d_verts1) return fail(c, NRT_ERR_INVALID, "motion queries: the context holds no motion keyframe (nrtSetMeshMotion)");
     if (c->d_nodes && !c->d_tris1) return fail(c, NRT_ERR_INVALID, "motion queries: internal: no keyframe-1 leaf records");
     if (((uintptr_t)l.times % sizeof(T)) != 0u) return fail(c, NRT_ERR_INVALID, "motion queries: the times array is not aligned to %zu bytes", sizeof(T));
+  }
+  if (l.masked()) { // (include/nanort_hip.h, "visibility masks")
+    const char *fn = l.kind == Query::Masked ? "nrtTraverseBatchMasked" : "nrtOccludedBatchMasked";
+    if (custom) return fail(c, NRT_ERR_INVALID, "%s: masked queries: triangle contexts only (this context holds %s)", fn, kPrimKinds[c->prim_kind].name);
+    if (!c->d_prim_masks) return fail(c, NRT_ERR_INVALID, "%s: masked queries: the context holds no visibility masks (nrtSetPrimMasks)", fn);
+    if (((uintptr_t)l.ray_masks & 3u) != 0u) return fail(c, NRT_ERR_INVALID, "%s: masked queries: the ray_masks array is not 4-byte aligned", fn);
   }
   if (l.has_skip_ids()) { // (include/nanort_hip.h, "per-ray skip ids")
     if (custom)
@@ -115,7 +125,7 @@ static nrt_status take_slot(nrt_ctx *c, hipStream_t s, nrt_ctx::LaunchSlot **out
 }
 
 // The kernel a launch runs, from the context's tree and tunables and the launch's kind and options.
-enum class Walk { Literal, OneLevel, TwoLevel, MultiHit, Motion }; // k_traverse, k_traverse_wide of WIDTH 2 / 4, k_traverse_multihit, k_traverse_motion
+enum class Walk { Literal, OneLevel, TwoLevel, MultiHit, Motion, Masked }; // k_traverse, k_traverse_wide of WIDTH 2 / 4, k_traverse_multihit, k_traverse_motion, k_traverse_masked
 struct WalkChoice {
   Walk walk;
   bool plain_options; // prim ids are < num_faces: nothing can be rejected by the trace options -> the kernel variant without the id tests
@@ -135,7 +145,7 @@ static WalkChoice choose_walk(const nrt_ctx *c, const TraverseLaunch<T> &l) {
 #endif
   const bool custom = c->prim_kind != kPrimTriangles; // the custom primitives share one launch geometry
   const bool multihit = l.kind == Query::MultiHit;
-  const bool use_wide = (c->wide || custom || l.kind == Query::Occlusion) && l.kind != Query::Count && c->d_wide && !multihit && !l.motion();
+  const bool use_wide = (c->wide || custom || l.kind == Query::Occlusion) && l.kind != Query::Count && c->d_wide && !l.own_walk();
   // two levels per step: closest-hit walks of nested fp32 triangle trees, outside the profiling / splitting variants
   w.plain_options = l.opt->prim_ids_range[0] == 0u && l.opt->prim_ids_range[1] >= c->num_faces && l.opt->skip_prim_id >= c->num_faces &&
                     !l.opt->cull_back_face;
@@ -148,8 +158,8 @@ static WalkChoice choose_walk(const nrt_ctx *c, const TraverseLaunch<T> &l) {
   w.wide4_big = c->num_branch_records >= (1ull << 25) || (c->wide4_big_ok == 2 && c->prim_kind == kPrimTriangles); // (2: forced, for the tests)
   const bool use_wide4 = use_wide && c->d_wide4 && c->wide_stack == 10 && c->tree_nested && c->root_is_branch && !prof_needs_w2 &&
                          (!w.wide4_big || (!custom && !c->order4 && !(w.dbg & (32u | 8192u))));
-  w.walk = l.motion() ? Walk::Motion : multihit ? Walk::MultiHit : (use_wide4 ? Walk::TwoLevel : (use_wide ? Walk::OneLevel : Walk::Literal));
-  w.lds_entries = (multihit || l.motion()) ? kLdsStackDefault : (use_wide4 ? kWide4LdsStack : (custom ? 10 : (use_wide ? c->wide_stack : c->lds_stack)));
+  w.walk = l.masked() ? Walk::Masked : l.motion() ? Walk::Motion : multihit ? Walk::MultiHit : (use_wide4 ? Walk::TwoLevel : (use_wide ? Walk::OneLevel : Walk::Literal));
+  w.lds_entries = l.own_walk() ? kLdsStackDefault : (use_wide4 ? kWide4LdsStack : (custom ? 10 : (use_wide ? c->wide_stack : c->lds_stack)));
   return w;
 }
 
@@ -158,7 +168,8 @@ template <typename T>
 static GridPlan size_grid(nrt_ctx *c, const WalkChoice &w, uint64_t n) {
   auto &e = c->occupancy[(int)w.walk][c->prim_kind];
   if (e.blocks_per_cu == 0 || e.lds_entries != w.lds_entries)
-    e = {w.lds_entries, (unsigned)(w.walk == Walk::Motion    ? traverse_motion_blocks_per_cu<T>()
+    e = {w.lds_entries, (unsigned)(w.walk == Walk::Masked    ? traverse_masked_blocks_per_cu<T>()
+                        : w.walk == Walk::Motion    ? traverse_motion_blocks_per_cu<T>()
                         : w.walk == Walk::MultiHit  ? traverse_multihit_blocks_per_cu<T>()
                         : w.walk == Walk::Literal ? traverse_blocks_per_cu<T>(w.lds_entries)
                                                   : traverse_wide_blocks_per_cu<T>(w.lds_entries, c->prim_kind, w.wide4()))};
@@ -190,7 +201,7 @@ static void fill_walk_args(const nrt_ctx *c, const TraverseLaunch<T> &l, const W
   a.skip_prim = l.opt->skip_prim_id;
   a.skip_ids = l.skip_ids; // (MultiBatch: null, the table's skip_v instead)
   a.cull_back_face = l.opt->cull_back_face ? 1u : 0u;
-  a.any_hit = (l.kind == Query::Occlusion || l.kind == Query::OcclusionPrims || l.kind == Query::MotionOcclusion) ? 1u : 0u;
+  a.any_hit = (l.kind == Query::Occlusion || l.kind == Query::OcclusionPrims || l.kind == Query::MotionOcclusion || l.kind == Query::MaskedOcclusion) ? 1u : 0u;
   a.plain_options = w.plain_options ? 1u : 0u;
   a.root_test = c->tree_nested ? 0u : 1u;
   a.order4 = (c->order4 && w.wide4() && c->prim_kind == kPrimTriangles && l.kind != Query::Occlusion && !profiled) ? 1u : 0u;
@@ -277,7 +288,10 @@ static nrt_status enqueue_launch(nrt_ctx *c, const TraverseLaunch<T> &l, const W
   a.done_publish = post_pass ? 0u : 1u;
   const bool timed = l.timed && !use_rec;
   if (timed) HIPCHK(c, hipEventRecord(slot->t0, s));
-  if (w.walk == Walk::Motion) {
+  if (w.walk == Walk::Masked) {
+    HIPCHK(c, launch_traverse_masked<T>(a, (const uint32_t *)c->b_leaf_masks.p, l.ray_masks, grid, s));
+    c->last_kernel = sizeof(T) == 4 ? "nrt::k_traverse_masked<float>" : "nrt::k_traverse_masked<double>";
+  } else if (w.walk == Walk::Motion) {
     HIPCHK(c, launch_traverse_motion<T>(a, c->d_tris1, l.times, grid, s));
     c->last_kernel = sizeof(T) == 4 ? "nrt::k_traverse_motion<float>" : "nrt::k_traverse_motion<double>";
   } else if (w.walk == Walk::MultiHit) {
@@ -313,6 +327,23 @@ static nrt_status enqueue_launch(nrt_ctx *c, const TraverseLaunch<T> &l, const W
   return NRT_OK;
 }
 
+// The leaf-order words of a masked launch (masked.hip): b_leaf_masks[k] = b_prim_masks[d_tris[k].prim_id], derived again whenever the
+// setter or free_tree said that it no longer is (ctx.h, leaf_masks_stale).  Under launch_mutex.  No launch reads the array meanwhile:
+// whoever set the flag waited for the launches in flight first, and no masked launch starts without passing here.  The host waits for
+// the kernel, on the context's own stream: launches on every stream may read the array once this returns, with no event between them
+// (once per change of the masks or of the tree, some tens of microseconds; a Device refit in flight rewrites d_tris — in the same
+// order — so it is waited for first).
+template <typename T>
+static nrt_status refresh_leaf_masks(nrt_ctx *c) {
+  if (!c->leaf_masks_stale) return NRT_OK;
+  HIPCHK(c, refit_host_wait_locked(c));
+  if (nrt_status st = ensure(c, c->b_leaf_masks, std::max<size_t>(1, c->num_indices) * sizeof(uint32_t))) return st;
+  HIPCHK(c, launch_permute_masks<T>(c->d_tris, c->d_prim_masks, c->num_faces, (uint32_t *)c->b_leaf_masks.p, (uint32_t)c->num_indices, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->leaf_masks_stale = false;
+  return NRT_OK;
+}
+
 // Every ray query of the C ABI ends here.  launch_mutex is held from the checks to the last event record.
 template <typename T>
 static nrt_status traverse_device(nrt_ctx *c, TraverseLaunch<T> l) {
@@ -323,6 +354,7 @@ static nrt_status traverse_device(nrt_ctx *c, TraverseLaunch<T> l) {
   if (st || l.n == 0) return st;
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, refit_stream_wait(c, l.stream)); // (a Device refit in flight on another stream)
+  if (l.masked() && (st = refresh_leaf_masks<T>(c))) return st;
   nrt_ctx::LaunchSlot *slot = nullptr;
   if ((st = take_slot(c, l.stream, &slot))) return st;
   const WalkChoice w = choose_walk(c, l);
@@ -349,7 +381,7 @@ static nrt_status traverse_device(nrt_ctx *c, TraverseLaunch<T> l) {
 }
 
 const uint64_t kStagedRays = 1ull << 26; // rays per launch of the staged host paths (keeps staging bounded)
-const uint64_t kPiece = 1ull << 19; // rays per pipeline stage of traverse_host (19 MB up, 8 MB down in fp32), and per launch of the motion queries' staged path
+const uint64_t kPiece = 1ull << 19; // rays per pipeline stage of traverse_host (19 MB up, 8 MB down in fp32), and per launch of the motion and masked queries' staged path
 
 // Multi-hit (include/nanort_hip.h, nrtMultiHitTraverseBatch*): the kind's own refusals, ahead of the ones every query shares.
 template <typename T>
@@ -381,8 +413,8 @@ static nrt_status query_device(nrt_ctx *c, const char *fn, const TraverseLaunch<
 
 // The entry of every host form (`fn`: the entry point its message names): `host` carries the caller's HOST pointers, and no stream.
 // Its refusals in the order a caller has always seen them; then one call at a time (host_mutex: the staging buffers are the
-// context's), in pieces: the piece's rays — and its slice of the skip ids and of the times, where the query has them — up into
-// st_rays (st_skip, st_times), the launch over the staging buffers, the kind's record and flag bytes per ray of st_hits / st_mask
+// context's), in pieces: the piece's rays — and its slice of the skip ids, of the times and of the ray masks, where the query has them — up into
+// st_rays (st_skip, st_times, st_ray_masks), the launch over the staging buffers, the kind's record and flag bytes per ray of st_hits / st_mask
 // back into the caller's arrays (a null one is not copied).
 template <typename T>
 static nrt_status query_host(nrt_ctx *c, const char *fn, const TraverseLaunch<T> &host) {
@@ -403,7 +435,7 @@ static nrt_status query_host(nrt_ctx *c, const char *fn, const TraverseLaunch<T>
   // rays per launch: multi-hit keeps the staged records within 256 MiB whatever K is; the motion queries go in traverse_host's pieces
   // (their staging stays as small as the pipeline's)
   const uint64_t chunk = multihit        ? std::max<uint64_t>(1u, std::min<uint64_t>(1ull << 26, (256ull << 20) / rec_bytes))
-                         : host.motion() ? kPiece
+                         : (host.motion() || host.masked()) ? kPiece
                                          : kStagedRays;
   std::lock_guard<std::mutex> host_lock(c->host_mutex);
   HIPCHK(c, hipSetDevice(c->device));
@@ -425,6 +457,11 @@ static nrt_status query_host(nrt_ctx *c, const char *fn, const TraverseLaunch<T>
       if ((st = ensure(c, c->st_times, m * sizeof(T)))) return st;
       HIPCHK(c, hipMemcpyAsync(c->st_times.p, host.times + off, m * sizeof(T), hipMemcpyHostToDevice, c->stream));
       l.times = (const T *)c->st_times.p;
+    }
+    if (host.ray_masks) {
+      if ((st = ensure(c, c->st_ray_masks, m * sizeof(uint32_t)))) return st;
+      HIPCHK(c, hipMemcpyAsync(c->st_ray_masks.p, host.ray_masks + off, m * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+      l.ray_masks = (const uint32_t *)c->st_ray_masks.p;
     }
     l.rays = (const Ray *)c->st_rays.p;
     if (own_records) l.cyl_hits = c->st_hits.p;
@@ -453,7 +490,7 @@ static bool is_pinned_host(const void *p) {
 // trace -> download, one after the other.  With PAGE-LOCKED buffers (nrtHostAlloc) the batch is cut into pieces and
 // pipelined over three streams — piece k+1 uploads while piece k is traced and piece k-1 downloads (PCIe is full duplex) —
 // so the call approaches the slower of the two copy directions instead of their sum plus the kernel.
-// `host`: a Closest or Motion query over the caller's host arrays (skip ids and times may be null).  Whether the call takes the
+// `host`: a Closest, Motion or Masked query over the caller's host arrays (skip ids, times and ray masks may be null).  Whether the call takes the
 // pipeline is read off its size and its pointers before the lock; every other call, the refusals included, is query_host's.
 template <typename T>
 static nrt_status traverse_host(nrt_ctx *c, const TraverseLaunch<T> &host) {
@@ -464,9 +501,11 @@ static nrt_status traverse_host(nrt_ctx *c, const TraverseLaunch<T> &host) {
   uint8_t *mask = host.mask;
   const uint32_t *skip_ids = host.skip_ids;
   const T *times = host.times;
+  const uint32_t *ray_masks = host.ray_masks;
   const uint64_t n = host.n;
   if (c && n >= 2 * kPiece && c->host_pipeline && rays && hits && is_pinned_host(rays) && is_pinned_host(hits) && (!mask || is_pinned_host(mask)) &&
-      (!skip_ids || is_pinned_host(skip_ids)) && (!times || is_pinned_host(times))) {
+      (!skip_ids || is_pinned_host(skip_ids)) && (!times || is_pinned_host(times)) &&
+      (!ray_masks || is_pinned_host(ray_masks))) {
     std::lock_guard<std::mutex> host_lock(c->host_mutex);
     HIPCHK(c, hipSetDevice(c->device));
     if (!c->copy_in) HIPCHK(c, hipStreamCreateWithFlags(&c->copy_in, hipStreamNonBlocking));
@@ -477,7 +516,7 @@ static nrt_status traverse_host(nrt_ctx *c, const TraverseLaunch<T> &host) {
     nrt_status st;
     if ((st = ensure(c, c->st_rays, 2 * kPiece * sizeof(Ray))) || (st = ensure(c, c->st_hits, 2 * kPiece * sizeof(Hit))) ||
         (st = ensure(c, c->st_mask, 2 * kPiece)) || (skip_ids && (st = ensure(c, c->st_skip, 2 * kPiece * sizeof(uint32_t)))) ||
-        (times && (st = ensure(c, c->st_times, 2 * kPiece * sizeof(T)))))
+        (times && (st = ensure(c, c->st_times, 2 * kPiece * sizeof(T)))) || (ray_masks && (st = ensure(c, c->st_ray_masks, 2 * kPiece * sizeof(uint32_t)))))
       return st;
     uint64_t piece = 0;
     for (uint64_t off = 0; off < n; off += kPiece, piece++) {
@@ -488,16 +527,18 @@ static nrt_status traverse_host(nrt_ctx *c, const TraverseLaunch<T> &host) {
       uint8_t *d_m = (uint8_t *)c->st_mask.p + (size_t)b * kPiece;
       uint32_t *d_s = skip_ids ? (uint32_t *)c->st_skip.p + (size_t)b * kPiece : nullptr; // (the piece's slice of the ids travels with its rays)
       T *d_t = times ? (T *)c->st_times.p + (size_t)b * kPiece : nullptr;                 // (... and its slice of the times)
+      uint32_t *d_v = ray_masks ? (uint32_t *)c->st_ray_masks.p + (size_t)b * kPiece : nullptr; // (... and of the visibility words)
       // the ray slot is free once the trace that read it (two pieces ago) is done; the record slot once its download is
       if (piece >= 2) HIPCHK(c, hipStreamWaitEvent(c->copy_in, c->ev_tr[b], 0));
       HIPCHK(c, hipMemcpyAsync(d_r, rays + off, m * sizeof(Ray), hipMemcpyHostToDevice, c->copy_in));
       if (d_s) HIPCHK(c, hipMemcpyAsync(d_s, skip_ids + off, m * sizeof(uint32_t), hipMemcpyHostToDevice, c->copy_in));
       if (d_t) HIPCHK(c, hipMemcpyAsync(d_t, times + off, m * sizeof(T), hipMemcpyHostToDevice, c->copy_in));
+      if (d_v) HIPCHK(c, hipMemcpyAsync(d_v, ray_masks + off, m * sizeof(uint32_t), hipMemcpyHostToDevice, c->copy_in));
       HIPCHK(c, hipEventRecord(c->ev_in[b], c->copy_in));
       HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_in[b], 0));
       if (piece >= 2) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_out[b], 0));
       st = traverse_device<T>(c, {.kind = host.kind, .rays = d_r, .n = m, .opt = host.opt, .stream = c->stream, .timed = true, .hits = d_h, .mask = d_m,
-                                  .skip_ids = d_s, .times = d_t});
+                                  .skip_ids = d_s, .times = d_t, .ray_masks = d_v});
       if (st) { // (copies into the caller's buffers may still be in flight: let them land before the call returns)
         (void)hipStreamSynchronize(c->copy_in);
         (void)hipStreamSynchronize(c->stream);
@@ -514,7 +555,7 @@ static nrt_status traverse_host(nrt_ctx *c, const TraverseLaunch<T> &host) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return NRT_OK;
   }
-  return query_host<T>(c, "nrtTraverseBatch", host);
+  return query_host<T>(c, host.masked() ? "nrtTraverseBatchMasked" : "nrtTraverseBatch", host);
 }
 
 // One host batch spread over several contexts — one per GPU of the node, each holding the same tree (the build is
@@ -921,6 +962,42 @@ nrt_status nrtOccludedBatchMotionDevice_f64(nrt_ctx *c, const nrt_ray_f64 *r, co
                                             void *s) {
   return query_device<double>(c, "nrtOccludedBatchMotionDevice", {.kind = Query::MotionOcclusion, .rays = r, .n = n, .opt = o, .stream = (hipStream_t)s, .timed = true,
                                                                   .mask = m, .times = t});
+}
+
+// Visibility masks (include/nanort_hip.h; the triangles' words: api_geometry.hip): the closest-hit and occlusion queries with one word per ray.
+nrt_status nrtTraverseBatchMasked_f32(nrt_ctx *c, const nrt_ray_f32 *r, const uint32_t *v, uint64_t n, const nrt_trace_options *o, nrt_hit_f32 *h,
+                                      uint8_t *m) {
+  return traverse_host<float>(c, {.kind = Query::Masked, .rays = r, .n = n, .opt = o, .hits = h, .mask = m, .ray_masks = v});
+}
+nrt_status nrtTraverseBatchMasked_f64(nrt_ctx *c, const nrt_ray_f64 *r, const uint32_t *v, uint64_t n, const nrt_trace_options *o, nrt_hit_f64 *h,
+                                      uint8_t *m) {
+  return traverse_host<double>(c, {.kind = Query::Masked, .rays = r, .n = n, .opt = o, .hits = h, .mask = m, .ray_masks = v});
+}
+nrt_status nrtTraverseBatchMaskedDevice_f32(nrt_ctx *c, const nrt_ray_f32 *r, const uint32_t *v, uint64_t n, const nrt_trace_options *o,
+                                            nrt_hit_f32 *h, uint8_t *m, void *s) {
+  return query_device<float>(c, "nrtTraverseBatchMaskedDevice", {.kind = Query::Masked, .rays = r, .n = n, .opt = o, .stream = (hipStream_t)s, .timed = true,
+                                                                 .hits = h, .mask = m, .ray_masks = v});
+}
+nrt_status nrtTraverseBatchMaskedDevice_f64(nrt_ctx *c, const nrt_ray_f64 *r, const uint32_t *v, uint64_t n, const nrt_trace_options *o,
+                                            nrt_hit_f64 *h, uint8_t *m, void *s) {
+  return query_device<double>(c, "nrtTraverseBatchMaskedDevice", {.kind = Query::Masked, .rays = r, .n = n, .opt = o, .stream = (hipStream_t)s, .timed = true,
+                                                                  .hits = h, .mask = m, .ray_masks = v});
+}
+nrt_status nrtOccludedBatchMasked_f32(nrt_ctx *c, const nrt_ray_f32 *r, const uint32_t *v, uint64_t n, const nrt_trace_options *o, uint8_t *m) {
+  return query_host<float>(c, "nrtOccludedBatchMasked", {.kind = Query::MaskedOcclusion, .rays = r, .n = n, .opt = o, .mask = m, .ray_masks = v});
+}
+nrt_status nrtOccludedBatchMasked_f64(nrt_ctx *c, const nrt_ray_f64 *r, const uint32_t *v, uint64_t n, const nrt_trace_options *o, uint8_t *m) {
+  return query_host<double>(c, "nrtOccludedBatchMasked", {.kind = Query::MaskedOcclusion, .rays = r, .n = n, .opt = o, .mask = m, .ray_masks = v});
+}
+nrt_status nrtOccludedBatchMaskedDevice_f32(nrt_ctx *c, const nrt_ray_f32 *r, const uint32_t *v, uint64_t n, const nrt_trace_options *o, uint8_t *m,
+                                            void *s) {
+  return query_device<float>(c, "nrtOccludedBatchMaskedDevice", {.kind = Query::MaskedOcclusion, .rays = r, .n = n, .opt = o, .stream = (hipStream_t)s, .timed = true,
+                                                                 .mask = m, .ray_masks = v});
+}
+nrt_status nrtOccludedBatchMaskedDevice_f64(nrt_ctx *c, const nrt_ray_f64 *r, const uint32_t *v, uint64_t n, const nrt_trace_options *o, uint8_t *m,
+                                            void *s) {
+  return query_device<double>(c, "nrtOccludedBatchMaskedDevice", {.kind = Query::MaskedOcclusion, .rays = r, .n = n, .opt = o, .stream = (hipStream_t)s, .timed = true,
+                                                                  .mask = m, .ray_masks = v});
 }
 
 nrt_status nrtTraverseBatchMulti_f32(nrt_ctx *const *ctxs, uint32_t num_ctx, const nrt_ray_f32 *r, uint64_t n, uint64_t row_len,

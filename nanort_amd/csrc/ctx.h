@@ -153,7 +153,7 @@ struct nrt_ctx {
   int dyn_head = 1; // batches too small for a static group per wave: every wave's first chunk is its own (traverse.hip claim_init; tunable dyn_head)
   int wide_scramble = 0; // probe (tunable wide_scramble): the private node records in a pseudo-random order instead of pre-order
   // resident blocks per CU of the variants launched so far, by what selects the kernel: [walk][primitive kind] at `lds_entries` (a context keeps one precision; size_grid)
-  struct { int lds_entries; unsigned blocks_per_cu; } occupancy[5][kNumPrimKinds] = {};
+  struct { int lds_entries; unsigned blocks_per_cu; } occupancy[6][kNumPrimKinds] = {};
 
   hipEvent_t ev_b0 = nullptr, ev_b1 = nullptr;
   hipEvent_t ev_build_state = nullptr; // the builder's state block has reached build_state
@@ -169,6 +169,15 @@ struct nrt_ctx {
   DevBuf b_verts1, b_tris1, st_times; // (st_times: per-ray times of the staged host forms, beside st_rays)
   void *d_verts1 = nullptr; // == b_verts1.p while a keyframe is set
   void *d_tris1 = nullptr;  // == b_tris1.p while a keyframe and a tree are present
+
+  // visibility masks (nrtSetPrimMasks*): one word per face in face order, and the same words in leaf order beside
+  // d_tris (masked.hip, k_permute_masks).  leaf_masks_stale: b_leaf_masks is not the permutation of b_prim_masks by the current
+  // leaf order.  Set by the two events that can make it so — the setter (new words) and free_tree (every path to a new leaf order
+  // passes it: nrtBuild, nrtSetTree, the mesh and keyframe setters; a refit rewrites d_tris in the same order and leaves it) —
+  // and cleared by the one place that derives the array, the first masked query behind them (api_query.hip, refresh_leaf_masks).
+  DevBuf b_prim_masks, b_leaf_masks, st_ray_masks; // (st_ray_masks: per-ray words of the staged host forms, beside st_rays)
+  uint32_t *d_prim_masks = nullptr; // == b_prim_masks.p while masks are set
+  bool leaf_masks_stale = true;
 };
 
 inline nrt_status fail(nrt_ctx *c, nrt_status st, const char *fmt, ...) {
@@ -281,6 +290,7 @@ inline void free_tree(nrt_ctx *c) {
   c->d_indices = nullptr;
   c->d_tris = nullptr;
   c->d_tris1 = nullptr;
+  c->leaf_masks_stale = true; // (whatever tree comes next has a leaf order of its own)
   c->num_nodes = c->num_indices = 0;
   c->tree_depth = 0;
   c->refit_planned = false;
@@ -291,6 +301,7 @@ inline void free_mesh(nrt_ctx *c) {
   c->d_faces = nullptr;
   c->d_radii = nullptr;
   c->d_verts1 = nullptr; // (the motion keyframe goes with the mesh it belongs to)
+  c->d_prim_masks = nullptr; // (... and so do the visibility masks)
   c->num_faces = c->num_verts = 0;
   c->num_segs = 0;
 }

@@ -62,6 +62,17 @@ hipError_t launch_traverse_motion(const TraverseArgs<T> &args, const void *tris1
 template <typename T>
 int traverse_motion_blocks_per_cu();
 
+// ---- masked.hip: the visibility-mask walk (a triangle context with one 32-bit word per face) -----------------------------------
+// `leaf_masks`: the faces' words in leaf order, one beside each LeafTri<T> of args.tris; `ray_masks`: one word per ray, or null
+// (every ray 0xFFFFFFFF); args.any_hit: the occlusion query
+template <typename T>
+hipError_t launch_traverse_masked(const TraverseArgs<T> &args, const uint32_t *leaf_masks, const uint32_t *ray_masks, unsigned grid, hipStream_t s);
+template <typename T>
+int traverse_masked_blocks_per_cu();
+// leaf_masks[k] = masks[tris[k].prim_id] for the `n` LeafTri<T> records of `tris` (`masks`: num_faces words in face order)
+template <typename T>
+hipError_t launch_permute_masks(const void *tris, const uint32_t *masks, uint32_t num_faces, uint32_t *leaf_masks, uint32_t n, hipStream_t s);
+
 // ---- build.hip --------------------------------------------------------------------------------------------------------
 enum : unsigned { kBuildMorton = 1u, kBuildSubtreeDfs = 2u }; // gpu_build's build_flags: Morton pre-pass, one-node-per-step subtree kernel
 struct BuildResult {
