@@ -76,17 +76,27 @@ def hidden_faces(f, prim_masks, m):
     return f_m
 
 
-def expected(oracle, nodes, idx, v, f, prim_masks, rays, ray_masks, opts=None):
-    """(hits, mask) a masked query must return.  ray_masks None: every ray 0xFFFFFFFF."""
+def expected(oracle, nodes, idx, v, f, prim_masks, rays, ray_masks, opts=None, stride=None, count=False):
+    """(hits, mask) a masked query must return.  ray_masks None: every ray 0xFFFFFFFF.  `stride`: the vertex rows' stride in bytes
+    (None: tight xyz).  count: also {word: the oracle's max-stack counter over the rays that carry it}."""
     n = rays.shape[0]
     hits = np.zeros(n, dtype=hit_dtype(v.dtype))
     mask = np.zeros(n, dtype=np.uint8)
     words = np.full(n, 0xFFFFFFFF, dtype=np.uint32) if ray_masks is None else np.asarray(ray_masks, dtype=np.uint32)
+    depth = {}
     for m in np.unique(words):
         sel = np.nonzero(words == m)[0]
-        h, k = oracle.traverse(nodes, idx, v, hidden_faces(f, prim_masks, m), np.ascontiguousarray(rays[sel]), opts)
-        hits[sel], mask[sel] = h, k
-    return hits, mask
+        out = oracle.traverse(nodes, idx, v, hidden_faces(f, prim_masks, m), np.ascontiguousarray(rays[sel]), opts, stride=stride, count=count)
+        hits[sel], mask[sel] = out[0], out[1]
+        if count:
+            depth[int(m)] = int(out[2][3])
+    return (hits, mask, depth) if count else (hits, mask)
+
+
+def other_primitive(eh, em, ph, pm):
+    """Per ray: the masked record (eh, em) is a hit on another primitive than the unmasked record (ph, pm) names (which may be a
+    miss): the ray went on walking past what it does not see."""
+    return (em != 0) & ((pm == 0) | (eh["prim_id"] != ph["prim_id"]))
 
 
 def miss_records(rays, real):

@@ -1,13 +1,15 @@
-"""The three kernels that run the binary walk (nanort_amd/csrc/binary_walk_dev.h) under odd thresholds and work splits: closest hit
-with the literal walk (tunable wide = 0, k_traverse), multi-hit (k_traverse_multihit) and motion closest hit / occlusion
-(k_traverse_motion).  The walk's refill gate, its early exit from the inner-node loop and the static / dynamic hand-out of rays are
-one piece of code under all three; whatever the setting, every ray is traced exactly once and its walk is its own, so records,
-masks and counts equal the default configuration's byte for byte.  (The defaults themselves are tied to the oracle by
-test_gpu_traverse.py, test_gpu_launch_variants.py, test_gpu_skip_ids.py, test_gpu_multihit.py and test_gpu_motion.py;
-test_work_distribution_tunables_cover_every_ray sweeps the same settings on the default wide walk.)"""
+"""The four kernels that run the binary walk (nanort_amd/csrc/binary_walk_dev.h) under odd thresholds and work splits: closest hit
+with the literal walk (tunable wide = 0, k_traverse), multi-hit (k_traverse_multihit), motion closest hit / occlusion
+(k_traverse_motion) and masked closest hit / occlusion (k_traverse_masked).  The walk's refill gate, its early exit from the
+inner-node loop and the static / dynamic hand-out of rays are one piece of code under all four; whatever the setting, every ray is
+traced exactly once and its walk is its own, so records, masks and counts equal the default configuration's byte for byte.  (The
+defaults themselves are tied to the oracle by test_gpu_traverse.py, test_gpu_launch_variants.py, test_gpu_skip_ids.py,
+test_gpu_multihit.py, test_gpu_motion.py, test_gpu_masks.py and test_gpu_own_walks.py; test_work_distribution_tunables_cover_every_ray
+sweeps the same settings on the default wide walk.)"""
 import numpy as np
 import pytest
 
+import masks_fixture as kf
 import motion_fixture as mf
 from nanort_amd import BVHAccel, MotionTriangleMesh, TriangleMesh, scenes
 
@@ -20,7 +22,7 @@ COMBOS = [dict(refill_min=1, trav_min=1), dict(refill_min=64, trav_min=64), dict
           dict(blocks_per_cu=1, static_bands=3)]
 
 
-def run_walks(plain, moving, rays, times):
+def run_walks(plain, moving, rays, times, words):
     """name -> bytes of everything the walk's launch wrote."""
     out = {}
     h, m = plain.TraverseBatch(rays)
@@ -33,6 +35,11 @@ def run_walks(plain, moving, rays, times):
     assert moving.LastKernelName() == "nrt::k_traverse_motion<float>"
     out["motion"] = h.tobytes() + m.tobytes()
     out["motion occlusion"] = moving.OccludedBatchMotion(rays, times).tobytes()
+    h, m = plain.TraverseBatchMasked(rays, words)
+    assert plain.LastKernelName() == "nrt::k_traverse_masked<float>"
+    out["masked"] = h.tobytes() + m.tobytes()
+    out["masked occlusion"] = plain.OccludedBatchMasked(rays, words).tobytes()
+    assert plain.LastKernelName() == "nrt::k_traverse_masked<float>"
     return out
 
 
@@ -43,14 +50,19 @@ def world():
     plain, moving = BVHAccel(np.float32), BVHAccel(np.float32)
     assert plain.Build(f.shape[0], TriangleMesh(v, f))
     plain.SetTunable("wide", 0)
+    plain.SetPrimMasks(kf.prim_patterns(f.shape[0])["random"])
     assert moving.Build(f.shape[0], MotionTriangleMesh(v, mf.deformations(v)["wave"], f))
     cases = {}
     for size in SIZES:
         rays = scenes.camera_rays(*size)
         times = mf.assign_times(rays.shape[0], np.float32)
-        cases[size] = (rays, times, run_walks(plain, moving, rays, times))  # under the default tunables, computed once
-    h, m = plain.TraverseBatch(cases[SIZES[0]][0])
+        words = kf.assign_ray_masks(rays.shape[0])
+        cases[size] = (rays, times, words, run_walks(plain, moving, rays, times, words))  # under the default tunables, computed once
+    rays, _, words, _ = cases[SIZES[0]]
+    h, m = plain.TraverseBatch(rays)
     assert 0 < int(m.sum())  # (not vacuous: rays hit the mesh)
+    kh, km = plain.TraverseBatchMasked(rays, words)
+    assert 0 < int(km.sum()) and int(mf.differs(kh, km, h, m).sum()) > 0  # (... also through the masks, which change records)
     yield plain, moving, cases
     plain.close()
     moving.close()
@@ -60,13 +72,13 @@ def world():
 @pytest.mark.parametrize("combo", COMBOS, ids=lambda c: ",".join("%s=%d" % kv for kv in c.items()))
 def test_thresholds_and_work_split_leave_every_record_as_it_is(world, combo, size):
     plain, moving, cases = world
-    rays, times, ref = cases[size]
+    rays, times, words, ref = cases[size]
     saved = [(a, k, a.GetTunable(k)) for a in (plain, moving) for k in combo]
     try:
         for a in (plain, moving):
             for k, val in combo.items():
                 a.SetTunable(k, val)
-        got = run_walks(plain, moving, rays, times)
+        got = run_walks(plain, moving, rays, times, words)
     finally:
         for a, k, val in saved:
             a.SetTunable(k, val)

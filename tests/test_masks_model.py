@@ -109,6 +109,32 @@ def test_all_ones_is_the_plain_query_and_zero_sees_nothing(oracle, world):
     assert_hits_identical(hm, mm, *kf.expected(oracle, nodes, idx, v, f, pat["random"], rays, np.zeros(rays.shape[0], dtype=np.uint32)))
 
 
+@pytest.mark.parametrize("real", REALS, ids=["f32", "f64"])
+def test_fixture_conditions_of_the_own_walk_tests(oracle, real):
+    """What tests/test_gpu_own_walks.py rests on, from the reference alone (measured, f32 and f64 alike unless said): the pile's tree is
+    138 deep and the walk's max-stack counter is 137 for each of the eight ray words — past the masked walk's 32 LDS entries — with
+    the random and with the mod3 prim words; with the random words 1318 of the 1500 rays hit and 667 get a hit on another primitive
+    than the unmasked record's (a quarter is asked for).  Over the soup 975 of the 6000 hostile rays hit through the masks and 288
+    (f64: 286) hit another primitive than without them (150 asked for)."""
+    import own_walks_fixture as ow
+
+    v, f, rays, words = ow.pile(real)
+    nodes, idx, st = oracle.build(v, f)
+    assert st["max_tree_depth"] > ow.PILE_MIN_STACK
+    assert sorted(np.unique(words)) == sorted(kf.RAY_MASK_VALUES)
+    for name in ("random", "mod3"):
+        pm = kf.prim_patterns(f.shape[0])[name]
+        _, _, depth, hits, other = ow.masked_figures(oracle, nodes, idx, v, f, pm, rays, words)
+        assert len(depth) == len(kf.RAY_MASK_VALUES) and min(depth.values()) > ow.PILE_MIN_STACK, (name, depth)
+        assert hits > 0
+        if name == "random":
+            assert other >= ow.PILE_MIN_OTHER, other
+    vbuf, f, stride, rays, words, pm = ow.soup_masked(real)
+    nodes, idx, _ = oracle.build(vbuf, f, stride=stride)
+    _, _, _, hits, other = ow.masked_figures(oracle, nodes, idx, vbuf, f, pm, rays, words, stride)
+    assert hits > 0 and other >= ow.SOUP_MIN_OTHER, (hits, other)
+
+
 # ---- 3. include/nanort.h, MaskedTriangleIntersector on the host ------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def host_check(tmp_path_factory):

@@ -56,6 +56,23 @@ def test_fixture_condition_the_time_matters(oracle, c1_mesh, name):
     assert share >= 0.10, share
 
 
+@pytest.mark.parametrize("real", REALS, ids=["f32", "f64"])
+def test_fixture_conditions_of_the_own_walk_tests(oracle, real):
+    """What tests/test_gpu_own_walks.py rests on, from the reference alone (measured, f32 and f64 alike): over the soup with its
+    jittered keyframe 1125 of the 6000 hostile rays hit at their times (100 asked for) and 681 records differ from the keyframe-0
+    record (50 asked for); the pile's tree with union boxes is still deeper than the motion walk's 32 LDS entries (max stack 137)."""
+    import own_walks_fixture as ow
+
+    v0, v1, f, rays, times = ow.soup_motion(real)
+    nodes, idx, _ = ow.motion_tree(oracle, v0, v1, f)
+    _, _, hits, differ = ow.motion_figures(oracle, nodes, idx, v0, v1, f, rays, times)
+    assert hits >= ow.SOUP_MOTION_MIN_HITS and differ >= ow.SOUP_MOTION_MIN_DIFFER, (hits, differ)
+    v, f, rays, _ = ow.pile(real)
+    nodes, idx, st = ow.motion_tree(oracle, v, ow.pile_keyframe1(v), f)
+    _, _, cnt = oracle.traverse(nodes, idx, v, f, rays, count=True)
+    assert st["max_tree_depth"] > ow.PILE_MIN_STACK and cnt[3] > ow.PILE_MIN_STACK
+
+
 def test_binding_table_header_and_library_carry_the_twelve_symbols():
     header = open(os.path.join(ROOT, "include", "nanort_hip.h")).read()
     assert len(NAMES) == 12
