@@ -1299,163 +1299,52 @@ struct build_tag {
 };
 
 #ifdef NANORT_USE_HIP_BACKEND
-// float/double -> the matching C-ABI entry points
+// float/double -> the matching C-ABI entry points (include/nanort_hip.h): ONE list, a line per entry point, instantiated for
+// {float, f32} and {double, f64}.  (constexpr pointers: a call through one is a direct call, and none needs a definition.)
 template <typename T>
 struct HipApi;
-template <>
-struct HipApi<float> {
-  typedef nrt_ray_f32 RayPod;
-  typedef nrt_node_f32 NodePod;
-  typedef nrt_hit_f32 HitPod;
-  typedef nrt_build_options_f32 BuildPod;
-  static nrt_status SetMesh(nrt_ctx *c, const float *v, size_t s, const unsigned int *f, unsigned int n) { return nrtSetMesh_f32(c, v, s, f, n); }
-  static nrt_status Build(nrt_ctx *c, const BuildPod *o, nrt_build_stats *st, uint64_t *nn) { return nrtBuild_f32(c, o, st, nn); }
-  static nrt_status GetTree(nrt_ctx *c, NodePod *n, uint32_t *i) { return nrtGetTree_f32(c, n, i); }
-  static nrt_status TreeBounds(nrt_ctx *c, float *lo, float *hi) { return nrtGetTreeBounds_f32(c, lo, hi); }
-  static nrt_status SetTree(nrt_ctx *c, const NodePod *n, uint64_t nn, const uint32_t *i, uint64_t ni) { return nrtSetTree_f32(c, n, nn, i, ni); }
-  static nrt_status Refit(nrt_ctx *c, const float *v, size_t s) { return nrtRefit_f32(c, v, s); }
-  static nrt_status Traverse(nrt_ctx *c, const RayPod *r, uint64_t n, const nrt_trace_options *o, HitPod *h, uint8_t *m) {
-    return nrtTraverseBatch_f32(c, r, n, o, h, m);
-  }
-  static nrt_status TraverseDevice(nrt_ctx *c, const RayPod *r, uint64_t n, const nrt_trace_options *o, HitPod *h, uint8_t *m, void *s) {
-    return nrtTraverseBatchDevice_f32(c, r, n, o, h, m, s);
-  }
-  static nrt_status TraverseBatches(nrt_ctx *c, uint32_t nb, const RayPod *const *r, const uint64_t *n, const nrt_trace_options *o, HitPod *const *h,
-                                    uint8_t *const *m, const uint32_t *fl, void *s) {
-    return nrtTraverseBatchesDevice_f32(c, nb, r, n, o, h, m, fl, s);
-  }
-  static nrt_status TraverseBatchesHost(nrt_ctx *c, uint32_t nb, const RayPod *const *r, const uint64_t *n, const nrt_trace_options *o, HitPod *const *h,
-                                        uint8_t *const *m, const uint32_t *fl) {
-    return nrtTraverseBatches_f32(c, nb, r, n, o, h, m, fl);
-  }
-  static nrt_status TraverseMulti(nrt_ctx *const *cs, uint32_t nc, const RayPod *r, uint64_t n, uint64_t row, const nrt_trace_options *o, HitPod *h, uint8_t *m) {
-    return nrtTraverseBatchMulti_f32(cs, nc, r, n, row, o, h, m);
-  }
-  static nrt_status Occluded(nrt_ctx *c, const RayPod *r, uint64_t n, const nrt_trace_options *o, uint8_t *m) { return nrtOccludedBatch_f32(c, r, n, o, m); }
-  static nrt_status OccludedDevice(nrt_ctx *c, const RayPod *r, uint64_t n, const nrt_trace_options *o, uint8_t *m, void *s) {
-    return nrtOccludedBatchDevice_f32(c, r, n, o, m, s);
-  }
-  // (per-ray skip ids, include/nanort_hip.h: the calls above with one skip id per ray)
-  static nrt_status TraverseSkip(nrt_ctx *c, const RayPod *r, uint64_t n, const nrt_trace_options *o, const uint32_t *ids, HitPod *h, uint8_t *m) {
-    return nrtTraverseBatchSkip_f32(c, r, n, o, ids, h, m);
-  }
-  static nrt_status TraverseSkipDevice(nrt_ctx *c, const RayPod *r, uint64_t n, const nrt_trace_options *o, const uint32_t *ids, HitPod *h, uint8_t *m,
-                                       void *s) {
-    return nrtTraverseBatchSkipDevice_f32(c, r, n, o, ids, h, m, s);
-  }
-  static nrt_status OccludedSkip(nrt_ctx *c, const RayPod *r, uint64_t n, const nrt_trace_options *o, const uint32_t *ids, uint8_t *m) {
-    return nrtOccludedBatchSkip_f32(c, r, n, o, ids, m);
-  }
-  static nrt_status OccludedSkipDevice(nrt_ctx *c, const RayPod *r, uint64_t n, const nrt_trace_options *o, const uint32_t *ids, uint8_t *m, void *s) {
-    return nrtOccludedBatchSkipDevice_f32(c, r, n, o, ids, m, s);
-  }
-  static nrt_status TraverseBatchesSkip(nrt_ctx *c, uint32_t nb, const RayPod *const *r, const uint64_t *n, const nrt_trace_options *o,
-                                        const uint32_t *const *ids, HitPod *const *h, uint8_t *const *m, const uint32_t *fl, void *s) {
-    return nrtTraverseBatchesSkipDevice_f32(c, nb, r, n, o, ids, h, m, fl, s);
-  }
-  static nrt_status TraverseBatchesSkipHost(nrt_ctx *c, uint32_t nb, const RayPod *const *r, const uint64_t *n, const nrt_trace_options *o,
-                                            const uint32_t *const *ids, HitPod *const *h, uint8_t *const *m, const uint32_t *fl) {
-    return nrtTraverseBatchesSkip_f32(c, nb, r, n, o, ids, h, m, fl);
-  }
-  static nrt_status MultiHit(nrt_ctx *c, const RayPod *r, uint64_t n, uint32_t k, const nrt_trace_options *o, HitPod *h, uint32_t *cnt) {
-    return nrtMultiHitTraverseBatch_f32(c, r, n, k, o, h, cnt);
-  }
-  static nrt_status MultiHitDevice(nrt_ctx *c, const RayPod *r, uint64_t n, uint32_t k, const nrt_trace_options *o, HitPod *h, uint32_t *cnt, void *s) {
-    return nrtMultiHitTraverseBatchDevice_f32(c, r, n, k, o, h, cnt, s);
-  }
-  // (motion blur, include/nanort_hip.h: the second vertex keyframe and the queries with one time per ray)
-  static nrt_status SetMeshMotion(nrt_ctx *c, const float *v, size_t s) { return nrtSetMeshMotion_f32(c, v, s); }
-  static nrt_status TraverseMotion(nrt_ctx *c, const RayPod *r, const float *t, uint64_t n, const nrt_trace_options *o, HitPod *h, uint8_t *m) {
-    return nrtTraverseBatchMotion_f32(c, r, t, n, o, h, m);
-  }
-  static nrt_status OccludedMotion(nrt_ctx *c, const RayPod *r, const float *t, uint64_t n, const nrt_trace_options *o, uint8_t *m) {
-    return nrtOccludedBatchMotion_f32(c, r, t, n, o, m);
-  }
-  // (visibility masks, include/nanort_hip.h: the queries with one word per ray; the setter nrtSetPrimMasks has no precision)
-  static nrt_status TraverseMasked(nrt_ctx *c, const RayPod *r, const uint32_t *v, uint64_t n, const nrt_trace_options *o, HitPod *h, uint8_t *m) {
-    return nrtTraverseBatchMasked_f32(c, r, v, n, o, h, m);
-  }
-  static nrt_status OccludedMasked(nrt_ctx *c, const RayPod *r, const uint32_t *v, uint64_t n, const nrt_trace_options *o, uint8_t *m) {
-    return nrtOccludedBatchMasked_f32(c, r, v, n, o, m);
-  }
-};
-template <>
-struct HipApi<double> {
-  typedef nrt_ray_f64 RayPod;
-  typedef nrt_node_f64 NodePod;
-  typedef nrt_hit_f64 HitPod;
-  typedef nrt_build_options_f64 BuildPod;
-  static nrt_status SetMesh(nrt_ctx *c, const double *v, size_t s, const unsigned int *f, unsigned int n) { return nrtSetMesh_f64(c, v, s, f, n); }
-  static nrt_status Build(nrt_ctx *c, const BuildPod *o, nrt_build_stats *st, uint64_t *nn) { return nrtBuild_f64(c, o, st, nn); }
-  static nrt_status GetTree(nrt_ctx *c, NodePod *n, uint32_t *i) { return nrtGetTree_f64(c, n, i); }
-  static nrt_status TreeBounds(nrt_ctx *c, double *lo, double *hi) { return nrtGetTreeBounds_f64(c, lo, hi); }
-  static nrt_status SetTree(nrt_ctx *c, const NodePod *n, uint64_t nn, const uint32_t *i, uint64_t ni) { return nrtSetTree_f64(c, n, nn, i, ni); }
-  static nrt_status Refit(nrt_ctx *c, const double *v, size_t s) { return nrtRefit_f64(c, v, s); }
-  static nrt_status Traverse(nrt_ctx *c, const RayPod *r, uint64_t n, const nrt_trace_options *o, HitPod *h, uint8_t *m) {
-    return nrtTraverseBatch_f64(c, r, n, o, h, m);
-  }
-  static nrt_status TraverseDevice(nrt_ctx *c, const RayPod *r, uint64_t n, const nrt_trace_options *o, HitPod *h, uint8_t *m, void *s) {
-    return nrtTraverseBatchDevice_f64(c, r, n, o, h, m, s);
-  }
-  static nrt_status TraverseBatches(nrt_ctx *c, uint32_t nb, const RayPod *const *r, const uint64_t *n, const nrt_trace_options *o, HitPod *const *h,
-                                    uint8_t *const *m, const uint32_t *fl, void *s) {
-    return nrtTraverseBatchesDevice_f64(c, nb, r, n, o, h, m, fl, s);
-  }
-  static nrt_status TraverseBatchesHost(nrt_ctx *c, uint32_t nb, const RayPod *const *r, const uint64_t *n, const nrt_trace_options *o, HitPod *const *h,
-                                        uint8_t *const *m, const uint32_t *fl) {
-    return nrtTraverseBatches_f64(c, nb, r, n, o, h, m, fl);
-  }
-  static nrt_status TraverseMulti(nrt_ctx *const *cs, uint32_t nc, const RayPod *r, uint64_t n, uint64_t row, const nrt_trace_options *o, HitPod *h, uint8_t *m) {
-    return nrtTraverseBatchMulti_f64(cs, nc, r, n, row, o, h, m);
-  }
-  static nrt_status Occluded(nrt_ctx *c, const RayPod *r, uint64_t n, const nrt_trace_options *o, uint8_t *m) { return nrtOccludedBatch_f64(c, r, n, o, m); }
-  static nrt_status OccludedDevice(nrt_ctx *c, const RayPod *r, uint64_t n, const nrt_trace_options *o, uint8_t *m, void *s) {
-    return nrtOccludedBatchDevice_f64(c, r, n, o, m, s);
-  }
-  // (per-ray skip ids, include/nanort_hip.h: the calls above with one skip id per ray)
-  static nrt_status TraverseSkip(nrt_ctx *c, const RayPod *r, uint64_t n, const nrt_trace_options *o, const uint32_t *ids, HitPod *h, uint8_t *m) {
-    return nrtTraverseBatchSkip_f64(c, r, n, o, ids, h, m);
-  }
-  static nrt_status TraverseSkipDevice(nrt_ctx *c, const RayPod *r, uint64_t n, const nrt_trace_options *o, const uint32_t *ids, HitPod *h, uint8_t *m,
-                                       void *s) {
-    return nrtTraverseBatchSkipDevice_f64(c, r, n, o, ids, h, m, s);
-  }
-  static nrt_status OccludedSkip(nrt_ctx *c, const RayPod *r, uint64_t n, const nrt_trace_options *o, const uint32_t *ids, uint8_t *m) {
-    return nrtOccludedBatchSkip_f64(c, r, n, o, ids, m);
-  }
-  static nrt_status OccludedSkipDevice(nrt_ctx *c, const RayPod *r, uint64_t n, const nrt_trace_options *o, const uint32_t *ids, uint8_t *m, void *s) {
-    return nrtOccludedBatchSkipDevice_f64(c, r, n, o, ids, m, s);
-  }
-  static nrt_status TraverseBatchesSkip(nrt_ctx *c, uint32_t nb, const RayPod *const *r, const uint64_t *n, const nrt_trace_options *o,
-                                        const uint32_t *const *ids, HitPod *const *h, uint8_t *const *m, const uint32_t *fl, void *s) {
-    return nrtTraverseBatchesSkipDevice_f64(c, nb, r, n, o, ids, h, m, fl, s);
-  }
-  static nrt_status TraverseBatchesSkipHost(nrt_ctx *c, uint32_t nb, const RayPod *const *r, const uint64_t *n, const nrt_trace_options *o,
-                                            const uint32_t *const *ids, HitPod *const *h, uint8_t *const *m, const uint32_t *fl) {
-    return nrtTraverseBatchesSkip_f64(c, nb, r, n, o, ids, h, m, fl);
-  }
-  static nrt_status MultiHit(nrt_ctx *c, const RayPod *r, uint64_t n, uint32_t k, const nrt_trace_options *o, HitPod *h, uint32_t *cnt) {
-    return nrtMultiHitTraverseBatch_f64(c, r, n, k, o, h, cnt);
-  }
-  static nrt_status MultiHitDevice(nrt_ctx *c, const RayPod *r, uint64_t n, uint32_t k, const nrt_trace_options *o, HitPod *h, uint32_t *cnt, void *s) {
-    return nrtMultiHitTraverseBatchDevice_f64(c, r, n, k, o, h, cnt, s);
-  }
-  // (motion blur, include/nanort_hip.h: the second vertex keyframe and the queries with one time per ray)
-  static nrt_status SetMeshMotion(nrt_ctx *c, const double *v, size_t s) { return nrtSetMeshMotion_f64(c, v, s); }
-  static nrt_status TraverseMotion(nrt_ctx *c, const RayPod *r, const double *t, uint64_t n, const nrt_trace_options *o, HitPod *h, uint8_t *m) {
-    return nrtTraverseBatchMotion_f64(c, r, t, n, o, h, m);
-  }
-  static nrt_status OccludedMotion(nrt_ctx *c, const RayPod *r, const double *t, uint64_t n, const nrt_trace_options *o, uint8_t *m) {
-    return nrtOccludedBatchMotion_f64(c, r, t, n, o, m);
-  }
-  // (visibility masks, include/nanort_hip.h: the queries with one word per ray; the setter nrtSetPrimMasks has no precision)
-  static nrt_status TraverseMasked(nrt_ctx *c, const RayPod *r, const uint32_t *v, uint64_t n, const nrt_trace_options *o, HitPod *h, uint8_t *m) {
-    return nrtTraverseBatchMasked_f64(c, r, v, n, o, h, m);
-  }
-  static nrt_status OccludedMasked(nrt_ctx *c, const RayPod *r, const uint32_t *v, uint64_t n, const nrt_trace_options *o, uint8_t *m) {
-    return nrtOccludedBatchMasked_f64(c, r, v, n, o, m);
-  }
-};
+#define NANORT_HIP_ENTRY(name, entry, S) static constexpr decltype(&entry##_##S) name = &entry##_##S;
+#define NANORT_HIP_API(T, S)                                                      \
+  template <>                                                                     \
+  struct HipApi<T> {                                                              \
+    typedef nrt_ray_##S RayPod;                                                   \
+    typedef nrt_node_##S NodePod;                                                 \
+    typedef nrt_hit_##S HitPod;                                                   \
+    typedef nrt_build_options_##S BuildPod;                                       \
+    NANORT_HIP_ENTRY(SetMesh, nrtSetMesh, S)                                      \
+    NANORT_HIP_ENTRY(Build, nrtBuild, S)                                          \
+    NANORT_HIP_ENTRY(GetTree, nrtGetTree, S)                                      \
+    NANORT_HIP_ENTRY(TreeBounds, nrtGetTreeBounds, S)                             \
+    NANORT_HIP_ENTRY(SetTree, nrtSetTree, S)                                      \
+    NANORT_HIP_ENTRY(Refit, nrtRefit, S)                                          \
+    NANORT_HIP_ENTRY(Traverse, nrtTraverseBatch, S)                               \
+    NANORT_HIP_ENTRY(TraverseDevice, nrtTraverseBatchDevice, S)                   \
+    NANORT_HIP_ENTRY(TraverseBatches, nrtTraverseBatchesDevice, S)                \
+    NANORT_HIP_ENTRY(TraverseBatchesHost, nrtTraverseBatches, S)                  \
+    NANORT_HIP_ENTRY(TraverseMulti, nrtTraverseBatchMulti, S)                     \
+    NANORT_HIP_ENTRY(Occluded, nrtOccludedBatch, S)                               \
+    NANORT_HIP_ENTRY(OccludedDevice, nrtOccludedBatchDevice, S)                   \
+    /* per-ray skip ids: the calls above with one skip id per ray */              \
+    NANORT_HIP_ENTRY(TraverseSkip, nrtTraverseBatchSkip, S)                       \
+    NANORT_HIP_ENTRY(TraverseSkipDevice, nrtTraverseBatchSkipDevice, S)           \
+    NANORT_HIP_ENTRY(OccludedSkip, nrtOccludedBatchSkip, S)                       \
+    NANORT_HIP_ENTRY(OccludedSkipDevice, nrtOccludedBatchSkipDevice, S)           \
+    NANORT_HIP_ENTRY(TraverseBatchesSkip, nrtTraverseBatchesSkipDevice, S)        \
+    NANORT_HIP_ENTRY(TraverseBatchesSkipHost, nrtTraverseBatchesSkip, S)          \
+    NANORT_HIP_ENTRY(MultiHit, nrtMultiHitTraverseBatch, S)                       \
+    NANORT_HIP_ENTRY(MultiHitDevice, nrtMultiHitTraverseBatchDevice, S)           \
+    /* motion blur: the second vertex keyframe, the queries with a time per ray */ \
+    NANORT_HIP_ENTRY(SetMeshMotion, nrtSetMeshMotion, S)                          \
+    NANORT_HIP_ENTRY(TraverseMotion, nrtTraverseBatchMotion, S)                   \
+    NANORT_HIP_ENTRY(OccludedMotion, nrtOccludedBatchMotion, S)                   \
+    /* visibility masks: the queries with one word per ray (the setter, nrtSetPrimMasks, has no precision) */ \
+    NANORT_HIP_ENTRY(TraverseMasked, nrtTraverseBatchMasked, S)                   \
+    NANORT_HIP_ENTRY(OccludedMasked, nrtOccludedBatchMasked, S)                   \
+  };
+NANORT_HIP_API(float, f32)
+NANORT_HIP_API(double, f64)
+#undef NANORT_HIP_API
+#undef NANORT_HIP_ENTRY
 struct CtxDeleter {
   void operator()(nrt_ctx *c) const { nrtDestroy(c); }
 };
@@ -1480,7 +1369,8 @@ class BVHAccel {
   // makes the change to contexts of its own (copy-on-write: the primitive arrays Build() was given are sent again, so they
   // must outlive the accel, as the reference's Traverse() already requires).  Neither side ever traces the other's tree.
   // A move transfers the contexts, a pending read-back and the staging buffers as they are (no read-back); the source is
-  // left empty (IsValid() false), ready to be rebuilt or destroyed.
+  // left empty (IsValid() false), ready to be rebuilt or destroyed.  What the device holds travels as two records (DeviceState,
+  // DeviceGeometry below): the copy copies them, the move takes them and leaves default-constructed ones in the source.
   BVHAccel(const BVHAccel &o) : pad0_(0) { CopyFrom(o); }
   BVHAccel &operator=(const BVHAccel &o) {
     if (this != &o) CopyFrom(o);
@@ -1511,7 +1401,7 @@ class BVHAccel {
   template <class Prim>
   bool Refit(const Prim &p) {
 #ifdef NANORT_USE_HIP_BACKEND
-    if (ctx_ && !device_tree_stale_) {  // (the GPU holds this tree: refit it there — Refit(TriangleMesh) — or rebuild)
+    if (dev_.ctx && !dev_.tree_stale) {  // (the GPU holds this tree: refit it there — Refit(TriangleMesh) — or rebuild)
       backend_error_ = "Refit: this tree was built on the GPU over built-in primitives; refit a triangle mesh with Refit(TriangleMesh)";
       return false;
     }
@@ -1524,68 +1414,39 @@ class BVHAccel {
   // with a copy first moves to contexts of its own (copy-on-write: the copy keeps its tree and positions) and keeps the new
   // vertex array, as Build() does: it must outlive the accel.  The host copy of the tree is read back on the next host access.
   bool Refit(const TriangleMesh<T> &mesh) {
-    typedef detail::HipApi<T> Api;
-    if (!ctx_) return RefitHost(mesh);  // (a tree built on the host or Load()ed before any GPU Build())
+    if (!dev_.ctx) return RefitHost(mesh);  // (a tree built on the host or Load()ed before any GPU Build())
     std::lock_guard<std::mutex> lock(batch_mutex_);
-    if (device_prim_kind_ == 1 || device_prim_kind_ == 2 || device_prim_kind_ == 3) {
-      backend_error_ = device_prim_kind_ == 1 ? "Refit: sphere trees do not refit on the GPU (Build() again)"
-                                              : (device_prim_kind_ == 2 ? "Refit: cylinder trees do not refit on the GPU (Build() again)"
-                                                                        : "Refit: curve trees do not refit on the GPU (Build() again)");
-      return false;
-    }
-    if (device_prim_kind_ != 0) {
+    if (geom_.kind >= 1 && geom_.kind <= 3) return NoGpuRefit(geom_.kind);
+    if (geom_.kind != 0) {
       backend_error_ = "Refit: no triangle tree (Build() with TriangleMesh/TriangleSAHPred first)";
       return false;
     }
-    if (tri_vertices1_) {  // (the library refuses too: nrtRefit on a context that holds a motion keyframe)
+    if (geom_.vertices1) {  // (the library refuses too: nrtRefit on a context that holds a motion keyframe)
       backend_error_ = "Refit: this accel was built over a MotionTriangleMesh: its boxes hold both keyframes (Build() again)";
       return false;
     }
-    if (mesh.GetFaces() != tri_faces_ &&
-        (!mesh.GetFaces() || !tri_faces_ || std::memcmp(mesh.GetFaces(), tri_faces_, 3 * sizeof(unsigned int) * prim_count_) != 0)) {
+    if (mesh.GetFaces() != geom_.faces &&
+        (!mesh.GetFaces() || !geom_.faces || std::memcmp(mesh.GetFaces(), geom_.faces, 3 * sizeof(unsigned int) * geom_.count) != 0)) {
       backend_error_ = "Refit: the mesh's faces differ from the ones the tree was built over";
       return false;
     }
     if (!RefitContexts(0, [&](nrt_ctx *c) { return Api::Refit(c, mesh.GetVertices(), mesh.GetVertexStrideBytes()); })) return false;
-    tri_vertices_ = mesh.GetVertices();  // (a later detach sends these)
-    tri_stride_ = mesh.GetVertexStrideBytes();
+    geom_.vertices = mesh.GetVertices();  // (a later detach sends these)
+    geom_.stride = mesh.GetVertexStrideBytes();
     return RefitDone();
   }
-  bool Refit(const SphereGeometry &) {
-    backend_error_ = "Refit: sphere trees do not refit on the GPU (Build() again)";
-    return false;
-  }
-  bool Refit(const CylinderGeometry &) {
-    backend_error_ = "Refit: cylinder trees do not refit on the GPU (Build() again)";
-    return false;
-  }
-  bool Refit(const BezierCurveGeometry &) {
-    backend_error_ = "Refit: curve trees do not refit on the GPU (Build() again)";
-    return false;
-  }
+  bool Refit(const SphereGeometry &) { return NoGpuRefit(1); }
+  bool Refit(const CylinderGeometry &) { return NoGpuRefit(2); }
+  bool Refit(const BezierCurveGeometry &) { return NoGpuRefit(3); }
   // The GPU refit of a sphere or curve accel (nrtRefitPrims, include/nanort_hip.h) from the geometry's arrays, as Refit(TriangleMesh)
   // for a mesh: every context this object holds, after a copy-on-write detach when they are shared with copies; the new arrays
   // are kept as Build() keeps its own (they must outlive the accel).  The geometry carries no count: `num_primitives`, when
   // given, must be the count of the Build().  False with a reason (LastBackendError()) when the object holds another kind or count.
   bool RefitGeometry(const SphereGeometry &geom, unsigned int num_primitives = ~0u) {
-    std::lock_guard<std::mutex> lock(batch_mutex_);
-    const float *centers = geom.GetCenters(), *radii = geom.GetRadii();
-    if (!HoldsKind("RefitGeometry(SphereGeometry)", 1, num_primitives) ||
-        !RefitContexts(1, [&](nrt_ctx *c) { return nrtRefitPrims_f32(c, centers, radii, prim_count_); }))
-      return false;
-    sph_centers_ = centers;  // (a later detach sends these)
-    sph_radii_ = radii;
-    return RefitDone();
+    return RefitPrims("RefitGeometry(SphereGeometry)", 1, geom.GetCenters(), geom.GetRadii(), num_primitives);
   }
   bool RefitGeometry(const BezierCurveGeometry &geom, unsigned int num_primitives = ~0u) {
-    std::lock_guard<std::mutex> lock(batch_mutex_);
-    const float *cps = geom.GetControlPoints(), *radii = geom.GetRadii();
-    if (!HoldsKind("RefitGeometry(BezierCurveGeometry)", 3, num_primitives) ||
-        !RefitContexts(3, [&](nrt_ctx *c) { return nrtRefitPrims_f32(c, cps, radii, prim_count_); }))
-      return false;
-    crv_cps_ = cps;
-    crv_radii_ = radii;
-    return RefitDone();
+    return RefitPrims("RefitGeometry(BezierCurveGeometry)", 3, geom.GetControlPoints(), geom.GetRadii(), num_primitives);
   }
 #endif
 
@@ -1627,7 +1488,7 @@ class BVHAccel {
     indices_.resize(ni);
     if (ni && fread(&indices_[0], sizeof(unsigned int), ni, fp) != ni) return false;
 #ifdef NANORT_USE_HIP_BACKEND
-    device_tree_stale_ = true;  // re-uploaded lazily by TraverseBatch once a mesh is known
+    dev_.tree_stale = true;  // re-uploaded lazily by TraverseBatch once a mesh is known
 #endif
     return true;
   }
@@ -1874,17 +1735,10 @@ class BVHAccel {
   bool TraverseBatchDevice(const Ray<T> *d_rays, size_t num_rays, TriangleIntersection<T> *d_isects, unsigned char *d_hit,
                            void *hip_stream, const BVHTraceOptions &options = BVHTraceOptions(), const unsigned int *d_skip_prim_ids = NULL) const {
     std::lock_guard<std::mutex> lock(batch_mutex_);
-    if (!ctx_ || device_tree_stale_ || device_prim_kind_ != 0) {
-      backend_error_ = "TraverseBatchDevice: no triangle tree on the GPU (Build() with the built-in triangle types, or TraverseBatch() once after Load())";
-      return false;
-    }
-    nrt_trace_options o;
-    std::memcpy(&o, &options, sizeof(o));
-    if (DeviceLaunch(ctx_.get(), d_rays, num_rays, &o, d_isects, d_hit, hip_stream, d_skip_prim_ids) != NRT_OK) {
-      backend_error_ = nrtLastError(ctx_.get());
-      return false;
-    }
-    return true;
+    if (!TriangleTreeOnDevice("TraverseBatchDevice: no triangle tree on the GPU (Build() with the built-in triangle types, or TraverseBatch() once after Load())")) return false;
+    const nrt_trace_options o = TraceOptions(options);
+    return Ok(d_skip_prim_ids ? Api::TraverseSkipDevice(Context(), Pod(d_rays), num_rays, &o, d_skip_prim_ids, Pod(d_isects), d_hit, hip_stream)
+                              : Api::TraverseDevice(Context(), Pod(d_rays), num_rays, &o, Pod(d_isects), d_hit, hip_stream));
   }
   // Several independent device-resident waves in ONE launch (nrtTraverseBatchesDevice): `occlusion[k]` != 0 makes wave k an
   // occlusion query (only d_hit[k] is written, d_isects[k] may be NULL).  One launch tail for all the waves — a renderer's
@@ -1892,34 +1746,24 @@ class BVHAccel {
   bool TraverseBatchesDevice(size_t num_waves, const Ray<T> *const *d_rays, const size_t *num_rays, TriangleIntersection<T> *const *d_isects,
                              unsigned char *const *d_hit, const unsigned char *occlusion, void *hip_stream,
                              const BVHTraceOptions &options = BVHTraceOptions(), const unsigned int *const *d_skip_prim_ids = NULL) const {
-    typedef detail::HipApi<T> Api;
     std::lock_guard<std::mutex> lock(batch_mutex_);
-    if (!ctx_ || device_tree_stale_ || device_prim_kind_ != 0) {
-      backend_error_ = "TraverseBatchesDevice: no triangle tree on the GPU";
-      return false;
-    }
-    nrt_trace_options o;
-    std::memcpy(&o, &options, sizeof(o));
-    std::vector<const typename Api::RayPod *> r(num_waves);
-    std::vector<typename Api::HitPod *> h(num_waves);
+    if (!TriangleTreeOnDevice("TraverseBatchesDevice: no triangle tree on the GPU")) return false;
+    const nrt_trace_options o = TraceOptions(options);
+    std::vector<const RayPod *> r(num_waves);
+    std::vector<HitPod *> h(num_waves);
     std::vector<uint8_t *> m(num_waves);
     std::vector<uint64_t> n(num_waves);
     std::vector<uint32_t> fl(num_waves);
     for (size_t k = 0; k < num_waves; k++) {
-      r[k] = reinterpret_cast<const typename Api::RayPod *>(d_rays[k]);
-      h[k] = reinterpret_cast<typename Api::HitPod *>(d_isects ? d_isects[k] : NULL);
+      r[k] = Pod(d_rays[k]);
+      h[k] = Pod(d_isects ? d_isects[k] : NULL);
       m[k] = d_hit ? d_hit[k] : NULL;
       n[k] = num_rays[k];
       fl[k] = (occlusion && occlusion[k]) ? NRT_BATCH_OCCLUSION : 0u;
     }
-    if ((d_skip_prim_ids ? Api::TraverseBatchesSkip(ctx_.get(), static_cast<uint32_t>(num_waves), r.data(), n.data(), &o, d_skip_prim_ids, h.data(),
-                                                    m.data(), fl.data(), hip_stream)
-                         : Api::TraverseBatches(ctx_.get(), static_cast<uint32_t>(num_waves), r.data(), n.data(), &o, h.data(), m.data(), fl.data(),
-                                                hip_stream)) != NRT_OK) {
-      backend_error_ = nrtLastError(ctx_.get());
-      return false;
-    }
-    return true;
+    const uint32_t nw = static_cast<uint32_t>(num_waves);
+    return Ok(d_skip_prim_ids ? Api::TraverseBatchesSkip(Context(), nw, r.data(), n.data(), &o, d_skip_prim_ids, h.data(), m.data(), fl.data(), hip_stream)
+                              : Api::TraverseBatches(Context(), nw, r.data(), n.data(), &o, h.data(), m.data(), fl.data(), hip_stream));
   }
   // Several independent HOST waves in ONE launch (nrtTraverseBatches): what a host-shaded wavefront renderer has ready at the
   // same time — the shadow query of one depth and the path wave of the next — uploaded together, walked by one persistent
@@ -1930,8 +1774,6 @@ class BVHAccel {
   bool TraverseBatches(size_t num_waves, const Ray<T> *const *rays, const size_t *num_rays, TriangleIntersection<T> *const *isects,
                        unsigned char *const *hit_out, const unsigned char *occlusion, const BVHTraceOptions &options = BVHTraceOptions(),
                        const unsigned int *const *skip_prim_ids = NULL) const {
-    typedef detail::HipApi<T> Api;
-    typedef typename Api::HitPod HitPod;
     std::lock_guard<std::mutex> lock(batch_mutex_);
     if (!DeviceTreeReady(0)) return false;  // (context, primitive kind, a tree adopted by Load())
     size_t total = 0;
@@ -1943,7 +1785,7 @@ class BVHAccel {
       backend_error_ = "TraverseBatches: out of host memory for the staging buffers";
       return false;
     }
-    std::vector<const typename Api::RayPod *> r(num_waves);
+    std::vector<const RayPod *> r(num_waves);
     std::vector<HitPod *> h(num_waves);
     std::vector<uint8_t *> m(num_waves);
     std::vector<uint64_t> n(num_waves);
@@ -1955,22 +1797,18 @@ class BVHAccel {
         backend_error_ = "TraverseBatches: an occlusion wave needs its hit_out array";
         return false;
       }
-      r[k] = reinterpret_cast<const typename Api::RayPod *>(rays[k]);
+      r[k] = Pod(rays[k]);
       h[k] = occ ? NULL : tmp + off;
       m[k] = (hit_out && hit_out[k]) ? hit_out[k] : tmask + off;
       n[k] = num_rays[k];
       fl[k] = occ ? NRT_BATCH_OCCLUSION : 0u;
       off += num_rays[k];
     }
-    nrt_trace_options o;
-    std::memcpy(&o, &options, sizeof(o));
-    if ((skip_prim_ids ? Api::TraverseBatchesSkipHost(ctx_.get(), static_cast<uint32_t>(num_waves), r.data(), n.data(), &o, skip_prim_ids, h.data(),
-                                                      m.data(), fl.data())
-                       : Api::TraverseBatchesHost(ctx_.get(), static_cast<uint32_t>(num_waves), r.data(), n.data(), &o, h.data(), m.data(), fl.data())) !=
-        NRT_OK) {
-      backend_error_ = nrtLastError(ctx_.get());
+    const nrt_trace_options o = TraceOptions(options);
+    const uint32_t nw = static_cast<uint32_t>(num_waves);
+    if (!Ok(skip_prim_ids ? Api::TraverseBatchesSkipHost(Context(), nw, r.data(), n.data(), &o, skip_prim_ids, h.data(), m.data(), fl.data())
+                          : Api::TraverseBatchesHost(Context(), nw, r.data(), n.data(), &o, h.data(), m.data(), fl.data())))
       return false;
-    }
     for (size_t k = 0; k < num_waves; k++) {
       if (fl[k] || !isects || !isects[k]) continue;
       const HitPod *src = h[k];
@@ -1985,57 +1823,30 @@ class BVHAccel {
   // TraverseBatch() would report in hit_out[i], but a ray stops at the first primitive it accepts (shadow rays).
   bool OccludedBatch(const Ray<T> *rays, size_t num_rays, unsigned char *occluded_out, const BVHTraceOptions &options = BVHTraceOptions(),
                      const unsigned int *skip_prim_ids = NULL) const {
-    typedef detail::HipApi<T> Api;
     std::lock_guard<std::mutex> lock(batch_mutex_);
-    if (!ctx_ || device_tree_stale_ || device_prim_kind_ != 0) {
-      backend_error_ = "OccludedBatch: no triangle tree on the GPU (Build() with the built-in triangle types, or TraverseBatch() once after Load())";
-      return false;
-    }
-    nrt_trace_options o;
-    std::memcpy(&o, &options, sizeof(o));
-    const typename Api::RayPod *r = reinterpret_cast<const typename Api::RayPod *>(rays);
-    if ((skip_prim_ids ? Api::OccludedSkip(ctx_.get(), r, num_rays, &o, skip_prim_ids, occluded_out) : Api::Occluded(ctx_.get(), r, num_rays, &o, occluded_out)) !=
-        NRT_OK) {
-      backend_error_ = nrtLastError(ctx_.get());
-      return false;
-    }
-    return true;
+    if (!TriangleTreeOnDevice("OccludedBatch: no triangle tree on the GPU (Build() with the built-in triangle types, or TraverseBatch() once after Load())")) return false;
+    const nrt_trace_options o = TraceOptions(options);
+    return Ok(skip_prim_ids ? Api::OccludedSkip(Context(), Pod(rays), num_rays, &o, skip_prim_ids, occluded_out)
+                            : Api::Occluded(Context(), Pod(rays), num_rays, &o, occluded_out));
   }
   // ... and with device pointers, asynchronous on `hip_stream` (see TraverseBatchDevice).
   bool OccludedBatchDevice(const Ray<T> *d_rays, size_t num_rays, unsigned char *d_occluded, void *hip_stream,
                            const BVHTraceOptions &options = BVHTraceOptions(), const unsigned int *d_skip_prim_ids = NULL) const {
-    typedef detail::HipApi<T> Api;
     std::lock_guard<std::mutex> lock(batch_mutex_);
-    if (!ctx_ || device_tree_stale_ || device_prim_kind_ != 0) {
-      backend_error_ = "OccludedBatchDevice: no triangle tree on the GPU";
-      return false;
-    }
-    nrt_trace_options o;
-    std::memcpy(&o, &options, sizeof(o));
-    const typename Api::RayPod *r = reinterpret_cast<const typename Api::RayPod *>(d_rays);
-    if ((d_skip_prim_ids ? Api::OccludedSkipDevice(ctx_.get(), r, num_rays, &o, d_skip_prim_ids, d_occluded, hip_stream)
-                         : Api::OccludedDevice(ctx_.get(), r, num_rays, &o, d_occluded, hip_stream)) != NRT_OK) {
-      backend_error_ = nrtLastError(ctx_.get());
-      return false;
-    }
-    return true;
+    if (!TriangleTreeOnDevice("OccludedBatchDevice: no triangle tree on the GPU")) return false;
+    const nrt_trace_options o = TraceOptions(options);
+    return Ok(d_skip_prim_ids ? Api::OccludedSkipDevice(Context(), Pod(d_rays), num_rays, &o, d_skip_prim_ids, d_occluded, hip_stream)
+                              : Api::OccludedDevice(Context(), Pod(d_rays), num_rays, &o, d_occluded, hip_stream));
   }
   // The max_hits frontmost hits of each of `num_rays` rays in one GPU launch (nrtMultiHitTraverseBatch: the contract of
   // MultiHitTraverse above, on a GPU-built or adopted triangle tree).  isects[i * max_hits + j] holds ray i's hits in ascending
   // (t, prim_id) order, then miss records {0, 0, ray.max_t, 0xFFFFFFFF}; counts_out[i] (may be NULL) how many it holds.
   bool MultiHitTraverseBatch(const Ray<T> *rays, size_t num_rays, unsigned int max_hits, TriangleIntersection<T> *isects,
                              unsigned int *counts_out = NULL, const BVHTraceOptions &options = BVHTraceOptions()) const {
-    typedef detail::HipApi<T> Api;
     std::lock_guard<std::mutex> lock(batch_mutex_);
     if (!DeviceTreeReady(0)) return false;  // (context, primitive kind, a tree adopted by Load())
-    nrt_trace_options o;
-    std::memcpy(&o, &options, sizeof(o));
-    if (Api::MultiHit(ctx_.get(), reinterpret_cast<const typename Api::RayPod *>(rays), num_rays, max_hits, &o,
-                      reinterpret_cast<typename Api::HitPod *>(isects), counts_out) != NRT_OK) {
-      backend_error_ = nrtLastError(ctx_.get());
-      return false;
-    }
-    return true;
+    const nrt_trace_options o = TraceOptions(options);
+    return Ok(Api::MultiHit(Context(), Pod(rays), num_rays, max_hits, &o, Pod(isects), counts_out));
   }
   // Motion blur (include/nanort_hip.h, "motion blur"): the closest hit of each of `num_rays` rays at its own time, over a tree built
   // by Build() with MotionTriangleMesh / MotionTriangleSAHPred.  times[i] is ray i's time (clamped to [0, 1]; NULL: every ray at
@@ -2043,31 +1854,18 @@ class BVHAccel {
   // with a MotionTriangleIntersector set to that time gives over the same tree; hit_out[i] (optional) receives 1 / 0.
   bool TraverseBatchMotion(const Ray<T> *rays, const T *times, size_t num_rays, TriangleIntersection<T> *isects, unsigned char *hit_out = NULL,
                            const BVHTraceOptions &options = BVHTraceOptions()) const {
-    typedef detail::HipApi<T> Api;
     std::lock_guard<std::mutex> lock(batch_mutex_);
     if (!MotionTreeReady("TraverseBatchMotion")) return false;
-    nrt_trace_options o;
-    std::memcpy(&o, &options, sizeof(o));
-    if (Api::TraverseMotion(ctx_.get(), reinterpret_cast<const typename Api::RayPod *>(rays), times, num_rays, &o,
-                            reinterpret_cast<typename Api::HitPod *>(isects), hit_out) != NRT_OK) {
-      backend_error_ = nrtLastError(ctx_.get());
-      return false;
-    }
-    return true;
+    const nrt_trace_options o = TraceOptions(options);
+    return Ok(Api::TraverseMotion(Context(), Pod(rays), times, num_rays, &o, Pod(isects), hit_out));
   }
   // ... and its occlusion query: occluded_out[i] is exactly the hit_out[i] of TraverseBatchMotion().
   bool OccludedBatchMotion(const Ray<T> *rays, const T *times, size_t num_rays, unsigned char *occluded_out,
                            const BVHTraceOptions &options = BVHTraceOptions()) const {
-    typedef detail::HipApi<T> Api;
     std::lock_guard<std::mutex> lock(batch_mutex_);
     if (!MotionTreeReady("OccludedBatchMotion")) return false;
-    nrt_trace_options o;
-    std::memcpy(&o, &options, sizeof(o));
-    if (Api::OccludedMotion(ctx_.get(), reinterpret_cast<const typename Api::RayPod *>(rays), times, num_rays, &o, occluded_out) != NRT_OK) {
-      backend_error_ = nrtLastError(ctx_.get());
-      return false;
-    }
-    return true;
+    const nrt_trace_options o = TraceOptions(options);
+    return Ok(Api::OccludedMotion(Context(), Pod(rays), times, num_rays, &o, occluded_out));
   }
   // Visibility masks (include/nanort_hip.h, "visibility masks"): one word per primitive of the triangle mesh the accel was built
   // over (`count` must be its primitive count; NULL removes the masks).  The array is copied to the GPU now and kept by pointer, as
@@ -2076,16 +1874,16 @@ class BVHAccel {
   // own, so the copies keep their visibility.  Build() over a new mesh drops the masks.
   bool SetPrimMasks(const unsigned int *prim_masks, size_t count) {
     std::lock_guard<std::mutex> lock(batch_mutex_);
-    if (!ctx_ || device_prim_kind_ != 0) {
+    if (!dev_.ctx || geom_.kind != 0) {
       backend_error_ = "SetPrimMasks: no triangle mesh on the GPU (Build() with the built-in triangle types first)";
       return false;
     }
-    if (prim_masks && count != prim_count_) {
+    if (prim_masks && count != geom_.count) {
       backend_error_ = "SetPrimMasks: count differs from the number of primitives the tree was built over";
       return false;
     }
     if (!RefitContexts(0, [&](nrt_ctx *c) { return nrtSetPrimMasks(c, prim_masks, count); })) return false;
-    tri_masks_ = prim_masks;
+    geom_.masks = prim_masks;
     return true;
   }
   // The closest hit of each of `num_rays` rays among the triangles it sees: ray i sees primitive p iff (prim_masks[p] & ray_masks[i])
@@ -2094,49 +1892,26 @@ class BVHAccel {
   // (optional) receives 1 / 0.
   bool TraverseBatchMasked(const Ray<T> *rays, const unsigned int *ray_masks, size_t num_rays, TriangleIntersection<T> *isects,
                            unsigned char *hit_out = NULL, const BVHTraceOptions &options = BVHTraceOptions()) const {
-    typedef detail::HipApi<T> Api;
     std::lock_guard<std::mutex> lock(batch_mutex_);
     if (!MaskedTreeReady("TraverseBatchMasked")) return false;
-    nrt_trace_options o;
-    std::memcpy(&o, &options, sizeof(o));
-    if (Api::TraverseMasked(ctx_.get(), reinterpret_cast<const typename Api::RayPod *>(rays), ray_masks, num_rays, &o,
-                            reinterpret_cast<typename Api::HitPod *>(isects), hit_out) != NRT_OK) {
-      backend_error_ = nrtLastError(ctx_.get());
-      return false;
-    }
-    return true;
+    const nrt_trace_options o = TraceOptions(options);
+    return Ok(Api::TraverseMasked(Context(), Pod(rays), ray_masks, num_rays, &o, Pod(isects), hit_out));
   }
   // ... and its occlusion query: occluded_out[i] is exactly the hit_out[i] of TraverseBatchMasked().
   bool OccludedBatchMasked(const Ray<T> *rays, const unsigned int *ray_masks, size_t num_rays, unsigned char *occluded_out,
                            const BVHTraceOptions &options = BVHTraceOptions()) const {
-    typedef detail::HipApi<T> Api;
     std::lock_guard<std::mutex> lock(batch_mutex_);
     if (!MaskedTreeReady("OccludedBatchMasked")) return false;
-    nrt_trace_options o;
-    std::memcpy(&o, &options, sizeof(o));
-    if (Api::OccludedMasked(ctx_.get(), reinterpret_cast<const typename Api::RayPod *>(rays), ray_masks, num_rays, &o, occluded_out) != NRT_OK) {
-      backend_error_ = nrtLastError(ctx_.get());
-      return false;
-    }
-    return true;
+    const nrt_trace_options o = TraceOptions(options);
+    return Ok(Api::OccludedMasked(Context(), Pod(rays), ray_masks, num_rays, &o, occluded_out));
   }
   // ... and with device pointers, asynchronous on `hip_stream` (see TraverseBatchDevice).
   bool MultiHitTraverseBatchDevice(const Ray<T> *d_rays, size_t num_rays, unsigned int max_hits, TriangleIntersection<T> *d_isects,
                                    unsigned int *d_counts, void *hip_stream, const BVHTraceOptions &options = BVHTraceOptions()) const {
-    typedef detail::HipApi<T> Api;
     std::lock_guard<std::mutex> lock(batch_mutex_);
-    if (!ctx_ || device_tree_stale_ || device_prim_kind_ != 0) {
-      backend_error_ = "MultiHitTraverseBatchDevice: no triangle tree on the GPU (Build() with the built-in triangle types, or TraverseBatch() once after Load())";
-      return false;
-    }
-    nrt_trace_options o;
-    std::memcpy(&o, &options, sizeof(o));
-    if (Api::MultiHitDevice(ctx_.get(), reinterpret_cast<const typename Api::RayPod *>(d_rays), num_rays, max_hits, &o,
-                            reinterpret_cast<typename Api::HitPod *>(d_isects), d_counts, hip_stream) != NRT_OK) {
-      backend_error_ = nrtLastError(ctx_.get());
-      return false;
-    }
-    return true;
+    if (!TriangleTreeOnDevice("MultiHitTraverseBatchDevice: no triangle tree on the GPU (Build() with the built-in triangle types, or TraverseBatch() once after Load())")) return false;
+    const nrt_trace_options o = TraceOptions(options);
+    return Ok(Api::MultiHitDevice(Context(), Pod(d_rays), num_rays, max_hits, &o, Pod(d_isects), d_counts, hip_stream));
   }
   // Same for a tree built over the built-in sphere primitive (SphereGeometry + SpherePred).
   bool TraverseBatch(const Ray<T> *rays, size_t num_rays, SphereIntersection *isects, unsigned char *hit_out = NULL,
@@ -2151,22 +1926,8 @@ class BVHAccel {
     static_assert(detail::same_type<T, float>::value, "the cylinder primitive is fp32");
     static_assert(sizeof(CylinderIntersection) == sizeof(nrt_cyl_hit_f32), "CylinderIntersection layout");
     std::lock_guard<std::mutex> lock(batch_mutex_);
-    if (!CylinderTreeReady("TraverseBatch(CylinderIntersection*)", test_cap)) return false;
-    if (num_rays == 0) return true;
-    std::vector<CylinderIntersection> tmp(num_rays);
-    std::vector<unsigned char> mask(num_rays);
-    nrt_trace_options o;
-    std::memcpy(&o, &options, sizeof(o));
-    if (nrtTraverseBatchCylinders_f32(ctx_.get(), reinterpret_cast<const nrt_ray_f32 *>(rays), num_rays, &o,
-                                      reinterpret_cast<nrt_cyl_hit_f32 *>(&tmp[0]), &mask[0]) != NRT_OK) {
-      backend_error_ = nrtLastError(ctx_.get());
-      return false;
-    }
-    for (size_t i = 0; i < num_rays; i++) {
-      if (mask[i]) isects[i] = tmp[i];
-      if (hit_out) hit_out[i] = mask[i];
-    }
-    return true;
+    return CylinderTreeReady("TraverseBatch(CylinderIntersection*)", test_cap) &&
+           StagedTrace<nrt_cyl_hit_f32>(rays, num_rays, isects, hit_out, options, nrtTraverseBatchCylinders_f32);
   }
   // Same for a tree built over the built-in curve primitive (BezierCurveGeometry + BezierCurvePred); `num_subdivisions` is the
   // BezierCurveIntersector constructor argument (1..64).
@@ -2175,22 +1936,8 @@ class BVHAccel {
     static_assert(detail::same_type<T, float>::value, "the curve primitive is fp32");
     static_assert(sizeof(BezierCurveIntersection) == sizeof(nrt_curve_hit_f32), "BezierCurveIntersection layout");
     std::lock_guard<std::mutex> lock(batch_mutex_);
-    if (!CurveTreeReady("TraverseBatch(BezierCurveIntersection*)", num_subdivisions)) return false;
-    if (num_rays == 0) return true;
-    std::vector<BezierCurveIntersection> tmp(num_rays);
-    std::vector<unsigned char> mask(num_rays);
-    nrt_trace_options o;
-    std::memcpy(&o, &options, sizeof(o));
-    if (nrtTraverseBatchCurves_f32(ctx_.get(), reinterpret_cast<const nrt_ray_f32 *>(rays), num_rays, &o,
-                                   reinterpret_cast<nrt_curve_hit_f32 *>(&tmp[0]), &mask[0]) != NRT_OK) {
-      backend_error_ = nrtLastError(ctx_.get());
-      return false;
-    }
-    for (size_t i = 0; i < num_rays; i++) {
-      if (mask[i]) isects[i] = tmp[i];
-      if (hit_out) hit_out[i] = mask[i];
-    }
-    return true;
+    return CurveTreeReady("TraverseBatch(BezierCurveIntersection*)", num_subdivisions) &&
+           StagedTrace<nrt_curve_hit_f32>(rays, num_rays, isects, hit_out, options, nrtTraverseBatchCurves_f32);
   }
   // Opt-in extension without a reference counterpart: occlusion queries of the sphere, cylinder and curve accels
   // (nrtOccludedBatchPrims_f32).  occluded_out[i] is 1 / 0: exactly the flag of the host OccludedBatch(rays, n, intersector, out)
@@ -2235,22 +1982,51 @@ class BVHAccel {
   }
   const std::string &LastBackendError() const { return backend_error_; }
   // The C-ABI context behind this accel (NULL before a GPU Build()): what nrtSceneAddNode_f32 takes (include/nanosg_hip.h).
-  nrt_ctx *HipContext() const { return device_tree_stale_ ? NULL : ctx_.get(); }
+  nrt_ctx *HipContext() const { return dev_.tree_stale ? NULL : dev_.ctx.get(); }
   // Multi-GPU (environment variable NANORT_HIP_DEVICES = "all" or a list such as "0,1,2,3"; read by Build()): Build() makes a
   // replica of the tree on every listed device (the build is deterministic: the replicas are bit-identical) and
   // TraverseBatch() splits a host batch over them in interleaved rows of this many rays (default 4096; a renderer passes its
   // image width).  Records are the single-device ones.
-  size_t NumHipDevices() const { return ctx_ ? 1 + peers_.size() : 0; }
-  void SetTraverseBatchRowLength(size_t rays_per_row) { batch_row_len_ = rays_per_row; }
+  size_t NumHipDevices() const { return dev_.ctx ? 1 + dev_.peers.size() : 0; }
+  void SetTraverseBatchRowLength(size_t rays_per_row) { dev_.batch_row_len = rays_per_row; }
 
  private:
-  static nrt_status DeviceLaunch(nrt_ctx *c, const Ray<T> *r, size_t n, const nrt_trace_options *o, TriangleIntersection<T> *h,
-                                 unsigned char *m, void *stream, const unsigned int *ids = NULL) {
-    typedef detail::HipApi<T> Api;
-    if (ids) return Api::TraverseSkipDevice(c, reinterpret_cast<const typename Api::RayPod *>(r), n, o, ids, reinterpret_cast<typename Api::HitPod *>(h), m, stream);
-    return Api::TraverseDevice(c, reinterpret_cast<const typename Api::RayPod *>(r), n, o, reinterpret_cast<typename Api::HitPod *>(h), m, stream);
+  typedef detail::HipApi<T> Api;
+  typedef typename Api::RayPod RayPod;
+  typedef typename Api::HitPod HitPod;
+  static const RayPod *Pod(const Ray<T> *r) { return reinterpret_cast<const RayPod *>(r); }
+  static HitPod *Pod(TriangleIntersection<T> *h) { return reinterpret_cast<HitPod *>(h); }
+  // Context 0 is the primary, 1 .. NumHipDevices() - 1 the replicas on the other devices of NANORT_HIP_DEVICES.
+  nrt_ctx *Context(size_t k = 0) const { return k == 0 ? dev_.ctx.get() : dev_.peers[k - 1].get(); }
+  // The call path of every C-ABI call: its status becomes the method's result, with the reason of the context it came from
+  // (default: the primary) in LastBackendError(); the options cross as the C struct of the same layout.
+  bool Ok(nrt_status st, nrt_ctx *c) const {
+    if (st == NRT_OK) return true;
+    backend_error_ = nrtLastError(c);
+    return false;
   }
-  // What a GPU refit does around the call that is its own (caller holds batch_mutex_; `kind` is the object's device_prim_kind_):
+  bool Ok(nrt_status st) const { return Ok(st, Context()); }
+  static nrt_trace_options TraceOptions(const BVHTraceOptions &options) {
+    static_assert(sizeof(BVHTraceOptions) == sizeof(nrt_trace_options), "BVHTraceOptions layout");
+    nrt_trace_options o;
+    std::memcpy(&o, &options, sizeof(o));
+    return o;
+  }
+  // The check of the Device forms and of OccludedBatch (caller holds batch_mutex_), which upload nothing: a triangle tree that is
+  // on the GPU now, or `refusal`.
+  bool TriangleTreeOnDevice(const char *refusal) const {
+    if (dev_.ctx && !dev_.tree_stale && geom_.kind == 0) return true;
+    backend_error_ = refusal;
+    return false;
+  }
+  // Refit() of the kinds it does not refit on the GPU (1 spheres, 2 cylinders, 3 curves).
+  bool NoGpuRefit(int kind) {
+    backend_error_ = kind == 1 ? "Refit: sphere trees do not refit on the GPU (Build() again)"
+                               : (kind == 2 ? "Refit: cylinder trees do not refit on the GPU (Build() again)"
+                                            : "Refit: curve trees do not refit on the GPU (Build() again)");
+    return false;
+  }
+  // What a GPU refit does around the call that is its own (caller holds batch_mutex_; `kind` is the object's geom_.kind):
   // an object that shares its contexts with copies first moves to contexts of its own, a Load()ed tree is uploaded, then
   // `refit_ctx` runs on the primary and on every replica.
   template <class RefitCtx>
@@ -2261,22 +2037,18 @@ class BVHAccel {
         backend_error_ = "Refit: empty tree";
         return false;
       }
-      if (!DetachDeviceContext(cyl_test_cap_)) return false;
+      if (!DetachDeviceContext(geom_.cyl_test_cap)) return false;
     }
     if (!DeviceTreeReady(kind)) return false;  // (a Load()ed tree is uploaded first)
     // The primary first: its refusal leaves everything as it was (a device error drops its tree: Build() again).  The
     // replicas pass the same checks, so only a device error can stop one: the object then traces on the primary alone, as
     // after a replica's failed build, and never on a replica that still holds the old boxes.
-    if (refit_ctx(ctx_.get()) != NRT_OK) {
-      backend_error_ = nrtLastError(ctx_.get());
-      return false;
-    }
-    for (size_t k = 0; k < peers_.size(); k++) {
-      if (refit_ctx(peers_[k].get()) != NRT_OK) {
-        backend_error_ = nrtLastError(peers_[k].get());
-        fprintf(stderr, "[nanort] HIP refit of replica %zu failed (%s): tracing on one device\n", k + 1, backend_error_.c_str());
-        peers_.clear();
-        devices_.resize(1);
+    if (!Ok(refit_ctx(Context()))) return false;
+    for (size_t k = 1; k < NumHipDevices(); k++) {
+      if (!Ok(refit_ctx(Context(k)), Context(k))) {
+        fprintf(stderr, "[nanort] HIP refit of replica %zu failed (%s): tracing on one device\n", k, backend_error_.c_str());
+        dev_.peers.clear();
+        dev_.devices.resize(1);
         break;
       }
     }
@@ -2285,30 +2057,32 @@ class BVHAccel {
   // ... and behind it: the root's box, and the host copy of the tree is read back on the next host access.
   bool RefitDone() {
     uint64_t nn = 0, ni = 0;
-    if (nrtTreeSize(ctx_.get(), &nn, &ni) != NRT_OK || detail::HipApi<T>::TreeBounds(ctx_.get(), root_bmin_, root_bmax_) != NRT_OK) {
-      backend_error_ = nrtLastError(ctx_.get());
-      return false;
-    }
-    pending_nodes_ = nn;
-    pending_indices_ = ni;
+    if (!Ok(nrtTreeSize(Context(), &nn, &ni)) || !Ok(Api::TreeBounds(Context(), dev_.root_bmin, dev_.root_bmax))) return false;
+    dev_.pending_nodes = nn;
+    dev_.pending_indices = ni;
     __atomic_store_n(&host_tree_pending_, true, __ATOMIC_RELEASE);  // GetNodes(), Traverse(), Dump() and copies read the refit boxes
     return true;
   }
-  // RefitGeometry: the object was built on the GPU over `kind` (1 spheres, 3 curves) and, when a count is given, over that many.
-  bool HoldsKind(const char *who, int kind, unsigned int num_primitives) {
-    if (!ctx_ || device_prim_kind_ != kind) {
+  // RefitGeometry: the object was built on the GPU over `kind` (1 spheres, 3 curves) and, when a count is given, over that many;
+  // then the refit of every context, and the new arrays are the ones a later detach sends.
+  bool RefitPrims(const char *who, int kind, const float *positions, const float *radii, unsigned int num_primitives) {
+    std::lock_guard<std::mutex> lock(batch_mutex_);
+    if (!dev_.ctx || geom_.kind != kind) {
       backend_error_ = std::string(who) + (kind == 1 ? ": this accel was not built on the GPU over a SphereGeometry" : ": this accel was not built on the GPU over a BezierCurveGeometry");
       return false;
     }
-    if (num_primitives != ~0u && num_primitives != prim_count_) {
+    if (num_primitives != ~0u && num_primitives != geom_.count) {
       backend_error_ = std::string(who) + ": the tree was built over another number of primitives";
       return false;
     }
-    return true;
+    if (!RefitContexts(kind, [&](nrt_ctx *c) { return nrtRefitPrims_f32(c, positions, radii, geom_.count); })) return false;
+    geom_.positions = positions;
+    geom_.radii = radii;
+    return RefitDone();
   }
   // The checks of the motion queries (caller holds batch_mutex_): a triangle accel built over a MotionTriangleMesh.
   bool MotionTreeReady(const char *who) const {
-    if (!ctx_ || device_prim_kind_ != 0 || !tri_vertices1_) {
+    if (!dev_.ctx || geom_.kind != 0 || !geom_.vertices1) {
       backend_error_ = std::string(who) + ": Build() with MotionTriangleMesh/MotionTriangleSAHPred first";
       return false;
     }
@@ -2316,7 +2090,7 @@ class BVHAccel {
   }
   // The checks of the masked queries (caller holds batch_mutex_): a triangle accel that holds masks.
   bool MaskedTreeReady(const char *who) const {
-    if (!ctx_ || device_prim_kind_ != 0 || !tri_masks_) {
+    if (!dev_.ctx || geom_.kind != 0 || !geom_.masks) {
       backend_error_ = std::string(who) + ": SetPrimMasks() on an accel built over a TriangleMesh first";
       return false;
     }
@@ -2326,114 +2100,91 @@ class BVHAccel {
   // for (0 triangles, 1 spheres), and a tree adopted by Load() uploaded — after a copy-on-write detach when the contexts are
   // shared with copies.
   bool DeviceTreeReady(int want_kind) const {
-    typedef detail::HipApi<T> Api;
-    if (!ctx_) {
+    if (!dev_.ctx) {
       backend_error_ = "TraverseBatch: no GPU context (Build() with TriangleMesh/TriangleSAHPred first)";
       return false;
     }
-    if (device_prim_kind_ != want_kind) {  // records of one primitive kind must not be read as another's
+    if (geom_.kind != want_kind) {  // records of one primitive kind must not be read as another's
       backend_error_ = want_kind == 0 ? "TraverseBatch(TriangleIntersection*): this accel was not built over a TriangleMesh"
                                       : "TraverseBatch(SphereIntersection*): this accel was not built over a SphereGeometry";
       return false;
     }
-    if (device_tree_stale_) {
+    if (dev_.tree_stale) {
       EnsureHostTree();  // (Load() already dropped any pending read-back: a no-op, kept so the upload never sees a half state)
       if (nodes_.empty()) {
         backend_error_ = "TraverseBatch: empty tree";
         return false;
       }
-      if (SharesDeviceContext() && !DetachDeviceContext(cyl_test_cap_)) return false;  // copy-on-write
-      for (size_t k = 0; k <= peers_.size(); k++) {  // (the replicas on the other devices adopt the same arrays)
-        nrt_ctx *c = k == 0 ? ctx_.get() : peers_[k - 1].get();
-        if (Api::SetTree(c, reinterpret_cast<const typename Api::NodePod *>(&nodes_[0]), nodes_.size(), indices_.empty() ? NULL : &indices_[0],
-                         indices_.size()) != NRT_OK) {
-          backend_error_ = nrtLastError(c);
+      if (SharesDeviceContext() && !DetachDeviceContext(geom_.cyl_test_cap)) return false;  // copy-on-write
+      for (size_t k = 0; k < NumHipDevices(); k++)  // (the replicas on the other devices adopt the same arrays)
+        if (!Ok(Api::SetTree(Context(k), reinterpret_cast<const typename Api::NodePod *>(&nodes_[0]), nodes_.size(),
+                             indices_.empty() ? NULL : &indices_[0], indices_.size()),
+                Context(k)))
           return false;
-        }
-      }
-      device_tree_stale_ = false;
+      dev_.tree_stale = false;
     }
     return true;
   }
-  // The same for the cylinder and the curve accels (caller holds batch_mutex_; `who` opens the error text).  The intersector's
-  // constructor argument — test_cap, num_subdivisions — lives with the primitives on the device: when it differs from what was
-  // sent last, or the tree was adopted by Load(), the primitives go again with the new value and the tree behind them.
-  bool CylinderTreeReady(const char *who, bool test_cap) const {
-    if (!ctx_ || !cyl_endpoints_ || device_prim_kind_ != 2) {
-      backend_error_ = std::string(who) + ": Build() with CylinderGeometry/CylinderPred first";
+  // The same for the cylinder (kind 2) and the curve (kind 3) accels (caller holds batch_mutex_; `who` opens the error text).  The
+  // intersector's constructor argument — test_cap, num_subdivisions; the other kind's is passed as it stands — lives with the
+  // primitives on the device: when it differs from what was sent last, or the tree was adopted by Load(), the primitives go again
+  // with the new value and the tree behind them.
+  bool ResentTreeReady(const char *who, int kind, bool test_cap, int num_subdivisions) const {
+    if (!dev_.ctx || !geom_.positions || geom_.kind != kind) {
+      backend_error_ = std::string(who) + (kind == 2 ? ": Build() with CylinderGeometry/CylinderPred first" : ": Build() with BezierCurveGeometry/BezierCurvePred first");
       return false;
     }
-    if (test_cap == cyl_test_cap_ && !device_tree_stale_) return true;
-    // (the host tree first: it may still be pending after Build(), and nrtSetCylinders_f32 frees the device tree)
-    EnsureHostTree();
-    if (nodes_.empty()) {
-      backend_error_ = std::string(who) + ": empty tree";
-      return false;
-    }
-    if (SharesDeviceContext()) {  // copy-on-write: the shared context stays with the copies
-      if (!DetachDeviceContext(test_cap)) return false;  // (sends the cylinders with the new flag)
-    } else if (nrtSetCylinders_f32(ctx_.get(), cyl_endpoints_, cyl_radii_, cyl_count_, test_cap ? 1 : 0) != NRT_OK) {
-      backend_error_ = nrtLastError(ctx_.get());
-      return false;
-    }
-    if (nrtSetTree_f32(ctx_.get(), reinterpret_cast<const nrt_node_f32 *>(&nodes_[0]), nodes_.size(), &indices_[0], indices_.size()) != NRT_OK) {
-      backend_error_ = nrtLastError(ctx_.get());
-      return false;
-    }
-    cyl_test_cap_ = test_cap;
-    device_tree_stale_ = false;
-    return true;
-  }
-  bool CurveTreeReady(const char *who, int num_subdivisions) const {
-    if (!ctx_ || !crv_cps_ || device_prim_kind_ != 3) {
-      backend_error_ = std::string(who) + ": Build() with BezierCurveGeometry/BezierCurvePred first";
-      return false;
-    }
-    if (num_subdivisions < 1 || num_subdivisions > 64) {
+    if (kind == 3 && (num_subdivisions < 1 || num_subdivisions > 64)) {
       backend_error_ = std::string(who) + ": num_subdivisions outside 1..64";
       return false;
     }
-    if (num_subdivisions == crv_subdiv_ && !device_tree_stale_) return true;
-    // (the host tree first: it may still be pending after Build(), and nrtSetCurves_f32 frees the device tree)
+    if (test_cap == geom_.cyl_test_cap && num_subdivisions == geom_.crv_subdiv && !dev_.tree_stale) return true;
+    // (the host tree first: it may still be pending after Build(), and sending the primitives frees the device tree)
     EnsureHostTree();
     if (nodes_.empty()) {
       backend_error_ = std::string(who) + ": empty tree";
       return false;
     }
-    crv_subdiv_ = num_subdivisions;
-    if (SharesDeviceContext()) {  // copy-on-write: the shared context stays with the copies
-      if (!DetachDeviceContext(cyl_test_cap_)) return false;  // (sends the curves with the new count)
-    } else if (nrtSetCurves_f32(ctx_.get(), crv_cps_, crv_radii_, prim_count_, static_cast<uint32_t>(num_subdivisions)) != NRT_OK) {
-      backend_error_ = nrtLastError(ctx_.get());
+    // The subdivision count is stored before the send, which reads it from the record; the cap goes into the send and is stored
+    // only once the tree is up again.  A failed re-send therefore leaves what it always left: the new count, the old cap.
+    geom_.crv_subdiv = num_subdivisions;
+    if (SharesDeviceContext() ? !DetachDeviceContext(test_cap)  // copy-on-write: the shared context stays with the copies
+                              : !Ok(SendPrimitives(Context(), test_cap)))
       return false;
+    if (!Ok(nrtSetTree_f32(Context(), reinterpret_cast<const nrt_node_f32 *>(&nodes_[0]), nodes_.size(), &indices_[0], indices_.size()))) return false;
+    geom_.cyl_test_cap = test_cap;
+    dev_.tree_stale = false;
+    return true;
+  }
+  bool CylinderTreeReady(const char *who, bool test_cap) const { return ResentTreeReady(who, 2, test_cap, geom_.crv_subdiv); }
+  bool CurveTreeReady(const char *who, int num_subdivisions) const { return ResentTreeReady(who, 3, geom_.cyl_test_cap, num_subdivisions); }
+  // The trace of the two kinds whose records are their own (caller holds batch_mutex_, the kind's tree is ready): staged, then
+  // isects[i] is written only on a hit, like Traverse().
+  template <class HitPodK, class Hit, class Trace>
+  bool StagedTrace(const Ray<T> *rays, size_t num_rays, Hit *isects, unsigned char *hit_out, const BVHTraceOptions &options, Trace trace) const {
+    if (num_rays == 0) return true;
+    std::vector<Hit> tmp(num_rays);
+    std::vector<unsigned char> mask(num_rays);
+    const nrt_trace_options o = TraceOptions(options);
+    if (!Ok(trace(Context(), reinterpret_cast<const nrt_ray_f32 *>(rays), num_rays, &o, reinterpret_cast<HitPodK *>(&tmp[0]), &mask[0]))) return false;
+    for (size_t i = 0; i < num_rays; i++) {
+      if (mask[i]) isects[i] = tmp[i];
+      if (hit_out) hit_out[i] = mask[i];
     }
-    if (nrtSetTree_f32(ctx_.get(), reinterpret_cast<const nrt_node_f32 *>(&nodes_[0]), nodes_.size(), &indices_[0], indices_.size()) != NRT_OK) {
-      backend_error_ = nrtLastError(ctx_.get());
-      return false;
-    }
-    device_tree_stale_ = false;
     return true;
   }
   // The launch of OccludedBatch<Kind>[Device] once the kind's tree is ready (caller holds batch_mutex_).
   bool OccludedPrims(const Ray<T> *rays, size_t num_rays, unsigned char *occluded, const BVHTraceOptions &options, bool device, void *hip_stream) const {
-    static_assert(sizeof(BVHTraceOptions) == sizeof(nrt_trace_options), "BVHTraceOptions layout");
-    nrt_trace_options o;
-    std::memcpy(&o, &options, sizeof(o));
+    const nrt_trace_options o = TraceOptions(options);
     const nrt_ray_f32 *r = reinterpret_cast<const nrt_ray_f32 *>(rays);
-    if ((device ? nrtOccludedBatchPrimsDevice_f32(ctx_.get(), r, num_rays, &o, occluded, hip_stream)
-                : nrtOccludedBatchPrims_f32(ctx_.get(), r, num_rays, &o, occluded)) != NRT_OK) {
-      backend_error_ = nrtLastError(ctx_.get());
-      return false;
-    }
-    return true;
+    return Ok(device ? nrtOccludedBatchPrimsDevice_f32(Context(), r, num_rays, &o, occluded, hip_stream)
+                     : nrtOccludedBatchPrims_f32(Context(), r, num_rays, &o, occluded));
   }
   template <class Hit>
   bool TraverseBatchImpl(const Ray<T> *rays, size_t num_rays, Hit *isects, unsigned char *hit_out, const BVHTraceOptions &options,
                          const unsigned int *skip_prim_ids = NULL) const {
-    typedef detail::HipApi<T> Api;
-    static_assert(sizeof(Ray<T>) == sizeof(typename Api::RayPod), "Ray layout");
-    static_assert(sizeof(Hit) == sizeof(typename Api::HitPod), "intersection record layout");
-    static_assert(sizeof(BVHTraceOptions) == sizeof(nrt_trace_options), "BVHTraceOptions layout");
+    static_assert(sizeof(Ray<T>) == sizeof(RayPod), "Ray layout");
+    static_assert(sizeof(Hit) == sizeof(HitPod), "intersection record layout");
     const int want_kind = detail::same_type<Hit, TriangleIntersection<T> >::value ? 0 : 1;
     std::lock_guard<std::mutex> lock(batch_mutex_);  // (staging, launch and scatter: see the comment above TraverseBatch)
     if (!DeviceTreeReady(want_kind)) return false;
@@ -2441,33 +2192,25 @@ class BVHAccel {
     // Grow-only byte staging owned by the accel, page-locked when the backend can provide it (the device-to-host copy
     // then runs at PCIe speed; PODs: no per-element construction, no fresh pages to fault in on every wave); the caller's
     // mask array is used directly when there is one.
-    typedef typename Api::HitPod HitPod;
     HitPod *tmp = static_cast<HitPod *>(StageEnsure(&stage_hits_, &stage_hits_cap_, num_rays * sizeof(HitPod)));
     unsigned char *mask = hit_out ? hit_out : static_cast<unsigned char *>(StageEnsure(&stage_mask_, &stage_mask_cap_, num_rays));
     if (!tmp || !mask) {
       backend_error_ = "TraverseBatch: out of host memory for the staging buffers";
       return false;
     }
-    nrt_trace_options o;
-    std::memcpy(&o, &options, sizeof(o));
+    const nrt_trace_options o = TraceOptions(options);
+    nrt_status st;
     if (skip_prim_ids) {  // (one device: nrtTraverseBatchMulti takes no per-ray ids, and the records are the same)
-      if (Api::TraverseSkip(ctx_.get(), reinterpret_cast<const typename Api::RayPod *>(rays), num_rays, &o, skip_prim_ids, tmp, mask) != NRT_OK) {
-        backend_error_ = nrtLastError(ctx_.get());
-        return false;
-      }
-    } else if (!peers_.empty() && want_kind == 0) {
+      st = Api::TraverseSkip(Context(), Pod(rays), num_rays, &o, skip_prim_ids, tmp, mask);
+    } else if (!dev_.peers.empty() && want_kind == 0) {
       // NANORT_HIP_DEVICES: the batch is split row-interleaved over the replicas, one per device (nrtTraverseBatchMulti)
-      std::vector<nrt_ctx *> cs(1, ctx_.get());
-      for (size_t k = 0; k < peers_.size(); k++) cs.push_back(peers_[k].get());
-      if (Api::TraverseMulti(&cs[0], static_cast<uint32_t>(cs.size()), reinterpret_cast<const typename Api::RayPod *>(rays), num_rays, batch_row_len_,
-                             &o, reinterpret_cast<HitPod *>(tmp), mask) != NRT_OK) {
-        backend_error_ = nrtLastError(ctx_.get());
-        return false;
-      }
-    } else if (Api::Traverse(ctx_.get(), reinterpret_cast<const typename Api::RayPod *>(rays), num_rays, &o, tmp, mask) != NRT_OK) {
-      backend_error_ = nrtLastError(ctx_.get());
-      return false;
+      std::vector<nrt_ctx *> cs;
+      for (size_t k = 0; k < NumHipDevices(); k++) cs.push_back(Context(k));
+      st = Api::TraverseMulti(&cs[0], static_cast<uint32_t>(cs.size()), Pod(rays), num_rays, dev_.batch_row_len, &o, tmp, mask);
+    } else {
+      st = Api::Traverse(Context(), Pod(rays), num_rays, &o, tmp, mask);
     }
+    if (!Ok(st)) return false;
     // isects[i] is written only on a hit, like Traverse().  (At most half of what the process may use, detail::HostThreads():
     // an OpenMP default of "all hardware threads" inside a CPU-quota'd container starves the HIP runtime's own threads —
     // measured 10x slower.)
@@ -2496,8 +2239,8 @@ class BVHAccel {
 #ifdef NANORT_USE_HIP_BACKEND
     if (HostTreePending()) {  // (the root's box came back with the build: no need for the whole array)
       for (int k = 0; k < 3; k++) {
-        bmin[k] = root_bmin_[k];
-        bmax[k] = root_bmax_[k];
+        bmin[k] = dev_.root_bmin[k];
+        bmax[k] = dev_.root_bmax[k];
       }
       return;
     }
@@ -2516,11 +2259,10 @@ class BVHAccel {
     if (!__atomic_load_n(&host_tree_pending_, __ATOMIC_ACQUIRE)) return;
     std::lock_guard<std::mutex> lock(detail::HostTreeMutex());
     if (!host_tree_pending_) return;
-    typedef detail::HipApi<T> Api;
-    nodes_.resize(static_cast<size_t>(pending_nodes_));
-    indices_.resize(static_cast<size_t>(pending_indices_));
-    if (!ctx_ || Api::GetTree(ctx_.get(), reinterpret_cast<typename Api::NodePod *>(&nodes_[0]), indices_.empty() ? NULL : &indices_[0]) != NRT_OK) {
-      backend_error_ = ctx_ ? nrtLastError(ctx_.get()) : "host tree requested without a GPU context";
+    nodes_.resize(static_cast<size_t>(dev_.pending_nodes));
+    indices_.resize(static_cast<size_t>(dev_.pending_indices));
+    if (!dev_.ctx || Api::GetTree(Context(), reinterpret_cast<typename Api::NodePod *>(&nodes_[0]), indices_.empty() ? NULL : &indices_[0]) != NRT_OK) {
+      backend_error_ = dev_.ctx ? nrtLastError(Context()) : "host tree requested without a GPU context";
       fprintf(stderr, "[nanort] reading the tree back from the GPU failed: %s\n", backend_error_.c_str());
       nodes_.clear();
       indices_.clear();
@@ -2896,81 +2638,101 @@ class BVHAccel {
 #ifdef NANORT_USE_HIP_BACKEND
     // user primitives live on the host only: a device context left over from an earlier built-in Build() holds other
     // primitives and must not be traced against this tree
-    ctx_.reset();
-    peers_.clear();
-    devices_.clear();
-    device_tree_stale_ = false;
-    device_prim_kind_ = -1;
+    dev_.ctx.reset();
+    dev_.peers.clear();
+    dev_.devices.clear();
+    dev_.tree_stale = false;
+    geom_.kind = -1;
 #endif
     return true;
   }
 
 #ifdef NANORT_USE_HIP_BACKEND
-  // Built-in primitive types: construction on the GPU through the C ABI.
+  // What the device holds, in two records: a copy copies them, a move takes them and leaves default-constructed ones behind, so
+  // a new piece of per-context state is ONE field here and nothing in CopyFrom() / MoveFrom().
+  // The contexts and what goes with them:
+  struct DeviceState {
+    std::shared_ptr<nrt_ctx> ctx;
+    std::vector<std::shared_ptr<nrt_ctx> > peers;  // replicas on the other devices of NANORT_HIP_DEVICES
+    std::vector<int> devices;                      // the devices of ctx, then of peers
+    size_t batch_row_len = 0;                      // rays per interleaved row of a multi-device TraverseBatch (0: 4096)
+    bool tree_stale = false;                       // the tree is in nodes_ / indices_ (Load(), a detach) and not on the device yet
+    uint64_t pending_nodes = 0, pending_indices = 0;  // the sizes of a tree that is on the device only (host_tree_pending_) ...
+    T root_bmin[3] = {T(0), T(0), T(0)}, root_bmax[3] = {T(0), T(0), T(0)};  // ... and its root's box
+  };
+  // The geometry the contexts were built over: the arrays the last built-in Build() (then Refit(), RefitGeometry(), SetPrimMasks())
+  // was given, by pointer — SendPrimitives() sends a fresh context exactly this.
+  struct DeviceGeometry {
+    int kind = -1;           // 0 triangles, 1 spheres, 2 cylinders, 3 curves, -1 nothing usable
+    unsigned int count = 0;  // primitives
+    const T *vertices = NULL, *vertices1 = NULL;  // triangles: keyframe 0, keyframe 1 of a MotionTriangleMesh (NULL: none) ...
+    size_t stride = 0;                            // ... their stride in bytes ...
+    const unsigned int *faces = NULL, *masks = NULL;  // ... the faces, the visibility masks of the last SetPrimMasks() (NULL: none)
+    const float *positions = NULL, *radii = NULL;  // spheres: centers; cylinders: endpoints; curves: control points
+    bool cyl_test_cap = true;  // the cylinder intersector's flag and the curve intersector's subdivision count the contexts
+    int crv_subdiv = 4;        // hold now (the intersectors' defaults after a Build())
+  };
+  static DeviceGeometry MeshRecord(unsigned int n, const T *vertices, const T *vertices1, size_t stride, const unsigned int *faces) {
+    DeviceGeometry g;  // (no masks: nrtSetMesh drops them, they belong to the mesh)
+    g.count = n;
+    g.vertices = vertices;
+    g.vertices1 = vertices1;
+    g.stride = stride;
+    g.faces = faces;
+    return g;
+  }
+  static DeviceGeometry RadiusRecord(unsigned int n, const float *positions, const float *radii) {
+    DeviceGeometry g;
+    g.count = n;
+    g.positions = positions;
+    g.radii = radii;
+    return g;
+  }
+  // Built-in primitive types: construction on the GPU through the C ABI.  Each overload states what the contexts will hold as a
+  // fresh record (the arrays are kept by pointer: a copy-on-write detach sends them to the new context) and how to send it.
   bool BuildImpl(unsigned int n, const TriangleMesh<T> &mesh, const TriangleSAHPred<T> &pred, const BVHBuildOptions<T> &options,
                  detail::triangle_tag) {
     (void)pred;
-    typedef detail::HipApi<T> Api;
-    tri_vertices_ = mesh.GetVertices();  // (kept: a copy-on-write detach sends them to the new context)
-    tri_stride_ = mesh.GetVertexStrideBytes();
-    tri_faces_ = mesh.GetFaces();
-    tri_vertices1_ = NULL;
-    tri_masks_ = NULL;  // (nrtSetMesh drops the masks: they belong to the mesh)
-    prim_count_ = n;
-    return HipBuild(n, options, 0, [&](nrt_ctx *c) { return Api::SetMesh(c, tri_vertices_, tri_stride_, tri_faces_, n); });
+    const DeviceGeometry g = MeshRecord(n, mesh.GetVertices(), NULL, mesh.GetVertexStrideBytes(), mesh.GetFaces());
+    return HipBuild(options, 0, g, [&](nrt_ctx *c) { return Api::SetMesh(c, g.vertices, g.stride, g.faces, n); });
   }
   // A triangle mesh with a second vertex keyframe: nrtSetMesh + nrtSetMeshMotion + nrtBuild.  The accel stays a triangle accel (the
   // triangle batch methods answer for keyframe 0); TraverseBatchMotion() / OccludedBatchMotion() trace it with one time per ray.
   bool BuildImpl(unsigned int n, const MotionTriangleMesh<T> &mesh, const MotionTriangleSAHPred<T> &pred, const BVHBuildOptions<T> &options,
                  detail::motion_triangle_tag) {
     (void)pred;
-    typedef detail::HipApi<T> Api;
-    tri_vertices_ = mesh.GetVertices();
-    tri_stride_ = mesh.GetVertexStrideBytes();
-    tri_faces_ = mesh.GetFaces();
-    tri_vertices1_ = mesh.GetVertices1();
-    tri_masks_ = NULL;
-    prim_count_ = n;
-    return HipBuild(n, options, 0, [&](nrt_ctx *c) {
-      const nrt_status st = Api::SetMesh(c, tri_vertices_, tri_stride_, tri_faces_, n);
-      return st != NRT_OK ? st : Api::SetMeshMotion(c, tri_vertices1_, tri_stride_);
+    const DeviceGeometry g = MeshRecord(n, mesh.GetVertices(), mesh.GetVertices1(), mesh.GetVertexStrideBytes(), mesh.GetFaces());
+    return HipBuild(options, 0, g, [&](nrt_ctx *c) {
+      const nrt_status st = Api::SetMesh(c, g.vertices, g.stride, g.faces, n);
+      return st != NRT_OK ? st : Api::SetMeshMotion(c, g.vertices1, g.stride);
     });
   }
   bool BuildImpl(unsigned int n, const SphereGeometry &geom, const SpherePred &pred, const BVHBuildOptions<T> &options,
                  detail::sphere_tag) {
     (void)pred;
-    sph_centers_ = geom.GetCenters();
-    sph_radii_ = geom.GetRadii();
-    prim_count_ = n;
-    return HipBuild(n, options, 1, [&](nrt_ctx *c) { return nrtSetSpheres_f32(c, sph_centers_, sph_radii_, n); });
+    const DeviceGeometry g = RadiusRecord(n, geom.GetCenters(), geom.GetRadii());
+    return HipBuild(options, 1, g, [&](nrt_ctx *c) { return nrtSetSpheres_f32(c, g.positions, g.radii, n); });
   }
-
-  // (the intersector's test_cap flag is a traversal-time property: TraverseBatch() re-sends the primitives if it differs)
+  // (the intersector's test_cap flag and num_subdivisions are traversal-time properties: TraverseBatch() re-sends the primitives
+  // when one differs from the record's, which starts at the intersectors' defaults: caps tested, 4 subdivisions)
   bool BuildImpl(unsigned int n, const CylinderGeometry &geom, const CylinderPred &pred, const BVHBuildOptions<T> &options,
                  detail::cylinder_tag) {
     (void)pred;
-    cyl_endpoints_ = geom.GetEndpoints();
-    cyl_radii_ = geom.GetRadii();
-    cyl_count_ = n;
-    cyl_test_cap_ = true;
-    return HipBuild(n, options, 2, [&](nrt_ctx *c) { return nrtSetCylinders_f32(c, geom.GetEndpoints(), geom.GetRadii(), n, 1); });
+    const DeviceGeometry g = RadiusRecord(n, geom.GetEndpoints(), geom.GetRadii());
+    return HipBuild(options, 2, g, [&](nrt_ctx *c) { return nrtSetCylinders_f32(c, g.positions, g.radii, n, g.cyl_test_cap ? 1 : 0); });
   }
-
-  // (the intersector's num_subdivisions is a traversal-time property: TraverseBatch() re-sends the primitives if it differs)
   bool BuildImpl(unsigned int n, const BezierCurveGeometry &geom, const BezierCurvePred &pred, const BVHBuildOptions<T> &options,
                  detail::curve_tag) {
     (void)pred;
-    crv_cps_ = geom.GetControlPoints();
-    crv_radii_ = geom.GetRadii();
-    crv_subdiv_ = 4;
-    prim_count_ = n;
-    return HipBuild(n, options, 3, [&](nrt_ctx *c) { return nrtSetCurves_f32(c, crv_cps_, crv_radii_, n, 4); });
+    const DeviceGeometry g = RadiusRecord(n, geom.GetControlPoints(), geom.GetRadii());
+    return HipBuild(options, 3, g, [&](nrt_ctx *c) { return nrtSetCurves_f32(c, g.positions, g.radii, n, static_cast<uint32_t>(g.crv_subdiv)); });
   }
 
+  // `g` becomes the object's record (its kind only once the tree is built: -1, nothing usable, until then); `set_prims` sends it.
   template <class SetPrims>
-  bool HipBuild(unsigned int n, const BVHBuildOptions<T> &options, int prim_kind, SetPrims set_prims) {
-    device_prim_kind_ = -1;
-    typedef detail::HipApi<T> Api;
+  bool HipBuild(const BVHBuildOptions<T> &options, int prim_kind, const DeviceGeometry &g, SetPrims set_prims) {
+    const unsigned int n = g.count;
+    geom_ = g;
     static_assert(sizeof(BVHNode<T>) == sizeof(typename Api::NodePod), "BVHNode layout");
     static_assert(sizeof(BVHBuildOptions<T>) == sizeof(typename Api::BuildPod), "BVHBuildOptions layout");
     static_assert(sizeof(BVHBuildStatistics) == sizeof(nrt_build_stats), "BVHBuildStatistics layout");
@@ -2982,17 +2744,16 @@ class BVHAccel {
     assert(options_.bin_size > 1);
     if (n == 0) return false;
     if (SharesDeviceContext()) {  // copy-on-write: the copies keep the contexts they share with this object
-      ctx_.reset();
-      peers_.clear();
+      dev_.ctx.reset();
+      dev_.peers.clear();
     }
-    if (!ctx_ && !CreateContexts(DeviceList())) return false;
-    nrt_ctx *c = ctx_.get();
+    if (!dev_.ctx && !CreateContexts(DeviceList())) return false;
+    nrt_ctx *c = Context();
     typename Api::BuildPod o;
     std::memcpy(&o, &options, sizeof(o));
     nrt_build_stats st;
     uint64_t num_nodes = 0;
-    if (set_prims(c) != NRT_OK || Api::Build(c, &o, &st, &num_nodes) != NRT_OK) {
-      backend_error_ = nrtLastError(c);
+    if (!Ok(set_prims(c)) || !Ok(Api::Build(c, &o, &st, &num_nodes))) {
       fprintf(stderr, "[nanort] HIP build failed: %s\n", backend_error_.c_str());
       return false;
     }
@@ -3002,12 +2763,9 @@ class BVHAccel {
     if (nrtTreeSize(c, &tree_nodes, &tree_indices) != NRT_OK) tree_indices = n;
     // The arrays stay on the device until the host asks for them (EnsureHostTree): an application that only calls
     // TraverseBatch() never pays the 27 MB read-back of a 1 M-triangle tree.  The root's box comes back now (24 / 48 bytes).
-    pending_nodes_ = num_nodes;
-    pending_indices_ = tree_indices;
-    if (Api::TreeBounds(c, root_bmin_, root_bmax_) != NRT_OK) {
-      backend_error_ = nrtLastError(c);
-      return false;
-    }
+    dev_.pending_nodes = num_nodes;
+    dev_.pending_indices = tree_indices;
+    if (!Ok(Api::TreeBounds(c, dev_.root_bmin, dev_.root_bmax))) return false;
     __atomic_store_n(&host_tree_pending_, true, __ATOMIC_RELEASE);
     static const bool eager = std::getenv("NANORT_HIP_EAGER_READBACK") != NULL && std::atoi(std::getenv("NANORT_HIP_EAGER_READBACK")) != 0;
     if (eager) {
@@ -3019,19 +2777,19 @@ class BVHAccel {
     stats_.num_branch_nodes = st.num_branch_nodes;
     stats_.build_secs = st.build_secs;
     // replicas on the other devices: the same primitives, the same (deterministic) build
-    for (size_t k = 0; k < peers_.size(); k++) {
+    for (size_t k = 1; k < NumHipDevices(); k++) {
       nrt_build_stats pst;
       uint64_t pn = 0;
-      if (set_prims(peers_[k].get()) != NRT_OK || Api::Build(peers_[k].get(), &o, &pst, &pn) != NRT_OK || pn != num_nodes) {
-        backend_error_ = nrtLastError(peers_[k].get());
-        fprintf(stderr, "[nanort] HIP build of replica %zu failed (%s): tracing on one device\n", k + 1, backend_error_.c_str());
-        peers_.clear();
-        devices_.resize(1);
+      if (set_prims(Context(k)) != NRT_OK || Api::Build(Context(k), &o, &pst, &pn) != NRT_OK || pn != num_nodes) {
+        backend_error_ = nrtLastError(Context(k));
+        fprintf(stderr, "[nanort] HIP build of replica %zu failed (%s): tracing on one device\n", k, backend_error_.c_str());
+        dev_.peers.clear();
+        dev_.devices.resize(1);
         break;
       }
     }
-    device_tree_stale_ = false;
-    device_prim_kind_ = prim_kind;
+    dev_.tree_stale = false;
+    geom_.kind = prim_kind;
     return true;
   }
 
@@ -3057,11 +2815,11 @@ class BVHAccel {
     }
     return devices;
   }
-  // Fresh contexts on `devices` (ctx_ on the first, a replica in peers_ on each other one that opens), replacing the current ones.
+  // Fresh contexts on `devices` (the primary on the first, a replica on each other one that opens), replacing the current ones.
   bool CreateContexts(const std::vector<int> &devices) const {
-    ctx_.reset();
-    peers_.clear();
-    devices_.clear();
+    dev_.ctx.reset();
+    dev_.peers.clear();
+    dev_.devices.clear();
     for (size_t k = 0; k < devices.size(); k++) {
       nrt_ctx *raw = NULL;
       if (nrtCreate(devices[k], &raw) != NRT_OK) {
@@ -3074,47 +2832,43 @@ class BVHAccel {
         break;
       }
       if (k == 0)
-        ctx_ = std::shared_ptr<nrt_ctx>(raw, detail::CtxDeleter());
+        dev_.ctx = std::shared_ptr<nrt_ctx>(raw, detail::CtxDeleter());
       else
-        peers_.push_back(std::shared_ptr<nrt_ctx>(raw, detail::CtxDeleter()));
-      devices_.push_back(devices[k]);
+        dev_.peers.push_back(std::shared_ptr<nrt_ctx>(raw, detail::CtxDeleter()));
+      dev_.devices.push_back(devices[k]);
     }
     return true;
   }
-  // Copies share ctx_ / peers_ until one side changes what they hold (O(1): no device call, no read-back).
+  // Copies share the contexts until one side changes what they hold (O(1): no device call, no read-back).
   bool SharesDeviceContext() const {
-    if (ctx_.use_count() > 1) return true;
-    for (size_t k = 0; k < peers_.size(); k++)
-      if (peers_[k].use_count() > 1) return true;
+    if (dev_.ctx.use_count() > 1) return true;
+    for (size_t k = 0; k < dev_.peers.size(); k++)
+      if (dev_.peers[k].use_count() > 1) return true;
     return false;
   }
-  // The primitives of the last built-in Build(), from the arrays it was given (`cylinder_cap`: the cylinder intersector's flag).
+  // The record's primitives to one context (`cylinder_cap`: the cylinder intersector's flag to send, which may be a new one).
   nrt_status SendPrimitives(nrt_ctx *c, bool cylinder_cap) const {
-    switch (device_prim_kind_) {
+    const DeviceGeometry &g = geom_;
+    switch (g.kind) {
       case 0: {
-        nrt_status st = detail::HipApi<T>::SetMesh(c, tri_vertices_, tri_stride_, tri_faces_, prim_count_);
-        if (st == NRT_OK && tri_vertices1_) st = detail::HipApi<T>::SetMeshMotion(c, tri_vertices1_, tri_stride_);
-        return (st != NRT_OK || !tri_masks_) ? st : nrtSetPrimMasks(c, tri_masks_, prim_count_);
+        nrt_status st = Api::SetMesh(c, g.vertices, g.stride, g.faces, g.count);
+        if (st == NRT_OK && g.vertices1) st = Api::SetMeshMotion(c, g.vertices1, g.stride);
+        return (st != NRT_OK || !g.masks) ? st : nrtSetPrimMasks(c, g.masks, g.count);
       }
-      case 1: return nrtSetSpheres_f32(c, sph_centers_, sph_radii_, prim_count_);
-      case 2: return nrtSetCylinders_f32(c, cyl_endpoints_, cyl_radii_, cyl_count_, cylinder_cap ? 1 : 0);
-      case 3: return nrtSetCurves_f32(c, crv_cps_, crv_radii_, prim_count_, static_cast<uint32_t>(crv_subdiv_));
+      case 1: return nrtSetSpheres_f32(c, g.positions, g.radii, g.count);
+      case 2: return nrtSetCylinders_f32(c, g.positions, g.radii, g.count, cylinder_cap ? 1 : 0);
+      case 3: return nrtSetCurves_f32(c, g.positions, g.radii, g.count, static_cast<uint32_t>(g.crv_subdiv));
       default: return NRT_ERR_INVALID;
     }
   }
   // Copy-on-write (caller holds batch_mutex_): leave the contexts shared with copies to them and move to fresh ones on the
   // same devices, holding this object's primitives; the caller then sends the tree (from the host arrays).
   bool DetachDeviceContext(bool cylinder_cap) const {
-    const std::vector<int> devices = devices_.empty() ? DeviceList() : devices_;
-    device_tree_stale_ = true;  // (until the caller has sent the tree: a failure below leaves a state the next call retries)
+    const std::vector<int> devices = dev_.devices.empty() ? DeviceList() : dev_.devices;
+    dev_.tree_stale = true;  // (until the caller has sent the tree: a failure below leaves a state the next call retries)
     if (!CreateContexts(devices)) return false;
-    for (size_t k = 0; k <= peers_.size(); k++) {
-      nrt_ctx *c = k == 0 ? ctx_.get() : peers_[k - 1].get();
-      if (SendPrimitives(c, cylinder_cap) != NRT_OK) {
-        backend_error_ = nrtLastError(c);
-        return false;
-      }
-    }
+    for (size_t k = 0; k < NumHipDevices(); k++)
+      if (!Ok(SendPrimitives(Context(k), cylinder_cap), Context(k))) return false;
     return true;
   }
 #endif
@@ -3131,6 +2885,8 @@ class BVHAccel {
   unsigned int pad0_;
 #ifdef NANORT_USE_HIP_BACKEND
   void DropPendingHostTree() { __atomic_store_n(&host_tree_pending_, false, __ATOMIC_RELEASE); }
+  // A copy materialises the source's host tree first and takes it, shares the source's contexts and takes its record; the
+  // staging stays with its owner (scratch, grown on the first TraverseBatch()) and nothing is pending in the copy.
   void CopyFrom(const BVHAccel &o) {
     o.EnsureHostTree();
     std::lock_guard<std::mutex> lock(o.batch_mutex_);  // (o's contexts may be replaced by a batch call of another thread)
@@ -3138,37 +2894,19 @@ class BVHAccel {
     indices_ = o.indices_;
     options_ = o.options_;
     stats_ = o.stats_;
-    ctx_ = o.ctx_;
-    peers_ = o.peers_;
-    devices_ = o.devices_;
-    batch_row_len_ = o.batch_row_len_;
-    device_tree_stale_ = o.device_tree_stale_;
-    device_prim_kind_ = o.device_prim_kind_;
-    cyl_endpoints_ = o.cyl_endpoints_;
-    cyl_radii_ = o.cyl_radii_;
-    cyl_count_ = o.cyl_count_;
-    cyl_test_cap_ = o.cyl_test_cap_;
-    tri_vertices_ = o.tri_vertices_;
-    tri_vertices1_ = o.tri_vertices1_;
-    tri_masks_ = o.tri_masks_;
-    tri_stride_ = o.tri_stride_;
-    tri_faces_ = o.tri_faces_;
-    sph_centers_ = o.sph_centers_;
-    sph_radii_ = o.sph_radii_;
-    crv_cps_ = o.crv_cps_;
-    crv_radii_ = o.crv_radii_;
-    crv_subdiv_ = o.crv_subdiv_;
-    prim_count_ = o.prim_count_;
+    dev_ = o.dev_;
+    geom_ = o.geom_;
     host_tree_pending_ = false;
-    pending_nodes_ = pending_indices_ = 0;
-    for (int k = 0; k < 3; k++) {
-      root_bmin_[k] = o.root_bmin_[k];
-      root_bmax_[k] = o.root_bmax_[k];
-    }
     backend_error_ = o.backend_error_;
-    // (the staging buffers stay with their owner: they are scratch, grown on the first TraverseBatch())
   }
-  // Everything as it is, the pending read-back and the staging included; `o` is left empty (IsValid() false).
+  template <class Record>
+  static Record Take(Record *r) noexcept {  // (what *r held; *r is left default-constructed)
+    Record taken(std::move(*r));
+    *r = Record();
+    return taken;
+  }
+  // Everything as it is, the pending read-back and the staging included; `o` is left empty (IsValid() false): no contexts, the
+  // records at their defaults.
   void MoveFrom(BVHAccel *o) noexcept {
     nodes_ = std::move(o->nodes_);
     indices_ = std::move(o->indices_);
@@ -3178,46 +2916,8 @@ class BVHAccel {
     stats_ = o->stats_;
     host_tree_pending_ = o->HostTreePending();
     o->DropPendingHostTree();
-    pending_nodes_ = o->pending_nodes_;
-    pending_indices_ = o->pending_indices_;
-    for (int k = 0; k < 3; k++) {
-      root_bmin_[k] = o->root_bmin_[k];
-      root_bmax_[k] = o->root_bmax_[k];
-    }
-    ctx_ = std::move(o->ctx_);
-    peers_ = std::move(o->peers_);
-    devices_ = std::move(o->devices_);
-    o->ctx_.reset();
-    o->peers_.clear();
-    o->devices_.clear();
-    batch_row_len_ = o->batch_row_len_;
-    device_tree_stale_ = o->device_tree_stale_;
-    device_prim_kind_ = o->device_prim_kind_;
-    o->device_tree_stale_ = false;
-    o->device_prim_kind_ = -1;
-    cyl_endpoints_ = o->cyl_endpoints_;
-    cyl_radii_ = o->cyl_radii_;
-    cyl_count_ = o->cyl_count_;
-    cyl_test_cap_ = o->cyl_test_cap_;
-    tri_vertices_ = o->tri_vertices_;
-    tri_vertices1_ = o->tri_vertices1_;
-    tri_masks_ = o->tri_masks_;
-    tri_stride_ = o->tri_stride_;
-    tri_faces_ = o->tri_faces_;
-    sph_centers_ = o->sph_centers_;
-    sph_radii_ = o->sph_radii_;
-    crv_cps_ = o->crv_cps_;
-    crv_radii_ = o->crv_radii_;
-    crv_subdiv_ = o->crv_subdiv_;
-    prim_count_ = o->prim_count_;
-    o->crv_cps_ = o->crv_radii_ = NULL;
-    o->cyl_endpoints_ = o->cyl_radii_ = NULL;
-    o->tri_vertices_ = NULL;
-    o->tri_vertices1_ = NULL;
-    o->tri_masks_ = NULL;
-    o->tri_faces_ = NULL;
-    o->sph_centers_ = o->sph_radii_ = NULL;
-    o->cyl_count_ = o->prim_count_ = 0;
+    dev_ = Take(&o->dev_);
+    geom_ = Take(&o->geom_);
     stage_hits_ = std::move(o->stage_hits_);
     stage_mask_ = std::move(o->stage_mask_);
     stage_hits_cap_ = o->stage_hits_cap_;
@@ -3227,30 +2927,10 @@ class BVHAccel {
     o->backend_error_.clear();
   }
   mutable bool host_tree_pending_ = false;  // the tree of the last GPU Build() has not been copied to nodes_ / indices_ yet
-  uint64_t pending_nodes_ = 0, pending_indices_ = 0;
-  T root_bmin_[3] = {T(0), T(0), T(0)}, root_bmax_[3] = {T(0), T(0), T(0)};
-  // (mutable: a batch call may move the object to contexts of its own, copy-on-write — DetachDeviceContext)
-  mutable std::shared_ptr<nrt_ctx> ctx_;
-  mutable std::vector<std::shared_ptr<nrt_ctx> > peers_;  // replicas on the other devices of NANORT_HIP_DEVICES
-  mutable std::vector<int> devices_;                      // the devices of ctx_, then of peers_
-  size_t batch_row_len_ = 0;                      // rays per interleaved row of a multi-device TraverseBatch (0: 4096)
-  mutable bool device_tree_stale_ = false;
-  int device_prim_kind_ = -1;  // what the device context was built over: 0 triangles, 1 spheres, 2 cylinders, 3 curves, -1 nothing usable
-  const float *cyl_endpoints_ = NULL;  // cylinder primitive: what Build() was given
-  const float *cyl_radii_ = NULL;
-  unsigned int cyl_count_ = 0;
-  mutable bool cyl_test_cap_ = true;
-  const T *tri_vertices_ = NULL;  // triangle / sphere primitives: what Build() was given (a detach sends them again)
-  size_t tri_stride_ = 0;
-  const T *tri_vertices1_ = NULL;  // ... and the second vertex keyframe of a Build() over MotionTriangleMesh (NULL: none)
-  const unsigned int *tri_masks_ = NULL;  // ... and the visibility masks of the last SetPrimMasks() (NULL: none)
-  const unsigned int *tri_faces_ = NULL;
-  const float *sph_centers_ = NULL;
-  const float *sph_radii_ = NULL;
-  const float *crv_cps_ = NULL;  // curve primitive: what Build() was given, and the subdivision count the device context holds
-  const float *crv_radii_ = NULL;
-  mutable int crv_subdiv_ = 4;
-  unsigned int prim_count_ = 0;
+  // (mutable, both: a const batch call may move the object to contexts of its own, copy-on-write — DetachDeviceContext — and
+  // re-send the primitives with a new cap flag or subdivision count)
+  mutable DeviceState dev_;
+  mutable DeviceGeometry geom_;
   mutable std::mutex batch_mutex_;  // one per object, never copied: see the comment above TraverseBatch
   // TraverseBatch staging (grow-only): pinned through nrtHostAlloc, plain malloc if that fails
   mutable std::shared_ptr<void> stage_hits_, stage_mask_;

@@ -2,11 +2,19 @@
 // and threads (tests/test_gpu_accel_lifecycle.py).
 //
 //   accel_lifecycle_check --list
+//   accel_lifecycle_check --fixture DIR
 //   accel_lifecycle_check SCENARIO f32|f64 DIR [OUT]
 //
 // DIR holds what the test writes: mesh_a.bin, mesh_b.bin ({u32 nv, u32 nf, float xyz[nv], u32 ijk[nf]}), rays.bin and
 // prays.bin ({u64 n, Ray<float>[n]}: a camera over the meshes and the particle camera), spheres.bin ({u32 n, float
-// xyz[n], float r[n]}), cylinders.bin ({u32 n, float ends[n][2][3], float radii[n][2]}).  f64 widens meshes and rays.
+// xyz[n], float r[n]}), cylinders.bin ({u32 n, float ends[n][2][3], float radii[n][2]}), motion.bin ({u32 nv, u32 nf, float
+// xyz0[nv], float xyz1[nv], u32 ijk[nf], u32 masks[nf], u32 other_masks[nf]}: a mesh with a second keyframe and two sets of
+// visibility masks), mrays.bin (a camera over it), curves.bin ({u32 n, float cps[n][4][3], float radii[n][4]}) and crays.bin
+// (the curve camera).  f64 widens meshes and rays.
+//
+// --fixture: no HIP call.  From the header's host classes alone, over host-built trees: the share of mrays.bin that answers
+// differently at time 0.5 than at time 0, with the masks than without, with the other masks than with the first; the share of
+// crays.bin that answers differently at 2 than at 4 subdivisions, and that hits at all.  The test holds them against its bounds.
 //
 // After every step, for every live accel, one invariant: each batch method returns exactly what the same object's per-ray
 // host method returns on that object's own tree (TraverseBatch / TraverseBatches / the device variants against Traverse,
@@ -54,6 +62,12 @@ struct Inputs {
   std::vector<Ray<float> > rays, prays;
   std::vector<float> sc, sr, ce, cr;
   unsigned int ns = 0, nc = 0;
+  Mesh<float> m0;          // motion.bin: keyframe 0 and the faces ...
+  std::vector<float> m1;   // ... keyframe 1
+  std::vector<unsigned int> masks, masks2;
+  std::vector<Ray<float> > mrays, crays;
+  std::vector<float> kc, kr;  // curves.bin
+  unsigned int nk = 0;
 };
 Inputs g_in;
 std::string g_dir;
@@ -97,7 +111,27 @@ bool read_prims(const std::string &path, unsigned int per_a, unsigned int per_b,
   fclose(fp);
   return ok;
 }
+bool read_motion(const std::string &path) {
+  FILE *fp = fopen(path.c_str(), "rb");
+  if (!fp) return false;
+  uint32_t nv = 0, nf = 0;
+  bool ok = fread(&nv, 4, 1, fp) == 1 && fread(&nf, 4, 1, fp) == 1;
+  g_in.m0.v.resize(3 * (size_t)nv);
+  g_in.m1.resize(3 * (size_t)nv);
+  g_in.m0.f.resize(3 * (size_t)nf);
+  g_in.m0.nf = nf;
+  g_in.masks.resize(nf);
+  g_in.masks2.resize(nf);
+  ok = ok && fread(g_in.m0.v.data(), 4, 3 * (size_t)nv, fp) == 3 * (size_t)nv && fread(g_in.m1.data(), 4, 3 * (size_t)nv, fp) == 3 * (size_t)nv &&
+       fread(g_in.m0.f.data(), 4, 3 * (size_t)nf, fp) == 3 * (size_t)nf && fread(g_in.masks.data(), 4, nf, fp) == nf &&
+       fread(g_in.masks2.data(), 4, nf, fp) == nf;
+  fclose(fp);
+  return ok;
+}
 bool read_inputs(const std::string &dir) {
+  if (!(read_motion(dir + "/motion.bin") && read_rays(dir + "/mrays.bin", &g_in.mrays) && read_rays(dir + "/crays.bin", &g_in.crays) &&
+        read_prims(dir + "/curves.bin", 12, 4, &g_in.kc, &g_in.kr, &g_in.nk)))
+    return false;
   return read_mesh(dir + "/mesh_a.bin", &g_in.a) && read_mesh(dir + "/mesh_b.bin", &g_in.b) && read_rays(dir + "/rays.bin", &g_in.rays) &&
          read_rays(dir + "/prays.bin", &g_in.prays) && read_prims(dir + "/spheres.bin", 3, 1, &g_in.sc, &g_in.sr, &g_in.ns) &&
          read_prims(dir + "/cylinders.bin", 6, 2, &g_in.ce, &g_in.cr, &g_in.nc);
@@ -471,6 +505,153 @@ void prims_batch_first(float) {
 }
 void prims_batch_first(double) {}
 
+// ---- a triangle accel over a MotionTriangleMesh that holds visibility masks: the motion and the masked queries ----
+template <typename T>
+struct MotionFixture {
+  Mesh<T> k0;        // keyframe 0 and the faces
+  std::vector<T> v1;  // keyframe 1
+  std::vector<Ray<T> > rays;
+  std::vector<T> times;                 // every ray at time 0.5
+  std::vector<unsigned int> ray_masks;  // 1, 2, 3, 1, ...: never all-ones
+  MotionFixture() : k0(widen<T>(g_in.m0)), v1(g_in.m1.begin(), g_in.m1.end()), rays(widen<T>(g_in.mrays)), times(g_in.mrays.size(), T(0.5)) {
+    for (size_t i = 0; i < rays.size(); i++) ray_masks.push_back(1u + static_cast<unsigned int>(i % 3));
+  }
+  nanort::MotionTriangleMesh<T> mesh() const { return nanort::MotionTriangleMesh<T>(k0.v.data(), v1.data(), k0.f.data(), sizeof(T) * 3); }
+  nanort::MotionTriangleSAHPred<T> pred() const { return nanort::MotionTriangleSAHPred<T>(k0.v.data(), v1.data(), k0.f.data(), sizeof(T) * 3); }
+  nanort::MotionTriangleIntersector<T> at_time() const { return nanort::MotionTriangleIntersector<T>(k0.v.data(), v1.data(), k0.f.data(), sizeof(T) * 3); }
+  nanort::MaskedTriangleIntersector<T> masked(const unsigned int *masks) const {
+    return nanort::MaskedTriangleIntersector<T>(k0.v.data(), k0.f.data(), sizeof(T) * 3, masks);
+  }
+};
+
+// per ray, through the host walk: the record of `isect` after prepare(isect, i), the miss record where it misses
+template <typename T, class I, class Prepare>
+void host_records(const BVHAccel<T> &a, const std::vector<Ray<T> > &rays, const I &isect, Prepare prepare, std::vector<nanort::TriangleIntersection<T> > *h,
+                  std::vector<unsigned char> *m) {
+  h->resize(rays.size());
+  m->resize(rays.size());
+  for (size_t i = 0; i < rays.size(); i++) {
+    nanort::TriangleIntersection<T> x;
+    prepare(isect, i);
+    (*m)[i] = a.Traverse(rays[i], isect, &x) ? 1 : 0;
+    if (!(*m)[i]) {
+      x.u = x.v = T(0);
+      x.t = rays[i].max_t;
+      x.prim_id = 0xFFFFFFFFu;
+    }
+    (*h)[i] = x;
+  }
+}
+template <typename T>
+unsigned long long records_differ(const std::vector<nanort::TriangleIntersection<T> > &x, const std::vector<unsigned char> &xm,
+                                  const std::vector<nanort::TriangleIntersection<T> > &y, const std::vector<unsigned char> &ym) {
+  unsigned long long bad = 0;
+  for (size_t i = 0; i < x.size(); i++)
+    bad += !(xm[i] == ym[i] && bits_eq(x[i].t, y[i].t) && x[i].prim_id == y[i].prim_id && bits_eq(x[i].u, y[i].u) && bits_eq(x[i].v, y[i].v));
+  return bad;
+}
+
+// `masks`: the words the accel holds now (NULL: none — after a Build() — and the masked queries must refuse)
+template <typename T>
+void check_motion(const char *where, const BVHAccel<T> &a, const MotionFixture<T> &F, const unsigned int *masks) {
+  typedef nanort::TriangleIntersection<T> H;
+  const size_t n = F.rays.size();
+  H sentinel;
+  memset(static_cast<void *>(&sentinel), 0x5A, sizeof(H));
+  std::vector<H> th(n, sentinel), kh(n, sentinel), hh;
+  std::vector<unsigned char> tm(n, 7), to(n, 7), km(n, 7), ko(n, 7), hm;
+  // the batch methods first (every record is written, a miss as the miss record), then the host walk of the same object
+  const bool ok_t = a.TraverseBatchMotion(F.rays.data(), F.times.data(), n, th.data(), tm.data());
+  const std::string err_t = a.LastBackendError();
+  const bool ok_to = a.OccludedBatchMotion(F.rays.data(), F.times.data(), n, to.data());
+  const std::string err_to = a.LastBackendError();
+  const bool ok_k = a.TraverseBatchMasked(F.rays.data(), F.ray_masks.data(), n, kh.data(), km.data());
+  const std::string err_k = a.LastBackendError();
+  const bool ok_ko = a.OccludedBatchMasked(F.rays.data(), F.ray_masks.data(), n, ko.data());
+  const std::string err_ko = a.LastBackendError();
+  host_records(a, F.rays, F.at_time(), [&](const nanort::MotionTriangleIntersector<T> &x, size_t i) { x.SetTime(F.times[i]); }, &hh, &hm);
+  if (ok_t)
+    tally(where, "TraverseBatchMotion", records_differ(th, tm, hh, hm));
+  else
+    refusal(where, "TraverseBatchMotion", err_t);
+  if (ok_to)
+    tally(where, "OccludedBatchMotion", to != hm);
+  else
+    refusal(where, "OccludedBatchMotion", err_to);
+  if (!masks) {
+    must_refuse(where, "TraverseBatchMasked", ok_k, err_k);
+    must_refuse(where, "OccludedBatchMasked", ok_ko, err_ko);
+    return;
+  }
+  host_records(a, F.rays, F.masked(masks), [&](const nanort::MaskedTriangleIntersector<T> &x, size_t i) { x.SetRayMask(F.ray_masks[i]); }, &hh, &hm);
+  if (ok_k)
+    tally(where, "TraverseBatchMasked", records_differ(kh, km, hh, hm));
+  else
+    refusal(where, "TraverseBatchMasked", err_k);
+  if (ok_ko)
+    tally(where, "OccludedBatchMasked", ko != hm);
+  else
+    refusal(where, "OccludedBatchMasked", err_ko);
+}
+// an object with no tree (moved-from): the four queries refuse
+template <typename T>
+void check_motion_refused(const char *where, const BVHAccel<T> &a, const MotionFixture<T> &F) {
+  const size_t n = 64;
+  std::vector<nanort::TriangleIntersection<T> > h(n);
+  std::vector<unsigned char> m(n);
+  must_refuse(where, "TraverseBatchMotion", a.TraverseBatchMotion(F.rays.data(), F.times.data(), n, h.data(), m.data()), a.LastBackendError());
+  must_refuse(where, "OccludedBatchMotion", a.OccludedBatchMotion(F.rays.data(), F.times.data(), n, m.data()), a.LastBackendError());
+  must_refuse(where, "TraverseBatchMasked", a.TraverseBatchMasked(F.rays.data(), F.ray_masks.data(), n, h.data(), m.data()), a.LastBackendError());
+  must_refuse(where, "OccludedBatchMasked", a.OccludedBatchMasked(F.rays.data(), F.ray_masks.data(), n, m.data()), a.LastBackendError());
+}
+
+// ---- curves: TraverseBatch(BezierCurveIntersection*) and OccludedBatchCurves against Traverse (fp32 only) ----
+void host_curves(const BVHAccel<float> &a, int subdiv, std::vector<nanort::BezierCurveIntersection> *h, std::vector<unsigned char> *m) {
+  const std::vector<Ray<float> > &rays = g_in.crays;
+  h->assign(rays.size(), nanort::BezierCurveIntersection());
+  m->assign(rays.size(), 0);
+  for (size_t i = 0; i < rays.size(); i++) {
+    nanort::BezierCurveIntersector<> isect(g_in.kc.data(), g_in.kr.data(), subdiv);
+    (*m)[i] = a.Traverse(rays[i], isect, &(*h)[i]) ? 1 : 0;
+  }
+}
+void check_crv(const char *where, const BVHAccel<float> &a, int subdiv) {
+  typedef nanort::BezierCurveIntersection H;
+  const std::vector<Ray<float> > &rays = g_in.crays;
+  const size_t n = rays.size();
+  std::vector<H> bh(n), hh;
+  std::vector<unsigned char> bm(n, 7), bo(n, 7), hm;
+  const bool ok = a.TraverseBatch(rays.data(), n, bh.data(), bm.data(), nanort::BVHTraceOptions(), subdiv);
+  const std::string err = a.LastBackendError();
+  const bool ok_o = a.OccludedBatchCurves(rays.data(), n, bo.data(), nanort::BVHTraceOptions(), subdiv);
+  const std::string err_o = a.LastBackendError();
+  host_curves(a, subdiv, &hh, &hm);
+  char name[64];
+  snprintf(name, sizeof(name), "TraverseBatch(curve, %d subdivisions)", subdiv);
+  if (ok) {
+    unsigned long long bad = 0;
+    for (size_t i = 0; i < n; i++) bad += bm[i] != hm[i] || memcmp(static_cast<const void *>(&bh[i]), static_cast<const void *>(&hh[i]), sizeof(H)) != 0;
+    tally(where, name, bad);
+  } else {
+    refusal(where, name, err);
+  }
+  if (ok_o)
+    tally(where, "OccludedBatchCurves", bo != hm);
+  else
+    refusal(where, "OccludedBatchCurves", err_o);
+}
+void check_crv_refused(const char *where, const BVHAccel<float> &a) {
+  std::vector<nanort::BezierCurveIntersection> h(64);
+  std::vector<unsigned char> m(64);
+  must_refuse(where, "TraverseBatch(curve)", a.TraverseBatch(g_in.crays.data(), 64, h.data()), a.LastBackendError());
+  must_refuse(where, "OccludedBatchCurves", a.OccludedBatchCurves(g_in.crays.data(), 64, m.data()), a.LastBackendError());
+}
+bool build_crv(BVHAccel<float> *a) {
+  nanort::BVHBuildOptions<float> o;
+  o.cache_bbox = false;
+  return a->Build(g_in.nk, nanort::BezierCurveGeometry(g_in.kc.data(), g_in.kr.data()), nanort::BezierCurvePred(g_in.kc.data()), o);
+}
+
 // ================================ scenarios ================================
 template <typename T>
 struct Fixture {
@@ -822,6 +1003,112 @@ void replicas() {
   replicas_prims(T());
 }
 
+// Build, move-construct, move-assign, copy, then the copied object onto contexts of its own; after every step every live
+// object: the moved-from ones refuse (4 queries each), the others equal their own host walk.
+template <typename T>
+void motion_masks() {
+  MotionFixture<T> F;
+  const unsigned int nf = F.k0.nf;
+  const unsigned int *masks = g_in.masks.data(), *other = g_in.masks2.data();
+  BVHAccel<T> a;
+  BUILD(a.Build(nf, F.mesh(), F.pred()));
+  BUILD(a.SetPrimMasks(masks, nf));
+  check_motion("motion_masks built", a, F, masks);
+  BVHAccel<T> b(std::move(a));
+  expect("motion_masks", "moved-from source: IsValid() == false", !a.IsValid());
+  check_motion_refused("motion_masks moved-from (constructed)", a, F);
+  check_motion("motion_masks move-constructed", b, F, masks);
+  BVHAccel<T> c;
+  c = std::move(b);
+  check_motion_refused("motion_masks moved-from (constructed), after the assignment", a, F);
+  check_motion_refused("motion_masks moved-from (assigned)", b, F);
+  check_motion("motion_masks move-assigned", c, F, masks);
+  BVHAccel<T> d(c);
+  expect("motion_masks", "a copy shares the original's context until one of them changes it", d.HipContext() == c.HipContext());
+  check_motion("motion_masks copied-from", c, F, masks);
+  check_motion("motion_masks copy", d, F, masks);
+  BUILD(c.SetPrimMasks(other, nf));  // the copied-from object moves to contexts of its own: both keyframes and the new words go along
+  expect("motion_masks", "SetPrimMasks() on a shared context detaches", d.HipContext() != c.HipContext() && c.HipContext() != NULL);
+  check_motion("motion_masks copied-from, other masks", c, F, other);
+  check_motion("motion_masks copy, its own masks", d, F, masks);
+  check_motion_refused("motion_masks moved-from (constructed), after the detach", a, F);
+  check_motion_refused("motion_masks moved-from (assigned), after the detach", b, F);
+  BUILD(c.Build(nf, F.mesh(), F.pred()));  // a Build() drops the masks: the two masked queries refuse
+  check_motion("motion_masks rebuilt", c, F, NULL);
+  check_motion("motion_masks copy after the rebuild", d, F, masks);
+  BVHAccel<T> e(d);
+  BUILD(e.SetPrimMasks(other, nf));  // ... and the COPY is the one that detaches, from what it was given by the copy
+  check_motion("motion_masks second copy, other masks", e, F, other);
+  check_motion("motion_masks copy, still its own masks", d, F, masks);
+}
+
+// The same for a curve accel; the argument change is the subdivision count, 4 and then 2.
+void curve_subdiv() {
+  BVHAccel<float> a;
+  BUILD(build_crv(&a));
+  check_crv("curve_subdiv built", a, 4);
+  BVHAccel<float> b(std::move(a));
+  expect("curve_subdiv", "moved-from source: IsValid() == false", !a.IsValid());
+  check_crv_refused("curve_subdiv moved-from (constructed)", a);
+  check_crv("curve_subdiv move-constructed", b, 4);
+  BVHAccel<float> c;
+  c = std::move(b);
+  check_crv_refused("curve_subdiv moved-from (constructed), after the assignment", a);
+  check_crv_refused("curve_subdiv moved-from (assigned)", b);
+  check_crv("curve_subdiv move-assigned", c, 4);
+  BVHAccel<float> d(c);
+  check_crv("curve_subdiv copied-from", c, 4);
+  check_crv("curve_subdiv copy", d, 4);
+  check_crv("curve_subdiv copied-from, 2 subdivisions", c, 2);  // moves to contexts of its own, the curves sent with the new count
+  expect("curve_subdiv", "a new subdivision count on a shared context detaches", d.HipContext() != c.HipContext() && c.HipContext() != NULL);
+  check_crv("curve_subdiv copy, still 4", d, 4);
+  check_crv("curve_subdiv copied-from, 2 again", c, 2);
+  check_crv_refused("curve_subdiv moved-from (constructed), after the detach", a);
+  check_crv_refused("curve_subdiv moved-from (assigned), after the detach", b);
+  check_crv("curve_subdiv copied-from, back to 4", c, 4);
+  check_crv("curve_subdiv copy, 2 (no copy left to keep apart: a re-send)", d, 2);
+}
+
+// ---- --fixture: what the scenes of the two scenarios above can tell apart, on the host alone ----
+struct HostCurvePred : nanort::BezierCurvePred {
+  explicit HostCurvePred(const float *cps) : nanort::BezierCurvePred(cps) {}
+};
+template <typename T>
+void fixture_motion(const char *prec) {
+  typedef nanort::TriangleIntersection<T> H;
+  MotionFixture<T> F;
+  BVHAccel<T> a;  // (a predicate of another type: the host builder, over keyframe 0; the host refit makes the boxes hold keyframe 1 too)
+  BUILD(a.Build(F.k0.nf, F.k0.tm(), HostPred<T>(F.k0.v.data(), F.k0.f.data(), sizeof(T) * 3)));
+  BUILD(a.Refit(F.mesh()));
+  std::vector<H> h0, h5, hp, hk, ho;
+  std::vector<unsigned char> m0, m5, mp, mk, mo;
+  host_records(a, F.rays, F.at_time(), [&](const nanort::MotionTriangleIntersector<T> &x, size_t) { x.SetTime(T(0)); }, &h0, &m0);
+  host_records(a, F.rays, F.at_time(), [&](const nanort::MotionTriangleIntersector<T> &x, size_t i) { x.SetTime(F.times[i]); }, &h5, &m5);
+  host_records(a, F.rays, F.masked(NULL), [&](const nanort::MaskedTriangleIntersector<T> &x, size_t) { x.SetRayMask(0xFFFFFFFFu); }, &hp, &mp);
+  host_records(a, F.rays, F.masked(g_in.masks.data()), [&](const nanort::MaskedTriangleIntersector<T> &x, size_t i) { x.SetRayMask(F.ray_masks[i]); }, &hk, &mk);
+  host_records(a, F.rays, F.masked(g_in.masks2.data()), [&](const nanort::MaskedTriangleIntersector<T> &x, size_t i) { x.SetRayMask(F.ray_masks[i]); }, &ho, &mo);
+  const double n = static_cast<double>(F.rays.size());
+  printf("fixture motion %s rays %zu faces %u time %.4f masks %.4f other_masks %.4f\n", prec, F.rays.size(), F.k0.nf, records_differ(h5, m5, h0, m0) / n,
+         records_differ(hk, mk, hp, mp) / n, records_differ(ho, mo, hk, mk) / n);
+}
+void fixture_curves() {
+  BVHAccel<float> a;
+  nanort::BVHBuildOptions<float> o;
+  o.cache_bbox = false;
+  BUILD(a.Build(g_in.nk, nanort::BezierCurveGeometry(g_in.kc.data(), g_in.kr.data()), HostCurvePred(g_in.kc.data()), o));
+  std::vector<nanort::BezierCurveIntersection> h2, h4;
+  std::vector<unsigned char> m2, m4;
+  host_curves(a, 2, &h2, &m2);
+  host_curves(a, 4, &h4, &m4);
+  size_t differ = 0, hit = 0;
+  for (size_t i = 0; i < h2.size(); i++) {
+    differ += m2[i] != m4[i] || memcmp(static_cast<const void *>(&h2[i]), static_cast<const void *>(&h4[i]), sizeof(h2[i])) != 0;
+    hit += m2[i] || m4[i];
+  }
+  printf("fixture curves rays %zu curves %u subdivisions %.4f hit %.4f\n", h2.size(), g_in.nk, differ / static_cast<double>(h2.size()),
+         hit / static_cast<double>(h2.size()));
+}
+
 struct Scenario {
   const char *name;
   bool f64;  // also runs with T = double
@@ -845,6 +1132,8 @@ const Scenario kScenarios[] = {
     {"threads_same_object", true, SC(threads_same_object)},
     {"threads_copies", true, SC(threads_copies)},
     {"replicas", true, SC(replicas)},
+    {"motion_masks", true, SC(motion_masks)},
+    {"curve_subdiv", false, [](const char *) { curve_subdiv(); }, NULL},
 };
 
 }  // namespace
@@ -854,8 +1143,18 @@ int main(int argc, char **argv) {
     for (const Scenario &s : kScenarios) printf("%s %s\n", s.name, s.f64 ? "f32,f64" : "f32");
     return 0;
   }
+  if (argc == 3 && !strcmp(argv[1], "--fixture")) {  // (host classes only: no HIP call on this path either)
+    if (!read_inputs(argv[2])) {
+      fprintf(stderr, "cannot read the inputs in %s\n", argv[2]);
+      return 2;
+    }
+    fixture_motion<float>("f32");
+    fixture_motion<double>("f64");
+    fixture_curves();
+    return 0;
+  }
   if (argc < 4 || (strcmp(argv[2], "f32") && strcmp(argv[2], "f64"))) {
-    fprintf(stderr, "usage: accel_lifecycle_check --list | SCENARIO f32|f64 DIR [OUT]\n");
+    fprintf(stderr, "usage: accel_lifecycle_check --list | --fixture DIR | SCENARIO f32|f64 DIR [OUT]\n");
     return 64;
   }
   const bool f64 = !strcmp(argv[2], "f64");
