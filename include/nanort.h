@@ -745,6 +745,84 @@ class MaskedTriangleIntersector : public TriangleIntersector<T, H> {
   mutable unsigned int ray_mask_;
 };
 
+// The three per-ray things at once (include/nanort_hip.h, "one descriptor for every triangle ray query"): a TriangleIntersector that
+// holds, besides the mesh, a second vertex keyframe and one word per primitive — both optional — and of the ray being traced its
+// time, its word and its skip id.  Intersect() returns false BEFORE ANY ARITHMETIC for a primitive the ray does not see
+// ((prim_mask & ray_mask) == 0), one outside prim_ids_range, and the ray's skip id; the corners of every other primitive are
+// interpolated to the ray's time by the shared rule (nanort_motion.h) when there is a keyframe 1 (none: keyframe 0 as stored) and
+// tested by TriangleIntersector's own arithmetic.  SetRay() before Traverse(), once per ray; an intersector SetRay() was never
+// called on traces at time 0 with the word 0xFFFFFFFF and the options' skip_prim_id.  Works on the host without the backend.
+template <typename T = float, class H = TriangleIntersection<T> >
+class QueryTriangleIntersector : public TriangleIntersector<T, H> {
+  typedef TriangleIntersector<T, H> Base;
+
+ public:
+  // vertices1 == NULL: no motion; prim_masks == NULL: every primitive carries 0xFFFFFFFF
+  QueryTriangleIntersector(const T *vertices0, const unsigned int *faces, const size_t vertex_stride_bytes, const T *vertices1 = NULL,
+                           const unsigned int *prim_masks = NULL)
+      : Base(vertices0, faces, vertex_stride_bytes), vertices1_(vertices1), prim_masks_(prim_masks), shutter_(static_cast<T>(0.0)),
+        ray_mask_(0xFFFFFFFFu), skip_prim_id_(0xFFFFFFFFu), own_skip_(false) {}
+
+  // The ray's time (clamped to [0, 1], NaN and negatives to 0), its visibility word, and its skip id — which takes the place of
+  // the trace options' skip_prim_id for this ray (0xFFFFFFFF, or an id that names no primitive: nothing is skipped).
+  void SetRay(T time, unsigned int ray_mask, unsigned int skip_prim_id) const {
+    shutter_ = nanort_motion::ClampTime<T>(time);
+    ray_mask_ = ray_mask;
+    skip_prim_id_ = skip_prim_id;
+    own_skip_ = true;
+  }
+  T GetShutterTime() const { return shutter_; }
+  unsigned int GetRayMask() const { return ray_mask_; }
+
+  bool Intersect(T *t_inout, const unsigned int prim_index) const {
+    if (((prim_masks_ ? prim_masks_[prim_index] : 0xFFFFFFFFu) & ray_mask_) == 0u) return false;
+    if (prim_index < this->trace_options_.prim_ids_range[0] || prim_index >= this->trace_options_.prim_ids_range[1]) return false;
+    if (prim_index == (own_skip_ ? skip_prim_id_ : this->trace_options_.skip_prim_id)) return false;
+    real3<T> p[3];
+    for (int c = 0; c < 3; c++) {
+      const unsigned int vi = this->faces_[3 * prim_index + c];
+      const T *a = get_vertex_addr<T>(this->vertices_, vi, this->vertex_stride_bytes_);
+      if (vertices1_) {
+        const T *b = get_vertex_addr<T>(vertices1_, vi, this->vertex_stride_bytes_);
+        for (int k = 0; k < 3; k++) p[c][k] = nanort_motion::Lerp<T>(a[k], b[k], shutter_);
+      } else {
+        for (int k = 0; k < 3; k++) p[c][k] = a[k];
+      }
+    }
+    return this->IntersectVertices(t_inout, p[0], p[1], p[2]);
+  }
+
+ private:
+  const T *vertices1_;
+  const unsigned int *prim_masks_;
+  mutable T shutter_;
+  mutable unsigned int ray_mask_;
+  mutable unsigned int skip_prim_id_;
+  mutable bool own_skip_;
+};
+
+// What BVHAccel::TraverseBatchQuery() is asked for: a wave of rays and whichever of a time, a visibility word and a skip id each of
+// them carries.  `motion` / `masked` say whether the keyframes are interpolated / the masks applied (times == NULL with motion:
+// every ray at time 0; ray_masks == NULL with masked: every ray 0xFFFFFFFF; an array whose flag is off is not read).
+// skip_prim_ids == NULL: options.skip_prim_id for every ray.  `occlusion`: only hit_out is written (required then), each ray
+// stopping at the first triangle that settles it; otherwise EVERY record of isects is written — a miss stores {0, 0, ray.max_t,
+// 0xFFFFFFFF} — and hit_out (optional) receives 1 / 0.
+template <typename T = float>
+struct BatchQuery {
+  BatchQuery()
+      : rays(NULL), num_rays(0), times(NULL), ray_masks(NULL), skip_prim_ids(NULL), motion(false), masked(false), occlusion(false), isects(NULL),
+        hit_out(NULL) {}
+  const Ray<T> *rays;
+  size_t num_rays;
+  const T *times;
+  const unsigned int *ray_masks;
+  const unsigned int *skip_prim_ids;
+  bool motion, masked, occlusion;
+  BVHTraceOptions options;
+  TriangleIntersection<T> *isects;
+  unsigned char *hit_out;
+};
+
 // Robust slab test (Ize 2013), t_max terms widened by MaxMult
 // (ref nanort.h:2278-2370).
 namespace detail {
@@ -1340,6 +1418,10 @@ struct HipApi;
     /* visibility masks: the queries with one word per ray (the setter, nrtSetPrimMasks, has no precision) */ \
     NANORT_HIP_ENTRY(TraverseMasked, nrtTraverseBatchMasked, S)                   \
     NANORT_HIP_ENTRY(OccludedMasked, nrtOccludedBatchMasked, S)                   \
+    /* skip ids, words and times on the same ray: one descriptor */              \
+    typedef nrt_ray_query_##S QueryPod;                                           \
+    NANORT_HIP_ENTRY(Query, nrtQueryBatch, S)                                     \
+    NANORT_HIP_ENTRY(QueryDevice, nrtQueryBatchDevice, S)                         \
   };
 NANORT_HIP_API(float, f32)
 NANORT_HIP_API(double, f64)
@@ -1708,6 +1790,32 @@ class BVHAccel {
     }
     return true;
   }
+  // The combined query on the HOST, with or without NANORT_USE_HIP_BACKEND (BatchQuery and QueryTriangleIntersector above; the
+  // contract of include/nanort_hip.h, "one descriptor for every triangle ray query"): N calls of Traverse(), ray i through a copy of
+  // `intersector` of its own on which SetRay() was called with the ray's time (q.motion: q.times[i], or 0), word (q.masked:
+  // q.ray_masks[i], or 0xFFFFFFFF) and skip id (q.skip_prim_ids[i], or q.options.skip_prim_id).  It is the caller who gives
+  // `intersector` keyframe 1 for a q.motion query and the primitives' words for a q.masked one.  Every record is written (a miss:
+  // {0, 0, ray.max_t, 0xFFFFFFFF}); with q.occlusion only q.hit_out.  Returns false, nothing written, when the query has rays and
+  // lacks them or its output.
+  bool TraverseBatchQuery(const BatchQuery<T> &q, const QueryTriangleIntersector<T> &intersector) const {
+    if (q.num_rays && (!q.rays || !(q.occlusion ? static_cast<const void *>(q.hit_out) : static_cast<const void *>(q.isects)))) return false;
+    for (size_t i = 0; i < q.num_rays; i++) {
+      const QueryTriangleIntersector<T> ray_intersector(intersector);
+      ray_intersector.SetRay((q.motion && q.times) ? q.times[i] : static_cast<T>(0.0), (q.masked && q.ray_masks) ? q.ray_masks[i] : 0xFFFFFFFFu,
+                             q.skip_prim_ids ? q.skip_prim_ids[i] : q.options.skip_prim_id);
+      TriangleIntersection<T> isect;
+      const bool hit = Traverse(q.rays[i], ray_intersector, &isect, q.options);
+      if (!q.occlusion) {
+        TriangleIntersection<T> &out = q.isects[i];  // (field by field: the caller's padding bytes stay the caller's)
+        out.u = hit ? isect.u : static_cast<T>(0.0);
+        out.v = hit ? isect.v : static_cast<T>(0.0);
+        out.t = hit ? isect.t : q.rays[i].max_t;
+        out.prim_id = hit ? isect.prim_id : 0xFFFFFFFFu;
+      }
+      if (q.hit_out) q.hit_out[i] = hit ? 1 : 0;
+    }
+    return true;
+  }
 
 #ifdef NANORT_USE_HIP_BACKEND
   // Closest hit for each of `num_rays` rays in one GPU launch.  isects[i] is written only when
@@ -1905,6 +2013,25 @@ class BVHAccel {
     const nrt_trace_options o = TraceOptions(options);
     return Ok(Api::OccludedMasked(Context(), Pod(rays), ray_masks, num_rays, &o, occluded_out));
   }
+  // The combined query on the GPU (nrtQueryBatch: include/nanort_hip.h, "one descriptor for every triangle ray query"): each ray
+  // at its own time (q.motion: a tree built with MotionTriangleMesh), among the triangles it sees (q.masked: SetPrimMasks() first)
+  // and other than the one it left (q.skip_prim_ids).  Records and flags equal those of the host form above, TraverseBatchQuery(q,
+  // intersector), over the same tree.  A query with one of the three alone is the existing call for it.
+  bool TraverseBatchQuery(const BatchQuery<T> &q) const {
+    std::lock_guard<std::mutex> lock(batch_mutex_);
+    if (!QueryTreeReady(q, "TraverseBatchQuery")) return false;
+    const nrt_trace_options o = TraceOptions(q.options);
+    const typename Api::QueryPod d = QueryDescriptor(q, &o);
+    return Ok(Api::Query(Context(), &d));
+  }
+  // ... and with device pointers in every array of `q`, asynchronous on `hip_stream` (see TraverseBatchDevice).
+  bool TraverseBatchQueryDevice(const BatchQuery<T> &q, void *hip_stream) const {
+    std::lock_guard<std::mutex> lock(batch_mutex_);
+    if (!TriangleTreeOnDevice("TraverseBatchQueryDevice: no triangle tree on the GPU") || !QueryTreeReady(q, "TraverseBatchQueryDevice")) return false;
+    const nrt_trace_options o = TraceOptions(q.options);
+    const typename Api::QueryPod d = QueryDescriptor(q, &o);
+    return Ok(Api::QueryDevice(Context(), &d, hip_stream));
+  }
   // ... and with device pointers, asynchronous on `hip_stream` (see TraverseBatchDevice).
   bool MultiHitTraverseBatchDevice(const Ray<T> *d_rays, size_t num_rays, unsigned int max_hits, TriangleIntersection<T> *d_isects,
                                    unsigned int *d_counts, void *hip_stream, const BVHTraceOptions &options = BVHTraceOptions()) const {
@@ -2095,6 +2222,27 @@ class BVHAccel {
       return false;
     }
     return DeviceTreeReady(0);
+  }
+  // The checks of the combined query (caller holds batch_mutex_): those of every feature it has, or of a plain triangle batch.
+  bool QueryTreeReady(const BatchQuery<T> &q, const char *who) const {
+    if (q.motion && !MotionTreeReady(who)) return false;
+    if (q.masked && !MaskedTreeReady(who)) return false;
+    return DeviceTreeReady(0);
+  }
+  // ... and its descriptor for the C ABI (`o`: the caller's converted options, which outlive the call).
+  typename Api::QueryPod QueryDescriptor(const BatchQuery<T> &q, const nrt_trace_options *o) const {
+    typename Api::QueryPod d;
+    d.struct_size = static_cast<uint32_t>(sizeof(d));
+    d.flags = (q.occlusion ? NRT_QUERY_OCCLUSION : 0u) | (q.motion ? NRT_QUERY_MOTION : 0u) | (q.masked ? NRT_QUERY_MASKED : 0u);
+    d.rays = Pod(q.rays);
+    d.num_rays = q.num_rays;
+    d.options = o;
+    d.skip_prim_ids = q.skip_prim_ids;
+    d.times = q.times;
+    d.ray_masks = q.ray_masks;
+    d.hits_out = Pod(q.isects);
+    d.mask_out = q.hit_out;
+    return d;
   }
   // The checks every host batch call makes (caller holds batch_mutex_): a context, the primitive kind the call's records are
   // for (0 triangles, 1 spheres), and a tree adopted by Load() uploaded — after a copy-on-write detach when the contexts are

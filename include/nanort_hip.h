@@ -158,12 +158,42 @@ typedef struct {
   uint64_t max_stack;     /* deepest stack (entries) any ray needed     */
 } nrt_trace_counters;
 
+/* The descriptor of nrtQueryBatch* ("one descriptor for every triangle ray query" below, where every field is explained). */
+#define NRT_QUERY_OCCLUSION 1u /* flags only: mask_out[i] is exactly the closest-hit flag; hits_out is not read */
+#define NRT_QUERY_MOTION 2u    /* every ray at its own time (times == NULL: every ray at time 0) */
+#define NRT_QUERY_MASKED 4u    /* every ray with its own word (ray_masks == NULL: every ray 0xFFFFFFFF) */
+typedef struct nrt_ray_query_f32 {
+  uint32_t struct_size; /* sizeof(nrt_ray_query_f32): lets the struct grow */
+  uint32_t flags;       /* NRT_QUERY_* */
+  const nrt_ray_f32 *rays;
+  uint64_t num_rays;
+  const nrt_trace_options *options; /* NULL: defaults */
+  const uint32_t *skip_prim_ids;    /* NULL: options->skip_prim_id for every ray */
+  const float *times;               /* read with NRT_QUERY_MOTION only */
+  const uint32_t *ray_masks;        /* read with NRT_QUERY_MASKED only */
+  nrt_hit_f32 *hits_out;
+  uint8_t *mask_out;
+} nrt_ray_query_f32;
+typedef struct nrt_ray_query_f64 {
+  uint32_t struct_size; /* sizeof(nrt_ray_query_f64) */
+  uint32_t flags;
+  const nrt_ray_f64 *rays;
+  uint64_t num_rays;
+  const nrt_trace_options *options;
+  const uint32_t *skip_prim_ids;
+  const double *times;
+  const uint32_t *ray_masks;
+  nrt_hit_f64 *hits_out;
+  uint8_t *mask_out;
+} nrt_ray_query_f64;
+
 #ifdef __cplusplus
 static_assert(sizeof(nrt_ray_f32) == 36 && sizeof(nrt_ray_f64) == 72, "Ray layout");
 static_assert(sizeof(nrt_node_f32) == 40 && sizeof(nrt_node_f64) == 64, "BVHNode layout");
 static_assert(sizeof(nrt_hit_f32) == 16 && sizeof(nrt_hit_f64) == 32, "TriangleIntersection layout");
 static_assert(sizeof(nrt_build_options_f32) == 28 && sizeof(nrt_build_options_f64) == 32, "BVHBuildOptions layout");
 static_assert(sizeof(nrt_build_stats) == 16 && sizeof(nrt_trace_options) == 16, "stats/options layout");
+static_assert(sizeof(nrt_ray_query_f32) == 72 && sizeof(nrt_ray_query_f64) == 72, "ray query descriptor layout");
 #endif
 
 /* ---- context ------------------------------------------------------------ */
@@ -574,7 +604,8 @@ NRT_API nrt_status nrtTraverseBatches_f64(nrt_ctx *ctx, uint32_t num_batches, co
  * launch, asynchronously on `hip_stream`.  nrtOccludedBatchSkip*: mask[i] is the hit flag of the closest-hit form with the same ids.
  * nrtTraverseBatchesSkip*: an array of `num_batches` pointers; the array or any entry of it may be NULL, and a batch with a NULL
  * entry uses options->skip_prim_id; records are exactly those of separate calls (fp32: still one launch, fp64: one after the other).
- * Not covered: multi-hit, nrtTraverseCountDevice, nrtTraverseBatchMulti, nrtGroup*, scenes and the Embree shim take no per-ray ids. */
+ * Not covered: multi-hit, nrtTraverseCountDevice, nrtTraverseBatchMulti, nrtGroup*, scenes and the Embree shim take no per-ray ids.
+ * These calls take Closest / Occlusion launches only; ids together with motion times or visibility words: nrtQueryBatch* below. */
 NRT_API nrt_status nrtTraverseBatchSkip_f32(nrt_ctx *ctx, const nrt_ray_f32 *rays, uint64_t num_rays, const nrt_trace_options *options,
                                             const uint32_t *skip_prim_ids, nrt_hit_f32 *hits_out, uint8_t *hit_mask_out);
 NRT_API nrt_status nrtTraverseBatchSkip_f64(nrt_ctx *ctx, const nrt_ray_f64 *rays, uint64_t num_rays, const nrt_trace_options *options,
@@ -640,7 +671,9 @@ NRT_API nrt_status nrtTraverseBatchesSkip_f64(nrt_ctx *ctx, uint32_t num_batches
  * `hip_stream`; nrtBuild / nrtSetTree / nrtSetMesh* / nrtSetMeshMotion* / nrtDestroy wait for them.  A context without a keyframe
  * and contexts of the other primitive kinds are refused (NRT_ERR_INVALID).
  *
- * Every other entry point keeps working on a motion context and answers for keyframe 0 (over the wider boxes). */
+ * Every other entry point keeps working on a motion context and answers for keyframe 0 (over the wider boxes).
+ * Not covered: the motion queries take one launch-wide skip_prim_id and no visibility words; a time per ray together with an id or
+ * a word per ray: nrtQueryBatch* below. */
 NRT_API nrt_status nrtSetMeshMotion_f32(nrt_ctx *ctx, const float *vertices_t1, size_t vertex_stride_bytes);
 NRT_API nrt_status nrtSetMeshMotion_f64(nrt_ctx *ctx, const double *vertices_t1, size_t vertex_stride_bytes);
 NRT_API nrt_status nrtSetMeshMotionDevice_f32(nrt_ctx *ctx, const float *d_vertices_t1, uint32_t num_vertices, size_t vertex_stride_bytes,
@@ -698,9 +731,9 @@ NRT_API nrt_status nrtOccludedBatchMotionDevice_f64(nrt_ctx *ctx, const nrt_ray_
  * nrtDestroy wait for them.  NRT_ERR_INVALID: a context without masks, a context of another primitive kind, a misaligned
  * `d_ray_masks`; NRT_ERR_PRECISION: a context of the other precision.  A refusal sets nrtLastError and writes nothing.
  *
- * Not covered: every other entry point ignores the masks — multi-hit, the motion queries, per-ray skip ids, the batch tables,
- * nrtTraverseBatchMulti, nrtGroup*, scenes / instances (and with them the Embree shim, whose ray.mask stays ignored); spheres,
- * cylinders and curves take no masks. */
+ * Not covered: every other entry point but nrtQueryBatch* (below: words together with motion times and per-ray skip ids) ignores
+ * the masks — multi-hit, the motion queries, the per-ray skip id calls, the batch tables, nrtTraverseBatchMulti, nrtGroup*, scenes /
+ * instances (and with them the Embree shim, whose ray.mask stays ignored); spheres, cylinders and curves take no masks. */
 NRT_API nrt_status nrtSetPrimMasks(nrt_ctx *ctx, const uint32_t *masks, uint64_t count);
 NRT_API nrt_status nrtSetPrimMasksDevice(nrt_ctx *ctx, const uint32_t *d_masks, uint64_t count, void *hip_stream);
 NRT_API nrt_status nrtTraverseBatchMasked_f32(nrt_ctx *ctx, const nrt_ray_f32 *rays, const uint32_t *ray_masks, uint64_t num_rays,
@@ -721,6 +754,62 @@ NRT_API nrt_status nrtOccludedBatchMaskedDevice_f32(nrt_ctx *ctx, const nrt_ray_
                                                     const nrt_trace_options *options, uint8_t *d_mask_out, void *hip_stream);
 NRT_API nrt_status nrtOccludedBatchMaskedDevice_f64(nrt_ctx *ctx, const nrt_ray_f64 *d_rays, const uint32_t *d_ray_masks, uint64_t num_rays,
                                                     const nrt_trace_options *options, uint8_t *d_mask_out, void *hip_stream);
+
+/* ---- one descriptor for every triangle ray query: skip ids, visibility words and motion times on the SAME ray -----------------
+ * An OPT-IN EXTENSION.  The three families above each apply one thing per ray and ignore the other two.  A renderer's bounce or
+ * shadow wave needs all three at once: the ray leaves a triangle (its skip id), has a type (its word) and, on a moving mesh, a
+ * shutter time.  nrtQueryBatch* takes a DESCRIPTOR (nrt_ray_query_f32 / _f64, among the PODs above) that names whichever of them
+ * the wave has:
+ *
+ *     struct_size    sizeof(the descriptor): lets the struct grow
+ *     flags          NRT_QUERY_OCCLUSION | NRT_QUERY_MOTION | NRT_QUERY_MASKED
+ *     rays, num_rays
+ *     options        NULL: the reference's defaults
+ *     skip_prim_ids  one id per ray, NULL: options->skip_prim_id for every ray
+ *     times          read with MOTION only; NULL: every ray at time 0
+ *     ray_masks      read with MASKED only; NULL: every ray 0xFFFFFFFF
+ *     hits_out       the records (not read with OCCLUSION)
+ *     mask_out       the flags (optional without OCCLUSION, the output with it)
+ *
+ * Triangle contexts of the call's precision only.
+ *
+ * Contract.  A record is that of the reference's Traverse (nanort.h:2487-2556) over the context's own node array with an
+ * intersector that, for primitive p and ray i,
+ *  - returns false WITHOUT TOUCHING THE RAY'S STATE when MASKED is set and (prim_mask[p] & ray_masks[i]) == 0, when p is outside
+ *    options->prim_ids_range, or when p is the ray's skip id;
+ *  - the ray's skip id is skip_prim_ids[i], or options->skip_prim_id where the array is NULL; 0xFFFFFFFF and every id at or above
+ *    the context's number of faces skip nothing;
+ *  - with MOTION takes the three corners interpolated to ClampTime(times[i]) by include/nanort_motion.h's rule (the motion blur
+ *    section above); without MOTION the corners of keyframe 0;
+ *  - then runs TriangleIntersector's own test (nanort.h:1054-1150), cull_back_face included.
+ * Every field of every record is bit-identical to that; a miss is {0, 0, max_t, 0xFFFFFFFF}; every record is written.  With
+ * OCCLUSION a ray is settled once its hit distance is < max_t, and mask_out[i] is exactly the closest-hit flag.
+ *
+ * Routing.  A descriptor that an existing call can express IS that call — the same kernel (nrtLastKernelName), the same bytes out:
+ *     no flag but OCCLUSION, no ids           nrtTraverseBatch* / nrtOccludedBatch*
+ *     ids only                                nrtTraverseBatchSkip* / nrtOccludedBatchSkip*
+ *     MOTION only                             nrtTraverseBatchMotion* / nrtOccludedBatchMotion*      (k_traverse_motion)
+ *     MASKED only                             nrtTraverseBatchMasked* / nrtOccludedBatchMasked*      (k_traverse_masked)
+ *     two or three of ids, MOTION, MASKED     the combined walk (k_traverse_query)
+ *
+ * Refusals; each writes nothing and sets nrtLastError.  NRT_ERR_INVALID: a NULL context (no message to set) or descriptor; a
+ * struct_size other than the struct's; unknown flag bits; NULL rays with num_rays > 0; the kind's output missing (hits_out without
+ * OCCLUSION, mask_out with it); MOTION on a context without a keyframe; MASKED on a context without masks; a sphere, cylinder or
+ * curve context; a Device array (times, ray_masks, skip_prim_ids) that is not aligned to its element size; no tree; more than
+ * 2^31-1 rays.  NRT_ERR_PRECISION: a context of the other precision.  num_rays == 0 is NRT_OK.
+ *
+ * Ordering: the rules of the motion and masked queries.  nrtQueryBatchDevice_* reads and writes device memory, asynchronously on
+ * `hip_stream`; nrtSetMesh* / nrtSetMeshMotion* / nrtSetPrimMasks* / nrtBuild / nrtSetTree / nrtDestroy wait for it.  nrtQueryBatch_*
+ * takes host arrays through the staged and (page-locked arrays, nrtHostAlloc) pipelined paths of the calls above; a batch traced
+ * in pieces carries, with each piece, its slices of all three per-ray arrays.  The first MASKED query behind a change of the masks
+ * or of the tree re-derives the words' leaf-order copy, as a masked query does.
+ *
+ * Not covered: multi-hit, the batch tables, nrtTraverseBatchMulti, nrtGroup*, scenes and the Embree shim, and the sphere,
+ * cylinder and curve kinds keep ignoring what they ignore today. */
+NRT_API nrt_status nrtQueryBatch_f32(nrt_ctx *ctx, const nrt_ray_query_f32 *query);
+NRT_API nrt_status nrtQueryBatch_f64(nrt_ctx *ctx, const nrt_ray_query_f64 *query);
+NRT_API nrt_status nrtQueryBatchDevice_f32(nrt_ctx *ctx, const nrt_ray_query_f32 *query, void *hip_stream);
+NRT_API nrt_status nrtQueryBatchDevice_f64(nrt_ctx *ctx, const nrt_ray_query_f64 *query, void *hip_stream);
 
 /* One HOST batch spread over several contexts — typically one per GPU of the node (nrtDeviceCount), each holding the same
  * tree: nrtBuild is deterministic, so building the same mesh on every context gives bit-identical replicas (or nrtSetTree the

@@ -861,6 +861,50 @@ class BVHAccel:
             self._h, d_rays.data_ptr(), self._device_ray_masks(d_ray_masks, n), n, _p(options), d_mask.data_ptr(), self._stream_handle(stream)))
         return n
 
+    # -- one descriptor for every triangle ray query (include/nanort_hip.h) ----
+    @staticmethod
+    def _query_flags(times, ray_masks, motion, masked, occlusion):
+        motion = (times is not None) if motion is None else bool(motion)
+        masked = (ray_masks is not None) if masked is None else bool(masked)
+        return (capi.NRT_QUERY_OCCLUSION if occlusion else 0) | (capi.NRT_QUERY_MOTION if motion else 0) | (capi.NRT_QUERY_MASKED if masked else 0)
+
+    def QueryBatch(self, rays, times=None, ray_masks=None, skip_prim_ids=None, motion=None, masked=None, occlusion=False, options=None):
+        """nrtQueryBatch: one call for whichever of a shutter time, a visibility word and a skip id every ray carries.  `motion` /
+        `masked`: whether the query interpolates the keyframes / applies the masks (None: iff the array is given; True with no array:
+        every ray at time 0 / with the word 0xFFFFFFFF).  Returns (hits, mask), or with `occlusion` only the flags."""
+        rays = np.ascontiguousarray(rays, dtype=ray_dtype(self.real))
+        n = rays.shape[0]
+        t = self._host_times(times, n)
+        v = self._host_ray_masks(ray_masks, n)
+        ids = None if skip_prim_ids is None else self._host_skip_ids(skip_prim_ids, n)
+        hits = None if occlusion else np.zeros((n,), dtype=hit_dtype(self.real))
+        mask = np.zeros((n,), dtype=np.uint8)
+        options = _opts(options)
+        q = capi.RayQuery(ctypes.sizeof(capi.RayQuery), self._query_flags(times, ray_masks, motion, masked, occlusion), rays.ctypes.data, n,
+                          None if options is None else options.ctypes.data, None if ids is None else ids.ctypes.data,
+                          None if t is None else t.ctypes.data, None if v is None else v.ctypes.data,
+                          None if hits is None else hits.ctypes.data, mask.ctypes.data)
+        self._check(getattr(self._L, "nrtQueryBatch_" + self._s)(self._h, ctypes.addressof(q)))
+        return mask if occlusion else (hits, mask)
+
+    def QueryBatchDevice(self, d_rays, d_hits=None, d_mask=None, times=None, ray_masks=None, skip_prim_ids=None, motion=None, masked=None,
+                         occlusion=False, options=None, stream=None):
+        """nrtQueryBatchDevice: the same on HBM-resident torch tensors (raw PODs; `times` in the accel's precision, `ray_masks` and
+        `skip_prim_ids` 32-bit words, one per ray), asynchronous on `stream` (default: torch's current stream).  With `occlusion`
+        only `d_mask` is written and `d_hits` is not read.  Returns n."""
+        n = self._n_rays(d_rays)
+        if not occlusion and d_hits is not None:
+            assert d_hits.numel() * d_hits.element_size() >= n * hit_dtype(self.real).itemsize
+        assert d_mask is None or d_mask.numel() >= n
+        options = _opts(options)
+        q = capi.RayQuery(ctypes.sizeof(capi.RayQuery), self._query_flags(times, ray_masks, motion, masked, occlusion), d_rays.data_ptr(), n,
+                          None if options is None else options.ctypes.data,
+                          None if skip_prim_ids is None else self._device_skip_ids(skip_prim_ids, n), self._device_times(times, n),
+                          self._device_ray_masks(ray_masks, n), None if d_hits is None else d_hits.data_ptr(),
+                          None if d_mask is None else d_mask.data_ptr())
+        self._check(getattr(self._L, "nrtQueryBatchDevice_" + self._s)(self._h, ctypes.addressof(q), self._stream_handle(stream)))
+        return n
+
     def MultiHitTraverseBatch(self, rays, max_hits, options=None):
         """The K = max_hits frontmost hits of every ray (include/nanort_hip.h, nrtMultiHitTraverseBatch): returns (hits[n, K],
         counts[n]); row i holds ray i's hits by ascending (t, prim_id), then miss records {0, 0, max_t, 0xFFFFFFFF}."""

@@ -28,6 +28,25 @@ class TraceCounters(ctypes.Structure):
     ]
 
 
+NRT_QUERY_OCCLUSION, NRT_QUERY_MOTION, NRT_QUERY_MASKED = 1, 2, 4
+
+
+class RayQuery(ctypes.Structure):
+    """nrt_ray_query_f32 / nrt_ray_query_f64: the two differ in what their pointers point at, not in their layout."""
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32),
+        ("flags", ctypes.c_uint32),
+        ("rays", ctypes.c_void_p),
+        ("num_rays", ctypes.c_uint64),
+        ("options", ctypes.c_void_p),
+        ("skip_prim_ids", ctypes.c_void_p),
+        ("times", ctypes.c_void_p),
+        ("ray_masks", ctypes.c_void_p),
+        ("hits_out", ctypes.c_void_p),
+        ("mask_out", ctypes.c_void_p),
+    ]
+
+
 _LIB = None
 
 vp, u32, u64, sz, i32, P = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER
@@ -96,6 +115,9 @@ SIGNATURES = [
     ("nrtTraverseBatchMaskedDevice", _BOTH, _QT + [vp, vp, vp], i32),
     ("nrtOccludedBatchMasked", _BOTH, _QT + [vp], i32),
     ("nrtOccludedBatchMaskedDevice", _BOTH, _QT + [vp, vp], i32),
+    # one descriptor for every triangle ray query (RayQuery below): ctx, descriptor[, stream]
+    ("nrtQueryBatch", _BOTH, [vp, vp], i32),
+    ("nrtQueryBatchDevice", _BOTH, [vp, vp, vp], i32),
     ("nrtTraverseBatchMulti", _BOTH, [vp, u32, vp, u64, u64, vp, vp, vp], i32),
     ("nrtDeviceCount", None, [], i32),
     ("nrtTraverseCountDevice", _BOTH, _Q + [P(TraceCounters)], i32),

@@ -24,7 +24,10 @@ struct TraverseBatches {
 // records, no post pass; on a triangle context it IS Occlusion: traverse_device says so under the lock.)
 // (Motion / MotionOcclusion: the closest-hit and occlusion queries of nrt*BatchMotion*, every ray at its own time: motion.hip)
 // (Masked / MaskedOcclusion: those of nrt*BatchMasked*, every ray with its own visibility word: masked.hip)
-enum class Query { Closest, Occlusion, Count, MultiHit, Cylinders, MultiBatch, Curves, OcclusionPrims, Motion, MotionOcclusion, Masked, MaskedOcclusion };
+// (Combined / CombinedOcclusion: those of nrtQueryBatch* with two or more of per-ray skip ids, times and words — with_motion,
+// with_masks and skip_ids say which: query.hip)
+enum class Query { Closest, Occlusion, Count, MultiHit, Cylinders, MultiBatch, Curves, OcclusionPrims, Motion, MotionOcclusion, Masked, MaskedOcclusion,
+                   Combined, CombinedOcclusion };
 template <typename T>
 struct TraverseLaunch {
   Query kind;
@@ -39,14 +42,20 @@ struct TraverseLaunch {
   uint32_t max_hits = 0;
   uint32_t *hit_counts = nullptr;        // MultiHit (may be null): one word per ray
   const TraverseBatches<T> *batches = nullptr; // MultiBatch: rays and outputs per batch, n = all their rays (the context takes one launch: the caller checked)
-  const uint32_t *skip_ids = nullptr;    // Closest, Occlusion (nrt*BatchSkip*): one skip id per ray in the place of opt->skip_prim_id (MultiBatch: batches->skip[])
-  const T *times = nullptr;              // Motion, MotionOcclusion: one time per ray (null: every ray at time 0)
-  const uint32_t *ray_masks = nullptr;   // Masked, MaskedOcclusion: one visibility word per ray (null: every ray 0xFFFFFFFF)
-  bool motion() const { return kind == Query::Motion || kind == Query::MotionOcclusion; }
-  bool masked() const { return kind == Query::Masked || kind == Query::MaskedOcclusion; }
+  const uint32_t *skip_ids = nullptr;    // Closest, Occlusion (nrt*BatchSkip*), Combined*: one skip id per ray in the place of opt->skip_prim_id (MultiBatch: batches->skip[])
+  const T *times = nullptr;              // Motion, MotionOcclusion, Combined* with_motion: one time per ray (null: every ray at time 0)
+  const uint32_t *ray_masks = nullptr;   // Masked, MaskedOcclusion, Combined* with_masks: one visibility word per ray (null: every ray 0xFFFFFFFF)
+  bool with_motion = false, with_masks = false; // Combined, CombinedOcclusion: the features of the launch besides its ids
+  bool descriptor = false;               // the launch came through nrtQueryBatch*: triangle contexts only, whatever it was routed to
+  bool combined() const { return kind == Query::Combined || kind == Query::CombinedOcclusion; }
+  bool motion() const { return kind == Query::Motion || kind == Query::MotionOcclusion || (combined() && with_motion); }
+  bool masked() const { return kind == Query::Masked || kind == Query::MaskedOcclusion || (combined() && with_masks); }
   bool own_walk() const { return kind == Query::MultiHit || motion() || masked(); } // a binary walk of its own: no wide records, no completion record
   // the output the kind is for — what a call with rays cannot do without — is its flags; else its records: hits, or (Cylinders, Curves) cyl_hits
-  bool flags_only() const { return kind == Query::Occlusion || kind == Query::OcclusionPrims || kind == Query::MotionOcclusion || kind == Query::MaskedOcclusion; }
+  bool flags_only() const {
+    return kind == Query::Occlusion || kind == Query::OcclusionPrims || kind == Query::MotionOcclusion || kind == Query::MaskedOcclusion ||
+           kind == Query::CombinedOcclusion;
+  }
   void *records() const { return (kind == Query::Cylinders || kind == Query::Curves) ? cyl_hits : (void *)hits; }
   // the launch carries per-ray skip ids
   bool has_skip_ids() const {
@@ -64,6 +73,8 @@ template <typename T>
 static nrt_status validate_launch(nrt_ctx *c, const TraverseLaunch<T> &l) {
   const bool custom = c->prim_kind != kPrimTriangles; // spheres / cylinders
   if (c->prec != (int)sizeof(T)) return fail(c, NRT_ERR_PRECISION, "nrtTraverseBatch: precision mismatch");
+  if (l.descriptor && custom) // (include/nanort_hip.h, "one descriptor for every triangle ray query")
+    return fail(c, NRT_ERR_INVALID, "nrtQueryBatch: triangle contexts only (this context holds %s)", kPrimKinds[c->prim_kind].name);
   if (l.motion()) { // (include/nanort_hip.h, "motion blur")
     if (custom) return fail(c, NRT_ERR_INVALID, "motion queries: triangle contexts only (this context holds %s)", kPrimKinds[c->prim_kind].name);
     if (!c->d_verts1) return fail(c, NRT_ERR_INVALID, "motion queries: the context holds no motion keyframe (nrtSetMeshMotion)");
@@ -71,7 +82,7 @@ static nrt_status validate_launch(nrt_ctx *c, const TraverseLaunch<T> &l) {
     if (((uintptr_t)l.times % sizeof(T)) != 0u) return fail(c, NRT_ERR_INVALID, "motion queries: the times array is not aligned to %zu bytes", sizeof(T));
   }
   if (l.masked()) { // (include/nanort_hip.h, "visibility masks")
-    const char *fn = l.kind == Query::Masked ? "nrtTraverseBatchMasked" : "nrtOccludedBatchMasked";
+    const char *fn = l.combined() ? "nrtQueryBatch" : l.kind == Query::Masked ? "nrtTraverseBatchMasked" : "nrtOccludedBatchMasked";
     if (custom) return fail(c, NRT_ERR_INVALID, "%s: masked queries: triangle contexts only (this context holds %s)", fn, kPrimKinds[c->prim_kind].name);
     if (!c->d_prim_masks) return fail(c, NRT_ERR_INVALID, "%s: masked queries: the context holds no visibility masks (nrtSetPrimMasks)", fn);
     if (((uintptr_t)l.ray_masks & 3u) != 0u) return fail(c, NRT_ERR_INVALID, "%s: masked queries: the ray_masks array is not 4-byte aligned", fn);
@@ -79,7 +90,7 @@ static nrt_status validate_launch(nrt_ctx *c, const TraverseLaunch<T> &l) {
   if (l.has_skip_ids()) { // (include/nanort_hip.h, "per-ray skip ids")
     if (custom)
       return fail(c, NRT_ERR_INVALID, "per-ray skip ids: triangle contexts only (the sphere, cylinder and curve intersectors have no skip id)");
-    if (l.kind != Query::Closest && l.kind != Query::Occlusion && l.kind != Query::MultiBatch)
+    if (l.kind != Query::Closest && l.kind != Query::Occlusion && l.kind != Query::MultiBatch && !l.combined())
       return fail(c, NRT_ERR_INVALID, "per-ray skip ids: closest-hit and occlusion queries only");
     bool aligned = ((uintptr_t)l.skip_ids & 3u) == 0u;
     if (l.batches)
@@ -125,7 +136,9 @@ static nrt_status take_slot(nrt_ctx *c, hipStream_t s, nrt_ctx::LaunchSlot **out
 }
 
 // The kernel a launch runs, from the context's tree and tunables and the launch's kind and options.
-enum class Walk { Literal, OneLevel, TwoLevel, MultiHit, Motion, Masked }; // k_traverse, k_traverse_wide of WIDTH 2 / 4, k_traverse_multihit, k_traverse_motion, k_traverse_masked
+// k_traverse, k_traverse_wide of WIDTH 2 / 4, k_traverse_multihit, k_traverse_motion, k_traverse_masked, k_traverse_query<MOTION, MASKED>
+// of <true, false> / <false, true> / <true, true>  (nrt_ctx::occupancy has one row per value)
+enum class Walk { Literal, OneLevel, TwoLevel, MultiHit, Motion, Masked, QueryMotion, QueryMasked, QueryMotionMasked };
 struct WalkChoice {
   Walk walk;
   bool plain_options; // prim ids are < num_faces: nothing can be rejected by the trace options -> the kernel variant without the id tests
@@ -134,6 +147,9 @@ struct WalkChoice {
   unsigned dbg;
   bool wide() const { return walk == Walk::OneLevel || walk == Walk::TwoLevel; }
   bool wide4() const { return walk == Walk::TwoLevel; }
+  bool query() const { return walk == Walk::QueryMotion || walk == Walk::QueryMasked || walk == Walk::QueryMotionMasked; }
+  bool query_motion() const { return walk == Walk::QueryMotion || walk == Walk::QueryMotionMasked; }
+  bool query_masked() const { return walk == Walk::QueryMasked || walk == Walk::QueryMotionMasked; }
 };
 template <typename T>
 static WalkChoice choose_walk(const nrt_ctx *c, const TraverseLaunch<T> &l) {
@@ -158,7 +174,8 @@ static WalkChoice choose_walk(const nrt_ctx *c, const TraverseLaunch<T> &l) {
   w.wide4_big = c->num_branch_records >= (1ull << 25) || (c->wide4_big_ok == 2 && c->prim_kind == kPrimTriangles); // (2: forced, for the tests)
   const bool use_wide4 = use_wide && c->d_wide4 && c->wide_stack == 10 && c->tree_nested && c->root_is_branch && !prof_needs_w2 &&
                          (!w.wide4_big || (!custom && !c->order4 && !(w.dbg & (32u | 8192u))));
-  w.walk = l.masked() ? Walk::Masked : l.motion() ? Walk::Motion : multihit ? Walk::MultiHit : (use_wide4 ? Walk::TwoLevel : (use_wide ? Walk::OneLevel : Walk::Literal));
+  w.walk = l.combined() ? (l.with_motion ? (l.with_masks ? Walk::QueryMotionMasked : Walk::QueryMotion) : Walk::QueryMasked)
+           : l.masked() ? Walk::Masked : l.motion() ? Walk::Motion : multihit ? Walk::MultiHit : (use_wide4 ? Walk::TwoLevel : (use_wide ? Walk::OneLevel : Walk::Literal));
   w.lds_entries = l.own_walk() ? kLdsStackDefault : (use_wide4 ? kWide4LdsStack : (custom ? 10 : (use_wide ? c->wide_stack : c->lds_stack)));
   return w;
 }
@@ -168,7 +185,8 @@ template <typename T>
 static GridPlan size_grid(nrt_ctx *c, const WalkChoice &w, uint64_t n) {
   auto &e = c->occupancy[(int)w.walk][c->prim_kind];
   if (e.blocks_per_cu == 0 || e.lds_entries != w.lds_entries)
-    e = {w.lds_entries, (unsigned)(w.walk == Walk::Masked    ? traverse_masked_blocks_per_cu<T>()
+    e = {w.lds_entries, (unsigned)(w.query()                 ? traverse_query_blocks_per_cu<T>(w.query_motion(), w.query_masked())
+                        : w.walk == Walk::Masked    ? traverse_masked_blocks_per_cu<T>()
                         : w.walk == Walk::Motion    ? traverse_motion_blocks_per_cu<T>()
                         : w.walk == Walk::MultiHit  ? traverse_multihit_blocks_per_cu<T>()
                         : w.walk == Walk::Literal ? traverse_blocks_per_cu<T>(w.lds_entries)
@@ -201,7 +219,7 @@ static void fill_walk_args(const nrt_ctx *c, const TraverseLaunch<T> &l, const W
   a.skip_prim = l.opt->skip_prim_id;
   a.skip_ids = l.skip_ids; // (MultiBatch: null, the table's skip_v instead)
   a.cull_back_face = l.opt->cull_back_face ? 1u : 0u;
-  a.any_hit = (l.kind == Query::Occlusion || l.kind == Query::OcclusionPrims || l.kind == Query::MotionOcclusion || l.kind == Query::MaskedOcclusion) ? 1u : 0u;
+  a.any_hit = l.flags_only() ? 1u : 0u; // (every kind that writes flags only is an occlusion query)
   a.plain_options = w.plain_options ? 1u : 0u;
   a.root_test = c->tree_nested ? 0u : 1u;
   a.order4 = (c->order4 && w.wide4() && c->prim_kind == kPrimTriangles && l.kind != Query::Occlusion && !profiled) ? 1u : 0u;
@@ -288,7 +306,15 @@ static nrt_status enqueue_launch(nrt_ctx *c, const TraverseLaunch<T> &l, const W
   a.done_publish = post_pass ? 0u : 1u;
   const bool timed = l.timed && !use_rec;
   if (timed) HIPCHK(c, hipEventRecord(slot->t0, s));
-  if (w.walk == Walk::Masked) {
+  if (w.query()) {
+    static const char *const names[2][3] = {{"nrt::k_traverse_query<float, 32, true, false>", "nrt::k_traverse_query<float, 32, false, true>",
+                                             "nrt::k_traverse_query<float, 32, true, true>"},
+                                            {"nrt::k_traverse_query<double, 32, true, false>", "nrt::k_traverse_query<double, 32, false, true>",
+                                             "nrt::k_traverse_query<double, 32, true, true>"}};
+    static_assert(kLdsStackDefault == 32, "the names above carry the stack depth");
+    HIPCHK(c, launch_traverse_query<T>(a, w.query_motion(), w.query_masked(), c->d_tris1, l.times, (const uint32_t *)c->b_leaf_masks.p, l.ray_masks, grid, s));
+    c->last_kernel = names[sizeof(T) == 4 ? 0 : 1][w.walk == Walk::QueryMotion ? 0 : w.walk == Walk::QueryMasked ? 1 : 2];
+  } else if (w.walk == Walk::Masked) {
     HIPCHK(c, launch_traverse_masked<T>(a, (const uint32_t *)c->b_leaf_masks.p, l.ray_masks, grid, s));
     c->last_kernel = sizeof(T) == 4 ? "nrt::k_traverse_masked<float>" : "nrt::k_traverse_masked<double>";
   } else if (w.walk == Walk::Motion) {
@@ -490,7 +516,7 @@ static bool is_pinned_host(const void *p) {
 // trace -> download, one after the other.  With PAGE-LOCKED buffers (nrtHostAlloc) the batch is cut into pieces and
 // pipelined over three streams — piece k+1 uploads while piece k is traced and piece k-1 downloads (PCIe is full duplex) —
 // so the call approaches the slower of the two copy directions instead of their sum plus the kernel.
-// `host`: a Closest, Motion or Masked query over the caller's host arrays (skip ids, times and ray masks may be null).  Whether the call takes the
+// `host`: a Closest, Motion, Masked or Combined query over the caller's host arrays (skip ids, times and ray masks may be null).  Whether the call takes the
 // pipeline is read off its size and its pointers before the lock; every other call, the refusals included, is query_host's.
 template <typename T>
 static nrt_status traverse_host(nrt_ctx *c, const TraverseLaunch<T> &host) {
@@ -537,8 +563,9 @@ static nrt_status traverse_host(nrt_ctx *c, const TraverseLaunch<T> &host) {
       HIPCHK(c, hipEventRecord(c->ev_in[b], c->copy_in));
       HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_in[b], 0));
       if (piece >= 2) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_out[b], 0));
-      st = traverse_device<T>(c, {.kind = host.kind, .rays = d_r, .n = m, .opt = host.opt, .stream = c->stream, .timed = true, .hits = d_h, .mask = d_m,
-                                  .skip_ids = d_s, .times = d_t, .ray_masks = d_v});
+      TraverseLaunch<T> l = host; // (its kind and what a Combined launch carries besides)
+      l.rays = d_r, l.n = m, l.stream = c->stream, l.timed = true, l.hits = d_h, l.mask = d_m, l.skip_ids = d_s, l.times = d_t, l.ray_masks = d_v;
+      st = traverse_device<T>(c, l);
       if (st) { // (copies into the caller's buffers may still be in flight: let them land before the call returns)
         (void)hipStreamSynchronize(c->copy_in);
         (void)hipStreamSynchronize(c->stream);
@@ -555,7 +582,7 @@ static nrt_status traverse_host(nrt_ctx *c, const TraverseLaunch<T> &host) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return NRT_OK;
   }
-  return query_host<T>(c, host.masked() ? "nrtTraverseBatchMasked" : "nrtTraverseBatch", host);
+  return query_host<T>(c, host.descriptor ? "nrtQueryBatch" : host.masked() ? "nrtTraverseBatchMasked" : "nrtTraverseBatch", host);
 }
 
 // One host batch spread over several contexts — one per GPU of the node, each holding the same tree (the build is
@@ -776,6 +803,47 @@ static nrt_status traverse_batches_host(nrt_ctx *c, uint32_t nb, const typename 
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return NRT_OK;
+}
+
+// nrtQueryBatch* (include/nanort_hip.h, "one descriptor for every triangle ray query"): the descriptor's own refusals, then the launch
+// it describes.  A descriptor an existing entry point can express becomes exactly that entry point's launch — the same kind, the
+// same arrays, hence the same kernel and the same bytes; two or more of {ids, MOTION, MASKED} become a Combined launch (query.hip).
+// D: nrt_ray_query_f32 / _f64.  `device`: the arrays are the caller's device memory and `stream` its stream.
+template <typename T, typename D>
+static nrt_status query_batch(nrt_ctx *c, const D *q, bool device, void *stream) {
+  const char *fn = device ? "nrtQueryBatchDevice" : "nrtQueryBatch";
+  if (!c) return NRT_ERR_INVALID;
+  if (!q) return fail(c, NRT_ERR_INVALID, "%s: NULL descriptor", fn);
+  if (q->struct_size != sizeof(D)) return fail(c, NRT_ERR_INVALID, "%s: struct_size %u, this library's descriptor has %zu bytes", fn, q->struct_size, sizeof(D));
+  const uint32_t known = NRT_QUERY_OCCLUSION | NRT_QUERY_MOTION | NRT_QUERY_MASKED;
+  if (q->flags & ~known) return fail(c, NRT_ERR_INVALID, "%s: unknown flag bits 0x%x", fn, q->flags & ~known);
+  const bool occ = (q->flags & NRT_QUERY_OCCLUSION) != 0u, motion = (q->flags & NRT_QUERY_MOTION) != 0u, masked = (q->flags & NRT_QUERY_MASKED) != 0u;
+  if (q->num_rays > 0x7FFFFFFFull) return fail(c, NRT_ERR_INVALID, "%s: more than 2^31-1 rays in one call", fn);
+  if (q->num_rays && !q->rays) return fail(c, NRT_ERR_INVALID, "%s: NULL rays", fn);
+  if (q->num_rays && !(occ ? (const void *)q->mask_out : (const void *)q->hits_out)) return fail(c, NRT_ERR_INVALID, "%s: NULL %s", fn, occ ? "mask_out" : "hits_out");
+  const bool ids = q->skip_prim_ids != nullptr;
+  TraverseLaunch<T> l = {};
+  l.kind = ((int)ids + (int)motion + (int)masked >= 2) ? (occ ? Query::CombinedOcclusion : Query::Combined)
+           : motion                                    ? (occ ? Query::MotionOcclusion : Query::Motion)
+           : masked                                    ? (occ ? Query::MaskedOcclusion : Query::Masked)
+                                                       : (occ ? Query::Occlusion : Query::Closest);
+  l.rays = q->rays;
+  l.n = q->num_rays;
+  l.opt = q->options;
+  l.hits = occ ? nullptr : q->hits_out; // (an occlusion query does not read hits_out)
+  l.mask = q->mask_out;
+  l.skip_ids = q->skip_prim_ids;
+  l.times = motion ? q->times : nullptr;         // (an array whose flag is not set is not read)
+  l.ray_masks = masked ? q->ray_masks : nullptr;
+  l.with_motion = motion;
+  l.with_masks = masked;
+  l.descriptor = true;
+  if (device) {
+    l.stream = (hipStream_t)stream;
+    l.timed = true;
+    return query_device<T>(c, fn, l);
+  }
+  return occ ? query_host<T>(c, fn, l) : traverse_host<T>(c, l);
 }
 
 // ---------------------------------------------------------------------------
@@ -999,6 +1067,12 @@ nrt_status nrtOccludedBatchMaskedDevice_f64(nrt_ctx *c, const nrt_ray_f64 *r, co
   return query_device<double>(c, "nrtOccludedBatchMaskedDevice", {.kind = Query::MaskedOcclusion, .rays = r, .n = n, .opt = o, .stream = (hipStream_t)s, .timed = true,
                                                                   .mask = m, .ray_masks = v});
 }
+
+// One descriptor for every triangle ray query (include/nanort_hip.h): skip ids, words and times on the same ray.
+nrt_status nrtQueryBatch_f32(nrt_ctx *c, const nrt_ray_query_f32 *q) { return query_batch<float>(c, q, false, nullptr); }
+nrt_status nrtQueryBatch_f64(nrt_ctx *c, const nrt_ray_query_f64 *q) { return query_batch<double>(c, q, false, nullptr); }
+nrt_status nrtQueryBatchDevice_f32(nrt_ctx *c, const nrt_ray_query_f32 *q, void *s) { return query_batch<float>(c, q, true, s); }
+nrt_status nrtQueryBatchDevice_f64(nrt_ctx *c, const nrt_ray_query_f64 *q, void *s) { return query_batch<double>(c, q, true, s); }
 
 nrt_status nrtTraverseBatchMulti_f32(nrt_ctx *const *ctxs, uint32_t num_ctx, const nrt_ray_f32 *r, uint64_t n, uint64_t row_len,
                                      const nrt_trace_options *o, nrt_hit_f32 *h, uint8_t *m) {

@@ -73,6 +73,15 @@ int traverse_masked_blocks_per_cu();
 template <typename T>
 hipError_t launch_permute_masks(const void *tris, const uint32_t *masks, uint32_t num_faces, uint32_t *leaf_masks, uint32_t n, hipStream_t s);
 
+// ---- query.hip: the combined walk (two or more of: per-ray skip ids in args.skip_ids, motion times, visibility words) --------------
+// `motion` / `masked` select the instantiation (at least one of them); the arrays of a feature that is off are not read.
+// `tris1`, `times`: as launch_traverse_motion's; `leaf_masks`, `ray_masks`: as launch_traverse_masked's; args.any_hit: the occlusion query
+template <typename T>
+hipError_t launch_traverse_query(const TraverseArgs<T> &args, bool motion, bool masked, const void *tris1, const T *times, const uint32_t *leaf_masks,
+                                 const uint32_t *ray_masks, unsigned grid, hipStream_t s);
+template <typename T>
+int traverse_query_blocks_per_cu(bool motion, bool masked);
+
 // ---- build.hip --------------------------------------------------------------------------------------------------------
 enum : unsigned { kBuildMorton = 1u, kBuildSubtreeDfs = 2u }; // gpu_build's build_flags: Morton pre-pass, one-node-per-step subtree kernel
 struct BuildResult {

@@ -15,7 +15,7 @@
 // Like the multi-hit walk the launch publishes no completion record: its slot is closed by an event (api_query.hip, enqueue_launch).
 #include "binary_walk_dev.h"
 #include "kernels.h"
-#include "../../include/nanort_motion.h"
+#include "motion_dev.h" // motion_record: the interpolated leaf record (shared with query.hip)
 
 namespace nrt {
 
@@ -25,20 +25,6 @@ struct MotionArgs {
   const LeafTri<T> *tris1; // the leaf records of keyframe 1, in the same leaf order
   const T *times;          // [num_rays] one time per ray, or null: every ray at time 0
 };
-
-// The leaf record a ray at shutter time `s` sees: nine interpolated components, the id of keyframe 0's record.
-template <typename T>
-__device__ __forceinline__ LeafTri<T> motion_record(const LeafTri<T> &k0, const LeafTri<T> &k1, T s) {
-  LeafTri<T> tri;
-#pragma unroll
-  for (int j = 0; j < 3; j++) {
-    tri.p0[j] = nanort_motion::Lerp<T>(k0.p0[j], k1.p0[j], s);
-    tri.p1[j] = nanort_motion::Lerp<T>(k0.p1[j], k1.p1[j], s);
-    tri.p2[j] = nanort_motion::Lerp<T>(k0.p2[j], k1.p2[j], s);
-  }
-  tri.prim_id = k0.prim_id;
-  return tri;
-}
 
 // The motion query of the binary walk: closest hit, or occlusion when `any`.
 template <typename T>
