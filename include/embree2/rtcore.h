@@ -16,8 +16,10 @@
  *  - a miss sets geomID = primID = instID = RTC_INVALID_GEOMETRY_ID and leaves tfar alone; Ng is never written;
  *  - no back-face culling, ray masks and time are ignored; the ray's [tnear, tfar] selects candidate meshes by
  *    their boxes, the per-mesh search itself is unbounded (nanosg.h:817, see nanort_hip.h "two-level scenes").
- *    (The library has visibility masks — nanort_hip.h, "visibility masks" — for single triangle contexts only; this shim goes
- *    through two-level scenes, which take none, so ray.mask and rtcSetMask stay without effect here.) */
+ *    (The library has visibility masks for single triangle contexts — nanort_hip.h, "visibility masks" — and, per instance, for
+ *    the two-level scenes this shim goes through — "instance visibility masks on a scene": nrtSceneSetNodeMasks and the
+ *    nrtScene*BatchMasked* queries.  The shim does not use them yet: it still ignores ray.mask and offers no rtcSetMask, because
+ *    its export set and the ignored ray.mask are pinned by its own tests; that is left for a later change.) */
 #ifndef NANORT_EMBREE2_RTCORE_H_
 #define NANORT_EMBREE2_RTCORE_H_
 

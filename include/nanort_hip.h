@@ -732,8 +732,9 @@ NRT_API nrt_status nrtOccludedBatchMotionDevice_f64(nrt_ctx *ctx, const nrt_ray_
  * `d_ray_masks`; NRT_ERR_PRECISION: a context of the other precision.  A refusal sets nrtLastError and writes nothing.
  *
  * Not covered: every other entry point but nrtQueryBatch* (below: words together with motion times and per-ray skip ids) ignores
- * the masks — multi-hit, the motion queries, the per-ray skip id calls, the batch tables, nrtTraverseBatchMulti, nrtGroup*, scenes /
- * instances (and with them the Embree shim, whose ray.mask stays ignored); spheres, cylinders and curves take no masks. */
+ * the masks — multi-hit, the motion queries, the per-ray skip id calls, the batch tables, nrtTraverseBatchMulti, nrtGroup*; inside a
+ * scene the triangle words of its mesh contexts are ignored (scenes have words per INSTANCE: "instance visibility masks on a scene",
+ * below; the Embree shim's ray.mask stays ignored); spheres, cylinders and curves take no masks. */
 NRT_API nrt_status nrtSetPrimMasks(nrt_ctx *ctx, const uint32_t *masks, uint64_t count);
 NRT_API nrt_status nrtSetPrimMasksDevice(nrt_ctx *ctx, const uint32_t *d_masks, uint64_t count, void *hip_stream);
 NRT_API nrt_status nrtTraverseBatchMasked_f32(nrt_ctx *ctx, const nrt_ray_f32 *rays, const uint32_t *ray_masks, uint64_t num_rays,
@@ -1023,6 +1024,53 @@ NRT_API int nrtSceneLastPath(const nrt_scene *scene);
  *      the reference's cull comparing a distance with a parameter, cannot hand an occlusion ray over. */
 NRT_API nrt_status nrtSceneOccludedBatch_f32(nrt_scene *scene, const nrt_ray_f32 *rays, uint64_t num_rays, uint8_t *mask_out);
 NRT_API nrt_status nrtSceneOccludedBatchDevice_f32(nrt_scene *scene, const nrt_ray_f32 *d_rays, uint64_t num_rays, uint8_t *d_mask_out);
+
+/* ---- instance visibility masks on a scene: 32 bits per node, 32 bits per ray ------------------------------------------------------
+ * An OPT-IN EXTENSION, the scene-level counterpart of "visibility masks" above (the instance masks of DXR and OptiX; a camera bit,
+ * a shadow bit, a reflection bit — INTEGRATION.md): one scene serves every ray type instead of one committed scene per type.
+ *
+ *     an instance exists for a ray  iff  (node_mask & ray_mask) != 0;
+ *     a masked query answers exactly as the unmasked query would on a scene committed from the visible nodes alone, with the
+ *     node ids kept.
+ *
+ * "Does not exist" is stronger than "is skipped when reached": of the reference's quirks, the 64 nearest entered node boxes by
+ * (entry distance, node id) are counted among the VISIBLE nodes (kMaxIntersections) — a hidden instance takes no place among them.
+ *
+ * Setter.  nrtSceneSetNodeMasks takes one word per node in node-id order; `count` must equal the number of nodes added so far
+ * (NRT_ERR_INVALID otherwise, nothing changed).  masks == NULL resets every node to 0xFFFFFFFF (count is not read).  A node
+ * added later starts at 0xFFFFFFFF.  The words are NO PART OF THE TOP-LEVEL TREE: the setter works before or after nrtSceneCommit,
+ * nrtSceneCommit keeps them, and a change after Commit needs no new Commit — it takes effect at the next masked query, which
+ * uploads the words on the scene's stream first (scene calls are synchronous, so nothing is in flight).
+ *
+ * Queries.  nrtSceneTraverseBatchMasked* / nrtSceneOccludedBatchMasked* are the four scene queries above with `ray_masks`: one word
+ * per ray, NULL = every ray carries 0xFFFFFFFF; a ray whose word is 0 sees nothing and gets the miss record (flag 0) of the unmasked
+ * call.  Contract, on a committed scene:
+ *   1. Records: every field of every record is bit-identical to what nrtSceneTraverseBatch* returns on the scene of the nodes
+ *      visible to that ray (same mesh contexts, same transforms, in node order), with node_id mapped back to the node's id in
+ *      THIS scene; flags likewise.
+ *   2. Occlusion: the flags of nrtSceneOccludedBatchMasked* are exactly the masked closest-hit flags, within the limit of
+ *      exactness of item 2 of the occlusion contract above.
+ *   3. With all-ones words on either side (every node 0xFFFFFFFF, or every ray 0xFFFFFFFF / ray_masks == NULL and no node word 0)
+ *      the bytes are those of the unmasked call.
+ *   4. Ordering, ray limit (2^31 - 1), the stale-mesh check, nrtSceneLastPath / nrtSceneLastRedone and every tunable: as for the
+ *      unmasked calls ("scan_max" and "walk_min" keep comparing the node count, not the visible count).  The masked closest-hit
+ *      call consults and updates the walk back-off exactly as the unmasked one does; the masked occlusion call does neither.
+ *   5. Refusals, each NRT_ERR_INVALID with nrtSceneLastError set and nothing written: those of the unmasked forms (NULL rays,
+ *      NULL hits or mask, an uncommitted or stale scene, too many rays) and a `d_ray_masks` that is not 4-byte aligned.
+ *      The host forms upload the words beside the rays; the Device forms read num_rays words in HBM.
+ *
+ * The unmasked calls ignore node masks entirely.  Triangle masks of a mesh context (nrtSetPrimMasks) remain ignored inside scenes,
+ * by the masked and the unmasked scene calls alike.  Not covered: the Embree shim (its ray.mask stays ignored; rtcSetMask is not
+ * offered), nrtGroup*. */
+NRT_API nrt_status nrtSceneSetNodeMasks(nrt_scene *scene, const uint32_t *masks, uint32_t count);
+NRT_API nrt_status nrtSceneTraverseBatchMasked_f32(nrt_scene *scene, const nrt_ray_f32 *rays, const uint32_t *ray_masks, uint64_t num_rays,
+                                                   nrt_scene_hit_f32 *hits_out, uint8_t *hit_mask_out);
+NRT_API nrt_status nrtSceneTraverseBatchMaskedDevice_f32(nrt_scene *scene, const nrt_ray_f32 *d_rays, const uint32_t *d_ray_masks,
+                                                         uint64_t num_rays, nrt_scene_hit_f32 *d_hits_out, uint8_t *d_mask_out);
+NRT_API nrt_status nrtSceneOccludedBatchMasked_f32(nrt_scene *scene, const nrt_ray_f32 *rays, const uint32_t *ray_masks, uint64_t num_rays,
+                                                   uint8_t *mask_out);
+NRT_API nrt_status nrtSceneOccludedBatchMaskedDevice_f32(nrt_scene *scene, const nrt_ray_f32 *d_rays, const uint32_t *d_ray_masks,
+                                                         uint64_t num_rays, uint8_t *d_mask_out);
 
 #ifdef __cplusplus
 }

@@ -94,6 +94,37 @@ class BatchTracer {
     return true;
   }
 
+  // Instance visibility masks (include/nanort_hip.h, nrtSceneSetNodeMasks): one word per node of the scene in node order, or
+  // NULL = every node 0xFFFFFFFF.  No new Commit is needed; the next TraverseMasked sees the change.
+  bool SetNodeMasks(const uint32_t *masks, size_t count) {
+    if (!handle_) return false;
+    if (nrtSceneSetNodeMasks(handle_, masks, static_cast<uint32_t>(count)) != NRT_OK) {
+      error_ = nrtSceneLastError(handle_);
+      return false;
+    }
+    return true;
+  }
+
+  // Traverse on the nodes each ray sees: node i exists for ray r iff (masks[i] & ray_masks[r]) != 0 (ray_masks == NULL: every
+  // ray 0xFFFFFFFF).  A thin forward to nrtSceneTraverseBatchMasked_f32; records are finished as Traverse finishes them.
+  template <class IsectT>
+  bool TraverseMasked(const nanort::Ray<float> *rays, const uint32_t *ray_masks, size_t num_rays, IsectT *isects, unsigned char *hit_out = NULL) {
+    if (!handle_) return false;
+    if (num_rays == 0) return true;
+    std::vector<nrt_scene_hit_f32> hits(num_rays);
+    std::vector<unsigned char> mask(num_rays);
+    if (nrtSceneTraverseBatchMasked_f32(handle_, reinterpret_cast<const nrt_ray_f32 *>(rays), ray_masks, num_rays, &hits[0], &mask[0]) != NRT_OK) {
+      error_ = nrtSceneLastError(handle_);
+      return false;
+    }
+    for (size_t i = 0; i < num_rays; i++) {
+      if (hit_out) hit_out[i] = mask[i];
+      if (!mask[i]) continue;
+      Finish(rays[i], hits[i], &isects[i]);
+    }
+    return true;
+  }
+
   // For callers that keep their ray waves in HBM: device pointers in and out, compact records {t, u, v, prim_id, node_id}
   // (every record is written: a miss carries t = ray.max_t and ids 0xFFFFFFFF), optional hit flags.  The rest of the
   // reference's Intersection record (P, Ns, Ng) is the shader's business on the device.  Synchronous.

@@ -1059,3 +1059,72 @@ class Scene:
         assert d_rays.is_cuda and d_mask.is_cuda and d_mask.numel() >= n
         torch.cuda.current_stream().synchronize()
         self._check(self._L.nrtSceneOccludedBatchDevice_f32(self._h, d_rays.data_ptr(), n, d_mask.data_ptr()))
+
+    def SetNodeMasks(self, masks):
+        """Instance visibility masks (nrtSceneSetNodeMasks): one uint32 per node in node-id order, or None = every node
+        0xFFFFFFFF.  An instance exists for a ray of a masked query iff (node word & ray word) != 0.  No part of the top-level tree:
+        before or after Commit, and a change needs no new Commit."""
+        if masks is None:
+            self._check(self._L.nrtSceneSetNodeMasks(self._h, None, 0))
+            return
+        masks = np.ascontiguousarray(masks, dtype=np.uint32)
+        self._check(self._L.nrtSceneSetNodeMasks(self._h, _p(masks), masks.shape[0]))
+
+    @staticmethod
+    def _ray_words(ray_masks, n):
+        if ray_masks is None:
+            return None
+        ray_masks = np.ascontiguousarray(ray_masks, dtype=np.uint32)
+        assert ray_masks.shape == (n,), "one uint32 word per ray"
+        return ray_masks
+
+    def TraverseBatchMasked(self, rays, ray_masks=None):
+        """`TraverseBatch` on the nodes each ray sees (nrtSceneTraverseBatchMasked_f32): `ray_masks` is one uint32 per ray,
+        None = every ray 0xFFFFFFFF.  Node ids are this scene's."""
+        from .wire import RAY_F32, SCENE_HIT_F32
+
+        rays = np.ascontiguousarray(rays, dtype=RAY_F32)
+        words = self._ray_words(ray_masks, rays.shape[0])
+        hits = np.zeros((rays.shape[0],), dtype=SCENE_HIT_F32)
+        mask = np.zeros((rays.shape[0],), dtype=np.uint8)
+        self._check(self._L.nrtSceneTraverseBatchMasked_f32(self._h, _p(rays), _p(words), rays.shape[0],
+                                                            _p(hits), _p(mask)))
+        return hits, mask
+
+    def TraverseBatchMaskedDevice(self, d_rays, d_ray_masks, d_hits, d_mask=None):
+        """`TraverseBatchDevice` with the rays' words in HBM: `d_ray_masks` is a torch tensor of one 32-bit word per ray (or None).
+        Synchronous (see nrtSceneTraverseBatchMaskedDevice_f32); waits for torch's current stream first."""
+        import torch
+
+        from .wire import RAY_F32, SCENE_HIT_F32
+
+        n = d_rays.numel() // RAY_F32.itemsize
+        assert d_rays.is_cuda and d_hits.is_cuda and d_hits.numel() >= n * SCENE_HIT_F32.itemsize
+        assert d_ray_masks is None or (d_ray_masks.is_cuda and d_ray_masks.numel() * d_ray_masks.element_size() >= 4 * n)
+        torch.cuda.current_stream().synchronize()
+        self._check(self._L.nrtSceneTraverseBatchMaskedDevice_f32(self._h, d_rays.data_ptr(), d_ray_masks.data_ptr() if d_ray_masks is not None else None,
+                                                                  n, d_hits.data_ptr(), d_mask.data_ptr() if d_mask is not None else None))
+
+    def OccludedBatchMasked(self, rays, ray_masks=None):
+        """`OccludedBatch` on the nodes each ray sees (nrtSceneOccludedBatchMasked_f32): the flags `TraverseBatchMasked` would
+        return, and nothing else."""
+        from .wire import RAY_F32
+
+        rays = np.ascontiguousarray(rays, dtype=RAY_F32)
+        words = self._ray_words(ray_masks, rays.shape[0])
+        mask = np.zeros((rays.shape[0],), dtype=np.uint8)
+        self._check(self._L.nrtSceneOccludedBatchMasked_f32(self._h, _p(rays), _p(words), rays.shape[0], _p(mask)))
+        return mask
+
+    def OccludedBatchMaskedDevice(self, d_rays, d_ray_masks, d_mask):
+        """`OccludedBatchDevice` with the rays' words in HBM (see TraverseBatchMaskedDevice).  Synchronous."""
+        import torch
+
+        from .wire import RAY_F32
+
+        n = d_rays.numel() // RAY_F32.itemsize
+        assert d_rays.is_cuda and d_mask.is_cuda and d_mask.numel() >= n
+        assert d_ray_masks is None or (d_ray_masks.is_cuda and d_ray_masks.numel() * d_ray_masks.element_size() >= 4 * n)
+        torch.cuda.current_stream().synchronize()
+        self._check(self._L.nrtSceneOccludedBatchMaskedDevice_f32(self._h, d_rays.data_ptr(), d_ray_masks.data_ptr() if d_ray_masks is not None else None,
+                                                                  n, d_mask.data_ptr()))

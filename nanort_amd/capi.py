@@ -141,6 +141,12 @@ SIGNATURES = [
     ("nrtSceneLastPath", None, [vp], i32),
     ("nrtSceneOccludedBatch", _F32, [vp, vp, u64, vp], i32),
     ("nrtSceneOccludedBatchDevice", _F32, [vp, vp, u64, vp], i32),
+    # instance visibility masks: one word per node (no precision), and the four scene queries with the per-ray words behind the rays
+    ("nrtSceneSetNodeMasks", None, [vp, vp, u32], i32),
+    ("nrtSceneTraverseBatchMasked", _F32, [vp, vp, vp, u64, vp, vp], i32),
+    ("nrtSceneTraverseBatchMaskedDevice", _F32, [vp, vp, vp, u64, vp, vp], i32),
+    ("nrtSceneOccludedBatchMasked", _F32, [vp, vp, vp, u64, vp], i32),
+    ("nrtSceneOccludedBatchMaskedDevice", _F32, [vp, vp, vp, u64, vp], i32),
 ]
 # Declared by the header, bound elsewhere: nanort_amd/dist.py sets the signatures of the nrtGroup* calls when a Group is made.
 BOUND_ELSEWHERE = [

@@ -330,6 +330,10 @@ struct SceneTraceArgs {
   uint32_t cand_busy_max;
   const uint32_t *subset;     // non-null: the launch traces rays[subset[s]] for s < n (lists and counts are indexed by s, results by the ray)
   uint32_t any_hit;           // launcher only: the occlusion instantiation (k_scene_trace<.., ANY = true>): flags only, `hits` is never touched
+  // instance visibility masks, read by the MASKED instantiations alone (the scan; a listed ray's list holds visible instances already)
+  uint32_t masked;            // launcher only: the MASKED instantiation of the scan (scan_nodes != 0)
+  const uint32_t *ray_masks;  // one word per ray (indexed like `rays`), or null: every ray carries 0xFFFFFFFF
+  const uint32_t *inst_masks; // one word per instance, by id: an instance exists for a ray iff (inst_mask & ray_mask) != 0
 };
 
 // The single-pass scene walk (scene_kernels.hip k_scene_walk): the top-level tree and the instances' trees walked by the same lane on
@@ -377,6 +381,11 @@ struct SceneWalkArgs {
   unsigned long long *counters; // profiling build only (libnanort_hip_prof.so): 13 loop counters of the launch, or null
   uint32_t any_hit;     // launcher only: the occlusion instantiation (k_scene_walk<.., ANY = true>): flags only, `hits` is never touched, `mask` non-null
   uint32_t num_insts;   // ... which ends a ray at its first hit when the scene has at most 64 instances (every entered box is listed)
+  // instance visibility masks, read by the MASKED instantiations alone
+  uint32_t masked;            // launcher only: k_scene_walk<.., MASKED = true>
+  const uint32_t *ray_masks;  // one word per ray, or null: every ray carries 0xFFFFFFFF
+  const uint32_t *top_masks;  // one word per instance in the order of `open_top` (a leaf reference's `first` indexes both: the word's
+                              // load is issued with the 128-byte line's, not behind it)
 };
 
 // Completion record of a launch slot, in page-locked host memory the device writes to: the last wave of a traversal

@@ -44,9 +44,12 @@ int scene_walk_blocks_per_cu();
 // The listing step in the form the host chose: a scan of every world box (`nodes`, `num_nodes`), or a walk of the top-level tree
 // `top` through its reference-format nodes or its Wide4Node records, the latter with or without pruning beyond a full list.
 // One ray per thread, rays[subset ? subset[i] : i] into slot i of n; at most `cap` entries per ray.
+// `inst_masks` non-null: the MASKED instantiations (instance visibility masks: one word per instance by id; `ray_masks`: one word per
+// ray, indexed like `rays`, or null = every ray 0xFFFFFFFF) — a hidden instance is never listed.
 enum SceneListForm : int { kSceneListScan, kSceneListBvh, kSceneListW4, kSceneListW4Prune };
 hipError_t launch_scene_list(SceneListForm form, const TreeViewF32 &top, const nrt_ray_f32 *rays, uint32_t n, const NodeDev *nodes, uint32_t num_nodes,
-                             uint32_t cap, float *list_t, uint32_t *list_node, uint32_t *count, const uint32_t *subset, hipStream_t s);
+                             uint32_t cap, float *list_t, uint32_t *list_node, uint32_t *count, const uint32_t *subset, const uint32_t *inst_masks,
+                             const uint32_t *ray_masks, hipStream_t s);
 
 // ---- multihit.hip -----------------------------------------------------------------------------------------------------
 template <typename T>

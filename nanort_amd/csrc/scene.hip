@@ -139,6 +139,13 @@ struct nrt_scene {
   std::vector<Inst> insts;
   std::vector<NodeDev> host_nodes;
   bool committed = false;
+  // instance visibility masks (nrtSceneSetNodeMasks): one word per node by id, no part of the top-level tree.  The device holds two
+  // copies — by id (the listing kernels, the scan) and in the order of d_open_top (the walk: the word beside the line it opens) —
+  // rewritten from this one by the next masked query when `masks_dirty` (scene calls are synchronous: nothing is in flight).
+  std::vector<uint32_t> node_masks;  // insts.size() words
+  std::vector<uint32_t> top_order;   // the top-level tree's index array at Commit (empty: no top-level tree)
+  std::vector<uint32_t> top_masks_h; // staging: node_masks in that order
+  bool masks_dirty = true;
   std::vector<std::pair<nrt_ctx *, uint64_t> > mesh_gens; // the distinct mesh contexts and their generations at Commit (the
                                                           // per-instance table caches their device addresses and flags)
   nrt_ctx *top = nullptr;        // top-level BVH over the nodes' world boxes (scenes of two nodes or more)
@@ -148,6 +155,7 @@ struct nrt_scene {
   uint32_t max_inst_depth = 0;   // deepest instance tree: sizes the overflow stack of k_scene_trace
   nrt::DevBuf d_nodes, d_insts, d_rays, d_list_t, d_list_node, d_count, d_best, d_mask, d_spill, d_spill_tmin, d_cursor;
   nrt::DevBuf d_redo, d_redo_count, d_counters, d_open_top, d_meshes;
+  nrt::DevBuf d_node_masks, d_top_masks, d_ray_masks; // the two copies of node_masks; the host forms' staged ray words
   bool walk_meshes_ok = false; // every mesh of the scene has the private layout k_scene_walk steps through (else: the listing path)
   unsigned count_loops = 0; // profiling build only (tunable "count_loops"): the next calls run the counting instantiation of k_scene_walk
   uint32_t *h_redo_count = nullptr; // page-locked: how many rays the single-pass walk left to the listing path
@@ -214,7 +222,8 @@ void nrtSceneDestroy(nrt_scene *s) {
   (void)hipSetDevice(s->device);
   (void)hipStreamSynchronize(s->stream);
   nrt::DevBuf *bufs[] = {&s->d_nodes, &s->d_insts, &s->d_rays, &s->d_list_t, &s->d_list_node, &s->d_count,
-                         &s->d_best,  &s->d_mask,  &s->d_spill, &s->d_spill_tmin, &s->d_cursor, &s->d_redo, &s->d_redo_count, &s->d_counters, &s->d_open_top, &s->d_meshes};
+                         &s->d_best,  &s->d_mask,  &s->d_spill, &s->d_spill_tmin, &s->d_cursor, &s->d_redo, &s->d_redo_count, &s->d_counters, &s->d_open_top, &s->d_meshes,
+                         &s->d_node_masks, &s->d_top_masks, &s->d_ray_masks};
   for (nrt::DevBuf *b : bufs)
     if (b->p) (void)hipFree(b->p);
   if (s->h_redo_count) (void)hipHostFree(s->h_redo_count);
@@ -237,6 +246,8 @@ nrt_status nrtSceneAddNode_f32(nrt_scene *s, nrt_ctx *mesh, const float local_xf
   in.mesh = mesh;
   memcpy(in.local, local_xform, sizeof(in.local));
   s->insts.push_back(in);
+  s->node_masks.push_back(0xFFFFFFFFu); // visible to every non-zero ray word until nrtSceneSetNodeMasks says otherwise
+  s->masks_dirty = true;
   s->committed = false;
   if (node_id_out) *node_id_out = (uint32_t)s->insts.size() - 1;
   return NRT_OK;
@@ -306,6 +317,8 @@ nrt_status nrtSceneCommit(nrt_scene *s) {
   s->use_top = false;
   s->have_top = false;
   s->walk_backoff = 0;
+  s->top_order.clear(); // (Commit keeps the masks themselves; their copy in top-level order follows the new tree)
+  s->masks_dirty = true;
   // ... only where something reads it: the listing kernels of scenes of more than kScanMaxNodes nodes, the single-pass walk from
   // walk_min nodes (or forced, single_pass = 2).  A handful of nodes is scanned: no context, no build, no read-back for them
   // (a tunable that makes the walk eligible later commits the scene again: scene_traverse).
@@ -352,6 +365,7 @@ nrt_status nrtSceneCommit(nrt_scene *s) {
         o.id = e.id;
         o.mesh = mesh_of[order[q]];
       }
+      s->top_order = order;
       SCHK(s, nrt::devbuf_ensure(&s->d_open_top, open.size() * sizeof(nrt::SceneOpen)));
       SCHK(s, hipMemcpy(s->d_open_top.p, open.data(), open.size() * sizeof(nrt::SceneOpen), hipMemcpyHostToDevice));
       std::vector<nrt::SceneMesh> mt(meshes.size());
@@ -381,6 +395,19 @@ nrt_status nrtSceneCommit(nrt_scene *s) {
   s->mesh_gens.clear();
   for (size_t m = 0; m < meshes.size(); m++) s->mesh_gens.push_back(std::make_pair(meshes[m].first, meshes[m].second.tv.generation));
   s->committed = true;
+  return NRT_OK;
+}
+
+// One visibility word per node, in node-id order (include/nanort_hip.h).  Host state only: the next masked query uploads it.
+nrt_status nrtSceneSetNodeMasks(nrt_scene *s, const uint32_t *masks, uint32_t count) {
+  if (!s) return NRT_ERR_INVALID;
+  if (masks && (size_t)count != s->insts.size())
+    return sfail(s, NRT_ERR_INVALID, "nrtSceneSetNodeMasks: %u words for a scene of %zu nodes (one word per node added so far)", count, s->insts.size());
+  if (masks)
+    s->node_masks.assign(masks, masks + count);
+  else
+    s->node_masks.assign(s->insts.size(), 0xFFFFFFFFu);
+  s->masks_dirty = true;
   return NRT_OK;
 }
 
@@ -422,8 +449,11 @@ nrt_status nrtSceneNodeState_f32(nrt_scene *s, uint32_t node_id, float out[64]) 
 // The listing path: one of the listing kernels + k_scene_trace, enqueued on the scene's stream, over the whole batch
 // (`subset` == nullptr) or over the rays named by `subset` (the ones the single-pass walk left over).  `any_hit`: the occlusion
 // instantiation of k_scene_trace — the same lists, flags only, d_hits unused.
+// `masked`: the MASKED instantiations of the listing kernels and of the scan, with `d_ray_masks` (one word per ray of the batch, or
+// null) and the scene's by-id words.
 static nrt_status scene_list_and_trace(nrt_scene *s, const nrt_ray_f32 *d_rays, uint32_t n, const uint32_t *subset,
-                                       nrt_scene_hit_f32 *d_hits, uint8_t *d_mask, bool any_hit) {
+                                       nrt_scene_hit_f32 *d_hits, uint8_t *d_mask, bool any_hit, bool masked = false,
+                                       const uint32_t *d_ray_masks = nullptr) {
   const uint32_t num_nodes = (uint32_t)s->insts.size();
   const uint32_t cap = std::min<uint32_t>(kMaxList, num_nodes);
   SCHK(s, nrt::devbuf_ensure(&s->d_list_t, (size_t)cap * n * sizeof(float)));
@@ -446,7 +476,7 @@ static nrt_status scene_list_and_trace(nrt_scene *s, const nrt_ray_f32 *d_rays, 
                                          : (s->use_top ? nrt::kSceneListBvh : nrt::kSceneListScan);
   if (s->use_top || !fused_scan) // (else: a handful of nodes — k_scene_trace tests every world box itself as it fetches a ray: no listing launch)
     SCHK(s, nrt::launch_scene_list(form, s->top_view, d_rays, n, d_nodes, num_nodes, cap, (float *)s->d_list_t.p, (uint32_t *)s->d_list_node.p,
-                                   (uint32_t *)s->d_count.p, subset, s->stream));
+                                   (uint32_t *)s->d_count.p, subset, masked ? (const uint32_t *)s->d_node_masks.p : nullptr, d_ray_masks, s->stream));
   nrt::SceneTraceArgs a;
   a.scan_nodes = fused_scan ? num_nodes : 0u;
   a.rays = d_rays;
@@ -468,6 +498,9 @@ static nrt_status scene_list_and_trace(nrt_scene *s, const nrt_ray_f32 *d_rays, 
   a.cand_busy_max = s->cand_busy_max;
   a.subset = subset;
   a.any_hit = any_hit ? 1u : 0u;
+  a.masked = (masked && fused_scan) ? 1u : 0u; // (a listed ray's list holds visible instances only: the plain instantiation traces it)
+  a.ray_masks = d_ray_masks;
+  a.inst_masks = (const uint32_t *)s->d_node_masks.p;
   SCHK(s, nrt::launch_scene_trace(a, trace_grid, s->stream));
   return NRT_OK;
 }
@@ -477,15 +510,19 @@ static nrt_status scene_list_and_trace(nrt_scene *s, const nrt_ray_f32 *d_rays, 
 // nodes) and single_pass = 0: the listing path on the whole batch.  The call returns with everything finished (the scene owns
 // the per-ray scratch).  `occluded`: the occlusion query (scene_occluded below) — the same path selection and ray staging with
 // the any-hit kernel instantiations; no record buffer is allocated, written or copied (hits_out is NULL), mask_out is required,
-// and the closest-hit back-off is neither consulted nor updated.
+// and the closest-hit back-off is neither consulted nor updated.  `masked`: the masked queries (nrtScene*BatchMasked*) — the same
+// checks, path selection, back-off and reporting with the MASKED kernel instantiations; `ray_masks` (one word per ray, host or
+// device as the rays; NULL: every ray 0xFFFFFFFF) is staged beside the rays, and the node words are uploaded first if they changed.
 static nrt_status scene_traverse(nrt_scene *s, const nrt_ray_f32 *rays, uint64_t n64, nrt_scene_hit_f32 *hits_out,
-                                 uint8_t *mask_out, bool device, bool occluded = false) {
+                                 uint8_t *mask_out, bool device, bool occluded = false, bool masked = false, const uint32_t *ray_masks = nullptr) {
   if (!s) return NRT_ERR_INVALID;
-  const char *what = occluded ? "nrtSceneOccludedBatch" : "nrtSceneTraverseBatch";
+  const char *what = masked ? (occluded ? "nrtSceneOccludedBatchMasked" : "nrtSceneTraverseBatchMasked") : (occluded ? "nrtSceneOccludedBatch" : "nrtSceneTraverseBatch");
   if (!s->committed) return sfail(s, NRT_ERR_INVALID, "%s: commit the scene first", what);
   if (n64 == 0) return NRT_OK;
   if (!rays || (occluded ? !mask_out : !hits_out)) return sfail(s, NRT_ERR_INVALID, "%s: NULL rays/%s", what, occluded ? "mask" : "hits");
   if (n64 > 0x7FFFFFFFull) return sfail(s, NRT_ERR_INVALID, "%s: too many rays in one call", what);
+  if (masked && device && ((uintptr_t)ray_masks & 3u) != 0)
+    return sfail(s, NRT_ERR_INVALID, "%s: d_ray_masks is not 4-byte aligned", what);
   // the instance table holds device addresses, layout flags and stack depths of the mesh contexts' trees as they were at
   // Commit: a context rebuilt or re-set since then may have moved or re-shaped them — refuse instead of walking stale memory
   for (size_t m = 0; m < s->mesh_gens.size(); m++)
@@ -524,6 +561,27 @@ static nrt_status scene_traverse(nrt_scene *s, const nrt_ray_f32 *rays, uint64_t
   nrt_scene_hit_f32 *d_hits = occluded ? nullptr : (device ? hits_out : (nrt_scene_hit_f32 *)s->d_best.p);
   uint8_t *d_mask = device ? mask_out : (mask_out ? (uint8_t *)s->d_mask.p : nullptr);
   if (!device) SCHK(s, hipMemcpyAsync(s->d_rays.p, rays, (size_t)n * sizeof(nrt_ray_f32), hipMemcpyHostToDevice, s->stream));
+  const uint32_t *d_ray_masks = nullptr;
+  if (masked) {
+    d_ray_masks = ray_masks;
+    if (!device && ray_masks) { // the words travel beside the rays
+      SCHK(s, nrt::devbuf_ensure(&s->d_ray_masks, (size_t)n * sizeof(uint32_t)));
+      SCHK(s, hipMemcpyAsync(s->d_ray_masks.p, ray_masks, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
+      d_ray_masks = (const uint32_t *)s->d_ray_masks.p;
+    }
+    if (s->masks_dirty) { // changed since the last masked query (or the tree's order did): both device copies from the host's
+      const size_t bytes = s->node_masks.size() * sizeof(uint32_t);
+      SCHK(s, nrt::devbuf_ensure(&s->d_node_masks, bytes));
+      SCHK(s, hipMemcpyAsync(s->d_node_masks.p, s->node_masks.data(), bytes, hipMemcpyHostToDevice, s->stream));
+      if (s->top_order.size() == s->node_masks.size()) {
+        s->top_masks_h.resize(s->top_order.size());
+        for (size_t q = 0; q < s->top_order.size(); q++) s->top_masks_h[q] = s->node_masks[s->top_order[q]];
+        SCHK(s, nrt::devbuf_ensure(&s->d_top_masks, bytes));
+        SCHK(s, hipMemcpyAsync(s->d_top_masks.p, s->top_masks_h.data(), bytes, hipMemcpyHostToDevice, s->stream));
+      }
+      s->masks_dirty = false;
+    }
+  }
 
   s->last_redone = 0;
   s->last_path = 0;
@@ -575,8 +633,11 @@ static nrt_status scene_traverse(nrt_scene *s, const nrt_ray_f32 *rays, uint64_t
     w.counters = nullptr;
     w.any_hit = occluded ? 1u : 0u;
     w.num_insts = (uint32_t)s->insts.size();
+    w.masked = masked ? 1u : 0u;
+    w.ray_masks = d_ray_masks;
+    w.top_masks = (const uint32_t *)s->d_top_masks.p;
 #ifdef NRT_PROF
-    if (s->count_loops && !occluded) {
+    if (s->count_loops && !occluded && !masked) {
       SCHK(s, nrt::devbuf_ensure(&s->d_counters, 16 * sizeof(unsigned long long)));
       SCHK(s, hipMemsetAsync(s->d_counters.p, 0, 16 * sizeof(unsigned long long), s->stream));
       w.counters = (unsigned long long *)s->d_counters.p;
@@ -588,11 +649,11 @@ static nrt_status scene_traverse(nrt_scene *s, const nrt_ray_f32 *rays, uint64_t
     s->last_redone = *s->h_redo_count;
     if (!occluded && (uint64_t)*s->h_redo_count * 100u > (uint64_t)n * s->walk_backoff_pct) s->walk_backoff = kWalkBackoff;
     if (*s->h_redo_count) {
-      const nrt_status st = scene_list_and_trace(s, d_rays, *s->h_redo_count, (const uint32_t *)s->d_redo.p, d_hits, d_mask, occluded);
+      const nrt_status st = scene_list_and_trace(s, d_rays, *s->h_redo_count, (const uint32_t *)s->d_redo.p, d_hits, d_mask, occluded, masked, d_ray_masks);
       if (st != NRT_OK) return st;
     }
   } else {
-    const nrt_status st = scene_list_and_trace(s, d_rays, n, nullptr, d_hits, d_mask, occluded);
+    const nrt_status st = scene_list_and_trace(s, d_rays, n, nullptr, d_hits, d_mask, occluded, masked, d_ray_masks);
     if (st != NRT_OK) return st;
   }
   if (!device) {
@@ -627,6 +688,25 @@ nrt_status nrtSceneTraverseBatch_f32(nrt_scene *s, const nrt_ray_f32 *rays, uint
 nrt_status nrtSceneTraverseBatchDevice_f32(nrt_scene *s, const nrt_ray_f32 *d_rays, uint64_t n, nrt_scene_hit_f32 *d_hits_out,
                                            uint8_t *d_mask_out) {
   return scene_traverse(s, d_rays, n, d_hits_out, d_mask_out, true);
+}
+
+// The masked queries: the four calls above with one visibility word per ray (include/nanort_hip.h).
+nrt_status nrtSceneTraverseBatchMasked_f32(nrt_scene *s, const nrt_ray_f32 *rays, const uint32_t *ray_masks, uint64_t n, nrt_scene_hit_f32 *hits_out,
+                                           uint8_t *mask_out) {
+  return scene_traverse(s, rays, n, hits_out, mask_out, false, false, true, ray_masks);
+}
+
+nrt_status nrtSceneTraverseBatchMaskedDevice_f32(nrt_scene *s, const nrt_ray_f32 *d_rays, const uint32_t *d_ray_masks, uint64_t n,
+                                                 nrt_scene_hit_f32 *d_hits_out, uint8_t *d_mask_out) {
+  return scene_traverse(s, d_rays, n, d_hits_out, d_mask_out, true, false, true, d_ray_masks);
+}
+
+nrt_status nrtSceneOccludedBatchMasked_f32(nrt_scene *s, const nrt_ray_f32 *rays, const uint32_t *ray_masks, uint64_t n, uint8_t *mask_out) {
+  return scene_traverse(s, rays, n, nullptr, mask_out, false, true, true, ray_masks);
+}
+
+nrt_status nrtSceneOccludedBatchMaskedDevice_f32(nrt_scene *s, const nrt_ray_f32 *d_rays, const uint32_t *d_ray_masks, uint64_t n, uint8_t *d_mask_out) {
+  return scene_traverse(s, d_rays, n, nullptr, d_mask_out, true, true, true, d_ray_masks);
 }
 
 nrt_status nrtSceneSetTunable(nrt_scene *s, const char *name, int value) {

@@ -108,7 +108,10 @@ __device__ __forceinline__ void scene_local_ray(const float (&inv)[4][W], const 
 // t_world < FLT_MAX.  It writes no record (a.hits is not read).  The one place the forms can differ: the dropped walk's hit is the
 // first accepted, not the nearest, and where world distances overflow or are NaN the two may disagree on t_world < FLT_MAX
 // (include/nanort_hip.h states that limit).
-template <int STACK, bool SCAN, bool ANY = false>
+// MASKED (with SCAN: a listed ray's list comes from a listing kernel, which has applied the words already): instance visibility
+// masks — an instance exists for a ray iff (a.inst_masks[id] & ray word) != 0, so a hidden instance's box is not accepted as
+// entered and never reaches the list.  The ray's word is read with the ray and dies with the scan.
+template <int STACK, bool SCAN, bool ANY = false, bool MASKED = false>
 __global__ __launch_bounds__(kTraverseBlock) void k_scene_trace(const SceneTraceArgs a) {
   typedef float T;
   typedef StackEntry<float> SE;
@@ -156,8 +159,13 @@ __global__ __launch_bounds__(kTraverseBlock) void k_scene_trace(const SceneTrace
           }
           if (SCAN) {
             cnt = 0u;
+            uint32_t rm = 0xFFFFFFFFu;
+            if constexpr (MASKED) rm = a.ray_masks ? a.ray_masks[ri] : 0xFFFFFFFFu;
             for (uint32_t k = 0; k < a.scan_nodes; k++) { // (wave-uniform addresses: the boxes arrive through the scalar cache)
               float t;
+              if constexpr (MASKED) {
+                if ((a.inst_masks[k] & rm) == 0u) continue; // hidden from this ray: it does not exist
+              }
               if (!scene_node_interval(r, a.insts[k].xbmin, a.insts[k].xbmax, t)) continue;
               a.list_t[(size_t)cnt * a.n + i] = t;
               a.list_node[(size_t)cnt * a.n + i] = k;
@@ -311,13 +319,14 @@ __global__ __launch_bounds__(kTraverseBlock) void k_scene_trace(const SceneTrace
   }
 }
 
-static const void *scene_trace_kernel(bool scan, bool any) {
+static const void *scene_trace_kernel(bool scan, bool any, bool masked = false) {
+  if (masked && scan) return any ? (const void *)k_scene_trace<kSceneLdsStack, true, true, true> : (const void *)k_scene_trace<kSceneLdsStack, true, false, true>;
   if (any) return scan ? (const void *)k_scene_trace<kSceneLdsStack, true, true> : (const void *)k_scene_trace<kSceneLdsStack, false, true>;
   return scan ? (const void *)k_scene_trace<kSceneLdsStack, true> : (const void *)k_scene_trace<kSceneLdsStack, false>;
 }
 hipError_t launch_scene_trace(const SceneTraceArgs &args, unsigned grid, hipStream_t s) {
   if (args.n == 0) return hipSuccess;
-  launch_persistent(scene_trace_kernel(args.scan_nodes != 0, args.any_hit != 0), grid, args, s);
+  launch_persistent(scene_trace_kernel(args.scan_nodes != 0, args.any_hit != 0, args.masked != 0), grid, args, s);
   return hipGetLastError();
 }
 int scene_trace_blocks_per_cu() { // (one grid size for both: the fewer)
@@ -370,6 +379,17 @@ int scene_trace_blocks_per_cu() { // (one grid size for both: the fewer)
 //   * shortcut   a scene of at most 64 instances: every entered instance is listed, the first qualifying hit ends the ray with 1.
 // `redo` rays go through the listing path in its ANY form, which is exact.  No record is written (a.hits is not read).  The rule
 // is modelled and tested on the CPU with random visiting orders and random legal skipping (tests/test_scene_occlusion_model.py).
+//
+// MASKED = true: INSTANCE VISIBILITY MASKS (nrtScene*BatchMasked*).  An instance exists for a ray iff (its word & the ray's word)
+// != 0, and the answer is the unmasked one on the scene of the visible instances with their ids kept.  The one change: where an
+// instance's world box is accepted as entered (`entered`, below), the acceptance is ANDed with that test.  A hidden instance is
+// therefore neither opened nor counted — not in `traced` (the at-most-64 certificate), not in the ANY form's bound B, not among
+// its "entered instances met later".  Both arguments above carry over unchanged, because they are the unmasked arguments on the
+// visible sub-scene: the top-level tree only ever prunes (a subtree is skipped by its box and the winner, never by what it holds),
+// so walking the tree of ALL instances and dropping the hidden ones at the leaves visits the visible instances a tree over
+// them alone would let the lane reach, in some order — and the arguments hold for any order.  The `num_insts <= 64` shortcut stays
+// valid: visible <= total.  The ray's word is loaded when the lane claims the ray and kept in a register; an instance's word
+// comes from a.top_masks, in the order of a.open_top, so its load is issued WITH the 128-byte line's, not behind it.
 // ---------------------------------------------------------------------------
 enum : int { T_ENTER = 7, S_END = 8 }; // a top-level leaf was reached: open its instance / the top-level stack ran empty: the ray is finished
 
@@ -394,7 +414,7 @@ do {                                                                            
   state = fin_ ? (in_top ? S_END : S_FIN) : (enter_ ? ((ref_ & kLeafBit) ? W_LEAF : W_TRAV) : W_POP); \
 } while (0)
 
-template <int STACK, bool STATS, bool ANY = false>
+template <int STACK, bool STATS, bool ANY = false, bool MASKED = false>
 __global__ __launch_bounds__(kTraverseBlock, STATS ? 1 : NRT_SCENE_WALK_WAVES) void k_scene_walk(const SceneWalkArgs a) {
   typedef float T;
   typedef StackEntry<float> SE;
@@ -428,6 +448,7 @@ __global__ __launch_bounds__(kTraverseBlock, STATS ? 1 : NRT_SCENE_WALK_WAVES) v
   const LeafTri<float> *tris = nullptr;
   bool exhausted = false;
   uint32_t part = blockIdx.x % a.num_parts, tried = 0u;
+  uint32_t ray_word = 0xFFFFFFFFu; // MASKED: this ray's visibility word
 
   auto world_ray = [&]() { // the lane (re-)enters the top-level tree
     L.org0 = worg[0];
@@ -457,6 +478,7 @@ __global__ __launch_bounds__(kTraverseBlock, STATS ? 1 : NRT_SCENE_WALK_WAVES) v
         if (state == S_DONE && mine < a.n) {
           i = mine;
           const nrt_ray_f32 r = a.rays[i];
+          if constexpr (MASKED) ray_word = a.ray_masks ? a.ray_masks[i] : 0xFFFFFFFFu;
           // tame: ordinary non-zero direction components and a finite origin — entry distances then only grow from a box to a
           // box inside it, which is what skipping top-level SUBTREES rests on.  Any other ray (axis-parallel, say) walks the whole
           // top-level tree it enters (cull_t stays +inf) and skips per instance only, by the instance's own entry distance.
@@ -552,6 +574,8 @@ __global__ __launch_bounds__(kTraverseBlock, STATS ? 1 : NRT_SCENE_WALK_WAVES) v
           NRT_PUSH_IF(lcount > 1u, kLeafBit | packed_leaf_ref(lcount - 1u, lfirst + 1u), -__builtin_huge_valf());
           const SceneOpen &nd = a.open_top[lfirst]; // (everything the opening needs in one 128-byte line: id, world box, matrices, mesh)
           const uint32_t k = nd.id;
+          uint32_t inst_word = 0xFFFFFFFFu;
+          if constexpr (MASKED) inst_word = a.top_masks[lfirst]; // (no address depends on the line: both loads are in flight together)
           const float bx[6] = {nd.xbmin[0], nd.xbmin[1], nd.xbmin[2], nd.xbmax[0], nd.xbmax[1], nd.xbmax[2]};
           const bool s0 = wdir[0] < 0.0f, s1 = wdir[1] < 0.0f, s2 = wdir[2] < 0.0f;
           const float n0 = ((s0 ? bx[3] : bx[0]) - worg[0]) * winv[0], n1 = ((s1 ? bx[4] : bx[1]) - worg[1]) * winv[1],
@@ -583,7 +607,8 @@ __global__ __launch_bounds__(kTraverseBlock, STATS ? 1 : NRT_SCENE_WALK_WAVES) v
           e = (a2 > e) ? a2 : e;
           float f = (b1 < b0) ? b1 : b0;
           f = (b2 < f) ? b2 : f;
-          const bool entered = tmn <= tmx && e <= f;
+          bool entered = tmn <= tmx && e <= f;
+          if constexpr (MASKED) entered = entered && (inst_word & ray_word) != 0u; // hidden from this ray: it does not exist
           bool behind = has_hit && best_t < e && (best_tmin < e || (best_tmin == e && best_id < k)); // ranks behind a nearer hit
           if constexpr (ANY) { // counting mode: nothing is opened any more; an entered box that ranks before the hit instance's counts
             behind = has_hit;
@@ -713,7 +738,11 @@ hipError_t launch_scene_walk(const SceneWalkArgs &args, unsigned grid, hipStream
   }
 #endif
   NRT_RANGE("scene walk launch (k_scene_walk)");
-  if (args.any_hit)
+  if (args.masked && args.any_hit)
+    hipLaunchKernelGGL((k_scene_walk<kSceneWalkLdsStack, false, true, true>), dim3(grid), dim3(kTraverseBlock), 0, s, args);
+  else if (args.masked)
+    hipLaunchKernelGGL((k_scene_walk<kSceneWalkLdsStack, false, false, true>), dim3(grid), dim3(kTraverseBlock), 0, s, args);
+  else if (args.any_hit)
     hipLaunchKernelGGL((k_scene_walk<kSceneWalkLdsStack, false, true>), dim3(grid), dim3(kTraverseBlock), 0, s, args);
   else
     hipLaunchKernelGGL((k_scene_walk<kSceneWalkLdsStack, false>), dim3(grid), dim3(kTraverseBlock), 0, s, args);
@@ -776,17 +805,30 @@ __device__ inline void list_add(ListTail &st, float t, uint32_t k, uint32_t cap,
   }
 }
 
+// MASKED, in all three listing kernels: instance visibility masks (`inst_masks`: one word per instance by id; `ray_masks`: one word
+// per ray, indexed like `rays`, or null = 0xFFFFFFFF).  Wherever an instance's box would be accepted as entered, the acceptance is
+// ANDed with (inst word & ray word) != 0: a hidden instance is never ADDED, so it takes no place among the `cap` nearest and the
+// pruning walk's "full list" is a list of visible entries.  Subtree pruning is untouched: the tree only prunes.
+__device__ __forceinline__ uint32_t list_ray_word(const uint32_t *ray_masks, uint32_t ray) { return ray_masks ? ray_masks[ray] : 0xFFFFFFFFu; }
+
 // list_t / list_node: [kMaxList or num_nodes][n] (entry-major, so lane-consecutive accesses coalesce)
+template <bool MASKED = false>
 __global__ __launch_bounds__(256) void k_scene_list(const nrt_ray_f32 *__restrict__ rays, uint32_t n,
                                                     const NodeDev *__restrict__ nodes, uint32_t num_nodes, uint32_t cap,
                                                     float *__restrict__ list_t, uint32_t *__restrict__ list_node,
-                                                    uint32_t *__restrict__ count, const uint32_t *__restrict__ subset) {
+                                                    uint32_t *__restrict__ count, const uint32_t *__restrict__ subset,
+                                                    const uint32_t *__restrict__ inst_masks, const uint32_t *__restrict__ ray_masks) {
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
   if (i >= n) return;
   const nrt_ray_f32 r = rays[subset ? subset[i] : i]; // (a subset launch lists rays[subset[i]] into slot i of n)
+  uint32_t rm = 0xFFFFFFFFu;
+  if constexpr (MASKED) rm = list_ray_word(ray_masks, subset ? subset[i] : i);
   ListTail st;
   for (uint32_t k = 0; k < num_nodes; k++) {
     float t;
+    if constexpr (MASKED) {
+      if ((inst_masks[k] & rm) == 0u) continue;
+    }
     if (!node_interval(r, nodes[k], t)) continue;
     list_add(st, t, k, cap, list_t, list_node, n, i);
   }
@@ -810,15 +852,19 @@ __device__ inline bool top_box_hit(const nrt_ray_f32 &r, const float inv[3], con
   return tmin <= tmax;
 }
 
+template <bool MASKED = false>
 __global__ __launch_bounds__(256) void k_scene_list_bvh(const nrt_ray_f32 *__restrict__ rays, uint32_t n,
                                                         const nrt_node_f32 *__restrict__ top_nodes,
                                                         const uint32_t *__restrict__ top_indices,
                                                         const NodeDev *__restrict__ nodes, uint32_t cap,
                                                         float *__restrict__ list_t, uint32_t *__restrict__ list_node,
-                                                        uint32_t *__restrict__ count, const uint32_t *__restrict__ subset) {
+                                                        uint32_t *__restrict__ count, const uint32_t *__restrict__ subset,
+                                                        const uint32_t *__restrict__ inst_masks, const uint32_t *__restrict__ ray_masks) {
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
   if (i >= n) return;
   const nrt_ray_f32 r = rays[subset ? subset[i] : i];
+  uint32_t rm = 0xFFFFFFFFu;
+  if constexpr (MASKED) rm = list_ray_word(ray_masks, subset ? subset[i] : i);
   float inv[3];
   int sign[3];
 #pragma unroll
@@ -844,6 +890,9 @@ __global__ __launch_bounds__(256) void k_scene_list_bvh(const nrt_ray_f32 *__res
     for (uint32_t q = 0; q < nd.data[0]; q++) {
       const uint32_t k = top_indices[nd.data[1] + q];
       float t;
+      if constexpr (MASKED) {
+        if ((inst_masks[k] & rm) == 0u) continue;
+      }
       if (!node_interval(r, nodes[k], t)) continue;
       list_add(st, t, k, cap, list_t, list_node, n, i);
     }
@@ -859,17 +908,21 @@ __global__ __launch_bounds__(256) void k_scene_list_bvh(const nrt_ray_f32 *__res
 // no fetch at all: its slot's box IS the instance's world box (the builder's box of the zero-radius cylinder xbmin -> xbmax).
 // PRUNE: keep entry distances on the stack, walk front to back and skip what lies beyond a full list (scenes of many
 // instances, where rays enter more boxes than the list holds; on smaller scenes the bookkeeping costs 5-10 % and buys nothing).
-template <bool PRUNE>
+// (MASKED: the leaf of one instance, listed from its slot's box, has to fetch that instance's word.)
+template <bool PRUNE, bool MASKED = false>
 __global__ __launch_bounds__(256) void k_scene_list_w4(const nrt_ray_f32 *__restrict__ rays, uint32_t n,
                                                        const nrt::Wide4Node<float> *__restrict__ wide4,
                                                        const nrt_node_f32 *__restrict__ top_nodes, uint32_t packed_leaves,
                                                        const uint32_t *__restrict__ top_indices,
                                                        const NodeDev *__restrict__ nodes, uint32_t cap,
                                                        float *__restrict__ list_t, uint32_t *__restrict__ list_node,
-                                                       uint32_t *__restrict__ count, const uint32_t *__restrict__ subset) {
+                                                       uint32_t *__restrict__ count, const uint32_t *__restrict__ subset,
+                                                       const uint32_t *__restrict__ inst_masks, const uint32_t *__restrict__ ray_masks) {
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
   if (i >= n) return;
   const nrt_ray_f32 r = rays[subset ? subset[i] : i];
+  uint32_t rm = 0xFFFFFFFFu;
+  if constexpr (MASKED) rm = list_ray_word(ray_masks, subset ? subset[i] : i);
   float inv[3], pinv[3];
   int sign[3];
   bool tame = PRUNE; // every direction component is an ordinary non-zero number and the origin is finite: entry distances are monotone in the box
@@ -933,6 +986,9 @@ __global__ __launch_bounds__(256) void k_scene_list_w4(const nrt_ray_f32 *__rest
       for (uint32_t q = 0; q < lcount; q++) {
         const uint32_t k = top_indices[lfirst + q];
         float t;
+        if constexpr (MASKED) {
+          if ((inst_masks[k] & rm) == 0u) continue;
+        }
         if (lcount == 1u) {
           if (!nrt::scene_node_interval(r, bmin, bmax, t)) continue;
         } else if (!node_interval(r, nodes[k], t)) {
@@ -966,23 +1022,35 @@ __global__ __launch_bounds__(256) void k_scene_list_w4(const nrt_ray_f32 *__rest
 namespace nrt {
 
 hipError_t launch_scene_list(SceneListForm form, const TreeViewF32 &top, const nrt_ray_f32 *rays, uint32_t n, const NodeDev *nodes, uint32_t num_nodes,
-                             uint32_t cap, float *list_t, uint32_t *list_node, uint32_t *count, const uint32_t *subset, hipStream_t s) {
+                             uint32_t cap, float *list_t, uint32_t *list_node, uint32_t *count, const uint32_t *subset, const uint32_t *inst_masks,
+                             const uint32_t *ray_masks, hipStream_t s) {
   const dim3 grid((n + 255u) / 256u), block(256); // one ray per thread
   const Wide4Node<float> *wide4 = (const Wide4Node<float> *)top.wide4;
+  const bool masked = inst_masks != nullptr; // (the unmasked instantiations read neither array)
+#define NRT_LIST_W4(K) hipLaunchKernelGGL(K, grid, block, 0, s, rays, n, wide4, top.nodes, top.packed_leaves, top.indices, nodes, cap, list_t, list_node, count, subset, inst_masks, ray_masks)
+#define NRT_LIST_BVH(K) hipLaunchKernelGGL(K, grid, block, 0, s, rays, n, top.nodes, top.indices, nodes, cap, list_t, list_node, count, subset, inst_masks, ray_masks)
+#define NRT_LIST_SCAN(K) hipLaunchKernelGGL(K, grid, block, 0, s, rays, n, nodes, num_nodes, cap, list_t, list_node, count, subset, inst_masks, ray_masks)
   switch (form) {
     case kSceneListW4Prune:
-      hipLaunchKernelGGL(k_scene_list_w4<true>, grid, block, 0, s, rays, n, wide4, top.nodes, top.packed_leaves, top.indices, nodes, cap, list_t, list_node, count, subset);
+      if (masked) NRT_LIST_W4((k_scene_list_w4<true, true>));
+      else NRT_LIST_W4((k_scene_list_w4<true, false>));
       break;
     case kSceneListW4:
-      hipLaunchKernelGGL(k_scene_list_w4<false>, grid, block, 0, s, rays, n, wide4, top.nodes, top.packed_leaves, top.indices, nodes, cap, list_t, list_node, count, subset);
+      if (masked) NRT_LIST_W4((k_scene_list_w4<false, true>));
+      else NRT_LIST_W4((k_scene_list_w4<false, false>));
       break;
     case kSceneListBvh:
-      hipLaunchKernelGGL(k_scene_list_bvh, grid, block, 0, s, rays, n, top.nodes, top.indices, nodes, cap, list_t, list_node, count, subset);
+      if (masked) NRT_LIST_BVH(k_scene_list_bvh<true>);
+      else NRT_LIST_BVH(k_scene_list_bvh<false>);
       break;
     case kSceneListScan:
-      hipLaunchKernelGGL(k_scene_list, grid, block, 0, s, rays, n, nodes, num_nodes, cap, list_t, list_node, count, subset);
+      if (masked) NRT_LIST_SCAN(k_scene_list<true>);
+      else NRT_LIST_SCAN(k_scene_list<false>);
       break;
   }
+#undef NRT_LIST_W4
+#undef NRT_LIST_BVH
+#undef NRT_LIST_SCAN
   return hipGetLastError();
 }
 

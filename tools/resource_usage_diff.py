@@ -14,9 +14,13 @@ file to another is found by its mangled name).  `--kernels REGEX` picks the kern
 `k_traverse`).  Prints one markdown row per kernel: VGPRs, SGPRs, scratch bytes per lane, waves per SIMD, LDS bytes per block
 and code bytes (`-` without assembly) of both builds, and whether they are the same.  A kernel whose mangled name exists on
 one side only is paired with one of the same demangled name without its parameter list, and the row says that the name differs.
+A kernel that gained template parameters, all `false` in the instantiation at hand (`k<16, true>` -> `k<16, true, false>`, `k` ->
+`k<false>`: a feature switch added at its off position), is paired the same way.  A kernel that exists in the second build only
+is printed with its figures; `--allow-new` lets such kernels pass.
 
 Exit status 1 when a PLAIN instantiation of k_traverse_wide differs in any figure, or any other kernel changed its waves per SIMD
-or gained scratch, or a kernel has no partner; with `--strict`, when anything differs at all.
+or gained scratch, or a kernel has no partner (`--allow-new`: has none in the second build); with `--strict`, when anything differs
+at all.
 """
 import argparse
 import re
@@ -73,12 +77,27 @@ def short_name(name):
     return re.sub(r"\(.*$", "", name.replace("(anonymous namespace)::", "")).replace("void ", "").replace("nrt::", "")
 
 
+def without_trailing_false(short):
+    """`k<16, false, false>` -> [`k<16, false>`, `k<16>`], `k<false>` -> [`k`]: the names it may have had before template
+    parameters were added at `false`, the longest first."""
+    m = re.match(r"(.*?)<(.*)>$", short)
+    if not m:
+        return []
+    args = [a.strip() for a in m.group(2).split(",")]
+    out = []
+    while args and args[-1] == "false":
+        args.pop()
+        out.append(m.group(1) + ("<" + ", ".join(args) + ">" if args else ""))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("first")
     ap.add_argument("second")
     ap.add_argument("--kernels", default="k_traverse", help="regular expression over the demangled kernel names")
     ap.add_argument("--strict", action="store_true", help="any difference fails")
+    ap.add_argument("--allow-new", action="store_true", help="a kernel of the second build without a partner in the first does not fail")
     o = ap.parse_args()
     a, b = parse(o.first), parse(o.second)
     names = demangle(sorted(set(a) | set(b)))
@@ -91,6 +110,12 @@ def main():
             rows.append((short_name(name), is_plain(name), a[mangled], b[mangled], True))
         else:
             alone.setdefault(short_name(name), {})["a" if mangled in a else "b"] = (a.get(mangled) or b.get(mangled))
+    # a kernel of the first build whose partner gained template parameters at `false`: one row under the new name
+    for short in sorted((k for k, v in alone.items() if "a" not in v), key=len):
+        for old in without_trailing_false(short):
+            if old in alone and "b" not in alone[old]:
+                alone[short]["a"] = alone.pop(old)["a"]
+                break
     for short, sides in alone.items():
         rows.append((short, None, sides.get("a"), sides.get("b"), False))
     bad = 0
@@ -98,8 +123,11 @@ def main():
     print("|---|---|---|---|---|---|---|---|---|")
     for short, plain, x, y, same_name in sorted(rows, key=lambda r: r[0]):
         if x is None or y is None:
-            print("| `%s` | | only in %s | | | | | | no |" % (short, "the second" if x is None else "the first"))
-            bad = 1
+            z = x or y
+            cells = ["%d" % z[k] if z.get(k) is not None else "-" for k in KEYS]
+            print("| `%s` | - | %s | only in %s |" % (short, " | ".join(cells), "the second" if x is None else "the first"))
+            if y is None or not o.allow_new:
+                bad = 1
             continue
         same = all(x.get(k) == y.get(k) for k in KEYS)
         cells = []
