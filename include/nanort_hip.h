@@ -604,7 +604,8 @@ NRT_API nrt_status nrtTraverseBatches_f64(nrt_ctx *ctx, uint32_t num_batches, co
  * launch, asynchronously on `hip_stream`.  nrtOccludedBatchSkip*: mask[i] is the hit flag of the closest-hit form with the same ids.
  * nrtTraverseBatchesSkip*: an array of `num_batches` pointers; the array or any entry of it may be NULL, and a batch with a NULL
  * entry uses options->skip_prim_id; records are exactly those of separate calls (fp32: still one launch, fp64: one after the other).
- * Not covered: multi-hit, nrtTraverseCountDevice, nrtTraverseBatchMulti, nrtGroup*, scenes and the Embree shim take no per-ray ids.
+ * Not covered: multi-hit, nrtTraverseCountDevice, nrtTraverseBatchMulti, nrtGroup* and the Embree shim take no per-ray ids; scenes take
+ * (primitive, node) pairs through nrtSceneQueryBatch* (below).
  * These calls take Closest / Occlusion launches only; ids together with motion times or visibility words: nrtQueryBatch* below. */
 NRT_API nrt_status nrtTraverseBatchSkip_f32(nrt_ctx *ctx, const nrt_ray_f32 *rays, uint64_t num_rays, const nrt_trace_options *options,
                                             const uint32_t *skip_prim_ids, nrt_hit_f32 *hits_out, uint8_t *hit_mask_out);
@@ -1061,7 +1062,7 @@ NRT_API nrt_status nrtSceneOccludedBatchDevice_f32(nrt_scene *scene, const nrt_r
  *
  * The unmasked calls ignore node masks entirely.  Triangle masks of a mesh context (nrtSetPrimMasks) remain ignored inside scenes,
  * by the masked and the unmasked scene calls alike.  Not covered: the Embree shim (its ray.mask stays ignored; rtcSetMask is not
- * offered), nrtGroup*. */
+ * offered), nrtGroup*.  (Per-ray skip ids on scenes: nrtSceneQueryBatch*, below.) */
 NRT_API nrt_status nrtSceneSetNodeMasks(nrt_scene *scene, const uint32_t *masks, uint32_t count);
 NRT_API nrt_status nrtSceneTraverseBatchMasked_f32(nrt_scene *scene, const nrt_ray_f32 *rays, const uint32_t *ray_masks, uint64_t num_rays,
                                                    nrt_scene_hit_f32 *hits_out, uint8_t *hit_mask_out);
@@ -1071,6 +1072,63 @@ NRT_API nrt_status nrtSceneOccludedBatchMasked_f32(nrt_scene *scene, const nrt_r
                                                    uint8_t *mask_out);
 NRT_API nrt_status nrtSceneOccludedBatchMaskedDevice_f32(nrt_scene *scene, const nrt_ray_f32 *d_rays, const uint32_t *d_ray_masks,
                                                          uint64_t num_rays, uint8_t *d_mask_out);
+
+/* ---- one descriptor for the scene queries, with per-ray skip (node, primitive) pairs ---------------------------------------------
+ * An OPT-IN EXTENSION, the scene-level counterpart of nrtQueryBatch* and of per-ray skip_prim_id: a bounce or shadow ray that starts
+ * ON a triangle of an instanced scene names that triangle and leaves it without an epsilon offset.  The scene calls above trace every
+ * instance with the reference's literal local ray on [0, FLT_MAX] and default trace options, so without this about half of the
+ * secondary rays of a path tracer over nrtScene* hit the triangle they start from (min_t acts on the box listing only).
+ *
+ * The descriptor names the kind in `flags` and carries what the kind reads:
+ *     NRT_SCENE_QUERY_OCCLUSION  flags only (nrtSceneOccludedBatch*): mask_out is the output, hits_out is not read;
+ *     NRT_SCENE_QUERY_MASKED     instance visibility masks (nrtScene*BatchMasked*): ray_masks is read (NULL: every ray 0xFFFFFFFF);
+ *     NRT_SCENE_QUERY_SKIP       skip pairs: skip_pairs and skip_stride_bytes are read (skip_pairs == NULL: no ray skips anything).
+ *
+ * The pair.  Two uint32_t, {prim_id, node_id} IN THAT ORDER — the order of the last two fields of nrt_scene_hit_f32 — and ray i's
+ * pair lies at (const char *)skip_pairs + i * skip_stride_bytes.  That layout is chosen so that a bounce wave passes the previous
+ * wave's records as they lie, with no packing pass:
+ *     q.skip_pairs = &hits[0].prim_id;  q.skip_stride_bytes = sizeof(nrt_scene_hit_f32);
+ * A tightly packed array of pairs uses stride 8.
+ *
+ * Contract, on a committed scene: every field of every record is bit-identical to the same query without SKIP, with ONE change — in
+ * the per-node Traverse of node n, the trace options carry skip_prim_id = p for a ray whose pair is (p, n); every other node gets
+ * the default options.  The intersector returns false for that one primitive of that one instance without touching the ray's state.
+ *   1. Nothing else moves: the box listing, the 64 nearest entered boxes, the early cull, the world distance and the
+ *      strictly-nearer rule are those of the calls above.
+ *   2. A pair skips nothing when node_id is 0xFFFFFFFF or >= the node count, or prim_id is 0xFFFFFFFF or >= the node's face count:
+ *      the miss record of a previous wave is a valid "no skip".
+ *   3. Instances that share a mesh context are distinct: (p, n) leaves primitive p of every other node alone.
+ *   4. With MASKED, the visibility rule applies first (the scene of the visible nodes, ids kept), the skip on top of it.
+ *   5. With OCCLUSION, the flags are exactly the closest-hit flags of the same descriptor, within item 2 of the occlusion contract.
+ *   6. Routing: a descriptor without SKIP, or with SKIP and skip_pairs == NULL, IS the corresponding call above
+ *      (nrtSceneTraverseBatch*, nrtSceneOccludedBatch*, their Masked forms): same path, same kernels, same bytes, same
+ *      nrtSceneLastPath / nrtSceneLastRedone.  Path selection and every tunable act on a SKIP query as on the unskipped one; the
+ *      SKIP closest-hit call consults and updates the walk back-off like the unskipped call, the SKIP occlusion call does neither.
+ *   7. Refusals, each NRT_ERR_INVALID with nrtSceneLastError set and nothing written: a NULL scene or descriptor; a wrong
+ *      struct_size, unknown flag bits, a non-zero `reserved`; NULL rays with num_rays > 0; the kind's output missing (hits_out
+ *      without OCCLUSION, mask_out with it); an uncommitted or stale scene; more than 2^31 - 1 rays; with SKIP and a non-NULL
+ *      array, a stride below 8 or not a multiple of 4; in the Device form, a skip_pairs or ray_masks pointer that is not 4-byte
+ *      aligned, and a skip_pairs range that overlaps hits_out or mask_out (the walk re-reads a pair while other rays' records are
+ *      being written).  num_rays == 0 on a committed scene is NRT_OK.
+ * The host form stages the pairs packed to 8 bytes beside the rays; the Device form reads them where they lie, and is synchronous
+ * like every scene call.  Not covered: the Embree shim, nrtGroup*. */
+#define NRT_SCENE_QUERY_OCCLUSION 1u
+#define NRT_SCENE_QUERY_MASKED 2u
+#define NRT_SCENE_QUERY_SKIP 4u
+typedef struct {
+  uint32_t struct_size;        /* sizeof(nrt_scene_query_f32): lets the struct grow */
+  uint32_t flags;              /* NRT_SCENE_QUERY_OCCLUSION | NRT_SCENE_QUERY_MASKED | NRT_SCENE_QUERY_SKIP */
+  const nrt_ray_f32 *rays;
+  uint64_t num_rays;
+  const uint32_t *ray_masks;   /* read with MASKED only; NULL: every ray 0xFFFFFFFF */
+  const void *skip_pairs;      /* read with SKIP only; NULL: no ray skips anything */
+  uint32_t skip_stride_bytes;  /* distance between two rays' pairs; >= 8, a multiple of 4 */
+  uint32_t reserved;           /* 0 */
+  nrt_scene_hit_f32 *hits_out; /* not read with OCCLUSION */
+  uint8_t *mask_out;           /* optional without OCCLUSION, the output with it */
+} nrt_scene_query_f32;         /* 64 bytes */
+NRT_API nrt_status nrtSceneQueryBatch_f32(nrt_scene *scene, const nrt_scene_query_f32 *query);
+NRT_API nrt_status nrtSceneQueryBatchDevice_f32(nrt_scene *scene, const nrt_scene_query_f32 *query);
 
 #ifdef __cplusplus
 }

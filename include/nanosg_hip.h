@@ -125,6 +125,42 @@ class BatchTracer {
     return true;
   }
 
+  // One call for whichever of a visibility word and a skip pair every ray carries (include/nanort_hip.h, nrtSceneQueryBatch_f32).
+  // `ray_masks` (NULL: the query is unmasked) as in TraverseMasked.  `skip_pairs` (NULL: no ray skips anything): ray i's pair
+  // {prim_id, node_id} lies at (const char *)skip_pairs + i * skip_stride_bytes, and that primitive of that node does not exist for
+  // the ray — a bounce ray leaves the triangle it starts on.  The previous wave's compact records serve as they lie
+  // (&records[0].prim_id, sizeof(nrt_scene_hit_f32)); a packed array of pairs uses stride 8.  `occlusion`: only the flags are
+  // computed — hit_out is required, isects is not touched (it may be NULL).
+  template <class IsectT>
+  bool TraverseQuery(const nanort::Ray<float> *rays, size_t num_rays, const uint32_t *ray_masks, const void *skip_pairs, size_t skip_stride_bytes,
+                     bool occlusion, IsectT *isects, unsigned char *hit_out = NULL) {
+    if (!handle_) return false;
+    if (num_rays == 0) return true;
+    std::vector<nrt_scene_hit_f32> hits(occlusion ? 0 : num_rays);
+    std::vector<unsigned char> mask(num_rays);
+    nrt_scene_query_f32 q;
+    q.struct_size = static_cast<uint32_t>(sizeof(q));
+    q.flags = (occlusion ? NRT_SCENE_QUERY_OCCLUSION : 0u) | (ray_masks ? NRT_SCENE_QUERY_MASKED : 0u) | (skip_pairs ? NRT_SCENE_QUERY_SKIP : 0u);
+    q.rays = reinterpret_cast<const nrt_ray_f32 *>(rays);
+    q.num_rays = num_rays;
+    q.ray_masks = ray_masks;
+    q.skip_pairs = skip_pairs;
+    q.skip_stride_bytes = static_cast<uint32_t>(skip_stride_bytes);
+    q.reserved = 0;
+    q.hits_out = occlusion ? NULL : &hits[0];
+    q.mask_out = &mask[0];
+    if (nrtSceneQueryBatch_f32(handle_, &q) != NRT_OK) {
+      error_ = nrtSceneLastError(handle_);
+      return false;
+    }
+    for (size_t i = 0; i < num_rays; i++) {
+      if (hit_out) hit_out[i] = mask[i];
+      if (occlusion || !mask[i]) continue;
+      Finish(rays[i], hits[i], &isects[i]);
+    }
+    return true;
+  }
+
   // For callers that keep their ray waves in HBM: device pointers in and out, compact records {t, u, v, prim_id, node_id}
   // (every record is written: a miss carries t = ray.max_t and ids 0xFFFFFFFF), optional hit flags.  The rest of the
   // reference's Intersection record (P, Ns, Ng) is the shader's business on the device.  Synchronous.

@@ -1128,3 +1128,74 @@ class Scene:
         torch.cuda.current_stream().synchronize()
         self._check(self._L.nrtSceneOccludedBatchMaskedDevice_f32(self._h, d_rays.data_ptr(), d_ray_masks.data_ptr() if d_ray_masks is not None else None,
                                                                   n, d_mask.data_ptr()))
+
+    # -- one descriptor for the scene queries, with per-ray skip pairs (include/nanort_hip.h) ----
+    @staticmethod
+    def _scene_query_flags(ray_masks, skip_pairs, occlusion):
+        return ((capi.NRT_SCENE_QUERY_OCCLUSION if occlusion else 0) | (capi.NRT_SCENE_QUERY_MASKED if ray_masks is not None else 0) |
+                (capi.NRT_SCENE_QUERY_SKIP if skip_pairs is not None else 0))
+
+    @staticmethod
+    def _host_skip_pairs(skip_pairs, n):
+        """(array to keep alive, address of ray 0's pair, stride): an (n, 2) uint32 array {prim_id, node_id}, or the SCENE_HIT_F32
+        records of a previous wave, which are passed as they lie (their last two fields are the pair)."""
+        from .wire import SCENE_HIT_F32
+
+        if skip_pairs is None:
+            return None, None, 0
+        if getattr(skip_pairs, "dtype", None) == SCENE_HIT_F32:
+            a = skip_pairs if skip_pairs.flags["C_CONTIGUOUS"] else np.ascontiguousarray(skip_pairs)
+            assert a.shape == (n,), "one record per ray"
+            return a, a.ctypes.data + SCENE_HIT_F32.fields["prim_id"][1], SCENE_HIT_F32.itemsize
+        a = np.ascontiguousarray(skip_pairs, dtype=np.uint32)
+        assert a.shape == (n, 2), "one {prim_id, node_id} pair per ray"
+        return a, a.ctypes.data, 8
+
+    def QueryBatch(self, rays, ray_masks=None, skip_pairs=None, occlusion=False):
+        """nrtSceneQueryBatch_f32: `TraverseBatch` / `OccludedBatch` (with `ray_masks`: their Masked forms) in which ray i does not
+        see primitive p of node n for its pair skip_pairs[i] = (p, n) — a bounce ray leaves the triangle it starts on.  `skip_pairs`:
+        an (n, 2) uint32 array, or the SCENE_HIT_F32 records of the previous wave (passed strided, without a copy; a miss record skips
+        nothing).  Returns (hits, mask), or with `occlusion` only the flags."""
+        from .wire import RAY_F32, SCENE_HIT_F32
+
+        rays = np.ascontiguousarray(rays, dtype=RAY_F32)
+        n = rays.shape[0]
+        words = self._ray_words(ray_masks, n)
+        keep, pairs, stride = self._host_skip_pairs(skip_pairs, n)
+        hits = None if occlusion else np.zeros((n,), dtype=SCENE_HIT_F32)
+        mask = np.zeros((n,), dtype=np.uint8)
+        q = capi.SceneQuery(ctypes.sizeof(capi.SceneQuery), self._scene_query_flags(ray_masks, skip_pairs, occlusion), rays.ctypes.data, n,
+                            None if words is None else words.ctypes.data, pairs, stride, 0,
+                            None if hits is None else hits.ctypes.data, mask.ctypes.data)
+        self._check(self._L.nrtSceneQueryBatch_f32(self._h, ctypes.addressof(q)))
+        del keep
+        return mask if occlusion else (hits, mask)
+
+    def QueryBatchDevice(self, d_rays, d_hits=None, d_mask=None, ray_masks=None, skip_pairs=None, occlusion=False):
+        """nrtSceneQueryBatchDevice_f32: the same on HBM-resident torch tensors.  `ray_masks`: one 32-bit word per ray.  `skip_pairs`:
+        a tensor of 32-bit words, two per ray (stride 8), or a uint8 tensor holding the previous wave's SCENE_HIT_F32 records, read
+        where they lie (stride 20) — never the tensor this call writes.  With `occlusion` only `d_mask` is written.  Synchronous;
+        waits for torch's current stream first."""
+        import torch
+
+        from .wire import RAY_F32, SCENE_HIT_F32
+
+        n = d_rays.numel() // RAY_F32.itemsize
+        assert d_rays.is_cuda and (d_hits is None or (d_hits.is_cuda and d_hits.numel() * d_hits.element_size() >= n * SCENE_HIT_F32.itemsize))
+        assert d_mask is None or (d_mask.is_cuda and d_mask.numel() >= n)
+        assert ray_masks is None or (ray_masks.is_cuda and ray_masks.numel() * ray_masks.element_size() >= 4 * n)
+        pairs, stride = None, 0
+        if skip_pairs is not None:
+            assert skip_pairs.is_cuda
+            if skip_pairs.element_size() == 1:  # records
+                assert skip_pairs.numel() >= n * SCENE_HIT_F32.itemsize
+                pairs, stride = skip_pairs.data_ptr() + SCENE_HIT_F32.fields["prim_id"][1], SCENE_HIT_F32.itemsize
+            else:
+                assert skip_pairs.element_size() == 4 and skip_pairs.numel() >= 2 * n, "two 32-bit words per ray"
+                pairs, stride = skip_pairs.data_ptr(), 8
+        torch.cuda.current_stream().synchronize()
+        q = capi.SceneQuery(ctypes.sizeof(capi.SceneQuery), self._scene_query_flags(ray_masks, skip_pairs, occlusion), d_rays.data_ptr(), n,
+                            None if ray_masks is None else ray_masks.data_ptr(), pairs, stride, 0,
+                            None if d_hits is None else d_hits.data_ptr(), None if d_mask is None else d_mask.data_ptr())
+        self._check(self._L.nrtSceneQueryBatchDevice_f32(self._h, ctypes.addressof(q)))
+        return n

@@ -47,6 +47,26 @@ class RayQuery(ctypes.Structure):
     ]
 
 
+NRT_SCENE_QUERY_OCCLUSION, NRT_SCENE_QUERY_MASKED, NRT_SCENE_QUERY_SKIP = 1, 2, 4
+
+
+class SceneQuery(ctypes.Structure):
+    """nrt_scene_query_f32: one descriptor for the scene queries.  A skip pair is two uint32 {prim_id, node_id}, ray i's at
+    skip_pairs + i * skip_stride_bytes."""
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32),
+        ("flags", ctypes.c_uint32),
+        ("rays", ctypes.c_void_p),
+        ("num_rays", ctypes.c_uint64),
+        ("ray_masks", ctypes.c_void_p),
+        ("skip_pairs", ctypes.c_void_p),
+        ("skip_stride_bytes", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
+        ("hits_out", ctypes.c_void_p),
+        ("mask_out", ctypes.c_void_p),
+    ]
+
+
 _LIB = None
 
 vp, u32, u64, sz, i32, P = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER
@@ -147,6 +167,9 @@ SIGNATURES = [
     ("nrtSceneTraverseBatchMaskedDevice", _F32, [vp, vp, vp, u64, vp, vp], i32),
     ("nrtSceneOccludedBatchMasked", _F32, [vp, vp, vp, u64, vp], i32),
     ("nrtSceneOccludedBatchMaskedDevice", _F32, [vp, vp, vp, u64, vp], i32),
+    # one descriptor for the scene queries, with per-ray skip pairs (SceneQuery above): scene, descriptor
+    ("nrtSceneQueryBatch", _F32, [vp, vp], i32),
+    ("nrtSceneQueryBatchDevice", _F32, [vp, vp], i32),
 ]
 # Declared by the header, bound elsewhere: nanort_amd/dist.py sets the signatures of the nrtGroup* calls when a Group is made.
 BOUND_ELSEWHERE = [

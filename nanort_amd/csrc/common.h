@@ -334,6 +334,10 @@ struct SceneTraceArgs {
   uint32_t masked;            // launcher only: the MASKED instantiation of the scan (scan_nodes != 0)
   const uint32_t *ray_masks;  // one word per ray (indexed like `rays`), or null: every ray carries 0xFFFFFFFF
   const uint32_t *inst_masks; // one word per instance, by id: an instance exists for a ray iff (inst_mask & ray_mask) != 0
+  // per-ray skip pairs, read by the SKIP instantiations alone
+  uint32_t skip;              // launcher only: the SKIP instantiation (its scan is the MASKED form: a null inst_masks = all-ones words)
+  uint32_t skip_stride;       // bytes between two rays' pairs (>= 8, a multiple of 4)
+  const void *skip_pairs;     // ray r's pair {prim_id, node_id} at skip_pairs + r * skip_stride, indexed like `rays`; never null with `skip`
 };
 
 // The single-pass scene walk (scene_kernels.hip k_scene_walk): the top-level tree and the instances' trees walked by the same lane on
@@ -386,6 +390,10 @@ struct SceneWalkArgs {
   const uint32_t *ray_masks;  // one word per ray, or null: every ray carries 0xFFFFFFFF
   const uint32_t *top_masks;  // one word per instance in the order of `open_top` (a leaf reference's `first` indexes both: the word's
                               // load is issued with the 128-byte line's, not behind it)
+  // per-ray skip pairs, read by the SKIP instantiations alone
+  uint32_t skip;              // launcher only: k_scene_walk<.., MASKED = true, SKIP = true> (a null top_masks = all-ones words)
+  uint32_t skip_stride;       // bytes between two rays' pairs (>= 8, a multiple of 4)
+  const void *skip_pairs;     // ray r's pair {prim_id, node_id} at skip_pairs + r * skip_stride; never null with `skip`
 };
 
 // Completion record of a launch slot, in page-locked host memory the device writes to: the last wave of a traversal

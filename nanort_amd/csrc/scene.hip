@@ -156,6 +156,8 @@ struct nrt_scene {
   nrt::DevBuf d_nodes, d_insts, d_rays, d_list_t, d_list_node, d_count, d_best, d_mask, d_spill, d_spill_tmin, d_cursor;
   nrt::DevBuf d_redo, d_redo_count, d_counters, d_open_top, d_meshes;
   nrt::DevBuf d_node_masks, d_top_masks, d_ray_masks; // the two copies of node_masks; the host forms' staged ray words
+  nrt::DevBuf d_skip_pairs;               // the host form's staged skip pairs (nrtSceneQueryBatch_f32), packed to 8 bytes
+  std::vector<uint32_t> skip_pairs_h;     // ... and where they are packed (alive until the call's last synchronize)
   bool walk_meshes_ok = false; // every mesh of the scene has the private layout k_scene_walk steps through (else: the listing path)
   unsigned count_loops = 0; // profiling build only (tunable "count_loops"): the next calls run the counting instantiation of k_scene_walk
   uint32_t *h_redo_count = nullptr; // page-locked: how many rays the single-pass walk left to the listing path
@@ -223,7 +225,7 @@ void nrtSceneDestroy(nrt_scene *s) {
   (void)hipStreamSynchronize(s->stream);
   nrt::DevBuf *bufs[] = {&s->d_nodes, &s->d_insts, &s->d_rays, &s->d_list_t, &s->d_list_node, &s->d_count,
                          &s->d_best,  &s->d_mask,  &s->d_spill, &s->d_spill_tmin, &s->d_cursor, &s->d_redo, &s->d_redo_count, &s->d_counters, &s->d_open_top, &s->d_meshes,
-                         &s->d_node_masks, &s->d_top_masks, &s->d_ray_masks};
+                         &s->d_node_masks, &s->d_top_masks, &s->d_ray_masks, &s->d_skip_pairs};
   for (nrt::DevBuf *b : bufs)
     if (b->p) (void)hipFree(b->p);
   if (s->h_redo_count) (void)hipHostFree(s->h_redo_count);
@@ -451,9 +453,11 @@ nrt_status nrtSceneNodeState_f32(nrt_scene *s, uint32_t node_id, float out[64]) 
 // instantiation of k_scene_trace — the same lists, flags only, d_hits unused.
 // `masked`: the MASKED instantiations of the listing kernels and of the scan, with `d_ray_masks` (one word per ray of the batch, or
 // null) and the scene's by-id words.
+// `d_skip_pairs` non-null: the SKIP instantiations of k_scene_trace (the listing kernels test no primitive), pairs `skip_stride` bytes
+// apart and indexed by the ray, like `d_ray_masks`.
 static nrt_status scene_list_and_trace(nrt_scene *s, const nrt_ray_f32 *d_rays, uint32_t n, const uint32_t *subset,
                                        nrt_scene_hit_f32 *d_hits, uint8_t *d_mask, bool any_hit, bool masked = false,
-                                       const uint32_t *d_ray_masks = nullptr) {
+                                       const uint32_t *d_ray_masks = nullptr, const void *d_skip_pairs = nullptr, uint32_t skip_stride = 0) {
   const uint32_t num_nodes = (uint32_t)s->insts.size();
   const uint32_t cap = std::min<uint32_t>(kMaxList, num_nodes);
   SCHK(s, nrt::devbuf_ensure(&s->d_list_t, (size_t)cap * n * sizeof(float)));
@@ -501,6 +505,10 @@ static nrt_status scene_list_and_trace(nrt_scene *s, const nrt_ray_f32 *d_rays, 
   a.masked = (masked && fused_scan) ? 1u : 0u; // (a listed ray's list holds visible instances only: the plain instantiation traces it)
   a.ray_masks = d_ray_masks;
   a.inst_masks = (const uint32_t *)s->d_node_masks.p;
+  a.skip = d_skip_pairs ? 1u : 0u;
+  a.skip_stride = skip_stride;
+  a.skip_pairs = d_skip_pairs;
+  if (d_skip_pairs && !masked) a.inst_masks = nullptr; // (the SKIP scan is the MASKED form: null = all-ones node words, and d_ray_masks is null)
   SCHK(s, nrt::launch_scene_trace(a, trace_grid, s->stream));
   return NRT_OK;
 }
@@ -513,16 +521,34 @@ static nrt_status scene_list_and_trace(nrt_scene *s, const nrt_ray_f32 *d_rays, 
 // and the closest-hit back-off is neither consulted nor updated.  `masked`: the masked queries (nrtScene*BatchMasked*) — the same
 // checks, path selection, back-off and reporting with the MASKED kernel instantiations; `ray_masks` (one word per ray, host or
 // device as the rays; NULL: every ray 0xFFFFFFFF) is staged beside the rays, and the node words are uploaded first if they changed.
+// `skip_pairs` non-null (nrtSceneQueryBatch* with SKIP): per-ray skip pairs `skip_stride` bytes apart, host or device as the rays —
+// the same checks, path selection, back-off and reporting with the SKIP kernel instantiations; the host form stages the pairs packed
+// to 8 bytes beside the rays.  `query`: the call is nrtSceneQueryBatch* (the name in messages).
 static nrt_status scene_traverse(nrt_scene *s, const nrt_ray_f32 *rays, uint64_t n64, nrt_scene_hit_f32 *hits_out,
-                                 uint8_t *mask_out, bool device, bool occluded = false, bool masked = false, const uint32_t *ray_masks = nullptr) {
+                                 uint8_t *mask_out, bool device, bool occluded = false, bool masked = false, const uint32_t *ray_masks = nullptr,
+                                 const void *skip_pairs = nullptr, uint32_t skip_stride = 0, bool query = false) {
   if (!s) return NRT_ERR_INVALID;
-  const char *what = masked ? (occluded ? "nrtSceneOccludedBatchMasked" : "nrtSceneTraverseBatchMasked") : (occluded ? "nrtSceneOccludedBatch" : "nrtSceneTraverseBatch");
+  const char *what = query ? (device ? "nrtSceneQueryBatchDevice" : "nrtSceneQueryBatch") : masked ? (occluded ? "nrtSceneOccludedBatchMasked" : "nrtSceneTraverseBatchMasked") : (occluded ? "nrtSceneOccludedBatch" : "nrtSceneTraverseBatch");
   if (!s->committed) return sfail(s, NRT_ERR_INVALID, "%s: commit the scene first", what);
   if (n64 == 0) return NRT_OK;
   if (!rays || (occluded ? !mask_out : !hits_out)) return sfail(s, NRT_ERR_INVALID, "%s: NULL rays/%s", what, occluded ? "mask" : "hits");
   if (n64 > 0x7FFFFFFFull) return sfail(s, NRT_ERR_INVALID, "%s: too many rays in one call", what);
   if (masked && device && ((uintptr_t)ray_masks & 3u) != 0)
     return sfail(s, NRT_ERR_INVALID, "%s: d_ray_masks is not 4-byte aligned", what);
+  if (skip_pairs) {
+    if (skip_stride < 8u || (skip_stride & 3u) != 0)
+      return sfail(s, NRT_ERR_INVALID, "%s: skip_stride_bytes = %u (a pair is 8 bytes: at least 8, and a multiple of 4)", what, skip_stride);
+    if (device) {
+      if (((uintptr_t)skip_pairs & 3u) != 0) return sfail(s, NRT_ERR_INVALID, "%s: skip_pairs is not 4-byte aligned", what);
+      // the walk re-reads a pair while other rays' records are being written
+      const uintptr_t p0 = (uintptr_t)skip_pairs, p1 = p0 + (uintptr_t)(n64 - 1) * skip_stride + 8u;
+      const uintptr_t h0 = (uintptr_t)hits_out, h1 = h0 + (uintptr_t)n64 * sizeof(nrt_scene_hit_f32);
+      const uintptr_t m0 = (uintptr_t)mask_out, m1 = m0 + (uintptr_t)n64;
+      if ((!occluded && p0 < h1 && h0 < p1) || (mask_out && p0 < m1 && m0 < p1))
+        return sfail(s, NRT_ERR_INVALID, "%s: skip_pairs overlaps %s (pass the PREVIOUS wave's records, not the ones being written)", what,
+                     (!occluded && p0 < h1 && h0 < p1) ? "hits_out" : "mask_out");
+    }
+  }
   // the instance table holds device addresses, layout flags and stack depths of the mesh contexts' trees as they were at
   // Commit: a context rebuilt or re-set since then may have moved or re-shaped them — refuse instead of walking stale memory
   for (size_t m = 0; m < s->mesh_gens.size(); m++)
@@ -569,6 +595,18 @@ static nrt_status scene_traverse(nrt_scene *s, const nrt_ray_f32 *rays, uint64_t
       SCHK(s, hipMemcpyAsync(s->d_ray_masks.p, ray_masks, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
       d_ray_masks = (const uint32_t *)s->d_ray_masks.p;
     }
+  }
+  const void *d_skip_pairs = skip_pairs;
+  uint32_t d_skip_stride = skip_stride;
+  if (skip_pairs && !device) { // the pairs travel beside the rays, packed to 8 bytes
+    s->skip_pairs_h.resize((size_t)n * 2u);
+    for (uint32_t r = 0; r < n; r++) memcpy(&s->skip_pairs_h[(size_t)r * 2u], (const char *)skip_pairs + (size_t)r * skip_stride, 8);
+    SCHK(s, nrt::devbuf_ensure(&s->d_skip_pairs, (size_t)n * 8u));
+    SCHK(s, hipMemcpyAsync(s->d_skip_pairs.p, s->skip_pairs_h.data(), (size_t)n * 8u, hipMemcpyHostToDevice, s->stream));
+    d_skip_pairs = s->d_skip_pairs.p;
+    d_skip_stride = 8u;
+  }
+  if (masked) {
     if (s->masks_dirty) { // changed since the last masked query (or the tree's order did): both device copies from the host's
       const size_t bytes = s->node_masks.size() * sizeof(uint32_t);
       SCHK(s, nrt::devbuf_ensure(&s->d_node_masks, bytes));
@@ -636,8 +674,12 @@ static nrt_status scene_traverse(nrt_scene *s, const nrt_ray_f32 *rays, uint64_t
     w.masked = masked ? 1u : 0u;
     w.ray_masks = d_ray_masks;
     w.top_masks = (const uint32_t *)s->d_top_masks.p;
+    w.skip = d_skip_pairs ? 1u : 0u;
+    w.skip_stride = d_skip_stride;
+    w.skip_pairs = d_skip_pairs;
+    if (d_skip_pairs && !masked) w.top_masks = nullptr; // (the SKIP walk is the MASKED form: null = all-ones node words, and d_ray_masks is null)
 #ifdef NRT_PROF
-    if (s->count_loops && !occluded && !masked) {
+    if (s->count_loops && !occluded && !masked && !d_skip_pairs) {
       SCHK(s, nrt::devbuf_ensure(&s->d_counters, 16 * sizeof(unsigned long long)));
       SCHK(s, hipMemsetAsync(s->d_counters.p, 0, 16 * sizeof(unsigned long long), s->stream));
       w.counters = (unsigned long long *)s->d_counters.p;
@@ -649,11 +691,11 @@ static nrt_status scene_traverse(nrt_scene *s, const nrt_ray_f32 *rays, uint64_t
     s->last_redone = *s->h_redo_count;
     if (!occluded && (uint64_t)*s->h_redo_count * 100u > (uint64_t)n * s->walk_backoff_pct) s->walk_backoff = kWalkBackoff;
     if (*s->h_redo_count) {
-      const nrt_status st = scene_list_and_trace(s, d_rays, *s->h_redo_count, (const uint32_t *)s->d_redo.p, d_hits, d_mask, occluded, masked, d_ray_masks);
+      const nrt_status st = scene_list_and_trace(s, d_rays, *s->h_redo_count, (const uint32_t *)s->d_redo.p, d_hits, d_mask, occluded, masked, d_ray_masks, d_skip_pairs, d_skip_stride);
       if (st != NRT_OK) return st;
     }
   } else {
-    const nrt_status st = scene_list_and_trace(s, d_rays, n, nullptr, d_hits, d_mask, occluded, masked, d_ray_masks);
+    const nrt_status st = scene_list_and_trace(s, d_rays, n, nullptr, d_hits, d_mask, occluded, masked, d_ray_masks, d_skip_pairs, d_skip_stride);
     if (st != NRT_OK) return st;
   }
   if (!device) {
@@ -708,6 +750,27 @@ nrt_status nrtSceneOccludedBatchMasked_f32(nrt_scene *s, const nrt_ray_f32 *rays
 nrt_status nrtSceneOccludedBatchMaskedDevice_f32(nrt_scene *s, const nrt_ray_f32 *d_rays, const uint32_t *d_ray_masks, uint64_t n, uint8_t *d_mask_out) {
   return scene_traverse(s, d_rays, n, nullptr, d_mask_out, true, true, true, d_ray_masks);
 }
+
+// One descriptor for the scene queries (include/nanort_hip.h).  Without SKIP, or with SKIP and no pair array, the descriptor IS one of
+// the eight calls above: the same arguments reach scene_traverse.  The unmasked kinds do not read ray_masks, the OCCLUSION kinds do not
+// read hits_out.
+static nrt_status scene_query(nrt_scene *s, const nrt_scene_query_f32 *q, bool device) {
+  const char *what = device ? "nrtSceneQueryBatchDevice" : "nrtSceneQueryBatch";
+  if (!s) return sfail(nullptr, NRT_ERR_INVALID, "%s: scene == NULL", what);
+  if (!q) return sfail(s, NRT_ERR_INVALID, "%s: descriptor == NULL", what);
+  if (q->struct_size != sizeof(nrt_scene_query_f32))
+    return sfail(s, NRT_ERR_INVALID, "%s: struct_size = %u, this library's nrt_scene_query_f32 has %zu bytes", what, q->struct_size, sizeof(nrt_scene_query_f32));
+  if (q->flags & ~(uint32_t)(NRT_SCENE_QUERY_OCCLUSION | NRT_SCENE_QUERY_MASKED | NRT_SCENE_QUERY_SKIP))
+    return sfail(s, NRT_ERR_INVALID, "%s: unknown flag bits 0x%x", what, q->flags);
+  if (q->reserved != 0) return sfail(s, NRT_ERR_INVALID, "%s: reserved = %u (must be 0)", what, q->reserved);
+  const bool occluded = (q->flags & NRT_SCENE_QUERY_OCCLUSION) != 0, masked = (q->flags & NRT_SCENE_QUERY_MASKED) != 0;
+  const void *pairs = (q->flags & NRT_SCENE_QUERY_SKIP) ? q->skip_pairs : nullptr;
+  return scene_traverse(s, q->rays, q->num_rays, occluded ? nullptr : q->hits_out, q->mask_out, device, occluded, masked,
+                        masked ? q->ray_masks : nullptr, pairs, pairs ? q->skip_stride_bytes : 0u, true);
+}
+
+nrt_status nrtSceneQueryBatch_f32(nrt_scene *s, const nrt_scene_query_f32 *q) { return scene_query(s, q, false); }
+nrt_status nrtSceneQueryBatchDevice_f32(nrt_scene *s, const nrt_scene_query_f32 *q) { return scene_query(s, q, true); }
 
 nrt_status nrtSceneSetTunable(nrt_scene *s, const char *name, int value) {
   if (!s || !name) return NRT_ERR_INVALID;

@@ -96,6 +96,17 @@ __device__ __forceinline__ void scene_local_ray(const float (&inv)[4][W], const 
   lane_init<float>(L, lr);
 }
 
+// SKIP (both tracing kernels): the skip id a lane tests a leaf of instance `inst` with — its ray's pair {prim_id, node_id} at
+// pairs + rid * stride names ONE primitive of ONE instance, so the id is the pair's primitive when the open instance is the pair's node
+// and kInvalid (rejects nothing) otherwise.  The pair lives nowhere: it is re-read at every leaf, so a refilled lane, whose rid is
+// new, has its new ray's pair, and the load is issued before the leaf's records and independent of them.  A pair that names no
+// primitive of the scene (either id 0xFFFFFFFF or out of range) needs no test of its own: no instance and no record carries such an id.
+__device__ __forceinline__ uint32_t scene_skip_id(const void *pairs, uint32_t stride, uint32_t rid, uint32_t inst) {
+  const uint32_t *p = (const uint32_t *)((const char *)pairs + (size_t)rid * stride);
+  const uint32_t prim = p[0], node = p[1];
+  return node == inst ? prim : kInvalid;
+}
+
 // SCAN: a scene of a handful of instances (a.scan_nodes of them): the lane lists the instances its ray enters ITSELF when it fetches
 // the ray — every world box tested in id order, exactly what the listing kernel of such scenes did in a launch of its own
 // (k_scene_list) — into its own slots of the list arrays, which it alone reads back: one launch per batch, no second
@@ -111,7 +122,10 @@ __device__ __forceinline__ void scene_local_ray(const float (&inv)[4][W], const 
 // MASKED (with SCAN: a listed ray's list comes from a listing kernel, which has applied the words already): instance visibility
 // masks — an instance exists for a ray iff (a.inst_masks[id] & ray word) != 0, so a hidden instance's box is not accepted as
 // entered and never reaches the list.  The ray's word is read with the ray and dies with the scan.
-template <int STACK, bool SCAN, bool ANY = false, bool MASKED = false>
+// SKIP: per-ray skip pairs (nrtSceneQueryBatch*) — the leaf steps use the rejecting form of the triangle test with
+// scene_skip_id's id and the range [0, 0xFFFFFFFF), which holds every primitive; nothing else moves.  The scan of a SKIP query always
+// runs as the MASKED form, with a null a.inst_masks standing for all-ones words (the bytes of the unmasked scan, §3.14 item 3).
+template <int STACK, bool SCAN, bool ANY = false, bool MASKED = false, bool SKIP = false>
 __global__ __launch_bounds__(kTraverseBlock) void k_scene_trace(const SceneTraceArgs a) {
   typedef float T;
   typedef StackEntry<float> SE;
@@ -164,7 +178,8 @@ __global__ __launch_bounds__(kTraverseBlock) void k_scene_trace(const SceneTrace
             for (uint32_t k = 0; k < a.scan_nodes; k++) { // (wave-uniform addresses: the boxes arrive through the scalar cache)
               float t;
               if constexpr (MASKED) {
-                if ((a.inst_masks[k] & rm) == 0u) continue; // hidden from this ray: it does not exist
+                const uint32_t iw = (SKIP && a.inst_masks == nullptr) ? 0xFFFFFFFFu : a.inst_masks[k];
+                if ((iw & rm) == 0u) continue; // hidden from this ray: it does not exist
               }
               if (!scene_node_interval(r, a.insts[k].xbmin, a.insts[k].xbmax, t)) continue;
               a.list_t[(size_t)cnt * a.n + i] = t;
@@ -302,14 +317,18 @@ __global__ __launch_bounds__(kTraverseBlock) void k_scene_trace(const SceneTrace
     // ---- phase 2: leaves -----------------------------------------------------------------------------------------
     if (__ballot(state == W_LEAF) != 0ull) {
       uint32_t lcnt = 0, first = 0;
+      uint32_t skip = kInvalid;
+      if constexpr (SKIP) {
+        if (state == W_LEAF) skip = scene_skip_id(a.skip_pairs, a.skip_stride, ri, inst);
+      }
       if (state == W_LEAF) leaf_span(packed, nodes, cur, lcnt, first);
       for (uint32_t k = 0; __ballot(k < lcnt) != 0ull; k += 2u) { // two records per trip, as in k_traverse_wide
         if (k < lcnt) { // (divergent on purpose: the lanes' record arrays differ)
           const bool two = k + 1u < lcnt;
           const LeafTri<float> t0 = load_global_record(tris + first + k);
           const LeafTri<float> t1 = load_global_record(tris + first + (two ? k + 1u : k));
-          tri_test<float, true>(L, t0, true, 0u, 0u, 0u, false); // default trace options (nanosg.h:817)
-          tri_test<float, true>(L, t1, two, 0u, 0u, 0u, false);
+          tri_test<float, !SKIP>(L, t0, true, 0u, 0xFFFFFFFFu, skip, false); // default trace options (nanosg.h:817); SKIP: but for skip_prim_id
+          tri_test<float, !SKIP>(L, t1, two, 0u, 0xFFFFFFFFu, skip, false);
         }
       }
       // occlusion query: any accepted primitive settles this instance — drop what is left of its stack (as k_traverse_wide does)
@@ -319,14 +338,16 @@ __global__ __launch_bounds__(kTraverseBlock) void k_scene_trace(const SceneTrace
   }
 }
 
-static const void *scene_trace_kernel(bool scan, bool any, bool masked = false) {
+static const void *scene_trace_kernel(bool scan, bool any, bool masked = false, bool skip = false) {
+  if (skip && scan) return any ? (const void *)k_scene_trace<kSceneLdsStack, true, true, true, true> : (const void *)k_scene_trace<kSceneLdsStack, true, false, true, true>;
+  if (skip) return any ? (const void *)k_scene_trace<kSceneLdsStack, false, true, false, true> : (const void *)k_scene_trace<kSceneLdsStack, false, false, false, true>;
   if (masked && scan) return any ? (const void *)k_scene_trace<kSceneLdsStack, true, true, true> : (const void *)k_scene_trace<kSceneLdsStack, true, false, true>;
   if (any) return scan ? (const void *)k_scene_trace<kSceneLdsStack, true, true> : (const void *)k_scene_trace<kSceneLdsStack, false, true>;
   return scan ? (const void *)k_scene_trace<kSceneLdsStack, true> : (const void *)k_scene_trace<kSceneLdsStack, false>;
 }
 hipError_t launch_scene_trace(const SceneTraceArgs &args, unsigned grid, hipStream_t s) {
   if (args.n == 0) return hipSuccess;
-  launch_persistent(scene_trace_kernel(args.scan_nodes != 0, args.any_hit != 0, args.masked != 0), grid, args, s);
+  launch_persistent(scene_trace_kernel(args.scan_nodes != 0, args.any_hit != 0, args.masked != 0, args.skip != 0), grid, args, s);
   return hipGetLastError();
 }
 int scene_trace_blocks_per_cu() { // (one grid size for both: the fewer)
@@ -390,6 +411,12 @@ int scene_trace_blocks_per_cu() { // (one grid size for both: the fewer)
 // them alone would let the lane reach, in some order — and the arguments hold for any order.  The `num_insts <= 64` shortcut stays
 // valid: visible <= total.  The ray's word is loaded when the lane claims the ray and kept in a register; an instance's word
 // comes from a.top_masks, in the order of a.open_top, so its load is issued WITH the 128-byte line's, not behind it.
+//
+// SKIP = true: PER-RAY SKIP PAIRS (nrtSceneQueryBatch*).  The leaf phase tests with scene_skip_id's id (the lane keeps
+// the open instance's id for the record already; leaf_items_one_trip fetches the OWNER's id across the wave) in the rejecting form of
+// the triangle test over the range [0, 0xFFFFFFFF).  The intersector then returns false for that one primitive of that one instance
+// without touching the ray's state, which is all the contract changes: certificate, cull and hand-over argue about hits that WERE
+// accepted and hold as they are.  Only MASKED forms exist with SKIP; a null a.top_masks stands for all-ones words.
 // ---------------------------------------------------------------------------
 enum : int { T_ENTER = 7, S_END = 8 }; // a top-level leaf was reached: open its instance / the top-level stack ran empty: the ray is finished
 
@@ -414,7 +441,7 @@ do {                                                                            
   state = fin_ ? (in_top ? S_END : S_FIN) : (enter_ ? ((ref_ & kLeafBit) ? W_LEAF : W_TRAV) : W_POP); \
 } while (0)
 
-template <int STACK, bool STATS, bool ANY = false, bool MASKED = false>
+template <int STACK, bool STATS, bool ANY = false, bool MASKED = false, bool SKIP = false>
 __global__ __launch_bounds__(kTraverseBlock, STATS ? 1 : NRT_SCENE_WALK_WAVES) void k_scene_walk(const SceneWalkArgs a) {
   typedef float T;
   typedef StackEntry<float> SE;
@@ -575,7 +602,7 @@ __global__ __launch_bounds__(kTraverseBlock, STATS ? 1 : NRT_SCENE_WALK_WAVES) v
           const SceneOpen &nd = a.open_top[lfirst]; // (everything the opening needs in one 128-byte line: id, world box, matrices, mesh)
           const uint32_t k = nd.id;
           uint32_t inst_word = 0xFFFFFFFFu;
-          if constexpr (MASKED) inst_word = a.top_masks[lfirst]; // (no address depends on the line: both loads are in flight together)
+          if constexpr (MASKED) inst_word = (SKIP && a.top_masks == nullptr) ? 0xFFFFFFFFu : a.top_masks[lfirst]; // (no address depends on the line: both loads are in flight together)
           const float bx[6] = {nd.xbmin[0], nd.xbmin[1], nd.xbmin[2], nd.xbmax[0], nd.xbmax[1], nd.xbmax[2]};
           const bool s0 = wdir[0] < 0.0f, s1 = wdir[1] < 0.0f, s2 = wdir[2] < 0.0f;
           const float n0 = ((s0 ? bx[3] : bx[0]) - worg[0]) * winv[0], n1 = ((s1 ? bx[4] : bx[1]) - worg[1]) * winv[1],
@@ -696,13 +723,17 @@ __global__ __launch_bounds__(kTraverseBlock, STATS ? 1 : NRT_SCENE_WALK_WAVES) v
     if (STATS) st[11] += c2_ - c1_;
     if (__ballot(state == W_LEAF) != 0ull) {
       uint32_t lcnt = 0, first = 0;
+      uint32_t skip = kInvalid;
+      if constexpr (SKIP) {
+        if (state == W_LEAF) skip = scene_skip_id(a.skip_pairs, a.skip_stride, i, inst);
+      }
       if (state == W_LEAF) { // (packed leaf references: scene.hip checks)
         lcnt = packed_leaf_count(cur);
         first = packed_leaf_first(cur);
       }
       // (few lanes wait at a leaf in this kernel — 10 of 64 on the instanced scenes: their records nearly always fit one trip)
       const bool items_done_ = !STATS && a.leaf_items != 0u &&
-                               leaf_items_one_trip<true, const LeafTri<float> *>(L, lcnt, nullptr, tris + first, lane, s_item_owner[tid / kWave], s_item_rec[tid / kWave], 0u, 0u, 0u, false);
+                               leaf_items_one_trip<!SKIP, const LeafTri<float> *>(L, lcnt, nullptr, tris + first, lane, s_item_owner[tid / kWave], s_item_rec[tid / kWave], 0u, 0xFFFFFFFFu, skip, false);
       if (!items_done_)
       for (uint32_t k = 0; __ballot(k < lcnt) != 0ull; k += 2u) { // (k_scene_trace's loop, with the counters: as ONE function it costs this kernel two registers)
         if (STATS) {
@@ -713,8 +744,8 @@ __global__ __launch_bounds__(kTraverseBlock, STATS ? 1 : NRT_SCENE_WALK_WAVES) v
           const bool two = k + 1u < lcnt;
           const LeafTri<float> t0 = load_global_record(tris + first + k);
           const LeafTri<float> t1 = load_global_record(tris + first + (two ? k + 1u : k));
-          tri_test<float, true>(L, t0, true, 0u, 0u, 0u, false); // default trace options (nanosg.h:817)
-          tri_test<float, true>(L, t1, two, 0u, 0u, 0u, false);
+          tri_test<float, !SKIP>(L, t0, true, 0u, 0xFFFFFFFFu, skip, false); // default trace options (nanosg.h:817); SKIP: but for skip_prim_id
+          tri_test<float, !SKIP>(L, t1, two, 0u, 0xFFFFFFFFu, skip, false);
         }
       }
       // occlusion query: any accepted primitive settles this instance — drop what is left of ITS part of the stack
@@ -738,7 +769,11 @@ hipError_t launch_scene_walk(const SceneWalkArgs &args, unsigned grid, hipStream
   }
 #endif
   NRT_RANGE("scene walk launch (k_scene_walk)");
-  if (args.masked && args.any_hit)
+  if (args.skip && args.any_hit)
+    hipLaunchKernelGGL((k_scene_walk<kSceneWalkLdsStack, false, true, true, true>), dim3(grid), dim3(kTraverseBlock), 0, s, args);
+  else if (args.skip)
+    hipLaunchKernelGGL((k_scene_walk<kSceneWalkLdsStack, false, false, true, true>), dim3(grid), dim3(kTraverseBlock), 0, s, args);
+  else if (args.masked && args.any_hit)
     hipLaunchKernelGGL((k_scene_walk<kSceneWalkLdsStack, false, true, true>), dim3(grid), dim3(kTraverseBlock), 0, s, args);
   else if (args.masked)
     hipLaunchKernelGGL((k_scene_walk<kSceneWalkLdsStack, false, false, true>), dim3(grid), dim3(kTraverseBlock), 0, s, args);
