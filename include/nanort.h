@@ -823,6 +823,26 @@ struct BatchQuery {
   unsigned char *hit_out;
 };
 
+// What BVHAccel::MultiHitTraverseBatchQuery() is asked for: BatchQuery's wave — `motion`, `masked` and the three arrays mean what they
+// mean there — for the max_hits frontmost hits of every ray.  isects[i * max_hits + j] holds ray i's hits in ascending (t, prim_id)
+// order, then miss records {0, 0, ray.max_t, 0xFFFFFFFF}: every record is written.  counts_out (optional) receives the hits held.
+template <typename T = float>
+struct MultiHitBatchQuery {
+  MultiHitBatchQuery()
+      : rays(NULL), num_rays(0), times(NULL), ray_masks(NULL), skip_prim_ids(NULL), motion(false), masked(false), isects(NULL), max_hits(0),
+        counts_out(NULL) {}
+  const Ray<T> *rays;
+  size_t num_rays;
+  const T *times;
+  const unsigned int *ray_masks;
+  const unsigned int *skip_prim_ids;
+  bool motion, masked;
+  BVHTraceOptions options;
+  TriangleIntersection<T> *isects;
+  unsigned int max_hits;
+  unsigned int *counts_out;
+};
+
 // Robust slab test (Ize 2013), t_max terms widened by MaxMult
 // (ref nanort.h:2278-2370).
 namespace detail {
@@ -1422,6 +1442,10 @@ struct HipApi;
     typedef nrt_ray_query_##S QueryPod;                                           \
     NANORT_HIP_ENTRY(Query, nrtQueryBatch, S)                                     \
     NANORT_HIP_ENTRY(QueryDevice, nrtQueryBatchDevice, S)                         \
+    /* ... and the multi-hit query with the same three: its own descriptor */     \
+    typedef nrt_multihit_query_##S MultiHitQueryPod;                              \
+    NANORT_HIP_ENTRY(MultiHitQuery, nrtMultiHitQueryBatch, S)                     \
+    NANORT_HIP_ENTRY(MultiHitQueryDevice, nrtMultiHitQueryBatchDevice, S)         \
   };
 NANORT_HIP_API(float, f32)
 NANORT_HIP_API(double, f64)
@@ -1817,6 +1841,32 @@ class BVHAccel {
     return true;
   }
 
+  // Multi-hit under the combined intersector on the HOST, with or without NANORT_USE_HIP_BACKEND (MultiHitBatchQuery above; the
+  // contract of include/nanort_hip.h, nrtMultiHitQueryBatch): N calls of MultiHitTraverse(), ray i through a copy of `intersector` of
+  // its own on which SetRay() was called as TraverseBatchQuery() does.  Rows and counts in the library's layout, miss records
+  // included.  Returns false, nothing written, when max_hits is outside 1..64 or the query has rays and lacks them or its rows.
+  bool MultiHitTraverseBatchQuery(const MultiHitBatchQuery<T> &q, const QueryTriangleIntersector<T> &intersector) const {
+    if (q.max_hits == 0 || q.max_hits > 64) return false;
+    if (q.num_rays && (!q.rays || !q.isects)) return false;
+    StackVector<TriangleIntersection<T>, 128> held;
+    for (size_t i = 0; i < q.num_rays; i++) {
+      const QueryTriangleIntersector<T> ray_intersector(intersector);
+      ray_intersector.SetRay((q.motion && q.times) ? q.times[i] : static_cast<T>(0.0), (q.masked && q.ray_masks) ? q.ray_masks[i] : 0xFFFFFFFFu,
+                             q.skip_prim_ids ? q.skip_prim_ids[i] : q.options.skip_prim_id);
+      MultiHitTraverse(q.rays[i], static_cast<int>(q.max_hits), ray_intersector, &held, q.options);
+      const size_t count = held->size();
+      for (size_t j = 0; j < q.max_hits; j++) {
+        TriangleIntersection<T> &out = q.isects[i * q.max_hits + j];  // (field by field: the caller's padding bytes stay the caller's)
+        out.u = j < count ? held[j].u : static_cast<T>(0.0);
+        out.v = j < count ? held[j].v : static_cast<T>(0.0);
+        out.t = j < count ? held[j].t : q.rays[i].max_t;
+        out.prim_id = j < count ? held[j].prim_id : 0xFFFFFFFFu;
+      }
+      if (q.counts_out) q.counts_out[i] = static_cast<unsigned int>(count);
+    }
+    return true;
+  }
+
 #ifdef NANORT_USE_HIP_BACKEND
   // Closest hit for each of `num_rays` rays in one GPU launch.  isects[i] is written only when
   // ray i hits (exactly like N calls of Traverse()); hit_out[i] (optional) receives 1 / 0.
@@ -2032,6 +2082,23 @@ class BVHAccel {
     const typename Api::QueryPod d = QueryDescriptor(q, &o);
     return Ok(Api::QueryDevice(Context(), &d, hip_stream));
   }
+  // Multi-hit under the combined intersector on the GPU (nrtMultiHitQueryBatch): rows and counts equal those of the host form above,
+  // MultiHitTraverseBatchQuery(q, intersector), over the same tree.  A query with none of the three is MultiHitTraverseBatch().
+  bool MultiHitTraverseBatchQuery(const MultiHitBatchQuery<T> &q) const {
+    std::lock_guard<std::mutex> lock(batch_mutex_);
+    if (!QueryTreeReady(q, "MultiHitTraverseBatchQuery")) return false;
+    const nrt_trace_options o = TraceOptions(q.options);
+    const typename Api::MultiHitQueryPod d = MultiHitQueryDescriptor(q, &o);
+    return Ok(Api::MultiHitQuery(Context(), &d));
+  }
+  // ... and with device pointers in every array of `q`, asynchronous on `hip_stream` (see TraverseBatchDevice).
+  bool MultiHitTraverseBatchQueryDevice(const MultiHitBatchQuery<T> &q, void *hip_stream) const {
+    std::lock_guard<std::mutex> lock(batch_mutex_);
+    if (!TriangleTreeOnDevice("MultiHitTraverseBatchQueryDevice: no triangle tree on the GPU") || !QueryTreeReady(q, "MultiHitTraverseBatchQueryDevice")) return false;
+    const nrt_trace_options o = TraceOptions(q.options);
+    const typename Api::MultiHitQueryPod d = MultiHitQueryDescriptor(q, &o);
+    return Ok(Api::MultiHitQueryDevice(Context(), &d, hip_stream));
+  }
   // ... and with device pointers, asynchronous on `hip_stream` (see TraverseBatchDevice).
   bool MultiHitTraverseBatchDevice(const Ray<T> *d_rays, size_t num_rays, unsigned int max_hits, TriangleIntersection<T> *d_isects,
                                    unsigned int *d_counts, void *hip_stream, const BVHTraceOptions &options = BVHTraceOptions()) const {
@@ -2224,7 +2291,8 @@ class BVHAccel {
     return DeviceTreeReady(0);
   }
   // The checks of the combined query (caller holds batch_mutex_): those of every feature it has, or of a plain triangle batch.
-  bool QueryTreeReady(const BatchQuery<T> &q, const char *who) const {
+  template <class Q>
+  bool QueryTreeReady(const Q &q, const char *who) const {
     if (q.motion && !MotionTreeReady(who)) return false;
     if (q.masked && !MaskedTreeReady(who)) return false;
     return DeviceTreeReady(0);
@@ -2242,6 +2310,22 @@ class BVHAccel {
     d.ray_masks = q.ray_masks;
     d.hits_out = Pod(q.isects);
     d.mask_out = q.hit_out;
+    return d;
+  }
+  typename Api::MultiHitQueryPod MultiHitQueryDescriptor(const MultiHitBatchQuery<T> &q, const nrt_trace_options *o) const {
+    typename Api::MultiHitQueryPod d;
+    d.struct_size = static_cast<uint32_t>(sizeof(d));
+    d.flags = (q.motion ? NRT_QUERY_MOTION : 0u) | (q.masked ? NRT_QUERY_MASKED : 0u);
+    d.rays = Pod(q.rays);
+    d.num_rays = q.num_rays;
+    d.options = o;
+    d.skip_prim_ids = q.skip_prim_ids;
+    d.times = q.times;
+    d.ray_masks = q.ray_masks;
+    d.hits_out = Pod(q.isects);
+    d.counts_out = q.counts_out;
+    d.max_hits = q.max_hits;
+    d.reserved = 0;
     return d;
   }
   // The checks every host batch call makes (caller holds batch_mutex_): a context, the primitive kind the call's records are

@@ -187,6 +187,37 @@ typedef struct nrt_ray_query_f64 {
   uint8_t *mask_out;
 } nrt_ray_query_f64;
 
+/* The descriptor of nrtMultiHitQueryBatch* ("multi-hit with per-ray skip ids, visibility words and motion times" below).  Its first
+ * 56 bytes lie as in nrt_ray_query_*. */
+typedef struct nrt_multihit_query_f32 {
+  uint32_t struct_size;             /* sizeof(nrt_multihit_query_f32) */
+  uint32_t flags;                   /* NRT_QUERY_MOTION | NRT_QUERY_MASKED; NRT_QUERY_OCCLUSION is refused */
+  const nrt_ray_f32 *rays;
+  uint64_t num_rays;
+  const nrt_trace_options *options; /* NULL: defaults */
+  const uint32_t *skip_prim_ids;    /* NULL: options->skip_prim_id for every ray */
+  const float *times;               /* read with NRT_QUERY_MOTION only; NULL: every ray at time 0 */
+  const uint32_t *ray_masks;        /* read with NRT_QUERY_MASKED only; NULL: every ray 0xFFFFFFFF */
+  nrt_hit_f32 *hits_out;            /* num_rays * max_hits records */
+  uint32_t *counts_out;             /* may be NULL */
+  uint32_t max_hits;                /* K, 1..NRT_MAX_MULTIHIT */
+  uint32_t reserved;                /* must be 0 */
+} nrt_multihit_query_f32;
+typedef struct nrt_multihit_query_f64 {
+  uint32_t struct_size;             /* sizeof(nrt_multihit_query_f64) */
+  uint32_t flags;
+  const nrt_ray_f64 *rays;
+  uint64_t num_rays;
+  const nrt_trace_options *options;
+  const uint32_t *skip_prim_ids;
+  const double *times;
+  const uint32_t *ray_masks;
+  nrt_hit_f64 *hits_out;
+  uint32_t *counts_out;
+  uint32_t max_hits;
+  uint32_t reserved;
+} nrt_multihit_query_f64;
+
 #ifdef __cplusplus
 static_assert(sizeof(nrt_ray_f32) == 36 && sizeof(nrt_ray_f64) == 72, "Ray layout");
 static_assert(sizeof(nrt_node_f32) == 40 && sizeof(nrt_node_f64) == 64, "BVHNode layout");
@@ -194,6 +225,7 @@ static_assert(sizeof(nrt_hit_f32) == 16 && sizeof(nrt_hit_f64) == 32, "TriangleI
 static_assert(sizeof(nrt_build_options_f32) == 28 && sizeof(nrt_build_options_f64) == 32, "BVHBuildOptions layout");
 static_assert(sizeof(nrt_build_stats) == 16 && sizeof(nrt_trace_options) == 16, "stats/options layout");
 static_assert(sizeof(nrt_ray_query_f32) == 72 && sizeof(nrt_ray_query_f64) == 72, "ray query descriptor layout");
+static_assert(sizeof(nrt_multihit_query_f32) == 80 && sizeof(nrt_multihit_query_f64) == 80, "multi-hit query descriptor layout");
 #endif
 
 /* ---- context ------------------------------------------------------------ */
@@ -604,8 +636,8 @@ NRT_API nrt_status nrtTraverseBatches_f64(nrt_ctx *ctx, uint32_t num_batches, co
  * launch, asynchronously on `hip_stream`.  nrtOccludedBatchSkip*: mask[i] is the hit flag of the closest-hit form with the same ids.
  * nrtTraverseBatchesSkip*: an array of `num_batches` pointers; the array or any entry of it may be NULL, and a batch with a NULL
  * entry uses options->skip_prim_id; records are exactly those of separate calls (fp32: still one launch, fp64: one after the other).
- * Not covered: multi-hit, nrtTraverseCountDevice, nrtTraverseBatchMulti, nrtGroup* and the Embree shim take no per-ray ids; scenes take
- * (primitive, node) pairs through nrtSceneQueryBatch* (below).
+ * Not covered: nrtMultiHitTraverseBatch*, nrtTraverseCountDevice, nrtTraverseBatchMulti, nrtGroup* and the Embree shim take no per-ray
+ * ids; multi-hit takes them through nrtMultiHitQueryBatch* (below), scenes take (primitive, node) pairs through nrtSceneQueryBatch* (below).
  * These calls take Closest / Occlusion launches only; ids together with motion times or visibility words: nrtQueryBatch* below. */
 NRT_API nrt_status nrtTraverseBatchSkip_f32(nrt_ctx *ctx, const nrt_ray_f32 *rays, uint64_t num_rays, const nrt_trace_options *options,
                                             const uint32_t *skip_prim_ids, nrt_hit_f32 *hits_out, uint8_t *hit_mask_out);
@@ -806,12 +838,65 @@ NRT_API nrt_status nrtOccludedBatchMaskedDevice_f64(nrt_ctx *ctx, const nrt_ray_
  * in pieces carries, with each piece, its slices of all three per-ray arrays.  The first MASKED query behind a change of the masks
  * or of the tree re-derives the words' leaf-order copy, as a masked query does.
  *
- * Not covered: multi-hit, the batch tables, nrtTraverseBatchMulti, nrtGroup*, scenes and the Embree shim, and the sphere,
- * cylinder and curve kinds keep ignoring what they ignore today. */
+ * Not covered: the batch tables, nrtTraverseBatchMulti, nrtGroup*, scenes and the Embree shim, and the sphere, cylinder and curve
+ * kinds keep ignoring what they ignore today.  Multi-hit takes the same three inputs through a descriptor of its own:
+ * nrtMultiHitQueryBatch* (next). */
 NRT_API nrt_status nrtQueryBatch_f32(nrt_ctx *ctx, const nrt_ray_query_f32 *query);
 NRT_API nrt_status nrtQueryBatch_f64(nrt_ctx *ctx, const nrt_ray_query_f64 *query);
 NRT_API nrt_status nrtQueryBatchDevice_f32(nrt_ctx *ctx, const nrt_ray_query_f32 *query, void *hip_stream);
 NRT_API nrt_status nrtQueryBatchDevice_f64(nrt_ctx *ctx, const nrt_ray_query_f64 *query, void *hip_stream);
+
+/* ---- multi-hit with per-ray skip ids, visibility words and motion times ---------------------------------------------------------
+ * An OPT-IN EXTENSION.  A transparent-shadow or transmission wave wants the K frontmost triangles of every ray, and it starts on a
+ * surface (its skip id), has a ray type (its word) and, on a moving mesh, a shutter time.  nrtMultiHitQueryBatch* takes a DESCRIPTOR
+ * (nrt_multihit_query_f32 / _f64, among the PODs above):
+ *
+ *     struct_size    sizeof(the descriptor)
+ *     flags          NRT_QUERY_MOTION | NRT_QUERY_MASKED  (NRT_QUERY_OCCLUSION is refused: multi-hit has no occlusion form)
+ *     rays, num_rays
+ *     options        NULL: the reference's defaults
+ *     skip_prim_ids  one id per ray, NULL: options->skip_prim_id for every ray
+ *     times          read with MOTION only; NULL: every ray at time 0
+ *     ray_masks      read with MASKED only; NULL: every ray 0xFFFFFFFF
+ *     hits_out       num_rays * max_hits records
+ *     counts_out     one word per ray, may be NULL
+ *     max_hits       K, 1..NRT_MAX_MULTIHIT
+ *     reserved       must be 0
+ *
+ * Triangle contexts of the call's precision only.
+ *
+ * Contract.  The multi-hit contract (items 1-5 above nrtMultiHitTraverseBatch*) in which "TriangleIntersector::Intersect" is the
+ * intersector of the nrtQueryBatch* contract.  For primitive p and ray i that intersector returns false WITHOUT TOUCHING THE RAY'S
+ * STATE — p is no candidate — when MASKED is set and (prim_mask[p] & ray_masks[i]) == 0, when p is outside options->prim_ids_range,
+ * or when p is the ray's skip id: skip_prim_ids[i], or options->skip_prim_id where the array is NULL; 0xFFFFFFFF and every id at or
+ * above the context's number of faces skip nothing.  Otherwise it tests, with MOTION, the three corners interpolated to
+ * ClampTime(times[i]) by include/nanort_motion.h's rule, and without MOTION the corners of keyframe 0.  The rest is the multi-hit
+ * contract unchanged: the reference's binary loop over the context's node array with B as defined there, ranking by (t, prim_id),
+ * the K-buffer in the ray's own row, unused slots = the miss record {0, 0, max_t, 0xFFFFFFFF}, every byte written.
+ * K = 1: count and t equal nrtQueryBatch*'s flag and t with the same arrays and flags on every ray; prim_id / u / v differ only at
+ * exact-t ties, where multi-hit names the smaller id.
+ *
+ * Routing.  A descriptor with no flag and no ids IS nrtMultiHitTraverseBatch* — the same kernel (nrtLastKernelName:
+ * nrt::k_traverse_multihit<...>), the same bytes out.  Everything else — ids alone included, which no other call can express — runs
+ * nrt::k_multihit_query<T, 32, MOTION, MASKED>.
+ *
+ * Refusals; each writes nothing and sets nrtLastError, naming nrtMultiHitQueryBatch.  NRT_ERR_INVALID: a NULL context (no message to
+ * set) or descriptor; a struct_size other than the struct's; unknown flag bits or NRT_QUERY_OCCLUSION; reserved != 0; K == 0 or
+ * K > NRT_MAX_MULTIHIT; NULL rays or hits_out with num_rays > 0; MOTION on a context without a keyframe; MASKED on a context without
+ * masks; a sphere, cylinder or curve context; a Device array (times, ray_masks, skip_prim_ids, counts_out) that is not aligned to its
+ * element size; no tree; more than 2^31-1 rays.  NRT_ERR_PRECISION: a context of the other precision.  num_rays == 0 is NRT_OK.
+ *
+ * Ordering: the rules of multi-hit and of the masked queries.  The launch takes one of the context's launch slots and closes it with
+ * an event; nrtSetMesh* / nrtSetMeshMotion* / nrtSetPrimMasks* / nrtBuild / nrtSetTree / nrtDestroy wait for it.  The first MASKED
+ * query behind a change of the masks or of the tree re-derives the words' leaf-order copy.  nrtMultiHitQueryBatch_* takes host arrays
+ * through the staged path of nrtMultiHitTraverseBatch_* (pieces whose rows stay within 256 MiB); each piece carries its slices of
+ * all three per-ray arrays.
+ *
+ * Not covered: scenes, the sphere, cylinder and curve kinds, the batch tables, nrtTraverseBatchMulti, nrtGroup* and the Embree shim. */
+NRT_API nrt_status nrtMultiHitQueryBatch_f32(nrt_ctx *ctx, const nrt_multihit_query_f32 *query);
+NRT_API nrt_status nrtMultiHitQueryBatch_f64(nrt_ctx *ctx, const nrt_multihit_query_f64 *query);
+NRT_API nrt_status nrtMultiHitQueryBatchDevice_f32(nrt_ctx *ctx, const nrt_multihit_query_f32 *query, void *hip_stream);
+NRT_API nrt_status nrtMultiHitQueryBatchDevice_f64(nrt_ctx *ctx, const nrt_multihit_query_f64 *query, void *hip_stream);
 
 /* One HOST batch spread over several contexts — typically one per GPU of the node (nrtDeviceCount), each holding the same
  * tree: nrtBuild is deterministic, so building the same mesh on every context gives bit-identical replicas (or nrtSetTree the

@@ -930,6 +930,41 @@ class BVHAccel:
             None if d_counts is None else d_counts.data_ptr(), stream))
         return n
 
+    def MultiHitQueryBatch(self, rays, max_hits, times=None, ray_masks=None, skip_prim_ids=None, motion=None, masked=None, options=None):
+        """nrtMultiHitQueryBatch: MultiHitTraverseBatch for whichever of a shutter time, a visibility word and a skip id every ray
+        carries.  `motion` / `masked`: as QueryBatch's (None: iff the array is given).  Returns (hits[n, K], counts[n])."""
+        rays = np.ascontiguousarray(rays, dtype=ray_dtype(self.real))
+        n = rays.shape[0]
+        t = self._host_times(times, n)
+        v = self._host_ray_masks(ray_masks, n)
+        ids = None if skip_prim_ids is None else self._host_skip_ids(skip_prim_ids, n)
+        hits = np.zeros((n, max(int(max_hits), 1)), dtype=hit_dtype(self.real))
+        counts = np.zeros((n,), dtype=np.uint32)
+        options = _opts(options)
+        q = capi.MultiHitQuery(ctypes.sizeof(capi.MultiHitQuery), self._query_flags(times, ray_masks, motion, masked, False), rays.ctypes.data, n,
+                               None if options is None else options.ctypes.data, None if ids is None else ids.ctypes.data,
+                               None if t is None else t.ctypes.data, None if v is None else v.ctypes.data, hits.ctypes.data, counts.ctypes.data,
+                               int(max_hits), 0)
+        self._check(getattr(self._L, "nrtMultiHitQueryBatch_" + self._s)(self._h, ctypes.addressof(q)))
+        return hits, counts
+
+    def MultiHitQueryBatchDevice(self, d_rays, max_hits, d_hits, d_counts=None, times=None, ray_masks=None, skip_prim_ids=None, motion=None,
+                                 masked=None, options=None, stream=None):
+        """nrtMultiHitQueryBatchDevice: the same on HBM-resident torch tensors (raw PODs: d_hits holds n * max_hits records, d_counts n
+        uint32; `times` in the accel's precision, `ray_masks` and `skip_prim_ids` 32-bit words, one per ray), asynchronous on `stream`
+        (default: torch's current stream).  Returns n."""
+        n = self._n_rays(d_rays)
+        assert d_hits.numel() * d_hits.element_size() >= n * int(max_hits) * hit_dtype(self.real).itemsize
+        assert d_counts is None or d_counts.numel() * d_counts.element_size() >= n * 4
+        options = _opts(options)
+        q = capi.MultiHitQuery(ctypes.sizeof(capi.MultiHitQuery), self._query_flags(times, ray_masks, motion, masked, False), d_rays.data_ptr(), n,
+                               None if options is None else options.ctypes.data,
+                               None if skip_prim_ids is None else self._device_skip_ids(skip_prim_ids, n), self._device_times(times, n),
+                               self._device_ray_masks(ray_masks, n), d_hits.data_ptr(), None if d_counts is None else d_counts.data_ptr(),
+                               int(max_hits), 0)
+        self._check(getattr(self._L, "nrtMultiHitQueryBatchDevice_" + self._s)(self._h, ctypes.addressof(q), self._stream_handle(stream)))
+        return n
+
     def TraverseCountDevice(self, d_rays, options=None):
         """Work counters (nodes visited, leaves, triangle tests, max stack) of one batch."""
         n = self._n_rays(d_rays)

@@ -47,6 +47,27 @@ class RayQuery(ctypes.Structure):
     ]
 
 
+NRT_MAX_MULTIHIT = 64
+
+
+class MultiHitQuery(ctypes.Structure):
+    """nrt_multihit_query_f32 / nrt_multihit_query_f64: RayQuery's first 56 bytes, then the rows, the counts and K."""
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32),
+        ("flags", ctypes.c_uint32),
+        ("rays", ctypes.c_void_p),
+        ("num_rays", ctypes.c_uint64),
+        ("options", ctypes.c_void_p),
+        ("skip_prim_ids", ctypes.c_void_p),
+        ("times", ctypes.c_void_p),
+        ("ray_masks", ctypes.c_void_p),
+        ("hits_out", ctypes.c_void_p),
+        ("counts_out", ctypes.c_void_p),
+        ("max_hits", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
+    ]
+
+
 NRT_SCENE_QUERY_OCCLUSION, NRT_SCENE_QUERY_MASKED, NRT_SCENE_QUERY_SKIP = 1, 2, 4
 
 
@@ -138,6 +159,9 @@ SIGNATURES = [
     # one descriptor for every triangle ray query (RayQuery below): ctx, descriptor[, stream]
     ("nrtQueryBatch", _BOTH, [vp, vp], i32),
     ("nrtQueryBatchDevice", _BOTH, [vp, vp, vp], i32),
+    # multi-hit under the same three per-ray inputs (MultiHitQuery above): ctx, descriptor[, stream]
+    ("nrtMultiHitQueryBatch", _BOTH, [vp, vp], i32),
+    ("nrtMultiHitQueryBatchDevice", _BOTH, [vp, vp, vp], i32),
     ("nrtTraverseBatchMulti", _BOTH, [vp, u32, vp, u64, u64, vp, vp, vp], i32),
     ("nrtDeviceCount", None, [], i32),
     ("nrtTraverseCountDevice", _BOTH, _Q + [P(TraceCounters)], i32),

@@ -26,8 +26,10 @@ struct TraverseBatches {
 // (Masked / MaskedOcclusion: those of nrt*BatchMasked*, every ray with its own visibility word: masked.hip)
 // (Combined / CombinedOcclusion: those of nrtQueryBatch* with two or more of per-ray skip ids, times and words — with_motion,
 // with_masks and skip_ids say which: query.hip)
+// (MultiHitQuery: the multi-hit query of nrtMultiHitQueryBatch* with any of the three — with_motion, with_masks and skip_ids say which:
+// multihit_query.hip; a descriptor with none of them is a MultiHit launch)
 enum class Query { Closest, Occlusion, Count, MultiHit, Cylinders, MultiBatch, Curves, OcclusionPrims, Motion, MotionOcclusion, Masked, MaskedOcclusion,
-                   Combined, CombinedOcclusion };
+                   Combined, CombinedOcclusion, MultiHitQuery };
 template <typename T>
 struct TraverseLaunch {
   Query kind;
@@ -40,17 +42,20 @@ struct TraverseLaunch {
   uint8_t *mask = nullptr;               // Closest (may be null), Occlusion, OcclusionPrims, Cylinders, Curves
   void *cyl_hits = nullptr;              // Cylinders: 28-byte records, Curves: 40-byte records, written by the post pass
   uint32_t max_hits = 0;
-  uint32_t *hit_counts = nullptr;        // MultiHit (may be null): one word per ray
+  uint32_t *hit_counts = nullptr;        // MultiHit, MultiHitQuery (may be null): one word per ray
   const TraverseBatches<T> *batches = nullptr; // MultiBatch: rays and outputs per batch, n = all their rays (the context takes one launch: the caller checked)
   const uint32_t *skip_ids = nullptr;    // Closest, Occlusion (nrt*BatchSkip*), Combined*: one skip id per ray in the place of opt->skip_prim_id (MultiBatch: batches->skip[])
   const T *times = nullptr;              // Motion, MotionOcclusion, Combined* with_motion: one time per ray (null: every ray at time 0)
   const uint32_t *ray_masks = nullptr;   // Masked, MaskedOcclusion, Combined* with_masks: one visibility word per ray (null: every ray 0xFFFFFFFF)
-  bool with_motion = false, with_masks = false; // Combined, CombinedOcclusion: the features of the launch besides its ids
+  bool with_motion = false, with_masks = false; // Combined, CombinedOcclusion, MultiHitQuery: the features of the launch besides its ids
   bool descriptor = false;               // the launch came through nrtQueryBatch*: triangle contexts only, whatever it was routed to
+  bool multihit_descriptor = false;      // the launch came through nrtMultiHitQueryBatch* (its refusals are multihit_query_batch's)
   bool combined() const { return kind == Query::Combined || kind == Query::CombinedOcclusion; }
-  bool motion() const { return kind == Query::Motion || kind == Query::MotionOcclusion || (combined() && with_motion); }
-  bool masked() const { return kind == Query::Masked || kind == Query::MaskedOcclusion || (combined() && with_masks); }
-  bool own_walk() const { return kind == Query::MultiHit || motion() || masked(); } // a binary walk of its own: no wide records, no completion record
+  bool multihit() const { return kind == Query::MultiHit || kind == Query::MultiHitQuery; } // rows of max_hits records and a count per ray
+  bool features() const { return combined() || kind == Query::MultiHitQuery; }             // with_motion / with_masks are read
+  bool motion() const { return kind == Query::Motion || kind == Query::MotionOcclusion || (features() && with_motion); }
+  bool masked() const { return kind == Query::Masked || kind == Query::MaskedOcclusion || (features() && with_masks); }
+  bool own_walk() const { return multihit() || motion() || masked(); } // a binary walk of its own: no wide records, no completion record
   // the output the kind is for — what a call with rays cannot do without — is its flags; else its records: hits, or (Cylinders, Curves) cyl_hits
   bool flags_only() const {
     return kind == Query::Occlusion || kind == Query::OcclusionPrims || kind == Query::MotionOcclusion || kind == Query::MaskedOcclusion ||
@@ -82,7 +87,7 @@ static nrt_status validate_launch(nrt_ctx *c, const TraverseLaunch<T> &l) {
     if (((uintptr_t)l.times % sizeof(T)) != 0u) return fail(c, NRT_ERR_INVALID, "motion queries: the times array is not aligned to %zu bytes", sizeof(T));
   }
   if (l.masked()) { // (include/nanort_hip.h, "visibility masks")
-    const char *fn = l.combined() ? "nrtQueryBatch" : l.kind == Query::Masked ? "nrtTraverseBatchMasked" : "nrtOccludedBatchMasked";
+    const char *fn = l.combined() ? "nrtQueryBatch" : l.kind == Query::MultiHitQuery ? "nrtMultiHitQueryBatch" : l.kind == Query::Masked ? "nrtTraverseBatchMasked" : "nrtOccludedBatchMasked";
     if (custom) return fail(c, NRT_ERR_INVALID, "%s: masked queries: triangle contexts only (this context holds %s)", fn, kPrimKinds[c->prim_kind].name);
     if (!c->d_prim_masks) return fail(c, NRT_ERR_INVALID, "%s: masked queries: the context holds no visibility masks (nrtSetPrimMasks)", fn);
     if (((uintptr_t)l.ray_masks & 3u) != 0u) return fail(c, NRT_ERR_INVALID, "%s: masked queries: the ray_masks array is not 4-byte aligned", fn);
@@ -90,8 +95,8 @@ static nrt_status validate_launch(nrt_ctx *c, const TraverseLaunch<T> &l) {
   if (l.has_skip_ids()) { // (include/nanort_hip.h, "per-ray skip ids")
     if (custom)
       return fail(c, NRT_ERR_INVALID, "per-ray skip ids: triangle contexts only (the sphere, cylinder and curve intersectors have no skip id)");
-    if (l.kind != Query::Closest && l.kind != Query::Occlusion && l.kind != Query::MultiBatch && !l.combined())
-      return fail(c, NRT_ERR_INVALID, "per-ray skip ids: closest-hit and occlusion queries only");
+    if (l.kind != Query::Closest && l.kind != Query::Occlusion && l.kind != Query::MultiBatch && !l.features())
+      return fail(c, NRT_ERR_INVALID, "per-ray skip ids: closest-hit, occlusion and nrtMultiHitQueryBatch queries only");
     bool aligned = ((uintptr_t)l.skip_ids & 3u) == 0u;
     if (l.batches)
       for (uint32_t k = 0; k < l.batches->nb; k++) aligned = aligned && ((uintptr_t)l.batches->skip[k] & 3u) == 0u;
@@ -137,8 +142,11 @@ static nrt_status take_slot(nrt_ctx *c, hipStream_t s, nrt_ctx::LaunchSlot **out
 
 // The kernel a launch runs, from the context's tree and tunables and the launch's kind and options.
 // k_traverse, k_traverse_wide of WIDTH 2 / 4, k_traverse_multihit, k_traverse_motion, k_traverse_masked, k_traverse_query<MOTION, MASKED>
-// of <true, false> / <false, true> / <true, true>  (nrt_ctx::occupancy has one row per value)
-enum class Walk { Literal, OneLevel, TwoLevel, MultiHit, Motion, Masked, QueryMotion, QueryMasked, QueryMotionMasked };
+// of <true, false> / <false, true> / <true, true>, k_multihit_query<MOTION, MASKED> of <false, false> / <true, false> / <false, true> /
+// <true, true>  (nrt_ctx::occupancy has one row per value)
+enum class Walk { Literal, OneLevel, TwoLevel, MultiHit, Motion, Masked, QueryMotion, QueryMasked, QueryMotionMasked,
+                  MultiHitIds, MultiHitMotion, MultiHitMasked, MultiHitMotionMasked, Count_ };
+static_assert((int)Walk::Count_ == (int)(sizeof(nrt_ctx::occupancy) / sizeof(nrt_ctx::occupancy[0])), "nrt_ctx::occupancy: one row per walk");
 struct WalkChoice {
   Walk walk;
   bool plain_options; // prim ids are < num_faces: nothing can be rejected by the trace options -> the kernel variant without the id tests
@@ -150,6 +158,9 @@ struct WalkChoice {
   bool query() const { return walk == Walk::QueryMotion || walk == Walk::QueryMasked || walk == Walk::QueryMotionMasked; }
   bool query_motion() const { return walk == Walk::QueryMotion || walk == Walk::QueryMotionMasked; }
   bool query_masked() const { return walk == Walk::QueryMasked || walk == Walk::QueryMotionMasked; }
+  bool multihit_query() const { return walk >= Walk::MultiHitIds && walk <= Walk::MultiHitMotionMasked; }
+  bool multihit_motion() const { return walk == Walk::MultiHitMotion || walk == Walk::MultiHitMotionMasked; }
+  bool multihit_masked() const { return walk == Walk::MultiHitMasked || walk == Walk::MultiHitMotionMasked; }
 };
 template <typename T>
 static WalkChoice choose_walk(const nrt_ctx *c, const TraverseLaunch<T> &l) {
@@ -174,7 +185,9 @@ static WalkChoice choose_walk(const nrt_ctx *c, const TraverseLaunch<T> &l) {
   w.wide4_big = c->num_branch_records >= (1ull << 25) || (c->wide4_big_ok == 2 && c->prim_kind == kPrimTriangles); // (2: forced, for the tests)
   const bool use_wide4 = use_wide && c->d_wide4 && c->wide_stack == 10 && c->tree_nested && c->root_is_branch && !prof_needs_w2 &&
                          (!w.wide4_big || (!custom && !c->order4 && !(w.dbg & (32u | 8192u))));
-  w.walk = l.combined() ? (l.with_motion ? (l.with_masks ? Walk::QueryMotionMasked : Walk::QueryMotion) : Walk::QueryMasked)
+  w.walk = l.kind == Query::MultiHitQuery
+               ? (l.with_motion ? (l.with_masks ? Walk::MultiHitMotionMasked : Walk::MultiHitMotion) : (l.with_masks ? Walk::MultiHitMasked : Walk::MultiHitIds))
+           : l.combined() ? (l.with_motion ? (l.with_masks ? Walk::QueryMotionMasked : Walk::QueryMotion) : Walk::QueryMasked)
            : l.masked() ? Walk::Masked : l.motion() ? Walk::Motion : multihit ? Walk::MultiHit : (use_wide4 ? Walk::TwoLevel : (use_wide ? Walk::OneLevel : Walk::Literal));
   w.lds_entries = l.own_walk() ? kLdsStackDefault : (use_wide4 ? kWide4LdsStack : (custom ? 10 : (use_wide ? c->wide_stack : c->lds_stack)));
   return w;
@@ -185,7 +198,8 @@ template <typename T>
 static GridPlan size_grid(nrt_ctx *c, const WalkChoice &w, uint64_t n) {
   auto &e = c->occupancy[(int)w.walk][c->prim_kind];
   if (e.blocks_per_cu == 0 || e.lds_entries != w.lds_entries)
-    e = {w.lds_entries, (unsigned)(w.query()                 ? traverse_query_blocks_per_cu<T>(w.query_motion(), w.query_masked())
+    e = {w.lds_entries, (unsigned)(w.multihit_query()        ? multihit_query_blocks_per_cu<T>(w.multihit_motion(), w.multihit_masked())
+                        : w.query()                 ? traverse_query_blocks_per_cu<T>(w.query_motion(), w.query_masked())
                         : w.walk == Walk::Masked    ? traverse_masked_blocks_per_cu<T>()
                         : w.walk == Walk::Motion    ? traverse_motion_blocks_per_cu<T>()
                         : w.walk == Walk::MultiHit  ? traverse_multihit_blocks_per_cu<T>()
@@ -306,7 +320,16 @@ static nrt_status enqueue_launch(nrt_ctx *c, const TraverseLaunch<T> &l, const W
   a.done_publish = post_pass ? 0u : 1u;
   const bool timed = l.timed && !use_rec;
   if (timed) HIPCHK(c, hipEventRecord(slot->t0, s));
-  if (w.query()) {
+  if (w.multihit_query()) {
+    static const char *const names[2][4] = {{"nrt::k_multihit_query<float, 32, false, false>", "nrt::k_multihit_query<float, 32, true, false>",
+                                             "nrt::k_multihit_query<float, 32, false, true>", "nrt::k_multihit_query<float, 32, true, true>"},
+                                            {"nrt::k_multihit_query<double, 32, false, false>", "nrt::k_multihit_query<double, 32, true, false>",
+                                             "nrt::k_multihit_query<double, 32, false, true>", "nrt::k_multihit_query<double, 32, true, true>"}};
+    static_assert(kLdsStackDefault == 32, "the names above carry the stack depth");
+    HIPCHK(c, launch_multihit_query<T>(a, l.max_hits, l.hit_counts, w.multihit_motion(), w.multihit_masked(), c->d_tris1, l.times,
+                                       (const uint32_t *)c->b_leaf_masks.p, l.ray_masks, grid, s));
+    c->last_kernel = names[sizeof(T) == 4 ? 0 : 1][(int)w.walk - (int)Walk::MultiHitIds];
+  } else if (w.query()) {
     static const char *const names[2][3] = {{"nrt::k_traverse_query<float, 32, true, false>", "nrt::k_traverse_query<float, 32, false, true>",
                                              "nrt::k_traverse_query<float, 32, true, true>"},
                                             {"nrt::k_traverse_query<double, 32, true, false>", "nrt::k_traverse_query<double, 32, false, true>",
@@ -407,6 +430,7 @@ static nrt_status traverse_device(nrt_ctx *c, TraverseLaunch<T> l) {
 }
 
 const uint64_t kStagedRays = 1ull << 26; // rays per launch of the staged host paths (keeps staging bounded)
+const uint64_t kMultiHitStagedBytes = 256ull << 20; // record bytes per launch of the staged multi-hit paths, whatever K is
 const uint64_t kPiece = 1ull << 19; // rays per pipeline stage of traverse_host (19 MB up, 8 MB down in fp32), and per launch of the motion and masked queries' staged path
 
 // Multi-hit (include/nanort_hip.h, nrtMultiHitTraverseBatch*): the kind's own refusals, ahead of the ones every query shares.
@@ -429,7 +453,7 @@ static nrt_status multihit_check(nrt_ctx *c, const void *rays, uint64_t n, uint3
 template <typename T>
 static nrt_status query_device(nrt_ctx *c, const char *fn, const TraverseLaunch<T> &l) {
   if (!c) return NRT_ERR_INVALID;
-  if (l.kind == Query::MultiHit) {
+  if (l.kind == Query::MultiHit && !l.multihit_descriptor) {
     const nrt_status st = multihit_check<T>(c, l.rays, l.n, l.max_hits, l.hits);
     if (st || l.n == 0) return st;
   }
@@ -447,8 +471,8 @@ static nrt_status query_host(nrt_ctx *c, const char *fn, const TraverseLaunch<T>
   typedef typename Wire<T>::Ray Ray;
   typedef typename Wire<T>::Hit Hit;
   if (!c) return NRT_ERR_INVALID;
-  const bool multihit = host.kind == Query::MultiHit, own_records = host.kind == Query::Cylinders || host.kind == Query::Curves;
-  if (multihit)
+  const bool multihit = host.multihit(), own_records = host.kind == Query::Cylinders || host.kind == Query::Curves;
+  if (multihit && !host.multihit_descriptor) // (a descriptor's refusals carry its own entry point's name: multihit_query_batch)
     if (nrt_status st = multihit_check<T>(c, host.rays, host.n, host.max_hits, host.hits)) return st;
   if (host.n == 0) return NRT_OK;
   void *recs = host.records(), *flags = multihit ? (void *)host.hit_counts : (void *)host.mask;
@@ -458,9 +482,9 @@ static nrt_status query_host(nrt_ctx *c, const char *fn, const TraverseLaunch<T>
                            : multihit        ? host.max_hits * sizeof(Hit)
                                              : sizeof(Hit);
   const size_t flag_bytes = multihit ? sizeof(uint32_t) : 1;
-  // rays per launch: multi-hit keeps the staged records within 256 MiB whatever K is; the motion queries go in traverse_host's pieces
+  // rays per launch: multi-hit keeps the staged records within kMultiHitStagedBytes (256 MiB) whatever K is; the motion queries go in traverse_host's pieces
   // (their staging stays as small as the pipeline's)
-  const uint64_t chunk = multihit        ? std::max<uint64_t>(1u, std::min<uint64_t>(1ull << 26, (256ull << 20) / rec_bytes))
+  const uint64_t chunk = multihit        ? std::max<uint64_t>(1u, std::min<uint64_t>(1ull << 26, kMultiHitStagedBytes / rec_bytes))
                          : (host.motion() || host.masked()) ? kPiece
                                          : kStagedRays;
   std::lock_guard<std::mutex> host_lock(c->host_mutex);
@@ -846,6 +870,59 @@ static nrt_status query_batch(nrt_ctx *c, const D *q, bool device, void *stream)
   return occ ? query_host<T>(c, fn, l) : traverse_host<T>(c, l);
 }
 
+// nrtMultiHitQueryBatch* (include/nanort_hip.h, "multi-hit with per-ray skip ids, visibility words and motion times"): the descriptor's
+// own refusals and the context's, every one under the entry point's name, then the launch it describes.  A descriptor with no flag and
+// no ids IS nrtMultiHitTraverseBatch* — a MultiHit launch: the same kernel, the same bytes; everything else is a MultiHitQuery launch
+// (multihit_query.hip), ids alone included.  D: nrt_multihit_query_f32 / _f64.  `device`: as query_batch's.
+template <typename T, typename D>
+static nrt_status multihit_query_batch(nrt_ctx *c, const D *q, bool device, void *stream) {
+  const char *fn = device ? "nrtMultiHitQueryBatchDevice" : "nrtMultiHitQueryBatch";
+  if (!c) return NRT_ERR_INVALID;
+  if (!q) return fail(c, NRT_ERR_INVALID, "%s: NULL descriptor", fn);
+  if (q->struct_size != sizeof(D)) return fail(c, NRT_ERR_INVALID, "%s: struct_size %u, this library's descriptor has %zu bytes", fn, q->struct_size, sizeof(D));
+  const uint32_t known = NRT_QUERY_MOTION | NRT_QUERY_MASKED;
+  if (q->flags & NRT_QUERY_OCCLUSION) return fail(c, NRT_ERR_INVALID, "%s: NRT_QUERY_OCCLUSION: a multi-hit query has no occlusion form", fn);
+  if (q->flags & ~known) return fail(c, NRT_ERR_INVALID, "%s: unknown flag bits 0x%x", fn, q->flags & ~known);
+  if (q->reserved != 0u) return fail(c, NRT_ERR_INVALID, "%s: reserved is %u, must be 0", fn, q->reserved);
+  if (q->max_hits == 0u || q->max_hits > NRT_MAX_MULTIHIT) return fail(c, NRT_ERR_INVALID, "%s: max_hits %u outside 1..%u", fn, q->max_hits, NRT_MAX_MULTIHIT);
+  const bool motion = (q->flags & NRT_QUERY_MOTION) != 0u, masked = (q->flags & NRT_QUERY_MASKED) != 0u, ids = q->skip_prim_ids != nullptr;
+  if (q->num_rays > 0x7FFFFFFFull) return fail(c, NRT_ERR_INVALID, "%s: more than 2^31-1 rays in one call", fn);
+  if (q->num_rays && !q->rays) return fail(c, NRT_ERR_INVALID, "%s: NULL rays", fn);
+  if (q->num_rays && !q->hits_out) return fail(c, NRT_ERR_INVALID, "%s: NULL hits_out", fn);
+  if (c->prec != (int)sizeof(T)) return fail(c, NRT_ERR_PRECISION, "%s: precision mismatch", fn);
+  if (c->prim_kind != kPrimTriangles) return fail(c, NRT_ERR_INVALID, "%s: triangle contexts only (this context holds %s)", fn, kPrimKinds[c->prim_kind].name);
+  if (motion && !c->d_verts1) return fail(c, NRT_ERR_INVALID, "%s: MOTION: the context holds no motion keyframe (nrtSetMeshMotion)", fn);
+  if (masked && !c->d_prim_masks) return fail(c, NRT_ERR_INVALID, "%s: MASKED: the context holds no visibility masks (nrtSetPrimMasks)", fn);
+  if (device) { // (the host form stages every array: any alignment does)
+    if (motion && ((uintptr_t)q->times % sizeof(T)) != 0u) return fail(c, NRT_ERR_INVALID, "%s: the times array is not aligned to %zu bytes", fn, sizeof(T));
+    if (masked && ((uintptr_t)q->ray_masks & 3u) != 0u) return fail(c, NRT_ERR_INVALID, "%s: the ray_masks array is not 4-byte aligned", fn);
+    if (((uintptr_t)q->skip_prim_ids & 3u) != 0u) return fail(c, NRT_ERR_INVALID, "%s: the skip_prim_ids array is not 4-byte aligned", fn);
+    if (((uintptr_t)q->counts_out & 3u) != 0u) return fail(c, NRT_ERR_INVALID, "%s: the counts_out array is not 4-byte aligned", fn);
+  }
+  if (!c->d_nodes) return fail(c, NRT_ERR_INVALID, "%s: no tree (call nrtBuild or nrtSetTree)", fn);
+  if (q->num_rays == 0) return NRT_OK;
+  TraverseLaunch<T> l = {};
+  l.kind = (ids || motion || masked) ? Query::MultiHitQuery : Query::MultiHit;
+  l.rays = q->rays;
+  l.n = q->num_rays;
+  l.opt = q->options;
+  l.hits = q->hits_out;
+  l.max_hits = q->max_hits;
+  l.hit_counts = q->counts_out;
+  l.skip_ids = q->skip_prim_ids;
+  l.times = motion ? q->times : nullptr;         // (an array whose flag is not set is not read)
+  l.ray_masks = masked ? q->ray_masks : nullptr;
+  l.with_motion = motion;
+  l.with_masks = masked;
+  l.multihit_descriptor = true;
+  if (device) {
+    l.stream = (hipStream_t)stream;
+    l.timed = true;
+    return query_device<T>(c, fn, l);
+  }
+  return query_host<T>(c, fn, l);
+}
+
 // ---------------------------------------------------------------------------
 // The entry points, in the order of include/nanort_hip.h.  A host form names its arrays and goes through query_host (closest hits:
 // traverse_host), a Device form names its arrays and its stream and goes through query_device; the string is the name its
@@ -1073,6 +1150,12 @@ nrt_status nrtQueryBatch_f32(nrt_ctx *c, const nrt_ray_query_f32 *q) { return qu
 nrt_status nrtQueryBatch_f64(nrt_ctx *c, const nrt_ray_query_f64 *q) { return query_batch<double>(c, q, false, nullptr); }
 nrt_status nrtQueryBatchDevice_f32(nrt_ctx *c, const nrt_ray_query_f32 *q, void *s) { return query_batch<float>(c, q, true, s); }
 nrt_status nrtQueryBatchDevice_f64(nrt_ctx *c, const nrt_ray_query_f64 *q, void *s) { return query_batch<double>(c, q, true, s); }
+
+// Multi-hit under the same three per-ray inputs (include/nanort_hip.h): the K frontmost triangles of the combined intersector.
+nrt_status nrtMultiHitQueryBatch_f32(nrt_ctx *c, const nrt_multihit_query_f32 *q) { return multihit_query_batch<float>(c, q, false, nullptr); }
+nrt_status nrtMultiHitQueryBatch_f64(nrt_ctx *c, const nrt_multihit_query_f64 *q) { return multihit_query_batch<double>(c, q, false, nullptr); }
+nrt_status nrtMultiHitQueryBatchDevice_f32(nrt_ctx *c, const nrt_multihit_query_f32 *q, void *s) { return multihit_query_batch<float>(c, q, true, s); }
+nrt_status nrtMultiHitQueryBatchDevice_f64(nrt_ctx *c, const nrt_multihit_query_f64 *q, void *s) { return multihit_query_batch<double>(c, q, true, s); }
 
 nrt_status nrtTraverseBatchMulti_f32(nrt_ctx *const *ctxs, uint32_t num_ctx, const nrt_ray_f32 *r, uint64_t n, uint64_t row_len,
                                      const nrt_trace_options *o, nrt_hit_f32 *h, uint8_t *m) {

@@ -153,7 +153,7 @@ struct nrt_ctx {
   int dyn_head = 1; // batches too small for a static group per wave: every wave's first chunk is its own (traverse.hip claim_init; tunable dyn_head)
   int wide_scramble = 0; // probe (tunable wide_scramble): the private node records in a pseudo-random order instead of pre-order
   // resident blocks per CU of the variants launched so far, by what selects the kernel: [walk][primitive kind] at `lds_entries` (a context keeps one precision; size_grid)
-  struct { int lds_entries; unsigned blocks_per_cu; } occupancy[9][kNumPrimKinds] = {}; // (api_query.hip, enum Walk: its nine values)
+  struct { int lds_entries; unsigned blocks_per_cu; } occupancy[13][kNumPrimKinds] = {}; // (api_query.hip, enum Walk: its thirteen values)
 
   hipEvent_t ev_b0 = nullptr, ev_b1 = nullptr;
   hipEvent_t ev_build_state = nullptr; // the builder's state block has reached build_state

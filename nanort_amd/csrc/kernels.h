@@ -57,6 +57,16 @@ hipError_t launch_traverse_multihit(const TraverseArgs<T> &args, uint32_t max_hi
 template <typename T>
 int traverse_multihit_blocks_per_cu();
 
+// ---- multihit_query.hip: multi-hit under the combined intersector (per-ray skip ids in args.skip_ids, motion times, visibility words) ----
+// `motion` / `masked` select the instantiation (neither: ids alone); the arrays of a feature that is off are not read.
+// `max_hits`, `counts`: as launch_traverse_multihit's; `tris1`, `times`: as launch_traverse_motion's; `leaf_masks`, `ray_masks`: as
+// launch_traverse_masked's
+template <typename T>
+hipError_t launch_multihit_query(const TraverseArgs<T> &args, uint32_t max_hits, uint32_t *counts, bool motion, bool masked, const void *tris1, const T *times,
+                                 const uint32_t *leaf_masks, const uint32_t *ray_masks, unsigned grid, hipStream_t s);
+template <typename T>
+int multihit_query_blocks_per_cu(bool motion, bool masked);
+
 // ---- motion.hip: the motion-blur walk (a triangle context with a second vertex keyframe) --------------------------------------
 // `tris1`: the LeafTri<T> records of keyframe 1 in leaf order; `times`: one time per ray, or null (every ray at time 0);
 // args.any_hit: the occlusion query
