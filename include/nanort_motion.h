@@ -11,7 +11,7 @@
 // Time 0 is keyframe 0 and time 1 is keyframe 1, and the clamp puts every interpolated vertex inside the box the builder gives the
 // primitive (the union of the two keyframes' boxes), so a moving triangle is as watertight against its boxes as a static one.
 //
-// Included by the device walk (nanort_amd/csrc/motion.hip) and by the host intersector (nanort.h, MotionTriangleIntersector).
+// Included by the device walk (nanort_amd/csrc/own_walks.hip) and by the host intersector (nanort.h, MotionTriangleIntersector).
 #ifndef NANORT_MOTION_H_
 #define NANORT_MOTION_H_
 

@@ -18,18 +18,13 @@ struct TraverseBatches {
   uint32_t anyhit; // bit k: batch k is an occlusion query
 };
 
-// What one traversal launch is asked for: the query kind says which of the outputs it reads.  (Occlusion: every ray stops at the
-// first primitive it accepts; Count: the literal kernel's counting pass into d_counters, no output of its own; OcclusionPrims: the
-// occlusion query of nrtOccludedBatchPrims*, which every primitive kind takes — flags straight into the caller's mask, no compact
-// records, no post pass; on a triangle context it IS Occlusion: traverse_device says so under the lock.)
-// (Motion / MotionOcclusion: the closest-hit and occlusion queries of nrt*BatchMotion*, every ray at its own time: motion.hip)
-// (Masked / MaskedOcclusion: those of nrt*BatchMasked*, every ray with its own visibility word: masked.hip)
-// (Combined / CombinedOcclusion: those of nrtQueryBatch* with two or more of per-ray skip ids, times and words — with_motion,
-// with_masks and skip_ids say which: query.hip)
-// (MultiHitQuery: the multi-hit query of nrtMultiHitQueryBatch* with any of the three — with_motion, with_masks and skip_ids say which:
-// multihit_query.hip; a descriptor with none of them is a MultiHit launch)
-enum class Query { Closest, Occlusion, Count, MultiHit, Cylinders, MultiBatch, Curves, OcclusionPrims, Motion, MotionOcclusion, Masked, MaskedOcclusion,
-                   Combined, CombinedOcclusion, MultiHitQuery };
+// What one traversal launch is asked for: the query kind names an OUTPUT — which of the outputs below the launch writes.  (Occlusion:
+// every ray stops at the first primitive it accepts; Count: the literal kernel's counting pass into d_counters, no output of its own;
+// OcclusionPrims: the occlusion query of nrtOccludedBatchPrims*, which every primitive kind takes — flags straight into the caller's
+// mask, no compact records, no post pass; on a triangle context it IS Occlusion: traverse_device says so under the lock.)
+// What a triangle launch reads per ray besides its rays — skip ids, shutter times, visibility words — is three independent facts of
+// the launch (skip_ids, motion, masked), and own_walk_id() says which kernel they make of it.
+enum class Query { Closest, Occlusion, Count, MultiHit, Cylinders, MultiBatch, Curves, OcclusionPrims };
 template <typename T>
 struct TraverseLaunch {
   Query kind;
@@ -42,25 +37,32 @@ struct TraverseLaunch {
   uint8_t *mask = nullptr;               // Closest (may be null), Occlusion, OcclusionPrims, Cylinders, Curves
   void *cyl_hits = nullptr;              // Cylinders: 28-byte records, Curves: 40-byte records, written by the post pass
   uint32_t max_hits = 0;
-  uint32_t *hit_counts = nullptr;        // MultiHit, MultiHitQuery (may be null): one word per ray
+  uint32_t *hit_counts = nullptr;        // MultiHit (may be null): one word per ray
   const TraverseBatches<T> *batches = nullptr; // MultiBatch: rays and outputs per batch, n = all their rays (the context takes one launch: the caller checked)
-  const uint32_t *skip_ids = nullptr;    // Closest, Occlusion (nrt*BatchSkip*), Combined*: one skip id per ray in the place of opt->skip_prim_id (MultiBatch: batches->skip[])
-  const T *times = nullptr;              // Motion, MotionOcclusion, Combined* with_motion: one time per ray (null: every ray at time 0)
-  const uint32_t *ray_masks = nullptr;   // Masked, MaskedOcclusion, Combined* with_masks: one visibility word per ray (null: every ray 0xFFFFFFFF)
-  bool with_motion = false, with_masks = false; // Combined, CombinedOcclusion, MultiHitQuery: the features of the launch besides its ids
+  const uint32_t *skip_ids = nullptr;    // Closest, Occlusion, MultiHit: one skip id per ray in the place of opt->skip_prim_id (MultiBatch: batches->skip[])
+  const T *times = nullptr;              // motion: one time per ray (null: every ray at time 0)
+  const uint32_t *ray_masks = nullptr;   // masked: one visibility word per ray (null: every ray 0xFFFFFFFF)
+  // Closest, Occlusion, MultiHit: every ray at its own time (nrt*BatchMotion*, NRT_QUERY_MOTION) / with its own visibility word
+  // (nrt*BatchMasked*, NRT_QUERY_MASKED).  Set by what the entry point is, not by whether the array is there.
+  bool motion = false, masked = false;
   bool descriptor = false;               // the launch came through nrtQueryBatch*: triangle contexts only, whatever it was routed to
   bool multihit_descriptor = false;      // the launch came through nrtMultiHitQueryBatch* (its refusals are multihit_query_batch's)
-  bool combined() const { return kind == Query::Combined || kind == Query::CombinedOcclusion; }
-  bool multihit() const { return kind == Query::MultiHit || kind == Query::MultiHitQuery; } // rows of max_hits records and a count per ray
-  bool features() const { return combined() || kind == Query::MultiHitQuery; }             // with_motion / with_masks are read
-  bool motion() const { return kind == Query::Motion || kind == Query::MotionOcclusion || (features() && with_motion); }
-  bool masked() const { return kind == Query::Masked || kind == Query::MaskedOcclusion || (features() && with_masks); }
-  bool own_walk() const { return multihit() || motion() || masked(); } // a binary walk of its own: no wide records, no completion record
-  // the output the kind is for — what a call with rays cannot do without — is its flags; else its records: hits, or (Cylinders, Curves) cyl_hits
-  bool flags_only() const {
-    return kind == Query::Occlusion || kind == Query::OcclusionPrims || kind == Query::MotionOcclusion || kind == Query::MaskedOcclusion ||
-           kind == Query::CombinedOcclusion;
+  bool multihit() const { return kind == Query::MultiHit; } // rows of max_hits records and a count per ray
+  // THE routing: the binary walk of its own the launch runs (own_walks.hip), or kNumOwnWalks for none — the wide or the literal walk.
+  // A launch an older entry point can express is that entry point's launch: the same kernel, the same bytes.
+  OwnWalk own_walk_id() const {
+    const bool ids = skip_ids != nullptr;
+    if (multihit()) // nrtMultiHitTraverseBatch*; with any of the three, k_multihit_query<motion, masked>
+      return !(ids || motion || masked) ? kOwnMultiHit
+             : motion                   ? (masked ? kOwnMultiHitMotionMasked : kOwnMultiHitMotion)
+                                        : (masked ? kOwnMultiHitMasked : kOwnMultiHitIds);
+    if ((int)ids + (int)motion + (int)masked >= 2) // k_traverse_query<motion, masked>
+      return motion ? (masked ? kOwnQueryMotionMasked : kOwnQueryMotion) : kOwnQueryMasked;
+    return motion ? kOwnMotion : masked ? kOwnMasked : kNumOwnWalks; // nrt*BatchMotion*, nrt*BatchMasked*; ids alone or nothing: none
   }
+  bool own_walk() const { return own_walk_id() != kNumOwnWalks; } // no wide records, no completion record
+  // the output the kind is for — what a call with rays cannot do without — is its flags; else its records: hits, or (Cylinders, Curves) cyl_hits
+  bool flags_only() const { return kind == Query::Occlusion || kind == Query::OcclusionPrims; }
   void *records() const { return (kind == Query::Cylinders || kind == Query::Curves) ? cyl_hits : (void *)hits; }
   // the launch carries per-ray skip ids
   bool has_skip_ids() const {
@@ -80,14 +82,14 @@ static nrt_status validate_launch(nrt_ctx *c, const TraverseLaunch<T> &l) {
   if (c->prec != (int)sizeof(T)) return fail(c, NRT_ERR_PRECISION, "nrtTraverseBatch: precision mismatch");
   if (l.descriptor && custom) // (include/nanort_hip.h, "one descriptor for every triangle ray query")
     return fail(c, NRT_ERR_INVALID, "nrtQueryBatch: triangle contexts only (this context holds %s)", kPrimKinds[c->prim_kind].name);
-  if (l.motion()) { // (include/nanort_hip.h, "motion blur")
+  if (l.motion) { // (include/nanort_hip.h, "motion blur")
     if (custom) return fail(c, NRT_ERR_INVALID, "motion queries: triangle contexts only (this context holds %s)", kPrimKinds[c->prim_kind].name);
     if (!c->d_verts1) return fail(c, NRT_ERR_INVALID, "motion queries: the context holds no motion keyframe (nrtSetMeshMotion)");
     if (c->d_nodes && !c->d_tris1) return fail(c, NRT_ERR_INVALID, "motion queries: internal: no keyframe-1 leaf records");
     if (((uintptr_t)l.times % sizeof(T)) != 0u) return fail(c, NRT_ERR_INVALID, "motion queries: the times array is not aligned to %zu bytes", sizeof(T));
   }
-  if (l.masked()) { // (include/nanort_hip.h, "visibility masks")
-    const char *fn = l.combined() ? "nrtQueryBatch" : l.kind == Query::MultiHitQuery ? "nrtMultiHitQueryBatch" : l.kind == Query::Masked ? "nrtTraverseBatchMasked" : "nrtOccludedBatchMasked";
+  if (l.masked) { // (include/nanort_hip.h, "visibility masks"; the masked-alone walk reports as its own entry points, whoever asked)
+    const char *fn = l.multihit() ? "nrtMultiHitQueryBatch" : l.own_walk_id() != kOwnMasked ? "nrtQueryBatch" : l.flags_only() ? "nrtOccludedBatchMasked" : "nrtTraverseBatchMasked";
     if (custom) return fail(c, NRT_ERR_INVALID, "%s: masked queries: triangle contexts only (this context holds %s)", fn, kPrimKinds[c->prim_kind].name);
     if (!c->d_prim_masks) return fail(c, NRT_ERR_INVALID, "%s: masked queries: the context holds no visibility masks (nrtSetPrimMasks)", fn);
     if (((uintptr_t)l.ray_masks & 3u) != 0u) return fail(c, NRT_ERR_INVALID, "%s: masked queries: the ray_masks array is not 4-byte aligned", fn);
@@ -95,7 +97,7 @@ static nrt_status validate_launch(nrt_ctx *c, const TraverseLaunch<T> &l) {
   if (l.has_skip_ids()) { // (include/nanort_hip.h, "per-ray skip ids")
     if (custom)
       return fail(c, NRT_ERR_INVALID, "per-ray skip ids: triangle contexts only (the sphere, cylinder and curve intersectors have no skip id)");
-    if (l.kind != Query::Closest && l.kind != Query::Occlusion && l.kind != Query::MultiBatch && !l.features())
+    if (l.kind != Query::Closest && l.kind != Query::Occlusion && l.kind != Query::MultiBatch && !l.multihit())
       return fail(c, NRT_ERR_INVALID, "per-ray skip ids: closest-hit, occlusion and nrtMultiHitQueryBatch queries only");
     bool aligned = ((uintptr_t)l.skip_ids & 3u) == 0u;
     if (l.batches)
@@ -115,7 +117,7 @@ static nrt_status validate_launch(nrt_ctx *c, const TraverseLaunch<T> &l) {
   if (l.n > 0x7FFFFFFFull) return fail(c, NRT_ERR_INVALID, "nrtTraverseBatch: more than 2^31-1 rays in one call");
   if (custom && (l.kind == Query::Count || !c->d_wide))
     return fail(c, NRT_ERR_INVALID, "nrtTraverse: custom primitives run on the WideNode kernel only (no counting pass)");
-  if (l.kind == Query::Occlusion && (custom || !c->d_wide))
+  if (l.kind == Query::Occlusion && !l.own_walk() && (custom || !c->d_wide))
     return fail(c, NRT_ERR_INVALID, "nrtOccludedBatch: occlusion queries run on the triangle WideNode kernel only");
   if (l.kind == Query::MultiBatch && (sizeof(T) != 4 || custom || !c->wide || !c->d_wide))
     return fail(c, NRT_ERR_INVALID, "internal: multi-batch launch on a context that cannot take it");
@@ -140,27 +142,16 @@ static nrt_status take_slot(nrt_ctx *c, hipStream_t s, nrt_ctx::LaunchSlot **out
   return NRT_OK;
 }
 
-// The kernel a launch runs, from the context's tree and tunables and the launch's kind and options.
-// k_traverse, k_traverse_wide of WIDTH 2 / 4, k_traverse_multihit, k_traverse_motion, k_traverse_masked, k_traverse_query<MOTION, MASKED>
-// of <true, false> / <false, true> / <true, true>, k_multihit_query<MOTION, MASKED> of <false, false> / <true, false> / <false, true> /
-// <true, true>  (nrt_ctx::occupancy has one row per value)
-enum class Walk { Literal, OneLevel, TwoLevel, MultiHit, Motion, Masked, QueryMotion, QueryMasked, QueryMotionMasked,
-                  MultiHitIds, MultiHitMotion, MultiHitMasked, MultiHitMotionMasked, Count_ };
-static_assert((int)Walk::Count_ == (int)(sizeof(nrt_ctx::occupancy) / sizeof(nrt_ctx::occupancy[0])), "nrt_ctx::occupancy: one row per walk");
+// The kernel a launch runs (Walk: ctx.h), from the context's tree and tunables and the launch's kind and options.
 struct WalkChoice {
   Walk walk;
+  OwnWalk own;        // Walk::Own: which of own_walks.hip's kernels
   bool plain_options; // prim ids are < num_faces: nothing can be rejected by the trace options -> the kernel variant without the id tests
   bool wide4_big;     // the two-level records are addressed with 64-bit offsets
   int lds_entries;    // per-lane stack entries the variant keeps in LDS
   unsigned dbg;
   bool wide() const { return walk == Walk::OneLevel || walk == Walk::TwoLevel; }
   bool wide4() const { return walk == Walk::TwoLevel; }
-  bool query() const { return walk == Walk::QueryMotion || walk == Walk::QueryMasked || walk == Walk::QueryMotionMasked; }
-  bool query_motion() const { return walk == Walk::QueryMotion || walk == Walk::QueryMotionMasked; }
-  bool query_masked() const { return walk == Walk::QueryMasked || walk == Walk::QueryMotionMasked; }
-  bool multihit_query() const { return walk >= Walk::MultiHitIds && walk <= Walk::MultiHitMotionMasked; }
-  bool multihit_motion() const { return walk == Walk::MultiHitMotion || walk == Walk::MultiHitMotionMasked; }
-  bool multihit_masked() const { return walk == Walk::MultiHitMasked || walk == Walk::MultiHitMotionMasked; }
 };
 template <typename T>
 static WalkChoice choose_walk(const nrt_ctx *c, const TraverseLaunch<T> &l) {
@@ -171,7 +162,6 @@ static WalkChoice choose_walk(const nrt_ctx *c, const TraverseLaunch<T> &l) {
   w.dbg = c->debug_flags & ~(32u | 64u | 8192u); // (the counting / clocked instantiations live in libnanort_hip_prof.so)
 #endif
   const bool custom = c->prim_kind != kPrimTriangles; // the custom primitives share one launch geometry
-  const bool multihit = l.kind == Query::MultiHit;
   const bool use_wide = (c->wide || custom || l.kind == Query::Occlusion) && l.kind != Query::Count && c->d_wide && !l.own_walk();
   // two levels per step: closest-hit walks of nested fp32 triangle trees, outside the profiling / splitting variants
   w.plain_options = l.opt->prim_ids_range[0] == 0u && l.opt->prim_ids_range[1] >= c->num_faces && l.opt->skip_prim_id >= c->num_faces &&
@@ -185,10 +175,8 @@ static WalkChoice choose_walk(const nrt_ctx *c, const TraverseLaunch<T> &l) {
   w.wide4_big = c->num_branch_records >= (1ull << 25) || (c->wide4_big_ok == 2 && c->prim_kind == kPrimTriangles); // (2: forced, for the tests)
   const bool use_wide4 = use_wide && c->d_wide4 && c->wide_stack == 10 && c->tree_nested && c->root_is_branch && !prof_needs_w2 &&
                          (!w.wide4_big || (!custom && !c->order4 && !(w.dbg & (32u | 8192u))));
-  w.walk = l.kind == Query::MultiHitQuery
-               ? (l.with_motion ? (l.with_masks ? Walk::MultiHitMotionMasked : Walk::MultiHitMotion) : (l.with_masks ? Walk::MultiHitMasked : Walk::MultiHitIds))
-           : l.combined() ? (l.with_motion ? (l.with_masks ? Walk::QueryMotionMasked : Walk::QueryMotion) : Walk::QueryMasked)
-           : l.masked() ? Walk::Masked : l.motion() ? Walk::Motion : multihit ? Walk::MultiHit : (use_wide4 ? Walk::TwoLevel : (use_wide ? Walk::OneLevel : Walk::Literal));
+  w.own = l.own_walk_id();
+  w.walk = l.own_walk() ? Walk::Own : (use_wide4 ? Walk::TwoLevel : (use_wide ? Walk::OneLevel : Walk::Literal));
   w.lds_entries = l.own_walk() ? kLdsStackDefault : (use_wide4 ? kWide4LdsStack : (custom ? 10 : (use_wide ? c->wide_stack : c->lds_stack)));
   return w;
 }
@@ -196,15 +184,11 @@ static WalkChoice choose_walk(const nrt_ctx *c, const TraverseLaunch<T> &l) {
 // Persistent grid: every block resident.  A variant's occupancy is asked for once per context and key (what selects the kernel).
 template <typename T>
 static GridPlan size_grid(nrt_ctx *c, const WalkChoice &w, uint64_t n) {
-  auto &e = c->occupancy[(int)w.walk][c->prim_kind];
+  auto &e = c->occupancy[(int)w.walk + (w.walk == Walk::Own ? (int)w.own : 0)][c->prim_kind];
   if (e.blocks_per_cu == 0 || e.lds_entries != w.lds_entries)
-    e = {w.lds_entries, (unsigned)(w.multihit_query()        ? multihit_query_blocks_per_cu<T>(w.multihit_motion(), w.multihit_masked())
-                        : w.query()                 ? traverse_query_blocks_per_cu<T>(w.query_motion(), w.query_masked())
-                        : w.walk == Walk::Masked    ? traverse_masked_blocks_per_cu<T>()
-                        : w.walk == Walk::Motion    ? traverse_motion_blocks_per_cu<T>()
-                        : w.walk == Walk::MultiHit  ? traverse_multihit_blocks_per_cu<T>()
-                        : w.walk == Walk::Literal ? traverse_blocks_per_cu<T>(w.lds_entries)
-                                                  : traverse_wide_blocks_per_cu<T>(w.lds_entries, c->prim_kind, w.wide4()))};
+    e = {w.lds_entries, (unsigned)(w.walk == Walk::Own       ? own_walk_blocks_per_cu<T>(w.own)
+                                   : w.walk == Walk::Literal ? traverse_blocks_per_cu<T>(w.lds_entries)
+                                                             : traverse_wide_blocks_per_cu<T>(w.lds_entries, c->prim_kind, w.wide4()))};
   const unsigned per_cu = c->max_blocks_per_cu && e.blocks_per_cu > c->max_blocks_per_cu ? c->max_blocks_per_cu : e.blocks_per_cu;
   return plan_grid(n, kTraverseBlock, (uint32_t)c->num_cus, per_cu, c->num_parts);
 }
@@ -320,32 +304,9 @@ static nrt_status enqueue_launch(nrt_ctx *c, const TraverseLaunch<T> &l, const W
   a.done_publish = post_pass ? 0u : 1u;
   const bool timed = l.timed && !use_rec;
   if (timed) HIPCHK(c, hipEventRecord(slot->t0, s));
-  if (w.multihit_query()) {
-    static const char *const names[2][4] = {{"nrt::k_multihit_query<float, 32, false, false>", "nrt::k_multihit_query<float, 32, true, false>",
-                                             "nrt::k_multihit_query<float, 32, false, true>", "nrt::k_multihit_query<float, 32, true, true>"},
-                                            {"nrt::k_multihit_query<double, 32, false, false>", "nrt::k_multihit_query<double, 32, true, false>",
-                                             "nrt::k_multihit_query<double, 32, false, true>", "nrt::k_multihit_query<double, 32, true, true>"}};
-    static_assert(kLdsStackDefault == 32, "the names above carry the stack depth");
-    HIPCHK(c, launch_multihit_query<T>(a, l.max_hits, l.hit_counts, w.multihit_motion(), w.multihit_masked(), c->d_tris1, l.times,
-                                       (const uint32_t *)c->b_leaf_masks.p, l.ray_masks, grid, s));
-    c->last_kernel = names[sizeof(T) == 4 ? 0 : 1][(int)w.walk - (int)Walk::MultiHitIds];
-  } else if (w.query()) {
-    static const char *const names[2][3] = {{"nrt::k_traverse_query<float, 32, true, false>", "nrt::k_traverse_query<float, 32, false, true>",
-                                             "nrt::k_traverse_query<float, 32, true, true>"},
-                                            {"nrt::k_traverse_query<double, 32, true, false>", "nrt::k_traverse_query<double, 32, false, true>",
-                                             "nrt::k_traverse_query<double, 32, true, true>"}};
-    static_assert(kLdsStackDefault == 32, "the names above carry the stack depth");
-    HIPCHK(c, launch_traverse_query<T>(a, w.query_motion(), w.query_masked(), c->d_tris1, l.times, (const uint32_t *)c->b_leaf_masks.p, l.ray_masks, grid, s));
-    c->last_kernel = names[sizeof(T) == 4 ? 0 : 1][w.walk == Walk::QueryMotion ? 0 : w.walk == Walk::QueryMasked ? 1 : 2];
-  } else if (w.walk == Walk::Masked) {
-    HIPCHK(c, launch_traverse_masked<T>(a, (const uint32_t *)c->b_leaf_masks.p, l.ray_masks, grid, s));
-    c->last_kernel = sizeof(T) == 4 ? "nrt::k_traverse_masked<float>" : "nrt::k_traverse_masked<double>";
-  } else if (w.walk == Walk::Motion) {
-    HIPCHK(c, launch_traverse_motion<T>(a, c->d_tris1, l.times, grid, s));
-    c->last_kernel = sizeof(T) == 4 ? "nrt::k_traverse_motion<float>" : "nrt::k_traverse_motion<double>";
-  } else if (w.walk == Walk::MultiHit) {
-    HIPCHK(c, launch_traverse_multihit<T>(a, l.max_hits, l.hit_counts, grid, s));
-    c->last_kernel = sizeof(T) == 4 ? "nrt::k_traverse_multihit<float>" : "nrt::k_traverse_multihit<double>";
+  if (w.walk == Walk::Own) {
+    HIPCHK(c, (launch_own_walk<T>(w.own, a, {l.max_hits, l.hit_counts, c->d_tris1, l.times, (const uint32_t *)c->b_leaf_masks.p, l.ray_masks}, grid, s,
+                                  &c->last_kernel)));
   } else if (w.wide()) {
     HIPCHK(c, launch_traverse_wide<T>(a, grid, w.lds_entries, c->prim_kind, s, &c->last_kernel));
   } else {
@@ -376,7 +337,7 @@ static nrt_status enqueue_launch(nrt_ctx *c, const TraverseLaunch<T> &l, const W
   return NRT_OK;
 }
 
-// The leaf-order words of a masked launch (masked.hip): b_leaf_masks[k] = b_prim_masks[d_tris[k].prim_id], derived again whenever the
+// The leaf-order words of a masked launch (prims.hip, k_permute_masks): b_leaf_masks[k] = b_prim_masks[d_tris[k].prim_id], derived again whenever the
 // setter or free_tree said that it no longer is (ctx.h, leaf_masks_stale).  Under launch_mutex.  No launch reads the array meanwhile:
 // whoever set the flag waited for the launches in flight first, and no masked launch starts without passing here.  The host waits for
 // the kernel, on the context's own stream: launches on every stream may read the array once this returns, with no event between them
@@ -403,7 +364,7 @@ static nrt_status traverse_device(nrt_ctx *c, TraverseLaunch<T> l) {
   if (st || l.n == 0) return st;
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, refit_stream_wait(c, l.stream)); // (a Device refit in flight on another stream)
-  if (l.masked() && (st = refresh_leaf_masks<T>(c))) return st;
+  if (l.masked && (st = refresh_leaf_masks<T>(c))) return st;
   nrt_ctx::LaunchSlot *slot = nullptr;
   if ((st = take_slot(c, l.stream, &slot))) return st;
   const WalkChoice w = choose_walk(c, l);
@@ -453,7 +414,7 @@ static nrt_status multihit_check(nrt_ctx *c, const void *rays, uint64_t n, uint3
 template <typename T>
 static nrt_status query_device(nrt_ctx *c, const char *fn, const TraverseLaunch<T> &l) {
   if (!c) return NRT_ERR_INVALID;
-  if (l.kind == Query::MultiHit && !l.multihit_descriptor) {
+  if (l.multihit() && !l.multihit_descriptor) {
     const nrt_status st = multihit_check<T>(c, l.rays, l.n, l.max_hits, l.hits);
     if (st || l.n == 0) return st;
   }
@@ -485,7 +446,7 @@ static nrt_status query_host(nrt_ctx *c, const char *fn, const TraverseLaunch<T>
   // rays per launch: multi-hit keeps the staged records within kMultiHitStagedBytes (256 MiB) whatever K is; the motion queries go in traverse_host's pieces
   // (their staging stays as small as the pipeline's)
   const uint64_t chunk = multihit        ? std::max<uint64_t>(1u, std::min<uint64_t>(1ull << 26, kMultiHitStagedBytes / rec_bytes))
-                         : (host.motion() || host.masked()) ? kPiece
+                         : (host.motion || host.masked) ? kPiece
                                          : kStagedRays;
   std::lock_guard<std::mutex> host_lock(c->host_mutex);
   HIPCHK(c, hipSetDevice(c->device));
@@ -540,7 +501,7 @@ static bool is_pinned_host(const void *p) {
 // trace -> download, one after the other.  With PAGE-LOCKED buffers (nrtHostAlloc) the batch is cut into pieces and
 // pipelined over three streams — piece k+1 uploads while piece k is traced and piece k-1 downloads (PCIe is full duplex) —
 // so the call approaches the slower of the two copy directions instead of their sum plus the kernel.
-// `host`: a Closest, Motion, Masked or Combined query over the caller's host arrays (skip ids, times and ray masks may be null).  Whether the call takes the
+// `host`: a Closest query, with or without motion and masks, over the caller's host arrays (skip ids, times and ray masks may be null).  Whether the call takes the
 // pipeline is read off its size and its pointers before the lock; every other call, the refusals included, is query_host's.
 template <typename T>
 static nrt_status traverse_host(nrt_ctx *c, const TraverseLaunch<T> &host) {
@@ -587,7 +548,7 @@ static nrt_status traverse_host(nrt_ctx *c, const TraverseLaunch<T> &host) {
       HIPCHK(c, hipEventRecord(c->ev_in[b], c->copy_in));
       HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_in[b], 0));
       if (piece >= 2) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_out[b], 0));
-      TraverseLaunch<T> l = host; // (its kind and what a Combined launch carries besides)
+      TraverseLaunch<T> l = host; // (its kind, motion, masked and where it came from)
       l.rays = d_r, l.n = m, l.stream = c->stream, l.timed = true, l.hits = d_h, l.mask = d_m, l.skip_ids = d_s, l.times = d_t, l.ray_masks = d_v;
       st = traverse_device<T>(c, l);
       if (st) { // (copies into the caller's buffers may still be in flight: let them land before the call returns)
@@ -606,7 +567,7 @@ static nrt_status traverse_host(nrt_ctx *c, const TraverseLaunch<T> &host) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return NRT_OK;
   }
-  return query_host<T>(c, host.descriptor ? "nrtQueryBatch" : host.masked() ? "nrtTraverseBatchMasked" : "nrtTraverseBatch", host);
+  return query_host<T>(c, host.descriptor ? "nrtQueryBatch" : host.masked ? "nrtTraverseBatchMasked" : "nrtTraverseBatch", host);
 }
 
 // One host batch spread over several contexts — one per GPU of the node, each holding the same tree (the build is
@@ -830,8 +791,8 @@ static nrt_status traverse_batches_host(nrt_ctx *c, uint32_t nb, const typename 
 }
 
 // nrtQueryBatch* (include/nanort_hip.h, "one descriptor for every triangle ray query"): the descriptor's own refusals, then the launch
-// it describes.  A descriptor an existing entry point can express becomes exactly that entry point's launch — the same kind, the
-// same arrays, hence the same kernel and the same bytes; two or more of {ids, MOTION, MASKED} become a Combined launch (query.hip).
+// it describes — its arrays and flags copied into a TraverseLaunch.  That a descriptor an existing entry point can express runs that
+// entry point's kernel and writes its bytes follows from own_walk_id(), which sees no difference between the two launches.
 // D: nrt_ray_query_f32 / _f64.  `device`: the arrays are the caller's device memory and `stream` its stream.
 template <typename T, typename D>
 static nrt_status query_batch(nrt_ctx *c, const D *q, bool device, void *stream) {
@@ -845,12 +806,8 @@ static nrt_status query_batch(nrt_ctx *c, const D *q, bool device, void *stream)
   if (q->num_rays > 0x7FFFFFFFull) return fail(c, NRT_ERR_INVALID, "%s: more than 2^31-1 rays in one call", fn);
   if (q->num_rays && !q->rays) return fail(c, NRT_ERR_INVALID, "%s: NULL rays", fn);
   if (q->num_rays && !(occ ? (const void *)q->mask_out : (const void *)q->hits_out)) return fail(c, NRT_ERR_INVALID, "%s: NULL %s", fn, occ ? "mask_out" : "hits_out");
-  const bool ids = q->skip_prim_ids != nullptr;
   TraverseLaunch<T> l = {};
-  l.kind = ((int)ids + (int)motion + (int)masked >= 2) ? (occ ? Query::CombinedOcclusion : Query::Combined)
-           : motion                                    ? (occ ? Query::MotionOcclusion : Query::Motion)
-           : masked                                    ? (occ ? Query::MaskedOcclusion : Query::Masked)
-                                                       : (occ ? Query::Occlusion : Query::Closest);
+  l.kind = occ ? Query::Occlusion : Query::Closest;
   l.rays = q->rays;
   l.n = q->num_rays;
   l.opt = q->options;
@@ -859,8 +816,8 @@ static nrt_status query_batch(nrt_ctx *c, const D *q, bool device, void *stream)
   l.skip_ids = q->skip_prim_ids;
   l.times = motion ? q->times : nullptr;         // (an array whose flag is not set is not read)
   l.ray_masks = masked ? q->ray_masks : nullptr;
-  l.with_motion = motion;
-  l.with_masks = masked;
+  l.motion = motion;
+  l.masked = masked;
   l.descriptor = true;
   if (device) {
     l.stream = (hipStream_t)stream;
@@ -871,9 +828,9 @@ static nrt_status query_batch(nrt_ctx *c, const D *q, bool device, void *stream)
 }
 
 // nrtMultiHitQueryBatch* (include/nanort_hip.h, "multi-hit with per-ray skip ids, visibility words and motion times"): the descriptor's
-// own refusals and the context's, every one under the entry point's name, then the launch it describes.  A descriptor with no flag and
-// no ids IS nrtMultiHitTraverseBatch* — a MultiHit launch: the same kernel, the same bytes; everything else is a MultiHitQuery launch
-// (multihit_query.hip), ids alone included.  D: nrt_multihit_query_f32 / _f64.  `device`: as query_batch's.
+// own refusals and the context's, every one under the entry point's name, then the launch it describes: a MultiHit launch with the
+// descriptor's arrays and flags (none of them: nrtMultiHitTraverseBatch*'s kernel and bytes — own_walk_id()).
+// D: nrt_multihit_query_f32 / _f64.  `device`: as query_batch's.
 template <typename T, typename D>
 static nrt_status multihit_query_batch(nrt_ctx *c, const D *q, bool device, void *stream) {
   const char *fn = device ? "nrtMultiHitQueryBatchDevice" : "nrtMultiHitQueryBatch";
@@ -885,7 +842,7 @@ static nrt_status multihit_query_batch(nrt_ctx *c, const D *q, bool device, void
   if (q->flags & ~known) return fail(c, NRT_ERR_INVALID, "%s: unknown flag bits 0x%x", fn, q->flags & ~known);
   if (q->reserved != 0u) return fail(c, NRT_ERR_INVALID, "%s: reserved is %u, must be 0", fn, q->reserved);
   if (q->max_hits == 0u || q->max_hits > NRT_MAX_MULTIHIT) return fail(c, NRT_ERR_INVALID, "%s: max_hits %u outside 1..%u", fn, q->max_hits, NRT_MAX_MULTIHIT);
-  const bool motion = (q->flags & NRT_QUERY_MOTION) != 0u, masked = (q->flags & NRT_QUERY_MASKED) != 0u, ids = q->skip_prim_ids != nullptr;
+  const bool motion = (q->flags & NRT_QUERY_MOTION) != 0u, masked = (q->flags & NRT_QUERY_MASKED) != 0u;
   if (q->num_rays > 0x7FFFFFFFull) return fail(c, NRT_ERR_INVALID, "%s: more than 2^31-1 rays in one call", fn);
   if (q->num_rays && !q->rays) return fail(c, NRT_ERR_INVALID, "%s: NULL rays", fn);
   if (q->num_rays && !q->hits_out) return fail(c, NRT_ERR_INVALID, "%s: NULL hits_out", fn);
@@ -902,7 +859,7 @@ static nrt_status multihit_query_batch(nrt_ctx *c, const D *q, bool device, void
   if (!c->d_nodes) return fail(c, NRT_ERR_INVALID, "%s: no tree (call nrtBuild or nrtSetTree)", fn);
   if (q->num_rays == 0) return NRT_OK;
   TraverseLaunch<T> l = {};
-  l.kind = (ids || motion || masked) ? Query::MultiHitQuery : Query::MultiHit;
+  l.kind = Query::MultiHit;
   l.rays = q->rays;
   l.n = q->num_rays;
   l.opt = q->options;
@@ -912,8 +869,8 @@ static nrt_status multihit_query_batch(nrt_ctx *c, const D *q, bool device, void
   l.skip_ids = q->skip_prim_ids;
   l.times = motion ? q->times : nullptr;         // (an array whose flag is not set is not read)
   l.ray_masks = masked ? q->ray_masks : nullptr;
-  l.with_motion = motion;
-  l.with_masks = masked;
+  l.motion = motion;
+  l.masked = masked;
   l.multihit_descriptor = true;
   if (device) {
     l.stream = (hipStream_t)stream;
@@ -1076,73 +1033,73 @@ nrt_status nrtTraverseBatchesSkip_f64(nrt_ctx *c, uint32_t nb, const nrt_ray_f64
 // Motion blur (include/nanort_hip.h; the keyframe's setter: api_geometry.hip): the closest-hit and occlusion queries with one time per ray.
 nrt_status nrtTraverseBatchMotion_f32(nrt_ctx *c, const nrt_ray_f32 *r, const float *t, uint64_t n, const nrt_trace_options *o, nrt_hit_f32 *h,
                                       uint8_t *m) {
-  return traverse_host<float>(c, {.kind = Query::Motion, .rays = r, .n = n, .opt = o, .hits = h, .mask = m, .times = t});
+  return traverse_host<float>(c, {.kind = Query::Closest, .rays = r, .n = n, .opt = o, .hits = h, .mask = m, .times = t, .motion = true});
 }
 nrt_status nrtTraverseBatchMotion_f64(nrt_ctx *c, const nrt_ray_f64 *r, const double *t, uint64_t n, const nrt_trace_options *o, nrt_hit_f64 *h,
                                       uint8_t *m) {
-  return traverse_host<double>(c, {.kind = Query::Motion, .rays = r, .n = n, .opt = o, .hits = h, .mask = m, .times = t});
+  return traverse_host<double>(c, {.kind = Query::Closest, .rays = r, .n = n, .opt = o, .hits = h, .mask = m, .times = t, .motion = true});
 }
 nrt_status nrtTraverseBatchMotionDevice_f32(nrt_ctx *c, const nrt_ray_f32 *r, const float *t, uint64_t n, const nrt_trace_options *o,
                                             nrt_hit_f32 *h, uint8_t *m, void *s) {
-  return query_device<float>(c, "nrtTraverseBatchMotionDevice", {.kind = Query::Motion, .rays = r, .n = n, .opt = o, .stream = (hipStream_t)s, .timed = true,
-                                                                 .hits = h, .mask = m, .times = t});
+  return query_device<float>(c, "nrtTraverseBatchMotionDevice", {.kind = Query::Closest, .rays = r, .n = n, .opt = o, .stream = (hipStream_t)s, .timed = true,
+                                                                 .hits = h, .mask = m, .times = t, .motion = true});
 }
 nrt_status nrtTraverseBatchMotionDevice_f64(nrt_ctx *c, const nrt_ray_f64 *r, const double *t, uint64_t n, const nrt_trace_options *o,
                                             nrt_hit_f64 *h, uint8_t *m, void *s) {
-  return query_device<double>(c, "nrtTraverseBatchMotionDevice", {.kind = Query::Motion, .rays = r, .n = n, .opt = o, .stream = (hipStream_t)s, .timed = true,
-                                                                  .hits = h, .mask = m, .times = t});
+  return query_device<double>(c, "nrtTraverseBatchMotionDevice", {.kind = Query::Closest, .rays = r, .n = n, .opt = o, .stream = (hipStream_t)s, .timed = true,
+                                                                  .hits = h, .mask = m, .times = t, .motion = true});
 }
 nrt_status nrtOccludedBatchMotion_f32(nrt_ctx *c, const nrt_ray_f32 *r, const float *t, uint64_t n, const nrt_trace_options *o, uint8_t *m) {
-  return query_host<float>(c, "nrtOccludedBatch", {.kind = Query::MotionOcclusion, .rays = r, .n = n, .opt = o, .mask = m, .times = t});
+  return query_host<float>(c, "nrtOccludedBatch", {.kind = Query::Occlusion, .rays = r, .n = n, .opt = o, .mask = m, .times = t, .motion = true});
 }
 nrt_status nrtOccludedBatchMotion_f64(nrt_ctx *c, const nrt_ray_f64 *r, const double *t, uint64_t n, const nrt_trace_options *o, uint8_t *m) {
-  return query_host<double>(c, "nrtOccludedBatch", {.kind = Query::MotionOcclusion, .rays = r, .n = n, .opt = o, .mask = m, .times = t});
+  return query_host<double>(c, "nrtOccludedBatch", {.kind = Query::Occlusion, .rays = r, .n = n, .opt = o, .mask = m, .times = t, .motion = true});
 }
 nrt_status nrtOccludedBatchMotionDevice_f32(nrt_ctx *c, const nrt_ray_f32 *r, const float *t, uint64_t n, const nrt_trace_options *o, uint8_t *m,
                                             void *s) {
-  return query_device<float>(c, "nrtOccludedBatchMotionDevice", {.kind = Query::MotionOcclusion, .rays = r, .n = n, .opt = o, .stream = (hipStream_t)s, .timed = true,
-                                                                 .mask = m, .times = t});
+  return query_device<float>(c, "nrtOccludedBatchMotionDevice", {.kind = Query::Occlusion, .rays = r, .n = n, .opt = o, .stream = (hipStream_t)s, .timed = true,
+                                                                 .mask = m, .times = t, .motion = true});
 }
 nrt_status nrtOccludedBatchMotionDevice_f64(nrt_ctx *c, const nrt_ray_f64 *r, const double *t, uint64_t n, const nrt_trace_options *o, uint8_t *m,
                                             void *s) {
-  return query_device<double>(c, "nrtOccludedBatchMotionDevice", {.kind = Query::MotionOcclusion, .rays = r, .n = n, .opt = o, .stream = (hipStream_t)s, .timed = true,
-                                                                  .mask = m, .times = t});
+  return query_device<double>(c, "nrtOccludedBatchMotionDevice", {.kind = Query::Occlusion, .rays = r, .n = n, .opt = o, .stream = (hipStream_t)s, .timed = true,
+                                                                  .mask = m, .times = t, .motion = true});
 }
 
 // Visibility masks (include/nanort_hip.h; the triangles' words: api_geometry.hip): the closest-hit and occlusion queries with one word per ray.
 nrt_status nrtTraverseBatchMasked_f32(nrt_ctx *c, const nrt_ray_f32 *r, const uint32_t *v, uint64_t n, const nrt_trace_options *o, nrt_hit_f32 *h,
                                       uint8_t *m) {
-  return traverse_host<float>(c, {.kind = Query::Masked, .rays = r, .n = n, .opt = o, .hits = h, .mask = m, .ray_masks = v});
+  return traverse_host<float>(c, {.kind = Query::Closest, .rays = r, .n = n, .opt = o, .hits = h, .mask = m, .ray_masks = v, .masked = true});
 }
 nrt_status nrtTraverseBatchMasked_f64(nrt_ctx *c, const nrt_ray_f64 *r, const uint32_t *v, uint64_t n, const nrt_trace_options *o, nrt_hit_f64 *h,
                                       uint8_t *m) {
-  return traverse_host<double>(c, {.kind = Query::Masked, .rays = r, .n = n, .opt = o, .hits = h, .mask = m, .ray_masks = v});
+  return traverse_host<double>(c, {.kind = Query::Closest, .rays = r, .n = n, .opt = o, .hits = h, .mask = m, .ray_masks = v, .masked = true});
 }
 nrt_status nrtTraverseBatchMaskedDevice_f32(nrt_ctx *c, const nrt_ray_f32 *r, const uint32_t *v, uint64_t n, const nrt_trace_options *o,
                                             nrt_hit_f32 *h, uint8_t *m, void *s) {
-  return query_device<float>(c, "nrtTraverseBatchMaskedDevice", {.kind = Query::Masked, .rays = r, .n = n, .opt = o, .stream = (hipStream_t)s, .timed = true,
-                                                                 .hits = h, .mask = m, .ray_masks = v});
+  return query_device<float>(c, "nrtTraverseBatchMaskedDevice", {.kind = Query::Closest, .rays = r, .n = n, .opt = o, .stream = (hipStream_t)s, .timed = true,
+                                                                 .hits = h, .mask = m, .ray_masks = v, .masked = true});
 }
 nrt_status nrtTraverseBatchMaskedDevice_f64(nrt_ctx *c, const nrt_ray_f64 *r, const uint32_t *v, uint64_t n, const nrt_trace_options *o,
                                             nrt_hit_f64 *h, uint8_t *m, void *s) {
-  return query_device<double>(c, "nrtTraverseBatchMaskedDevice", {.kind = Query::Masked, .rays = r, .n = n, .opt = o, .stream = (hipStream_t)s, .timed = true,
-                                                                  .hits = h, .mask = m, .ray_masks = v});
+  return query_device<double>(c, "nrtTraverseBatchMaskedDevice", {.kind = Query::Closest, .rays = r, .n = n, .opt = o, .stream = (hipStream_t)s, .timed = true,
+                                                                  .hits = h, .mask = m, .ray_masks = v, .masked = true});
 }
 nrt_status nrtOccludedBatchMasked_f32(nrt_ctx *c, const nrt_ray_f32 *r, const uint32_t *v, uint64_t n, const nrt_trace_options *o, uint8_t *m) {
-  return query_host<float>(c, "nrtOccludedBatchMasked", {.kind = Query::MaskedOcclusion, .rays = r, .n = n, .opt = o, .mask = m, .ray_masks = v});
+  return query_host<float>(c, "nrtOccludedBatchMasked", {.kind = Query::Occlusion, .rays = r, .n = n, .opt = o, .mask = m, .ray_masks = v, .masked = true});
 }
 nrt_status nrtOccludedBatchMasked_f64(nrt_ctx *c, const nrt_ray_f64 *r, const uint32_t *v, uint64_t n, const nrt_trace_options *o, uint8_t *m) {
-  return query_host<double>(c, "nrtOccludedBatchMasked", {.kind = Query::MaskedOcclusion, .rays = r, .n = n, .opt = o, .mask = m, .ray_masks = v});
+  return query_host<double>(c, "nrtOccludedBatchMasked", {.kind = Query::Occlusion, .rays = r, .n = n, .opt = o, .mask = m, .ray_masks = v, .masked = true});
 }
 nrt_status nrtOccludedBatchMaskedDevice_f32(nrt_ctx *c, const nrt_ray_f32 *r, const uint32_t *v, uint64_t n, const nrt_trace_options *o, uint8_t *m,
                                             void *s) {
-  return query_device<float>(c, "nrtOccludedBatchMaskedDevice", {.kind = Query::MaskedOcclusion, .rays = r, .n = n, .opt = o, .stream = (hipStream_t)s, .timed = true,
-                                                                 .mask = m, .ray_masks = v});
+  return query_device<float>(c, "nrtOccludedBatchMaskedDevice", {.kind = Query::Occlusion, .rays = r, .n = n, .opt = o, .stream = (hipStream_t)s, .timed = true,
+                                                                 .mask = m, .ray_masks = v, .masked = true});
 }
 nrt_status nrtOccludedBatchMaskedDevice_f64(nrt_ctx *c, const nrt_ray_f64 *r, const uint32_t *v, uint64_t n, const nrt_trace_options *o, uint8_t *m,
                                             void *s) {
-  return query_device<double>(c, "nrtOccludedBatchMaskedDevice", {.kind = Query::MaskedOcclusion, .rays = r, .n = n, .opt = o, .stream = (hipStream_t)s, .timed = true,
-                                                                  .mask = m, .ray_masks = v});
+  return query_device<double>(c, "nrtOccludedBatchMaskedDevice", {.kind = Query::Occlusion, .rays = r, .n = n, .opt = o, .stream = (hipStream_t)s, .timed = true,
+                                                                  .mask = m, .ray_masks = v, .masked = true});
 }
 
 // One descriptor for every triangle ray query (include/nanort_hip.h): skip ids, words and times on the same ray.

@@ -1,9 +1,9 @@
 // nanort_amd/csrc/binary_walk_dev.h — THE one statement of the reference's binary while-while loop (BVHAccel::Traverse,
 // nanort.h:2487-2556) as a persistent-threads walk: one ray per lane, rays claimed in chunks and handed to idle lanes by ballot rank,
-// inner nodes until a lane reaches a leaf, the leaves of the whole wave together, then pop or finish.  Six kernels run it —
-// k_traverse (traverse.hip), k_traverse_multihit (multihit.hip), k_traverse_motion (motion.hip), k_traverse_masked (masked.hip),
-// k_traverse_query (query.hip), k_multihit_query (multihit_query.hip) — each with its own __shared__ stack array and a QUERY: a compile-time type that says what the kernels
-// do differently, and nothing else.
+// inner nodes until a lane reaches a leaf, the leaves of the whole wave together, then pop or finish.  k_traverse (traverse.hip)
+// runs it, and the five kernels of own_walks.hip (k_traverse_multihit, k_traverse_motion, k_traverse_masked, k_traverse_query,
+// k_multihit_query) — each with its own __shared__ stack array and a QUERY: a compile-time type that says what the kernels do
+// differently, and nothing else.
 //
 // A query Q derives from BinaryQuery and states (every member __forceinline__; `a` is the launch block, `L` the lane's ray):
 //   Ray  load(a, rid)                       the ray a lane takes at a refill

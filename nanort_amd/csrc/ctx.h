@@ -35,6 +35,9 @@ using namespace nrt;
 
 inline thread_local std::string g_create_error; // why the calling thread's last nrtCreate / nrtHostAlloc failed (nrtLastError(NULL))
 
+// The kernel a traversal launch runs (api_query.hip, choose_walk): k_traverse, k_traverse_wide of WIDTH 2 / 4, or one of own_walks.hip's.
+enum class Walk { Literal, OneLevel, TwoLevel, Own };
+
 struct nrt_ctx {
   int device = 0;
   hipStream_t stream = nullptr; // internal stream for host entry points / build
@@ -152,8 +155,9 @@ struct nrt_ctx {
   int leaf_compact = 1; // walk_dev.h "leaf items" (leaf_items_one_trip, round 6): when the records of all the lanes waiting at a leaf fit one trip of the wave, they are tested one per lane with the owner's ray constants and accepted by the owner in record order — records bit-identical, C3 +2 %, C4 tile +2.8 %; 0: every owner tests its own records
   int dyn_head = 1; // batches too small for a static group per wave: every wave's first chunk is its own (traverse.hip claim_init; tunable dyn_head)
   int wide_scramble = 0; // probe (tunable wide_scramble): the private node records in a pseudo-random order instead of pre-order
-  // resident blocks per CU of the variants launched so far, by what selects the kernel: [walk][primitive kind] at `lds_entries` (a context keeps one precision; size_grid)
-  struct { int lds_entries; unsigned blocks_per_cu; } occupancy[13][kNumPrimKinds] = {}; // (api_query.hip, enum Walk: its thirteen values)
+  // resident blocks per CU of the variants launched so far, by what selects the kernel: [walk][primitive kind] at `lds_entries` (a context
+  // keeps one precision; api_query.hip, size_grid).  A row per Walk, the own walks' rows (kernels.h, OwnWalk) in the place of Walk::Own's.
+  struct { int lds_entries; unsigned blocks_per_cu; } occupancy[(int)Walk::Own + kNumOwnWalks][kNumPrimKinds] = {};
 
   hipEvent_t ev_b0 = nullptr, ev_b1 = nullptr;
   hipEvent_t ev_build_state = nullptr; // the builder's state block has reached build_state
@@ -171,7 +175,7 @@ struct nrt_ctx {
   void *d_tris1 = nullptr;  // == b_tris1.p while a keyframe and a tree are present
 
   // visibility masks (nrtSetPrimMasks*): one word per face in face order, and the same words in leaf order beside
-  // d_tris (masked.hip, k_permute_masks).  leaf_masks_stale: b_leaf_masks is not the permutation of b_prim_masks by the current
+  // d_tris (prims.hip, k_permute_masks).  leaf_masks_stale: b_leaf_masks is not the permutation of b_prim_masks by the current
   // leaf order.  Set by the two events that can make it so — the setter (new words) and free_tree (every path to a new leaf order
   // passes it: nrtBuild, nrtSetTree, the mesh and keyframe setters; a refit rewrites d_tris in the same order and leaves it) —
   // and cleared by the one place that derives the array, the first masked query behind them (api_query.hip, refresh_leaf_masks).

@@ -51,49 +51,32 @@ hipError_t launch_scene_list(SceneListForm form, const TreeViewF32 &top, const n
                              uint32_t cap, float *list_t, uint32_t *list_node, uint32_t *count, const uint32_t *subset, const uint32_t *inst_masks,
                              const uint32_t *ray_masks, hipStream_t s);
 
-// ---- multihit.hip -----------------------------------------------------------------------------------------------------
+// ---- own_walks.hip: the triangle queries with a binary walk of their own (multi-hit, motion, masks, the three per-ray inputs combined) ----
+// One id per kernel; which of them a launch runs: api_query.hip, TraverseLaunch::own_walk_id.
+enum OwnWalk : int {
+  kOwnMultiHit,                                                                       // k_traverse_multihit
+  kOwnMotion,                                                                         // k_traverse_motion
+  kOwnMasked,                                                                         // k_traverse_masked
+  kOwnQueryMotion, kOwnQueryMasked, kOwnQueryMotionMasked,                            // k_traverse_query<MOTION, MASKED>, with or without ids
+  kOwnMultiHitIds, kOwnMultiHitMotion, kOwnMultiHitMasked, kOwnMultiHitMotionMasked,  // k_multihit_query<MOTION, MASKED>, with or without ids
+  kNumOwnWalks
+};
+// What such a launch reads and writes besides its TraverseArgs (args.skip_ids: the per-ray skip ids; args.any_hit: the occlusion query).
+// A walk reads the members of its own features only.
 template <typename T>
-hipError_t launch_traverse_multihit(const TraverseArgs<T> &args, uint32_t max_hits, uint32_t *counts, unsigned grid, hipStream_t s);
+struct OwnWalkInputs {
+  uint32_t max_hits;          // multi-hit: K; args.hits holds K records per ray
+  uint32_t *counts;           // multi-hit: held hits per ray, may be null
+  const void *tris1;          // motion: the LeafTri<T> records of keyframe 1 in leaf order
+  const T *times;             // motion: one time per ray, or null (every ray at time 0)
+  const uint32_t *leaf_masks; // masked: the faces' words in leaf order, one beside each LeafTri<T> of args.tris
+  const uint32_t *ray_masks;  // masked: one word per ray, or null (every ray 0xFFFFFFFF)
+};
+// (hipErrorInvalidValue: a motion walk without tris1, a masked walk without leaf_masks; `name_out`: as launch_traverse_wide's)
 template <typename T>
-int traverse_multihit_blocks_per_cu();
-
-// ---- multihit_query.hip: multi-hit under the combined intersector (per-ray skip ids in args.skip_ids, motion times, visibility words) ----
-// `motion` / `masked` select the instantiation (neither: ids alone); the arrays of a feature that is off are not read.
-// `max_hits`, `counts`: as launch_traverse_multihit's; `tris1`, `times`: as launch_traverse_motion's; `leaf_masks`, `ray_masks`: as
-// launch_traverse_masked's
+hipError_t launch_own_walk(OwnWalk w, const TraverseArgs<T> &args, const OwnWalkInputs<T> &in, unsigned grid, hipStream_t s, const char **name_out);
 template <typename T>
-hipError_t launch_multihit_query(const TraverseArgs<T> &args, uint32_t max_hits, uint32_t *counts, bool motion, bool masked, const void *tris1, const T *times,
-                                 const uint32_t *leaf_masks, const uint32_t *ray_masks, unsigned grid, hipStream_t s);
-template <typename T>
-int multihit_query_blocks_per_cu(bool motion, bool masked);
-
-// ---- motion.hip: the motion-blur walk (a triangle context with a second vertex keyframe) --------------------------------------
-// `tris1`: the LeafTri<T> records of keyframe 1 in leaf order; `times`: one time per ray, or null (every ray at time 0);
-// args.any_hit: the occlusion query
-template <typename T>
-hipError_t launch_traverse_motion(const TraverseArgs<T> &args, const void *tris1, const T *times, unsigned grid, hipStream_t s);
-template <typename T>
-int traverse_motion_blocks_per_cu();
-
-// ---- masked.hip: the visibility-mask walk (a triangle context with one 32-bit word per face) -----------------------------------
-// `leaf_masks`: the faces' words in leaf order, one beside each LeafTri<T> of args.tris; `ray_masks`: one word per ray, or null
-// (every ray 0xFFFFFFFF); args.any_hit: the occlusion query
-template <typename T>
-hipError_t launch_traverse_masked(const TraverseArgs<T> &args, const uint32_t *leaf_masks, const uint32_t *ray_masks, unsigned grid, hipStream_t s);
-template <typename T>
-int traverse_masked_blocks_per_cu();
-// leaf_masks[k] = masks[tris[k].prim_id] for the `n` LeafTri<T> records of `tris` (`masks`: num_faces words in face order)
-template <typename T>
-hipError_t launch_permute_masks(const void *tris, const uint32_t *masks, uint32_t num_faces, uint32_t *leaf_masks, uint32_t n, hipStream_t s);
-
-// ---- query.hip: the combined walk (two or more of: per-ray skip ids in args.skip_ids, motion times, visibility words) --------------
-// `motion` / `masked` select the instantiation (at least one of them); the arrays of a feature that is off are not read.
-// `tris1`, `times`: as launch_traverse_motion's; `leaf_masks`, `ray_masks`: as launch_traverse_masked's; args.any_hit: the occlusion query
-template <typename T>
-hipError_t launch_traverse_query(const TraverseArgs<T> &args, bool motion, bool masked, const void *tris1, const T *times, const uint32_t *leaf_masks,
-                                 const uint32_t *ray_masks, unsigned grid, hipStream_t s);
-template <typename T>
-int traverse_query_blocks_per_cu(bool motion, bool masked);
+int own_walk_blocks_per_cu(OwnWalk w);
 
 // ---- build.hip --------------------------------------------------------------------------------------------------------
 enum : unsigned { kBuildMorton = 1u, kBuildSubtreeDfs = 2u }; // gpu_build's build_flags: Morton pre-pass, one-node-per-step subtree kernel
@@ -143,6 +126,9 @@ hipError_t launch_max_index(const uint32_t *faces, uint64_t n_indices, uint32_t 
 // are multiples of sizeof(T), byte loads otherwise)
 template <typename T>
 hipError_t launch_gather_vertices(const void *src, size_t stride, uint32_t nv, T *tight, hipStream_t s);
+// leaf_masks[k] = masks[tris[k].prim_id] for the `n` LeafTri<T> records of `tris` (`masks`: num_faces words in face order)
+template <typename T>
+hipError_t launch_permute_masks(const void *tris, const uint32_t *masks, uint32_t num_faces, uint32_t *leaf_masks, uint32_t n, hipStream_t s);
 hipError_t launch_cylinder_segments(const float *verts, const float *radii, const uint32_t *seg_off, uint32_t n, float *seg_verts,
                                     float *seg_radii, uint32_t *seg_prim, hipStream_t s);
 // the kind's Leaf* record (common.h) for each of the `n` slots of `indices`, into `out` (`faces`: triangles only, `radii`: the others)

@@ -7,6 +7,7 @@
 //                                    the caller's num_vertices is checked against it before any vertex is read; strided rows ->
 //                                    the context's tight xyz (also the vertex pass of a refit, refit.hip).  max over u32 is exact
 //                                    and order-free: the word never depends on scheduling.
+//   k_permute_masks                  the triangles' visibility words (nrtSetPrimMasks*) in leaf order, for the masked walks
 //   k_cylinder_segments              long cylinders cut into segments for the builder (nrtSetCylinders)
 //   k_gather_leaf_*                  leaf-ordered primitive records from the index array of a tree (launch_gather_leaf)
 //   k_sphere_uv, k_cylinder_post,    the pass behind a walk over spheres, cylinders, curves (launch_post_pass): it finishes the
@@ -95,6 +96,24 @@ hipError_t launch_gather_vertices(const void *src, size_t stride, uint32_t nv, T
   return hipGetLastError();
 }
 
+// leaf_masks[k] = masks[tris[k].prim_id]: one thread per leaf record, the grid covers them all.  (tris[k].prim_id < num_faces by
+// construction: the builder emits a permutation of the face ids, nrtSetTree checks every index; read with a guard all the same.)
+// Derived whenever either side of that permutation changed (api_query.hip, refresh_leaf_masks).
+template <typename T>
+__global__ __launch_bounds__(256) void k_permute_masks(const LeafTri<T> *__restrict__ tris, const uint32_t *__restrict__ masks, uint32_t num_faces,
+                                                       uint32_t *__restrict__ leaf_masks, uint32_t n) {
+  const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+  if (k >= n) return;
+  const uint32_t p = tris[k].prim_id;
+  leaf_masks[k] = p < num_faces ? masks[p] : 0u;
+}
+
+template <typename T>
+hipError_t launch_permute_masks(const void *tris, const uint32_t *masks, uint32_t num_faces, uint32_t *leaf_masks, uint32_t n, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL((k_permute_masks<T>), dim3((n + 255u) / 256u), dim3(256), 0, s, (const LeafTri<T> *)tris, masks, num_faces, leaf_masks, n);
+  return hipGetLastError();
+}
 
 // ---------------------------------------------------------------------------
 // Long cylinders, cut into SEGMENTS for the builder (round 5).  The cylinder example's scene is box-spanning needles (random
@@ -443,6 +462,7 @@ hipError_t launch_post_pass(int kind, const typename Wire<T>::Ray *rays, typenam
 }
 
 NRT_INSTANTIATE_F32_F64(launch_gather_vertices)
+NRT_INSTANTIATE_F32_F64(launch_permute_masks)
 NRT_INSTANTIATE_F32_F64(leaf_record_bytes)
 NRT_INSTANTIATE_F32_F64(launch_gather_leaf)
 NRT_INSTANTIATE_F32_F64(launch_post_pass)

@@ -1,5 +1,5 @@
 // nanort_amd/csrc/traverse_dev.h — the device pieces of the binary-loop traversal that more than one kernel file uses
-// (traverse.hip and scene_kernels.hip through walk_dev.h; traverse.hip, multihit.hip and motion.hip through binary_walk_dev.h, which
+// (traverse.hip and scene_kernels.hip through walk_dev.h; traverse.hip and own_walks.hip through binary_walk_dev.h, which
 // states the loop itself): ray setup, slab and primitive tests, ray claims, streaming loads / stores, completion records, the lane
 // stack and, at the end, the host side of a persistent launch.  Everything here is a template, forceinline device code or a static
 // host function, so each including file compiles its own copy.

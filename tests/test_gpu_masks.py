@@ -1,4 +1,4 @@
-"""Visibility masks on the GPU (nanort_amd/csrc/masked.hip; include/nanort_hip.h, "visibility masks"): one 32-bit word
+"""Visibility masks on the GPU (nanort_amd/csrc/own_walks.hip; include/nanort_hip.h, "visibility masks"): one 32-bit word
 per triangle, one per ray, and a triangle exists for a ray iff the two share a bit.
 
 Parity is exact.  For the rays that share one mask word the expected records are oracle.traverse — the project's pinned restatement

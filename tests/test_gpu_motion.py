@@ -1,4 +1,4 @@
-"""Motion blur on the GPU (nanort_amd/csrc/motion.hip; include/nanort_hip.h, "motion blur"): a second vertex
+"""Motion blur on the GPU (nanort_amd/csrc/own_walks.hip; include/nanort_hip.h, "motion blur"): a second vertex
 keyframe per triangle context and one time per ray.
 
 Parity is exact.  For the rays that share one clamped time s the expected records are oracle.traverse — the project's pinned

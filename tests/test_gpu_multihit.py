@@ -1,4 +1,4 @@
-"""Multi-hit traversal on the GPU (nanort_amd/csrc/multihit.hip, include/nanort_hip.h nrtMultiHitTraverseBatch*): every byte of
+"""Multi-hit traversal on the GPU (nanort_amd/csrc/own_walks.hip, include/nanort_hip.h nrtMultiHitTraverseBatch*): every byte of
 the hit rows and counts equals the CPU model of the contract (tests/multihit_model.c) on the same node array; K = 1 is closest hit
 up to exact-t ties; layers, shared edges, the device entry on several streams, the header's batch method, error paths, and
 rebuilds that wait for multi-hit launches in flight."""

@@ -1,5 +1,5 @@
 """Multi-hit with per-ray skip ids, visibility words and motion times on the GPU (include/nanort_hip.h, nrtMultiHitQueryBatch*;
-DESIGN.md 3.16; nanort_amd/csrc/multihit_query.hip).
+DESIGN.md 3.16; nanort_amd/csrc/own_walks.hip).
 
   1. shells: every combination through the Device form, K = 2, all three at K = 1 and 4, and under two sets of trace options;
   2. pile: all three at K = 4 and 64, past the walk's 32 LDS stack entries;

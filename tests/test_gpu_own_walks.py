@@ -1,4 +1,4 @@
-"""The three "own walk" kernels — multi-hit, motion, masked (nanort_amd/csrc/multihit.hip, motion.hip, masked.hip) — where the plain
+"""The three "own walk" kernels — multi-hit, motion, masked (nanort_amd/csrc/own_walks.hip) — where the plain
 walk is tested, and the launch path only they take (api_query.hip, own_walk()): 32 LDS stack entries and then the slot's spill array,
 no completion record, the slot closed by an event, a taken-over slot waited for with hipStreamWaitEvent.
 

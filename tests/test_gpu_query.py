@@ -1,5 +1,5 @@
 """The combined ray query on the GPU (include/nanort_hip.h, "one descriptor for every triangle ray query"; DESIGN.md 3.13;
-nanort_amd/csrc/query.hip): per-ray skip ids, visibility words and motion times on the same ray.
+nanort_amd/csrc/own_walks.hip): per-ray skip ids, visibility words and motion times on the same ray.
 
   1. shells: the four composite combinations through the Device form, closest hit and occlusion, one arm with trace options;
   2. pile: all three past the walk's 32 LDS stack entries;

@@ -219,7 +219,7 @@ def _scratch(path):
 
 
 def test_no_new_instantiation_uses_more_scratch_than_the_motion_walk():
-    query, motion = _scratch("query.hip"), _scratch("motion.hip")
+    query = motion = _scratch("own_walks.hip")  # (every own walk is an instantiation of that one file)
     for t in ("f", "d"):  # the mangled template argument of the precision: If / Id
         base = [v for k, v in motion.items() if "k_traverse_motionI" + t in k]
         new = {k: v for k, v in query.items() if "k_traverse_queryI" + t in k}
