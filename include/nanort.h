@@ -48,6 +48,7 @@
 #include <vector>
 
 #include "nanort_motion.h"  // the motion-blur vertex rule (MotionTriangleIntersector), shared with the device walk
+#include "nanort_closest.h"  // the closest-point rule (BVHAccel::ClosestPoint), shared with the device kernel
 #ifdef NANORT_USE_HIP_BACKEND
 #include <mutex>
 
@@ -487,6 +488,21 @@ class TriangleIntersection {
   T v;
   T t;
   unsigned int prim_id;
+};
+
+// The answer of BVHAccel::ClosestPoint() / ClosestPointBatch() (no reference counterpart; laid out as nrt_closest_f32 / _f64 of
+// include/nanort_hip.h): the nearest point of the mesh, its squared distance, its barycentrics on face prim_id (u weighs the
+// face's second vertex and v its third, as in TriangleIntersection).  Nothing within max_dist: point = the query point,
+// dist2 = max_dist * max_dist, u = v = 0, prim_id = 0xFFFFFFFF.
+template <typename T = float>
+class ClosestPointResult {
+ public:
+  T point[3];
+  T dist2;
+  T u;
+  T v;
+  unsigned int prim_id;
+  unsigned int pad;
 };
 
 // Watertight ray/triangle test (Woop, Benthin, Wald 2013), same operation
@@ -1446,6 +1462,10 @@ struct HipApi;
     typedef nrt_multihit_query_##S MultiHitQueryPod;                              \
     NANORT_HIP_ENTRY(MultiHitQuery, nrtMultiHitQueryBatch, S)                     \
     NANORT_HIP_ENTRY(MultiHitQueryDevice, nrtMultiHitQueryBatchDevice, S)         \
+    /* closest-point queries */                                                   \
+    typedef nrt_point_##S PointPod;                                               \
+    typedef nrt_closest_##S ClosestPod;                                           \
+    NANORT_HIP_ENTRY(ClosestPoint, nrtClosestPointBatch, S)                       \
   };
 NANORT_HIP_API(float, f32)
 NANORT_HIP_API(double, f64)
@@ -1865,6 +1885,70 @@ class BVHAccel {
       if (q.counts_out) q.counts_out[i] = static_cast<unsigned int>(count);
     }
     return true;
+  }
+
+  // The nearest face of `mesh` to the point `p` and where on it, among the faces `options` admits (prim_ids_range, skip_prim_id;
+  // cull_back_face is ignored) and within max_dist — on the HOST, with or without NANORT_USE_HIP_BACKEND.  The rule is
+  // nanort_closest.h's: the smallest dist2, among equal dist2 the smallest prim_id, so the answer does not depend on the tree; the
+  // walk of nodes_ enters the nearer child first and skips a subtree iff its box lies strictly farther than the best so far.
+  // Returns whether a face was found; *out is written either way (ClosestPointResult above).  `mesh`: the one the tree was built over.
+  bool ClosestPoint(const T p[3], T max_dist, const TriangleMesh<T> &mesh, const BVHTraceOptions &options, ClosestPointResult<T> *out) const {
+    EnsureHostTree();
+    out->point[0] = p[0], out->point[1] = p[1], out->point[2] = p[2];
+    out->dist2 = max_dist * max_dist;
+    out->u = out->v = static_cast<T>(0.0);
+    out->prim_id = 0xFFFFFFFFu;
+    out->pad = 0u;
+    if (nodes_.empty() || !nanort_closest::Searchable<T>(p, max_dist)) return false;
+    std::vector<unsigned int> todo(1, 0u);  // (a vector: no depth limit)
+    while (!todo.empty()) {
+      const BVHNode<T> &node = nodes_[todo.back()];
+      todo.pop_back();
+      if (nanort_closest::Culled<T>(nanort_closest::BoxDist2<T>(p, node.bmin, node.bmax), out->dist2)) continue;
+      if (node.flag == 0) {
+        const BVHNode<T> &n0 = nodes_[node.data[0]], &n1 = nodes_[node.data[1]];
+        const T d0 = nanort_closest::BoxDist2<T>(p, n0.bmin, n0.bmax), d1 = nanort_closest::BoxDist2<T>(p, n1.bmin, n1.bmax);
+        const bool second = d1 < d0;  // on ties the first child
+        if (!nanort_closest::Culled<T>(second ? d0 : d1, out->dist2)) todo.push_back(node.data[second ? 0 : 1]);  // the farther child waits
+        if (!nanort_closest::Culled<T>(second ? d1 : d0, out->dist2)) todo.push_back(node.data[second ? 1 : 0]);
+      } else {
+        for (unsigned int i = 0; i < node.data[0]; i++) {
+          const unsigned int prim = indices_[node.data[1] + i];
+          if (prim < options.prim_ids_range[0] || prim >= options.prim_ids_range[1] || prim == options.skip_prim_id) continue;
+          const T *a = get_vertex_addr<T>(mesh.vertices_, mesh.faces_[3 * prim + 0], mesh.vertex_stride_bytes_);
+          const T *b = get_vertex_addr<T>(mesh.vertices_, mesh.faces_[3 * prim + 1], mesh.vertex_stride_bytes_);
+          const T *c = get_vertex_addr<T>(mesh.vertices_, mesh.faces_[3 * prim + 2], mesh.vertex_stride_bytes_);
+          T u, v, q[3];
+          nanort_closest::ClosestUV<T>(p, a, b, c, &u, &v);
+          const T dist2 = nanort_closest::ClosestOnTriangle<T>(p, a, b, c, u, v, q);
+          if (!nanort_closest::Better<T>(dist2, prim, out->dist2, out->prim_id)) continue;
+          out->point[0] = q[0], out->point[1] = q[1], out->point[2] = q[2];
+          out->dist2 = dist2;
+          out->u = u, out->v = v;
+          out->prim_id = prim;
+        }
+      }
+    }
+    return out->prim_id != 0xFFFFFFFFu;
+  }
+  // ... for `num_points` points, point i at points[3 * i] with max_dists[i] (NULL: +inf for every point): N calls of ClosestPoint().
+  // Every record is written; found_out[i] (optional) receives 1 / 0.
+  bool ClosestPointBatchHost(const T *points, const T *max_dists, size_t num_points, const TriangleMesh<T> &mesh, ClosestPointResult<T> *out,
+                             unsigned char *found_out = NULL, const BVHTraceOptions &options = BVHTraceOptions()) const {
+    for (size_t i = 0; i < num_points; i++) {
+      const bool found = ClosestPoint(points + 3 * i, max_dists ? max_dists[i] : std::numeric_limits<T>::infinity(), mesh, options, &out[i]);
+      if (found_out) found_out[i] = found ? 1 : 0;
+    }
+    return true;
+  }
+  // The batch call: with NANORT_USE_HIP_BACKEND and a triangle tree on the GPU one launch of nrtClosestPointBatch (records
+  // byte-identical to the host loop's: the answer does not depend on the tree or on who walks it), the host loop otherwise.
+  bool ClosestPointBatch(const T *points, const T *max_dists, size_t num_points, const TriangleMesh<T> &mesh, ClosestPointResult<T> *out,
+                         unsigned char *found_out = NULL, const BVHTraceOptions &options = BVHTraceOptions()) const {
+#ifdef NANORT_USE_HIP_BACKEND
+    if (dev_.ctx && geom_.kind == 0) return ClosestPointBatchBackend(points, max_dists, num_points, out, found_out, options);
+#endif
+    return ClosestPointBatchHost(points, max_dists, num_points, mesh, out, found_out, options);
   }
 
 #ifdef NANORT_USE_HIP_BACKEND
@@ -2327,6 +2411,21 @@ class BVHAccel {
     d.max_hits = q.max_hits;
     d.reserved = 0;
     return d;
+  }
+  // The GPU side of ClosestPointBatch(): the points packed into the library's 4-scalar records, one host call of the library.
+  bool ClosestPointBatchBackend(const T *points, const T *max_dists, size_t num_points, ClosestPointResult<T> *out, unsigned char *found_out,
+                                const BVHTraceOptions &options) const {
+    static_assert(sizeof(ClosestPointResult<T>) == sizeof(typename Api::ClosestPod), "closest-point record layout");
+    std::lock_guard<std::mutex> lock(batch_mutex_);
+    if (!DeviceTreeReady(0)) return false;
+    if (num_points == 0) return true;
+    std::vector<typename Api::PointPod> pts(num_points);
+    for (size_t i = 0; i < num_points; i++) {
+      for (int k = 0; k < 3; k++) pts[i].p[k] = points[3 * i + k];
+      pts[i].max_dist = max_dists ? max_dists[i] : std::numeric_limits<T>::infinity();
+    }
+    const nrt_trace_options o = TraceOptions(options);
+    return Ok(Api::ClosestPoint(Context(), &pts[0], num_points, &o, reinterpret_cast<typename Api::ClosestPod *>(out), found_out));
   }
   // The checks every host batch call makes (caller holds batch_mutex_): a context, the primitive kind the call's records are
   // for (0 triangles, 1 spheres), and a tree adopted by Load() uploaded — after a copy-on-write detach when the contexts are

@@ -218,7 +218,15 @@ typedef struct nrt_multihit_query_f64 {
   uint32_t reserved;
 } nrt_multihit_query_f64;
 
+/* The query and the answer of nrtClosestPointBatch* ("closest-point queries" below). */
+typedef struct { float  p[3]; float  max_dist; } nrt_point_f32;
+typedef struct { double p[3]; double max_dist; } nrt_point_f64;
+typedef struct { float  point[3]; float  dist2; float  u, v; uint32_t prim_id; uint32_t _pad; } nrt_closest_f32;
+typedef struct { double point[3]; double dist2; double u, v; uint32_t prim_id; uint32_t _pad; } nrt_closest_f64;
+
 #ifdef __cplusplus
+static_assert(sizeof(nrt_point_f32) == 16 && sizeof(nrt_point_f64) == 32, "closest-point query layout");
+static_assert(sizeof(nrt_closest_f32) == 32 && sizeof(nrt_closest_f64) == 56, "closest-point record layout");
 static_assert(sizeof(nrt_ray_f32) == 36 && sizeof(nrt_ray_f64) == 72, "Ray layout");
 static_assert(sizeof(nrt_node_f32) == 40 && sizeof(nrt_node_f64) == 64, "BVHNode layout");
 static_assert(sizeof(nrt_hit_f32) == 16 && sizeof(nrt_hit_f64) == 32, "TriangleIntersection layout");
@@ -897,6 +905,43 @@ NRT_API nrt_status nrtMultiHitQueryBatch_f32(nrt_ctx *ctx, const nrt_multihit_qu
 NRT_API nrt_status nrtMultiHitQueryBatch_f64(nrt_ctx *ctx, const nrt_multihit_query_f64 *query);
 NRT_API nrt_status nrtMultiHitQueryBatchDevice_f32(nrt_ctx *ctx, const nrt_multihit_query_f32 *query, void *hip_stream);
 NRT_API nrt_status nrtMultiHitQueryBatchDevice_f64(nrt_ctx *ctx, const nrt_multihit_query_f64 *query, void *hip_stream);
+
+/* ---- closest-point queries ------------------------------------------------------------------------------------------------------
+ * Which triangle of the context's mesh is nearest to a point, and where on it — the question Embree answers with rtcPointQuery, over
+ * the tree nrtBuild / nrtSetTree / nrtRefit left in HBM.  (No reference counterpart.)  DESIGN.md §3.17.
+ *
+ * The rule is include/nanort_closest.h's, in the context's precision, every operation rounded on its own: per face ClosestUV
+ * (Ericson's region test) gives (u, v) — u the weight of the face's second vertex, v of its third, as in the ray hit records — and
+ * ClosestOnTriangle the point and dist2.  Among the faces the options admit (prim_ids_range, skip_prim_id as in a ray query;
+ * cull_back_face is ignored) the answer is the face with the smallest dist2, among equal dist2 the smallest prim_id.  A face counts
+ * only if dist2 <= r2 = max_dist * max_dist: equality counts, max_dist = +inf is allowed, a NaN or negative max_dist finds nothing,
+ * a face whose dist2 is NaN is never the answer, a point with a non-finite coordinate finds nothing.  The answer is a minimum with a
+ * total tie-break, so it does not depend on the tree: a record is byte-identical to a loop over all the faces with the same rule.
+ *
+ * Found: point = the nearest point, dist2, u, v, prim_id.  Not found: point = p, dist2 = r2, u = v = 0, prim_id = 0xFFFFFFFF.
+ * _pad is written as 0.  found_out (may be NULL) receives 1 / 0 per point.
+ *
+ * A context with a motion keyframe answers for keyframe 0.  An adopted tree (nrtSetTree) is inside the contract when every box
+ * contains the triangles below it.  Runs nrt::k_closest_point<T, 32> (nrtLastKernelName).
+ *
+ * Refusals; each writes nothing and sets nrtLastError.  NRT_ERR_INVALID: a NULL context (no message to set); NULL points or
+ * closest_out with num_points > 0; no tree; a sphere, cylinder or curve context; more than 2^31-1 points; a Device array that is not
+ * aligned (points and closest_out to 16 bytes in fp32 and 8 in fp64).  NRT_ERR_PRECISION: a context of the other precision.
+ * num_points == 0 is NRT_OK.
+ *
+ * nrtClosestPointBatch_* takes host arrays, staged through the context's grow-only buffers in pieces of 2^22 points, one host call at
+ * a time.  nrtClosestPointBatchDevice_* takes device arrays and is asynchronous on `hip_stream`; it takes one of the context's launch
+ * slots and closes it with an event, so nrtSetMesh* / nrtBuild / nrtSetTree / nrtRefit* / nrtDestroy wait for it.
+ *
+ * Not covered: scenes, the sphere, cylinder and curve kinds, per-point skip ids or masks, the k nearest faces, motion time. */
+NRT_API nrt_status nrtClosestPointBatch_f32(nrt_ctx *ctx, const nrt_point_f32 *points, uint64_t num_points, const nrt_trace_options *options,
+                                            nrt_closest_f32 *closest_out, uint8_t *found_out);
+NRT_API nrt_status nrtClosestPointBatch_f64(nrt_ctx *ctx, const nrt_point_f64 *points, uint64_t num_points, const nrt_trace_options *options,
+                                            nrt_closest_f64 *closest_out, uint8_t *found_out);
+NRT_API nrt_status nrtClosestPointBatchDevice_f32(nrt_ctx *ctx, const nrt_point_f32 *points, uint64_t num_points, const nrt_trace_options *options,
+                                                  nrt_closest_f32 *closest_out, uint8_t *found_out, void *hip_stream);
+NRT_API nrt_status nrtClosestPointBatchDevice_f64(nrt_ctx *ctx, const nrt_point_f64 *points, uint64_t num_points, const nrt_trace_options *options,
+                                                  nrt_closest_f64 *closest_out, uint8_t *found_out, void *hip_stream);
 
 /* One HOST batch spread over several contexts — typically one per GPU of the node (nrtDeviceCount), each holding the same
  * tree: nrtBuild is deterministic, so building the same mesh on every context gives bit-identical replicas (or nrtSetTree the

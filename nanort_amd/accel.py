@@ -612,6 +612,47 @@ class BVHAccel:
         )
         return n
 
+    # -- closest point ------------------------------------------------------
+    def ClosestPointBatch(self, points, max_dist=np.inf, options=None):
+        """The nearest face of the mesh to each point and where on it (nrtClosestPointBatch; the rule: include/nanort_closest.h).
+        `points`: [n, 3] coordinates with `max_dist` a scalar or one value per point, or a wire.point_dtype record array (then
+        `max_dist` is not read).  Returns (records, found): wire.closest_dtype records and a uint8 per point."""
+        from .wire import closest_dtype, point_dtype
+
+        pd = point_dtype(self.real)
+        if isinstance(points, np.ndarray) and points.dtype == pd:
+            pts = np.ascontiguousarray(points).reshape(-1)
+        else:
+            xyz = np.asarray(points, dtype=self.real).reshape(-1, 3)
+            pts = np.zeros((xyz.shape[0],), dtype=pd)
+            pts["p"] = xyz
+            pts["max_dist"] = np.asarray(max_dist, dtype=self.real)
+        n = pts.shape[0]
+        out = np.zeros((n,), dtype=closest_dtype(self.real))
+        found = np.zeros((n,), dtype=np.uint8)
+        options = _opts(options)
+        self._check(getattr(self._L, "nrtClosestPointBatch_" + self._s)(self._h, _p(pts), n, _p(options), _p(out), _p(found)))
+        return out, found
+
+    def ClosestPointBatchDevice(self, d_points, d_out, d_found=None, options=None, stream=None):
+        """Same on HBM-resident torch tensors of raw records (wire.point_dtype in, wire.closest_dtype out, a byte per point in
+        `d_found`), asynchronous on `stream` (default: torch's current stream).  Returns the number of points."""
+        from .wire import closest_dtype, point_dtype
+
+        for t, what in ((d_points, "d_points"), (d_out, "d_out"), (d_found, "d_found")):
+            if t is not None:
+                self._on_device(t, what)
+        n = d_points.numel() * d_points.element_size() // point_dtype(self.real).itemsize
+        if d_out.numel() * d_out.element_size() < n * closest_dtype(self.real).itemsize:
+            raise ValueError("d_out holds fewer records than d_points holds points")
+        if d_found is not None and d_found.numel() * d_found.element_size() < n:
+            raise ValueError("d_found holds fewer bytes than d_points holds points")
+        options = _opts(options)
+        self._check(getattr(self._L, "nrtClosestPointBatchDevice_" + self._s)(
+            self._h, d_points.data_ptr(), n, _p(options), d_out.data_ptr(), None if d_found is None else d_found.data_ptr(),
+            self._stream_handle(stream)))
+        return n
+
     def TraverseBatchesDevice(self, batches, options=None, stream=None, skip_prim_ids=None):
         """nrtTraverseBatchesDevice: several independent batches — a list of (d_rays, d_hits, d_mask or None, n or None[, "occlusion"])
         torch uint8 tensors — walked by ONE persistent launch (asynchronous on `stream`).  A batch marked "occlusion" is an

@@ -162,6 +162,9 @@ SIGNATURES = [
     # multi-hit under the same three per-ray inputs (MultiHitQuery above): ctx, descriptor[, stream]
     ("nrtMultiHitQueryBatch", _BOTH, [vp, vp], i32),
     ("nrtMultiHitQueryBatchDevice", _BOTH, [vp, vp, vp], i32),
+    # closest-point queries: ctx, points, num_points, options, closest_out, found_out[, stream]
+    ("nrtClosestPointBatch", _BOTH, _Q + [vp, vp], i32),
+    ("nrtClosestPointBatchDevice", _BOTH, _Q + [vp, vp, vp], i32),
     ("nrtTraverseBatchMulti", _BOTH, [vp, u32, vp, u64, u64, vp, vp, vp], i32),
     ("nrtDeviceCount", None, [], i32),
     ("nrtTraverseCountDevice", _BOTH, _Q + [P(TraceCounters)], i32),

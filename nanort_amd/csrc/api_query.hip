@@ -124,6 +124,24 @@ static nrt_status validate_launch(nrt_ctx *c, const TraverseLaunch<T> &l) {
   return NRT_OK;
 }
 
+// The entry checks of the closest-point query (include/nanort_hip.h, "closest-point queries"), in the ray queries' order and with
+// their statuses (under launch_mutex).  `device`: the arrays are the caller's device memory, whose alignment the kernel's loads and
+// stores rely on (the host form stages them).
+template <typename T>
+static nrt_status validate_closest(nrt_ctx *c, const char *fn, const void *points, uint64_t n, const void *out, const void *found, bool device) {
+  (void)found; // (may be NULL; a byte array has no alignment to check)
+  if (c->prec != (int)sizeof(T)) return fail(c, NRT_ERR_PRECISION, "%s: precision mismatch", fn);
+  if (c->prim_kind != kPrimTriangles) return fail(c, NRT_ERR_INVALID, "%s: triangle contexts only (this context holds %s)", fn, kPrimKinds[c->prim_kind].name);
+  if (!c->d_nodes) return fail(c, NRT_ERR_INVALID, "%s: no tree (call nrtBuild or nrtSetTree)", fn);
+  if (n == 0) return NRT_OK;
+  if (!points || !out) return fail(c, NRT_ERR_INVALID, "%s: NULL points/closest_out", fn);
+  if (n > 0x7FFFFFFFull) return fail(c, NRT_ERR_INVALID, "%s: more than 2^31-1 points in one call", fn);
+  const uintptr_t align = sizeof(T) == 4 ? 16u : 8u;
+  if (device && (((uintptr_t)points % align) != 0u || ((uintptr_t)out % align) != 0u))
+    return fail(c, NRT_ERR_INVALID, "%s: the device arrays are not aligned to %zu bytes", fn, (size_t)align);
+  return NRT_OK;
+}
+
 // Launch slot: the one this stream used last (stream order already serialises the two launches), else
 // a fresh one, else the oldest — whose previous launch this stream then waits for on the device
 static nrt_status take_slot(nrt_ctx *c, hipStream_t s, nrt_ctx::LaunchSlot **out) {
@@ -388,6 +406,96 @@ static nrt_status traverse_device(nrt_ctx *c, TraverseLaunch<T> l) {
   fill_walk_args(c, l, w, a);
   fill_launch_args(l, slot, g, d, levels, a);
   return enqueue_launch(c, l, w, slot, a, g.grid);
+}
+
+// The closest-point query (closest.hip, k_closest_point) takes the path of a ray launch — launch_mutex from the checks to the slot's
+// event, a launch slot for its cursors and its overflow stack, the persistent grid and the claim plan of launch_plan.h — with points
+// in the place of rays: `points`, `out` and `found` are device arrays, `s` the stream the launch is enqueued on.  It publishes no
+// completion record: the slot is closed by its event, which is what a rebuild or a refit waits for (wait_for_launches).
+template <typename T>
+static nrt_status closest_device(nrt_ctx *c, const char *fn, const void *points, uint64_t n, const nrt_trace_options *opt, void *out, uint8_t *found,
+                                 bool device, hipStream_t s) {
+  if (!c) return NRT_ERR_INVALID;
+  if (!opt) opt = &kDefaultTrace;
+  std::lock_guard<std::mutex> lock(c->launch_mutex);
+  nrt_status st = validate_closest<T>(c, fn, points, n, out, found, device);
+  if (st || n == 0) return st;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, refit_stream_wait(c, s)); // (a Device refit in flight on another stream)
+  nrt_ctx::LaunchSlot *slot = nullptr;
+  if ((st = take_slot(c, s, &slot))) return st;
+  if (c->closest_blocks_per_cu == 0) c->closest_blocks_per_cu = (unsigned)closest_point_blocks_per_cu<T>();
+  const unsigned per_cu = c->max_blocks_per_cu && c->closest_blocks_per_cu > c->max_blocks_per_cu ? c->max_blocks_per_cu : c->closest_blocks_per_cu;
+  const GridPlan g = plan_grid(n, kTraverseBlock, (uint32_t)c->num_cus, per_cu, c->num_parts);
+  const uint32_t total_threads = g.grid * kTraverseBlock, total_waves = g.grid * (kTraverseBlock / kWave);
+  const DistributionPlan d = plan_distribution((uint32_t)n, total_waves, g.parts, c->static_pct, c->static_bands, c->static_slice_groups, c->chunk);
+  // (one pending sibling per level of the path, as the binary walk: trees deeper than the LDS stack go on in the slot's overflow area)
+  const uint32_t levels = plan_spill_levels(c->tree_depth, false, (uint32_t)kLdsStackDefault);
+  if (levels && (st = ensure(c, slot->spill, (size_t)levels * total_threads * sizeof(uint32_t)))) return st;
+  TraverseLaunch<T> l = {};
+  l.kind = Query::Closest;
+  l.n = n;
+  l.opt = opt;
+  l.stream = s;
+  WalkChoice w = {};
+  w.walk = Walk::Literal; // (the node array, no private records)
+  w.own = kNumOwnWalks;
+  w.lds_entries = kLdsStackDefault;
+  TraverseArgs<T> a = {};
+  fill_walk_args(c, l, w, a);
+  fill_launch_args(l, slot, g, d, levels, a);
+#ifdef NRT_PROF
+  HIPCHK(c, hipMemsetAsync(c->d_counters, 0, 16 * sizeof(unsigned long long), s)); // (nodes opened, triangles tested: nrtDebugCounters [0], [2])
+#else
+  a.counters = nullptr;
+#endif
+  HIPCHK(c, hipEventRecord(slot->t0, s));
+  HIPCHK(c, launch_closest_point<T>(a, points, out, found, g.grid, s, &c->last_kernel));
+  // (the kernel is enqueued: the slot's state follows it now, as in enqueue_launch)
+  slot->last_has_rec = false;
+  slot->last_timed = false;
+  slot->parity ^= 1u;
+  slot->stream = s;
+  slot->used = true;
+  HIPCHK(c, hipEventRecord(slot->t1, s));
+  slot->last_timed = true;
+  c->last_timed_slot = (int)(slot - c->slots);
+  HIPCHK(c, hipEventRecord(slot->done, s));
+  return NRT_OK;
+}
+
+const uint64_t kClosestPiece = 1ull << 20; // points per launch of the staged host form (16 MB up, 33 MB down in fp32)
+
+// ... over the caller's HOST arrays: one call at a time (host_mutex: the staging buffers are the context's), in pieces of kClosestPiece
+// points — the piece up into st_rays, the launch over the staging buffers, its records and bytes of st_hits / st_mask back.
+template <typename T>
+static nrt_status closest_host(nrt_ctx *c, const typename ClosestWire<T>::Point *points, uint64_t n, const nrt_trace_options *opt,
+                               typename ClosestWire<T>::Record *out, uint8_t *found) {
+  typedef typename ClosestWire<T>::Point Point;
+  typedef typename ClosestWire<T>::Record Record;
+  const char *fn = "nrtClosestPointBatch";
+  if (!c) return NRT_ERR_INVALID;
+  {
+    std::lock_guard<std::mutex> lock(c->launch_mutex);
+    const nrt_status st = validate_closest<T>(c, fn, points, n, out, found, false);
+    if (st || n == 0) return st;
+  }
+  std::lock_guard<std::mutex> host_lock(c->host_mutex);
+  HIPCHK(c, hipSetDevice(c->device));
+  for (uint64_t off = 0; off < n; off += kClosestPiece) {
+    const uint64_t m = std::min(kClosestPiece, n - off);
+    nrt_status st;
+    if ((st = ensure(c, c->st_rays, m * sizeof(Point))) || (st = ensure(c, c->st_hits, m * sizeof(Record))) || (st = ensure(c, c->st_mask, m))) return st;
+    HIPCHK(c, hipMemcpyAsync(c->st_rays.p, points + off, m * sizeof(Point), hipMemcpyHostToDevice, c->stream));
+    if ((st = closest_device<T>(c, fn, c->st_rays.p, m, opt, c->st_hits.p, (uint8_t *)c->st_mask.p, false, c->stream))) {
+      (void)hipStreamSynchronize(c->stream);
+      return st;
+    }
+    HIPCHK(c, hipMemcpyAsync(out + off, c->st_hits.p, m * sizeof(Record), hipMemcpyDeviceToHost, c->stream));
+    if (found) HIPCHK(c, hipMemcpyAsync(found + off, c->st_mask.p, m, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  return NRT_OK;
 }
 
 const uint64_t kStagedRays = 1ull << 26; // rays per launch of the staged host paths (keeps staging bounded)
@@ -1113,6 +1221,22 @@ nrt_status nrtMultiHitQueryBatch_f32(nrt_ctx *c, const nrt_multihit_query_f32 *q
 nrt_status nrtMultiHitQueryBatch_f64(nrt_ctx *c, const nrt_multihit_query_f64 *q) { return multihit_query_batch<double>(c, q, false, nullptr); }
 nrt_status nrtMultiHitQueryBatchDevice_f32(nrt_ctx *c, const nrt_multihit_query_f32 *q, void *s) { return multihit_query_batch<float>(c, q, true, s); }
 nrt_status nrtMultiHitQueryBatchDevice_f64(nrt_ctx *c, const nrt_multihit_query_f64 *q, void *s) { return multihit_query_batch<double>(c, q, true, s); }
+
+// Closest-point queries (include/nanort_hip.h): the nearest face of the mesh to each point.
+nrt_status nrtClosestPointBatch_f32(nrt_ctx *c, const nrt_point_f32 *p, uint64_t n, const nrt_trace_options *o, nrt_closest_f32 *out, uint8_t *f) {
+  return closest_host<float>(c, p, n, o, out, f);
+}
+nrt_status nrtClosestPointBatch_f64(nrt_ctx *c, const nrt_point_f64 *p, uint64_t n, const nrt_trace_options *o, nrt_closest_f64 *out, uint8_t *f) {
+  return closest_host<double>(c, p, n, o, out, f);
+}
+nrt_status nrtClosestPointBatchDevice_f32(nrt_ctx *c, const nrt_point_f32 *p, uint64_t n, const nrt_trace_options *o, nrt_closest_f32 *out, uint8_t *f,
+                                          void *s) {
+  return closest_device<float>(c, "nrtClosestPointBatchDevice", p, n, o, out, f, true, (hipStream_t)s);
+}
+nrt_status nrtClosestPointBatchDevice_f64(nrt_ctx *c, const nrt_point_f64 *p, uint64_t n, const nrt_trace_options *o, nrt_closest_f64 *out, uint8_t *f,
+                                          void *s) {
+  return closest_device<double>(c, "nrtClosestPointBatchDevice", p, n, o, out, f, true, (hipStream_t)s);
+}
 
 nrt_status nrtTraverseBatchMulti_f32(nrt_ctx *const *ctxs, uint32_t num_ctx, const nrt_ray_f32 *r, uint64_t n, uint64_t row_len,
                                      const nrt_trace_options *o, nrt_hit_f32 *h, uint8_t *m) {

@@ -159,6 +159,8 @@ struct nrt_ctx {
   // keeps one precision; api_query.hip, size_grid).  A row per Walk, the own walks' rows (kernels.h, OwnWalk) in the place of Walk::Own's.
   struct { int lds_entries; unsigned blocks_per_cu; } occupancy[(int)Walk::Own + kNumOwnWalks][kNumPrimKinds] = {};
 
+  unsigned closest_blocks_per_cu = 0; // ... and of k_closest_point (closest.hip; 0: not asked for yet)
+
   hipEvent_t ev_b0 = nullptr, ev_b1 = nullptr;
   hipEvent_t ev_build_state = nullptr; // the builder's state block has reached build_state
   void *build_state = nullptr;         // page-locked, kBuildPinnedBytes

@@ -78,6 +78,27 @@ hipError_t launch_own_walk(OwnWalk w, const TraverseArgs<T> &args, const OwnWalk
 template <typename T>
 int own_walk_blocks_per_cu(OwnWalk w);
 
+// ---- closest.hip: the closest-point query (k_closest_point; include/nanort_closest.h states its rule) ---------------------------
+template <typename T>
+struct ClosestWire;
+template <>
+struct ClosestWire<float> {
+  typedef nrt_point_f32 Point;
+  typedef nrt_closest_f32 Record;
+};
+template <>
+struct ClosestWire<double> {
+  typedef nrt_point_f64 Point;
+  typedef nrt_closest_f64 Record;
+};
+// `args`: the tree, the trace options, the claim plan over num_rays points and the overflow stack (its rays / hits / mask are not
+// read); `points` / `out`: ClosestWire<T>'s records, `found`: a byte per point or null; `name_out`: as launch_traverse_wide's
+template <typename T>
+hipError_t launch_closest_point(const TraverseArgs<T> &args, const void *points, void *out, uint8_t *found, unsigned grid, hipStream_t s,
+                                const char **name_out);
+template <typename T>
+int closest_point_blocks_per_cu();
+
 // ---- build.hip --------------------------------------------------------------------------------------------------------
 enum : unsigned { kBuildMorton = 1u, kBuildSubtreeDfs = 2u }; // gpu_build's build_flags: Morton pre-pass, one-node-per-step subtree kernel
 struct BuildResult {

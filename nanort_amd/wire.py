@@ -90,7 +90,23 @@ assert CYL_HIT_F32.itemsize == 28
 CURVE_HIT_F32 = np.dtype([("t", "<f4"), ("prim_id", "<u4"), ("u", "<f4"), ("v", "<f4"), ("tangent", "<f4", 3), ("normal", "<f4", 3)])
 assert CURVE_HIT_F32.itemsize == 40
 
+# the query and the answer of the closest-point queries (include/nanort_hip.h: nrt_point_*, nrt_closest_*; no reference counterpart)
+POINT_F32 = np.dtype([("p", "<f4", 3), ("max_dist", "<f4")])
+POINT_F64 = np.dtype([("p", "<f8", 3), ("max_dist", "<f8")])
+CLOSEST_F32 = np.dtype([("point", "<f4", 3), ("dist2", "<f4"), ("u", "<f4"), ("v", "<f4"), ("prim_id", "<u4"), ("_pad", "<u4")])
+CLOSEST_F64 = np.dtype([("point", "<f8", 3), ("dist2", "<f8"), ("u", "<f8"), ("v", "<f8"), ("prim_id", "<u4"), ("_pad", "<u4")])
+assert POINT_F32.itemsize == 16 and POINT_F64.itemsize == 32
+assert CLOSEST_F32.itemsize == 32 and CLOSEST_F64.itemsize == 56
+
 MISS_PRIM_ID = 0xFFFFFFFF
+
+
+def point_dtype(real):
+    return POINT_F32 if np.dtype(real) == np.float32 else POINT_F64
+
+
+def closest_dtype(real):
+    return CLOSEST_F32 if np.dtype(real) == np.float32 else CLOSEST_F64
 
 
 def ray_dtype(real):
