@@ -1919,8 +1919,7 @@ class BVHAccel {
           const T *b = get_vertex_addr<T>(mesh.vertices_, mesh.faces_[3 * prim + 1], mesh.vertex_stride_bytes_);
           const T *c = get_vertex_addr<T>(mesh.vertices_, mesh.faces_[3 * prim + 2], mesh.vertex_stride_bytes_);
           T u, v, q[3];
-          nanort_closest::ClosestUV<T>(p, a, b, c, &u, &v);
-          const T dist2 = nanort_closest::ClosestOnTriangle<T>(p, a, b, c, u, v, q);
+          const T dist2 = nanort_closest::ClosestPointOnTriangle<T>(p, a, b, c, &u, &v, q);
           if (!nanort_closest::Better<T>(dist2, prim, out->dist2, out->prim_id)) continue;
           out->point[0] = q[0], out->point[1] = q[1], out->point[2] = q[2];
           out->dist2 = dist2;

@@ -5,15 +5,37 @@
 // library and every program that wants its bits compile with -ffp-contract=off), dots and sums of squares are summed left to right,
 // x*x' + y*y' + z*z'.
 //
-//   ClosestUV(p, a, b, c) -> (u, v)      Ericson's region test (Real-Time Collision Detection 5.1.5), in the book's order.  u is the
+//   ClosestOnTriangle(p, a, b, c, u, v)  q_k = w0*a_k + u*b_k + v*c_k with w0 = (1 - u) - v, clamped per component to
+//                                        [min(a_k, b_k, c_k), max(a_k, b_k, c_k)]; dist2 = (p0-q0)^2 + (p1-q1)^2 + (p2-q2)^2.  u is the
 //                                        weight of the triangle's second vertex and v of its third — the convention of the ray hit
 //                                        records (nanort.h, TriangleIntersector: u_ = V * rcpDet weighs p1, v_ = W * rcpDet p2).
-//   ClosestOnTriangle(p, a, b, c, u, v)  q_k = w0*a_k + u*b_k + v*c_k with w0 = (1 - u) - v, clamped per component to
-//                                        [min(a_k, b_k, c_k), max(a_k, b_k, c_k)]; dist2 = (p0-q0)^2 + (p1-q1)^2 + (p2-q2)^2.  The
-//                                        weighted form returns a vertex exactly in the vertex regions, and the clamp (what
-//                                        nanort_motion::Lerp does for the same reason) puts q inside every box that contains the
-//                                        triangle.
+//                                        The weighted form returns a vertex exactly where (u, v) is (0, 0), (1, 0) or (0, 1), and
+//                                        the clamp (what nanort_motion::Lerp does for the same reason) puts q inside every box
+//                                        that contains the triangle.
+//   ClosestPointOnTriangle(p, a, b, c)   -> (u, v), q, dist2: the nearest of up to four candidates, each valued by ClosestOnTriangle,
+//                                        in this order, a later one taken only when strictly nearer (or when all before it are NaN):
+//                                          edge ab  (t, 0),      t = clamp(((p-a).(b-a)) / ((b-a).(b-a)), 0, 1)
+//                                          edge ac  (0, t),      t = clamp(((p-a).(c-a)) / ((c-a).(c-a)), 0, 1)
+//                                          edge bc  (1 - t, t),  t = clamp(((p-b).(c-b)) / ((c-b).(c-b)), 0, 1)
+//                                          face     (s - v m, v) with s = ((p-a).(b-a)) / ((b-a).(b-a)), m = ((b-a).(c-a)) / ((b-a).(b-a)),
+//                                                   e = (c-a) - m (b-a), r = (p-a) - s (b-a), v = (r.e) / (e.e) — only where
+//                                                   u >= 0, v >= 0 and u + v <= 1
+//                                        (t = 0 for an edge of no length).  A clamped t is exactly 0 or 1, so the vertex regions
+//                                        return their vertex exactly; dist2 is NaN only where every candidate's is.
+//   ClosestUV(p, a, b, c) -> (u, v)      the same (u, v) alone; ClosestOnTriangle of them gives the same q and dist2, bit for bit
+//                                        (the tests' model states the rule in these two calls).
 //   BoxDist2(p, bmin, bmax)              m_k = max(bmin_k - p_k, p_k - bmax_k, 0), the squares summed in the same order.
+//
+// Why candidates and not a region test.  Ericson's cascade (Real-Time Collision Detection 5.1.5), which this rule was first, decides
+// the region from vc = d1*d4 - d3*d2 and its siblings and divides by their sum.  On a triangle whose corners are nearly in line
+// those cancel to rounding noise: the point went to the wrong region and the answer was off by a few hundredths on a mesh of size 1, in
+// both precisions ("Accuracy").  A minimum over candidates cannot leave the triangle and cannot miss by more than
+// its best candidate does.  The edges are exact to rounding whatever the shape.  The foot of the perpendicular is found along ab and
+// along e, what is left of ac without its part along ab, after the part of p - a along ab is taken off as well: the error of e's
+// direction, which grows as the triangle narrows, then meets only the short vector r and not all of p - a.  Where the foot is
+// still uncertain by more than rounding — a narrow triangle seen from afar — the nearest edge point is within the triangle's width
+// of it, and the two errors cannot both be large.  The contract the tests hold it to: sqrt(dist2) within 8 eps(T) S of the true
+// distance, S the largest absolute coordinate involved; measured 1.1 at most.
 //
 // Because q_k lies in the box and each of subtraction, square and sum is monotone under rounding, BoxDist2 <= dist2 holds IN
 // FLOATING POINT for every box that contains the triangle's vertices: a subtree whose box lies farther than the best distance found
@@ -42,48 +64,6 @@ NANORT_CLOSEST_FN T Dot(T x0, T x1, T x2, T y0, T y1, T y2) {
   return x0 * y0 + x1 * y1 + x2 * y2;
 }
 
-template <typename T>
-NANORT_CLOSEST_FN void ClosestUV(const T p[3], const T a[3], const T b[3], const T c[3], T *u, T *v) {
-  const T ab0 = b[0] - a[0], ab1 = b[1] - a[1], ab2 = b[2] - a[2];
-  const T ac0 = c[0] - a[0], ac1 = c[1] - a[1], ac2 = c[2] - a[2];
-  const T ap0 = p[0] - a[0], ap1 = p[1] - a[1], ap2 = p[2] - a[2];
-  const T d1 = Dot(ab0, ab1, ab2, ap0, ap1, ap2), d2 = Dot(ac0, ac1, ac2, ap0, ap1, ap2);
-  if (d1 <= T(0) && d2 <= T(0)) { // vertex a
-    *u = T(0), *v = T(0);
-    return;
-  }
-  const T bp0 = p[0] - b[0], bp1 = p[1] - b[1], bp2 = p[2] - b[2];
-  const T d3 = Dot(ab0, ab1, ab2, bp0, bp1, bp2), d4 = Dot(ac0, ac1, ac2, bp0, bp1, bp2);
-  if (d3 >= T(0) && d4 <= d3) { // vertex b
-    *u = T(1), *v = T(0);
-    return;
-  }
-  const T vc = d1 * d4 - d3 * d2;
-  if (vc <= T(0) && d1 >= T(0) && d3 <= T(0)) { // edge ab
-    *u = d1 / (d1 - d3), *v = T(0);
-    return;
-  }
-  const T cp0 = p[0] - c[0], cp1 = p[1] - c[1], cp2 = p[2] - c[2];
-  const T d5 = Dot(ab0, ab1, ab2, cp0, cp1, cp2), d6 = Dot(ac0, ac1, ac2, cp0, cp1, cp2);
-  if (d6 >= T(0) && d5 <= d6) { // vertex c
-    *u = T(0), *v = T(1);
-    return;
-  }
-  const T vb = d5 * d2 - d1 * d6;
-  if (vb <= T(0) && d2 >= T(0) && d6 <= T(0)) { // edge ac
-    *u = T(0), *v = d2 / (d2 - d6);
-    return;
-  }
-  const T va = d3 * d6 - d5 * d4;
-  if (va <= T(0) && d4 - d3 >= T(0) && d5 - d6 >= T(0)) { // edge bc
-    const T w = (d4 - d3) / ((d4 - d3) + (d5 - d6));
-    *u = T(1) - w, *v = w;
-    return;
-  }
-  const T den = T(1) / (va + vb + vc); // the face
-  *u = vb * den, *v = vc * den;
-}
-
 // One component of the point (u, v) names, inside [min(a, b, c), max(a, b, c)].
 template <typename T>
 NANORT_CLOSEST_FN T ClampedWeighted(T a, T b, T c, T w0, T u, T v) {
@@ -94,7 +74,7 @@ NANORT_CLOSEST_FN T ClampedWeighted(T a, T b, T c, T w0, T u, T v) {
   return x < lo ? lo : (x > hi ? hi : x);
 }
 
-// The point of the triangle that (u, v) of ClosestUV name, into q; returns its squared distance to p.
+// The point of the triangle that (u, v) name, into q; returns its squared distance to p.
 template <typename T>
 NANORT_CLOSEST_FN T ClosestOnTriangle(const T p[3], const T a[3], const T b[3], const T c[3], T u, T v, T q[3]) {
   const T w0 = (T(1) - u) - v;
@@ -103,6 +83,61 @@ NANORT_CLOSEST_FN T ClosestOnTriangle(const T p[3], const T a[3], const T b[3], 
   q[2] = ClampedWeighted(a[2], b[2], c[2], w0, u, v);
   const T e0 = p[0] - q[0], e1 = p[1] - q[1], e2 = p[2] - q[2];
   return e0 * e0 + e1 * e1 + e2 * e2;
+}
+
+// Where on the segment x + t (y - x) the point projects: num / den = ((p - x).(y - x)) / ((y - x).(y - x)) clamped to [0, 1]; 0 for a
+// segment of no length (den is a sum of squares: not above 0 only when it is 0 or NaN).
+template <typename T>
+NANORT_CLOSEST_FN T SegmentParam(T num, T den) {
+  if (!(den > T(0))) return T(0);
+  const T t = num / den;
+  return t < T(0) ? T(0) : (t > T(1) ? T(1) : t);
+}
+
+// The candidate (cu, cv) against the best so far (*u, *v, q, *dist2): taken when strictly nearer, or when the best is NaN.
+template <typename T>
+NANORT_CLOSEST_FN void ClosestCandidate(const T p[3], const T a[3], const T b[3], const T c[3], T cu, T cv, T *u, T *v, T q[3], T *dist2) {
+  T cq[3];
+  const T d = ClosestOnTriangle(p, a, b, c, cu, cv, cq);
+  const bool take = d < *dist2 || *dist2 != *dist2;
+  *u = take ? cu : *u, *v = take ? cv : *v;
+  q[0] = take ? cq[0] : q[0], q[1] = take ? cq[1] : q[1], q[2] = take ? cq[2] : q[2];
+  *dist2 = take ? d : *dist2;
+}
+
+// The nearest point of the triangle to p: (u, v) and the point into q; returns dist2.  See the head of the file.
+template <typename T>
+NANORT_CLOSEST_FN T ClosestPointOnTriangle(const T p[3], const T a[3], const T b[3], const T c[3], T *u, T *v, T q[3]) {
+  const T ab0 = b[0] - a[0], ab1 = b[1] - a[1], ab2 = b[2] - a[2];
+  const T ac0 = c[0] - a[0], ac1 = c[1] - a[1], ac2 = c[2] - a[2];
+  const T bc0 = c[0] - b[0], bc1 = c[1] - b[1], bc2 = c[2] - b[2];
+  const T ap0 = p[0] - a[0], ap1 = p[1] - a[1], ap2 = p[2] - a[2];
+  const T bp0 = p[0] - b[0], bp1 = p[1] - b[1], bp2 = p[2] - b[2];
+  const T d00 = Dot(ab0, ab1, ab2, ab0, ab1, ab2), d01 = Dot(ab0, ab1, ab2, ac0, ac1, ac2), d11 = Dot(ac0, ac1, ac2, ac0, ac1, ac2);
+  const T d1 = Dot(ab0, ab1, ab2, ap0, ap1, ap2), d2 = Dot(ac0, ac1, ac2, ap0, ap1, ap2);
+  // the three edges: ab, ac, bc
+  const T tab = SegmentParam(d1, d00), tac = SegmentParam(d2, d11);
+  const T tbc = SegmentParam(Dot(bc0, bc1, bc2, bp0, bp1, bp2), Dot(bc0, bc1, bc2, bc0, bc1, bc2));
+  *u = tab, *v = T(0);
+  T dist2 = ClosestOnTriangle(p, a, b, c, tab, T(0), q);
+  ClosestCandidate(p, a, b, c, T(0), tac, u, v, q, &dist2);
+  ClosestCandidate(p, a, b, c, T(1) - tbc, tbc, u, v, q, &dist2);
+  // the foot of the perpendicular, where its weights say it lies inside (false for the NaN of a triangle without area): along ab,
+  // then along what is left of ac once its part along ab is taken off — of p - a, too, before the two meet in a dot product
+  const T s = d1 / d00, m = d01 / d00;
+  const T e0 = ac0 - m * ab0, e1 = ac1 - m * ab1, e2 = ac2 - m * ab2;
+  const T r0 = ap0 - s * ab0, r1 = ap1 - s * ab1, r2 = ap2 - s * ab2;
+  const T fv = Dot(r0, r1, r2, e0, e1, e2) / Dot(e0, e1, e2, e0, e1, e2), fu = s - fv * m;
+  if (fu >= T(0) && fv >= T(0) && fu + fv <= T(1)) ClosestCandidate(p, a, b, c, fu, fv, u, v, q, &dist2);
+  return dist2;
+}
+
+// The (u, v) alone, for a caller that values them itself: ClosestOnTriangle(p, a, b, c, u, v, q) then gives the q and the dist2 of
+// ClosestPointOnTriangle, bit for bit (it is the function that valued the winning candidate).
+template <typename T>
+NANORT_CLOSEST_FN void ClosestUV(const T p[3], const T a[3], const T b[3], const T c[3], T *u, T *v) {
+  T q[3];
+  ClosestPointOnTriangle(p, a, b, c, u, v, q);
 }
 
 // One component of the box distance: max(bmin - p, p - bmax, 0).  (A NaN bound drops out: such a box is never culled.)

@@ -910,9 +910,12 @@ NRT_API nrt_status nrtMultiHitQueryBatchDevice_f64(nrt_ctx *ctx, const nrt_multi
  * Which triangle of the context's mesh is nearest to a point, and where on it — the question Embree answers with rtcPointQuery, over
  * the tree nrtBuild / nrtSetTree / nrtRefit left in HBM.  (No reference counterpart.)  DESIGN.md §3.17.
  *
- * The rule is include/nanort_closest.h's, in the context's precision, every operation rounded on its own: per face ClosestUV
- * (Ericson's region test) gives (u, v) — u the weight of the face's second vertex, v of its third, as in the ray hit records — and
- * ClosestOnTriangle the point and dist2.  Among the faces the options admit (prim_ids_range, skip_prim_id as in a ray query;
+ * The rule is include/nanort_closest.h's, in the context's precision, every operation rounded on its own: per face
+ * ClosestPointOnTriangle takes the nearest of the three clamped edge projections and, where it falls inside, the foot of the
+ * perpendicular, and gives (u, v) — u the weight of the face's second vertex, v of its third, as in the ray hit records — the point
+ * and dist2.  Accuracy: sqrt(dist2) is within 8 eps S of the true distance to the nearest admitted face, eps the precision's and S
+ * the largest absolute coordinate among the points and the vertices, on triangles of any shape — slivers, needles, corners in line.
+ * Among the faces the options admit (prim_ids_range, skip_prim_id as in a ray query;
  * cull_back_face is ignored) the answer is the face with the smallest dist2, among equal dist2 the smallest prim_id.  A face counts
  * only if dist2 <= r2 = max_dist * max_dist: equality counts, max_dist = +inf is allowed, a NaN or negative max_dist finds nothing,
  * a face whose dist2 is NaN is never the answer, a point with a non-finite coordinate finds nothing.  The answer is a minimum with a

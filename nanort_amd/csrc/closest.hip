@@ -1,7 +1,7 @@
 // nanort_amd/csrc/closest.hip — the closest-point query for gfx950: which triangle of the context's mesh is nearest to a point, and
 // where on it (include/nanort_hip.h, "closest-point queries").
 //
-// The rule is include/nanort_closest.h's — ClosestUV, ClosestOnTriangle, BoxDist2, and the answer as a minimum over the admitted
+// The rule is include/nanort_closest.h's — ClosestPointOnTriangle, BoxDist2, and the answer as a minimum over the admitted
 // faces with a total tie-break (smallest dist2, then smallest prim_id) — so the answer does not depend on the tree, and the walk
 // below only decides which faces need not be looked at: a subtree is skipped iff the BoxDist2 of its box is strictly greater than
 // the best dist2 found so far, which in floating point can hide no face at or below it.
@@ -187,8 +187,7 @@ __global__ __launch_bounds__(kTraverseBlock) void k_closest_point(const ClosestA
           if ((prim >= a.range0) & (prim < a.range1) & (prim != a.skip_prim)) { // (as tri_solve: nanort.h:2387-2395)
             const T p[3] = {L.p0, L.p1, L.p2};
             T u, v, q[3];
-            nanort_closest::ClosestUV<T>(p, tri.p0, tri.p1, tri.p2, &u, &v);
-            const T dist2 = nanort_closest::ClosestOnTriangle<T>(p, tri.p0, tri.p1, tri.p2, u, v, q);
+            const T dist2 = nanort_closest::ClosestPointOnTriangle<T>(p, tri.p0, tri.p1, tri.p2, &u, &v, q);
             const bool acc = nanort_closest::Better<T>(dist2, prim, L.best, L.prim);
             L.best = acc ? dist2 : L.best;
             L.q0 = acc ? q[0] : L.q0;

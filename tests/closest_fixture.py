@@ -1,6 +1,7 @@
 """Closest-point test fixture (nrtClosestPointBatch*, include/nanort_closest.h): the CPU model (tests/closest_model.cc: brute force
 over the faces and a plain walk of a given tree), the header's host form (tests/cpp/closest_host_shim.cc over include/nanort.h,
-without the backend), and the point sets the CPU and the GPU tests share.
+without the backend), the point sets the CPU and the GPU tests share, and — for the rule's ACCURACY, which parity between
+implementations of one header cannot see — a long-double reference, hostile meshes and the envelope (at the end of the file).
 
 The point sets lie over the C1 mesh; each has more than 128 points and a count that is no multiple of 64:
   a  hit points of scenes.camera_rays(96, 64), pushed off the surface by random offsets up to a tenth of the mesh's diagonal
@@ -323,6 +324,364 @@ def _check_sets(real, verts, faces, sets):
         out, _ = brute(verts, faces, ab, opts)
         changed = sum(out[i].tobytes() != base[i].tobytes() for i in have)
         assert changed >= have.shape[0] / 10.0, "%s changes only %d of %d answers" % (what, changed, have.shape[0])
+
+
+# ---- accuracy: a long-double reference, hostile meshes and THE envelope ------------------------------------------------------------------
+# Everything above compares implementations of include/nanort_closest.h with each other.  What follows asks whether that rule is
+# accurate, against a formulation that shares nothing with it, on triangles chosen to hurt ("Accuracy").
+LD = np.longdouble
+# blob: well-shaped triangles in [-1, 1]^3, points uniform in [-1.5, 1.5]^3; blob_far: its points on a shell 1e6 away; blob_off:
+# everything offset by 1000; sliverN: c = a + s (b - a) + N eps(T) noise; needle: one edge 64 eps long; speck: two; collinear: integer
+# corners on one line; duplicates: blob with faces repeated and faces with two equal indices.  blob_near and sliver_ladder have
+# their points NEAR the faces — a point of a face pushed off by 10^-j, j = 0..7 — where an error along the face is an error of the
+# distance; the ladder's slivers are 2^k eps wide for every k up to the significand's length, corners in any order.  mixed: all of them.
+HOSTILE_NAMES = ("blob", "blob_far", "blob_off", "sliver1", "sliver4", "sliver16", "sliver64", "needle", "speck", "collinear", "duplicates",
+                 "blob_near", "sliver_ladder", "mixed")
+ENVELOPE = 8  # tol = ENVELOPE * eps(T) * S
+_HOSTILE = {}
+_HOSTILE_REF = {}
+_HOSTILE_BRUTE = {}
+_ORACLE = None
+
+
+def reference_available():
+    """The reference is only one if long double carries at least 61 bits: true on x86-64, not where it is an alias of double."""
+    return bool(np.finfo(LD).eps <= 2.0 ** -60)
+
+
+def require_reference():
+    import pytest
+
+    if not reference_available():
+        pytest.skip("np.longdouble has eps %.3g > 2^-60 on this machine: no high-precision reference to measure against" % float(np.finfo(LD).eps))
+
+
+def _split(x):
+    """Veltkamp's split of a long double (64-bit significand) into two halves of at most 32 bits: x = hi + lo exactly."""
+    t = x * LD(4294967297.0)  # 2^32 + 1
+    hi = t - (t - x)
+    return hi, x - hi
+
+
+def _diff_of_products(a, b, c, d):
+    """a*b - c*d with both products carried exactly (Dekker): the cross product of two nearly parallel edges keeps its direction."""
+    def two_prod(x, y):
+        p = x * y
+        xh, xl = _split(x)
+        yh, yl = _split(y)
+        return p, ((xh * yh - p) + xh * yl + xl * yh) + xl * yl
+
+    p, pe = two_prod(a, b)
+    q, qe = two_prod(c, d)
+    return (p - q) + (pe - qe)
+
+
+def _cross(x, y):
+    return np.stack([_diff_of_products(x[..., 1], y[..., 2], x[..., 2], y[..., 1]), _diff_of_products(x[..., 2], y[..., 0], x[..., 0], y[..., 2]),
+                     _diff_of_products(x[..., 0], y[..., 1], x[..., 1], y[..., 0])], axis=-1)
+
+
+def _reference_pairs(p, a, b, c):
+    """Distance from p to the triangle (a, b, c) in long double, arrays broadcast against each other: the smallest of the three
+    clamped segment projections, and the distance to the plane where the foot of the perpendicular lies inside the triangle."""
+    def seg(x, y):
+        d = y - x
+        dd = (d * d).sum(-1)
+        t = np.clip(((p - x) * d).sum(-1) / np.where(dd > 0, dd, LD(1)), LD(0), LD(1))
+        e = p - (x + t[..., None] * d)
+        return (e * e).sum(-1)
+
+    edge2 = np.minimum(np.minimum(seg(a, b), seg(b, c)), seg(c, a))
+    n = _cross(b - a, c - a)
+    nn = (n * n).sum(-1)
+    ok = nn > 0
+    h = ((p - a) * n).sum(-1)
+    inside = ok
+    for x, y in ((a, b), (b, c), (c, a)):  # the foot is inside iff p lies on the inner side of the three planes through an edge along n
+        inside = inside & (((p - x) * _cross(n, y - x)).sum(-1) >= 0)
+    plane2 = h * h / np.where(ok, nn, LD(1))
+    return np.sqrt(np.where(inside, plane2, edge2))
+
+
+def reference_distance(verts, faces, pts):
+    """d_true per point, np.longdouble: the distance from pts[k] (an (n, 3) array) to the nearest of `faces`; +inf without faces."""
+    assert reference_available()
+    v = np.asarray(verts).astype(LD)
+    f = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
+    p = np.asarray(pts).astype(LD).reshape(-1, 3)
+    out = np.full((p.shape[0],), np.inf, dtype=LD)
+    if f.shape[0] == 0:
+        return out
+    a, b, c = v[f[:, 0]][None], v[f[:, 1]][None], v[f[:, 2]][None]
+    for i in range(0, p.shape[0], 256):
+        out[i:i + 256] = _reference_pairs(p[i:i + 256, None, :], a, b, c).min(axis=1)
+    return out
+
+
+def reference_face_distance(verts, face_ids, pts):
+    """Paired: the distance from pts[k] to the triangle whose three vertex indices are face_ids[k], np.longdouble."""
+    assert reference_available()
+    v = np.asarray(verts).astype(LD)
+    f = np.asarray(face_ids, dtype=np.int64).reshape(-1, 3)
+    p = np.asarray(pts).astype(LD).reshape(-1, 3)
+    assert f.shape[0] == p.shape[0]
+    return _reference_pairs(p, v[f[:, 0]], v[f[:, 1]], v[f[:, 2]])
+
+
+def _soup(tri):
+    """(n, 3, 3) corners -> (verts, faces) with every face on vertices of its own."""
+    n = tri.shape[0]
+    return np.ascontiguousarray(tri.reshape(3 * n, 3)), np.arange(3 * n, dtype=np.uint32).reshape(n, 3)
+
+
+def _blob_tris(rng, real, n):
+    centre = rng.uniform(-0.75, 0.75, size=(n, 1, 3))
+    return (centre + rng.uniform(-0.25, 0.25, size=(n, 3, 3))).astype(real)
+
+
+def _unit(rng, n):
+    d = rng.normal(size=(n, 3))
+    return d / np.linalg.norm(d, axis=1)[:, None]
+
+
+def _sliver_tris(rng, real, n, width):
+    """c = a + s (b - a) + width eps(T) noise, computed IN `real`: |b - a| about 0.5, s in [0.1, 0.9]."""
+    real = np.dtype(real).type
+    a = rng.uniform(-0.75, 0.75, size=(n, 3)).astype(real)
+    b = (a + (_unit(rng, n) * rng.uniform(0.4, 0.6, size=(n, 1))).astype(real)).astype(real)
+    s = rng.uniform(0.1, 0.9, size=(n, 1)).astype(real)
+    noise = rng.uniform(-1.0, 1.0, size=(n, 3)).astype(real)
+    c = (a + s * (b - a)) + real(width * np.finfo(real).eps) * noise
+    assert c.dtype == np.dtype(real)
+    return np.stack([a, b, c], axis=1)
+
+
+def _short_edge_tris(rng, real, n, both):
+    """b (and, for a speck, c) 64 eps(T) away from a; otherwise c about 0.5 away."""
+    real = np.dtype(real).type
+    a = rng.uniform(-0.75, 0.75, size=(n, 3)).astype(real)
+    tiny = real(64 * np.finfo(real).eps)
+    b = a + tiny * _unit(rng, n).astype(real)
+    c = a + (tiny * _unit(rng, n).astype(real) if both else (_unit(rng, n) * rng.uniform(0.4, 0.6, size=(n, 1))).astype(real))
+    return np.stack([a, b, c], axis=1).astype(real)
+
+
+def _collinear_tris(rng, real, n):
+    """Integer corners, c = a + j d on the line through a and b = a + 4 d: between them for j in 1..3, beyond b for j = 6."""
+    a = rng.integers(-3, 4, size=(n, 3))
+    d = rng.integers(-2, 3, size=(n, 3))
+    d[(d == 0).all(axis=1)] = (1, 0, -1)
+    j = rng.choice([1, 2, 3, 6], size=(n, 1))
+    return np.stack([a, a + 4 * d, a + j * d], axis=1).astype(real)
+
+
+def _uniform_points(rng, real, n, half=1.5, centre=0.0):
+    return (centre + rng.uniform(-half, half, size=(n, 3))).astype(real)
+
+
+def _near_points(rng, real, tri, n):
+    """n points near the faces: a random point of a random face, pushed off in a random direction by 10^-j, j = 0..7."""
+    w = rng.dirichlet([1.0, 1.0, 1.0], size=n)
+    on_face = (w[:, :, None] * tri[rng.integers(0, tri.shape[0], size=n)].astype(np.float64)).sum(axis=1)
+    return (on_face + _unit(rng, n) * 10.0 ** -rng.integers(0, 8, size=(n, 1))).astype(real)
+
+
+def _ladder_tris(rng, real, n):
+    """Slivers 2^k eps(T) wide, k = face % (bits - 1): from one rounding wide to nearly well-shaped; corners in a random order."""
+    bits = np.finfo(real).nmant
+    tri = np.concatenate([_sliver_tris(rng, real, 1, 2 ** (i % (bits - 1))) for i in range(n)])
+    order = np.stack([rng.permutation(3) for _ in range(n)])
+    return np.ascontiguousarray(tri[np.arange(n)[:, None], order])
+
+
+def _hostile_geometry(real, name):
+    """(verts, faces, xyz) of one class, in `real` from the first rounding on; every class from a seed of its own."""
+    rng = np.random.default_rng(20261021 + 97 * HOSTILE_NAMES.index(name))
+    nf, npts = 299, 2999  # (no multiple of 64, more than one block of 256 lanes)
+    if name == "sliver_ladder":
+        tri = _ladder_tris(rng, real, nf)
+        return _soup(tri) + (_near_points(rng, real, tri, npts),)
+    if name in ("blob", "blob_far", "blob_off", "duplicates", "blob_near"):
+        tri = _blob_tris(np.random.default_rng(20261021), real, nf)  # the same blob in all five
+        if name == "blob_near":
+            return _soup(tri) + (_near_points(rng, real, tri, npts),)
+        if name == "blob_off":
+            tri = (tri + np.dtype(real).type(1000)).astype(real)
+            return _soup(tri) + (_uniform_points(rng, real, npts, centre=1000.0),)
+        if name == "blob_far":
+            return _soup(tri) + ((_unit(rng, npts) * 1e6).astype(real),)
+        v, f = _soup(tri)
+        if name == "duplicates":  # a tenth of the faces twice (the smaller prim_id must answer), a tenth with two equal indices
+            again = f[rng.choice(240, size=30, replace=False)]
+            flat = f[rng.choice(240, size=30, replace=False)].copy()
+            flat[:, 2] = flat[np.arange(30), rng.integers(0, 2, size=30)]
+            f = np.ascontiguousarray(np.concatenate([f[:240], again, flat])[rng.permutation(300)], dtype=np.uint32)
+        return v, f, _uniform_points(rng, real, npts)
+    if name.startswith("sliver"):
+        return _soup(_sliver_tris(rng, real, nf, int(name[6:]))) + (_uniform_points(rng, real, npts),)
+    if name in ("needle", "speck"):
+        return _soup(_short_edge_tris(rng, real, nf, name == "speck")) + (_uniform_points(rng, real, npts),)
+    if name == "collinear":
+        xyz = _uniform_points(rng, real, npts, half=12.0)
+        xyz[::3] = np.round(xyz[::3] * 2) / 2  # a third of the points on the half-integer lattice: exact ties, points on the segments
+        return _soup(_collinear_tris(rng, real, nf)) + (xyz,)
+    assert name == "mixed"
+    # 23 faces of every other class in one mesh, 299 in all, shuffled (blob_far and blob_near have blob's faces: 23 more slivers of
+    # 1 eps and 23 more of the ladder stand in for them); the points are uniform around the origin, around the offset blob and over
+    # the lattice triangles, and near the faces.  No point of the 1e6 shell: S, and with it the envelope, would grow a thousandfold
+    # and say nothing about the slivers any more.
+    parts = []
+    for other in HOSTILE_NAMES[:-1]:
+        v, f, _ = _hostile_geometry(real, other)
+        pick = np.random.default_rng(5 + HOSTILE_NAMES.index(other)).choice(f.shape[0], size=23, replace=False)
+        parts.append(_sliver_tris(rng, real, 23, 1) if other == "blob_far" else _ladder_tris(rng, real, 23) if other == "blob_near" else v[f[pick]])
+    tri = np.concatenate(parts)[rng.permutation(23 * len(parts))].astype(real)
+    xyz = np.concatenate([_uniform_points(rng, real, 1500), _uniform_points(rng, real, 400, centre=1000.0), _uniform_points(rng, real, 399, half=12.0),
+                          _near_points(rng, real, tri, 700)])
+    return _soup(tri) + (xyz[rng.permutation(xyz.shape[0])],)
+
+
+def scale_of(verts, xyz):
+    """S: the largest absolute coordinate among the points and the vertices."""
+    return float(max(np.abs(np.asarray(verts, dtype=np.float64)).max(), np.abs(np.asarray(xyz, dtype=np.float64)).max()))
+
+
+def tolerance(real, verts, xyz):
+    return LD(ENVELOPE) * LD(np.finfo(real).eps) * LD(scale_of(verts, xyz))
+
+
+def _check_radii(real, name, verts, pts, d_true):
+    """From the reference alone: the finite radii split the class's points both ways, and few of them lie where either answer passes."""
+    tol = tolerance(real, verts, pts["p"])
+    md = pts["max_dist"].astype(LD)
+    fin = np.isfinite(pts["max_dist"])
+    assert fin.sum() >= pts.shape[0] // 3
+    inside, outside = fin & (d_true <= md - tol), fin & (d_true > md + tol)
+    band = fin & ~inside & ~outside
+    assert band.sum() <= 0.01 * pts.shape[0], "class %s: %d points lie within the tolerance of their radius" % (name, band.sum())
+    assert inside.sum() >= fin.sum() / 10.0 and outside.sum() >= fin.sum() / 10.0, "class %s: radii split %d / %d" % (name, inside.sum(), outside.sum())
+
+
+def hostile_classes(real):
+    """{name: (verts, faces, points)} in `real`: at most 300 faces and 3000 point records per class; max_dist is +inf for every even
+    point and, for every odd one, drawn around the reference's median distance as _radii draws it.  Computed once; do not write."""
+    real = np.dtype(real)
+    if real not in _HOSTILE:
+        assert reference_available()
+        _HOSTILE[real] = _HostileClasses(real)
+    return _HOSTILE[real]
+
+
+class _HostileClasses(dict):
+    """hostile_classes' dictionary; a class and its reference distances are made when the class is first asked for."""
+
+    def __init__(self, real):
+        dict.__init__(self)
+        self.real = real
+
+    def __missing__(self, name):
+        real = self.real
+        v, f, xyz = _hostile_geometry(real, name)
+        assert v.dtype == real and xyz.dtype == real and f.shape[0] <= 300 and xyz.shape[0] <= 3000 and xyz.shape[0] % 64 != 0
+        d_true = reference_distance(v, f, xyz)
+        rng = np.random.default_rng(77 + HOSTILE_NAMES.index(name))
+        md = float(np.median(d_true)) * np.exp(rng.uniform(-1.0, 1.0, size=xyz.shape[0]))
+        md[::2] = np.inf
+        pts = make_points(real, xyz, md)
+        _check_radii(real, name, v, pts, d_true)
+        for arr in (v, f, pts, d_true):
+            arr.setflags(write=False)
+        _HOSTILE_REF[(real, name)] = d_true
+        self[name] = (v, f, pts)
+        return self[name]
+
+
+def hostile_reference(real, name):
+    """d_true of class `name`'s points over all of its faces (computed with the class; do not write)."""
+    hostile_classes(real)[name]
+    return _HOSTILE_REF[(np.dtype(real), name)]
+
+
+def hostile_brute(real, name):
+    """The model's brute force over class `name` (once per precision and class; do not write)."""
+    key = (np.dtype(real), name)
+    if key not in _HOSTILE_BRUTE:
+        v, f, pts = hostile_classes(real)[name]
+        out, found = brute(v, f, pts)
+        out.setflags(write=False)
+        found.setflags(write=False)
+        _HOSTILE_BRUTE[key] = (out, found)
+    return _HOSTILE_BRUTE[key]
+
+
+def mixed_trees(real):
+    """The two reference-built trees over `mixed` that the CPU and the GPU tests walk: the oracle's default build, and one with
+    min_leaf = 16 and max_depth = 3, which must have a leaf of more than 16 faces.  {name: (nodes, indices)}."""
+    global _ORACLE
+    from oracle.bindings import Oracle
+
+    if _ORACLE is None:
+        _ORACLE = Oracle()
+    v, f, _ = hostile_classes(real)["mixed"]
+    trees = {"default": _ORACLE.build(v, f)[:2], "deep_leaves": _ORACLE.build(v, f, min_leaf=16, max_depth=3)[:2]}
+    nodes = trees["deep_leaves"][0]
+    leaves = nodes[nodes["flag"] != 0]
+    assert leaves["data"][:, 0].max() > 16, "the min_leaf = 16, max_depth = 3 tree has no leaf of more than 16 faces"
+    assert leaves["data"][:, 0].sum() == f.shape[0]
+    return trees
+
+
+def admitted(nf, opts):
+    """Which of nf faces the options (range0, range1, skip) admit."""
+    r0, r1, skip = DEFAULT_OPTS if opts is None else opts
+    ids = np.arange(nf, dtype=np.int64)
+    return (ids >= r0) & (ids < r1) & (ids != skip)
+
+
+def assert_within_envelope(real, verts, faces, pts, records, found, what, opts=None, d_true=None):
+    """THE accuracy contract of a closest-point answer ("Accuracy"), against the long-double reference over the faces
+    the options admit.  With tol = 8 eps(T) S, S the largest absolute coordinate among the points and the vertices:
+      * |sqrt(dist2) - d_true| <= tol for every found point — too near is as wrong as too far;
+      * the reported point lies within tol of the face prim_id (reference_face_distance);
+      * dist2 is |p - point|^2, recomputed in long double, within 4 eps relative plus tol^2;
+      * (1 - u - v) a + u b + v c is the reported point, within tol per component; u >= 0, v >= 0, u + v <= 1 + 4 eps;
+      * found is 1 where d_true <= max_dist - tol and 0 where d_true > max_dist + tol (between them either passes).
+    prim_id is not compared with the reference's face: near-ties legitimately differ.  Prints the largest errors, in eps(T) S."""
+    real = np.dtype(real)
+    eps = LD(np.finfo(real).eps)
+    faces = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
+    found = np.asarray(found)
+    ok = admitted(faces.shape[0], opts)
+    if d_true is None:
+        d_true = reference_distance(verts, faces[ok], pts["p"])
+    unit = eps * LD(scale_of(verts, pts["p"]))
+    tol = LD(ENVELOPE) * unit
+    md = pts["max_dist"].astype(LD)
+    must, must_not = d_true <= md - tol, d_true > md + tol
+    sel = found != 0
+    rec, p, d = records[sel], pts["p"][sel].astype(LD), d_true[sel]
+    prim = rec["prim_id"].astype(np.int64)
+    assert ok[prim].all(), "%s: a face the options exclude is reported" % what
+    err = (np.sqrt(rec["dist2"].astype(LD)) - d) / unit
+    q = rec["point"].astype(LD)
+    on_face = reference_face_distance(verts, faces[prim], rec["point"]) / unit
+    again = ((p - q) ** 2).sum(-1)
+    v = np.asarray(verts).astype(LD)
+    a, b, c = v[faces[prim, 0]], v[faces[prim, 1]], v[faces[prim, 2]]
+    u_, v_ = rec["u"].astype(LD), rec["v"].astype(LD)
+    named = np.abs(((LD(1) - u_ - v_)[:, None] * a + u_[:, None] * b + v_[:, None] * c) - q).max() / unit
+    print("%s: %d found, error of sqrt(dist2) in eps*S [%.3g, %.3g], point off its face %.3g, point off its (u, v) %.3g"
+          % (what, sel.sum(), float(err.min()), float(err.max()), float(on_face.max()), float(named)))
+    assert found[must].all(), "%s: %d points with a face well inside max_dist are not found" % (what, (found[must] == 0).sum())
+    assert not found[must_not].any(), "%s: %d points whose nearest face is well outside max_dist are found" % (what, (found[must_not] != 0).sum())
+    assert sel.sum() >= sel.shape[0] // 2, "%s: fewer than half of the points are found" % what
+    assert float(err.max()) <= ENVELOPE, "%s: sqrt(dist2) is up to %.4g eps*S ABOVE the true distance" % (what, float(err.max()))
+    assert float(err.min()) >= -ENVELOPE, "%s: sqrt(dist2) is up to %.4g eps*S BELOW the true distance" % (what, -float(err.min()))
+    assert float(on_face.max()) <= ENVELOPE, "%s: a reported point lies %.4g eps*S off its face" % (what, float(on_face.max()))
+    assert (np.abs(rec["dist2"].astype(LD) - again) <= LD(4) * eps * again + tol * tol).all(), "%s: dist2 is not |p - point|^2" % what
+    assert float(named) <= ENVELOPE, "%s: (u, v) name a point %.4g eps*S from the reported one" % (what, float(named))
+    assert (rec["u"] >= 0).all() and (rec["v"] >= 0).all() and (u_ + v_ <= LD(1) + LD(4) * eps).all(), "%s: (u, v) outside the triangle" % what
+    return float(err.min()), float(err.max())
 
 
 def assert_same(out, found, ref_out, ref_found, what=""):

@@ -1,5 +1,6 @@
 """The closest-point rule (include/nanort_closest.h) on the CPU: the bound its cull rests on, the walk against brute force on two
-trees, the header's host form, an independent formulation, and the C ABI's layout and exports.  No GPU."""
+trees, the header's host form, an independent formulation, the accuracy envelope against a long-double reference on hostile
+meshes, and the C ABI's layout and exports.  No GPU."""
 import ctypes
 import os
 import re
@@ -117,10 +118,10 @@ def _independent_dist2(p, a, b, c):
 
 def test_rule_agrees_with_an_independent_formulation():
     """The rule at double against the formulation above, on the coordinates of sets a and b with max_dist = +inf: the largest
-    relative difference of dist2 measured here is 1.65e-12 (set a 1.65e-12, set b 1.56e-13; the model's answer against the minimum
-    of the other formulation over all faces).  The bound is eight times that — room for other meshes' conditioning, not for error
-    in the rule."""
-    measured = 1.65e-12
+    relative difference of dist2 measured here is 1.24e-12 (set a 1.24e-12, set b 3.42e-13; the model's answer against the minimum
+    of the other formulation over all faces; 1.65e-12 while the rule was Ericson's cascade).  The bound is eight times that — room
+    for other meshes' conditioning, not for error in the rule."""
+    measured = 1.24e-12
     v, f = cf.mesh(np.float64)
     a, b, c = v[f[:, 0]], v[f[:, 1]], v[f[:, 2]]
     worst = 0.0
@@ -134,6 +135,63 @@ def test_rule_agrees_with_an_independent_formulation():
         print("independent formulation, set %s: largest relative difference of dist2 %.3g" % (name, rel.max()))
         worst = max(worst, float(rel.max()))
     assert worst <= 8 * measured
+
+
+@pytest.mark.parametrize("name", cf.HOSTILE_NAMES)
+@pytest.mark.parametrize("real", REALS, ids=IDS)
+def test_rule_within_envelope_of_the_reference(real, name):
+    """The rule's brute force on every hostile class against the long-double reference: cf.assert_within_envelope, 8 eps(T) S.
+    Largest errors of sqrt(dist2) measured here, in eps(T) S, [most below, most above] the true distance:
+
+      class          fp32, Ericson's cascade  fp32, this rule   fp64, Ericson's cascade  fp64, this rule
+      blob           [-0.48, 0.42]            [-0.41, 0.42]     [-0.42, 0.40]            [-0.42, 0.52]
+      blob_far       [-0.62, 0.58]            [-0.62, 0.58]     [-0.57, 0.49]            [-0.57, 0.49]
+      blob_off       [-0.96, 0.93]            [-1.05, 1.11]     [-0.84, 1.09]            [-0.84, 1.08]
+      sliver1        [-0.39, 2.1e5]           [-0.45, 0.43]     [-0.46, 7.5e12]          [-0.46, 0.34]
+      sliver4        [-0.44, 7.8e4]           [-0.37, 0.42]     [-0.40, 2.8e12]          [-0.40, 0.33]
+      sliver16       [-0.41, 2.1e4]           [-0.40, 0.41]     [-0.38, 1.1e14]          [-0.38, 0.43]
+      sliver64       [-0.47, 0.46]            [-0.47, 0.46]     [-0.34, 1.01]            [-0.38, 0.41]
+      needle         [-0.32, 0.37]            [-0.37, 0.48]     [-0.40, 0.39]            [-0.34, 0.39]
+      speck          [-0.43, 0.29]            [-0.43, 0.29]     [-0.31, 0.28]            [-0.31, 0.28]
+      collinear      [-0.48, 2.3e5]           [-0.48, 0.23]     [-0.67, 4.8e13]          [-0.67, 0.25]
+      duplicates     [-0.45, 0.50]            [-0.51, 0.50]     [-0.49, 0.47]            [-0.49, 0.47]
+      blob_near      [-0.41, 47.6]            [-0.40, 0.41]     [-0.48, 0.35]            [-0.41, 0.47]
+      sliver_ladder  [-0.32, 3.4e5]           [-0.29, 0.32]     [-0.27, 1.6e14]          [-0.26, 0.35]
+      mixed          [-0.70, 238]             [-0.68, 0.86]     [-0.78, 1.2e12]          [-0.65, 0.56]
+
+    "Ericson's cascade" is the rule as it stood before ClosestPointOnTriangle (the region test alone): this test failed on the
+    slivers, `collinear` (a face whose third corner lies on the line beyond the second), the ladder and `mixed` in both precisions,
+    and on `blob_near` in fp32 — off by a few hundredths in absolute terms on coordinates of size 1.  All rows are now below 1.2 of 8."""
+    cf.require_reference()
+    v, f, pts = cf.hostile_classes(real)[name]
+    out, found = cf.hostile_brute(real, name)
+    cf.assert_within_envelope(real, v, f, pts, out, found, "%s, %s" % (IDS[REALS.index(real)], name), d_true=cf.hostile_reference(real, name))
+
+
+@pytest.fixture(scope="module", params=REALS, ids=IDS)
+def mixed(request):
+    cf.require_reference()
+    real = request.param
+    v, f, pts = cf.hostile_classes(real)["mixed"]
+    return real, v, f, pts, cf.mixed_trees(real)
+
+
+@pytest.mark.parametrize("tree", ["default", "deep_leaves"])
+def test_walk_over_the_mixed_mesh_within_envelope(mixed, tree):
+    """The model's walk over both reference-built trees of `mixed`: byte-equal to brute force, and within the envelope."""
+    real, v, f, pts, trees = mixed
+    nodes, idx = trees[tree]
+    out, found = cf.walk(nodes, idx, v, f, pts)
+    cf.assert_same(out, found, *cf.hostile_brute(real, "mixed"), what="mixed, %s tree" % tree)
+    cf.assert_within_envelope(real, v, f, pts, out, found, "mixed, walk of the %s tree" % tree, d_true=cf.hostile_reference(real, "mixed"))
+
+
+def test_header_host_form_over_the_mixed_mesh_within_envelope(mixed):
+    """BVHAccel<T>::ClosestPointBatch of include/nanort.h without the backend, over its own host-built tree of `mixed`."""
+    real, v, f, pts, _ = mixed
+    out, found = cf.HostAccel(v, f).closest(pts)
+    cf.assert_same(out, found, *cf.hostile_brute(real, "mixed"), what="mixed, header's host form")
+    cf.assert_within_envelope(real, v, f, pts, out, found, "mixed, header's host form", d_true=cf.hostile_reference(real, "mixed"))
 
 
 def test_layout_and_exports():

@@ -1,5 +1,6 @@
 """nrtClosestPointBatch* on the GPU: byte-identical records and found bytes against the model's brute force over the faces
-(tests/closest_fixture.py, tests/closest_model.cc), in fp32 and fp64."""
+(tests/closest_fixture.py, tests/closest_model.cc), in fp32 and fp64; on the hostile meshes also within the accuracy envelope of the
+fixture's long-double reference."""
 import os
 import re
 
@@ -169,6 +170,79 @@ def test_motion_context_answers_for_keyframe_0(real):
     for name in ("a", "b"):
         out, found = a.ClosestPointBatch(cf.point_sets(real)[name])
         cf.assert_same(out, found, *cf.expected(real, name), what="set %s, motion context" % name)
+
+
+# ---- accuracy on hostile meshes: byte-equal to brute force AND within the envelope of the long-double reference ------------------------
+@pytest.mark.parametrize("name", cf.HOSTILE_NAMES)
+@pytest.mark.parametrize("real", REALS, ids=IDS)
+def test_hostile_classes_built_tree(real, name):
+    """Build over every hostile class (tests/closest_fixture.py: slivers, needles, specks, collinear and repeated faces, far and
+    offset points, points near the faces), then the query: the model's brute force byte for byte, and cf.assert_within_envelope.
+    `mixed` goes through the Device form."""
+    cf.require_reference()
+    v, f, pts = cf.hostile_classes(real)[name]
+    a = built(real, v, f)
+    if name == "mixed":
+        _, d_out, d_found = device_query(a, pts)
+        out, found = from_device(real, d_out, d_found)
+    else:
+        out, found = a.ClosestPointBatch(pts)
+    what = "%s, %s" % (IDS[REALS.index(real)], name)
+    cf.assert_same(out, found, *cf.hostile_brute(real, name), what=what)
+    cf.assert_within_envelope(real, v, f, pts, out, found, what, d_true=cf.hostile_reference(real, name))
+
+
+@pytest.mark.parametrize("tree", ["default", "deep_leaves"])
+@pytest.mark.parametrize("real", REALS, ids=IDS)
+def test_hostile_mixed_adopted_trees(real, tree):
+    """SetTree with the reference-built trees of `mixed` — the default build, and min_leaf = 16 with max_depth = 3, whose leaves
+    hold more than 16 records (cf.mixed_trees asserts it) — under the class's radii (+inf and finite by turns), then a
+    prim_ids_range and a skip_prim_id case on the first 999 points, the reference restricted to the admitted faces."""
+    cf.require_reference()
+    v, f, pts = cf.hostile_classes(real)["mixed"]
+    nodes, idx = cf.mixed_trees(real)[tree]
+    a = BVHAccel(real)
+    a.SetMesh(TriangleMesh(v, f))
+    a.SetTree(nodes, idx)
+    what = "%s, mixed, %s tree" % (IDS[REALS.index(real)], tree)
+    ref_out, ref_found = cf.hostile_brute(real, "mixed")
+    out, found = a.ClosestPointBatch(pts)
+    cf.assert_same(out, found, ref_out, ref_found, what=what)
+    cf.assert_within_envelope(real, v, f, pts, out, found, what, d_true=cf.hostile_reference(real, "mixed"))
+    some = pts[:999]
+    busiest = int(np.bincount(ref_out["prim_id"][:999][ref_found[:999] != 0]).argmax())
+    for oname, opts in (("range", cf.middle_third(f.shape[0])), ("skip", (0, 0x7FFFFFFF, busiest))):
+        exp_out, exp_found = cf.brute(v, f, some, opts)
+        assert exp_out.tobytes() != ref_out[:999].tobytes(), "the %s case changes no answer" % oname
+        out, found = a.ClosestPointBatch(some, options=cf.trace_options(opts))
+        cf.assert_same(out, found, exp_out, exp_found, what="%s, options %s" % (what, oname))
+        cf.assert_within_envelope(real, v, f, some, out, found, "%s, options %s" % (what, oname), opts=opts)
+
+
+@pytest.mark.parametrize("real", REALS, ids=IDS)
+def test_refit_collapses_faces_into_slivers(real):
+    """Refit of `blob` to vertices that put the third corner of every third face within a rounding or so of its first edge."""
+    cf.require_reference()
+    v, f, pts = cf.hostile_classes(real)["blob"]
+    a = built(real, v, f)
+    rng = np.random.default_rng(12)
+    third = np.arange(0, f.shape[0], 3)
+    moved = v.copy()
+    A, B = moved[f[third, 0]], moved[f[third, 1]]
+    s = rng.uniform(0.1, 0.9, size=(third.shape[0], 1)).astype(real)
+    moved[f[third, 2]] = (A + s * (B - A)) + np.dtype(real).type(np.finfo(real).eps) * rng.uniform(-1.0, 1.0, size=A.shape).astype(real)
+    assert moved.dtype == np.dtype(real)
+    # really slivers of about one rounding, by long double alone: the third corner's height over the first edge
+    ld = cf.LD
+    ab, ac = (B.astype(ld) - A.astype(ld)), (moved[f[third, 2]].astype(ld) - A.astype(ld))
+    height = np.sqrt((cf._cross(ab, ac) ** 2).sum(-1) / (ab * ab).sum(-1))
+    assert (height <= 4 * np.finfo(real).eps).all() and (height > 0).sum() >= 0.9 * third.shape[0]
+    a.Refit(moved)
+    some = pts[:1499]
+    out, found = a.ClosestPointBatch(some)
+    what = "%s, blob after a collapsing Refit" % IDS[REALS.index(real)]
+    cf.assert_same(out, found, *cf.brute(moved, f, some), what=what)
+    cf.assert_within_envelope(real, moved, f, some, out, found, what)
 
 
 def _tiled(real, n):
