@@ -49,6 +49,7 @@
 
 #include "nanort_motion.h"  // the motion-blur vertex rule (MotionTriangleIntersector), shared with the device walk
 #include "nanort_closest.h"  // the closest-point rule (BVHAccel::ClosestPoint), shared with the device kernel
+#include "nanort_sdf.h"      // the signed-distance rule (BVHAccel::SignedDistance, FeatureNormals), shared with the device kernels
 #ifdef NANORT_USE_HIP_BACKEND
 #include <mutex>
 
@@ -503,6 +504,24 @@ class ClosestPointResult {
   T v;
   unsigned int prim_id;
   unsigned int pad;
+};
+
+// The answer of BVHAccel::SignedDistance() / SignedDistanceBatch() (laid out as nrt_signed_f32 / _f64): a ClosestPointResult with
+// `feature` in the place of `pad` — bits 0..2 the feature of face prim_id that holds the nearest point (0 its interior, 1 / 2 / 3 the
+// edge ab / ac / bc, 4 / 5 / 6 the vertex a / b / c), bit 31 set exactly when the query point is inside; 0 when nothing was found.
+template <typename T = float>
+class SignedDistanceResult {
+ public:
+  T point[3];
+  T dist2;
+  T u;
+  T v;
+  unsigned int prim_id;
+  unsigned int feature;
+  bool Inside() const { return (feature & nanort_sdf::kInsideBit) != 0u; }
+  unsigned int Feature() const { return feature & nanort_sdf::kFeatureMask; }
+  // The distance with its sign: negative inside.
+  T Signed() const { return Inside() ? -std::sqrt(dist2) : std::sqrt(dist2); }
 };
 
 // Watertight ray/triangle test (Woop, Benthin, Wald 2013), same operation
@@ -1466,6 +1485,9 @@ struct HipApi;
     typedef nrt_point_##S PointPod;                                               \
     typedef nrt_closest_##S ClosestPod;                                           \
     NANORT_HIP_ENTRY(ClosestPoint, nrtClosestPointBatch, S)                       \
+    /* signed distance queries */                                                 \
+    typedef nrt_signed_##S SignedPod;                                             \
+    NANORT_HIP_ENTRY(SignedDistance, nrtSignedDistanceBatch, S)                   \
   };
 NANORT_HIP_API(float, f32)
 NANORT_HIP_API(double, f64)
@@ -1481,6 +1503,39 @@ inline std::mutex &HostTreeMutex() {
 }
 #endif
 }  // namespace detail
+
+// The angle-weighted pseudonormals of a triangle mesh, built on the host by the rule of nanort_sdf.h (BuildFeatureNormals): what
+// BVHAccel::SignedDistance() signs with.  face_normals: [num_faces][4][3] — the unit normal, then the edge normals of ab, ac, bc;
+// vertex_normals: [num_vertices][3], num_vertices the largest vertex index + 1.  Vertices are identified by index, not position.
+// (The GPU derives its own from the device-resident mesh: nrtGetFeatureNormals; face and edge normals are the same bytes, vertex
+// normals differ by the device's atan2.)
+template <typename T = float>
+class FeatureNormals {
+ public:
+  FeatureNormals() : num_faces(0), num_vertices(0) {}
+  FeatureNormals(const TriangleMesh<T> &mesh, size_t num_faces_) { Build(mesh, num_faces_); }
+  void Build(const TriangleMesh<T> &mesh, size_t num_faces_) {
+    num_faces = num_faces_;
+    num_vertices = 0;
+    for (size_t i = 0; i < 3 * num_faces; i++) num_vertices = std::max(num_vertices, static_cast<size_t>(mesh.faces_[i]) + 1);
+    std::vector<T> tight(3 * num_vertices);
+    for (size_t v = 0; v < num_vertices; v++) {
+      const T *src = get_vertex_addr<T>(mesh.vertices_, v, mesh.vertex_stride_bytes_);
+      tight[3 * v + 0] = src[0], tight[3 * v + 1] = src[1], tight[3 * v + 2] = src[2];
+    }
+    face_normals.assign(12 * num_faces, static_cast<T>(0.0));
+    vertex_normals.assign(3 * num_vertices, static_cast<T>(0.0));
+    nanort_sdf::BuildFeatureNormals<T>(tight.empty() ? NULL : &tight[0], mesh.faces_, num_faces, num_vertices,
+                                       face_normals.empty() ? NULL : &face_normals[0], vertex_normals.empty() ? NULL : &vertex_normals[0]);
+  }
+  // The normal of `feature` (0..6) of face `prim`.
+  const T *Of(const TriangleMesh<T> &mesh, unsigned int prim, unsigned int feature) const {
+    if (feature < nanort_sdf::kFeatureVertexA) return &face_normals[12 * static_cast<size_t>(prim) + 3 * feature];
+    return &vertex_normals[3 * static_cast<size_t>(mesh.faces_[3 * static_cast<size_t>(prim) + (feature - nanort_sdf::kFeatureVertexA)])];
+  }
+  std::vector<T> face_normals, vertex_normals;
+  size_t num_faces, num_vertices;
+};
 
 template <typename T>
 class BVHAccel {
@@ -1893,7 +1948,14 @@ class BVHAccel {
   // walk of nodes_ enters the nearer child first and skips a subtree iff its box lies strictly farther than the best so far.
   // Returns whether a face was found; *out is written either way (ClosestPointResult above).  `mesh`: the one the tree was built over.
   bool ClosestPoint(const T p[3], T max_dist, const TriangleMesh<T> &mesh, const BVHTraceOptions &options, ClosestPointResult<T> *out) const {
+    unsigned int feature;
+    return ClosestWalk(p, max_dist, mesh, options, out, &feature);
+  }
+  // The walk behind ClosestPoint() and SignedDistance(): *feature receives the winning candidate's code of the answer (0: none).
+  bool ClosestWalk(const T p[3], T max_dist, const TriangleMesh<T> &mesh, const BVHTraceOptions &options, ClosestPointResult<T> *out,
+                   unsigned int *feature) const {
     EnsureHostTree();
+    *feature = 0u;
     out->point[0] = p[0], out->point[1] = p[1], out->point[2] = p[2];
     out->dist2 = max_dist * max_dist;
     out->u = out->v = static_cast<T>(0.0);
@@ -1919,16 +1981,51 @@ class BVHAccel {
           const T *b = get_vertex_addr<T>(mesh.vertices_, mesh.faces_[3 * prim + 1], mesh.vertex_stride_bytes_);
           const T *c = get_vertex_addr<T>(mesh.vertices_, mesh.faces_[3 * prim + 2], mesh.vertex_stride_bytes_);
           T u, v, q[3];
-          const T dist2 = nanort_closest::ClosestPointOnTriangle<T>(p, a, b, c, &u, &v, q);
+          unsigned int f;
+          const T dist2 = nanort_closest::ClosestFeatureOnTriangle<T>(p, a, b, c, &u, &v, q, &f);
           if (!nanort_closest::Better<T>(dist2, prim, out->dist2, out->prim_id)) continue;
           out->point[0] = q[0], out->point[1] = q[1], out->point[2] = q[2];
           out->dist2 = dist2;
           out->u = u, out->v = v;
           out->prim_id = prim;
+          *feature = f;
         }
       }
     }
     return out->prim_id != 0xFFFFFFFFu;
+  }
+  // ClosestPoint(), and on which side of the surface p lies (nanort_sdf.h: the sign of (p - point) . n for the pseudonormal n of
+  // the feature that holds the nearest point) — on the HOST, with or without the backend.  `normals`: FeatureNormals of `mesh`,
+  // always of the WHOLE mesh, whatever faces `options` admits.  Returns whether a face was found.
+  bool SignedDistance(const T p[3], T max_dist, const TriangleMesh<T> &mesh, const FeatureNormals<T> &normals, const BVHTraceOptions &options,
+                      SignedDistanceResult<T> *out) const {
+    static_assert(sizeof(SignedDistanceResult<T>) == sizeof(ClosestPointResult<T>), "a signed record is a closest-point record");
+    ClosestPointResult<T> r;
+    unsigned int feature;
+    const bool found = ClosestWalk(p, max_dist, mesh, options, &r, &feature);
+    out->point[0] = r.point[0], out->point[1] = r.point[1], out->point[2] = r.point[2];
+    out->dist2 = r.dist2, out->u = r.u, out->v = r.v, out->prim_id = r.prim_id;
+    out->feature = found ? nanort_sdf::FeatureWord<T>(p, r.point, normals.Of(mesh, r.prim_id, feature), feature) : 0u;
+    return found;
+  }
+  bool SignedDistanceBatchHost(const T *points, const T *max_dists, size_t num_points, const TriangleMesh<T> &mesh, const FeatureNormals<T> &normals,
+                               SignedDistanceResult<T> *out, unsigned char *found_out = NULL, const BVHTraceOptions &options = BVHTraceOptions()) const {
+    for (size_t i = 0; i < num_points; i++) {
+      const bool found = SignedDistance(points + 3 * i, max_dists ? max_dists[i] : std::numeric_limits<T>::infinity(), mesh, normals, options, &out[i]);
+      if (found_out) found_out[i] = found ? 1 : 0;
+    }
+    return true;
+  }
+  // The batch call: with NANORT_USE_HIP_BACKEND and a triangle tree on the GPU one launch of nrtSignedDistanceBatch, which signs with
+  // the normals the GPU derived from its own copy of the mesh (`normals` is not read: point, dist2, u, v, prim_id and the feature code
+  // are byte-identical to the host loop's, the sign may differ where (p - point) . n is within rounding of 0 at a vertex); the host
+  // loop otherwise.
+  bool SignedDistanceBatch(const T *points, const T *max_dists, size_t num_points, const TriangleMesh<T> &mesh, const FeatureNormals<T> &normals,
+                           SignedDistanceResult<T> *out, unsigned char *found_out = NULL, const BVHTraceOptions &options = BVHTraceOptions()) const {
+#ifdef NANORT_USE_HIP_BACKEND
+    if (dev_.ctx && geom_.kind == 0) return SignedDistanceBatchBackend(points, max_dists, num_points, out, found_out, options);
+#endif
+    return SignedDistanceBatchHost(points, max_dists, num_points, mesh, normals, out, found_out, options);
   }
   // ... for `num_points` points, point i at points[3 * i] with max_dists[i] (NULL: +inf for every point): N calls of ClosestPoint().
   // Every record is written; found_out[i] (optional) receives 1 / 0.
@@ -2411,10 +2508,12 @@ class BVHAccel {
     d.reserved = 0;
     return d;
   }
-  // The GPU side of ClosestPointBatch(): the points packed into the library's 4-scalar records, one host call of the library.
-  bool ClosestPointBatchBackend(const T *points, const T *max_dists, size_t num_points, ClosestPointResult<T> *out, unsigned char *found_out,
-                                const BVHTraceOptions &options) const {
-    static_assert(sizeof(ClosestPointResult<T>) == sizeof(typename Api::ClosestPod), "closest-point record layout");
+  // The GPU side of ClosestPointBatch() and SignedDistanceBatch(): the points packed into the library's 4-scalar records, one host
+  // call of the library (`entry`: Api::ClosestPoint or Api::SignedDistance, whose records share one layout).
+  template <class Entry, class Pod, class Result>
+  bool PointBatchBackend(Entry entry, const T *points, const T *max_dists, size_t num_points, Result *out, unsigned char *found_out,
+                         const BVHTraceOptions &options) const {
+    static_assert(sizeof(Result) == sizeof(Pod), "point query record layout");
     std::lock_guard<std::mutex> lock(batch_mutex_);
     if (!DeviceTreeReady(0)) return false;
     if (num_points == 0) return true;
@@ -2424,7 +2523,15 @@ class BVHAccel {
       pts[i].max_dist = max_dists ? max_dists[i] : std::numeric_limits<T>::infinity();
     }
     const nrt_trace_options o = TraceOptions(options);
-    return Ok(Api::ClosestPoint(Context(), &pts[0], num_points, &o, reinterpret_cast<typename Api::ClosestPod *>(out), found_out));
+    return Ok(entry(Context(), &pts[0], num_points, &o, reinterpret_cast<Pod *>(out), found_out));
+  }
+  bool ClosestPointBatchBackend(const T *points, const T *max_dists, size_t num_points, ClosestPointResult<T> *out, unsigned char *found_out,
+                                const BVHTraceOptions &options) const {
+    return PointBatchBackend<decltype(Api::ClosestPoint), typename Api::ClosestPod>(Api::ClosestPoint, points, max_dists, num_points, out, found_out, options);
+  }
+  bool SignedDistanceBatchBackend(const T *points, const T *max_dists, size_t num_points, SignedDistanceResult<T> *out, unsigned char *found_out,
+                                  const BVHTraceOptions &options) const {
+    return PointBatchBackend<decltype(Api::SignedDistance), typename Api::SignedPod>(Api::SignedDistance, points, max_dists, num_points, out, found_out, options);
   }
   // The checks every host batch call makes (caller holds batch_mutex_): a context, the primitive kind the call's records are
   // for (0 triangles, 1 spheres), and a tree adopted by Load() uploaded — after a copy-on-write detach when the contexts are

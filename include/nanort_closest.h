@@ -22,6 +22,10 @@
 //                                                   u >= 0, v >= 0 and u + v <= 1
 //                                        (t = 0 for an edge of no length).  A clamped t is exactly 0 or 1, so the vertex regions
 //                                        return their vertex exactly; dist2 is NaN only where every candidate's is.
+//   ClosestFeatureOnTriangle(..., &feature)  the same, and the code of the candidate that WON: 0 the face candidate, 1 / 2 / 3 the edge
+//                                        ab / ac / bc, 4 / 5 / 6 the vertex a / b / c — an edge candidate whose clamped t is exactly 0
+//                                        or 1 is a vertex (ab: a, b; ac: a, c; bc: b, c).  It cannot be recovered from (u, v)
+//                                        afterwards; include/nanort_sdf.h signs the distance by it.
 //   ClosestUV(p, a, b, c) -> (u, v)      the same (u, v) alone; ClosestOnTriangle of them gives the same q and dist2, bit for bit
 //                                        (the tests' model states the rule in these two calls).
 //   BoxDist2(p, bmin, bmax)              m_k = max(bmin_k - p_k, p_k - bmax_k, 0), the squares summed in the same order.
@@ -94,20 +98,36 @@ NANORT_CLOSEST_FN T SegmentParam(T num, T den) {
   return t < T(0) ? T(0) : (t > T(1) ? T(1) : t);
 }
 
-// The candidate (cu, cv) against the best so far (*u, *v, q, *dist2): taken when strictly nearer, or when the best is NaN.
+// Which candidate won (ClosestFeatureOnTriangle): the face's interior, an edge or a vertex.
+namespace feature_codes {
+enum : unsigned int { kFeatureFace = 0u, kFeatureEdgeAB = 1u, kFeatureEdgeAC = 2u, kFeatureEdgeBC = 3u, kFeatureVertexA = 4u, kFeatureVertexB = 5u, kFeatureVertexC = 6u };
+}
+using namespace feature_codes;
+
+// The code of an edge candidate at parameter t: the vertex at t == 0, the vertex at t == 1, the edge between them otherwise.
 template <typename T>
-NANORT_CLOSEST_FN void ClosestCandidate(const T p[3], const T a[3], const T b[3], const T c[3], T cu, T cv, T *u, T *v, T q[3], T *dist2) {
+NANORT_CLOSEST_FN unsigned int EdgeFeature(T t, unsigned int edge, unsigned int at0, unsigned int at1) {
+  return t == T(0) ? at0 : (t == T(1) ? at1 : edge);
+}
+
+// The candidate (cu, cv) with code cf against the best so far (*u, *v, q, *dist2, *feature): taken when strictly nearer, or when the
+// best is NaN.
+template <typename T>
+NANORT_CLOSEST_FN void FeatureCandidate(const T p[3], const T a[3], const T b[3], const T c[3], T cu, T cv, unsigned int cf, T *u, T *v, T q[3],
+                                        T *dist2, unsigned int *feature) {
   T cq[3];
   const T d = ClosestOnTriangle(p, a, b, c, cu, cv, cq);
   const bool take = d < *dist2 || *dist2 != *dist2;
   *u = take ? cu : *u, *v = take ? cv : *v;
   q[0] = take ? cq[0] : q[0], q[1] = take ? cq[1] : q[1], q[2] = take ? cq[2] : q[2];
   *dist2 = take ? d : *dist2;
+  *feature = take ? cf : *feature;
 }
 
-// The nearest point of the triangle to p: (u, v) and the point into q; returns dist2.  See the head of the file.
+// The nearest point of the triangle to p: (u, v), the point into q and the code of the winning candidate; returns dist2.  See the
+// head of the file.
 template <typename T>
-NANORT_CLOSEST_FN T ClosestPointOnTriangle(const T p[3], const T a[3], const T b[3], const T c[3], T *u, T *v, T q[3]) {
+NANORT_CLOSEST_FN T ClosestFeatureOnTriangle(const T p[3], const T a[3], const T b[3], const T c[3], T *u, T *v, T q[3], unsigned int *feature) {
   const T ab0 = b[0] - a[0], ab1 = b[1] - a[1], ab2 = b[2] - a[2];
   const T ac0 = c[0] - a[0], ac1 = c[1] - a[1], ac2 = c[2] - a[2];
   const T bc0 = c[0] - b[0], bc1 = c[1] - b[1], bc2 = c[2] - b[2];
@@ -119,17 +139,25 @@ NANORT_CLOSEST_FN T ClosestPointOnTriangle(const T p[3], const T a[3], const T b
   const T tab = SegmentParam(d1, d00), tac = SegmentParam(d2, d11);
   const T tbc = SegmentParam(Dot(bc0, bc1, bc2, bp0, bp1, bp2), Dot(bc0, bc1, bc2, bc0, bc1, bc2));
   *u = tab, *v = T(0);
+  *feature = EdgeFeature(tab, kFeatureEdgeAB, kFeatureVertexA, kFeatureVertexB);
   T dist2 = ClosestOnTriangle(p, a, b, c, tab, T(0), q);
-  ClosestCandidate(p, a, b, c, T(0), tac, u, v, q, &dist2);
-  ClosestCandidate(p, a, b, c, T(1) - tbc, tbc, u, v, q, &dist2);
+  FeatureCandidate(p, a, b, c, T(0), tac, EdgeFeature(tac, kFeatureEdgeAC, kFeatureVertexA, kFeatureVertexC), u, v, q, &dist2, feature);
+  FeatureCandidate(p, a, b, c, T(1) - tbc, tbc, EdgeFeature(tbc, kFeatureEdgeBC, kFeatureVertexB, kFeatureVertexC), u, v, q, &dist2, feature);
   // the foot of the perpendicular, where its weights say it lies inside (false for the NaN of a triangle without area): along ab,
   // then along what is left of ac once its part along ab is taken off — of p - a, too, before the two meet in a dot product
   const T s = d1 / d00, m = d01 / d00;
   const T e0 = ac0 - m * ab0, e1 = ac1 - m * ab1, e2 = ac2 - m * ab2;
   const T r0 = ap0 - s * ab0, r1 = ap1 - s * ab1, r2 = ap2 - s * ab2;
   const T fv = Dot(r0, r1, r2, e0, e1, e2) / Dot(e0, e1, e2, e0, e1, e2), fu = s - fv * m;
-  if (fu >= T(0) && fv >= T(0) && fu + fv <= T(1)) ClosestCandidate(p, a, b, c, fu, fv, u, v, q, &dist2);
+  if (fu >= T(0) && fv >= T(0) && fu + fv <= T(1)) FeatureCandidate(p, a, b, c, fu, fv, (unsigned int)kFeatureFace, u, v, q, &dist2, feature);
   return dist2;
+}
+
+// The same without the code.
+template <typename T>
+NANORT_CLOSEST_FN T ClosestPointOnTriangle(const T p[3], const T a[3], const T b[3], const T c[3], T *u, T *v, T q[3]) {
+  unsigned int feature;
+  return ClosestFeatureOnTriangle(p, a, b, c, u, v, q, &feature);
 }
 
 // The (u, v) alone, for a caller that values them itself: ClosestOnTriangle(p, a, b, c, u, v, q) then gives the q and the dist2 of

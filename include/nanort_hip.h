@@ -223,10 +223,25 @@ typedef struct { float  p[3]; float  max_dist; } nrt_point_f32;
 typedef struct { double p[3]; double max_dist; } nrt_point_f64;
 typedef struct { float  point[3]; float  dist2; float  u, v; uint32_t prim_id; uint32_t _pad; } nrt_closest_f32;
 typedef struct { double point[3]; double dist2; double u, v; uint32_t prim_id; uint32_t _pad; } nrt_closest_f64;
+/* The answer of nrtSignedDistanceBatch* ("signed distance queries" below): a closest-point record with `feature` in the place of
+ * `_pad` — bits 0..2 the feature of the face that holds the nearest point (NRT_FEATURE_*), bit 31 set exactly when the point is
+ * inside, every other bit 0. */
+typedef struct { float  point[3]; float  dist2; float  u, v; uint32_t prim_id; uint32_t feature; } nrt_signed_f32;
+typedef struct { double point[3]; double dist2; double u, v; uint32_t prim_id; uint32_t feature; } nrt_signed_f64;
+#define NRT_FEATURE_FACE 0u      /* the face's interior */
+#define NRT_FEATURE_EDGE_AB 1u   /* an edge: between the face's first and second, first and third, second and third vertex */
+#define NRT_FEATURE_EDGE_AC 2u
+#define NRT_FEATURE_EDGE_BC 3u
+#define NRT_FEATURE_VERTEX_A 4u  /* the face's first, second, third vertex */
+#define NRT_FEATURE_VERTEX_B 5u
+#define NRT_FEATURE_VERTEX_C 6u
+#define NRT_FEATURE_MASK 7u
+#define NRT_SIGNED_INSIDE 0x80000000u
 
 #ifdef __cplusplus
 static_assert(sizeof(nrt_point_f32) == 16 && sizeof(nrt_point_f64) == 32, "closest-point query layout");
 static_assert(sizeof(nrt_closest_f32) == 32 && sizeof(nrt_closest_f64) == 56, "closest-point record layout");
+static_assert(sizeof(nrt_signed_f32) == 32 && sizeof(nrt_signed_f64) == 56, "signed distance record layout");
 static_assert(sizeof(nrt_ray_f32) == 36 && sizeof(nrt_ray_f64) == 72, "Ray layout");
 static_assert(sizeof(nrt_node_f32) == 40 && sizeof(nrt_node_f64) == 64, "BVHNode layout");
 static_assert(sizeof(nrt_hit_f32) == 16 && sizeof(nrt_hit_f64) == 32, "TriangleIntersection layout");
@@ -932,7 +947,7 @@ NRT_API nrt_status nrtMultiHitQueryBatchDevice_f64(nrt_ctx *ctx, const nrt_multi
  * aligned (points and closest_out to 16 bytes in fp32 and 8 in fp64).  NRT_ERR_PRECISION: a context of the other precision.
  * num_points == 0 is NRT_OK.
  *
- * nrtClosestPointBatch_* takes host arrays, staged through the context's grow-only buffers in pieces of 2^22 points, one host call at
+ * nrtClosestPointBatch_* takes host arrays, staged through the context's grow-only buffers in pieces of 2^20 points, one host call at
  * a time.  nrtClosestPointBatchDevice_* takes device arrays and is asynchronous on `hip_stream`; it takes one of the context's launch
  * slots and closes it with an event, so nrtSetMesh* / nrtBuild / nrtSetTree / nrtRefit* / nrtDestroy wait for it.
  *
@@ -945,6 +960,48 @@ NRT_API nrt_status nrtClosestPointBatchDevice_f32(nrt_ctx *ctx, const nrt_point_
                                                   nrt_closest_f32 *closest_out, uint8_t *found_out, void *hip_stream);
 NRT_API nrt_status nrtClosestPointBatchDevice_f64(nrt_ctx *ctx, const nrt_point_f64 *points, uint64_t num_points, const nrt_trace_options *options,
                                                   nrt_closest_f64 *closest_out, uint8_t *found_out, void *hip_stream);
+
+/* ---- signed distance queries ----------------------------------------------------------------------------------------------------
+ * The closest-point query above, and on which side of the surface the point lies: what a signed distance field, a voxelisation or
+ * a containment test needs.  DESIGN.md §3.18.
+ *
+ * The rule is include/nanort_sdf.h's (Baerentzen and Aanaes 2005, the angle-weighted pseudonormal).  ClosestFeatureOnTriangle is
+ * ClosestPointOnTriangle — point, dist2, u, v and prim_id are the closest-point query's, byte for byte — and also says which of
+ * its candidates won: the face's interior, one of its edges, one of its vertices (an edge candidate clamped to an end is that
+ * vertex).  The point is inside exactly when (p - point) . n < 0 for the pseudonormal n of that feature: the face's unit normal; at
+ * an edge the sum of the unit normals of all faces that hold both of its vertex indices; at a vertex the sum over its corners of
+ * corner angle times unit normal.  Outside is the side from which a face's vertices run counter-clockwise.  A zero or NaN product —
+ * a point on the surface, a zero normal — is "not inside".  The squared distance stays unsigned: sign it by bit 31 of `feature`.
+ *
+ * The normals are derived on the GPU from the mesh where it lies, by the first signed query (or nrtGetFeatureNormals_*) after any
+ * nrtSetMesh* or nrtRefit*: nothing is downloaded, and the same mesh gives the same bytes on every run (no floating-point atomics).
+ * They belong to the mesh, not to the tree: nrtBuild, nrtSetTree, nrtSetPrimMasks* and nrtSetMeshMotion* leave them alone, and
+ * prim_ids_range and skip_prim_id restrict the faces SEARCHED as before while the normals are always those of the WHOLE mesh (an
+ * edge normal still sums faces the options exclude).  Vertices are identified by index, not by position: an unwelded mesh has
+ * only boundary edges, and its signs are those of the face normals.  A context with a motion keyframe answers for keyframe 0.
+ *
+ * Not found: the closest-point query's record, feature = 0.  Runs nrt::k_signed_distance<T, 32> (nrtLastKernelName).
+ *
+ * Arguments, entry checks, refusals (each writes nothing), staging, launch slots and events are nrtClosestPointBatch*'s; one more
+ * refusal, NRT_ERR_INVALID: a mesh of more than floor((2^32 - 1) / 3) faces.
+ *
+ * nrtGetFeatureNormals_*: face_normals_out [num_faces][4][3] (the unit normal, then the edge normals of ab, ac, bc) and
+ * vertex_normals_out [num_verts][3] (num_verts: the mesh's largest vertex index + 1), refreshed first if stale, to HOST arrays;
+ * either pointer may be NULL.  Needs a triangle mesh, not a tree.  For shading with the normals, and for the tests.
+ *
+ * The sign is guaranteed on closed, consistently oriented meshes without zero-area faces.  Elsewhere — open boundaries, zero-area
+ * faces, non-manifold edges — it is what the rule gives: byte-reproducible, not guaranteed to be meaningful.
+ * Not covered: scenes, the sphere, cylinder and curve kinds, welding by position. */
+NRT_API nrt_status nrtSignedDistanceBatch_f32(nrt_ctx *ctx, const nrt_point_f32 *points, uint64_t num_points, const nrt_trace_options *options,
+                                              nrt_signed_f32 *signed_out, uint8_t *found_out);
+NRT_API nrt_status nrtSignedDistanceBatch_f64(nrt_ctx *ctx, const nrt_point_f64 *points, uint64_t num_points, const nrt_trace_options *options,
+                                              nrt_signed_f64 *signed_out, uint8_t *found_out);
+NRT_API nrt_status nrtSignedDistanceBatchDevice_f32(nrt_ctx *ctx, const nrt_point_f32 *points, uint64_t num_points, const nrt_trace_options *options,
+                                                    nrt_signed_f32 *signed_out, uint8_t *found_out, void *hip_stream);
+NRT_API nrt_status nrtSignedDistanceBatchDevice_f64(nrt_ctx *ctx, const nrt_point_f64 *points, uint64_t num_points, const nrt_trace_options *options,
+                                                    nrt_signed_f64 *signed_out, uint8_t *found_out, void *hip_stream);
+NRT_API nrt_status nrtGetFeatureNormals_f32(nrt_ctx *ctx, float *face_normals_out /* [num_faces][4][3] */, float *vertex_normals_out /* [num_verts][3] */);
+NRT_API nrt_status nrtGetFeatureNormals_f64(nrt_ctx *ctx, double *face_normals_out /* [num_faces][4][3] */, double *vertex_normals_out /* [num_verts][3] */);
 
 /* One HOST batch spread over several contexts — typically one per GPU of the node (nrtDeviceCount), each holding the same
  * tree: nrtBuild is deterministic, so building the same mesh on every context gives bit-identical replicas (or nrtSetTree the

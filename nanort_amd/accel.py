@@ -617,7 +617,42 @@ class BVHAccel:
         """The nearest face of the mesh to each point and where on it (nrtClosestPointBatch; the rule: include/nanort_closest.h).
         `points`: [n, 3] coordinates with `max_dist` a scalar or one value per point, or a wire.point_dtype record array (then
         `max_dist` is not read).  Returns (records, found): wire.closest_dtype records and a uint8 per point."""
-        from .wire import closest_dtype, point_dtype
+        from .wire import closest_dtype
+
+        return self._point_query("nrtClosestPointBatch_", closest_dtype(self.real), points, max_dist, options)
+
+    def ClosestPointBatchDevice(self, d_points, d_out, d_found=None, options=None, stream=None):
+        """Same on HBM-resident torch tensors of raw records (wire.point_dtype in, wire.closest_dtype out, a byte per point in
+        `d_found`), asynchronous on `stream` (default: torch's current stream).  Returns the number of points."""
+        return self._point_query_device("nrtClosestPointBatchDevice_", d_points, d_out, d_found, options, stream)
+
+    # -- signed distance ----------------------------------------------------
+    def SignedDistanceBatch(self, points, max_dist=np.inf, options=None):
+        """ClosestPointBatch, and on which side of the surface each point lies (nrtSignedDistanceBatch; the rule:
+        include/nanort_sdf.h, angle-weighted pseudonormals).  Returns (records, found): wire.signed_dtype records — `feature` holds
+        the feature of the face that holds the nearest point in bits 0..2 and wire.SIGNED_INSIDE when the point is inside."""
+        from .wire import signed_dtype
+
+        return self._point_query("nrtSignedDistanceBatch_", signed_dtype(self.real), points, max_dist, options)
+
+    def SignedDistanceBatchDevice(self, d_points, d_out, d_found=None, options=None, stream=None):
+        """Same on HBM-resident torch tensors of raw records (wire.point_dtype in, wire.signed_dtype out), asynchronous on `stream`."""
+        return self._point_query_device("nrtSignedDistanceBatchDevice_", d_points, d_out, d_found, options, stream)
+
+    def FeatureNormals(self):
+        """The pseudonormals of the triangle mesh as the library derived them on the GPU (nrtGetFeatureNormals): (face_normals
+        [num_faces, 4, 3] — the unit normal and the edge normals of ab, ac, bc — and vertex_normals [num_verts, 3])."""
+        m = self._mesh
+        nv = self._refit_rows()
+        if nv is None:
+            raise ValueError("FeatureNormals: no triangle mesh is set")
+        fn = np.zeros((int(m.num_faces), 4, 3), dtype=self.real)
+        vn = np.zeros((int(nv), 3), dtype=self.real)
+        self._check(getattr(self._L, "nrtGetFeatureNormals_" + self._s)(self._h, _p(fn), _p(vn)))
+        return fn, vn
+
+    def _point_query(self, fn, record_dtype, points, max_dist, options):
+        from .wire import point_dtype
 
         pd = point_dtype(self.real)
         if isinstance(points, np.ndarray) and points.dtype == pd:
@@ -628,27 +663,25 @@ class BVHAccel:
             pts["p"] = xyz
             pts["max_dist"] = np.asarray(max_dist, dtype=self.real)
         n = pts.shape[0]
-        out = np.zeros((n,), dtype=closest_dtype(self.real))
+        out = np.zeros((n,), dtype=record_dtype)
         found = np.zeros((n,), dtype=np.uint8)
         options = _opts(options)
-        self._check(getattr(self._L, "nrtClosestPointBatch_" + self._s)(self._h, _p(pts), n, _p(options), _p(out), _p(found)))
+        self._check(getattr(self._L, fn + self._s)(self._h, _p(pts), n, _p(options), _p(out), _p(found)))
         return out, found
 
-    def ClosestPointBatchDevice(self, d_points, d_out, d_found=None, options=None, stream=None):
-        """Same on HBM-resident torch tensors of raw records (wire.point_dtype in, wire.closest_dtype out, a byte per point in
-        `d_found`), asynchronous on `stream` (default: torch's current stream).  Returns the number of points."""
+    def _point_query_device(self, fn, d_points, d_out, d_found, options, stream):
         from .wire import closest_dtype, point_dtype
 
         for t, what in ((d_points, "d_points"), (d_out, "d_out"), (d_found, "d_found")):
             if t is not None:
                 self._on_device(t, what)
         n = d_points.numel() * d_points.element_size() // point_dtype(self.real).itemsize
-        if d_out.numel() * d_out.element_size() < n * closest_dtype(self.real).itemsize:
+        if d_out.numel() * d_out.element_size() < n * closest_dtype(self.real).itemsize:  # (both record kinds have this size)
             raise ValueError("d_out holds fewer records than d_points holds points")
         if d_found is not None and d_found.numel() * d_found.element_size() < n:
             raise ValueError("d_found holds fewer bytes than d_points holds points")
         options = _opts(options)
-        self._check(getattr(self._L, "nrtClosestPointBatchDevice_" + self._s)(
+        self._check(getattr(self._L, fn + self._s)(
             self._h, d_points.data_ptr(), n, _p(options), d_out.data_ptr(), None if d_found is None else d_found.data_ptr(),
             self._stream_handle(stream)))
         return n

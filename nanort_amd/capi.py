@@ -165,6 +165,10 @@ SIGNATURES = [
     # closest-point queries: ctx, points, num_points, options, closest_out, found_out[, stream]
     ("nrtClosestPointBatch", _BOTH, _Q + [vp, vp], i32),
     ("nrtClosestPointBatchDevice", _BOTH, _Q + [vp, vp, vp], i32),
+    # signed distance queries: the same arguments; the mesh's pseudonormals: ctx, face_normals_out, vertex_normals_out
+    ("nrtSignedDistanceBatch", _BOTH, _Q + [vp, vp], i32),
+    ("nrtSignedDistanceBatchDevice", _BOTH, _Q + [vp, vp, vp], i32),
+    ("nrtGetFeatureNormals", _BOTH, [vp, vp, vp], i32),
     ("nrtTraverseBatchMulti", _BOTH, [vp, u32, vp, u64, u64, vp, vp, vp], i32),
     ("nrtDeviceCount", None, [], i32),
     ("nrtTraverseCountDevice", _BOTH, _Q + [P(TraceCounters)], i32),

@@ -408,13 +408,52 @@ static nrt_status traverse_device(nrt_ctx *c, TraverseLaunch<T> l) {
   return enqueue_launch(c, l, w, slot, a, g.grid);
 }
 
+// The pseudonormals of the signed distance query (sdf.hip): derived again from d_verts / d_faces whenever a mesh setter or a refit
+// said that they no longer are the mesh's (ctx.h, feature_normals_stale).  As refresh_leaf_masks: under launch_mutex, a Device refit
+// in flight (it rewrites d_verts) waited for first, on the context's own stream, and the host waits for the kernels — launches on
+// every stream may read the buffers once this returns.  No launch reads them meanwhile: whoever set the flag waited for the
+// launches in flight first.  More than floor((2^32 - 1) / 3) faces are refused: a corner id has 32 bits.
+template <typename T>
+static nrt_status refresh_feature_normals(nrt_ctx *c, const char *fn) {
+  if (!c->feature_normals_stale) return NRT_OK;
+  if (c->num_faces > 0xFFFFFFFFu / 3u) return fail(c, NRT_ERR_INVALID, "%s: more than %u faces: a corner id 3 * face + k has 32 bits", fn, 0xFFFFFFFFu / 3u);
+  HIPCHK(c, refit_host_wait_locked(c));
+  nrt_status st;
+  if ((st = ensure(c, c->b_face_normals, std::max<size_t>(1, c->num_faces) * 12 * sizeof(T))) ||
+      (st = ensure(c, c->b_vertex_normals, std::max<size_t>(1, c->num_verts) * 3 * sizeof(T))) ||
+      (st = ensure(c, c->b_sdf_ws, std::max<size_t>(1, feature_normals_workspace_bytes<T>(c->num_faces, c->num_verts)))))
+    return st;
+  HIPCHK(c, launch_feature_normals<T>((const T *)c->d_verts, c->d_faces, c->num_faces, c->num_verts, c->b_sdf_ws.p, (T *)c->b_face_normals.p,
+                                      (T *)c->b_vertex_normals.p, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->feature_normals_stale = false;
+  return NRT_OK;
+}
+
+// nrtGetFeatureNormals_*: the normals (refreshed if stale) to the host.  Either pointer may be NULL.  Needs a triangle mesh, not a tree.
+template <typename T>
+static nrt_status get_feature_normals(nrt_ctx *c, T *face_normals, T *vertex_normals) {
+  const char *fn = "nrtGetFeatureNormals";
+  if (!c) return NRT_ERR_INVALID;
+  std::lock_guard<std::mutex> lock(c->launch_mutex);
+  if (c->prec != (int)sizeof(T)) return fail(c, NRT_ERR_PRECISION, "%s: precision mismatch", fn);
+  if (c->prim_kind != kPrimTriangles) return fail(c, NRT_ERR_INVALID, "%s: triangle contexts only (this context holds %s)", fn, kPrimKinds[c->prim_kind].name);
+  if (!c->d_verts || !c->d_faces) return fail(c, NRT_ERR_INVALID, "%s: no mesh (call nrtSetMesh)", fn);
+  HIPCHK(c, hipSetDevice(c->device));
+  if (nrt_status st = refresh_feature_normals<T>(c, fn)) return st;
+  if (face_normals) HIPCHK(c, hipMemcpy(face_normals, c->b_face_normals.p, (size_t)c->num_faces * 12 * sizeof(T), hipMemcpyDeviceToHost));
+  if (vertex_normals) HIPCHK(c, hipMemcpy(vertex_normals, c->b_vertex_normals.p, (size_t)c->num_verts * 3 * sizeof(T), hipMemcpyDeviceToHost));
+  return NRT_OK;
+}
+
 // The closest-point query (closest.hip, k_closest_point) takes the path of a ray launch — launch_mutex from the checks to the slot's
 // event, a launch slot for its cursors and its overflow stack, the persistent grid and the claim plan of launch_plan.h — with points
 // in the place of rays: `points`, `out` and `found` are device arrays, `s` the stream the launch is enqueued on.  It publishes no
 // completion record: the slot is closed by its event, which is what a rebuild or a refit waits for (wait_for_launches).
+// `is_signed`: the signed distance query (k_signed_distance) — the same checks, slot and events, the pseudonormals refreshed first.
 template <typename T>
 static nrt_status closest_device(nrt_ctx *c, const char *fn, const void *points, uint64_t n, const nrt_trace_options *opt, void *out, uint8_t *found,
-                                 bool device, hipStream_t s) {
+                                 bool device, hipStream_t s, bool is_signed = false) {
   if (!c) return NRT_ERR_INVALID;
   if (!opt) opt = &kDefaultTrace;
   std::lock_guard<std::mutex> lock(c->launch_mutex);
@@ -422,10 +461,13 @@ static nrt_status closest_device(nrt_ctx *c, const char *fn, const void *points,
   if (st || n == 0) return st;
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, refit_stream_wait(c, s)); // (a Device refit in flight on another stream)
+  if (is_signed && (st = refresh_feature_normals<T>(c, fn))) return st;
   nrt_ctx::LaunchSlot *slot = nullptr;
   if ((st = take_slot(c, s, &slot))) return st;
   if (c->closest_blocks_per_cu == 0) c->closest_blocks_per_cu = (unsigned)closest_point_blocks_per_cu<T>();
-  const unsigned per_cu = c->max_blocks_per_cu && c->closest_blocks_per_cu > c->max_blocks_per_cu ? c->max_blocks_per_cu : c->closest_blocks_per_cu;
+  if (is_signed && c->signed_blocks_per_cu == 0) c->signed_blocks_per_cu = (unsigned)signed_distance_blocks_per_cu<T>();
+  const unsigned resident = is_signed ? c->signed_blocks_per_cu : c->closest_blocks_per_cu;
+  const unsigned per_cu = c->max_blocks_per_cu && resident > c->max_blocks_per_cu ? c->max_blocks_per_cu : resident;
   const GridPlan g = plan_grid(n, kTraverseBlock, (uint32_t)c->num_cus, per_cu, c->num_parts);
   const uint32_t total_threads = g.grid * kTraverseBlock, total_waves = g.grid * (kTraverseBlock / kWave);
   const DistributionPlan d = plan_distribution((uint32_t)n, total_waves, g.parts, c->static_pct, c->static_bands, c->static_slice_groups, c->chunk);
@@ -450,7 +492,12 @@ static nrt_status closest_device(nrt_ctx *c, const char *fn, const void *points,
   a.counters = nullptr;
 #endif
   HIPCHK(c, hipEventRecord(slot->t0, s));
-  HIPCHK(c, launch_closest_point<T>(a, points, out, found, g.grid, s, &c->last_kernel));
+  if (is_signed) {
+    const SignedInputs<T> in = {(const T *)c->b_face_normals.p, (const T *)c->b_vertex_normals.p, c->d_faces, c->num_faces, c->num_verts};
+    HIPCHK(c, launch_signed_distance<T>(a, in, points, out, found, g.grid, s, &c->last_kernel));
+  } else {
+    HIPCHK(c, launch_closest_point<T>(a, points, out, found, g.grid, s, &c->last_kernel));
+  }
   // (the kernel is enqueued: the slot's state follows it now, as in enqueue_launch)
   slot->last_has_rec = false;
   slot->last_timed = false;
@@ -470,10 +517,10 @@ const uint64_t kClosestPiece = 1ull << 20; // points per launch of the staged ho
 // points — the piece up into st_rays, the launch over the staging buffers, its records and bytes of st_hits / st_mask back.
 template <typename T>
 static nrt_status closest_host(nrt_ctx *c, const typename ClosestWire<T>::Point *points, uint64_t n, const nrt_trace_options *opt,
-                               typename ClosestWire<T>::Record *out, uint8_t *found) {
+                               typename ClosestWire<T>::Record *out, uint8_t *found, bool is_signed = false) {
   typedef typename ClosestWire<T>::Point Point;
   typedef typename ClosestWire<T>::Record Record;
-  const char *fn = "nrtClosestPointBatch";
+  const char *fn = is_signed ? "nrtSignedDistanceBatch" : "nrtClosestPointBatch";
   if (!c) return NRT_ERR_INVALID;
   {
     std::lock_guard<std::mutex> lock(c->launch_mutex);
@@ -487,7 +534,7 @@ static nrt_status closest_host(nrt_ctx *c, const typename ClosestWire<T>::Point 
     nrt_status st;
     if ((st = ensure(c, c->st_rays, m * sizeof(Point))) || (st = ensure(c, c->st_hits, m * sizeof(Record))) || (st = ensure(c, c->st_mask, m))) return st;
     HIPCHK(c, hipMemcpyAsync(c->st_rays.p, points + off, m * sizeof(Point), hipMemcpyHostToDevice, c->stream));
-    if ((st = closest_device<T>(c, fn, c->st_rays.p, m, opt, c->st_hits.p, (uint8_t *)c->st_mask.p, false, c->stream))) {
+    if ((st = closest_device<T>(c, fn, c->st_rays.p, m, opt, c->st_hits.p, (uint8_t *)c->st_mask.p, false, c->stream, is_signed))) {
       (void)hipStreamSynchronize(c->stream);
       return st;
     }
@@ -1255,3 +1302,24 @@ nrt_status nrtTraverseCountDevice_f64(nrt_ctx *c, const nrt_ray_f64 *r, uint64_t
 }
 
 } // extern "C"
+
+// Signed distance queries (include/nanort_hip.h): the closest-point query with the side of the surface; the records share the layout.
+static_assert(sizeof(nrt_signed_f32) == sizeof(nrt_closest_f32) && sizeof(nrt_signed_f64) == sizeof(nrt_closest_f64) &&
+                  offsetof(nrt_signed_f32, feature) == offsetof(nrt_closest_f32, _pad) && offsetof(nrt_signed_f64, feature) == offsetof(nrt_closest_f64, _pad),
+              "a signed record is a closest-point record with `feature` in the place of `_pad`");
+nrt_status nrtSignedDistanceBatch_f32(nrt_ctx *c, const nrt_point_f32 *p, uint64_t n, const nrt_trace_options *o, nrt_signed_f32 *out, uint8_t *f) {
+  return closest_host<float>(c, p, n, o, (nrt_closest_f32 *)out, f, true);
+}
+nrt_status nrtSignedDistanceBatch_f64(nrt_ctx *c, const nrt_point_f64 *p, uint64_t n, const nrt_trace_options *o, nrt_signed_f64 *out, uint8_t *f) {
+  return closest_host<double>(c, p, n, o, (nrt_closest_f64 *)out, f, true);
+}
+nrt_status nrtSignedDistanceBatchDevice_f32(nrt_ctx *c, const nrt_point_f32 *p, uint64_t n, const nrt_trace_options *o, nrt_signed_f32 *out, uint8_t *f,
+                                            void *s) {
+  return closest_device<float>(c, "nrtSignedDistanceBatchDevice", p, n, o, out, f, true, (hipStream_t)s, true);
+}
+nrt_status nrtSignedDistanceBatchDevice_f64(nrt_ctx *c, const nrt_point_f64 *p, uint64_t n, const nrt_trace_options *o, nrt_signed_f64 *out, uint8_t *f,
+                                            void *s) {
+  return closest_device<double>(c, "nrtSignedDistanceBatchDevice", p, n, o, out, f, true, (hipStream_t)s, true);
+}
+nrt_status nrtGetFeatureNormals_f32(nrt_ctx *c, float *fn, float *vn) { return get_feature_normals<float>(c, fn, vn); }
+nrt_status nrtGetFeatureNormals_f64(nrt_ctx *c, double *fn, double *vn) { return get_feature_normals<double>(c, fn, vn); }

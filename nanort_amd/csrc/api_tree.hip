@@ -298,6 +298,7 @@ static nrt_status refit(nrt_ctx *c, const T *vertices, size_t stride, bool devic
   if ((st = refit_plan<T>(c, s))) return st;
   // From here on the vertices, the boxes and the leaf / wide records are being rewritten: a device error leaves no half-refit
   // tree behind — the context drops its tree and its primitives (free_tree bumps generation), as a failed build drops its tree.
+  c->feature_normals_stale = true; // (the vertices move: the pseudonormals of the signed distance query are the old mesh's)
   const hipError_t e = launch_refit<T>(src, stride, nv, (T *)c->d_verts, c->d_faces, c->d_indices,
                                        (typename Wire<T>::Node *)c->d_nodes, c->num_nodes, c->num_branch_records, c->tree_depth,
                                        (const uint32_t *)c->b_refit_plan.p, s);

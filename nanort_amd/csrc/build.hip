@@ -414,6 +414,22 @@ __global__ __launch_bounds__(256) void k_radix_scatter(const uint32_t *__restric
   }
 }
 
+// The four passes over 32-bit keys (kernels.h): the sorted pairs are back in keys[0] / vals[0]; keys[1] / vals[1] are scratch of the
+// same size and block_hist holds 256 * sort_pairs_blocks(n) words.
+size_t sort_pairs_blocks(uint32_t n) { return ((size_t)n + kSortTile - 1) / kSortTile; }
+hipError_t launch_sort_pairs(uint32_t *const keys[2], uint32_t *const vals[2], uint32_t *block_hist, uint32_t n, hipStream_t s) {
+  const unsigned nb = (unsigned)sort_pairs_blocks(n);
+  if (n == 0) return hipSuccess;
+  int pp = 0;
+  for (int shift = 0; shift < 32; shift += 8) {
+    hipLaunchKernelGGL(k_radix_hist, dim3(nb), dim3(256), 0, s, keys[pp], n, shift, block_hist, nb);
+    hipLaunchKernelGGL(k_radix_scan, dim3(1), dim3(1024), 0, s, block_hist, 256u * nb);
+    hipLaunchKernelGGL(k_radix_scatter, dim3(nb), dim3(256), 0, s, keys[pp], vals[pp], keys[1 - pp], vals[1 - pp], n, shift, block_hist, nb);
+    pp = 1 - pp;
+  }
+  return hipGetLastError();
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void k_gather_records(const PrimRec<T> *__restrict__ in,
                                                         const uint32_t *__restrict__ order, uint32_t n,
@@ -1385,7 +1401,7 @@ struct BuildPlan { // carve-up of the build workspace for n primitives
     off_scene = take((1 + kSceneReplicas) * sizeof(BoundsAcc<T>));
     off_info = take(sizeof(LevelInfo));
     // Morton sort: keys/values ping-pong (4 x n u32) + digit-major block histograms
-    sort_blocks = ((size_t)n + kSortTile - 1) / kSortTile;
+    sort_blocks = sort_pairs_blocks(n);
     off_sort = take((4 * (size_t)n + 256 * sort_blocks) * sizeof(uint32_t));
     total = o;
   }
@@ -1461,17 +1477,10 @@ hipError_t gpu_build(hipStream_t s, const T *d_verts, const T *d_verts1, const u
       uint32_t *keys[2] = {(uint32_t *)(base + plan.off_sort), (uint32_t *)(base + plan.off_sort) + (size_t)n};
       uint32_t *vals[2] = {keys[1] + (size_t)n, keys[1] + 2 * (size_t)n};
       uint32_t *block_hist = keys[1] + 3 * (size_t)n;
-      const unsigned nb = (unsigned)plan.sort_blocks;
       hipLaunchKernelGGL((k_combine_scene<T>), dim3(1), dim3(64), 0, s, scene);
       hipLaunchKernelGGL((k_morton_keys<T>), dim3((n + 255) / 256), dim3(256), 0, s, recs[0], n, scene, keys[0], vals[0]);
-      int pp = 0;
-      for (int shift = 0; shift < 32; shift += 8) {
-        hipLaunchKernelGGL(k_radix_hist, dim3(nb), dim3(256), 0, s, keys[pp], n, shift, block_hist, nb);
-        hipLaunchKernelGGL(k_radix_scan, dim3(1), dim3(1024), 0, s, block_hist, 256u * nb);
-        hipLaunchKernelGGL(k_radix_scatter, dim3(nb), dim3(256), 0, s, keys[pp], vals[pp], keys[1 - pp], vals[1 - pp], n,
-                           shift, block_hist, nb);
-        pp = 1 - pp;
-      }
+      (void)launch_sort_pairs(keys, vals, block_hist, n, s); // (gpu_build's own hipGetLastError() follows)
+      const int pp = 0;
       hipLaunchKernelGGL((k_gather_records<T>), dim3((n + 255) / 256), dim3(256), 0, s, recs[0], vals[pp], n, recs[1]);
       cur = 1;
     }

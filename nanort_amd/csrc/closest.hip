@@ -18,11 +18,16 @@
 //     trace options are honoured as tri_solve honours them; cull_back_face means nothing here.
 //   * A point that is not Searchable (a non-finite coordinate, a NaN or negative max_dist) takes its not-found record at the refill
 //     and walks nothing.
+// closest_walk<T, STACK, SIGNED> states that walk once, for two kernels.  k_signed_distance<T, STACK> (SIGNED; nrtSignedDistanceBatch*,
+// DESIGN.md §3.18) carries the winning candidate's feature code of the best face beside its prim_id (ClosestFeatureOnTriangle) and,
+// when a lane finishes a FOUND query, fetches one pseudonormal — the face's record [4][3] for features 0..3, the vertex normal of
+// faces[3 * prim + feature - 4] for 4..6 — and sets bit 31 of the record's last word where nanort_sdf::Inside says so: once per
+// query, not per face; the cull, the order and the tie-break are the unsigned walk's.
 // No inline assembly; plain loads and stores, the records in 16-byte (fp32) and 8-byte (fp64) pieces.
 // The profiling library (-DNRT_PROF) counts nodes opened and triangles tested into a.counters[0] / [2] (tools/closest_probe.py).
 #include "traverse_dev.h"
 #include "kernels.h"
-#include "../../include/nanort_closest.h"
+#include "../../include/nanort_sdf.h" // (includes nanort_closest.h)
 
 namespace nrt {
 
@@ -42,15 +47,22 @@ struct ClosestLane {
   T q0, q1, q2, u, v;
   uint32_t prim;
 };
+// ... and, in the signed walk, the feature code of that answer.
+template <bool SIGNED>
+struct FeatureLane {};
+template <>
+struct FeatureLane<true> {
+  uint32_t feature;
+};
 
 template <typename T>
-__device__ __forceinline__ void store_closest_record(const ClosestArgs<T> &m, const ClosestLane<T> &L, uint32_t rid) {
+__device__ __forceinline__ void store_closest_record(const ClosestArgs<T> &m, const ClosestLane<T> &L, uint32_t rid, uint32_t last_word = 0u) {
   typename ClosestWire<T>::Record r;
   r.point[0] = L.q0, r.point[1] = L.q1, r.point[2] = L.q2;
   r.dist2 = L.best;
   r.u = L.u, r.v = L.v;
   r.prim_id = L.prim;
-  r._pad = 0u;
+  r._pad = last_word; // (the signed record's `feature`)
   typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
   typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
   if constexpr (sizeof(T) == 4) { // 32-byte records of a 16-byte aligned array
@@ -67,11 +79,26 @@ __device__ __forceinline__ void store_closest_record(const ClosestArgs<T> &m, co
   if (m.found) m.found[rid] = L.prim != kInvalid ? 1 : 0;
 }
 
-template <typename T, int STACK>
-__global__ __launch_bounds__(kTraverseBlock) void k_closest_point(const ClosestArgs<T> m) {
+// The `feature` word of a finished signed query: the code, and bit 31 when the point is inside (0 when nothing was found).
+template <typename T>
+__device__ __forceinline__ uint32_t signed_word(const SignedInputs<T> &in, const ClosestLane<T> &L, uint32_t feature) {
+  if (L.prim == kInvalid || L.prim >= in.num_faces) return 0u;
+  const T *n = in.face_normals + 12 * (size_t)L.prim + 3u * feature;
+  if (feature >= nanort_sdf::kFeatureVertexA) {
+    const uint32_t vtx = in.faces[3 * (size_t)L.prim + (feature - nanort_sdf::kFeatureVertexA)];
+    if (vtx >= in.num_verts) return feature;
+    n = in.vertex_normals + 3 * (size_t)vtx;
+  }
+  const T p[3] = {L.p0, L.p1, L.p2}, q[3] = {L.q0, L.q1, L.q2}, nn[3] = {n[0], n[1], n[2]};
+  return nanort_sdf::FeatureWord<T>(p, q, nn, feature);
+}
+
+template <typename T, int STACK, bool SIGNED>
+// (the arguments BY VALUE: by reference the unsigned kernel came out at 96 / 125 VGPRs instead of 82 / 122)
+__device__ __forceinline__ void closest_walk(const ClosestArgs<T> m, const SignedInputs<T> sn) {
+  __shared__ uint32_t s_stack[STACK][kTraverseBlock]; // (one per kernel: the walk is inlined into each)
   typedef typename Wire<T>::Node Node;
   typedef typename ClosestWire<T>::Point Point;
-  __shared__ uint32_t s_stack[STACK][kTraverseBlock];
   const TraverseArgs<T> &a = m.a;
 
   const unsigned tid = threadIdx.x;
@@ -79,6 +106,7 @@ __global__ __launch_bounds__(kTraverseBlock) void k_closest_point(const ClosestA
   const LaneStack<StackRef, STACK, TraverseArgs<T>> stk = {a, tid, blockIdx.x * kTraverseBlock + tid};
 
   ClosestLane<T> L;
+  FeatureLane<SIGNED> F;
   uint32_t rid = kInvalid;
   uint32_t cur = 0;
   uint32_t leaf_first = 0, leaf_cnt = 0;
@@ -94,10 +122,15 @@ __global__ __launch_bounds__(kTraverseBlock) void k_closest_point(const ClosestA
 
   // Pop the next node, or finish the query when the stack is empty (select-style updates, as binary_walk's).  The popped node's box
   // is tested when the node is opened, against the best of that moment.
+#define NRT_CLOSEST_STORE()                                                         \
+  do {                                                                              \
+    if constexpr (SIGNED) store_closest_record<T>(m, L, rid, signed_word<T>(sn, L, F.feature)); \
+    else store_closest_record<T>(m, L, rid);                                        \
+  } while (0)
 #define NRT_CLOSEST_POP_OR_FINISH()               \
   do {                                            \
     const bool fin_ = sp == 0;                    \
-    if (fin_) store_closest_record<T>(m, L, rid); \
+    if (fin_) NRT_CLOSEST_STORE();                \
     if (!fin_) stk.load(s_stack, sp - 1, cur);    \
     sp = fin_ ? 0 : sp - 1;                       \
     rid = fin_ ? kInvalid : rid;                  \
@@ -123,12 +156,13 @@ __global__ __launch_bounds__(kTraverseBlock) void k_closest_point(const ClosestA
           L.q0 = p[0], L.q1 = p[1], L.q2 = p[2];
           L.u = T(0), L.v = T(0);
           L.prim = kInvalid;
+          if constexpr (SIGNED) F.feature = 0u;
           if (nanort_closest::Searchable<T>(p, pt.max_dist)) {
             cur = 0;
             sp = 0;
             state = LANE_TRAV;
           } else { // finds nothing and walks nothing: the lane stays idle and takes another point
-            store_closest_record<T>(m, L, rid);
+            NRT_CLOSEST_STORE();
             rid = kInvalid;
           }
         }
@@ -187,7 +221,10 @@ __global__ __launch_bounds__(kTraverseBlock) void k_closest_point(const ClosestA
           if ((prim >= a.range0) & (prim < a.range1) & (prim != a.skip_prim)) { // (as tri_solve: nanort.h:2387-2395)
             const T p[3] = {L.p0, L.p1, L.p2};
             T u, v, q[3];
-            const T dist2 = nanort_closest::ClosestPointOnTriangle<T>(p, tri.p0, tri.p1, tri.p2, &u, &v, q);
+            uint32_t feature = 0u;
+            T dist2;
+            if constexpr (SIGNED) dist2 = nanort_closest::ClosestFeatureOnTriangle<T>(p, tri.p0, tri.p1, tri.p2, &u, &v, q, &feature);
+            else dist2 = nanort_closest::ClosestPointOnTriangle<T>(p, tri.p0, tri.p1, tri.p2, &u, &v, q);
             const bool acc = nanort_closest::Better<T>(dist2, prim, L.best, L.prim);
             L.best = acc ? dist2 : L.best;
             L.q0 = acc ? q[0] : L.q0;
@@ -196,6 +233,7 @@ __global__ __launch_bounds__(kTraverseBlock) void k_closest_point(const ClosestA
             L.u = acc ? u : L.u;
             L.v = acc ? v : L.v;
             L.prim = acc ? prim : L.prim;
+            if constexpr (SIGNED) F.feature = acc ? feature : F.feature;
 #ifdef NRT_PROF
             n_tris++;
 #endif
@@ -206,12 +244,29 @@ __global__ __launch_bounds__(kTraverseBlock) void k_closest_point(const ClosestA
     }
   }
 #undef NRT_CLOSEST_POP_OR_FINISH
+#undef NRT_CLOSEST_STORE
 #ifdef NRT_PROF
   if (a.counters) {
     atomicAdd(a.counters + 0, n_nodes);
     atomicAdd(a.counters + 2, n_tris);
   }
 #endif
+}
+
+template <typename T, int STACK>
+__global__ __launch_bounds__(kTraverseBlock) void k_closest_point(const ClosestArgs<T> m) {
+  const SignedInputs<T> none = {};
+  closest_walk<T, STACK, false>(m, none);
+}
+
+template <typename T>
+struct SignedArgs {
+  ClosestArgs<T> m;
+  SignedInputs<T> in;
+};
+template <typename T, int STACK>
+__global__ __launch_bounds__(kTraverseBlock) void k_signed_distance(const SignedArgs<T> sa) {
+  closest_walk<T, STACK, true>(sa.m, sa.in);
 }
 
 static_assert(kLdsStackDefault == 32, "the names below carry the stack depth");
@@ -238,7 +293,28 @@ int closest_point_blocks_per_cu() {
   return resident_blocks(closest_kernel<T>(), 1);
 }
 
+template <typename T>
+hipError_t launch_signed_distance(const TraverseArgs<T> &args, const SignedInputs<T> &in, const void *points, void *out, uint8_t *found, unsigned grid,
+                                  hipStream_t s, const char **name_out) {
+  SignedArgs<T> sa;
+  sa.m.a = args;
+  sa.m.points = (const typename ClosestWire<T>::Point *)points;
+  sa.m.out = (typename ClosestWire<T>::Record *)out;
+  sa.m.found = found;
+  sa.in = in;
+  launch_persistent((const void *)k_signed_distance<T, kLdsStackDefault>, grid, sa, s);
+  if (name_out) *name_out = sizeof(T) == 4 ? "nrt::k_signed_distance<float, 32>" : "nrt::k_signed_distance<double, 32>";
+  return hipGetLastError();
+}
+
+template <typename T>
+int signed_distance_blocks_per_cu() {
+  return resident_blocks((const void *)k_signed_distance<T, kLdsStackDefault>, 1);
+}
+
 NRT_INSTANTIATE_F32_F64(launch_closest_point)
+NRT_INSTANTIATE_F32_F64(launch_signed_distance)
+NRT_INSTANTIATE_F32_F64(signed_distance_blocks_per_cu)
 NRT_INSTANTIATE_F32_F64(closest_point_blocks_per_cu)
 
 } // namespace nrt

@@ -160,6 +160,7 @@ struct nrt_ctx {
   struct { int lds_entries; unsigned blocks_per_cu; } occupancy[(int)Walk::Own + kNumOwnWalks][kNumPrimKinds] = {};
 
   unsigned closest_blocks_per_cu = 0; // ... and of k_closest_point (closest.hip; 0: not asked for yet)
+  unsigned signed_blocks_per_cu = 0;  // ... and of k_signed_distance
 
   hipEvent_t ev_b0 = nullptr, ev_b1 = nullptr;
   hipEvent_t ev_build_state = nullptr; // the builder's state block has reached build_state
@@ -184,6 +185,16 @@ struct nrt_ctx {
   DevBuf b_prim_masks, b_leaf_masks, st_ray_masks; // (st_ray_masks: per-ray words of the staged host forms, beside st_rays)
   uint32_t *d_prim_masks = nullptr; // == b_prim_masks.p while masks are set
   bool leaf_masks_stale = true;
+
+  // signed distance (nrtSignedDistanceBatch*): the pseudonormals of the triangle mesh (sdf.hip) — per face its unit
+  // normal and its three edge normals [num_faces][4][3], per vertex the angle-weighted normal [num_verts][3] — and the workspace of
+  // their derivation.  They belong to the MESH, not to the tree.  feature_normals_stale: the buffers do not hold the normals of
+  // d_verts / d_faces.  Set by the events that change the mesh — every triangle mesh setter (free_mesh: all of them pass it) and
+  // every triangle refit, host and Device forms — and not by nrtBuild, nrtSetTree, the mask setters or the second keyframe's
+  // setter; cleared by the one place that derives them, the first signed query or nrtGetFeatureNormals behind the change
+  // (api_query.hip, refresh_feature_normals).
+  DevBuf b_face_normals, b_vertex_normals, b_sdf_ws;
+  bool feature_normals_stale = true;
 };
 
 inline nrt_status fail(nrt_ctx *c, nrt_status st, const char *fmt, ...) {
@@ -308,6 +319,7 @@ inline void free_mesh(nrt_ctx *c) {
   c->d_radii = nullptr;
   c->d_verts1 = nullptr; // (the motion keyframe goes with the mesh it belongs to)
   c->d_prim_masks = nullptr; // (... and so do the visibility masks)
+  c->feature_normals_stale = true; // (... and so do the pseudonormals of the signed distance query)
   c->num_faces = c->num_verts = 0;
   c->num_segs = 0;
 }

@@ -98,6 +98,31 @@ hipError_t launch_closest_point(const TraverseArgs<T> &args, const void *points,
                                 const char **name_out);
 template <typename T>
 int closest_point_blocks_per_cu();
+// The signed form (k_signed_distance: the same walk, carrying the winning feature; include/nanort_sdf.h states the sign): the
+// records are ClosestWire<T>'s with the `feature` word in the place of `_pad`.  `face_normals`: [num_faces][4][3], `vertex_normals`:
+// [num_verts][3] (sdf.hip), `faces`: the mesh's index trios.
+template <typename T>
+struct SignedInputs {
+  const T *face_normals, *vertex_normals;
+  const uint32_t *faces;
+  uint32_t num_faces, num_verts;
+};
+template <typename T>
+hipError_t launch_signed_distance(const TraverseArgs<T> &args, const SignedInputs<T> &in, const void *points, void *out, uint8_t *found, unsigned grid,
+                                  hipStream_t s, const char **name_out);
+template <typename T>
+int signed_distance_blocks_per_cu();
+
+// ---- sdf.hip: the angle-weighted pseudonormals of a triangle mesh (include/nanort_sdf.h states them) ---------------------------------
+// The workspace of one derivation for `num_faces` faces and `num_verts` vertices, in bytes.
+template <typename T>
+size_t feature_normals_workspace_bytes(uint32_t num_faces, uint32_t num_verts);
+// face_normals[num_faces][4][3] and vertex_normals[num_verts][3] from the mesh where it lies; the same bytes on every run (no
+// floating-point atomics: the corners are sorted by vertex with build.hip's stable sort, and every sum runs in list order).
+// 3 * num_faces must fit 32 bits (the caller refuses larger meshes).
+template <typename T>
+hipError_t launch_feature_normals(const T *verts, const uint32_t *faces, uint32_t num_faces, uint32_t num_verts, void *workspace, T *face_normals,
+                                  T *vertex_normals, hipStream_t s);
 
 // ---- build.hip --------------------------------------------------------------------------------------------------------
 enum : unsigned { kBuildMorton = 1u, kBuildSubtreeDfs = 2u }; // gpu_build's build_flags: Morton pre-pass, one-node-per-step subtree kernel
@@ -112,6 +137,11 @@ hipError_t gpu_build(hipStream_t s, const T *d_verts, const T *d_verts1, const u
                      uint32_t num_faces, uint32_t min_leaf, uint32_t max_depth, uint32_t bin_size, unsigned build_flags, DevBuf *workspace,
                      DevBuf *nodes_buf, DevBuf *indices_buf, void *pinned, hipEvent_t ev, std::string *err);
 hipError_t gpu_build_result(const void *pinned, hipEvent_t ev, BuildResult *res);
+// The builder's stable LSD radix sort of `n` (32-bit key, value) pairs, 8 bits a pass: sorted pairs end in keys[0] / vals[0];
+// keys[1] / vals[1]: scratch of n words each; block_hist: 256 * sort_pairs_blocks(n) words.  No atomics on the order: the same
+// output on every run.
+size_t sort_pairs_blocks(uint32_t n);
+hipError_t launch_sort_pairs(uint32_t *const keys[2], uint32_t *const vals[2], uint32_t *block_hist, uint32_t n, hipStream_t s);
 
 // ---- build_subtree.hip: the subtree phase of a build (the types are the builder's own: build_dev.h) ------------------------
 template <typename T>

@@ -95,6 +95,13 @@ POINT_F32 = np.dtype([("p", "<f4", 3), ("max_dist", "<f4")])
 POINT_F64 = np.dtype([("p", "<f8", 3), ("max_dist", "<f8")])
 CLOSEST_F32 = np.dtype([("point", "<f4", 3), ("dist2", "<f4"), ("u", "<f4"), ("v", "<f4"), ("prim_id", "<u4"), ("_pad", "<u4")])
 CLOSEST_F64 = np.dtype([("point", "<f8", 3), ("dist2", "<f8"), ("u", "<f8"), ("v", "<f8"), ("prim_id", "<u4"), ("_pad", "<u4")])
+# the answer of the signed distance queries (nrt_signed_*): a closest-point record with `feature` in the place of `_pad` — bits 0..2
+# the feature that holds the nearest point (0 face, 1 / 2 / 3 edge ab / ac / bc, 4 / 5 / 6 vertex a / b / c), bit 31 set when inside
+SIGNED_F32 = np.dtype([("point", "<f4", 3), ("dist2", "<f4"), ("u", "<f4"), ("v", "<f4"), ("prim_id", "<u4"), ("feature", "<u4")])
+SIGNED_F64 = np.dtype([("point", "<f8", 3), ("dist2", "<f8"), ("u", "<f8"), ("v", "<f8"), ("prim_id", "<u4"), ("feature", "<u4")])
+FEATURE_MASK = 7
+SIGNED_INSIDE = 0x80000000
+assert SIGNED_F32.itemsize == 32 and SIGNED_F64.itemsize == 56
 assert POINT_F32.itemsize == 16 and POINT_F64.itemsize == 32
 assert CLOSEST_F32.itemsize == 32 and CLOSEST_F64.itemsize == 56
 
@@ -107,6 +114,10 @@ def point_dtype(real):
 
 def closest_dtype(real):
     return CLOSEST_F32 if np.dtype(real) == np.float32 else CLOSEST_F64
+
+
+def signed_dtype(real):
+    return SIGNED_F32 if np.dtype(real) == np.float32 else SIGNED_F64
 
 
 def ray_dtype(real):
