@@ -1488,6 +1488,8 @@ struct HipApi;
     /* signed distance queries */                                                 \
     typedef nrt_signed_##S SignedPod;                                             \
     NANORT_HIP_ENTRY(SignedDistance, nrtSignedDistanceBatch, S)                   \
+    /* nearest-faces queries */                                                   \
+    NANORT_HIP_ENTRY(NearestFaces, nrtNearestFacesBatch, S)                       \
   };
 NANORT_HIP_API(float, f32)
 NANORT_HIP_API(double, f64)
@@ -2047,6 +2049,80 @@ class BVHAccel {
     return ClosestPointBatchHost(points, max_dists, num_points, mesh, out, found_out, options);
   }
 
+  // The `max_faces` nearest faces of `mesh` to the point `p`, in order — on the HOST, with or without NANORT_USE_HIP_BACKEND.  The
+  // rule is nanort_closest.h's K-nearest rule: the candidates are the faces `options` admits (as ClosestPoint) with dist2 <= max_dist^2,
+  // ranked by (dist2, prim_id) ascending, so the answer does not depend on the tree; the walk of nodes_ is ClosestPoint's with the
+  // bound at the worst held dist2 once max_faces are held.  out[0 .. *count) receives the found records, out[*count .. max_faces) the
+  // not-found record of ClosestPoint; `count` may be NULL.  Returns false (and writes nothing) when max_faces is 0.
+  bool NearestFaces(const T p[3], T max_dist, unsigned int max_faces, const TriangleMesh<T> &mesh, const BVHTraceOptions &options,
+                    ClosestPointResult<T> *out, unsigned int *count = NULL) const {
+    if (max_faces == 0) return false;
+    EnsureHostTree();
+    const T r2 = max_dist * max_dist;
+    unsigned int held = 0;
+    if (!nodes_.empty() && nanort_closest::Searchable<T>(p, max_dist)) {
+      std::vector<unsigned int> todo(1, 0u);  // (a vector: no depth limit)
+      while (!todo.empty()) {
+        const BVHNode<T> &node = nodes_[todo.back()];
+        todo.pop_back();
+        const T bound = nanort_closest::NearestBound<T>(held, max_faces, r2, held ? out[held - 1].dist2 : r2);
+        if (nanort_closest::Culled<T>(nanort_closest::BoxDist2<T>(p, node.bmin, node.bmax), bound)) continue;
+        if (node.flag == 0) {
+          const BVHNode<T> &n0 = nodes_[node.data[0]], &n1 = nodes_[node.data[1]];
+          const T d0 = nanort_closest::BoxDist2<T>(p, n0.bmin, n0.bmax), d1 = nanort_closest::BoxDist2<T>(p, n1.bmin, n1.bmax);
+          const bool second = d1 < d0;  // on ties the first child
+          if (!nanort_closest::Culled<T>(second ? d0 : d1, bound)) todo.push_back(node.data[second ? 0 : 1]);  // the farther child waits
+          if (!nanort_closest::Culled<T>(second ? d1 : d0, bound)) todo.push_back(node.data[second ? 1 : 0]);
+        } else {
+          for (unsigned int i = 0; i < node.data[0]; i++) {
+            const unsigned int prim = indices_[node.data[1] + i];
+            if (prim < options.prim_ids_range[0] || prim >= options.prim_ids_range[1] || prim == options.skip_prim_id) continue;
+            const T *a = get_vertex_addr<T>(mesh.vertices_, mesh.faces_[3 * prim + 0], mesh.vertex_stride_bytes_);
+            const T *b = get_vertex_addr<T>(mesh.vertices_, mesh.faces_[3 * prim + 1], mesh.vertex_stride_bytes_);
+            const T *c = get_vertex_addr<T>(mesh.vertices_, mesh.faces_[3 * prim + 2], mesh.vertex_stride_bytes_);
+            ClosestPointResult<T> rec;
+            rec.dist2 = nanort_closest::ClosestPointOnTriangle<T>(p, a, b, c, &rec.u, &rec.v, rec.point);
+            rec.prim_id = prim;
+            rec.pad = 0u;
+            const bool full = held == max_faces;
+            if (!nanort_closest::NearestEnters<T>(rec.dist2, prim, r2, held, max_faces, full ? out[held - 1].dist2 : r2,
+                                                  full ? out[held - 1].prim_id : 0xFFFFFFFFu))
+              continue;
+            held = nanort_closest::NearestInsert(out, held, max_faces, rec);
+          }
+        }
+      }
+    }
+    for (unsigned int j = held; j < max_faces; j++) {
+      out[j].point[0] = p[0], out[j].point[1] = p[1], out[j].point[2] = p[2];
+      out[j].dist2 = r2;
+      out[j].u = out[j].v = static_cast<T>(0.0);
+      out[j].prim_id = 0xFFFFFFFFu;
+      out[j].pad = 0u;
+    }
+    if (count) *count = held;
+    return true;
+  }
+  // ... for `num_points` points, point i at points[3 * i] with max_dists[i] (NULL: +inf for every point): N calls of NearestFaces(),
+  // row i at out[i * max_faces].  Every record is written; counts_out[i] (optional) receives the count.
+  bool NearestFacesBatchHost(const T *points, const T *max_dists, size_t num_points, unsigned int max_faces, const TriangleMesh<T> &mesh,
+                             ClosestPointResult<T> *out, unsigned int *counts_out = NULL, const BVHTraceOptions &options = BVHTraceOptions()) const {
+    if (max_faces == 0) return false;
+    for (size_t i = 0; i < num_points; i++)
+      NearestFaces(points + 3 * i, max_dists ? max_dists[i] : std::numeric_limits<T>::infinity(), max_faces, mesh, options, out + i * max_faces,
+                   counts_out ? counts_out + i : NULL);
+    return true;
+  }
+  // The batch call: with NANORT_USE_HIP_BACKEND and a triangle tree on the GPU one call of nrtNearestFacesBatch (max_faces up to
+  // NRT_MAX_NEAREST; rows byte-identical to the host loop's), the host loop otherwise.
+  bool NearestFacesBatch(const T *points, const T *max_dists, size_t num_points, unsigned int max_faces, const TriangleMesh<T> &mesh,
+                         ClosestPointResult<T> *out, unsigned int *counts_out = NULL, const BVHTraceOptions &options = BVHTraceOptions()) const {
+#ifdef NANORT_USE_HIP_BACKEND
+    if (dev_.ctx && geom_.kind == 0) return NearestFacesBatchBackend(points, max_dists, num_points, max_faces, out, counts_out, options);
+#endif
+    return NearestFacesBatchHost(points, max_dists, num_points, max_faces, mesh, out, counts_out, options);
+  }
+
 #ifdef NANORT_USE_HIP_BACKEND
   // Closest hit for each of `num_rays` rays in one GPU launch.  isects[i] is written only when
   // ray i hits (exactly like N calls of Traverse()); hit_out[i] (optional) receives 1 / 0.
@@ -2517,13 +2593,28 @@ class BVHAccel {
     std::lock_guard<std::mutex> lock(batch_mutex_);
     if (!DeviceTreeReady(0)) return false;
     if (num_points == 0) return true;
+    const std::vector<typename Api::PointPod> pts = PackPoints(points, max_dists, num_points);
+    const nrt_trace_options o = TraceOptions(options);
+    return Ok(entry(Context(), &pts[0], num_points, &o, reinterpret_cast<Pod *>(out), found_out));
+  }
+  std::vector<typename Api::PointPod> PackPoints(const T *points, const T *max_dists, size_t num_points) const {
     std::vector<typename Api::PointPod> pts(num_points);
     for (size_t i = 0; i < num_points; i++) {
       for (int k = 0; k < 3; k++) pts[i].p[k] = points[3 * i + k];
       pts[i].max_dist = max_dists ? max_dists[i] : std::numeric_limits<T>::infinity();
     }
+    return pts;
+  }
+  // ... and of NearestFacesBatch(): max_faces records and one count per point.
+  bool NearestFacesBatchBackend(const T *points, const T *max_dists, size_t num_points, unsigned int max_faces, ClosestPointResult<T> *out,
+                                unsigned int *counts_out, const BVHTraceOptions &options) const {
+    static_assert(sizeof(ClosestPointResult<T>) == sizeof(typename Api::ClosestPod) && sizeof(unsigned int) == sizeof(uint32_t), "point query record layout");
+    std::lock_guard<std::mutex> lock(batch_mutex_);
+    if (!DeviceTreeReady(0)) return false;
+    const std::vector<typename Api::PointPod> pts = PackPoints(points, max_dists, num_points);
     const nrt_trace_options o = TraceOptions(options);
-    return Ok(entry(Context(), &pts[0], num_points, &o, reinterpret_cast<Pod *>(out), found_out));
+    return Ok(Api::NearestFaces(Context(), num_points ? &pts[0] : NULL, num_points, max_faces, &o, reinterpret_cast<typename Api::ClosestPod *>(out),
+                                counts_out));
   }
   bool ClosestPointBatchBackend(const T *points, const T *max_dists, size_t num_points, ClosestPointResult<T> *out, unsigned char *found_out,
                                 const BVHTraceOptions &options) const {

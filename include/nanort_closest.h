@@ -51,7 +51,10 @@
 // (Searchable).  A minimum with a total tie-break: it does not depend on the tree.  A subtree is skipped iff BoxDist2 > best,
 // strictly, where best starts at r2 (Culled): a box at exactly best is entered, because the tie-break may prefer a face inside it.
 //
-// Included by the device kernel (nanort_amd/csrc/closest.hip), by the host classes of nanort.h and by the CPU model of the tests.
+// The K nearest faces in the place of the nearest one: the K-nearest rule at the end of the file (NearestBound, NearestEnters).
+//
+// Included by the device kernels (nanort_amd/csrc/closest.hip, nearest.hip), by the host classes of nanort.h and by the CPU models
+// of the tests.
 #ifndef NANORT_CLOSEST_H_
 #define NANORT_CLOSEST_H_
 
@@ -200,6 +203,43 @@ NANORT_CLOSEST_FN bool Better(T dist2, unsigned int prim_id, T best, unsigned in
 template <typename T>
 NANORT_CLOSEST_FN bool Culled(T box_dist2, T best) {
   return box_dist2 > best;
+}
+
+// ---- the K nearest faces (include/nanort_hip.h, "nearest-faces queries") -----------------------------------------
+// The answer of a query (p, max_dist, K) over a set of admitted faces: the CANDIDATES are the faces whose dist2 is not NaN and
+// <= r2 = max_dist * max_dist (a point that is not Searchable has none); they are ranked by the key (dist2, prim_id) ascending —
+// dist2 numerically, then prim_id — and the K with the smallest keys are the answer, in that order.  The key is total over the faces
+// of a mesh, so which candidates are held never depends on the order in which they were tested, nor on the tree.
+//
+// A walk holds at most K candidates.  Its BOUND is r2 while fewer than K are held and the worst held dist2 once K are; a subtree is
+// skipped iff Culled(BoxDist2, bound) — strictly farther, as above: a box at exactly the bound may hold a face that the prim_id
+// prefers.  A candidate ENTERS when fewer than K are held or when Better(dist2, prim_id, worst_dist2, worst_prim_id); the worst is
+// then evicted.  With K = 1 this is the rule above.
+
+// The bound of a walk that holds `held` of at most `k` candidates, the worst of them at worst_dist2.
+template <typename T>
+NANORT_CLOSEST_FN T NearestBound(unsigned int held, unsigned int k, T r2, T worst_dist2) {
+  return held < k ? r2 : worst_dist2;
+}
+
+// Does the face (dist2, prim_id) enter a held set of `held` of at most `k` candidates whose worst key is (worst_dist2, worst_prim)?
+template <typename T>
+NANORT_CLOSEST_FN bool NearestEnters(T dist2, unsigned int prim_id, T r2, unsigned int held, unsigned int k, T worst_dist2, unsigned int worst_prim) {
+  if (!(dist2 <= r2)) return false;  // (not a candidate: too far, or NaN)
+  return held < k || Better<T>(dist2, prim_id, worst_dist2, worst_prim);
+}
+
+// A candidate that NearestEnters admitted, into the sorted row[0 .. held) of at most k records (R: any record with the members dist2
+// and prim_id): the records behind it move one slot up, the worst is dropped when the row is full.  Returns the new count.
+template <typename R>
+NANORT_CLOSEST_FN unsigned int NearestInsert(R *row, unsigned int held, unsigned int k, const R &rec) {
+  unsigned int j = held < k ? held : k - 1u;  // the slot the shift starts from
+  while (j > 0u && Better(rec.dist2, rec.prim_id, row[j - 1u].dist2, row[j - 1u].prim_id)) {
+    row[j] = row[j - 1u];
+    j--;
+  }
+  row[j] = rec;
+  return held < k ? held + 1u : k;
 }
 
 }  // namespace nanort_closest

@@ -951,7 +951,8 @@ NRT_API nrt_status nrtMultiHitQueryBatchDevice_f64(nrt_ctx *ctx, const nrt_multi
  * a time.  nrtClosestPointBatchDevice_* takes device arrays and is asynchronous on `hip_stream`; it takes one of the context's launch
  * slots and closes it with an event, so nrtSetMesh* / nrtBuild / nrtSetTree / nrtRefit* / nrtDestroy wait for it.
  *
- * Not covered: scenes, the sphere, cylinder and curve kinds, per-point skip ids or masks, the k nearest faces, motion time. */
+ * Not covered: scenes, the sphere, cylinder and curve kinds, per-point skip ids or masks, motion time.  (The k nearest faces:
+ * "nearest-faces queries" below.) */
 NRT_API nrt_status nrtClosestPointBatch_f32(nrt_ctx *ctx, const nrt_point_f32 *points, uint64_t num_points, const nrt_trace_options *options,
                                             nrt_closest_f32 *closest_out, uint8_t *found_out);
 NRT_API nrt_status nrtClosestPointBatch_f64(nrt_ctx *ctx, const nrt_point_f64 *points, uint64_t num_points, const nrt_trace_options *options,
@@ -1002,6 +1003,53 @@ NRT_API nrt_status nrtSignedDistanceBatchDevice_f64(nrt_ctx *ctx, const nrt_poin
                                                     nrt_signed_f64 *signed_out, uint8_t *found_out, void *hip_stream);
 NRT_API nrt_status nrtGetFeatureNormals_f32(nrt_ctx *ctx, float *face_normals_out /* [num_faces][4][3] */, float *vertex_normals_out /* [num_verts][3] */);
 NRT_API nrt_status nrtGetFeatureNormals_f64(nrt_ctx *ctx, double *face_normals_out /* [num_faces][4][3] */, double *vertex_normals_out /* [num_verts][3] */);
+
+/* ---- nearest-faces queries ------------------------------------------------------------------------------------------------------
+ * The K = max_faces faces of the context's mesh nearest to a point, in order, 1 <= K <= NRT_MAX_NEAREST — what contact generation
+ * (every face within a radius), attribute transfer (the few nearest faces) and inside/outside voting need, and what an Embree user
+ * writes as an rtcPointQuery callback that collects.  It is to nrtClosestPointBatch* what nrtMultiHitTraverseBatch* is to the
+ * closest hit.  DESIGN.md §3.19.
+ *
+ * The rule is include/nanort_closest.h's.  The CANDIDATES of point i are the faces the options admit (prim_ids_range, skip_prim_id
+ * exactly as in nrtClosestPointBatch*; cull_back_face is ignored) whose dist2 from ClosestPointOnTriangle is not NaN and
+ * <= r2 = max_dist * max_dist; a point with a non-finite coordinate, a NaN or a negative max_dist has none.  They are ranked by the
+ * key (dist2, prim_id) ascending: dist2 numerically, then prim_id.
+ *
+ *   nearest_out[i * K + j], j < count[i]   the candidates with the K smallest keys, in ascending key order; each is exactly the FOUND
+ *                                          record nrtClosestPointBatch* would write for that face alone: point, dist2, u, v, prim_id,
+ *                                          _pad = 0
+ *   nearest_out[i * K + j], j >= count[i]  the NOT FOUND record: point = p, dist2 = r2, u = v = 0, prim_id = 0xFFFFFFFF, _pad = 0
+ *   counts_out[i] (may be NULL)            count[i] = min(K, number of candidates)
+ *
+ * Every byte of every row is written.  The result is byte-identical to sorting all admitted faces by the key and taking the first
+ * K: it does not depend on the tree (nrtBuild, nrtSetTree, nrtRefit) nor on the order in which a walk meets the faces.  With K = 1
+ * the record is nrtClosestPointBatch*'s byte for byte and count equals its found byte.
+ *
+ * A context with a motion keyframe answers for keyframe 0.  An adopted tree (nrtSetTree) is inside the contract when every box
+ * contains the triangles below it.  Runs nrt::k_nearest_faces<T, 32> (nrtLastKernelName).
+ *
+ * Refusals; each writes nothing and sets nrtLastError.  NRT_ERR_INVALID: max_faces == 0 or > NRT_MAX_NEAREST, and everything
+ * nrtClosestPointBatch* refuses — a NULL context (no message to set); NULL points or nearest_out with num_points > 0; no tree; a
+ * sphere, cylinder or curve context; more than 2^31-1 points; a Device array that is not aligned (points and nearest_out to 16 bytes
+ * in fp32 and 8 in fp64, counts_out to 4).  NRT_ERR_PRECISION: a context of the other precision.  num_points == 0 is NRT_OK.
+ *
+ * nrtNearestFacesBatch_* takes host arrays, staged through the context's grow-only buffers, one host call at a time, in pieces of
+ * max(1, 2^20 / K) points (integer division): a piece stages no more records than a piece of nrtClosestPointBatch_*.
+ * nrtNearestFacesBatchDevice_* takes device arrays and is asynchronous on `hip_stream`; launch slot and event as
+ * nrtClosestPointBatchDevice_*'s.  While it runs, a point's row holds the candidates found so far: read it after the stream has passed
+ * the launch.
+ *
+ * Not covered: scenes, the sphere, cylinder and curve kinds, a signed form, per-point skip ids or masks, motion time, more than
+ * NRT_MAX_NEAREST faces per point. */
+#define NRT_MAX_NEAREST 64u
+NRT_API nrt_status nrtNearestFacesBatch_f32(nrt_ctx *ctx, const nrt_point_f32 *points, uint64_t num_points, uint32_t max_faces,
+                                            const nrt_trace_options *options, nrt_closest_f32 *nearest_out, uint32_t *counts_out);
+NRT_API nrt_status nrtNearestFacesBatch_f64(nrt_ctx *ctx, const nrt_point_f64 *points, uint64_t num_points, uint32_t max_faces,
+                                            const nrt_trace_options *options, nrt_closest_f64 *nearest_out, uint32_t *counts_out);
+NRT_API nrt_status nrtNearestFacesBatchDevice_f32(nrt_ctx *ctx, const nrt_point_f32 *points, uint64_t num_points, uint32_t max_faces,
+                                                  const nrt_trace_options *options, nrt_closest_f32 *nearest_out, uint32_t *counts_out, void *hip_stream);
+NRT_API nrt_status nrtNearestFacesBatchDevice_f64(nrt_ctx *ctx, const nrt_point_f64 *points, uint64_t num_points, uint32_t max_faces,
+                                                  const nrt_trace_options *options, nrt_closest_f64 *nearest_out, uint32_t *counts_out, void *hip_stream);
 
 /* One HOST batch spread over several contexts — typically one per GPU of the node (nrtDeviceCount), each holding the same
  * tree: nrtBuild is deterministic, so building the same mesh on every context gives bit-identical replicas (or nrtSetTree the

@@ -651,17 +651,55 @@ class BVHAccel:
         self._check(getattr(self._L, "nrtGetFeatureNormals_" + self._s)(self._h, _p(fn), _p(vn)))
         return fn, vn
 
-    def _point_query(self, fn, record_dtype, points, max_dist, options):
+    # -- nearest faces -------------------------------------------------------
+    def NearestFacesBatch(self, points, max_faces, max_dist=np.inf, options=None):
+        """The `max_faces` (1..capi.NRT_MAX_NEAREST) nearest faces of the mesh to each point, in ascending (dist2, prim_id) order
+        (nrtNearestFacesBatch; the rule: include/nanort_closest.h).  `points`, `max_dist`: as ClosestPointBatch's.  Returns
+        (records[n, max_faces], counts): wire.closest_dtype records — row i holds counts[i] found records, then not-found ones — and a
+        uint32 per point."""
+        from .wire import closest_dtype
+
+        pts = self._point_records(points, max_dist)
+        n, k = pts.shape[0], int(max_faces)
+        out = np.zeros((n, k if 0 < k <= capi.NRT_MAX_NEAREST else 0), dtype=closest_dtype(self.real))  # (a K outside 1..64: the library refuses)
+        counts = np.zeros((n,), dtype=np.uint32)
+        options = _opts(options)
+        self._check(getattr(self._L, "nrtNearestFacesBatch_" + self._s)(self._h, _p(pts), n, k, _p(options), _p(out), _p(counts)))
+        return out, counts
+
+    def NearestFacesBatchDevice(self, d_points, max_faces, d_out, d_counts=None, options=None, stream=None):
+        """Same on HBM-resident torch tensors of raw records (wire.point_dtype in, max_faces wire.closest_dtype records per point out, a
+        uint32 per point in `d_counts`), asynchronous on `stream` (default: torch's current stream).  Returns the number of points."""
+        from .wire import closest_dtype, point_dtype
+
+        for t, what in ((d_points, "d_points"), (d_out, "d_out"), (d_counts, "d_counts")):
+            if t is not None:
+                self._on_device(t, what)
+        n, k = d_points.numel() * d_points.element_size() // point_dtype(self.real).itemsize, int(max_faces)
+        if d_out.numel() * d_out.element_size() < n * k * closest_dtype(self.real).itemsize:
+            raise ValueError("d_out holds fewer than max_faces records per point of d_points")
+        if d_counts is not None and d_counts.numel() * d_counts.element_size() < 4 * n:
+            raise ValueError("d_counts holds fewer words than d_points holds points")
+        options = _opts(options)
+        self._check(getattr(self._L, "nrtNearestFacesBatchDevice_" + self._s)(
+            self._h, d_points.data_ptr(), n, k, _p(options), d_out.data_ptr(), None if d_counts is None else d_counts.data_ptr(),
+            self._stream_handle(stream)))
+        return n
+
+    def _point_records(self, points, max_dist):
         from .wire import point_dtype
 
         pd = point_dtype(self.real)
         if isinstance(points, np.ndarray) and points.dtype == pd:
-            pts = np.ascontiguousarray(points).reshape(-1)
-        else:
-            xyz = np.asarray(points, dtype=self.real).reshape(-1, 3)
-            pts = np.zeros((xyz.shape[0],), dtype=pd)
-            pts["p"] = xyz
-            pts["max_dist"] = np.asarray(max_dist, dtype=self.real)
+            return np.ascontiguousarray(points).reshape(-1)
+        xyz = np.asarray(points, dtype=self.real).reshape(-1, 3)
+        pts = np.zeros((xyz.shape[0],), dtype=pd)
+        pts["p"] = xyz
+        pts["max_dist"] = np.asarray(max_dist, dtype=self.real)
+        return pts
+
+    def _point_query(self, fn, record_dtype, points, max_dist, options):
+        pts = self._point_records(points, max_dist)
         n = pts.shape[0]
         out = np.zeros((n,), dtype=record_dtype)
         found = np.zeros((n,), dtype=np.uint8)

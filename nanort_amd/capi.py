@@ -48,6 +48,7 @@ class RayQuery(ctypes.Structure):
 
 
 NRT_MAX_MULTIHIT = 64
+NRT_MAX_NEAREST = 64
 
 
 class MultiHitQuery(ctypes.Structure):
@@ -169,6 +170,9 @@ SIGNATURES = [
     ("nrtSignedDistanceBatch", _BOTH, _Q + [vp, vp], i32),
     ("nrtSignedDistanceBatchDevice", _BOTH, _Q + [vp, vp, vp], i32),
     ("nrtGetFeatureNormals", _BOTH, [vp, vp, vp], i32),
+    # nearest-faces queries: ctx, points, num_points, max_faces, options, nearest_out, counts_out[, stream]
+    ("nrtNearestFacesBatch", _BOTH, [vp, vp, u64, u32, vp, vp, vp], i32),
+    ("nrtNearestFacesBatchDevice", _BOTH, [vp, vp, u64, u32, vp, vp, vp, vp], i32),
     ("nrtTraverseBatchMulti", _BOTH, [vp, u32, vp, u64, u64, vp, vp, vp], i32),
     ("nrtDeviceCount", None, [], i32),
     ("nrtTraverseCountDevice", _BOTH, _Q + [P(TraceCounters)], i32),

@@ -124,21 +124,32 @@ static nrt_status validate_launch(nrt_ctx *c, const TraverseLaunch<T> &l) {
   return NRT_OK;
 }
 
-// The entry checks of the closest-point query (include/nanort_hip.h, "closest-point queries"), in the ray queries' order and with
-// their statuses (under launch_mutex).  `device`: the arrays are the caller's device memory, whose alignment the kernel's loads and
-// stores rely on (the host form stages them).
+// The entry checks of the three point queries — closest point, signed distance, nearest faces (include/nanort_hip.h, "closest-point
+// queries", "nearest-faces queries") — in the ray queries' order and with their statuses (under launch_mutex).  `device`: the arrays
+// are the caller's device memory, whose alignment the kernel's loads and stores rely on (the host form stages them).  `flags`: the
+// found bytes, or the nearest-faces query's count words (either may be NULL).
+enum class PointQuery { Closest, Signed, Nearest };
+struct PointKind {
+  PointQuery query = PointQuery::Closest;
+  uint32_t max_faces = 1; // Nearest: K, 1..NRT_MAX_NEAREST records per point
+  bool nearest() const { return query == PointQuery::Nearest; }
+};
 template <typename T>
-static nrt_status validate_closest(nrt_ctx *c, const char *fn, const void *points, uint64_t n, const void *out, const void *found, bool device) {
-  (void)found; // (may be NULL; a byte array has no alignment to check)
+static nrt_status validate_closest(nrt_ctx *c, const char *fn, const PointKind &k, const void *points, uint64_t n, const void *out, const void *flags,
+                                   bool device) {
   if (c->prec != (int)sizeof(T)) return fail(c, NRT_ERR_PRECISION, "%s: precision mismatch", fn);
   if (c->prim_kind != kPrimTriangles) return fail(c, NRT_ERR_INVALID, "%s: triangle contexts only (this context holds %s)", fn, kPrimKinds[c->prim_kind].name);
   if (!c->d_nodes) return fail(c, NRT_ERR_INVALID, "%s: no tree (call nrtBuild or nrtSetTree)", fn);
+  if (k.nearest() && (k.max_faces == 0u || k.max_faces > NRT_MAX_NEAREST))
+    return fail(c, NRT_ERR_INVALID, "%s: max_faces %u outside 1..%u", fn, k.max_faces, NRT_MAX_NEAREST);
   if (n == 0) return NRT_OK;
-  if (!points || !out) return fail(c, NRT_ERR_INVALID, "%s: NULL points/closest_out", fn);
+  if (!points || !out) return fail(c, NRT_ERR_INVALID, "%s: NULL points/%s", fn, k.nearest() ? "nearest_out" : "closest_out");
   if (n > 0x7FFFFFFFull) return fail(c, NRT_ERR_INVALID, "%s: more than 2^31-1 points in one call", fn);
   const uintptr_t align = sizeof(T) == 4 ? 16u : 8u;
   if (device && (((uintptr_t)points % align) != 0u || ((uintptr_t)out % align) != 0u))
     return fail(c, NRT_ERR_INVALID, "%s: the device arrays are not aligned to %zu bytes", fn, (size_t)align);
+  if (device && k.nearest() && ((uintptr_t)flags % sizeof(uint32_t)) != 0u) // (a found byte has no alignment to check)
+    return fail(c, NRT_ERR_INVALID, "%s: counts_out is not aligned to 4 bytes", fn);
   return NRT_OK;
 }
 
@@ -450,14 +461,18 @@ static nrt_status get_feature_normals(nrt_ctx *c, T *face_normals, T *vertex_nor
 // event, a launch slot for its cursors and its overflow stack, the persistent grid and the claim plan of launch_plan.h — with points
 // in the place of rays: `points`, `out` and `found` are device arrays, `s` the stream the launch is enqueued on.  It publishes no
 // completion record: the slot is closed by its event, which is what a rebuild or a refit waits for (wait_for_launches).
-// `is_signed`: the signed distance query (k_signed_distance) — the same checks, slot and events, the pseudonormals refreshed first.
+// `k`: which of the three point queries.  Signed (k_signed_distance): the same checks, slot and events, the pseudonormals refreshed
+// first.  Nearest (nearest.hip, k_nearest_faces): `out` holds k.max_faces records per point and `flags` a count word per point where
+// the other two have a found byte.
 template <typename T>
-static nrt_status closest_device(nrt_ctx *c, const char *fn, const void *points, uint64_t n, const nrt_trace_options *opt, void *out, uint8_t *found,
-                                 bool device, hipStream_t s, bool is_signed = false) {
+static nrt_status closest_device(nrt_ctx *c, const char *fn, const void *points, uint64_t n, const nrt_trace_options *opt, void *out, void *flags,
+                                 bool device, hipStream_t s, const PointKind &k = {}) {
+  const bool is_signed = k.query == PointQuery::Signed;
+  uint8_t *found = (uint8_t *)flags;
   if (!c) return NRT_ERR_INVALID;
   if (!opt) opt = &kDefaultTrace;
   std::lock_guard<std::mutex> lock(c->launch_mutex);
-  nrt_status st = validate_closest<T>(c, fn, points, n, out, found, device);
+  nrt_status st = validate_closest<T>(c, fn, k, points, n, out, flags, device);
   if (st || n == 0) return st;
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, refit_stream_wait(c, s)); // (a Device refit in flight on another stream)
@@ -466,7 +481,8 @@ static nrt_status closest_device(nrt_ctx *c, const char *fn, const void *points,
   if ((st = take_slot(c, s, &slot))) return st;
   if (c->closest_blocks_per_cu == 0) c->closest_blocks_per_cu = (unsigned)closest_point_blocks_per_cu<T>();
   if (is_signed && c->signed_blocks_per_cu == 0) c->signed_blocks_per_cu = (unsigned)signed_distance_blocks_per_cu<T>();
-  const unsigned resident = is_signed ? c->signed_blocks_per_cu : c->closest_blocks_per_cu;
+  if (k.nearest() && c->nearest_blocks_per_cu == 0) c->nearest_blocks_per_cu = (unsigned)nearest_faces_blocks_per_cu<T>();
+  const unsigned resident = is_signed ? c->signed_blocks_per_cu : k.nearest() ? c->nearest_blocks_per_cu : c->closest_blocks_per_cu;
   const unsigned per_cu = c->max_blocks_per_cu && resident > c->max_blocks_per_cu ? c->max_blocks_per_cu : resident;
   const GridPlan g = plan_grid(n, kTraverseBlock, (uint32_t)c->num_cus, per_cu, c->num_parts);
   const uint32_t total_threads = g.grid * kTraverseBlock, total_waves = g.grid * (kTraverseBlock / kWave);
@@ -495,6 +511,8 @@ static nrt_status closest_device(nrt_ctx *c, const char *fn, const void *points,
   if (is_signed) {
     const SignedInputs<T> in = {(const T *)c->b_face_normals.p, (const T *)c->b_vertex_normals.p, c->d_faces, c->num_faces, c->num_verts};
     HIPCHK(c, launch_signed_distance<T>(a, in, points, out, found, g.grid, s, &c->last_kernel));
+  } else if (k.nearest()) {
+    HIPCHK(c, launch_nearest_faces<T>(a, points, k.max_faces, out, (uint32_t *)flags, g.grid, s, &c->last_kernel));
   } else {
     HIPCHK(c, launch_closest_point<T>(a, points, out, found, g.grid, s, &c->last_kernel));
   }
@@ -514,32 +532,39 @@ static nrt_status closest_device(nrt_ctx *c, const char *fn, const void *points,
 const uint64_t kClosestPiece = 1ull << 20; // points per launch of the staged host form (16 MB up, 33 MB down in fp32)
 
 // ... over the caller's HOST arrays: one call at a time (host_mutex: the staging buffers are the context's), in pieces of kClosestPiece
-// points — the piece up into st_rays, the launch over the staging buffers, its records and bytes of st_hits / st_mask back.
+// points — the piece up into st_rays, the launch over the staging buffers, its records and bytes of st_hits / st_mask back.  The
+// nearest-faces query has K = k.max_faces records and one count word per point: its pieces are max(1, kClosestPiece / K) points, so
+// that a piece stages no more records than the other two queries'.
 template <typename T>
 static nrt_status closest_host(nrt_ctx *c, const typename ClosestWire<T>::Point *points, uint64_t n, const nrt_trace_options *opt,
-                               typename ClosestWire<T>::Record *out, uint8_t *found, bool is_signed = false) {
+                               typename ClosestWire<T>::Record *out, void *flags, const PointKind &k = {}) {
   typedef typename ClosestWire<T>::Point Point;
   typedef typename ClosestWire<T>::Record Record;
-  const char *fn = is_signed ? "nrtSignedDistanceBatch" : "nrtClosestPointBatch";
+  const char *fn = k.query == PointQuery::Signed ? "nrtSignedDistanceBatch" : k.nearest() ? "nrtNearestFacesBatch" : "nrtClosestPointBatch";
   if (!c) return NRT_ERR_INVALID;
   {
     std::lock_guard<std::mutex> lock(c->launch_mutex);
-    const nrt_status st = validate_closest<T>(c, fn, points, n, out, found, false);
+    const nrt_status st = validate_closest<T>(c, fn, k, points, n, out, flags, false);
     if (st || n == 0) return st;
   }
   std::lock_guard<std::mutex> host_lock(c->host_mutex);
   HIPCHK(c, hipSetDevice(c->device));
-  for (uint64_t off = 0; off < n; off += kClosestPiece) {
-    const uint64_t m = std::min(kClosestPiece, n - off);
+  const uint64_t per_point = k.nearest() ? k.max_faces : 1u;           // records
+  const uint64_t flag_bytes = k.nearest() ? sizeof(uint32_t) : 1u;     // a count word or a found byte
+  const uint64_t piece = std::max<uint64_t>(1, kClosestPiece / per_point);
+  for (uint64_t off = 0; off < n; off += piece) {
+    const uint64_t m = std::min(piece, n - off);
     nrt_status st;
-    if ((st = ensure(c, c->st_rays, m * sizeof(Point))) || (st = ensure(c, c->st_hits, m * sizeof(Record))) || (st = ensure(c, c->st_mask, m))) return st;
+    if ((st = ensure(c, c->st_rays, m * sizeof(Point))) || (st = ensure(c, c->st_hits, m * per_point * sizeof(Record))) ||
+        (st = ensure(c, c->st_mask, m * flag_bytes)))
+      return st;
     HIPCHK(c, hipMemcpyAsync(c->st_rays.p, points + off, m * sizeof(Point), hipMemcpyHostToDevice, c->stream));
-    if ((st = closest_device<T>(c, fn, c->st_rays.p, m, opt, c->st_hits.p, (uint8_t *)c->st_mask.p, false, c->stream, is_signed))) {
+    if ((st = closest_device<T>(c, fn, c->st_rays.p, m, opt, c->st_hits.p, c->st_mask.p, false, c->stream, k))) {
       (void)hipStreamSynchronize(c->stream);
       return st;
     }
-    HIPCHK(c, hipMemcpyAsync(out + off, c->st_hits.p, m * sizeof(Record), hipMemcpyDeviceToHost, c->stream));
-    if (found) HIPCHK(c, hipMemcpyAsync(found + off, c->st_mask.p, m, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out + off * per_point, c->st_hits.p, m * per_point * sizeof(Record), hipMemcpyDeviceToHost, c->stream));
+    if (flags) HIPCHK(c, hipMemcpyAsync((uint8_t *)flags + off * flag_bytes, c->st_mask.p, m * flag_bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
   }
   return NRT_OK;
@@ -1303,23 +1328,41 @@ nrt_status nrtTraverseCountDevice_f64(nrt_ctx *c, const nrt_ray_f64 *r, uint64_t
 
 } // extern "C"
 
+// Nearest-faces queries (include/nanort_hip.h): the K nearest faces of the mesh to each point, a sorted row of closest-point records.
+nrt_status nrtNearestFacesBatch_f32(nrt_ctx *c, const nrt_point_f32 *p, uint64_t n, uint32_t k, const nrt_trace_options *o, nrt_closest_f32 *out,
+                                    uint32_t *counts) {
+  return closest_host<float>(c, p, n, o, out, counts, {PointQuery::Nearest, k});
+}
+nrt_status nrtNearestFacesBatch_f64(nrt_ctx *c, const nrt_point_f64 *p, uint64_t n, uint32_t k, const nrt_trace_options *o, nrt_closest_f64 *out,
+                                    uint32_t *counts) {
+  return closest_host<double>(c, p, n, o, out, counts, {PointQuery::Nearest, k});
+}
+nrt_status nrtNearestFacesBatchDevice_f32(nrt_ctx *c, const nrt_point_f32 *p, uint64_t n, uint32_t k, const nrt_trace_options *o, nrt_closest_f32 *out,
+                                          uint32_t *counts, void *s) {
+  return closest_device<float>(c, "nrtNearestFacesBatchDevice", p, n, o, out, counts, true, (hipStream_t)s, {PointQuery::Nearest, k});
+}
+nrt_status nrtNearestFacesBatchDevice_f64(nrt_ctx *c, const nrt_point_f64 *p, uint64_t n, uint32_t k, const nrt_trace_options *o, nrt_closest_f64 *out,
+                                          uint32_t *counts, void *s) {
+  return closest_device<double>(c, "nrtNearestFacesBatchDevice", p, n, o, out, counts, true, (hipStream_t)s, {PointQuery::Nearest, k});
+}
+
 // Signed distance queries (include/nanort_hip.h): the closest-point query with the side of the surface; the records share the layout.
 static_assert(sizeof(nrt_signed_f32) == sizeof(nrt_closest_f32) && sizeof(nrt_signed_f64) == sizeof(nrt_closest_f64) &&
                   offsetof(nrt_signed_f32, feature) == offsetof(nrt_closest_f32, _pad) && offsetof(nrt_signed_f64, feature) == offsetof(nrt_closest_f64, _pad),
               "a signed record is a closest-point record with `feature` in the place of `_pad`");
 nrt_status nrtSignedDistanceBatch_f32(nrt_ctx *c, const nrt_point_f32 *p, uint64_t n, const nrt_trace_options *o, nrt_signed_f32 *out, uint8_t *f) {
-  return closest_host<float>(c, p, n, o, (nrt_closest_f32 *)out, f, true);
+  return closest_host<float>(c, p, n, o, (nrt_closest_f32 *)out, f, {PointQuery::Signed});
 }
 nrt_status nrtSignedDistanceBatch_f64(nrt_ctx *c, const nrt_point_f64 *p, uint64_t n, const nrt_trace_options *o, nrt_signed_f64 *out, uint8_t *f) {
-  return closest_host<double>(c, p, n, o, (nrt_closest_f64 *)out, f, true);
+  return closest_host<double>(c, p, n, o, (nrt_closest_f64 *)out, f, {PointQuery::Signed});
 }
 nrt_status nrtSignedDistanceBatchDevice_f32(nrt_ctx *c, const nrt_point_f32 *p, uint64_t n, const nrt_trace_options *o, nrt_signed_f32 *out, uint8_t *f,
                                             void *s) {
-  return closest_device<float>(c, "nrtSignedDistanceBatchDevice", p, n, o, out, f, true, (hipStream_t)s, true);
+  return closest_device<float>(c, "nrtSignedDistanceBatchDevice", p, n, o, out, f, true, (hipStream_t)s, {PointQuery::Signed});
 }
 nrt_status nrtSignedDistanceBatchDevice_f64(nrt_ctx *c, const nrt_point_f64 *p, uint64_t n, const nrt_trace_options *o, nrt_signed_f64 *out, uint8_t *f,
                                             void *s) {
-  return closest_device<double>(c, "nrtSignedDistanceBatchDevice", p, n, o, out, f, true, (hipStream_t)s, true);
+  return closest_device<double>(c, "nrtSignedDistanceBatchDevice", p, n, o, out, f, true, (hipStream_t)s, {PointQuery::Signed});
 }
 nrt_status nrtGetFeatureNormals_f32(nrt_ctx *c, float *fn, float *vn) { return get_feature_normals<float>(c, fn, vn); }
 nrt_status nrtGetFeatureNormals_f64(nrt_ctx *c, double *fn, double *vn) { return get_feature_normals<double>(c, fn, vn); }

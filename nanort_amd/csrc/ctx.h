@@ -161,6 +161,7 @@ struct nrt_ctx {
 
   unsigned closest_blocks_per_cu = 0; // ... and of k_closest_point (closest.hip; 0: not asked for yet)
   unsigned signed_blocks_per_cu = 0;  // ... and of k_signed_distance
+  unsigned nearest_blocks_per_cu = 0; // ... and of k_nearest_faces (nearest.hip)
 
   hipEvent_t ev_b0 = nullptr, ev_b1 = nullptr;
   hipEvent_t ev_build_state = nullptr; // the builder's state block has reached build_state

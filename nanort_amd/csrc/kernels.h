@@ -113,6 +113,15 @@ hipError_t launch_signed_distance(const TraverseArgs<T> &args, const SignedInput
 template <typename T>
 int signed_distance_blocks_per_cu();
 
+// ---- nearest.hip: the nearest-faces query (k_nearest_faces; the K-nearest rule of include/nanort_closest.h) ----------------------
+// `args`, `points`: as launch_closest_point's; `out`: num_rays * max_faces of ClosestWire<T>'s records, each point's row sorted by
+// (dist2, prim_id); `counts`: a word per point or null; max_faces: 1..NRT_MAX_NEAREST
+template <typename T>
+hipError_t launch_nearest_faces(const TraverseArgs<T> &args, const void *points, uint32_t max_faces, void *out, uint32_t *counts, unsigned grid,
+                                hipStream_t s, const char **name_out);
+template <typename T>
+int nearest_faces_blocks_per_cu();
+
 // ---- sdf.hip: the angle-weighted pseudonormals of a triangle mesh (include/nanort_sdf.h states them) ---------------------------------
 // The workspace of one derivation for `num_faces` faces and `num_verts` vertices, in bytes.
 template <typename T>
