@@ -52,8 +52,9 @@
 // strictly, where best starts at r2 (Culled): a box at exactly best is entered, because the tie-break may prefer a face inside it.
 //
 // The K nearest faces in the place of the nearest one: the K-nearest rule at the end of the file (NearestBound, NearestEnters).
+// The faces of an instanced scene in the place of one mesh's: XformPoint, XformBox, BetterInScene, before it.
 //
-// Included by the device kernels (nanort_amd/csrc/closest.hip, nearest.hip), by the host classes of nanort.h and by the CPU models
+// Included by the device kernels (nanort_amd/csrc/closest.hip, nearest.hip, scene_closest.hip), by the host classes of nanort.h and by the CPU models
 // of the tests.
 #ifndef NANORT_CLOSEST_H_
 #define NANORT_CLOSEST_H_
@@ -203,6 +204,49 @@ NANORT_CLOSEST_FN bool Better(T dist2, unsigned int prim_id, T best, unsigned in
 template <typename T>
 NANORT_CLOSEST_FN bool Culled(T box_dist2, T best) {
   return box_dist2 > best;
+}
+
+// ---- instanced scenes (include/nanort_hip.h, "closest-point queries on scenes") ---------------------------------
+// fp32, as scenes are.  A face of an instance IS the triangle of the three XformPoint images of its local vertices, m the instance's
+// local -> world matrix (row 3 the translation: nanosg's convention), and the answer of a query over a scene is the rule above over
+// all (node, face) pairs of admitted nodes: the smallest dist2, then the smallest node_id, then the smallest prim_id (BetterInScene) —
+// byte for byte the answer over ONE mesh, the world vertices of all instances concatenated in node order.  Nothing is inverted, so a
+// singular matrix (an instance flattened to a plane) is inside the contract; finite matrices and vertices are.
+//
+//   XformPoint(m, v)             w_k = m[0][k]*v0 + m[1][k]*v1 + m[2][k]*v2 + m[3][k], summed left to right: Matrix::MultV of the
+//                                scene code (nanort_amd/csrc/common.h, mult_v), operation for operation.
+//   XformBox(m, bmin, bmax)      per output component k, the low side is XformPoint's sum over bmin_j where m[j][k] >= 0 and bmax_j
+//                                otherwise, the high side over the opposite choice.  Each product and each sum is monotone under
+//                                rounding, so in floating point (a) the result is the min / max over the eight XformPoint corner
+//                                images — the world box Commit stores for an instance — and (b) it contains XformPoint(m, v) for
+//                                every v inside [bmin, bmax].
+//
+// The clamp of ClosestOnTriangle puts q inside every box that contains the three world vertices, so BoxDist2(p, XformBox(node box))
+// <= dist2 holds in floating point for every face below a node of an instance's tree, BoxDist2 of the instance's world box likewise,
+// and of every box of a top-level tree over those boxes: Culled hides nothing at either level.
+template <typename T, int W>
+NANORT_CLOSEST_FN void XformPoint(const T (&m)[4][W], const T v[3], T w[3]) {
+  const T w0 = m[0][0] * v[0] + m[1][0] * v[1] + m[2][0] * v[2] + m[3][0];
+  const T w1 = m[0][1] * v[0] + m[1][1] * v[1] + m[2][1] * v[2] + m[3][1];
+  const T w2 = m[0][2] * v[0] + m[1][2] * v[1] + m[2][2] * v[2] + m[3][2];
+  w[0] = w0, w[1] = w1, w[2] = w2;
+}
+
+template <typename T, int W>
+NANORT_CLOSEST_FN void XformBox(const T (&m)[4][W], const T bmin[3], const T bmax[3], T wmin[3], T wmax[3]) {
+  T lo[3], hi[3];
+  for (int k = 0; k < 3; k++) {
+    const bool up0 = m[0][k] >= T(0), up1 = m[1][k] >= T(0), up2 = m[2][k] >= T(0);
+    lo[k] = m[0][k] * (up0 ? bmin[0] : bmax[0]) + m[1][k] * (up1 ? bmin[1] : bmax[1]) + m[2][k] * (up2 ? bmin[2] : bmax[2]) + m[3][k];
+    hi[k] = m[0][k] * (up0 ? bmax[0] : bmin[0]) + m[1][k] * (up1 ? bmax[1] : bmin[1]) + m[2][k] * (up2 ? bmax[2] : bmin[2]) + m[3][k];
+  }
+  for (int k = 0; k < 3; k++) wmin[k] = lo[k], wmax[k] = hi[k];
+}
+
+// Better, over the faces of a scene: (dist2, node_id, prim_id) ascending.  `best` starts at r2 with both ids 0xFFFFFFFF.
+template <typename T>
+NANORT_CLOSEST_FN bool BetterInScene(T dist2, unsigned int node_id, unsigned int prim_id, T best, unsigned int best_node, unsigned int best_prim) {
+  return dist2 < best || (dist2 == best && (node_id < best_node || (node_id == best_node && prim_id < best_prim)));
 }
 
 // ---- the K nearest faces (include/nanort_hip.h, "nearest-faces queries") -----------------------------------------

@@ -951,8 +951,8 @@ NRT_API nrt_status nrtMultiHitQueryBatchDevice_f64(nrt_ctx *ctx, const nrt_multi
  * a time.  nrtClosestPointBatchDevice_* takes device arrays and is asynchronous on `hip_stream`; it takes one of the context's launch
  * slots and closes it with an event, so nrtSetMesh* / nrtBuild / nrtSetTree / nrtRefit* / nrtDestroy wait for it.
  *
- * Not covered: scenes, the sphere, cylinder and curve kinds, per-point skip ids or masks, motion time.  (The k nearest faces:
- * "nearest-faces queries" below.) */
+ * Not covered: the sphere, cylinder and curve kinds, per-point skip ids or masks, motion time.  (The k nearest faces:
+ * "nearest-faces queries" below; instanced scenes: nrtSceneClosestPointBatch*, at the end of the scene calls.) */
 NRT_API nrt_status nrtClosestPointBatch_f32(nrt_ctx *ctx, const nrt_point_f32 *points, uint64_t num_points, const nrt_trace_options *options,
                                             nrt_closest_f32 *closest_out, uint8_t *found_out);
 NRT_API nrt_status nrtClosestPointBatch_f64(nrt_ctx *ctx, const nrt_point_f64 *points, uint64_t num_points, const nrt_trace_options *options,
@@ -1232,7 +1232,8 @@ NRT_API nrt_status nrtSceneSetTunable(nrt_scene *scene, const char *name, int va
 /* How many rays of the last nrtSceneTraverseBatch* call the single-pass walk handed to the listing path. */
 NRT_API uint64_t nrtSceneLastRedone(const nrt_scene *scene);
 /* Which path the last nrtSceneTraverseBatch* call took: 1 = the single-pass walk (plus the listing path for the rays it handed
- * over), 0 = the listing path alone (small scenes, single_pass = 0, a mesh whose tree the walk cannot step through, back-off). */
+ * over), 0 = the listing path alone (small scenes, single_pass = 0, a mesh whose tree the walk cannot step through, back-off).
+ * After nrtSceneClosestPointBatch* (below): 2 = its one kernel, nrt::k_scene_closest_point<32>. */
 NRT_API int nrtSceneLastPath(const nrt_scene *scene);
 
 /* ---- occlusion queries on a scene: is the ray blocked at all? (shadow rays, rtcOccluded) --------------------------
@@ -1367,6 +1368,51 @@ typedef struct {
 } nrt_scene_query_f32;         /* 64 bytes */
 NRT_API nrt_status nrtSceneQueryBatch_f32(nrt_scene *scene, const nrt_scene_query_f32 *query);
 NRT_API nrt_status nrtSceneQueryBatchDevice_f32(nrt_scene *scene, const nrt_scene_query_f32 *query);
+
+/* ---- closest-point queries on scenes ------------------------------------------------------------------------------------------------
+ * Which face of which node of a committed scene is nearest to a point, and where on it: "closest-point queries" above, over the
+ * instances of a scene instead of one mesh — Embree's rtcPointQuery with its instance stack.  (No reference counterpart.)  DESIGN.md §3.20.
+ *
+ * The rule is include/nanort_closest.h's, in fp32, every operation rounded on its own.  A face of a node IS the triangle of the three
+ * XformPoint images of its local vertices — w_k = m[0][k]*v0 + m[1][k]*v1 + m[2][k]*v2 + m[3][k] summed left to right, m the node's
+ * xform (nrtSceneNodeState_f32) — and ClosestPointOnTriangle of the world point against that triangle gives point (world), dist2, u
+ * and v.  The answer is taken over all (node, face) pairs of the admitted nodes: the smallest dist2, then the smallest node_id, then
+ * the smallest prim_id.  max_dist, non-finite points, NaN faces and equality at r2 = max_dist * max_dist are as in the single-mesh
+ * query.  The record is therefore byte-identical to nrtClosestPointBatch_f32's on ONE mesh — the world vertices of all nodes
+ * concatenated in node order — with that mesh's face index mapped back to (node_id, prim_id); the accuracy contract (8 eps S) holds
+ * against the triangles of the rounded world vertices.  No matrix is inverted: a singular xform (a node flattened to a plane) is
+ * inside the contract, finite matrices and vertices are.
+ *
+ * Found: point = the nearest point (world), dist2, u, v, prim_id, node_id.  Not found: point = p, dist2 = r2, u = v = 0,
+ * prim_id = node_id = 0xFFFFFFFF.  found_out (may be NULL) receives 1 / 0 per point.
+ *
+ * Masks.  point_masks == NULL: every node is admitted, whatever its word.  Otherwise one word per point, and a node is admitted for
+ * a point iff (node word & point word) != 0 — the words of nrtSceneSetNodeMasks, as "instance visibility masks" above defines them
+ * for rays: 0xFFFFFFFF until set, no part of the top-level tree, no Commit needed on a change.
+ *
+ * Runs nrt::k_scene_closest_point<32>, one launch per call (per piece in the host form): the top-level tree where nrtSceneCommit
+ * built one and a scan of the nodes' world boxes where it did not ("scan_max"), and the nodes' own trees, on one stack per point;
+ * nrtSceneLastPath reports 2.  Mesh trees adopted with nrtSetTree are inside the contract when every box contains the triangles
+ * below it.  The trace options of a mesh context, its triangle masks and its motion keyframe 1 are not read.
+ *
+ * Refusals; each NRT_ERR_INVALID, writes nothing and sets nrtSceneLastError: a NULL scene; a scene that is not committed; a mesh
+ * context rebuilt, re-set or refitted since nrtSceneCommit; NULL points or closest_out with num_points > 0; more than 2^31-1
+ * points; in the Device form, points or closest_out not aligned to 16 bytes or point_masks not to 4.  num_points == 0 on a committed
+ * scene is NRT_OK.
+ *
+ * nrtSceneClosestPointBatch_f32 takes host arrays, staged through the scene's grow-only buffers in pieces of 2^20 points.
+ * nrtSceneClosestPointBatchDevice_f32 takes device arrays; like every scene call it runs on the scene's own stream and is
+ * SYNCHRONOUS, and the caller makes sure the inputs are complete before calling.
+ *
+ * Not covered: signed distance and the K nearest faces on scenes, per-point skip pairs, fp64. */
+typedef struct { float point[3]; float dist2; float u, v; uint32_t prim_id; uint32_t node_id; } nrt_scene_closest_f32;
+#ifdef __cplusplus
+static_assert(sizeof(nrt_scene_closest_f32) == 32, "scene closest-point record layout");
+#endif
+NRT_API nrt_status nrtSceneClosestPointBatch_f32(nrt_scene *scene, const nrt_point_f32 *points, uint64_t num_points, const uint32_t *point_masks,
+                                                 nrt_scene_closest_f32 *closest_out, uint8_t *found_out);
+NRT_API nrt_status nrtSceneClosestPointBatchDevice_f32(nrt_scene *scene, const nrt_point_f32 *d_points, uint64_t num_points,
+                                                       const uint32_t *d_point_masks, nrt_scene_closest_f32 *d_closest_out, uint8_t *d_found_out);
 
 #ifdef __cplusplus
 }

@@ -30,7 +30,9 @@ NRT_API long nrtDebugWaveClocks(nrt_ctx *ctx, unsigned long long *out, long cap)
  * instantiated, slower k_scene_walk).  out16[0] = outer trips of all waves, [1..2] level-change blocks run / lanes served,
  * [3..4] inner-phase trips / lane steps, [5] of those in the top-level tree, [6..7] leaf-phase trips / lanes with a first
  * record, [8] instances opened, [9] top-level leaves reached, [10..12] shader-clock ticks in level changes / the inner phase /
- * the leaf phase.  Returns 0 on success (tools/scene_loop_stats.py). */
+ * the leaf phase.  Returns 0 on success (tools/scene_loop_stats.py).
+ * After nrtSceneClosestPointBatch* (every call of the profiling library counts; the host form: its last piece): out16[0] = nodes
+ * opened at both levels, [1] = instances entered, [2] = triangles tested (tools/scene_closest_probe.py). */
 NRT_API int nrtSceneDebugCounters(nrt_scene *scene, unsigned long long *out, int capacity /* >= 16 */);
 
 #ifdef __cplusplus

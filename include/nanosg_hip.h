@@ -173,6 +173,19 @@ class BatchTracer {
     return true;
   }
 
+  // Which face of which node is nearest to each point, and where on it, in world space (include/nanort_hip.h, "closest-point
+  // queries on scenes"): points[i] = {p, max_dist}, out[i] = {point, dist2, u, v, prim_id, node_id} — ids 0xFFFFFFFF and point = p
+  // where nothing lies within max_dist — and found[i] (optional) 1 / 0.  `point_masks` (NULL: every node): one word per point, a
+  // node is admitted iff its word (SetNodeMasks) shares a bit with it.  A thin forward to nrtSceneClosestPointBatch_f32.
+  bool ClosestPoint(const nrt_point_f32 *points, size_t num_points, const uint32_t *point_masks, nrt_scene_closest_f32 *out, unsigned char *found = NULL) {
+    if (!handle_) return false;
+    if (nrtSceneClosestPointBatch_f32(handle_, points, num_points, point_masks, out, found) != NRT_OK) {
+      error_ = nrtSceneLastError(handle_);
+      return false;
+    }
+    return true;
+  }
+
  private:
   struct NodeState {
     float m[64];  // xform, inv_xform, inv_xform33, inv_transpose_xform33 (nrtSceneNodeState_f32)

@@ -1160,7 +1160,8 @@ class Scene:
         return int(self._L.nrtSceneLastRedone(self._h))
 
     def LastPath(self):
-        """1: the last call went through the single-pass walk, 0: the listing path alone (nrtSceneLastPath)."""
+        """1: the last call went through the single-pass walk, 0: the listing path alone; 2: it was a closest-point query, whose one
+        kernel is nrt::k_scene_closest_point<32> (nrtSceneLastPath)."""
         return int(self._L.nrtSceneLastPath(self._h))
 
     def TraverseBatch(self, rays):
@@ -1345,4 +1346,50 @@ class Scene:
                             None if ray_masks is None else ray_masks.data_ptr(), pairs, stride, 0,
                             None if d_hits is None else d_hits.data_ptr(), None if d_mask is None else d_mask.data_ptr())
         self._check(self._L.nrtSceneQueryBatchDevice_f32(self._h, ctypes.addressof(q)))
+        return n
+
+    # -- closest point (include/nanort_hip.h, "closest-point queries on scenes") ----
+    def ClosestPointBatch(self, points, max_dist=np.inf, point_masks=None):
+        """The nearest face of the nearest node to each point and where on it, in world space (nrtSceneClosestPointBatch_f32; the rule:
+        include/nanort_closest.h).  `points`: [n, 3] coordinates with `max_dist` a scalar or one value per point, or a wire.POINT_F32
+        record array (then `max_dist` is not read).  `point_masks`: one uint32 per point — a node is admitted iff its word
+        (SetNodeMasks) shares a bit with the point's — or None: every node.  Returns (records, found): wire.SCENE_CLOSEST_F32 records and
+        a uint8 per point."""
+        from .wire import POINT_F32, SCENE_CLOSEST_F32
+
+        if isinstance(points, np.ndarray) and points.dtype == POINT_F32:
+            pts = np.ascontiguousarray(points).reshape(-1)
+        else:
+            xyz = np.asarray(points, dtype=np.float32).reshape(-1, 3)
+            pts = np.zeros((xyz.shape[0],), dtype=POINT_F32)
+            pts["p"] = xyz
+            pts["max_dist"] = np.asarray(max_dist, dtype=np.float32)
+        n = pts.shape[0]
+        words = self._ray_words(point_masks, n)
+        out = np.zeros((n,), dtype=SCENE_CLOSEST_F32)
+        found = np.zeros((n,), dtype=np.uint8)
+        self._check(self._L.nrtSceneClosestPointBatch_f32(self._h, _p(pts), n, _p(words), _p(out), _p(found)))
+        return out, found
+
+    def ClosestPointBatchDevice(self, d_points, d_out, d_found=None, d_point_masks=None):
+        """The same on HBM-resident torch tensors of raw records (wire.POINT_F32 in, wire.SCENE_CLOSEST_F32 out, a byte per point in
+        `d_found`, one 32-bit word per point in `d_point_masks`).  Synchronous (see nrtSceneClosestPointBatchDevice_f32); waits for
+        torch's current stream first.  Returns the number of points."""
+        import torch
+
+        from .wire import POINT_F32, SCENE_CLOSEST_F32
+
+        for t, what in ((d_points, "d_points"), (d_out, "d_out"), (d_found, "d_found"), (d_point_masks, "d_point_masks")):
+            if t is not None and not t.is_cuda:
+                raise ValueError("%s is not a device tensor" % what)
+        n = d_points.numel() * d_points.element_size() // POINT_F32.itemsize
+        if d_out.numel() * d_out.element_size() < n * SCENE_CLOSEST_F32.itemsize:
+            raise ValueError("d_out holds fewer records than d_points holds points")
+        if d_found is not None and d_found.numel() * d_found.element_size() < n:
+            raise ValueError("d_found holds fewer bytes than d_points holds points")
+        if d_point_masks is not None and d_point_masks.numel() * d_point_masks.element_size() < 4 * n:
+            raise ValueError("d_point_masks holds fewer words than d_points holds points")
+        torch.cuda.current_stream().synchronize()
+        self._check(self._L.nrtSceneClosestPointBatchDevice_f32(self._h, d_points.data_ptr(), n, None if d_point_masks is None else d_point_masks.data_ptr(),
+                                                                d_out.data_ptr(), None if d_found is None else d_found.data_ptr()))
         return n

@@ -205,6 +205,9 @@ SIGNATURES = [
     # one descriptor for the scene queries, with per-ray skip pairs (SceneQuery above): scene, descriptor
     ("nrtSceneQueryBatch", _F32, [vp, vp], i32),
     ("nrtSceneQueryBatchDevice", _F32, [vp, vp], i32),
+    # closest-point queries on scenes: scene, points, num_points, point_masks, closest_out, found_out
+    ("nrtSceneClosestPointBatch", _F32, [vp, vp, u64, vp, vp, vp], i32),
+    ("nrtSceneClosestPointBatchDevice", _F32, [vp, vp, u64, vp, vp, vp], i32),
 ]
 # Declared by the header, bound elsewhere: nanort_amd/dist.py sets the signatures of the nrtGroup* calls when a Group is made.
 BOUND_ELSEWHERE = [

@@ -51,6 +51,29 @@ hipError_t launch_scene_list(SceneListForm form, const TreeViewF32 &top, const n
                              uint32_t cap, float *list_t, uint32_t *list_node, uint32_t *count, const uint32_t *subset, const uint32_t *inst_masks,
                              const uint32_t *ray_masks, hipStream_t s);
 
+// ---- scene_closest.hip: the closest-point query on a scene (k_scene_closest_point; include/nanort_closest.h states its rule) -----
+constexpr uint32_t kSceneClosestChunk = 64; // points a wave claims per atomic
+struct SceneClosestArgs {
+  const nrt_point_f32 *points;
+  uint32_t n;
+  uint32_t num_insts;
+  const SceneInst *insts;       // by id: world box, xform, the reference-format nodes and the LeafTri<float> records of the instance's tree
+  const nrt_node_f32 *top_nodes; // the top-level tree over the instances' world boxes (reference format), or null: every instance is scanned
+  const uint32_t *top_indices;  // ... and its index array: slot -> instance id
+  const uint32_t *node_masks;   // one word per instance by id, or null: every instance is admitted
+  const uint32_t *point_masks;  // one word per point, or null: every point carries 0xFFFFFFFF
+  nrt_scene_closest_f32 *out;
+  uint8_t *found;               // may be null
+  uint32_t *spill;              // overflow stack [levels][spill_stride], null when no lane's stack can pass the LDS entries
+  uint32_t spill_stride;        // == total threads of the launch
+  uint32_t *cursor;             // one chunk counter per point partition, kCursorStrideWords apart, zero at launch
+  uint32_t num_parts;           // point partitions (<= kMaxParts): whole chunks each
+  uint32_t refill_min, trav_min; // as TraverseArgs'
+  unsigned long long *counters; // profiling build only: [0] nodes opened (both levels), [1] instances entered, [2] triangles tested; or null
+};
+hipError_t launch_scene_closest_point(const SceneClosestArgs &args, unsigned grid, hipStream_t s);
+int scene_closest_point_blocks_per_cu();
+
 // ---- own_walks.hip: the triangle queries with a binary walk of their own (multi-hit, motion, masks, the three per-ray inputs combined) ----
 // One id per kernel; which of them a launch runs: api_query.hip, TraverseLaunch::own_walk_id.
 enum OwnWalk : int {

@@ -177,6 +177,8 @@ struct nrt_scene {
   unsigned fuse_scan = 1; // scenes of at most kScanMaxNodes nodes: k_scene_trace lists a ray's instances itself (one launch); 0: k_scene_list in a launch of its own (the A/B)
   unsigned trav_min = 8;
   unsigned cand_min = 1, cand_busy_max = 64; // batching of the per-instance steps of k_scene_trace (env NRT_SCENE_CAND / NRT_SCENE_CAND_BUSY; 1 / 64: none)
+  unsigned closest_blocks_per_cu = 0; // persistent grid of k_scene_closest_point (scene_closest below)
+  unsigned closest_refill_min = 44, closest_trav_min = 16; // ... and its phase thresholds: the single-mesh closest-point walk's (ctx.h), not measured apart
   unsigned trace_blocks_per_cu = 0, num_cus = 0, refill_min = 56; // persistent grid of k_scene_trace (env NRT_SCENE_REFILL; 16-48 measured slower on small scenes, 64 slower on 10 000 instances)
 };
 
@@ -448,6 +450,23 @@ nrt_status nrtSceneNodeState_f32(nrt_scene *s, uint32_t node_id, float out[64]) 
 
 } // extern "C"
 
+// The node words on the device, enqueued on the scene's stream before a query that reads them: both copies from the host's when they
+// changed since the last such query (or the top-level tree's order did).
+static nrt_status upload_node_masks(nrt_scene *s) {
+  if (!s->masks_dirty) return NRT_OK;
+  const size_t bytes = s->node_masks.size() * sizeof(uint32_t);
+  SCHK(s, nrt::devbuf_ensure(&s->d_node_masks, bytes));
+  SCHK(s, hipMemcpyAsync(s->d_node_masks.p, s->node_masks.data(), bytes, hipMemcpyHostToDevice, s->stream));
+  if (s->top_order.size() == s->node_masks.size()) {
+    s->top_masks_h.resize(s->top_order.size());
+    for (size_t q = 0; q < s->top_order.size(); q++) s->top_masks_h[q] = s->node_masks[s->top_order[q]];
+    SCHK(s, nrt::devbuf_ensure(&s->d_top_masks, bytes));
+    SCHK(s, hipMemcpyAsync(s->d_top_masks.p, s->top_masks_h.data(), bytes, hipMemcpyHostToDevice, s->stream));
+  }
+  s->masks_dirty = false;
+  return NRT_OK;
+}
+
 // The listing path: one of the listing kernels + k_scene_trace, enqueued on the scene's stream, over the whole batch
 // (`subset` == nullptr) or over the rays named by `subset` (the ones the single-pass walk left over).  `any_hit`: the occlusion
 // instantiation of k_scene_trace — the same lists, flags only, d_hits unused.
@@ -607,18 +626,8 @@ static nrt_status scene_traverse(nrt_scene *s, const nrt_ray_f32 *rays, uint64_t
     d_skip_stride = 8u;
   }
   if (masked) {
-    if (s->masks_dirty) { // changed since the last masked query (or the tree's order did): both device copies from the host's
-      const size_t bytes = s->node_masks.size() * sizeof(uint32_t);
-      SCHK(s, nrt::devbuf_ensure(&s->d_node_masks, bytes));
-      SCHK(s, hipMemcpyAsync(s->d_node_masks.p, s->node_masks.data(), bytes, hipMemcpyHostToDevice, s->stream));
-      if (s->top_order.size() == s->node_masks.size()) {
-        s->top_masks_h.resize(s->top_order.size());
-        for (size_t q = 0; q < s->top_order.size(); q++) s->top_masks_h[q] = s->node_masks[s->top_order[q]];
-        SCHK(s, nrt::devbuf_ensure(&s->d_top_masks, bytes));
-        SCHK(s, hipMemcpyAsync(s->d_top_masks.p, s->top_masks_h.data(), bytes, hipMemcpyHostToDevice, s->stream));
-      }
-      s->masks_dirty = false;
-    }
+    const nrt_status st = upload_node_masks(s);
+    if (st != NRT_OK) return st;
   }
 
   s->last_redone = 0;
@@ -712,7 +721,117 @@ static nrt_status scene_occluded(nrt_scene *s, const nrt_ray_f32 *rays, uint64_t
   return scene_traverse(s, rays, n64, nullptr, mask_out, device, true);
 }
 
+// ---- the closest-point query (include/nanort_hip.h, "closest-point queries on scenes"; the kernel: scene_closest.hip) --------------
+const uint64_t kSceneClosestPiece = 1ull << 20; // points per launch of the staged host form (16 MB and 4 MB of words up, 33 MB down)
+
+// One launch of k_scene_closest_point over `n` points in device memory, enqueued on the scene's stream; the caller synchronises.
+static nrt_status scene_closest_launch(nrt_scene *s, const nrt_point_f32 *d_points, uint32_t n, const uint32_t *d_point_masks,
+                                       nrt_scene_closest_f32 *d_out, uint8_t *d_found) {
+  if (s->num_cus == 0) {
+    int cus = 0;
+    SCHK(s, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, s->device));
+    s->num_cus = (unsigned)std::max(1, cus);
+  }
+  if (s->closest_blocks_per_cu == 0) s->closest_blocks_per_cu = (unsigned)nrt::scene_closest_point_blocks_per_cu();
+  const unsigned grid = std::max(1u, std::min((n + 255u) / 256u, s->num_cus * s->closest_blocks_per_cu));
+  // a lane's stack: the top level's entries — one pending sibling per level of the top-level tree and the instances of one of its
+  // leaves, or every instance of a scanned scene — below the open instance's, one pending sibling per level of its tree
+  const uint32_t top_entries = s->have_top ? s->top_view.tree_depth + 2u + s->top_view.max_leaf_count : (uint32_t)s->insts.size();
+  const uint32_t need = top_entries + s->max_inst_depth + 2u;
+  const uint32_t levels = need > (uint32_t)nrt::kLdsStackDefault ? need - nrt::kLdsStackDefault : 0;
+  if (levels) SCHK(s, nrt::devbuf_ensure(&s->d_spill, (size_t)levels * grid * 256u * sizeof(uint32_t)));
+  SCHK(s, nrt::devbuf_ensure(&s->d_cursor, (size_t)nrt::kMaxParts * nrt::kCursorStrideWords * sizeof(uint32_t)));
+  SCHK(s, hipMemsetAsync(s->d_cursor.p, 0, (size_t)nrt::kMaxParts * nrt::kCursorStrideWords * sizeof(uint32_t), s->stream));
+  nrt::SceneClosestArgs a;
+  a.points = d_points;
+  a.n = n;
+  a.num_insts = (uint32_t)s->insts.size();
+  a.insts = (const nrt::SceneInst *)s->d_insts.p;
+  a.top_nodes = s->have_top ? s->top_view.nodes : nullptr; // (no top-level build that Commit did not make: such scenes are scanned)
+  a.top_indices = s->have_top ? s->top_view.indices : nullptr;
+  a.node_masks = d_point_masks ? (const uint32_t *)s->d_node_masks.p : nullptr;
+  a.point_masks = d_point_masks;
+  a.out = d_out;
+  a.found = d_found;
+  a.spill = levels ? (uint32_t *)s->d_spill.p : nullptr;
+  a.spill_stride = grid * 256u;
+  a.cursor = (uint32_t *)s->d_cursor.p;
+  a.num_parts = std::max(1u, std::min(8u, grid));
+  a.refill_min = s->closest_refill_min;
+  a.trav_min = s->closest_trav_min;
+  a.counters = nullptr;
+#ifdef NRT_PROF
+  SCHK(s, nrt::devbuf_ensure(&s->d_counters, 16 * sizeof(unsigned long long))); // (nodes opened, instances entered, triangles tested: nrtSceneDebugCounters [0..2])
+  SCHK(s, hipMemsetAsync(s->d_counters.p, 0, 16 * sizeof(unsigned long long), s->stream));
+  a.counters = (unsigned long long *)s->d_counters.p;
+#endif
+  SCHK(s, nrt::launch_scene_closest_point(a, grid, s->stream));
+  return NRT_OK;
+}
+
+// `device`: points / point_masks / closest_out / found_out are device pointers, whose alignment the kernel's loads and stores rely
+// on; else the caller's host arrays, staged in pieces of kSceneClosestPiece points through the scene's grow-only buffers — the piece
+// and its words up, the launch, its records and bytes back.  Either way the call returns with everything finished.
+static nrt_status scene_closest(nrt_scene *s, const nrt_point_f32 *points, uint64_t n64, const uint32_t *point_masks, nrt_scene_closest_f32 *out,
+                                uint8_t *found, bool device) {
+  const char *what = device ? "nrtSceneClosestPointBatchDevice" : "nrtSceneClosestPointBatch";
+  if (!s) return sfail(nullptr, NRT_ERR_INVALID, "%s: scene == NULL", what);
+  if (!s->committed) return sfail(s, NRT_ERR_INVALID, "%s: commit the scene first", what);
+  if (n64 == 0) return NRT_OK;
+  if (!points || !out) return sfail(s, NRT_ERR_INVALID, "%s: NULL points/closest_out", what);
+  if (n64 > 0x7FFFFFFFull) return sfail(s, NRT_ERR_INVALID, "%s: more than 2^31-1 points in one call", what);
+  if (device && (((uintptr_t)points & 15u) != 0 || ((uintptr_t)out & 15u) != 0))
+    return sfail(s, NRT_ERR_INVALID, "%s: the device arrays are not aligned to 16 bytes", what);
+  if (device && ((uintptr_t)point_masks & 3u) != 0) return sfail(s, NRT_ERR_INVALID, "%s: d_point_masks is not 4-byte aligned", what);
+  // (the instance table holds the mesh contexts' device addresses and stack depths as they were at Commit: scene_traverse)
+  for (size_t m = 0; m < s->mesh_gens.size(); m++)
+    if (nrt_internal_generation(s->mesh_gens[m].first) != s->mesh_gens[m].second)
+      return sfail(s, NRT_ERR_INVALID, "%s: a mesh context was rebuilt, re-set or refitted since nrtSceneCommit (commit the scene again)", what);
+  SCHK(s, hipSetDevice(s->device));
+  if (point_masks) {
+    const nrt_status st = upload_node_masks(s);
+    if (st != NRT_OK) return st;
+  }
+  s->last_redone = 0;
+  s->last_path = 2;
+  if (device) {
+    const nrt_status st = scene_closest_launch(s, points, (uint32_t)n64, point_masks, out, found);
+    if (st != NRT_OK) return st;
+    SCHK(s, hipStreamSynchronize(s->stream));
+    return NRT_OK;
+  }
+  for (uint64_t off = 0; off < n64; off += kSceneClosestPiece) {
+    const uint32_t m = (uint32_t)std::min(kSceneClosestPiece, n64 - off);
+    SCHK(s, nrt::devbuf_ensure(&s->d_rays, (size_t)m * sizeof(nrt_point_f32)));
+    SCHK(s, nrt::devbuf_ensure(&s->d_best, (size_t)m * sizeof(nrt_scene_closest_f32)));
+    SCHK(s, nrt::devbuf_ensure(&s->d_mask, (size_t)m));
+    if (point_masks) SCHK(s, nrt::devbuf_ensure(&s->d_ray_masks, (size_t)m * sizeof(uint32_t)));
+    SCHK(s, hipMemcpyAsync(s->d_rays.p, points + off, (size_t)m * sizeof(nrt_point_f32), hipMemcpyHostToDevice, s->stream));
+    if (point_masks) SCHK(s, hipMemcpyAsync(s->d_ray_masks.p, point_masks + off, (size_t)m * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
+    const nrt_status st = scene_closest_launch(s, (const nrt_point_f32 *)s->d_rays.p, m, point_masks ? (const uint32_t *)s->d_ray_masks.p : nullptr,
+                                               (nrt_scene_closest_f32 *)s->d_best.p, (uint8_t *)s->d_mask.p);
+    if (st != NRT_OK) {
+      (void)hipStreamSynchronize(s->stream);
+      return st;
+    }
+    SCHK(s, hipMemcpyAsync(out + off, s->d_best.p, (size_t)m * sizeof(nrt_scene_closest_f32), hipMemcpyDeviceToHost, s->stream));
+    if (found) SCHK(s, hipMemcpyAsync(found + off, s->d_mask.p, (size_t)m, hipMemcpyDeviceToHost, s->stream));
+    SCHK(s, hipStreamSynchronize(s->stream));
+  }
+  return NRT_OK;
+}
+
 extern "C" {
+
+nrt_status nrtSceneClosestPointBatch_f32(nrt_scene *s, const nrt_point_f32 *points, uint64_t n, const uint32_t *point_masks, nrt_scene_closest_f32 *out,
+                                         uint8_t *found) {
+  return scene_closest(s, points, n, point_masks, out, found, false);
+}
+
+nrt_status nrtSceneClosestPointBatchDevice_f32(nrt_scene *s, const nrt_point_f32 *d_points, uint64_t n, const uint32_t *d_point_masks,
+                                               nrt_scene_closest_f32 *d_out, uint8_t *d_found) {
+  return scene_closest(s, d_points, n, d_point_masks, d_out, d_found, true);
+}
 
 nrt_status nrtSceneOccludedBatch_f32(nrt_scene *s, const nrt_ray_f32 *rays, uint64_t n, uint8_t *mask_out) {
   return scene_occluded(s, rays, n, mask_out, false);

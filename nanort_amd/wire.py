@@ -102,6 +102,9 @@ SIGNED_F64 = np.dtype([("point", "<f8", 3), ("dist2", "<f8"), ("u", "<f8"), ("v"
 FEATURE_MASK = 7
 SIGNED_INSIDE = 0x80000000
 assert SIGNED_F32.itemsize == 32 and SIGNED_F64.itemsize == 56
+# the answer of the closest-point queries on scenes (nrt_scene_closest_f32): a closest-point record with `node_id` in the place of `_pad`
+SCENE_CLOSEST_F32 = np.dtype([("point", "<f4", 3), ("dist2", "<f4"), ("u", "<f4"), ("v", "<f4"), ("prim_id", "<u4"), ("node_id", "<u4")])
+assert SCENE_CLOSEST_F32.itemsize == 32
 assert POINT_F32.itemsize == 16 and POINT_F64.itemsize == 32
 assert CLOSEST_F32.itemsize == 32 and CLOSEST_F64.itemsize == 56
 
